@@ -117,6 +117,41 @@ def cpu_baseline(cfg, B, L, budget_s=20.0):
                       f"{sec * 1e3:.0f} ms/step, torch threads={threads}, os.cpu_count()={os.cpu_count()}"}
 
 
+DUMP_SAMPLE = 1 << 20      # flat-buffer elements per sampled array of --dump-outputs (4 arrays x 4 MiB + an 8 MiB index)
+
+
+def dump_step_outputs(out_dir, model, opt, reducer, plan, world, fused):
+    """--dump-outputs: what the timed step's last replay left for its caller, as float32 / float64 .npy files - the loss, the
+    logits, and a fixed seeded sample (`param_index`, the same for every run of a workload) of the fp32 parameters, the gradient
+    buffer the optimizer read (summed over valid utterances, bf16 when the step rounded it; not written by the fused step, whose
+    weight-gradient launch keeps dW in registers) and the two Adam moments.  Reads only: nothing the timed path uses is moved."""
+    import numpy as np
+    eng = model.engine()
+    n = eng.flat.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    idx_dev = torch.from_numpy(idx).to(eng.flat.device)
+    if fused:
+        grads = None
+    elif world > 1 and reducer.exchange == "bf16":
+        grads = reducer.buf16
+    else:
+        grads = eng.grad_bf16_buf if eng.grad_bf16_buf is not None else eng.flat_grad
+    arrays = {"loss": reducer.global_loss().reshape(1), "logits": plan.logits, "param_index": torch.from_numpy(idx.astype(np.float64)),
+              "params": eng.flat[idx_dev], "exp_avg": opt._m[idx_dev], "exp_avg_sq": opt._v[idx_dev]}
+    if grads is not None:
+        arrays["grads"] = grads[idx_dev]
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "params_total": n}
+
 
 def source_hash():
     """sha256 over the kernel sources and headers: committed profile digests carry the hash they were measured on."""
@@ -151,7 +186,7 @@ PARTS = ["encoders", "fusion", "classifier"]
 
 
 def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragged, buckets, exchange, roofline=True, dump="", packed=False,
-                 repeats=1, overlap=False, algorithm="all_reduce", fused_adam=False, grad_bf16=True, fp32_grad_leg=True):
+                 repeats=1, overlap=False, algorithm="all_reduce", fused_adam=False, grad_bf16=True, fp32_grad_leg=True, dump_outputs=""):
     cfg, B, L = wl["cfg"], wl["B"], wl["L"]
     torch.manual_seed(0)                               # identical replicas on every rank
     model = M2FNet(cfg, precision=dtype, shape_buckets=False).to(device).train()      # the plan IS the workload's (B, L): no bucket padding
@@ -220,6 +255,8 @@ def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragge
         elapsed = dp.reduce_metrics([elapsed], device=device)[0]
         loss = float(stepper.reducer.global_loss().item())
         plan.check_status()
+        # what the timed path's last step computed, before anything below runs the model again
+        dumped = dump_step_outputs(dump_outputs, model, opt, stepper.reducer, plan, world, fused_steps[0] > 0) if dump_outputs else None
         # the same bracket four more times (spread of the measurement; `value` stays the FIRST bracket = exactly `steps` steps)
         rep_ms = [elapsed / steps * 1e3]
         for _ in range(repeats - 1):
@@ -370,6 +407,8 @@ def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragge
     }
     if comm is not None:
         out["comm"] = comm
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if roofline:
         out["roofline"] = {
             "bound": "mfma", "kernel": "bf16: m2f_gemm16_ring_kernel (forward / input-gradient launches as 256x128, 128x128, 128x64 or 64x64 ring tiles) + m2f_gemm_p8_kernel (the weight-gradient table launch, 256x256 tiles on the eight-phase schedule); fp32: m2f_gemm_kernel - the grouped MFMA GEMM launches of one step",
@@ -415,6 +454,10 @@ def main():
     ap.add_argument("--grad-exchange", default="auto", choices=["auto", "fp32", "bf16"],
                     help="dtype of the gradient all-reduce at N > 1 (auto: bf16 for --dtype bf16, fp32 for --dtype fp32)")
     ap.add_argument("--dump-launches", default="", help="write the per-launch timing table (kind, us, GFLOP) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (loss, logits, and a fixed seeded "
+                         "sample of parameters, gradients and Adam moments; float32 / float64, at most 24 MiB): two builds run with the same "
+                         "arguments can then be compared output for output")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="form the process group (gloo when there is no GPU), check its size against --gpus, print it, exit: "
                          "the launch path without the measurement (tests/test_dp_cpu.py)")
@@ -442,6 +485,8 @@ def main():
     ap.add_argument("--secondary", default="c2", choices=sorted(WORKLOADS) + ["none"],
                     help="second single-GPU configuration reported under `secondary` (N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher environment: start the ranks ourselves - fresh child processes, before this process touches the GPU
@@ -476,7 +521,8 @@ def main():
     exchange = args.grad_exchange if args.grad_exchange != "auto" else ("bf16" if args.dtype == "bf16" else "fp32")
     res = run_workload(wl, args.dtype, rank, world, device, args.steps, args.warmup, use_graph, args.ragged, args.buckets, exchange,
                        roofline=True, dump=args.dump_launches if rank == 0 else "", packed=args.packed, repeats=max(1, args.repeats),
-                       overlap=args.dp_overlap and not args.no_overlap, algorithm=args.dp_algorithm, fused_adam=args.fused_adam, grad_bf16=not args.grad_fp32, fp32_grad_leg=not args.no_fp32_grad_leg)
+                       overlap=args.dp_overlap and not args.no_overlap, algorithm=args.dp_algorithm, fused_adam=args.fused_adam, grad_bf16=not args.grad_fp32, fp32_grad_leg=not args.no_fp32_grad_leg,
+                       dump_outputs=args.dump_outputs if rank == 0 else "")
     if rank == 0:
         out = res
         if world == 1 and args.dtype == "bf16" and not args.no_parity_leg and not args.ragged and not args.packed:

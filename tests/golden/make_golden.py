@@ -290,6 +290,26 @@ def init_fixture(out_dir):
     print("init fixture:", len(rec["names"]), "tensors")
 
 
+def default_init_logits_fixture(out_dir):
+    """The reference's OWN default init (manual_seed(5), not the synthetic weights) of tiny_odd_heads and its eval logits on
+    the synthetic inputs.  The weights themselves are not stored (random, 3 MB): per-tensor digests pin them, and
+    tests/test_oracle.py regenerates them with the mirror's default init under the same seed, checks the digests and feeds
+    them to the oracle."""
+    cfg, B, L, lengths, kind = synth.CASES["tiny_odd_heads"]
+    torch.manual_seed(5)
+    m = ref_model.M2FNet(ns(cfg)).eval()
+    text, audio, key_pad, _ = synth.make_inputs(cfg, B, L, lengths, kind)
+    with torch.inference_mode():
+        logits = m(text, audio, key_pad)
+    sd = m.state_dict()
+    vals = [v.double() for v in sd.values()]
+    rec = {"names": np.array(list(sd.keys())), "logits_eval": logits.numpy(),
+           "sums": np.array([float(v.sum()) for v in vals]), "abs_sums": np.array([float(v.abs().sum()) for v in vals]),
+           "dots": np.array([float((v * synth.digest_vector(tuple(v.shape), 9, i).double()).sum()) for i, v in enumerate(vals)])}
+    np.savez_compressed(os.path.join(out_dir, "default_init_odd_heads.npz"), **rec)
+    print("default-init fixture:", len(sd), "tensors")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     tabs = real_tables()
@@ -302,3 +322,5 @@ if __name__ == "__main__":
     if not only:
         metric_fixture(HERE)
         init_fixture(HERE)
+    if not only or "default_init_odd_heads" in only:
+        default_init_logits_fixture(HERE)

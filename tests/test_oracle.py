@@ -189,24 +189,23 @@ def test_pad_contents_do_not_change_valid_logits(golden_dir):
     assert (a - b)[~key_pad].abs().max() == 0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/model.py"), reason="reference only in the build container")
-def test_oracle_vs_live_reference_default_init():
-    """Live check on the reference's OWN default init (not the synthetic weights)."""
-    import sys
-    import types
-    import warnings
-    sys.path.insert(0, "/root/reference/src")
-    sys.dont_write_bytecode = True
-    warnings.filterwarnings("ignore")
-    import model as ref_model
+def test_oracle_vs_reference_default_init(golden_dir):
+    """The reference's OWN default init (not the synthetic weights) and its eval logits, as recorded by
+    tests/golden/make_golden.py (default_init_odd_heads.npz): the weights are regenerated by the mirror's default init under
+    the reference's seed and must match the reference's per-tensor digests before the oracle runs on them."""
+    from mer_amd.model import M2FNet
+    fx = _load(golden_dir, "default_init_odd_heads")
     cfg, B, L, lengths, kind = synth.CASES["tiny_odd_heads"]
-
-    def ns(d):
-        return types.SimpleNamespace(**{k: (ns(v) if isinstance(v, dict) else v) for k, v in d.items()})
     torch.manual_seed(5)
-    m = ref_model.M2FNet(ns(cfg)).eval()
+    sd = M2FNet(cfg).state_dict()
+    assert list(sd.keys()) == [str(n) for n in fx["names"]]
+    vals = [v.double() for v in sd.values()]
+    sums = np.array([float(v.sum()) for v in vals])
+    abss = np.array([float(v.abs().sum()) for v in vals])
+    dots = np.array([float((v * synth.digest_vector(tuple(v.shape), 9, i).double()).sum()) for i, v in enumerate(vals)])
+    assert np.allclose(sums, fx["sums"], rtol=0, atol=1e-6) and np.allclose(abss, fx["abs_sums"], rtol=1e-9)
+    assert np.allclose(dots, fx["dots"], rtol=0, atol=1e-6)
     text, audio, key_pad, _ = synth.make_inputs(cfg, B, L, lengths, kind)
-    with torch.inference_mode():
-        ref = m(text, audio, key_pad)
-    mine = O.forward(dict(m.state_dict()), cfg, text, audio, key_pad)
+    ref = torch.from_numpy(fx["logits_eval"])
+    mine = O.forward(sd, cfg, text, audio, key_pad)
     assert (mine - ref)[~key_pad].abs().max() < TOL_LOGITS
