@@ -78,7 +78,10 @@ m2f_plan* m2f_plan_create(const m2f_config* cfg, int B, int L, int precision, in
  * cu[b] .. cu[b+1]-1 of M2F_BUF_CU_SEQLENS (int32 [B+1], cu[0] = 0, cu[B] <= T, written by the caller before each step; rows from
  * cu[B] on are padding: label -1, finite inputs).  No pad slots inside dialogues, so a ragged batch (reference collate_fn,
  * src/dataset.py:69-89, pads every dialogue to the longest) costs its valid utterances only.  M2F_BUF_KEYPAD is not read.
- * Same arithmetic per valid utterance as the padded plan of the same dialogues; B <= T <= B * L. */
+ * Same arithmetic per valid utterance as the padded plan of the same dialogues; B <= T <= B * L.
+ * L (the longest dialogue the plan holds) may be 1 .. 512 here, against 1 .. 64 for the padded plans: above 64 the dialogue
+ * attention runs on the long-dialogue kernels (m2f_attention_varlen_*), and B * H * L * L must stay below 2^32 for every
+ * attention site's head count H (the dropout keep index is 32-bit). */
 int64_t m2f_workspace_bytes_packed(const m2f_config* cfg, int B, int L, int T, int train);
 m2f_plan* m2f_plan_create_packed(const m2f_config* cfg, int B, int L, int T, int precision, int train,
                                  float* params, float* grads, void* workspace, int64_t workspace_bytes,
@@ -90,7 +93,8 @@ m2f_plan* m2f_plan_create_packed(const m2f_config* cfg, int B, int L, int T, int
  * through m2f_adam_step_shadowed writes the shadows of the parameters it has just updated.  The caller then declares them
  * current with m2f_plan_params_fresh(plan, 1) and the forward skips its parameter casts (2 x 87 us of 2.7 ms at C3); after
  * any OTHER write to the parameters (load_state_dict, a foreign optimizer) it must pass 0 again - a forward that ran the casts
- * leaves the shadows current, too.  T = 0: padded plan, T > 0: packed plan of T token rows (as m2f_plan_create_packed).
+ * leaves the shadows current, too.  T = 0: padded plan (L <= 64), T > 0: packed plan of T token rows (as m2f_plan_create_packed,
+ * L <= 512).
  * No counterpart in the reference: torch keeps no low-precision parameter copies (src/train.py:56,231 is all it does). */
 int64_t m2f_param_shadow_elems(const m2f_config* cfg);
 int m2f_param_shadow_init(const m2f_config* cfg, uint16_t* param_shadow, m2f_stream_t stream);
@@ -325,6 +329,22 @@ int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, cons
                       int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream);
 int64_t m2f_attention_probs_elems(int B, int H, int L);
+/* The same attention for dialogues of up to 512 utterances (the kernels packed plans with L > 64 run): one workgroup per 64-row
+ * block of a (dialogue, head), keys streamed in 64-row blocks.  Rows are given in one of two forms:
+ *   packed: cu (int32 [B+1], device) - dialogue b owns rows cu[b] .. cu[b+1]-1 (at most L of them), T rows in all; rows cu[B] ..
+ *           T-1 of out (dq / dk / dv) are written as zeros; key_pad = NULL;
+ *   padded: key_pad (uint8 [B*L], 1 = padded key, masked with -inf before the softmax) - dialogue b owns rows b*L .. b*L+L-1; cu = NULL.
+ * probs receives P^T (pre-dropout) in the layout of m2f_attention_fwd, [B*H, Lp, Lp] (m2f_attention_probs_elems); the backward
+ * reads it back (no recompute) and replays dropout from the same keep index.  1 <= L <= 512, hd <= 256, B * H * L * L < 2^32.
+ * Deterministic: every result element is written by one workgroup, no atomics. */
+int m2f_attention_varlen_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                             const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
+                             float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream);
+int m2f_attention_varlen_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                             const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo,
+                             const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk,
+                             float* dv, int lddv, uint32_t drop_site, float drop_p, const uint32_t* rng_state,
+                             m2f_stream_t stream);
 /* out = (res ? res : 0) + LayerNorm(x) (nn.LayerNorm, eps), stats[T,2] = (mean, rstd). */
 int m2f_layernorm_fwd(int T, int d, const float* x, const float* gamma, const float* beta, const float* res,
                       float* out, float* stats, float eps, m2f_stream_t stream);

@@ -13,7 +13,10 @@ import sys
 # (ring_wait_vm): scratch loads / stores are vector-memory operations on the same counter, so ANY scratch use (spills) in
 # such a kernel makes the counts wrong - the build must not produce one.
 ring = len(sys.argv) > 2 and sys.argv[1] == "--ring"
-path = sys.argv[2] if ring else sys.argv[1]
+# --dlong <remarks>: the long-dialogue attention kernels (attention_dlong.hip) keep their output accumulators in registers through
+# fully unrolled loops with static indices; an unroll that fails turns them into scratch arrays - refuse the build instead.
+dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
+path = sys.argv[2] if (ring or dlong) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -27,6 +30,14 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
+if dlong:
+    kernels = [r for r in rows if "m2f_attn_dlong" in r["name"]]
+    if not kernels:
+        sys.exit(f"check_spills: no long-dialogue attention kernel found in {path} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0]
+    for r in bad:
+        print(f"check_spills: {r['name']} uses {r['scratch']} bytes of scratch per lane", file=sys.stderr)
+    sys.exit(1 if bad else 0)
 if ring:
     kernels = [r for r in rows if "m2f_gemm16_ring_kernel" in r["name"] or "m2f_gemm_p8_kernel" in r["name"]]
     if not kernels:

@@ -205,6 +205,14 @@ hipError_t m2f_launch_attn_long_fwd(const float* q, int ldq, const float* k, int
                                     hipStream_t stream);
 hipError_t m2f_launch_attn_bwd(AttnBatch& ab, hipStream_t stream);
 size_t m2f_attn_probs_elems(int B, int H, int L);
+// Long-dialogue forms (attention_dlong.hip): the same AttnBatch contract - packed (cu) or padded (key_pad) - for 1 <= L <= 512,
+// one workgroup per 64-row block of a (dialogue, head).  Forward writes P^T to pr[i].probs as above; the backward runs two
+// kernels (dK / dV per key block, dQ per query block).  The plans launch them for L > 64; B * H * L * L must stay below 2^32
+// (the dropout keep index is 32-bit).
+#define M2F_ATTN_DLONG_MAX_L 512
+bool m2f_attn_dlong_index_ok(int B, int H, int L);
+hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream);
+hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // Row-wise kernels

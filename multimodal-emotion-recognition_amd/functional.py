@@ -132,6 +132,49 @@ def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, dr
     return dq, dk, dv
 
 
+def _varlen_rows(cu: Optional[torch.Tensor], key_pad: Optional[torch.Tensor]):
+    if (cu is None) == (key_pad is None):
+        raise ValueError("give exactly one of cu (packed rows) and key_pad (padded rows)")
+    cu32 = cu.to(torch.int32).contiguous() if cu is not None else None
+    kp = key_pad.reshape(-1).to(torch.uint8).contiguous() if key_pad is not None else None
+    return cu32, kp
+
+
+def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, L: int, H: int,
+                         cu: Optional[torch.Tensor] = None, key_pad: Optional[torch.Tensor] = None, drop_site: int = 0,
+                         drop_p: float = 0.0, rng: Optional[torch.Tensor] = None):
+    """Long-dialogue attention (m2f_attention_varlen_fwd, L <= 512).  q/k/v: [T, H*hd] (possibly column slices) with either
+    cu (int [B+1]: dialogue b = rows cu[b] .. cu[b+1]-1, T = q.shape[0]) or key_pad ([B, L] or [B*L], True = padded key;
+    T = B*L).  Returns (out [T, H*hd], probs^T [B*H, Lp, Lp])."""
+    runtime.require_gpu()
+    T, E = q.shape
+    hd = E // H
+    cu32, kp = _varlen_rows(cu, key_pad)
+    out = torch.empty(T, E, dtype=torch.float32, device=q.device)
+    Lp = 16 * ((L + 15) // 16)
+    probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                         ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()),
+          "m2f_attention_varlen_fwd")
+    return out, probs
+
+
+def attention_varlen_bwd(q, k, v, out, probs, dout, B: int, L: int, H: int, cu: Optional[torch.Tensor] = None,
+                         key_pad: Optional[torch.Tensor] = None, drop_site: int = 0, drop_p: float = 0.0,
+                         rng: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of `attention_varlen_fwd` from its saved probabilities: (dq, dk, dv), each [T, H*hd]."""
+    runtime.require_gpu()
+    T, E = q.shape
+    hd = E // H
+    cu32, kp = _varlen_rows(cu, key_pad)
+    dq, dk, dv = (torch.zeros(T, E, dtype=torch.float32, device=q.device) for _ in range(3))
+    check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                         ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
+                                         _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()),
+          "m2f_attention_varlen_bwd")
+    return dq, dk, dv
+
+
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, res: Optional[torch.Tensor] = None,
                   eps: float = 1e-5):
     runtime.require_gpu()
@@ -178,7 +221,10 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     q = gemm(t, in_w[:E], NT, precision, bias=in_b[:E])
     k = gemm(a, in_w[E:2 * E], NT, precision, bias=in_b[E:2 * E])
     v = gemm(t, in_w[2 * E:], NT, precision, bias=in_b[2 * E:])
-    att, _ = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head)
+    if L > 64:          # (the dialogue kernels of attention_fwd hold L <= 64; above, the long-dialogue kernels, padded form)
+        att, _ = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad)
+    else:
+        att, _ = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head)
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
     return y.view(B, L, E)

@@ -213,25 +213,29 @@ class _Engine:
     @staticmethod
     def bucket(B: int, L: int) -> Tuple[int, int]:
         """Plan shape for a batch of B dialogues x L utterances: L rounded up to a multiple of 16 (the attention kernels'
-        tile; MELD batches have L anywhere in 1..33 -> three shapes), B to a power of two below 8 and a multiple of 8 above
-        (only the last, partial batch of an epoch differs from batch_size)."""
-        Lb = (L + 15) // 16 * 16
+        tile; MELD batches have L anywhere in 1..33 -> three shapes) - above 64, to a multiple of 64 (the long-dialogue
+        kernels' block) -, B to a power of two below 8 and a multiple of 8 above (only the last, partial batch of an epoch
+        differs from batch_size)."""
+        Lb = (L + 15) // 16 * 16 if L <= 64 else (L + 63) // 64 * 64
         Bb = 1 << max(B - 1, 0).bit_length() if B <= 8 else (B + 7) // 8 * 8
         return Bb, Lb
 
     def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None) -> runtime.Plan:
         """valid: number of valid utterances of the batch (packed mode) - the plan then holds that many token rows (rounded up to
         a multiple of 64, plus one row per filler dialogue and one spare) instead of B x L slots; batches that are at least
-        85 % full keep the padded plan."""
-        b_in = B
+        85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64)."""
+        b_in, l_in = B, L
         if self.shape_buckets:
             B, L = self.bucket(B, L)
+        long = L > 64
+        if long and valid is None:
+            valid = b_in * l_in
         T = None
         if valid is not None:
             need = int(valid) + (B - b_in) + 1
             Tb = (need + 63) // 64 * 64
-            if Tb <= 0.85 * B * L:
-                T = max(Tb, B)
+            if long or Tb <= 0.85 * B * L:
+                T = min(max(Tb, B), B * L)            # (every dialogue full: no spare row - runtime.Plan handles that)
         base = (B, L, T, want_backward, dropout_active, self.precision)
         inst, key, pl, oldest = 0, None, None, None
         while True:                                       # first instance of this shape that no live autograd graph owns
@@ -326,10 +330,11 @@ class M2FNet(nn.Module):
     """Drop-in for reference ``src/model.py:23-145``: ``M2FNet(config.model)``; ``forward(text, audio, mask)``
     with text [B,L,d_t], audio [B,L,d_a] fp32 and mask bool [B,L] (True = pad) -> logits [B,L,output_size].
 
-    Limits the reference does not have: at most 64 utterances per dialogue (L <= 64: the dialogue attention kernels keep a
-    whole dialogue in one workgroup; MELD's longest dialogue has 33) - longer inputs raise from ``m2f_plan_create``; each
-    backward OVERWRITES the gradients (the reference zeroes them every step, ``src/train.py:227``), so accumulating over
-    several backward calls needs a caller-side buffer."""
+    Limits the reference does not have: at most 512 utterances per dialogue - longer inputs raise from ``m2f_plan_create``.
+    Batches whose longest dialogue has more than 64 utterances always run on a packed plan (long-dialogue attention
+    kernels), whatever ``packed`` says: their logits at pad slots are zero, where the reference computes numbers that its
+    loss and metrics mask out (valid slots agree).  Each backward OVERWRITES the gradients (the reference zeroes them every
+    step, ``src/train.py:227``), so accumulating over several backward calls needs a caller-side buffer."""
 
     def __init__(self, config, precision: Optional[str] = None, shape_buckets: Optional[bool] = None,
                  packed: Optional[bool] = None):
@@ -400,7 +405,7 @@ class M2FNet(nn.Module):
         eng = self.engine(mask.device)
         B, L = mask.shape
         want_bwd = torch.is_grad_enabled() and any(p.requires_grad for p, *_ in eng.items)
-        valid = int((~mask.bool()).sum()) if self.packed else None
+        valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, want_bwd, self.training and self.m2f_config.dropout > 0.0, valid)
         plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask)
         if want_bwd:
@@ -422,7 +427,7 @@ class M2FNet(nn.Module):
         otherwise the optimizer's own kernel runs behind the step."""
         eng = self.engine(mask.device)
         B, L = mask.shape
-        valid = int((~mask.bool()).sum()) if self.packed else None
+        valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
 
         def body():

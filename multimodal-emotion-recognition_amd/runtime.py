@@ -104,6 +104,11 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                   c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_probs_elems": (c_int64, [c_int, c_int, c_int]),
+    "m2f_attention_varlen_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
+    "m2f_attention_varlen_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                         c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_set_shadow_map": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -256,6 +261,7 @@ class Plan:
         self._logits = self._view(BUF_LOGITS, (self.T, C) if self.packed else (B, L, C), torch.float32)
         self.cu_in = self._view(BUF_CU_SEQLENS, (B + 1,), torch.int32)
         self._dst = self._valid = None        # packed plans: token row of every (dialogue, slot) of the last batch; its validity
+        self._spare = None                    # packed plans of B * L rows: device flag "row T-1 is not owned by the last batch"
         if train and grads is not None:
             # (loss, den, num) live in the tail of the flat gradient buffer (see include/m2fnet_hip.h)
             assert grads.numel() >= params.numel() + 4, "gradient buffer needs a 64-float tail"
@@ -400,6 +406,8 @@ class Plan:
         if b < self.B:
             cu[b + 1:] = cu[b] + torch.arange(1, self.B - b + 1, device=dev)
         self.cu_in.copy_(cu.to(torch.int32), non_blocking=True)
+        # row T-1 is a real row only in a plan of B * L rows that the batch fills (no pad slot is then scattered there)
+        self._spare = None if T < self.B * self.L else cu[-1] < T
         dst = torch.where(valid, cu[:b, None] + rank, torch.full_like(rank, T - 1))
         self._dst, self._valid = dst, valid
         flat = dst.reshape(-1)
@@ -407,19 +415,26 @@ class Plan:
             if src is not None and on:
                 buf.zero_()
                 buf.index_copy_(0, flat, src.reshape(b * l, -1).to(buf.dtype))
-                buf[T - 1].zero_()
+                self._clear_spare(buf, 0)
         self.keypad_in.zero_()
         self.labels_in.fill_(-1)
         if labels is not None:
             self.labels_in.index_copy_(0, flat, labels.reshape(-1).to(torch.int64))
-            self.labels_in[T - 1] = -1
+            self._clear_spare(self.labels_in, -1)
+
+    def _clear_spare(self, buf: torch.Tensor, value) -> None:
+        """Row T-1 of a packed buffer := value, unless the batch owns it (see `_set_inputs_packed`)."""
+        if self._spare is None:
+            buf[self.T - 1] = value
+        else:
+            buf[self.T - 1] = torch.where(self._spare, torch.full_like(buf[self.T - 1], value), buf[self.T - 1])
 
     def set_dlogits(self, g: torch.Tensor) -> None:
         """d loss / d logits of the last batch ([b, l, C], padded surface) into the plan's buffer."""
         if self.packed:
             self._dlogits.zero_()
             self._dlogits.index_copy_(0, self._dst.reshape(-1), (g * self._valid[..., None].to(g.dtype)).reshape(-1, g.shape[-1]))
-            self._dlogits[self.T - 1].zero_()
+            self._clear_spare(self._dlogits, 0)
             return
         if self.in_B != self.B or self.in_L != self.L:
             self._dlogits.zero_()                 # filler slots of a bucketed plan carry no gradient
