@@ -12,11 +12,12 @@
 //     v_mfma_f32_32x32x2_f32 (exact fp32, 157 TF peak) or, in BF16 mode, v_mfma_f32_32x32x16_bf16 with the operands
 //     rounded to bf16 while being staged.  Register-staged operands (coalesced 16-byte loads one k-tile ahead), LDS images
 //     laid out for conflict-free fragment reads ([k][row] floats with row stride BR+1 | [row][k] bf16 with 272-byte rows).
-//   * BF16 mode proper: `m2f_gemm16_kernel` (+ `_dense_`, `_table_` variants), bf16-SOURCE: every operand also exists as a
+//   * BF16 mode proper: `m2f_gemm16_kernel` (+ `_dense_` variant), bf16-SOURCE: every operand also exists as a
 //     bf16 shadow in HBM (half the bytes through the per-CU L1 fill path that bounds these GEMMs).  Workgroups of 8 waves
 //     split into 4 producer waves (global -> register ring of D k-tiles -> LDS) and 4 consumer waves (LDS -> MFMA ->
-//     epilogue); tiles 64x64 (chain launches), 128x128 (weight gradients, persistent walk over a device-resident problem
-//     table) or 256x128 (text encoder); see the comment above gemm16_body.
+//     epilogue); tiles 64x64 (chain launches), 128x128 or 256x128 (text encoder); see the comment above gemm16_body.
+//     Chip-filling launches and the weight-gradient table launch (m2f_launch_gemm_table) run the LDS-DMA forms instead:
+//     gemm_ring.h and gemm_p8.h.
 //   * "grouped": one launch covers several independent problems (text+audio branch, q/k/v of a fusion layer, split
 //     concat) so the 256 CUs see more workgroups per launch and the launch-latency-bound chain gets shorter;
 //   * the epilogue fuses bias, ReLU / exact GELU, dropout, residual add, ReLU-gate and accumulate (32-bit offsets from
@@ -39,9 +40,6 @@
 // loads (see Stage16KC::wait_loaded): D = 3 of the 128-VGPR chain build spills and faults.
 #ifndef M2F_CHAIN_D
 #define M2F_CHAIN_D 2         // register sets in flight of the 64x64 chain build (experiment knob)
-#endif
-#ifndef M2F_T256_D
-#define M2F_T256_D 2          // register sets in flight of the 256x128 table build (experiment knob)
 #endif
 
 namespace {
@@ -612,9 +610,9 @@ struct Stage16KC {                       // element (row, k) at q[row*ld + k]
         }
     }
     // uniform 64-bit base + zero-extended 32-bit lane offset: the saddr form of global_load (no per-load 64-bit VALU add)
-    // The address-space cast matters for the table kernel: its operand pointers are read from device memory, so the compiler
-    // cannot prove them global and emits FLAT loads - which also count on lgkmcnt, share ordering with the ds_writes and
-    // turn every counted wait of the ring into vmcnt(0) lgkmcnt(0).
+    // The address-space cast matters wherever the compiler cannot prove an operand pointer global (one read from device
+    // memory): it then emits FLAT loads - which also count on lgkmcnt, share ordering with the ds_writes and turn every
+    // counted wait of the ring into vmcnt(0) lgkmcnt(0).
     __device__ __forceinline__ static m2f_u32x4 ld16(const char* base, uint32_t o) {
         return *(const __attribute__((address_space(1))) m2f_u32x4*)(base + (size_t)o);
     }
@@ -650,20 +648,6 @@ struct Stage16KC {                       // element (row, k) at q[row*ld + k]
             asm volatile("s_waitcnt vmcnt(%8)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]),
                          "+v"(v[7]) : "n"(NEWER) : "memory");
         else static_assert(NT == 1 || NT == 2 || NT == 4 || NT == 8, "chunks per thread");
-    }
-    // Branch-free variant for the table kernel (its operands never carry a ReLU flag): edge chunks are zeroed with selects,
-    // so the registers of a set are only touched in straight-line code and the ring keeps counted vmcnt waits.
-    __device__ __forceinline__ void store_select(char* lds) {
-        const int kc = tid_ % KCH;
-        const bool kok = full_ || (kbase_ + 8 * kc < kpad_);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int r = (tid_ + 256 * t) / KCH;
-            const bool ok = kok && (full_ || row0_ + r < rows_);
-            m2f_u32x4 x = v[t];
-            x.x = ok ? x.x : 0u; x.y = ok ? x.y : 0u; x.z = ok ? x.z : 0u; x.w = ok ? x.w : 0u;
-            *reinterpret_cast<m2f_u32x4*>(lds + r * ROWB + kc * 16) = x;
-        }
     }
     __device__ __forceinline__ void store(char* lds, bool relu) {
         // the rare fix-ups (edge masks, relu of the operand) sit behind ONE block-uniform branch, so the common path
@@ -785,40 +769,7 @@ __device__ unsigned long long m2f_dbg[64];
 // FP8: the operands are OCP e4m3 bytes.  The producers are unchanged - a k-tile is BK byte PAIRS per row either way (the
 // launcher passes k and ldq in byte pairs) - only the consumers differ: 2*BK/16 slices of v_mfma_f32_32x32x16_fp8_fp8 with
 // 8-byte fragments, and the epilogue de-quantises the accumulator.
-// Epilogue of the weight-gradient table kernel (plain stores: no bias / residual / gate / shadow).  The consumers multiply with
-// the operands SWAPPED, so a lane holds C[row = lane & 31][8 * g + 4 * (lane >> 5) + 0..3] of its 32x32 block: four consecutive
-// columns per register quad -> one 16-byte store instead of four 4-byte ones (16 instead of 64 store instructions per wave
-// and 64x64 quadrant).
-template <int MI, int NI, int BM, int BN>
-__device__ __forceinline__ void table_epilogue_t(const GemmProblem& P, f32x16 (&acc)[MI][NI], int m0, int n0, int lane, int wm, int wn) {
-    const int M = P.M, N = P.N, ldc = P.ldc;
-    float* __restrict__ C = P.c;
-    const bool vec = ((ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) && (m0 + BM <= M) && (n0 + BN <= N);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int row = m0 + wm * (BM / 2) + i * 32 + (lane & 31);
-            const int col0 = n0 + wn * (BN / 2) + j * 32 + 4 * (lane >> 5);
-            if (vec) {                                              // block-uniform
-                float* dst = C + (size_t)row * ldc + col0;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                    *reinterpret_cast<f32x4*>(dst + 8 * g) = v;
-                }
-            } else if (row < M) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int col = col0 + 8 * (r >> 2) + (r & 3);
-                    if (col < N) C[(size_t)row * ldc + col] = acc[i][j][r];
-                }
-            }
-        }
-    }
-}
-
-template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D, bool TABLE, bool GELU = false, bool FP8 = false>
+template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D, bool GELU = false, bool FP8 = false>
 __device__ __forceinline__ void gemm16_body(const GemmBatch& gb) {
     static_assert(!(A_RC && !B_RC), "layouts: NT, NN, TN");
     static_assert(!FP8 || (!A_RC && !B_RC), "fp8: forward form only");
@@ -834,10 +785,8 @@ __device__ __forceinline__ void gemm16_body(const GemmBatch& gb) {
     constexpr int U = (D % 2 == 0) ? D : 2 * D;                 // unroll so that set and LDS-buffer indices are static
     // NT form: the staging loads are issued from inline asm and waited for with hand-counted vmcnt (Stage16KC::wait_loaded).
     // hipcc's own waitcnt insertion answers the ring with vmcnt(0) as soon as the control flow around it is not trivial
-    // (always in the table kernel: 3 sets, 6-fold unroll), which drains all sets in flight at every k-tile.
+    // (e.g. 3 sets with a 6-fold unroll), which drains all sets in flight at every k-tile.
     constexpr bool ASM_LOADS = !A_RC && !B_RC;
-    // table kernel: transposed accumulators + 16-byte stores (table_epilogue_t); its problems carry no epilogue terms
-    constexpr bool TABLE_T = TABLE && !A_RC && !B_RC && !FP8 && !GELU;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const bool producer = threadIdx.x >= 256;                   // wave-uniform
@@ -849,27 +798,15 @@ __device__ __forceinline__ void gemm16_body(const GemmBatch& gb) {
     // PERSISTENT tile loop: a launch has at most chip-filling size; workgroup b walks tiles b, b + grid, ...  Both
     // roles see the same tile sequence and the same number of barriers per tile.  The producers of tile t+1 start as
     // soon as the last k-tile of t has been multiplied, i.e. they fetch under the consumers' epilogue of tile t.
-    const int total_tiles = TABLE ? gb.total_tiles : (int)gridDim.x;
+    const int total_tiles = (int)gridDim.x;
     M2F_TS(0);
   for (int bpos = xcd_remap((int)blockIdx.x, (int)gridDim.x); bpos < total_tiles; bpos += (int)gridDim.x) {
     int pi = 0;
-    if constexpr (TABLE) pi = gb.tile_prob[bpos];
-    else {
 #pragma unroll
-        for (int i = 1; i < M2F_GEMM_MAX_PROBLEMS; ++i)
-            if (bpos >= gb.tb[i]) pi = i;                        // unused slots hold INT_MAX
-    }
-    const GemmProblem& P = TABLE ? gb.table[pi] : gb.pr[pi];     // epilogue terms (consumers, off the critical path)
-    // descriptors the first loads depend on: from the compact header (grouped launches) or the device table
-    GemmHot Hh;
-    if constexpr (TABLE) {
-        Hh.aq[0] = P.a.q[0]; Hh.aq[1] = P.a.q[1]; Hh.bq[0] = P.b.q[0]; Hh.bq[1] = P.b.q[1];
-        Hh.M = P.M; Hh.N = P.N; Hh.k[0] = P.a.k[0]; Hh.k[1] = P.a.k[1];
-        Hh.ldaq[0] = P.a.ldq[0]; Hh.ldaq[1] = P.a.ldq[1]; Hh.ldbq[0] = P.b.ldq[0]; Hh.ldbq[1] = P.b.ldq[1];
-        Hh.flags = P.flags; Hh.tile_begin = P.tile_begin; Hh.has_bias_grad = P.bias_grad != nullptr;
-    } else {
-        Hh = gb.hot[pi];
-    }
+    for (int i = 1; i < M2F_GEMM_MAX_PROBLEMS; ++i)
+        if (bpos >= gb.tb[i]) pi = i;                            // unused slots hold INT_MAX
+    const GemmProblem& P = gb.pr[pi];                            // epilogue terms (consumers, off the critical path)
+    const GemmHot Hh = gb.hot[pi];                               // descriptors the first loads depend on: the compact header
     const int M = Hh.M, N = Hh.N;
     const int tl = bpos - Hh.tile_begin;
     const int tiles_m = (M + BM - 1) / BM;
@@ -935,11 +872,6 @@ __device__ __forceinline__ void gemm16_body(const GemmBatch& gb) {
                 constexpr int PER_SET = SAK::NT + SBK::NT;
                 st.ak.template wait_loaded<(D - 1) * PER_SET + SBK::NT>();
                 st.bk.template wait_loaded<(D - 1) * PER_SET>();
-            }
-            if constexpr (TABLE && !A_RC && !B_RC) {
-                st.ak.store_select(ldsA + buf * LDS_A);
-                st.bk.store_select(ldsB + buf * LDS_B);
-                return;
             }
             if constexpr (!A_RC) st.ak.store(ldsA + buf * LDS_A, reluA);
             if constexpr (!B_RC) st.bk.store(ldsB + buf * LDS_B, reluB);
@@ -1054,8 +986,7 @@ k_tiles_done:
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
-                    if constexpr (TABLE_T) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[ks][j], a[ks][i], acc[i][j], 0, 0, 0);
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
     };
 
     M2F_TS(1);
@@ -1081,8 +1012,7 @@ k_tiles_done:
         }
     }
     M2F_TS(3);
-    if constexpr (TABLE_T) table_epilogue_t<MI, NI, BM, BN>(P, acc, m0, n0, lane, wm, wn);
-    else gemm_epilogue<MI, NI, BM, BN, GELU, FP8, true>(gb, P, acc, m0, n0, lane, wm, wn);
+    gemm_epilogue<MI, NI, BM, BN, GELU, FP8, true>(gb, P, acc, m0, n0, lane, wm, wn);
     M2F_TS(4);
   }
 }
@@ -1092,20 +1022,11 @@ k_tiles_done:
 // workgroups per CU with a shallower ring each - the launches with more tiles than CUs.
 template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D, bool GELU = false, bool FP8 = false>
 __global__ __launch_bounds__(512) void m2f_gemm16_kernel(const GemmBatch gb) {
-    gemm16_body<A_RC, B_RC, BM, BN, BK, D, false, GELU, FP8>(gb);
+    gemm16_body<A_RC, B_RC, BM, BN, BK, D, GELU, FP8>(gb);
 }
 template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void m2f_gemm16_dense_kernel(const GemmBatch gb) {
-    gemm16_body<A_RC, B_RC, BM, BN, BK, D, false>(gb);
-}
-// TABLE form: problems in device memory, persistent walk over the tile list
-template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D>
-__global__ __launch_bounds__(512) void m2f_gemm16_table_kernel(const GemmBatch gb) {
-    gemm16_body<A_RC, B_RC, BM, BN, BK, D, true>(gb);
-}
-template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void m2f_gemm16_table_dense_kernel(const GemmBatch gb) {
-    gemm16_body<A_RC, B_RC, BM, BN, BK, D, true>(gb);
+    gemm16_body<A_RC, B_RC, BM, BN, BK, D>(gb);
 }
 
 template <bool A_RC, bool B_RC, int BM, int BN, int BK, int D, bool DENSE = false, bool GELU = false, bool FP8 = false>
@@ -1319,9 +1240,6 @@ hipError_t launch_tile16(GemmBatch& gb, int tile, hipStream_t stream) {
     // ring kept its loads in flight: 2.34 / 2.38 (depth 3 / 4, 256-VGPR build for launches of
     // at most 256 tiles) vs 2.32 ms; the step alternates between ~8 kernels, so every kilobyte of code is instruction-cache
     // traffic at each launch.
-#ifdef M2F_CHAIN_WIDE_D        // experiment: launches that give a CU one workgroup at most run a 256-VGPR build with a deeper ring
-    if (t <= 256) return launch_cfg16<A_RC, B_RC, 64, 64, 128, M2F_CHAIN_WIDE_D, false>(gb, t, stream);
-#endif
     return launch_cfg16<A_RC, B_RC, 64, 64, 128, M2F_CHAIN_D, true>(gb, t, stream);
 }
 
@@ -1356,50 +1274,7 @@ bool vec_ok(const GemmOperand& o, bool rc, int rows) {
     return true;
 }
 
-template <int BM, int BN, int BK, int D, bool DENSE>
-hipError_t launch_table16(const GemmBatch& gb, hipStream_t stream) {
-    constexpr int lds = 2 * Stage16KC<BM, BK>::LDS_BYTES + 2 * Stage16KC<BN, BK>::LDS_BYTES + (BK / 8) * BM * 4;
-    static_assert(lds <= 160 * 1024 && (!DENSE || 2 * lds <= 160 * 1024), "LDS budget");
-    void (*kern)(const GemmBatch);
-    if constexpr (DENSE) kern = m2f_gemm16_table_dense_kernel<false, false, BM, BN, BK, D>;
-    else kern = m2f_gemm16_table_kernel<false, false, BM, BN, BK, D>;
-    if (lds > 64 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            attr_set = true;
-        }
-    }
-    const int slots = 256 * (DENSE ? 2 : 1);                    // workgroups the chip holds at once
-    const int grid = gb.total_tiles < slots ? gb.total_tiles : slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, gb);
-    return hipGetLastError();
-}
-
 }  // namespace
-
-int m2f_gemm_table_layout(std::vector<GemmProblem>& prs, int tile, std::vector<uint16_t>& tile_prob, bool operand_options) {
-    // tile = 64: 64x64, 128: 128x128, 256: 256 (M) x 128 (N)
-    const int tile_m = tile, tile_n = tile == 256 ? 128 : tile;
-    tile_prob.clear();
-    if (prs.size() > 65535) return -1;
-    for (const GemmProblem& p : prs)
-        if ((p.flags & (GF_RELU_OUT | GF_ACCUM | GF_GELU_OUT)) || (!operand_options && ((p.flags & (GF_RELU_A | GF_RELU_B)) || p.bias_grad)) ||
-            p.bias || p.res || p.gate || p.drop_site || p.c8 || p.a.k[1] || p.b.k[1])
-            return -1;       // the table kernel stages operands as they are (store_select) and stores plain results (table_epilogue_t)
-    int t = 0;
-    for (size_t i = 0; i < prs.size(); ++i) {
-        GemmProblem& p = prs[i];
-        p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0;
-        p.tile_begin = t;
-        p.tiles_n = m2f_cdiv(p.N, tile_n);
-        const int n = m2f_cdiv(p.M, tile_m) * p.tiles_n;
-        for (int j = 0; j < n; ++j) tile_prob.push_back((uint16_t)i);
-        t += n;
-    }
-    return t;
-}
 
 int m2f_gemm_table_walk(const std::vector<GemmProblem>& prs_all, int walk, int n_wg, int tile_m, int tile_n, std::vector<uint32_t>& tile_rec, std::vector<int>& wg_begin,
                         const std::vector<int>* only) {
@@ -1417,7 +1292,7 @@ int m2f_gemm_table_walk(const std::vector<GemmProblem>& prs_all, int walk, int n
     if (prs_all.size() > 65535) return -1;
     std::vector<std::vector<uint32_t>> per_wg((size_t)n_wg);
     if (walk == 0) {
-        // the order of m2f_gemm_table_layout (m fastest inside a problem), dealt as ring_xcd_remap deals it
+        // problem by problem, m fastest inside a problem, dealt as ring_xcd_remap deals it
         std::vector<uint32_t> all;
         for (size_t p = 0; p < prs.size(); ++p) {
             const int tm = m2f_cdiv(prs[p].M, tile_m), tn = m2f_cdiv(prs[p].N, TILE);
@@ -1493,12 +1368,8 @@ extern "C" int m2f_dbg_read(unsigned long long* out) {
 #endif
 
 hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream) {
-    if (!gb.table || !gb.tile_prob || gb.total_tiles <= 0) return hipErrorInvalidValue;
-    if (gb.table_tile >= 129 && gb.table_tile <= 132) return m2f_launch_gemm_ring_table(gb, stream);                              // 128x128 tiles, ring form
-    if (gb.table_tile == 256) return launch_table16<256, 128, 64, M2F_T256_D, false>(gb, stream);
-    if (gb.table_tile == 128) return launch_table16<128, 128, 64, 3, false>(gb, stream);
-    if (gb.table_tile == 64) return launch_table16<64, 64, 128, 2, true>(gb, stream);
-    return hipErrorInvalidValue;
+    if (!gb.table || gb.total_tiles <= 0) return hipErrorInvalidValue;
+    return gb.table_p8 ? m2f_p8_launch_table_rc(gb, stream) : m2f_ring_launch_table_rc_256x128(gb, stream);
 }
 
 hipError_t m2f_ring_launch_256x128_fp8(GemmBatch& gb, hipStream_t stream);      // gemm_ring_256x128_fp8.hip

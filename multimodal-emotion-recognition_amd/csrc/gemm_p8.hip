@@ -106,7 +106,7 @@ extern "C" int m2f_gemm_p8(int rc, int M, int N, int K, const uint16_t* a, int l
         if (hipMemcpy(d_rec, rec.data(), rec.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -5;
         if (hipMemcpy(d_beg, beg.data(), beg.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -5;
     }
-    gb.table = d_tab; gb.tile_rec = d_rec; gb.wg_begin = d_beg; gb.wg_count = n_wg; gb.total_tiles = (int)rec.size(); gb.table_tile = 132;
+    gb.table = d_tab; gb.tile_rec = d_rec; gb.wg_begin = d_beg; gb.wg_count = n_wg; gb.total_tiles = (int)rec.size(); gb.table_p8 = true;
     for (int w = 0; w < n_wg; ++w) gb.p8_max_tiles = std::max(gb.p8_max_tiles, beg[(size_t)w + 1] - beg[(size_t)w]);
     return m2f_p8_launch_table_rc(gb, s) == hipSuccess ? 0 : -2;
 }

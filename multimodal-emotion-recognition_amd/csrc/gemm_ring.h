@@ -62,7 +62,7 @@ __device__ __forceinline__ void ring_lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// Epilogue of the ring form.  The consumers multiplied with the operands SWAPPED (as for table_epilogue_t), so a lane holds, of
+// Epilogue of the ring form.  The consumers multiplied with the operands SWAPPED, so a lane holds, of
 // its 32x32 block, row (lane & 31) and columns 8 g + 4 (lane >> 5) + 0..3 in registers 4 g .. 4 g + 3.  Stored from there, a
 // wave instruction touches 32 different 128-byte lines (measured: 12.9k cycles per 128x128 tile; the row-per-register layout
 // of gemm_epilogue with its 4-byte stores: 7.8k - both far above the tile's 8k cycles of MFMA work).  What the store path
@@ -288,7 +288,7 @@ __device__ __forceinline__ void ring_epilogue(const GemmBatch& gb, const RingEpi
 // Same accumulation order per output element as gemm16_body (k ascending, one MFMA chain) and the same epilogue operations per
 // element (ring_epilogue), so the results are bit-identical to the register-staged builds (tests/test_gemm_ring_gpu.py).
 // Tile configurations: 128x128 / 128x64 / 64x64 (4-5 slots) for the M2FNet step by launch size, 256x128 (3 slots) for
-// text-encoder-sized launches, and the table forms of the weight-gradient launch (TABLE; RC = row-major operands).
+// text-encoder-sized launches, and the table form of the weight-gradient launch (TABLE: row-major "RC" operands, 256x128).
 // =========================================================================================================
 typedef __amdgpu_buffer_rsrc_t m2f_rsrc_t;
 template <int BM, int BN, int S>
@@ -313,13 +313,13 @@ __device__ __forceinline__ int ring_problem_of(const GemmBatch& gb, int bpos) {
 }
 
 // The fields both roles need of the problem a tile belongs to.  Grouped launches: the compact header in the kernel arguments.
-// TABLE form (the weight-gradient launch, ~100 problems): tile -> problem through gb.tile_prob, the problem from the device
+// TABLE form (the weight-gradient launch, ~100 problems): problem and tile from the workgroup's tile record, the problem from the device
 // table; the index is made provably uniform so that these are scalar loads.
 struct RingDesc {
     const uint16_t* aq[2]; const uint16_t* bq[2];
     int M, N, k[2], ldaq[2], ldbq[2], pi, m0, n0;
     uint32_t flags;
-    float* bias_grad;           // TABLE + RC form only (the weight-gradient launch sums the bias gradients itself)
+    float* bias_grad;           // TABLE form only (the weight-gradient launch sums the bias gradients itself)
 };
 template <bool TABLE, int BM, int BN>
 __device__ __forceinline__ RingDesc ring_desc(const GemmBatch& gb, int bpos) {
@@ -331,7 +331,7 @@ __device__ __forceinline__ RingDesc ring_desc(const GemmBatch& gb, int bpos) {
         D.aq[0] = P.a.q[0]; D.aq[1] = P.a.q[0]; D.bq[0] = P.b.q[0]; D.bq[1] = P.b.q[0];
         D.M = P.M; D.N = P.N; D.k[0] = P.a.k[0]; D.k[1] = 0;
         D.ldaq[0] = P.a.ldq[0]; D.ldaq[1] = P.a.ldq[0]; D.ldbq[0] = P.b.ldq[0]; D.ldbq[1] = P.b.ldq[0];
-        D.flags = P.flags; D.bias_grad = P.bias_grad;      // (k-contiguous tables carry neither)
+        D.flags = P.flags; D.bias_grad = P.bias_grad;
     } else {
         D.pi = ring_problem_of(gb, bpos);
         const GemmHot& H = gb.hot[D.pi];
@@ -347,7 +347,7 @@ __device__ __forceinline__ RingDesc ring_desc(const GemmBatch& gb, int bpos) {
 
 // (the two roles are functions of their own: with the producer's lambdas inside the __global__ template hipcc emitted no host
 // stub for the kernel - no diagnostic, an undefined symbol at load time)
-template <int BM, int BN, int S, bool TABLE, bool RC>
+template <int BM, int BN, int S, bool TABLE>
 __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, int wave, int lane, int first, int grid, int total_tiles) {
     using C = RingCfg<BM, BN, S>;
     constexpr int BK = C::BK;
@@ -372,7 +372,7 @@ __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, i
     int im0 = 0, in0 = 0, ink0 = 0, ink = 0, kp0 = 0, kp1 = 0, ald0 = 0, ald1 = 0, bld0 = 0, bld1 = 0;
     unsigned offA[C::A_INSTR], offB[C::B_INSTR];
     int kpad = 0, kcur = 0;                                     // current segment: padded length, k of the next k-tile
-    unsigned stepA = 0, stepB = 0;                              // RC form: bytes per k-tile step (BK rows)
+    unsigned stepA = 0, stepB = 0;                              // TABLE form: bytes per k-tile step (BK rows)
     m2f_rsrc_t ra0, ra1, rb0, rb1, ra, rb;
     bool idone = ibpos >= total_tiles;
     M2F_TS(0);
@@ -380,13 +380,13 @@ __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, i
         const int lda = seg ? ald1 : ald0, ldb = seg ? bld1 : bld0;
         if (seg) { ra = ra1; rb = rb1; } else { ra = ra0; rb = rb0; }
         kpad = seg ? kp1 : kp0; kcur = 0;
-        if constexpr (RC) {
+        if constexpr (TABLE) {
             // RC operands ([k][row] in memory, e.g. the [token][feature] activations of the weight-gradient launch): the LDS
             // image is k-major, 256-byte rows of 128 features; a 1 KiB piece = 4 k-rows, lane -> (k-row lane >> 4, chunk
             // position lane & 15), the 16-byte chunk stored at a position is pos ^ (4 * (k-row & 3)) - which spreads the four
             // k-rows of a transposing fragment read (ds_read_b64_tr_b16) over four disjoint bank ranges
             // (a 256-wide operand is two such images of 128 features behind each other: piece p belongs to image p / 16)
-            static_assert(!RC || ((BM == 128 || BM == 256) && BN == 128), "RC form: 256-byte tile rows");
+            static_assert(!TABLE || ((BM == 128 || BM == 256) && BN == 128), "RC operands: 256-byte tile rows");
             const int kr = lane >> 4, p16 = lane & 15;
 #if defined(M2F_RING_EXP_ADDR)      // timing experiment (results are wrong): 8 k-rows x 128 bytes per piece instead of 4 x 256
             const int kr8 = lane >> 3, c8 = lane & 7;
@@ -432,8 +432,8 @@ __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, i
         kp0 = (H.k[0] + 7) & ~7; kp1 = (H.k[1] + 7) & ~7;
         ald0 = H.ldaq[0]; ald1 = H.ldaq[1]; bld0 = H.ldbq[0]; bld1 = H.ldbq[1];
         const bool two = H.k[1] > 0;
-        // (RC form: the rows of the buffer are the k index - loads past the reduction length are range-checked to zero)
-        ra0 = rsrc_of(H.aq[0], RC ? H.k[0] : H.M, ald0); rb0 = rsrc_of(H.bq[0], RC ? H.k[0] : H.N, bld0);
+        // (TABLE form: the rows of the buffer are the k index - loads past the reduction length are range-checked to zero)
+        ra0 = rsrc_of(H.aq[0], TABLE ? H.k[0] : H.M, ald0); rb0 = rsrc_of(H.bq[0], TABLE ? H.k[0] : H.N, bld0);
         ra1 = rsrc_of(two ? H.aq[1] : H.aq[0], H.M, two ? ald1 : ald0);
         rb1 = rsrc_of(two ? H.bq[1] : H.bq[0], H.N, two ? bld1 : bld0);
         set_segment(0);
@@ -443,7 +443,7 @@ __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, i
         if (ikt == ink0 && ikt > 0) set_segment(1);
         char* dstA = smem + islot * C::SLOT + wv * (C::A_INSTR * 1024);
         char* dstB = smem + islot * C::SLOT + C::A_BYTES + wv * (C::B_INSTR * 1024);
-        if constexpr (RC) {
+        if constexpr (TABLE) {
             const unsigned ka = (unsigned)(kcur / BK) * stepA, kbb = (unsigned)(kcur / BK) * stepB;
 #if defined(M2F_RING_EXP) && M2F_RING_EXP == 1      // experiment: no loads (consumer floor)
             if (false)
@@ -538,7 +538,7 @@ __device__ __forceinline__ void ring_producer(const GemmBatch& gb, char* smem, i
     M2F_ACC_FLUSH();
 }
 
-template <int BM, int BN, int S, bool TABLE, bool RC, int EPI>
+template <int BM, int BN, int S, bool TABLE, int EPI>
 __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, int wave, int lane, int first, int grid, int total_tiles) {
     using C = RingCfg<BM, BN, S>;
     constexpr int MI = BM / 64, NI = BN / 64, BK = C::BK;
@@ -549,7 +549,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) fo[ks] = ((2 * ks + h) ^ x) << 4;
     const int arow = (wm * (BM / 2) + (lane & 31)) * C::ROW, brow = C::A_BYTES + (wn * (BN / 2) + (lane & 31)) * C::ROW;
-    // RC form (k-major image, 256-byte rows): per 16-lane group g, lane 4 q + p supplies the address of k-row
+    // TABLE form (k-major image, 256-byte rows): per 16-lane group g, lane 4 q + p supplies the address of k-row
     // 8 (g >> 1) + q (+ 4 for the second read), features 16 (g & 1) + 4 p .. + 3 of the 32-feature block; lane i of the
     // group receives feature i.  Chunk index of those 8 bytes = (block base + 16 (g & 1)) / 8 + (p >> 1), XOR 4 q (the image's swizzle).
     int rc_row = 0, rc_a[MI], rc_b[NI];
@@ -574,8 +574,8 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
         const GemmProblem& P = TABLE ? gb.table[H.pi] : gb.pr[H.pi];
         const int m0 = H.m0, n0 = H.n0;
         const int nk = (H.k[0] + BK - 1) / BK + (H.k[1] + BK - 1) / BK;
-        const bool reluA = H.flags & GF_RELU_A, reluB = RC && (H.flags & GF_RELU_B);
-        const bool bgrad = RC && H.bias_grad && n0 == 0 && wn == 0;      // wave-uniform: this wave sums its rows of A over k
+        const bool reluA = H.flags & GF_RELU_A, reluB = TABLE && (H.flags & GF_RELU_B);
+        const bool bgrad = TABLE && H.bias_grad && n0 == 0 && wn == 0;      // wave-uniform: this wave sums its rows of A over k
         float bsum[MI];
 #pragma unroll
         for (int i = 0; i < MI; ++i) bsum[i] = 0.f;
@@ -635,7 +635,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
                 constexpr int KS = BK / 16;
                 bf16x8 fa[2][MI], fb[2][NI];
                 auto frags = [&](int ks, int buf) {
-                    if constexpr (RC) {
+                    if constexpr (TABLE) {
                         // MFMA operand (8 consecutive k of one row) out of the k-major image: two transposing reads of 4 k-rows
                         const char* img = smem + slot * C::SLOT + ks * 16 * 256 + rc_row;
 #pragma unroll
@@ -700,7 +700,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
         const unsigned long long tc1 = M2F_NOW();
         {
             const std::true_type T1{}; const std::false_type F0{};
-            if constexpr (RC) {
+            if constexpr (TABLE) {
                 const int sel = (reluA ? 1 : 0) | (reluB ? 2 : 0) | (bgrad ? 4 : 0);
                 switch (sel) {
                     case 0: kloop(F0, F0, F0); break;  case 1: kloop(T1, F0, F0); break;
@@ -713,7 +713,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
                 else kloop(F0, F0, F0);
             }
         }
-        if constexpr (RC) {
+        if constexpr (TABLE) {
             if (bgrad) {                                            // lanes l and l + 32 hold the two k-halves of row l
 #pragma unroll
                 for (int i = 0; i < MI; ++i) {
@@ -733,7 +733,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
     M2F_ACC_FLUSH();
 }
 
-template <int BM, int BN, int S, bool TABLE, bool RC = false, int EPI = (TABLE ? 1 : 0)>
+template <int BM, int BN, int S, bool TABLE, int EPI = (TABLE ? 1 : 0)>
 __global__ __launch_bounds__(512) void m2f_gemm16_ring_kernel(const GemmBatch gb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;      // role-local ids
@@ -749,11 +749,11 @@ __global__ __launch_bounds__(512) void m2f_gemm16_ring_kernel(const GemmBatch gb
     const int grid = TABLE ? 1 : (int)gridDim.x;
     const int total_tiles = TABLE ? __builtin_amdgcn_readfirstlane(gb.wg_begin[blockIdx.x + 1]) : gb.total_tiles;
     const int first = TABLE ? __builtin_amdgcn_readfirstlane(gb.wg_begin[blockIdx.x]) : ring_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    if (threadIdx.x >= 256) ring_producer<BM, BN, S, TABLE, RC>(gb, smem, wave, lane, first, grid, total_tiles);      // wave-uniform
-    else ring_consumer<BM, BN, S, TABLE, RC, EPI>(gb, smem, wave, lane, first, grid, total_tiles);
+    if (threadIdx.x >= 256) ring_producer<BM, BN, S, TABLE>(gb, smem, wave, lane, first, grid, total_tiles);      // wave-uniform
+    else ring_consumer<BM, BN, S, TABLE, EPI>(gb, smem, wave, lane, first, grid, total_tiles);
 }
 
-template <int BM, int BN, int S, bool TABLE, bool RC = false, int EPI = (TABLE ? 1 : 0)>
+template <int BM, int BN, int S, bool TABLE, int EPI = (TABLE ? 1 : 0)>
 hipError_t launch_ring_grid(const GemmBatch& hb, int t, hipStream_t stream) {
     using C = RingCfg<BM, BN, S>;
     static int n_cu = 0;
@@ -762,7 +762,7 @@ hipError_t launch_ring_grid(const GemmBatch& hb, int t, hipStream_t stream) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    auto kern = m2f_gemm16_ring_kernel<BM, BN, S, TABLE, RC, EPI>;
+    auto kern = m2f_gemm16_ring_kernel<BM, BN, S, TABLE, EPI>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
@@ -804,7 +804,7 @@ hipError_t launch_ring16(GemmBatch& gb, hipStream_t stream) {
         h.flags = p.flags; h.tile_begin = p.tile_begin; h.has_bias_grad = 0;
     }
     hb.total_tiles = t;
-    return launch_ring_grid<BM, BN, S, false, false, EPI>(hb, t, stream);
+    return launch_ring_grid<BM, BN, S, false, EPI>(hb, t, stream);
 }
 
 }  // namespace

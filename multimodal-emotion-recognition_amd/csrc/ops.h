@@ -93,15 +93,12 @@ struct GemmBatch {
     unsigned* splitk_cnt;
     int splitk_max_tiles;
     ShadowMap sh;             // C (when it lies in the workspace) is also written as bf16
-    // TABLE form (m2f_launch_gemm_table): the problems live in device memory and a launch of at most chip-filling size
-    // walks the whole tile list (persistent workgroups).  table[i] has tile_begin / tiles_n filled in for `table_tile`;
-    // tile_prob[t] = index of the problem tile t belongs to.  pr[] / count are unused in this form.
+    // TABLE form (m2f_launch_gemm_table): the problems live in device memory, table[i]; pr[] / count are unused in this form.
+    // Every workgroup walks its OWN tile list, tile_rec[wg_begin[b] .. wg_begin[b + 1]) for workgroup b of a grid of wg_count;
+    // a record = problem | m-tile << 16 | n-tile << 24 (m2f_gemm_table_walk)
     const GemmProblem* table;
-    const uint16_t* tile_prob;
     int total_tiles;
-    int table_tile;           // 64, 128, 256 (256x128) or 129 (128x128, ring form)
-    // RING table forms (129 / 130): every workgroup walks its OWN tile list, tile_rec[wg_begin[b] .. wg_begin[b + 1]) for
-    // workgroup b of a grid of wg_count; a record = problem | m-tile << 16 | n-tile << 24 (m2f_gemm_table_walk)
+    bool table_p8;            // 256 x 256 tiles on the eight-phase schedule (gemm_p8.h); false: 256 x 128 ring tiles (gemm_ring.h)
     const uint32_t* tile_rec;
     const int* wg_begin;
     int wg_count;
@@ -127,7 +124,7 @@ bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout);      // host: does t
 bool m2f_gemm_ring_ok(const GemmBatch& gb);
 bool m2f_gemm_ring256_ok(const GemmBatch& gb);       // 256x128 tiles: bias / ReLU / GELU / residual epilogues only
 hipError_t m2f_launch_gemm_ring(GemmBatch& gb, int bm, int bn, hipStream_t stream);
-hipError_t m2f_launch_gemm_ring_table(const GemmBatch& gb, hipStream_t stream);
+hipError_t m2f_ring_launch_table_rc_256x128(const GemmBatch& gb, hipStream_t stream);      // the table form, 256 x 128 tiles (gemm_ring_table.hip)
 // eight-phase 256x256 form (gemm_p8.h): forward-form launches with the 256x128 ring form's epilogue set, single segment, k % 64 == 0
 bool m2f_gemm_p8_ok(const GemmBatch& gb);
 hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream);
@@ -137,18 +134,17 @@ hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream);
 
 // Launches one grouped GEMM. Returns hipSuccess or the launch error. `tile` = 0 (auto), 64 or 128.
 hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStream_t stream);
-// TABLE form, bf16 mode, k-contiguous (NT) operands staged from gb.table[i].{a,b}.q.  Host-side preparation of a table:
-// m2f_gemm_table_layout fills tile_begin / tiles_n of every problem for `tile` and returns the tile -> problem map.
+// TABLE form, bf16 mode: the weight-gradient launch dW = dY^T X on the row-major bf16 shadows gb.table[i].{a,b}.q (reduction
+// over their rows), optional ReLU on either operand and the bias gradient (column sums of A); plain stores of C.
 hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream);
 // fp8 (OCP e4m3) operands, forward form only, single problem: C = act(acc_scale * A8 B8^T + bias) + res.  K % 16 == 0,
 // lda / ldb % 16 == 0, 16-byte aligned operands.  (SURVEY 8-f4 / BASELINE C5: the text encoder's GEMMs.)
 hipError_t m2f_launch_gemm_fp8(GemmBatch& gb, hipStream_t stream);
 #ifdef __cplusplus
 #include <vector>
-int m2f_gemm_table_layout(std::vector<GemmProblem>& prs, int tile, std::vector<uint16_t>& tile_prob, bool operand_options = false);
 bool m2f_gemm_p8_table_ok(const std::vector<GemmProblem>& prs);      // table form of gemm_p8.h: no ReLU on A, single segment
 // Per-workgroup tile lists of the ring table forms (tile_m x tile_n tiles: 128x128, 256x128, 256x256) for a grid of n_wg workgroups (workgroup b runs on XCD
-// b % 8 under round-robin placement - speed only).  walk = 0: the order of m2f_gemm_table_layout (every round spreads 256
+// b % 8 under round-robin placement - speed only).  walk = 0: problem by problem, m fastest inside a problem (every round spreads 256
 // consecutive tiles - usually of ONE problem - over all eight XCDs, so each L2 pulls its own copy of that problem's
 // operands); walk = 1: the tile list is cut into eight contiguous ranges of whole 8 x 4 super-tiles, one per XCD, so a
 // problem's operand panels are fetched by one L2 (two at a range boundary) and the 32 tiles an XCD multiplies at a time
@@ -188,7 +184,7 @@ struct AttnBatch {
     uint32_t drop_thresh;
     float drop_scale;
     ShadowMap sh;              // out (fwd) / dq, dk, dv (bwd) also written as bf16
-    int bwd_fast;              // set by the launcher: LDS holds the fifth (O) slab of the one-round-trip backward path
+    bool bwd_fast;             // set by the launcher: the backward takes its one-round-trip path (attention.hip, attn_bwd_fast)
     int bf16_math;             // bf16 mode, bit mask: 1 = the head-dim contractions (Q K^T, dO V^T) round their operands to bf16 and run
                                // on v_mfma_f32_16x16x32_bf16 (fp32 accumulate): 1/8 of the MFMA instructions at 1/2 the cycles each;
                                // 2 / 4 / 8 / 16 / 32 = the Q / K / V / dO / O slab is staged from the operand's bf16 shadow (half the bytes)
@@ -284,15 +280,6 @@ struct CastItem { const float* src; uint16_t* dst; int rows, cols, lds, ldd; uin
 struct CastBatch { CastItem it[M2F_CAST_MAX_ITEMS]; int count; };
 hipError_t m2f_launch_cast(const CastBatch& cb, hipStream_t stream);
 
-// Token-transposed bf16 copies of activations for the weight-gradient GEMMs: dst[f*ldt + t] = bf16(relu?(src[t*ld + f]))
-// for f < F, t < T; columns T..ldt-1 of dst are written as zero.  With both operands of dW = dY^T X stored
-// [feature][token] the weight gradient runs as the k-contiguous (forward-form) GEMM.  colsum (nullable): [F] sums over
-// tokens of the fp32 source = the bias gradient when src is dY (fixed summation order: deterministic).
-// The item table lives in device memory; block_item[b] = item of workgroup b, items[i].block_begin = its first workgroup
-// (one workgroup per 64 features).
-struct TransItem { const float* src; int ld, F; uint16_t* dst; int ldt; float* colsum; int relu; int block_begin; };
-struct TransBatch { const TransItem* items; const uint16_t* block_item; int blocks; int T; };
-hipError_t m2f_launch_transpose_tokens(const TransBatch& tb, hipStream_t stream);
 
 // Dialogue batcher (replaces Dataset.__getitem__ + collate_fn, reference src/dataset.py:32-89, on the device): token slot t
 // takes row rows[t] of the two device-resident embedding tables (rows[t] < 0: padded slot -> zeros, label -1, key_pad 1).

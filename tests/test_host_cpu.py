@@ -212,8 +212,8 @@ def test_spill_guard_of_the_ring_builds(tmp_path):
         p.write_text("\n".join(out) + "\n")
         return subprocess.run([sys.executable, script, "--ring", str(p)], capture_output=True, text=True)
 
-    a = "_ZN12_GLOBAL__N_122m2f_gemm16_ring_kernelILi256ELi128ELi3ELb1ELb1ELi1EEEv9GemmBatch"
-    b = "_ZN12_GLOBAL__N_122m2f_gemm16_ring_kernelILi128ELi128ELi4ELb1ELb1ELi1EEEv9GemmBatch"
+    a = "_ZN12_GLOBAL__N_122m2f_gemm16_ring_kernelILi256ELi128ELi3ELb1ELi1EEEv9GemmBatch"
+    b = "_ZN12_GLOBAL__N_122m2f_gemm16_ring_kernelILi128ELi128ELi4ELb0ELi0EEEv9GemmBatch"
     assert remarks([(a, 0), (b, 0)]).returncode == 0
     bad = remarks([(a, 112), (b, 0)])
     assert bad.returncode == 1 and "112 bytes of scratch" in bad.stderr
