@@ -106,12 +106,6 @@ int m2f_plan_params_fresh(m2f_plan* plan, int fresh);
 void m2f_plan_destroy(m2f_plan* plan);
 void* m2f_plan_buffer(m2f_plan* plan, int which);
 int m2f_plan_num_launches(m2f_plan* plan, int phase);   /* 0 fwd, 1 loss, 2 bwd */
-/* Kept for callers of rounds 2-3, when a plan could run its launch lists as two persistent ("strip-dataflow") launches (measured
- * slower than the lists and removed in round 4; git history keeps csrc/mega.hip): always 0 = launch lists. */
-int m2f_plan_persistent(m2f_plan* plan);
-/* Status record of a plan's kernels: out8 is zeroed and 0 returned - no kernel of the launch lists waits on another workgroup, so
- * none can give up (the persistent kernels left their bounded-wait record here).  Fails on a NULL / destroyed plan. */
-int m2f_plan_status(m2f_plan* plan, uint32_t* out8);
 
 /* M2FNet.forward (src/model.py:102-145): inputs read from M2F_BUF_TEXT/AUDIO/KEYPAD, logits -> M2F_BUF_LOGITS. */
 int m2f_forward(m2f_plan* plan, m2f_stream_t stream);
@@ -132,7 +126,8 @@ int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int n
  *            gradient whose operands that chain completes;   part 1 = the encoders' backward + the remaining weight gradients.
  * After part 0 the flat gradient buffer is final from element m2f_plan_split_offset(plan) on (fusion stack + classifier = its
  * tail, and the 64-float loss tail behind it), so a rank can put that bucket's all-reduce on the wire and run part 1 under it.
- * m2f_plan_split_offset returns 0 for plans that cannot be split (fp32 mode, eval plans); parts 0 and 1 must alternate. */
+ * m2f_plan_split_offset returns 0 for plans that cannot be split (fp32 mode, eval plans); parts 0 and 1 must alternate.
+ * The split step always writes fp32 gradients: it ignores m2f_plan_fused_adam and m2f_plan_grad_bf16. */
 int64_t m2f_plan_split_offset(m2f_plan* plan);
 int m2f_step_part(m2f_plan* plan, int part, float label_smoothing, int use_class_weights, int normalise, int use_graph,
                   m2f_stream_t stream);
@@ -146,7 +141,7 @@ int m2f_gather_dialogues(const float* text_table, int d_text, const float* audio
 
 /* Measurement aid: one EAGER m2f_step with a hipEvent pair recorded on `stream` around every launch.  Fills, per
  * launch, kinds[] (0/1/2 = grouped GEMM forward/dgrad/wgrad form, 3/4 attention fwd/bwd, 5/6 LayerNorm fwd/bwd,
- * 7 dropout-mask, 8 criterion, 9 LayerNorm-parameter reduce, 10 bf16 cast / token-transpose copies, 11 / 12 unused (the removed persistent kernels);
+ * 7 dropout-mask, 8 criterion, 9 LayerNorm-parameter reduce, 10 bf16 casts, 11 / 12 unused;
  * chain launches carry + 32 x their part of the model: 0 modality encoders, 1 fusion stack (FusionAttentionModule, src/model.py:13-20), 2 classifier), ms[]
  * (device time) and flops[] (algorithmic FLOPs of the launch, 0 for row-wise kernels).  Synchronises the stream.  Returns the number of launches, or <0. */
 int m2f_step_timed(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, m2f_stream_t stream,
@@ -293,7 +288,7 @@ int m2f_gemm(int precision, int layout, int M, int N, int K0, int K1,
  * with); hyper_dev = 8 device floats refreshed by m2f_adam_hyper BEFORE every step (lr, betas, eps, weight decay, step count t >= 1:
  * lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t) change every step and a replayed graph cannot take them as arguments);
  * grad_scale_ptr (nullable): device scalar the gradients are divided by (m2f_step(normalise = 0)).
- * m2f_plan_fused_adam(plan, 1 | 0) switches the form of the NEXT m2f_step (re-captures the graph on a change). */
+ * m2f_plan_fused_adam(plan, 1 | 0) switches the form of the NEXT m2f_step (re-captures the graph on a change, and after every setup). */
 int m2f_plan_fused_adam_setup(m2f_plan* plan, float* params, float* exp_avg, float* exp_avg_sq, uint16_t* param_shadow,
                               const float* hyper_dev, const float* grad_scale_ptr);
 int m2f_plan_fused_adam(m2f_plan* plan, int on);

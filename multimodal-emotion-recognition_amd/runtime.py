@@ -75,9 +75,7 @@ SIGNATURES = {
     "m2f_plan_destroy": (None, [c_void_p]),
     "m2f_plan_buffer": (c_void_p, [c_void_p, c_int]),
     "m2f_plan_num_launches": (c_int, [c_void_p, c_int]),
-    "m2f_plan_persistent": (c_int, [c_void_p]),
     "m2f_gemm_ring_launches": (ctypes.c_longlong, []),
-    "m2f_plan_status": (c_int, [c_void_p, ctypes.POINTER(c_uint32)]),
     "m2f_forward": (c_int, [c_void_p, c_void_p]),
     "m2f_loss": (c_int, [c_void_p, c_float, c_int, c_int, c_void_p]),
     "m2f_backward": (c_int, [c_void_p, c_void_p]),
@@ -318,14 +316,9 @@ class Plan:
         esize = torch.empty(0, dtype=dtype).element_size()
         return self.workspace[off: off + n * esize].view(dtype).view(*shape)
 
-    def persistent(self) -> int:
-        """Always 0 since round 4 (the persistent strip-dataflow kernels were removed; kept for callers that still ask)."""
-        return lib().m2f_plan_persistent(self._h())
-
     def check_status(self) -> None:
-        """Raises on a destroyed plan; nothing else can be wrong since the persistent kernels (bounded waits) were removed."""
-        out = (c_uint32 * 8)()
-        check(lib().m2f_plan_status(self._h(), out), "m2f_plan_status")
+        """Raises on a closed plan: no kernel of the launch lists can give up, so there is nothing else to check."""
+        self._h()
 
     def num_launches(self) -> Dict[str, int]:
         return {k: lib().m2f_plan_num_launches(self._h(), i) for i, k in enumerate(("forward", "loss", "backward"))}

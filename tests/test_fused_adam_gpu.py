@@ -6,6 +6,7 @@ is BIT FOR BIT against the two-launch path (m2f_step, then m2f_adam_step_shadowe
     whole and partial 256 x 256 tiles, a shared final LayerNorm, a model without fusion stack, the 300-wide audio operand;
   * with the gradients divided by a device-side denominator (the data-parallel / bench form of the step: normalise = 0);
   * a learning-rate change between steps reaches the captured graph (the step-dependent factors live in device memory);
+  * a second optimizer taking over the same model between captured steps is the one the replayed graph applies;
   * fp32 models fall back to the optimizer's own kernel without being asked."""
 import pytest
 import torch
@@ -24,18 +25,24 @@ def _model(cfg, precision="bf16"):
     return m.to("cuda:0").train()
 
 
-def _run(name, fused, steps=5, normalise=True, lr_change=False, precision="bf16"):
+def _run(name, fused, steps=5, normalise=True, lr_change=False, precision="bf16", swap_at=None):
+    """`swap_at`: from that step on a new FusedAdam (fresh moments) drives the same model."""
     cfg, B, L, lengths, kind = synth.CASES[name]
     batch = [t.cuda() for t in synth.make_inputs(cfg, B, L, lengths, kind)]
     m = _model(cfg, precision)
-    opt = FusedAdam(m, lr=1e-3, weight_decay=0.01)
-    if not normalise:
-        den = torch.tensor([float((batch[3] != -1).sum())], device="cuda")
-        opt.grad_scale = den
+
+    def optimizer():
+        opt = FusedAdam(m, lr=1e-3, weight_decay=0.01)
+        if not normalise:
+            opt.grad_scale = torch.tensor([float((batch[3] != -1).sum())], device="cuda")
+        return opt
+    opt = optimizer()
     losses = []
     for i in range(steps):
         if lr_change and i == 3:
             opt.param_groups[0]["lr"] = 2.5e-4
+        if i == swap_at:
+            opt = optimizer()
         if fused:
             losses.append(float(m.train_step(*batch, normalise=normalise, use_graph=i > 0, optimizer=opt)))
         else:
@@ -79,6 +86,19 @@ def test_learning_rate_changes_reach_the_captured_graph():
     assert torch.equal(a["p"], b["p"]) and torch.equal(a["m"], b["m"])
     c = _run("tiny_ragged", True, steps=6, lr_change=False)
     assert not torch.equal(a["p"], c["p"])
+
+
+def test_a_second_optimizer_drives_the_captured_graph():
+    """A new FusedAdam on the same model arms the plan again (new moments, new device tables): the captured step replays with its
+    buffers, not with those of the optimizer it replaced."""
+    a, b = _run("tiny_ragged", True, steps=6, swap_at=3), _run("tiny_ragged", False, steps=6, swap_at=3)
+    assert a["armed"] and not b["armed"], a["err"]
+    assert a["losses"] == b["losses"], (a["losses"], b["losses"])
+    for k in ("p", "m", "v"):
+        assert torch.equal(a[k], b[k]), (k, float((a[k] - b[k]).abs().max()))
+    c = _run("tiny_ragged", True, steps=6)
+    for k in ("p", "m", "v"):
+        assert not torch.equal(a[k], c[k]), k
 
 
 def test_fp32_models_take_the_optimizers_own_kernel():
