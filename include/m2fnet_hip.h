@@ -352,6 +352,35 @@ int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, 
                       float label_smoothing, int normalise, float* loss_terms, float* dlogits, float* loss_out,
                       m2f_stream_t stream);
 
+/* ---- wav2vec2 audio encoder (multimodal-emotion-recognition_amd/wav2vec2.py) ------------------------------------------------------
+ * The reference makes its audio embeddings in a separate stage (src/feature_extractors/audio_wav2vec2/embeddings.py:52-91:
+ * torchaudio WAV2VEC2_BASE on batches of zero-padded 16 kHz waveforms, then the mean of each utterance's valid frames).  These
+ * entries are the kernels of that model the GEMM / attention / LayerNorm entries do not cover.  Activations are channels-last; all
+ * are deterministic (no atomics, fixed reduction orders).
+ *
+ * Conv layer 0 (Conv1d(1, C, k0, stride s0, bias=False)) + GroupNorm(C, C) + exact GELU (torchaudio ConvLayerBlock 0; the
+ * reference's embeddings.py:77 call model(audio, lengths)): wave [B, N] fp32, the padded batch; w0 [C, k0]; the statistics of channel
+ * c of utterance b cover frames 0 .. T0-1 of the PADDED waveform (T0 = (N - k0) / s0 + 1), so a short utterance's output depends on
+ * the longest one in its batch, as in the reference.  Output row b * P0 + t (P0 >= T0; rows T0 .. P0-1 are written as zeros) of
+ * exactly one of out32 (fp32) / out16 (bf16 bits), C columns.  partial / stats: device scratch of
+ * m2f_w2v_conv0_scratch_floats(B, C, T0) floats, partial first, then stats (B * C * 2).  k0 <= 16, s0 <= 8. */
+int m2f_w2v_conv0(int B, int N, const float* wave, const float* w0, int k0, int s0, int C, int T0, int P0, const float* gamma,
+                  const float* beta, float eps, float* scratch, float* out32, uint16_t* out16, m2f_stream_t stream);
+int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0);
+/* Feature-projection LayerNorm (torchaudio FeatureProjection.layer_norm) with the row compaction of the conv stack folded into its
+ * read: row b * P + t of x [B * P, C] -> row b * S + t of out32 [B * S, C] (and of out16, bf16 bits, when non-NULL).  C <= 1024. */
+int m2f_w2v_feat_layernorm(int B, int S, int P, int C, const float* x, const float* gamma, const float* beta, float eps, float* out32,
+                           uint16_t* out16, m2f_stream_t stream);
+/* Positional convolution + residual (torchaudio ConvolutionalPositionalEmbedding, Conv1d(d, d, K, padding K/2, groups), weight norm
+ * folded into w; the extra last frame of an even K dropped; then x + GELU(conv(x))):
+ *   out[b*S + t, g*CG + o] = GELU(bias + sum_{k<K, c<CG} x[t + k - K/2, g*CG + c] w[g][k][o][c]) + x[t, g*CG + o]
+ * with rows of x at or past lengths[b] (int32, device) read as zero, the residual included.  x, out [B*S, d] fp32; CG = d / groups
+ * in {16, 32, 48, 64}; K <= 256.  bf16 = 0: w fp32, exact-fp32 MFMA; bf16 = 1: w bf16 bits, x rounded to bf16, fp32 accumulation. */
+int m2f_w2v_pos_conv(int B, int S, int d, int groups, int K, const float* x, const int32_t* lengths, const void* w, const float* bias,
+                     float* out, int bf16, m2f_stream_t stream);
+/* out[b, c] = mean of x[b*S + t, c] over t < lengths[b] (embeddings.py:80-85; fixed summation order, lengths[b] <= 0 gives zeros). */
+int m2f_w2v_masked_mean(int B, int S, int d, const float* x, const int32_t* lengths, float* out, m2f_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

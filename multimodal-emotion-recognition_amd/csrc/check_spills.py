@@ -16,7 +16,9 @@ ring = len(sys.argv) > 2 and sys.argv[1] == "--ring"
 # --dlong <remarks>: the long-dialogue attention kernels (attention_dlong.hip) keep their output accumulators in registers through
 # fully unrolled loops with static indices; an unroll that fails turns them into scratch arrays - refuse the build instead.
 dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
-path = sys.argv[2] if (ring or dlong) else sys.argv[1]
+# --w2v <remarks>: the wav2vec2 front end (audio_conv.hip) - the same rule for its kernels (the positional convolution's accumulators)
+w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
+path = sys.argv[2] if (ring or dlong or w2v) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -30,10 +32,11 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-if dlong:
-    kernels = [r for r in rows if "m2f_attn_dlong" in r["name"]]
+if dlong or w2v:
+    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_"
+    kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
-        sys.exit(f"check_spills: no long-dialogue attention kernel found in {path} - did the remark format change?")
+        sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0]
     for r in bad:
         print(f"check_spills: {r['name']} uses {r['scratch']} bytes of scratch per lane", file=sys.stderr)

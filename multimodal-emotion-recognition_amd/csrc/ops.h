@@ -342,3 +342,21 @@ __device__ __forceinline__ uint16_t* m2f_shadow_of(const ShadowMap& sh, const fl
     return (i >= 0 && (size_t)i < sh.ws_floats) ? sh.shadow + i : nullptr;
 }
 #endif
+
+// ------------------------------------------------------------------------------------------------
+// wav2vec2 audio encoder front end (audio_conv.hip; wav2vec2.py drives it, conv layers 1.. run on m2f_launch_gemm)
+// ------------------------------------------------------------------------------------------------
+#define M2F_W2V_CONV0_MAX_TAPS 16
+#define M2F_W2V_CONV0_MAX_STRIDE 8
+#define M2F_W2V_FEAT_MAX_C 1024
+#define M2F_W2V_POS_MAX_TAPS 256
+int m2f_w2v_conv0_chunks(int T0);            // partial statistics: 2 floats per (utterance, chunk, channel); stats: 2 per (utterance, channel)
+hipError_t m2f_launch_w2v_conv0(const float* wave, int B, int N, const float* w0, int k0, int s0, int C, int T0, int P0, const float* gamma,
+                                const float* beta, float eps, float* partial, float* stats, float* out32, uint16_t* out16,
+                                hipStream_t stream);
+hipError_t m2f_launch_w2v_feat_ln(const float* x, int B, int S, int P, int C, const float* gamma, const float* beta, float eps, float* out32,
+                                  uint16_t* out16, hipStream_t stream);
+size_t m2f_w2v_pos_conv_lds(int CG, int K, int bf16);
+hipError_t m2f_launch_w2v_pos_conv(const float* x, const int* lengths, int B, int S, int d, int groups, int K, const void* w, const float* bias,
+                                   float* out, int bf16, hipStream_t stream);
+hipError_t m2f_launch_w2v_masked_mean(const float* x, const int* lengths, int B, int S, int d, float* out, hipStream_t stream);

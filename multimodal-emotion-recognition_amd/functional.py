@@ -228,3 +228,89 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
     return y.view(B, L, E)
+
+
+# ---- wav2vec2 audio encoder kernels (wav2vec2.py) ------------------------------------------------------------------------------
+
+def w2v_conv0(wave: torch.Tensor, w0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, stride: int, P0: Optional[int] = None,
+              bf16_out: bool = False, eps: float = 1e-5) -> torch.Tensor:
+    """Conv1d(1, C, k0, stride, bias=False) + GroupNorm(C, C) + exact GELU of the padded batch wave [B, N]: rows b * P0 + t
+    ([B * P0, C]; rows T0 .. P0-1 zero) as fp32, or as bf16 when bf16_out."""
+    runtime.require_gpu()
+    B, N = wave.shape
+    C, k0 = w0.shape[0], w0.shape[-1]
+    T0 = (N - k0) // stride + 1
+    P0 = T0 if P0 is None else P0
+    scratch = torch.empty(int(lib().m2f_w2v_conv0_scratch_floats(B, C, T0)), dtype=torch.float32, device=wave.device)
+    out = torch.empty(B * P0, C, dtype=torch.bfloat16 if bf16_out else torch.float32, device=wave.device)
+    check(lib().m2f_w2v_conv0(B, N, ptr(wave.contiguous()), ptr(w0.reshape(C, k0).contiguous()), k0, stride, C, T0, P0, ptr(gamma),
+                              ptr(beta), eps, ptr(scratch), None if bf16_out else ptr(out), ptr(out) if bf16_out else None,
+                              stream_ptr()), "m2f_w2v_conv0")
+    return out
+
+
+def w2v_conv_layer(x: torch.Tensor, w: torch.Tensor, stride: int, P_in: int, precision: int = runtime.F32) -> torch.Tensor:
+    """One conv layer of the wav2vec2 front end (Conv1d(C, C, k, stride, bias=False) + exact GELU) on the grouped GEMM, the way
+    wav2vec2.py runs it: x [rows >= B * P_in + 1, C] holds utterance b's frames at rows b * P_in + t (P_in a multiple of stride;
+    the row behind the last pitch must exist: the last junk window reads it).  Returns [B * P_in / stride, C], output frame t of
+    utterance b at row b * P_in / stride + t.  w [C, C, k] with stride <= k <= 2 * stride."""
+    runtime.require_gpu()
+    C, _, k = w.shape
+    assert P_in % stride == 0 and stride <= k <= 2 * stride and x.is_contiguous() and x.shape[1] == C
+    B = (x.shape[0] - 1) // P_in
+    M, ld, K0, K1 = B * P_in // stride, stride * C, stride * C, (k - stride) * C
+    weff = w.permute(0, 2, 1).reshape(C, k * C).float().contiguous()
+    out = torch.empty(M, C, dtype=torch.float32, device=x.device)
+    bf16 = precision == runtime.BF16
+    x16 = x.to(torch.bfloat16).contiguous() if bf16 else None
+    w16 = weff.to(torch.bfloat16).contiguous() if bf16 else None
+    a1 = x.data_ptr() + ld * 4 if K1 else None
+    check(lib().m2f_gemm(precision, NT, M, C, K0, K1, ptr(x), ld, a1, ld if K1 else 0, ptr(weff), k * C,
+                         weff.data_ptr() + K0 * 4 if K1 else None, k * C if K1 else 0, ptr(out), C, None, None, 0, None, 0, 1.0, None,
+                         0, 0, 2, 0, 0, 0.0, None, 0, None, None, 0,
+                         ptr(x16), ld if bf16 else 0, x16.data_ptr() + ld * 2 if bf16 and K1 else None, ld if bf16 and K1 else 0,
+                         ptr(w16), k * C if bf16 else 0, w16.data_ptr() + K0 * 2 if bf16 and K1 else None, k * C if bf16 and K1 else 0,
+                         stream_ptr()), "m2f_gemm (conv layer)")
+    return out
+
+
+def w2v_feat_layernorm(x: torch.Tensor, B: int, S: int, P: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
+    """LayerNorm of rows b * P + t (t < S) of x [>= B * P, C] -> [B * S, C] (row b * S + t)."""
+    runtime.require_gpu()
+    C = x.shape[1]
+    out = torch.empty(B * S, C, dtype=torch.float32, device=x.device)
+    check(lib().m2f_w2v_feat_layernorm(B, S, P, C, ptr(x.contiguous()), ptr(gamma), ptr(beta), eps, ptr(out), None, stream_ptr()),
+          "m2f_w2v_feat_layernorm")
+    return out
+
+
+def w2v_pack_pos_weight(w: torch.Tensor, groups: int, bf16: bool = False) -> torch.Tensor:
+    """Conv1d(d, d, K, groups) weight [d, d / groups, K] (weight norm already folded) -> the kernel's [group][tap][o][c]."""
+    d, CG, K = w.shape
+    p = w.float().view(groups, CG, CG, K).permute(0, 3, 1, 2).contiguous()
+    return p.to(torch.bfloat16).contiguous() if bf16 else p
+
+
+def w2v_pos_conv(x: torch.Tensor, lengths: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, groups: int, B: int, S: int,
+                 bf16: bool = False) -> torch.Tensor:
+    """x [B * S, d] -> x + GELU(grouped conv(x) + bias) with padding K / 2, the extra frame of an even K dropped, rows at or past
+    lengths[b] of x read as zero (the residual too).  w [d, d / groups, K] fp32."""
+    runtime.require_gpu()
+    d = x.shape[1]
+    K = w.shape[2]
+    out = torch.empty_like(x)
+    wpk = w2v_pack_pos_weight(w, groups, bf16)
+    l32 = lengths.to(x.device, torch.int32).contiguous()
+    check(lib().m2f_w2v_pos_conv(B, S, d, groups, K, ptr(x.contiguous()), ptr(l32), ptr(wpk), ptr(bias), ptr(out), int(bf16),
+                                 stream_ptr()), "m2f_w2v_pos_conv")
+    return out
+
+
+def w2v_masked_mean(x: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """x [B, S, d] -> [B, d]: mean over the first lengths[b] frames."""
+    runtime.require_gpu()
+    B, S, d = x.shape
+    out = torch.empty(B, d, dtype=torch.float32, device=x.device)
+    l32 = lengths.to(x.device, torch.int32).contiguous()
+    check(lib().m2f_w2v_masked_mean(B, S, d, ptr(x.contiguous()), ptr(l32), ptr(out), stream_ptr()), "m2f_w2v_masked_mean")
+    return out

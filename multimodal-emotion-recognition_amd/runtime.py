@@ -135,6 +135,12 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p]),
     "m2f_cross_entropy": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
+                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
+    "m2f_w2v_feat_layernorm": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "m2f_w2v_pos_conv": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "m2f_w2v_masked_mean": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@ Unlike the reference (three full-DataFrame scans per utterance, src/dataset.py:3
 index is built ONCE at construction, so ``__getitem__`` is two tensor gathers."""
 import os
 import pickle
+import wave
 
 import numpy as np
 import torch
@@ -40,14 +41,47 @@ def tokenised_contexts(table, tokenizer, max_tokens=64):
     return enc["input_ids"].to(torch.int64), enc["attention_mask"].to(torch.int64)
 
 
+WAV_SAMPLE_RATE = 16000
+WAV_MAX_SECONDS = 10
+
+
+def load_wav(path, max_seconds=WAV_MAX_SECONDS):
+    """One utterance's waveform as the reference's wav2vec2 stage reads it (src/feature_extractors/audio_wav2vec2/dataset.py:37-48):
+    mono, 16 kHz, float in [-1, 1) (16-bit PCM / 32768), truncated to 10 s.  The files are what the reference's scripts/mp4towav.py
+    writes (ffmpeg -ac 1 -ar 16000); there is no resampler here, so other rates, channel counts and sample widths are refused."""
+    with wave.open(os.fspath(path), "rb") as w:
+        if w.getframerate() != WAV_SAMPLE_RATE:
+            raise ValueError(f"{path}: {w.getframerate()} Hz; only {WAV_SAMPLE_RATE} Hz is read (there is no resampler)")
+        if w.getnchannels() != 1 or w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: need mono 16-bit PCM (got {w.getnchannels()} channel(s), {8 * w.getsampwidth()}-bit, {w.getcomptype()})")
+        n = min(w.getnframes(), int(max_seconds * WAV_SAMPLE_RATE))
+        pcm = np.frombuffer(w.readframes(n), dtype="<i2")
+    return torch.from_numpy(pcm.astype(np.float32) / 32768.0)
+
+
+def load_waveforms(table, wav_dir, max_seconds=WAV_MAX_SECONDS):
+    """Waveforms of every table row, in row order: wav_dir/dia{Dialogue_ID}_utt{Utterance_ID}.wav (the reference's file names)."""
+    return [load_wav(os.path.join(os.fspath(wav_dir), f"dia{d}_utt{u}.wav"), max_seconds)
+            for d, u in zip(table["Dialogue_ID"].tolist(), table["Utterance_ID"].tolist())]
+
+
 class Dataset(torch.utils.data.Dataset):
-    def __init__(self, mode="train", text_embeddings=None, audio_embeddings=None, table=None, token_ids=None, token_mask=None):
+    def __init__(self, mode="train", text_embeddings=None, audio_embeddings=None, table=None, token_ids=None, token_mask=None,
+                 waveforms=None):
         """token_ids / token_mask ([N, S] int64, rows = table rows; `tokenised_contexts`): items and batches ALSO carry "text_ids" /
-        "text_mask" - what the in-loop text encoder consumes instead of the pre-extracted "text" rows (`runtime.text_encoder`)."""
+        "text_mask" - what the in-loop text encoder consumes instead of the pre-extracted "text" rows (`runtime.text_encoder`).
+        waveforms (a list of 1-D float tensors, rows = table rows; `load_waveforms`): items carry "wave" and batches "waveforms" /
+        "wave_lengths" / "wave_index" - what the in-loop audio encoder consumes (`runtime.audio_encoder`); the audio pickle is then
+        not read (audio_embeddings stays optional)."""
         super().__init__()
         self.mode = mode
         self.token_ids, self.token_mask = token_ids, token_mask
-        if text_embeddings is None or audio_embeddings is None:
+        self.waveforms = waveforms
+        if waveforms is not None:
+            if text_embeddings is None:
+                with open(os.path.join(os.path.abspath(get_config().embeddings.text), f"{mode}.pkl"), "rb") as f:
+                    text_embeddings = pickle.load(f)
+        elif text_embeddings is None or audio_embeddings is None:
             config = get_config()
             with open(os.path.join(os.path.abspath(config.embeddings.text), f"{mode}.pkl"), "rb") as f:
                 text_embeddings = pickle.load(f)
@@ -66,8 +100,11 @@ class Dataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         rows = torch.as_tensor(self.rows[idx])
-        item = {"text": self.text_embeddings[rows], "audio": self.audio_embeddings[rows],
-                "emotion": [e.reshape(1) for e in self._labels[rows]]}
+        item = {"text": self.text_embeddings[rows], "emotion": [e.reshape(1) for e in self._labels[rows]]}
+        if self.audio_embeddings is not None:
+            item["audio"] = self.audio_embeddings[rows]
+        if self.waveforms is not None:
+            item["wave"] = [self.waveforms[r] for r in rows.tolist()]
         if self.token_ids is not None:
             item["text_ids"] = self.token_ids[rows]
             item["text_mask"] = self.token_mask[rows] if self.token_mask is not None else torch.ones_like(item["text_ids"])
@@ -81,13 +118,29 @@ def collate_fn(batch):
     B = len(batch)
     L = max(d["text"].shape[0] for d in batch)
     text = batch[0]["text"].new_zeros(B, L, batch[0]["text"].shape[1])
-    audio = batch[0]["audio"].new_zeros(B, L, batch[0]["audio"].shape[1])
+    has_audio = "audio" in batch[0]
+    audio = batch[0]["audio"].new_zeros(B, L, batch[0]["audio"].shape[1]) if has_audio else None
     emotion = torch.full((B, L), -1, dtype=torch.int64)          # -1 = ignored by the criterion
     for i, d in enumerate(batch):
         n = d["text"].shape[0]
-        text[i, :n], audio[i, :n] = d["text"], d["audio"]
+        text[i, :n] = d["text"]
+        if has_audio:
+            audio[i, :n] = d["audio"]
         emotion[i, :n] = torch.cat([torch.as_tensor(e).reshape(1) for e in d["emotion"]]).to(torch.int64)
-    out = {"text": text, "audio": audio, "padding_mask": emotion == -1, "emotion": emotion}
+    out = {"text": text}
+    if has_audio:
+        out["audio"] = audio
+    out["padding_mask"], out["emotion"] = emotion == -1, emotion
+    if "wave" in batch[0]:
+        # in-loop audio encoder: the waveforms of all utterances of the batch, zero-padded to the longest ([n, N] fp32), their sample
+        # counts, and where each goes in the [B, L] grid (flat index b * L + t)
+        waves = [w for d in batch for w in d["wave"]]
+        lengths = torch.tensor([w.shape[0] for w in waves], dtype=torch.int64)
+        wav = torch.zeros(len(waves), int(lengths.max()) if len(waves) else 0, dtype=torch.float32)
+        for j, w in enumerate(waves):
+            wav[j, : w.shape[0]] = w
+        out["waveforms"], out["wave_lengths"] = wav, lengths
+        out["wave_index"] = torch.cat([i * L + torch.arange(len(d["wave"]), dtype=torch.int64) for i, d in enumerate(batch)])
     if "text_ids" in batch[0]:                                     # in-loop text encoder: [B, L, S] token ids + attention mask, zero on pads
         S = batch[0]["text_ids"].shape[1]
         ids = torch.zeros(B, L, S, dtype=torch.int64)

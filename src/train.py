@@ -85,6 +85,26 @@ def build_text_encoder(te_cfg, d_text, device):
     return enc.to(device).eval()
 
 
+def build_audio_encoder(ae_cfg, d_audio, device):
+    """`runtime.audio_encoder`: {enabled, precision: fp32 | bf16, geometry: base | a dict of Wav2Vec2Config fields, checkpoint: path of a
+    state_dict in transformers.Wav2Vec2Model or torchaudio wav2vec2 key layout (the encoder of the reference's AudioERC) or null =
+    random weights, wav_dir}."""
+    from mer_amd.wav2vec2 import Wav2Vec2Encoder, base_config
+    geo = ae_cfg.get("geometry", "base")
+    cfg = base_config()
+    if not isinstance(geo, str):
+        cfg.update(dict(geo))
+    elif geo != "base":
+        raise ValueError(f"runtime.audio_encoder.geometry {geo!r}: base or a dict of Wav2Vec2Config fields")
+    if cfg["hidden_size"] != d_audio:
+        raise ValueError(f"runtime.audio_encoder produces {cfg['hidden_size']}-wide rows but model.AUDIO.embedding_size is {d_audio}")
+    enc = Wav2Vec2Encoder(cfg, precision=ae_cfg.get("precision", "bf16"))
+    ck = ae_cfg.get("checkpoint", None)
+    if ck:
+        enc.load_state_dict(torch.load(os.path.abspath(ck), map_location="cpu"))
+    return enc.to(device).eval()
+
+
 def start_wandb(config):
     if wandb is None:
         raise RuntimeError("wandb.enabled is set but the wandb package is not installed")
@@ -126,6 +146,20 @@ def main(config=None):
         print(f"Using device {device}..." + (f" ({world} ranks)" if world > 1 else ""))
     torch.manual_seed(int(_runtime(config, "seed", 0)))       # identical replicas and identical shuffles on every rank
 
+    ae_cfg = _runtime(config, "audio_encoder", None) or {}
+    ae_on = bool(ae_cfg.get("enabled", False))
+    ds_kw = {"train": {}, "val": {}}
+    if ae_on:
+        # waveforms of every table row, read once (dia{D}_utt{U}.wav); the audio pickle is not read
+        if not ae_cfg.get("wav_dir", None):
+            raise RuntimeError("runtime.audio_encoder.enabled needs runtime.audio_encoder.wav_dir: the directory with dia{D}_utt{U}.wav")
+        if _runtime(config, "device_batcher", False):
+            raise RuntimeError("runtime.audio_encoder needs the DataLoader path (runtime.device_batcher: False): batches carry waveforms")
+        from dataset import load_waveforms
+        from utils import get_text
+        for mode in ds_kw:
+            table = get_text(mode)
+            ds_kw[mode] = {"table": table, "waveforms": load_waveforms(table, os.path.abspath(ae_cfg["wav_dir"]))}
     te_on = bool((_runtime(config, "text_encoder", None) or {}).get("enabled", False))
     if te_on:
         # the tokenizer is the caller's: a LOCAL directory with the files of the reference's RobertaTokenizer (text/dataset.py:9,42 fetch
@@ -137,11 +171,11 @@ def main(config=None):
         from dataset import tokenised_contexts
         tok = AutoTokenizer.from_pretrained(os.path.abspath(tok_dir))
         max_tokens = int(_runtime(config, "text_encoder").get("max_tokens", 64))
-        train_set, val_set = Dataset(mode="train"), Dataset(mode="val")
+        train_set, val_set = Dataset(mode="train", **ds_kw["train"]), Dataset(mode="val", **ds_kw["val"])
         for ds_ in (train_set, val_set):
             ds_.token_ids, ds_.token_mask = tokenised_contexts(ds_.text, tok, max_tokens)
     else:
-        train_set, val_set = Dataset(mode="train"), Dataset(mode="val")
+        train_set, val_set = Dataset(mode="train", **ds_kw["train"]), Dataset(mode="val", **ds_kw["val"])
     if _runtime(config, "device_batcher", False):          # embedding tables in HBM, one gather kernel per batch
         dl_train = DeviceLoader(train_set, device=device, seed=_runtime(config, "seed", 0), **config.train.data_loader)
         dl_val = DeviceLoader(val_set, device=device, **config.val.data_loader)
@@ -164,6 +198,9 @@ def main(config=None):
         # embeddings/<text>/<mode>.pkl.  Built OUTSIDE the fusion model (object.__setattr__: not a sub-module - its weights are
         # neither in M2FNet's state_dict / checkpoint format nor in the optimizer, as in the reference, which trains it in its own stage).
         object.__setattr__(model, "text_encoder", build_text_encoder(te_cfg, config.model.TEXT.embedding_size, device))
+    if ae_on:
+        # the audio rows are computed in the loop from waveforms; built outside the fusion model, like the text encoder
+        object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device))
     criterion = build_criterion(config.solver, train_set, device)
     optimizer = FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
     if world > 1:
@@ -274,7 +311,8 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     running = 0.0
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
-        text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None))
+        text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
+                                                           audio_encoder=getattr(model, "audio_encoder", None))
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
@@ -329,7 +367,8 @@ def validate(model, dl_val, criterion, device):
     scores, loss_total = BatchScores(), 0.0
     with torch.inference_mode():
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
-            text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None))
+            text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
+                                                           audio_encoder=getattr(model, "audio_encoder", None))
             logits = model(text, audio, padding_mask)
             loss_total += criterion(logits.permute(0, 2, 1), emotion).item()
             scores.update(logits, emotion)
