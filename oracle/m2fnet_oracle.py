@@ -84,55 +84,212 @@ def attention(q: Tensor, k: Tensor, v: Tensor, key_pad: Tensor, n_head: int,
 
 
 # --------------------------------------------------------------------------------------
+# bf16-mode emulation (opt-in: loss_and_grads(..., rounding=Bf16Rounding()))
+# --------------------------------------------------------------------------------------
+class Bf16Rounding:
+    """Where bf16 mode rounds to bf16.  The emulation computes in float64 and rounds, round to nearest even on the fp32 value
+    (m2f_bf16_bits, csrc/common.h:72-75: a plain (__bf16) cast), exactly the operands the kernels round; everything else -
+    bias, ReLU, residual, gate, LayerNorm, softmax, criterion, the sums - is unrounded.  One attribute per rule, all on by
+    default; switching one off is what tests/test_bf16_emulation_cpu.py does to show the GPU bound would see it.
+    Paths below are relative to multimodal-emotion-recognition_amd/csrc.
+
+    GEMMs (every nn.Linear / in-projection / out-projection, the FAM's two-segment cat(relu(x), text) operand, the classifier):
+      fwd_x     forward A operand (activation) rounded: the producer writes a bf16 shadow at the same element index
+                (gemm.hip:353,360, rowops / attention epilogues), GEMMs stage from it ("bf16 operand
+                shadows"); a launch staged from fp32 rounds on the way into LDS (gemm.hip:208,215): the same value.
+      fwd_w     forward B operand (weight) rounded: parameter shadow W [rows][pad8(cols)] (m2f_cast_t_kernel, or
+                m2f_adam_shadow_kernel after a FusedAdam step).  Bias, ReLU, residual, gate: fp32 after the product
+                (gemm.hip:229).
+      dgrad_dy  dX = bf16(dY) . bf16(W): dY from the shadow its producer wrote (LayerNorm backward, attention backward, the
+                gated dgrad epilogue), ...
+      dgrad_w   ... and W from the transposed parameter shadow W^T [cols][pad8(rows)] (the NN dgrad rerouted through it).
+      wgrad_dy  dW = bf16(dY)^T . bf16(X): the weight-gradient table launch reads the row-major shadows (gemm_p8.h,
+      wgrad_x   gemm_ring.h TABLE form); the [T, C] criterion gradient is cast to 8-column bf16 rows in front of it (plan.hip:949).
+      bias_dy   bias gradient = column sum of bf16(dY): the table forms sum the bf16 fragments they stage (gemm_p8.h:395,
+                gemm_ring.h:663), the bf16-source grouped form its staged bf16 tile (gemm.hip:829,914).  Finding: the
+                fp32-SOURCE grouped form sums the fp32 values before it rounds them (gemm.hip:185-191, a contract
+                tests/test_kernels_gpu.py::test_gemm_layouts pins); with M2F_WGRAD_TABLE=0 it takes the one weight-gradient
+                problem whose dY has no shadow, the classifier's last Linear (the [T, C] criterion gradient), so
+                wgrad_table=False (that variant) sums that bias gradient from the fp32 dY.
+      skinny    the classifier's last Linear ([T, C] problems, C <= 8) runs on the skinny kernels, which round both operands
+                as the MFMA kernels do (skinny.hip:16-18,192: shadows when every operand has one, else r16): off = its
+                forward and its input gradient are not rounded (its weight gradient stays in the table launch).
+      The criterion gradient itself is fp32 (m2f_ce_kernel) and is rounded only where it enters these products.
+
+    Dialogue attention, L <= 64 (attention.hip, AttnBatch::bf16_math = 63 in bf16 mode, plan.hip:824-826):
+      bit 1 (attention.hip:129,337,388): Q K^T and dO V^T on the bf16 MFMA - both operands rounded on the way in
+                (slab8_bf16, attention.hip:42-50), whatever the slabs hold; the scale 1/sqrt(hd) is applied to the fp32
+                product afterwards (attention.hip:113,151: s * scale; backward: p * (dp - delta) * scale).
+      bits 2/4/8 (Q/K/V, forward and backward) and 16/32 (dO/O, backward) (attention.hip:35,662): the slabs are staged
+                from the operands' bf16 shadows, so EVERY use of the operand sees it rounded: P V (forward), dQ = dS K,
+                dK = dS^T Q, dV = P^T dO and delta = sum(dO * O) (attention.hip:264-275).  Only on the fast staging path
+                (slab_fast_ok, attn_slab.h:68-71, with slab_shadow: hd % 4 == 0 and head dim padded to 16 <= 128; backward
+                also attn_bwd_fast, attention.hip:601-603: 5 Lp (W + 2) + Lp floats <= 160 KiB).  Otherwise the slabs are
+                fp32 and only the bit-1 contractions round (finding: e.g. head dim 75 of c2_slice's audio encoder, 15 of
+                tiny_odd_heads: there V, and in the backward K, Q, dO (for dQ/dK/dV) and O stay fp32).
+      P, dS, the softmax and the row sums are fp32.  attn_q / attn_k / attn_v / attn_do / attn_o switch one operand's
+      rounding (everywhere it is rounded); attn = False switches all of them (M2F_ATTN_BF16=0).  The mode is decided per
+      attention problem from its own head dim (a merged launch takes the widest head dim for attn_bwd_fast: it only
+      matters at Lp = 64 with head dims 113..128 in one launch and others narrower, which no test case has).
+    Plans with L > 64 (attention_dlong.hip; picked by the plan's L, plan.hip:1329-1330, packed or not): no attention
+    rounding, those kernels read fp32 operands.  The L here is the batch's L (the shape bucket rounds up to a multiple of 16,
+    which does not cross 64).
+    LayerNorm, the residual stream, the criterion and Adam: fp32, no rounding.
+    """
+    GEMM_RULES = ("fwd_x", "fwd_w", "dgrad_dy", "dgrad_w", "wgrad_dy", "wgrad_x", "bias_dy", "skinny")
+    ATTN_RULES = ("attn_q", "attn_k", "attn_v", "attn_do", "attn_o")
+    RULES = GEMM_RULES + ATTN_RULES
+
+    def __init__(self, attn: bool = True, wgrad_table: bool = True, jitter: float = 0.0, seed: int = 0, **off):
+        for r in self.RULES:
+            setattr(self, r, True)
+        self.attn, self.wgrad_table = bool(attn), bool(wgrad_table)
+        # jitter > 0: every value is multiplied by (1 + jitter * N(0, 1)) just before it is rounded - a stand-in for the fp32
+        # summation noise of the kernels, to measure how stable a case's rounding decisions are (the emulation against itself)
+        self.jitter = float(jitter)
+        self._gen = torch.Generator().manual_seed(seed)
+        for r, v in off.items():
+            if r not in self.RULES:
+                raise ValueError(f"unknown rounding rule {r!r}")
+            setattr(self, r, bool(v))
+
+    def r(self, x: Tensor, on: bool) -> Tensor:
+        if on and self.jitter:
+            x = x * (1.0 + self.jitter * torch.randn(x.shape, generator=self._gen, dtype=x.dtype))
+        return _bf16(x, on)
+
+
+def _bf16(x: Tensor, on: bool = True) -> Tensor:
+    """Round to bf16 (nearest even, from the fp32 value as m2f_bf16_bits does) and back to x's dtype."""
+    return x.to(torch.float32).to(torch.bfloat16).to(x.dtype) if on else x
+
+
+class _Linear16(torch.autograd.Function):
+    """y = bf16(x) bf16(W)^T + b; backward dX = bf16(dY) bf16(W), dW = bf16(dY)^T bf16(X), db = sum bf16(dY)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, rnd, skinny):
+        sk = rnd.skinny or not skinny
+        ctx.rnd, ctx.sk, ctx.skinny = rnd, sk, skinny
+        ctx.save_for_backward(x, w)
+        y = rnd.r(x, rnd.fwd_x and sk) @ rnd.r(w, rnd.fwd_w and sk).t()
+        return y if b is None else y + b
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        r, sk = ctx.rnd, ctx.sk
+        dx = r.r(dy, r.dgrad_dy and sk) @ r.r(w, r.dgrad_w and sk)
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        dw = r.r(dy2, r.wgrad_dy).t() @ r.r(x.reshape(-1, x.shape[-1]), r.wgrad_x)
+        db = r.r(dy2, r.bias_dy and (r.wgrad_table or not ctx.skinny)).sum(dim=0)
+        return dx, dw, db, None, None
+
+
+class _Attn16(torch.autograd.Function):
+    """Dialogue attention as attention.hip computes it in bf16 mode (see Bf16Rounding); [B, L, E] in and out."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_pad, n_head, rnd):
+        B, L, E = q.shape
+        hd = E // n_head
+        W, Lp = (hd + 15) // 16 * 16, 16 * ((L + 15) // 16)
+        fast = hd % 4 == 0 and W <= 128                                   # staged from the shadows (forward)
+        ctx.bwd_fast = fast and (5 * Lp * (W + 2) + Lp) * 4 <= 160 * 1024
+        heads = lambda t: t.reshape(B, L, n_head, hd).permute(0, 2, 1, 3)
+        qh, kh, vh = heads(q), heads(k), heads(v)
+        scale = 1.0 / math.sqrt(hd)
+        s = (rnd.r(qh, rnd.attn_q) @ rnd.r(kh, rnd.attn_k).transpose(-1, -2)) * scale
+        s = s.masked_fill(key_pad[:, None, None, :], float("-inf"))
+        s = s - s.max(dim=-1, keepdim=True).values
+        p = torch.exp(s)
+        p = p / p.sum(dim=-1, keepdim=True)
+        o = p @ rnd.r(vh, rnd.attn_v and fast)
+        ctx.save_for_backward(qh, kh, vh, p, o)
+        ctx.rnd, ctx.scale, ctx.shape = rnd, scale, (B, L, n_head, hd)
+        return o.permute(0, 2, 1, 3).reshape(B, L, E)
+
+    @staticmethod
+    def backward(ctx, do):
+        qh, kh, vh, p, o = ctx.saved_tensors
+        r, f = ctx.rnd, ctx.bwd_fast
+        B, L, H, hd = ctx.shape
+        doh = do.reshape(B, L, H, hd).permute(0, 2, 1, 3)
+        dp = r.r(doh, r.attn_do) @ r.r(vh, r.attn_v).transpose(-1, -2)           # bit 1: always rounded
+        dor = r.r(doh, r.attn_do and f)
+        delta = (dor * r.r(o, r.attn_o and f)).sum(dim=-1, keepdim=True)
+        ds = p * (dp - delta) * ctx.scale
+        dq = ds @ r.r(kh, r.attn_k and f)
+        dk = ds.transpose(-1, -2) @ r.r(qh, r.attn_q and f)
+        dv = p.transpose(-1, -2) @ dor
+        back = lambda t: t.permute(0, 2, 1, 3).reshape(B, L, H * hd)
+        return back(dq), back(dk), back(dv), None, None, None
+
+
+def _lin(x: Tensor, w: Tensor, b: Optional[Tensor], rnd: Optional[Bf16Rounding], skinny: bool = False) -> Tensor:
+    return linear(x, w, b) if rnd is None else _Linear16.apply(x, w, b, rnd, skinny)
+
+
+def _attn(q, k, v, key_pad, n_head, rnd: Optional[Bf16Rounding], return_probs: bool = False):
+    if rnd is None:
+        return attention(q, k, v, key_pad, n_head, return_probs)
+    if not rnd.attn or q.shape[1] > 64:
+        return attention(q, k, v, key_pad, n_head, return_probs)
+    o = _Attn16.apply(q, k, v, key_pad, n_head, rnd)
+    return (o, None) if return_probs else o
+
+
+# --------------------------------------------------------------------------------------
 # blocks
 # --------------------------------------------------------------------------------------
-def encoder_layer(x: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor, n_head: int) -> Tensor:
+def encoder_layer(x: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor, n_head: int,
+                  rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
     """Post-LN TransformerEncoderLayer (norm_first=False, ReLU), dropout = identity.
 
     x <- LN1(x + SA(x)); x <- LN2(x + W2 relu(W1 x + b1) + b2)   
     """
     E = x.shape[-1]
-    qkv = linear(x, sd[pre + "self_attn.in_proj_weight"], sd[pre + "self_attn.in_proj_bias"])
+    qkv = _lin(x, sd[pre + "self_attn.in_proj_weight"], sd[pre + "self_attn.in_proj_bias"], rnd)
     q, k, v = qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:]
-    a = attention(q, k, v, key_pad, n_head)
-    a = linear(a, sd[pre + "self_attn.out_proj.weight"], sd[pre + "self_attn.out_proj.bias"])
+    a = _attn(q, k, v, key_pad, n_head, rnd)
+    a = _lin(a, sd[pre + "self_attn.out_proj.weight"], sd[pre + "self_attn.out_proj.bias"], rnd)
     x = layer_norm(x + a, sd[pre + "norm1.weight"], sd[pre + "norm1.bias"])
-    h = torch.relu(linear(x, sd[pre + "linear1.weight"], sd[pre + "linear1.bias"]))
-    h = linear(h, sd[pre + "linear2.weight"], sd[pre + "linear2.bias"])
+    h = torch.relu(_lin(x, sd[pre + "linear1.weight"], sd[pre + "linear1.bias"], rnd))
+    h = _lin(h, sd[pre + "linear2.weight"], sd[pre + "linear2.bias"], rnd)
     return layer_norm(x + h, sd[pre + "norm2.weight"], sd[pre + "norm2.bias"])
 
 
 def encoder_stack(x: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor, n_head: int,
-                  n_layers: int) -> Tensor:
+                  n_layers: int, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
     """nn.TransformerEncoder(layer, num_layers, norm): layers then the final LayerNorm."""
     for l in range(n_layers):
-        x = encoder_layer(x, sd, f"{pre}layers.{l}.", key_pad, n_head)
+        x = encoder_layer(x, sd, f"{pre}layers.{l}.", key_pad, n_head, rnd)
     return layer_norm(x, sd[pre + "norm.weight"], sd[pre + "norm.bias"])
 
 
 def fam_layer(text: Tensor, audio: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor,
-              n_head: int, inter: Optional[dict] = None) -> Tensor:
+              n_head: int, inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
     """FusionAttentionModule.forward (src/model.py:13-20): Q = V = text, K = audio."""
     E = text.shape[-1]
     w = sd[pre + "multihead_attention.in_proj_weight"]
     b = sd[pre + "multihead_attention.in_proj_bias"]
-    q = linear(text, w[:E], b[:E])
-    k = linear(audio, w[E:2 * E], b[E:2 * E])
-    v = linear(text, w[2 * E:], b[2 * E:])
-    a, p = attention(q, k, v, key_pad, n_head, return_probs=True)
-    x = linear(a, sd[pre + "multihead_attention.out_proj.weight"],
-               sd[pre + "multihead_attention.out_proj.bias"])
-    y = torch.relu(linear(torch.relu(torch.cat((x, text), dim=2)),
-                          sd[pre + "linear.weight"], sd[pre + "linear.bias"]))
+    q = _lin(text, w[:E], b[:E], rnd)
+    k = _lin(audio, w[E:2 * E], b[E:2 * E], rnd)
+    v = _lin(text, w[2 * E:], b[2 * E:], rnd)
+    a, p = _attn(q, k, v, key_pad, n_head, rnd, return_probs=True)
+    x = _lin(a, sd[pre + "multihead_attention.out_proj.weight"],
+             sd[pre + "multihead_attention.out_proj.bias"], rnd)
+    y = torch.relu(_lin(torch.relu(torch.cat((x, text), dim=2)),
+                        sd[pre + "linear.weight"], sd[pre + "linear.bias"], rnd))
     if inter is not None:
         inter.update(q=q, k=k, v=v, p=p, attn=a, x=x, y=y)
     return y
 
 
 def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Tensor,
-            inter: Optional[dict] = None) -> Tensor:
+            inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
     """M2FNet.forward (src/model.py:102-145) with every dropout as identity
-    (eval mode, or train mode with model.dropout = 0.0).
+    (eval mode, or train mode with model.dropout = 0.0).  rnd: see Bf16Rounding (None = no rounding).
 
     text [B,L,d_t], audio [B,L,d_a] fp32; key_pad bool [B,L] (True = pad) -> logits [B,L,C].
     """
@@ -146,13 +303,13 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
     if a_on:
         for e in range(_get(A, "n_transformers")):                                 # src/model.py:106-107
             audio = audio + encoder_stack(audio, sd, f"audio_encoders.{e}.", key_pad,
-                                          _get(A, "n_head"), _get(A, "n_encoder_layers"))
-        audio = linear(audio, sd["audio_proj.weight"], sd["audio_proj.bias"])      # :111-113
+                                          _get(A, "n_head"), _get(A, "n_encoder_layers"), rnd)
+        audio = _lin(audio, sd["audio_proj.weight"], sd["audio_proj.bias"], rnd)      # :111-113
     if t_on:
         for e in range(_get(Tx, "n_transformers")):                                # :118-119
             text = text + encoder_stack(text, sd, f"text_encoders.{e}.", key_pad,
-                                        _get(Tx, "n_head"), _get(Tx, "n_encoder_layers"))
-        text = linear(text, sd["text_proj.weight"], sd["text_proj.bias"])          # :123-125
+                                        _get(Tx, "n_head"), _get(Tx, "n_encoder_layers"), rnd)
+        text = _lin(text, sd["text_proj.weight"], sd["text_proj.bias"], rnd)          # :123-125
     if inter is not None:
         inter["audio_proj"] = audio if a_on else None
         inter["text_proj"] = text if t_on else None
@@ -160,7 +317,7 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
     if f_on:
         for i in range(_get(F, "n_layers")):                                       # :129-131
             li = {} if inter is not None else None
-            text = fam_layer(text, audio, sd, f"fusion_layers.{i}.", key_pad, _get(F, "n_head"), li)
+            text = fam_layer(text, audio, sd, f"fusion_layers.{i}.", key_pad, _get(F, "n_head"), li, rnd)
             if inter is not None:
                 inter[f"fam{i}"] = li
         x = torch.cat((audio, text), dim=2)                                        # :134  (audio, text)
@@ -170,13 +327,13 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
         x = text if t_on else audio
 
     n_cls = _get(C, "n_layers")                                                    # :89-100
-    x = linear(x, sd["output_layer.0.weight"], sd["output_layer.0.bias"])
+    x = _lin(x, sd["output_layer.0.weight"], sd["output_layer.0.bias"], rnd)
     idx = 0
     for _ in range(max(n_cls - 2, 0)):
         idx += 2
-        x = linear(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"])
+        x = _lin(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"], rnd)
     idx += 3
-    return linear(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"])
+    return _lin(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"], rnd, skinny=True)
 
 
 # --------------------------------------------------------------------------------------
@@ -268,15 +425,22 @@ def collate(dialogues: Sequence[Dict[str, Tensor]]) -> Dict[str, Tensor]:
 
 
 def loss_and_grads(sd: Dict[str, Tensor], cfg, text, audio, key_pad, target,
-                   class_weight: Optional[Tensor] = None):
-    """forward + criterion + backward; returns (logits, loss, {name: grad}) for unique tensors."""
+                   class_weight: Optional[Tensor] = None, rounding: "Optional[Bf16Rounding]" = None):
+    """forward + criterion + backward; returns (logits, loss, {name: grad}) for unique tensors.
+
+    rounding (a Bf16Rounding): emulate bf16 mode - everything in float64, rounded to bf16 where the kernels round; the
+    results are float64.  None (the default): the plain oracle."""
+    if rounding is not None:
+        text, audio = text.double(), audio.double()
+        class_weight = None if class_weight is None else class_weight.double()
     leaves: Dict[int, Tensor] = {}
     sd2 = {}
     for k, v in sd.items():
         if id(v) not in leaves:
-            leaves[id(v)] = v.detach().clone().requires_grad_(True)
+            t = v.detach().clone() if rounding is None else v.detach().double()
+            leaves[id(v)] = t.requires_grad_(True)
         sd2[k] = leaves[id(v)]
-    logits = forward(sd2, cfg, text, audio, key_pad)
+    logits = forward(sd2, cfg, text, audio, key_pad, rnd=rounding)
     loss = cross_entropy(logits, target, class_weight)
     loss.backward()
     grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in sd2.items()}
