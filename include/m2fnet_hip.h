@@ -381,6 +381,31 @@ int m2f_w2v_pos_conv(int B, int S, int d, int groups, int K, const float* x, con
 /* out[b, c] = mean of x[b*S + t, c] over t < lengths[b] (embeddings.py:80-85; fixed summation order, lengths[b] <= 0 gives zeros). */
 int m2f_w2v_masked_mean(int B, int S, int d, const float* x, const int32_t* lengths, float* out, m2f_stream_t stream);
 
+/* ---- audio_mel encoder (multimodal-emotion-recognition_amd/mel_resnet.py) ---------------------------------------------------------
+ * The reference's third per-utterance feature extractor (src/feature_extractors/audio_mel): a log-mel spectrogram of each utterance,
+ * min-max normalised (and, as its PNG cache returns it, quantised to 8-bit levels), as a [3, 1001, 128] image into torchvision's
+ * resnet18, then ReLU -> Linear(1000, 300) -> L2 normalise.  Activations are NHWC; all entries are deterministic and per utterance.
+ *
+ * Front end: wave [B, N] fp32 (padded batch), lengths [B] int32 on the device (<= N, <= 160,000 samples); basis [400][402] = Hann
+ * window x (cos | sin) of the 201 DFT bins; fbT [201][128] the mel filters (L1-normalised rows) transposed.  img [B, 1001, 128] fp32:
+ * frames 0 .. len / 160 normalised to [0, 1] (floor(v * 255) / 255 when png_levels), zero rows behind them; a silent clip or a
+ * flat spectrogram gives all zeros.  scratch: m2f_mel_frontend_scratch_floats(B) floats. */
+int m2f_mel_frontend(int B, int N, const float* wave, const int32_t* lengths, const float* basis, const float* fbT, int png_levels,
+                     float* scratch, float* img, m2f_stream_t stream);
+int64_t m2f_mel_frontend_scratch_floats(int B);
+/* Stem: 7x7/2 conv of img (one channel: the three identical input channels folded) + BatchNorm folded into w [49][64] (tap-major) and
+ * bias [64] + ReLU + 3x3/2 max pool -> [B, 251, 32, 64] NHWC, exactly one of out32 (fp32) / out16 (bf16 bits).  fp32 arithmetic. */
+int m2f_mel_stem(int B, const float* img, const float* w, const float* bias, float* out32, uint16_t* out16, m2f_stream_t stream);
+/* Convolution (implicit GEMM, no im2col): x [B, H, W, Cin], w [Cout][ks][ks][Cin] (BatchNorm folded), pad ks / 2, out / res
+ * [B, Ho, Wo, Cout]: out = act(conv(x) + bias (+ res)), act = ReLU when relu.  bf16 = 0: x, w, res, out fp32 (fp32 MFMA); bf16 = 1:
+ * x, w, res bf16 bits, fp32 accumulation, out bf16 bits (fp32 when out_fp32).  Cin % 32 == 0, Cout % 64 == 0, ks 1 or 3, stride 1 or 2. */
+int m2f_mel_conv(int B, int H, int W, int Cin, int Cout, int ks, int stride, const void* x, const void* w, const float* bias,
+                 const void* res, void* out, int bf16, int out_fp32, int relu, m2f_stream_t stream);
+/* Head: x [B, HW, C] (bf16 bits when bf16_in) -> mean over HW -> ReLU(. W1^T + b1) -> . W2^T + b2 -> / max(||.||, 1e-12): out [B, N2].
+ * w1t [C][N1], w2t [N1][N2] (transposed Linear weights); fp32, fixed summation orders. */
+int m2f_mel_head(int B, int HW, int C, const void* x, int bf16_in, const float* w1t, const float* b1, int N1, const float* w2t,
+                 const float* b2, int N2, float* out, m2f_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

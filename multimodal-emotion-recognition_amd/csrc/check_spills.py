@@ -18,7 +18,9 @@ ring = len(sys.argv) > 2 and sys.argv[1] == "--ring"
 dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
 # --w2v <remarks>: the wav2vec2 front end (audio_conv.hip) - the same rule for its kernels (the positional convolution's accumulators)
 w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
-path = sys.argv[2] if (ring or dlong or w2v) else sys.argv[1]
+# --mel <remarks>: the audio_mel encoder (mel_resnet.hip) - the same rule for its kernels (the convolution's accumulators, the STFT sums)
+mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
+path = sys.argv[2] if (ring or dlong or w2v or mel) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -32,8 +34,8 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-if dlong or w2v:
-    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_"
+if dlong or w2v or mel:
+    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_"
     kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
         sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")

@@ -360,3 +360,25 @@ size_t m2f_w2v_pos_conv_lds(int CG, int K, int bf16);
 hipError_t m2f_launch_w2v_pos_conv(const float* x, const int* lengths, int B, int S, int d, int groups, int K, const void* w, const float* bias,
                                    float* out, int bf16, hipStream_t stream);
 hipError_t m2f_launch_w2v_masked_mean(const float* x, const int* lengths, int B, int S, int d, float* out, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
+// audio_mel encoder (mel_resnet.hip; mel_resnet.py drives it): log-mel front end, ResNet18 on NHWC activations, projection head
+// ------------------------------------------------------------------------------------------------
+#define M2F_MEL_NFFT 400
+#define M2F_MEL_HOP 160
+#define M2F_MEL_BANDS 128
+#define M2F_MEL_FRAMES 1001                  // 1 + 160000 / 160: 10 s at 16 kHz
+#define M2F_MEL_LOG_EPS 2.220446049250313e-16f
+#define M2F_MEL_C0 64                        // stem channels
+#define M2F_MEL_STEM_H 501
+#define M2F_MEL_STEM_W 64
+#define M2F_MEL_POOL_H 251
+#define M2F_MEL_POOL_W 32
+hipError_t m2f_launch_mel_frontend(const float* wave, const int* lengths, int B, int N, const float* basis, const float* fbT, int levels,
+                                   float* peak, float* logmel, float* img, hipStream_t stream);
+hipError_t m2f_launch_mel_stem(const float* img, int B, const float* w, const float* bias, float* out32, uint16_t* out16,
+                               hipStream_t stream);
+hipError_t m2f_launch_mel_conv(const void* x, const void* w, const float* bias, const void* res, void* out, int B, int H, int W, int Cin,
+                               int Cout, int ks, int stride, int bf16, int out32, int relu, hipStream_t stream);
+hipError_t m2f_launch_mel_head(const void* x, int in16, int B, int HW, int C, const float* w1t, const float* b1, int N1, const float* w2t,
+                               const float* b2, int N2, float* out, hipStream_t stream);

@@ -85,10 +85,28 @@ def build_text_encoder(te_cfg, d_text, device):
     return enc.to(device).eval()
 
 
-def build_audio_encoder(ae_cfg, d_audio, device):
-    """`runtime.audio_encoder`: {enabled, precision: fp32 | bf16, geometry: base | a dict of Wav2Vec2Config fields, checkpoint: path of a
-    state_dict in transformers.Wav2Vec2Model or torchaudio wav2vec2 key layout (the encoder of the reference's AudioERC) or null =
-    random weights, wav_dir}."""
+def build_audio_encoder(ae_cfg, d_audio, device, n_head=None):
+    """`runtime.audio_encoder`: {enabled, model: wav2vec2 (default) | mel_resnet18, precision: fp32 | bf16, wav_dir, checkpoint}.
+    wav2vec2: geometry: base | a dict of Wav2Vec2Config fields; checkpoint: path of a state_dict in transformers.Wav2Vec2Model or
+    torchaudio wav2vec2 key layout (the encoder of the reference's AudioERC) or null = random weights.
+    mel_resnet18: the reference's audio_mel extractor (300-wide rows, so model.AUDIO.embedding_size must be 300 and n_head must
+    divide it); checkpoint: the reference's checkpoints/audio_mel/checkpoint.pth or a bare state_dict in its key layout; png_levels:
+    True (default: the 8-bit levels of the reference's spectrogram cache) | False."""
+    kind = ae_cfg.get("model", "wav2vec2")
+    if kind == "mel_resnet18":
+        from mer_amd.mel_resnet import EMBED, MelResNetEncoder
+        if d_audio != EMBED:
+            raise ValueError(f"runtime.audio_encoder.model mel_resnet18 produces {EMBED}-wide rows but model.AUDIO.embedding_size is "
+                             f"{d_audio}: set it to {EMBED}")
+        if n_head is not None and EMBED % int(n_head):
+            raise ValueError(f"runtime.audio_encoder.model mel_resnet18: model.AUDIO.n_head {n_head} does not divide {EMBED}")
+        enc = MelResNetEncoder(precision=ae_cfg.get("precision", "bf16"), png_levels=bool(ae_cfg.get("png_levels", True)))
+        ck = ae_cfg.get("checkpoint", None)
+        if ck:
+            enc.load_state_dict(torch.load(os.path.abspath(ck), map_location="cpu"))
+        return enc.to(device).eval()
+    if kind != "wav2vec2":
+        raise ValueError(f"runtime.audio_encoder.model {kind!r}: wav2vec2 or mel_resnet18")
     from mer_amd.wav2vec2 import Wav2Vec2Encoder, base_config
     geo = ae_cfg.get("geometry", "base")
     cfg = base_config()
@@ -200,7 +218,8 @@ def main(config=None):
         object.__setattr__(model, "text_encoder", build_text_encoder(te_cfg, config.model.TEXT.embedding_size, device))
     if ae_on:
         # the audio rows are computed in the loop from waveforms; built outside the fusion model, like the text encoder
-        object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device))
+        object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
+                                                                             n_head=config.model.AUDIO.n_head))
     criterion = build_criterion(config.solver, train_set, device)
     optimizer = FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
     if world > 1:
