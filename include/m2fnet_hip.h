@@ -51,7 +51,9 @@ enum {
     M2F_BUF_DLOGITS = 7,    /* float [B*L, cls_out]  d loss / d logits (written by m2f_loss, or by host) */
     M2F_BUF_FAM0_OUT = 8,   /* float [B*L, pad8(d_fam)] first fusion layer output (kernel-level parity)  */
     M2F_BUF_CU_SEQLENS = 9, /* int32 [B+1]           input of PACKED plans: dialogue b owns token rows cu[b] .. cu[b+1]-1 */
-    M2F_BUF_COUNT = 10
+    M2F_BUF_DTEXT = 10,     /* float [B*L, pad8(d_text)]  output d loss / d text (text.grad, src/model.py:115-119; train plans, m2f_plan_backward_outputs) */
+    M2F_BUF_DAUDIO = 11,    /* float [B*L, pad8(d_audio)] output d loss / d audio (audio.grad, src/model.py:103-107; same rows as M2F_BUF_AUDIO)  */
+    M2F_BUF_COUNT = 12
 };
 
 const char* m2f_last_error(void);
@@ -116,6 +118,17 @@ int m2f_forward(m2f_plan* plan, m2f_stream_t stream);
 int m2f_loss(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, m2f_stream_t stream);
 /* loss.backward() (src/train.py:230): consumes M2F_BUF_DLOGITS, OVERWRITES the flat gradient buffer. */
 int m2f_backward(m2f_plan* plan, m2f_stream_t stream);
+/* What m2f_backward computes (loss.backward() reaching `text` / `audio` as autograd leaves, src/model.py:106-119, and / or the
+ * parameters).  input_mask: 1 = d loss / d text into M2F_BUF_DTEXT, 2 = d loss / d audio into M2F_BUF_DAUDIO (token rows as the
+ * input staging buffers; an enabled modality only): the backward chain runs on through the QKV in-projection of the first encoder
+ * layer of stack 0 (the outer skip x + enc(x) included) - one more dgrad launch behind the branch chains, both modalities grouped.
+ * param_grads = 0: no weight gradients, no LayerNorm-parameter reduces, the flat gradient buffer is never written (a train plan
+ * created with grads = NULL starts so and cannot switch to 1); m2f_step, m2f_step_part, m2f_plan_fused_adam_setup and
+ * m2f_plan_grad_bf16 then fail.  Default (0, 1): the backward of m2f_plan_create as before, launch for launch; the parameter
+ * gradients are bit-identical with input gradients on.  A change rebuilds every launch list in the same workspace and destroys the
+ * captured graphs (fused-optimizer and bf16-gradient setups must be repeated); call it between steps, never between a forward and
+ * its backward. */
+int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,

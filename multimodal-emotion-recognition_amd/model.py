@@ -103,17 +103,22 @@ class FusionAttentionModule(nn.Module):
 
 
 class _Anchor(torch.autograd.Function):
-    """Connects the plan's forward/backward to autograd through ONE dummy leaf: ``loss.backward()``
-    (reference src/train.py:230) reaches ``backward`` below, which runs the HIP backward launch list and
-    publishes the flat gradient buffer as the parameters' ``.grad`` views."""
+    """Connects the plan's forward/backward to autograd: ``text`` and ``audio`` are real inputs (as in the reference, where they are
+    ordinary autograd leaves or outputs of whatever made them), the dummy leaf ``anchor`` stands for the parameters.
+    ``loss.backward()`` (reference src/train.py:230) reaches ``backward`` below, which runs the HIP backward launch list, publishes
+    the flat gradient buffer as the parameters' ``.grad`` views (when the plan computes them) and returns fresh copies of the
+    input gradients the plan computed."""
 
     @staticmethod
-    def forward(ctx, anchor, model, plan):
+    def forward(ctx, anchor, text, audio, model, plan):
         eng = model._engine
         if plan.cfg.dropout > 0.0 and plan.train:
             runtime.check(runtime.lib().m2f_rng_advance(eng.rng.data_ptr(), runtime.stream_ptr()), "m2f_rng_advance")
         logits = plan.forward()
         ctx.model, ctx.plan, ctx.version = model, plan, plan.version
+        # the token-row map of THIS batch (a later forward on another instance cannot touch it, a packed plan re-makes it per batch)
+        ctx.rows = (plan._dst, plan._valid, (plan.in_B, plan.in_L))
+        ctx.in_shapes = tuple((x.shape, x.dtype) if isinstance(x, torch.Tensor) else None for x in (text, audio))
         return logits.clone()
 
     @staticmethod
@@ -128,8 +133,18 @@ class _Anchor(torch.autograd.Function):
         plan.set_dlogits(dlogits)
         plan.backward()
         plan.release()                                    # (a second backward through the same graph re-runs on the same buffers)
-        ctx.model._engine.publish_grads()
-        return None, None, None
+        if plan.param_grads:
+            ctx.model._engine.publish_grads()
+        dst, valid, shape = ctx.rows
+        grads = []
+        for i, bit in ((1, runtime.IN_TEXT), (2, runtime.IN_AUDIO)):
+            if not (ctx.needs_input_grad[i] and plan.input_mask & bit):
+                grads.append(None)
+                continue
+            g = plan.input_grad(bit, dst, valid, shape)
+            xshape, xdtype = ctx.in_shapes[i - 1]
+            grads.append(g.to(xdtype).reshape(xshape))
+        return None, grads[0], grads[1], None, None
 
 
 class _Engine:
@@ -220,10 +235,13 @@ class _Engine:
         Bb = 1 << max(B - 1, 0).bit_length() if B <= 8 else (B + 7) // 8 * 8
         return Bb, Lb
 
-    def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None) -> runtime.Plan:
+    def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None,
+             outputs: Tuple[int, bool] = (0, True)) -> runtime.Plan:
         """valid: number of valid utterances of the batch (packed mode) - the plan then holds that many token rows (rounded up to
         a multiple of 64, plus one row per filler dialogue and one spare) instead of B x L slots; batches that are at least
-        85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64)."""
+        85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64).
+        outputs: what a backward computes - (input_mask, parameter gradients) of m2f_plan_backward_outputs; part of the key, so a
+        plan of one setting never flips to another (train_step always uses the default (0, True))."""
         b_in, l_in = B, L
         if self.shape_buckets:
             B, L = self.bucket(B, L)
@@ -236,7 +254,8 @@ class _Engine:
             Tb = (need + 63) // 64 * 64
             if long or Tb <= 0.85 * B * L:
                 T = min(max(Tb, B), B * L)            # (every dialogue full: no spare row - runtime.Plan handles that)
-        base = (B, L, T, want_backward, dropout_active, self.precision)
+        outputs = (int(outputs[0]), bool(outputs[1]))
+        base = (B, L, T, want_backward, dropout_active, self.precision) + (() if outputs == (0, True) else (outputs,))
         inst, key, pl, oldest = 0, None, None, None
         while True:                                       # first instance of this shape that no live autograd graph owns
             key = base + (inst,)
@@ -256,19 +275,22 @@ class _Engine:
                 cfg = M2FConfig(**{**cfg.__dict__, "dropout": 0.0})
             # the C side couples "keeps a backward list" and "dropout active" in its train flag
             train = want_backward or dropout_active
-            if train:
+            pgrads = train and outputs[1]                 # (input gradients only: the plan gets no gradient buffer at all)
+            if pgrads:
                 self.ensure_grad()
             self._evict(max(self.max_plans, 1) - 1, self.max_plan_bytes)
-            pl = runtime.Plan(cfg, B, L, self.precision, train, self.flat, self.flat_grad_ext if train else None, self.rng, T=T,
+            pl = runtime.Plan(cfg, B, L, self.precision, train, self.flat, self.flat_grad_ext if pgrads else None, self.rng, T=T,
                               param_shadow=self.wshadow)
             pl._on_cast = self.mark_shadows_fresh
+            if train and outputs != (0, True):
+                pl.backward_outputs(*outputs)
             self.plans[key] = pl
             self._evict(max(self.max_plans, 1), self.max_plan_bytes, protect=key)
         else:
             self.plans.move_to_end(key)
             self._evict(max(self.max_plans, 1), self.max_plan_bytes, protect=key)      # (the caps may have been lowered since)
         pl.params_fresh(self.shadows_fresh())
-        if pl.train:
+        if pl.train and pl.param_grads:
             self._arm_grad_bf16(pl)
         return pl
 
@@ -334,7 +356,14 @@ class M2FNet(nn.Module):
     Batches whose longest dialogue has more than 64 utterances always run on a packed plan (long-dialogue attention
     kernels), whatever ``packed`` says: their logits at pad slots are zero, where the reference computes numbers that its
     loss and metrics mask out (valid slots agree).  Each backward OVERWRITES the gradients (the reference zeroes them every
-    step, ``src/train.py:227``), so accumulating over several backward calls needs a caller-side buffer."""
+    step, ``src/train.py:227``), so accumulating over several backward calls needs a caller-side buffer.
+
+    ``text`` and ``audio`` are autograd inputs as in the reference: when they require grad, ``backward`` gives them (fresh tensors of
+    their shape and dtype) d loss / d input computed by the gfx950 backward, so an adapter or encoder in front of the model trains.
+    Padded plans match the reference at every slot, pad slots included; packed and long-dialogue plans at valid slots, with exact
+    zeros at pad slots (their logits are zero there, see above).  When NO parameter requires grad (``requires_grad_(False)``:
+    saliency, attribution, adversarial inputs) the backward computes the input gradients only and every ``p.grad`` is left as it
+    was; a partly frozen model computes and publishes all parameter gradients as before."""
 
     def __init__(self, config, precision: Optional[str] = None, shape_buckets: Optional[bool] = None,
                  packed: Optional[bool] = None):
@@ -404,12 +433,23 @@ class M2FNet(nn.Module):
     def forward(self, text, audio, mask):
         eng = self.engine(mask.device)
         B, L = mask.shape
-        want_bwd = torch.is_grad_enabled() and any(p.requires_grad for p, *_ in eng.items)
+        grad_on = torch.is_grad_enabled()
+        want_params = grad_on and any(p.requires_grad for p, *_ in eng.items)
+        in_mask = 0
+        if grad_on:
+            if self.text_enabled and isinstance(text, torch.Tensor) and text.requires_grad:
+                in_mask |= runtime.IN_TEXT
+            if self.audio_enabled and isinstance(audio, torch.Tensor) and audio.requires_grad:
+                in_mask |= runtime.IN_AUDIO
+        want_bwd = want_params or in_mask != 0
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
-        plan = eng.plan(B, L, want_bwd, self.training and self.m2f_config.dropout > 0.0, valid)
-        plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask)
+        outputs = (in_mask, want_params) if in_mask else (0, True)          # (no input gradient wanted: today's plans, keys and all)
+        plan = eng.plan(B, L, want_bwd, self.training and self.m2f_config.dropout > 0.0, valid, outputs)
+        # (detached: the staging copies are plumbing, autograd reaches the inputs through _Anchor)
+        det = lambda x: x.detach() if isinstance(x, torch.Tensor) else x          # noqa: E731
+        plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask)
         if want_bwd:
-            out = _Anchor.apply(eng.anchor, self, plan)
+            out = _Anchor.apply(eng.anchor, text, audio, self, plan)
             plan.hold(out.grad_fn)
             return out
         if plan.train and plan.cfg.dropout > 0.0:
@@ -469,7 +509,7 @@ class M2FNet(nn.Module):
         elif eng.precision == runtime.BF16 and eng.grad_bf16_buf is None:
             eng.grad_bf16_buf = torch.zeros(eng.flat.numel(), dtype=torch.bfloat16, device=eng.flat.device)
         for pl in list(eng.plans.values()):
-            if pl.train:
+            if pl.train and pl.param_grads:
                 eng._arm_grad_bf16(pl)
         return eng.grad_bf16_buf is not None
 

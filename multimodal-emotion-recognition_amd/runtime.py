@@ -24,7 +24,8 @@ HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "m2fnet_hip.h
 F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
- BUF_FAM0_OUT, BUF_CU_SEQLENS) = range(10)
+ BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO) = range(12)
+IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                                 ctypes.c_int64, ctypes.c_uint32)
@@ -109,6 +110,7 @@ SIGNATURES = {
                                          c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_set_shadow_map": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
+    "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
     "m2f_adam_hyper": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p]),
@@ -273,6 +275,12 @@ class Plan:
         self.cu_in = self._view(BUF_CU_SEQLENS, (B + 1,), torch.int32)
         self._dst = self._valid = None        # packed plans: token row of every (dialogue, slot) of the last batch; its validity
         self._spare = None                    # packed plans of B * L rows: device flag "row T-1 is not owned by the last batch"
+        # input gradients (train plans; m2f_plan_backward_outputs): d loss / d text, d loss / d audio in the token rows of text_in / audio_in
+        self._dtext = (self._view(BUF_DTEXT, (self.T, pad8(cfg.d_text)), torch.float32)[:, : cfg.d_text]
+                       if train and cfg.text_enabled else None)
+        self._daudio = (self._view(BUF_DAUDIO, (self.T, pad8(cfg.d_audio)), torch.float32)[:, : cfg.d_audio]
+                        if train and cfg.audio_enabled else None)
+        self.input_mask, self.param_grads = 0, bool(train and grads is not None)
         if train and grads is not None:
             # (loss, den, num) live in the tail of the flat gradient buffer (see include/m2fnet_hip.h)
             assert grads.numel() >= params.numel() + 4, "gradient buffer needs a 64-float tail"
@@ -486,6 +494,31 @@ class Plan:
         """m2f_plan_grad_bf16: the NEXT steps leave every gradient, rounded once, in `buf16` (bf16 [n_params]; None: back to fp32)."""
         check(lib().m2f_plan_grad_bf16(self._h(), buf16.data_ptr() if buf16 is not None else None), "m2f_plan_grad_bf16")
         self._g16_ref = buf16
+
+    def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
+        """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |
+        IN_AUDIO) and / or the parameter gradients.  A change rebuilds the launch lists and drops the captured graphs and the bf16-gradient
+        arming (the engine re-arms plans that compute parameter gradients)."""
+        check(lib().m2f_plan_backward_outputs(self._h(), int(input_mask), int(bool(param_grads))), "m2f_plan_backward_outputs")
+        if (int(input_mask), bool(param_grads)) != (self.input_mask, self.param_grads):
+            self._g16_ref = None
+            self._g16_bad = False
+        self.input_mask, self.param_grads = int(input_mask), bool(param_grads)
+
+    def input_grad(self, which: int, dst=None, valid=None, shape=None) -> torch.Tensor:
+        """A FRESH tensor (never a view of the plan's buffer, which the next backward overwrites) holding d loss / d text (which =
+        IN_TEXT) or d loss / d audio (IN_AUDIO) of the last backward, on the padded surface [b, l, d] of the batch.  Packed plans map
+        the token rows back through `dst` / `valid` (the forward's `_dst` / `_valid`) and leave exact zeros at pad slots: indexing and
+        copies only."""
+        rows = self._dtext if which == IN_TEXT else self._daudio
+        if rows is None:
+            raise HipError("this plan holds no input gradient of that modality (eval plan, or the modality is disabled)")
+        b, l = (self.in_B, self.in_L) if shape is None else shape
+        if self.packed:
+            out = torch.zeros(b, l, rows.shape[1], dtype=rows.dtype, device=rows.device)
+            out[valid] = rows.index_select(0, dst[valid])
+            return out
+        return rows.view(self.B, self.L, -1)[:b, :l].clone()
 
     def fused_adam(self, on: bool) -> None:
         """The NEXT step() also takes the optimizer step (on) / leaves the weight gradients in the gradient buffer (off)."""
