@@ -9,10 +9,13 @@ forward + criterion + backward (one hipGraph launch), gradient all-reduce over R
 The headline metric (BASELINE.json) is utterances/s; per-GPU work is fixed (weak scaling, global batch = N * B).
 Workload = BASELINE.json configs[2] ("c3": shipped depth, roberta-large 1024 + wav2vec2 768, B=64 x L=16, bf16) - the largest
 single-GPU configuration and the one north_star's target is stated on; configs[1] ("c2") runs with --workload c2.
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel = the grouped MFMA GEMM,
-timed live with hipEvents per launch; `roofline.fam_gemm` = the same figure over the fusion-attention stack's GEMM
-launches alone, the kernels north_star's target is stated on), `secondary` (the other single-GPU configuration, C2) and
-`cpu_baseline` (the CPU oracle on the host cores, N=1 only).
+A plain run sets up, warms up, times the `--steps` steps, writes `--dump-outputs` if asked and prints ONE JSON line (rank 0)
+with the contract fields, the configuration and the loss.  `--full` measures everything else after the timed steps, on the
+same model: `repeats` (more timed brackets), `fwd_bwd_only`, `fp32_gradients`, `comm` (N > 1), `roofline` (dominant kernel =
+the grouped MFMA GEMM, timed live with hipEvents per launch; `roofline.fam_gemm` = the same figure over the fusion-attention
+stack's GEMM launches alone, the kernels north_star's target is stated on; `--dump-launches`) and, at N=1, `parity_mode` (the
+fp32 mode), `secondary` (the other single-GPU configuration, C2) and `cpu_baseline` (the CPU oracle on the host cores).
+None of it changes `value`: the timed steps and the dumped outputs come first.
 
 `python bench.py --gpus N` started WITHOUT a torchrun environment launches its own N ranks (one child process per GPU
 through torch.distributed.run, decided before anything touches the GPU) and exits with their status; a rank whose RCCL
@@ -185,8 +188,65 @@ LAUNCH_NAMES = ["gemm_fwd", "gemm_dgrad", "gemm_wgrad", "attn_fwd", "attn_bwd", 
 PARTS = ["encoders", "fusion", "classifier"]
 
 
-def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragged, buckets, exchange, roofline=True, dump="", packed=False,
+def roofline_figures(reps, dump, wl, dtype, ev_empty_ms, ev_trivial_ms):
+    """`roofline` of a --full run from the per-launch hipEvent timings of eager steps (`reps` = plan.step_timed() results);
+    `dump` = file for the per-launch table (--dump-launches)."""
+    n_l = len(reps[0])
+    avg_ms = [sum(r[i][1] for r in reps) / len(reps) for i in range(n_l)]
+    kinds = [reps[0][i][0] & 31 for i in range(n_l)]
+    parts = [reps[0][i][0] >> 5 for i in range(n_l)]
+    flops = [reps[0][i][2] for i in range(n_l)]
+    if dump:
+        with open(dump, "w") as f:
+            for i in range(n_l):
+                tf = flops[i] / (avg_ms[i] * 1e-3) / 1e12 if avg_ms[i] > 0 else 0.0
+                f.write(f"{i:4d} {LAUNCH_NAMES[kinds[i]]:14s} {PARTS[parts[i]]:10s} {avg_ms[i] * 1e3:9.2f} us {flops[i] / 1e9:9.3f} GFLOP {tf:8.1f} TFLOP/s\n")
+    # every launch that carries GEMM FLOPs: the grouped GEMM launches
+    gemm_idx = [i for i in range(n_l) if kinds[i] in (0, 1, 2)]
+    gemm_ms = sum(avg_ms[i] for i in gemm_idx)
+    gemm_fl = sum(flops[i] for i in gemm_idx)
+    fam_idx = [i for i in gemm_idx if kinds[i] in (0, 1) and parts[i] == 1]
+    fam_ms, fam_fl = sum(avg_ms[i] for i in fam_idx), sum(flops[i] for i in fam_idx)
+    achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    peak = PEAK_TFLOPS[dtype]
+    wl_key = [k for k, v in WORKLOADS.items() if v is wl][0]
+    # HBM-side bytes per GEMM launch and the kernels' own begin..end durations cannot be read from inside the process: they
+    # come from committed rocprofv3 passes of this same command (tools/traffic.sh, tools/kstats_bench.sh) - and are only
+    # quoted while the kernel sources are the ones they were measured on
+    traffic = load_profile_digest("traffic", wl_key, dtype)
+    kstats = load_profile_digest("kstats", wl_key, dtype)
+    rocprof = None
+    if kstats is not None:
+        rocprof = {"source": kstats["_source"], "stale": kstats["_stale"]}
+        if not kstats["_stale"]:
+            rocprof.update({"avg_launch_us": kstats["avg_launch_us"], "gemm_ms_per_step": kstats["gemm_ms_per_step"],
+                            "achieved": kstats.get("gemm_gflop_per_step", gemm_fl / 1e9) / kstats["gemm_ms_per_step"], "unit": "TFLOP/s"})   # GFLOP / ms
+    return {
+        "bound": "mfma", "kernel": "bf16: m2f_gemm16_ring_kernel (forward / input-gradient launches as 256x128, 128x128, 128x64 or 64x64 ring tiles) + m2f_gemm_p8_kernel (the weight-gradient table launch, 256x256 tiles on the eight-phase schedule); fp32: m2f_gemm_kernel - the grouped MFMA GEMM launches of one step",
+        "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+        "traffic": None if traffic is None or traffic["_stale"] else float(traffic["traffic_bytes_per_launch"]),
+        "traffic_source": None if traffic is None else {"file": traffic["_source"], "stale": traffic["_stale"]},
+        "launches_per_step": len(gemm_idx), "avg_launch_us": gemm_ms / max(len(gemm_idx), 1) * 1e3,
+        # the fusion-attention stack's own GEMM launches (q/v, k, out-projection, Linear(2E->E); forward + input gradient):
+        # north_star states its roofline target on these.  Their weight-gradient problems run inside the ONE table launch
+        # of the step and cannot be timed apart from the other layers'.
+        "fam_gemm": None if not fam_idx else {
+            "achieved": fam_fl / (fam_ms * 1e-3) / 1e12, "peak": peak, "frac": fam_fl / (fam_ms * 1e-3) / 1e12 / peak,
+            "launches": len(fam_idx), "gflop": fam_fl / 1e9, "ms": fam_ms, "avg_launch_us": fam_ms / len(fam_idx) * 1e3,
+            "what": "forward + input-gradient GEMM launches of the fusion stack (hipEvent intervals)"},
+        # what a hipEvent interval holds besides the kernel's own begin..end (which is what rocprofv3 reports):
+        # NOT subtracted from `achieved`, stated so the two can be reconciled
+        "event_interval_overhead_us": {"empty_pair": ev_empty_ms * 1e3, "pair_around_one_thread_kernel": ev_trivial_ms * 1e3},
+        "rocprof": rocprof,
+        "algorithmic_gflop_per_step": gemm_fl / 1e9, "gemm_ms_per_step": gemm_ms,
+        "all_kernels_ms_per_step_eager": sum(avg_ms),
+    }
+
+
+def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragged, buckets, exchange, full=False, dump="", packed=False,
                  repeats=1, overlap=False, algorithm="all_reduce", fused_adam=False, grad_bf16=True, fp32_grad_leg=True, dump_outputs=""):
+    """Warm-up, `steps` timed steps, `dump_outputs`; with `full` also the legs that follow them (repeats, comm, fp32_gradients,
+    fwd_bwd_only, roofline and its launch table `dump`)."""
     cfg, B, L = wl["cfg"], wl["B"], wl["L"]
     torch.manual_seed(0)                               # identical replicas on every rank
     model = M2FNet(cfg, precision=dtype, shape_buckets=False).to(device).train()      # the plan IS the workload's (B, L): no bucket padding
@@ -257,102 +317,87 @@ def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragge
         plan.check_status()
         # what the timed path's last step computed, before anything below runs the model again
         dumped = dump_step_outputs(dump_outputs, model, opt, stepper.reducer, plan, world, fused_steps[0] > 0) if dump_outputs else None
-        # the same bracket four more times (spread of the measurement; `value` stays the FIRST bracket = exactly `steps` steps)
-        rep_ms = [elapsed / steps * 1e3]
-        for _ in range(repeats - 1):
-            if world > 1:
-                torch.distributed.barrier()
-            torch.cuda.synchronize()
-            tr0 = time.perf_counter()
-            for _ in range(steps):
-                one_step()
-            side.synchronize()
-            torch.cuda.synchronize()
-            if world > 1:
-                torch.distributed.barrier()
-            rep_ms.append(dp.reduce_metrics([time.perf_counter() - tr0], device=device)[0] / steps * 1e3)
-
-        # ---- N > 1: what the exchange costs, so that a scaling record explains itself ---------------------------------------------
-        comm = None
-        if world > 1:
-            red = stepper.reducer
-            n_c = max(5, min(steps, 20))
-
-            def bracket(fn, n):
-                torch.distributed.barrier()
+        if full:
+            # the same bracket four more times (spread of the measurement; `value` stays the FIRST bracket = exactly `steps` steps)
+            rep_ms = [elapsed / steps * 1e3]
+            for _ in range(repeats - 1):
+                if world > 1:
+                    torch.distributed.barrier()
                 torch.cuda.synchronize()
-                tc0 = time.perf_counter()
-                for _ in range(n):
-                    fn()
+                tr0 = time.perf_counter()
+                for _ in range(steps):
+                    one_step()
                 side.synchronize()
                 torch.cuda.synchronize()
-                torch.distributed.barrier()
-                return dp.reduce_metrics([time.perf_counter() - tc0], device=device)[0] / n * 1e3
-            for _ in range(3):
-                red.exchange_only()
-            alone_ms = bracket(red.exchange_only, n_c)          # the step's collectives alone: same buckets, dtypes and order, no compute
-            red.stub = True                                    # the same step on identical data with every collective a no-op
-            for _ in range(3):
-                one_step()
-            nocomm_ms = bracket(one_step, n_c)
-            red.stub = False
-            one_step()                                         # (leave the replicas in step with each other again: real sums)
-            comm = {"algorithm": red.algorithm, "exchange_dtype": red.exchange, "buckets": len(red.param_chunks if red.exchange == "bf16" else red.chunks),
-                    "overlap_with_backward": bool(split), "gradients_rounded_by": "the step (bf16 dW from the weight-gradient launch)" if red.buf16_filled else ("a pass over the fp32 buffer" if red.exchange == "bf16" else None),
-                    "bytes_per_step": red.bytes_per_step(),
-                    "allreduce_alone_ms": alone_ms, "algbw_GBps_alone": red.bytes_per_step() / (alone_ms * 1e-3) / 1e9,
-                    "step_without_collectives_ms": nocomm_ms, "exposed_ms": elapsed / steps * 1e3 - nocomm_ms, "steps_each": n_c,
-                    "note": "exposed_ms = ms_per_step - the same step with the collectives stubbed to no-ops on identical data; "
-                            "allreduce_alone_ms = the same buckets with no compute around them (max over ranks)"}
+                if world > 1:
+                    torch.distributed.barrier()
+                rep_ms.append(dp.reduce_metrics([time.perf_counter() - tr0], device=device)[0] / steps * 1e3)
 
-        # ---- secondary figure: forward + criterion + backward only (SURVEY 8-d's strict metric; `value` above also
-        # pays for the optimizer and, at N > 1, the gradient exchange) ---------------------------------------------
-        n_fb = max(10, min(steps, 50))
-        fp32_grad_ms = None
-        if g16_on and fp32_grad_leg:
-            # ... and the same step with fp32 gradients (rounds 1-3), on the same clock, beside it
-            model.set_grad_bf16(False)
-            for _ in range(3):
-                one_step()
-            side.synchronize()
-            tg0 = time.perf_counter()
-            for _ in range(steps):
-                one_step()
-            side.synchronize()
-            fp32_grad_ms = (time.perf_counter() - tg0) / steps * 1e3
-            model.set_grad_bf16(True)                      # (what follows measures the default mode again)
-            for _ in range(2):
-                one_step()
-        for _ in range(3):
-            plan.step(0.1, False, False, use_graph)
-        side.synchronize()
-        tf0 = time.perf_counter()
-        for _ in range(n_fb):
-            plan.step(0.1, False, False, use_graph)
-        side.synchronize()
-        fb_sec = (time.perf_counter() - tf0) / n_fb
+            # ---- N > 1: what the exchange costs, so that a scaling record explains itself ---------------------------------------------
+            comm = None
+            if world > 1:
+                red = stepper.reducer
+                n_c = max(5, min(steps, 20))
 
-        # ---- roofline of the dominant kernel (grouped GEMM), per-launch hipEvent timing ------------------
-        for _ in range(5):
-            plan.step_timed(0.1, False, False)
-        reps = [plan.step_timed(0.1, False, False) for _ in range(10)]
-        ev_empty_ms, ev_trivial_ms = runtime.event_overhead(200)
-    n_l = len(reps[0])
-    avg_ms = [sum(r[i][1] for r in reps) / len(reps) for i in range(n_l)]
-    kinds = [reps[0][i][0] & 31 for i in range(n_l)]
-    parts = [reps[0][i][0] >> 5 for i in range(n_l)]
-    flops = [reps[0][i][2] for i in range(n_l)]
-    if dump:
-        with open(dump, "w") as f:
-            for i in range(n_l):
-                tf = flops[i] / (avg_ms[i] * 1e-3) / 1e12 if avg_ms[i] > 0 else 0.0
-                f.write(f"{i:4d} {LAUNCH_NAMES[kinds[i]]:14s} {PARTS[parts[i]]:10s} {avg_ms[i] * 1e3:9.2f} us {flops[i] / 1e9:9.3f} GFLOP {tf:8.1f} TFLOP/s\n")
-    # every launch that carries GEMM FLOPs: the grouped GEMM launches
-    gemm_idx = [i for i in range(n_l) if kinds[i] in (0, 1, 2)]
-    gemm_ms = sum(avg_ms[i] for i in gemm_idx)
-    gemm_fl = sum(flops[i] for i in gemm_idx)
-    fam_idx = [i for i in gemm_idx if kinds[i] in (0, 1) and parts[i] == 1]
-    fam_ms, fam_fl = sum(avg_ms[i] for i in fam_idx), sum(flops[i] for i in fam_idx)
+                def bracket(fn, n):
+                    torch.distributed.barrier()
+                    torch.cuda.synchronize()
+                    tc0 = time.perf_counter()
+                    for _ in range(n):
+                        fn()
+                    side.synchronize()
+                    torch.cuda.synchronize()
+                    torch.distributed.barrier()
+                    return dp.reduce_metrics([time.perf_counter() - tc0], device=device)[0] / n * 1e3
+                for _ in range(3):
+                    red.exchange_only()
+                alone_ms = bracket(red.exchange_only, n_c)          # the step's collectives alone: same buckets, dtypes and order, no compute
+                red.stub = True                                    # the same step on identical data with every collective a no-op
+                for _ in range(3):
+                    one_step()
+                nocomm_ms = bracket(one_step, n_c)
+                red.stub = False
+                one_step()                                         # (leave the replicas in step with each other again: real sums)
+                comm = {"algorithm": red.algorithm, "exchange_dtype": red.exchange, "buckets": len(red.param_chunks if red.exchange == "bf16" else red.chunks),
+                        "overlap_with_backward": bool(split), "gradients_rounded_by": "the step (bf16 dW from the weight-gradient launch)" if red.buf16_filled else ("a pass over the fp32 buffer" if red.exchange == "bf16" else None),
+                        "bytes_per_step": red.bytes_per_step(),
+                        "allreduce_alone_ms": alone_ms, "algbw_GBps_alone": red.bytes_per_step() / (alone_ms * 1e-3) / 1e9,
+                        "step_without_collectives_ms": nocomm_ms, "exposed_ms": elapsed / steps * 1e3 - nocomm_ms, "steps_each": n_c,
+                        "note": "exposed_ms = ms_per_step - the same step with the collectives stubbed to no-ops on identical data; "
+                                "allreduce_alone_ms = the same buckets with no compute around them (max over ranks)"}
+
+            # ---- secondary figure: forward + criterion + backward only (SURVEY 8-d's strict metric; `value` above also
+            # pays for the optimizer and, at N > 1, the gradient exchange) ---------------------------------------------
+            n_fb = max(10, min(steps, 50))
+            fp32_grad_ms = None
+            if g16_on and fp32_grad_leg:
+                # ... and the same step with fp32 gradients (rounds 1-3), on the same clock, beside it
+                model.set_grad_bf16(False)
+                for _ in range(3):
+                    one_step()
+                side.synchronize()
+                tg0 = time.perf_counter()
+                for _ in range(steps):
+                    one_step()
+                side.synchronize()
+                fp32_grad_ms = (time.perf_counter() - tg0) / steps * 1e3
+                model.set_grad_bf16(True)                      # (what follows measures the default mode again)
+                for _ in range(2):
+                    one_step()
+            for _ in range(3):
+                plan.step(0.1, False, False, use_graph)
+            side.synchronize()
+            tf0 = time.perf_counter()
+            for _ in range(n_fb):
+                plan.step(0.1, False, False, use_graph)
+            side.synchronize()
+            fb_sec = (time.perf_counter() - tf0) / n_fb
+
+            # ---- roofline of the dominant kernel (grouped GEMM), per-launch hipEvent timing ------------------
+            for _ in range(5):
+                plan.step_timed(0.1, False, False)
+            reps = [plan.step_timed(0.1, False, False) for _ in range(10)]
+            ev_empty_ms, ev_trivial_ms = runtime.event_overhead(200)
     c = model.m2f_config
     _, fb_per_slot = layout.flops_per_slot(c, L)
     ms_per_step = elapsed / steps * 1e3
@@ -362,20 +407,7 @@ def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragge
     n_valid_all = int(nv.item())
     utt_per_s = n_valid_all / (elapsed / steps)
     slots_per_s = world * (plan.T if plan.packed else B * L) / (elapsed / steps)          # padded slots are computed too (unless packed)
-    achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     peak = PEAK_TFLOPS[dtype]
-    wl_key = [k for k, v in WORKLOADS.items() if v is wl][0]
-    # HBM-side bytes per GEMM launch and the kernels' own begin..end durations cannot be read from inside the process: they
-    # come from committed rocprofv3 passes of this same command (tools/traffic.sh, tools/kstats_bench.sh) - and are only
-    # quoted while the kernel sources are the ones they were measured on
-    traffic = load_profile_digest("traffic", wl_key, dtype)
-    kstats = load_profile_digest("kstats", wl_key, dtype)
-    rocprof = None
-    if kstats is not None:
-        rocprof = {"source": kstats["_source"], "stale": kstats["_stale"]}
-        if not kstats["_stale"]:
-            rocprof.update({"avg_launch_us": kstats["avg_launch_us"], "gemm_ms_per_step": kstats["gemm_ms_per_step"],
-                            "achieved": kstats.get("gemm_gflop_per_step", gemm_fl / 1e9) / kstats["gemm_ms_per_step"], "unit": "TFLOP/s"})   # GFLOP / ms
     out = {
         "metric": "utterances/sec (fwd+bwd) M2FNet fusion, MELD dialogues, 1/2/4/8 MI355X",
         "value": utt_per_s, "unit": "utterances/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -394,42 +426,24 @@ def run_workload(wl, dtype, rank, world, device, steps, warmup, use_graph, ragge
                                     else ("re-cast at the head of every forward" if dtype == "bf16" else None),
                    "source_hash": source_hash()},
         "loss": loss,
-        "repeats": {"n": len(rep_ms), "steps_each": steps, "ms_per_step": rep_ms, "median": sorted(rep_ms)[len(rep_ms) // 2],
-                    "min": min(rep_ms), "max": max(rep_ms),
-                    "note": "`value` / `ms_per_step` are the first bracket; the others repeat it back to back"},
-        "fwd_bwd_only": {"ms_per_step": fb_sec * 1e3, "utterances_per_s_rank0": n_valid / fb_sec, "steps": n_fb,
-                         "note": "fwd + CE + bwd graph replays on rank 0, optimizer and gradient exchange excluded"},
-        "fp32_gradients": None if fp32_grad_ms is None else {"ms_per_step": fp32_grad_ms, "value": n_valid / (fp32_grad_ms * 1e-3), "steps": steps,
-                                                               "note": "the same step with fp32 gradients between backward and optimizer (M2FNet.set_grad_bf16(False)); "
-                                                                       "`value` runs with gradients rounded once to bf16, as under the bf16 exchange at N > 1"},
-        "step_tflops": slots_per_s * fb_per_slot / 1e12,
-        "step_frac_of_peak": slots_per_s * fb_per_slot / 1e12 / (peak * world),
     }
-    if comm is not None:
+    if full:
+        out["repeats"] = {"n": len(rep_ms), "steps_each": steps, "ms_per_step": rep_ms, "median": sorted(rep_ms)[len(rep_ms) // 2],
+                           "min": min(rep_ms), "max": max(rep_ms),
+                           "note": "`value` / `ms_per_step` are the first bracket; the others repeat it back to back"}
+        out["fwd_bwd_only"] = {"ms_per_step": fb_sec * 1e3, "utterances_per_s_rank0": n_valid / fb_sec, "steps": n_fb,
+                               "note": "fwd + CE + bwd graph replays on rank 0, optimizer and gradient exchange excluded"}
+        out["fp32_gradients"] = None if fp32_grad_ms is None else {"ms_per_step": fp32_grad_ms, "value": n_valid / (fp32_grad_ms * 1e-3), "steps": steps,
+                                                                   "note": "the same step with fp32 gradients between backward and optimizer (M2FNet.set_grad_bf16(False)); "
+                                                                           "`value` runs with gradients rounded once to bf16, as under the bf16 exchange at N > 1"}
+    out["step_tflops"] = slots_per_s * fb_per_slot / 1e12
+    out["step_frac_of_peak"] = slots_per_s * fb_per_slot / 1e12 / (peak * world)
+    if full and comm is not None:
         out["comm"] = comm
     if dumped is not None:
         out["outputs_dumped"] = dumped
-    if roofline:
-        out["roofline"] = {
-            "bound": "mfma", "kernel": "bf16: m2f_gemm16_ring_kernel (forward / input-gradient launches as 256x128, 128x128, 128x64 or 64x64 ring tiles) + m2f_gemm_p8_kernel (the weight-gradient table launch, 256x256 tiles on the eight-phase schedule); fp32: m2f_gemm_kernel - the grouped MFMA GEMM launches of one step",
-            "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-            "traffic": None if traffic is None or traffic["_stale"] else float(traffic["traffic_bytes_per_launch"]),
-            "traffic_source": None if traffic is None else {"file": traffic["_source"], "stale": traffic["_stale"]},
-            "launches_per_step": len(gemm_idx), "avg_launch_us": gemm_ms / max(len(gemm_idx), 1) * 1e3,
-            # the fusion-attention stack's own GEMM launches (q/v, k, out-projection, Linear(2E->E); forward + input gradient):
-            # north_star states its roofline target on these.  Their weight-gradient problems run inside the ONE table launch
-            # of the step and cannot be timed apart from the other layers'.
-            "fam_gemm": None if not fam_idx else {
-                "achieved": fam_fl / (fam_ms * 1e-3) / 1e12, "peak": peak, "frac": fam_fl / (fam_ms * 1e-3) / 1e12 / peak,
-                "launches": len(fam_idx), "gflop": fam_fl / 1e9, "ms": fam_ms, "avg_launch_us": fam_ms / len(fam_idx) * 1e3,
-                "what": "forward + input-gradient GEMM launches of the fusion stack (hipEvent intervals)"},
-            # what a hipEvent interval holds besides the kernel's own begin..end (which is what rocprofv3 reports):
-            # NOT subtracted from `achieved`, stated so the two can be reconciled
-            "event_interval_overhead_us": {"empty_pair": ev_empty_ms * 1e3, "pair_around_one_thread_kernel": ev_trivial_ms * 1e3},
-            "rocprof": rocprof,
-            "algorithmic_gflop_per_step": gemm_fl / 1e9, "gemm_ms_per_step": gemm_ms,
-            "all_kernels_ms_per_step_eager": sum(avg_ms),
-        }
+    if full:
+        out["roofline"] = roofline_figures(reps, dump, wl, dtype, ev_empty_ms, ev_trivial_ms)
     del stepper, opt, model, plan, eng
     torch.cuda.empty_cache()
     return out
@@ -446,14 +460,18 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="secondary workload of SURVEY 8-d: MELD-like dialogue lengths, "
                     "`value` then counts VALID utterances only")
     ap.add_argument("--packed", action="store_true", help="packed token layout (valid utterances only; with --ragged)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else the line can carry: `repeats`, `fwd_bwd_only`, `fp32_gradients`, "
+                         "`comm` (N > 1), `roofline` and, at N = 1, `parity_mode`, `secondary` and `cpu_baseline`.  Without it a run does "
+                         "only what `value` and `ms_per_step` need (and --dump-outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU-oracle steps for `cpu_baseline`")
     ap.add_argument("--buckets", type=int, default=4,
                     help="gradient all-reduce buckets at N > 1 (31 MB each for the bf16 exchange at C2: large enough for "
                          "ring bandwidth, small enough that only the last bucket's Adam launch is exposed)")
     ap.add_argument("--grad-exchange", default="auto", choices=["auto", "fp32", "bf16"],
                     help="dtype of the gradient all-reduce at N > 1 (auto: bf16 for --dtype bf16, fp32 for --dtype fp32)")
-    ap.add_argument("--dump-launches", default="", help="write the per-launch timing table (kind, us, GFLOP) to this file")
+    ap.add_argument("--dump-launches", default="", help="--full: write the per-launch timing table (kind, us, GFLOP) to this file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the timed path computed in its last timed step to DIR/<name>.npy (loss, logits, and a fixed seeded "
                          "sample of parameters, gradients and Adam moments; float32 / float64, at most 24 MiB): two builds run with the same "
@@ -461,7 +479,8 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="form the process group (gloo when there is no GPU), check its size against --gpus, print it, exit: "
                          "the launch path without the measurement (tests/test_dp_cpu.py)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed brackets of `--steps` steps each (the first one is `value`)")
+    ap.add_argument("--repeats", type=int, default=None, help="--full: timed brackets of `--steps` steps each (the first one is `value`; "
+                    "default 5)")
     ap.add_argument("--dp-overlap", action="store_true", default=os.environ.get("M2F_DP_OVERLAP", "0") == "1",
                     help="N > 1: the fusion stack's / classifier's gradient bucket travels under the encoders' backward (the step runs as two "
                          "hipGraphs).  OFF by default: verified bit for bit against the plain order through gloo staging, never yet run on RCCL "
@@ -479,14 +498,16 @@ def main():
                     "since round 4: the step leaves its gradients rounded once to bf16 - the precision every rank's gradient has under the bf16 "
                     "exchange at N > 1 - and the optimizer reads those (no fp32 dW round trip); the fp32-gradient step is timed beside it "
                     "(`fp32_gradients`)")
-    ap.add_argument("--no-fp32-grad-leg", action="store_true", help="skip the fp32-gradient step timed beside the default line (profiling runs: every "
+    ap.add_argument("--no-fp32-grad-leg", action="store_true", help="--full: skip the fp32-gradient step timed beside the default line (profiling runs: every "
                     "kernel of the run is then the default mode's)")
-    ap.add_argument("--no-parity-leg", action="store_true", help="skip the fp32 (1e-3 parity mode) leg of the same workload")
+    ap.add_argument("--no-parity-leg", action="store_true", help="--full: skip the fp32 (1e-3 parity mode) leg of the same workload")
     ap.add_argument("--secondary", default="c2", choices=sorted(WORKLOADS) + ["none"],
-                    help="second single-GPU configuration reported under `secondary` (N = 1 only)")
+                    help="--full: second single-GPU configuration reported under `secondary` (N = 1 only)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.dump_launches or (args.repeats or 1) > 1):
+        ap.error("--dump-launches and --repeats above 1 are measured after the timed steps: they need --full")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher environment: start the ranks ourselves - fresh child processes, before this process touches the GPU
@@ -520,28 +541,29 @@ def main():
     use_graph = not args.no_graph
     exchange = args.grad_exchange if args.grad_exchange != "auto" else ("bf16" if args.dtype == "bf16" else "fp32")
     res = run_workload(wl, args.dtype, rank, world, device, args.steps, args.warmup, use_graph, args.ragged, args.buckets, exchange,
-                       roofline=True, dump=args.dump_launches if rank == 0 else "", packed=args.packed, repeats=max(1, args.repeats),
+                       full=args.full, dump=args.dump_launches if rank == 0 else "", packed=args.packed,
+                       repeats=max(1, args.repeats if args.repeats is not None else 5),
                        overlap=args.dp_overlap and not args.no_overlap, algorithm=args.dp_algorithm, fused_adam=args.fused_adam, grad_bf16=not args.grad_fp32, fp32_grad_leg=not args.no_fp32_grad_leg,
                        dump_outputs=args.dump_outputs if rank == 0 else "")
     if rank == 0:
         out = res
-        if world == 1 and args.dtype == "bf16" and not args.no_parity_leg and not args.ragged and not args.packed:
+        if args.full and world == 1 and args.dtype == "bf16" and not args.no_parity_leg and not args.ragged and not args.packed:
             # the mode that meets north_star's 1e-3 logits bound (exact-fp32 MFMA, tests/test_bench_geometry_gpu.py), same workload,
             # same protocol, shorter run: what parity-exact costs, on the same clock as the headline
             par = run_workload(wl, "fp32", rank, world, device, max(10, args.steps // 5), max(3, args.warmup // 2), use_graph, False,
-                               args.buckets, "fp32", roofline=True, dump="", repeats=3)
+                               args.buckets, "fp32", full=True, dump="", repeats=3)
             out["parity_mode"] = {"dtype": "fp32", "value": par["value"], "unit": par["unit"], "ms_per_step": par["ms_per_step"],
                                   "steps": par["steps"], "fwd_bwd_only": par["fwd_bwd_only"], "repeats": par["repeats"],
                                   "roofline": {k: par["roofline"][k] for k in ("achieved", "peak", "frac", "unit", "launches_per_step", "fam_gemm")},
                                   "tolerance": "logits within 1e-3 of the reference (asserted < 2e-4 at this geometry)"}
-        if world == 1 and args.secondary != "none" and args.secondary != args.workload:
+        if args.full and world == 1 and args.secondary != "none" and args.secondary != args.workload:
             # the other single-GPU configuration of BASELINE.json, same protocol, shorter run
             sec = run_workload(WORKLOADS[args.secondary], args.dtype, rank, world, device, max(20, args.steps // 2), args.warmup,
-                               use_graph, False, args.buckets, exchange, roofline=True, dump="")
+                               use_graph, False, args.buckets, exchange, full=True, dump="")
             out["secondary"] = {k: sec[k] for k in ("value", "unit", "ms_per_step", "fwd_bwd_only", "step_tflops", "step_frac_of_peak")}
             out["secondary"]["workload"] = sec["config"]["workload"]
             out["secondary"]["roofline"] = {k: sec["roofline"][k] for k in ("achieved", "peak", "frac", "fam_gemm", "launches_per_step")}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 share = len(os.sched_getaffinity(0))
             except AttributeError:

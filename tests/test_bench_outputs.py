@@ -1,6 +1,6 @@
 """bench.py's measurement contract: `--steps` is the number of timed steps of `ms_per_step`, and `--dump-outputs DIR` writes what
 the timed path computed in its last step (loss, logits, a fixed seeded sample of parameters / gradients / Adam moments) as float
-.npy files under 64 MB, the same from run to run of the same arguments."""
+.npy files under 64 MB, the same from run to run of the same arguments.  What is measured after the timed steps needs `--full`."""
 import os
 import subprocess
 import sys
@@ -18,10 +18,18 @@ def test_bench_refuses_zero_steps():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]
 
 
-def _run(out_dir, steps):
+def test_bench_refuses_after_step_figures_without_full(tmp_path):
+    for extra in (["--dump-launches", str(tmp_path / "launches.txt")], ["--repeats", "3"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2"] + extra,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "need --full" in r.stderr, r.stderr[-2000:]
+    assert not (tmp_path / "launches.txt").exists()
+
+
+def _run(out_dir, steps, **kw):
     import bench
     dev = torch.device("cuda", 0)
-    return bench.run_workload(bench.WORKLOADS["c1"], "bf16", 0, 1, dev, steps, 1, True, False, 4, "bf16", dump_outputs=str(out_dir))
+    return bench.run_workload(bench.WORKLOADS["c1"], "bf16", 0, 1, dev, steps, 1, True, False, 4, "bf16", dump_outputs=str(out_dir), **kw)
 
 
 @pytest.mark.gpu
@@ -46,3 +54,22 @@ def test_dump_outputs_of_the_timed_step(tmp_path):
     for k in names:
         assert np.allclose(np.load(b / (k + ".npy")), arr[k], rtol=1e-5, atol=1e-6), k
     assert (np.load(b / "param_index.npy") == idx).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_after_step_figures_to_full(tmp_path):
+    """A plain run reports the timed steps only; `full` adds the legs measured after them, and the timed steps compute the same."""
+    extras = {"repeats", "fwd_bwd_only", "fp32_gradients", "comm", "roofline"}
+    plain = _run(tmp_path / "plain", 3)
+    assert not extras & set(plain)
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    table = tmp_path / "launches.txt"
+    full = _run(tmp_path / "full", 3, full=True, repeats=2, dump=str(table))
+    assert set(full) - set(plain) == extras - {"comm"}                  # (comm: N > 1 only)
+    assert full["repeats"]["n"] == 2 and full["repeats"]["ms_per_step"][0] == full["ms_per_step"]
+    assert full["fwd_bwd_only"]["ms_per_step"] > 0 and full["fp32_gradients"]["ms_per_step"] > 0
+    assert full["roofline"]["launches_per_step"] > 0 and full["roofline"]["achieved"] > 0
+    assert len(table.read_text().splitlines()) >= full["roofline"]["launches_per_step"]
+    assert full["loss"] == pytest.approx(plain["loss"], rel=1e-5)
+    for k in ("params", "exp_avg", "exp_avg_sq", "logits"):
+        assert np.allclose(np.load(tmp_path / "full" / (k + ".npy")), np.load(tmp_path / "plain" / (k + ".npy")), rtol=1e-5, atol=1e-6), k

@@ -12,12 +12,12 @@ for w in c3 c2; do
   cp gpurun_out/ks_${tag}_$w/bench.json $O/bench_under_rocprof_${w}_bf16.json
   tools/traffic.sh ${tag}_$w --workload $w --secondary none > $O/traffic_${w}.txt 2>&1
   cp gpurun_out/traffic_${tag}_$w/traffic.json $O/traffic_${w}_bf16.json
-  python3 bench.py --workload $w --secondary none --no-cpu-baseline --no-parity-leg --dump-launches $O/launches_${w}_bf16.txt > $O/bench_${w}_bf16.json 2> $O/bench_${w}.err
+  python3 bench.py --full --workload $w --secondary none --no-cpu-baseline --no-parity-leg --dump-launches $O/launches_${w}_bf16.txt > $O/bench_${w}_bf16.json 2> $O/bench_${w}.err
 done
 tools/pmc_bench.sh "ring_kernel<128, 64" --workload c3 --secondary none > $O/pmc_ring_128x64_c3.txt 2>&1
 tools/pmc_bench.sh "ring_kernel<128, 128, 4, false" --workload c3 --secondary none > $O/pmc_ring_128x128_c3.txt 2>&1
 tools/pmc_bench.sh "ring_kernel<256, 128, 3, true" --workload c3 --secondary none > $O/pmc_ring_table_rc_256x128_c3.txt 2>&1
 tools/pmc_bench.sh "m2f_attn_bwd" --workload c3 --secondary none > $O/pmc_attn_bwd_c3.txt 2>&1
 tools/pmc_bench.sh "m2f_ln_bwd" --workload c3 --secondary none > $O/pmc_ln_bwd_c3.txt 2>&1
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo done > $O/DONE

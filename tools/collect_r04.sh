@@ -11,20 +11,20 @@ if [ "$part" = "1" ]; then
     cp gpurun_out/ks_${tag}_$w/bench.json $O/bench_under_rocprof_${w}_bf16.json
     tools/traffic.sh ${tag}_$w --workload $w --secondary none > $O/traffic_${w}.txt 2>&1
     cp gpurun_out/traffic_${tag}_$w/traffic.json $O/traffic_${w}_bf16.json
-    python3 bench.py --workload $w --secondary none --no-cpu-baseline --no-parity-leg --dump-launches $O/launches_${w}_bf16.txt > $O/bench_${w}_bf16.json 2> $O/bench_${w}.err
+    python3 bench.py --full --workload $w --secondary none --no-cpu-baseline --no-parity-leg --dump-launches $O/launches_${w}_bf16.txt > $O/bench_${w}_bf16.json 2> $O/bench_${w}.err
     echo "done $w"
   done
   tools/pmc_bench_multi.sh $O --workload c3 --secondary none -- "ring_128x64_c3=ring_kernel<128, 64" "ring_128x128_c3=ring_kernel<128, 128, 4, false" "p8_table_rc_c3=m2f_gemm_p8_kernel<true, true, 1" "attn_bwd_c3=m2f_attn_bwd" "ln_bwd_c3=m2f_ln_bwd" "adam_c3=m2f_adam_shadow"
   echo done > $O/DONE1
 else
-  python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$?"
-  python3 bench.py --workload c3l24 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3l24_bf16.json 2>> $O/err.txt
-  python3 bench.py --workload c3 --ragged --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_ragged.json 2>> $O/err.txt
-  python3 bench.py --workload c3 --packed --ragged --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_ragged_packed.json 2>> $O/err.txt
-  python3 bench.py --workload c2 --dtype fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c2_fp32.json 2>> $O/err.txt
-  python3 bench.py --workload c3 --dtype fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_fp32.json 2>> $O/err.txt
-  python3 bench.py --workload c3b256 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_b256_bf16.json 2>> $O/err.txt
-  python3 bench.py --workload c3 --grad-fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_grad_fp32.json 2>> $O/err.txt
+  python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$?"
+  python3 bench.py --full --workload c3l24 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3l24_bf16.json 2>> $O/err.txt
+  python3 bench.py --full --workload c3 --ragged --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_ragged.json 2>> $O/err.txt
+  python3 bench.py --full --workload c3 --packed --ragged --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_ragged_packed.json 2>> $O/err.txt
+  python3 bench.py --full --workload c2 --dtype fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c2_fp32.json 2>> $O/err.txt
+  python3 bench.py --full --workload c3 --dtype fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_fp32.json 2>> $O/err.txt
+  python3 bench.py --full --workload c3b256 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_b256_bf16.json 2>> $O/err.txt
+  python3 bench.py --full --workload c3 --grad-fp32 --secondary none --no-cpu-baseline --no-parity-leg > $O/bench_c3_bf16_grad_fp32.json 2>> $O/err.txt
   for m in base large; do
     python3 tools/bench_text_encoder.py --model $m > $O/f4_text_encoder_${m}_bf16.json 2>> $O/err.txt
     python3 tools/bench_text_encoder.py --model $m --dtype fp8 > $O/f4_text_encoder_${m}_fp8.json 2>> $O/err.txt

@@ -14,7 +14,7 @@ PY
 done
 ( export M2F_LIB=$PWD/multimodal-emotion-recognition_amd/csrc/libm2fnet_hip_p8timing.so; for S in "1 8192 8192 1024" "0 8192 8192 1024"; do timeout -k 10 120 python tools/p8_timing.py $S 2>&1 | grep -v amdgpu.ids >> $O/p8_phase_totals.txt; done ); cat $O/p8_phase_totals.txt
 for T in 131 132 131 132; do
-  timeout -k 10 200 env M2F_TABLE_TILE=$T python bench.py --steps 50 --warmup 10 --secondary none --no-parity-leg --no-cpu-baseline --repeats 3 --dump-launches $O/launches_$T.txt > $O/bench_$T.json 2> $O/bench_$T.err; echo "bench($T) rc=$?"
+  timeout -k 10 200 env M2F_TABLE_TILE=$T python bench.py --full --steps 50 --warmup 10 --secondary none --no-parity-leg --no-cpu-baseline --repeats 3 --dump-launches $O/launches_$T.txt > $O/bench_$T.json 2> $O/bench_$T.err; echo "bench($T) rc=$?"
   python - <<PY
 import json
 d=json.load(open("$O/bench_$T.json"))

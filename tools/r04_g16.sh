@@ -2,7 +2,7 @@
 O=gpurun_out/r04l; mkdir -p $O
 for F in "" "--grad-bf16" "" "--grad-bf16"; do
   N=$([ -z "$F" ] && echo fp32grad || echo bf16grad)
-  timeout -k 10 200 python bench.py --steps 50 --warmup 10 --secondary none --no-parity-leg --no-cpu-baseline --repeats 3 $F > $O/bench_$N.json 2> $O/bench_$N.err; echo "bench($N) rc=$?"
+  timeout -k 10 200 python bench.py --full --steps 50 --warmup 10 --secondary none --no-parity-leg --no-cpu-baseline --repeats 3 $F > $O/bench_$N.json 2> $O/bench_$N.err; echo "bench($N) rc=$?"
   python - <<PY
 import json
 d=json.load(open("$O/bench_$N.json"))
