@@ -273,6 +273,35 @@ int m2f_quantize_fp8(const float* src, uint8_t* dst, int64_t n, float scale, m2f
  * operand ring, 128x128 tiles; taken by k-contiguous launches of at least M2F_RING_MIN = 200 such tiles unless M2F_RING=0).
  * Diagnostic: lets a test assert that the form it means to check actually ran. */
 long long m2f_gemm_ring_launches(void);
+/* The kernel form the last m2f_gemm / m2f_gemm_fp8 / m2f_gemm_p8 call (or any GEMM launch of a plan) dispatched to: one
+ * M2F_FORM_* value, plus M2F_FORM_VEC when the fp32-source or skinny kernel moves its operands in 16-byte chunks, M2F_FORM_SRC16
+ * when the skinny kernel reads bf16 shadows, and M2F_FORM_NN_T when a bf16 NN launch ran as the k-contiguous form through the
+ * transposed shadows; M2F_FORM_NONE after a call that launched nothing.  Host-side diagnostic: lets a test assert the kernel it covers. */
+int m2f_gemm_last_form(void);
+enum {
+    M2F_FORM_NONE = 0,
+    M2F_FORM_F32SRC_64 = 1,            /* m2f_gemm_kernel: fp32 mode, or bf16 mode staged from fp32 originals; 64x64 tiles */
+    M2F_FORM_F32SRC_128 = 2,           /* ... 128x128 tiles */
+    M2F_FORM_F32SRC_SPLITK = 3,        /* ... 64x64 tiles, in-launch split-K */
+    M2F_FORM_BF16SRC_64 = 4,           /* m2f_gemm16_kernel: register-staged from bf16 shadows; 64x64 tiles */
+    M2F_FORM_BF16SRC_128 = 5,          /* ... 128x128 tiles */
+    M2F_FORM_BF16SRC_256x128 = 6,      /* ... 256x128 tiles */
+    M2F_FORM_RING_64x64 = 7,           /* m2f_gemm16_ring_kernel, gemm_ring.h */
+    M2F_FORM_RING_128x64 = 8,
+    M2F_FORM_RING_128x128 = 9,
+    M2F_FORM_RING_256x128 = 10,
+    M2F_FORM_P8_KC = 11,               /* eight-phase 256x256 form, gemm_p8.h: k-contiguous operands */
+    M2F_FORM_P8_RC = 12,               /* ... row-major (weight-gradient) operands, table launch */
+    M2F_FORM_SKINNY_NT = 13,           /* skinny.hip: the classifier head */
+    M2F_FORM_SKINNY_NN = 14,
+    M2F_FORM_FP8_128x128 = 15,         /* register-staged e4m3 form */
+    M2F_FORM_FP8_256x128 = 16,
+    M2F_FORM_FP8_RING = 17,            /* ring form, 256x128 tiles, e4m3 operands */
+    M2F_FORM_FP8_P8 = 18,              /* eight-phase form, e4m3 operands */
+    M2F_FORM_VEC = 0x100,
+    M2F_FORM_SRC16 = 0x200,
+    M2F_FORM_NN_T = 0x400
+};
 
 /* C[M,N] = epilogue(A x B); layout 0: C = A[M,K] B[N,K]^T (nn.Linear forward), 1: C = A[M,K] B[K,N]
  * (input gradient), 2: C = A[K,M]^T B[K,N] (weight gradient; bias_grad[M] = column sums of A).

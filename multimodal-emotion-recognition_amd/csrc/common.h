@@ -86,7 +86,7 @@ __device__ __forceinline__ uint32_t m2f_fp8x4_bits(float a, float b, float c, fl
 }
 
 #ifdef __HIPCC__
-// erf for the GELU epilogues.  POLY (bf16 / fp8 kernels): odd degree-13 minimax polynomial on |z| <= 3, max error 4.3e-4
+// erf for the GELU epilogues.  POLY (bf16 / fp8 kernels): odd degree-13 minimax polynomial on |z| <= 3, max error 4.33e-4
 // (far inside bf16 operand rounding), 7 FMAs, no quarter-rate instructions; otherwise Abramowitz-Stegun 7.1.26 (1.5e-7) on
 // the hardware exp / rcp (libm's erff is several times slower still).
 template <bool POLY>

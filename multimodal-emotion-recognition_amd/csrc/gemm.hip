@@ -1049,6 +1049,8 @@ hipError_t launch_cfg16(const GemmBatch& gb, int total_tiles, hipStream_t stream
     }
     void (*kern)(const GemmBatch);
     static_assert(!(DENSE && GELU), "the GELU epilogue exists for the wide forward-form kernels only");
+    m2f_g_last_form = FP8 ? (BM == 256 ? M2F_FORM_FP8_256x128 : M2F_FORM_FP8_128x128)
+                          : (BM == 256 ? M2F_FORM_BF16SRC_256x128 : BM == 128 ? M2F_FORM_BF16SRC_128 : M2F_FORM_BF16SRC_64);
     if constexpr (DENSE) kern = m2f_gemm16_dense_kernel<A_RC, B_RC, BM, BN, BK, D>;
     else kern = m2f_gemm16_kernel<A_RC, B_RC, BM, BN, BK, D, GELU, FP8>;
     if (lds > 64 * 1024) {
@@ -1070,6 +1072,9 @@ hipError_t launch_cfg(const GemmBatch& gb, int total_tiles, hipStream_t stream) 
     constexpr int lds = 2 * SA::LDS_BYTES + 2 * SB::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = m2f_gemm_kernel<PREC, A_RC, B_RC, BM, BN, BK, VEC, GELU>;
+    bool split = false;
+    for (int i = 0; i < gb.count; ++i) split = split || gb.pr[i].splitk > 1;
+    m2f_g_last_form = (BM == 128 ? M2F_FORM_F32SRC_128 : split ? M2F_FORM_F32SRC_SPLITK : M2F_FORM_F32SRC_64) | (VEC ? M2F_FORM_VEC : 0);
     if (lds > 64 * 1024) {
         static bool attr_set = false;
         if (!attr_set) {
@@ -1375,6 +1380,7 @@ hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream) {
 hipError_t m2f_ring_launch_256x128_fp8(GemmBatch& gb, hipStream_t stream);      // gemm_ring_256x128_fp8.hip
 
 hipError_t m2f_launch_gemm_fp8(GemmBatch& gb, hipStream_t stream) {
+    m2f_g_last_form = M2F_FORM_NONE;
     if (gb.count != 1) return hipErrorInvalidValue;
     GemmProblem& p = gb.pr[0];
     if (p.M <= 0 || p.N <= 0 || p.a.k[0] <= 0 || p.a.k[1] != 0 || p.a.k[0] != p.b.k[0] || (p.a.k[0] & 15) || !p.a.q[0] || !p.b.q[0] ||
@@ -1397,8 +1403,10 @@ hipError_t m2f_launch_gemm_fp8(GemmBatch& gb, hipStream_t stream) {
         static const int ring8 = getenv("M2F_RING_FP8") ? atoi(getenv("M2F_RING_FP8")) : 1;
         const bool small = (size_t)p.M * p.a.ldq[0] * 2 < 0x80000000ull && (size_t)p.N * p.b.ldq[0] * 2 < 0x80000000ull;
         const bool whole = p.M % 256 == 0 && p.N % 128 == 0;       // (the ring epilogue writes e4m3 results of whole tiles only)
-        if (ring8 && small && m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 128) >= 256 && !(p.flags & GF_RELU_OUT) && (!p.c8 || whole))
+        if (ring8 && small && m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 128) >= 256 && !(p.flags & GF_RELU_OUT) && (!p.c8 || whole)) {
+            m2f_g_last_form = M2F_FORM_FP8_RING;
             return m2f_ring_launch_256x128_fp8(gb, stream);
+        }
     }
     int tile_m = 256, tile_n = 128;
     if (m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 128) < 1024) { tile_m = 128; tile_n = 128; }
@@ -1432,6 +1440,7 @@ bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout) {
 }
 
 hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStream_t stream) {
+    m2f_g_last_form = M2F_FORM_NONE;
     if (gb.count <= 0 || gb.count > M2F_GEMM_MAX_PROBLEMS) return hipErrorInvalidValue;
     const bool a_rc = layout == M2F_LAYOUT_TN;
     const bool b_rc = layout != M2F_LAYOUT_NT;
@@ -1460,7 +1469,11 @@ hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStr
             GemmBatch t = gb;
             for (int i = 0; i < t.count; ++i)
                 for (int sgm = 0; sgm < 2; ++sgm) { t.pr[i].b.q[sgm] = t.pr[i].b.qt[sgm]; t.pr[i].b.ldq[sgm] = t.pr[i].b.ldqt[sgm]; }
-            if (src16_ok(t, false, false)) return launch_tile16<false, false>(t, tile, stream);
+            if (src16_ok(t, false, false)) {
+                const hipError_t e = launch_tile16<false, false>(t, tile, stream);
+                m2f_g_last_form |= M2F_FORM_NN_T;
+                return e;
+            }
         }
     }
     if (prec == M2F_PREC_BF16 && src16_ok(gb, a_rc, b_rc)) {

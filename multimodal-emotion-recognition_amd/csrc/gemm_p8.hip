@@ -17,6 +17,7 @@ static int p8_skew_env() {
 
 hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream) {
     GemmBatch hb = gb;                                   // (ReLU on the A operand has no loop copy in this form: m2f_gemm_p8_table_ok)
+    m2f_g_last_form = M2F_FORM_P8_RC;
     if (!hb.p8_max_tiles) hb.p8_skew = 0;               // (the plan / the test entry fill p8_max_tiles from the walk)
     else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
     return launch_p8_grid<true, true, 1>(hb, hb.total_tiles, stream);
@@ -25,6 +26,7 @@ hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream) {
 // forward-form launches whose epilogue is bias / ReLU / GELU / residual (m2f_gemm_ring256_ok) and whose k is a multiple of 64
 hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream) {
     gb.p8_skew = p8_skew_env();
+    m2f_g_last_form = M2F_FORM_P8_KC;
     return launch_p8_grouped<false, 2>(gb, stream);
 }
 
@@ -32,6 +34,7 @@ hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream) {
 // the staging code moves 16-byte chunks of a row whatever they hold): de-quantising epilogue, fp32 / bf16 / e4m3 result
 hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream) {
     gb.p8_skew = p8_skew_env();
+    m2f_g_last_form = M2F_FORM_FP8_P8;
     return launch_p8_grouped<false, 4>(gb, stream);
 }
 
@@ -71,6 +74,7 @@ extern "C" int m2f_gemm_p8(int rc, int M, int N, int K, const uint16_t* a, int l
                            const float* bias, const float* res, int ldres, int act, int relu_a, int relu_b, float* bias_grad,
                            void* scratch, int64_t scratch_bytes, int n_wg, m2f_stream_t stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
+    m2f_g_last_form = M2F_FORM_NONE;
     GemmBatch gb;
     memset(&gb, 0, sizeof(gb));
     GemmProblem p;

@@ -4,8 +4,10 @@
 #include "ops.h"
 
 long long m2f_g_ring_launches = 0;
+int m2f_g_last_form = M2F_FORM_NONE;
 
 extern "C" long long m2f_gemm_ring_launches(void) { return m2f_g_ring_launches; }
+extern "C" int m2f_gemm_last_form(void) { return m2f_g_last_form; }
 
 hipError_t m2f_ring_launch_128x128(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_ring_launch_128x64(GemmBatch& gb, hipStream_t stream);
@@ -38,6 +40,7 @@ bool m2f_gemm_ring256_ok(const GemmBatch& gb) {
 }
 
 hipError_t m2f_launch_gemm_ring(GemmBatch& gb, int bm, int bn, hipStream_t stream) {
+    m2f_g_last_form = bm == 256 ? M2F_FORM_RING_256x128 : bm == 64 ? M2F_FORM_RING_64x64 : bn == 64 ? M2F_FORM_RING_128x64 : M2F_FORM_RING_128x128;
     if (bm == 128 && bn == 128) return m2f_ring_launch_128x128(gb, stream);
     if (bm == 128 && bn == 64) return m2f_ring_launch_128x64(gb, stream);
     if (bm == 64 && bn == 64) return m2f_ring_launch_64x64(gb, stream);

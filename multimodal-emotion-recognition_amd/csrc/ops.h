@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/m2fnet_hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // Grouped GEMM:  C[M,N] = epilogue( sum_k A(m,k) * B(n,k) )
@@ -119,6 +120,7 @@ struct M2FAdamFuse {
 #define M2F_SPLITK_MAX_TILES 512
 
 // RING form of the k-contiguous bf16 GEMM (gemm_ring.h): bm x bn = 128x128 or 128x64; the table form walks gb.table.
+extern int m2f_g_last_form;        // host-side record of the kernel form the last GEMM launch dispatched to (M2F_FORM_*, gemm_ring.hip)
 int m2f_launch_gemm_skinny(const GemmBatch& gb, int prec, int layout, hipStream_t stream);      // skinny.hip: 1 launched, 0 not skinny, < 0 error
 bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout);      // host: does the bf16-mode launch read bf16 shadows only?
 bool m2f_gemm_ring_ok(const GemmBatch& gb);

@@ -206,6 +206,7 @@ int m2f_launch_gemm_skinny(const GemmBatch& gb, int prec, int layout, hipStream_
                 (!s.gate || ((s.ldgate & 3) == 0 && al(s.gate, 16))) &&
                 (use16 ? ((s.ldb16 & 3) == 0 && al(s.b16, 8)) : ((s.ldb & 3) == 0 && al(s.b, 16)));
     }
+    m2f_g_last_form = (nt ? M2F_FORM_SKINNY_NT : M2F_FORM_SKINNY_NN) | (s.vec ? M2F_FORM_VEC : 0) | (use16 ? M2F_FORM_SRC16 : 0);
     if (nt) hipLaunchKernelGGL(m2f_skinny_nt_kernel, dim3((p.M + 3) / 4), dim3(256), 0, stream, s);
     else hipLaunchKernelGGL(m2f_skinny_nn_kernel, dim3((unsigned)(((size_t)p.M * ((p.N + 3) >> 2) + 255) / 256)), dim3(256), 0, stream, s);
     const hipError_t e = hipGetLastError();

@@ -249,18 +249,22 @@ def w2v_conv0(wave: torch.Tensor, w0: torch.Tensor, gamma: torch.Tensor, beta: t
     return out
 
 
-def w2v_conv_layer(x: torch.Tensor, w: torch.Tensor, stride: int, P_in: int, precision: int = runtime.F32) -> torch.Tensor:
+def w2v_conv_layer(x: torch.Tensor, w: torch.Tensor, stride: int, P_in: int, precision: int = runtime.F32,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One conv layer of the wav2vec2 front end (Conv1d(C, C, k, stride, bias=False) + exact GELU) on the grouped GEMM, the way
     wav2vec2.py runs it: x [rows >= B * P_in + 1, C] holds utterance b's frames at rows b * P_in + t (P_in a multiple of stride;
     the row behind the last pitch must exist: the last junk window reads it).  Returns [B * P_in / stride, C], output frame t of
-    utterance b at row b * P_in / stride + t.  w [C, C, k] with stride <= k <= 2 * stride."""
+    utterance b at row b * P_in / stride + t.  w [C, C, k] with stride <= k <= 2 * stride.  `out`: a contiguous [B * P_in / stride, C]
+    buffer to write instead of a new one."""
     runtime.require_gpu()
     C, _, k = w.shape
     assert P_in % stride == 0 and stride <= k <= 2 * stride and x.is_contiguous() and x.shape[1] == C
     B = (x.shape[0] - 1) // P_in
     M, ld, K0, K1 = B * P_in // stride, stride * C, stride * C, (k - stride) * C
     weff = w.permute(0, 2, 1).reshape(C, k * C).float().contiguous()
-    out = torch.empty(M, C, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(M, C, dtype=torch.float32, device=x.device)
+    assert out.shape == (M, C) and out.is_contiguous() and out.dtype == torch.float32
     bf16 = precision == runtime.BF16
     x16 = x.to(torch.bfloat16).contiguous() if bf16 else None
     w16 = weff.to(torch.bfloat16).contiguous() if bf16 else None
@@ -292,13 +296,16 @@ def w2v_pack_pos_weight(w: torch.Tensor, groups: int, bf16: bool = False) -> tor
 
 
 def w2v_pos_conv(x: torch.Tensor, lengths: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, groups: int, B: int, S: int,
-                 bf16: bool = False) -> torch.Tensor:
+                 bf16: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [B * S, d] -> x + GELU(grouped conv(x) + bias) with padding K / 2, the extra frame of an even K dropped, rows at or past
-    lengths[b] of x read as zero (the residual too).  w [d, d / groups, K] fp32."""
+    lengths[b] of x read as zero (the residual too).  w [d, d / groups, K] fp32.  `out`: a contiguous fp32 buffer shaped like x to
+    write instead of a new one."""
     runtime.require_gpu()
     d = x.shape[1]
     K = w.shape[2]
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.is_contiguous() and out.dtype == torch.float32
     wpk = w2v_pack_pos_weight(w, groups, bf16)
     l32 = lengths.to(x.device, torch.int32).contiguous()
     check(lib().m2f_w2v_pos_conv(B, S, d, groups, K, ptr(x.contiguous()), ptr(l32), ptr(wpk), ptr(bias), ptr(out), int(bf16),
