@@ -304,7 +304,8 @@ enum {
 };
 
 /* C[M,N] = epilogue(A x B); layout 0: C = A[M,K] B[N,K]^T (nn.Linear forward), 1: C = A[M,K] B[K,N]
- * (input gradient), 2: C = A[K,M]^T B[K,N] (weight gradient; bias_grad[M] = column sums of A).
+ * (input gradient), 2: C = A[K,M]^T B[K,N] (weight gradient; bias_grad[M] = column sums of A; with accumulate != 0 both C and
+ * bias_grad accumulate: bias_grad[M] += the column sums).
  * Optional second operand segment (a1/b1, k1) = never-materialised torch.cat along the reduction dim. */
 int m2f_gemm(int precision, int layout, int M, int N, int K0, int K1,
              const float* a0, int lda0, const float* a1, int lda1,
@@ -342,6 +343,16 @@ int m2f_adam_hyper(float* hyper_dev, float lr, float beta1, float beta2, float e
  * the all-reduce), all others through one cast launch behind the backward.  The fp32 buffer then holds only those others (and the loss
  * tail).  m2f_plan_grad_bf16(plan, NULL) restores fp32 gradients.  Same bits as rounding the fp32 gradients of a plain step. */
 int m2f_plan_grad_bf16(m2f_plan* plan, uint16_t* grads_bf16);
+
+/* Gradient accumulation over micro-batches: while m2f_plan_accumulate_grads(plan, 1) is on, m2f_backward / m2f_step of the plan ADD
+ * every parameter gradient into `grads` (old + new, one rounded fp32 add of the value the overwrite form stores: the sum of two
+ * backwards equals the fp32 sum of their overwrite-form gradients bit for bit), and m2f_loss / m2f_step add den and num of the
+ * criterion tail (grads[n_params + 1], grads[n_params + 2]) to what it holds; grads[n_params] is still this batch's num / den.  The
+ * caller zeroes what starts a group.  Plans that share one gradient buffer accumulate into it together.  The accumulate launch lists
+ * and the step graph of that form are built the first time it is switched on (a plan that never accumulates keeps its lists and graph);
+ * m2f_plan_accumulate_grads(plan, 0) restores the overwrite form.  Fails for a plan without a gradient buffer, with fused Adam on or
+ * bf16 gradients armed; while it is on, m2f_step_part, m2f_plan_fused_adam(plan, 1) and m2f_plan_grad_bf16(plan, non-NULL) fail. */
+int m2f_plan_accumulate_grads(m2f_plan* plan, int on);
 
 /* The 256x256-tile bf16 GEMM on the eight-phase schedule (csrc/gemm_p8.h; round 4), bf16 operands handed over directly - the kernel
  * the weight-gradient table launch (rc = 1) and the text encoder's launches (rc = 0) run, for kernel-level tests and measurements.

@@ -520,7 +520,8 @@ __global__ __launch_bounds__(256) void m2f_gemm_kernel(const GemmBatch gb) {
             if (tid < BM) {
                 float sum = 0.f;
                 for (int q = 0; q < G; ++q) sum += red[q * BM + tid];
-                if (m0 + tid < M) P.bias_grad[m0 + tid] = sum;
+                // (GF_ACCUM, the accumulate form of a weight gradient: the bias gradient accumulates with C - old + new, as C does)
+                if (m0 + tid < M) P.bias_grad[m0 + tid] = (P.flags & GF_ACCUM) ? P.bias_grad[m0 + tid] + sum : sum;
             }
         }
     }
@@ -1007,7 +1008,8 @@ k_tiles_done:
             if (tid < BM) {
                 float sum = 0.f;
                 for (int q = 0; q < KP; ++q) sum += red[q * BM + tid];
-                if (m0 + tid < M) P.bias_grad[m0 + tid] = sum;
+                // (GF_ACCUM, the accumulate form of a weight gradient: the bias gradient accumulates with C - old + new, as C does)
+                if (m0 + tid < M) P.bias_grad[m0 + tid] = (P.flags & GF_ACCUM) ? P.bias_grad[m0 + tid] + sum : sum;
             }
         }
     }
@@ -1375,6 +1377,11 @@ extern "C" int m2f_dbg_read(unsigned long long* out) {
 hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream) {
     if (!gb.table || gb.total_tiles <= 0) return hipErrorInvalidValue;
     return gb.table_p8 ? m2f_p8_launch_table_rc(gb, stream) : m2f_ring_launch_table_rc_256x128(gb, stream);
+}
+
+hipError_t m2f_launch_gemm_table_acc(const GemmBatch& gb, hipStream_t stream) {
+    if (!gb.table || gb.total_tiles <= 0) return hipErrorInvalidValue;
+    return gb.table_p8 ? m2f_p8_launch_table_rc_acc(gb, stream) : m2f_ring_launch_table_rc_256x128_acc(gb, stream);
 }
 
 hipError_t m2f_ring_launch_256x128_fp8(GemmBatch& gb, hipStream_t stream);      // gemm_ring_256x128_fp8.hip

@@ -139,6 +139,12 @@ __device__ __forceinline__ void p8_adam4(f32x4& pp, const f32x4& gg, f32x4& mm, 
 //          and step, and the HBM-bound optimizer streams while other workgroups multiply)
 // EPI: 1 = plain fp32 result (the weight-gradient table: + bias-gradient row sums, ReLU on either operand's fragments),
 //      2 = text-encoder launches: bias, ReLU / GELU, residual, fp32 result unless GF_NO_F32, bf16 shadow
+//      5 = the ACCUMULATE form of 1 (m2f_plan_accumulate_grads): every dW element and bias-gradient row leaves as old + new, one rounded
+//          fp32 add of the value EPI 1 would store (no bf16 gradient, no Adam).  The old dW is read AFTER the k-loop, in two batches of
+//          sixteen 16-byte loads per lane as the residual of EPI 2 is: the compiler's wait for them also drains the prefetch pieces of the
+//          next tile issued before them (a deliberate drain, this form only - the counted waits of the k-loop see no extra operation
+//          outstanding, and ep_relax stays the store count).  Loading the old dW under the last k-tiles instead would hold 128 more
+//          VGPRs across the MFMA loop of a 256 x 256 tile that already keeps 128 accumulators per lane.
 template <bool RC, bool TABLE, int EPI>
 __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
     using C = P8Cfg;
@@ -165,6 +171,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
     // range-checked to zeros AND redirected into a 2 KiB dump area behind the operand buffers (the wave's W^T image, unused until then)
     constexpr bool PER_TILE = EPI == 3;
     constexpr bool FWD = EPI == 2 || EPI == 4;          // forward-form epilogue (bias / activation / residual); 4: OCP e4m3 operands (see quad)
+    constexpr bool ACC = EPI == 5;                       // weight-gradient table, accumulate form
+    constexpr bool WG = EPI == 1 || ACC;                 // weight-gradient table (overwrite or accumulate)
     unsigned s_dump = 0;                                           // 0 = normal destinations
     unsigned s_kA = 0, s_kB = 0, s_stepA = 0, s_stepB = 0, s_halfA = 0, s_halfB = 0, vA[2], vB[2];
     ring_u32x4 ra, rb;
@@ -334,8 +342,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
         const auto& P = *(TABLE ? (c_probp)(gb.table) + H.pi : (c_probp)(const GemmProblem*)&gb.pr[H.pi]);
         const int m0 = H.m0, n0 = H.n0, nk = (H.K + C::BK - 1) / C::BK;
         const bool reluA = false, reluB = H.flags & GF_RELU_B;
-        float* bias_grad = (EPI == 1 || EPI == 3) ? P.bias_grad : nullptr;
-        const bool bgrad = (EPI == 1 || EPI == 3) && RC && bias_grad && n0 == 0 && wc == 0;      // wave-uniform
+        float* bias_grad = (WG || EPI == 3) ? P.bias_grad : nullptr;
+        const bool bgrad = (WG || EPI == 3) && RC && bias_grad && n0 == 0 && wc == 0;      // wave-uniform
         float bsum[2][4];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -363,7 +371,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
         uint8_t* __restrict__ C8 = EPI == 4 ? P.c8 : nullptr;
         // EPI 1, `res` set: the weight gradient leaves as bf16 INSTEAD of fp32, at the same element index of a bf16 gradient buffer (the
         // data-parallel bf16 exchange sends that buffer as it is: no fp32 dW round trip, no rounding pass; m2f_plan_grad_bf16)
-        uint16_t* __restrict__ G16 = EPI == 1 ? reinterpret_cast<uint16_t*>(const_cast<float*>(P.res)) : nullptr;
+        uint16_t* __restrict__ G16 = EPI == 1 ? reinterpret_cast<uint16_t*>(const_cast<float*>(P.res)) : nullptr;      // (EPI 5: none)
 
         auto quad = [&](auto a_tag, auto b_tag, const bf16x8 (&bb)[2][2]) {
             constexpr int AH = decltype(a_tag)::value, BH = decltype(b_tag)::value;
@@ -517,7 +525,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
 #else
 #define P8_LOOP(MASK) do { _Pragma("unroll 1") for (int kt = 0; kt < nk; ++kt) { ktile(par, std::integral_constant<int, MASK>{}, kt == 0 ? ep_relax : 0); par ^= 1; } } while (0)
 #endif
-        const int optm = (EPI == 1 || EPI == 3) ? (bgrad ? 1 : 0) | (reluA ? 2 : 0) | (reluB ? 4 : 0) : 0;
+        const int optm = (WG || EPI == 3) ? (bgrad ? 1 : 0) | (reluA ? 2 : 0) | (reluB ? 4 : 0) : 0;
         if (optm == 0) P8_LOOP(0);
         else if (optm == 1) P8_LOOP(1);
         else if (optm == 4) P8_LOOP(4);
@@ -535,7 +543,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                     float t = bsum[a][i];
                     t += __shfl_xor(t, 16); t += __shfl_xor(t, 32);
                     const int m = m0 + a * 128 + wr * 64 + i * 16 + lr;
-                    if (g == 0 && m < Mm) bias_grad[m] = t;
+                    if constexpr (ACC) { if (g == 0 && m < Mm) bias_grad[m] = bias_grad[m] + t; }
+                    else { if (g == 0 && m < Mm) bias_grad[m] = t; }
                 }
         }
         if constexpr (EPI == 3) {
@@ -737,6 +746,28 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                     }
                 }
             }
+            if constexpr (ACC) {
+                // old dW, two batches of sixteen loads (see EPI 5 above): acc = acc + old, element by element
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    f32x4 ov[2][4][2];
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) {
+                                const int row = m0 + a * 128 + wr * 64 + i * 16 + lr, col = n0 + b * 128 + wc * 32 + j * 16 + 4 * g;
+                                ov[b][i][j] = *reinterpret_cast<const f32x4*>(Cp + (size_t)((uint32_t)(row * ldc + col)));
+                            }
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) acc[a][b][i][j] = ov[b][i][j] + acc[a][b][i][j];
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);                   // (no store may move above the last residual load)
             uint16_t* __restrict__ O16 = EPI == 1 ? G16 : C16;
 #pragma unroll
@@ -803,7 +834,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                                     if (bias && in) bvv = bias[col + e];
                                     if (res && in) rvv = res[(size_t)((uint32_t)(row * ldres + col + e))];
                                 }
-                                const float x = element(v[e], bvv, rvv);
+                                float x = element(v[e], bvv, rvv);
+                                if constexpr (ACC) { if (in) x = Cp[oc] + x; }
                                 if (in && EPI == 1 && G16) G16[oc] = m2f_bf16_bits(x);
                                 else if (in && C8) C8[oc] = (uint8_t)(m2f_fp8x4_bits(x * c8_scale, 0.f, 0.f, 0.f) & 0xffu);
                                 else if (in) {

@@ -15,13 +15,18 @@ static int p8_skew_env() {
     return v;
 }
 
-hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream) {
+// the table launch: EPI 1 = overwrite, EPI 5 = accumulate (dW and the bias gradients leave as old + new; m2f_plan_accumulate_grads -
+// its own instantiation, so the overwrite form compiles as it did; fp contraction is off for the whole unit: gemm_ring.h's pragma)
+template <int EPI>
+static hipError_t p8_launch_table(const GemmBatch& gb, hipStream_t stream) {
     GemmBatch hb = gb;                                   // (ReLU on the A operand has no loop copy in this form: m2f_gemm_p8_table_ok)
     m2f_g_last_form = M2F_FORM_P8_RC;
     if (!hb.p8_max_tiles) hb.p8_skew = 0;               // (the plan / the test entry fill p8_max_tiles from the walk)
     else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
-    return launch_p8_grid<true, true, 1>(hb, hb.total_tiles, stream);
+    return launch_p8_grid<true, true, EPI>(hb, hb.total_tiles, stream);
 }
+hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream) { return p8_launch_table<1>(gb, stream); }
+hipError_t m2f_p8_launch_table_rc_acc(const GemmBatch& gb, hipStream_t stream) { return p8_launch_table<5>(gb, stream); }
 
 // forward-form launches whose epilogue is bias / ReLU / GELU / residual (m2f_gemm_ring256_ok) and whose k is a multiple of 64
 hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream) {

@@ -102,7 +102,8 @@ __device__ __forceinline__ RingEpi ring_epilogue_args(const GemmBatch& gb, const
 // EPI selects the set of term combinations compiled in: 0 = all 16 (dropout site / gate / residual / accumulate), 1 = none
 // (the weight-gradient table), 2 = {-, residual} x {-, GELU} (the in-loop text encoder's launches: 256x128 tiles hold 128
 // accumulator registers, the full set would spill - a fifth variant already sends the accumulators to scratch), 3 = bias only,
-// with or without the fp32 store (GF_NO_F32)
+// with or without the fp32 store (GF_NO_F32), 5 = accumulate only (the weight-gradient table's accumulate form: C = old C + the value
+// EPI 1 stores; the consumer waves issue no LDS-DMA, so these loads share the counter with nothing the producers count)
 template <int MI, int NI, int BM, int BN, int EPI = 0>
 __device__ __forceinline__ void ring_epilogue(const GemmBatch& gb, const RingEpi& E, f32x16 (&acc)[MI][NI], int m0, int n0,
                                               int lane, int wm, int wn, char* ep) {
@@ -116,7 +117,7 @@ __device__ __forceinline__ void ring_epilogue(const GemmBatch& gb, const RingEpi
     const float c8s = E.c8_scale;
     const int ldc = E.ldc, ldres = E.ldres, ldgate = E.ldgate;
     const float gscale = E.gscale;
-    const bool relu_out = E.relu_out, accum = E.accum, vec = E.vec, w32 = !E.no32;
+    const bool relu_out = E.relu_out, accum = EPI == 5 ? true : E.accum, vec = E.vec, w32 = !E.no32;
     const uint32_t site = E.site, key = E.key;
     // F = which optional terms this launch has (block-uniform): 1 dropout site, 2 gate, 4 residual, 8 accumulate.  As runtime
     // branches inside the per-element code they made the epilogue ~45 instructions per element (10k cycles per 128x128
@@ -217,6 +218,7 @@ __device__ __forceinline__ void ring_epilogue(const GemmBatch& gb, const RingEpi
         // (bit 32 = no fp32 store; never together with accumulate, which reads C)
         const int fmask = EPI == 1 ? 0 : (site ? 1 : 0) | (gate ? 2 : 0) | (res ? 4 : 0) | (accum ? 8 : 0) | (E.gelu ? 16 : 0) | (w32 ? 0 : 32);
         if constexpr (EPI == 1) blocks(std::integral_constant<int, 0>{});
+        else if constexpr (EPI == 5) blocks(std::integral_constant<int, 8>{});
         else if constexpr (EPI == 2) {
             switch (fmask & ~32) {                                  // (the launcher admits nothing else: m2f_gemm_ring_ok)
                 case 0: blocks(std::integral_constant<int, 0>{}); break;
@@ -719,7 +721,8 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
                 for (int i = 0; i < MI; ++i) {
                     const float tot = bsum[i] + __shfl_xor(bsum[i], 32);
                     const int m = m0 + wm * (BM / 2) + i * 32 + (lane & 31);
-                    if (lane < 32 && m < H.M) H.bias_grad[m] = tot;
+                    if constexpr (EPI == 5) { if (lane < 32 && m < H.M) H.bias_grad[m] = H.bias_grad[m] + tot; }
+                    else { if (lane < 32 && m < H.M) H.bias_grad[m] = tot; }
                 }
             }
         }

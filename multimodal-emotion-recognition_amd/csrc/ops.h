@@ -127,18 +127,22 @@ bool m2f_gemm_ring_ok(const GemmBatch& gb);
 bool m2f_gemm_ring256_ok(const GemmBatch& gb);       // 256x128 tiles: bias / ReLU / GELU / residual epilogues only
 hipError_t m2f_launch_gemm_ring(GemmBatch& gb, int bm, int bn, hipStream_t stream);
 hipError_t m2f_ring_launch_table_rc_256x128(const GemmBatch& gb, hipStream_t stream);      // the table form, 256 x 128 tiles (gemm_ring_table.hip)
+hipError_t m2f_ring_launch_table_rc_256x128_acc(const GemmBatch& gb, hipStream_t stream);  // ... its accumulate form, old + new (gemm_ring_table_acc.hip)
 // eight-phase 256x256 form (gemm_p8.h): forward-form launches with the 256x128 ring form's epilogue set, single segment, k % 64 == 0
 bool m2f_gemm_p8_ok(const GemmBatch& gb);
 hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream);     // Adam in the epilogue (gb.adam)
+hipError_t m2f_p8_launch_table_rc_acc(const GemmBatch& gb, hipStream_t stream);      // accumulate form: dW, bias gradients = old + new
 
 // Launches one grouped GEMM. Returns hipSuccess or the launch error. `tile` = 0 (auto), 64 or 128.
 hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStream_t stream);
 // TABLE form, bf16 mode: the weight-gradient launch dW = dY^T X on the row-major bf16 shadows gb.table[i].{a,b}.q (reduction
 // over their rows), optional ReLU on either operand and the bias gradient (column sums of A); plain stores of C.
 hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream);
+// the same launch in its accumulate form (m2f_plan_accumulate_grads): every dW element and bias gradient = old + new, one rounded fp32 add
+hipError_t m2f_launch_gemm_table_acc(const GemmBatch& gb, hipStream_t stream);
 // fp8 (OCP e4m3) operands, forward form only, single problem: C = act(acc_scale * A8 B8^T + bias) + res.  K % 16 == 0,
 // lda / ldb % 16 == 0, 16-byte aligned operands.  (SURVEY 8-f4 / BASELINE C5: the text encoder's GEMMs.)
 hipError_t m2f_launch_gemm_fp8(GemmBatch& gb, hipStream_t stream);
@@ -255,7 +259,8 @@ static inline int m2f_ln_row_blocks(int T) { return (T + M2F_LN_ROWS_PER_BLOCK -
 struct LnReduceItem { const float* partial; float* dgamma; float* dbeta; int d; int nblk; };
 #define M2F_LNRED_MAX_ITEMS 32
 struct LnReduceBatch { LnReduceItem it[M2F_LNRED_MAX_ITEMS]; int count; };
-hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t stream);
+// accumulate != 0: dgamma / dbeta = old + the reduced sum (the accumulate form of the backward, m2f_plan_accumulate_grads)
+hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t stream, int accumulate = 0);
 
 // Criterion of src/train.py:48-50 on logits [T, C] (C <= 16): CrossEntropyLoss(ignore_index=-1,
 // label_smoothing, optional class weights).  Per token it writes the loss numerator / denominator
@@ -272,8 +277,9 @@ hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream);
 // loss_out[0] = num/den, loss_out[1] = den, loss_out[2] = num.  normalise != 0: dlogits *= 1/den
 // (single-process mean-over-valid loss); normalise == 0 leaves the sum-gradient for the data-parallel
 // path, which divides by the GLOBAL denominator after the all-reduce.
+// accumulate != 0: loss_out[1] and loss_out[2] ADD this batch's den and num to what they hold (loss_out[0] is still this batch's num / den)
 hipError_t m2f_launch_loss_finalize(const float* loss_terms, int T, int C, float* dlogits, float* loss_out,
-                                    int normalise, hipStream_t stream);
+                                    int normalise, hipStream_t stream, int accumulate = 0);
 
 // fp32 -> bf16 (round to nearest even) of up to M2F_CAST_MAX_ITEMS 2-D blocks in one launch: dst[r*ldd + c] =
 // bf16(src[r*lds + c]) for c < cols (pad columns of dst are left untouched = zero).

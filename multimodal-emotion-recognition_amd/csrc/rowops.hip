@@ -237,6 +237,8 @@ __global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
 
 // one block = 64 columns of one LayerNorm; its 4 wavefronts each sum a quarter of the row-block partials, then a
 // fixed-order LDS combine (deterministic).  Grid (ceil(max_d / 64), items).
+// ACC (the accumulate form): dgamma / dbeta = old + the sum, one rounded add of the value the overwrite form stores
+template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_ln_param_reduce_kernel(const LnReduceBatch rb) {
     __shared__ float part[4][2][64];
     const LnReduceItem& it = rb.it[blockIdx.y];
@@ -267,8 +269,10 @@ __global__ __launch_bounds__(256) void m2f_ln_param_reduce_kernel(const LnReduce
     part[w][1][lane] = sb;
     __syncthreads();
     if (w == 0 && c < it.d) {
-        it.dgamma[c] = (part[0][0][lane] + part[1][0][lane]) + (part[2][0][lane] + part[3][0][lane]);
-        it.dbeta[c] = (part[0][1][lane] + part[1][1][lane]) + (part[2][1][lane] + part[3][1][lane]);
+        const float dg = (part[0][0][lane] + part[1][0][lane]) + (part[2][0][lane] + part[3][0][lane]);
+        const float db = (part[0][1][lane] + part[1][1][lane]) + (part[2][1][lane] + part[3][1][lane]);
+        if constexpr (ACC) { it.dgamma[c] = it.dgamma[c] + dg; it.dbeta[c] = it.dbeta[c] + db; }
+        else { it.dgamma[c] = dg; it.dbeta[c] = db; }
     }
 }
 
@@ -316,6 +320,8 @@ __global__ __launch_bounds__(256) void m2f_ce_kernel(const CeArgs a) {
     }
 }
 
+// ACC (the accumulate form): den and num are added to loss_out[1], loss_out[2] (a group of micro-batches); loss_out[0] stays this batch's
+template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_loss_finalize_kernel(const float* __restrict__ terms, int T, int C,
                                                                 float* __restrict__ dlogits, float* __restrict__ loss_out,
                                                                 int normalise) {
@@ -328,7 +334,11 @@ __global__ __launch_bounds__(256) void m2f_loss_finalize_kernel(const float* __r
     __syncthreads();
     const float num = (sn[0] + sn[1]) + (sn[2] + sn[3]);
     const float den = (sd[0] + sd[1]) + (sd[2] + sd[3]);
-    if (threadIdx.x == 0) { loss_out[0] = num / den; loss_out[1] = den; loss_out[2] = num; }
+    if constexpr (ACC) {
+        if (threadIdx.x == 0) { loss_out[0] = num / den; loss_out[1] = loss_out[1] + den; loss_out[2] = loss_out[2] + num; }
+    } else {
+        if (threadIdx.x == 0) { loss_out[0] = num / den; loss_out[1] = den; loss_out[2] = num; }
+    }
     if (normalise) {
         const float inv = 1.0f / den;
         for (int e = threadIdx.x; e < T * C; e += 256) dlogits[e] *= inv;
@@ -640,12 +650,13 @@ hipError_t ln_launch(LnBatch& lb, hipStream_t stream) {
 hipError_t m2f_launch_ln_fwd(LnBatch& lb, hipStream_t stream) { return ln_launch<false>(lb, stream); }
 hipError_t m2f_launch_ln_bwd(LnBatch& lb, hipStream_t stream) { return ln_launch<true>(lb, stream); }
 
-hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t stream) {
+hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t stream, int accumulate) {
     if (rb.count <= 0) return hipSuccess;
     if (rb.count > M2F_LNRED_MAX_ITEMS) return hipErrorInvalidValue;
     int maxd = 0;
     for (int i = 0; i < rb.count; ++i) if (rb.it[i].d > maxd) maxd = rb.it[i].d;
-    hipLaunchKernelGGL(m2f_ln_param_reduce_kernel, dim3(m2f_cdiv(maxd, 64), rb.count), dim3(256), 0, stream, rb);
+    if (accumulate) hipLaunchKernelGGL(m2f_ln_param_reduce_kernel<true>, dim3(m2f_cdiv(maxd, 64), rb.count), dim3(256), 0, stream, rb);
+    else hipLaunchKernelGGL(m2f_ln_param_reduce_kernel<false>, dim3(m2f_cdiv(maxd, 64), rb.count), dim3(256), 0, stream, rb);
     return hipGetLastError();
 }
 
@@ -656,8 +667,9 @@ hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream) {
 }
 
 hipError_t m2f_launch_loss_finalize(const float* loss_terms, int T, int C, float* dlogits, float* loss_out,
-                                    int normalise, hipStream_t stream) {
-    hipLaunchKernelGGL(m2f_loss_finalize_kernel, dim3(1), dim3(256), 0, stream, loss_terms, T, C, dlogits, loss_out, normalise);
+                                    int normalise, hipStream_t stream, int accumulate) {
+    if (accumulate) hipLaunchKernelGGL(m2f_loss_finalize_kernel<true>, dim3(1), dim3(256), 0, stream, loss_terms, T, C, dlogits, loss_out, normalise);
+    else hipLaunchKernelGGL(m2f_loss_finalize_kernel<false>, dim3(1), dim3(256), 0, stream, loss_terms, T, C, dlogits, loss_out, normalise);
     return hipGetLastError();
 }
 

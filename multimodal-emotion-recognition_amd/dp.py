@@ -413,6 +413,7 @@ class DataParallelStep:
         self.model, self.optimizer, self.overlap = model, optimizer, bool(overlap)
         self.grad_bf16 = (os.environ.get("M2F_GRAD_BF16", "1") != "0") if grad_bf16 is None else bool(grad_bf16)
         self._split: Optional[int] = None
+        self._pending = False          # micro-batches of this rank since the last synced call wrote the gradient buffer (sync=False)
         eng = model.engine()
         eng.ensure_grad()
         self.reducer = GradReducer(eng.flat_grad_ext, eng.flat.numel(), group, n_buckets, exchange, algorithm)
@@ -438,16 +439,37 @@ class DataParallelStep:
                                "the ranks' gradient collectives would no longer match")
         return self._split
 
+    def _micro_batches_on(self) -> None:
+        """First sync=False call: accumulated gradients stay fp32 (the bf16 exchange casts them per bucket, GradReducer), and the
+        split step has no accumulate form."""
+        if self.overlap and self.reducer.world() > 1:
+            raise RuntimeError("mer_amd.dp: micro-batches (sync=False) do not combine with overlap=True (the split step has no "
+                               "accumulate form)")
+        eng = self.model.engine()
+        if eng.grad_bf16_buf is not None:
+            self.model.set_grad_bf16(False)
+
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
-                 use_graph: bool = True) -> torch.Tensor:
+                 use_graph: bool = True, sync: bool = True) -> torch.Tensor:
+        """sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
+        synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
+        micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
+        global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
         eng = self.model.engine()
         B, L = mask.shape
+        if not sync:
+            self._micro_batches_on()
         cur = torch.cuda.current_stream(eng.device)
         eng.stream.wait_stream(cur)
+        if B == 0 and not sync:                       # empty micro-batch: nothing to contribute, no collective
+            cur.wait_stream(eng.stream)
+            return torch.zeros((), device=eng.device)
         if B == 0:                                    # empty shard: contribute zeros, but take part in every collective
             with torch.cuda.stream(eng.stream):
                 self.reducer.buf16_filled = eng.grad_bf16_buf is not None and eng.grad_bf16_buf is self.reducer.buf16
-                self.reducer.zero_contribution()
+                if not self._pending:                 # (earlier micro-batches of this group wrote the buffer: they are the contribution)
+                    self.reducer.zero_contribution()
+                self._pending = False
                 eng.publish_grads()
                 # the SAME bucket schedule as the ranks that hold dialogues (number, order and sizes of the collectives)
                 split = self.split_for(None)
@@ -464,6 +486,16 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
+            if self._pending or getattr(plan, "_acc", False):
+                plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
+            if not sync:
+                plan.step(label_smoothing, class_weights is not None, False, use_graph)   # tail <- (loss, den += , num += )
+                self._pending = True
+                eng.publish_grads()
+                loss = plan.loss[0].clone()
+                cur.wait_stream(eng.stream)
+                return loss
+            self._pending = False
             split = self.split_for(plan)
             # bf16 exchange, whole-step form: the step itself leaves every gradient rounded in the exchange buffer (the weight-gradient
             # launch writes bf16 dW directly: no fp32 dW round trip, no rounding pass over 4 bytes per parameter before the all-reduce) -

@@ -60,7 +60,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, layout: int = NT, precision: int = ru
     if a1 is not None:
         K1 = a1.shape[0] if layout == TN else a1.shape[1]
     c = out if out is not None else torch.empty(M, N, dtype=torch.float32, device=a.device)
-    bg = torch.empty(M, dtype=torch.float32, device=a.device) if bias_grad else None
+    # (accumulate: the kernel adds the column sums to bias_grad as it adds to C - a fresh buffer starts at zero)
+    bg = (torch.zeros if accumulate else torch.empty)(M, dtype=torch.float32, device=a.device) if bias_grad else None
     ws, tickets, nmax = _splitk_scratch(a.device) if split_k else (None, None, 0)
     # bf16 shadows (test plumbing: in the plan the producer kernels write them): zero-padded to a multiple of 8 columns
     sh = list(shadows) if shadows is not None else [None if (t is None or not src16) else _shadow16(t) for t in (a, a1, b, b1)]

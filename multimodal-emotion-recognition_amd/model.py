@@ -131,6 +131,8 @@ class _Anchor(torch.autograd.Function):
                                "same plan shape (more graphs were kept alive than the plan cache may hold - raise "
                                "M2F_MAX_PLANS / M2F_MAX_PLAN_BYTES, or call backward() before further forwards)")
         plan.set_dlogits(dlogits)
+        if plan.param_grads:
+            ctx.model._engine.begin_backward(plan)
         plan.backward()
         plan.release()                                    # (a second backward through the same graph re-runs on the same buffers)
         if plan.param_grads:
@@ -196,6 +198,7 @@ class _Engine:
         # their forward as before.  Writes that bypass the counters (p.data...) need `invalidate_shadows()`; `flat_parameters()` calls it.  M2F_SHARED_SHADOWS=0: off.
         self.wshadow: Optional[torch.Tensor] = None
         self.grad_bf16_buf: Optional[torch.Tensor] = None     # bf16 [n_params]: train plans leave their gradients here (set_grad_bf16)
+        self.accumulate = False                               # torch's .grad rule at every backward (M2FNet.set_grad_accumulation)
         self._fresh_token = None
         if self.precision == runtime.BF16 and os.environ.get("M2F_SHARED_SHADOWS", "1") != "0":
             self.wshadow = runtime.param_shadow_buffer(self.cfg, device)
@@ -333,9 +336,33 @@ class _Engine:
         """HBM held by the cached plans' workspaces."""
         return sum(p.nbytes() for p in self.plans.values())
 
+    def begin_backward(self, plan) -> None:
+        """Chooses the form of the next backward of `plan`, which writes parameter gradients.  Accumulation off: the overwrite form,
+        as ever.  On (M2FNet.set_grad_accumulation), torch's rule per parameter: ``.grad`` None (or a foreign tensor, which
+        `publish_grads` adds to) takes this backward's gradient, the engine's view adds it.  Every ``.grad`` None: the overwrite form
+        (the criterion tail's den / num start afresh too); otherwise the views of the parameters that take a fresh gradient are zeroed
+        in one launch and the plan runs its accumulate form."""
+        if not self.accumulate:
+            if getattr(plan, "_acc", False):
+                plan.accumulate_grads(False)
+            return
+        fresh = []
+        for i, ((p, _, _, _), v) in enumerate(zip(self.items, self.grad_views)):
+            g = p.grad
+            if g is None or (g is not v and g.data_ptr() != v.data_ptr()):
+                fresh.append(i)
+        if len(fresh) == len(self.items):
+            plan.accumulate_grads(False)
+            return
+        if fresh:
+            idx = torch.cat([torch.arange(self.items[i][1], self.items[i][1] + self.items[i][2]) for i in fresh])
+            self.flat_grad.index_fill_(0, idx.to(self.device), 0.0)
+        plan.accumulate_grads(True)
+
     def publish_grads(self) -> None:
         """Expose the flat gradient buffer as ``p.grad`` views.  Gradients are OVERWRITTEN each backward
-        (the reference zeroes them every step, src/train.py:227); a foreign ``.grad`` tensor is added to."""
+        (the reference zeroes them every step, src/train.py:227) unless accumulation is on (`begin_backward`); a foreign ``.grad``
+        tensor is added to."""
         for (p, _, _, _), v in zip(self.items, self.grad_views):
             g = p.grad
             if g is None:
@@ -355,8 +382,9 @@ class M2FNet(nn.Module):
     Limits the reference does not have: at most 512 utterances per dialogue - longer inputs raise from ``m2f_plan_create``.
     Batches whose longest dialogue has more than 64 utterances always run on a packed plan (long-dialogue attention
     kernels), whatever ``packed`` says: their logits at pad slots are zero, where the reference computes numbers that its
-    loss and metrics mask out (valid slots agree).  Each backward OVERWRITES the gradients (the reference zeroes them every
-    step, ``src/train.py:227``), so accumulating over several backward calls needs a caller-side buffer.
+    loss and metrics mask out (valid slots agree).  By default each backward OVERWRITES the gradients (the reference zeroes them
+    every step, ``src/train.py:227``); after ``set_grad_accumulation(True)`` every backward follows torch's ``.grad`` rule and adds
+    into the gradients, inside the kernels (micro-batches; ``loss_terms()`` holds the group's criterion denominator).
 
     ``text`` and ``audio`` are autograd inputs as in the reference: when they require grad, ``backward`` gives them (fresh tensors of
     their shape and dtype) d loss / d input computed by the gfx950 backward, so an adapter or encoder in front of the model trains.
@@ -413,6 +441,7 @@ class M2FNet(nn.Module):
         head.append(_LinearParams(c.cls_hidden, c.cls_out))
         self.output_layer = nn.Sequential(*head)
         self._engine: Optional[_Engine] = None
+        self._grad_accumulation = False
 
     # -- device plumbing -------------------------------------------------------------------------------
     def _apply(self, fn, *args, **kwargs):
@@ -427,6 +456,7 @@ class M2FNet(nn.Module):
                                    "(there is no CPU fallback; the CPU oracle lives in oracle/ for tests only)")
         if self._engine is None or self._engine.device != device or not self._engine.owns():
             self._engine = _Engine(self, device)
+            self._engine.accumulate = self._grad_accumulation
         return self._engine
 
     # -- reference surface -----------------------------------------------------------------------------
@@ -466,6 +496,9 @@ class M2FNet(nn.Module):
         weight-gradient launch applies the update itself (``FusedAdam.prepare_fused``; the matrices' ``.grad`` is then not written),
         otherwise the optimizer's own kernel runs behind the step."""
         eng = self.engine(mask.device)
+        if optimizer is not None and eng.accumulate:
+            raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
+                               "gradient accumulation (set_grad_accumulation(True)); call optimizer.step() after the group's micro-batches")
         B, L = mask.shape
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
@@ -475,7 +508,9 @@ class M2FNet(nn.Module):
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
             if optimizer is None:
+                eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
+            eng.begin_backward(plan)                     # (accumulation is refused above: the overwrite form)
             plan.params_fresh(eng.shadows_fresh())
             if optimizer.prepare_fused(plan):
                 out = plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -504,14 +539,61 @@ class M2FNet(nn.Module):
         eight-GPU run then train with the same gradient precision; it saves the fp32 dW round trip (8 bytes per parameter and step: 2.66 ->
         2.59 ms per C3 step).  The matrices' fp32 ``.grad`` is NOT written in this mode.  Returns whether the mode is on (fp32 models: no)."""
         eng = self.engine()
+        if on and eng.accumulate:
+            raise RuntimeError("M2FNet.set_grad_bf16: bf16 gradients do not combine with gradient accumulation "
+                               "(set_grad_accumulation(True)): accumulated gradients stay fp32")
         if not on:
             eng.grad_bf16_buf = None
-        elif eng.precision == runtime.BF16 and eng.grad_bf16_buf is None:
+        else:
+            for pl in list(eng.plans.values()):             # (plans left in the accumulate form by a data-parallel micro-batch group)
+                if getattr(pl, "_acc", False):
+                    pl.accumulate_grads(False)
+        if on and eng.grad_bf16_buf is None and eng.precision == runtime.BF16:
             eng.grad_bf16_buf = torch.zeros(eng.flat.numel(), dtype=torch.bfloat16, device=eng.flat.device)
         for pl in list(eng.plans.values()):
             if pl.train and pl.param_grads:
                 eng._arm_grad_bf16(pl)
         return eng.grad_bf16_buf is not None
+
+    def set_grad_accumulation(self, on: bool = True) -> None:
+        """Every following backward - ``loss.backward()`` or ``train_step`` - follows torch's ``.grad`` rule per parameter: a ``.grad``
+        of None takes the gradient of this backward (a view of the flat buffer, as ever), the engine's view ADDS it (inside the kernels:
+        one rounded fp32 add per element, so the sum of k backwards is the fp32 sum of their gradients bit for bit), a foreign tensor is
+        added to.  ``train_step``'s criterion tail follows suit: ``loss_terms()[1:]`` (den, num) sum over the micro-batches since the
+        gradients were last None (``optimizer.zero_grad()`` starts a group; ``zero_grad(set_to_none=False)`` restarts the gradients but
+        not den / num).  Exact big-batch training on one GPU::
+
+            optimizer.zero_grad()
+            for mb in group:
+                model.train_step(*mb, normalise=False)
+            optimizer.grad_scale = model.loss_terms()[1:2]
+            optimizer.step()
+
+        Off (the default): every backward overwrites, with today's kernels, launch lists and graphs.  Refused together with bf16
+        gradients (``set_grad_bf16``), ``train_step(optimizer=...)`` and the data-parallel split step (``overlap=True``)."""
+        on = bool(on)
+        if on and self._engine is not None and self._engine.grad_bf16_buf is not None:
+            raise RuntimeError("M2FNet.set_grad_accumulation: bf16 gradients are on (set_grad_bf16(True)); accumulated gradients "
+                               "stay fp32 - call set_grad_bf16(False) first")
+        self._grad_accumulation = on
+        if self._engine is not None:
+            self._engine.accumulate = on
+            if not on:                                      # every plan back in the overwrite form now, whatever runs next
+                for pl in list(self._engine.plans.values()):
+                    if getattr(pl, "_acc", False):
+                        pl.accumulate_grads(False)
+
+    def grad_accumulation(self) -> bool:
+        return self._grad_accumulation
+
+    def loss_terms(self) -> torch.Tensor:
+        """Device view ``(loss, den, num)`` of the criterion tail of the gradient buffer that ``train_step`` writes: ``loss`` of the last
+        micro-batch, and - with accumulation on - ``den`` / ``num`` summed over the micro-batches of the group (valid utterances,
+        weighted by the class weights; label-smoothed numerators)."""
+        eng = self.engine()
+        eng.ensure_grad()
+        n = eng.flat.numel()
+        return eng.flat_grad_ext[n: n + 3]
 
     def invalidate_shadows(self) -> None:
         """Call after writing parameters in a way torch's version counters do not see (``p.data`` edits, writes through

@@ -111,6 +111,7 @@ SIGNATURES = {
                                          c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_set_shadow_map": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
+    "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
@@ -495,6 +496,16 @@ class Plan:
         """m2f_plan_grad_bf16: the NEXT steps leave every gradient, rounded once, in `buf16` (bf16 [n_params]; None: back to fp32)."""
         check(lib().m2f_plan_grad_bf16(self._h(), buf16.data_ptr() if buf16 is not None else None), "m2f_plan_grad_bf16")
         self._g16_ref = buf16
+
+    def accumulate_grads(self, on: bool) -> None:
+        """m2f_plan_accumulate_grads: the NEXT backwards / steps ADD every parameter gradient and the criterion tail's den and num into
+        the gradient buffer (on) / overwrite them (off).  Raises for a plan without a gradient buffer, with fused Adam on or bf16
+        gradients armed."""
+        on = bool(on)
+        if on == getattr(self, "_acc", False):
+            return
+        check(lib().m2f_plan_accumulate_grads(self._h(), int(on)), "m2f_plan_accumulate_grads")
+        self._acc = on
 
     def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
         """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |

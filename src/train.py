@@ -42,6 +42,42 @@ def _runtime(cfg, key, default):
     return block.get(key, default) if block else default
 
 
+def grad_accumulation_steps(cfg, world: int = 1) -> int:
+    """`runtime.grad_accumulation` = k micro-batches (consecutive DataLoader batches) per optimizer step, checked on the host before
+    the GPU is touched: k > 1 needs the fused step (train_step; runtime.fused_step: True), the optimizer outside it
+    (runtime.fused_optimizer: False), fp32 gradients on one rank (runtime.grad_bf16: False; several ranks ignore that key) and, with
+    several ranks, the whole-step exchange (runtime.grad_overlap: False)."""
+    k = _runtime(cfg, "grad_accumulation", 1)
+    if isinstance(k, bool) or int(k) != k or int(k) < 1:
+        raise ValueError(f"runtime.grad_accumulation must be an integer >= 1 (got {k!r})")
+    k = int(k)
+    if k > 1:
+        if not bool(_runtime(cfg, "fused_step", True)):
+            raise ValueError("runtime.grad_accumulation > 1 needs runtime.fused_step: True (the micro-batches run train_step)")
+        if bool(_runtime(cfg, "fused_optimizer", False)):
+            raise ValueError("runtime.grad_accumulation > 1 does not combine with runtime.fused_optimizer: True "
+                             "(the optimizer steps once per group, after the last micro-batch)")
+        if world == 1 and bool(_runtime(cfg, "grad_bf16", False)):
+            raise ValueError("runtime.grad_accumulation > 1 does not combine with runtime.grad_bf16: True "
+                             "(accumulated gradients stay fp32)")
+        if world > 1 and bool(_runtime(cfg, "grad_overlap", False)):
+            raise ValueError("runtime.grad_accumulation > 1 does not combine with runtime.grad_overlap: True "
+                             "(the split step has no accumulate form)")
+    return k
+
+
+def group_batches(batches, k: int):
+    """k consecutive batches per group; the last group of an epoch may be shorter."""
+    group = []
+    for b in batches:
+        group.append(b)
+        if len(group) == k:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
 # ---- construction of the solver pieces from config.solver -----------------------------------------------------------
 def build_criterion(solver, train_set, device):
     """CE(ignore_index=-1, label_smoothing=0.1), optionally with sklearn's balanced class weights of the train labels."""
@@ -153,6 +189,7 @@ def main(config=None):
     # global batch are sharded over the ranks, gradients are summed over RCCL with the GLOBAL valid-utterance denominator
     # (mer_amd/dp.py).  The reference is single-process (src/train.py:20); a single rank behaves exactly like it.
     want_dp = _runtime(config, "data_parallel", "auto")
+    grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # W independent trainings on one device, all writing the same checkpoint, is never what a launcher was asked for
         raise RuntimeError(f"runtime.data_parallel is {want_dp!r} but this process was launched as one of "
@@ -208,6 +245,7 @@ def main(config=None):
     # how train() runs the loop body: (fused m2f_step instead of forward / criterion / backward, as one hipGraph)
     model.step_mode = (bool(_runtime(config, "fused_step", True)), bool(_runtime(config, "use_graph", True)))
     model.fused_optimizer = bool(_runtime(config, "fused_optimizer", False))
+    model.grad_accumulation_k = grad_accumulation_steps(config, world)
     if bool(_runtime(config, "grad_bf16", False)) and world == 1:
         model.set_grad_bf16(True)
     te_cfg = _runtime(config, "text_encoder", None)
@@ -327,6 +365,9 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     model.train()
     fused, use_graph = _step_mode(model, criterion)
     dp_step = getattr(model, "dp_step", None)             # set by main() when there is more than one rank
+    k = int(getattr(model, "grad_accumulation_k", 1))
+    if k > 1:
+        return _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log, device, k, fused, use_graph, dp_step)
     running = 0.0
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
@@ -357,6 +398,44 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step})
     return running / len(dl_train)
+
+
+def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log, device, k, fused, use_graph, dp_step):
+    """One epoch with runtime.grad_accumulation = k > 1: k consecutive batches per optimizer step, each a train_step(normalise=False)
+    that adds its gradients and its criterion den / num into the model's buffers (M2FNet.set_grad_accumulation); the optimizer then
+    divides by the group's den - the reference criterion on the concatenated batch.  The last, shorter group steps as well.  Under
+    data parallelism micro-batches 1 .. k-1 run with sync=False and the last one exchanges once.  Returns the mean over the
+    optimizer steps of the group losses num / den."""
+    if not fused:
+        raise ValueError("runtime.grad_accumulation > 1 needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+    if dp_step is None:
+        model.set_grad_accumulation(True)
+    n_groups = (len(dl_train) + k - 1) // k
+    running = 0.0
+    progress = tqdm(enumerate(group_batches(dl_train, k)), total=n_groups, desc=f"Epoch {epoch}", disable=_rank() != 0)
+    for step, group in progress:
+        if dp_step is None:
+            optimizer.zero_grad()                        # (every .grad None: the first micro-batch overwrites, den / num too)
+        for j, batch in enumerate(group):
+            text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
+                                                               audio_encoder=getattr(model, "audio_encoder", None))
+            if dp_step is not None:
+                loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
+                               class_weights=criterion.weight, use_graph=use_graph, sync=j == len(group) - 1)
+            else:
+                model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
+                                 class_weights=criterion.weight, normalise=False, use_graph=use_graph)
+        if dp_step is None:
+            terms = model.loss_terms()
+            optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
+            optimizer.step()
+            loss = terms[2] / terms[1]
+        running += loss.item()
+        if wandb_log:
+            wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step})
+    if dp_step is None:
+        optimizer.grad_scale = None
+    return running / max(n_groups, 1)
 
 
 def _rank_share(dl_val, rank, world):
