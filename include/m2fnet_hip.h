@@ -198,6 +198,30 @@ int m2f_adam_step_shadowed_range(const m2f_config* cfg, float* params, const voi
                                  float* exp_avg_sq, uint16_t* param_shadow, int64_t first, int64_t end, float lr, float beta1, float beta2,
                                  float eps, float weight_decay, int step, const float* grad_scale_ptr, m2f_stream_t stream);
 
+/* Gradient clipping by global L2 norm (torch.nn.utils.clip_grad_norm_, norm_type 2) without touching the gradients: the norm of the
+ * flat gradient buffer is reduced on the device and the clip is folded into the divisor the optimizer entry points above read as
+ * *grad_scale_ptr.  No counterpart in the reference, whose loop does not clip; the rule is torch's.
+ *
+ * m2f_grad_sumsq: float64 sums of squares of the parameter tensors at flat offsets [first, end) (as m2f_adam_step_shadowed_range:
+ * both the offset of a tensor; end < 0: to the last one) of `grads` - fp32, or (grads_bf16 != 0) bf16 with the same indexing;
+ * 16-byte aligned - into `scratch` (m2f_grad_norm_scratch_bytes(cfg) bytes, 8-byte aligned): one partial per slice of 8192 elements
+ * of one tensor.  Only parameter elements are read: the alignment pads between tensors may hold anything.  Calls over disjoint
+ * ranges fill disjoint partials (the data-parallel path may sum bucket by bucket).  grid: workgroups of the launch, <= 0 = default
+ * (at most 2048); nontemporal != 0: nontemporal loads.  Neither changes a bit of the result: a partial depends on its slice alone.
+ *
+ * m2f_grad_norm_finalize: sums EVERY partial of cfg in index order (the caller has covered all tensors) and writes four floats,
+ * computed in float64 and rounded once each:
+ *   record[0] = norm    = sqrt(sum of squares) / den        den = *den_ptr, or 1 when den_ptr is NULL
+ *   record[1] = coef    = min(1, max_norm / (norm + 1e-6))
+ *   record[2] = divisor = den if coef == 1 (den's bits), else den / coef         -> pass &record[2] as grad_scale_ptr
+ *   record[3] = sqrt(sum of squares)
+ * A non-finite norm gives a non-finite coef and divisor (torch's error_if_nonfinite=False).  Same bits on every run. */
+int64_t m2f_grad_norm_scratch_bytes(const m2f_config* cfg);
+int m2f_grad_sumsq(const m2f_config* cfg, const void* grads, int grads_bf16, int64_t first, int64_t end, double* scratch, int grid,
+                   int nontemporal, m2f_stream_t stream);
+int m2f_grad_norm_finalize(const m2f_config* cfg, const double* scratch, const float* den_ptr, double max_norm, float* record,
+                           m2f_stream_t stream);
+
 /* bf16-mode plans write every activation twice - fp32 and the bf16 shadow the GEMMs / attention kernels stage from.  When a plan
  * is built, the readers of every workspace buffer are enumerated from its final launch lists; a copy nobody reads is not written
  * (fp32 of QKV projections, attention outputs, their gradients and the FFN hidden gradients; the shadows of results that are only

@@ -20,7 +20,9 @@ dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
 w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
 # --mel <remarks>: the audio_mel encoder (mel_resnet.hip) - the same rule for its kernels (the convolution's accumulators, the STFT sums)
 mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
-path = sys.argv[2] if (ring or dlong or w2v or mel) else sys.argv[1]
+# --gradnorm <remarks>: the gradient-norm kernels (gradnorm.hip) - the same rule (a slice's loads and float64 accumulators stay in registers)
+gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
+path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -34,8 +36,8 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-if dlong or w2v or mel:
-    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_"
+if dlong or w2v or mel or gradnorm:
+    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_"
     kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
         sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")

@@ -342,6 +342,18 @@ hipError_t m2f_launch_adam_hyper(float* hyper_dev, float lr, float beta1, float 
 hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, float* v, uint16_t* shadow, const AdamItem* items, const int* tile_begin,
                                         int n_items, int total_tiles, const float* hyper_dev, const float* grad_scale_ptr, hipStream_t stream);
 
+// Global gradient norm + clip record (gradnorm.hip).  A slice = at most M2F_GRADNORM_SLICE consecutive elements of ONE parameter tensor
+// (`off`: its first element in the flat buffer; only the last slice of a tensor is short), cut by the host from the parameter map, so
+// the alignment pads between tensors belong to no slice.  Stage 1 writes partial[s], one float64 sum of squares per slice of [s0, s1)
+// (grid <= 0: min(2048, slices) workgroups; the value of partial[s] does not depend on the grid); the finalize launch sums
+// partial[0, n) in index order and writes record = (norm, coef, divisor, sqrt(sum of squares)) as fp32 - see the kernel.
+struct GradSlice { long long off; int n; int pad_; };
+#define M2F_GRADNORM_SLICE 8192
+hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const GradSlice* slices, int s0, int s1, double* partial, int grid,
+                                 int nontemporal, hipStream_t stream);
+hipError_t m2f_launch_grad_norm_finalize(const double* partial, int n, const float* den_ptr, double max_norm, float* record,
+                                         hipStream_t stream);
+
 #ifdef __HIPCC__
 // shadow address of a workspace element, or null (no shadows / pointer outside the workspace, e.g. the gradient buffer)
 __device__ __forceinline__ uint16_t* m2f_shadow_of(const ShadowMap& sh, const float* p) {

@@ -292,7 +292,12 @@ class GradReducer:
     def reduce_and_step(self, optimizer) -> None:
         """Pipelined exchange + update: the buckets are all-reduced LAST FIRST (the tail bucket carries the global
         denominator every update needs), and the fused-Adam launch of bucket k only waits for bucket k's collective,
-        so the HBM-bound optimizer runs under the xGMI-bound exchange of the following buckets."""
+        so the HBM-bound optimizer runs under the xGMI-bound exchange of the following buckets.
+        With ``optimizer.max_grad_norm`` set (gradient clipping) the collectives are issued as ever, but the optimizer waits for ALL
+        of them, reduces the global norm of the reduced buffer (``buf16`` under the bf16 exchange; den = the global denominator) -
+        every rank holds the same buffer, so every rank computes the same norm bits locally, no extra collective - and only then
+        steps the buckets (``FusedAdam.step_ranges``): the optimizer launches no longer hide under the exchange.  That is the price
+        of a global norm."""
         if not dist.is_initialized():
             optimizer.step()
             return
@@ -322,7 +327,9 @@ class GradReducer:
         (the encoders' backward).  The tail bucket's all-reduce is put on the wire FIRST - torch's asynchronous collectives wait for
         the work already queued on the current stream, i.e. for part 0 only - then part 1 is enqueued and computes while that
         bucket travels; the encoder buckets follow last-first as in `reduce_and_step`, each bucket's fused-Adam launch behind its
-        own collective.  At C3 the tail bucket is 35.5 M of 103.8 M parameters (71 MB of the 198 MB bf16 exchange)."""
+        own collective.  At C3 the tail bucket is 35.5 M of 103.8 M parameters (71 MB of the 198 MB bf16 exchange).
+        Refused with gradient clipping (``optimizer.max_grad_norm``): see ``_refuse_clipped_split``."""
+        _refuse_clipped_split(optimizer)
         if not dist.is_initialized():
             run_rest()
             optimizer.step()
@@ -362,6 +369,14 @@ class GradReducer:
 
     def global_loss(self) -> torch.Tensor:
         return self.buf[self.n + 2] / self.buf[self.n + 1]
+
+
+def _refuse_clipped_split(optimizer) -> None:
+    """The split step exists to step the tail bucket while the encoders' backward still runs; a global gradient norm exists only
+    after the whole backward and the whole exchange - the two do not combine."""
+    if getattr(optimizer, "max_grad_norm", None) is not None:
+        raise RuntimeError("mer_amd.dp: gradient clipping (FusedAdam.max_grad_norm) does not combine with overlap=True / the split "
+                           "step (the global norm needs every bucket's reduced gradients before the first update); use overlap=False")
 
 
 def sum_over_ranks(values: Sequence[float], device=None) -> List[float]:
@@ -457,6 +472,8 @@ class DataParallelStep:
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
         eng = self.model.engine()
         B, L = mask.shape
+        if self.overlap and self.reducer.world() > 1:
+            _refuse_clipped_split(self.optimizer)     # (before any launch or collective: every rank refuses alike)
         if not sync:
             self._micro_batches_on()
         cur = torch.cuda.current_stream(eng.device)

@@ -322,3 +322,20 @@ def w2v_masked_mean(x: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
     l32 = lengths.to(x.device, torch.int32).contiguous()
     check(lib().m2f_w2v_masked_mean(B, S, d, ptr(x.contiguous()), ptr(l32), ptr(out), stream_ptr()), "m2f_w2v_masked_mean")
     return out
+
+
+def grad_norm(cfg, grads: torch.Tensor, max_norm: float, den: Optional[torch.Tensor] = None, grid: int = 0,
+              nontemporal: Optional[bool] = None) -> torch.Tensor:
+    """Global L2 norm of a flat gradient buffer of `cfg`'s parameter layout (fp32 or bf16, at least the layout's length; only
+    parameter elements count, the pads between tensors may hold anything) and torch.nn.utils.clip_grad_norm_'s coefficient for
+    `max_norm`: -> 4 fp32 values (norm = sqrt(sum of squares) / den, coef = min(1, max_norm / (norm + 1e-6)), divisor = den / coef,
+    sqrt(sum of squares)); den: nullable device scalar, absent = 1.  `grid` / `nontemporal`: launch shape of the reduction; the
+    result does not depend on them."""
+    runtime.require_gpu()
+    assert grads.is_cuda and grads.dim() == 1 and grads.is_contiguous() and grads.dtype in (torch.float32, torch.bfloat16)
+    assert grads.numel() >= runtime.verify_layout(cfg), "the buffer is shorter than the configuration's flat parameter layout"
+    scratch = runtime.grad_norm_scratch(cfg, grads.device)
+    record = torch.zeros(4, dtype=torch.float32, device=grads.device)
+    runtime.grad_sumsq(cfg, grads, scratch, 0, -1, grid, nontemporal)
+    runtime.grad_norm_finalize(cfg, scratch, record, max_norm, den)
+    return record

@@ -55,10 +55,26 @@ class FusedAdam(torch.optim.Optimizer):
     parameter / gradient / moment buffers.  Differences from torch worth knowing: every parameter of the model is updated every
     step - a parameter whose ``.grad`` is None is treated as having a zero gradient (it still receives weight decay and the
     moment decay; torch skips it), which never happens on the M2FNet path, where backward writes every gradient; there is one
-    parameter group (one lr / betas / eps / weight_decay for the whole model)."""
+    parameter group (one lr / betas / eps / weight_decay for the whole model).
 
-    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    ``max_grad_norm`` (constructor argument and plain attribute; may be changed or set to None between steps; not part of
+    ``state_dict``): every step first clips the gradient by its global L2 norm, ``torch.nn.utils.clip_grad_norm_(parameters,
+    max_grad_norm)``'s rule, on the device - two launches reduce the norm of the gradient buffer THIS step reads (fp32, or the bf16
+    buffer of ``M2FNet.set_grad_bf16`` / the data-parallel bf16 exchange) in float64, divided by ``grad_scale`` where one is set, and
+    fold ``coef = min(1, max_grad_norm / (norm + 1e-6))`` into the divisor the Adam kernel already applies.  Differences from torch:
+    ``.grad`` is NOT scaled - the clip exists only where the optimizer reads; the norm is that of the gradient the optimizer uses
+    (after the division by ``grad_scale``: the mean gradient of an accumulation group or of the global batch), which a norm over
+    ``.grad`` is not in those modes; ``grad_norm()`` / ``clip_coef()`` are device tensors, nothing on the step path waits for the
+    host.  A non-finite norm gives a non-finite divisor and non-finite parameters, as torch's default ``error_if_nonfinite=False``
+    does.  None (the default): the step as it was, launch for launch."""
+
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None):
         self.model = model
+        self.max_grad_norm = max_grad_norm
+        self._clip_scratch: Optional[torch.Tensor] = None  # float64 partial sums of squares (runtime.grad_norm_scratch)
+        self._clip_record: Optional[torch.Tensor] = None   # 4 fp32 on the device: norm, coef, divisor, sqrt(sum of squares)
+        self._clip_cfg = None
         params = list(model.parameters())
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._engine = None
@@ -91,6 +107,36 @@ class FusedAdam(torch.optim.Optimizer):
                 self.state[p] = {"step": torch.tensor(float(self._step)),
                                  "exp_avg": self._m[o: o + n].view(s), "exp_avg_sq": self._v[o: o + n].view(s)}
 
+    def _clip(self, eng, flat_grad) -> Optional[torch.Tensor]:
+        """-> the device scalar the Adam kernels divide the gradients by: ``grad_scale`` itself without clipping; with it, the
+        divisor of the clip record, written by the two norm launches over `flat_grad` on the current stream."""
+        if self.max_grad_norm is None:
+            return self.grad_scale
+        max_norm = float(self.max_grad_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"FusedAdam.max_grad_norm must be a positive number or None (got {self.max_grad_norm!r})")
+        if self._clip_record is None or self._clip_record.device != eng.flat.device or self._clip_cfg is not eng.cfg:
+            self._clip_scratch = runtime.grad_norm_scratch(eng.cfg, eng.flat.device)
+            self._clip_record = torch.zeros(4, dtype=torch.float32, device=eng.flat.device)
+            self._clip_cfg = eng.cfg
+        runtime.grad_sumsq(eng.cfg, flat_grad, self._clip_scratch)
+        runtime.grad_norm_finalize(eng.cfg, self._clip_scratch, self._clip_record, max_norm, self.grad_scale)
+        return self._clip_record[2:3]
+
+    def _clip_value(self, i: int, what: str) -> torch.Tensor:
+        if self._clip_record is None:
+            raise RuntimeError(f"FusedAdam.{what}: no step has clipped yet (max_grad_norm is None, or step() has not run)")
+        return self._clip_record[i]
+
+    def grad_norm(self) -> torch.Tensor:
+        """Device scalar (a view: the next clipping step overwrites it): global L2 norm of the gradient the last clipping step
+        read, divided by ``grad_scale`` - what ``clip_grad_norm_`` returns for the gradients Adam used."""
+        return self._clip_value(0, "grad_norm")
+
+    def clip_coef(self) -> torch.Tensor:
+        """Device scalar (a view): ``min(1, max_grad_norm / (grad_norm + 1e-6))`` of the last clipping step."""
+        return self._clip_value(1, "clip_coef")
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -112,15 +158,16 @@ class FusedAdam(torch.optim.Optimizer):
                 elif p.grad.data_ptr() != view.data_ptr():
                     view.copy_(p.grad)
         self._step += 1
+        scale = self._clip(eng, flat_grad)                   # grad_scale, or the clip record's divisor (max_grad_norm)
         if eng.wshadow is not None:
             # bf16 mode: the update and the bf16 shadows (W, W^T) of every 2-D parameter in ONE pass - the forward then skips its
             # parameter casts (engine.shadows_fresh)
             runtime.adam_step_shadowed(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, self._step, g["lr"], g["betas"],
-                                       g["eps"], g["weight_decay"], self.grad_scale)
+                                       g["eps"], g["weight_decay"], scale)
             eng.mark_shadows_fresh()
         else:
             runtime.adam_step(eng.flat, flat_grad, self._m, self._v, self._step, g["lr"], g["betas"], g["eps"],
-                              g["weight_decay"], self.grad_scale)
+                              g["weight_decay"], scale)
         return loss
 
     @torch.no_grad()
@@ -130,7 +177,10 @@ class FusedAdam(torch.optim.Optimizer):
         process; csrc/gemm_p8.h EPI 3).  Same arithmetic on the same gradients as ``step()`` - bit-identical parameters, moments and
         parameter shadows (tests/test_fused_adam_gpu.py) - but the weight gradients of the table's matrices never reach memory:
         their ``.grad`` keeps whatever it held.  Returns False (and changes nothing) when the plan cannot; call ``finish_fused``
-        after the step."""
+        after the step.  With ``max_grad_norm`` set it returns False: the in-launch optimizer updates elements before the global norm
+        can exist, so ``train_step(optimizer=...)`` takes its two-launch branch (the step, then ``step()``)."""
+        if self.max_grad_norm is not None:
+            return False
         eng = self._bind()
         if eng.wshadow is None or not plan.train or not getattr(plan, "shared_shadow", False):
             return False
@@ -167,13 +217,23 @@ class FusedAdam(torch.optim.Optimizer):
         is launched - the data-parallel path waits there for that range's all-reduce, so the update of one bucket
         overlaps the exchange of the next.  `grads`: gradient buffer to read instead of the engine's (same indexing;
         fp32 or bf16 - the reduced buffer of the bf16 exchange).  Ranges made of whole parameter tensors keep the bf16
-        parameter shadows current (m2f_adam_step_shadowed_range); other ranges leave them to the next forward's casts."""
+        parameter shadows current (m2f_adam_step_shadowed_range); other ranges leave them to the next forward's casts.
+        With ``max_grad_norm`` set the global norm needs every range's gradients: `before_each` runs for ALL ranges first, then the
+        norm launches over the whole buffer, then the ranges' updates with the clip record's divisor - the updates no longer hide
+        under the exchange of the following buckets; that is the price of a global norm."""
         eng = self._bind()
         g = self.param_groups[0]
         flat_grad = eng.ensure_grad() if grads is None else grads
         n = eng.flat.numel()
         self._step += 1
         ranges = [(lo, min(hi, n)) for (lo, hi) in ranges]
+        scale = self.grad_scale
+        if self.max_grad_norm is not None:
+            if before_each is not None:
+                for i in range(len(ranges)):
+                    before_each(i)
+                before_each = None
+            scale = self._clip(eng, flat_grad)
         # bf16 mode with the model-wide parameter shadows: ranges that start and end at parameter tensors (dp.GradReducer aligns its
         # buckets that way) go through the shadow-writing kernel, so the next forward needs no parameter casts under data parallelism
         # either; anything else updates the parameters only and the next forward re-casts
@@ -188,10 +248,10 @@ class FusedAdam(torch.optim.Optimizer):
                 continue
             if shadowed:
                 runtime.adam_step_shadowed(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, self._step, g["lr"], g["betas"],
-                                           g["eps"], g["weight_decay"], self.grad_scale, first=lo, end=(-1 if hi >= n else hi))
+                                           g["eps"], g["weight_decay"], scale, first=lo, end=(-1 if hi >= n else hi))
             else:
                 runtime.adam_step(eng.flat[lo:hi], flat_grad[lo:hi], self._m[lo:hi], self._v[lo:hi], self._step, g["lr"],
-                                  g["betas"], g["eps"], g["weight_decay"], self.grad_scale)
+                                  g["betas"], g["eps"], g["weight_decay"], scale)
         if shadowed:
             covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
             whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))

@@ -72,6 +72,9 @@ SIGNATURES = {
                                        c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "m2f_adam_step_shadowed_range": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64,
                                              c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
+    "m2f_grad_norm_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC)]),
+    "m2f_grad_sumsq": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_grad_norm_finalize": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     "m2f_plan_skipped_copies": (c_int, [c_void_p]),
     "m2f_plan_destroy": (None, [c_void_p]),
     "m2f_plan_buffer": (c_void_p, [c_void_p, c_int]),
@@ -612,6 +615,39 @@ def adam_step_shadowed(cfg: M2FConfig, params, grads, exp_avg, exp_avg_sq, param
                                              exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param_shadow.data_ptr(), int(first), int(end),
                                              lr, betas[0], betas[1], eps, weight_decay, step, ptr(grad_scale), stream_ptr()),
           "m2f_adam_step_shadowed_range")
+
+
+# Loads of the sum-of-squares kernel: nontemporal.  The optimizer reads the same gradients right behind it, but plain loads do not
+# leave them where it would find them - measured inside the C3 bf16 step (tools/bench_grad_clip.py, rocprofv3 kernel times): fp32
+# gradients 90 us plain / 70 us nontemporal, bf16 gradients 42 / 37 us, the Adam kernel behind it 597 / 596 us and 566 / 567 us.
+GRAD_NORM_NONTEMPORAL = True
+
+
+def grad_norm_scratch(cfg: M2FConfig, device) -> torch.Tensor:
+    """float64 scratch of the gradient-norm launches: one partial sum of squares per 8192-element slice of a parameter tensor."""
+    cc = config_to_c(cfg)
+    n = lib().m2f_grad_norm_scratch_bytes(ctypes.byref(cc))
+    if n < 0:
+        raise HipError(lib().m2f_last_error().decode())
+    return torch.zeros(n // 8, dtype=torch.float64, device=device)
+
+
+def grad_sumsq(cfg: M2FConfig, grads: torch.Tensor, scratch: torch.Tensor, first: int = 0, end: int = -1, grid: int = 0,
+               nontemporal: Optional[bool] = None) -> None:
+    """m2f_grad_sumsq: the partial sums of squares of the parameter tensors at flat offsets [first, end) of `grads` (the WHOLE flat
+    gradient buffer, fp32 or bf16) into `scratch`, on the current stream.  `grid` / `nontemporal` change speed only, never a bit."""
+    cc = config_to_c(cfg)
+    nt = GRAD_NORM_NONTEMPORAL if nontemporal is None else bool(nontemporal)
+    check(lib().m2f_grad_sumsq(ctypes.byref(cc), grads.data_ptr(), int(grads.dtype == torch.bfloat16), int(first), int(end),
+                               scratch.data_ptr(), int(grid), int(nt), stream_ptr()), "m2f_grad_sumsq")
+
+
+def grad_norm_finalize(cfg: M2FConfig, scratch: torch.Tensor, record: torch.Tensor, max_norm: float,
+                       den: Optional[torch.Tensor] = None) -> None:
+    """m2f_grad_norm_finalize: record <- (norm, coef, divisor, sqrt(sum of squares)), four fp32 values, from every partial of `scratch`."""
+    cc = config_to_c(cfg)
+    check(lib().m2f_grad_norm_finalize(ctypes.byref(cc), scratch.data_ptr(), ptr(den), float(max_norm), record.data_ptr(), stream_ptr()),
+          "m2f_grad_norm_finalize")
 
 
 def adam_hyper(hyper: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0) -> None:

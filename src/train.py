@@ -66,6 +66,25 @@ def grad_accumulation_steps(cfg, world: int = 1) -> int:
     return k
 
 
+def clip_grad_norm(cfg, world: int = 1):
+    """`runtime.clip_grad_norm` = null (off) or a positive number: every optimizer step clips the gradient by its global L2 norm
+    (torch.nn.utils.clip_grad_norm_'s rule, on the device: FusedAdam.max_grad_norm).  Checked on the host before the GPU is touched:
+    the optimizer must run outside the step (runtime.fused_optimizer: False - the in-launch optimizer updates elements before the
+    norm exists) and, with several ranks, behind the whole exchange (runtime.grad_overlap: False)."""
+    v = _runtime(cfg, "clip_grad_norm", None)
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0 or v != v or v == float("inf"):
+        raise ValueError(f"runtime.clip_grad_norm must be null or a positive finite number (got {v!r})")
+    if bool(_runtime(cfg, "fused_optimizer", False)):
+        raise ValueError("runtime.clip_grad_norm does not combine with runtime.fused_optimizer: True "
+                         "(the optimizer inside the step updates elements before the global norm exists)")
+    if world > 1 and bool(_runtime(cfg, "grad_overlap", False)):
+        raise ValueError("runtime.clip_grad_norm does not combine with runtime.grad_overlap: True "
+                         "(the global norm needs every bucket's reduced gradients before the first update)")
+    return float(v)
+
+
 def group_batches(batches, k: int):
     """k consecutive batches per group; the last group of an epoch may be shorter."""
     group = []
@@ -190,6 +209,7 @@ def main(config=None):
     # (mer_amd/dp.py).  The reference is single-process (src/train.py:20); a single rank behaves exactly like it.
     want_dp = _runtime(config, "data_parallel", "auto")
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
+    clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # W independent trainings on one device, all writing the same checkpoint, is never what a launcher was asked for
         raise RuntimeError(f"runtime.data_parallel is {want_dp!r} but this process was launched as one of "
@@ -260,6 +280,7 @@ def main(config=None):
                                                                              n_head=config.model.AUDIO.n_head))
     criterion = build_criterion(config.solver, train_set, device)
     optimizer = FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
+    optimizer.max_grad_norm = clip_grad_norm(config, world)
     if world > 1:
         model.dp_step = dp.DataParallelStep(model, optimizer, n_buckets=int(_runtime(config, "grad_buckets", 4)),
                                             exchange=_runtime(config, "grad_exchange", "fp32"),
@@ -360,6 +381,14 @@ def _step_mode(model, criterion):
     return fused and isinstance(criterion, M2FCrossEntropyLoss) and hasattr(model, "train_step"), use_graph
 
 
+def _grad_norm_log(optimizer):
+    """{"Train/Grad_norm": ...} of the step just taken when the optimizer clips (runtime.clip_grad_norm), else nothing.  One more
+    scalar read on a path that already waits for loss.item() every step."""
+    if getattr(optimizer, "max_grad_norm", None) is None:
+        return {}
+    return {"Train/Grad_norm": float(optimizer.grad_norm())}
+
+
 def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     """One epoch; returns the mean of the per-batch losses (reference src/train.py:217-243)."""
     model.train()
@@ -385,7 +414,8 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                                         class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer)
                 running += loss.item()
                 if wandb_log:
-                    wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step})
+                    wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
+                               **_grad_norm_log(optimizer)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
@@ -396,7 +426,8 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
             optimizer.step()
         running += loss.item()
         if wandb_log:
-            wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step})
+            wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
+                       **_grad_norm_log(optimizer)})
     return running / len(dl_train)
 
 
@@ -432,7 +463,8 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             loss = terms[2] / terms[1]
         running += loss.item()
         if wandb_log:
-            wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step})
+            wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step,
+                       **_grad_norm_log(optimizer)})
     if dp_step is None:
         optimizer.grad_scale = None
     return running / max(n_groups, 1)
