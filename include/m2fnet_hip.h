@@ -222,6 +222,36 @@ int m2f_grad_sumsq(const m2f_config* cfg, const void* grads, int grads_bf16, int
 int m2f_grad_norm_finalize(const m2f_config* cfg, const double* scratch, const float* den_ptr, double max_norm, float* record,
                            m2f_stream_t stream);
 
+/* Scoring of validation / test batches on the device: what the reference's loops do per batch on the host with torch and sklearn
+ * (validate: src/train.py:245-272 - criterion(...).item(), argmax, the label != -1 masks, accuracy_score and
+ * f1_score(average="weighted") per batch, averaged unweighted over the batches; test: src/test.py:51-74, the same without the loss).
+ *
+ * The rule, over the rows of one batch whose label is not -1: prediction = index of the first maximal logit (a NaN counts as
+ * maximal, torch.argmax); cm[true][predicted] in integers; accuracy = trace / n; weighted F1 = (sum over c = 0 .. C-1 of
+ * f_c * support_c) / n with f_c = 2 cm[c][c] / (support_c + predicted_c), 0 when that denominator is 0 (sklearn's default), both
+ * in float64; loss = the criterion of m2f_loss / m2f_cross_entropy (num / den in fp32, the same bits for the same rows) without
+ * its gradient.  A batch with no labelled row gives NaN three times.
+ *
+ * record (m2f_eval_record_bytes(C) bytes, 8-byte aligned, zeroed by the caller before a pass; every call ADDS one batch):
+ *   double[0] loss_sum (the fp32 batch losses widened)  [1] acc_sum  [2] f1_sum  [3] n_batches
+ *   double[4..6] loss, accuracy, weighted F1 of the LAST batch   [7] unused
+ *   int64 [C][C] behind them: the confusion matrix of the whole pass.
+ * scratch: m2f_eval_scratch_bytes(T, C) bytes, 8-byte aligned, contents irrelevant.  C <= 16.  Two launches, no atomics on
+ * floats, no memset: capturable, and the same bytes on every run.
+ *
+ * m2f_eval_scores: logits [T, C] fp32 and labels [T] int64 of the caller, class_w [C] or NULL.
+ * m2f_eval_step: the plan's forward (as m2f_forward: inputs from the staging buffers) followed by the scoring of M2F_BUF_LOGITS
+ * against M2F_BUF_LABELS (class weights from M2F_BUF_CLASSW when use_class_weights), all T token rows of a padded or packed plan -
+ * pad and filler rows carry label -1.  Eval plans and train plans without dropout; a train plan with dropout active is refused
+ * (the reference validates under model.eval(), src/train.py:247).  use_graph = 1: the first call runs eagerly, later ones replay
+ * one captured graph (re-captured when label_smoothing, use_class_weights, `record`, m2f_plan_params_fresh or the plan's launch
+ * lists change).  Neither the flat gradient buffer, M2F_BUF_LOSS nor the dropout RNG state is touched. */
+int64_t m2f_eval_scratch_bytes(int T, int C);
+int64_t m2f_eval_record_bytes(int C);
+int m2f_eval_scores(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
+                    void* scratch, void* record, m2f_stream_t stream);
+int m2f_eval_step(m2f_plan* plan, float label_smoothing, int use_class_weights, void* record, int use_graph, m2f_stream_t stream);
+
 /* bf16-mode plans write every activation twice - fp32 and the bf16 shadow the GEMMs / attention kernels stage from.  When a plan
  * is built, the readers of every workspace buffer are enumerated from its final launch lists; a copy nobody reads is not written
  * (fp32 of QKV projections, attention outputs, their gradients and the FFN hidden gradients; the shadows of results that are only

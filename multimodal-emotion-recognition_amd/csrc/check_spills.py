@@ -22,7 +22,9 @@ w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
 mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
 # --gradnorm <remarks>: the gradient-norm kernels (gradnorm.hip) - the same rule (a slice's loads and float64 accumulators stay in registers)
 gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
-path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm) else sys.argv[1]
+# --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
+metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
+path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or metrics) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -36,8 +38,8 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-if dlong or w2v or mel or gradnorm:
-    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_"
+if dlong or w2v or mel or gradnorm or metrics:
+    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_eval_"
     kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
         sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")

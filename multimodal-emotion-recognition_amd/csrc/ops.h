@@ -281,6 +281,23 @@ hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream);
 hipError_t m2f_launch_loss_finalize(const float* loss_terms, int T, int C, float* dlogits, float* loss_out,
                                     int normalise, hipStream_t stream, int accumulate = 0);
 
+// Scoring of one evaluation batch (metrics.hip; src/train.py:245-272, src/test.py:51-74 of the reference): the criterion's loss without
+// its gradient, first-max argmax, the C x C confusion matrix, accuracy and weighted F1, ADDED to `record` (M2F_EVAL_RECORD_HEAD
+// doubles: loss_sum, acc_sum, f1_sum, n_batches, the last batch's loss / accuracy / F1, one unused; then C x C int64).  Two launches.
+#define M2F_EVAL_MAX_C 16
+#define M2F_EVAL_MAX_BLOCKS 128
+#define M2F_EVAL_RECORD_HEAD 8
+struct EvalArgs {
+    const float* logits; int T, C;
+    const int64_t* labels;                 // [T], -1 = unlabelled (pad and filler rows)
+    const float* class_w;                  // [C] or null
+    float label_smoothing;
+    float* terms;                          // [T, 2] (numerator, denominator), as CeArgs::loss_terms
+    int* partial;                          // [m2f_eval_blocks(T)][C * C]: one integer tile per workgroup of the rows launch
+};
+static inline int m2f_eval_blocks(int T) { const int b = (T + 255) / 256; return b < M2F_EVAL_MAX_BLOCKS ? b : M2F_EVAL_MAX_BLOCKS; }
+hipError_t m2f_launch_eval_scores(const EvalArgs& a, double* record, hipStream_t stream);
+
 // fp32 -> bf16 (round to nearest even) of up to M2F_CAST_MAX_ITEMS 2-D blocks in one launch: dst[r*ldd + c] =
 // bf16(src[r*lds + c]) for c < cols (pad columns of dst are left untouched = zero).
 struct CastItem { const float* src; uint16_t* dst; int rows, cols, lds, ldd; uint16_t* dst_t; int ldd_t; };   // dst_t: transposed copy [cols][rows] (nullable)

@@ -532,6 +532,39 @@ class M2FNet(nn.Module):
         eng.publish_grads()
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
+    # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
+    def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,
+                  label_smoothing: float = 0.1, use_graph: bool = True) -> None:
+        """Loop body of the reference's ``validate`` / ``test`` (src/train.py:252-272, src/test.py:55-74) in one call: the forward of
+        a no-grad ``forward`` (same plan: buckets, packed plans, long dialogues), then the batch's criterion loss, accuracy, weighted
+        F1 and confusion matrix ADDED to ``scores`` (a ``metrics.DeviceScores``), all on the device.  Returns nothing and waits for
+        nothing: ``scores.last()`` is a device view of the batch's three numbers, ``scores.result()`` / ``mean_loss()`` read the pass.
+        The plan's own token rows are scored - pad and filler rows carry label -1."""
+        if self.training and self.m2f_config.dropout > 0.0:
+            raise RuntimeError("M2FNet.eval_step: the model is in training mode with dropout > 0; evaluation scores the model "
+                               "without dropout - call model.eval() first")
+        eng = self.engine(mask.device)
+        if scores.n_classes != self.m2f_config.cls_out or scores.record.device != eng.device:
+            raise ValueError(f"M2FNet.eval_step: scores must be a DeviceScores({self.m2f_config.cls_out}, {eng.device})")
+        B, L = mask.shape
+        valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
+        plan = eng.plan(B, L, False, False, valid)
+
+        def body():
+            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion)
+            if class_weights is not None:
+                plan.class_w[: class_weights.numel()].copy_(class_weights)
+            plan.eval_step(scores.record, label_smoothing, class_weights is not None, use_graph)
+
+        if use_graph:                                    # capture / replay on the engine's own stream
+            cur = torch.cuda.current_stream(eng.device)
+            eng.stream.wait_stream(cur)
+            with torch.cuda.stream(eng.stream):
+                body()
+            cur.wait_stream(eng.stream)
+        else:
+            body()
+
     def set_grad_bf16(self, on: bool = True) -> bool:
         """bf16 mode: every following training step leaves its gradients ROUNDED ONCE TO BF16 in one flat bf16 buffer - the weight-gradient
         launch writes bf16 dW directly, one cast launch rounds the rest - and ``FusedAdam`` reads that buffer (fp32 moments and parameters as

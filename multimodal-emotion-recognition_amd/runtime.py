@@ -75,6 +75,10 @@ SIGNATURES = {
     "m2f_grad_norm_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC)]),
     "m2f_grad_sumsq": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p]),
     "m2f_grad_norm_finalize": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+    "m2f_eval_scratch_bytes": (c_int64, [c_int, c_int]),
+    "m2f_eval_record_bytes": (c_int64, [c_int]),
+    "m2f_eval_scores": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "m2f_eval_step": (c_int, [c_void_p, c_float, c_int, c_void_p, c_int, c_void_p]),
     "m2f_plan_skipped_copies": (c_int, [c_void_p]),
     "m2f_plan_destroy": (None, [c_void_p]),
     "m2f_plan_buffer": (c_void_p, [c_void_p, c_int]),
@@ -487,6 +491,15 @@ class Plan:
                              stream_ptr()), "m2f_step")
         self._casted()
         return self.loss
+
+    def eval_step(self, record: torch.Tensor, label_smoothing: float = 0.1, use_class_weights: bool = False,
+                  use_graph: bool = True) -> None:
+        """m2f_eval_step: the forward, then loss / accuracy / weighted F1 / confusion matrix of the plan's own logits against its
+        labels buffer, ADDED to `record` (metrics.DeviceScores.record).  Nothing comes back to the host."""
+        self.version += 1
+        check(lib().m2f_eval_step(self._h(), label_smoothing, int(use_class_weights), record.data_ptr(), int(use_graph), stream_ptr()),
+              "m2f_eval_step")
+        self._casted()
 
     def fused_adam_setup(self, params, exp_avg, exp_avg_sq, param_shadow, hyper, grad_scale=None) -> None:
         """m2f_plan_fused_adam_setup: the optimizer's buffers for steps that apply Adam inside the weight-gradient launch (raises when

@@ -33,15 +33,34 @@ def load_model_weights(model, checkpoint_path, device):
 
 
 def test(model, dl_test, device):
-    """-> (accuracy, weighted_f1) over the loader, per-batch scores averaged unweighted."""
-    scores = BatchScores()
+    """-> (accuracy, weighted_f1) over the loader, per-batch scores averaged unweighted.
+    With ``model.device_metrics`` (runtime.device_metrics) every batch is scored on the device (``M2FNet.eval_step``) and the host
+    reads the record once; ``model.test_scores`` then holds the pass's ``DeviceScores`` (confusion matrix, per-class report)."""
     model.eval()
+    if getattr(model, "device_metrics", False):
+        from mer_amd.metrics import DeviceScores
+        scores = DeviceScores(model.m2f_config.cls_out, device)
+        with torch.inference_mode():
+            for batch in tqdm(dl_test, total=len(dl_test)):
+                text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
+                                                               audio_encoder=getattr(model, "audio_encoder", None))
+                model.eval_step(text, audio, padding_mask, emotion, scores)
+        model.test_scores = scores
+        return scores.result()
+    scores = BatchScores()
     with torch.inference_mode():
         for batch in tqdm(dl_test, total=len(dl_test)):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             scores.update(model(text, audio, padding_mask), emotion)
     return scores.result()
+
+
+def print_class_report(report):
+    """Per-class precision / recall / F1 / support of the pass (DeviceScores.report())."""
+    print(f"{'class':>5} {'precision':>9} {'recall':>9} {'f1':>9} {'support':>8}")
+    for c, (p, r, f, s) in enumerate(zip(report["precision"], report["recall"], report["f1"], report["support"])):
+        print(f"{c:>5} {p * 100:>8.3f}% {r * 100:>8.3f}% {f * 100:>8.3f}% {s:>8}")
 
 
 def main(config=None):
@@ -54,10 +73,13 @@ def main(config=None):
     else:
         loader = torch.utils.data.DataLoader(Dataset(mode="test"), collate_fn=collate_fn, **config.test.data_loader)
     model = M2FNet(config.model, precision=runtime_cfg.get("precision", "fp32")).to(device)
+    model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     load_model_weights(model, config.checkpoint.load_path, device)
     print("Testing...")
     accuracy, weighted_f1 = test(model, loader, device)
     print(f"Accuracy=[{accuracy * 100:.3f}%] Weighted_F1=[{weighted_f1 * 100:.3f}%]")
+    if model.device_metrics:
+        print_class_report(model.test_scores.report())
     print("Testing complete")
 
 

@@ -266,6 +266,7 @@ def main(config=None):
     model.step_mode = (bool(_runtime(config, "fused_step", True)), bool(_runtime(config, "use_graph", True)))
     model.fused_optimizer = bool(_runtime(config, "fused_optimizer", False))
     model.grad_accumulation_k = grad_accumulation_steps(config, world)
+    model.device_metrics = bool(_runtime(config, "device_metrics", False))      # validate(): score on the device (M2FNet.eval_step)
     if bool(_runtime(config, "grad_bf16", False)) and world == 1:
         model.set_grad_bf16(True)
     te_cfg = _runtime(config, "text_encoder", None)
@@ -490,10 +491,14 @@ def validate(model, dl_val, criterion, device):
     """-> (mean batch loss, accuracy, weighted_f1); scores by the per-batch rule of ``metrics.BatchScores``.
     With several ranks the replicas are identical and the rule is a plain mean over the reference's batches
     (src/train.py:245-272), so rank r evaluates batches r, r + W, ... WHOLE and the per-batch sums are added over the ranks:
-    the same three numbers as the single-process loop, on every rank (early stopping decides alike everywhere)."""
+    the same three numbers as the single-process loop, on every rank (early stopping decides alike everywhere).
+    With ``model.device_metrics`` (runtime.device_metrics, read once in main()) the loop body is ``model.eval_step``: loss, argmax,
+    accuracy and weighted F1 of every batch are formed on the device and the host reads one record after the last batch."""
     rank = _rank()
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     model.eval()
+    if getattr(model, "device_metrics", False):
+        return _validate_on_device(model, dl_val, criterion, device, rank, world)
     scores, loss_total = BatchScores(), 0.0
     with torch.inference_mode():
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
@@ -504,6 +509,23 @@ def validate(model, dl_val, criterion, device):
             scores.update(logits, emotion)
     acc_sum, f1_sum = scores.sums()
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks([loss_total, acc_sum, f1_sum, float(scores.n_batches)], device=device)
+    n = max(n, 1.0)
+    return loss_total / n, acc_sum / n, f1_sum / n
+
+
+def _validate_on_device(model, dl_val, criterion, device, rank, world):
+    from mer_amd.metrics import DeviceScores
+    if not isinstance(criterion, M2FCrossEntropyLoss):
+        raise ValueError("runtime.device_metrics: True scores with the M2FCrossEntropyLoss criterion's kernel; another criterion needs the host loop")
+    scores = DeviceScores(model.m2f_config.cls_out, device)
+    _, use_graph = _step_mode(model, criterion)
+    with torch.inference_mode():
+        for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
+            text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
+                                                           audio_encoder=getattr(model, "audio_encoder", None))
+            model.eval_step(text, audio, padding_mask, emotion, scores, class_weights=criterion.weight,
+                            label_smoothing=criterion.label_smoothing, use_graph=use_graph)
+    loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks(list(scores.totals()), device=device)      # (the one read of the pass)
     n = max(n, 1.0)
     return loss_total / n, acc_sum / n, f1_sum / n
 
