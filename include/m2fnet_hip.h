@@ -391,6 +391,44 @@ int m2f_plan_fused_adam_setup(m2f_plan* plan, float* params, float* exp_avg, flo
 int m2f_plan_fused_adam(m2f_plan* plan, int on);
 int m2f_adam_hyper(float* hyper_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int step, m2f_stream_t stream);
 
+/* ---- parameter groups and decoupled weight decay ---------------------------------------------------------------
+ * optimizer.step() of torch.optim.Adam / torch.optim.AdamW built over SEVERAL param_groups, or over a subset of the model's parameters
+ * (the reference's stage-1 trainers: feature_extractors/text/train.py:62-63, audio_wav2vec2/train.py:62-63 - torch.optim.AdamW over the
+ * head alone, then over everything), each group with its own lr / betas / eps / weight_decay and step count.
+ *
+ * m2f_adam_hyper_groups: refreshes the hyper table - n_groups <= M2F_ADAM_MAX_GROUPS rows of 8 floats in device memory (lr / bc1, beta1,
+ * beta2, eps, coupled weight decay, 1 / sqrt(bc2), decay, spare) - from `groups`, one small launch on `stream`, the values passed by
+ * value (no host sync; `groups` may be freed at once).  decoupled != 0 (AdamW): decay = 1 - lr * weight_decay, formed in double and
+ * rounded once as torch forms the scalar of param.mul_, and the coupled weight decay of the row is 0; otherwise decay = 1 and the row
+ * is torch.optim.Adam's.  step >= 1 is the group's own count (bias corrections).  Kernels read the table when they run, so a captured
+ * graph that holds them follows a scheduler's new lr without a re-capture.
+ *
+ * m2f_adam_step_grouped: the update of the tensors at flat offsets [first, end) (both the offset of a parameter tensor; end < 0: to the
+ * last one) that some group owns.  tensor_group: n_tensors host ints in parameter order (m2f_param_layout), the group of each tensor
+ * or -1 = owned by none: such a tensor, its moments and its shadows are neither read nor written.  param_shadow non-NULL (bf16 mode,
+ * the buffer of m2f_param_shadow_init): the kernel also writes W / W^T shadows of what it updates, as m2f_adam_step_shadowed_range does;
+ * NULL (fp32 mode): slices of at most 8192 elements of one tensor each, the alignment pads between tensors are not touched.
+ * A group whose row is Adam's gives m2f_adam_step / m2f_adam_step_shadowed's bits on its tensors.  Device copies of the item / slice
+ * lists are cached per (configuration, device, map). */
+#define M2F_ADAM_MAX_GROUPS 16
+typedef struct m2f_adam_group {
+    double lr;                                 /* torch keeps it as a double; lr / bc1 is formed from (float)lr as m2f_adam_step does */
+    float beta1, beta2, eps, weight_decay;
+    int decoupled;                             /* 0: torch.optim.Adam (coupled L2), 1: torch.optim.AdamW */
+    int step;                                  /* >= 1 */
+} m2f_adam_group;
+int m2f_adam_hyper_groups(float* hyper_table, const m2f_adam_group* groups, int n_groups, m2f_stream_t stream);
+int m2f_adam_step_grouped(const m2f_config* cfg, float* params, const void* grads, int grads_bf16, float* exp_avg, float* exp_avg_sq,
+                          uint16_t* param_shadow, const int* tensor_group, int n_tensors, const float* hyper_table, int64_t first,
+                          int64_t end, const float* grad_scale_ptr, m2f_stream_t stream);
+/* m2f_plan_fused_adam_setup for a grouped optimizer (torch.optim.AdamW(groups).step inside m2f_step): hyper_table = the rows of
+ * m2f_adam_hyper_groups (refreshed BEFORE every step), tensor_group as above.  The weight-gradient launch updates a matrix with the row
+ * of its group; the residual launch is the grouped shadow-writing kernel over the owned tensors the table does not cover.  Fails when a
+ * matrix of the weight-gradient table is owned by no group (its gradient would have nowhere to go: the caller takes the two-launch path).
+ * Drops the plan's captured step, as every setup does; m2f_plan_fused_adam(plan, 1 | 0) switches the form as before. */
+int m2f_plan_fused_adam_setup_grouped(m2f_plan* plan, float* params, float* exp_avg, float* exp_avg_sq, uint16_t* param_shadow,
+                                      const float* hyper_table, const int* tensor_group, int n_tensors, const float* grad_scale_ptr);
+
 /* Gradients left as bf16 (round 4; the data-parallel bf16 exchange, multimodal-emotion-recognition_amd/dp.py): after m2f_plan_grad_bf16(plan, g16)
  * a step writes EVERY gradient, rounded once to bf16, at its element index of g16 (n_params uint16, 16-byte aligned) - the weight
  * gradients of the table launch directly (no fp32 dW: -2 bytes per parameter written, and no rounding pass over the fp32 buffer before

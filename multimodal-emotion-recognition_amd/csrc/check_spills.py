@@ -24,7 +24,10 @@ mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
 gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
 # --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
 metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
-path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or metrics) else sys.argv[1]
+# --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
+# registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each
+adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
+path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or metrics or adam) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -38,6 +41,18 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
+        m = re.search(r"\b(VGPRs|TotalSGPRs): (\d+)", line)
+        if m:
+            cur[m.group(1)] = int(m.group(2))
+if adam:
+    kernels = [r for r in rows if any(t in r["name"] for t in ("m2f_adam_shadow_grouped", "m2f_adam_slices", "m2f_adam_hyper_groups"))]
+    if len(kernels) < 5:
+        sys.exit(f"check_spills: expected the five grouped optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
 if dlong or w2v or mel or gradnorm or metrics:
     tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_eval_"
     kernels = [r for r in rows if tag in r["name"]]

@@ -137,6 +137,8 @@ __device__ __forceinline__ void p8_adam4(f32x4& pp, const f32x4& gg, f32x4& mm, 
 //          consecutive elements of dW loads p, m, v of those elements, applies Adam, stores p, m, v and both bf16 parameter shadows
 //          (W 8 bytes; W^T four 2-byte stores, 16 consecutive rows per 16 lanes) - dW never reaches memory (-8 bytes per parameter
 //          and step, and the HBM-bound optimizer streams while other workgroups multiply)
+//      6 = 3 with parameter groups (optim.FusedAdam(params=[...]) / FusedAdamW): the six factors come from the hyper-table row of the
+//          problem's group instead of ONE row for the launch, and the parameter is multiplied by the row's `decay` first (AdamW)
 // EPI: 1 = plain fp32 result (the weight-gradient table: + bias-gradient row sums, ReLU on either operand's fragments),
 //      2 = text-encoder launches: bias, ReLU / GELU, residual, fp32 result unless GF_NO_F32, bf16 shadow
 //      5 = the ACCUMULATE form of 1 (m2f_plan_accumulate_grads): every dW element and bias-gradient row leaves as old + new, one rounded
@@ -169,7 +171,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
     // EPI 3 (optimizer in the epilogue): the stream ENDS with its output tile - the epilogue needs the operand buffers as its own
     // staging ring - so pieces issued past the tile's last k-tile (the schedule keeps issuing them: the counted waits count them) are
     // range-checked to zeros AND redirected into a 2 KiB dump area behind the operand buffers (the wave's W^T image, unused until then)
-    constexpr bool PER_TILE = EPI == 3;
+    constexpr bool ADAM = EPI == 3 || EPI == 6;         // optimizer in the epilogue; 6: one hyper row per problem (parameter groups) + decay
+    constexpr bool PER_TILE = ADAM;
     constexpr bool FWD = EPI == 2 || EPI == 4;          // forward-form epilogue (bias / activation / residual); 4: OCP e4m3 operands (see quad)
     constexpr bool ACC = EPI == 5;                       // weight-gradient table, accumulate form
     constexpr bool WG = EPI == 1 || ACC;                 // weight-gradient table (overwrite or accumulate)
@@ -342,8 +345,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
         const auto& P = *(TABLE ? (c_probp)(gb.table) + H.pi : (c_probp)(const GemmProblem*)&gb.pr[H.pi]);
         const int m0 = H.m0, n0 = H.n0, nk = (H.K + C::BK - 1) / C::BK;
         const bool reluA = false, reluB = H.flags & GF_RELU_B;
-        float* bias_grad = (WG || EPI == 3) ? P.bias_grad : nullptr;
-        const bool bgrad = (WG || EPI == 3) && RC && bias_grad && n0 == 0 && wc == 0;      // wave-uniform
+        float* bias_grad = (WG || ADAM) ? P.bias_grad : nullptr;
+        const bool bgrad = (WG || ADAM) && RC && bias_grad && n0 == 0 && wc == 0;      // wave-uniform
         float bsum[2][4];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -525,7 +528,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
 #else
 #define P8_LOOP(MASK) do { _Pragma("unroll 1") for (int kt = 0; kt < nk; ++kt) { ktile(par, std::integral_constant<int, MASK>{}, kt == 0 ? ep_relax : 0); par ^= 1; } } while (0)
 #endif
-        const int optm = (WG || EPI == 3) ? (bgrad ? 1 : 0) | (reluA ? 2 : 0) | (reluB ? 4 : 0) : 0;
+        const int optm = (WG || ADAM) ? (bgrad ? 1 : 0) | (reluA ? 2 : 0) | (reluB ? 4 : 0) : 0;
         if (optm == 0) P8_LOOP(0);
         else if (optm == 1) P8_LOOP(1);
         else if (optm == 4) P8_LOOP(4);
@@ -547,7 +550,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                     else { if (g == 0 && m < Mm) bias_grad[m] = t; }
                 }
         }
-        if constexpr (EPI == 3) {
+        if constexpr (ADAM) {
             typedef const __attribute__((address_space(4))) M2FAdamFuse* c_adamp;
             typedef const __attribute__((address_space(4))) float* c_f32p;
             const auto& AD = *(c_adamp)(gb.adam);
@@ -556,7 +559,9 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
             uint16_t* __restrict__ shw = reinterpret_cast<uint16_t*>(const_cast<float*>(P.res));
             uint16_t* __restrict__ shwt = reinterpret_cast<uint16_t*>(const_cast<float*>(P.gate));
             const int ldd = P.ldres, ldt = P.ldgate;
-            c_f32p hy = (c_f32p)(AD.hyper);
+            // EPI 6: the row of the group that owns this problem's tensor (the plan put it into the problem's c8 field; scalar loads as before)
+            c_f32p hy = EPI == 6 ? (c_f32p)(const float*)(P.c8) : (c_f32p)(AD.hyper);
+            [[maybe_unused]] const float decay = EPI == 6 ? hy[6] : 1.f;
             const float lr_bc1 = hy[0], beta1 = hy[1], beta2 = hy[2], eps = hy[3], wd = hy[4], inv_sqrt_bc2 = hy[5];
             const float gs = AD.gs_ptr ? 1.0f / *((c_f32p)(AD.gs_ptr)) : 1.0f;
             const bool avec = ((ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(Pp) & 15) == 0) && ((reinterpret_cast<uintptr_t>(shw) & 7) == 0) && ((ldd & 3) == 0);
@@ -607,6 +612,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                     const size_t oc = (size_t)((uint32_t)(row * ldc + col));
                     const char* sl = ringp + (n % 5) * 3072;
                     f32x4 pp = *reinterpret_cast<const f32x4*>(sl), mm = *reinterpret_cast<const f32x4*>(sl + 1024), vv = *reinterpret_cast<const f32x4*>(sl + 2048);
+                    if constexpr (EPI == 6) pp = pp * decay;          // AdamW's param.mul_(1 - lr * wd): rowops.hip::adamw4
                     p8_adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
                     *reinterpret_cast<f32x4*>(Pp + oc) = pp;
                     __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(Mp + oc));
@@ -656,6 +662,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                                     const size_t oc = in[e] ? (size_t)((uint32_t)(row * ldc + col + e)) : 0;
                                     pp[e] = Pp[oc]; mm[e] = Mp[oc]; vv[e] = Vp[oc];
                                 }
+                                if constexpr (EPI == 6) pp = pp * decay;
                                 p8_adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
 #pragma unroll
                                 for (int e = 0; e < 4; ++e)
@@ -871,7 +878,7 @@ hipError_t launch_p8_grid(const GemmBatch& hb, int tiles, hipStream_t stream) {
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     auto kern = m2f_gemm_p8_kernel<RC, TABLE, EPI>;
-    constexpr int lds_bytes = P8Cfg::LDS + (EPI == 3 ? 8 * P8_ADAM_T_BYTES : 0);
+    constexpr int lds_bytes = P8Cfg::LDS + ((EPI == 3 || EPI == 6) ? 8 * P8_ADAM_T_BYTES : 0);
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);

@@ -134,6 +134,9 @@ hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream);     // Adam in the epilogue (gb.adam)
+// ... with parameter groups (EPI 6): as above, and every problem carries the hyper-table row of its tensor's group in `c8` (a const float*;
+// fp8 launches alone use that field otherwise) - gb.adam->hyper is not read; the update multiplies the parameter by the row's `decay` first
+hipError_t m2f_p8_launch_table_rc_adam_grouped(const GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc_acc(const GemmBatch& gb, hipStream_t stream);      // accumulate form: dW, bias gradients = old + new
 
 // Launches one grouped GEMM. Returns hipSuccess or the launch error. `tile` = 0 (auto), 64 or 128.
@@ -358,6 +361,20 @@ hipError_t m2f_launch_cast_items(const float* src, uint16_t* dst, const AdamItem
 hipError_t m2f_launch_adam_hyper(float* hyper_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int step, hipStream_t stream);
 hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, float* v, uint16_t* shadow, const AdamItem* items, const int* tile_begin,
                                         int n_items, int total_tiles, const float* hyper_dev, const float* grad_scale_ptr, hipStream_t stream);
+
+// Parameter groups (optim.FusedAdam(params=[...]) / FusedAdamW; torch.optim.Adam / AdamW with several param_groups).  The hyper table
+// holds one row of 8 floats per group in device memory: lr / bc1, beta1, beta2, eps, coupled weight decay, 1 / sqrt(bc2), decay, spare -
+// decay = 1 - lr * weight_decay for a decoupled group (whose coupled weight decay is 0), 1.0f otherwise.  rows_host: n_groups x 8 floats,
+// passed to the refresh kernel by value.  The shadow-writing form walks items[] (the tensors some group owns, re-tiled; item_group[] runs
+// parallel to it); the flat form walks slices of at most M2F_ADAM_SLICE elements of one owned tensor (fp32 mode: no shadows).
+#define M2F_ADAM_SLICE 8192      // (M2F_ADAM_MAX_GROUPS: include/m2fnet_hip.h)
+struct AdamSlice { long long off; int n; int group; };
+hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host, int n_groups, hipStream_t stream);
+hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
+                                            const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
+                                            const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream);
+hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
+                                  const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream);
 
 // Global gradient norm + clip record (gradnorm.hip).  A slice = at most M2F_GRADNORM_SLICE consecutive elements of ONE parameter tensor
 // (`off`: its first element in the flat buffer; only the last slice of a tensor is short), cut by the host from the parameter map, so

@@ -441,6 +441,17 @@ __device__ __forceinline__ void adam4(f32x4& pp, const f32x4& gg, f32x4& mm, f32
     }
 }
 
+// The grouped kernels' update (one hyper row per parameter group, m2f_adam_hyper_groups_kernel): torch.optim.AdamW multiplies the
+// parameter by `decay` = 1 - lr * weight_decay first (torch's param.mul_: ONE rounded fp32 multiply; the row of a decoupled group holds
+// a coupled weight decay of 0), then the statements of adam4.  A coupled group's row holds decay = 1.0f, an exact multiply: its result
+// is adam4's, bit for bit.
+__device__ __forceinline__ void adamw4(f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv, float gs, float lr_bc1, float beta1,
+                                       float beta2, float eps, float wd, float inv_sqrt_bc2, float decay) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pp[e] = pp[e] * decay;
+    adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+}
+
 // G16: the gradient buffer holds bf16 (the data-parallel bf16 exchange), everything else stays fp32
 template <bool G16>
 __global__ __launch_bounds__(256) void m2f_adam_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
@@ -487,13 +498,17 @@ __device__ __forceinline__ float adam_grad1(const void* g, long long o) {
 
 // see ops.h (AdamItem).  Persistent 1-D grid over tiles [tile_first, total_tiles) of items[0, n_items) (tile_begin[] holds absolute
 // tile numbers); tile -> item by bisection of the prefix array (kept in LDS).
-template <bool G16>
+// GROUPED: items[] holds the tensors some parameter group owns, item_group[] (parallel to items[]) their group, and the six factors
+// plus `decay` come from row item_group[i] of the hyper table `hyt` instead of the arguments - the item is the same in every lane of
+// the workgroup, so the row arrives by scalar loads and costs no vector register.
+template <bool G16, bool GROUPED = false>
 __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, uint16_t* __restrict__ sh,
                                                  const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
                                                  int n_items, int tile_first, int total_tiles, float lr_bc1, float beta1,
                                                  float beta2, float eps, float wd, float inv_sqrt_bc2,
-                                                 const float* __restrict__ gs_ptr) {
+                                                 const float* __restrict__ gs_ptr, const float* __restrict__ hyt = nullptr,
+                                                 const int* __restrict__ item_group = nullptr) {
     __shared__ float tile[64][65];
     __shared__ int tb[M2F_ADAM_MAX_ITEMS + 1];
     const int tid = threadIdx.x;
@@ -508,6 +523,15 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
         }
         const AdamItem it = items[lo];
         const int tl = t - tb[lo];
+        float decay = 1.f;
+        if constexpr (GROUPED) {
+            const float* __restrict__ h = hyt + 8 * item_group[__builtin_amdgcn_readfirstlane(lo)];
+            lr_bc1 = h[0]; beta1 = h[1]; beta2 = h[2]; eps = h[3]; wd = h[4]; inv_sqrt_bc2 = h[5]; decay = h[6];
+        }
+        auto update = [&](f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv) {
+            if constexpr (GROUPED) adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
+            else adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+        };
         if (it.rows == 0) {                                         // 1-D parameter: 4096 consecutive elements per tile
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -518,7 +542,7 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
                     const f32x4 gg = adam_grad4<G16>(g, o);
                     f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + o));
                     f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + o));
-                    adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+                    update(pp, gg, mm, vv);
                     *reinterpret_cast<f32x4*>(p + o) = pp;
                     __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
                     __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
@@ -553,7 +577,7 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = lr + 16 * i, gr = r0 + r;
-            adam4(pp[i], gg[i], mm[i], vv[i], gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+            update(pp[i], gg[i], mm[i], vv[i]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) tile[r][c + e] = (in[i] && gc + e < cols) ? pp[i][e] : 0.f;
             if (in[i]) {
@@ -612,6 +636,69 @@ __global__ __launch_bounds__(256) void m2f_adam_shadow_dev_kernel(float* __restr
                                                                   int n_items, int total_tiles, const float* __restrict__ hy,
                                                                   const float* __restrict__ gs_ptr) {
     adam_shadow_body<false>(p, g, m, v, sh, items, tile_begin, n_items, 0, total_tiles, hy[0], hy[1], hy[2], hy[3], hy[4], hy[5], gs_ptr);
+}
+
+// Parameter groups (optim.FusedAdam(params=[...]), FusedAdamW): the shadow-writing update over the tensors of items[] with the hyper
+// row of each item's group.  The rows live in device memory (refreshed once per step by m2f_adam_hyper_groups_kernel), so this ONE
+// form serves the eager step, the [first, end) ranges of the data-parallel path and a captured graph.
+template <bool G16>
+__global__ __launch_bounds__(256) void m2f_adam_shadow_grouped_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
+                                                                      float* __restrict__ v, uint16_t* __restrict__ sh,
+                                                                      const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
+                                                                      const int* __restrict__ item_group, int n_items, int tile_first,
+                                                                      int total_tiles, const float* __restrict__ hyt,
+                                                                      const float* __restrict__ gs_ptr) {
+    adam_shadow_body<G16, true>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gs_ptr, hyt,
+                                item_group);
+}
+
+// fp32 mode (no shadows to write): the flat kernel runs over pads and tensors alike and cannot know a group, so the grouped form
+// walks SLICES - at most M2F_ADAM_SLICE consecutive elements of one owned tensor (ops.h AdamSlice; cut by the host from the parameter
+// map as the gradient norm's are: pads belong to no slice) - each with its group's hyper row.  16-byte accesses, g / m / v nontemporal
+// as in m2f_adam_kernel; the last 1-3 elements of a tensor whose size is no multiple of 4 go one by one, nothing behind them is touched.
+template <bool G16>
+__global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, const AdamSlice* __restrict__ slices, int s0, int s1,
+                                                              const float* __restrict__ hyt, const float* __restrict__ gs_ptr) {
+    const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
+    const int tid = threadIdx.x;
+    for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
+        const AdamSlice sl = slices[s];
+        const float* __restrict__ h = hyt + 8 * sl.group;
+        const float lr_bc1 = h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4], inv_sqrt_bc2 = h[5], decay = h[6];
+#pragma unroll 2
+        for (int j = 0; j < M2F_ADAM_SLICE / 1024; ++j) {
+            const int e = (j * 256 + tid) * 4;
+            const long long o = sl.off + e;                         // tensor offsets are multiples of 64 elements: 16-byte aligned
+            if (e + 4 <= sl.n) {
+                f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + o));
+                const f32x4 gg = adam_grad4<G16>(g, o);
+                f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + o));
+                f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + o));
+                adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
+                *reinterpret_cast<f32x4*>(p + o) = pp;
+                __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
+                __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
+            } else if (e < sl.n) {
+                f32x4 pp = {0.f, 0.f, 0.f, 0.f}, gg = pp, mm = pp, vv = pp;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (e + k < sl.n) { pp[k] = p[o + k]; gg[k] = adam_grad1<G16>(g, o + k); mm[k] = m[o + k]; vv[k] = v[o + k]; }
+                adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (e + k < sl.n) { p[o + k] = pp[k]; m[o + k] = mm[k]; v[o + k] = vv[k]; }
+            }
+        }
+    }
+}
+
+// the hyper table: G rows of 8 floats (lr / bc1, beta1, beta2, eps, coupled wd, 1 / sqrt(bc2), decay, spare), formed by the host and
+// passed BY VALUE - no host buffer to keep alive, no sync, and a captured graph that reads the table sees the new rows at its next replay
+struct AdamHyperRows { float r[M2F_ADAM_MAX_GROUPS * 8]; };
+__global__ __launch_bounds__(M2F_ADAM_MAX_GROUPS * 8) void m2f_adam_hyper_groups_kernel(float* __restrict__ h, int n, const AdamHyperRows rows) {
+    const int i = threadIdx.x;
+    if (i < n) h[i] = rows.r[i];
 }
 
 template <bool BWD>
@@ -980,5 +1067,41 @@ hipError_t m2f_launch_adam(float* p, const void* g, int g_is_bf16, float* m, flo
     else
         hipLaunchKernelGGL(m2f_adam_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, (float)(lr / bc1), beta1, beta2,
                            eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host, int n_groups, hipStream_t stream) {
+    if (!table_dev || !rows_host || n_groups < 1 || n_groups > M2F_ADAM_MAX_GROUPS) return hipErrorInvalidValue;
+    AdamHyperRows rows;
+    for (int i = 0; i < M2F_ADAM_MAX_GROUPS * 8; ++i) rows.r[i] = i < n_groups * 8 ? rows_host[i] : 0.f;
+    hipLaunchKernelGGL(m2f_adam_hyper_groups_kernel, dim3(1), dim3(M2F_ADAM_MAX_GROUPS * 8), 0, stream, table_dev, n_groups * 8, rows);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
+                                            const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
+                                            const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream) {
+    const int n_tiles = total_tiles - tile_first;
+    if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || tile_first < 0 || n_tiles < 1 || !items || !tile_begin || !item_group || !shadow || !hyper_table)
+        return hipErrorInvalidValue;
+    const int blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
+    if (g_is_bf16)
+        hipLaunchKernelGGL(m2f_adam_shadow_grouped_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin,
+                           item_group, n_items, tile_first, total_tiles, hyper_table, grad_scale_ptr);
+    else
+        hipLaunchKernelGGL(m2f_adam_shadow_grouped_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin,
+                           item_group, n_items, tile_first, total_tiles, hyper_table, grad_scale_ptr);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
+                                  const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream) {
+    if (!p || !g || !m || !v || !slices || !hyper_table || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
+    if (s1 == s0) return hipSuccess;
+    const int blocks = s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8;
+    if (g_is_bf16)
+        hipLaunchKernelGGL(m2f_adam_slices_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr);
+    else
+        hipLaunchKernelGGL(m2f_adam_slices_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr);
     return hipGetLastError();
 }

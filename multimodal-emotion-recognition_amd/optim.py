@@ -6,9 +6,12 @@
   L2, bias-corrected; ONE kernel over the flat parameter / gradient / moment buffers instead of ~130 per-tensor
   updates.  ``state_dict()`` keeps torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` /
   ``exp_avg_sq`` indexed in reference parameter order), so reference checkpoints load and vice versa.
+  ``FusedAdam(model, params=[...])`` takes torch's parameter groups (own lr / betas / eps / weight_decay per group, parameters in no
+  group left alone); ``decoupled_weight_decay=True`` / ``FusedAdamW`` = ``torch.optim.AdamW``.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -16,6 +19,11 @@ import torch.nn as nn
 
 from . import functional as F
 from . import runtime
+from .layout import param_specs
+
+# what torch.optim.Adam / AdamW accept and this optimizer does not: refused by name when set, never ignored
+_TORCH_ONLY = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused")
+MAX_GROUPS = runtime.ADAM_MAX_GROUPS
 
 
 class _CEFunction(torch.autograd.Function):
@@ -54,8 +62,22 @@ class FusedAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` (coupled L2 weight decay, reference ``src/train.py:56``) as ONE kernel over the model's flat
     parameter / gradient / moment buffers.  Differences from torch worth knowing: every parameter of the model is updated every
     step - a parameter whose ``.grad`` is None is treated as having a zero gradient (it still receives weight decay and the
-    moment decay; torch skips it), which never happens on the M2FNet path, where backward writes every gradient; there is one
-    parameter group (one lr / betas / eps / weight_decay for the whole model).
+    moment decay; torch skips it), which never happens on the M2FNet path, where backward writes every gradient.
+
+    Parameter groups and AdamW (keyword-only).  ``params``: torch's own format - an iterable of parameters, or of dicts with ``params``
+    and any of ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` / ``decoupled_weight_decay`` - at most 16 groups, every parameter one of
+    ``model``'s and in one group only.  None (the default) = ``model.parameters()`` in one group: with coupled decay that is the optimizer
+    described above, kernel for kernel.  ``decoupled_weight_decay=True`` (``FusedAdamW``: the same with ``weight_decay=1e-2``) =
+    ``torch.optim.AdamW``: the parameter is multiplied by ``1 - lr * weight_decay`` before Adam's update, and the decay stays out of
+    the moments.  A parameter in NO group is neither read nor written by a step - parameter, both moments and both bf16 shadows keep
+    their bits, ``engine.shadows_fresh()`` stays true - but its gradient is still computed, and still counts in ``max_grad_norm``'s
+    norm (``clip_grad_norm_(model.parameters(), x)``; one divisor for every group).  ``param_groups[i][...]`` are read at every step
+    (torch's schedulers work per group), every group counts its own steps (``add_param_group`` starts one at 0), and ``state_dict()``
+    / ``load_state_dict()`` keep torch's format with indices running on across the groups: a ``torch.optim.AdamW`` state dict over the
+    same parameter lists loads, and back.  ``amsgrad``, ``maximize``, ``foreach``, ``capturable``, ``differentiable`` and ``fused``
+    raise when set.  ``step_ranges`` of a grouped optimizer takes ranges of whole tensors only.  All of it runs through one hyper table
+    on the device (a row per group, refreshed by one small launch per step) and grouped forms of the same kernels: a coupled group's
+    tensors get the bits the single-group kernels give them (tests/test_optimizer_groups_gpu.py).
 
     ``max_grad_norm`` (constructor argument and plain attribute; may be changed or set to None between steps; not part of
     ``state_dict``): every step first clips the gradient by its global L2 norm, ``torch.nn.utils.clip_grad_norm_(parameters,
@@ -69,14 +91,30 @@ class FusedAdam(torch.optim.Optimizer):
     does.  None (the default): the step as it was, launch for launch."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, *, params=None, decoupled_weight_decay: bool = False, **torch_options):
+        for k, v in torch_options.items():
+            if k not in _TORCH_ONLY:
+                raise TypeError(f"FusedAdam.__init__() got an unexpected keyword argument {k!r}")
+            if v:
+                raise ValueError(f"FusedAdam does not implement {k}={v!r} (torch.optim.Adam's option; only {k}=False / None is accepted)")
         self.model = model
+        # grouped: anything but ONE coupled group over model.parameters() - the hyper table and the grouped kernels instead of
+        # the single-group entries
+        self._grouped = params is not None or bool(decoupled_weight_decay)
+        self._own_ids = {id(p) for p in model.parameters()}
+        self._gsteps = []                                  # grouped: one step count per parameter group
+        self._table: Optional[torch.Tensor] = None         # grouped: [16, 8] fp32 on the device (runtime.adam_hyper_groups)
+        self._tg = self._tg_key = None                     # tensor -> group map (ctypes int array) and what it was built from
         self.max_grad_norm = max_grad_norm
         self._clip_scratch: Optional[torch.Tensor] = None  # float64 partial sums of squares (runtime.grad_norm_scratch)
         self._clip_record: Optional[torch.Tensor] = None   # 4 fp32 on the device: norm, coef, divisor, sqrt(sum of squares)
         self._clip_cfg = None
-        params = list(model.parameters())
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if self._grouped:
+            # torch's own keys too, so that the groups of state_dict() load into torch.optim.Adam / AdamW, whose step() reads them
+            defaults.update({k: (None if k in ("foreach", "fused") else False) for k in _TORCH_ONLY})
+            defaults["decoupled_weight_decay"] = bool(decoupled_weight_decay)
+        super().__init__(list(model.parameters()) if params is None else params, defaults)
         self._engine = None
         self._m = self._v = None
         self._step = 0
@@ -85,10 +123,71 @@ class FusedAdam(torch.optim.Optimizer):
         self.grads_bf16: Optional[torch.Tensor] = None     # bf16 [n_params]: step() reads THIS instead of the fp32 gradient buffer (a plan
                                                            # armed with runtime.Plan.grad_bf16 left its gradients there, rounded once)
 
+    def add_param_group(self, param_group):
+        """torch's ``add_param_group`` with this optimizer's rules: the parameters are ``model``'s, at most 16 groups, no option this
+        optimizer does not implement.  Works before and between steps; the new group's step count starts at 0.  A second group turns
+        the single coupled group into a grouped optimizer (its count carries over)."""
+        if not isinstance(param_group, dict):
+            raise TypeError(f"param_group must be a dict (got {type(param_group).__name__})")
+        ps = param_group["params"]
+        ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+        foreign = [p for p in ps if id(p) not in self._own_ids]
+        if foreign:
+            raise ValueError(f"FusedAdam: {len(foreign)} parameter(s) of a group do not belong to the model (first shape: "
+                             f"{tuple(foreign[0].shape)}); the optimizer updates the model's flat buffer only")
+        if len(self.param_groups) >= MAX_GROUPS:
+            raise ValueError(f"FusedAdam takes at most {MAX_GROUPS} parameter groups (the hyper table's rows)")
+        for k in _TORCH_ONLY:
+            if param_group.get(k):
+                raise ValueError(f"FusedAdam does not implement {k}={param_group[k]!r} (parameter group {len(self.param_groups)})")
+        if self.param_groups and not self._grouped:
+            self._grouped = True
+            self._gsteps = [self._step]
+            self.param_groups[0].setdefault("decoupled_weight_decay", False)
+            self.defaults.setdefault("decoupled_weight_decay", False)
+        super().add_param_group({**param_group, "params": ps})
+        self._gsteps.append(0)
+        self._tg_key = None
+
+    def _unique_params(self):
+        """The model's parameter tensors in parameter-map order (layout.param_specs == plan.hip::build_param_map; the engine's items)."""
+        named = dict(self.model.named_parameters(remove_duplicate=False))
+        seen, out = set(), []
+        for sp in param_specs(self.model.m2f_config)[0]:
+            p = named[sp.name]
+            if sp.alias_of or id(p) in seen:
+                continue
+            seen.add(id(p))
+            out.append(p)
+        return out
+
+    def tensor_group_map(self):
+        """One int per parameter tensor in parameter-map order: the index of the group that owns it, -1 = none."""
+        key = tuple(len(g["params"]) for g in self.param_groups)
+        if self._tg_key != key:
+            owner = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+            self._tg_list = [owner.get(id(p), -1) for p in self._unique_params()]
+            self._tg = (ctypes.c_int * len(self._tg_list))(*self._tg_list)
+            self._tg_key = key
+        return list(self._tg_list)
+
+    def _refresh_table(self, eng):
+        """This step's row of every group into the device table (one launch, values by value: no sync); -> the tensor -> group map."""
+        if self._table is None or self._table.device != eng.flat.device:
+            self._table = torch.zeros(MAX_GROUPS, 8, dtype=torch.float32, device=eng.flat.device)
+        runtime.adam_hyper_groups(self._table, [(float(g["lr"]), g["betas"], g["eps"], g["weight_decay"],
+                                                 g.get("decoupled_weight_decay", self.defaults.get("decoupled_weight_decay", False)), t)
+                                                for g, t in zip(self.param_groups, self._gsteps)])
+        self.tensor_group_map()
+        return self._tg
+
+    def _owns_everything(self) -> bool:
+        return -1 not in self.tensor_group_map()
+
     def _bind(self):
         eng = self.model.engine()
         if eng is not self._engine:
-            old = {id(p): self.state.get(p) for p in self.param_groups[0]["params"]}
+            old = {id(p): self.state.get(p) for g in self.param_groups for p in g["params"]}
             self._engine = eng
             self._m = torch.zeros_like(eng.flat)
             self._v = torch.zeros_like(eng.flat)
@@ -157,6 +256,16 @@ class FusedAdam(torch.optim.Optimizer):
                     view.zero_()
                 elif p.grad.data_ptr() != view.data_ptr():
                     view.copy_(p.grad)
+        if self._grouped:
+            self._gsteps = [t + 1 for t in self._gsteps]
+            scale = self._clip(eng, flat_grad)
+            tg = self._refresh_table(eng)
+            # the owned tensors with their group's row: shadow-writing kernel (bf16 mode) or slices (fp32 mode).  Tensors of no group are
+            # not touched, so their shadows stay what they were: fresh before = fresh after (the version counters do not move)
+            runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale)
+            if eng.wshadow is not None and self._owns_everything():
+                eng.mark_shadows_fresh()
+            return loss
         self._step += 1
         scale = self._clip(eng, flat_grad)                   # grad_scale, or the clip record's divisor (max_grad_norm)
         if eng.wshadow is not None:
@@ -184,6 +293,8 @@ class FusedAdam(torch.optim.Optimizer):
         eng = self._bind()
         if eng.wshadow is None or not plan.train or not getattr(plan, "shared_shadow", False):
             return False
+        if self._grouped:
+            return self._prepare_fused_grouped(eng, plan)
         if getattr(plan, "_fused_bad", False):
             return False
         if self._hyper is None:
@@ -205,10 +316,37 @@ class FusedAdam(torch.optim.Optimizer):
         plan.fused_adam(True)
         return True
 
+    def _prepare_fused_grouped(self, eng, plan) -> bool:
+        # the in-launch form with groups (gemm_p8.h EPI 6): every matrix of the weight-gradient table must be owned - the launch holds
+        # its gradient in registers and has nowhere else to put it; otherwise the two-launch branch
+        tg = self.tensor_group_map()
+        if self._table is None or self._table.device != eng.flat.device:
+            self._table = torch.zeros(MAX_GROUPS, 8, dtype=torch.float32, device=eng.flat.device)
+        key = ("grouped", tuple(tg), self._m.data_ptr(), self._v.data_ptr(), eng.flat.data_ptr(), eng.wshadow.data_ptr(),
+               self._table.data_ptr(), self.grad_scale.data_ptr() if self.grad_scale is not None else 0)
+        if getattr(plan, "_fused_bad_key", None) == key:
+            return False
+        if getattr(plan, "_fused_key", None) != key:
+            try:
+                eng.ensure_grad()
+                plan.fused_adam_setup_grouped(eng.flat, self._m, self._v, eng.wshadow, self._table, tg, self.grad_scale)
+            except runtime.HipError as e:
+                plan._fused_key = None                     # (a failed setup leaves the plan without one)
+                plan._fused_bad_key = key
+                plan._fused_err = str(e)
+                return False
+            plan._fused_key = key
+        self._gsteps = [t + 1 for t in self._gsteps]
+        self._refresh_table(eng)
+        plan.fused_adam(True)
+        return True
+
     def finish_fused(self, plan) -> None:
-        """After the armed step: the kernels wrote every parameter and both bf16 shadows of every matrix."""
+        """After the armed step: the kernels wrote every parameter and both bf16 shadows of every matrix (grouped: of every owned
+        one - the others kept theirs, fresh if they were)."""
         plan.fused_adam(False)
-        self._engine.mark_shadows_fresh()
+        if not self._grouped or self._owns_everything():
+            self._engine.mark_shadows_fresh()
 
     @torch.no_grad()
     def step_ranges(self, ranges, before_each=None, grads=None):
@@ -225,8 +363,10 @@ class FusedAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         flat_grad = eng.ensure_grad() if grads is None else grads
         n = eng.flat.numel()
-        self._step += 1
         ranges = [(lo, min(hi, n)) for (lo, hi) in ranges]
+        if self._grouped:
+            return self._step_ranges_grouped(eng, flat_grad, ranges, before_each, n)
+        self._step += 1
         scale = self.grad_scale
         if self.max_grad_norm is not None:
             if before_each is not None:
@@ -260,6 +400,35 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 eng.invalidate_shadows()
 
+    def _step_ranges_grouped(self, eng, flat_grad, ranges, before_each, n):
+        starts = self._tensor_starts(eng)
+        for lo, hi in ranges:
+            if hi > lo and not (lo in starts and (hi >= n or hi in starts)):
+                raise ValueError(f"FusedAdam.step_ranges: the range [{lo}, {hi}) cuts a parameter tensor; an optimizer with parameter "
+                                 "groups / decoupled weight decay takes ranges of whole tensors only (dp.GradReducer's buckets are)")
+        self._gsteps = [t + 1 for t in self._gsteps]
+        scale = self.grad_scale
+        if self.max_grad_norm is not None:
+            if before_each is not None:
+                for i in range(len(ranges)):
+                    before_each(i)
+                before_each = None
+            scale = self._clip(eng, flat_grad)
+        tg = self._refresh_table(eng)
+        for i, (lo, hi) in enumerate(ranges):
+            if before_each is not None:
+                before_each(i)
+            if hi > lo:
+                runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale,
+                                          first=lo, end=(-1 if hi >= n else hi))
+        if eng.wshadow is not None:
+            covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
+            whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
+            if not whole:
+                eng.invalidate_shadows()
+            elif self._owns_everything():
+                eng.mark_shadows_fresh()
+
     def _tensor_starts(self, eng):
         if getattr(self, "_starts_of", None) is not eng:
             self._starts = frozenset(int(o) for (_, o, _, _) in eng.items)
@@ -267,6 +436,15 @@ class FusedAdam(torch.optim.Optimizer):
         return self._starts
 
     def state_dict(self):
+        if self._grouped:
+            if self._engine is not None:
+                at = {id(p): (o, n, s) for (p, o, n, s) in self._engine.items}
+                for g, t in zip(self.param_groups, self._gsteps):
+                    for p in (g["params"] if t > 0 else ()):                   # (a group that never stepped has no state, as in torch)
+                        o, n, s = at[id(p)]
+                        self.state[p] = {"step": torch.tensor(float(t)), "exp_avg": self._m[o: o + n].view(s),
+                                         "exp_avg_sq": self._v[o: o + n].view(s)}
+            return super().state_dict()
         if self._engine is not None and self._step > 0:
             self._materialise_state(self._engine)
             for p in self.param_groups[0]["params"]:
@@ -281,6 +459,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._v = torch.zeros_like(eng.flat)
         steps = [int(st["step"]) for st in self.state.values() if st and "step" in st]
         self._step = max(steps) if steps else 0
+        if self._grouped:                                  # every group's own count: what its parameters carry
+            self._gsteps = [max([int(self.state[p]["step"]) for p in g["params"] if self.state.get(p) and "step" in self.state[p]] or [0])
+                            for g in self.param_groups]
+            self._tg_key = None
         for (p, o, n, s) in eng.items:
             st = self.state.get(p)
             if st:
@@ -288,3 +470,13 @@ class FusedAdam(torch.optim.Optimizer):
                 mv.copy_(st["exp_avg"])
                 vv.copy_(st["exp_avg_sq"])
                 st["exp_avg"], st["exp_avg_sq"] = mv, vv
+
+
+class FusedAdamW(FusedAdam):
+    """``torch.optim.AdamW`` (the reference's stage-1 trainers, feature_extractors/text/train.py:62-63; the M2FNet paper's optimizer):
+    ``FusedAdam`` with decoupled weight decay and AdamW's default ``weight_decay=1e-2``.  ``params`` as in ``FusedAdam``."""
+
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 max_grad_norm: Optional[float] = None, *, params=None, **torch_options):
+        super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, params=params, decoupled_weight_decay=True,
+                         **torch_options)

@@ -123,6 +123,10 @@ SIGNATURES = {
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
     "m2f_adam_hyper": (c_int, [c_void_p, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p]),
+    "m2f_adam_hyper_groups": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "m2f_adam_step_grouped": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "m2f_plan_fused_adam_setup_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "m2f_gemm_p8": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                             c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "m2f_gemm_fp8": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p,
@@ -548,6 +552,14 @@ class Plan:
             return out
         return rows.view(self.B, self.L, -1)[:b, :l].clone()
 
+    def fused_adam_setup_grouped(self, params, exp_avg, exp_avg_sq, param_shadow, hyper_table, tensor_group, grad_scale=None) -> None:
+        """m2f_plan_fused_adam_setup_grouped: ``fused_adam_setup`` for an optimizer with parameter groups / decoupled weight decay -
+        `hyper_table` the rows of ``adam_hyper_groups``, `tensor_group` the group of every parameter tensor (-1: none)."""
+        tg = (c_int * len(tensor_group))(*tensor_group)
+        check(lib().m2f_plan_fused_adam_setup_grouped(self._h(), params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                                      param_shadow.data_ptr(), hyper_table.data_ptr(), tg, len(tensor_group), ptr(grad_scale)),
+              "m2f_plan_fused_adam_setup_grouped")
+
     def fused_adam(self, on: bool) -> None:
         """The NEXT step() also takes the optimizer step (on) / leaves the weight gradients in the gradient buffer (off)."""
         check(lib().m2f_plan_fused_adam(self._h(), int(bool(on))), "m2f_plan_fused_adam")
@@ -680,3 +692,31 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
     check(lib().m2f_adam_step(params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                               params.numel(), lr, betas[0], betas[1], eps, weight_decay, step, ptr(grad_scale),
                               stream_ptr()), "m2f_adam_step")
+
+
+ADAM_MAX_GROUPS = 16
+
+
+class AdamGroupC(ctypes.Structure):
+    """m2f_adam_group (include/m2fnet_hip.h)."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
+                ("decoupled", c_int), ("step", c_int)]
+
+
+def adam_hyper_groups(table: torch.Tensor, groups) -> None:
+    """m2f_adam_hyper_groups: one row of 8 floats per group into `table` ([>= len(groups), 8] fp32 on the device), one launch on the
+    current stream.  `groups`: (lr, (beta1, beta2), eps, weight_decay, decoupled, step) per group, step >= 1 the group's own count."""
+    arr = (AdamGroupC * len(groups))(*[AdamGroupC(float(lr), float(b[0]), float(b[1]), float(eps), float(wd), int(bool(dec)), int(step))
+                                       for (lr, b, eps, wd, dec, step) in groups])
+    check(lib().m2f_adam_hyper_groups(table.data_ptr(), arr, len(groups), stream_ptr()), "m2f_adam_hyper_groups")
+
+
+def adam_step_grouped(cfg: M2FConfig, params, grads, exp_avg, exp_avg_sq, param_shadow: Optional[torch.Tensor], tensor_group,
+                      hyper_table: torch.Tensor, grad_scale: Optional[torch.Tensor] = None, first: int = 0, end: int = -1) -> None:
+    """torch.optim.Adam / AdamW with parameter groups over the flat buffers (m2f_adam_step_grouped): the tensors at offsets
+    [first, end) that a group owns (`tensor_group`: a ctypes int array, one entry per parameter tensor, -1 = none) with their group's row
+    of `hyper_table`; `param_shadow` (bf16 mode) or None (fp32 mode); `grads` fp32 or bf16."""
+    cc = config_to_c(cfg)
+    check(lib().m2f_adam_step_grouped(ctypes.byref(cc), params.data_ptr(), grads.data_ptr(), int(grads.dtype == torch.bfloat16),
+                                      exp_avg.data_ptr(), exp_avg_sq.data_ptr(), ptr(param_shadow), tensor_group, len(tensor_group),
+                                      hyper_table.data_ptr(), int(first), int(end), ptr(grad_scale), stream_ptr()), "m2f_adam_step_grouped")

@@ -20,7 +20,7 @@ from metrics import BatchScores, move_batch  # noqa: E402
 from model import M2FNet  # noqa: E402
 from utils import get_config  # noqa: E402
 from mer_amd import dp  # noqa: E402
-from mer_amd.optim import FusedAdam, M2FCrossEntropyLoss  # noqa: E402
+from mer_amd.optim import MAX_GROUPS, FusedAdam, FusedAdamW, M2FCrossEntropyLoss  # noqa: E402
 
 try:
     from tqdm import tqdm
@@ -83,6 +83,93 @@ def clip_grad_norm(cfg, world: int = 1):
         raise ValueError("runtime.clip_grad_norm does not combine with runtime.grad_overlap: True "
                          "(the global norm needs every bucket's reduced gradients before the first update)")
     return float(v)
+
+
+def _under(name: str, prefix: str) -> bool:
+    return name == prefix or name.startswith(prefix + ".")
+
+
+def optimizer_groups(cfg, named_shapes):
+    """`runtime.optimizer` = {name: adam | adamw, no_decay_1d: bool, lr_scale: {state_dict prefix: multiplier of solver.lr},
+    frozen: [state_dict prefixes]} cut into parameter groups, on the host, from the model's (name, shape) list - checked before the
+    GPU is touched.  -> None when the block is absent or holds its defaults (the single coupled group of the reference, src/train.py:56),
+    else (name, groups, frozen names): groups = [{"names", "lr", "weight_decay"}] in order of first appearance, one per
+    (lr multiplier, decays or not) that occurs.  adamw = decoupled weight decay (torch.optim.AdamW); no_decay_1d: weight_decay 0 for every
+    1-D parameter (biases, LayerNorm); frozen parameters are handed to no group (their gradients are still computed)."""
+    block = _runtime(cfg, "optimizer", None)
+    if not block:
+        return None
+    unknown = sorted(set(block) - {"name", "no_decay_1d", "lr_scale", "frozen"})
+    if unknown:
+        raise ValueError(f"runtime.optimizer: unknown key(s) {unknown} (name, no_decay_1d, lr_scale, frozen)")
+    name = block.get("name", "adam")
+    if name not in ("adam", "adamw"):
+        raise ValueError(f"runtime.optimizer.name must be adam or adamw (got {name!r})")
+    no_decay_1d = block.get("no_decay_1d", False)
+    if not isinstance(no_decay_1d, bool):
+        raise ValueError(f"runtime.optimizer.no_decay_1d must be true or false (got {no_decay_1d!r})")
+    lr_scale = dict(block.get("lr_scale", None) or {})
+    frozen = list(block.get("frozen", None) or [])
+    for k, v in lr_scale.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0 or v == float("inf"):
+            raise ValueError(f"runtime.optimizer.lr_scale[{k!r}] must be a positive finite number (got {v!r})")
+    if name == "adam" and not no_decay_1d and not lr_scale and not frozen:
+        return None
+    names = [n for n, _ in named_shapes]
+    prefixes = [str(k) for k in lr_scale] + [str(k) for k in frozen]
+    for pre in prefixes:
+        if not any(_under(n, pre) for n in names):
+            raise ValueError(f"runtime.optimizer: prefix {pre!r} matches no parameter of the model")
+    for n in names:
+        hit = [pre for pre in prefixes if _under(n, pre)]
+        if len(hit) > 1:
+            raise ValueError(f"runtime.optimizer: prefixes {hit} overlap (both match {n!r})")
+    solver = cfg["solver"] if isinstance(cfg, dict) else cfg.solver
+    lr0 = float(solver["lr"] if isinstance(solver, dict) else solver.lr)
+    wd0 = float(solver["weight_decay"] if isinstance(solver, dict) else solver.weight_decay)
+    groups, at, frozen_names = [], {}, []
+    for n, shape in named_shapes:
+        if any(_under(n, pre) for pre in frozen):
+            frozen_names.append(n)
+            continue
+        scale = next((float(v) for k, v in lr_scale.items() if _under(n, str(k))), 1.0)
+        decays = not (no_decay_1d and len(shape) == 1)
+        if (scale, decays) not in at:
+            at[(scale, decays)] = len(groups)
+            groups.append({"names": [], "lr": lr0 * scale, "weight_decay": wd0 if decays else 0.0})
+        groups[at[(scale, decays)]]["names"].append(n)
+    if not groups:
+        raise ValueError("runtime.optimizer.frozen leaves no parameter to train")
+    if len(groups) > MAX_GROUPS:
+        raise ValueError(f"runtime.optimizer cuts {len(groups)} parameter groups; the optimizer takes at most {MAX_GROUPS}")
+    return name, groups, frozen_names
+
+
+def model_named_shapes(model_cfg):
+    """(state_dict name, shape) of every parameter of M2FNet(model_cfg), without building it."""
+    from mer_amd.layout import M2FConfig, param_specs
+    return [(sp.name, sp.shape) for sp in param_specs(M2FConfig.from_model_config(model_cfg))[0]]
+
+
+def build_optimizer(config, model):
+    """torch.optim.Adam(model.parameters(), lr, weight_decay) of the reference (src/train.py:56), or what `runtime.optimizer` asks for."""
+    cut = optimizer_groups(config, [(n, tuple(p.shape)) for n, p in model.named_parameters(remove_duplicate=False)])
+    if cut is None:
+        return FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
+    name, groups, _ = cut
+    named = dict(model.named_parameters(remove_duplicate=False))
+    params, seen = [], {}
+    for gi, g in enumerate(groups):
+        ps = []
+        for n in g["names"]:
+            p = named[n]
+            if seen.setdefault(id(p), gi) != gi:          # (the final LayerNorm the encoders of a modality share has several names)
+                raise ValueError(f"runtime.optimizer: {n!r} shares its tensor with a parameter of another group")
+            if not any(p is q for q in ps):
+                ps.append(p)
+        params.append({"params": ps, "lr": g["lr"], "weight_decay": g["weight_decay"]})
+    cls = FusedAdamW if name == "adamw" else FusedAdam
+    return cls(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay, params=params)
 
 
 def group_batches(batches, k: int):
@@ -210,6 +297,7 @@ def main(config=None):
     want_dp = _runtime(config, "data_parallel", "auto")
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
+    optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # W independent trainings on one device, all writing the same checkpoint, is never what a launcher was asked for
         raise RuntimeError(f"runtime.data_parallel is {want_dp!r} but this process was launched as one of "
@@ -280,7 +368,7 @@ def main(config=None):
         object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
                                                                              n_head=config.model.AUDIO.n_head))
     criterion = build_criterion(config.solver, train_set, device)
-    optimizer = FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
+    optimizer = build_optimizer(config, model)
     optimizer.max_grad_norm = clip_grad_norm(config, world)
     if world > 1:
         model.dp_step = dp.DataParallelStep(model, optimizer, n_buckets=int(_runtime(config, "grad_buckets", 4)),
