@@ -421,6 +421,39 @@ int m2f_adam_hyper_groups(float* hyper_table, const m2f_adam_group* groups, int 
 int m2f_adam_step_grouped(const m2f_config* cfg, float* params, const void* grads, int grads_bf16, float* exp_avg, float* exp_avg_sq,
                           uint16_t* param_shadow, const int* tensor_group, int n_tensors, const float* hyper_table, int64_t first,
                           int64_t end, const float* grad_scale_ptr, m2f_stream_t stream);
+/* Exponential moving average (EMA) of the weights inside the optimizer kernels (optim.FusedAdam(ema_decay=...)).  Replaces
+ * torch.optim.swa_utils.AveragedModel.update_parameters with multi_avg_fn = get_ema_multi_avg_fn(decay) called after optimizer.step():
+ * the kernel that has the updated parameter in registers also reads, updates and writes its average - 8 B per parameter on top of the
+ * update's own traffic instead of a second pass of 12 B, and one launch fewer.  No counterpart in the reference, whose loop scores the
+ * live weights.  `ema`: fp32, indexed and 16-byte aligned like `params`; ema_w = (float)(1 - decay) with 1 - decay formed in double, in
+ * [0, 1], ONE value for every launch of a step and every group:
+ *   e <- (ema_w == 1) ? p_new : fma(ema_w, p_new - e, e)
+ * ema_w == 1 is the first update, torch's n_averaged == 0 copy: the average takes the parameter's bits whatever the buffer held.
+ * Parameters, moments and shadows get the bits of the entry point without the suffix; every form gives the average the same bits.
+ *
+ * m2f_adam_step_ema / m2f_adam_step_g16_ema: m2f_adam_step / m2f_adam_step_g16 with the average over the same n elements (pads between
+ * tensors included: a zero parameter pad keeps a zero average).
+ * m2f_adam_step_shadowed_range_ema: m2f_adam_step_shadowed_range with the average of the tensors of [first, end).
+ * m2f_adam_step_grouped_ema: m2f_adam_step_grouped with the average of the OWNED tensors of [first, end); the EMA slice of a tensor
+ * no group owns is neither read nor written. */
+int m2f_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int step, float ema_w, const float* grad_scale_ptr, m2f_stream_t stream);
+int m2f_adam_step_g16_ema(float* params, const uint16_t* grads_bf16, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int step, float ema_w, const float* grad_scale_ptr,
+                          m2f_stream_t stream);
+int m2f_adam_step_shadowed_range_ema(const m2f_config* cfg, float* params, const void* grads, int grads_bf16, float* exp_avg,
+                                     float* exp_avg_sq, uint16_t* param_shadow, float* ema, float ema_w, int64_t first, int64_t end,
+                                     float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                     const float* grad_scale_ptr, m2f_stream_t stream);
+int m2f_adam_step_grouped_ema(const m2f_config* cfg, float* params, const void* grads, int grads_bf16, float* exp_avg, float* exp_avg_sq,
+                              uint16_t* param_shadow, float* ema, float ema_w, const int* tensor_group, int n_tensors,
+                              const float* hyper_table, int64_t first, int64_t end, const float* grad_scale_ptr, m2f_stream_t stream);
+/* m2f_ema_exchange: params[i] <-> ema[i] in place over every element of the tensors a group owns (tensor_group as in
+ * m2f_adam_step_grouped; all >= 0: every tensor) - evaluating with the averaged weights (what scoring AveragedModel.module instead of
+ * the model is in torch) without a copy through the host or a third buffer.  The alignment pads and the tensors of no group are not
+ * touched; a second call restores both buffers bit for bit.  The caller re-casts the bf16 parameter shadows afterwards. */
+int m2f_ema_exchange(const m2f_config* cfg, float* params, float* ema, const int* tensor_group, int n_tensors, m2f_stream_t stream);
+
 /* m2f_plan_fused_adam_setup for a grouped optimizer (torch.optim.AdamW(groups).step inside m2f_step): hyper_table = the rows of
  * m2f_adam_hyper_groups (refreshed BEFORE every step), tensor_group as above.  The weight-gradient launch updates a matrix with the row
  * of its group; the residual launch is the grouped shadow-writing kernel over the owned tensors the table does not cover.  Fails when a

@@ -25,7 +25,8 @@ gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
 # --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
 metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
-# registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each
+# registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
+# rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
 path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or metrics or adam) else sys.argv[1]
 rows, cur = [], None
@@ -45,9 +46,12 @@ for line in open(path, errors="replace"):
         if m:
             cur[m.group(1)] = int(m.group(2))
 if adam:
-    kernels = [r for r in rows if any(t in r["name"] for t in ("m2f_adam_shadow_grouped", "m2f_adam_slices", "m2f_adam_hyper_groups"))]
-    if len(kernels) < 5:
-        sys.exit(f"check_spills: expected the five grouped optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
+    kernels = [r for r in rows if any(t in r["name"] for t in ("m2f_adam_shadow_grouped", "m2f_adam_slices", "m2f_adam_hyper_groups", "m2f_adam_kernel",
+                                                                 "m2f_adam_shadow_kernel", "m2f_ema_exchange"))]
+    # grouped shadow-writing and slices: 2 gradient types x with / without the average; the hyper-table refresh; flat and single-group
+    # shadow-writing: 4 forms each; the exchange
+    if len(kernels) < 18:
+        sys.exit(f"check_spills: expected the eighteen optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

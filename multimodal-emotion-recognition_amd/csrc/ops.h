@@ -340,9 +340,11 @@ hipError_t m2f_launch_rng_advance(uint32_t* rng, hipStream_t stream);
 // grad_scale_ptr (device, may be null): gradients are multiplied by 1 / *grad_scale_ptr first (the
 // global valid-utterance denominator under data parallelism).
 // g_is_bf16: g points at bf16 gradients (data-parallel bf16 exchange) instead of fp32.
+// ema (device, may be null; here and in the three forms below): the exponential moving average of the parameters, same indexing as p -
+// after the update e <- (ema_w == 1) ? p : fma(ema_w, p - e, e), ema_w = (float)(1 - decay); null: the kernel without the stream.
 hipError_t m2f_launch_adam(float* p, const void* g, int g_is_bf16, float* m, float* v, int64_t n, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                           hipStream_t stream);
+                           float* ema, float ema_w, hipStream_t stream);
 
 // Fused Adam + parameter-shadow refresh (bf16 mode, single process): the same update as m2f_launch_adam, walked matrix by matrix
 // in 64x64 tiles so that the kernel that has the new fp32 parameter in registers also writes its bf16 shadows - W [rows][pad8(cols)]
@@ -355,7 +357,7 @@ struct AdamItem { long long off, soff, soff_t; int rows, cols, tile_begin, tiles
 hipError_t m2f_launch_adam_shadowed(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
                                     const int* tile_begin, int n_items, int tile_first, int total_tiles, float lr, float beta1,
                                     float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                                    hipStream_t stream);
+                                    float* ema, float ema_w, hipStream_t stream);
 
 hipError_t m2f_launch_cast_items(const float* src, uint16_t* dst, const AdamItem* items, const int* tile_begin, int n_items, int total_tiles, hipStream_t stream);
 hipError_t m2f_launch_adam_hyper(float* hyper_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int step, hipStream_t stream);
@@ -372,9 +374,12 @@ struct AdamSlice { long long off; int n; int group; };
 hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host, int n_groups, hipStream_t stream);
 hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
                                             const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
-                                            const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream);
+                                            const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w,
+                                            hipStream_t stream);
 hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
-                                  const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream);
+                                  const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w, hipStream_t stream);
+// p[i] <-> ema[i] over the slices [s0, s1) (whole owned tensors; pads and unowned tensors are in no slice)
+hipError_t m2f_launch_ema_exchange(float* p, float* ema, const AdamSlice* slices, int s0, int s1, hipStream_t stream);
 
 // Global gradient norm + clip record (gradnorm.hip).  A slice = at most M2F_GRADNORM_SLICE consecutive elements of ONE parameter tensor
 // (`off`: its first element in the flat buffer; only the last slice of a tensor is short), cut by the host from the parameter map, so

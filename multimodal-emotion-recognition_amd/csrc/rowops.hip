@@ -452,11 +452,24 @@ __device__ __forceinline__ void adamw4(f32x4& pp, const f32x4& gg, f32x4& mm, f3
     adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
 }
 
+// Exponential moving average of the weights (optim.FusedAdam(ema_decay=...); torch.optim.swa_utils.AveragedModel.update_parameters with
+// get_ema_multi_avg_fn(decay): e.lerp_(p, 1 - decay)) of four consecutive elements, applied to the parameter adam4 / adamw4 has just
+// produced.  w = (float)(1 - decay_t), formed in double on the host, the same for every launch of one step.  Written once, with its
+// contraction spelled out, for adam4's reason: every form of the update must give the average the same bits.  w == 1 is the first
+// update (torch's n_averaged == 0 copy): the average becomes the parameter's bits, whatever the buffer held.
+__device__ __forceinline__ void ema4(f32x4& ee, const f32x4& pp, float w) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ee[e] = (w == 1.0f) ? pp[e] : __builtin_fmaf(w, pp[e] - ee[e], ee[e]);
+}
+
 // G16: the gradient buffer holds bf16 (the data-parallel bf16 exchange), everything else stays fp32
-template <bool G16>
+// EMA: one more stream - the average `ema` of the parameters, read and written once per step like m and v and nontemporal like them
+// (8 B per parameter on top of 28); EMA == false is the kernel without it, `ema` / `ema_w` unread.
+template <bool G16, bool EMA>
 __global__ __launch_bounds__(256) void m2f_adam_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, int64_t n4, float lr_bc1, float beta1, float beta2,
-                                                       float eps, float wd, float inv_sqrt_bc2, const float* __restrict__ gs_ptr) {
+                                                       float eps, float wd, float inv_sqrt_bc2, const float* __restrict__ gs_ptr,
+                                                       float* __restrict__ ema, float ema_w) {
     // g, m, v are streamed once per step: nontemporal accesses keep them from displacing p (re-read by the bf16 cast that
     // opens the next forward) in the L2 / Infinity Cache; measured 0.554 -> 0.524 ms per C3 step for the optimizer part
     const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
@@ -476,6 +489,11 @@ __global__ __launch_bounds__(256) void m2f_adam_kernel(float* __restrict__ p, co
         reinterpret_cast<f32x4*>(p)[i] = pp;
         __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m) + i);
         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
+        if constexpr (EMA) {
+            f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(ema) + i);
+            ema4(ee, pp, ema_w);
+            __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema) + i);
+        }
     }
 }
 
@@ -501,14 +519,16 @@ __device__ __forceinline__ float adam_grad1(const void* g, long long o) {
 // GROUPED: items[] holds the tensors some parameter group owns, item_group[] (parallel to items[]) their group, and the six factors
 // plus `decay` come from row item_group[i] of the hyper table `hyt` instead of the arguments - the item is the same in every lane of
 // the workgroup, so the row arrives by scalar loads and costs no vector register.
-template <bool G16, bool GROUPED = false>
+// EMA: the average stream of ema4 (see m2f_adam_kernel) over exactly the elements whose parameter the tile writes.
+template <bool G16, bool GROUPED = false, bool EMA = false>
 __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, uint16_t* __restrict__ sh,
                                                  const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
                                                  int n_items, int tile_first, int total_tiles, float lr_bc1, float beta1,
                                                  float beta2, float eps, float wd, float inv_sqrt_bc2,
                                                  const float* __restrict__ gs_ptr, const float* __restrict__ hyt = nullptr,
-                                                 const int* __restrict__ item_group = nullptr) {
+                                                 const int* __restrict__ item_group = nullptr, float* __restrict__ ema = nullptr,
+                                                 float ema_w = 0.f) {
     __shared__ float tile[64][65];
     __shared__ int tb[M2F_ADAM_MAX_ITEMS + 1];
     const int tid = threadIdx.x;
@@ -546,6 +566,11 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
                     *reinterpret_cast<f32x4*>(p + o) = pp;
                     __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
                     __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
+                    if constexpr (EMA) {
+                        f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
+                        ema4(ee, pp, ema_w);
+                        __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
+                    }
                 }
             }
             continue;
@@ -591,10 +616,23 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
                     w.x = (uint32_t)m2f_bf16_bits(pp[i][0]) | ((uint32_t)m2f_bf16_bits(pp[i][1]) << 16);
                     w.y = (uint32_t)m2f_bf16_bits(pp[i][2]) | ((uint32_t)m2f_bf16_bits(pp[i][3]) << 16);
                     *reinterpret_cast<uint2*>(q) = w;
+                    if constexpr (EMA) {
+                        f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
+                        ema4(ee, pp[i], ema_w);
+                        __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
+                    }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if (gc + e < cols) { p[o + e] = pp[i][e]; m[o + e] = mm[i][e]; v[o + e] = vv[i][e]; q[e] = m2f_bf16_bits(pp[i][e]); }
+                    if constexpr (EMA) {
+                        f32x4 ee = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) if (gc + e < cols) ee[e] = ema[o + e];
+                        ema4(ee, pp[i], ema_w);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) if (gc + e < cols) ema[o + e] = ee[e];
+                    }
                 }
             }
         }
@@ -620,14 +658,15 @@ __device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const vo
     }
 }
 
-template <bool G16>
+template <bool G16, bool EMA>
 __global__ __launch_bounds__(256) void m2f_adam_shadow_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, uint16_t* __restrict__ sh,
                                                               const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
                                                               int n_items, int tile_first, int total_tiles, float lr_bc1, float beta1,
                                                               float beta2, float eps, float wd, float inv_sqrt_bc2,
-                                                              const float* __restrict__ gs_ptr) {
-    adam_shadow_body<G16>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, gs_ptr);
+                                                              const float* __restrict__ gs_ptr, float* __restrict__ ema, float ema_w) {
+    adam_shadow_body<G16, false, EMA>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, lr_bc1, beta1, beta2, eps, wd,
+                                      inv_sqrt_bc2, gs_ptr, nullptr, nullptr, ema, ema_w);
 }
 // the same update with the step-dependent factors read from device memory (m2f_launch_adam_hyper): a node of the captured step graph
 __global__ __launch_bounds__(256) void m2f_adam_shadow_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -641,25 +680,26 @@ __global__ __launch_bounds__(256) void m2f_adam_shadow_dev_kernel(float* __restr
 // Parameter groups (optim.FusedAdam(params=[...]), FusedAdamW): the shadow-writing update over the tensors of items[] with the hyper
 // row of each item's group.  The rows live in device memory (refreshed once per step by m2f_adam_hyper_groups_kernel), so this ONE
 // form serves the eager step, the [first, end) ranges of the data-parallel path and a captured graph.
-template <bool G16>
+template <bool G16, bool EMA>
 __global__ __launch_bounds__(256) void m2f_adam_shadow_grouped_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                                       float* __restrict__ v, uint16_t* __restrict__ sh,
                                                                       const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
                                                                       const int* __restrict__ item_group, int n_items, int tile_first,
                                                                       int total_tiles, const float* __restrict__ hyt,
-                                                                      const float* __restrict__ gs_ptr) {
-    adam_shadow_body<G16, true>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gs_ptr, hyt,
-                                item_group);
+                                                                      const float* __restrict__ gs_ptr, float* __restrict__ ema, float ema_w) {
+    adam_shadow_body<G16, true, EMA>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gs_ptr,
+                                     hyt, item_group, ema, ema_w);
 }
 
 // fp32 mode (no shadows to write): the flat kernel runs over pads and tensors alike and cannot know a group, so the grouped form
 // walks SLICES - at most M2F_ADAM_SLICE consecutive elements of one owned tensor (ops.h AdamSlice; cut by the host from the parameter
 // map as the gradient norm's are: pads belong to no slice) - each with its group's hyper row.  16-byte accesses, g / m / v nontemporal
 // as in m2f_adam_kernel; the last 1-3 elements of a tensor whose size is no multiple of 4 go one by one, nothing behind them is touched.
-template <bool G16>
+template <bool G16, bool EMA>
 __global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, const AdamSlice* __restrict__ slices, int s0, int s1,
-                                                              const float* __restrict__ hyt, const float* __restrict__ gs_ptr) {
+                                                              const float* __restrict__ hyt, const float* __restrict__ gs_ptr,
+                                                              float* __restrict__ ema, float ema_w) {
     const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
     const int tid = threadIdx.x;
     for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
@@ -679,6 +719,11 @@ __global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict_
                 *reinterpret_cast<f32x4*>(p + o) = pp;
                 __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
                 __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
+                if constexpr (EMA) {
+                    f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
+                    ema4(ee, pp, ema_w);
+                    __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
+                }
             } else if (e < sl.n) {
                 f32x4 pp = {0.f, 0.f, 0.f, 0.f}, gg = pp, mm = pp, vv = pp;
 #pragma unroll
@@ -688,6 +733,39 @@ __global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict_
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
                     if (e + k < sl.n) { p[o + k] = pp[k]; m[o + k] = mm[k]; v[o + k] = vv[k]; }
+                if constexpr (EMA) {
+                    f32x4 ee = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) if (e + k < sl.n) ee[k] = ema[o + k];
+                    ema4(ee, pp, ema_w);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) if (e + k < sl.n) ema[o + k] = ee[k];
+                }
+            }
+        }
+    }
+}
+
+// optim.FusedAdam.averaged_parameters(): params[i] <-> ema[i] in place over the slices [s0, s1) of whole owned tensors (the list the
+// flat grouped kernel walks: pads and the tensors of no group belong to no slice and are not touched).  16-byte accesses; the last
+// 1-3 elements of a tensor whose size is no multiple of 4 go one by one.  Run twice, it restores both buffers bit for bit.
+__global__ __launch_bounds__(256) void m2f_ema_exchange_kernel(float* __restrict__ p, float* __restrict__ ema,
+                                                               const AdamSlice* __restrict__ slices, int s0, int s1) {
+    const int tid = threadIdx.x;
+    for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
+        const AdamSlice sl = slices[s];
+#pragma unroll 2
+        for (int j = 0; j < M2F_ADAM_SLICE / 1024; ++j) {
+            const int e = (j * 256 + tid) * 4;
+            const long long o = sl.off + e;
+            if (e + 4 <= sl.n) {
+                const f32x4 pp = *reinterpret_cast<const f32x4*>(p + o);
+                const f32x4 ee = *reinterpret_cast<const f32x4*>(ema + o);
+                *reinterpret_cast<f32x4*>(p + o) = ee;
+                *reinterpret_cast<f32x4*>(ema + o) = pp;
+            } else if (e < sl.n) {
+                for (int k = 0; k < 3; ++k)
+                    if (e + k < sl.n) { const float a = p[o + k]; p[o + k] = ema[o + k]; ema[o + k] = a; }
             }
         }
     }
@@ -984,17 +1062,18 @@ hipError_t m2f_launch_rng_advance(uint32_t* rng, hipStream_t stream) {
 hipError_t m2f_launch_adam_shadowed(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
                                     const int* tile_begin, int n_items, int tile_first, int total_tiles, float lr, float beta1,
                                     float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                                    hipStream_t stream) {
+                                    float* ema, float ema_w, hipStream_t stream) {
     const int n_tiles = total_tiles - tile_first;
     if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || tile_first < 0 || n_tiles < 1 || !items || !tile_begin || !shadow) return hipErrorInvalidValue;
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     const int blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
-    if (g_is_bf16)
-        hipLaunchKernelGGL(m2f_adam_shadow_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, n_items,
-                           tile_first, total_tiles, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr);
-    else
-        hipLaunchKernelGGL(m2f_adam_shadow_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, n_items,
-                           tile_first, total_tiles, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, n_items, tile_first,
+                           total_tiles, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr, ema, ema_w);
+    };
+    if (ema) { if (g_is_bf16) go(m2f_adam_shadow_kernel<true, true>); else go(m2f_adam_shadow_kernel<false, true>); }
+    else if (g_is_bf16) go(m2f_adam_shadow_kernel<true, false>);
+    else go(m2f_adam_shadow_kernel<false, false>);
     return hipGetLastError();
 }
 
@@ -1055,18 +1134,19 @@ hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, floa
 
 hipError_t m2f_launch_adam(float* p, const void* g, int g_is_bf16, float* m, float* v, int64_t n, float lr, float beta1,
                            float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                           hipStream_t stream) {
+                           float* ema, float ema_w, hipStream_t stream) {
     if (n & 3) return hipErrorInvalidValue;      // flat buffers are padded to 64 floats per tensor
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     const int64_t n4 = n >> 2;
     int blocks = (int)((n4 + 255) / 256);
     if (blocks > 256 * 8) blocks = 256 * 8;
-    if (g_is_bf16)
-        hipLaunchKernelGGL(m2f_adam_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, (float)(lr / bc1), beta1, beta2,
-                           eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr);
-    else
-        hipLaunchKernelGGL(m2f_adam_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, (float)(lr / bc1), beta1, beta2,
-                           eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, (float)(lr / bc1), beta1, beta2, eps, weight_decay,
+                           (float)(1.0 / sqrt(bc2)), grad_scale_ptr, ema, ema_w);
+    };
+    if (ema) { if (g_is_bf16) go(m2f_adam_kernel<true, true>); else go(m2f_adam_kernel<false, true>); }
+    else if (g_is_bf16) go(m2f_adam_kernel<true, false>);
+    else go(m2f_adam_kernel<false, false>);
     return hipGetLastError();
 }
 
@@ -1080,28 +1160,39 @@ hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host
 
 hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
                                             const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
-                                            const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream) {
+                                            const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w,
+                                            hipStream_t stream) {
     const int n_tiles = total_tiles - tile_first;
     if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || tile_first < 0 || n_tiles < 1 || !items || !tile_begin || !item_group || !shadow || !hyper_table)
         return hipErrorInvalidValue;
     const int blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
-    if (g_is_bf16)
-        hipLaunchKernelGGL(m2f_adam_shadow_grouped_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin,
-                           item_group, n_items, tile_first, total_tiles, hyper_table, grad_scale_ptr);
-    else
-        hipLaunchKernelGGL(m2f_adam_shadow_grouped_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin,
-                           item_group, n_items, tile_first, total_tiles, hyper_table, grad_scale_ptr);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, item_group, n_items, tile_first,
+                           total_tiles, hyper_table, grad_scale_ptr, ema, ema_w);
+    };
+    if (ema) { if (g_is_bf16) go(m2f_adam_shadow_grouped_kernel<true, true>); else go(m2f_adam_shadow_grouped_kernel<false, true>); }
+    else if (g_is_bf16) go(m2f_adam_shadow_grouped_kernel<true, false>);
+    else go(m2f_adam_shadow_grouped_kernel<false, false>);
     return hipGetLastError();
 }
 
 hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
-                                  const float* hyper_table, const float* grad_scale_ptr, hipStream_t stream) {
+                                  const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w, hipStream_t stream) {
     if (!p || !g || !m || !v || !slices || !hyper_table || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
     if (s1 == s0) return hipSuccess;
     const int blocks = s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8;
-    if (g_is_bf16)
-        hipLaunchKernelGGL(m2f_adam_slices_kernel<true>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr);
-    else
-        hipLaunchKernelGGL(m2f_adam_slices_kernel<false>, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr, ema, ema_w);
+    };
+    if (ema) { if (g_is_bf16) go(m2f_adam_slices_kernel<true, true>); else go(m2f_adam_slices_kernel<false, true>); }
+    else if (g_is_bf16) go(m2f_adam_slices_kernel<true, false>);
+    else go(m2f_adam_slices_kernel<false, false>);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_ema_exchange(float* p, float* ema, const AdamSlice* slices, int s0, int s1, hipStream_t stream) {
+    if (!p || !ema || !slices || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
+    if (s1 == s0) return hipSuccess;
+    hipLaunchKernelGGL(m2f_ema_exchange_kernel, dim3(s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8), dim3(256), 0, stream, p, ema, slices, s0, s1);
     return hipGetLastError();
 }

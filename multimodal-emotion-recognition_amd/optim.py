@@ -11,6 +11,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Optional
 
@@ -24,6 +25,20 @@ from .layout import param_specs
 # what torch.optim.Adam / AdamW accept and this optimizer does not: refused by name when set, never ignored
 _TORCH_ONLY = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused")
 MAX_GROUPS = runtime.ADAM_MAX_GROUPS
+
+
+def check_ema_decay(decay) -> Optional[float]:
+    """``ema_decay``: None, or a number in [0, 1] (-> float); anything else is a ValueError."""
+    if decay is None:
+        return None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:
+        raise ValueError(f"FusedAdam.ema_decay must be None or a number in [0, 1] (got {decay!r})")
+    return float(decay)
+
+
+def ema_decay_at(decay: float, n: int, warmup: bool = False) -> float:
+    """The decay of update `n` (from 0): ``decay``, with warm-up ``min(decay, (1 + n) / (10 + n))``."""
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
 
 
 class _CEFunction(torch.autograd.Function):
@@ -88,16 +103,37 @@ class FusedAdam(torch.optim.Optimizer):
     (after the division by ``grad_scale``: the mean gradient of an accumulation group or of the global batch), which a norm over
     ``.grad`` is not in those modes; ``grad_norm()`` / ``clip_coef()`` are device tensors, nothing on the step path waits for the
     host.  A non-finite norm gives a non-finite divisor and non-finite parameters, as torch's default ``error_if_nonfinite=False``
-    does.  None (the default): the step as it was, launch for launch."""
+    does.  None (the default): the step as it was, launch for launch.
+
+    ``ema_decay`` (keyword-only constructor argument and plain attribute; a number in [0, 1] or None; may be changed between steps,
+    None stops updating and keeps the buffer) with ``ema_warmup``: an exponential moving average of the weights,
+    ``torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay)).update_parameters(model)`` after every
+    ``step()``, kept by the optimizer kernels themselves - the kernel that has the new parameter in registers reads, updates and
+    writes its average (one fp32 buffer the size of the flat parameter buffer, zeroed at the first averaging step; 8 B of traffic per
+    parameter).  ONE update per optimizer step however many micro-batches fed it and however many launches make it up (``step()``,
+    ``step_ranges()``, the grouped forms, bf16 gradients: the same bits from all of them); update ``n`` (from 0) uses ``decay``, with
+    ``ema_warmup`` ``min(decay, (1 + n) / (10 + n))``; update 0 copies the parameters.  Parameters, moments and shadows are what they
+    are without it, bit for bit.  Differences from ``AveragedModel``: no second module - ``with optimizer.averaged_parameters():``
+    swaps the average INTO the model (one launch in, one out) for validation, a checkpoint or ``test.py``; a tensor in no parameter
+    group is not averaged (its EMA slice is never touched, ``ema_state_dict`` reports its live value); buffers are not averaged
+    (M2FNet has none); the average is not part of ``state_dict()`` (torch's format) but of ``ema_state_dict()``.  Refused
+    combination: the optimizer inside the weight-gradient launch has no EMA stream - ``prepare_fused`` returns False, as with
+    ``max_grad_norm``.  None (the default): the step as it was, launch for launch."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: Optional[float] = None, *, params=None, decoupled_weight_decay: bool = False, **torch_options):
+                 max_grad_norm: Optional[float] = None, *, params=None, decoupled_weight_decay: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, **torch_options):
         for k, v in torch_options.items():
             if k not in _TORCH_ONLY:
                 raise TypeError(f"FusedAdam.__init__() got an unexpected keyword argument {k!r}")
             if v:
                 raise ValueError(f"FusedAdam does not implement {k}={v!r} (torch.optim.Adam's option; only {k}=False / None is accepted)")
         self.model = model
+        self.ema_decay = check_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema: Optional[torch.Tensor] = None           # fp32, the layout of engine.flat; allocated at the first averaging step
+        self._n_averaged = 0
+        self._averaged_in = False                          # inside averaged_parameters(): model <-> average exchanged
         # grouped: anything but ONE coupled group over model.parameters() - the hyper table and the grouped kernels instead of
         # the single-group entries
         self._grouped = params is not None or bool(decoupled_weight_decay)
@@ -126,7 +162,10 @@ class FusedAdam(torch.optim.Optimizer):
     def add_param_group(self, param_group):
         """torch's ``add_param_group`` with this optimizer's rules: the parameters are ``model``'s, at most 16 groups, no option this
         optimizer does not implement.  Works before and between steps; the new group's step count starts at 0.  A second group turns
-        the single coupled group into a grouped optimizer (its count carries over)."""
+        the single coupled group into a grouped optimizer (its count carries over).  With a weight average under way (``n_averaged``
+        > 0) the EMA slices of the new group's tensors are seeded with their parameters - the copy a first update makes - so their
+        average starts from the weights, not from the zeros of a slice that was never written."""
+        self._refuse_averaged("add_param_group()")
         if not isinstance(param_group, dict):
             raise TypeError(f"param_group must be a dict (got {type(param_group).__name__})")
         ps = param_group["params"]
@@ -148,6 +187,13 @@ class FusedAdam(torch.optim.Optimizer):
         super().add_param_group({**param_group, "params": ps})
         self._gsteps.append(0)
         self._tg_key = None
+        if self._ema is not None and self._n_averaged > 0 and self._engine is not None:
+            at = {id(p): (o, n) for (p, o, n, _) in self._engine.items}
+            with torch.no_grad():
+                for p in ps:
+                    if id(p) in at:
+                        o, n = at[id(p)]
+                        self._ema[o: o + n].copy_(self._engine.flat[o: o + n])
 
     def _unique_params(self):
         """The model's parameter tensors in parameter-map order (layout.param_specs == plan.hip::build_param_map; the engine's items)."""
@@ -198,7 +244,118 @@ class FusedAdam(torch.optim.Optimizer):
                     mv.copy_(st["exp_avg"])
                     vv.copy_(st["exp_avg_sq"])
                     self.state[p] = {"step": st["step"], "exp_avg": mv, "exp_avg_sq": vv}
+            if self._ema is not None:                      # (the flat layout is the configuration's: the same on the new engine)
+                self._ema = self._ema.to(eng.flat.device) if self._ema.numel() == eng.flat.numel() else None
         return eng
+
+    # ---- exponential moving average of the weights --------------------------------------------------------------------------------
+    def _refuse_averaged(self, what: str) -> None:
+        if self._averaged_in:
+            raise RuntimeError(f"FusedAdam.{what} inside averaged_parameters(): the model holds the averaged weights; leave the context first")
+
+    def _ema_begin(self, eng):
+        """-> (average buffer, 1 - decay_t) of the optimizer step that begins, or (None, 0.0) without ``ema_decay``."""
+        decay = check_ema_decay(self.ema_decay)
+        if decay is None:
+            return None, 0.0
+        if self._ema is None or self._ema.device != eng.flat.device:
+            self._ema = torch.zeros_like(eng.flat)
+        w = 1.0 if self._n_averaged == 0 else 1.0 - ema_decay_at(decay, self._n_averaged, self.ema_warmup)
+        return self._ema, w
+
+    @property
+    def n_averaged(self) -> int:
+        """EMA updates so far (one per optimizer step taken with ``ema_decay`` set)."""
+        return self._n_averaged
+
+    def ema_parameters(self) -> torch.Tensor:
+        """The average: flat fp32 device tensor, indexed like ``model.flat_parameters()`` (pads zero, the slices of tensors in no
+        group untouched).  The optimizer's own buffer, not a copy."""
+        self._refuse_averaged("ema_parameters()")
+        if self._ema is None:
+            raise RuntimeError("FusedAdam.ema_parameters: no EMA step has run yet (ema_decay is None, or step() has not been called)")
+        return self._ema
+
+    def _owned_ids(self):
+        return {id(p) for g in self.param_groups for p in g["params"]}
+
+    def ema_state_dict(self):
+        """``{"decay", "warmup", "n_averaged", "parameters": {name: tensor}}``; ``parameters`` has the names and shapes of
+        ``model.state_dict()`` and loads into the reference's ``M2FNet``.  A tensor in no parameter group is not averaged: its entry is
+        its live value."""
+        if self._ema is None:
+            raise RuntimeError("FusedAdam.ema_state_dict: no EMA step has run yet (ema_decay is None, or step() has not been called)")
+        eng = self._bind()
+        at = {id(p): (o, n, s) for (p, o, n, s) in eng.items}
+        named = dict(self.model.named_parameters(remove_duplicate=False))
+        owned = self._owned_ids()
+        src = eng.flat if self._averaged_in else self._ema            # (inside the context the model's buffer holds the average)
+        out = {}
+        for name, t in self.model.state_dict().items():
+            p = named.get(name)
+            if p is not None and id(p) in owned and id(p) in at:
+                o, n, s = at[id(p)]
+                out[name] = src[o: o + n].view(s).clone()
+            else:
+                out[name] = t.detach().clone()
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "n_averaged": self._n_averaged, "parameters": out}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, d) -> None:
+        """Restores ``ema_state_dict()``'s value: strict about the names and shapes of ``parameters`` (those of ``model.state_dict()``).
+        ``decay`` / ``warmup`` / ``n_averaged`` are taken over, so the warm-up continues where it was.  Entries of tensors in no group
+        are checked and otherwise ignored."""
+        self._refuse_averaged("load_ema_state_dict()")
+        missing = [k for k in ("decay", "warmup", "n_averaged", "parameters") if k not in d]
+        if missing:
+            raise KeyError(f"FusedAdam.load_ema_state_dict: missing key(s) {missing}")
+        want = self.model.state_dict()
+        got = d["parameters"]
+        if set(got) != set(want):
+            raise KeyError(f"FusedAdam.load_ema_state_dict: parameter names differ (missing {sorted(set(want) - set(got))[:4]}, "
+                           f"unexpected {sorted(set(got) - set(want))[:4]})")
+        for k, t in want.items():
+            if tuple(got[k].shape) != tuple(t.shape):
+                raise ValueError(f"FusedAdam.load_ema_state_dict: {k!r} has shape {tuple(got[k].shape)}, the model's is {tuple(t.shape)}")
+        decay = check_ema_decay(d["decay"])
+        n = int(d["n_averaged"])
+        if n < 0:
+            raise ValueError(f"FusedAdam.load_ema_state_dict: n_averaged = {n}")
+        eng = self._bind()
+        at = {id(p): (o, m, s) for (p, o, m, s) in eng.items}
+        named = dict(self.model.named_parameters(remove_duplicate=False))
+        owned = self._owned_ids()
+        ema = torch.zeros_like(eng.flat)
+        for name, t in got.items():
+            p = named.get(name)
+            if p is not None and id(p) in owned and id(p) in at:
+                o, m, s = at[id(p)]
+                ema[o: o + m].view(s).copy_(t)
+        self._ema, self._n_averaged = ema, n
+        self.ema_decay, self.ema_warmup = decay, bool(d["warmup"])
+
+    def _exchange(self, eng) -> None:
+        self.tensor_group_map()
+        runtime.ema_exchange(eng.cfg, eng.flat, self._ema, self._tg)
+        eng.invalidate_shadows()                           # (written behind torch's version counters: the next forward re-casts)
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """``with optimizer.averaged_parameters():`` - the model's parameters ARE the averaged weights inside: one exchange launch on
+        entry swaps every owned tensor with its average in place, the same launch on exit swaps them back, bit for bit.  Inside,
+        ``model.state_dict()``, ``forward``, ``eval_step`` and a checkpoint see the average (the bf16 shadows are re-cast by the next
+        forward, inside and again after); ``step()``, ``step_ranges()``, ``prepare_fused()`` and a nested entry raise."""
+        self._refuse_averaged("averaged_parameters()")
+        if self._ema is None or self._n_averaged == 0:
+            raise RuntimeError("FusedAdam.averaged_parameters: there is no average yet (no step has run with ema_decay set)")
+        eng = self._bind()
+        self._exchange(eng)
+        self._averaged_in = True
+        try:
+            yield self
+        finally:
+            self._exchange(eng)
+            self._averaged_in = False
 
     def _materialise_state(self, eng):
         for (p, o, n, s) in eng.items:
@@ -242,7 +399,9 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._refuse_averaged("step()")
         eng = self._bind()
+        ema, ema_w = self._ema_begin(eng)                    # one average update per optimizer step: every launch gets the same weight
         g = self.param_groups[0]
         flat_grad = eng.ensure_grad()
         # fast path: the engine published its flat-buffer views as .grad (checked on the two end parameters);
@@ -262,7 +421,9 @@ class FusedAdam(torch.optim.Optimizer):
             tg = self._refresh_table(eng)
             # the owned tensors with their group's row: shadow-writing kernel (bf16 mode) or slices (fp32 mode).  Tensors of no group are
             # not touched, so their shadows stay what they were: fresh before = fresh after (the version counters do not move)
-            runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale)
+            runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale,
+                                      ema=ema, ema_w=ema_w)
+            self._n_averaged += ema is not None
             if eng.wshadow is not None and self._owns_everything():
                 eng.mark_shadows_fresh()
             return loss
@@ -272,11 +433,12 @@ class FusedAdam(torch.optim.Optimizer):
             # bf16 mode: the update and the bf16 shadows (W, W^T) of every 2-D parameter in ONE pass - the forward then skips its
             # parameter casts (engine.shadows_fresh)
             runtime.adam_step_shadowed(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, self._step, g["lr"], g["betas"],
-                                       g["eps"], g["weight_decay"], scale)
+                                       g["eps"], g["weight_decay"], scale, ema=ema, ema_w=ema_w)
             eng.mark_shadows_fresh()
         else:
             runtime.adam_step(eng.flat, flat_grad, self._m, self._v, self._step, g["lr"], g["betas"], g["eps"],
-                              g["weight_decay"], scale)
+                              g["weight_decay"], scale, ema=ema, ema_w=ema_w)
+        self._n_averaged += ema is not None
         return loss
 
     @torch.no_grad()
@@ -287,8 +449,10 @@ class FusedAdam(torch.optim.Optimizer):
         parameter shadows (tests/test_fused_adam_gpu.py) - but the weight gradients of the table's matrices never reach memory:
         their ``.grad`` keeps whatever it held.  Returns False (and changes nothing) when the plan cannot; call ``finish_fused``
         after the step.  With ``max_grad_norm`` set it returns False: the in-launch optimizer updates elements before the global norm
-        can exist, so ``train_step(optimizer=...)`` takes its two-launch branch (the step, then ``step()``)."""
-        if self.max_grad_norm is not None:
+        can exist, so ``train_step(optimizer=...)`` takes its two-launch branch (the step, then ``step()``).  With ``ema_decay`` set it
+        returns False as well: the in-launch optimizer has no EMA stream (its epilogue is at its register budget)."""
+        self._refuse_averaged("prepare_fused()")
+        if self.max_grad_norm is not None or self.ema_decay is not None:
             return False
         eng = self._bind()
         if eng.wshadow is None or not plan.train or not getattr(plan, "shared_shadow", False):
@@ -359,13 +523,17 @@ class FusedAdam(torch.optim.Optimizer):
         With ``max_grad_norm`` set the global norm needs every range's gradients: `before_each` runs for ALL ranges first, then the
         norm launches over the whole buffer, then the ranges' updates with the clip record's divisor - the updates no longer hide
         under the exchange of the following buckets; that is the price of a global norm."""
+        self._refuse_averaged("step_ranges()")
         eng = self._bind()
         g = self.param_groups[0]
         flat_grad = eng.ensure_grad() if grads is None else grads
         n = eng.flat.numel()
         ranges = [(lo, min(hi, n)) for (lo, hi) in ranges]
+        ema, ema_w = self._ema_begin(eng)                    # the SAME weight for every range of this step
         if self._grouped:
-            return self._step_ranges_grouped(eng, flat_grad, ranges, before_each, n)
+            self._step_ranges_grouped(eng, flat_grad, ranges, before_each, n, ema, ema_w)
+            self._n_averaged += ema is not None
+            return
         self._step += 1
         scale = self.grad_scale
         if self.max_grad_norm is not None:
@@ -388,10 +556,11 @@ class FusedAdam(torch.optim.Optimizer):
                 continue
             if shadowed:
                 runtime.adam_step_shadowed(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, self._step, g["lr"], g["betas"],
-                                           g["eps"], g["weight_decay"], scale, first=lo, end=(-1 if hi >= n else hi))
+                                           g["eps"], g["weight_decay"], scale, first=lo, end=(-1 if hi >= n else hi), ema=ema, ema_w=ema_w)
             else:
                 runtime.adam_step(eng.flat[lo:hi], flat_grad[lo:hi], self._m[lo:hi], self._v[lo:hi], self._step, g["lr"],
-                                  g["betas"], g["eps"], g["weight_decay"], scale)
+                                  g["betas"], g["eps"], g["weight_decay"], scale, ema=None if ema is None else ema[lo:hi], ema_w=ema_w)
+        self._n_averaged += ema is not None
         if shadowed:
             covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
             whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
@@ -400,7 +569,7 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 eng.invalidate_shadows()
 
-    def _step_ranges_grouped(self, eng, flat_grad, ranges, before_each, n):
+    def _step_ranges_grouped(self, eng, flat_grad, ranges, before_each, n, ema=None, ema_w=0.0):
         starts = self._tensor_starts(eng)
         for lo, hi in ranges:
             if hi > lo and not (lo in starts and (hi >= n or hi in starts)):
@@ -420,7 +589,7 @@ class FusedAdam(torch.optim.Optimizer):
                 before_each(i)
             if hi > lo:
                 runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale,
-                                          first=lo, end=(-1 if hi >= n else hi))
+                                          first=lo, end=(-1 if hi >= n else hi), ema=ema, ema_w=ema_w)
         if eng.wshadow is not None:
             covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
             whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
@@ -477,6 +646,7 @@ class FusedAdamW(FusedAdam):
     ``FusedAdam`` with decoupled weight decay and AdamW's default ``weight_decay=1e-2``.  ``params`` as in ``FusedAdam``."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 max_grad_norm: Optional[float] = None, *, params=None, **torch_options):
+                 max_grad_norm: Optional[float] = None, *, params=None, ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 **torch_options):
         super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, params=params, decoupled_weight_decay=True,
-                         **torch_options)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, **torch_options)

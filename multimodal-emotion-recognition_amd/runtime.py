@@ -126,6 +126,16 @@ SIGNATURES = {
     "m2f_adam_hyper_groups": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "m2f_adam_step_grouped": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "m2f_adam_step_ema": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                  c_float, c_int, c_float, c_void_p, c_void_p]),
+    "m2f_adam_step_g16_ema": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                      c_float, c_int, c_float, c_void_p, c_void_p]),
+    "m2f_adam_step_shadowed_range_ema": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_float, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p,
+                                                 c_void_p]),
+    "m2f_adam_step_grouped_ema": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                          c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "m2f_ema_exchange": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "m2f_plan_fused_adam_setup_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "m2f_gemm_p8": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                             c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
@@ -631,11 +641,19 @@ def param_shadow_buffer(cfg: M2FConfig, device) -> torch.Tensor:
 
 def adam_step_shadowed(cfg: M2FConfig, params, grads, exp_avg, exp_avg_sq, param_shadow, step: int, lr: float,
                        betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                       grad_scale: Optional[torch.Tensor] = None, first: int = 0, end: int = -1) -> None:
+                       grad_scale: Optional[torch.Tensor] = None, first: int = 0, end: int = -1,
+                       ema: Optional[torch.Tensor] = None, ema_w: float = 0.0) -> None:
     """torch.optim.Adam's update over the flat buffers + the bf16 shadows of every 2-D parameter (m2f_adam_step_shadowed_range).
     The buffers are always passed WHOLE; `[first, end)` - offsets of parameter tensors, end < 0: to the last one - selects what is
-    updated; `grads` fp32, or bf16 (the reduced buffer of the data-parallel bf16 exchange, same indexing)."""
+    updated; `grads` fp32, or bf16 (the reduced buffer of the data-parallel bf16 exchange, same indexing).  `ema` (the WHOLE fp32
+    average buffer) with `ema_w` = 1 - decay: the same launch also averages what it updates (m2f_adam_step_shadowed_range_ema)."""
     cc = config_to_c(cfg)
+    if ema is not None:
+        check(lib().m2f_adam_step_shadowed_range_ema(ctypes.byref(cc), params.data_ptr(), grads.data_ptr(), int(grads.dtype == torch.bfloat16),
+                                                     exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param_shadow.data_ptr(), ema.data_ptr(),
+                                                     float(ema_w), int(first), int(end), lr, betas[0], betas[1], eps, weight_decay, step,
+                                                     ptr(grad_scale), stream_ptr()), "m2f_adam_step_shadowed_range_ema")
+        return
     check(lib().m2f_adam_step_shadowed_range(ctypes.byref(cc), params.data_ptr(), grads.data_ptr(), int(grads.dtype == torch.bfloat16),
                                              exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param_shadow.data_ptr(), int(first), int(end),
                                              lr, betas[0], betas[1], eps, weight_decay, step, ptr(grad_scale), stream_ptr()),
@@ -682,8 +700,16 @@ def adam_hyper(hyper: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999), ep
 
 def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: int,
               lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-              grad_scale: Optional[torch.Tensor] = None) -> None:
-    """grads: fp32, or bf16 (the reduced buffer of the data-parallel bf16 exchange) - same update, fp32 state either way."""
+              grad_scale: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None, ema_w: float = 0.0) -> None:
+    """grads: fp32, or bf16 (the reduced buffer of the data-parallel bf16 exchange) - same update, fp32 state either way.
+    `ema` (fp32, the elements of `params`) with `ema_w` = 1 - decay: the same launch also averages (m2f_adam_step_ema / _g16_ema)."""
+    if ema is not None:
+        g16 = grads.dtype == torch.bfloat16
+        fn = lib().m2f_adam_step_g16_ema if g16 else lib().m2f_adam_step_ema
+        check(fn(params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), ema.data_ptr(), params.numel(), lr,
+                 betas[0], betas[1], eps, weight_decay, step, float(ema_w), ptr(grad_scale), stream_ptr()),
+              "m2f_adam_step_g16_ema" if g16 else "m2f_adam_step_ema")
+        return
     if grads.dtype == torch.bfloat16:
         check(lib().m2f_adam_step_g16(params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                       params.numel(), lr, betas[0], betas[1], eps, weight_decay, step, ptr(grad_scale),
@@ -712,11 +738,27 @@ def adam_hyper_groups(table: torch.Tensor, groups) -> None:
 
 
 def adam_step_grouped(cfg: M2FConfig, params, grads, exp_avg, exp_avg_sq, param_shadow: Optional[torch.Tensor], tensor_group,
-                      hyper_table: torch.Tensor, grad_scale: Optional[torch.Tensor] = None, first: int = 0, end: int = -1) -> None:
+                      hyper_table: torch.Tensor, grad_scale: Optional[torch.Tensor] = None, first: int = 0, end: int = -1,
+                      ema: Optional[torch.Tensor] = None, ema_w: float = 0.0) -> None:
     """torch.optim.Adam / AdamW with parameter groups over the flat buffers (m2f_adam_step_grouped): the tensors at offsets
     [first, end) that a group owns (`tensor_group`: a ctypes int array, one entry per parameter tensor, -1 = none) with their group's row
-    of `hyper_table`; `param_shadow` (bf16 mode) or None (fp32 mode); `grads` fp32 or bf16."""
+    of `hyper_table`; `param_shadow` (bf16 mode) or None (fp32 mode); `grads` fp32 or bf16.  `ema` with `ema_w` = 1 - decay: the same
+    launch also averages the owned tensors (m2f_adam_step_grouped_ema)."""
     cc = config_to_c(cfg)
+    if ema is not None:
+        check(lib().m2f_adam_step_grouped_ema(ctypes.byref(cc), params.data_ptr(), grads.data_ptr(), int(grads.dtype == torch.bfloat16),
+                                              exp_avg.data_ptr(), exp_avg_sq.data_ptr(), ptr(param_shadow), ema.data_ptr(), float(ema_w),
+                                              tensor_group, len(tensor_group), hyper_table.data_ptr(), int(first), int(end),
+                                              ptr(grad_scale), stream_ptr()), "m2f_adam_step_grouped_ema")
+        return
     check(lib().m2f_adam_step_grouped(ctypes.byref(cc), params.data_ptr(), grads.data_ptr(), int(grads.dtype == torch.bfloat16),
                                       exp_avg.data_ptr(), exp_avg_sq.data_ptr(), ptr(param_shadow), tensor_group, len(tensor_group),
                                       hyper_table.data_ptr(), int(first), int(end), ptr(grad_scale), stream_ptr()), "m2f_adam_step_grouped")
+
+
+def ema_exchange(cfg: M2FConfig, params: torch.Tensor, ema: torch.Tensor, tensor_group) -> None:
+    """m2f_ema_exchange: params <-> ema in place over every tensor a group owns (`tensor_group` as in adam_step_grouped), on the current
+    stream; pads and unowned tensors are not touched."""
+    cc = config_to_c(cfg)
+    check(lib().m2f_ema_exchange(ctypes.byref(cc), params.data_ptr(), ema.data_ptr(), tensor_group, len(tensor_group), stream_ptr()),
+          "m2f_ema_exchange")

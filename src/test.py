@@ -22,13 +22,21 @@ except ImportError:
         return it
 
 
-def load_model_weights(model, checkpoint_path, device):
-    """Checkpoint format of the training loop: {'epoch', 'model_state_dict', 'optimizer_state_dict'}."""
+def load_model_weights(model, checkpoint_path, device, averaged: bool = False):
+    """Checkpoint format of the training loop: {'epoch', 'model_state_dict', 'optimizer_state_dict'} and, from a run with
+    runtime.ema enabled, 'ema_state_dict'.  averaged (runtime.ema.enabled and evaluate): the averaged weights are loaded when the
+    checkpoint holds them.  Prints which weights were loaded."""
     checkpoint_path = os.path.abspath(checkpoint_path)
     if not os.path.exists(checkpoint_path):
         raise ValueError("Checkpoint not found")
     state = torch.load(checkpoint_path, map_location=device)
-    model.load_state_dict(state["model_state_dict"])
+    if averaged and "ema_state_dict" in state:
+        ema = state["ema_state_dict"]
+        model.load_state_dict(ema["parameters"])
+        print(f"Scoring the averaged weights (EMA, decay {ema['decay']}, {ema['n_averaged']} updates)")
+    else:
+        model.load_state_dict(state["model_state_dict"])
+        print("Scoring the live weights (model_state_dict)")
     return state.get("epoch")
 
 
@@ -74,7 +82,9 @@ def main(config=None):
         loader = torch.utils.data.DataLoader(Dataset(mode="test"), collate_fn=collate_fn, **config.test.data_loader)
     model = M2FNet(config.model, precision=runtime_cfg.get("precision", "fp32")).to(device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
-    load_model_weights(model, config.checkpoint.load_path, device)
+    from train import ema_settings
+    ema = ema_settings(config)
+    load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
     print("Testing...")
     accuracy, weighted_f1 = test(model, loader, device)
     print(f"Accuracy=[{accuracy * 100:.3f}%] Weighted_F1=[{weighted_f1 * 100:.3f}%]")

@@ -33,6 +33,7 @@ except ImportError:
     wandb = None
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict")
+EMA_KEY = "ema_state_dict"                              # present only when runtime.ema is enabled
 N_CLASSES = 7
 
 
@@ -83,6 +84,35 @@ def clip_grad_norm(cfg, world: int = 1):
         raise ValueError("runtime.clip_grad_norm does not combine with runtime.grad_overlap: True "
                          "(the global norm needs every bucket's reduced gradients before the first update)")
     return float(v)
+
+
+def ema_settings(cfg):
+    """`runtime.ema` = {enabled, decay, warmup, evaluate}: an exponential moving average of the weights kept by the optimizer kernels
+    (FusedAdam.ema_decay).  -> None when the block is absent or disabled, else (decay, warmup, evaluate); evaluate: validation, early
+    stopping and test.py score the averaged weights.  Checked on the host before the GPU is touched: the optimizer must run outside
+    the step (runtime.fused_optimizer: False - the in-launch optimizer has no EMA stream)."""
+    block = _runtime(cfg, "ema", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.ema must be a mapping {{enabled, decay, warmup, evaluate}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - {"enabled", "decay", "warmup", "evaluate"})
+    if unknown:
+        raise ValueError(f"runtime.ema: unknown key(s) {unknown} (enabled, decay, warmup, evaluate)")
+    flags = {}
+    for k, default in (("enabled", False), ("warmup", False), ("evaluate", True)):
+        flags[k] = block.get(k, default)
+        if not isinstance(flags[k], bool):
+            raise ValueError(f"runtime.ema.{k} must be true or false (got {flags[k]!r})")
+    decay = block.get("decay", 0.999)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:
+        raise ValueError(f"runtime.ema.decay must be a number in [0, 1] (got {decay!r})")
+    if not flags["enabled"]:
+        return None
+    if bool(_runtime(cfg, "fused_optimizer", False)):
+        raise ValueError("runtime.ema.enabled does not combine with runtime.fused_optimizer: True "
+                         "(the optimizer inside the step has no EMA stream)")
+    return float(decay), flags["warmup"], flags["evaluate"]
 
 
 def _under(name: str, prefix: str) -> bool:
@@ -154,8 +184,10 @@ def model_named_shapes(model_cfg):
 def build_optimizer(config, model):
     """torch.optim.Adam(model.parameters(), lr, weight_decay) of the reference (src/train.py:56), or what `runtime.optimizer` asks for."""
     cut = optimizer_groups(config, [(n, tuple(p.shape)) for n, p in model.named_parameters(remove_duplicate=False)])
+    ema = ema_settings(config)
+    ema_kw = {} if ema is None else {"ema_decay": ema[0], "ema_warmup": ema[1]}
     if cut is None:
-        return FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay)
+        return FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay, **ema_kw)
     name, groups, _ = cut
     named = dict(model.named_parameters(remove_duplicate=False))
     params, seen = [], {}
@@ -169,7 +201,7 @@ def build_optimizer(config, model):
                 ps.append(p)
         params.append({"params": ps, "lr": g["lr"], "weight_decay": g["weight_decay"]})
     cls = FusedAdamW if name == "adamw" else FusedAdam
-    return cls(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay, params=params)
+    return cls(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay, params=params, **ema_kw)
 
 
 def group_batches(batches, k: int):
@@ -282,11 +314,25 @@ def resume_if_requested(config, model, optimizer, device):
     state = torch.load(path, map_location=device)
     model.load_state_dict(state["model_state_dict"])
     optimizer.load_state_dict(state["optimizer_state_dict"])
+    if ema_settings(config) is not None:
+        if EMA_KEY in state:
+            optimizer.load_ema_state_dict(state[EMA_KEY])
+        elif _rank() == 0:
+            print(f"Checkpoint {path} holds no {EMA_KEY}: the weight average starts afresh")
     return state["epoch"] + 1
 
 
+def _has_average(optimizer) -> bool:
+    return getattr(optimizer, "n_averaged", 0) > 0
+
+
 def write_checkpoint(path, epoch, model, optimizer):
-    torch.save(dict(zip(CHECKPOINT_KEYS, (epoch, model.state_dict(), optimizer.state_dict()))), path)
+    """The reference's three entries - the LIVE weights, so a resume is exact - and, when the optimizer keeps a weight average
+    (runtime.ema), FusedAdam.ema_state_dict() beside them."""
+    state = dict(zip(CHECKPOINT_KEYS, (epoch, model.state_dict(), optimizer.state_dict())))
+    if _has_average(optimizer):
+        state[EMA_KEY] = optimizer.ema_state_dict()
+    torch.save(state, path)
 
 
 def main(config=None):
@@ -297,6 +343,7 @@ def main(config=None):
     want_dp = _runtime(config, "data_parallel", "auto")
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
+    ema_settings(config)
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # W independent trainings on one device, all writing the same checkpoint, is never what a launcher was asked for
@@ -420,7 +467,7 @@ class EarlyStopper:
         print(f"Early stopping: patience {self.patience} reached")
         if self.restore:                                 # the final checkpoint becomes the best one; the side file goes away
             best = torch.load(self.best_path)
-            torch.save({k: best[k] for k in CHECKPOINT_KEYS}, self.save_path)
+            torch.save({k: best[k] for k in CHECKPOINT_KEYS + (EMA_KEY,) if k in best}, self.save_path)
             os.remove(self.best_path)
             print(f"Best model at epoch {best['epoch']} restored")
         return True
@@ -437,9 +484,16 @@ def training_loop(model, dl_train, dl_val, criterion, optimizer, lr_scheduler, s
 
     stopper = EarlyStopper(solver.early_stopping, save_path)
     history = {"loss_values": [], "val_loss_values": []}
+    ema = ema_settings(config)
     for epoch in range(start_epoch, solver.epochs):
         train_loss = train(model, dl_train, criterion, optimizer, epoch, log_to_wandb, device)
-        val_loss, accuracy, weighted_f1 = validate(model, dl_val, criterion, device)
+        if ema is not None and ema[2] and _has_average(optimizer):
+            # runtime.ema.evaluate: the printed and early-stopping numbers are those of the averaged weights (host path and
+            # device_metrics alike); the checkpoints below are written outside the context, with the live weights
+            with optimizer.averaged_parameters():
+                val_loss, accuracy, weighted_f1 = validate(model, dl_val, criterion, device)
+        else:
+            val_loss, accuracy, weighted_f1 = validate(model, dl_val, criterion, device)
         history["loss_values"].append(train_loss)
         history["val_loss_values"].append(val_loss)
 
