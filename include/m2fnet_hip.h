@@ -222,6 +222,34 @@ int m2f_grad_sumsq(const m2f_config* cfg, const void* grads, int grads_bf16, int
 int m2f_grad_norm_finalize(const m2f_config* cfg, const double* scratch, const float* den_ptr, double max_norm, float* record,
                            m2f_stream_t stream);
 
+/* Per-tensor statistics and histograms of one flat buffer in the model's parameter layout (the model watch: what
+ * wandb.watch(model, log="all") of the reference's loop, src/train.py:132-138, logs per parameter and per gradient tensor, computed
+ * where the values live).  `a`: fp32, or (a_is_bf16 != 0) bf16 with the same indexing, 16-byte aligned; `b` (fp32, or NULL): the
+ * statistics are those of x = a - b, one fp32 subtraction per element (a fp32).  Only parameter elements are read: the alignment
+ * pads between tensors may hold anything.
+ *
+ * Three launches on `stream`: pass 1 (one partial per slice of 8192 elements of one tensor, into `scratch`), a finalize launch, and
+ * pass 2, the histogram, a second read of the buffer.  record (m2f_tensor_stats_record_bytes(cfg, bins) bytes, 8-byte aligned, contents
+ * irrelevant before the call):
+ *   double[0] den = *den_ptr, or 1 when den_ptr is NULL   [1] number of tensors   [2] bins   [3] 0
+ *   then one row per parameter tensor, in parameter-map order (m2f_param_layout):
+ *     double[9]: numel, finite, nan, inf, zeros (x == 0), min, max over the finite values, their sum and sum of squares (float64
+ *                accumulation); a tensor with no finite value has NaN in the last four
+ *     int64[bins]: the counts of torch.histc(x[isfinite], bins, min, max) - pos = (int)((x - lo) * bins / (hi - lo)) in IEEE fp32 in
+ *                that order, pos == bins counted in the last bin; lo, hi = min, max (lo - 1, hi + 1 when they are equal); all zero for
+ *                a tensor with no finite value.
+ * bins in [2, 256].  grid: workgroups of the two passes, <= 0 = default (at most 2048); nontemporal != 0: nontemporal loads.  Neither
+ * changes a byte of the record, and two calls on the same buffer give the same bytes (float64 sums in a fixed order, integer counts).
+ * m2f_tensor_stats_passes: the same with passes = 1 (pass 1 + finalize), 2 (pass 2 alone, onto the rows an earlier pass 1 left; it
+ * ADDS its counts) or 3 (everything) - for timing the passes separately.  The size functions return -1 on a NULL configuration or bins
+ * out of range. */
+int64_t m2f_tensor_stats_scratch_bytes(const m2f_config* cfg, int bins);
+int64_t m2f_tensor_stats_record_bytes(const m2f_config* cfg, int bins);
+int m2f_tensor_stats(const m2f_config* cfg, const void* a, int a_is_bf16, const float* b, int bins, const float* den_ptr, void* scratch,
+                     void* record, int grid, int nontemporal, m2f_stream_t stream);
+int m2f_tensor_stats_passes(const m2f_config* cfg, const void* a, int a_is_bf16, const float* b, int bins, const float* den_ptr,
+                            void* scratch, void* record, int grid, int nontemporal, int passes, m2f_stream_t stream);
+
 /* Scoring of validation / test batches on the device: what the reference's loops do per batch on the host with torch and sklearn
  * (validate: src/train.py:245-272 - criterion(...).item(), argmax, the label != -1 masks, accuracy_score and
  * f1_score(average="weighted") per batch, averaged unweighted over the batches; test: src/test.py:51-74, the same without the loss).

@@ -22,13 +22,15 @@ w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
 mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
 # --gradnorm <remarks>: the gradient-norm kernels (gradnorm.hip) - the same rule (a slice's loads and float64 accumulators stay in registers)
 gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
+# --tstats <remarks>: the model-watch kernels (tensor_stats.hip) - the same rule (a slice's loads, float64 sums and counters stay in registers)
+tstats = len(sys.argv) > 2 and sys.argv[1] == "--tstats"
 # --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
 metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
 # registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
-path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or metrics or adam) else sys.argv[1]
+path = sys.argv[2] if (ring or dlong or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -57,8 +59,8 @@ if adam:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
               f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
     sys.exit(1 if bad else 0)
-if dlong or w2v or mel or gradnorm or metrics:
-    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_eval_"
+if dlong or w2v or mel or gradnorm or tstats or metrics:
+    tag = "m2f_attn_dlong" if dlong else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_tstats_" if tstats else "m2f_eval_"
     kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
         sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")

@@ -393,6 +393,20 @@ hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const GradSlice* 
 hipError_t m2f_launch_grad_norm_finalize(const double* partial, int n, const float* den_ptr, double max_norm, float* record,
                                          hipStream_t stream);
 
+// Per-tensor statistics and histograms of a flat buffer (tensor_stats.hip).  StatSlice = GradSlice's cut with the index of the slice's
+// tensor; tensor_begin[t] = first slice of tensor t, [n_tensors] = n_slices.  Pass 1 writes partial[s] (a slice's finite count is
+// n - nan - inf), the finalize launch the record header (M2F_TSTATS_HEADER doubles: den, n_tensors, bins, 0) and one row per tensor
+// (M2F_TSTATS_FIELDS doubles - numel, finite, nan, inf, zeros, min, max, sum, sumsq - then `bins` int64 counts, zeroed), pass 2 adds the
+// counts.  passes: bit 0 = pass 1 + finalize, bit 1 = pass 2 (which needs the rows of an earlier pass 1).  b (fp32, or null): x = a - b.
+struct StatSlice { long long off; int n; int tensor; };
+struct StatPartial { double sum, sumsq; float mn, mx; int nan, inf, zeros, pad_; };
+#define M2F_TSTATS_HEADER 4
+#define M2F_TSTATS_FIELDS 9
+#define M2F_TSTATS_MAX_BINS 256
+hipError_t m2f_launch_tensor_stats(const void* a, int a_is_bf16, const float* b, const StatSlice* slices, const int* tensor_begin,
+                                   int n_slices, int n_tensors, int bins, const float* den_ptr, StatPartial* partial, double* record,
+                                   int grid, int nontemporal, int passes, hipStream_t stream);
+
 #ifdef __HIPCC__
 // shadow address of a workspace element, or null (no shadows / pointer outside the workspace, e.g. the gradient buffer)
 __device__ __forceinline__ uint16_t* m2f_shadow_of(const ShadowMap& sh, const float* p) {

@@ -118,11 +118,21 @@ class FusedAdam(torch.optim.Optimizer):
     group is not averaged (its EMA slice is never touched, ``ema_state_dict`` reports its live value); buffers are not averaged
     (M2FNet has none); the average is not part of ``state_dict()`` (torch's format) but of ``ema_state_dict()``.  Refused
     combination: the optimizer inside the weight-gradient launch has no EMA stream - ``prepare_fused`` returns False, as with
-    ``max_grad_norm``.  None (the default): the step as it was, launch for launch."""
+    ``max_grad_norm``.  None (the default): the step as it was, launch for launch.
+
+    ``watch`` (keyword-only constructor argument and plain attribute; a ``watch.ModelWatch`` or None): the optimizer counts its own
+    steps, and on step ``n`` (from 0) with ``n % watch.log_freq == 0`` it enqueues, before the update kernels, one statistics collection
+    per watched kind on the buffers THIS step uses (``ModelWatch``'s docstring; csrc/tensor_stats.hip) and, for ``updates``, one after
+    them.  Nothing waits for the host; ``watch.read()`` does.  Clipping and the watch read the same gradient buffer in the same step and
+    neither changes the other; a tensor in no parameter group is watched like any other.  ``prepare_fused`` returns False while a watch
+    that logs ``gradients`` or ``updates`` is attached (the in-launch optimizer never stores the matrices' gradients); with other kinds
+    the in-launch step is counted and the buffers are collected as they are before it.  In ``step_ranges`` on a due step `before_each`
+    runs for all ranges first, as with clipping.  Parameters, moments, shadows and the EMA are what they are without it, bit for bit.
+    None (the default): the step as it was, launch for launch."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: Optional[float] = None, *, params=None, decoupled_weight_decay: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False, **torch_options):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, watch=None, **torch_options):
         for k, v in torch_options.items():
             if k not in _TORCH_ONLY:
                 raise TypeError(f"FusedAdam.__init__() got an unexpected keyword argument {k!r}")
@@ -134,6 +144,8 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema: Optional[torch.Tensor] = None           # fp32, the layout of engine.flat; allocated at the first averaging step
         self._n_averaged = 0
         self._averaged_in = False                          # inside averaged_parameters(): model <-> average exchanged
+        self.watch = watch                                 # watch.ModelWatch or None
+        self._n_steps = 0                                  # optimizer steps taken (every form): the watch's schedule
         # grouped: anything but ONE coupled group over model.parameters() - the hyper table and the grouped kernels instead of
         # the single-group entries
         self._grouped = params is not None or bool(decoupled_weight_decay)
@@ -363,6 +375,36 @@ class FusedAdam(torch.optim.Optimizer):
                 self.state[p] = {"step": torch.tensor(float(self._step)),
                                  "exp_avg": self._m[o: o + n].view(s), "exp_avg_sq": self._v[o: o + n].view(s)}
 
+    # ---- model watch ------------------------------------------------------------------------------------------------------------
+    def _watch_due(self):
+        """Counts the optimizer step that begins; -> the attached watch when that step is due, else None."""
+        n, self._n_steps = self._n_steps, self._n_steps + 1
+        w = self.watch
+        if w is None or not w.due(n):
+            return None
+        w.begin(n)
+        return w
+
+    def _watch_before(self, w, eng, flat_grad) -> None:
+        """The due step's collections on the buffers as they are before the update kernels; `flat_grad` None: no gradient buffer."""
+        for kind in w.kinds:
+            if kind == "gradients" and flat_grad is not None:
+                w.collect(kind, flat_grad, den=self.grad_scale)
+            elif kind == "parameters":
+                w.collect(kind, eng.flat)
+            elif kind == "exp_avg":
+                w.collect(kind, self._m)
+            elif kind == "exp_avg_sq":
+                w.collect(kind, self._v)
+            elif kind == "ema" and self._ema is not None and self._n_averaged > 0:
+                w.collect(kind, self._ema)
+            elif kind == "updates" and flat_grad is not None:
+                w.snapshot(eng.flat)
+
+    def _watch_after(self, w, eng) -> None:
+        if w is not None and "updates" in w.kinds:
+            w.collect("updates", eng.flat, other=w._snapshot)
+
     def _clip(self, eng, flat_grad) -> Optional[torch.Tensor]:
         """-> the device scalar the Adam kernels divide the gradients by: ``grad_scale`` itself without clipping; with it, the
         divisor of the clip record, written by the two norm launches over `flat_grad` on the current stream."""
@@ -415,6 +457,9 @@ class FusedAdam(torch.optim.Optimizer):
                     view.zero_()
                 elif p.grad.data_ptr() != view.data_ptr():
                     view.copy_(p.grad)
+        watch = self._watch_due()
+        if watch is not None:
+            self._watch_before(watch, eng, flat_grad)
         if self._grouped:
             self._gsteps = [t + 1 for t in self._gsteps]
             scale = self._clip(eng, flat_grad)
@@ -424,6 +469,7 @@ class FusedAdam(torch.optim.Optimizer):
             runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale,
                                       ema=ema, ema_w=ema_w)
             self._n_averaged += ema is not None
+            self._watch_after(watch, eng)
             if eng.wshadow is not None and self._owns_everything():
                 eng.mark_shadows_fresh()
             return loss
@@ -439,6 +485,7 @@ class FusedAdam(torch.optim.Optimizer):
             runtime.adam_step(eng.flat, flat_grad, self._m, self._v, self._step, g["lr"], g["betas"], g["eps"],
                               g["weight_decay"], scale, ema=ema, ema_w=ema_w)
         self._n_averaged += ema is not None
+        self._watch_after(watch, eng)
         return loss
 
     @torch.no_grad()
@@ -453,6 +500,8 @@ class FusedAdam(torch.optim.Optimizer):
         returns False as well: the in-launch optimizer has no EMA stream (its epilogue is at its register budget)."""
         self._refuse_averaged("prepare_fused()")
         if self.max_grad_norm is not None or self.ema_decay is not None:
+            return False
+        if self.watch is not None and ("gradients" in self.watch.kinds or "updates" in self.watch.kinds):
             return False
         eng = self._bind()
         if eng.wshadow is None or not plan.train or not getattr(plan, "shared_shadow", False):
@@ -476,6 +525,9 @@ class FusedAdam(torch.optim.Optimizer):
             plan._fused_key = key
         g = self.param_groups[0]
         self._step += 1
+        watch = self._watch_due()
+        if watch is not None:
+            self._watch_before(watch, eng, None)
         runtime.adam_hyper(self._hyper, self._step, g["lr"], g["betas"], g["eps"], g["weight_decay"])
         plan.fused_adam(True)
         return True
@@ -501,6 +553,9 @@ class FusedAdam(torch.optim.Optimizer):
                 return False
             plan._fused_key = key
         self._gsteps = [t + 1 for t in self._gsteps]
+        watch = self._watch_due()
+        if watch is not None:
+            self._watch_before(watch, eng, None)
         self._refresh_table(eng)
         plan.fused_adam(True)
         return True
@@ -522,7 +577,8 @@ class FusedAdam(torch.optim.Optimizer):
         parameter shadows current (m2f_adam_step_shadowed_range); other ranges leave them to the next forward's casts.
         With ``max_grad_norm`` set the global norm needs every range's gradients: `before_each` runs for ALL ranges first, then the
         norm launches over the whole buffer, then the ranges' updates with the clip record's divisor - the updates no longer hide
-        under the exchange of the following buckets; that is the price of a global norm."""
+        under the exchange of the following buckets; that is the price of a global norm.  A due step of an attached ``watch`` does the
+        same, on that step only: every range's `before_each` first, then the collections over the whole buffers, then the updates."""
         self._refuse_averaged("step_ranges()")
         eng = self._bind()
         g = self.param_groups[0]
@@ -530,17 +586,21 @@ class FusedAdam(torch.optim.Optimizer):
         n = eng.flat.numel()
         ranges = [(lo, min(hi, n)) for (lo, hi) in ranges]
         ema, ema_w = self._ema_begin(eng)                    # the SAME weight for every range of this step
+        watch = self._watch_due()
         if self._grouped:
-            self._step_ranges_grouped(eng, flat_grad, ranges, before_each, n, ema, ema_w)
+            self._step_ranges_grouped(eng, flat_grad, ranges, before_each, n, ema, ema_w, watch)
             self._n_averaged += ema is not None
+            self._watch_after(watch, eng)
             return
         self._step += 1
         scale = self.grad_scale
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or watch is not None:
             if before_each is not None:
                 for i in range(len(ranges)):
                     before_each(i)
                 before_each = None
+            if watch is not None:
+                self._watch_before(watch, eng, flat_grad)
             scale = self._clip(eng, flat_grad)
         # bf16 mode with the model-wide parameter shadows: ranges that start and end at parameter tensors (dp.GradReducer aligns its
         # buckets that way) go through the shadow-writing kernel, so the next forward needs no parameter casts under data parallelism
@@ -561,6 +621,7 @@ class FusedAdam(torch.optim.Optimizer):
                 runtime.adam_step(eng.flat[lo:hi], flat_grad[lo:hi], self._m[lo:hi], self._v[lo:hi], self._step, g["lr"],
                                   g["betas"], g["eps"], g["weight_decay"], scale, ema=None if ema is None else ema[lo:hi], ema_w=ema_w)
         self._n_averaged += ema is not None
+        self._watch_after(watch, eng)
         if shadowed:
             covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
             whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
@@ -569,7 +630,7 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 eng.invalidate_shadows()
 
-    def _step_ranges_grouped(self, eng, flat_grad, ranges, before_each, n, ema=None, ema_w=0.0):
+    def _step_ranges_grouped(self, eng, flat_grad, ranges, before_each, n, ema=None, ema_w=0.0, watch=None):
         starts = self._tensor_starts(eng)
         for lo, hi in ranges:
             if hi > lo and not (lo in starts and (hi >= n or hi in starts)):
@@ -577,11 +638,13 @@ class FusedAdam(torch.optim.Optimizer):
                                  "groups / decoupled weight decay takes ranges of whole tensors only (dp.GradReducer's buckets are)")
         self._gsteps = [t + 1 for t in self._gsteps]
         scale = self.grad_scale
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or watch is not None:
             if before_each is not None:
                 for i in range(len(ranges)):
                     before_each(i)
                 before_each = None
+            if watch is not None:
+                self._watch_before(watch, eng, flat_grad)
             scale = self._clip(eng, flat_grad)
         tg = self._refresh_table(eng)
         for i, (lo, hi) in enumerate(ranges):
@@ -647,6 +710,6 @@ class FusedAdamW(FusedAdam):
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  max_grad_norm: Optional[float] = None, *, params=None, ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                 **torch_options):
+                 watch=None, **torch_options):
         super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, params=params, decoupled_weight_decay=True,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, **torch_options)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, watch=watch, **torch_options)

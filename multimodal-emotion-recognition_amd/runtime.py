@@ -75,6 +75,12 @@ SIGNATURES = {
     "m2f_grad_norm_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC)]),
     "m2f_grad_sumsq": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p]),
     "m2f_grad_norm_finalize": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+    "m2f_tensor_stats_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
+    "m2f_tensor_stats_record_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
+    "m2f_tensor_stats": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_void_p]),
+    "m2f_tensor_stats_passes": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_int, c_int, c_void_p]),
     "m2f_eval_scratch_bytes": (c_int64, [c_int, c_int]),
     "m2f_eval_record_bytes": (c_int64, [c_int]),
     "m2f_eval_scores": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
@@ -691,6 +697,36 @@ def grad_norm_finalize(cfg: M2FConfig, scratch: torch.Tensor, record: torch.Tens
     cc = config_to_c(cfg)
     check(lib().m2f_grad_norm_finalize(ctypes.byref(cc), scratch.data_ptr(), ptr(den), float(max_norm), record.data_ptr(), stream_ptr()),
           "m2f_grad_norm_finalize")
+
+
+TSTATS_HEADER, TSTATS_FIELDS, TSTATS_MAX_BINS = 4, 9, 256      # csrc/ops.h M2F_TSTATS_*
+
+
+def tensor_stats_buffers(cfg: M2FConfig, bins: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (scratch, record) of m2f_tensor_stats for `bins` bins: uint8 scratch of one partial per 8192-element slice of a parameter
+    tensor, and the float64 record (TSTATS_HEADER values, then TSTATS_FIELDS + bins per parameter tensor; the counts are int64 bits)."""
+    cc = config_to_c(cfg)
+    ns, nr = lib().m2f_tensor_stats_scratch_bytes(ctypes.byref(cc), int(bins)), lib().m2f_tensor_stats_record_bytes(ctypes.byref(cc), int(bins))
+    if ns < 0 or nr < 0:
+        raise HipError(lib().m2f_last_error().decode())
+    return torch.zeros(ns // 8, dtype=torch.float64, device=device), torch.zeros(nr // 8, dtype=torch.float64, device=device)
+
+
+def tensor_stats(cfg: M2FConfig, a: torch.Tensor, scratch: torch.Tensor, record: torch.Tensor, bins: int,
+                 b: Optional[torch.Tensor] = None, den: Optional[torch.Tensor] = None, grid: int = 0,
+                 nontemporal: Optional[bool] = None, passes: int = 3) -> None:
+    """m2f_tensor_stats: statistics and `bins`-bin histogram of every parameter tensor of the WHOLE flat buffer `a` (fp32 or bf16; with
+    `b`, fp32: of a - b) into `record`, three launches on the current stream.  `grid` / `nontemporal` change speed only, never a byte;
+    `passes` (1: statistics, 2: histogram alone, 3: both) is for timing."""
+    cc = config_to_c(cfg)
+    nt = GRAD_NORM_NONTEMPORAL if nontemporal is None else bool(nontemporal)
+    if passes == 3:
+        check(lib().m2f_tensor_stats(ctypes.byref(cc), a.data_ptr(), int(a.dtype == torch.bfloat16), ptr(b), int(bins), ptr(den),
+                                     scratch.data_ptr(), record.data_ptr(), int(grid), int(nt), stream_ptr()), "m2f_tensor_stats")
+        return
+    check(lib().m2f_tensor_stats_passes(ctypes.byref(cc), a.data_ptr(), int(a.dtype == torch.bfloat16), ptr(b), int(bins), ptr(den),
+                                        scratch.data_ptr(), record.data_ptr(), int(grid), int(nt), int(passes), stream_ptr()),
+          "m2f_tensor_stats_passes")
 
 
 def adam_hyper(hyper: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0) -> None:

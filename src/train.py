@@ -21,6 +21,7 @@ from model import M2FNet  # noqa: E402
 from utils import get_config  # noqa: E402
 from mer_amd import dp  # noqa: E402
 from mer_amd.optim import MAX_GROUPS, FusedAdam, FusedAdamW, M2FCrossEntropyLoss  # noqa: E402
+from mer_amd.watch import ModelWatch, check_bins, check_kinds, check_log_freq  # noqa: E402
 
 try:
     from tqdm import tqdm
@@ -113,6 +114,63 @@ def ema_settings(cfg):
         raise ValueError("runtime.ema.enabled does not combine with runtime.fused_optimizer: True "
                          "(the optimizer inside the step has no EMA stream)")
     return float(decay), flags["warmup"], flags["evaluate"]
+
+
+def watch_settings(cfg, world: int = 1):
+    """`runtime.watch` = {enabled, log, log_freq, bins, file}: per-tensor statistics and histograms of the buffers the optimizer step
+    uses, every log_freq optimizer steps (mer_amd.watch.ModelWatch) - what `wandb.watch_model` asks of wandb's hooks, which cannot see
+    those buffers.  -> None when the block is absent or disabled, else {"log": kinds, "log_freq", "bins", "file"}.  Checked on the host
+    before the GPU is touched: the optimizer must run outside the step (runtime.fused_optimizer: False) and, with several ranks and
+    gradients or updates watched, behind the whole exchange (runtime.grad_overlap: False; one rank ignores that key)."""
+    block = _runtime(cfg, "watch", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.watch must be a mapping {{enabled, log, log_freq, bins, file}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - {"enabled", "log", "log_freq", "bins", "file"})
+    if unknown:
+        raise ValueError(f"runtime.watch: unknown key(s) {unknown} (enabled, log, log_freq, bins, file)")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.watch.enabled must be true or false (got {enabled!r})")
+    try:
+        kinds = check_kinds(block.get("log", "all"))
+        log_freq = check_log_freq(block.get("log_freq", 100))
+        bins = check_bins(block.get("bins", 64))
+    except ValueError as e:
+        raise ValueError(str(e).replace("ModelWatch: ", "runtime.watch.")) from None
+    file = block.get("file", None)
+    if file is not None and (not isinstance(file, str) or not file):
+        raise ValueError(f"runtime.watch.file must be null or a path (got {file!r})")
+    if not enabled:
+        return None
+    if bool(_runtime(cfg, "fused_optimizer", False)):
+        raise ValueError("runtime.watch.enabled does not combine with runtime.fused_optimizer: True "
+                         "(the optimizer inside the step never stores the matrices' gradients)")
+    if world > 1 and bool(_runtime(cfg, "grad_overlap", False)) and ("gradients" in kinds or "updates" in kinds):
+        raise ValueError("runtime.watch with gradients or updates does not combine with runtime.grad_overlap: True "
+                         "(the collection needs every bucket's reduced gradients before the first update)")
+    return {"log": kinds, "log_freq": log_freq, "bins": bins, "file": file}
+
+
+def attach_watch(cfg, model, optimizer, rank: int = 0, world: int = 1):
+    """Builds the ModelWatch `runtime.watch` asks for and attaches it to the optimizer - on rank 0 only: the replicas' reduced gradients
+    are identical, and what a due step adds waits on collectives that are already issued, so no rank blocks another.  -> the watch, or
+    None (block off, or another rank).  An optimizer that is not a FusedAdam is refused: only it knows the buffers a step reads."""
+    settings = watch_settings(cfg, world)
+    if settings is None:
+        return None
+    if not isinstance(optimizer, FusedAdam):
+        raise ValueError(f"runtime.watch.enabled needs the FusedAdam / FusedAdamW optimizer (got {type(optimizer).__name__}): "
+                         "it hands the watch the buffers each step reads")
+    if rank != 0:
+        return None
+    w = ModelWatch(model, log=settings["log"], log_freq=settings["log_freq"], bins=settings["bins"])
+    w.file = None if settings["file"] is None else os.path.abspath(settings["file"])
+    if w.file is not None:
+        os.makedirs(os.path.dirname(w.file), exist_ok=True)
+    optimizer.watch = w
+    return w
 
 
 def _under(name: str, prefix: str) -> bool:
@@ -344,6 +402,7 @@ def main(config=None):
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
+    watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # W independent trainings on one device, all writing the same checkpoint, is never what a launcher was asked for
@@ -417,6 +476,7 @@ def main(config=None):
     criterion = build_criterion(config.solver, train_set, device)
     optimizer = build_optimizer(config, model)
     optimizer.max_grad_norm = clip_grad_norm(config, world)
+    attach_watch(config, model, optimizer, rank, world)
     if world > 1:
         model.dp_step = dp.DataParallelStep(model, optimizer, n_buckets=int(_runtime(config, "grad_buckets", 4)),
                                             exchange=_runtime(config, "grad_exchange", "fp32"),
@@ -481,6 +541,9 @@ def training_loop(model, dl_train, dl_val, criterion, optimizer, lr_scheduler, s
     os.makedirs(os.path.dirname(save_path), exist_ok=True)
     if log_to_wandb and config.wandb.watch_model:
         wandb.watch(model, criterion=criterion, log="all", log_freq=100, log_graph=False)
+        if getattr(optimizer, "watch", None) is None:
+            print("wandb.watch_model: wandb's parameter hooks do not see the gradients the kernels write (INTEGRATION.md section B); "
+                  "runtime.watch: {enabled: True} logs them from the buffers the optimizer reads")
 
     stopper = EarlyStopper(solver.early_stopping, save_path)
     history = {"loss_values": [], "val_loss_values": []}
@@ -532,6 +595,22 @@ def _grad_norm_log(optimizer):
     return {"Train/Grad_norm": float(optimizer.grad_norm())}
 
 
+def _watch_log(optimizer, wandb_log):
+    """After a due step of the optimizer's watch (runtime.watch): reads its record - one copy, on a path that has just waited for
+    loss.item() - appends the JSON line to runtime.watch.file and returns {"gradients/<name>": wandb.Histogram, ...} for the step's
+    wandb.log call; otherwise nothing."""
+    w = getattr(optimizer, "watch", None)
+    if w is None or not w.pending:
+        return {}
+    rec = w.read()
+    if w.file is not None:
+        with open(w.file, "a") as f:
+            f.write(w.json_line(rec) + "\n")
+    if not wandb_log:
+        return {}
+    return {k: wandb.Histogram(np_histogram=v) for k, v in w.wandb_payload(rec).items()}
+
+
 def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     """One epoch; returns the mean of the per-batch losses (reference src/train.py:217-243)."""
     model.train()
@@ -568,9 +647,10 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 loss.backward()
             optimizer.step()
         running += loss.item()
+        watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                       **_grad_norm_log(optimizer)})
+                       **_grad_norm_log(optimizer), **watched})
     return running / len(dl_train)
 
 
@@ -605,9 +685,10 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             optimizer.step()
             loss = terms[2] / terms[1]
         running += loss.item()
+        watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step,
-                       **_grad_norm_log(optimizer)})
+                       **_grad_norm_log(optimizer), **watched})
     if dp_step is None:
         optimizer.grad_scale = None
     return running / max(n_groups, 1)
