@@ -2,9 +2,9 @@
 // norm type 2).  Two launches, no atomics, float64 sums: the published fp32 values are the same bits on every run, for every grid
 // size and on every rank that holds the same buffer.
 //
-//   m2f_gradnorm_sumsq_kernel     one float64 partial per SLICE: at most M2F_GRADNORM_SLICE consecutive elements of ONE parameter
-//                                 tensor (ops.h GradSlice; the host cuts the tensors, so the 256-byte pads between tensors belong to
-//                                 no slice - the data-parallel bf16 exchange buffer is torch.empty and its pads hold garbage).
+//   m2f_gradnorm_sumsq_kernel     one float64 partial per SLICE: at most M2F_PARAM_SLICE consecutive elements of ONE parameter
+//                                 tensor (ops.h ParamSlice, the slice every per-tensor kernel walks: param_tables.hip cuts the tensors
+//                                 once, so the 256-byte pads between tensors belong to no slice - the data-parallel bf16 exchange buffer is torch.empty and its pads hold garbage).
 //                                 A slice's sum depends on the slice alone: lane t of the workgroup takes the same elements in the
 //                                 same order whichever workgroup of whichever grid picks the slice up, the wave / LDS tree is fixed.
 //   m2f_gradnorm_finalize_kernel  one workgroup: the partials summed in a fixed order (thread t takes t, t + 1024, ...; then the same
@@ -80,19 +80,19 @@ __device__ __forceinline__ double grad1(const void* g, long long o) {
 // G16: the buffer holds bf16 (M2FNet.set_grad_bf16, the data-parallel bf16 exchange), same indexing.  NT: nontemporal loads.
 // Grid-stride over slices [s0, s1); partial[s] is written by exactly one workgroup.
 template <bool G16, bool NT>
-__global__ __launch_bounds__(256) void m2f_gradnorm_sumsq_kernel(const void* __restrict__ g, const GradSlice* __restrict__ slices,
+__global__ __launch_bounds__(256) void m2f_gradnorm_sumsq_kernel(const void* __restrict__ g, const ParamSlice* __restrict__ slices,
                                                                   int s0, int s1, double* __restrict__ partial) {
     constexpr int V = G16 ? 8 : 4;                               // elements per 16-byte load
-    constexpr int ROUNDS = M2F_GRADNORM_SLICE / (256 * V);       // loads per lane and slice: 8 (fp32), 4 (bf16)
+    constexpr int ROUNDS = M2F_PARAM_SLICE / (256 * V);          // loads per lane and slice: 8 (fp32), 4 (bf16)
     constexpr int ESZ = G16 ? 2 : 4;
     __shared__ double red[2][4];
     const int tid = threadIdx.x;
     int par = 0;
     for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x, par ^= 1) {
-        const GradSlice sl = slices[s];
+        const ParamSlice sl = slices[s];
         const char* base = static_cast<const char*>(g) + sl.off * ESZ;          // tensor offsets are multiples of 64 elements: 16-byte aligned
         double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        if (sl.n == M2F_GRADNORM_SLICE) {                        // whole slice (block-uniform): every load first, then the arithmetic
+        if (sl.n == M2F_PARAM_SLICE) {                           // whole slice (block-uniform): every load first, then the arithmetic
             u32x4 r[ROUNDS];
 #pragma unroll
             for (int j = 0; j < ROUNDS; ++j) r[j] = load16<NT>(base + ((size_t)j * 256 + tid) * 16);
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(1024) void m2f_gradnorm_finalize_kernel(const doubl
 
 }  // namespace
 
-hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const GradSlice* slices, int s0, int s1, double* partial, int grid,
+hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const ParamSlice* slices, int s0, int s1, double* partial, int grid,
                                  int nontemporal, hipStream_t stream) {
     if (!g || !slices || !partial || s0 < 0 || s1 < s0 || (reinterpret_cast<uintptr_t>(g) & 15)) return hipErrorInvalidValue;
     if (s1 == s0) return hipSuccess;

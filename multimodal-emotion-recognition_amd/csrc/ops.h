@@ -368,42 +368,42 @@ hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, floa
 // holds one row of 8 floats per group in device memory: lr / bc1, beta1, beta2, eps, coupled weight decay, 1 / sqrt(bc2), decay, spare -
 // decay = 1 - lr * weight_decay for a decoupled group (whose coupled weight decay is 0), 1.0f otherwise.  rows_host: n_groups x 8 floats,
 // passed to the refresh kernel by value.  The shadow-writing form walks items[] (the tensors some group owns, re-tiled; item_group[] runs
-// parallel to it); the flat form walks slices of at most M2F_ADAM_SLICE elements of one owned tensor (fp32 mode: no shadows).
-#define M2F_ADAM_SLICE 8192      // (M2F_ADAM_MAX_GROUPS: include/m2fnet_hip.h)
-struct AdamSlice { long long off; int n; int group; };
+// parallel to it); the flat form walks slices of at most M2F_PARAM_SLICE elements of one owned tensor (fp32 mode: no shadows).
+// ParamSlice: the one slice of the per-tensor kernels (rowops.hip, gradnorm.hip, tensor_stats.hip) - at most M2F_PARAM_SLICE
+// consecutive elements of ONE parameter tensor (`off`: its first element in the flat buffer; only the last slice of a tensor is short),
+// cut by the host from the parameter map (param_tables.hip), so the alignment pads between tensors belong to no slice.  tag: the owning
+// group for the grouped Adam and exchange kernels, the tensor's index for the statistics kernels; the norm kernel does not read it.
+#define M2F_PARAM_SLICE 8192     // (M2F_ADAM_MAX_GROUPS: include/m2fnet_hip.h)
+struct ParamSlice { long long off; int n; int tag; };
 hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host, int n_groups, hipStream_t stream);
 hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
                                             const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
                                             const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w,
                                             hipStream_t stream);
-hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
+hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const ParamSlice* slices, int s0, int s1,
                                   const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w, hipStream_t stream);
 // p[i] <-> ema[i] over the slices [s0, s1) (whole owned tensors; pads and unowned tensors are in no slice)
-hipError_t m2f_launch_ema_exchange(float* p, float* ema, const AdamSlice* slices, int s0, int s1, hipStream_t stream);
+hipError_t m2f_launch_ema_exchange(float* p, float* ema, const ParamSlice* slices, int s0, int s1, hipStream_t stream);
 
-// Global gradient norm + clip record (gradnorm.hip).  A slice = at most M2F_GRADNORM_SLICE consecutive elements of ONE parameter tensor
-// (`off`: its first element in the flat buffer; only the last slice of a tensor is short), cut by the host from the parameter map, so
-// the alignment pads between tensors belong to no slice.  Stage 1 writes partial[s], one float64 sum of squares per slice of [s0, s1)
+// Global gradient norm + clip record (gradnorm.hip), over the slices of every tensor (ParamSlice above; the same device array the
+// statistics walk).  Stage 1 writes partial[s], one float64 sum of squares per slice of [s0, s1)
 // (grid <= 0: min(2048, slices) workgroups; the value of partial[s] does not depend on the grid); the finalize launch sums
 // partial[0, n) in index order and writes record = (norm, coef, divisor, sqrt(sum of squares)) as fp32 - see the kernel.
-struct GradSlice { long long off; int n; int pad_; };
-#define M2F_GRADNORM_SLICE 8192
-hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const GradSlice* slices, int s0, int s1, double* partial, int grid,
+hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const ParamSlice* slices, int s0, int s1, double* partial, int grid,
                                  int nontemporal, hipStream_t stream);
 hipError_t m2f_launch_grad_norm_finalize(const double* partial, int n, const float* den_ptr, double max_norm, float* record,
                                          hipStream_t stream);
 
-// Per-tensor statistics and histograms of a flat buffer (tensor_stats.hip).  StatSlice = GradSlice's cut with the index of the slice's
+// Per-tensor statistics and histograms of a flat buffer (tensor_stats.hip).  slices: every tensor's ParamSlices, tag = the index of the slice's
 // tensor; tensor_begin[t] = first slice of tensor t, [n_tensors] = n_slices.  Pass 1 writes partial[s] (a slice's finite count is
 // n - nan - inf), the finalize launch the record header (M2F_TSTATS_HEADER doubles: den, n_tensors, bins, 0) and one row per tensor
 // (M2F_TSTATS_FIELDS doubles - numel, finite, nan, inf, zeros, min, max, sum, sumsq - then `bins` int64 counts, zeroed), pass 2 adds the
 // counts.  passes: bit 0 = pass 1 + finalize, bit 1 = pass 2 (which needs the rows of an earlier pass 1).  b (fp32, or null): x = a - b.
-struct StatSlice { long long off; int n; int tensor; };
 struct StatPartial { double sum, sumsq; float mn, mx; int nan, inf, zeros, pad_; };
 #define M2F_TSTATS_HEADER 4
 #define M2F_TSTATS_FIELDS 9
 #define M2F_TSTATS_MAX_BINS 256
-hipError_t m2f_launch_tensor_stats(const void* a, int a_is_bf16, const float* b, const StatSlice* slices, const int* tensor_begin,
+hipError_t m2f_launch_tensor_stats(const void* a, int a_is_bf16, const float* b, const ParamSlice* slices, const int* tensor_begin,
                                    int n_slices, int n_tensors, int bins, const float* den_ptr, StatPartial* partial, double* record,
                                    int grid, int nontemporal, int passes, hipStream_t stream);
 

@@ -692,22 +692,22 @@ __global__ __launch_bounds__(256) void m2f_adam_shadow_grouped_kernel(float* __r
 }
 
 // fp32 mode (no shadows to write): the flat kernel runs over pads and tensors alike and cannot know a group, so the grouped form
-// walks SLICES - at most M2F_ADAM_SLICE consecutive elements of one owned tensor (ops.h AdamSlice; cut by the host from the parameter
+// walks SLICES - at most M2F_PARAM_SLICE consecutive elements of one owned tensor (ops.h ParamSlice; cut by the host from the parameter
 // map as the gradient norm's are: pads belong to no slice) - each with its group's hyper row.  16-byte accesses, g / m / v nontemporal
 // as in m2f_adam_kernel; the last 1-3 elements of a tensor whose size is no multiple of 4 go one by one, nothing behind them is touched.
 template <bool G16, bool EMA>
 __global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, const AdamSlice* __restrict__ slices, int s0, int s1,
+                                                              float* __restrict__ v, const ParamSlice* __restrict__ slices, int s0, int s1,
                                                               const float* __restrict__ hyt, const float* __restrict__ gs_ptr,
                                                               float* __restrict__ ema, float ema_w) {
     const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
     const int tid = threadIdx.x;
     for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
-        const AdamSlice sl = slices[s];
-        const float* __restrict__ h = hyt + 8 * sl.group;
+        const ParamSlice sl = slices[s];
+        const float* __restrict__ h = hyt + 8 * sl.tag;
         const float lr_bc1 = h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4], inv_sqrt_bc2 = h[5], decay = h[6];
 #pragma unroll 2
-        for (int j = 0; j < M2F_ADAM_SLICE / 1024; ++j) {
+        for (int j = 0; j < M2F_PARAM_SLICE / 1024; ++j) {
             const int e = (j * 256 + tid) * 4;
             const long long o = sl.off + e;                         // tensor offsets are multiples of 64 elements: 16-byte aligned
             if (e + 4 <= sl.n) {
@@ -750,12 +750,12 @@ __global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict_
 // flat grouped kernel walks: pads and the tensors of no group belong to no slice and are not touched).  16-byte accesses; the last
 // 1-3 elements of a tensor whose size is no multiple of 4 go one by one.  Run twice, it restores both buffers bit for bit.
 __global__ __launch_bounds__(256) void m2f_ema_exchange_kernel(float* __restrict__ p, float* __restrict__ ema,
-                                                               const AdamSlice* __restrict__ slices, int s0, int s1) {
+                                                               const ParamSlice* __restrict__ slices, int s0, int s1) {
     const int tid = threadIdx.x;
     for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
-        const AdamSlice sl = slices[s];
+        const ParamSlice sl = slices[s];
 #pragma unroll 2
-        for (int j = 0; j < M2F_ADAM_SLICE / 1024; ++j) {
+        for (int j = 0; j < M2F_PARAM_SLICE / 1024; ++j) {
             const int e = (j * 256 + tid) * 4;
             const long long o = sl.off + e;
             if (e + 4 <= sl.n) {
@@ -1176,7 +1176,7 @@ hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf
     return hipGetLastError();
 }
 
-hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const AdamSlice* slices, int s0, int s1,
+hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const ParamSlice* slices, int s0, int s1,
                                   const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w, hipStream_t stream) {
     if (!p || !g || !m || !v || !slices || !hyper_table || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
     if (s1 == s0) return hipSuccess;
@@ -1190,7 +1190,7 @@ hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float*
     return hipGetLastError();
 }
 
-hipError_t m2f_launch_ema_exchange(float* p, float* ema, const AdamSlice* slices, int s0, int s1, hipStream_t stream) {
+hipError_t m2f_launch_ema_exchange(float* p, float* ema, const ParamSlice* slices, int s0, int s1, hipStream_t stream) {
     if (!p || !ema || !slices || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
     if (s1 == s0) return hipSuccess;
     hipLaunchKernelGGL(m2f_ema_exchange_kernel, dim3(s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8), dim3(256), 0, stream, p, ema, slices, s0, s1);

@@ -2,8 +2,8 @@
 // fp32 or bf16), or of the difference a - b of two fp32 buffers: what wandb.watch(model, log="all") logs per parameter tensor, taken
 // where the values live.  Three launches, no float atomics: every byte of the record is the same on every run and for every grid.
 //
-//   m2f_tstats_partial_kernel   pass 1: one StatPartial per SLICE (ops.h StatSlice: at most M2F_GRADNORM_SLICE consecutive elements of
-//                               ONE tensor - gradnorm.hip's cut, plus the tensor's index; the pads between tensors belong to no slice
+//   m2f_tstats_partial_kernel   pass 1: one StatPartial per SLICE (ops.h ParamSlice: at most M2F_PARAM_SLICE consecutive elements of
+//                               ONE tensor - the array gradnorm.hip walks; tag = the tensor's index; the pads between tensors belong to no slice
 //                               and are never read).  NaN / inf / zero counts, min and max of the finite values, their sum and sum of
 //                               squares in float64 (one FMA per element, as gradnorm.hip's square16).  A partial depends on its slice
 //                               alone: lane t takes the same elements in the same order whichever workgroup picks the slice up.
@@ -30,7 +30,7 @@
 
 namespace {
 
-constexpr int SLICE = M2F_GRADNORM_SLICE;
+constexpr int SLICE = M2F_PARAM_SLICE;
 constexpr int COPIES = 16;
 
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
@@ -72,7 +72,7 @@ __device__ __forceinline__ float value1(const void* a, const float* b, long long
 // round j at element (j * 256 + tid) * V.  A whole slice issues every load first; the short last slice of a tensor reads nothing at or
 // beyond element n (whole vectors while they fit, then single elements).  DIFF (fp32 only): x = a - b.
 template <bool A16, bool DIFF, bool NT, class F>
-__device__ __forceinline__ void slice_values(const void* a, const float* b, const StatSlice& sl, int tid, F& f) {
+__device__ __forceinline__ void slice_values(const void* a, const float* b, const ParamSlice& sl, int tid, F& f) {
     constexpr int V = A16 ? 8 : 4;
     constexpr int ROUNDS = SLICE / (256 * V);
     constexpr int ESZ = A16 ? 2 : 4;
@@ -110,13 +110,13 @@ struct WaveStat { double sum, sumsq; float mn, mx; int nan, inf, zeros; };
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------------------
 template <bool A16, bool DIFF, bool NT>
 __global__ __launch_bounds__(256) void m2f_tstats_partial_kernel(const void* __restrict__ a, const float* __restrict__ b,
-                                                                  const StatSlice* __restrict__ slices, int ns,
+                                                                  const ParamSlice* __restrict__ slices, int ns,
                                                                   StatPartial* __restrict__ partial) {
     __shared__ WaveStat red[2][4];
     const int tid = threadIdx.x;
     int par = 0;
     for (int s = (int)blockIdx.x; s < ns; s += (int)gridDim.x, par ^= 1) {
-        const StatSlice sl = slices[s];
+        const ParamSlice sl = slices[s];
         double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
         float mn = __builtin_inff(), mx = -__builtin_inff();
         int n_nan = 0, n_inf = 0, n_zero = 0;
@@ -169,7 +169,7 @@ __device__ __forceinline__ void fold(TensorStat& t, const TensorStat& u) {
     t.mn = fminf(t.mn, u.mn); t.mx = fmaxf(t.mx, u.mx);
 }
 
-__global__ __launch_bounds__(256) void m2f_tstats_finalize_kernel(const StatPartial* __restrict__ partial, const StatSlice* __restrict__ slices,
+__global__ __launch_bounds__(256) void m2f_tstats_finalize_kernel(const StatPartial* __restrict__ partial, const ParamSlice* __restrict__ slices,
                                                                    const int* __restrict__ tensor_begin, int n_tensors, int bins,
                                                                    const float* __restrict__ den_ptr, double* __restrict__ record) {
     __shared__ TensorStat red[4];
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void m2f_tstats_finalize_kernel(const StatPart
 // once per tensor the run touches, not once per slice.
 template <bool A16, bool DIFF, bool NT>
 __global__ __launch_bounds__(256) void m2f_tstats_hist_kernel(const void* __restrict__ a, const float* __restrict__ b,
-                                                               const StatSlice* __restrict__ slices, int ns, int per, int bins,
+                                                               const ParamSlice* __restrict__ slices, int ns, int per, int bins,
                                                                double* __restrict__ record) {
     __shared__ int h[256 * COPIES];
     const int tid = threadIdx.x;
@@ -249,10 +249,10 @@ __global__ __launch_bounds__(256) void m2f_tstats_hist_kernel(const void* __rest
         __syncthreads();
     };
     for (int s = s_begin; s < s_end; ++s) {
-        const StatSlice sl = slices[s];
-        if (sl.tensor != cur) {                                                // block-uniform
+        const ParamSlice sl = slices[s];
+        if (sl.tag != cur) {                                                // block-uniform
             if (cur >= 0 && live) flush(cur);
-            cur = sl.tensor;
+            cur = sl.tag;
             const double* row = record + M2F_TSTATS_HEADER + (size_t)cur * row_len;
             live = row[1] > 0.0;                                               // a tensor with no finite value: zero counts
             lo = (float)row[5];                                                // (fp32 values widened by the finalize launch: exact)
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void m2f_tstats_hist_kernel(const void* __rest
 
 }  // namespace
 
-hipError_t m2f_launch_tensor_stats(const void* a, int a_is_bf16, const float* b, const StatSlice* slices, const int* tensor_begin,
+hipError_t m2f_launch_tensor_stats(const void* a, int a_is_bf16, const float* b, const ParamSlice* slices, const int* tensor_begin,
                                    int n_slices, int n_tensors, int bins, const float* den_ptr, StatPartial* partial, double* record,
                                    int grid, int nontemporal, int passes, hipStream_t stream) {
     if (!a || !slices || !tensor_begin || !partial || !record || n_slices < 0 || n_tensors < 0 || bins < 2 || bins > M2F_TSTATS_MAX_BINS || !(passes & 3) ||

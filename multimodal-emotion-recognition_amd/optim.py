@@ -208,7 +208,7 @@ class FusedAdam(torch.optim.Optimizer):
                         self._ema[o: o + n].copy_(self._engine.flat[o: o + n])
 
     def _unique_params(self):
-        """The model's parameter tensors in parameter-map order (layout.param_specs == plan.hip::build_param_map; the engine's items)."""
+        """The model's parameter tensors in parameter-map order (layout.param_specs == param_tables.hip::build_param_map; the engine's items)."""
         named = dict(self.model.named_parameters(remove_duplicate=False))
         seen, out = set(), []
         for sp in param_specs(self.model.m2f_config)[0]:
@@ -229,11 +229,14 @@ class FusedAdam(torch.optim.Optimizer):
             self._tg_key = key
         return list(self._tg_list)
 
-    def _refresh_table(self, eng):
-        """This step's row of every group into the device table (one launch, values by value: no sync); -> the tensor -> group map."""
+    def _hyper_table(self, eng) -> torch.Tensor:
         if self._table is None or self._table.device != eng.flat.device:
             self._table = torch.zeros(MAX_GROUPS, 8, dtype=torch.float32, device=eng.flat.device)
-        runtime.adam_hyper_groups(self._table, [(float(g["lr"]), g["betas"], g["eps"], g["weight_decay"],
+        return self._table
+
+    def _refresh_table(self, eng):
+        """This step's row of every group into the device table (one launch, values by value: no sync); -> the tensor -> group map."""
+        runtime.adam_hyper_groups(self._hyper_table(eng), [(float(g["lr"]), g["betas"], g["eps"], g["weight_decay"],
                                                  g.get("decoupled_weight_decay", self.defaults.get("decoupled_weight_decay", False)), t)
                                                 for g, t in zip(self.param_groups, self._gsteps)])
         self.tensor_group_map()
@@ -536,10 +539,8 @@ class FusedAdam(torch.optim.Optimizer):
         # the in-launch form with groups (gemm_p8.h EPI 6): every matrix of the weight-gradient table must be owned - the launch holds
         # its gradient in registers and has nowhere else to put it; otherwise the two-launch branch
         tg = self.tensor_group_map()
-        if self._table is None or self._table.device != eng.flat.device:
-            self._table = torch.zeros(MAX_GROUPS, 8, dtype=torch.float32, device=eng.flat.device)
         key = ("grouped", tuple(tg), self._m.data_ptr(), self._v.data_ptr(), eng.flat.data_ptr(), eng.wshadow.data_ptr(),
-               self._table.data_ptr(), self.grad_scale.data_ptr() if self.grad_scale is not None else 0)
+               self._hyper_table(eng).data_ptr(), self.grad_scale.data_ptr() if self.grad_scale is not None else 0)
         if getattr(plan, "_fused_bad_key", None) == key:
             return False
         if getattr(plan, "_fused_key", None) != key:
@@ -593,15 +594,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._watch_after(watch, eng)
             return
         self._step += 1
-        scale = self.grad_scale
-        if self.max_grad_norm is not None or watch is not None:
-            if before_each is not None:
-                for i in range(len(ranges)):
-                    before_each(i)
-                before_each = None
-            if watch is not None:
-                self._watch_before(watch, eng, flat_grad)
-            scale = self._clip(eng, flat_grad)
+        scale, before_each = self._gather_then_clip(eng, flat_grad, len(ranges), before_each, watch)
         # bf16 mode with the model-wide parameter shadows: ranges that start and end at parameter tensors (dp.GradReducer aligns its
         # buckets that way) go through the shadow-writing kernel, so the next forward needs no parameter casts under data parallelism
         # either; anything else updates the parameters only and the next forward re-casts
@@ -623,9 +616,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._n_averaged += ema is not None
         self._watch_after(watch, eng)
         if shadowed:
-            covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
-            whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
-            if whole:
+            if self._cover_everything(ranges, n):
                 eng.mark_shadows_fresh()
             else:
                 eng.invalidate_shadows()
@@ -637,15 +628,7 @@ class FusedAdam(torch.optim.Optimizer):
                 raise ValueError(f"FusedAdam.step_ranges: the range [{lo}, {hi}) cuts a parameter tensor; an optimizer with parameter "
                                  "groups / decoupled weight decay takes ranges of whole tensors only (dp.GradReducer's buckets are)")
         self._gsteps = [t + 1 for t in self._gsteps]
-        scale = self.grad_scale
-        if self.max_grad_norm is not None or watch is not None:
-            if before_each is not None:
-                for i in range(len(ranges)):
-                    before_each(i)
-                before_each = None
-            if watch is not None:
-                self._watch_before(watch, eng, flat_grad)
-            scale = self._clip(eng, flat_grad)
+        scale, before_each = self._gather_then_clip(eng, flat_grad, len(ranges), before_each, watch)
         tg = self._refresh_table(eng)
         for i, (lo, hi) in enumerate(ranges):
             if before_each is not None:
@@ -654,12 +637,28 @@ class FusedAdam(torch.optim.Optimizer):
                 runtime.adam_step_grouped(eng.cfg, eng.flat, flat_grad, self._m, self._v, eng.wshadow, tg, self._table, scale,
                                           first=lo, end=(-1 if hi >= n else hi), ema=ema, ema_w=ema_w)
         if eng.wshadow is not None:
-            covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
-            whole = bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
-            if not whole:
+            if not self._cover_everything(ranges, n):
                 eng.invalidate_shadows()
             elif self._owns_everything():
                 eng.mark_shadows_fresh()
+
+    def _gather_then_clip(self, eng, flat_grad, n_ranges, before_each, watch):
+        """-> (the divisor of this step's updates, the `before_each` the range loop still has to call).  With ``max_grad_norm`` or a due
+        watch every range's `before_each` runs first, then the watch's collections and the norm over the whole buffer."""
+        if self.max_grad_norm is None and watch is None:
+            return self.grad_scale, before_each
+        if before_each is not None:
+            for i in range(n_ranges):
+                before_each(i)
+        if watch is not None:
+            self._watch_before(watch, eng, flat_grad)
+        return self._clip(eng, flat_grad), None
+
+    @staticmethod
+    def _cover_everything(ranges, n) -> bool:
+        """The non-empty ranges, put in order, tile [0, n) without a gap."""
+        covered = sorted((lo, hi) for lo, hi in ranges if hi > lo)
+        return bool(covered) and covered[0][0] == 0 and covered[-1][1] >= n and all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
 
     def _tensor_starts(self, eng):
         if getattr(self, "_starts_of", None) is not eng:

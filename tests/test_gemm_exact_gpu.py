@@ -634,7 +634,7 @@ def test_parameter_shadow_cast_rounds_ties_to_even_and_overflows_to_inf():
     torch.cuda.synchronize()
     assert torch.equal(got.view(torch.int32), p.view(torch.int32))
     r64, p8 = (lambda n: (n + 63) // 64 * 64), (lambda n: (n + 7) // 8 * 8)
-    run, n = 0, 0                                              # the shadow layout of csrc/plan.hip::pm_add (tests/test_shared_shadows_gpu.py)
+    run, n = 0, 0                                              # the shadow layout of csrc/param_tables.hip::pm_add (tests/test_shared_shadows_gpu.py)
     for sp in specs:
         if sp.alias_of or len(sp.shape) != 2:
             continue

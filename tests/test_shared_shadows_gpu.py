@@ -24,7 +24,7 @@ def _model(cfg, sd=None, precision="bf16"):
 
 
 def _shadow_offsets(c):
-    """(spec, soff, soff_t) of every 2-D parameter: the layout of csrc/plan.hip::pm_add."""
+    """(spec, soff, soff_t) of every 2-D parameter: the layout of csrc/param_tables.hip::pm_add."""
     specs, _ = layout.param_specs(c)
     out, run = [], 0
     r64 = lambda n: (n + 63) // 64 * 64
