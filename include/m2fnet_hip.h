@@ -553,6 +553,22 @@ int m2f_layernorm_fwd(int T, int d, const float* x, const float* gamma, const fl
 int m2f_layernorm_bwd(int T, int d, const float* x, const float* gamma, const float* stats, const float* dy,
                       const float* extra, float* dx, float* partial, float* dgamma, float* dbeta,
                       m2f_stream_t stream);
+/* The row-wise kernels with a dropout site, as the train plans launch them (kernel-level tests; no kernel of their own).  Rows have
+ * d elements and stride ld (0 = d); the keep index of element (row, col) is row * d + col, whatever ld.  drop_p > 0 and rng_state
+ * (4 device uint32) are needed when a site is non-zero.
+ * m2f_layernorm_fwd_drop: out = dropout_site((res ? res : 0) + LayerNorm(x)) - the pre-projection dropout on the last encoder stack's
+ * final norm. */
+int m2f_layernorm_fwd_drop(int T, int d, int ld, const float* x, const float* gamma, const float* beta, const float* res, float* out,
+                           float* stats, float eps, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream);
+/* m2f_layernorm_bwd_masked: m2f_layernorm_bwd with the second output dx_masked = LNbwd(dy) * keep(drop_site2) / (1 - p) (nullable;
+ * without `extra`: what flows on through dropout1 / dropout2), dx = LNbwd(dy) (+ extra) as ever. */
+int m2f_layernorm_bwd_masked(int T, int d, int ld, const float* x, const float* gamma, const float* stats, const float* dy,
+                             const float* extra, float* dx, float* dx_masked, float* partial, float* dgamma, float* dbeta,
+                             uint32_t drop_site2, float drop_p, const uint32_t* rng_state, m2f_stream_t stream);
+/* m2f_dropout_rows: in place x[t, c] *= keep(site, t * d + c) / (1 - p) for c < d; x2 (nullable): a second buffer of the same shape
+ * with its own site in the same launch (the two modalities' post-projection gradients). */
+int m2f_dropout_rows(float* x, float* x2, int T, int d, int ld, uint32_t site, uint32_t site2, float drop_p, const uint32_t* rng_state,
+                     m2f_stream_t stream);
 /* CrossEntropyLoss(ignore_index=-1, label_smoothing[, weight]) + gradient; loss_out[0..2] = loss, den, num. */
 int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, const float* class_w,
                       float label_smoothing, int normalise, float* loss_terms, float* dlogits, float* loss_out,

@@ -199,6 +199,50 @@ def layernorm_bwd(x, gamma, stats, dy, extra: Optional[torch.Tensor] = None):
     return dx, dg, db
 
 
+def layernorm_fwd_drop(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, res: Optional[torch.Tensor] = None,
+                       eps: float = 1e-5, drop_site: int = 0, drop_p: float = 0.0, rng: Optional[torch.Tensor] = None):
+    """dropout_site((res ? res : 0) + LayerNorm(x)) on [T, d] rows that may be column blocks of wider buffers (x, res and the
+    result share one row stride; the result has x's).  Returns (out, stats)."""
+    runtime.require_gpu()
+    T, d = x.shape
+    ld = _ld(x)
+    assert res is None or _ld(res) == ld
+    out = torch.zeros(T, ld, dtype=torch.float32, device=x.device)[:, :d]
+    stats = torch.empty(T, 2, dtype=torch.float32, device=x.device)
+    check(lib().m2f_layernorm_fwd_drop(T, d, ld, ptr(x), ptr(gamma), ptr(beta), ptr(res), ptr(out), ptr(stats), eps, drop_site,
+                                       drop_p, ptr(rng), stream_ptr()), "m2f_layernorm_fwd_drop")
+    return out, stats
+
+
+def layernorm_bwd_masked(x, gamma, stats, dy, extra: Optional[torch.Tensor] = None, drop_site2: int = 0, drop_p: float = 0.0,
+                         rng: Optional[torch.Tensor] = None):
+    """LayerNorm backward with its second output: (dx = LNbwd(dy) (+ extra), dx_masked = LNbwd(dy) * keep(site2) / (1 - p),
+    dgamma, dbeta); x, dy, extra share one row stride, dx and dx_masked get it too."""
+    runtime.require_gpu()
+    T, d = x.shape
+    ld = _ld(x)
+    assert _ld(dy) == ld and (extra is None or _ld(extra) == ld)
+    dx = torch.zeros(T, ld, dtype=torch.float32, device=x.device)[:, :d]
+    dxm = torch.zeros(T, ld, dtype=torch.float32, device=x.device)[:, :d]
+    partial = torch.empty((T + 3) // 4, 2, d, dtype=torch.float32, device=x.device)
+    dg = torch.empty(d, dtype=torch.float32, device=x.device)
+    db = torch.empty(d, dtype=torch.float32, device=x.device)
+    check(lib().m2f_layernorm_bwd_masked(T, d, ld, ptr(x), ptr(gamma), ptr(stats), ptr(dy), ptr(extra), ptr(dx), ptr(dxm),
+                                         ptr(partial), ptr(dg), ptr(db), drop_site2, drop_p, ptr(rng), stream_ptr()),
+          "m2f_layernorm_bwd_masked")
+    return dx, dxm, dg, db
+
+
+def dropout_rows(x: torch.Tensor, site: int, drop_p: float, rng: torch.Tensor, x2: Optional[torch.Tensor] = None,
+                 site2: int = 0) -> None:
+    """In place x[t, c] *= keep(site, t * d + c) / (1 - p) on [T, d] rows (stride ld >= d); x2: a second buffer of the same shape
+    and stride with its own site, same launch."""
+    runtime.require_gpu()
+    T, d = x.shape
+    assert x2 is None or (x2.shape == x.shape and _ld(x2) == _ld(x))
+    check(lib().m2f_dropout_rows(ptr(x), ptr(x2), T, d, _ld(x), site, site2, drop_p, ptr(rng), stream_ptr()), "m2f_dropout_rows")
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None,
                   label_smoothing: float = 0.1, normalise: bool = True):
     """logits [T, C], labels int64 [T] (-1 = ignore) -> (loss_out[4] = loss, den, num, -; dlogits [T, C])."""

@@ -164,6 +164,11 @@ SIGNATURES = {
                                   c_void_p]),
     "m2f_layernorm_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
+    "m2f_layernorm_fwd_drop": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_uint32,
+                                       c_float, c_void_p, c_void_p]),
+    "m2f_layernorm_bwd_masked": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
+    "m2f_dropout_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_cross_entropy": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,

@@ -63,11 +63,13 @@ def layer_norm(x: Tensor, g: Tensor, b: Tensor, eps: float = LN_EPS) -> Tensor:
 
 
 def attention(q: Tensor, k: Tensor, v: Tensor, key_pad: Tensor, n_head: int,
-              return_probs: bool = False):
+              return_probs: bool = False, drop=None, name: str = ""):
     """Multi-head scaled-dot-product attention on [B, L, E] tensors.
 
     key_pad: bool [B, L], True = padded key (gets -inf before softmax), the
     key_padding_mask / src_key_padding_mask convention of src/model.py:14,107.
+    drop (see `forward`): applied to the softmax probabilities [B, H, L, L] under `name`, where nn.MultiheadAttention applies its
+    dropout; the returned probabilities are the ones before it.
     """
     B, L, E = q.shape
     hd = E // n_head
@@ -79,7 +81,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, key_pad: Tensor, n_head: int,
     s = s - s.max(dim=-1, keepdim=True).values
     p = torch.exp(s)
     p = p / p.sum(dim=-1, keepdim=True)
-    o = (p @ vh).permute(0, 2, 1, 3).reshape(B, L, E)
+    o = ((p if drop is None else drop(name, p)) @ vh).permute(0, 2, 1, 3).reshape(B, L, E)
     return (o, p) if return_probs else o
 
 
@@ -190,7 +192,7 @@ class _Attn16(torch.autograd.Function):
     """Dialogue attention as attention.hip computes it in bf16 mode (see Bf16Rounding); [B, L, E] in and out."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_pad, n_head, rnd):
+    def forward(ctx, q, k, v, key_pad, n_head, rnd, keep=None):
         B, L, E = q.shape
         hd = E // n_head
         W, Lp = (hd + 15) // 16 * 16, 16 * ((L + 15) // 16)
@@ -204,8 +206,11 @@ class _Attn16(torch.autograd.Function):
         s = s - s.max(dim=-1, keepdim=True).values
         p = torch.exp(s)
         p = p / p.sum(dim=-1, keepdim=True)
-        o = p @ rnd.r(vh, rnd.attn_v and fast)
+        # keep (dropout on the probabilities: mask / (1 - p), [B, H, L, L]): P stays fp32 in the kernels, the dropped P feeds P V
+        # (attention.hip:176), and in the backward dV = (P keep)^T dO, dP = (dO V^T) keep (attention.hip:355,407)
+        o = (p if keep is None else p * keep) @ rnd.r(vh, rnd.attn_v and fast)
         ctx.save_for_backward(qh, kh, vh, p, o)
+        ctx.keep = keep
         ctx.rnd, ctx.scale, ctx.shape = rnd, scale, (B, L, n_head, hd)
         return o.permute(0, 2, 1, 3).reshape(B, L, E)
 
@@ -216,67 +221,83 @@ class _Attn16(torch.autograd.Function):
         B, L, H, hd = ctx.shape
         doh = do.reshape(B, L, H, hd).permute(0, 2, 1, 3)
         dp = r.r(doh, r.attn_do) @ r.r(vh, r.attn_v).transpose(-1, -2)           # bit 1: always rounded
+        if ctx.keep is not None:
+            dp = dp * ctx.keep
         dor = r.r(doh, r.attn_do and f)
         delta = (dor * r.r(o, r.attn_o and f)).sum(dim=-1, keepdim=True)
         ds = p * (dp - delta) * ctx.scale
         dq = ds @ r.r(kh, r.attn_k and f)
         dk = ds.transpose(-1, -2) @ r.r(qh, r.attn_q and f)
-        dv = p.transpose(-1, -2) @ dor
+        dv = (p if ctx.keep is None else p * ctx.keep).transpose(-1, -2) @ dor
         back = lambda t: t.permute(0, 2, 1, 3).reshape(B, L, H * hd)
-        return back(dq), back(dk), back(dv), None, None, None
+        return back(dq), back(dk), back(dv), None, None, None, None
 
 
 def _lin(x: Tensor, w: Tensor, b: Optional[Tensor], rnd: Optional[Bf16Rounding], skinny: bool = False) -> Tensor:
     return linear(x, w, b) if rnd is None else _Linear16.apply(x, w, b, rnd, skinny)
 
 
-def _attn(q, k, v, key_pad, n_head, rnd: Optional[Bf16Rounding], return_probs: bool = False):
+def _attn(q, k, v, key_pad, n_head, rnd: Optional[Bf16Rounding], return_probs: bool = False, drop=None, name: str = ""):
     if rnd is None:
-        return attention(q, k, v, key_pad, n_head, return_probs)
+        return attention(q, k, v, key_pad, n_head, return_probs, drop, name)
     if not rnd.attn or q.shape[1] > 64:
-        return attention(q, k, v, key_pad, n_head, return_probs)
-    o = _Attn16.apply(q, k, v, key_pad, n_head, rnd)
+        return attention(q, k, v, key_pad, n_head, return_probs, drop, name)
+    keep = None
+    if drop is not None:          # the hook is a mask times a scale: its image of ones is that factor
+        B, L, _ = q.shape
+        keep = drop(name, torch.ones(B, n_head, L, L, dtype=q.dtype))
+    o = _Attn16.apply(q, k, v, key_pad, n_head, rnd, keep)
     return (o, None) if return_probs else o
+
+
+def _drop(drop, name: str, x: Tensor) -> Tensor:
+    return x if drop is None else drop(name, x)
 
 
 # --------------------------------------------------------------------------------------
 # blocks
 # --------------------------------------------------------------------------------------
 def encoder_layer(x: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor, n_head: int,
-                  rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
-    """Post-LN TransformerEncoderLayer (norm_first=False, ReLU), dropout = identity.
+                  rnd: "Optional[Bf16Rounding]" = None, drop=None) -> Tensor:
+    """Post-LN TransformerEncoderLayer (norm_first=False, ReLU), dropout = identity unless `drop` is given.
 
     x <- LN1(x + SA(x)); x <- LN2(x + W2 relu(W1 x + b1) + b2)   
+    drop (see `forward`), where nn.TransformerEncoderLayer applies its four dropouts: `<pre>attn` on the softmax probabilities,
+    `<pre>dropout1` after out_proj before the residual, `<pre>ff` after relu(linear1), `<pre>dropout2` after linear2 before the
+    residual.  In bf16 mode the masks act on the fp32 results of the GEMM epilogues (bias, ReLU, mask, residual in that order),
+    i.e. before the value is rounded as the next GEMM's operand - which is where these lines put them.
     """
     E = x.shape[-1]
     qkv = _lin(x, sd[pre + "self_attn.in_proj_weight"], sd[pre + "self_attn.in_proj_bias"], rnd)
     q, k, v = qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:]
-    a = _attn(q, k, v, key_pad, n_head, rnd)
-    a = _lin(a, sd[pre + "self_attn.out_proj.weight"], sd[pre + "self_attn.out_proj.bias"], rnd)
+    a = _attn(q, k, v, key_pad, n_head, rnd, drop=drop, name=pre + "attn")
+    a = _drop(drop, pre + "dropout1", _lin(a, sd[pre + "self_attn.out_proj.weight"], sd[pre + "self_attn.out_proj.bias"], rnd))
     x = layer_norm(x + a, sd[pre + "norm1.weight"], sd[pre + "norm1.bias"])
-    h = torch.relu(_lin(x, sd[pre + "linear1.weight"], sd[pre + "linear1.bias"], rnd))
-    h = _lin(h, sd[pre + "linear2.weight"], sd[pre + "linear2.bias"], rnd)
+    h = _drop(drop, pre + "ff", torch.relu(_lin(x, sd[pre + "linear1.weight"], sd[pre + "linear1.bias"], rnd)))
+    h = _drop(drop, pre + "dropout2", _lin(h, sd[pre + "linear2.weight"], sd[pre + "linear2.bias"], rnd))
     return layer_norm(x + h, sd[pre + "norm2.weight"], sd[pre + "norm2.bias"])
 
 
 def encoder_stack(x: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor, n_head: int,
-                  n_layers: int, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
+                  n_layers: int, rnd: "Optional[Bf16Rounding]" = None, drop=None) -> Tensor:
     """nn.TransformerEncoder(layer, num_layers, norm): layers then the final LayerNorm."""
     for l in range(n_layers):
-        x = encoder_layer(x, sd, f"{pre}layers.{l}.", key_pad, n_head, rnd)
+        x = encoder_layer(x, sd, f"{pre}layers.{l}.", key_pad, n_head, rnd, drop)
     return layer_norm(x, sd[pre + "norm.weight"], sd[pre + "norm.bias"])
 
 
 def fam_layer(text: Tensor, audio: Tensor, sd: Dict[str, Tensor], pre: str, key_pad: Tensor,
-              n_head: int, inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
-    """FusionAttentionModule.forward (src/model.py:13-20): Q = V = text, K = audio."""
+              n_head: int, inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None, drop=None) -> Tensor:
+    """FusionAttentionModule.forward (src/model.py:13-20): Q = V = text, K = audio.
+    drop (see `forward`): `<pre>attn` on the softmax probabilities (nn.MultiheadAttention's own dropout); the dropout BEHIND the
+    layer (src/model.py:131) is applied by `forward` under `<pre>out`."""
     E = text.shape[-1]
     w = sd[pre + "multihead_attention.in_proj_weight"]
     b = sd[pre + "multihead_attention.in_proj_bias"]
     q = _lin(text, w[:E], b[:E], rnd)
     k = _lin(audio, w[E:2 * E], b[E:2 * E], rnd)
     v = _lin(text, w[2 * E:], b[2 * E:], rnd)
-    a, p = _attn(q, k, v, key_pad, n_head, rnd, return_probs=True)
+    a, p = _attn(q, k, v, key_pad, n_head, rnd, return_probs=True, drop=drop, name=pre + "attn")
     x = _lin(a, sd[pre + "multihead_attention.out_proj.weight"],
              sd[pre + "multihead_attention.out_proj.bias"], rnd)
     y = torch.relu(_lin(torch.relu(torch.cat((x, text), dim=2)),
@@ -287,9 +308,16 @@ def fam_layer(text: Tensor, audio: Tensor, sd: Dict[str, Tensor], pre: str, key_
 
 
 def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Tensor,
-            inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None) -> Tensor:
-    """M2FNet.forward (src/model.py:102-145) with every dropout as identity
-    (eval mode, or train mode with model.dropout = 0.0).  rnd: see Bf16Rounding (None = no rounding).
+            inter: Optional[dict] = None, rnd: "Optional[Bf16Rounding]" = None, drop=None) -> Tensor:
+    """M2FNet.forward (src/model.py:102-145).  Without `drop` every dropout is the identity (eval mode, or train mode with
+    model.dropout = 0.0); with it, train mode under the caller's masks.  rnd: see Bf16Rounding (None = no rounding).
+
+    drop: None (the default), or a callable (name, tensor) -> tensor standing for train-mode dropout
+    with masks the CALLER supplies - an element-wise factor keep / (1 - p); this file knows nothing about where masks come from.
+    It is called wherever the reference applies a dropout, under these names: `<stack>.layers.<l>.{attn, dropout1, ff, dropout2}`
+    (encoder_layer), `{audio, text}.pre_proj` / `.post_proj` before and after each projection (src/model.py:111-113,123-125),
+    `fusion_layers.<i>.attn` and `fusion_layers.<i>.out` (after every fusion layer, :131), `classifier` after the head's last
+    ReLU (:98).
 
     text [B,L,d_t], audio [B,L,d_a] fp32; key_pad bool [B,L] (True = pad) -> logits [B,L,C].
     """
@@ -303,13 +331,15 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
     if a_on:
         for e in range(_get(A, "n_transformers")):                                 # src/model.py:106-107
             audio = audio + encoder_stack(audio, sd, f"audio_encoders.{e}.", key_pad,
-                                          _get(A, "n_head"), _get(A, "n_encoder_layers"), rnd)
-        audio = _lin(audio, sd["audio_proj.weight"], sd["audio_proj.bias"], rnd)      # :111-113
+                                          _get(A, "n_head"), _get(A, "n_encoder_layers"), rnd, drop)
+        audio = _drop(drop, "audio.post_proj",
+                      _lin(_drop(drop, "audio.pre_proj", audio), sd["audio_proj.weight"], sd["audio_proj.bias"], rnd))      # :111-113
     if t_on:
         for e in range(_get(Tx, "n_transformers")):                                # :118-119
             text = text + encoder_stack(text, sd, f"text_encoders.{e}.", key_pad,
-                                        _get(Tx, "n_head"), _get(Tx, "n_encoder_layers"), rnd)
-        text = _lin(text, sd["text_proj.weight"], sd["text_proj.bias"], rnd)          # :123-125
+                                        _get(Tx, "n_head"), _get(Tx, "n_encoder_layers"), rnd, drop)
+        text = _drop(drop, "text.post_proj",
+                     _lin(_drop(drop, "text.pre_proj", text), sd["text_proj.weight"], sd["text_proj.bias"], rnd))          # :123-125
     if inter is not None:
         inter["audio_proj"] = audio if a_on else None
         inter["text_proj"] = text if t_on else None
@@ -317,7 +347,8 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
     if f_on:
         for i in range(_get(F, "n_layers")):                                       # :129-131
             li = {} if inter is not None else None
-            text = fam_layer(text, audio, sd, f"fusion_layers.{i}.", key_pad, _get(F, "n_head"), li, rnd)
+            text = _drop(drop, f"fusion_layers.{i}.out",
+                         fam_layer(text, audio, sd, f"fusion_layers.{i}.", key_pad, _get(F, "n_head"), li, rnd, drop))
             if inter is not None:
                 inter[f"fam{i}"] = li
         x = torch.cat((audio, text), dim=2)                                        # :134  (audio, text)
@@ -333,7 +364,8 @@ def forward(sd: Dict[str, Tensor], cfg, text: Tensor, audio: Tensor, key_pad: Te
         idx += 2
         x = _lin(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"], rnd)
     idx += 3
-    return _lin(torch.relu(x), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"], rnd, skinny=True)
+    return _lin(_drop(drop, "classifier", torch.relu(x)), sd[f"output_layer.{idx}.weight"], sd[f"output_layer.{idx}.bias"], rnd,
+                skinny=True)
 
 
 # --------------------------------------------------------------------------------------
@@ -425,8 +457,11 @@ def collate(dialogues: Sequence[Dict[str, Tensor]]) -> Dict[str, Tensor]:
 
 
 def loss_and_grads(sd: Dict[str, Tensor], cfg, text, audio, key_pad, target,
-                   class_weight: Optional[Tensor] = None, rounding: "Optional[Bf16Rounding]" = None):
+                   class_weight: Optional[Tensor] = None, rounding: "Optional[Bf16Rounding]" = None, drop=None,
+                   input_grads: bool = False):
     """forward + criterion + backward; returns (logits, loss, {name: grad}) for unique tensors.
+    drop: the dropout hook of `forward`.  input_grads: the dict also holds d loss / d text and d loss / d audio under "text" / "audio".
+    Without `rounding` the arithmetic runs in the dtype of `sd` and the inputs (float64 tensors give a float64 reference).
 
     rounding (a Bf16Rounding): emulate bf16 mode - everything in float64, rounded to bf16 where the kernels round; the
     results are float64.  None (the default): the plain oracle."""
@@ -440,8 +475,13 @@ def loss_and_grads(sd: Dict[str, Tensor], cfg, text, audio, key_pad, target,
             t = v.detach().clone() if rounding is None else v.detach().double()
             leaves[id(v)] = t.requires_grad_(True)
         sd2[k] = leaves[id(v)]
-    logits = forward(sd2, cfg, text, audio, key_pad, rnd=rounding)
+    if input_grads:
+        text, audio = text.detach().clone().requires_grad_(True), audio.detach().clone().requires_grad_(True)
+    logits = forward(sd2, cfg, text, audio, key_pad, rnd=rounding, drop=drop)
     loss = cross_entropy(logits, target, class_weight)
     loss.backward()
     grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in sd2.items()}
+    if input_grads:
+        grads["text"] = text.grad if text.grad is not None else torch.zeros_like(text)
+        grads["audio"] = audio.grad if audio.grad is not None else torch.zeros_like(audio)
     return logits.detach(), loss.detach(), grads
