@@ -8,8 +8,10 @@
 // One workgroup of four wavefronts owns one (dialogue, head): the sequence is the utterances of a dialogue
 // (L <= 64), so the whole L x L problem fits one wave's registers.  Q/K/V (and dO, O in backward) tiles of
 // the head are staged in LDS by all 256 threads (row stride = 2 mod 4 floats -> conflict-free MFMA fragment
-// reads; every operand is in flight before the first one is committed, so the fetch costs one memory round
-// trip), QK^T and PV run on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32, the softmax runs in registers with
+// reads; every operand - and with them the keys' pad flags and the dropout state, as range-checked buffer
+// loads (common.h) - is in flight before the first one is committed, so the fetch costs one memory round
+// trip; packed launches add the one for cu[] in front of it, which the addresses depend on), QK^T and PV
+// run on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32, the softmax runs in registers with
 // wavefront shuffles.  S^T = K Q^T is computed so the probability tile is already laid out as the A operand of
 // the PV product (accumulator as next operand, no LDS round trip).  Every wave evaluates the (tiny) score /
 // dS tiles itself and the waves split the 16-column output tiles of O / dQ / dK / dV between them: the kernel
@@ -83,11 +85,17 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     // padded layout: dialogue b owns rows b*LM .. +LM-1, pads flagged in key_pad; packed layout: rows cu[b] .. cu[b+1]-1, all valid
     int L = LM;
     size_t tok0 = (size_t)b * LM;
-    if (ab.cu) { const int c0 = ab.cu[b]; L = ab.cu[b + 1] - c0; tok0 = (size_t)c0; }
+    int tail0 = 0;                                            // packed layout: cu[B], the first token row that belongs to no dialogue
+    if (ab.cu) { const int c0 = ab.cu[b]; L = ab.cu[b + 1] - c0; tok0 = (size_t)c0; tail0 = ab.cu[ab.B]; }
     const float* qg = P.q + tok0 * P.ldq + h * hd;
     const float* kg = P.k + tok0 * P.ldk + h * hd;
     const float* vg = P.v + tok0 * P.ldv + h * hd;
-    const unsigned char kpad = ab.cu ? (unsigned char)0 : ab.key_pad[tok0 + (lane < L ? lane : 0)];
+    // The pad flags and the dropout state travel WITH the slabs: range-checked loads (common.h) that need no guard - a packed
+    // launch reads no flag (0 bytes: every key valid), a launch without a site no state.  As guarded plain loads each was a
+    // memory round trip of its own, the flags' in front of the slabs and the state's behind the barrier.
+    const unsigned char kpad = __builtin_amdgcn_raw_buffer_load_b8(
+        m2f_make_rsrc(ab.cu ? nullptr : ab.key_pad + (size_t)b * LM, (uint32_t)LM), lane < L ? lane : 0, 0, 0);
+    u32x4 rw = m2f_rng_words(ab.rng);
     constexpr int NV = 2 * NT;                                // float4 per thread and slab: covers W <= 128
     if (slab_fast_ok<NV>(qg, P.ldq, hd, Lp, W) && slab_fast_ok<NV>(kg, P.ldk, hd, Lp, W) && slab_fast_ok<NV>(vg, P.ldv, hd, Lp, W)) {
         SlabGeom<NV> G;
@@ -115,7 +123,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     const int ksteps = (hd + 3) >> 2;
     const uint32_t site = P.drop_site;
     uint32_t key = 0;
-    if (site) key = m2f_site_key(ab.rng, site);
+    m2f_rng_words_arrived(rw);                              // (issued in front of the slabs, which have been waited for)
+    if (site) key = m2f_site_key_words(rw, site);
     float* probs = P.probs + (size_t)bh * Lp * Lp;
     uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
     const bool w32 = !(P.no_f32 && out16);                  // (no fp32 reader: the bf16 shadow is the result)
@@ -200,7 +209,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     // packed layout: the token rows behind the last dialogue (cu[B] .. T-1) belong to nobody; a plan is re-used for batches of
     // other lengths, so they are written (zeros) by the last dialogue's workgroups - head h its own columns
     if (ab.cu && b == ab.B - 1) {
-        for (int r = ab.cu[ab.B] + wv; r < ab.T; r += NWAVE)
+        for (int r = tail0 + wv; r < ab.T; r += NWAVE)
             for (int c = lane; c < hd; c += 64) {
                 const size_t idx = (size_t)r * P.ldo + h * hd + c;
                 if (w32) P.out[idx] = 0.f;
@@ -233,7 +242,9 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
     float* dpart = delta + Lp;         // [NV][NTHR] (one-round-trip path: per-thread pieces of delta, summed per row in a fixed order)
     int L = LM;                                            // (packed layout: see the forward kernel)
     size_t tok0 = (size_t)b * LM;
-    if (ab.cu) { const int c0 = ab.cu[b]; L = ab.cu[b + 1] - c0; tok0 = (size_t)c0; }
+    int tail0 = 0;
+    if (ab.cu) { const int c0 = ab.cu[b]; L = ab.cu[b + 1] - c0; tok0 = (size_t)c0; tail0 = ab.cu[ab.B]; }
+    u32x4 rw = m2f_rng_words(ab.rng);                      // the dropout state, in flight with the slabs (see the forward kernel)
     const float* qg = P.q + tok0 * P.ldq + h * hd;
     const float* kg = P.k + tok0 * P.ldk + h * hd;
     const float* vg = P.v + tok0 * P.ldv + h * hd;
@@ -319,7 +330,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
     const int ksteps = (hd + 3) >> 2;
     const uint32_t site = P.drop_site;
     uint32_t key = 0;
-    if (site) key = m2f_site_key(ab.rng, site);
+    m2f_rng_words_arrived(rw);                              // (issued in front of the slabs, which have been waited for)
+    if (site) key = m2f_site_key_words(rw, site);
     uint16_t* dq16 = m2f_shadow_of(ab.sh, P.dq);
     uint16_t* dk16 = m2f_shadow_of(ab.sh, P.dk);
     uint16_t* dv16 = m2f_shadow_of(ab.sh, P.dv);
@@ -440,7 +452,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
     // packed layout: zero gradients for the token rows behind the last dialogue (see the forward kernel) - the input-gradient
     // and weight-gradient GEMMs read every row of these buffers
     if (ab.cu && b == ab.B - 1) {
-        for (int r = ab.cu[ab.B] + wv; r < ab.T; r += NWAVE)
+        for (int r = tail0 + wv; r < ab.T; r += NWAVE)
             for (int c = lane; c < hd; c += 64) {
                 const size_t iq = (size_t)r * P.lddq + h * hd + c, ik = (size_t)r * P.lddk + h * hd + c, iv = (size_t)r * P.lddv + h * hd + c;
                 if (w32) { P.dq[iq] = 0.f; P.dk[ik] = 0.f; P.dv[iv] = 0.f; }

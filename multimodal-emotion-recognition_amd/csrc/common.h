@@ -42,18 +42,46 @@ __device__ __forceinline__ uint32_t m2f_mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
-__device__ __forceinline__ uint32_t m2f_site_key(const uint32_t* __restrict__ rng, uint32_t site) {
-    uint32_t k = m2f_mix32(rng[0] ^ 0x9e3779b9U);
-    k = m2f_mix32(k ^ rng[1]);
-    k = m2f_mix32(k + rng[2] * 0x85ebca6bU);
-    k = m2f_mix32(k ^ (rng[3] + site * 0xc2b2ae35U));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// the site key from the four state words already in registers (m2f_rng_words below): the one statement of the key's arithmetic
+__device__ __forceinline__ uint32_t m2f_site_key_words(u32x4 w, uint32_t site) {
+    uint32_t k = m2f_mix32(w[0] ^ 0x9e3779b9U);
+    k = m2f_mix32(k ^ w[1]);
+    k = m2f_mix32(k + w[2] * 0x85ebca6bU);
+    k = m2f_mix32(k ^ (w[3] + site * 0xc2b2ae35U));
     return k;
+}
+__device__ __forceinline__ uint32_t m2f_site_key(const uint32_t* __restrict__ rng, uint32_t site) {
+    const u32x4 w = {rng[0], rng[1], rng[2], rng[3]};
+    return m2f_site_key_words(w, site);
 }
 __device__ __forceinline__ bool m2f_keep(uint32_t key, uint32_t idx, uint32_t thresh) {
     uint32_t h = m2f_mix32(idx * 0x9E3779B1U + key);
     h = m2f_mix32(h ^ (key >> 7) ^ 0x68e31da4U);
     return h >= thresh;       // P(keep) = 1 - thresh / 2^32
 }
+
+// ---- range-checked buffer loads ------------------------------------------------------------------
+// A load the row-wise kernels may or may not need (a nullable operand, a chunk behind the row's end, the dropout state) is
+// issued UNCONDITIONALLY through a buffer descriptor of `bytes` bytes at `p` (0 bytes for a null `p`): what lies outside reads as
+// zero and touches no memory.  A guarded plain load instead (`if (p) x = *p`, `if (c < d) ...`) compiles to a branch whose join
+// waits for every outstanding load, one memory round trip per guard (see rowops.hip).  `p` and `bytes` must be wave-uniform.
+typedef __amdgpu_buffer_rsrc_t m2f_rsrc_t;
+__device__ __forceinline__ m2f_rsrc_t m2f_make_rsrc(const void* p, uint32_t bytes) {
+    const unsigned long long u = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
+                                             __builtin_amdgcn_readfirstlane(p ? (int)bytes : 0), 0x00020000);
+}
+// the dropout state (seed_lo, seed_hi, step_lo, step_hi) as one 16-byte load in flight with the caller's other loads; zeros for a
+// null `rng` (a launch without a dropout site)
+__device__ __forceinline__ u32x4 m2f_rng_words(const uint32_t* rng) {
+    return __builtin_amdgcn_raw_buffer_load_b128(m2f_make_rsrc(rng, 16), 0, 0, 0);
+}
+// Left alone, hipcc sinks that load into the `if (site)` that uses it - behind the other loads' wait, a round trip of its own.  An
+// (empty) unconditional use keeps it where the source issues it; place the use where the words have certainly arrived (behind a
+// wait for loads issued AFTER them: the vector memory counter retires loads in order), so that it costs no wait itself.
+__device__ __forceinline__ void m2f_rng_words_arrived(u32x4& w) { asm volatile("" : "+v"(w)); }
 
 __device__ __forceinline__ float m2f_wave_sum(float v) {
 #pragma unroll

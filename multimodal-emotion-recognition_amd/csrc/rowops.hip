@@ -4,6 +4,11 @@
 // One wavefront per token row, rows cached in registers, 16-byte coalesced accesses, wave shuffles for
 // the row reductions; column reductions (dgamma/dbeta) go through per-block partials (deterministic,
 // no atomics, no memset).
+// The LayerNorm kernels' 16-byte path issues EVERY load of a wave - gamma, beta, x, residual / dy, extra, the row's statistics,
+// the dropout state - in one batch of range-checked buffer loads (common.h) before the first wait, and waits with counted
+// vmcnt: one memory round trip per wave.  (With a guard around every chunk, `if (c < d) { if (vec) ... }`, hipcc joined the
+// arms behind a full `s_waitcnt vmcnt(0)` each: the backward kernel walked eight round trips before its first multiply, four of
+// them for one row of gamma.)  The general path (d % 4 != 0 or an unaligned operand) keeps the guarded element loads.
 #include "common.h"
 #include "ops.h"
 #include <algorithm>
@@ -75,33 +80,55 @@ __device__ __forceinline__ bool is_vec(const void* p, int d) {
     return ((d & 3) == 0) && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
 }
 
+// 16-byte path: the row's NV chunks through a range-checked descriptor (common.h) of the row's 4 * d bytes, or of none for a
+// null operand - straight-line code, no guard per chunk: every load of a wave is in flight before the first wait
 template <int NV>
-__global__ __launch_bounds__(256) void m2f_ln_fwd_kernel(const LnBatch lb) {
-    static_assert(sizeof(LnBatch) + 64 <= 136 + 512, "m2f_kernarg_warm ranges no longer cover LnBatch + the hidden arguments");
-    m2f_kernarg_warm<0, 8, 136>();                  // the descriptor block (552 B + hidden arguments) in one miss
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int pi = 0;
+__device__ __forceinline__ void row_load_buf(RowRegs<NV>& r, const float* p, int d, int lane) {
+    const m2f_rsrc_t rs = m2f_make_rsrc(p, 4u * (uint32_t)d);
 #pragma unroll
-    for (int i = 1; i < M2F_LN_MAX_PROBLEMS; ++i)
-        if ((int)blockIdx.x >= lb.bb[i]) pi = i;
-    const LnProblem& P = lb.pr[pi];
+    for (int j = 0; j < NV; ++j)
+        r.v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (lane + 64 * j), 0, 0));
+}
+
+// the problem a workgroup belongs to: bb[] is ascending (INT_MAX in unused slots), fetched as one 16-byte block, no branches
+__device__ __forceinline__ int ln_problem_of(const LnBatch& lb) {
+    static_assert(M2F_LN_MAX_PROBLEMS == 4, "the search below reads bb[1..3]");
+    const int blk = (int)blockIdx.x;
+    return (blk >= lb.bb[1] ? 1 : 0) + (blk >= lb.bb[2] ? 1 : 0) + (blk >= lb.bb[3] ? 1 : 0);
+}
+
+// VEC: the launch-uniform 16-byte path (d % 4 == 0, every operand 16-byte aligned) - loads through row_load_buf, the dropout state
+// with them; otherwise the general path (any d, any alignment) with guarded element loads.  One body: the arithmetic is stated once.
+template <int NV, bool VEC>
+__device__ __forceinline__ void ln_fwd_body(const LnBatch& lb, const LnProblem& P, const int pi, const int lane, const int wave) {
     const int d = P.d;
     const int ld = P.ld ? P.ld : d;
     const int blk = (int)blockIdx.x - P.block_begin;
-    const bool vec = is_vec(P.x, d) && is_vec(P.out, d) && is_vec(P.gamma, d) && is_vec(P.beta, d) &&
-                     (!P.res || is_vec(P.res, d)) && ((ld & 3) == 0);
     uint16_t* out16 = m2f_shadow_of(lb.sh, P.out);
     RowRegs<NV> g, be;
-    row_load(g, P.gamma, d, vec, lane);
-    row_load(be, P.beta, d, vec, lane);
+    u32x4 rw = {0u, 0u, 0u, 0u};
     uint32_t key = 0;
-    if (P.drop_site) key = m2f_site_key(lb.rng, P.drop_site);
+    if constexpr (VEC) {
+        row_load_buf(g, P.gamma, d, lane);
+        row_load_buf(be, P.beta, d, lane);
+        rw = m2f_rng_words(lb.rng);
+    } else {
+        row_load(g, P.gamma, d, false, lane);
+        row_load(be, P.beta, d, false, lane);
+        if (P.drop_site) key = m2f_site_key(lb.rng, P.drop_site);
+    }
     const float invd = 1.0f / (float)d;
     for (int rr = 0; rr < LN_ROWS_PER_WAVE; ++rr) {
         const int row = blk * M2F_LN_ROWS_PER_BLOCK + wave * LN_ROWS_PER_WAVE + rr;
         if (row >= lb.T) break;                             // wave-uniform
-        RowRegs<NV> x;
-        row_load(x, P.x + (size_t)row * ld, d, vec, lane);
+        RowRegs<NV> x, res;
+        if constexpr (VEC) {                                // x and the residual row (no bytes for a null res) with gamma / beta / the state
+            row_load_buf(x, P.x + (size_t)row * ld, d, lane);
+            row_load_buf(res, P.res ? P.res + (size_t)row * ld : nullptr, d, lane);
+            __builtin_amdgcn_sched_barrier(0);              // (the whole batch is issued before anything waits)
+        } else {
+            row_load(x, P.x + (size_t)row * ld, d, false, lane);
+        }
         float mean, rstd;
         if (lb.pre_stats) {                                 // (diagnostic: statistics from memory, no reductions - block-uniform branch)
             mean = P.stats[2 * row]; rstd = P.stats[2 * row + 1];
@@ -121,8 +148,14 @@ __global__ __launch_bounds__(256) void m2f_ln_fwd_kernel(const LnBatch lb) {
                 }
             rstd = 1.0f / sqrtf(m2f_wave_sum(q) * invd + lb.eps);
         }
-        RowRegs<NV> res;
-        if (P.res) row_load(res, P.res + (size_t)row * ld, d, vec, lane);
+        if constexpr (VEC) {
+            if (rr == 0) {                                  // (x, issued behind the state words, has been waited for)
+                m2f_rng_words_arrived(rw);
+                if (P.drop_site) key = m2f_site_key_words(rw, P.drop_site);
+            }
+        } else {
+            if (P.res) row_load(res, P.res + (size_t)row * ld, d, false, lane);
+        }
 #pragma unroll
         for (int j = 0; j < NV; ++j)
 #pragma unroll
@@ -135,7 +168,7 @@ __global__ __launch_bounds__(256) void m2f_ln_fwd_kernel(const LnBatch lb) {
                 }
                 x.v[j][e] = y;
             }
-        row_store(x, P.out + (size_t)row * ld, d, vec, lane);
+        row_store(x, P.out + (size_t)row * ld, d, VEC, lane);
         if (out16) row_store_bf16(x, out16 + (size_t)row * ld, d, lane);
         if (lb.out8 && pi == 0) {
 #pragma unroll
@@ -151,41 +184,61 @@ __global__ __launch_bounds__(256) void m2f_ln_fwd_kernel(const LnBatch lb) {
 }
 
 template <int NV>
-__global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
+__global__ __launch_bounds__(256) void m2f_ln_fwd_kernel(const LnBatch lb) {
     static_assert(sizeof(LnBatch) + 64 <= 136 + 512, "m2f_kernarg_warm ranges no longer cover LnBatch + the hidden arguments");
     m2f_kernarg_warm<0, 8, 136>();                  // the descriptor block (552 B + hidden arguments) in one miss
-    extern __shared__ __attribute__((aligned(16))) float red[];      // [LN_WAVES][2][dpad]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < M2F_LN_MAX_PROBLEMS; ++i)
-        if ((int)blockIdx.x >= lb.bb[i]) pi = i;
-    const LnProblem& P = lb.pr[pi];
+    const int pi = ln_problem_of(lb);
+    const LnProblem P = lb.pr[pi];                  // by value: the problem's fields arrive in a few wide scalar loads
+    const int d = P.d;
+    const int ld = P.ld ? P.ld : d;
+    const bool vec = is_vec(P.x, d) && is_vec(P.out, d) && is_vec(P.gamma, d) && is_vec(P.beta, d) &&
+                     (!P.res || is_vec(P.res, d)) && ((ld & 3) == 0);
+    if (vec) ln_fwd_body<NV, true>(lb, P, pi, lane, wave);          // launch-uniform
+    else ln_fwd_body<NV, false>(lb, P, pi, lane, wave);
+}
+
+template <int NV, bool VEC>
+__device__ __forceinline__ void ln_bwd_body(const LnBatch& lb, const LnProblem& P, float* red, const int lane, const int wave) {
     const int d = P.d;
     const int ld = P.ld ? P.ld : d;
     const int dpad = (d + 3) & ~3;
     const int blk = (int)blockIdx.x - P.block_begin;
-    const bool vec = is_vec(P.x, d) && is_vec(P.dy, d) && is_vec(P.dx, d) && is_vec(P.gamma, d) &&
-                     (!P.extra || is_vec(P.extra, d)) && (!P.dx_masked || is_vec(P.dx_masked, d)) && ((ld & 3) == 0);
     uint16_t* dx16 = (P.skip & 2) ? nullptr : m2f_shadow_of(lb.sh, P.dx);
     uint16_t* dxm16 = P.dx_masked ? m2f_shadow_of(lb.sh, P.dx_masked) : nullptr;
     const bool dxm32 = P.dx_masked && !((P.skip & 1) && dxm16);
     RowRegs<NV> g, dg, db;
-    row_load(g, P.gamma, d, vec, lane);
+    u32x4 rw = {0u, 0u, 0u, 0u};
+    uint32_t key = 0;
+    if constexpr (VEC) {
+        row_load_buf(g, P.gamma, d, lane);
+        rw = m2f_rng_words(lb.rng);
+    } else {
+        row_load(g, P.gamma, d, false, lane);
+        if (P.drop_site2) key = m2f_site_key(lb.rng, P.drop_site2);
+    }
 #pragma unroll
     for (int j = 0; j < NV; ++j) { dg.v[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; db.v[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    uint32_t key = 0;
-    if (P.drop_site2) key = m2f_site_key(lb.rng, P.drop_site2);
     const float invd = 1.0f / (float)d;
     for (int rr = 0; rr < LN_ROWS_PER_WAVE; ++rr) {
         const int row = blk * M2F_LN_ROWS_PER_BLOCK + wave * LN_ROWS_PER_WAVE + rr;
         if (row >= lb.T) break;
-        RowRegs<NV> x, dy;
-        row_load(x, P.x + (size_t)row * ld, d, vec, lane);
-        row_load(dy, P.dy + (size_t)row * ld, d, vec, lane);
-        RowRegs<NV> ex;                                         // fetched with x / dy: one memory round trip, not two
-        if (P.extra) row_load(ex, P.extra + (size_t)row * ld, d, vec, lane);
-        const float mean = P.stats[2 * row], rstd = P.stats[2 * row + 1];
+        RowRegs<NV> x, dy, ex;                                  // x, dy, extra and the row's statistics: one batch of loads
+        float mean, rstd;
+        if constexpr (VEC) {
+            row_load_buf(x, P.x + (size_t)row * ld, d, lane);
+            row_load_buf(dy, P.dy + (size_t)row * ld, d, lane);
+            const m2f_rsrc_t rst = m2f_make_rsrc(P.stats + 2 * (size_t)row, 8);
+            const uint32_t st0 = __builtin_amdgcn_raw_buffer_load_b32(rst, 0, 0, 0), st1 = __builtin_amdgcn_raw_buffer_load_b32(rst, 4, 0, 0);
+            row_load_buf(ex, P.extra ? P.extra + (size_t)row * ld : nullptr, d, lane);
+            __builtin_amdgcn_sched_barrier(0);                  // (left alone, the scheduler moves extra's loads behind the first wait)
+            mean = __builtin_bit_cast(float, st0); rstd = __builtin_bit_cast(float, st1);
+        } else {
+            row_load(x, P.x + (size_t)row * ld, d, false, lane);
+            row_load(dy, P.dy + (size_t)row * ld, d, false, lane);
+            if (P.extra) row_load(ex, P.extra + (size_t)row * ld, d, false, lane);
+            mean = P.stats[2 * row]; rstd = P.stats[2 * row + 1];
+        }
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j)
@@ -201,6 +254,12 @@ __global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
                 db.v[j][e] += dy.v[j][e];
             }
         const float c1 = m2f_wave_sum(s1) * invd, c2 = m2f_wave_sum(s2) * invd;
+        if constexpr (VEC) {
+            if (rr == 0) {                                      // (x and dy, issued behind the state words, have been waited for)
+                m2f_rng_words_arrived(rw);
+                if (P.drop_site2) key = m2f_site_key_words(rw, P.drop_site2);
+            }
+        }
         RowRegs<NV> msk;
 #pragma unroll
         for (int j = 0; j < NV; ++j)
@@ -215,9 +274,9 @@ __global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
                 msk.v[j][e] = dm;
                 dy.v[j][e] = P.extra ? dx + ex.v[j][e] : dx;
             }
-        row_store(dy, P.dx + (size_t)row * ld, d, vec, lane);
+        row_store(dy, P.dx + (size_t)row * ld, d, VEC, lane);
         if (dx16) row_store_bf16(dy, dx16 + (size_t)row * ld, d, lane);
-        if (dxm32) row_store(msk, P.dx_masked + (size_t)row * ld, d, vec, lane);
+        if (dxm32) row_store(msk, P.dx_masked + (size_t)row * ld, d, VEC, lane);
         if (dxm16) row_store_bf16(msk, dxm16 + (size_t)row * ld, d, lane);
     }
     // per-block partial dgamma / dbeta: waves -> LDS -> fixed-order sum (deterministic)
@@ -233,6 +292,22 @@ __global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
         for (int w = 0; w < LN_WAVES; ++w) s += red[(size_t)w * 2 * dpad + which * dpad + cc];
         out[c] = s;
     }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void m2f_ln_bwd_kernel(const LnBatch lb) {
+    static_assert(sizeof(LnBatch) + 64 <= 136 + 512, "m2f_kernarg_warm ranges no longer cover LnBatch + the hidden arguments");
+    m2f_kernarg_warm<0, 8, 136>();                  // the descriptor block (552 B + hidden arguments) in one miss
+    extern __shared__ __attribute__((aligned(16))) float red[];      // [LN_WAVES][2][dpad]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pi = ln_problem_of(lb);
+    const LnProblem P = lb.pr[pi];                  // by value: the problem's fields arrive in a few wide scalar loads
+    const int d = P.d;
+    const int ld = P.ld ? P.ld : d;
+    const bool vec = is_vec(P.x, d) && is_vec(P.dy, d) && is_vec(P.dx, d) && is_vec(P.gamma, d) &&
+                     (!P.extra || is_vec(P.extra, d)) && (!P.dx_masked || is_vec(P.dx_masked, d)) && ((ld & 3) == 0);
+    if (vec) ln_bwd_body<NV, true>(lb, P, red, lane, wave);         // launch-uniform
+    else ln_bwd_body<NV, false>(lb, P, red, lane, wave);
 }
 
 // one block = 64 columns of one LayerNorm; its 4 wavefronts each sum a quarter of the row-block partials, then a
