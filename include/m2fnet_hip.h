@@ -129,6 +129,15 @@ int m2f_backward(m2f_plan* plan, m2f_stream_t stream);
  * captured graphs (fused-optimizer and bf16-gradient setups must be repeated); call it between steps, never between a forward and
  * its backward. */
 int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
+/* Context band of EVERY attention site of the plan - both modality encoders and every fusion layer, forward and backward (one
+ * unmasked site would leak the future): utterance i attends to utterances i - past .. i + future of its dialogue, each side >= 0
+ * or negative = unlimited (m2f_attention_fwd_band below has the rule and the rows that see no key).  (-1, 0): causal, the online
+ * setting of emotion recognition in conversation; (-1, -1), the default: the reference's offline attention, bit for bit what the plan
+ * computed before this entry existed.  No counterpart in the reference (its modules take no attn_mask).  Pad slots under a band
+ * are not the reference's numbers (as the pad slots of packed plans).  A change destroys the captured graphs; call it between
+ * steps, never between a forward and its backward.  m2f_plan_get_attention_band reads the setting back (-1 = unlimited). */
+int m2f_plan_attention_band(m2f_plan* plan, int past, int future);
+int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -530,6 +539,31 @@ int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, cons
                       int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream);
 int64_t m2f_attention_probs_elems(int B, int H, int L);
+/* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
+ * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
+ * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this
+ * one", (-1, -1) the entries above - which call these.  A hidden key has P = 0 exactly.  A query that sees NO key (a pad slot whose
+ * band holds pad keys only; a valid query always sees itself) gets a zero row of P, a zero output row and zero gradient terms, where
+ * torch's masked softmax gives NaN: such rows are pad rows of saved activations, and the weight gradients sum over every row.  The
+ * long-dialogue kernels (varlen) skip every pair of 64-row blocks the band hides as a whole and leave its block of `probs`
+ * unwritten; the backward must be given the band of the forward whose probabilities it reads. */
+int m2f_attention_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                           const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs,
+                           uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future);
+int m2f_attention_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                           const float* v, int ldv, const uint8_t* key_pad, const float* out, int ldo,
+                           const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk,
+                           int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
+                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future);
+int m2f_attention_varlen_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
+                                  float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream,
+                                  int past, int future);
+int m2f_attention_varlen_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo,
+                                  const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk,
+                                  float* dv, int lddv, uint32_t drop_site, float drop_p, const uint32_t* rng_state,
+                                  m2f_stream_t stream, int past, int future);
 /* The same attention for dialogues of up to 512 utterances (the kernels packed plans with L > 64 run): one workgroup per 64-row
  * block of a (dialogue, head), keys streamed in 64-row blocks.  Rows are given in one of two forms:
  *   packed: cu (int32 [B+1], device) - dialogue b owns rows cu[b] .. cu[b+1]-1 (at most L of them), T rows in all; rows cu[B] ..

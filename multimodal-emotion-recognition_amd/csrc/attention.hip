@@ -3,7 +3,11 @@
 // Replaces the attention inside nn.MultiheadAttention for both uses in the reference:
 //   * encoder self-attention  (src/model.py:107,119 -> TransformerEncoderLayer._sa_block)
 //   * FusionAttentionModule   (src/model.py:14: query = text, key = audio, value = text)
-// with key_padding_mask semantics (-inf on padded keys before the softmax).
+// with key_padding_mask semantics (-inf on padded keys before the softmax), and optionally a context band (AttnBatch::band_past /
+// band_future, ops.h: query i sees keys i - past .. i + future only - attn_mask of a band shape).  A hidden key has P = 0 exactly;
+// a query that sees no key at all (a pad slot whose band holds pad keys only) has a zero row of P and a zero output row - torch
+// gives NaN there.  The backward reads the saved P^T, so the band costs it nothing: P = 0 makes dS = 0, and with it the key's
+// terms of dQ, dK and dV, exactly.
 //
 // One workgroup of four wavefronts owns one (dialogue, head): the sequence is the utterances of a dialogue
 // (L <= 64), so the whole L x L problem fits one wave's registers.  Q/K/V (and dO, O in backward) tiles of
@@ -63,7 +67,8 @@ __device__ __forceinline__ f32x4 dot_rows_bf16(const float* arow, const float* b
     return acc;
 }
 
-template <int NT>
+// BAND: the launch has a context band (a second instantiation, so that a launch without one runs the code it always ran)
+template <int NT, bool BAND>
 __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) {
     static_assert(sizeof(AttnBatch) + 56 <= 192 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
     m2f_kernarg_warm<0, 8, 192>();                  // the descriptor block (648 B + hidden arguments) in one miss
@@ -151,13 +156,16 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
             if (ks < ksteps) acc0 = mfma4(kp[4 * ks], qp[4 * ks], acc0);
             s[jt] = acc0 + acc1;                            // S[i][j = 16jt + 4lg + r]
         }
+        // the keys this lane's query sees: the valid ones, inside the launch's context band (AttnBatch::band_past)
+        unsigned long long vis = kvalid;
+        if constexpr (BAND) vis &= m2f_attn_band_bits(ab, i, 0);
         float m = -INFINITY;
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
-                const float v = ((kvalid >> j) & 1ull) ? s[jt][r] * scale : -INFINITY;
+                const float v = ((vis >> j) & 1ull) ? s[jt][r] * scale : -INFINITY;
                 s[jt][r] = v;
                 m = fmaxf(m, v);
             }
@@ -168,13 +176,13 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
         for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float p = __expf(s[jt][r] - m);
+                const float p = (m == -INFINITY) ? 0.f : __expf(s[jt][r] - m);     // (a query that sees no key: P = 0, not exp(-inf + inf))
                 s[jt][r] = p;
                 sum += p;
             }
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
-        const float inv = (i < L) ? 1.0f / sum : 0.f;       // padded query rows of the tile: P = 0
+        const float inv = (i < L && sum > 0.f) ? 1.0f / sum : 0.f;       // padded query rows of the tile, rows that see no key: P = 0
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
@@ -634,9 +642,10 @@ hipError_t launch(AttnBatch& ab, hipStream_t stream) {
     const size_t lds = (size_t)(BWD ? 4 : 3) * Lp * (maxW + 2) * sizeof(float) +
                        (BWD ? (Lp + (ab.bwd_fast ? 2 * NT * NTHR : 0)) * sizeof(float) : 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const bool band = (ab.band_past | ab.band_future) != 0;
 #define M2F_ATTN_CASE(N)                                                                                   \
     case N: {                                                                                              \
-        auto kern = BWD ? m2f_attn_bwd_kernel<N> : m2f_attn_fwd_kernel<N>;                                 \
+        auto kern = BWD ? m2f_attn_bwd_kernel<N> : (band ? m2f_attn_fwd_kernel<N, true> : m2f_attn_fwd_kernel<N, false>); \
         if (lds > 64 * 1024) {                                                                             \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \

@@ -12,6 +12,10 @@
 //               block in both kernels (same code, same order -> same bits).
 // Thread shape and arithmetic as attention.hip: 256 threads, wave w owns rows 16w..16w+15 of its block, exact-fp32 MFMA
 // v_mfma_f32_16x16x4_f32, and S^T = K Q^T puts the probabilities in the accumulator layout that is the A operand of P V.
+// Context band (AttnBatch::band_past / band_future, ops.h): inside a block pair the band is one more term of the key mask; a pair
+// of 64-row blocks that the band hides as a whole is SKIPPED by all three kernels through the same test
+// (m2f_attn_band_blocks_meet) - the forward leaves that block of the probabilities buffer as it was (a plan's buffer holds the
+// previous step's values there) and neither backward kernel reads it.  A query that sees no key gets P = 0 and a zero output row.
 // Both layouts of AttnBatch: packed (cu: dialogue b owns rows cu[b] .. cu[b+1]-1, no pad keys) and padded (key_pad: masked
 // keys get -inf before the softmax).  Operands are read as fp32 in both precision modes; results also go to their bf16
 // shadows when the plan keeps them (out / dq / dk / dv, and AttnProblem::no_f32 as in attention.hip).
@@ -120,7 +124,9 @@ __device__ __forceinline__ unsigned long long key_bits(const AttnBatch& ab, cons
     return __ballot(lane < nk && kp == 0);
 }
 
-template <int CTM>      // CTM: 16-column tiles of the head dim held in registers (8: hd <= 128, 16: hd <= 256)
+// CTM: 16-column tiles of the head dim held in registers (8: hd <= 128, 16: hd <= 256); BAND: the launch has a context band (its
+// own instantiations of the three kernels, so that a launch without one runs the code it always ran)
+template <int CTM, bool BAND>
 __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatch ab) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -138,17 +144,19 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 
     const float scale = 1.0f / sqrtf((float)hd);
     const int ksteps = (hd + 3) >> 2;
-    const int i = 16 * wv + l15;                            // this lane's query row (block-local)
+    const int i = 16 * wv + l15, iq = q0 + i;               // this lane's query row (block-local / in the dialogue)
     const float* qrow = Qs + i * ld + lg;
     const float* kb_rows = KV + l15 * ld + lg;
 
     // pass 1: row max and normaliser
     float m_run = -INFINITY, l_run = 0.f;
     for (int kb = 0; kb < w.n; kb += BLK) {
+        if (BAND && !m2f_attn_band_blocks_meet(ab, q0, kb)) continue;     // (block-uniform; pass 2 and both backward kernels skip the same pairs)
         const int nk = min(BLK, w.n - kb);
         __syncthreads();                                    // previous K / V block consumed (and Q committed)
         stage(KV, P.k + (w.tok0 + kb) * P.ldk + w.h * hd, P.ldk, nk, hd, W, ld, tid);
-        const unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
+        unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
+        if constexpr (BAND) kvalid &= m2f_attn_band_bits(ab, iq, kb);     // (from here on per lane: the keys its query sees)
         __syncthreads();
         float s[4][4];
         float m_blk = -INFINITY;
@@ -177,8 +185,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
     }
 
     // pass 2: P = exp(S - m) / l -> P^T (pre-dropout) to probs, dropout, O += P V
-    const int iq = q0 + i;
-    const float inv = iq < w.n ? 1.0f / l_run : 0.f;       // rows past the dialogue: P = 0
+    const float inv = (iq < w.n && l_run > 0.f) ? 1.0f / l_run : 0.f;      // rows past the dialogue, rows that see no key: P = 0
     const uint32_t site = P.drop_site;
     uint32_t key = 0;
     if (site) key = m2f_site_key(ab.rng, site);
@@ -187,10 +194,12 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 #pragma unroll
     for (int ct = 0; ct < CTM; ++ct) o[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int kb = 0; kb < w.n; kb += BLK) {
+        if (BAND && !m2f_attn_band_blocks_meet(ab, q0, kb)) continue;     // (its block of probs keeps what it held: the backward skips it too)
         const int nk = min(BLK, w.n - kb);
         __syncthreads();
         stage(KV, P.k + (w.tok0 + kb) * P.ldk + w.h * hd, P.ldk, nk, hd, W, ld, tid);
-        const unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
+        unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
+        if constexpr (BAND) kvalid &= m2f_attn_band_bits(ab, iq, kb);
         __syncthreads();
         float p[4][4];
 #pragma unroll
@@ -200,7 +209,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
             for (int r = 0; r < 4; ++r) {
                 const int jl = 16 * jt + 4 * lg + r, j = kb + jl;
                 const float x = ((kvalid >> jl) & 1ull) ? acc[r] * scale : -INFINITY;
-                float pv = __expf(x - m_run) * inv;
+                float pv = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;   // (no visible key: exp(-inf + inf) would be NaN)
                 if (iq < Lp && j < Lp) probs[(size_t)j * Lp + iq] = pv;           // lanes: consecutive iq
                 if (site) pv = m2f_keep(key, drop_idx(w.bh, LM, iq, j), ab.drop_thresh) ? pv * ab.drop_scale : 0.f;
                 p[jt][r] = pv;
@@ -237,7 +246,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 }
 
 // dK = scale dS^T Q, dV = P~^T dO for the 64 keys of one block; lane = key (l15), registers = query rows
-template <int CTM>
+template <int CTM, bool BAND>
 __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_dkdv_kernel(const AttnBatch ab) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -269,6 +278,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_dkdv_kernel(const AttnBat
 #pragma unroll
     for (int ct = 0; ct < CTM; ++ct) { dk[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[ct] = dk[ct]; }
     for (int qb = 0; qb < w.n; qb += BLK) {
+        if (BAND && !m2f_attn_band_blocks_meet(ab, qb, j0)) continue;     // (the forward wrote no probabilities for this pair: all zero under the band)
         const int nq = min(BLK, w.n - qb);
         __syncthreads();                                    // previous Q slab consumed
         stage(X, P.dout + (w.tok0 + qb) * P.lddo + w.h * hd, P.lddo, nq, hd, W, ld, tid);
@@ -338,7 +348,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_dkdv_kernel(const AttnBat
 }
 
 // dQ = scale dS K for the 64 queries of one block; lane = query (l15), registers = keys
-template <int CTM>
+template <int CTM, bool BAND>
 __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_dq_kernel(const AttnBatch ab) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -374,6 +384,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_dq_kernel(const AttnBatch
 #pragma unroll
     for (int ct = 0; ct < CTM; ++ct) dq[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int kb = 0; kb < w.n; kb += BLK) {
+        if (BAND && !m2f_attn_band_blocks_meet(ab, q0, kb)) continue;     // (as the forward and dK / dV)
         const int nk = min(BLK, w.n - kb);
         __syncthreads();                                    // previous K slab consumed
         stage(KV, P.v + (w.tok0 + kb) * P.ldv + w.h * hd, P.ldv, nk, hd, W, ld, tid);
@@ -452,6 +463,8 @@ hipError_t go(K kern, int blocks, size_t lds, hipStream_t stream, const AttnBatc
     return hipGetLastError();
 }
 
+bool has_band(const AttnBatch& ab) { return (ab.band_past | ab.band_future) != 0; }
+
 }  // namespace
 
 bool m2f_attn_dlong_index_ok(int B, int H, int L) {
@@ -463,7 +476,9 @@ hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)2 * BLK * (maxW + 2) * sizeof(float);
-    return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16>, blocks, lds, stream, ab);
+    if (has_band(ab))
+        return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, true>, blocks, lds, stream, ab);
+    return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, false>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, false>, blocks, lds, stream, ab);
 }
 
 hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream) {
@@ -471,8 +486,14 @@ hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = ((size_t)2 * BLK * (maxW + 2) + BLK) * sizeof(float);
-    hipError_t e = maxW <= 128 ? go(m2f_attn_dlong_dkdv_kernel<8>, blocks, lds, stream, ab)
-                               : go(m2f_attn_dlong_dkdv_kernel<16>, blocks, lds, stream, ab);
+    if (has_band(ab)) {
+        hipError_t e = maxW <= 128 ? go(m2f_attn_dlong_dkdv_kernel<8, true>, blocks, lds, stream, ab)
+                                   : go(m2f_attn_dlong_dkdv_kernel<16, true>, blocks, lds, stream, ab);
+        if (e != hipSuccess) return e;
+        return maxW <= 128 ? go(m2f_attn_dlong_dq_kernel<8, true>, blocks, lds, stream, ab) : go(m2f_attn_dlong_dq_kernel<16, true>, blocks, lds, stream, ab);
+    }
+    hipError_t e = maxW <= 128 ? go(m2f_attn_dlong_dkdv_kernel<8, false>, blocks, lds, stream, ab)
+                               : go(m2f_attn_dlong_dkdv_kernel<16, false>, blocks, lds, stream, ab);
     if (e != hipSuccess) return e;
-    return maxW <= 128 ? go(m2f_attn_dlong_dq_kernel<8>, blocks, lds, stream, ab) : go(m2f_attn_dlong_dq_kernel<16>, blocks, lds, stream, ab);
+    return maxW <= 128 ? go(m2f_attn_dlong_dq_kernel<8, false>, blocks, lds, stream, ab) : go(m2f_attn_dlong_dq_kernel<16, false>, blocks, lds, stream, ab);
 }

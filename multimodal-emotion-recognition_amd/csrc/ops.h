@@ -186,9 +186,14 @@ struct AttnBatch {
     AttnProblem pr[M2F_ATTN_MAX_PROBLEMS];
     int count;
     int B, L;
+    int band_past;             // context band (below), past side - here and after T: the two fill alignment holes, the struct keeps its size
     const uint8_t* key_pad;    // [B, L], 1 = padded key
     const int* cu;             // PACKED layout (nullable): dialogue b owns token rows cu[b] .. cu[b+1]-1 (at most L of them); key_pad unused
     int T;                     // PACKED layout: token rows of the buffers; rows cu[B] .. T-1 belong to no dialogue and are written as zeros
+    // Context band, uniform per launch, stored + 1 so that a zeroed batch means "no band": query i (position inside its dialogue) sees
+    // key j iff j is a valid key as ever, and (band_past == 0 or j >= i - (band_past - 1)) and (band_future == 0 or
+    // j <= i + (band_future - 1)).  A query that sees no key (a pad slot behind a short dialogue) gets P = 0 and a zero output row.
+    int band_future;
     const uint32_t* rng;
     uint32_t drop_thresh;
     float drop_scale;
@@ -198,6 +203,23 @@ struct AttnBatch {
                                // on v_mfma_f32_16x16x32_bf16 (fp32 accumulate): 1/8 of the MFMA instructions at 1/2 the cycles each;
                                // 2 / 4 / 8 / 16 / 32 = the Q / K / V / dO / O slab is staged from the operand's bf16 shadow (half the bytes)
 };
+inline void m2f_attn_set_band(AttnBatch& ab, int past, int future) {      // (past, future): >= 0, or negative = unlimited
+    const int cap = 1 << 20;                                               // (far beyond any L: the same band, and i +- it cannot overflow)
+    ab.band_past = past < 0 ? 0 : (past < cap ? past : cap) + 1;
+    ab.band_future = future < 0 ? 0 : (future < cap ? future : cap) + 1;
+}
+// bit jl = the band lets query i see key kb + jl (jl = 0 .. 63); all ones without a band
+__host__ __device__ inline unsigned long long m2f_attn_band_bits(const AttnBatch& ab, int i, int kb) {
+    int lo = ab.band_past ? i - (ab.band_past - 1) - kb : 0;
+    int hi = ab.band_future ? i + (ab.band_future - 1) - kb : 63;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > 63 ? 63 : hi;
+    return lo > hi ? 0ull : (~0ull >> (63 - hi)) & (~0ull << lo);
+}
+// the 64-row blocks at q0 (queries) and k0 (keys) hold a pair the band lets through (the long-dialogue kernels skip the others)
+__host__ __device__ inline bool m2f_attn_band_blocks_meet(const AttnBatch& ab, int q0, int k0) {
+    return (!ab.band_past || k0 + 63 >= q0 - (ab.band_past - 1)) && (!ab.band_future || k0 <= q0 + 63 + (ab.band_future - 1));
+}
 int m2f_attn_shadow_only_bits(const AttnBatch& ab, int pi, bool bwd);     // host: operands this launch stages from bf16 shadows only
 hipError_t m2f_launch_attn_fwd(AttnBatch& ab, hipStream_t stream);
 // Long-sequence forward (S unbounded, hd <= 128): token-level self-attention of the in-loop text encoder (inference).

@@ -106,8 +106,13 @@ def quantize_fp8(src: torch.Tensor, scale: float, out: Optional[torch.Tensor] = 
 
 
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: torch.Tensor, B: int, L: int, H: int,
-                  drop_site: int = 0, drop_p: float = 0.0, rng: Optional[torch.Tensor] = None):
-    """q/k/v: [B*L, H*hd] (possibly column slices).  Returns (out [B*L, H*hd], probs^T [B*H, Lp, Lp])."""
+                  drop_site: int = 0, drop_p: float = 0.0, rng: Optional[torch.Tensor] = None,
+                  past: Optional[int] = None, future: Optional[int] = None):
+    """q/k/v: [B*L, H*hd] (possibly column slices).  Returns (out [B*L, H*hd], probs^T [B*H, Lp, Lp]).
+    past / future: context band - query slot i sees the valid keys of slots i - past .. i + future only (None = unlimited on that
+    side; (None, 0) is causal).  Hidden keys have probability exactly 0; a query that sees no key at all (a pad slot whose band
+    holds pad keys only) gets a zero row of probabilities and a zero output row, where torch's masked softmax gives NaN - pad
+    slots under a band are not the reference's numbers."""
     runtime.require_gpu()
     E = q.shape[1]
     hd = E // H
@@ -115,21 +120,34 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     Lp = 16 * ((L + 15) // 16)
     probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     kp = key_pad.to(torch.uint8).contiguous()
-    check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                  _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_fwd")
+    if past is None and future is None:
+        check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                      _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_fwd")
+    else:
+        check(lib().m2f_attention_fwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                           _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                           *runtime.context_band(past, future)), "m2f_attention_fwd_band")
     return out, probs
 
 
 def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, drop_site: int = 0, drop_p: float = 0.0,
-                  rng: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                  rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
+                  future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of `attention_fwd` from its saved probabilities (which carry the band: past / future are the forward's)."""
     runtime.require_gpu()
     E = q.shape[1]
     hd = E // H
     dq, dk, dv = (torch.zeros(B * L, E, dtype=torch.float32, device=q.device) for _ in range(3))
     kp = key_pad.to(torch.uint8).contiguous()
-    check(lib().m2f_attention_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                  _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
-                                  ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_bwd")
+    if past is None and future is None:
+        check(lib().m2f_attention_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                      _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
+                                      ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_bwd")
+    else:
+        check(lib().m2f_attention_bwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                           _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
+                                           ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                           *runtime.context_band(past, future)), "m2f_attention_bwd_band")
     return dq, dk, dv
 
 
@@ -143,36 +161,56 @@ def _varlen_rows(cu: Optional[torch.Tensor], key_pad: Optional[torch.Tensor]):
 
 def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, L: int, H: int,
                          cu: Optional[torch.Tensor] = None, key_pad: Optional[torch.Tensor] = None, drop_site: int = 0,
-                         drop_p: float = 0.0, rng: Optional[torch.Tensor] = None):
+                         drop_p: float = 0.0, rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
+                         future: Optional[int] = None, probs: Optional[torch.Tensor] = None):
     """Long-dialogue attention (m2f_attention_varlen_fwd, L <= 512).  q/k/v: [T, H*hd] (possibly column slices) with either
     cu (int [B+1]: dialogue b = rows cu[b] .. cu[b+1]-1, T = q.shape[0]) or key_pad ([B, L] or [B*L], True = padded key;
-    T = B*L).  Returns (out [T, H*hd], probs^T [B*H, Lp, Lp])."""
+    T = B*L).  Returns (out [T, H*hd], probs^T [B*H, Lp, Lp]).
+    past / future: context band as in `attention_fwd`, over utterance positions inside the dialogue (packed: row minus cu[b]).  Pairs
+    of 64-row blocks that the band hides as a whole are skipped: their part of the probabilities buffer is NOT written (zeros in
+    the fresh buffer made here; whatever it held in a buffer passed as `probs`), and `attention_varlen_bwd` given the same band
+    does not read it."""
     runtime.require_gpu()
     T, E = q.shape
     hd = E // H
     cu32, kp = _varlen_rows(cu, key_pad)
     out = torch.empty(T, E, dtype=torch.float32, device=q.device)
     Lp = 16 * ((L + 15) // 16)
-    probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
-    check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                         ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()),
-          "m2f_attention_varlen_fwd")
+    if probs is None:
+        probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
+    assert probs.shape == (B * H, Lp, Lp) and probs.is_contiguous() and probs.dtype == torch.float32 and probs.is_cuda
+    if past is None and future is None:
+        check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                             ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()),
+              "m2f_attention_varlen_fwd")
+    else:
+        check(lib().m2f_attention_varlen_fwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                                  ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                                  *runtime.context_band(past, future)), "m2f_attention_varlen_fwd_band")
     return out, probs
 
 
 def attention_varlen_bwd(q, k, v, out, probs, dout, B: int, L: int, H: int, cu: Optional[torch.Tensor] = None,
                          key_pad: Optional[torch.Tensor] = None, drop_site: int = 0, drop_p: float = 0.0,
-                         rng: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Backward of `attention_varlen_fwd` from its saved probabilities: (dq, dk, dv), each [T, H*hd]."""
+                         rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
+                         future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of `attention_varlen_fwd` from its saved probabilities: (dq, dk, dv), each [T, H*hd].  past / future: the band of that
+    forward (the block pairs it skipped are skipped here)."""
     runtime.require_gpu()
     T, E = q.shape
     hd = E // H
     cu32, kp = _varlen_rows(cu, key_pad)
     dq, dk, dv = (torch.zeros(T, E, dtype=torch.float32, device=q.device) for _ in range(3))
-    check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                         ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
-                                         _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()),
-          "m2f_attention_varlen_bwd")
+    if past is None and future is None:
+        check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                             ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
+                                             _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()),
+              "m2f_attention_varlen_bwd")
+    else:
+        check(lib().m2f_attention_varlen_bwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                                  ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
+                                                  _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                                  *runtime.context_band(past, future)), "m2f_attention_varlen_bwd_band")
     return dq, dk, dv
 
 
@@ -258,8 +296,9 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, class_w: Optional[
 
 
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
-                      precision: int = runtime.F32) -> torch.Tensor:
-    """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity."""
+                      precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None) -> torch.Tensor:
+    """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity.  past / future: context band of its
+    attention (`attention_fwd`); the reference has none."""
     B, L, E = text.shape
     t = text.reshape(B * L, E).contiguous()
     a = audio.reshape(B * L, E).contiguous()
@@ -267,9 +306,9 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     k = gemm(a, in_w[E:2 * E], NT, precision, bias=in_b[E:2 * E])
     v = gemm(t, in_w[2 * E:], NT, precision, bias=in_b[2 * E:])
     if L > 64:          # (the dialogue kernels of attention_fwd hold L <= 64; above, the long-dialogue kernels, padded form)
-        att, _ = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad)
+        att, _ = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future)
     else:
-        att, _ = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head)
+        att, _ = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future)
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
     return y.view(B, L, E)

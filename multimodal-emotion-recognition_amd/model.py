@@ -91,7 +91,10 @@ class FusionAttentionModule(nn.Module):
         self.relu = nn.ReLU()
         self.embedding_size, self.n_head, self.dropout_p = embedding_size, n_head, dropout
 
-    def forward(self, text: torch.Tensor, audio: torch.Tensor, key_padding_mask: torch.Tensor) -> torch.Tensor:
+    def forward(self, text: torch.Tensor, audio: torch.Tensor, key_padding_mask: torch.Tensor,
+                past: Optional[int] = None, future: Optional[int] = None) -> torch.Tensor:
+        """past / future: context band of the attention (``functional.attention_fwd``): text utterance i attends to the audio of
+        utterances i - past .. i + future only, None = unlimited.  The reference's module has no such argument."""
         from . import functional as F
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("standalone FusionAttentionModule.forward is inference-only; train it inside M2FNet "
@@ -99,7 +102,7 @@ class FusionAttentionModule(nn.Module):
         return F.fam_layer_forward(text, audio, key_padding_mask, self.multihead_attention.in_proj_weight,
                                    self.multihead_attention.in_proj_bias, self.multihead_attention.out_proj.weight,
                                    self.multihead_attention.out_proj.bias, self.linear.weight, self.linear.bias,
-                                   self.n_head)
+                                   self.n_head, past=past, future=future)
 
 
 class _Anchor(torch.autograd.Function):
@@ -238,13 +241,21 @@ class _Engine:
         Bb = 1 << max(B - 1, 0).bit_length() if B <= 8 else (B + 7) // 8 * 8
         return Bb, Lb
 
+    @staticmethod
+    def plan_key(B, L, T, want_backward, dropout_active, precision, outputs=(0, True), band=(None, None)) -> Tuple:
+        """A plan's key without its instance number.  Only a non-default `outputs` / context band extends the tuple: the keys of a
+        model that uses neither are what they were before either existed."""
+        key = (B, L, T, want_backward, dropout_active, precision) + (() if outputs == (0, True) else (outputs,))
+        return key if band == (None, None) else key + (("context",) + tuple(band),)
+
     def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None,
              outputs: Tuple[int, bool] = (0, True)) -> runtime.Plan:
         """valid: number of valid utterances of the batch (packed mode) - the plan then holds that many token rows (rounded up to
         a multiple of 64, plus one row per filler dialogue and one spare) instead of B x L slots; batches that are at least
         85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64).
         outputs: what a backward computes - (input_mask, parameter gradients) of m2f_plan_backward_outputs; part of the key, so a
-        plan of one setting never flips to another (train_step always uses the default (0, True))."""
+        plan of one setting never flips to another (train_step always uses the default (0, True)).
+        The model's context band (M2FNet.context) is part of the key in the same way: every band has its own plans."""
         b_in, l_in = B, L
         if self.shape_buckets:
             B, L = self.bucket(B, L)
@@ -258,7 +269,8 @@ class _Engine:
             if long or Tb <= 0.85 * B * L:
                 T = min(max(Tb, B), B * L)            # (every dialogue full: no spare row - runtime.Plan handles that)
         outputs = (int(outputs[0]), bool(outputs[1]))
-        base = (B, L, T, want_backward, dropout_active, self.precision) + (() if outputs == (0, True) else (outputs,))
+        band = self.model.context                         # (read per call: M2FNet.set_context only changes which plans are handed out)
+        base = self.plan_key(B, L, T, want_backward, dropout_active, self.precision, outputs, band)
         inst, key, pl, oldest = 0, None, None, None
         while True:                                       # first instance of this shape that no live autograd graph owns
             key = base + (inst,)
@@ -287,6 +299,8 @@ class _Engine:
             pl._on_cast = self.mark_shadows_fresh
             if train and outputs != (0, True):
                 pl.backward_outputs(*outputs)
+            if band != (None, None):
+                pl.attention_band(*band)                  # (once, before its first launch: a plan keeps the band of its key)
             self.plans[key] = pl
             self._evict(max(self.max_plans, 1), self.max_plan_bytes, protect=key)
         else:
@@ -394,9 +408,11 @@ class M2FNet(nn.Module):
     was; a partly frozen model computes and publishes all parameter gradients as before."""
 
     def __init__(self, config, precision: Optional[str] = None, shape_buckets: Optional[bool] = None,
-                 packed: Optional[bool] = None):
+                 packed: Optional[bool] = None, context: Optional[Tuple[Optional[int], Optional[int]]] = None):
         super().__init__()
         self.config = config
+        self._context: Tuple[Optional[int], Optional[int]] = (None, None)
+        self.set_context(*(context if context is not None else (None, None)))
         # packed ("varlen") token layout for `train_step` and no-grad `forward` (runtime.Plan, m2f_plan_create_packed): a ragged
         # batch costs its valid utterances, not B x L slots; needs the batch's valid count on the host (one sync per call).
         # Off by default (M2F_PACKED=1 or packed=True): the reference's batches reach the model as padded tensors either way
@@ -458,6 +474,24 @@ class M2FNet(nn.Module):
             self._engine = _Engine(self, device)
             self._engine.accumulate = self._grad_accumulation
         return self._engine
+
+    # -- context band ----------------------------------------------------------------------------------
+    @property
+    def context(self) -> Tuple[Optional[int], Optional[int]]:
+        """(past, future): how many utterances before / after its own an utterance attends to; None = unlimited."""
+        return self._context
+
+    def set_context(self, past: Optional[int] = None, future: Optional[int] = None) -> None:
+        """Context band of EVERY attention site - both modality encoders and every fusion layer - in ``forward``, ``train_step``
+        and ``eval_step``, padded, packed, bucketed and long-dialogue plans alike: utterance i attends to utterances i - past ..
+        i + future of its dialogue.  ``(None, 0)``: causal, the online setting (an utterance is labelled from the past only);
+        ``(k, 0)``: the last k utterances and this one; ``(None, None)``, the default: the reference's offline attention, bit for bit
+        what the model computed without a band.  The reference has no such setting (its modules are given no ``attn_mask``).
+        Valid utterances always see themselves; pad slots under a band are not the reference's numbers (a pad slot whose band holds
+        no valid utterance gets zero attention output where torch's masked softmax gives NaN) - loss and metrics mask them out, as
+        they do the pad slots of packed plans.  Takes effect at the next call; each band keeps its own plans, none is rewritten."""
+        runtime.context_band(past, future)                 # (raises ValueError)
+        self._context = (past, future)
 
     # -- reference surface -----------------------------------------------------------------------------
     def forward(self, text, audio, mask):

@@ -117,6 +117,19 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                   c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_probs_elems": (c_int64, [c_int, c_int, c_int]),
+    "m2f_attention_fwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
+    "m2f_attention_bwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                       c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
+    "m2f_attention_varlen_fwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
+                                              c_int, c_int]),
+    "m2f_attention_varlen_bwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
+    "m2f_plan_attention_band": (c_int, [c_void_p, c_int, c_int]),
+    "m2f_plan_get_attention_band": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "m2f_attention_varlen_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_varlen_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
@@ -231,6 +244,20 @@ def stream_ptr() -> int:
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def context_band(past, future) -> Tuple[int, int]:
+    """The two integers of a context band as the C entries take them: each side None (unlimited, -1) or an integer >= 0 - how many
+    utterances before (past) / after (future) its own an utterance attends to.  (None, 0) is causal attention."""
+    out = []
+    for name, v in (("past", past), ("future", future)):
+        if v is None:
+            out.append(-1)
+            continue
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"context band: {name} must be None (unlimited) or an integer >= 0, got {v!r}")
+        out.append(v)
+    return out[0], out[1]
 
 
 def c_param_layout(c: M2FConfig) -> Tuple[list, list, int]:
@@ -547,6 +574,19 @@ class Plan:
             return
         check(lib().m2f_plan_accumulate_grads(self._h(), int(on)), "m2f_plan_accumulate_grads")
         self._acc = on
+
+    def attention_band(self, past: Optional[int], future: Optional[int]) -> None:
+        """m2f_plan_attention_band: the context band of EVERY attention site of the plan (both encoders, every fusion layer, forward
+        and backward) - utterance i attends to utterances i - past .. i + future of its dialogue, None = unlimited on that side.  A
+        change drops the captured graphs; between steps only."""
+        check(lib().m2f_plan_attention_band(self._h(), *context_band(past, future)), "m2f_plan_attention_band")
+
+    @property
+    def band(self) -> Tuple[Optional[int], Optional[int]]:
+        """(past, future) as the plan's launches hold it, None = unlimited."""
+        a, b = c_int(0), c_int(0)
+        check(lib().m2f_plan_get_attention_band(self._h(), ctypes.byref(a), ctypes.byref(b)), "m2f_plan_get_attention_band")
+        return (None if a.value < 0 else a.value, None if b.value < 0 else b.value)
 
     def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
         """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |

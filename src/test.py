@@ -71,8 +71,17 @@ def print_class_report(report):
         print(f"{c:>5} {p * 100:>8.3f}% {r * 100:>8.3f}% {f * 100:>8.3f}% {s:>8}")
 
 
+def build_model(config, device):
+    """The model as train.py built it (train.build_model): runtime.precision and runtime.context, so a model trained under a context
+    band is tested under it."""
+    from train import build_model as build
+    return build(config, device)
+
+
 def main(config=None):
     config = get_config()
+    from train import context_settings
+    context_settings(config)                               # (refusal before the GPU is touched)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     print(f"Using device {device}...")
     runtime_cfg = config.get("runtime", {}) or {}
@@ -80,7 +89,7 @@ def main(config=None):
         loader = DeviceLoader(Dataset(mode="test"), device=device, **config.test.data_loader)
     else:
         loader = torch.utils.data.DataLoader(Dataset(mode="test"), collate_fn=collate_fn, **config.test.data_loader)
-    model = M2FNet(config.model, precision=runtime_cfg.get("precision", "fp32")).to(device)
+    model = build_model(config, device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     from train import ema_settings
     ema = ema_settings(config)

@@ -116,6 +116,35 @@ def ema_settings(cfg):
     return float(decay), flags["warmup"], flags["evaluate"]
 
 
+def context_settings(cfg):
+    """`runtime.context` = {past, future}: the context band of every attention site of the model (M2FNet(context=...)) - utterance i
+    attends to utterances i - past .. i + future of its dialogue; null = unlimited on that side.  {past: null, future: 0} is the online
+    setting (an utterance is labelled from the past only), {past: k, future: 0} its bounded form.  -> None when the block is absent,
+    null or unlimited on both sides (the reference's offline attention), else (past, future).  Checked on the host before the GPU is
+    touched."""
+    block = _runtime(cfg, "context", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.context must be a mapping {{past, future}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - {"past", "future"})
+    if unknown:
+        raise ValueError(f"runtime.context: unknown key(s) {unknown} (past, future)")
+    band = []
+    for k in ("past", "future"):
+        v = block.get(k, None)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+            raise ValueError(f"runtime.context.{k} must be null or an integer >= 0 (got {v!r})")
+        band.append(v)
+    return None if band == [None, None] else (band[0], band[1])
+
+
+def build_model(config, device):
+    """The M2FNet of `config` on `device` as train.py and test.py both build it: runtime.precision and runtime.context - so a model
+    trained under a context band is validated and tested under the same band."""
+    return M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=context_settings(config)).to(device)
+
+
 def watch_settings(cfg, world: int = 1):
     """`runtime.watch` = {enabled, log, log_freq, bins, file}: per-tensor statistics and histograms of the buffers the optimizer step
     uses, every log_freq optimizer steps (mer_amd.watch.ModelWatch) - what `wandb.watch_model` asks of wandb's hooks, which cannot see
@@ -402,6 +431,7 @@ def main(config=None):
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
+    context_settings(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -455,7 +485,7 @@ def main(config=None):
     if world > 1:
         dl_train = dp.ShardedLoader(dl_train, rank, world)
 
-    model = M2FNet(config.model, precision=_runtime(config, "precision", "fp32")).to(device)
+    model = build_model(config, device)
     # how train() runs the loop body: (fused m2f_step instead of forward / criterion / backward, as one hipGraph)
     model.step_mode = (bool(_runtime(config, "fused_step", True)), bool(_runtime(config, "use_graph", True)))
     model.fused_optimizer = bool(_runtime(config, "fused_optimizer", False))
