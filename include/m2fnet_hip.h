@@ -53,7 +53,9 @@ enum {
     M2F_BUF_CU_SEQLENS = 9, /* int32 [B+1]           input of PACKED plans: dialogue b owns token rows cu[b] .. cu[b+1]-1 */
     M2F_BUF_DTEXT = 10,     /* float [B*L, pad8(d_text)]  output d loss / d text (text.grad, src/model.py:115-119; train plans, m2f_plan_backward_outputs) */
     M2F_BUF_DAUDIO = 11,    /* float [B*L, pad8(d_audio)] output d loss / d audio (audio.grad, src/model.py:103-107; same rows as M2F_BUF_AUDIO)  */
-    M2F_BUF_COUNT = 12
+    M2F_BUF_STREAM_LEN = 12,    /* int32 [S]  stream plans: utterances cached per stream slot (advanced by m2f_stream_step, zeroed by m2f_stream_reset) */
+    M2F_BUF_STREAM_ACTIVE = 13, /* uint8 [S]  stream plans, input: 1 = the slot takes an utterance in the next m2f_stream_step */
+    M2F_BUF_COUNT = 14
 };
 
 const char* m2f_last_error(void);
@@ -138,6 +140,28 @@ int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
  * steps, never between a forward and its backward.  m2f_plan_get_attention_band reads the setting back (-1 = unlimited). */
 int m2f_plan_attention_band(m2f_plan* plan, int past, int future);
 int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
+/* STREAM plan: online inference under a causal context band (past, 0).  S stream slots, each one live dialogue; a step takes ONE new
+ * utterance per active slot (row s of M2F_BUF_TEXT / M2F_BUF_AUDIO, both [S, pad8(d)]; M2F_BUF_STREAM_ACTIVE [S]) and leaves its logits
+ * in row s of M2F_BUF_LOGITS [S, cls_out].  Under such a band the K and V rows of an utterance at every attention site depend on
+ * earlier utterances only, so each site keeps them in a per-slot cache ([S][H][C][pad(hd)], fp32 or - bf16 mode - bf16 rounded once;
+ * csrc/attention_stream.hip has the layout) and a step costs one row per dialogue instead of the whole prefix.  Forward only, no
+ * dropout; the launch list is the eval plan's for S rows (same GEMM, LayerNorm and classifier launches) with every attention launch
+ * replaced by m2f_attention_stream's kernel.  past < 0: no window - a slot holds at most C utterances (1 <= C <= 512), the caller
+ * must not step a slot whose count has reached C (the kernel then writes nothing and returns a zero row); past >= 0: the cache is a
+ * ring of C rows, C >= past + 1 (raised to it) - the slot sees its last C - 1 utterances, so C = past + 1 is the band (past, 0)
+ * and the stream has no length limit.  The caches cost 2 * sum over sites of S * C * pad(d_site) elements.
+ * param_shadow: NULL, or the shared parameter-shadow buffer of m2f_plan_create_shared (bf16 mode; m2f_plan_params_fresh applies).
+ * m2f_stream_step: forward + count[s] += active[s]; use_graph = 1 replays one captured graph (single stream, no forks) - everything
+ * that varies per call lives in device buffers.  m2f_stream_reset: count[s] = 0 for the slots whose byte in `slot_mask` (device uint8
+ * [S]) is non-zero, NULL = every slot; stale cache rows are never read, the live rows are counted from 0 again.
+ * The caches belong to the parameter values that wrote them: reset every slot after the parameters change.
+ * No counterpart in the reference (it has no incremental inference). */
+int64_t m2f_stream_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int shared);
+m2f_plan* m2f_plan_create_stream(const m2f_config* cfg, int S, int C, int past, int precision, float* params, void* workspace,
+                                 int64_t workspace_bytes, uint16_t* param_shadow);
+int m2f_stream_step(m2f_plan* plan, int use_graph, m2f_stream_t stream);
+int m2f_stream_reset(m2f_plan* plan, const uint8_t* slot_mask, m2f_stream_t stream);
+int64_t m2f_stream_cache_bytes(m2f_plan* plan);          /* bytes of all K / V caches of the plan */
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -539,6 +563,17 @@ int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, cons
                       int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream);
 int64_t m2f_attention_probs_elems(int B, int H, int L);
+/* Streaming attention, one launch (csrc/attention_stream.hip): slot s of S takes ONE new utterance - rows s of q / k / v [S, H*hd] fp32,
+ * column slices with their leading dimensions - against the rows the slot has cached.  count[s] (device int32) = utterances cached so far,
+ * active[s] (device uint8).  An active slot: the new K / V rows are stored at row count % C (ring != 0) or row count (ring == 0;
+ * count < C required) of kcache / vcache, and out[s] = softmax(q K^T / sqrt(hd)) V over the min(count + 1, C) live rows, the new one
+ * included (count == 0: the new V row itself).  An inactive slot: out[s] = 0, caches untouched.  count is NOT advanced.  Caches:
+ * [S][H][C][pad4(hd)] float (bf16 == 0) or [S][H][C][pad8(hd)] bf16 (bf16 != 0: K, V rounded once on the way in, q where it enters
+ * the product, softmax and sums fp32), 16-byte aligned, m2f_attention_stream_cache_elems elements each.  hd <= 128, C <= 512. */
+int64_t m2f_attention_stream_cache_elems(int S, int H, int hd, int C, int bf16);
+int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                         void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
+                         int bf16, m2f_stream_t stream);
 /* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
  * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
  * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this

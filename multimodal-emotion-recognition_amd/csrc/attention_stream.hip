@@ -1,0 +1,256 @@
+// Streaming ("decode") dialogue attention on gfx950: ONE new utterance per live dialogue against that dialogue's cached keys / values.
+//
+// The problem is (stream slot s, head h): the slot's new query row against the rows the slot has cached so far plus its new key row.
+// Under a causal context band (past, 0) layer l's K and V rows of utterance j depend on utterances <= j only, so they are computed
+// once, stored here, and never change; a step then costs one row per dialogue instead of the whole prefix.
+//
+// CACHE LAYOUT (per attention site, K and V alike):   cache[S][H][C][hdp]
+//   S slots, H heads, C rows of capacity, hdp = the head dim padded to a 16-byte multiple: pad4(hd) floats (fp32 mode) or pad8(hd)
+//   bf16 values (bf16 mode).  A head's rows are contiguous, every row starts 16-byte aligned, pad columns hold zeros.
+//   m2f_attn_stream_cache_elems gives the element count.  Row r of a slot holds utterance r (plain cache, len < C) or utterance
+//   u with u % C == r (ring: a window of past = C - 1 utterances; the row of the utterance that just left the window is the one the
+//   new utterance overwrites).  The number of live rows comes from len[s] alone, so stale rows behind a reset are never read.
+//
+// One wavefront per (s, h): byte-stream work (every cached row is read exactly once, with 16-byte loads straight into VGPRs), no MFMA.
+// A row is spread over CH = 2^k lanes (4 floats / 8 bf16 each; lanes past the row's end hold zeros in registers, no divergent tail),
+// 64 / CH rows per pass.  Pass 1: scores into LDS (fp32 product, then * 1/sqrt(hd), as attention.hip); softmax: max-subtracted __expf
+// in fp32 over the <= 512 scores; pass 2: P V with per-lane fp32 accumulators, folded across the row groups by a fixed xor butterfly.
+// No atomics, a fixed summation order: the same bits on every run.  The slot's own K / V row is taken from LDS, where the new rows are
+// staged (rounded once in bf16 mode: what the cache then holds), never read back from the cache row the same wave has just written.
+// len[] is NOT advanced here: every site of a step reads the same count, m2f_launch_stream_advance closes the step.
+#include "common.h"
+#include "ops.h"
+
+namespace {
+
+template <bool BF16> struct Row;
+template <> struct Row<false> {
+    static constexpr int EPL = 4;                 // elements per lane and 16-byte access
+    typedef float elem_t;
+    __device__ static __forceinline__ void load(const elem_t* p, float (&x)[4]) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+    }
+    __device__ static __forceinline__ void store(elem_t* p, const float (&x)[4]) {
+        const f32x4 v = {x[0], x[1], x[2], x[3]};
+        *reinterpret_cast<f32x4*>(p) = v;
+    }
+};
+template <> struct Row<true> {
+    static constexpr int EPL = 8;
+    typedef uint16_t elem_t;
+    __device__ static __forceinline__ void load(const elem_t* p, float (&x)[8]) {
+        const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = __builtin_bit_cast(float, v[i] << 16);
+            x[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xffff0000u);
+        }
+    }
+    __device__ static __forceinline__ void store(elem_t* p, const float (&x)[8]) {       // (x: already bf16 values)
+        u32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (uint32_t)m2f_bf16_bits(x[2 * i]) | ((uint32_t)m2f_bf16_bits(x[2 * i + 1]) << 16);
+        *reinterpret_cast<u32x4*>(p) = v;
+    }
+};
+
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
+    typedef Row<BF16> R;
+    typedef typename R::elem_t elem_t;
+    constexpr int EPL = R::EPL;
+    constexpr int U = 4;                          // passes in flight: their loads are issued together
+    __shared__ float sq[128], sk[128], sv[128];   // the slot's new rows of this head, zero behind hd (bf16 mode: rounded)
+    __shared__ float sc[M2F_ATTN_STREAM_MAX_C];   // scores, then the unnormalised probabilities
+
+    const int blk = blockIdx.x, lane = threadIdx.x;
+    int pi = 0;
+    while (pi + 1 < ab.count && blk >= ab.bb[pi + 1]) ++pi;
+    const AttnStreamProblem& P = ab.pr[pi];
+    const int local = blk - ab.bb[pi];
+    const int s = local / P.H, h = local - s * P.H;
+    const int hd = P.hd, C = ab.C;
+    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    float* orow = P.out + (size_t)s * P.ldo + (size_t)h * hd;
+    uint16_t* orow16 = m2f_shadow_of(ab.sh, orow);
+
+    const int n_old = ab.len[s];
+    const bool live = ab.active[s] != 0 && n_old >= 0 && (ab.ring || n_old < C);
+    if (!live) {                                  // inactive slot: a zero output row, cache and len untouched
+        for (int i = lane; i < hd; i += 64) {
+            orow[i] = 0.f;
+            if (orow16) orow16[i] = 0;
+        }
+        return;
+    }
+    const int pos = ab.ring ? n_old % C : n_old;              // the row the new utterance takes
+    const int nslots = n_old + 1 < C ? n_old + 1 : C;         // live rows, the new one included
+
+    {   // the new rows -> LDS
+        const float* qrow = P.q + (size_t)s * P.ldq + (size_t)h * hd;
+        const float* krow = P.k + (size_t)s * P.ldk + (size_t)h * hd;
+        const float* vrow = P.v + (size_t)s * P.ldv + (size_t)h * hd;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int i = lane + 64 * t;
+            float a = 0.f, b = 0.f, c = 0.f;
+            if (i < hd) { a = qrow[i]; b = krow[i]; c = vrow[i]; }
+            if (BF16) { a = m2f_bf16_to_f32(m2f_bf16_bits(a)); b = m2f_bf16_to_f32(m2f_bf16_bits(b)); c = m2f_bf16_to_f32(m2f_bf16_bits(c)); }
+            sq[i] = a; sk[i] = b; sv[i] = c;
+        }
+    }
+    __syncthreads();
+
+    const int nch = hdp / EPL;                    // 16-byte chunks per row
+    int CH = 1, lg = 0;
+    while (CH < nch) { CH <<= 1; ++lg; }          // lanes per row (<= 32: hd <= 128)
+    const int RPW = 64 >> lg;                     // rows per pass
+    const int r = lane >> lg, c = lane & (CH - 1);
+    const bool cact = c < nch;
+    const int e0 = c * EPL;                       // (< 128 for every lane: CH * EPL <= 128)
+
+    elem_t* kc = static_cast<elem_t*>(P.kcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    elem_t* vc = static_cast<elem_t*>(P.vcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    if (r == 0 && cact) {                         // the new K / V rows into the cache (vector stores; pad columns: zeros)
+        float kx[EPL], vx[EPL];
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) { kx[i] = sk[e0 + i]; vx[i] = sv[e0 + i]; }
+        R::store(kc + (size_t)pos * hdp + e0, kx);
+        R::store(vc + (size_t)pos * hdp + e0, vx);
+    }
+
+    float qx[EPL];
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) qx[i] = sq[e0 + i];
+    const float scale = 1.0f / sqrtf((float)hd);
+
+    // ---- pass 1: scores ---------------------------------------------------------------------------------------------------------
+    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
+        float kx[U][EPL];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) kx[u][i] = 0.f;
+            if (cact && j < nslots) {
+                if (j != pos) R::load(kc + (size_t)j * hdp + e0, kx[u]);
+                else {
+#pragma unroll
+                    for (int i = 0; i < EPL; ++i) kx[u][i] = sk[e0 + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) d = fmaf(qx[i], kx[u][i], d);
+            for (int o = CH >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+            if (c == 0 && j < nslots) sc[j] = d * scale;
+        }
+    }
+    __syncthreads();
+
+    // ---- softmax over the live rows (fp32, max-subtracted) ------------------------------------------------------------------------
+    float m = -INFINITY;
+    for (int j = lane; j < nslots; j += 64) m = fmaxf(m, sc[j]);
+    m = m2f_wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < nslots; j += 64) {
+        const float e = __expf(sc[j] - m);
+        sc[j] = e;
+        sum += e;
+    }
+    sum = m2f_wave_sum(sum);
+    const float inv = 1.0f / sum;                 // (sum >= 1: the row of the maximum contributes exp(0))
+    __syncthreads();
+
+    // ---- pass 2: P V ---------------------------------------------------------------------------------------------------------------
+    float acc[EPL];
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
+    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
+        float vx[U][EPL], p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) vx[u][i] = 0.f;
+            p[u] = 0.f;
+            if (cact && j < nslots) {
+                p[u] = sc[j];
+                if (j != pos) R::load(vc + (size_t)j * hdp + e0, vx[u]);
+                else {
+#pragma unroll
+                    for (int i = 0; i < EPL; ++i) vx[u][i] = sv[e0 + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) acc[i] = fmaf(p[u], vx[u][i], acc[i]);
+    }
+    for (int o = CH; o < 64; o <<= 1) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
+    }
+    if (r == 0 && cact) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) {
+            if (e0 + i < hd) {
+                const float o = acc[i] * inv;
+                orow[e0 + i] = o;
+                if (orow16) orow16[e0 + i] = m2f_bf16_bits(o);
+            }
+        }
+    }
+}
+
+// len[s] += active[s]: the one launch that closes a step
+__global__ void m2f_stream_advance_kernel(int* len, const uint8_t* active, int S) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S && active[s]) len[s] = len[s] + 1;
+}
+// len[s] = 0 for the slots of the mask (null: every slot)
+__global__ void m2f_stream_reset_kernel(int* len, const uint8_t* mask, int S) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S && (!mask || mask[s])) len[s] = 0;
+}
+
+}  // namespace
+
+size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16) {
+    const int hdp = bf16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    return (size_t)S * H * C * hdp;
+}
+
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream) {
+    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || !ab.len || !ab.active)
+        return hipErrorInvalidValue;
+    int blocks = 0;
+    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
+    for (int i = 0; i < ab.count; ++i) {
+        AttnStreamProblem& p = ab.pr[i];
+        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
+        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
+        p.block_begin = blocks;
+        ab.bb[i] = blocks;
+        blocks += ab.S * p.H;
+    }
+    if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab);
+    else hipLaunchKernelGGL(m2f_attn_stream_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream) {
+    hipLaunchKernelGGL(m2f_stream_advance_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, active, S);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStream_t stream) {
+    hipLaunchKernelGGL(m2f_stream_reset_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, mask, S);
+    return hipGetLastError();
+}

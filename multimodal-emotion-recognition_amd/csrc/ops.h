@@ -241,6 +241,34 @@ bool m2f_attn_dlong_index_ok(int B, int H, int L);
 hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream);
 hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream);
 
+// Streaming attention (attention_stream.hip): one new utterance per stream slot against the slot's cached K / V rows.  q / k / v: the
+// new rows [S, H*hd] (fp32, column slices with a leading dimension, as AttnProblem carries them); kcache / vcache: the site's caches,
+// [S][H][C][pad4(hd)] fp32 or [S][H][C][pad8(hd)] bf16 (16-byte aligned).  len[s] = utterances cached so far (read, not advanced),
+// active[s] = 0: zero output row, nothing else touched.  ring: the new row goes to len % C and min(len + 1, C) rows are live (a window
+// of C - 1 past utterances); otherwise to row len, and a slot with len >= C is treated as inactive (the host refuses it first).
+#define M2F_ATTN_STREAM_MAX_C 512
+struct AttnStreamProblem {
+    const float* q; const float* k; const float* v;
+    int ldq, ldk, ldv;
+    float* out; int ldo;
+    void* kcache; void* vcache;
+    int H, hd;
+    int block_begin;                                   // filled by the launcher
+};
+struct AttnStreamBatch {
+    int bb[M2F_ATTN_MAX_PROBLEMS];      // block_begin of problem i (INT_MAX for unused slots)
+    AttnStreamProblem pr[M2F_ATTN_MAX_PROBLEMS];
+    int count;
+    int S, C, ring, bf16;      // bf16: caches hold bf16 (K / V rounded once on the way in), q is rounded where it enters the product
+    const int* len;            // device int32 [S]
+    const uint8_t* active;     // device uint8 [S]
+    ShadowMap sh;              // out also written as bf16
+};
+size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16);     // elements (fp32 or bf16) of ONE cache (K or V) of a site
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream);
+hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream);      // len[s] += active[s]
+hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStream_t stream);          // len[s] = 0 where mask[s] (null: all)
+
 // ------------------------------------------------------------------------------------------------
 // Row-wise kernels
 // ------------------------------------------------------------------------------------------------

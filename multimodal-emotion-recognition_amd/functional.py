@@ -130,6 +130,40 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     return out, probs
 
 
+def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool = False, device="cuda", fill: float = 0.0):
+    """(kcache, vcache) of one streaming-attention site: flat tensors viewed [S, H, capacity, pad(hd)], fp32 (pad to 4) or bf16 (pad to
+    8), filled with `fill`."""
+    n = lib().m2f_attention_stream_cache_elems(S, H, hd, capacity, int(bf16))
+    if n < 0:
+        raise runtime.HipError("m2f_attention_stream_cache_elems: " + lib().m2f_last_error().decode())
+    hdp = (hd + 7) // 8 * 8 if bf16 else (hd + 3) // 4 * 4
+    dt = torch.bfloat16 if bf16 else torch.float32
+    return tuple(torch.full((S, H, capacity, hdp), fill, dtype=dt, device=device) for _ in range(2))
+
+
+def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, lengths: torch.Tensor,
+                     active: torch.Tensor, H: int, ring: bool = False, bf16: bool = False) -> torch.Tensor:
+    """One streaming-attention launch (m2f_attention_stream): slot s takes the new rows q[s] / k[s] / v[s] ([S, H*hd] fp32, possibly column
+    slices) against the rows it has cached.  kcache / vcache: `attention_stream_caches`; lengths int32 [S] = utterances cached so far
+    (read, NOT advanced); active uint8 / bool [S].  An active slot stores its new K / V rows at row lengths % capacity (ring) or
+    lengths (lengths < capacity required) and gets softmax(q K^T / sqrt(hd)) V over its min(lengths + 1, capacity) live rows; an
+    inactive slot gets a zero row and its caches stay as they are.  Returns out [S, H*hd]."""
+    runtime.require_gpu()
+    S, E = q.shape
+    hd = E // H
+    C = kcache.shape[2]
+    want = torch.bfloat16 if bf16 else torch.float32
+    if kcache.dtype != want or vcache.dtype != want or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError("attention_stream: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
+    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
+        raise ValueError("attention_stream: lengths int32 [S] and active [S] required")
+    act = active.to(torch.uint8).contiguous()
+    out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
+                                     ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream")
+    return out
+
+
 def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, drop_site: int = 0, drop_p: float = 0.0,
                   rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
                   future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -599,6 +599,29 @@ class M2FNet(nn.Module):
         else:
             body()
 
+    # -- streaming inference (one new utterance per live dialogue; streaming.DialogueStream) -----------------------------------------
+    def stream(self, max_streams: int, capacity: Optional[int] = None, use_graph: bool = True):
+        """A ``DialogueStream`` of ``max_streams`` slots over this model's weights: ``stream.step(text [S, d_t], audio [S, d_a],
+        active)`` labels the utterance that has just arrived in each active slot from per-site K / V caches on the device, at the
+        cost of one row per dialogue - where ``forward`` would re-run the whole prefix.  Needs a causal context band
+        (``context=(past, 0)``: a band that looks ahead cannot stream) and eval mode (or dropout = 0).
+        capacity: cache rows per slot and site, 1 .. 512; default ``past + 1`` for a window (a ring: no length limit; a smaller value is
+        raised to it) and 512 for ``past=None`` (the most utterances a slot can then hold).  The caches cost
+        ``2 * sum_sites pad(d_site) * max_streams * capacity * 4 B`` (bf16 mode: 2 B per element): 3.8 GB at C3, 64 streams, capacity 512.
+        They belong to the weights that wrote them - after ``load_state_dict``, an optimizer step or ``averaged_parameters()`` call
+        ``stream.reset()``.  Every refusal is raised before the GPU is touched."""
+        from .streaming import DialogueStream, resolve_capacity
+        past, future = self._context
+        if future != 0:
+            raise ValueError(f"M2FNet.stream: streaming needs a causal context band (past, 0), this model has context={self._context}; "
+                             "a band that looks ahead cannot label an utterance when it arrives (M2FNet(config, context=(past, 0)))")
+        if self.training and self.m2f_config.dropout > 0.0:
+            raise RuntimeError("M2FNet.stream: the model is in training mode with dropout > 0; a stream scores the model "
+                               "without dropout - call model.eval() first")
+        if isinstance(max_streams, bool) or not isinstance(max_streams, int) or max_streams < 1:
+            raise ValueError(f"M2FNet.stream: max_streams must be an integer >= 1, got {max_streams!r}")
+        return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph)
+
     def set_grad_bf16(self, on: bool = True) -> bool:
         """bf16 mode: every following training step leaves its gradients ROUNDED ONCE TO BF16 in one flat bf16 buffer - the weight-gradient
         launch writes bf16 dW directly, one cast launch rounds the rest - and ``FusedAdam`` reads that buffer (fp32 moments and parameters as

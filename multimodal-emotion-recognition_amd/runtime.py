@@ -24,7 +24,7 @@ HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "m2fnet_hip.h
 F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
- BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO) = range(12)
+ BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE) = range(14)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -130,6 +130,14 @@ SIGNATURES = {
                                               c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
     "m2f_plan_attention_band": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_get_attention_band": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "m2f_stream_workspace_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int]),
+    "m2f_plan_create_stream": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_stream_step": (c_int, [c_void_p, c_int, c_void_p]),
+    "m2f_stream_reset": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "m2f_stream_cache_bytes": (c_int64, [c_void_p]),
+    "m2f_attention_stream_cache_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "m2f_attention_stream": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_attention_varlen_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_varlen_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
@@ -658,6 +666,77 @@ class Plan:
 
     def close(self) -> None:
         """Destroy the plan (captured graph, launch lists) and drop its workspace."""
+        h = getattr(self, "handle", None)
+        if h and _lib is not None:
+            _lib.m2f_plan_destroy(h)
+        self.handle = None
+        self.workspace = None
+
+    def __del__(self):
+        self.close()
+
+
+class StreamPlan:
+    """One stream plan (m2f_plan_create_stream) + its workspace: `S` stream slots, K / V caches of `capacity` rows per slot at every
+    attention site (a ring when `past` is an integer).  `streaming.DialogueStream` drives it."""
+
+    def __init__(self, cfg: M2FConfig, S: int, capacity: int, past: Optional[int], precision: int, params: torch.Tensor,
+                 param_shadow: Optional[torch.Tensor] = None):
+        require_gpu()
+        with torch.inference_mode(False):          # (a stream opened under inference_mode must stay writable outside it)
+            self._create(cfg, S, capacity, past, precision, params, param_shadow)
+
+    def _create(self, cfg, S, capacity, past, precision, params, param_shadow) -> None:
+        self.cfg, self.S, self.capacity, self.past, self.precision = cfg, S, capacity, past, precision
+        self._cc = config_to_c(cfg)
+        self.shared_shadow = param_shadow is not None
+        self._fresh = False
+        past_c = -1 if past is None else int(past)
+        nbytes = lib().m2f_stream_workspace_bytes(ctypes.byref(self._cc), S, capacity, past_c, precision, int(self.shared_shadow))
+        if nbytes < 0:
+            raise HipError("m2f_stream_workspace_bytes: " + lib().m2f_last_error().decode())
+        self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=params.device)
+        torch.cuda.current_stream(params.device).synchronize()       # (as Plan: the create call uses blocking copies on the null stream)
+        base = self.workspace.data_ptr()
+        off = (-base) % 256
+        self._keep = (params, param_shadow)
+        self.handle = lib().m2f_plan_create_stream(ctypes.byref(self._cc), S, capacity, past_c, precision, params.data_ptr(), base + off,
+                                                   nbytes, ptr(param_shadow))
+        if not self.handle:
+            raise HipError("m2f_plan_create_stream: " + lib().m2f_last_error().decode())
+        pad8 = lambda w: (w + 7) // 8 * 8
+        self.text_in = self._view(BUF_TEXT, (S, pad8(max(cfg.d_text, 1))), torch.float32)[:, : max(cfg.d_text, 1)]
+        self.audio_in = self._view(BUF_AUDIO, (S, pad8(max(cfg.d_audio, 1))), torch.float32)[:, : max(cfg.d_audio, 1)]
+        self.logits = self._view(BUF_LOGITS, (S, cfg.cls_out), torch.float32)
+        self.len = self._view(BUF_STREAM_LEN, (S,), torch.int32)
+        self.active = self._view(BUF_STREAM_ACTIVE, (S,), torch.uint8)
+
+    _h = Plan._h
+    _view = Plan._view
+
+    def params_fresh(self, fresh: bool) -> None:
+        fresh = bool(fresh) and self.shared_shadow
+        if fresh != self._fresh:
+            check(lib().m2f_plan_params_fresh(self._h(), int(fresh)), "m2f_plan_params_fresh")
+            self._fresh = fresh
+
+    def step(self, use_graph: bool = True) -> None:
+        check(lib().m2f_stream_step(self._h(), int(use_graph), stream_ptr()), "m2f_stream_step")
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """mask: device uint8 [S], non-zero = the slot starts a new dialogue; None = every slot."""
+        check(lib().m2f_stream_reset(self._h(), ptr(mask), stream_ptr()), "m2f_stream_reset")
+
+    def cache_bytes(self) -> int:
+        return int(lib().m2f_stream_cache_bytes(self._h()))
+
+    def num_launches(self) -> int:
+        return lib().m2f_plan_num_launches(self._h(), 0) + 1
+
+    def nbytes(self) -> int:
+        return self.workspace.numel()
+
+    def close(self) -> None:
         h = getattr(self, "handle", None)
         if h and _lib is not None:
             _lib.m2f_plan_destroy(h)

@@ -40,11 +40,48 @@ def load_model_weights(model, checkpoint_path, device, averaged: bool = False):
     return state.get("epoch")
 
 
+def streaming_settings(config):
+    """`runtime.streaming`: True = test() scores every batch through a `DialogueStream` (M2FNet.stream) - each utterance labelled when it
+    arrives, from the K / V caches of the utterances before it - instead of `forward`.  Needs a causal `runtime.context` (future: 0): a
+    band that looks ahead cannot stream.  -> bool; checked on the host before the GPU is touched."""
+    from train import _runtime, context_settings
+    if not bool(_runtime(config, "streaming", False)):
+        return False
+    band = context_settings(config)
+    if band is None or band[1] != 0:
+        raise ValueError("runtime.streaming needs a causal runtime.context ({past: null or k, future: 0}): a band that looks ahead "
+                         f"cannot label an utterance when it arrives (got {None if band is None else dict(past=band[0], future=band[1])})")
+    return True
+
+
+def _stream_for(model, B, L):
+    """The model's test stream, opened (again) when a batch has more dialogues or - without a window - longer ones than it holds."""
+    st = getattr(model, "_test_stream", None)
+    windowed = model.context[0] is not None
+    if st is None or st.max_streams < B or (not windowed and st.capacity < L):
+        if st is not None:
+            st.close()
+        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64))
+        model._test_stream = st
+    return st
+
+
 def test(model, dl_test, device):
     """-> (accuracy, weighted_f1) over the loader, per-batch scores averaged unweighted.
+    With ``model.streaming`` (runtime.streaming) every batch goes through ``DialogueStream.run`` - column by column, one new utterance per
+    dialogue and step - and its logits are scored as the batched pass's are (on the host).
     With ``model.device_metrics`` (runtime.device_metrics) every batch is scored on the device (``M2FNet.eval_step``) and the host
     reads the record once; ``model.test_scores`` then holds the pass's ``DeviceScores`` (confusion matrix, per-class report)."""
     model.eval()
+    if getattr(model, "streaming", False):
+        scores = BatchScores()
+        with torch.inference_mode():
+            for batch in tqdm(dl_test, total=len(dl_test)):
+                text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
+                                                               audio_encoder=getattr(model, "audio_encoder", None))
+                stream = _stream_for(model, *padding_mask.shape)
+                scores.update(stream.run(text, audio, padding_mask), emotion)
+        return scores.result()
     if getattr(model, "device_metrics", False):
         from mer_amd.metrics import DeviceScores
         scores = DeviceScores(model.m2f_config.cls_out, device)
@@ -82,6 +119,7 @@ def main(config=None):
     config = get_config()
     from train import context_settings
     context_settings(config)                               # (refusal before the GPU is touched)
+    streaming = streaming_settings(config)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     print(f"Using device {device}...")
     runtime_cfg = config.get("runtime", {}) or {}
@@ -91,6 +129,7 @@ def main(config=None):
         loader = torch.utils.data.DataLoader(Dataset(mode="test"), collate_fn=collate_fn, **config.test.data_loader)
     model = build_model(config, device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
+    model.streaming = streaming
     from train import ema_settings
     ema = ema_settings(config)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
