@@ -55,7 +55,8 @@ enum {
     M2F_BUF_DAUDIO = 11,    /* float [B*L, pad8(d_audio)] output d loss / d audio (audio.grad, src/model.py:103-107; same rows as M2F_BUF_AUDIO)  */
     M2F_BUF_STREAM_LEN = 12,    /* int32 [S]  stream plans: utterances cached per stream slot (advanced by m2f_stream_step, zeroed by m2f_stream_reset) */
     M2F_BUF_STREAM_ACTIVE = 13, /* uint8 [S]  stream plans, input: 1 = the slot takes an utterance in the next m2f_stream_step */
-    M2F_BUF_COUNT = 14
+    M2F_BUF_STREAM_NEW = 14,    /* int32 [S]  chunk plans, input: utterances (0 .. T) the slot takes in the next m2f_stream_prefill */
+    M2F_BUF_COUNT = 15
 };
 
 const char* m2f_last_error(void);
@@ -162,6 +163,22 @@ m2f_plan* m2f_plan_create_stream(const m2f_config* cfg, int S, int C, int past, 
 int m2f_stream_step(m2f_plan* plan, int use_graph, m2f_stream_t stream);
 int m2f_stream_reset(m2f_plan* plan, const uint8_t* slot_mask, m2f_stream_t stream);
 int64_t m2f_stream_cache_bytes(m2f_plan* plan);          /* bytes of all K / V caches of the plan */
+/* CHUNK plan: the other half of the cache interface - UP TO T NEW UTTERANCES PER SLOT in one call (2 <= T <= 64), for loading a history
+ * into the caches at the cost of a forward over S * T rows instead of one launch-bound step per utterance.  It is an eval plan of B = S,
+ * L = T rows over the caches and counts of `parent`, a stream plan (it allocates no cache; same configuration, precision, capacity
+ * and band: m2f_plan_get_attention_band reports the parent's; the parent must outlive it and is not changed in any way).  Slot s takes
+ * its first n[s] rows - rows s*T + t, t < n[s], of M2F_BUF_TEXT / M2F_BUF_AUDIO ([S*T, pad8(d)]); n = M2F_BUF_STREAM_NEW, int32 [S],
+ * 0 .. T - and leaves their logits in the same rows of M2F_BUF_LOGITS; rows t >= n[s] must hold finite values, their logits mean
+ * nothing.  Every attention site runs m2f_attention_stream_chunk's kernel: row t attends to what the slot has cached and to the
+ * chunk's rows <= t under the band, exactly as n[s] steps would, and the rows' K / V are stored for the steps and chunks that
+ * follow.  past < 0: count[s] + n[s] <= C is the caller's to ensure (the kernel leaves such a slot untouched and returns zero rows).
+ * m2f_stream_prefill: forward + count[s] += n[s]; use_graph = 1 replays one captured graph of the chunk plan's own.  Steps of the
+ * parent and chunk calls interleave freely on one HIP stream.  M2F_BUF_STREAM_LEN of a chunk plan is the parent's buffer.
+ * m2f_stream_step, m2f_stream_reset and m2f_stream_cache_bytes refuse a chunk plan (the last returns -1: it owns no cache). */
+int64_t m2f_stream_chunk_workspace_bytes(m2f_plan* parent, int T, int shared);
+m2f_plan* m2f_plan_create_stream_chunk(m2f_plan* parent, int T, float* params, void* workspace, int64_t workspace_bytes,
+                                       uint16_t* param_shadow);
+int m2f_stream_prefill(m2f_plan* plan, int use_graph, m2f_stream_t stream);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -574,6 +591,16 @@ int64_t m2f_attention_stream_cache_elems(int S, int H, int hd, int C, int bf16);
 int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                          void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
                          int bf16, m2f_stream_t stream);
+/* The chunk form, one launch (csrc/attention_stream_chunk.hip): slot s takes n_new[s] (device int32, 0 .. T, T <= 64) new utterances -
+ * rows s*T + t of q / k / v / out [S*T, H*hd] - and gets, row by row, what n_new[s] launches of m2f_attention_stream give: row t
+ * attends to the chunk's rows <= t and to the cached utterances (ring != 0: to the last C - 1 utterances before it only), the chunk's
+ * own keys and values taken from the rows given (bf16 != 0: rounded once), never through the cache.  The new K / V rows are stored
+ * at rows (count + t) % C (ring) or count + t (ring == 0; count + n_new <= C required, else the slot is left untouched) after the
+ * launch's last cache read; of n_new > C rows on a ring the last C.  Output rows t >= n_new[s] are zeros and their input rows are
+ * never read; n_new[s] == 0 leaves the slot's caches untouched.  count is NOT advanced. */
+int m2f_attention_stream_chunk(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               void* kcache, void* vcache, int C, int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo,
+                               int bf16, m2f_stream_t stream);
 /* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
  * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
  * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this

@@ -1,0 +1,359 @@
+// Streaming ("prefill") dialogue attention on gfx950: UP TO T NEW UTTERANCES per live dialogue in one launch, against that dialogue's
+// cached keys / values and against each other under the stream's band.
+//
+// The problem is (stream slot s, head h): the slot's n_new[s] (0 .. T, T <= 64) new query rows - rows s*T + t of q / k / v - against the
+// n_old = len[s] utterances the slot has cached plus the chunk's own rows.  The defining rule is attention_stream.hip's, row by row: a
+// chunk of n rows gives what n single-row launches give.  Query t is utterance u = n_old + t; it sees the chunk's rows <= t and
+//   * plain cache: every cached utterance (n_old + n_new <= C required: a slot that would pass C is treated as not live);
+//   * ring of C rows (a window of C - 1): the utterances u - (C - 1) .. u only; utterance j lives in cache row j % C.
+// Cache layout, padding and element types are attention_stream.hip's (cache[S][H][C][hdp], fp32 or bf16): a step and a chunk call
+// interleave on the same caches.
+//
+// One workgroup of 4 waves per (s, h), the shape and arithmetic of attention_dlong.hip's forward with one query block: wave w owns the
+// queries 16w .. 16w + 15, exact-fp32 MFMA v_mfma_f32_16x16x4_f32, S^T = K Q^T so that the probabilities come out in the layout that is
+// the A operand of P V.  Q and the chunk's own K / V stay in LDS for the whole launch (bf16 mode: rounded there once - the values the
+// cache will hold); the cached rows stream through a fourth slab in 64-row blocks (bf16 caches are widened on the way in), in cache-row
+// order.  Two passes over the keys - row max and normaliser, then P and O += P V - in fp32, scale applied to the fp32 product.
+// The chunk's own keys are NEVER read through the cache.  On a ring the new rows overwrite rows that earlier queries of the same chunk
+// still need, so every store of a new row comes after the workgroup's last cache read, behind a barrier; of n_new > C new rows only
+// the last C are stored (the others would be overwritten inside the launch).  The row a ring is about to recycle for the chunk's
+// first utterance is dead to every query and is not read at all.  No atomics, one summation order: the same bits on every run.
+// len[] is NOT advanced here: every site of a prefill call reads the same counts, m2f_launch_stream_advance_n closes the call.
+#include "common.h"
+#include <algorithm>
+#include <type_traits>
+#include "ops.h"
+
+// (see attention.hip: no floating-point contraction, so every form of a formula rounds the same way)
+#pragma clang fp contract(off)
+
+namespace {
+
+#include "attn_slab.h"
+
+constexpr int BLK = 64;            // rows of the query block / of a key block
+constexpr int NV = 8;              // float4 per thread of a [BLK x 128] slab
+
+__device__ __forceinline__ float round_bf16(float x) { return m2f_bf16_to_f32(m2f_bf16_bits(x)); }
+
+// rows [0, n) x cols [0, hd) of a strided fp32 operand into a zero-padded [BLK x W] slab (bf16 mode: rounded once); rows >= n are
+// never read
+template <bool BF16>
+__device__ __forceinline__ void stage_new(float* __restrict__ lds, const float* __restrict__ src, int ldg, int n, int hd, int W, int ld,
+                                          int tid) {
+    if (slab_fast_ok<NV>(src, ldg, hd, BLK, W)) {
+        SlabGeom<NV> G;
+        slab_geom(G, n, hd, BLK, W, ld, tid);
+        SlabRegs<NV> R;
+        slab_issue(R, G, src, ldg);
+        if (BF16) {
+#pragma unroll
+            for (int u = 0; u < NV; ++u)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) R.x[u][i] = round_bf16(R.x[u][i]);
+        }
+        slab_commit(R, G, lds);
+        return;
+    }
+    const int total = BLK * W;
+#pragma unroll 1
+    for (int base = 0; base < total; base += NTHR * 4) {
+        float x[4];
+        int off[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = base + tid + NTHR * u;
+            const int r = e / W, c = e - r * W;
+            const bool ok = e < total && r < n && c < hd;
+            off[u] = e < total ? r * ld + c : -1;
+            x[u] = src[ok ? (size_t)r * ldg + c : (size_t)0];
+            x[u] = ok ? (BF16 ? round_bf16(x[u]) : x[u]) : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (off[u] >= 0) lds[off[u]] = x[u];
+    }
+}
+
+// cache rows [r0, r0 + n) of one (slot, head) into a zero-padded [BLK x W] slab; the row `dead` (absolute; -1: none) is not read.
+// Rows are hdp elements wide and 16-byte aligned, their pad columns hold zeros.
+template <bool BF16>
+__device__ __forceinline__ void stage_cache(float* __restrict__ lds, const void* __restrict__ cache, int r0, int n, int dead, int hdp,
+                                            int W, int ld, int tid) {
+    SlabGeom<NV> G;
+    slab_geom(G, n, hdp, BLK, W, ld, tid);
+#pragma unroll
+    for (int u = 0; u < NV; ++u) G.ok[u] = G.ok[u] && (r0 + (G.goff_rc[u] >> 16)) != dead;
+    SlabRegs<NV> R;
+    if (BF16) slab_issue16(R, G, static_cast<const uint16_t*>(cache) + (size_t)r0 * hdp, hdp);
+    else slab_issue(R, G, static_cast<const float*>(cache) + (size_t)r0 * hdp, hdp);
+    slab_commit(R, G, lds, BF16);
+}
+
+// C[m][n] = sum_c A[row m][c] B[row n][c] over the head dim (attention_dlong.hip) -> lane holds C[4 lg + r][l15]
+__device__ __forceinline__ f32x4 dot_tile(const float* as, const float* brow, int ksteps) {
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    int ks = 0;
+    for (; ks + 1 < ksteps; ks += 2) {
+        acc0 = mfma4(as[4 * ks], brow[4 * ks], acc0);
+        acc1 = mfma4(as[4 * ks + 4], brow[4 * ks + 4], acc1);
+    }
+    if (ks < ksteps) acc0 = mfma4(as[4 * ks], brow[4 * ks], acc0);
+    return acc0 + acc1;
+}
+
+// What query i of the chunk sees.  Cached rows are walked in cache-row order; on a ring row r holds the utterance that is d(r) places
+// behind the oldest live one, d(r) = (r - p0) mod C, p0 = the oldest live utterance's row.
+struct Vis {
+    int ring, C, nlive, p0, n_new;
+    // cache row r (r < nlive: it holds a live utterance) - its utterance j = n_old - nlive + d, visible iff j >= n_old + i - (C - 1)
+    __device__ __forceinline__ bool cached(int i, int r) const {
+        if (r >= nlive) return false;
+        if (!ring) return true;
+        const int d = r - p0 + (r < p0 ? C : 0);
+        return d >= i + nlive - C + 1;
+    }
+    // chunk row t
+    __device__ __forceinline__ bool own(int i, int t) const { return t < n_new && t <= i && (!ring || t >= i - (C - 1)); }
+};
+
+template <bool BF16>
+__global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnStreamBatch ab, const int T, const int* __restrict__ new_count) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    typedef typename std::conditional<BF16, uint16_t, float>::type elem_t;
+    constexpr int EPL = BF16 ? 8 : 4;                       // elements of a 16-byte access
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < M2F_ATTN_MAX_PROBLEMS; ++i)
+        if ((int)blockIdx.x >= ab.bb[i]) pi = i;
+    const AttnStreamProblem& P = ab.pr[pi];
+    const int local = (int)blockIdx.x - ab.bb[pi];
+    const int s = local / P.H, h = local - s * P.H;
+    const int hd = P.hd, C = ab.C, W = (hd + 15) & ~15, ld = W + 2, CT = W >> 4;
+    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    const size_t row0 = (size_t)s * T;                      // the slot's first row of q / k / v / out
+    uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
+
+    const int n_old = ab.len[s];
+    const int n_new = min(new_count[s], T);
+    const bool live = n_new > 0 && n_old >= 0 && (ab.ring || (n_old <= C && n_new <= C - n_old));
+    {   // rows that take nothing: zero output rows
+        const int first = live ? n_new : 0;
+        for (int e = tid; e < (T - first) * hd; e += NTHR) {
+            const int t = e / hd, c = e - t * hd;
+            const size_t idx = (row0 + first + t) * P.ldo + (size_t)h * hd + c;
+            P.out[idx] = 0.f;
+            if (out16) out16[idx] = 0;
+        }
+    }
+    if (!live) return;                                      // cache and len untouched
+
+    float* Qs = sm;
+    float* Ks = Qs + BLK * ld;                              // the chunk's own K / V: resident (what the cache will hold)
+    float* Vs = Ks + BLK * ld;
+    float* KV = Vs + BLK * ld;                              // cached K, then V, of the current block
+    stage_new<BF16>(Qs, P.q + row0 * P.ldq + (size_t)h * hd, P.ldq, n_new, hd, W, ld, tid);
+    stage_new<BF16>(Ks, P.k + row0 * P.ldk + (size_t)h * hd, P.ldk, n_new, hd, W, ld, tid);
+    stage_new<BF16>(Vs, P.v + row0 * P.ldv + (size_t)h * hd, P.ldv, n_new, hd, W, ld, tid);
+
+    elem_t* kc = static_cast<elem_t*>(P.kcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    elem_t* vc = static_cast<elem_t*>(P.vcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    const int nlive = min(n_old, C);                        // cache rows that hold a live utterance (ring: the last C)
+    Vis vis;
+    vis.ring = ab.ring; vis.C = C; vis.nlive = nlive; vis.p0 = ab.ring ? (n_old - nlive) % C : 0; vis.n_new = n_new;
+    const int dead = (ab.ring && nlive == C) ? vis.p0 : -1; // the row the chunk's first utterance recycles: outside every query's window
+
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int ksteps = (hd + 3) >> 2;
+    const int i = 16 * wv + l15;                            // this lane's query
+    const bool wave_on = 16 * wv < n_new;                   // (wave-uniform: a wave without a query only stages)
+    const float* qrow = Qs + i * ld + lg;
+    const float* kv_rows = KV + l15 * ld + lg;
+    const float* own_rows = Ks + l15 * ld + lg;
+    __syncthreads();                                        // Q and the chunk's K / V committed
+
+    // ---- pass 1: row max and normaliser -----------------------------------------------------------------------------------------
+    float m_run = -INFINITY, l_run = 0.f;
+    auto stats = [&](const float (&x)[4][4]) {
+        float m_blk = -INFINITY;
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) m_blk = fmaxf(m_blk, x[jt][r]);
+        m_blk = fmaxf(m_blk, __shfl_xor(m_blk, 16, 64));
+        m_blk = fmaxf(m_blk, __shfl_xor(m_blk, 32, 64));
+        const float m_new = fmaxf(m_run, m_blk);
+        float sum = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum += (m_new == -INFINITY) ? 0.f : __expf(x[jt][r] - m_new);
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        l_run = l_run * ((m_new == -INFINITY) ? 1.f : __expf(m_run - m_new)) + sum;
+        m_run = m_new;
+    };
+    for (int kb = 0; kb < nlive; kb += BLK) {
+        __syncthreads();                                    // previous block consumed
+        stage_cache<BF16>(KV, kc, kb, min(BLK, nlive - kb), dead, hdp, W, ld, tid);
+        __syncthreads();
+        if (wave_on) {
+            float x[4][4];
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);      // S[i][j = 16jt + 4lg + r]
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[jt][r] = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+            }
+            stats(x);
+        }
+    }
+    if (wave_on) {                                          // the chunk's own keys, from LDS
+        float x[4][4];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[jt][r] = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+        }
+        stats(x);
+    }
+
+    // ---- pass 2: P = exp(S - m) / l, O += P V ------------------------------------------------------------------------------------------
+    const float inv = (i < n_new && l_run > 0.f) ? 1.0f / l_run : 0.f;     // (a query always sees itself: l_run >= 1 for i < n_new)
+    f32x4 o[8];
+#pragma unroll
+    for (int ct = 0; ct < 8; ++ct) o[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto pv = [&](const float (&p)[4][4], const float* vslab) {
+#pragma unroll
+        for (int ct = 0; ct < 8; ++ct) {                    // static indices keep o[] in registers
+            if (ct >= CT) continue;
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                const float* vp = vslab + (16 * jt + 4 * lg) * ld + 16 * ct + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[ct] = mfma4(p[jt][r], vp[r * ld], o[ct]);
+            }
+        }
+    };
+    for (int kb = 0; kb < nlive; kb += BLK) {
+        const int nk = min(BLK, nlive - kb);
+        __syncthreads();
+        stage_cache<BF16>(KV, kc, kb, nk, dead, hdp, W, ld, tid);
+        __syncthreads();
+        float p[4][4];
+        if (wave_on) {
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float x = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+                    p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;      // (no visible key: exp(-inf + inf) would be NaN)
+                }
+            }
+        }
+        __syncthreads();                                    // K consumed
+        stage_cache<BF16>(KV, vc, kb, nk, dead, hdp, W, ld, tid);
+        __syncthreads();
+        if (wave_on) pv(p, KV);
+    }
+    if (wave_on) {
+        float p[4][4];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float x = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+                p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;
+            }
+        }
+        pv(p, Vs);
+#pragma unroll
+        for (int ct = 0; ct < 8; ++ct) {
+            if (ct >= CT) continue;
+            const int c = 16 * ct + l15;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t = 16 * wv + 4 * lg + r;
+                if (t < n_new && c < hd) {
+                    const size_t idx = (row0 + t) * P.ldo + (size_t)h * hd + c;
+                    P.out[idx] = o[ct][r];
+                    if (out16) out16[idx] = m2f_bf16_bits(o[ct][r]);
+                }
+            }
+        }
+    }
+
+    // ---- the new K / V rows into the cache: behind the workgroup's last cache read ------------------------------------------------
+    __syncthreads();
+    const int nst = min(n_new, C), t0 = n_new - nst;        // (n_new > C on a ring: the earlier rows would be overwritten in this launch)
+    const int nch = hdp / EPL;                              // 16-byte chunks of a row; pad columns: the slab's zeros
+    for (int e = tid; e < nst * nch; e += NTHR) {
+        const int tr = e / nch, c = (e - tr * nch) * EPL, t = t0 + tr;
+        const int pos = ab.ring ? (int)(((unsigned)n_old + (unsigned)t) % (unsigned)C) : n_old + t;
+        const float* kr = Ks + t * ld + c;
+        const float* vr = Vs + t * ld + c;
+        if constexpr (BF16) {
+            u32x4 a, b;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a[q] = (uint32_t)m2f_bf16_bits(kr[2 * q]) | ((uint32_t)m2f_bf16_bits(kr[2 * q + 1]) << 16);       // (kr: already bf16 values)
+                b[q] = (uint32_t)m2f_bf16_bits(vr[2 * q]) | ((uint32_t)m2f_bf16_bits(vr[2 * q + 1]) << 16);
+            }
+            *reinterpret_cast<u32x4*>(kc + (size_t)pos * hdp + c) = a;
+            *reinterpret_cast<u32x4*>(vc + (size_t)pos * hdp + c) = b;
+        } else {
+            *reinterpret_cast<f32x4*>(kc + (size_t)pos * hdp + c) = (f32x4){kr[0], kr[1], kr[2], kr[3]};
+            *reinterpret_cast<f32x4*>(vc + (size_t)pos * hdp + c) = (f32x4){vr[0], vr[1], vr[2], vr[3]};
+        }
+    }
+}
+
+// len[s] += min(max(n_new[s], 0), T): the one launch that closes a prefill call
+__global__ void m2f_stream_advance_n_kernel(int* len, const int* n_new, int S, int T) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S) {
+        const int n = min(max(n_new[s], 0), T);
+        if (n) len[s] = len[s] + n;
+    }
+}
+
+template <typename K>
+hipError_t go(K kern, int blocks, size_t lds, hipStream_t stream, const AttnStreamBatch& ab, int T, const int* n_new) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, ab, T, n_new);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, int T, const int* n_new, hipStream_t stream) {
+    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || !ab.len || !n_new ||
+        T < 1 || T > M2F_ATTN_STREAM_MAX_CHUNK)
+        return hipErrorInvalidValue;
+    int blocks = 0, maxW = 0;
+    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
+    for (int i = 0; i < ab.count; ++i) {
+        AttnStreamProblem& p = ab.pr[i];
+        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
+        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
+        p.block_begin = blocks;
+        ab.bb[i] = blocks;
+        blocks += ab.S * p.H;
+        maxW = std::max(maxW, (p.hd + 15) & ~15);
+    }
+    const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
+    return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true>, blocks, lds, stream, ab, T, n_new)
+                   : go(m2f_attn_stream_chunk_kernel<false>, blocks, lds, stream, ab, T, n_new);
+}
+
+hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream) {
+    hipLaunchKernelGGL(m2f_stream_advance_n_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, n_new, S, T);
+    return hipGetLastError();
+}

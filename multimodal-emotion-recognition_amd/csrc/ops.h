@@ -268,6 +268,13 @@ size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16);     /
 hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream);
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream);      // len[s] += active[s]
 hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStream_t stream);          // len[s] = 0 where mask[s] (null: all)
+// Chunk form (attention_stream_chunk.hip): slot s takes n_new[s] (0 .. T, T <= 64; device int32 [S]) new utterances - rows s*T + t of
+// q / k / v / out - in one launch; what n_new[s] launches of the kernel above give, row by row.  ab.active is not read.  A slot with
+// n_new == 0, or a plain cache that the chunk would overfill (len + n_new > C), gets zero output rows and keeps its cache; output rows
+// t >= n_new[s] are zeros, their input rows are never read.  len is not advanced: m2f_launch_stream_advance_n adds the clamped n_new.
+#define M2F_ATTN_STREAM_MAX_CHUNK 64
+hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, int T, const int* n_new, hipStream_t stream);
+hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream);   // len[s] += min(max(n_new[s], 0), T)
 
 // ------------------------------------------------------------------------------------------------
 // Row-wise kernels

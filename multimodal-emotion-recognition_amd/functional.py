@@ -164,6 +164,30 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
     return out
 
 
+def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                           lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, ring: bool = False, bf16: bool = False) -> torch.Tensor:
+    """One chunk launch of the streaming attention (m2f_attention_stream_chunk): slot s takes its first new[s] (int32 [S], 0 .. T, T <= 64)
+    rows of q / k / v ([S*T, H*hd] fp32, possibly column slices; rows s*T + t) against the rows it has cached - row by row what new[s]
+    `attention_stream` launches give.  lengths int32 [S] is read, NOT advanced.  The new K / V rows go to rows (lengths + t) % capacity
+    (ring) or lengths + t (lengths + new <= capacity required, else the slot is left untouched) - of more than `capacity` rows on a ring
+    the last `capacity`.  Rows t >= new[s] of the result are zeros and their input rows are never read.  Returns out [S*T, H*hd]."""
+    runtime.require_gpu()
+    rows, E = q.shape
+    hd = E // H
+    S, C = kcache.shape[0], kcache.shape[2]
+    want = torch.bfloat16 if bf16 else torch.float32
+    if kcache.dtype != want or vcache.dtype != want or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError("attention_stream_chunk: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
+    if not 1 <= T <= 64 or rows != S * T or k.shape[0] != rows or v.shape[0] != rows:
+        raise ValueError("attention_stream_chunk: q / k / v hold S * T rows, 1 <= T <= 64")
+    if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S:
+        raise ValueError("attention_stream_chunk: lengths int32 [S] and new int32 [S] required")
+    out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream_chunk(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
+                                           ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk")
+    return out
+
+
 def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, drop_site: int = 0, drop_p: float = 0.0,
                   rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
                   future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

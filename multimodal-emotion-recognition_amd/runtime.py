@@ -24,7 +24,7 @@ HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "m2fnet_hip.h
 F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
- BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE) = range(14)
+ BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW) = range(15)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -138,6 +138,11 @@ SIGNATURES = {
     "m2f_attention_stream_cache_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "m2f_attention_stream": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                      c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_stream_chunk_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "m2f_plan_create_stream_chunk": (c_void_p, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_stream_prefill": (c_int, [c_void_p, c_int, c_void_p]),
+    "m2f_attention_stream_chunk": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_attention_varlen_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_varlen_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
@@ -742,6 +747,58 @@ class StreamPlan:
             _lib.m2f_plan_destroy(h)
         self.handle = None
         self.workspace = None
+
+    def __del__(self):
+        self.close()
+
+
+class StreamChunkPlan:
+    """One chunk plan (m2f_plan_create_stream_chunk) + its workspace: up to `T` new utterances per slot and call over the caches and
+    counts of `parent`, a StreamPlan (which must stay open while this plan lives).  Rows s*T + t of `text_in` / `audio_in` / `logits`
+    ([S, T, .] views) belong to slot s; `new` (int32 [S]) holds how many of them the slot takes.  `streaming.DialogueStream.prefill`
+    drives it."""
+
+    def __init__(self, parent: "StreamPlan", T: int, params: torch.Tensor, param_shadow: Optional[torch.Tensor] = None):
+        require_gpu()
+        with torch.inference_mode(False):
+            self._create(parent, T, params, param_shadow)
+
+    def _create(self, parent, T, params, param_shadow) -> None:
+        cfg, S = parent.cfg, parent.S
+        self.cfg, self.S, self.T, self.parent, self.precision = cfg, S, T, parent, parent.precision
+        self.shared_shadow = param_shadow is not None
+        self._fresh = False
+        nbytes = lib().m2f_stream_chunk_workspace_bytes(parent._h(), T, int(self.shared_shadow))
+        if nbytes < 0:
+            raise HipError("m2f_stream_chunk_workspace_bytes: " + lib().m2f_last_error().decode())
+        self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=params.device)
+        torch.cuda.current_stream(params.device).synchronize()       # (as Plan: the create call uses blocking copies on the null stream)
+        base = self.workspace.data_ptr()
+        off = (-base) % 256
+        self._keep = (params, param_shadow, parent)
+        self.handle = lib().m2f_plan_create_stream_chunk(parent._h(), T, params.data_ptr(), base + off, nbytes, ptr(param_shadow))
+        if not self.handle:
+            raise HipError("m2f_plan_create_stream_chunk: " + lib().m2f_last_error().decode())
+        pad8 = lambda w: (w + 7) // 8 * 8
+        self.text_in = self._view(BUF_TEXT, (S, T, pad8(max(cfg.d_text, 1))), torch.float32)[:, :, : max(cfg.d_text, 1)]
+        self.audio_in = self._view(BUF_AUDIO, (S, T, pad8(max(cfg.d_audio, 1))), torch.float32)[:, :, : max(cfg.d_audio, 1)]
+        self.logits = self._view(BUF_LOGITS, (S, T, cfg.cls_out), torch.float32)
+        self.new = self._view(BUF_STREAM_NEW, (S,), torch.int32)
+        self.len = parent.len
+
+    _h = Plan._h
+    _view = Plan._view
+    params_fresh = StreamPlan.params_fresh
+    nbytes = StreamPlan.nbytes
+    close = StreamPlan.close
+
+    def prefill(self, use_graph: bool = True) -> None:
+        """forward over the chunk + len[s] += new[s]"""
+        self.parent._h()
+        check(lib().m2f_stream_prefill(self._h(), int(use_graph), stream_ptr()), "m2f_stream_prefill")
+
+    def num_launches(self) -> int:
+        return lib().m2f_plan_num_launches(self._h(), 0) + 1
 
     def __del__(self):
         self.close()

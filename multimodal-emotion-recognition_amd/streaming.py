@@ -5,6 +5,10 @@ site - both modality encoders, every fusion layer - depend on earlier utterances
 them in per-site caches on the device, so one step costs one row per dialogue where ``forward`` over the prefix costs the whole prefix
 again.  The arithmetic runs in the gfx950 kernels behind ``runtime.StreamPlan`` (``csrc/attention_stream.hip`` for the attention, the
 eval plan's own GEMM / LayerNorm / classifier launches for the rest); this module is plumbing.  The reference has no counterpart.
+
+A history - a dialogue joined in progress, a session moved to another process, the refill after ``reset()`` - is loaded with
+``prefill``: up to ``max_chunk`` utterances per slot and call through ``runtime.StreamChunkPlan`` (``csrc/attention_stream_chunk.hip``),
+which writes the same cache rows as that many steps at the cost of one forward over the chunk.
 """
 from __future__ import annotations
 
@@ -16,6 +20,47 @@ from . import runtime
 from .layout import M2FConfig
 
 MAX_CAPACITY = 512
+MAX_CHUNK = 64
+
+
+def resolve_max_chunk(max_chunk) -> int:
+    """1 (no chunk plan: ``prefill`` goes through ``step``) or 2 .. 64 utterances per slot and chunk call; ValueError otherwise."""
+    if isinstance(max_chunk, bool) or not isinstance(max_chunk, int) or not 1 <= max_chunk <= MAX_CHUNK:
+        raise ValueError(f"stream: max_chunk must be an integer in 1 .. {MAX_CHUNK}, got {max_chunk!r}")
+    return max_chunk
+
+
+def chunk_schedule(counts: Sequence[int], T: int) -> List[List[int]]:
+    """How ``prefill`` feeds ``counts[s]`` utterances per slot in chunks of at most T: ceil(max(counts) / T) calls, call i giving slot s
+    clamp(counts[s] - i * T, 0, T) rows.  Every entry is <= T and the entries of a slot sum to its count."""
+    if T < 1:
+        raise ValueError(f"chunk_schedule: T >= 1 required, got {T}")
+    counts = [int(c) for c in counts]
+    if any(c < 0 for c in counts):
+        raise ValueError(f"chunk_schedule: counts must be >= 0, got {counts}")
+    calls = (max(counts, default=0) + T - 1) // T
+    return [[min(max(c - i * T, 0), T) for c in counts] for i in range(calls)]
+
+
+def check_prefill_fits(lengths: Sequence[int], counts: Sequence[int], capacity: int, past: Optional[int]) -> None:
+    """A stream without a window holds at most ``capacity`` utterances per slot: RuntimeError if a slot's history would pass it -
+    checked for the whole call before anything is launched."""
+    if past is not None:
+        return
+    full = [s for s, (n, c) in enumerate(zip(lengths, counts)) if c > 0 and n + c > capacity]
+    if full:
+        raise RuntimeError(f"DialogueStream.prefill: slot(s) {full} would pass {capacity} utterances, the capacity of a stream without a "
+                           "window (context past=None); reset() the slot, or stream under a window (past, 0)")
+
+
+def prefix_counts(valid: torch.Tensor) -> Optional[List[int]]:
+    """valid bool [B, L] (True = an utterance): the per-dialogue lengths if every row is a valid prefix followed by padding (the collate
+    layout), else None."""
+    n = valid.sum(1)
+    L = valid.shape[1]
+    if torch.equal(valid, torch.arange(L)[None, :] < n[:, None]):
+        return n.tolist()
+    return None
 
 
 def resolve_capacity(past: Optional[int], capacity: Optional[int]) -> int:
@@ -49,7 +94,7 @@ def cache_bytes(cfg: M2FConfig, max_streams: int, capacity: int, bf16: bool = Fa
 
 
 class DialogueStream:
-    """``model.stream(max_streams, capacity=None, use_graph=True)``: ``max_streams`` slots, each one live dialogue.
+    """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1)``: ``max_streams`` slots, each one live dialogue.
 
     ``step(text [S, d_t], audio [S, d_a], active=None) -> logits [S, C_out]`` takes ONE new utterance per active slot and returns a
     fresh tensor with its logits (zero rows at inactive slots).  ``active`` is a host-side bool sequence or CPU tensor (None: every
@@ -64,11 +109,20 @@ class DialogueStream:
 
     ``reset(slots=None)`` starts new dialogues in those slots (stale rows are never read: the live count comes from the length).
     THE CACHES BELONG TO THE WEIGHTS THAT WROTE THEM: after ``load_state_dict``, an optimizer step or ``averaged_parameters()`` call
-    ``reset()`` before the next step.  A history is fed utterance by utterance (no batched prefill)."""
+    ``reset()`` before the next step.
 
-    def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True):
+    ``prefill(text [S, n, d_t], audio [S, n, d_a], counts=None) -> logits [S, n, C_out]`` loads a history: slot s takes its first
+    ``counts[s]`` rows (None: n for every slot, 0: the slot is untouched) and is left exactly as ``counts[s]`` steps would leave it -
+    same cache rows, same length - ready for ``step``; logits are zero at rows past the count.  With ``max_chunk = T`` in 2 .. 64 the
+    rows go through the chunk plan in ceil(n / T) calls of at most T rows per slot (``chunk_schedule``), each one captured graph of a
+    forward over S * T rows; with the default ``max_chunk = 1`` it goes through ``step``.  On a stream without a window a history that
+    would pass the capacity raises RuntimeError before anything is launched.  ``run`` feeds T columns per call when the batch has
+    the collate layout (every dialogue a valid prefix followed by padding)."""
+
+    def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1):
         self.model, self.use_graph = model, bool(use_graph)
         self.max_streams, self.capacity = int(max_streams), int(capacity)
+        self.max_chunk = resolve_max_chunk(max_chunk)
         self.past = model.context[0]
         eng = model.engine()
         self._eng = eng
@@ -76,8 +130,10 @@ class DialogueStream:
         if cfg.dropout != 0.0:
             cfg = M2FConfig(**{**cfg.__dict__, "dropout": 0.0})
         self.plan = runtime.StreamPlan(cfg, self.max_streams, self.capacity, self.past, eng.precision, eng.flat, eng.wshadow)
+        self.chunk_plan = runtime.StreamChunkPlan(self.plan, self.max_chunk, eng.flat, eng.wshadow) if self.max_chunk > 1 else None
         self.lengths: List[int] = [0] * self.max_streams
         self._active_host: Optional[List[bool]] = None        # what the device's mask holds (None: not written yet)
+        self._new_host: Optional[List[int]] = None            # ... and the chunk plan's per-slot row counts
 
     # -- plumbing ----------------------------------------------------------------------------------------------------------------
     def _on_stream(self, body):
@@ -101,11 +157,14 @@ class DialogueStream:
             raise ValueError(f"stream.step: `active` needs {n} entries, got {len(act)}")
         return act
 
+    def _refuse_training(self, what: str) -> None:
+        if self.model.training and self.model.m2f_config.dropout > 0.0:
+            raise RuntimeError(f"DialogueStream.{what}: the model is in training mode with dropout > 0; a stream scores the model "
+                               "without dropout - call model.eval() first")
+
     def _step(self, text, audio, act: List[bool]) -> torch.Tensor:
         """act: one entry per slot (rows of text / audio may be fewer: the leading slots)."""
-        if self.model.training and self.model.m2f_config.dropout > 0.0:
-            raise RuntimeError("DialogueStream.step: the model is in training mode with dropout > 0; a stream scores the model "
-                               "without dropout - call model.eval() first")
+        self._refuse_training("step")
         if self.past is None:
             full = [s for s, a in enumerate(act) if a and self.lengths[s] >= self.capacity]
             if full:
@@ -146,6 +205,81 @@ class DialogueStream:
                 raise ValueError(f"stream.step: {name} must be [max_streams = {S}, d], got {tuple(x.shape)}")
         return self._step(text, audio, self._mask(active, S))
 
+    def _chunk(self, text, audio, new: List[int], first: int) -> torch.Tensor:
+        """One chunk call: slot s takes rows first .. first + new[s] - 1 of text / audio ([B, n, d], B <= S leading slots).  Returns the
+        chunk plan's logits [S, T, C_out] as a fresh tensor, zeros at the rows past new[s]."""
+        pl, cfg, eng, T = self.chunk_plan, self.chunk_plan.cfg, self._eng, self.max_chunk
+        width = max(new)
+
+        def body():
+            if new != self._new_host:                       # the counts travel with the inputs (only when they change)
+                pl.new.copy_(torch.tensor(new, dtype=torch.int32), non_blocking=True)
+                self._new_host = list(new)
+            for buf, x, on in ((pl.text_in, text, cfg.text_enabled), (pl.audio_in, audio, cfg.audio_enabled)):
+                if not on:
+                    continue
+                B = x.shape[0]
+                buf.zero_()                                 # rows past a slot's count, slots not given: zeros whatever the caller holds there
+                xs = x[:, first: first + width].detach().to(buf.device, non_blocking=True)
+                rows = torch.arange(width, device=buf.device)[None, :] < pl.new[:B, None]
+                buf[:B, :width].copy_(torch.where(rows[:, :, None], xs, torch.zeros((), dtype=xs.dtype, device=buf.device)), non_blocking=True)
+            fresh = eng.shadows_fresh()
+            pl.params_fresh(fresh)
+            pl.prefill(self.use_graph)
+            if pl.shared_shadow and not fresh:
+                eng.mark_shadows_fresh()
+            keep = torch.arange(T, device=pl.logits.device)[None, :] < pl.new[:, None]
+            return torch.where(keep[:, :, None], pl.logits, torch.zeros((), dtype=pl.logits.dtype, device=pl.logits.device))
+
+        out = self._on_stream(body)
+        for s, n in enumerate(new):
+            self.lengths[s] += n
+        return out
+
+    def prefill(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+        S = self.max_streams
+        self._refuse_training("prefill")
+        cfg = self.plan.cfg
+        n = None
+        for x, on, name in ((text, cfg.text_enabled, "text"), (audio, cfg.audio_enabled, "audio")):
+            if not on:
+                continue
+            if x is None:
+                raise ValueError(f"stream.prefill: {name} is enabled in this model and must be given")
+            if x.dim() != 3 or x.shape[0] != S or (n is not None and x.shape[1] != n):
+                raise ValueError(f"stream.prefill: {name} must be [max_streams = {S}, n, d], got {tuple(x.shape)}")
+            n = x.shape[1]
+        if counts is None:
+            counts = [n] * S
+        else:
+            if isinstance(counts, torch.Tensor):
+                if counts.is_cuda:
+                    raise ValueError("stream.prefill: `counts` is host-side (an int sequence or a CPU tensor)")
+                counts = counts.reshape(-1).tolist()
+            counts = [int(c) for c in counts]
+            if len(counts) != S or any(not 0 <= c <= n for c in counts):
+                raise ValueError(f"stream.prefill: `counts` needs {S} entries in 0 .. {n}, got {counts}")
+        check_prefill_fits(self.lengths, counts, self.capacity, self.past)
+        return self._feed(text, audio, counts, n)
+
+    def _feed(self, text, audio, counts: List[int], n: int) -> torch.Tensor:
+        """counts: one entry per slot; text / audio [B, n, d] hold the leading B slots.  Returns logits [S, n, C_out]."""
+        S, T = self.max_streams, self.max_chunk
+        cfg = self.plan.cfg
+        for x, on, name in ((text, cfg.text_enabled, "text"), (audio, cfg.audio_enabled, "audio")):
+            if on and x is None:
+                raise ValueError(f"stream: {name} is enabled in this model and must be given")
+        out = torch.zeros(S, n, self.plan.cfg.cls_out, dtype=torch.float32, device=self._eng.device)
+        if T == 1:
+            for i in range(max(counts, default=0)):
+                act = [c > i for c in counts]
+                out[:, i] = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
+            return out
+        for i, new in enumerate(chunk_schedule(counts, T)):
+            w = max(new)
+            out[:, i * T: i * T + w] = self._chunk(text, audio, new, i * T)[:, :w]
+        return out
+
     def reset(self, slots: Optional[Sequence[int]] = None) -> None:
         S = self.max_streams
         if slots is None:
@@ -169,14 +303,22 @@ class DialogueStream:
 
     def run(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], mask: torch.Tensor) -> torch.Tensor:
         """A padded batch (text [B, L, d_t], audio [B, L, d_a], mask bool [B, L], True = pad; B <= max_streams) through the stream:
-        resets the first B slots and feeds the batch column by column with ``active = ~mask[:, i]``.  Returns logits [B, L, C_out]
-        with zeros at pad slots - what ``forward`` gives at the valid slots under the model's band.  Reads ``mask`` on the host once."""
+        resets the first B slots and feeds the batch column by column with ``active = ~mask[:, i]`` - or, on a stream with
+        ``max_chunk = T > 1`` and a batch in the collate layout (every row a valid prefix followed by padding), T columns per call.
+        Returns logits [B, L, C_out] with zeros at pad slots - what ``forward`` gives at the valid slots under the model's band.  Reads
+        ``mask`` on the host once."""
         B, L = mask.shape
         S = self.max_streams
         if B > S:
             raise ValueError(f"stream.run: {B} dialogues do not fit {S} stream slots")
         self.reset(range(B))
         valid = (~mask.bool()).cpu()
+        counts = prefix_counts(valid) if self.max_chunk > 1 else None
+        if counts is not None:
+            self._refuse_training("run")
+            counts = counts + [0] * (S - B)
+            check_prefill_fits(self.lengths, counts, self.capacity, self.past)
+            return self._feed(text, audio, counts, L)[:B]
         out = torch.zeros(B, L, self.plan.cfg.cls_out, dtype=torch.float32, device=self._eng.device)
         for i in range(L):
             act = valid[:, i].tolist() + [False] * (S - B)
@@ -189,5 +331,8 @@ class DialogueStream:
     def close(self) -> None:
         if self.plan is not None:
             torch.cuda.synchronize(self._eng.device)
+            if self.chunk_plan is not None:                 # (it borrows the stream plan's caches: it goes first)
+                self.chunk_plan.close()
+                self.chunk_plan = None
             self.plan.close()
             self.plan = None

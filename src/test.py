@@ -54,14 +54,28 @@ def streaming_settings(config):
     return True
 
 
+def stream_chunk_settings(config):
+    """`runtime.stream_chunk`: 1 (default) = a streamed test pass feeds every batch column by column; T in 2 .. 64 = the stream is opened
+    with `max_chunk=T` (M2FNet.stream) and `DialogueStream.run` feeds T columns per call through the chunk plan.  -> int; checked on the
+    host before the GPU is touched."""
+    from train import _runtime
+    from mer_amd.streaming import resolve_max_chunk
+    T = _runtime(config, "stream_chunk", 1)
+    try:
+        return resolve_max_chunk(1 if T is None else T)        # (the one statement of the range)
+    except ValueError as e:
+        raise ValueError(f"runtime.stream_chunk: {e}") from None
+
+
 def _stream_for(model, B, L):
     """The model's test stream, opened (again) when a batch has more dialogues or - without a window - longer ones than it holds."""
     st = getattr(model, "_test_stream", None)
     windowed = model.context[0] is not None
-    if st is None or st.max_streams < B or (not windowed and st.capacity < L):
+    chunk = getattr(model, "stream_chunk", 1)
+    if st is None or st.max_streams < B or (not windowed and st.capacity < L) or st.max_chunk != chunk:
         if st is not None:
             st.close()
-        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64))
+        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64), max_chunk=chunk)
         model._test_stream = st
     return st
 
@@ -69,7 +83,8 @@ def _stream_for(model, B, L):
 def test(model, dl_test, device):
     """-> (accuracy, weighted_f1) over the loader, per-batch scores averaged unweighted.
     With ``model.streaming`` (runtime.streaming) every batch goes through ``DialogueStream.run`` - column by column, one new utterance per
-    dialogue and step - and its logits are scored as the batched pass's are (on the host).
+    dialogue and step, or ``model.stream_chunk`` (runtime.stream_chunk) columns per chunk call - and its logits are scored as the batched
+    pass's are (on the host).
     With ``model.device_metrics`` (runtime.device_metrics) every batch is scored on the device (``M2FNet.eval_step``) and the host
     reads the record once; ``model.test_scores`` then holds the pass's ``DeviceScores`` (confusion matrix, per-class report)."""
     model.eval()
@@ -120,6 +135,7 @@ def main(config=None):
     from train import context_settings
     context_settings(config)                               # (refusal before the GPU is touched)
     streaming = streaming_settings(config)
+    stream_chunk = stream_chunk_settings(config)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     print(f"Using device {device}...")
     runtime_cfg = config.get("runtime", {}) or {}
@@ -130,6 +146,7 @@ def main(config=None):
     model = build_model(config, device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     model.streaming = streaming
+    model.stream_chunk = stream_chunk
     from train import ema_settings
     ema = ema_settings(config)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
