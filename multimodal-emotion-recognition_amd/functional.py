@@ -130,6 +130,58 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     return out, probs
 
 
+def attention_long_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: Optional[torch.Tensor], B: int, S: int, H: int,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Token-level self-attention of the in-loop encoders' fp32 mode (m2f_attention_long_fwd): q / k / v [B*S, H*hd] fp32, possibly
+    column slices of a wider matrix (token b*S + i at row b*S + i); key_pad uint8 / bool [B, S] (1 = padded key) or None.
+    softmax(q k^T / sqrt(hd)) v over the valid keys per (sequence, head), any S, hd <= 128; a query whose keys are all padded gets a
+    zero row.  `out`: a preallocated fp32 tensor of at least B*S rows and H*hd columns (a wider pitch is legal, the columns behind
+    H*hd are left alone).  Returns the [B*S, H*hd] view of the result."""
+    runtime.require_gpu()
+    T, E = B * S, q.shape[1]
+    if H < 1 or E % H or k.shape != q.shape or v.shape != q.shape or q.shape[0] != T:
+        raise ValueError("attention_long_fwd: q / k / v hold B * S rows of H * hd columns")
+    if out is None:
+        out = torch.empty(T, E, dtype=torch.float32, device=q.device)
+    if out.dim() != 2 or out.shape[0] < T or out.shape[1] < E:
+        raise ValueError("attention_long_fwd: out needs at least B * S rows and H * hd columns")
+    kp = None
+    if key_pad is not None:
+        if key_pad.numel() != T or key_pad.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("attention_long_fwd: key_pad uint8 / bool [B, S] required")
+        kp = key_pad.to(device=q.device, dtype=torch.uint8).contiguous()
+    check(lib().m2f_attention_long_fwd(B, S, H, E // H, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out), _ld(out),
+                                       stream_ptr()), "m2f_attention_long_fwd")
+    return out[:T, :E]
+
+
+def embed_layernorm(ids: torch.Tensor, pos_ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, type_row0: torch.Tensor,
+                    gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RoBERTa embeddings (m2f_embed_layernorm): LayerNorm(word[ids] + pos[pos_ids] + type_row0) * gamma + beta.  ids / pos_ids int64
+    [T]; word [vocab, d], pos [max_pos, d] contiguous fp32; type_row0 / gamma / beta fp32 [d]; d % 4 == 0, d <= 2048.  `out`: a
+    preallocated fp32 tensor of at least T rows and d columns (a wider pitch is legal).  Returns the [T, d] view of the result."""
+    runtime.require_gpu()
+    T, d = ids.numel(), word.shape[1]
+    if ids.dtype != torch.int64 or pos_ids.dtype != torch.int64 or ids.dim() != 1 or pos_ids.shape != ids.shape:
+        raise ValueError("embed_layernorm: ids and pos_ids int64 [T] required")
+    for t in (word, pos):
+        if t.dim() != 2 or t.shape[1] != d or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("embed_layernorm: the tables must be contiguous, 16-byte aligned fp32 [rows, d]")
+    for t in (type_row0, gamma, beta):
+        if t.shape != (d,) or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("embed_layernorm: type_row0 / gamma / beta must be contiguous, 16-byte aligned fp32 [d]")
+    if T and (int(ids.min()) < 0 or int(ids.max()) >= word.shape[0] or int(pos_ids.min()) < 0 or int(pos_ids.max()) >= pos.shape[0]):
+        raise ValueError("embed_layernorm: an id lies outside its table")
+    if out is None:
+        out = torch.empty(T, d, dtype=torch.float32, device=word.device)
+    if out.dim() != 2 or out.shape[0] < T or out.shape[1] < d or out.data_ptr() % 16:
+        raise ValueError("embed_layernorm: out needs at least T rows and d columns, 16-byte aligned")
+    ids, pos_ids = ids.contiguous(), pos_ids.contiguous()
+    check(lib().m2f_embed_layernorm(T, d, ptr(ids), ptr(pos_ids), ptr(word), ptr(pos), ptr(type_row0), ptr(gamma), ptr(beta), float(eps),
+                                    ptr(out), _ld(out), stream_ptr()), "m2f_embed_layernorm")
+    return out[:T, :d]
+
+
 def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool = False, device="cuda", fill: float = 0.0):
     """(kcache, vcache) of one streaming-attention site: flat tensors viewed [S, H, capacity, pad(hd)], fp32 (pad to 4) or bf16 (pad to
     8), filled with `fill`."""

@@ -47,12 +47,13 @@ class RobertaEncoder(torch.nn.Module):
         act = _get(config, "hidden_act", "gelu")
         if act != "gelu":
             raise ValueError(f"hidden_act={act!r}: only the exact 'gelu' of RoBERTa is implemented")
-        if self.d % self.n_head or self.d % 8 or self.inter % 8:
-            raise ValueError("hidden_size must be divisible by num_attention_heads; hidden / intermediate sizes by 8")
+        assert precision in ("bf16", "fp32", "fp8")
+        # (fp32 mode keeps no packed bf16 / e4m3 operand copies: only the embedding kernel's float4 rows bound its hidden size)
+        if self.d % self.n_head or self.d % (4 if precision == "fp32" else 8) or self.inter % 8:
+            raise ValueError("hidden_size must be divisible by num_attention_heads; hidden / intermediate sizes by 8 (fp32 mode: hidden by 4)")
         self.hd = self.d // self.n_head
         if self.hd > 128 or self.d > 2048:
             raise ValueError("head dim <= 128 and hidden size <= 2048")
-        assert precision in ("bf16", "fp32", "fp8")
         # fp8 (BASELINE C5): the four GEMMs of every layer on fp8 MFMA (OCP e4m3, fp32 accumulate); weights quantised once
         # with a per-tensor scale 448 / amax, activations with fixed scales (LayerNorm / attention outputs x16, GELU
         # outputs x8, saturating) - everything else (embeddings, attention, LayerNorm, residual stream) stays fp32

@@ -37,6 +37,36 @@ def test_fp32_matches_transformers_fixture_and_oracle(golden_dir, name):
     assert torch.equal(cls, hid[:, 0, :])
 
 
+# Shapes no fixture holds (transformers' output cannot be regenerated for new ones): the fp32 mode against the live oracle evaluated in
+# float64 on the same weights.  name -> (config, B, S, lengths)
+LIVE_CASES = {
+    # hd = 128: the attention kernel's opt-in LDS launch and all eight output tiles, four key blocks; max_position_embeddings is the smallest
+    # value the encoder accepts for S = 200, so the full sequence reads the last row of the position table
+    "hd128_four_blocks_last_position": (SR.cfg(256, 1, 2, 512, 120, 202), 3, 200, [200, 1, 77]),
+    # hd = 25: the generic slab staging (hd % 4 != 0) under the module, two key blocks
+    "hd25_generic_slabs": (SR.cfg(100, 2, 4, 200, 90, 80), 2, 70, [70, 33]),
+}
+
+
+@pytest.mark.parametrize("name", list(LIVE_CASES))
+def test_fp32_matches_the_float64_oracle_at_shapes_without_a_fixture(name):
+    c, B, S, lengths = LIVE_CASES[name]
+    ids, mask = SR.make_batch(c, B, S, lengths)
+    if name == "hd128_four_blocks_last_position":
+        assert RO.position_ids(ids, c["pad_token_id"]).max().item() == c["max_position_embeddings"] - 1
+        with pytest.raises(ValueError):
+            RobertaEncoder(dict(c, max_position_embeddings=c["max_position_embeddings"] - 1), precision="fp32").cuda()(ids.cuda(), mask.cuda())
+    m = _enc(c, "fp32")
+    hid = m(ids.cuda(), mask.cuda()).cpu()
+    sd64 = {n: t.double() for n, t in SR.make_state_dict(c).items()}
+    ref = RO.forward(sd64, c, ids, mask)
+    assert ref.dtype == torch.float64
+    err = (hid.double() - ref)[mask.bool()].abs().max().item()
+    print(f"fp32 encoder vs the float64 oracle, {name}: max |d| on valid tokens {err:.3e}")
+    assert err < 1e-4, err
+    assert torch.equal(m.cls_embeddings(ids.cuda(), mask.cuda()).cpu(), hid[:, 0, :])
+
+
 @pytest.mark.parametrize("name", ["roberta_tiny", "roberta_three_blocks", "roberta_base_width"])
 def test_bf16_within_stated_tolerance(golden_dir, name):
     c, B, S, lengths = SR.CASES[name]
