@@ -56,7 +56,8 @@ enum {
     M2F_BUF_STREAM_LEN = 12,    /* int32 [S]  stream plans: utterances cached per stream slot (advanced by m2f_stream_step, zeroed by m2f_stream_reset) */
     M2F_BUF_STREAM_ACTIVE = 13, /* uint8 [S]  stream plans, input: 1 = the slot takes an utterance in the next m2f_stream_step */
     M2F_BUF_STREAM_NEW = 14,    /* int32 [S]  chunk plans, input: utterances (0 .. T) the slot takes in the next m2f_stream_prefill */
-    M2F_BUF_COUNT = 15
+    M2F_BUF_STREAM_TABLE = 15,  /* int32 [S, ceil(C / page_rows)]  paged stream plans, input: the page of each run of page_rows cache rows of a slot (a chunk plan: its parent's) */
+    M2F_BUF_COUNT = 16
 };
 
 const char* m2f_last_error(void);
@@ -179,6 +180,20 @@ int64_t m2f_stream_chunk_workspace_bytes(m2f_plan* parent, int T, int shared);
 m2f_plan* m2f_plan_create_stream_chunk(m2f_plan* parent, int T, float* params, void* workspace, int64_t workspace_bytes,
                                        uint16_t* param_shadow);
 int m2f_stream_prefill(m2f_plan* plan, int use_graph, m2f_stream_t stream);
+/* PAGED stream plan: the same stream with the cache rows allocated in pages.  Every attention site holds K and V POOLS
+ * [n_pages][H][page_rows][pad(hd)] (page_rows = 16, 32 or 64; rows padded and aligned as the dense caches') instead of
+ * [S][H][C][pad(hd)], and logical cache row r of slot s - utterance r of a plain cache, utterance u with u % C == r of a ring - is row
+ * r % page_rows of page table[s][r / page_rows].  table = M2F_BUF_STREAM_TABLE, int32 [S, ceil(C / page_rows)], an INPUT like the mask:
+ * the caller owns the allocation (which pages are free, which slot holds which) and writes the table before the call that needs it.
+ * Page ids are shared by all sites: page p is index p of every pool.  A step / chunk call reads only the entries of pages that hold
+ * a live row of the slot or take a row of this call, entries e < ceil(min(count + new, C) / page_rows); the rest may hold anything.
+ * Ids outside 0 .. n_pages - 1 are clamped into the pool.  Memory follows n_pages, not S: S is limited only by the plan's row-wise
+ * and GEMM launches.  Arithmetic, order and results are the dense plan's bit for bit.  m2f_plan_create_stream_chunk accepts a paged
+ * parent (its sites then run the paged chunk kernel through the parent's table); m2f_stream_step / _prefill / _reset work as on a
+ * dense plan and m2f_stream_cache_bytes returns the pools' bytes.  The table starts as zeros. */
+int64_t m2f_stream_paged_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows, int shared);
+m2f_plan* m2f_plan_create_stream_paged(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows,
+                                       float* params, void* workspace, int64_t workspace_bytes, uint16_t* param_shadow);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -601,6 +616,17 @@ int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const fl
 int m2f_attention_stream_chunk(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                void* kcache, void* vcache, int C, int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo,
                                int bf16, m2f_stream_t stream);
+/* Paged forms of the two launches above (layout: m2f_plan_create_stream_paged): kpool / vpool [n_pages][H][page_rows][pad(hd)],
+ * m2f_attention_stream_pool_elems elements each, 16-byte aligned; table device int32 [S, table_cols], table_cols = ceil(C / page_rows).
+ * Same results, bit for bit, as the dense launches on caches that hold the same rows.  Refused before any launch: page_rows outside
+ * {16, 32, 64}, misaligned pools, table_cols != ceil(C / page_rows), C > 512, hd > 128. */
+int64_t m2f_attention_stream_pool_elems(int n_pages, int H, int hd, int page_rows, int bf16);
+int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                               const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, m2f_stream_t stream);
+int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                     void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                     const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream);
 /* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
  * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
  * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this

@@ -209,6 +209,179 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBat
     }
 }
 
+// PAGED FORM.  The same problem over a page pool instead of a per-slot cache:   pool[n_pages][H][R][hdp]
+//   R = 16, 32 or 64 rows per page; one page of a head is contiguous, rows padded and aligned as above.  Logical cache row j of slot s
+//   (the row the dense kernel calls j) lives at row j % R of page table[s][j / R], table = int32 [S][ceil(C / R)].  Page ids are shared
+//   by every site of a stream: page p is index p of every site's pool.
+// Work split, row order, arithmetic and summation order are the dense kernel's statement for statement, so the results are its bits;
+// only the address of a row differs.  The wave fetches its slot's page ids ONCE - lane e loads entry e (<= 32 entries: 512 rows of
+// 16-row pages) into LDS - and the row loops take the id from LDS: no dependent global load per row.  Only the entries of pages that
+// hold a live row or take the new one are loaded (e < ceil(min(len + 1, C) / R)); entries behind that are never dereferenced,
+// whatever they hold.  An id is clamped to the pool (0 .. n_pages - 1): a torn table reads the wrong page, never unmapped memory.
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
+    typedef Row<BF16> R;
+    typedef typename R::elem_t elem_t;
+    constexpr int EPL = R::EPL;
+    constexpr int U = 4;
+    __shared__ float sq[128], sk[128], sv[128];
+    __shared__ float sc[M2F_ATTN_STREAM_MAX_C];
+    __shared__ int spg[32];                       // the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
+
+    const int blk = blockIdx.x, lane = threadIdx.x;
+    int pi = 0;
+    while (pi + 1 < ab.count && blk >= ab.bb[pi + 1]) ++pi;
+    const AttnStreamProblem& P = ab.pr[pi];
+    const int local = blk - ab.bb[pi];
+    const int s = local / P.H, h = local - s * P.H;
+    const int hd = P.hd, C = ab.C;
+    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    float* orow = P.out + (size_t)s * P.ldo + (size_t)h * hd;
+    uint16_t* orow16 = m2f_shadow_of(ab.sh, orow);
+
+    const int n_old = ab.len[s];
+    const bool live = ab.active[s] != 0 && n_old >= 0 && (ab.ring || n_old < C);
+    if (!live) {
+        for (int i = lane; i < hd; i += 64) {
+            orow[i] = 0.f;
+            if (orow16) orow16[i] = 0;
+        }
+        return;
+    }
+    const int pos = ab.ring ? n_old % C : n_old;
+    const int nslots = n_old + 1 < C ? n_old + 1 : C;
+    const int lgR = pg.lgR, rmask = (1 << lgR) - 1;
+
+    if (lane < 32) {                              // the page ids -> LDS (one 4-byte load per page that may be read)
+        int id = 0;
+        if (lane < ((nslots + rmask) >> lgR)) id = pg.table[(size_t)s * pg.tw + lane];
+        spg[lane] = min(max(id, 0), pg.n_pages - 1);
+    }
+    {   // the new rows -> LDS
+        const float* qrow = P.q + (size_t)s * P.ldq + (size_t)h * hd;
+        const float* krow = P.k + (size_t)s * P.ldk + (size_t)h * hd;
+        const float* vrow = P.v + (size_t)s * P.ldv + (size_t)h * hd;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int i = lane + 64 * t;
+            float a = 0.f, b = 0.f, c = 0.f;
+            if (i < hd) { a = qrow[i]; b = krow[i]; c = vrow[i]; }
+            if (BF16) { a = m2f_bf16_to_f32(m2f_bf16_bits(a)); b = m2f_bf16_to_f32(m2f_bf16_bits(b)); c = m2f_bf16_to_f32(m2f_bf16_bits(c)); }
+            sq[i] = a; sk[i] = b; sv[i] = c;
+        }
+    }
+    __syncthreads();
+
+    const int nch = hdp / EPL;
+    int CH = 1, lg = 0;
+    while (CH < nch) { CH <<= 1; ++lg; }
+    const int RPW = 64 >> lg;
+    const int r = lane >> lg, c = lane & (CH - 1);
+    const bool cact = c < nch;
+    const int e0 = c * EPL;
+
+    const size_t page_stride = (size_t)P.H * (size_t)(hdp << lgR);       // elements of one page, all heads
+    elem_t* kc = static_cast<elem_t*>(P.kcache) + (size_t)h * (size_t)(hdp << lgR) + e0;      // this head's rows of page 0, this lane's chunk
+    elem_t* vc = static_cast<elem_t*>(P.vcache) + (size_t)h * (size_t)(hdp << lgR) + e0;
+    auto row_off = [&](int j) { return (size_t)spg[j >> lgR] * page_stride + (size_t)((j & rmask) * hdp); };
+    if (r == 0 && cact) {                         // the new K / V rows into their page (vector stores; pad columns: zeros)
+        float kx[EPL], vx[EPL];
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) { kx[i] = sk[e0 + i]; vx[i] = sv[e0 + i]; }
+        const size_t o = row_off(pos);
+        R::store(kc + o, kx);
+        R::store(vc + o, vx);
+    }
+
+    float qx[EPL];
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) qx[i] = sq[e0 + i];
+    const float scale = 1.0f / sqrtf((float)hd);
+
+    // ---- pass 1: scores ---------------------------------------------------------------------------------------------------------
+    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
+        float kx[U][EPL];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) kx[u][i] = 0.f;
+            if (cact && j < nslots) {
+                if (j != pos) R::load(kc + row_off(j), kx[u]);
+                else {
+#pragma unroll
+                    for (int i = 0; i < EPL; ++i) kx[u][i] = sk[e0 + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) d = fmaf(qx[i], kx[u][i], d);
+            for (int o = CH >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+            if (c == 0 && j < nslots) sc[j] = d * scale;
+        }
+    }
+    __syncthreads();
+
+    // ---- softmax over the live rows (fp32, max-subtracted) ------------------------------------------------------------------------
+    float m = -INFINITY;
+    for (int j = lane; j < nslots; j += 64) m = fmaxf(m, sc[j]);
+    m = m2f_wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < nslots; j += 64) {
+        const float e = __expf(sc[j] - m);
+        sc[j] = e;
+        sum += e;
+    }
+    sum = m2f_wave_sum(sum);
+    const float inv = 1.0f / sum;
+    __syncthreads();
+
+    // ---- pass 2: P V ---------------------------------------------------------------------------------------------------------------
+    float acc[EPL];
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
+    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
+        float vx[U][EPL], p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * RPW + r;
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) vx[u][i] = 0.f;
+            p[u] = 0.f;
+            if (cact && j < nslots) {
+                p[u] = sc[j];
+                if (j != pos) R::load(vc + row_off(j), vx[u]);
+                else {
+#pragma unroll
+                    for (int i = 0; i < EPL; ++i) vx[u][i] = sv[e0 + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) acc[i] = fmaf(p[u], vx[u][i], acc[i]);
+    }
+    for (int o = CH; o < 64; o <<= 1) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
+    }
+    if (r == 0 && cact) {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) {
+            if (e0 + i < hd) {
+                const float o = acc[i] * inv;
+                orow[e0 + i] = o;
+                if (orow16) orow16[e0 + i] = m2f_bf16_bits(o);
+            }
+        }
+    }
+}
+
 // len[s] += active[s]: the one launch that closes a step
 __global__ void m2f_stream_advance_kernel(int* len, const uint8_t* active, int S) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -242,6 +415,38 @@ hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream) {
     }
     if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab);
     else hipLaunchKernelGGL(m2f_attn_stream_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab);
+    return hipGetLastError();
+}
+
+size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16) {
+    const int hdp = bf16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    return (size_t)n_pages * H * R * hdp;
+}
+
+// What both paged launchers refuse before anything is launched; fills pg.lgR.
+bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg) {
+    if (pg.R != 16 && pg.R != 32 && pg.R != 64) return false;
+    if (!pg.table || (reinterpret_cast<uintptr_t>(pg.table) & 3) || pg.n_pages < 1) return false;
+    if (ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || pg.tw != (ab.C + pg.R - 1) / pg.R) return false;
+    pg.lgR = pg.R == 16 ? 4 : pg.R == 32 ? 5 : 6;
+    return true;
+}
+
+hipError_t m2f_launch_attn_stream_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, hipStream_t stream) {
+    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || !ab.len || !ab.active || !m2f_attn_stream_paging_ok(ab, pg))
+        return hipErrorInvalidValue;
+    int blocks = 0;
+    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
+    for (int i = 0; i < ab.count; ++i) {
+        AttnStreamProblem& p = ab.pr[i];
+        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
+        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
+        p.block_begin = blocks;
+        ab.bb[i] = blocks;
+        blocks += ab.S * p.H;
+    }
+    if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg);
+    else hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg);
     return hipGetLastError();
 }
 

@@ -275,6 +275,20 @@ hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStre
 #define M2F_ATTN_STREAM_MAX_CHUNK 64
 hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, int T, const int* n_new, hipStream_t stream);
 hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream);   // len[s] += min(max(n_new[s], 0), T)
+// Paged forms: kcache / vcache of a problem are the site's page POOLS, [n_pages][H][R][pad(hd)] (rows padded and aligned as the dense
+// caches'), and logical cache row j of slot s - the row the dense kernels call j - is row j % R of page table[s][j / R].  The dense
+// kernels, their batch struct and their launches are untouched; the paging travels as a kernel argument of its own.  Only the table
+// entries of pages that hold a live row or take a new one are read; ids are clamped to the pool.
+struct AttnStreamPaging {
+    const int* table;          // device int32 [S][tw]
+    int tw;                    // entries per slot: ceil(C / R)
+    int R, lgR;                // rows per page, 16 / 32 / 64 (lgR: filled by the launcher)
+    int n_pages;               // pages of every pool
+};
+size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16);        // elements (fp32 or bf16) of ONE pool (K or V) of a site
+bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg);       // R, table, tw against ab.C; fills lgR
+hipError_t m2f_launch_attn_stream_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, hipStream_t stream);
+hipError_t m2f_launch_attn_stream_chunk_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, int T, const int* n_new, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // Row-wise kernels

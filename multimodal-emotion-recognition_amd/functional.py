@@ -240,6 +240,71 @@ def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kc
     return out
 
 
+def attention_stream_pools(n_pages: int, H: int, hd: int, page_rows: int = 16, bf16: bool = False, device="cuda", fill: float = 0.0):
+    """(kpool, vpool) of one paged streaming-attention site: tensors [n_pages, H, page_rows, pad(hd)], fp32 (pad to 4) or bf16 (pad to
+    8), filled with `fill`.  page_rows: 16, 32 or 64."""
+    n = lib().m2f_attention_stream_pool_elems(n_pages, H, hd, page_rows, int(bf16))
+    if n < 0:
+        raise runtime.HipError("m2f_attention_stream_pool_elems: " + lib().m2f_last_error().decode())
+    hdp = (hd + 7) // 8 * 8 if bf16 else (hd + 3) // 4 * 4
+    dt = torch.bfloat16 if bf16 else torch.float32
+    return tuple(torch.full((n_pages, H, page_rows, hdp), fill, dtype=dt, device=device) for _ in range(2))
+
+
+def _paged_args(who: str, kpool, vpool, table, S: int, capacity: int, bf16: bool):
+    """(n_pages, page_rows) of a pool pair after the checks that need tensors; sizes and alignment are the library's to refuse."""
+    want = torch.bfloat16 if bf16 else torch.float32
+    if kpool.dtype != want or vpool.dtype != want or kpool.dim() != 4 or kpool.shape != vpool.shape:
+        raise ValueError(f"{who}: the pools must be two " + ("bfloat16" if bf16 else "float32") + " tensors [n_pages, H, page_rows, pad(hd)]")
+    if not kpool.is_contiguous() or not vpool.is_contiguous():
+        raise ValueError(f"{who}: the pools must be contiguous")
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] != S or not table.is_contiguous():
+        raise ValueError(f"{who}: the page table must be a contiguous int32 tensor [S, ceil(capacity / page_rows)]")
+    return kpool.shape[0], kpool.shape[2]
+
+
+def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
+                           lengths: torch.Tensor, active: torch.Tensor, H: int, capacity: int, ring: bool = False,
+                           bf16: bool = False) -> torch.Tensor:
+    """`attention_stream` over page pools (m2f_attention_stream_paged): logical cache row r of slot s - the row `attention_stream` calls r -
+    is row r % page_rows of page table[s, r // page_rows].  kpool / vpool: `attention_stream_pools`; table int32 [S, ceil(capacity /
+    page_rows)], read only at the entries of pages that hold a live row or take the new one.  The same bits as `attention_stream` on
+    caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd]."""
+    runtime.require_gpu()
+    S, E = q.shape
+    hd = E // H
+    n_pages, R = _paged_args("attention_stream_paged", kpool, vpool, table, S, capacity, bf16)
+    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
+        raise ValueError("attention_stream_paged: lengths int32 [S] and active [S] required")
+    act = active.to(torch.uint8).contiguous()
+    out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
+                                           table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
+                                           int(bf16), stream_ptr()), "m2f_attention_stream_paged")
+    return out
+
+
+def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
+                                 table: torch.Tensor, lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, capacity: int,
+                                 ring: bool = False, bf16: bool = False) -> torch.Tensor:
+    """`attention_stream_chunk` over page pools (m2f_attention_stream_chunk_paged; layout: `attention_stream_paged`).  q / k / v hold
+    S * T rows, S = table.shape[0].  The same bits, output and stored rows, as the dense chunk launch.  Returns out [S*T, H*hd]."""
+    runtime.require_gpu()
+    rows, E = q.shape
+    hd = E // H
+    S = lengths.numel()
+    n_pages, R = _paged_args("attention_stream_chunk_paged", kpool, vpool, table, S, capacity, bf16)
+    if not 1 <= T <= 64 or rows != S * T or k.shape[0] != rows or v.shape[0] != rows:
+        raise ValueError("attention_stream_chunk_paged: q / k / v hold S * T rows, 1 <= T <= 64")
+    if lengths.dtype != torch.int32 or new.dtype != torch.int32 or new.numel() != S:
+        raise ValueError("attention_stream_chunk_paged: lengths int32 [S] and new int32 [S] required")
+    out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream_chunk_paged(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
+                                                 ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
+                                                 ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk_paged")
+    return out
+
+
 def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, drop_site: int = 0, drop_p: float = 0.0,
                   rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
                   future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

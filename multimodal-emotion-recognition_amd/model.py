@@ -600,7 +600,8 @@ class M2FNet(nn.Module):
             body()
 
     # -- streaming inference (one new utterance per live dialogue; streaming.DialogueStream) -----------------------------------------
-    def stream(self, max_streams: int, capacity: Optional[int] = None, use_graph: bool = True, max_chunk: int = 1):
+    def stream(self, max_streams: int, capacity: Optional[int] = None, use_graph: bool = True, max_chunk: int = 1,
+               pages: Optional[int] = None, page_rows: int = 16):
         """A ``DialogueStream`` of ``max_streams`` slots over this model's weights: ``stream.step(text [S, d_t], audio [S, d_a],
         active)`` labels the utterance that has just arrived in each active slot from per-site K / V caches on the device, at the
         cost of one row per dialogue - where ``forward`` would re-run the whole prefix.  Needs a causal context band
@@ -613,8 +614,14 @@ class M2FNet(nn.Module):
         max_chunk: 1 (default: nothing beyond the step plan is created), or T in 2 .. 64 - the stream also gets a chunk plan and
         ``stream.prefill(text [S, n, d_t], audio [S, n, d_a], counts)`` loads a history T utterances per slot and call (one forward over
         S * T rows each) instead of one launch-bound step per utterance; ``stream.run`` then feeds collate-layout batches T columns at a
-        time.  Every refusal is raised before the GPU is touched."""
-        from .streaming import DialogueStream, resolve_capacity, resolve_max_chunk
+        time.
+        pages: None (default: the dense caches above), or N >= 1 - PAGED caches: every site holds pools of N pages of ``page_rows`` (16,
+        32 or 64) rows, ``2 * sum_sites pad(d_site) * N * page_rows`` elements, and a slot takes pages as its dialogue grows and
+        returns them at ``reset`` (``streaming.PageAllocator``).  Memory follows the utterances cached, not ``max_streams * capacity``:
+        the 3.8 GB above hold 2,048 pages of 16 rows, about 2,000 live MELD-length dialogues.  Same logits, bit for bit; a call that
+        would need more pages than are free raises RuntimeError and changes nothing.
+        Every refusal is raised before the GPU is touched."""
+        from .streaming import DialogueStream, resolve_capacity, resolve_max_chunk, resolve_pages
         past, future = self._context
         if future != 0:
             raise ValueError(f"M2FNet.stream: streaming needs a causal context band (past, 0), this model has context={self._context}; "
@@ -624,7 +631,8 @@ class M2FNet(nn.Module):
                                "without dropout - call model.eval() first")
         if isinstance(max_streams, bool) or not isinstance(max_streams, int) or max_streams < 1:
             raise ValueError(f"M2FNet.stream: max_streams must be an integer >= 1, got {max_streams!r}")
-        return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph, resolve_max_chunk(max_chunk))
+        pages, page_rows = resolve_pages(pages, page_rows)
+        return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph, resolve_max_chunk(max_chunk), pages, page_rows)
 
     def set_grad_bf16(self, on: bool = True) -> bool:
         """bf16 mode: every following training step leaves its gradients ROUNDED ONCE TO BF16 in one flat bf16 buffer - the weight-gradient

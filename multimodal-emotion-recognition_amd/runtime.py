@@ -24,7 +24,7 @@ HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "m2fnet_hip.h
 F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
- BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW) = range(15)
+ BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE) = range(16)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -138,6 +138,14 @@ SIGNATURES = {
     "m2f_attention_stream_cache_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "m2f_attention_stream": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                      c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_stream_paged_workspace_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "m2f_plan_create_stream_paged": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                                c_void_p]),
+    "m2f_attention_stream_pool_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "m2f_attention_stream_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_attention_stream_chunk_paged": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                 c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_stream_chunk_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "m2f_plan_create_stream_chunk": (c_void_p, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_prefill": (c_int, [c_void_p, c_int, c_void_p]),
@@ -683,38 +691,52 @@ class Plan:
 
 class StreamPlan:
     """One stream plan (m2f_plan_create_stream) + its workspace: `S` stream slots, K / V caches of `capacity` rows per slot at every
-    attention site (a ring when `past` is an integer).  `streaming.DialogueStream` drives it."""
+    attention site (a ring when `past` is an integer).  `streaming.DialogueStream` drives it.
+
+    With `pages` (m2f_plan_create_stream_paged) every site holds pools of `pages` pages of `page_rows` (16 / 32 / 64) rows instead, and
+    `table` (int32 [S, ceil(capacity / page_rows)], an input like `active`) names the page of each run of `page_rows` logical cache
+    rows of a slot; the caller allocates (`streaming.PageAllocator`)."""
 
     def __init__(self, cfg: M2FConfig, S: int, capacity: int, past: Optional[int], precision: int, params: torch.Tensor,
-                 param_shadow: Optional[torch.Tensor] = None):
+                 param_shadow: Optional[torch.Tensor] = None, pages: Optional[int] = None, page_rows: int = 16):
         require_gpu()
         with torch.inference_mode(False):          # (a stream opened under inference_mode must stay writable outside it)
-            self._create(cfg, S, capacity, past, precision, params, param_shadow)
+            self._create(cfg, S, capacity, past, precision, params, param_shadow, pages, page_rows)
 
-    def _create(self, cfg, S, capacity, past, precision, params, param_shadow) -> None:
+    def _create(self, cfg, S, capacity, past, precision, params, param_shadow, pages=None, page_rows=16) -> None:
         self.cfg, self.S, self.capacity, self.past, self.precision = cfg, S, capacity, past, precision
+        self.pages, self.page_rows = pages, page_rows
         self._cc = config_to_c(cfg)
         self.shared_shadow = param_shadow is not None
         self._fresh = False
         past_c = -1 if past is None else int(past)
-        nbytes = lib().m2f_stream_workspace_bytes(ctypes.byref(self._cc), S, capacity, past_c, precision, int(self.shared_shadow))
+        if pages is None:
+            nbytes = lib().m2f_stream_workspace_bytes(ctypes.byref(self._cc), S, capacity, past_c, precision, int(self.shared_shadow))
+        else:
+            nbytes = lib().m2f_stream_paged_workspace_bytes(ctypes.byref(self._cc), S, capacity, past_c, precision, pages, page_rows,
+                                                            int(self.shared_shadow))
         if nbytes < 0:
-            raise HipError("m2f_stream_workspace_bytes: " + lib().m2f_last_error().decode())
+            raise HipError(("m2f_stream_workspace_bytes: " if pages is None else "m2f_stream_paged_workspace_bytes: ") + lib().m2f_last_error().decode())
         self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=params.device)
         torch.cuda.current_stream(params.device).synchronize()       # (as Plan: the create call uses blocking copies on the null stream)
         base = self.workspace.data_ptr()
         off = (-base) % 256
         self._keep = (params, param_shadow)
-        self.handle = lib().m2f_plan_create_stream(ctypes.byref(self._cc), S, capacity, past_c, precision, params.data_ptr(), base + off,
-                                                   nbytes, ptr(param_shadow))
+        if pages is None:
+            self.handle = lib().m2f_plan_create_stream(ctypes.byref(self._cc), S, capacity, past_c, precision, params.data_ptr(), base + off,
+                                                       nbytes, ptr(param_shadow))
+        else:
+            self.handle = lib().m2f_plan_create_stream_paged(ctypes.byref(self._cc), S, capacity, past_c, precision, pages, page_rows,
+                                                             params.data_ptr(), base + off, nbytes, ptr(param_shadow))
         if not self.handle:
-            raise HipError("m2f_plan_create_stream: " + lib().m2f_last_error().decode())
+            raise HipError(("m2f_plan_create_stream: " if pages is None else "m2f_plan_create_stream_paged: ") + lib().m2f_last_error().decode())
         pad8 = lambda w: (w + 7) // 8 * 8
         self.text_in = self._view(BUF_TEXT, (S, pad8(max(cfg.d_text, 1))), torch.float32)[:, : max(cfg.d_text, 1)]
         self.audio_in = self._view(BUF_AUDIO, (S, pad8(max(cfg.d_audio, 1))), torch.float32)[:, : max(cfg.d_audio, 1)]
         self.logits = self._view(BUF_LOGITS, (S, cfg.cls_out), torch.float32)
         self.len = self._view(BUF_STREAM_LEN, (S,), torch.int32)
         self.active = self._view(BUF_STREAM_ACTIVE, (S,), torch.uint8)
+        self.table = None if pages is None else self._view(BUF_STREAM_TABLE, (S, (capacity + page_rows - 1) // page_rows), torch.int32)
 
     _h = Plan._h
     _view = Plan._view
@@ -785,6 +807,7 @@ class StreamChunkPlan:
         self.logits = self._view(BUF_LOGITS, (S, T, cfg.cls_out), torch.float32)
         self.new = self._view(BUF_STREAM_NEW, (S,), torch.int32)
         self.len = parent.len
+        self.pages, self.page_rows, self.table = parent.pages, parent.page_rows, parent.table     # (a paged parent: its pools, its table)
 
     _h = Plan._h
     _view = Plan._view

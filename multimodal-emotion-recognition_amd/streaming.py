@@ -9,9 +9,16 @@ eval plan's own GEMM / LayerNorm / classifier launches for the rest); this modul
 A history - a dialogue joined in progress, a session moved to another process, the refill after ``reset()`` - is loaded with
 ``prefill``: up to ``max_chunk`` utterances per slot and call through ``runtime.StreamChunkPlan`` (``csrc/attention_stream_chunk.hip``),
 which writes the same cache rows as that many steps at the cost of one forward over the chunk.
+
+PAGED CACHES (``model.stream(..., pages=N, page_rows=16)``): a dense stream reserves ``capacity`` rows per slot and site whether or not
+the dialogue ever fills them.  A paged stream allocates cache rows in pages of ``page_rows`` from one pool of N pages per site through
+a per-slot page table, so memory follows the utterances actually cached and ``max_streams`` can be in the thousands.  The allocation
+lives here on the host (``PageAllocator``), next to the mirrored lengths; the table travels to the device with the inputs, only when it
+changed.  The kernels are the paged forms in the same two files and give the dense stream's bits.
 """
 from __future__ import annotations
 
+import heapq
 from typing import List, Optional, Sequence
 
 import torch
@@ -21,6 +28,7 @@ from .layout import M2FConfig
 
 MAX_CAPACITY = 512
 MAX_CHUNK = 64
+PAGE_ROWS = (16, 32, 64)
 
 
 def resolve_max_chunk(max_chunk) -> int:
@@ -93,8 +101,95 @@ def cache_bytes(cfg: M2FConfig, max_streams: int, capacity: int, bf16: bool = Fa
     return 2 * width * max_streams * capacity * esize
 
 
+def resolve_pages(pages, page_rows):
+    """(None, page_rows): a dense stream; (pages >= 1, page_rows in 16 / 32 / 64): a paged one; ValueError otherwise."""
+    if isinstance(page_rows, bool) or page_rows not in PAGE_ROWS:
+        raise ValueError(f"stream: page_rows must be one of {PAGE_ROWS}, got {page_rows!r}")
+    if pages is None:
+        return None, page_rows
+    if isinstance(pages, bool) or not isinstance(pages, int) or pages < 1:
+        raise ValueError(f"stream: pages must be None (dense caches) or an integer >= 1, got {pages!r}")
+    return pages, page_rows
+
+
+def _pages_of(rows: int, page_rows: int) -> int:
+    return (rows + page_rows - 1) // page_rows
+
+
+def pages_needed(lengths: Sequence[int], new: Sequence[int], capacity: int, page_rows: int, ring: bool) -> List[int]:
+    """Pages each slot GAINS when it takes ``new[s]`` utterances on top of ``lengths[s]``: a slot holds ceil(rows / page_rows) pages for
+    its rows = min(utterances, capacity) live cache rows - on a ring the rows are recycled once ``capacity`` are in use, so a slot never
+    holds more than ceil(capacity / page_rows).  A plain cache cannot pass its capacity: ValueError."""
+    out = []
+    for s, (n, a) in enumerate(zip(lengths, new)):
+        if not ring and n + a > capacity:
+            raise ValueError(f"pages_needed: slot {s} would hold {n + a} utterances, past the capacity {capacity} of a plain cache")
+        out.append(_pages_of(min(n + a, capacity), page_rows) - _pages_of(min(n, capacity), page_rows))
+    return out
+
+
+def cache_bytes_paged(cfg: M2FConfig, pages: int, page_rows: int, bf16: bool = False) -> int:
+    """Bytes of every site's K and V pools: ``cache_bytes`` with ``pages * page_rows`` rows in place of ``max_streams * capacity``."""
+    return cache_bytes(cfg, pages, page_rows, bf16)
+
+
+class PageAllocator:
+    """Which page holds which rows, on the host.  ``pages`` ids 0 .. pages - 1, shared by every attention site; the lowest free id is
+    handed out first, so a run is reproducible.  ``slot_pages[s]`` lists slot s's pages in logical order - entry e holds its cache rows
+    e * page_rows .. - and ``table`` (CPU int32 [slots, ceil(capacity / page_rows)]) carries the same ids for the device; entries past a
+    slot's list are stale and never read.  ``dirty`` is set whenever the table changed since it was last cleared."""
+
+    def __init__(self, pages: int, slots: int, capacity: int, page_rows: int):
+        self.pages, self.slots, self.capacity, self.page_rows = int(pages), int(slots), int(capacity), int(page_rows)
+        self._free = list(range(self.pages))               # a heap: the lowest id first
+        self.slot_pages: List[List[int]] = [[] for _ in range(self.slots)]
+        self.table = torch.zeros(self.slots, _pages_of(self.capacity, self.page_rows), dtype=torch.int32)
+        self.dirty = False
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free)
+
+    def shortfall(self, need: Sequence[int]) -> List[int]:
+        """The slots that would go without a page if ``need[s]`` pages were taken in slot order ([]: everything fits)."""
+        left, short = len(self._free), []
+        for s, n in enumerate(need):
+            if n > left:
+                short.append(s)
+            left -= min(n, left)
+        return short
+
+    def take(self, need: Sequence[int], what: str = "PageAllocator.take") -> None:
+        """Gives slot s ``need[s]`` more pages.  All or nothing: RuntimeError naming the slots left short, nothing changed."""
+        need = [int(n) for n in need]
+        if len(need) != self.slots or any(n < 0 for n in need):
+            raise ValueError(f"{what}: one count >= 0 per slot required")
+        width = self.table.shape[1]
+        over = [s for s, n in enumerate(need) if len(self.slot_pages[s]) + n > width]
+        if over:
+            raise ValueError(f"{what}: slot(s) {over} would hold more than {width} pages, the {self.capacity} rows of a slot")
+        short = self.shortfall(need)
+        if short:
+            raise RuntimeError(f"{what}: slot(s) {short} need a cache page and the pool has {len(self._free)} free of {self.pages} "
+                               f"({sum(need)} needed); reset() finished dialogues or open the stream with more pages")
+        for s, n in enumerate(need):
+            for _ in range(n):
+                page = heapq.heappop(self._free)
+                self.table[s, len(self.slot_pages[s])] = page
+                self.slot_pages[s].append(page)
+                self.dirty = True
+
+    def release(self, slots: Optional[Sequence[int]] = None) -> None:
+        """Returns the pages of those slots (None: of every slot) to the pool."""
+        for s in range(self.slots) if slots is None else slots:
+            for page in self.slot_pages[s]:
+                heapq.heappush(self._free, page)
+            self.slot_pages[s] = []
+
+
 class DialogueStream:
-    """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1)``: ``max_streams`` slots, each one live dialogue.
+    """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1, pages=None, page_rows=16)``: ``max_streams``
+    slots, each one live dialogue.
 
     ``step(text [S, d_t], audio [S, d_a], active=None) -> logits [S, C_out]`` takes ONE new utterance per active slot and returns a
     fresh tensor with its logits (zero rows at inactive slots).  ``active`` is a host-side bool sequence or CPU tensor (None: every
@@ -117,9 +212,16 @@ class DialogueStream:
     rows go through the chunk plan in ceil(n / T) calls of at most T rows per slot (``chunk_schedule``), each one captured graph of a
     forward over S * T rows; with the default ``max_chunk = 1`` it goes through ``step``.  On a stream without a window a history that
     would pass the capacity raises RuntimeError before anything is launched.  ``run`` feeds T columns per call when the batch has
-    the collate layout (every dialogue a valid prefix followed by padding)."""
+    the collate layout (every dialogue a valid prefix followed by padding).
 
-    def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1):
+    PAGED: with ``pages = N`` every site holds pools ``[N][H][page_rows][pad(hd)]`` instead (``cache_bytes_paged``) and a slot takes a
+    page from the shared pool whenever its next row crosses a page boundary (``PageAllocator``; ``pages_free`` tells what is left);
+    ``reset`` returns a slot's pages.  Everything above holds unchanged and the logits are the dense stream's bits.  A ``step``,
+    ``prefill`` or ``run`` that would need more pages than are free raises RuntimeError naming the slots before anything is launched
+    or allocated, and leaves the stream exactly as it was."""
+
+    def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1,
+                 pages: Optional[int] = None, page_rows: int = 16):
         self.model, self.use_graph = model, bool(use_graph)
         self.max_streams, self.capacity = int(max_streams), int(capacity)
         self.max_chunk = resolve_max_chunk(max_chunk)
@@ -129,7 +231,10 @@ class DialogueStream:
         cfg = eng.cfg
         if cfg.dropout != 0.0:
             cfg = M2FConfig(**{**cfg.__dict__, "dropout": 0.0})
-        self.plan = runtime.StreamPlan(cfg, self.max_streams, self.capacity, self.past, eng.precision, eng.flat, eng.wshadow)
+        self.pages, self.page_rows = resolve_pages(pages, page_rows)
+        self.plan = runtime.StreamPlan(cfg, self.max_streams, self.capacity, self.past, eng.precision, eng.flat, eng.wshadow,
+                                       self.pages, self.page_rows)
+        self.allocator = PageAllocator(self.pages, self.max_streams, self.capacity, self.page_rows) if self.pages else None
         self.chunk_plan = runtime.StreamChunkPlan(self.plan, self.max_chunk, eng.flat, eng.wshadow) if self.max_chunk > 1 else None
         self.lengths: List[int] = [0] * self.max_streams
         self._active_host: Optional[List[bool]] = None        # what the device's mask holds (None: not written yet)
@@ -162,6 +267,27 @@ class DialogueStream:
             raise RuntimeError(f"DialogueStream.{what}: the model is in training mode with dropout > 0; a stream scores the model "
                                "without dropout - call model.eval() first")
 
+    @property
+    def pages_free(self) -> Optional[int]:
+        """Free pages of a paged stream's pool (None: a dense stream)."""
+        return None if self.allocator is None else self.allocator.pages_free
+
+    def _reserve(self, new: Sequence[int], what: str) -> None:
+        """Paged: the pages the slots need for ``new[s]`` more utterances each, beyond what they hold - all of them or RuntimeError."""
+        al = self.allocator
+        if al is None:
+            return
+        gain = pages_needed(self.lengths, new, self.capacity, self.page_rows, self.past is not None)
+        held = pages_needed([0] * self.max_streams, self.lengths, self.capacity, self.page_rows, True)
+        al.take([max(0, h + g - len(p)) for h, g, p in zip(held, gain, al.slot_pages)], f"DialogueStream.{what}")
+
+    def _send_table(self) -> None:
+        """(inside _on_stream) the page table travels with the inputs, only when it changed"""
+        al = self.allocator
+        if al is not None and al.dirty:
+            self.plan.table.copy_(al.table, non_blocking=True)
+            al.dirty = False
+
     def _step(self, text, audio, act: List[bool]) -> torch.Tensor:
         """act: one entry per slot (rows of text / audio may be fewer: the leading slots)."""
         self._refuse_training("step")
@@ -170,9 +296,11 @@ class DialogueStream:
             if full:
                 raise RuntimeError(f"DialogueStream.step: slot(s) {full} already hold {self.capacity} utterances, the capacity of a "
                                    "stream without a window (context past=None); reset() the slot, or stream under a window (past, 0)")
+        self._reserve([int(a) for a in act], "step")
         pl, cfg, eng = self.plan, self.plan.cfg, self._eng
 
         def body():
+            self._send_table()
             for buf, x, on, name in ((pl.text_in, text, cfg.text_enabled, "text"), (pl.audio_in, audio, cfg.audio_enabled, "audio")):
                 if not on:
                     continue
@@ -211,7 +339,10 @@ class DialogueStream:
         pl, cfg, eng, T = self.chunk_plan, self.chunk_plan.cfg, self._eng, self.max_chunk
         width = max(new)
 
+        self._reserve(new, "prefill")
+
         def body():
+            self._send_table()
             if new != self._new_host:                       # the counts travel with the inputs (only when they change)
                 pl.new.copy_(torch.tensor(new, dtype=torch.int32), non_blocking=True)
                 self._new_host = list(new)
@@ -260,6 +391,7 @@ class DialogueStream:
             if len(counts) != S or any(not 0 <= c <= n for c in counts):
                 raise ValueError(f"stream.prefill: `counts` needs {S} entries in 0 .. {n}, got {counts}")
         check_prefill_fits(self.lengths, counts, self.capacity, self.past)
+        self._reserve(counts, "prefill")                   # (the whole call's pages, before its first launch)
         return self._feed(text, audio, counts, n)
 
     def _feed(self, text, audio, counts: List[int], n: int) -> torch.Tensor:
@@ -285,6 +417,8 @@ class DialogueStream:
         if slots is None:
             self._on_stream(lambda: self.plan.reset(None))
             self.lengths = [0] * S
+            if self.allocator is not None:
+                self.allocator.release()
             return
         slots = [int(s) for s in slots]
         if any(not 0 <= s < S for s in slots):
@@ -300,6 +434,8 @@ class DialogueStream:
         self._on_stream(body)
         for s in slots:
             self.lengths[s] = 0
+        if self.allocator is not None:
+            self.allocator.release(set(slots))
 
     def run(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], mask: torch.Tensor) -> torch.Tensor:
         """A padded batch (text [B, L, d_t], audio [B, L, d_a], mask bool [B, L], True = pad; B <= max_streams) through the stream:
@@ -318,7 +454,13 @@ class DialogueStream:
             self._refuse_training("run")
             counts = counts + [0] * (S - B)
             check_prefill_fits(self.lengths, counts, self.capacity, self.past)
+            self._reserve(counts, "run")
             return self._feed(text, audio, counts, L)[:B]
+        if self.allocator is not None:                      # (the whole batch's pages, before its first step)
+            rows = valid.sum(1).tolist() + [0] * (S - B)
+            if self.past is None:
+                check_prefill_fits(self.lengths, rows, self.capacity, self.past)
+            self._reserve(rows, "run")
         out = torch.zeros(B, L, self.plan.cfg.cls_out, dtype=torch.float32, device=self._eng.device)
         for i in range(L):
             act = valid[:, i].tolist() + [False] * (S - B)

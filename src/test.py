@@ -67,15 +67,32 @@ def stream_chunk_settings(config):
         raise ValueError(f"runtime.stream_chunk: {e}") from None
 
 
+def stream_pages_settings(config):
+    """`runtime.stream_pages`: 0 (default) = the streamed test pass keeps dense K / V caches; N >= 1 = the stream is opened with `pages=N`
+    (M2FNet.stream: cache rows allocated in pages of 16 from a pool of N per site).  -> int; checked on the host before the GPU is
+    touched."""
+    from train import _runtime
+    from mer_amd.streaming import resolve_pages
+    N = _runtime(config, "stream_pages", 0)
+    N = 0 if N is None else N
+    if isinstance(N, bool) or not isinstance(N, int) or N < 0:
+        raise ValueError(f"runtime.stream_pages: 0 (dense caches) or a number of pages >= 1, got {N!r}")
+    try:
+        return resolve_pages(N or None, 16)[0] or 0
+    except ValueError as e:
+        raise ValueError(f"runtime.stream_pages: {e}") from None
+
+
 def _stream_for(model, B, L):
     """The model's test stream, opened (again) when a batch has more dialogues or - without a window - longer ones than it holds."""
     st = getattr(model, "_test_stream", None)
     windowed = model.context[0] is not None
     chunk = getattr(model, "stream_chunk", 1)
-    if st is None or st.max_streams < B or (not windowed and st.capacity < L) or st.max_chunk != chunk:
+    pages = getattr(model, "stream_pages", 0) or None
+    if st is None or st.max_streams < B or (not windowed and st.capacity < L) or st.max_chunk != chunk or st.pages != pages:
         if st is not None:
             st.close()
-        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64), max_chunk=chunk)
+        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64), max_chunk=chunk, pages=pages)
         model._test_stream = st
     return st
 
@@ -136,6 +153,7 @@ def main(config=None):
     context_settings(config)                               # (refusal before the GPU is touched)
     streaming = streaming_settings(config)
     stream_chunk = stream_chunk_settings(config)
+    stream_pages = stream_pages_settings(config)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     print(f"Using device {device}...")
     runtime_cfg = config.get("runtime", {}) or {}
@@ -147,6 +165,7 @@ def main(config=None):
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     model.streaming = streaming
     model.stream_chunk = stream_chunk
+    model.stream_pages = stream_pages
     from train import ema_settings
     ema = ema_settings(config)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
