@@ -194,6 +194,22 @@ int m2f_stream_prefill(m2f_plan* plan, int use_graph, m2f_stream_t stream);
 int64_t m2f_stream_paged_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows, int shared);
 m2f_plan* m2f_plan_create_stream_paged(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows,
                                        float* params, void* workspace, int64_t workspace_bytes, uint16_t* param_shadow);
+/* SNAPSHOT / RESTORE of a stream plan's dialogues (dense or paged; csrc/stream_cache.hip).  The caches are a dialogue's whole state and
+ * never change once written, so its live rows plus its count are an exact checkpoint.  The packed format: entry e holds the
+ * rows = min(lengths[e], C) live physical rows of slot slots[e] as [site in plan order][K, V][H][rows][pad(hd)] at element
+ * row_offsets[e] * W, W = m2f_stream_snapshot_row_elems(plan) = sum over sites of 2 * H * pad(hd); it does not depend on dense / paged,
+ * page_rows, S or the slot.  m2f_stream_snapshot_sites writes the (H, hd) of up to max_sites sites in plan order and returns their
+ * number.  m2f_stream_gather: caches -> packed for n listed slots; m2f_stream_scatter: packed -> caches and count[slot] = lengths[e]
+ * (a paged plan: M2F_BUF_STREAM_TABLE must already name the pages of those rows).  slots, lengths: device int32 [n]; row_offsets:
+ * device int64 [n]; packed: 16-byte aligned, packed_elems elements of the caches' type.  One eager launch for all sites (per 64
+ * sites), outside the captured step graph - which reads the counts and the table from device buffers and is not recaptured.  Both
+ * refuse a chunk plan, as m2f_stream_reset does.  A snapshot belongs to the parameter values that wrote it. */
+int64_t m2f_stream_snapshot_row_elems(m2f_plan* plan);
+int m2f_stream_snapshot_sites(m2f_plan* plan, int* H, int* hd, int max_sites);
+int m2f_stream_gather(m2f_plan* plan, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
+                      int64_t packed_elems, m2f_stream_t stream);
+int m2f_stream_scatter(m2f_plan* plan, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
+                       int64_t packed_elems, m2f_stream_t stream);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -627,6 +643,30 @@ int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, co
 int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                      void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
                                      const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream);
+/* Snapshot / restore of ONE site's stream caches (csrc/stream_cache.hip): the live rows of listed slots <-> a packed buffer.  Entry e
+ * of n_entries holds the rows = min(lengths[e], C) live PHYSICAL cache rows 0 .. rows - 1 of slot slots[e] (a ring keeps its phase) as
+ * [K, V][H][rows][pad(hd)] - the dense cache with C replaced by rows, pad columns as they are - and starts at element
+ * row_offsets[e] * 2 * H * pad(hd) of `packed` (16-byte aligned, packed_elems elements of the caches' type).  slots, lengths (device
+ * int32) and row_offsets (device int64) have n_entries entries.  gather: caches -> packed, the caches are only read.  scatter:
+ * packed -> caches and count[slot] = lengths[e] (an entry of length 0 resets its slot); rows >= min(lengths[e], C) of a listed slot,
+ * every other slot and - paged - every other page are not written; the caller lists a slot once and keeps lengths <= C on a plain
+ * cache.  An entry out of range (slot outside 0 .. S - 1, negative length or offset, rows past packed_elems) is skipped whole.
+ * The paged forms take the pools and the table of m2f_attention_stream_paged and read the table only at the entries of pages that
+ * hold a row of the entry; the packed bytes do not depend on the form.  Argument checks as m2f_attention_stream[_paged]. */
+int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, int C, int bf16, int n_entries,
+                                      const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
+                                      int64_t packed_elems, m2f_stream_t stream);
+int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, int C, int bf16, int n_entries,
+                                       const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
+                                       int64_t packed_elems, int32_t* count, m2f_stream_t stream);
+int m2f_attention_stream_cache_gather_paged(int S, int H, int hd, const void* kpool, const void* vpool, const int32_t* table, int table_cols,
+                                            int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                            const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
+                                            m2f_stream_t stream);
+int m2f_attention_stream_cache_scatter_paged(int S, int H, int hd, void* kpool, void* vpool, const int32_t* table, int table_cols,
+                                             int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                             const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
+                                             int32_t* count, m2f_stream_t stream);
 /* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
  * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
  * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this

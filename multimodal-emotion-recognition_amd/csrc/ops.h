@@ -289,6 +289,36 @@ size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16); 
 bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg);       // R, table, tw against ab.C; fills lgR
 hipError_t m2f_launch_attn_stream_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, hipStream_t stream);
 hipError_t m2f_launch_attn_stream_chunk_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, int T, const int* n_new, hipStream_t stream);
+// Snapshot / restore of those caches (stream_cache.hip has the packed layout): entry e of n_entries = the min(lengths[e], C) live
+// physical rows of slot slots[e], every listed site, K then V, packed at row row_offsets[e].  One launch for all sites and entries
+// (slices of 65,535 entries); the kernels move 16-byte vectors, so a site is described by `vpr` = vectors per padded row and the
+// element type never enters.  kcache / vcache: the site's caches, or (with a paging) its pools.  scatter: packed -> caches, and
+// len[slot] = lengths[e]; otherwise caches -> packed.  An entry that is out of range (slot, length, offset, rows past packed_vecs)
+// is skipped whole by the kernel.
+#define M2F_STREAM_CACHE_MAX_SITES 64
+struct StreamCacheSite {
+    void* kcache; void* vcache;
+    int H;
+    int vpr;                   // 16-byte vectors per padded row: m2f_stream_cache_row_vecs(hd, bf16)
+    int colv;                  // vectors of one packed row that belong to the sites before this one
+    int pad_;
+};
+struct StreamCacheBatch {
+    int sb[M2F_STREAM_CACHE_MAX_SITES];      // first segment (blockIdx.x) of site i (INT_MAX for unused slots); filled by the launcher
+    StreamCacheSite site[M2F_STREAM_CACHE_MAX_SITES];
+    int count;
+    int S, C;
+    int rowv;                  // vectors of one packed row, all sites of the FORMAT (>= what the listed sites cover)
+    int n_entries, e0;         // e0: first entry of the launch (filled by the launcher)
+    const int* slots;          // device int32 [n_entries]
+    const int* lengths;        // device int32 [n_entries]: utterances of the entry (a ring: the unwrapped count)
+    const int64_t* row_offsets;     // device int64 [n_entries]: first packed row of the entry
+    void* packed;              // 16-byte aligned
+    int64_t packed_vecs;       // vectors the packed buffer holds
+    int* len;                  // scatter: device int32 [S], the plan's counters
+};
+int m2f_stream_cache_row_vecs(int hd, int bf16);
+hipError_t m2f_launch_stream_cache(StreamCacheBatch& cb, const AttnStreamPaging* paging, int scatter, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // Row-wise kernels

@@ -305,6 +305,58 @@ def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     return out
 
 
+def _stream_cache_move(who: str, scatter: bool, kcache, vcache, hd: int, slots, lengths, row_offsets, packed, count, table, capacity, bf16):
+    runtime.require_gpu()
+    want = torch.bfloat16 if bf16 else torch.float32
+    if kcache.dtype != want or vcache.dtype != want or kcache.dim() != 4 or kcache.shape != vcache.shape or not kcache.is_contiguous() \
+            or not vcache.is_contiguous():
+        raise ValueError(f"{who}: the caches must be two contiguous " + ("bfloat16" if bf16 else "float32") + " tensors of one 4-D shape")
+    if packed.dtype != want or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError(f"{who}: packed must be a contiguous 1-D tensor of the caches' type")
+    n = slots.numel()
+    if slots.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.numel() != n or row_offsets.dtype != torch.int64 \
+            or row_offsets.numel() != n:
+        raise ValueError(f"{who}: slots int32 [n], lengths int32 [n] and row_offsets int64 [n] required")
+    if scatter and (count is None or count.dtype != torch.int32):
+        raise ValueError(f"{who}: count int32 [S] required")
+    H = kcache.shape[1]
+    tail = (ptr(count), stream_ptr()) if scatter else (stream_ptr(),)
+    if table is None:
+        S, C = kcache.shape[0], kcache.shape[2]
+        if scatter and count.numel() != S:
+            raise ValueError(f"{who}: count int32 [S] required")
+        fn = lib().m2f_attention_stream_cache_scatter if scatter else lib().m2f_attention_stream_cache_gather
+        check(fn(S, H, hd, ptr(kcache), ptr(vcache), C, int(bf16), n, ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed), packed.numel(),
+                 *tail), who)
+        return
+    S = table.shape[0] if table.dim() == 2 else -1
+    n_pages, R = _paged_args(who, kcache, vcache, table, S, capacity, bf16)
+    if scatter and count.numel() != S:
+        raise ValueError(f"{who}: count int32 [S] required")
+    fn = lib().m2f_attention_stream_cache_scatter_paged if scatter else lib().m2f_attention_stream_cache_gather_paged
+    check(fn(S, H, hd, ptr(kcache), ptr(vcache), ptr(table), table.shape[1], n_pages, R, capacity, int(bf16), n, ptr(slots), ptr(lengths),
+             ptr(row_offsets), ptr(packed), packed.numel(), *tail), who)
+
+
+def attention_stream_cache_gather(kcache: torch.Tensor, vcache: torch.Tensor, hd: int, slots: torch.Tensor, lengths: torch.Tensor,
+                                  row_offsets: torch.Tensor, packed: torch.Tensor, table: Optional[torch.Tensor] = None,
+                                  capacity: Optional[int] = None, bf16: bool = False) -> torch.Tensor:
+    """One site's live cache rows -> `packed` (m2f_attention_stream_cache_gather[_paged], csrc/stream_cache.hip): entry e holds the
+    min(lengths[e], capacity) physical rows 0 .. of slot slots[e] as [K, V][H][rows][pad(hd)] at element row_offsets[e] * 2 * H * pad(hd).
+    kcache / vcache: `attention_stream_caches`, or with `table` (int32 [S, ceil(capacity / page_rows)]) and `capacity` the pools of
+    `attention_stream_pools`.  slots, lengths int32 [n], row_offsets int64 [n] on the device.  Returns packed."""
+    _stream_cache_move("attention_stream_cache_gather", False, kcache, vcache, hd, slots, lengths, row_offsets, packed, None, table, capacity, bf16)
+    return packed
+
+
+def attention_stream_cache_scatter(kcache: torch.Tensor, vcache: torch.Tensor, hd: int, slots: torch.Tensor, lengths: torch.Tensor,
+                                   row_offsets: torch.Tensor, packed: torch.Tensor, count: torch.Tensor, table: Optional[torch.Tensor] = None,
+                                   capacity: Optional[int] = None, bf16: bool = False) -> None:
+    """The reverse of `attention_stream_cache_gather` (m2f_attention_stream_cache_scatter[_paged]): `packed` -> the rows
+    0 .. min(lengths[e], capacity) - 1 of slot slots[e], and count[slots[e]] = lengths[e]; nothing else is written."""
+    _stream_cache_move("attention_stream_cache_scatter", True, kcache, vcache, hd, slots, lengths, row_offsets, packed, count, table, capacity, bf16)
+
+
 def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, drop_site: int = 0, drop_p: float = 0.0,
                   rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
                   future: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

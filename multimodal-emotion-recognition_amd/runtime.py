@@ -146,6 +146,18 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_attention_stream_chunk_paged": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_stream_snapshot_row_elems": (c_int64, [c_void_p]),
+    "m2f_stream_snapshot_sites": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "m2f_stream_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_stream_scatter": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_attention_stream_cache_gather": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_int64, c_void_p]),
+    "m2f_attention_stream_cache_scatter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_int64, c_void_p, c_void_p]),
+    "m2f_attention_stream_cache_gather_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_attention_stream_cache_scatter_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "m2f_stream_chunk_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "m2f_plan_create_stream_chunk": (c_void_p, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_prefill": (c_int, [c_void_p, c_int, c_void_p]),
@@ -756,6 +768,34 @@ class StreamPlan:
 
     def cache_bytes(self) -> int:
         return int(lib().m2f_stream_cache_bytes(self._h()))
+
+    def snapshot_row_elems(self) -> int:
+        """W: elements of one cached utterance over every site, K and V (m2f_stream_snapshot_row_elems)."""
+        n = int(lib().m2f_stream_snapshot_row_elems(self._h()))
+        if n < 0:
+            raise HipError("m2f_stream_snapshot_row_elems: " + lib().m2f_last_error().decode())
+        return n
+
+    def snapshot_sites(self):
+        """((H, hd), ...) of the attention sites in plan order: the order of a snapshot's segments."""
+        n = lib().m2f_stream_snapshot_sites(self._h(), None, None, 0)
+        if n < 0:
+            raise HipError("m2f_stream_snapshot_sites: " + lib().m2f_last_error().decode())
+        H, hd = (c_int * n)(), (c_int * n)()
+        lib().m2f_stream_snapshot_sites(self._h(), H, hd, n)
+        return tuple((int(a), int(b)) for a, b in zip(H, hd))
+
+    def gather(self, slots: torch.Tensor, lengths: torch.Tensor, row_offsets: torch.Tensor, packed: torch.Tensor) -> None:
+        """The live cache rows of the listed slots -> `packed` (m2f_stream_gather).  slots, lengths: device int32 [n]; row_offsets: device
+        int64 [n]; packed: a contiguous 1-D tensor of the caches' element type."""
+        check(lib().m2f_stream_gather(self._h(), slots.numel(), ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed), packed.numel(),
+                                      stream_ptr()), "m2f_stream_gather")
+
+    def scatter(self, slots: torch.Tensor, lengths: torch.Tensor, row_offsets: torch.Tensor, packed: torch.Tensor) -> None:
+        """`packed` -> the cache rows of the listed slots, and len[slot] = lengths[e] (m2f_stream_scatter); a paged plan's table must
+        already name the pages."""
+        check(lib().m2f_stream_scatter(self._h(), slots.numel(), ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed), packed.numel(),
+                                       stream_ptr()), "m2f_stream_scatter")
 
     def num_launches(self) -> int:
         return lib().m2f_plan_num_launches(self._h(), 0) + 1

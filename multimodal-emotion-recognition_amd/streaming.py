@@ -15,6 +15,19 @@ the dialogue ever fills them.  A paged stream allocates cache rows in pages of `
 a per-slot page table, so memory follows the utterances actually cached and ``max_streams`` can be in the thousands.  The allocation
 lives here on the host (``PageAllocator``), next to the mirrored lengths; the table travels to the device with the inputs, only when it
 changed.  The kernels are the paged forms in the same two files and give the dense stream's bits.
+
+SNAPSHOTS (``snapshot`` / ``restore`` / ``evict`` / ``fork``): the caches are a dialogue's whole state and never change once written,
+so its live cache rows plus its length are an exact checkpoint - restoring it gives the bits an uninterrupted stream gives, where a
+``prefill`` recomputes (and under a window is not even exact from a truncated history).  A ``StreamSnapshot`` is one packed 1-D tensor
+of the caches' element type (float32, or bfloat16 in bf16 mode) plus host-side lists.  Entry e holds the ``rows_e = min(length_e, C)``
+live PHYSICAL cache rows 0 .. rows_e - 1 of its slot (a ring keeps its phase), laid out as the dense cache with C replaced by rows_e:
+
+    [site in plan order][K, V][H][rows_e][pad(hd)]
+
+and starts at element ``row_offsets[e] * W``, ``W = sum_sites 2 * H * pad(hd)`` (``cache_bytes(cfg, 1, 1, bf16)`` over the element size);
+pad columns travel as they are (zeros) and every segment starts 16-byte aligned.  The format does not depend on dense or paged caches,
+``page_rows``, ``max_streams`` or the slot number, so a dialogue moves freely between streams of the same model and window.  The rows
+are copied by the gfx950 kernels of ``csrc/stream_cache.hip``, one launch for all sites and slots.
 """
 from __future__ import annotations
 
@@ -186,6 +199,227 @@ class PageAllocator:
                 heapq.heappush(self._free, page)
             self.slot_pages[s] = []
 
+    def state(self) -> tuple:
+        """A copy of the allocation (``set_state`` puts it back and marks the table as changed)."""
+        return list(self._free), [list(p) for p in self.slot_pages], self.table.clone()
+
+    def set_state(self, state: tuple) -> None:
+        free, pages, table = state
+        self._free, self.slot_pages = list(free), [list(p) for p in pages]
+        self.table.copy_(table)
+        self.dirty = True
+
+    def replace_shortfall(self, slots: Sequence[int], need: Sequence[int]) -> List[int]:
+        """The slots of ``slots`` that would go without a page if they returned the pages they hold and then took ``need[e]`` each, in
+        the order given ([]: everything fits)."""
+        left, short = len(self._free) + sum(len(self.slot_pages[s]) for s in slots), []
+        for s, n in zip(slots, need):
+            if n > left:
+                short.append(s)
+            left -= min(n, left)
+        return short
+
+    def replace(self, slots: Sequence[int], need: Sequence[int], what: str = "PageAllocator.replace") -> None:
+        """Slot ``slots[e]`` (each listed once) gives up its pages and takes ``need[e]`` new ones, the lowest free id first.  All or
+        nothing, decided before anything is released: free pages plus the pages those slots hold must cover the need, otherwise
+        RuntimeError naming the slots left short and nothing changed."""
+        slots, need = [int(s) for s in slots], [int(n) for n in need]
+        width = self.table.shape[1]
+        if len(slots) != len(need) or len(set(slots)) != len(slots) or any(not 0 <= s < self.slots for s in slots) \
+                or any(not 0 <= n <= width for n in need):
+            raise ValueError(f"{what}: distinct slots in 0 .. {self.slots - 1} with 0 .. {width} pages each required")
+        short = self.replace_shortfall(slots, need)
+        if short:
+            held = sum(len(self.slot_pages[s]) for s in slots)
+            raise RuntimeError(f"{what}: slot(s) {short} need cache pages the pool cannot give: {sum(need)} needed, {len(self._free)} free "
+                               f"of {self.pages} and {held} held by the target slots; reset() finished dialogues, evict() idle ones or "
+                               "open the stream with more pages")
+        self.release(slots)
+        full = [0] * self.slots
+        for s, n in zip(slots, need):
+            full[s] = n
+        self.take(full, what)
+
+
+def config_sites(cfg: M2FConfig) -> List[tuple]:
+    """(H, hd) of every attention site of the model, encoders first (audio, text), then the fusion layers.  The ORDER of a snapshot's
+    segments is the plan's (``runtime.StreamPlan.snapshot_sites``: launches are merged across the encoders); this list is the same sites
+    and serves the sums that do not depend on the order."""
+    sites = []
+    if cfg.audio_enabled:
+        sites += [(cfg.nhead_audio, cfg.d_audio // cfg.nhead_audio)] * (cfg.ntrans_audio * cfg.nlayers_audio)
+    if cfg.text_enabled:
+        sites += [(cfg.nhead_text, cfg.d_text // cfg.nhead_text)] * (cfg.ntrans_text * cfg.nlayers_text)
+    if cfg.fam_enabled:
+        sites += [(cfg.nhead_fam, cfg.d_fam // cfg.nhead_fam)] * cfg.nlayers_fam
+    return sites
+
+
+def _pad_hd(hd: int, bf16: bool) -> int:
+    q = 8 if bf16 else 4
+    return (hd + q - 1) // q * q
+
+
+def snapshot_row_elems(sites: Sequence[Sequence[int]], bf16: bool) -> int:
+    """W: the elements one cached utterance takes in a snapshot - K and V of every site, heads padded as in the caches."""
+    return sum(2 * H * _pad_hd(hd, bf16) for H, hd in sites)
+
+
+def snapshot_rows(lengths: Sequence[int], ring: Optional[int]) -> List[int]:
+    """Live cache rows per entry: the length itself on a plain cache, min(length, ring capacity) on a ring."""
+    return [int(n) if ring is None else min(int(n), ring) for n in lengths]
+
+
+def snapshot_row_offsets(rows: Sequence[int]) -> List[int]:
+    """First packed row of each entry: the exclusive running sum of the entries' rows."""
+    out, at = [], 0
+    for r in rows:
+        out.append(at)
+        at += r
+    return out
+
+
+def snapshot_segments(sites: Sequence[Sequence[int]], bf16: bool, rows: Sequence[int]) -> List[List[tuple]]:
+    """segments[e][i] = (start, elements) of the i-th (site, K / V, head) segment of entry e in the packed tensor, i running over
+    [site][K, V][H]: each holds rows[e] * pad(hd) elements, rows major."""
+    W = snapshot_row_elems(sites, bf16)
+    out = []
+    for r, off in zip(rows, snapshot_row_offsets(rows)):
+        at, segs = off * W, []
+        for H, hd in sites:
+            for _ in range(2 * H):
+                segs.append((at, r * _pad_hd(hd, bf16)))
+                at += r * _pad_hd(hd, bf16)
+        out.append(segs)
+    return out
+
+
+def make_signature(sites, bf16: bool, past: Optional[int], capacity: int) -> tuple:
+    """What a snapshot and the stream that takes it must share: the (H, hd) of every site in plan order, the precision, the window and -
+    under a window - the ring capacity (None for a plain cache, whose snapshots fit any capacity that holds them)."""
+    return (tuple((int(H), int(hd)) for H, hd in sites), bool(bf16), None if past is None else int(past),
+            None if past is None else int(capacity))
+
+
+def check_restore_slots(slots: Sequence[int], entries: int, max_streams: int) -> List[int]:
+    """One target slot per entry, each in range and listed once: ValueError otherwise."""
+    slots = [int(s) for s in slots]
+    if len(slots) != entries:
+        raise ValueError(f"stream.restore: {entries} snapshot entries need {entries} slots, got {len(slots)}")
+    if any(not 0 <= s < max_streams for s in slots):
+        raise ValueError(f"stream.restore: slots must be in 0 .. {max_streams - 1}, got {slots}")
+    if len(set(slots)) != len(slots):
+        raise ValueError(f"stream.restore: a slot is listed twice in {slots}")
+    return slots
+
+
+def check_restore_fits(lengths: Sequence[int], slots: Sequence[int], capacity: int, past: Optional[int]) -> None:
+    """A plain cache holds at most ``capacity`` utterances: RuntimeError naming the slots whose entry is longer."""
+    if past is not None:
+        return
+    full = [s for s, n in zip(slots, lengths) if n > capacity]
+    if full:
+        raise RuntimeError(f"DialogueStream.restore: the entries for slot(s) {full} hold more than {capacity} utterances, the capacity of "
+                           "this stream without a window (context past=None)")
+
+
+class StreamSnapshot:
+    """The cached state of some dialogues, out of a ``DialogueStream`` (module docstring: the format).  ``data``: the packed tensor;
+    ``lengths``: the true utterance counts (a ring: the unwrapped count); ``row_offsets``: first packed row of each entry;
+    ``signature``: ``make_signature`` of the stream that wrote it.  ``len(snap)`` entries, ``nbytes`` of payload, ``entry(e)`` its (K, V) views per site.  ``select(indices)``
+    picks entries into a new snapshot, ``cpu(pin=False)`` / ``to(device)`` move the payload, ``state_dict()`` /
+    ``StreamSnapshot.from_state_dict(d)`` hold tensors, ints and lists only (``torch.save`` / ``torch.load``).
+    A SNAPSHOT BELONGS TO THE WEIGHTS THAT WROTE IT, like the caches it came from."""
+
+    def __init__(self, data: torch.Tensor, lengths: Sequence[int], row_offsets: Sequence[int], signature: tuple, _ready=None):
+        sites, bf16, past, ring = signature
+        self.signature = make_signature(sites, bf16, past, 0 if ring is None else ring)
+        self.lengths = [int(n) for n in lengths]
+        self.row_offsets = [int(o) for o in row_offsets]
+        rows = self.rows
+        if any(n < 0 for n in self.lengths) or self.row_offsets != snapshot_row_offsets(rows):
+            raise ValueError("StreamSnapshot: lengths must be >= 0 and row_offsets the running sum of the entries' rows")
+        want = torch.bfloat16 if self.signature[1] else torch.float32
+        if data.dim() != 1 or data.dtype != want or data.numel() != sum(rows) * self.row_elems:
+            raise ValueError(f"StreamSnapshot: data must be a 1-D {want} tensor of {sum(rows) * self.row_elems} elements, "
+                             f"got {data.dtype} {tuple(data.shape)}")
+        self._data, self._ready = data, _ready
+
+    @property
+    def data(self) -> torch.Tensor:
+        if self._ready is not None:                        # (an evicted snapshot: its copy to the host may still be under way)
+            self._ready.synchronize()
+            self._ready = None
+        return self._data
+
+    @property
+    def rows(self) -> List[int]:
+        return snapshot_rows(self.lengths, self.signature[3])
+
+    @property
+    def row_elems(self) -> int:
+        return snapshot_row_elems(self.signature[0], self.signature[1])
+
+    @property
+    def nbytes(self) -> int:
+        return self._data.numel() * self._data.element_size()
+
+    def __len__(self) -> int:
+        return len(self.lengths)
+
+    def entry(self, e: int) -> List[tuple]:
+        """Entry e as the caches see it: per site in plan order (K, V), each a view [H, rows_e, pad(hd)] of ``data``."""
+        if not 0 <= int(e) < len(self):
+            raise ValueError(f"StreamSnapshot.entry: entries are 0 .. {len(self) - 1}, got {e}")
+        sites, bf16 = self.signature[0], self.signature[1]
+        rows, data = self.rows, self.data
+        segs = snapshot_segments(sites, bf16, rows)[int(e)]
+        out, i = [], 0
+        for H, hd in sites:
+            kv = []
+            for _ in range(2):
+                start = segs[i][0]
+                kv.append(data[start: start + H * segs[i][1]].view(H, rows[int(e)], _pad_hd(hd, bf16)))
+                i += H
+            out.append(tuple(kv))
+        return out
+
+    def select(self, indices: Sequence[int]) -> "StreamSnapshot":
+        idx = [int(i) for i in indices]
+        if any(not 0 <= i < len(self) for i in idx):
+            raise ValueError(f"StreamSnapshot.select: indices must be in 0 .. {len(self) - 1}, got {idx}")
+        W, rows, data = self.row_elems, self.rows, self.data
+        parts = [data[self.row_offsets[i] * W: (self.row_offsets[i] + rows[i]) * W] for i in idx]
+        picked = torch.cat(parts) if parts else data[:0]
+        return StreamSnapshot(picked, [self.lengths[i] for i in idx], snapshot_row_offsets([rows[i] for i in idx]), self.signature)
+
+    def to(self, device) -> "StreamSnapshot":
+        return StreamSnapshot(self.data.to(device), self.lengths, self.row_offsets, self.signature)
+
+    def cpu(self, pin: bool = False) -> "StreamSnapshot":
+        data = self.data
+        if pin and not data.is_pinned():
+            host = torch.empty(data.shape, dtype=data.dtype, pin_memory=True)
+            host.copy_(data)
+            data = host
+        else:
+            data = data.cpu()
+        return StreamSnapshot(data, self.lengths, self.row_offsets, self.signature)
+
+    def state_dict(self) -> dict:
+        sites, bf16, past, ring = self.signature
+        return {"data": self.data, "lengths": list(self.lengths), "row_offsets": list(self.row_offsets),
+                "sites": [[H, hd] for H, hd in sites], "bf16": int(bf16), "past": -1 if past is None else past,
+                "ring": -1 if ring is None else ring}
+
+    @classmethod
+    def from_state_dict(cls, d: dict) -> "StreamSnapshot":
+        past = None if int(d["past"]) < 0 else int(d["past"])
+        ring = None if int(d["ring"]) < 0 else int(d["ring"])
+        if (past is None) != (ring is None):
+            raise ValueError("StreamSnapshot.from_state_dict: a window and a ring capacity come together")
+        return cls(d["data"], d["lengths"], d["row_offsets"], (tuple((int(H), int(hd)) for H, hd in d["sites"]), bool(d["bf16"]), past, ring))
+
 
 class DialogueStream:
     """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1, pages=None, page_rows=16)``: ``max_streams``
@@ -218,7 +452,20 @@ class DialogueStream:
     page from the shared pool whenever its next row crosses a page boundary (``PageAllocator``; ``pages_free`` tells what is left);
     ``reset`` returns a slot's pages.  Everything above holds unchanged and the logits are the dense stream's bits.  A ``step``,
     ``prefill`` or ``run`` that would need more pages than are free raises RuntimeError naming the slots before anything is launched
-    or allocated, and leaves the stream exactly as it was."""
+    or allocated, and leaves the stream exactly as it was.
+
+    SNAPSHOTS: ``snapshot(slots=None) -> StreamSnapshot`` copies the live cache rows and lengths of those slots (None: every slot; a
+    slot of length 0 gives an empty entry) into one packed device tensor, sized from the host-mirrored lengths; the stream is unchanged.
+    ``restore(snap, slots=None)`` puts entry e into ``slots[e]`` (None: slots 0 .. len(snap) - 1), which are then exactly as the source
+    slots were - same cache rows, same ``lengths``, same device counts - whatever they held before; an empty entry resets its slot.
+    The source may have been dense or paged, of another ``max_streams``, ``page_rows`` or slot, and - without a window - of another
+    capacity that holds the dialogue.  Refused before anything is released or launched: a snapshot of another site geometry,
+    precision, ``past`` or ring capacity (ValueError), duplicate or out-of-range slots (ValueError), on a plain cache a length above
+    the capacity (RuntimeError), and on a paged stream a need the free pages plus the target slots' own pages cannot cover
+    (RuntimeError naming the slots; the stream is left exactly as it was).  ``evict(slots)`` is ``snapshot(slots)`` copied to pinned
+    host memory on the engine's stream, then ``reset(slots)``: on a paged stream the pages are free when it returns, and the copy is
+    ordered before any later write of the stream.  ``fork(src, dst)`` is ``restore(snapshot([src]), [dst])``.  A SNAPSHOT BELONGS TO THE
+    WEIGHTS THAT WROTE IT: the rule above for the caches holds for what was copied out of them."""
 
     def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1,
                  pages: Optional[int] = None, page_rows: int = 16):
@@ -239,6 +486,7 @@ class DialogueStream:
         self.lengths: List[int] = [0] * self.max_streams
         self._active_host: Optional[List[bool]] = None        # what the device's mask holds (None: not written yet)
         self._new_host: Optional[List[int]] = None            # ... and the chunk plan's per-slot row counts
+        self._signature: Optional[tuple] = None               # what a snapshot of this stream carries (read from the plan once)
 
     # -- plumbing ----------------------------------------------------------------------------------------------------------------
     def _on_stream(self, body):
@@ -469,6 +717,91 @@ class DialogueStream:
             logits = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
             out[:, i] = logits[:B]
         return out
+
+    # -- snapshots ---------------------------------------------------------------------------------------------------------------
+    @property
+    def signature(self) -> tuple:
+        if self._signature is None:
+            sites = self.plan.snapshot_sites()
+            if sorted(sites) != sorted(config_sites(self.plan.cfg)):
+                raise RuntimeError(f"stream: the plan reports attention sites {sites}, the configuration has {config_sites(self.plan.cfg)}")
+            self._signature = make_signature(sites, self._eng.precision == runtime.BF16, self.past, self.capacity)
+        return self._signature
+
+    def _entries(self, slots: Sequence[int], lengths: Sequence[int], row_offsets: Sequence[int]):
+        """(inside _on_stream) the per-entry arrays of a gather / scatter, uploaded without waiting for the device"""
+        dev = self._eng.device
+        idx = torch.tensor([list(slots), list(lengths)], dtype=torch.int32).to(dev, non_blocking=True)
+        off = torch.tensor(list(row_offsets), dtype=torch.int64).to(dev, non_blocking=True)
+        return idx[0], idx[1], off
+
+    def _snapshot(self, slots, pinned: bool) -> StreamSnapshot:
+        S = self.max_streams
+        slots = list(range(S)) if slots is None else [int(s) for s in slots]
+        if any(not 0 <= s < S for s in slots):
+            raise ValueError(f"stream.snapshot: slots must be in 0 .. {S - 1}, got {slots}")
+        sig = self.signature
+        lengths = [self.lengths[s] for s in slots]
+        rows = [min(n, self.capacity) for n in lengths]
+        offsets = snapshot_row_offsets(rows)
+        dev = self._eng.device
+        data = torch.empty(sum(rows) * snapshot_row_elems(sig[0], sig[1]), dtype=torch.bfloat16 if sig[1] else torch.float32, device=dev)
+        host = torch.empty(data.shape, dtype=data.dtype, pin_memory=True) if pinned else None
+        ready = None
+
+        def body():
+            nonlocal ready
+            self._send_table()                              # (every path that changes the table sends it; a gather must never depend on that)
+            if data.numel():
+                self.plan.gather(*self._entries(slots, lengths, offsets), data)
+            if host is not None:
+                host.copy_(data, non_blocking=True)
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(dev))
+        self._on_stream(body)
+        return StreamSnapshot(data if host is None else host, lengths, offsets, sig, _ready=ready)
+
+    def snapshot(self, slots: Optional[Sequence[int]] = None) -> StreamSnapshot:
+        return self._snapshot(slots, pinned=False)
+
+    def restore(self, snap: StreamSnapshot, slots: Optional[Sequence[int]] = None) -> None:
+        if snap.signature != self.signature:
+            raise ValueError(f"stream.restore: the snapshot was written under (sites (H, hd), bf16, past, ring capacity) = {snap.signature}, "
+                             f"this stream runs {self.signature}")
+        slots = check_restore_slots(range(len(snap)) if slots is None else slots, len(snap), self.max_streams)
+        check_restore_fits(snap.lengths, slots, self.capacity, self.past)
+        data = snap.data
+        if data.device != self._eng.device:
+            raise ValueError(f"stream.restore: the snapshot lives on {data.device}, the stream on {self._eng.device}; snap.to(device) first")
+        rows = snap.rows
+        if not slots:
+            return
+        al = self.allocator
+        if al is not None:                                  # (all the pages or nothing, before anything is released or launched)
+            before = al.state()
+            al.replace(slots, [_pages_of(r, self.page_rows) for r in rows], "DialogueStream.restore")
+        src = data if data.numel() else torch.zeros(8, dtype=data.dtype, device=data.device)      # (every entry empty: nothing is read)
+
+        def body():
+            self._send_table()                              # the table goes first: the scatter writes through it
+            self.plan.scatter(*self._entries(slots, snap.lengths, snap.row_offsets), src)
+        try:
+            self._on_stream(body)
+        except Exception:                                   # a launch that was refused: the host keeps describing the device -
+            if al is not None:                              # the old pages and lengths; the old table is sent again with the next call
+                al.set_state(before)
+            raise
+        for s, n in zip(slots, snap.lengths):
+            self.lengths[s] = n
+
+    def evict(self, slots: Sequence[int]) -> StreamSnapshot:
+        slots = [int(s) for s in slots]
+        snap = self._snapshot(slots, pinned=True)
+        self.reset(slots)
+        return snap
+
+    def fork(self, src: int, dst: int) -> None:
+        self.restore(self.snapshot([src]), [dst])
 
     def close(self) -> None:
         if self.plan is not None:
