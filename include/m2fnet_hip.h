@@ -57,7 +57,9 @@ enum {
     M2F_BUF_STREAM_ACTIVE = 13, /* uint8 [S]  stream plans, input: 1 = the slot takes an utterance in the next m2f_stream_step */
     M2F_BUF_STREAM_NEW = 14,    /* int32 [S]  chunk plans, input: utterances (0 .. T) the slot takes in the next m2f_stream_prefill */
     M2F_BUF_STREAM_TABLE = 15,  /* int32 [S, ceil(C / page_rows)]  paged stream plans, input: the page of each run of page_rows cache rows of a slot (a chunk plan: its parent's) */
-    M2F_BUF_COUNT = 16
+    M2F_BUF_TEACHER = 16,       /* float [B*L, cls_out]  train plans, input of the distillation criterion: the teacher's logits, token rows as M2F_BUF_LOGITS */
+    M2F_BUF_DISTILL = 17,       /* float [2]  train plans, input of the distillation criterion: alpha, tau (read on the device at every step) */
+    M2F_BUF_COUNT = 18
 };
 
 const char* m2f_last_error(void);
@@ -588,6 +590,21 @@ int m2f_plan_grad_bf16(m2f_plan* plan, uint16_t* grads_bf16);
  * bf16 gradients armed; while it is on, m2f_step_part, m2f_plan_fused_adam(plan, 1) and m2f_plan_grad_bf16(plan, non-NULL) fail. */
 int m2f_plan_accumulate_grads(m2f_plan* plan, int on);
 
+/* Distillation criterion: while m2f_plan_distill(plan, 1) is on, the criterion launch of m2f_loss / m2f_step / m2f_step_part /
+ * m2f_step_timed blends the hard-label cross entropy with the KL divergence from a teacher's logits (M2F_BUF_TEACHER), per token row
+ * (z the plan's logits, u the teacher's, q = softmax(z / tau), p = softmax(u / tau), w_y the class weight of the label or 1):
+ *   num = (1 - alpha) * numCE + alpha * tau^2 * w_y * sum_c p_c (log p_c - log q_c)        den = w_y (unchanged)
+ *   dlogits = (1 - alpha) * dCE + alpha * tau * w_y * (q - p)                              (unnormalised, as ever)
+ * and loss = sum num / sum den through the unchanged tail: ONE denominator, so normalise = 0, the accumulate form and the
+ * data-parallel division by the global den hold as they are.  Without class weights this is (1 - alpha) * CrossEntropyLoss(...) +
+ * alpha * tau^2 * kl_div(log_softmax(z / tau), softmax(u / tau), reduction='batchmean') over the labelled rows.  alpha = 0 gives
+ * the plain criterion's bits.  Rows with label -1 (or out of range) write zeros whatever their teacher row holds.
+ * alpha, tau = M2F_BUF_DISTILL[0], [1] are read ON THE DEVICE by every step (a captured step follows a schedule without a new
+ * capture); the call itself writes nothing and waits for nothing: the caller writes its pair (tau > 0) and the teacher rows on its
+ * stream before the first step, the teacher rows before each step.  A change of the switch bumps the plan's generation: no captured step replays the other criterion.  Works with fused
+ * Adam, bf16 gradients and the accumulate form.  Fails for a plan without a gradient buffer. */
+int m2f_plan_distill(m2f_plan* plan, int on);
+
 /* The 256x256-tile bf16 GEMM on the eight-phase schedule (csrc/gemm_p8.h; round 4), bf16 operands handed over directly - the kernel
  * the weight-gradient table launch (rc = 1) and the text encoder's launches (rc = 0) run, for kernel-level tests and measurements.
  *   rc = 0: C[M,N] = act(A[M,K] B[N,K]^T + bias) + res   (nn.Linear forward: src/feature_extractors/text/model.py:16-21's encoder
@@ -735,6 +752,11 @@ int m2f_dropout_rows(float* x, float* x2, int T, int d, int ld, uint32_t site, u
 int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, const float* class_w,
                       float label_smoothing, int normalise, float* loss_terms, float* dlogits, float* loss_out,
                       m2f_stream_t stream);
+/* The distillation criterion of m2f_plan_distill on its own: m2f_cross_entropy with teacher logits [T, C] and hyper_dev (device
+ * float [2]: alpha in [0, 1], tau > 0). */
+int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
+                              float label_smoothing, const float* hyper_dev, int normalise, float* loss_terms, float* dlogits,
+                              float* loss_out, m2f_stream_t stream);
 
 /* ---- wav2vec2 audio encoder (multimodal-emotion-recognition_amd/wav2vec2.py) ------------------------------------------------------
  * The reference makes its audio embeddings in a separate stage (src/feature_extractors/audio_wav2vec2/embeddings.py:52-91:

@@ -34,7 +34,8 @@ tstats = len(sys.argv) > 2 and sys.argv[1] == "--tstats"
 metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
 # registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
-# rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to
+# rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
+# and for the distillation criterion kernel of the same file (m2f_ce_distill_kernel; its own list below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
 path = sys.argv[2] if (ring or dlong or stream or stream_chunk or stream_cache or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
 rows, cur = [], None
@@ -60,6 +61,11 @@ if adam:
     # shadow-writing: 4 forms each; the exchange
     if len(kernels) < 18:
         sys.exit(f"check_spills: expected the eighteen optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
+    # the other kernel of rowops.hip under this gate: the distillation criterion (a row's 4 x 16 values stay in registers)
+    criterion = [r for r in rows if "m2f_ce_distill_kernel" in r["name"]]
+    if len(criterion) != 1:
+        sys.exit(f"check_spills: expected m2f_ce_distill_kernel in {path}, found {len(criterion)} - did the remark format change?")
+    kernels = kernels + criterion
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

@@ -378,6 +378,22 @@ struct CeArgs {
     float* dlogits;                        // [T, C]
 };
 hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream);
+// Distillation criterion: the same launch with a teacher.  Per token row (q = softmax(z / tau), p = softmax(teacher / tau)):
+//   numerator   = (1 - alpha) * CE numerator + alpha * tau^2 * w_y * KL(p || q)          denominator = w_y, as CeArgs
+//   dlogits     = (1 - alpha) * CE gradient  + alpha * tau * w_y * (q - p)               (unnormalised, as CeArgs)
+// alpha and tau are READ FROM THE DEVICE (hyper[0], hyper[1]): a captured step replays while a schedule changes them.
+// alpha = 0 gives m2f_launch_ce's bits.  Rows with an invalid label write zeros whatever their teacher row holds.
+struct CeDistillArgs {
+    const float* logits; int T, C;
+    const int64_t* labels;                 // [T], ignore_index = -1
+    const float* class_w;                  // [C] or null
+    float label_smoothing;
+    const float* teacher;                  // [T, C] teacher logits, token rows as logits
+    const float* hyper;                    // device float [2]: alpha in [0, 1], tau > 0
+    float* loss_terms;                     // [T, 2] (numerator, denominator)
+    float* dlogits;                        // [T, C]
+};
+hipError_t m2f_launch_ce_distill(const CeDistillArgs& a, hipStream_t stream);
 // loss_out[0] = num/den, loss_out[1] = den, loss_out[2] = num.  normalise != 0: dlogits *= 1/den
 // (single-process mean-over-valid loss); normalise == 0 leaves the sum-gradient for the data-parallel
 // path, which divides by the GLOBAL denominator after the all-reduce.

@@ -465,13 +465,17 @@ class DataParallelStep:
             self.model.set_grad_bf16(False)
 
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
-                 use_graph: bool = True, sync: bool = True) -> torch.Tensor:
-        """sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
+                 use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None) -> torch.Tensor:
+        """teacher_logits, distill=(alpha, temperature): as ``M2FNet.train_step`` - the rank's step runs the distillation criterion
+        (one denominator: the exchange, the global den and the micro-batch group hold as they are); both or neither.
+        sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
-        eng = self.model.engine()
+        from .distill import resolve_distill_args
         B, L = mask.shape
+        dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
+        eng = self.model.engine()
         if self.overlap and self.reducer.world() > 1:
             _refuse_clipped_split(self.optimizer)     # (before any launch or collective: every rank refuses alike)
         if not sync:
@@ -503,6 +507,7 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
+            self.model._set_criterion(plan, teacher_logits, dist)
             if self._pending or getattr(plan, "_acc", False):
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

@@ -522,6 +522,27 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, class_w: Optional[
     return out, dl
 
 
+def cross_entropy_distill(logits: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None,
+                          label_smoothing: float = 0.1, alpha: float = 0.5, temperature: float = 2.0, normalise: bool = True):
+    """The distillation criterion (m2f_cross_entropy_distill): logits, teacher [T, C] fp32, labels int64 [T] (-1 = ignore) ->
+    (loss_out[4] = loss, den, num, -; dlogits [T, C]) of (1 - alpha) * cross entropy + alpha * temperature^2 * KL(softmax(teacher /
+    temperature) || softmax(logits / temperature)), both over the labelled rows with ONE denominator (sum of w_y).  alpha = 0 gives
+    `cross_entropy`'s bits."""
+    runtime.require_gpu()
+    T, C = logits.shape
+    if teacher.shape != logits.shape or teacher.dtype != torch.float32 or logits.dtype != torch.float32:
+        raise ValueError(f"cross_entropy_distill: logits and teacher must be fp32 of one shape (got {tuple(logits.shape)} {logits.dtype}, "
+                         f"{tuple(teacher.shape)} {teacher.dtype})")
+    terms = torch.empty(T, 2, dtype=torch.float32, device=logits.device)
+    dl = torch.empty(T, C, dtype=torch.float32, device=logits.device)
+    out = torch.zeros(4, dtype=torch.float32, device=logits.device)
+    hyper = torch.tensor([float(alpha), float(temperature)], dtype=torch.float32).to(logits.device, non_blocking=True)
+    check(lib().m2f_cross_entropy_distill(T, C, ptr(logits.contiguous()), ptr(teacher.contiguous()), ptr(labels.contiguous()), ptr(class_w),
+                                          label_smoothing, ptr(hyper), int(normalise), ptr(terms), ptr(dl), ptr(out), stream_ptr()),
+          "m2f_cross_entropy_distill")
+    return out, dl
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None) -> torch.Tensor:
     """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity.  past / future: context band of its

@@ -294,8 +294,11 @@ class _Engine:
             if pgrads:
                 self.ensure_grad()
             self._evict(max(self.max_plans, 1) - 1, self.max_plan_bytes)
-            pl = runtime.Plan(cfg, B, L, self.precision, train, self.flat, self.flat_grad_ext if pgrads else None, self.rng, T=T,
-                              param_shadow=self.wshadow)
+            # (outside inference mode even when the caller is inside it: the workspace and its views stay ordinary tensors, so a plan
+            # first used under torch.inference_mode() - a Distiller's teacher - still serves torch.no_grad() and autograd callers)
+            with torch.inference_mode(False):
+                pl = runtime.Plan(cfg, B, L, self.precision, train, self.flat, self.flat_grad_ext if pgrads else None, self.rng, T=T,
+                                  param_shadow=self.wshadow)
             pl._on_cast = self.mark_shadows_fresh
             if train and outputs != (0, True):
                 pl.backward_outputs(*outputs)
@@ -523,12 +526,21 @@ class M2FNet(nn.Module):
     # -- fused fast path (forward + criterion + backward as one launch list / hipGraph) ---------------
     def train_step(self, text, audio, mask, emotion, label_smoothing: float = 0.1,
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
-                   use_graph: bool = True, optimizer=None) -> torch.Tensor:
+                   use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
+                   distill: Optional[Tuple[float, float]] = None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
+        teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
+        distillation criterion (distill.py) - ``(1 - alpha) * cross entropy + alpha * temperature^2 * KL(softmax(teacher / temperature) ||
+        softmax(logits / temperature))`` over the labelled utterances, one kernel in the criterion's place, the same ``loss_terms()``
+        tail; both or neither, anything invalid is a ValueError before any launch.  The pair lives on the device (uploaded only when it
+        changed): a schedule of alpha replays the captured step.  Distilled and plain calls mix freely on one model.
         optimizer (a ``FusedAdam`` of this model): the call is ALSO ``optimizer.step()`` (src/train.py:231) - in bf16 mode the
         weight-gradient launch applies the update itself (``FusedAdam.prepare_fused``; the matrices' ``.grad`` is then not written),
         otherwise the optimizer's own kernel runs behind the step."""
+        from .distill import resolve_distill_args
+        dist = resolve_distill_args(teacher_logits, distill, mask.shape[0], mask.shape[1], self.m2f_config.cls_out, mask.device,
+                                    "M2FNet.train_step")
         eng = self.engine(mask.device)
         if optimizer is not None and eng.accumulate:
             raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
@@ -541,6 +553,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
+            self._set_criterion(plan, teacher_logits, dist)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -565,6 +578,15 @@ class M2FNet(nn.Module):
             loss = body()
         eng.publish_grads()
         return loss[0].clone()          # (the buffer is overwritten by the next step)
+
+    @staticmethod
+    def _set_criterion(plan, teacher_logits, dist) -> None:
+        """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
+        temperature), or (dist None) the plain one.  After `set_inputs` (a packed plan maps the teacher rows as it mapped the batch)."""
+        plan.distill(dist is not None)
+        if dist is not None:
+            plan.set_teacher(teacher_logits)
+            plan.set_distill_hyper(*dist)
 
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,

@@ -73,6 +73,52 @@ class M2FCrossEntropyLoss(nn.Module):
         return _CEFunction.apply(logits.contiguous().float(), target.reshape(-1).contiguous(), w, self.label_smoothing)
 
 
+class _DistillFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits2d, teacher2d, target1d, weight, label_smoothing, alpha, temperature):
+        out, dl = F.cross_entropy_distill(logits2d, teacher2d, target1d, weight, label_smoothing, alpha, temperature, True)
+        ctx.save_for_backward(dl)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dl,) = ctx.saved_tensors
+        return dl * grad_out, None, None, None, None, None, None
+
+
+class M2FDistillationLoss(nn.Module):
+    """``(1 - alpha) * M2FCrossEntropyLoss + alpha * temperature^2 * KL(softmax(teacher / temperature) || softmax(input / temperature))``
+    over the labelled rows, one kernel (``functional.cross_entropy_distill``; the criterion ``M2FNet.train_step(teacher_logits=,
+    distill=)`` runs inside the step) on the autograd surface.  ``forward(input, target, teacher_logits)``: input and teacher_logits
+    ``[B, C, L]`` or ``[T, C]``, target ``[B, L]`` or ``[T]``; the teacher gets no gradient."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -1, label_smoothing: float = 0.1,
+                 alpha: float = 0.5, temperature: float = 2.0):
+        super().__init__()
+        if ignore_index != -1:
+            raise ValueError("the fused criterion implements ignore_index=-1 (reference src/train.py:48-50)")
+        from .distill import check_distill
+        self.alpha, self.temperature = check_distill((alpha, temperature), "M2FDistillationLoss")
+        self.register_buffer("weight", weight)
+        self.label_smoothing = float(label_smoothing)
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor, teacher_logits: torch.Tensor) -> torch.Tensor:
+        from .distill import check_distill
+        alpha, temperature = check_distill((self.alpha, self.temperature), "M2FDistillationLoss")
+        if teacher_logits.shape != input.shape:
+            raise ValueError(f"M2FDistillationLoss: teacher_logits {tuple(teacher_logits.shape)} must have the input's shape "
+                             f"{tuple(input.shape)}")
+        if input.dim() == 3:
+            C = input.shape[1]
+            logits = input.permute(0, 2, 1).reshape(-1, C)
+            teacher = teacher_logits.permute(0, 2, 1).reshape(-1, C)
+        else:
+            logits, teacher = input, teacher_logits
+        w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
+        return _DistillFunction.apply(logits.contiguous().float(), teacher.detach().contiguous().float(), target.reshape(-1).contiguous(),
+                                      w, self.label_smoothing, alpha, temperature)
+
+
 class FusedAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` (coupled L2 weight decay, reference ``src/train.py:56``) as ONE kernel over the model's flat
     parameter / gradient / moment buffers.  Differences from torch worth knowing: every parameter of the model is updated every

@@ -24,7 +24,8 @@ HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "m2fnet_hip.h
 F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
- BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE) = range(16)
+ BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
+ BUF_TEACHER, BUF_DISTILL) = range(18)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -171,6 +172,7 @@ SIGNATURES = {
     "m2f_set_shadow_map": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
     "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),
+    "m2f_plan_distill": (c_int, [c_void_p, c_int]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
@@ -217,6 +219,8 @@ SIGNATURES = {
     "m2f_dropout_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_uint32, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_cross_entropy": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "m2f_cross_entropy_distill": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -383,6 +387,12 @@ class Plan:
         else:
             self.loss = self._view(BUF_LOSS, (4,), torch.float32)
         self._dlogits = self._view(BUF_DLOGITS, (self.T, C) if self.packed else (B, L, C), torch.float32)
+        # inputs of the distillation criterion (train plans with a gradient buffer; `distill`): the teacher's logits in the token rows
+        # of the plan's own logits, and the (alpha, temperature) pair the criterion kernel reads on the device
+        self._teacher = self._view(BUF_TEACHER, (self.T, C) if self.packed else (B, L, C), torch.float32) if train else None
+        self.distill_hyper = self._view(BUF_DISTILL, (2,), torch.float32) if train else None
+        self._distill = False
+        self.hyper_host = None                # host mirror of distill_hyper: what was last uploaded (None: nothing yet)
         self._fam0_out = (self._view(BUF_FAM0_OUT, (self.T, pad8(cfg.d_fam)) if self.packed else (B, L, pad8(cfg.d_fam)),
                                      torch.float32)[..., : cfg.d_fam] if cfg.fam_enabled else None)
         # shape of the batch last handed to set_inputs: a plan may be larger than the batch it runs (shape buckets), the
@@ -547,6 +557,46 @@ class Plan:
         if self.in_B != self.B or self.in_L != self.L:
             self._dlogits.zero_()                 # filler slots of a bucketed plan carry no gradient
         self._dlogits[: self.in_B, : self.in_L].copy_(g.reshape(self.in_B, self.in_L, -1))
+
+    @property
+    def teacher(self) -> torch.Tensor:
+        """The teacher rows of the last batch on its padded surface [b, l, C] (as `logits`)."""
+        if self._teacher is None:
+            raise HipError("this plan holds no teacher buffer (an eval plan)")
+        if self.packed:
+            return self._unpack(self._teacher)
+        return self._teacher[: self.in_B, : self.in_L]
+
+    def set_teacher(self, u: torch.Tensor) -> None:
+        """The teacher's logits of the last batch ([b, l, C], padded surface) into the plan's buffer: they travel as `set_dlogits`
+        moves a gradient - filler rows of a bucketed plan zero, packed plans through the batch's row map with the spare row cleared."""
+        if self._teacher is None:
+            raise HipError("this plan holds no teacher buffer (an eval plan)")
+        if self.packed:
+            self._teacher.zero_()
+            self._teacher.index_copy_(0, self._dst.reshape(-1), (u * self._valid[..., None].to(u.dtype)).reshape(-1, u.shape[-1]))
+            self._clear_spare(self._teacher, 0)
+            return
+        if self.in_B != self.B or self.in_L != self.L:
+            self._teacher.zero_()                 # filler slots of a bucketed plan: label -1, the criterion selects zeros there
+        self._teacher[: self.in_B, : self.in_L].copy_(u.reshape(self.in_B, self.in_L, -1))
+
+    def distill(self, on: bool) -> None:
+        """m2f_plan_distill: the NEXT losses / steps run the distillation criterion on `teacher` and `distill_hyper` (on) / the plain
+        criterion (off).  A change drops the captured steps.  Neither writes nor waits: `set_distill_hyper` and `set_teacher` fill the
+        two buffers on the stream before the step.  Raises for a plan without a gradient buffer."""
+        on = bool(on)
+        if on == self._distill:
+            return
+        check(lib().m2f_plan_distill(self._h(), int(on)), "m2f_plan_distill")
+        self._distill = on
+
+    def set_distill_hyper(self, alpha: float, temperature: float) -> None:
+        """(alpha, temperature) into `distill_hyper`, uploaded only when the pair differs from the host mirror of the last upload."""
+        pair = (float(alpha), float(temperature))
+        if pair != self.hyper_host:
+            self.distill_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
+            self.hyper_host = pair
 
     def _casted(self) -> None:
         if self.shared_shadow and not self._fresh and self._on_cast is not None:

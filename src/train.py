@@ -116,6 +116,89 @@ def ema_settings(cfg):
     return float(decay), flags["warmup"], flags["evaluate"]
 
 
+DISTILL_KEYS = ("enabled", "teacher_checkpoint", "teacher_weights", "alpha", "temperature", "teacher_context")
+
+
+def resolve_distill(cfg):
+    """`runtime.distill` = {enabled, teacher_checkpoint, teacher_weights, alpha, temperature, teacher_context}: train the model against
+    the logits of a teacher with the `model:` geometry whose weights come from a checkpoint this loop wrote (mer_amd.distill) - the
+    usual case is an online student (runtime.context: {past: ..., future: 0}) under an offline teacher (teacher_context both null).
+    teacher_weights: model | ema picks the checkpoint's model_state_dict or the parameters of its ema_state_dict.  -> None when the block
+    is absent or disabled, else a dict {checkpoint, weights, alpha, temperature, context}.  Checked on the host before the GPU is
+    touched: needs runtime.fused_step: True (the criterion lives in the train step)."""
+    from mer_amd.distill import check_distill
+    block = _runtime(cfg, "distill", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.distill must be a mapping {{{', '.join(DISTILL_KEYS)}}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - set(DISTILL_KEYS))
+    if unknown:
+        raise ValueError(f"runtime.distill: unknown key(s) {unknown} ({', '.join(DISTILL_KEYS)})")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.distill.enabled must be true or false (got {enabled!r})")
+    weights = block.get("teacher_weights", "model")
+    if weights not in ("model", "ema"):
+        raise ValueError(f"runtime.distill.teacher_weights must be model or ema (got {weights!r})")
+    try:
+        alpha, temperature = check_distill((block.get("alpha", 0.5), block.get("temperature", 2.0)), "runtime.distill")
+    except ValueError as e:
+        raise ValueError(str(e).replace("distill alpha", "alpha").replace("distill temperature", "temperature")) from None
+    ctx = block.get("teacher_context", None)
+    ctx = {} if ctx is None else ctx
+    if not hasattr(ctx, "keys") or set(ctx.keys()) - {"past", "future"}:
+        raise ValueError(f"runtime.distill.teacher_context must be a mapping {{past, future}} (got {ctx!r})")
+    band = []
+    for k in ("past", "future"):
+        v = ctx.get(k, None)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+            raise ValueError(f"runtime.distill.teacher_context.{k} must be null or an integer >= 0 (got {v!r})")
+        band.append(v)
+    path = block.get("teacher_checkpoint", None)
+    if path is not None and not isinstance(path, str):
+        raise ValueError(f"runtime.distill.teacher_checkpoint must be null or a path (got {path!r})")
+    if not enabled:
+        return None
+    if not path:
+        raise ValueError("runtime.distill.enabled needs runtime.distill.teacher_checkpoint: a checkpoint written by this loop")
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.distill.enabled needs runtime.fused_step: True (the distillation criterion lives in the train step)")
+    return {"checkpoint": path, "weights": weights, "alpha": alpha, "temperature": temperature, "context": (band[0], band[1])}
+
+
+def attach_distiller(config, model, device):
+    """runtime.distill enabled: builds the teacher (the `model:` geometry, runtime.precision, the block's context band), loads its weights
+    from the checkpoint and hangs a mer_amd.distill.Distiller on the model (object.__setattr__: not a sub-module - state_dict, the
+    checkpoint, validate() and test.py hold and score the student only).  train() then distils in every branch.  -> the Distiller or None."""
+    settings = resolve_distill(config)
+    if settings is None:
+        return None
+    from mer_amd.distill import Distiller
+    path = os.path.abspath(settings["checkpoint"])
+    state = torch.load(path, map_location=device)
+    if settings["weights"] == "ema":
+        if EMA_KEY not in state:
+            raise ValueError(f"runtime.distill.teacher_weights: ema, but {path} holds no {EMA_KEY} (it was written without runtime.ema)")
+        weights = state[EMA_KEY]["parameters"]
+    else:
+        weights = state["model_state_dict"]
+    teacher = M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=settings["context"])
+    teacher.load_state_dict(weights)
+    teacher = teacher.to(device)
+    distiller = Distiller(model, teacher, alpha=settings["alpha"], temperature=settings["temperature"])
+    object.__setattr__(model, "distiller", distiller)
+    return distiller
+
+
+def _distill_kw(model, text, audio, padding_mask):
+    """{teacher_logits, distill} of this batch for train_step / DataParallelStep when the model carries a Distiller, else nothing."""
+    d = getattr(model, "distiller", None)
+    if d is None:
+        return {}
+    return {"teacher_logits": d.teacher_logits(text, audio, padding_mask), "distill": (d.alpha, d.temperature)}
+
+
 def context_settings(cfg):
     """`runtime.context` = {past, future}: the context band of every attention site of the model (M2FNet(context=...)) - utterance i
     attends to utterances i - past .. i + future of its dialogue; null = unlimited on that side.  {past: null, future: 0} is the online
@@ -432,6 +515,7 @@ def main(config=None):
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
     context_settings(config)
+    resolve_distill(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -503,6 +587,7 @@ def main(config=None):
         # the audio rows are computed in the loop from waveforms; built outside the fusion model, like the text encoder
         object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
                                                                              n_head=config.model.AUDIO.n_head))
+    attach_distiller(config, model, device)
     criterion = build_criterion(config.solver, train_set, device)
     optimizer = build_optimizer(config, model)
     optimizer.max_grad_norm = clip_grad_norm(config, world)
@@ -657,13 +742,14 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                           class_weights=criterion.weight, use_graph=use_graph)
+                           class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask))
         else:
             optimizer.zero_grad()
             if fused and getattr(model, "fused_optimizer", False) and isinstance(optimizer, FusedAdam):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                        class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer)
+                                        class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer,
+                                        **_distill_kw(model, text, audio, padding_mask))
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
@@ -671,8 +757,10 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                        class_weights=criterion.weight, use_graph=use_graph)
+                                        class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask))
             else:
+                if getattr(model, "distiller", None) is not None:
+                    raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
                 loss = criterion(model(text, audio, padding_mask).permute(0, 2, 1), emotion)
                 loss.backward()
             optimizer.step()
@@ -705,10 +793,12 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
                                                                audio_encoder=getattr(model, "audio_encoder", None))
             if dp_step is not None:
                 loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                               class_weights=criterion.weight, use_graph=use_graph, sync=j == len(group) - 1)
+                               class_weights=criterion.weight, use_graph=use_graph, sync=j == len(group) - 1,
+                               **_distill_kw(model, text, audio, padding_mask))
             else:
                 model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                 class_weights=criterion.weight, normalise=False, use_graph=use_graph)
+                                 class_weights=criterion.weight, normalise=False, use_graph=use_graph,
+                                 **_distill_kw(model, text, audio, padding_mask))
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
