@@ -4,12 +4,17 @@
 // Under a causal context band (past, 0) layer l's K and V rows of utterance j depend on utterances <= j only, so they are computed
 // once, stored here, and never change; a step then costs one row per dialogue instead of the whole prefix.
 //
-// CACHE LAYOUT (per attention site, K and V alike):   cache[S][H][C][hdp]
-//   S slots, H heads, C rows of capacity, hdp = the head dim padded to a 16-byte multiple: pad4(hd) floats (fp32 mode) or pad8(hd)
-//   bf16 values (bf16 mode).  A head's rows are contiguous, every row starts 16-byte aligned, pad columns hold zeros.
-//   m2f_attn_stream_cache_elems gives the element count.  Row r of a slot holds utterance r (plain cache, len < C) or utterance
-//   u with u % C == r (ring: a window of past = C - 1 utterances; the row of the utterance that just left the window is the one the
-//   new utterance overwrites).  The number of live rows comes from len[s] alone, so stale rows behind a reset are never read.
+// CACHE LAYOUT (per attention site, K and V alike), in one of two addressings:
+//   dense   cache[S][H][C][hdp]        S slots, H heads, C rows of capacity
+//   paged   pool[n_pages][H][R][hdp]   R = 16, 32 or 64 rows per page; logical cache row j of slot s lives at row j % R of page
+//                                      table[s][j / R], table = int32 [S][ceil(C / R)].  Page ids are shared by every site of a
+//                                      stream: page p is index p of every site's pool.
+//   hdp = the head dim padded to a 16-byte multiple (m2f_stream_hdp): pad4(hd) floats (fp32 mode) or pad8(hd) bf16 values (bf16 mode).
+//   A head's rows (dense) or its rows of one page (paged) are contiguous, every row starts 16-byte aligned, pad columns hold zeros.
+//   m2f_attn_stream_cache_elems / m2f_attn_stream_pool_elems give the element counts.  Row r of a slot holds utterance r (plain cache,
+//   len < C) or utterance u with u % C == r (ring: a window of past = C - 1 utterances; the row of the utterance that just left the
+//   window is the one the new utterance overwrites).  The number of live rows comes from len[s] alone, so stale rows behind a reset are
+//   never read.
 //
 // One wavefront per (s, h): byte-stream work (every cached row is read exactly once, with 16-byte loads straight into VGPRs), no MFMA.
 // A row is spread over CH = 2^k lanes (4 floats / 8 bf16 each; lanes past the row's end hold zeros in registers, no divergent tail),
@@ -18,51 +23,26 @@
 // No atomics, a fixed summation order: the same bits on every run.  The slot's own K / V row is taken from LDS, where the new rows are
 // staged (rounded once in bf16 mode: what the cache then holds), never read back from the cache row the same wave has just written.
 // len[] is NOT advanced here: every site of a step reads the same count, m2f_launch_stream_advance closes the step.
+//
+// The two addressings are ONE kernel body (attn_stream_body<BF16, PAGED>): work split, row order, arithmetic and summation order are
+// one text, so the paged form gives the dense form's bits.  Behind PAGED stand only the fetch of the slot's page ids into LDS
+// (attn_stream_rows.h: the entries of pages that hold a live row or take the new one, e < ceil(min(len + 1, C) / R)), the base pointer
+// of a head's rows and the offset of row j.
 #include "common.h"
 #include "ops.h"
+#include "attn_stream_rows.h"
 
 namespace {
 
-template <bool BF16> struct Row;
-template <> struct Row<false> {
-    static constexpr int EPL = 4;                 // elements per lane and 16-byte access
-    typedef float elem_t;
-    __device__ static __forceinline__ void load(const elem_t* p, float (&x)[4]) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-        x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
-    }
-    __device__ static __forceinline__ void store(elem_t* p, const float (&x)[4]) {
-        const f32x4 v = {x[0], x[1], x[2], x[3]};
-        *reinterpret_cast<f32x4*>(p) = v;
-    }
-};
-template <> struct Row<true> {
-    static constexpr int EPL = 8;
-    typedef uint16_t elem_t;
-    __device__ static __forceinline__ void load(const elem_t* p, float (&x)[8]) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __builtin_bit_cast(float, v[i] << 16);
-            x[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xffff0000u);
-        }
-    }
-    __device__ static __forceinline__ void store(elem_t* p, const float (&x)[8]) {       // (x: already bf16 values)
-        u32x4 v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (uint32_t)m2f_bf16_bits(x[2 * i]) | ((uint32_t)m2f_bf16_bits(x[2 * i + 1]) << 16);
-        *reinterpret_cast<u32x4*>(p) = v;
-    }
-};
-
-template <bool BF16>
-__global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
+template <bool BF16, bool PAGED>
+__device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg) {
     typedef Row<BF16> R;
     typedef typename R::elem_t elem_t;
     constexpr int EPL = R::EPL;
     constexpr int U = 4;                          // passes in flight: their loads are issued together
     __shared__ float sq[128], sk[128], sv[128];   // the slot's new rows of this head, zero behind hd (bf16 mode: rounded)
     __shared__ float sc[M2F_ATTN_STREAM_MAX_C];   // scores, then the unnormalised probabilities
+    __shared__ int spg[32];                       // paged: the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
 
     const int blk = blockIdx.x, lane = threadIdx.x;
     int pi = 0;
@@ -71,7 +51,7 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBat
     const int local = blk - ab.bb[pi];
     const int s = local / P.H, h = local - s * P.H;
     const int hd = P.hd, C = ab.C;
-    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    const int hdp = m2f_stream_hdp(hd, BF16);
     float* orow = P.out + (size_t)s * P.ldo + (size_t)h * hd;
     uint16_t* orow16 = m2f_shadow_of(ab.sh, orow);
 
@@ -86,7 +66,9 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBat
     }
     const int pos = ab.ring ? n_old % C : n_old;              // the row the new utterance takes
     const int nslots = n_old + 1 < C ? n_old + 1 : C;         // live rows, the new one included
+    const int lgR = PAGED ? pg.lgR : 0;
 
+    if (PAGED) m2f_stream_page_ids(spg, pg, s, nslots, lane);
     {   // the new rows -> LDS
         const float* qrow = P.q + (size_t)s * P.ldq + (size_t)h * hd;
         const float* krow = P.k + (size_t)s * P.ldk + (size_t)h * hd;
@@ -110,181 +92,13 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBat
     const bool cact = c < nch;
     const int e0 = c * EPL;                       // (< 128 for every lane: CH * EPL <= 128)
 
-    elem_t* kc = static_cast<elem_t*>(P.kcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
-    elem_t* vc = static_cast<elem_t*>(P.vcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    // this lane's chunk of row 0 of the head: of the slot's cache (dense) or of page 0 (paged), and from there to row j
+    const size_t page_stride = (size_t)P.H * (size_t)(hdp << lgR);       // paged: elements of one page, all heads
+    const size_t head0 = PAGED ? (size_t)h * (size_t)(hdp << lgR) + e0 : ((size_t)s * P.H + h) * (size_t)C * hdp + e0;
+    elem_t* kc = static_cast<elem_t*>(P.kcache) + head0;
+    elem_t* vc = static_cast<elem_t*>(P.vcache) + head0;
+    auto row_off = [&](int j) { return PAGED ? m2f_stream_row_off(spg, lgR, page_stride, j, hdp) : (size_t)j * hdp; };
     if (r == 0 && cact) {                         // the new K / V rows into the cache (vector stores; pad columns: zeros)
-        float kx[EPL], vx[EPL];
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) { kx[i] = sk[e0 + i]; vx[i] = sv[e0 + i]; }
-        R::store(kc + (size_t)pos * hdp + e0, kx);
-        R::store(vc + (size_t)pos * hdp + e0, vx);
-    }
-
-    float qx[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) qx[i] = sq[e0 + i];
-    const float scale = 1.0f / sqrtf((float)hd);
-
-    // ---- pass 1: scores ---------------------------------------------------------------------------------------------------------
-    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
-        float kx[U][EPL];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * RPW + r;
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) kx[u][i] = 0.f;
-            if (cact && j < nslots) {
-                if (j != pos) R::load(kc + (size_t)j * hdp + e0, kx[u]);
-                else {
-#pragma unroll
-                    for (int i = 0; i < EPL; ++i) kx[u][i] = sk[e0 + i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * RPW + r;
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) d = fmaf(qx[i], kx[u][i], d);
-            for (int o = CH >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-            if (c == 0 && j < nslots) sc[j] = d * scale;
-        }
-    }
-    __syncthreads();
-
-    // ---- softmax over the live rows (fp32, max-subtracted) ------------------------------------------------------------------------
-    float m = -INFINITY;
-    for (int j = lane; j < nslots; j += 64) m = fmaxf(m, sc[j]);
-    m = m2f_wave_max(m);
-    float sum = 0.f;
-    for (int j = lane; j < nslots; j += 64) {
-        const float e = __expf(sc[j] - m);
-        sc[j] = e;
-        sum += e;
-    }
-    sum = m2f_wave_sum(sum);
-    const float inv = 1.0f / sum;                 // (sum >= 1: the row of the maximum contributes exp(0))
-    __syncthreads();
-
-    // ---- pass 2: P V ---------------------------------------------------------------------------------------------------------------
-    float acc[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
-    for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
-        float vx[U][EPL], p[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * RPW + r;
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) vx[u][i] = 0.f;
-            p[u] = 0.f;
-            if (cact && j < nslots) {
-                p[u] = sc[j];
-                if (j != pos) R::load(vc + (size_t)j * hdp + e0, vx[u]);
-                else {
-#pragma unroll
-                    for (int i = 0; i < EPL; ++i) vx[u][i] = sv[e0 + i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) acc[i] = fmaf(p[u], vx[u][i], acc[i]);
-    }
-    for (int o = CH; o < 64; o <<= 1) {
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
-    }
-    if (r == 0 && cact) {
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) {
-            if (e0 + i < hd) {
-                const float o = acc[i] * inv;
-                orow[e0 + i] = o;
-                if (orow16) orow16[e0 + i] = m2f_bf16_bits(o);
-            }
-        }
-    }
-}
-
-// PAGED FORM.  The same problem over a page pool instead of a per-slot cache:   pool[n_pages][H][R][hdp]
-//   R = 16, 32 or 64 rows per page; one page of a head is contiguous, rows padded and aligned as above.  Logical cache row j of slot s
-//   (the row the dense kernel calls j) lives at row j % R of page table[s][j / R], table = int32 [S][ceil(C / R)].  Page ids are shared
-//   by every site of a stream: page p is index p of every site's pool.
-// Work split, row order, arithmetic and summation order are the dense kernel's statement for statement, so the results are its bits;
-// only the address of a row differs.  The wave fetches its slot's page ids ONCE - lane e loads entry e (<= 32 entries: 512 rows of
-// 16-row pages) into LDS - and the row loops take the id from LDS: no dependent global load per row.  Only the entries of pages that
-// hold a live row or take the new one are loaded (e < ceil(min(len + 1, C) / R)); entries behind that are never dereferenced,
-// whatever they hold.  An id is clamped to the pool (0 .. n_pages - 1): a torn table reads the wrong page, never unmapped memory.
-template <bool BF16>
-__global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
-    typedef Row<BF16> R;
-    typedef typename R::elem_t elem_t;
-    constexpr int EPL = R::EPL;
-    constexpr int U = 4;
-    __shared__ float sq[128], sk[128], sv[128];
-    __shared__ float sc[M2F_ATTN_STREAM_MAX_C];
-    __shared__ int spg[32];                       // the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
-
-    const int blk = blockIdx.x, lane = threadIdx.x;
-    int pi = 0;
-    while (pi + 1 < ab.count && blk >= ab.bb[pi + 1]) ++pi;
-    const AttnStreamProblem& P = ab.pr[pi];
-    const int local = blk - ab.bb[pi];
-    const int s = local / P.H, h = local - s * P.H;
-    const int hd = P.hd, C = ab.C;
-    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
-    float* orow = P.out + (size_t)s * P.ldo + (size_t)h * hd;
-    uint16_t* orow16 = m2f_shadow_of(ab.sh, orow);
-
-    const int n_old = ab.len[s];
-    const bool live = ab.active[s] != 0 && n_old >= 0 && (ab.ring || n_old < C);
-    if (!live) {
-        for (int i = lane; i < hd; i += 64) {
-            orow[i] = 0.f;
-            if (orow16) orow16[i] = 0;
-        }
-        return;
-    }
-    const int pos = ab.ring ? n_old % C : n_old;
-    const int nslots = n_old + 1 < C ? n_old + 1 : C;
-    const int lgR = pg.lgR, rmask = (1 << lgR) - 1;
-
-    if (lane < 32) {                              // the page ids -> LDS (one 4-byte load per page that may be read)
-        int id = 0;
-        if (lane < ((nslots + rmask) >> lgR)) id = pg.table[(size_t)s * pg.tw + lane];
-        spg[lane] = min(max(id, 0), pg.n_pages - 1);
-    }
-    {   // the new rows -> LDS
-        const float* qrow = P.q + (size_t)s * P.ldq + (size_t)h * hd;
-        const float* krow = P.k + (size_t)s * P.ldk + (size_t)h * hd;
-        const float* vrow = P.v + (size_t)s * P.ldv + (size_t)h * hd;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int i = lane + 64 * t;
-            float a = 0.f, b = 0.f, c = 0.f;
-            if (i < hd) { a = qrow[i]; b = krow[i]; c = vrow[i]; }
-            if (BF16) { a = m2f_bf16_to_f32(m2f_bf16_bits(a)); b = m2f_bf16_to_f32(m2f_bf16_bits(b)); c = m2f_bf16_to_f32(m2f_bf16_bits(c)); }
-            sq[i] = a; sk[i] = b; sv[i] = c;
-        }
-    }
-    __syncthreads();
-
-    const int nch = hdp / EPL;
-    int CH = 1, lg = 0;
-    while (CH < nch) { CH <<= 1; ++lg; }
-    const int RPW = 64 >> lg;
-    const int r = lane >> lg, c = lane & (CH - 1);
-    const bool cact = c < nch;
-    const int e0 = c * EPL;
-
-    const size_t page_stride = (size_t)P.H * (size_t)(hdp << lgR);       // elements of one page, all heads
-    elem_t* kc = static_cast<elem_t*>(P.kcache) + (size_t)h * (size_t)(hdp << lgR) + e0;      // this head's rows of page 0, this lane's chunk
-    elem_t* vc = static_cast<elem_t*>(P.vcache) + (size_t)h * (size_t)(hdp << lgR) + e0;
-    auto row_off = [&](int j) { return (size_t)spg[j >> lgR] * page_stride + (size_t)((j & rmask) * hdp); };
-    if (r == 0 && cact) {                         // the new K / V rows into their page (vector stores; pad columns: zeros)
         float kx[EPL], vx[EPL];
 #pragma unroll
         for (int i = 0; i < EPL; ++i) { kx[i] = sk[e0 + i]; vx[i] = sv[e0 + i]; }
@@ -337,7 +151,7 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStr
         sum += e;
     }
     sum = m2f_wave_sum(sum);
-    const float inv = 1.0f / sum;
+    const float inv = 1.0f / sum;                 // (sum >= 1: the row of the maximum contributes exp(0))
     __syncthreads();
 
     // ---- pass 2: P V ---------------------------------------------------------------------------------------------------------------
@@ -382,6 +196,15 @@ __global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStr
     }
 }
 
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
+    attn_stream_body<BF16, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0});
+}
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
+    attn_stream_body<BF16, true>(ab, pg);
+}
+
 // len[s] += active[s]: the one launch that closes a step
 __global__ void m2f_stream_advance_kernel(int* len, const uint8_t* active, int S) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -395,35 +218,10 @@ __global__ void m2f_stream_reset_kernel(int* len, const uint8_t* mask, int S) {
 
 }  // namespace
 
-size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16) {
-    const int hdp = bf16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
-    return (size_t)S * H * C * hdp;
-}
+size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16) { return (size_t)S * H * C * m2f_stream_hdp(hd, bf16 != 0); }
+size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16) { return (size_t)n_pages * H * R * m2f_stream_hdp(hd, bf16 != 0); }
 
-hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream) {
-    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || !ab.len || !ab.active)
-        return hipErrorInvalidValue;
-    int blocks = 0;
-    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
-    for (int i = 0; i < ab.count; ++i) {
-        AttnStreamProblem& p = ab.pr[i];
-        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
-        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
-        p.block_begin = blocks;
-        ab.bb[i] = blocks;
-        blocks += ab.S * p.H;
-    }
-    if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab);
-    else hipLaunchKernelGGL(m2f_attn_stream_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab);
-    return hipGetLastError();
-}
-
-size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16) {
-    const int hdp = bf16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
-    return (size_t)n_pages * H * R * hdp;
-}
-
-// What both paged launchers refuse before anything is launched; fills pg.lgR.
+// What every paged launcher refuses before anything is launched; fills pg.lgR.
 bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg) {
     if (pg.R != 16 && pg.R != 32 && pg.R != 64) return false;
     if (!pg.table || (reinterpret_cast<uintptr_t>(pg.table) & 3) || pg.n_pages < 1) return false;
@@ -432,21 +230,37 @@ bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg) 
     return true;
 }
 
-hipError_t m2f_launch_attn_stream_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, hipStream_t stream) {
-    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || !ab.len || !ab.active || !m2f_attn_stream_paging_ok(ab, pg))
-        return hipErrorInvalidValue;
-    int blocks = 0;
+// What the step and the chunk launcher refuse, dense or paged (pg: null for dense; a copy, lgR filled, goes to the kernel), and the
+// launch geometry: block_begin / bb[] of every problem.  -> workgroups, or -1; *maxW: the widest head dim padded to 16.
+int m2f_attn_stream_prepare(AttnStreamBatch& ab, AttnStreamPaging* pg, int* maxW) {
+    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || !ab.len) return -1;
+    if (pg && !m2f_attn_stream_paging_ok(ab, *pg)) return -1;
+    int blocks = 0, w = 0;
     for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
     for (int i = 0; i < ab.count; ++i) {
         AttnStreamProblem& p = ab.pr[i];
-        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
-        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
+        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return -1;
+        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return -1;
         p.block_begin = blocks;
         ab.bb[i] = blocks;
         blocks += ab.S * p.H;
+        w = w > ((p.hd + 15) & ~15) ? w : (p.hd + 15) & ~15;
     }
-    if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg);
-    else hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg);
+    if (maxW) *maxW = w;
+    return blocks;
+}
+
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream) {
+    AttnStreamPaging pg = paging ? *paging : AttnStreamPaging{nullptr, 0, 0, 0, 0};
+    const int blocks = ab.active ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, nullptr) : -1;
+    if (blocks < 0) return hipErrorInvalidValue;
+    if (paging) {
+        if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg);
+        else hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg);
+    } else {
+        if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab);
+        else hipLaunchKernelGGL(m2f_attn_stream_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab);
+    }
     return hipGetLastError();
 }
 

@@ -8,6 +8,12 @@
 //   * ring of C rows (a window of C - 1): the utterances u - (C - 1) .. u only; utterance j lives in cache row j % C.
 // Cache layout, padding and element types are attention_stream.hip's (cache[S][H][C][hdp], fp32 or bf16): a step and a chunk call
 // interleave on the same caches.
+// The caches may also be page pools (attention_stream.hip has both layouts): logical cache row j of the slot is then row j % R of page
+// table[s][j / R].  A 64-row block of cached rows starts at a multiple of 64 logical rows, so it is 64 / R whole pages; the staging
+// takes each row from its page, the ids coming from LDS, where the workgroup put the slot's table entries once (attn_stream_rows.h:
+// only the entries of pages that hold a live row or take a new one, e < ceil(min(len + n_new, C) / R)).  Dense and paged are ONE
+// kernel body (attn_stream_chunk_body<BF16, PAGED>); behind PAGED stand only that fetch, the base pointer of a head's rows and the
+// offset of a row, so the output and the rows stored are the same bits in both.
 //
 // One workgroup of 4 waves per (s, h), the shape and arithmetic of attention_dlong.hip's forward with one query block: wave w owns the
 // queries 16w .. 16w + 15, exact-fp32 MFMA v_mfma_f32_16x16x4_f32, S^T = K Q^T so that the probabilities come out in the layout that is
@@ -20,9 +26,8 @@
 // first utterance is dead to every query and is not read at all.  No atomics, one summation order: the same bits on every run.
 // len[] is NOT advanced here: every site of a prefill call reads the same counts, m2f_launch_stream_advance_n closes the call.
 #include "common.h"
-#include <algorithm>
-#include <type_traits>
 #include "ops.h"
+#include "attn_stream_rows.h"
 
 // (see attention.hip: no floating-point contraction, so every form of a formula rounds the same way)
 #pragma clang fp contract(off)
@@ -76,17 +81,28 @@ __device__ __forceinline__ void stage_new(float* __restrict__ lds, const float* 
 }
 
 // cache rows [r0, r0 + n) of one (slot, head) into a zero-padded [BLK x W] slab; the row `dead` (absolute; -1: none) is not read.
-// Rows are hdp elements wide and 16-byte aligned, their pad columns hold zeros.
-template <bool BF16>
-__device__ __forceinline__ void stage_cache(float* __restrict__ lds, const void* __restrict__ cache, int r0, int n, int dead, int hdp,
-                                            int W, int ld, int tid) {
+// Rows are hdp elements wide and 16-byte aligned, their pad columns hold zeros.  cache: the head's row 0 (dense) or its row 0 of page
+// 0 (paged: spg, lgR, page_stride say where a row is).  Loads are unconditional: a slot outside the block reads the block's first row.
+template <bool BF16, bool PAGED>
+__device__ __forceinline__ void stage_cache(float* __restrict__ lds, const void* __restrict__ cache, const int* __restrict__ spg, int lgR,
+                                            size_t page_stride, int r0, int n, int dead, int hdp, int W, int ld, int tid) {
     SlabGeom<NV> G;
     slab_geom(G, n, hdp, BLK, W, ld, tid);
-#pragma unroll
-    for (int u = 0; u < NV; ++u) G.ok[u] = G.ok[u] && (r0 + (G.goff_rc[u] >> 16)) != dead;
     SlabRegs<NV> R;
-    if (BF16) slab_issue16(R, G, static_cast<const uint16_t*>(cache) + (size_t)r0 * hdp, hdp);
-    else slab_issue(R, G, static_cast<const float*>(cache) + (size_t)r0 * hdp, hdp);
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int r = G.goff_rc[u] >> 16, c = G.goff_rc[u] & 0xFFFF;
+        G.ok[u] = G.ok[u] && (r0 + r) != dead;
+        size_t o;
+        if (PAGED) o = m2f_stream_row_off(spg, lgR, page_stride, G.ok[u] ? r0 + r : r0, hdp, G.ok[u] ? c : 0);
+        else o = (size_t)r0 * hdp + (size_t)(G.ok[u] ? (uint32_t)(r * hdp + c) : 0u);
+        if (BF16) {
+            const uint2 w = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(cache) + o);
+            R.w0[u] = w.x; R.w1[u] = w.y;
+        } else {
+            R.x[u] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(cache) + o);
+        }
+    }
     slab_commit(R, G, lds, BF16);
 }
 
@@ -117,11 +133,14 @@ struct Vis {
     __device__ __forceinline__ bool own(int i, int t) const { return t < n_new && t <= i && (!ring || t >= i - (C - 1)); }
 };
 
-template <bool BF16>
-__global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnStreamBatch ab, const int T, const int* __restrict__ new_count) {
+template <bool BF16, bool PAGED>
+__device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const int T,
+                                                       const int* __restrict__ new_count) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    typedef typename std::conditional<BF16, uint16_t, float>::type elem_t;
-    constexpr int EPL = BF16 ? 8 : 4;                       // elements of a 16-byte access
+    __shared__ int spg[32];                                 // paged: the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
+    typedef Row<BF16> R;
+    typedef typename R::elem_t elem_t;
+    constexpr int EPL = R::EPL;                             // elements of a 16-byte access
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
     int pi = 0;
 #pragma unroll
@@ -131,7 +150,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     const int local = (int)blockIdx.x - ab.bb[pi];
     const int s = local / P.H, h = local - s * P.H;
     const int hd = P.hd, C = ab.C, W = (hd + 15) & ~15, ld = W + 2, CT = W >> 4;
-    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
+    const int hdp = m2f_stream_hdp(hd, BF16);
     const size_t row0 = (size_t)s * T;                      // the slot's first row of q / k / v / out
     uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
 
@@ -149,6 +168,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     }
     if (!live) return;                                      // cache and len untouched
 
+    const int lgR = PAGED ? pg.lgR : 0;
+    if (PAGED) m2f_stream_page_ids(spg, pg, s, n_old < C - n_new ? n_old + n_new : C, tid);      // rows: min(n_old + n_new, C) without overflow
     float* Qs = sm;
     float* Ks = Qs + BLK * ld;                              // the chunk's own K / V: resident (what the cache will hold)
     float* Vs = Ks + BLK * ld;
@@ -157,8 +178,11 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     stage_new<BF16>(Ks, P.k + row0 * P.ldk + (size_t)h * hd, P.ldk, n_new, hd, W, ld, tid);
     stage_new<BF16>(Vs, P.v + row0 * P.ldv + (size_t)h * hd, P.ldv, n_new, hd, W, ld, tid);
 
-    elem_t* kc = static_cast<elem_t*>(P.kcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
-    elem_t* vc = static_cast<elem_t*>(P.vcache) + ((size_t)s * P.H + h) * (size_t)C * hdp;
+    // row 0 of the head: of the slot's cache (dense) or of page 0 (paged), and from there to logical row j
+    const size_t page_stride = (size_t)P.H * (size_t)(hdp << lgR);           // paged: elements of one page, all heads
+    const size_t head0 = PAGED ? (size_t)h * (size_t)(hdp << lgR) : ((size_t)s * P.H + h) * (size_t)C * hdp;
+    elem_t* kc = static_cast<elem_t*>(P.kcache) + head0;
+    elem_t* vc = static_cast<elem_t*>(P.vcache) + head0;
     const int nlive = min(n_old, C);                        // cache rows that hold a live utterance (ring: the last C)
     Vis vis;
     vis.ring = ab.ring; vis.C = C; vis.nlive = nlive; vis.p0 = ab.ring ? (n_old - nlive) % C : 0; vis.n_new = n_new;
@@ -171,7 +195,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     const float* qrow = Qs + i * ld + lg;
     const float* kv_rows = KV + l15 * ld + lg;
     const float* own_rows = Ks + l15 * ld + lg;
-    __syncthreads();                                        // Q and the chunk's K / V committed
+    __syncthreads();                                        // Q, the chunk's K / V and the page ids committed
 
     // ---- pass 1: row max and normaliser -----------------------------------------------------------------------------------------
     float m_run = -INFINITY, l_run = 0.f;
@@ -196,7 +220,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     };
     for (int kb = 0; kb < nlive; kb += BLK) {
         __syncthreads();                                    // previous block consumed
-        stage_cache<BF16>(KV, kc, kb, min(BLK, nlive - kb), dead, hdp, W, ld, tid);
+        stage_cache<BF16, PAGED>(KV, kc, spg, lgR, page_stride, kb, min(BLK, nlive - kb), dead, hdp, W, ld, tid);
         __syncthreads();
         if (wave_on) {
             float x[4][4];
@@ -240,7 +264,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     for (int kb = 0; kb < nlive; kb += BLK) {
         const int nk = min(BLK, nlive - kb);
         __syncthreads();
-        stage_cache<BF16>(KV, kc, kb, nk, dead, hdp, W, ld, tid);
+        stage_cache<BF16, PAGED>(KV, kc, spg, lgR, page_stride, kb, nk, dead, hdp, W, ld, tid);
         __syncthreads();
         float p[4][4];
         if (wave_on) {
@@ -255,7 +279,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
             }
         }
         __syncthreads();                                    // K consumed
-        stage_cache<BF16>(KV, vc, kb, nk, dead, hdp, W, ld, tid);
+        stage_cache<BF16, PAGED>(KV, vc, spg, lgR, page_stride, kb, nk, dead, hdp, W, ld, tid);
         __syncthreads();
         if (wave_on) pv(p, KV);
     }
@@ -294,258 +318,23 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnS
     for (int e = tid; e < nst * nch; e += NTHR) {
         const int tr = e / nch, c = (e - tr * nch) * EPL, t = t0 + tr;
         const int pos = ab.ring ? (int)(((unsigned)n_old + (unsigned)t) % (unsigned)C) : n_old + t;
-        const float* kr = Ks + t * ld + c;
-        const float* vr = Vs + t * ld + c;
-        if constexpr (BF16) {
-            u32x4 a, b;
+        const size_t o = PAGED ? m2f_stream_row_off(spg, lgR, page_stride, pos, hdp, c) : (size_t)pos * hdp + c;
+        float kx[EPL], vx[EPL];                             // (already bf16 values in bf16 mode)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a[q] = (uint32_t)m2f_bf16_bits(kr[2 * q]) | ((uint32_t)m2f_bf16_bits(kr[2 * q + 1]) << 16);       // (kr: already bf16 values)
-                b[q] = (uint32_t)m2f_bf16_bits(vr[2 * q]) | ((uint32_t)m2f_bf16_bits(vr[2 * q + 1]) << 16);
-            }
-            *reinterpret_cast<u32x4*>(kc + (size_t)pos * hdp + c) = a;
-            *reinterpret_cast<u32x4*>(vc + (size_t)pos * hdp + c) = b;
-        } else {
-            *reinterpret_cast<f32x4*>(kc + (size_t)pos * hdp + c) = (f32x4){kr[0], kr[1], kr[2], kr[3]};
-            *reinterpret_cast<f32x4*>(vc + (size_t)pos * hdp + c) = (f32x4){vr[0], vr[1], vr[2], vr[3]};
-        }
+        for (int q = 0; q < EPL; ++q) { kx[q] = Ks[t * ld + c + q]; vx[q] = Vs[t * ld + c + q]; }
+        R::store(kc + o, kx);
+        R::store(vc + o, vx);
     }
 }
 
-// PAGED FORM (attention_stream.hip has the pool layout): logical cache row j of the slot is row j % R of page table[s][j / R].  A 64-row
-// block of cached rows starts at a multiple of 64 logical rows, so it is 64 / R whole pages: the staging below takes each row from its
-// page, the ids coming from LDS, where the workgroup put the slot's table entries once (lane e loads entry e; only the entries of pages
-// that hold a live row or take a new one: e < ceil(min(len + n_new, C) / R); ids clamped to the pool).  Everything else - the dead row
-// of a ring, the last C of more than C new rows, the chunk's own keys from LDS, the stores behind the last cache read - is the dense
-// kernel's statement for statement, so the output and the rows stored are its bits.
 template <bool BF16>
-__device__ __forceinline__ void stage_cache_paged(float* __restrict__ lds, const void* __restrict__ pool, const int* __restrict__ spg, int lgR,
-                                                  size_t page_stride, size_t head_off, int r0, int n, int dead, int hdp, int W, int ld, int tid) {
-    SlabGeom<NV> G;
-    slab_geom(G, n, hdp, BLK, W, ld, tid);
-    SlabRegs<NV> R;
-    const int rmask = (1 << lgR) - 1;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int r = r0 + (G.goff_rc[u] >> 16), c = G.goff_rc[u] & 0xFFFF;
-        G.ok[u] = G.ok[u] && r != dead;
-        const int j = G.ok[u] ? r : r0, cc = G.ok[u] ? c : 0;                  // (unconditional loads: a slot outside the block reads its first row)
-        const size_t o = (size_t)spg[j >> lgR] * page_stride + head_off + (size_t)((j & rmask) * hdp + cc);
-        if (BF16) {
-            const uint2 w = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(pool) + o);
-            R.w0[u] = w.x; R.w1[u] = w.y;
-        } else {
-            R.x[u] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(pool) + o);
-        }
-    }
-    slab_commit(R, G, lds, BF16);
+__global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnStreamBatch ab, const int T, const int* __restrict__ new_count) {
+    attn_stream_chunk_body<BF16, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, T, new_count);
 }
-
 template <bool BF16>
 __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const int T,
                                                                            const int* __restrict__ new_count) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ int spg[32];                                 // the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
-    typedef typename std::conditional<BF16, uint16_t, float>::type elem_t;
-    constexpr int EPL = BF16 ? 8 : 4;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < M2F_ATTN_MAX_PROBLEMS; ++i)
-        if ((int)blockIdx.x >= ab.bb[i]) pi = i;
-    const AttnStreamProblem& P = ab.pr[pi];
-    const int local = (int)blockIdx.x - ab.bb[pi];
-    const int s = local / P.H, h = local - s * P.H;
-    const int hd = P.hd, C = ab.C, W = (hd + 15) & ~15, ld = W + 2, CT = W >> 4;
-    const int hdp = BF16 ? (hd + 7) & ~7 : (hd + 3) & ~3;
-    const size_t row0 = (size_t)s * T;
-    uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
-
-    const int n_old = ab.len[s];
-    const int n_new = min(new_count[s], T);
-    const bool live = n_new > 0 && n_old >= 0 && (ab.ring || (n_old <= C && n_new <= C - n_old));
-    {   // rows that take nothing: zero output rows
-        const int first = live ? n_new : 0;
-        for (int e = tid; e < (T - first) * hd; e += NTHR) {
-            const int t = e / hd, c = e - t * hd;
-            const size_t idx = (row0 + first + t) * P.ldo + (size_t)h * hd + c;
-            P.out[idx] = 0.f;
-            if (out16) out16[idx] = 0;
-        }
-    }
-    if (!live) return;                                      // pools and len untouched
-
-    const int lgR = pg.lgR, rmask = (1 << lgR) - 1;
-    if (tid < 32) {                                         // the page ids -> LDS (one 4-byte load per page that may be touched)
-        const int rows = n_old < C - n_new ? n_old + n_new : C;               // min(n_old + n_new, C) without overflow
-        int id = 0;
-        if (tid < ((rows + rmask) >> lgR)) id = pg.table[(size_t)s * pg.tw + tid];
-        spg[tid] = min(max(id, 0), pg.n_pages - 1);
-    }
-
-    float* Qs = sm;
-    float* Ks = Qs + BLK * ld;
-    float* Vs = Ks + BLK * ld;
-    float* KV = Vs + BLK * ld;
-    stage_new<BF16>(Qs, P.q + row0 * P.ldq + (size_t)h * hd, P.ldq, n_new, hd, W, ld, tid);
-    stage_new<BF16>(Ks, P.k + row0 * P.ldk + (size_t)h * hd, P.ldk, n_new, hd, W, ld, tid);
-    stage_new<BF16>(Vs, P.v + row0 * P.ldv + (size_t)h * hd, P.ldv, n_new, hd, W, ld, tid);
-
-    const size_t head_off = (size_t)h * (size_t)(hdp << lgR), page_stride = (size_t)P.H * (size_t)(hdp << lgR);
-    elem_t* kc = static_cast<elem_t*>(P.kcache);
-    elem_t* vc = static_cast<elem_t*>(P.vcache);
-    const int nlive = min(n_old, C);
-    Vis vis;
-    vis.ring = ab.ring; vis.C = C; vis.nlive = nlive; vis.p0 = ab.ring ? (n_old - nlive) % C : 0; vis.n_new = n_new;
-    const int dead = (ab.ring && nlive == C) ? vis.p0 : -1;
-
-    const float scale = 1.0f / sqrtf((float)hd);
-    const int ksteps = (hd + 3) >> 2;
-    const int i = 16 * wv + l15;
-    const bool wave_on = 16 * wv < n_new;
-    const float* qrow = Qs + i * ld + lg;
-    const float* kv_rows = KV + l15 * ld + lg;
-    const float* own_rows = Ks + l15 * ld + lg;
-    __syncthreads();                                        // Q, the chunk's K / V and the page ids committed
-
-    // ---- pass 1: row max and normaliser -----------------------------------------------------------------------------------------
-    float m_run = -INFINITY, l_run = 0.f;
-    auto stats = [&](const float (&x)[4][4]) {
-        float m_blk = -INFINITY;
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m_blk = fmaxf(m_blk, x[jt][r]);
-        m_blk = fmaxf(m_blk, __shfl_xor(m_blk, 16, 64));
-        m_blk = fmaxf(m_blk, __shfl_xor(m_blk, 32, 64));
-        const float m_new = fmaxf(m_run, m_blk);
-        float sum = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sum += (m_new == -INFINITY) ? 0.f : __expf(x[jt][r] - m_new);
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        l_run = l_run * ((m_new == -INFINITY) ? 1.f : __expf(m_run - m_new)) + sum;
-        m_run = m_new;
-    };
-    for (int kb = 0; kb < nlive; kb += BLK) {
-        __syncthreads();
-        stage_cache_paged<BF16>(KV, kc, spg, lgR, page_stride, head_off, kb, min(BLK, nlive - kb), dead, hdp, W, ld, tid);
-        __syncthreads();
-        if (wave_on) {
-            float x[4][4];
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) {
-                const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[jt][r] = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
-            }
-            stats(x);
-        }
-    }
-    if (wave_on) {
-        float x[4][4];
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-            const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[jt][r] = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
-        }
-        stats(x);
-    }
-
-    // ---- pass 2: P = exp(S - m) / l, O += P V ------------------------------------------------------------------------------------------
-    const float inv = (i < n_new && l_run > 0.f) ? 1.0f / l_run : 0.f;
-    f32x4 o[8];
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) o[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto pv = [&](const float (&p)[4][4], const float* vslab) {
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct) {
-            if (ct >= CT) continue;
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) {
-                const float* vp = vslab + (16 * jt + 4 * lg) * ld + 16 * ct + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[ct] = mfma4(p[jt][r], vp[r * ld], o[ct]);
-            }
-        }
-    };
-    for (int kb = 0; kb < nlive; kb += BLK) {
-        const int nk = min(BLK, nlive - kb);
-        __syncthreads();
-        stage_cache_paged<BF16>(KV, kc, spg, lgR, page_stride, head_off, kb, nk, dead, hdp, W, ld, tid);
-        __syncthreads();
-        float p[4][4];
-        if (wave_on) {
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) {
-                const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
-                    p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;
-                }
-            }
-        }
-        __syncthreads();                                    // K consumed
-        stage_cache_paged<BF16>(KV, vc, spg, lgR, page_stride, head_off, kb, nk, dead, hdp, W, ld, tid);
-        __syncthreads();
-        if (wave_on) pv(p, KV);
-    }
-    if (wave_on) {
-        float p[4][4];
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-            const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float x = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
-                p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;
-            }
-        }
-        pv(p, Vs);
-#pragma unroll
-        for (int ct = 0; ct < 8; ++ct) {
-            if (ct >= CT) continue;
-            const int c = 16 * ct + l15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 16 * wv + 4 * lg + r;
-                if (t < n_new && c < hd) {
-                    const size_t idx = (row0 + t) * P.ldo + (size_t)h * hd + c;
-                    P.out[idx] = o[ct][r];
-                    if (out16) out16[idx] = m2f_bf16_bits(o[ct][r]);
-                }
-            }
-        }
-    }
-
-    // ---- the new K / V rows into their pages: behind the workgroup's last cache read ------------------------------------------------
-    __syncthreads();
-    const int nst = min(n_new, C), t0 = n_new - nst;
-    const int nch = hdp / EPL;
-    for (int e = tid; e < nst * nch; e += NTHR) {
-        const int tr = e / nch, c = (e - tr * nch) * EPL, t = t0 + tr;
-        const int pos = ab.ring ? (int)(((unsigned)n_old + (unsigned)t) % (unsigned)C) : n_old + t;
-        const size_t po = (size_t)spg[pos >> lgR] * page_stride + head_off + (size_t)((pos & rmask) * hdp + c);
-        const float* kr = Ks + t * ld + c;
-        const float* vr = Vs + t * ld + c;
-        if constexpr (BF16) {
-            u32x4 a, b;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a[q] = (uint32_t)m2f_bf16_bits(kr[2 * q]) | ((uint32_t)m2f_bf16_bits(kr[2 * q + 1]) << 16);
-                b[q] = (uint32_t)m2f_bf16_bits(vr[2 * q]) | ((uint32_t)m2f_bf16_bits(vr[2 * q + 1]) << 16);
-            }
-            *reinterpret_cast<u32x4*>(kc + po) = a;
-            *reinterpret_cast<u32x4*>(vc + po) = b;
-        } else {
-            *reinterpret_cast<f32x4*>(kc + po) = (f32x4){kr[0], kr[1], kr[2], kr[3]};
-            *reinterpret_cast<f32x4*>(vc + po) = (f32x4){vr[0], vr[1], vr[2], vr[3]};
-        }
-    }
+    attn_stream_chunk_body<BF16, true>(ab, pg, T, new_count);
 }
 
 // len[s] += min(max(n_new[s], 0), T): the one launch that closes a prefill call
@@ -557,68 +346,29 @@ __global__ void m2f_stream_advance_n_kernel(int* len, const int* n_new, int S, i
     }
 }
 
-template <typename K>
-hipError_t go(K kern, int blocks, size_t lds, hipStream_t stream, const AttnStreamBatch& ab, int T, const int* n_new) {
+template <typename K, typename... Args>
+hipError_t go(K kern, int blocks, size_t lds, hipStream_t stream, const Args&... args) {
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, ab, T, n_new);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, args...);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, int T, const int* n_new, hipStream_t stream) {
-    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || ab.C < 1 || ab.C > M2F_ATTN_STREAM_MAX_C || !ab.len || !n_new ||
-        T < 1 || T > M2F_ATTN_STREAM_MAX_CHUNK)
-        return hipErrorInvalidValue;
-    int blocks = 0, maxW = 0;
-    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
-    for (int i = 0; i < ab.count; ++i) {
-        AttnStreamProblem& p = ab.pr[i];
-        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
-        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
-        p.block_begin = blocks;
-        ab.bb[i] = blocks;
-        blocks += ab.S * p.H;
-        maxW = std::max(maxW, (p.hd + 15) & ~15);
-    }
+hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPaging* paging, int T, const int* n_new, hipStream_t stream) {
+    AttnStreamPaging pg = paging ? *paging : AttnStreamPaging{nullptr, 0, 0, 0, 0};
+    int maxW = 0;
+    const int blocks = n_new && T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, &maxW) : -1;
+    if (blocks < 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
+    if (paging)
+        return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true>, blocks, lds, stream, ab, pg, T, n_new)
+                       : go(m2f_attn_stream_chunk_paged_kernel<false>, blocks, lds, stream, ab, pg, T, n_new);
     return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true>, blocks, lds, stream, ab, T, n_new)
                    : go(m2f_attn_stream_chunk_kernel<false>, blocks, lds, stream, ab, T, n_new);
-}
-
-namespace {
-template <typename K>
-hipError_t go_paged(K kern, int blocks, size_t lds, hipStream_t stream, const AttnStreamBatch& ab, const AttnStreamPaging& pg, int T, const int* n_new) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, ab, pg, T, n_new);
-    return hipGetLastError();
-}
-}  // namespace
-
-hipError_t m2f_launch_attn_stream_chunk_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, int T, const int* n_new, hipStream_t stream) {
-    if (ab.count < 1 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.S < 1 || !ab.len || !n_new || T < 1 || T > M2F_ATTN_STREAM_MAX_CHUNK ||
-        !m2f_attn_stream_paging_ok(ab, pg))
-        return hipErrorInvalidValue;
-    int blocks = 0, maxW = 0;
-    for (int i = 0; i < M2F_ATTN_MAX_PROBLEMS; ++i) ab.bb[i] = 0x7fffffff;
-    for (int i = 0; i < ab.count; ++i) {
-        AttnStreamProblem& p = ab.pr[i];
-        if (p.H < 1 || p.hd < 1 || p.hd > 128 || !p.q || !p.k || !p.v || !p.out || !p.kcache || !p.vcache) return hipErrorInvalidValue;
-        if ((reinterpret_cast<uintptr_t>(p.kcache) & 15) || (reinterpret_cast<uintptr_t>(p.vcache) & 15)) return hipErrorInvalidValue;
-        p.block_begin = blocks;
-        ab.bb[i] = blocks;
-        blocks += ab.S * p.H;
-        maxW = std::max(maxW, (p.hd + 15) & ~15);
-    }
-    const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
-    return ab.bf16 ? go_paged(m2f_attn_stream_chunk_paged_kernel<true>, blocks, lds, stream, ab, pg, T, n_new)
-                   : go_paged(m2f_attn_stream_chunk_paged_kernel<false>, blocks, lds, stream, ab, pg, T, n_new);
 }
 
 hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream) {

@@ -265,7 +265,6 @@ struct AttnStreamBatch {
     ShadowMap sh;              // out also written as bf16
 };
 size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16);     // elements (fp32 or bf16) of ONE cache (K or V) of a site
-hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, hipStream_t stream);
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream);      // len[s] += active[s]
 hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStream_t stream);          // len[s] = 0 where mask[s] (null: all)
 // Chunk form (attention_stream_chunk.hip): slot s takes n_new[s] (0 .. T, T <= 64; device int32 [S]) new utterances - rows s*T + t of
@@ -273,22 +272,25 @@ hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStre
 // n_new == 0, or a plain cache that the chunk would overfill (len + n_new > C), gets zero output rows and keeps its cache; output rows
 // t >= n_new[s] are zeros, their input rows are never read.  len is not advanced: m2f_launch_stream_advance_n adds the clamped n_new.
 #define M2F_ATTN_STREAM_MAX_CHUNK 64
-hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, int T, const int* n_new, hipStream_t stream);
 hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream);   // len[s] += min(max(n_new[s], 0), T)
-// Paged forms: kcache / vcache of a problem are the site's page POOLS, [n_pages][H][R][pad(hd)] (rows padded and aligned as the dense
-// caches'), and logical cache row j of slot s - the row the dense kernels call j - is row j % R of page table[s][j / R].  The dense
-// kernels, their batch struct and their launches are untouched; the paging travels as a kernel argument of its own.  Only the table
-// entries of pages that hold a live row or take a new one are read; ids are clamped to the pool.
+// Paged addressing: kcache / vcache of a problem are the site's page POOLS, [n_pages][H][R][pad(hd)] (rows padded and aligned as the
+// dense caches'), and logical cache row j of slot s - the row the dense addressing calls j - is row j % R of page table[s][j / R].
+// Each streaming kernel is ONE body with two addressings (a template flag): a launch without a paging runs it over per-slot caches,
+// a launch with one over pools, and the two give the same bits.  The paging travels as a kernel argument of its own, beside the
+// batch.  Only the table entries of pages that hold a live row or take a new one are read; ids are clamped to the pool.
 struct AttnStreamPaging {
     const int* table;          // device int32 [S][tw]
     int tw;                    // entries per slot: ceil(C / R)
-    int R, lgR;                // rows per page, 16 / 32 / 64 (lgR: filled by the launcher)
+    int R, lgR;                // rows per page, 16 / 32 / 64 (lgR: filled by the launcher, in its own copy)
     int n_pages;               // pages of every pool
 };
 size_t m2f_attn_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16);        // elements (fp32 or bf16) of ONE pool (K or V) of a site
 bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg);       // R, table, tw against ab.C; fills lgR
-hipError_t m2f_launch_attn_stream_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, hipStream_t stream);
-hipError_t m2f_launch_attn_stream_chunk_paged(AttnStreamBatch& ab, AttnStreamPaging& pg, int T, const int* n_new, hipStream_t stream);
+// The launches; paging == nullptr: dense caches.  Both refuse (hipErrorInvalidValue, nothing launched) what m2f_attn_stream_prepare
+// refuses - a bad count, S, C > 512, hd > 128, a null or misaligned cache / pool, a paging that is not ok - and fill block_begin / bb[].
+int m2f_attn_stream_prepare(AttnStreamBatch& ab, AttnStreamPaging* pg, int* maxW);     // -> workgroups or -1; maxW: widest pad16(hd)
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream);
+hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPaging* paging, int T, const int* n_new, hipStream_t stream);
 // Snapshot / restore of those caches (stream_cache.hip has the packed layout): entry e of n_entries = the min(lengths[e], C) live
 // physical rows of slot slots[e], every listed site, K then V, packed at row row_offsets[e].  One launch for all sites and entries
 // (slices of 65,535 entries); the kernels move 16-byte vectors, so a site is described by `vpr` = vectors per padded row and the

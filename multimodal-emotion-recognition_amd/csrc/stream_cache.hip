@@ -21,6 +21,7 @@
 // packed buffer) is skipped whole: device-side arrays can never send an access outside the buffers the launch was given.
 #include "common.h"
 #include "ops.h"
+#include "attn_stream_rows.h"
 
 namespace {
 
@@ -51,14 +52,9 @@ __global__ __launch_bounds__(256) void m2f_stream_cache_kernel(const StreamCache
     int runv = 0;                                 // paged: vectors of one page's rows of one head
     size_t page_stride = 0;
     if (PAGED) {
-        const int lgR = pg.lgR, rmask = (1 << lgR) - 1;
-        if (tid < 32) {                           // the page ids -> LDS (one 4-byte load per page that holds a row of the entry)
-            int id = 0;
-            if (tid < ((rows + rmask) >> lgR)) id = pg.table[(size_t)slot * pg.tw + tid];
-            spg[tid] = min(max(id, 0), pg.n_pages - 1);
-        }
+        m2f_stream_page_ids(spg, pg, slot, rows, tid);          // (one 4-byte load per page that holds a row of the entry)
         __syncthreads();
-        runv = vpr << lgR;
+        runv = vpr << pg.lgR;
         page_stride = (size_t)H * (size_t)runv;
         cache += (size_t)h * (size_t)runv;        // this head's rows of page 0
     } else {
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(256) void m2f_stream_cache_kernel(const StreamCache
 }  // namespace
 
 int m2f_stream_cache_row_vecs(int hd, int bf16) {
-    return bf16 ? ((hd + 7) & ~7) / 8 : ((hd + 3) & ~3) / 4;
+    return m2f_stream_hdp(hd, bf16 != 0) / (bf16 ? 8 : 4);
 }
 
 // cb.site[i].colv and cb.rowv are the caller's (a launch may serve a slice of a longer site list); sb, e0 are filled here.
