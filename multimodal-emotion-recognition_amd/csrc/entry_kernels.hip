@@ -1,0 +1,597 @@
+// Entry points of the C ABI (include/m2fnet_hip.h) that never touch a plan: the gather, RNG and optimizer steps, and the kernel-level
+// test and encoder entry points (m2f_gemm, m2f_attention_*, m2f_layernorm_*, m2f_w2v_*, m2f_mel_*) with their thread-local shadow map.
+#include "plan.h"
+
+using namespace m2f;
+
+extern "C" {
+
+int m2f_gather_dialogues(const float* text_table, int d_text, const float* audio_table, int d_audio,
+                         const int64_t* label_table, const int32_t* rows, int T, float* text_out, int ld_text,
+                         float* audio_out, int ld_audio, uint8_t* key_pad_out, int64_t* labels_out, m2f_stream_t stream) {
+    GatherArgs a;
+    a.text_table = text_table; a.audio_table = audio_table; a.label_table = label_table; a.rows = rows;
+    a.T = T; a.d_text = d_text; a.d_audio = d_audio; a.ld_text = ld_text; a.ld_audio = ld_audio;
+    a.text_out = text_out; a.audio_out = audio_out; a.key_pad = key_pad_out; a.labels = labels_out;
+    M2F_HIP(m2f_launch_gather(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_rng_advance(uint32_t* rng_state, m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_rng_advance(rng_state, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr, m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_adam(params, grads, 0, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_ptr,
+                            nullptr, 0.f, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_adam_step_g16(float* params, const uint16_t* grads_bf16, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
+                      m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_adam(params, grads_bf16, 1, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_ptr,
+                            nullptr, 0.f, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int step, float ema_w, const float* grad_scale_ptr, m2f_stream_t stream) {
+    if (ema_args_bad("m2f_adam_step_ema", ema, ema_w)) return 1;
+    M2F_HIP(m2f_launch_adam(params, grads, 0, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_ptr, ema, ema_w,
+                            static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_adam_step_g16_ema(float* params, const uint16_t* grads_bf16, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int step, float ema_w, const float* grad_scale_ptr,
+                          m2f_stream_t stream) {
+    if (ema_args_bad("m2f_adam_step_g16_ema", ema, ema_w)) return 1;
+    M2F_HIP(m2f_launch_adam(params, grads_bf16, 1, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_ptr,
+                            ema, ema_w, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- kernel-level entry points -----------------------------------------------------------------------
+// Optional bf16 shadow map for the kernel-level entry points (the plans carry their own): outputs that lie inside
+// [ws_base, ws_base + floats) are also written as bf16 at the same element index of `shadow`.
+static thread_local ShadowMap g_sh = {nullptr, nullptr, 0};
+int m2f_set_shadow_map(const float* ws_base, uint16_t* shadow, int64_t floats) {
+    if ((ws_base == nullptr) != (shadow == nullptr) || floats < 0) return fail("m2f_set_shadow_map: base / shadow must both be set or both be NULL");
+    g_sh = {ws_base, shadow, (size_t)floats};
+    return 0;
+}
+
+static thread_local int g_shadow_only = 0;
+int m2f_set_shadow_only(int on) { g_shadow_only = on != 0; return 0; }
+
+static void drop_params(float p, uint32_t* thresh, float* scale) {
+    *thresh = (uint32_t)std::min(4294967295.0, std::floor((double)p * 4294967296.0));
+    *scale = 1.0f / (1.0f - p);
+}
+
+int m2f_gemm(int precision, int layout, int M, int N, int K0, int K1, const float* a0, int lda0, const float* a1, int lda1,
+             const float* b0, int ldb0, const float* b1, int ldb1, float* c, int ldc, const float* bias, const float* res,
+             int ldres, const float* gate, int ldgate, float gate_scale, float* bias_grad, int relu_a, int relu_b,
+             int relu_out, int accumulate, uint32_t drop_site, float drop_p, const uint32_t* rng_state, int tile,
+             float* splitk_ws, uint32_t* splitk_tickets, int splitk_max_tiles,
+             const uint16_t* a0q, int ldaq0, const uint16_t* a1q, int ldaq1,
+             const uint16_t* b0q, int ldbq0, const uint16_t* b1q, int ldbq1, m2f_stream_t stream) {
+    GemmBatch gb;
+    memset(&gb, 0, sizeof(gb));
+    GemmProblem p = gp_make(a0, lda0, b0, ldb0, M, N, K0, c, ldc);
+    if (K1 > 0) gp_seg2(p, a1, lda1, b1, ldb1, K1);
+    p.bias = bias; p.res = res; p.ldres = ldres; p.gate = gate; p.ldgate = ldgate; p.gate_scale = gate_scale;
+    p.bias_grad = bias_grad; p.drop_site = drop_site;
+    p.flags = (relu_a ? GF_RELU_A : 0) | (relu_b ? GF_RELU_B : 0) | (relu_out == 1 ? GF_RELU_OUT : 0) |
+              (relu_out == 2 ? GF_GELU_OUT : 0) | (accumulate ? GF_ACCUM : 0) | (g_shadow_only && !accumulate ? GF_NO_F32 : 0);
+    p.a.q[0] = a0q; p.a.ldq[0] = ldaq0; p.a.q[1] = a1q; p.a.ldq[1] = ldaq1;
+    p.b.q[0] = b0q; p.b.ldq[0] = ldbq0; p.b.q[1] = b1q; p.b.ldq[1] = ldbq1;
+    p.a.qt[0] = p.a.qt[1] = p.b.qt[0] = p.b.qt[1] = nullptr;
+    gb.pr[0] = p; gb.count = 1; gb.rng = rng_state; gb.sh = g_sh;
+    gb.splitk_ws = splitk_ws; gb.splitk_cnt = splitk_tickets; gb.splitk_max_tiles = splitk_ws && splitk_tickets ? splitk_max_tiles : 0;
+    if (drop_site) drop_params(drop_p, &gb.drop_thresh, &gb.drop_scale);
+    M2F_HIP(m2f_launch_gemm(gb, precision, layout, tile, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_quantize_fp8(const float* src, uint8_t* dst, int64_t n, float scale, m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_quant_fp8(src, dst, n, scale, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_gemm_fp8(int M, int N, int K, const uint8_t* a8, int lda, const uint8_t* b8, int ldb, float acc_scale, float* c, int ldc,
+                 const float* bias, const float* res, int ldres, int activation, uint8_t* c8, float c8_scale,
+                 m2f_stream_t stream) {
+    GemmBatch gb;
+    memset(&gb, 0, sizeof(gb));
+    GemmProblem p;
+    memset(&p, 0, sizeof(p));
+    p.a.q[0] = reinterpret_cast<const uint16_t*>(a8); p.a.ldq[0] = lda; p.a.k[0] = K;
+    p.b.q[0] = reinterpret_cast<const uint16_t*>(b8); p.b.ldq[0] = ldb; p.b.k[0] = K;
+    p.M = M; p.N = N; p.c = c; p.ldc = ldc; p.bias = bias; p.res = res; p.ldres = ldres;
+    p.gate_scale = 1.f; p.acc_scale = acc_scale; p.c8 = c8; p.c8_scale = c8_scale;
+    if (!c && !c8) return fail("m2f_gemm_fp8: no output buffer");
+    p.flags = (activation == 1 ? GF_RELU_OUT : 0) | (activation == 2 ? GF_GELU_OUT : 0) | (g_shadow_only && c && !c8 ? GF_NO_F32 : 0);
+    gb.pr[0] = p; gb.count = 1; gb.sh = g_sh;
+    M2F_HIP(m2f_launch_gemm_fp8(gb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static void attn_fill(AttnBatch& ab, int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                      const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                      float drop_p, const uint32_t* rng_state) {
+    memset(&ab, 0, sizeof(ab));
+    AttnProblem& p = ab.pr[0];
+    p.q = q; p.k = k; p.v = v; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.out = out; p.ldo = ldo; p.probs = probs;
+    p.H = H; p.hd = hd; p.drop_site = drop_site;
+    ab.count = 1; ab.B = B; ab.L = L; ab.key_pad = key_pad; ab.rng = rng_state;
+    ab.drop_scale = 1.f;
+    ab.sh = g_sh;                                              // (m2f_set_shadow_map: operands / results inside that range have bf16 copies)
+    {   // kernel-level tests of the bf16-mode forms: M2F_ATTN_BF16_KERNEL=<mask> (AttnBatch::bf16_math), read per call
+        const char* e = getenv("M2F_ATTN_BF16_KERNEL");
+        ab.bf16_math = e ? atoi(e) & 63 : 0;
+    }
+    if (drop_site) drop_params(drop_p, &ab.drop_thresh, &ab.drop_scale);
+}
+
+int m2f_attention_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                           const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
+                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+    AttnBatch ab;
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
+    m2f_attn_set_band(ab, past, future);
+    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                      const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
+                      const uint32_t* rng_state, m2f_stream_t stream) {
+    return m2f_attention_fwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state, stream, -1, -1);
+}
+
+int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                      const uint8_t* key_pad, const float* out, int ldo, const float* probs, const float* dout, int lddo,
+                      float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
+                      const uint32_t* rng_state, m2f_stream_t stream) {
+    return m2f_attention_bwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, dout, lddo, dq, lddq, dk, lddk, dv, lddv,
+                                  drop_site, drop_p, rng_state, stream, -1, -1);
+}
+int m2f_attention_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                           const uint8_t* key_pad, const float* out, int ldo, const float* probs, const float* dout, int lddo,
+                           float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
+                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+    AttnBatch ab;
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, const_cast<float*>(out), ldo, const_cast<float*>(probs),
+              drop_site, drop_p, rng_state);
+    AttnProblem& p = ab.pr[0];
+    p.dout = dout; p.lddo = lddo; p.dq = dq; p.dk = dk; p.dv = dv; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+    m2f_attn_set_band(ab, past, future);               // (the saved P^T carries the band: the short kernel does not read it)
+    M2F_HIP(m2f_launch_attn_bwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static int attn_varlen_fill(AttnBatch& ab, int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                            const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs,
+                            uint32_t drop_site, float drop_p, const uint32_t* rng_state) {
+    if (B < 1 || L < 1 || L > M2F_ATTN_DLONG_MAX_L) return fail("m2f_attention_varlen: 1 <= L <= 512 required (got L = " + std::to_string(L) + ")");
+    if (!cu == !key_pad) return fail("m2f_attention_varlen: exactly one of cu (packed rows) and key_pad (padded rows) must be given");
+    if (cu && T < 1) return fail("m2f_attention_varlen: packed rows need T >= 1");
+    if (!m2f_attn_dlong_index_ok(B, H, L)) return fail("m2f_attention_varlen: B * H * L * L must stay below 2^32");
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
+    ab.bf16_math = 0;                                          // (the long-dialogue kernels read fp32 operands only)
+    ab.cu = cu; ab.T = cu ? T : B * L;
+    return 0;
+}
+
+int m2f_attention_varlen_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                             const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                             float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
+    return m2f_attention_varlen_fwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state,
+                                         stream, -1, -1);
+}
+int m2f_attention_varlen_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                                  float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+    AttnBatch ab;
+    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
+    m2f_attn_set_band(ab, past, future);
+    M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_attention_varlen_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                             const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo, const float* probs,
+                             const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                             uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
+    return m2f_attention_varlen_bwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, dout, lddo, dq, lddq, dk, lddk,
+                                         dv, lddv, drop_site, drop_p, rng_state, stream, -1, -1);
+}
+int m2f_attention_varlen_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo, const float* probs,
+                                  const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                                  uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+    AttnBatch ab;
+    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, const_cast<float*>(out), ldo, const_cast<float*>(probs),
+                         drop_site, drop_p, rng_state)) return -1;
+    m2f_attn_set_band(ab, past, future);               // (the backward skips the block pairs the forward skipped)
+    AttnProblem& p = ab.pr[0];
+    p.dout = dout; p.lddo = lddo; p.dq = dq; p.dk = dk; p.dv = dv; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+    M2F_HIP(m2f_launch_attn_dlong_bwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int64_t m2f_attention_stream_cache_elems(int S, int H, int hd, int C, int bf16) {
+    if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) { fail("m2f_attention_stream_cache_elems: S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512 required"); return -1; }
+    return (int64_t)m2f_attn_stream_cache_elems(S, H, hd, C, bf16 != 0);
+}
+int64_t m2f_attention_stream_pool_elems(int n_pages, int H, int hd, int R, int bf16) {
+    if (n_pages < 1 || H < 1 || hd < 1 || hd > 128 || (R != 16 && R != 32 && R != 64)) { fail("m2f_attention_stream_pool_elems: n_pages, H >= 1, 1 <= hd <= 128, R in {16, 32, 64} required"); return -1; }
+    return (int64_t)m2f_attn_stream_pool_elems(n_pages, H, hd, R, bf16 != 0);
+}
+static int paged_args_ok(const char* who, int S, int H, int hd, int C, int n_pages, int R, int table_cols, const void* kpool, const void* vpool, const void* table) {
+    const std::string w(who);
+    if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) return fail(w + ": S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512 required");
+    if (R != 16 && R != 32 && R != 64) return fail(w + ": page_rows must be 16, 32 or 64");
+    if (n_pages < 1) return fail(w + ": n_pages >= 1 required");
+    if (!kpool || !vpool || !table) return fail(w + ": NULL argument");
+    if (table_cols != (C + R - 1) / R) return fail(w + ": the table must be int32 [S, ceil(C / page_rows)]");
+    if ((reinterpret_cast<uintptr_t>(kpool) & 15) || (reinterpret_cast<uintptr_t>(vpool) & 15)) return fail(w + ": the pools must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(table) & 3) return fail(w + ": the table must be 4-byte aligned");
+    return 0;
+}
+/* The four kernel-level launches: one argument check and one batch fill.  chunk: the chunk form of T rows per slot (`second` = n_new),
+   otherwise the step form (`second` = active); pg == nullptr: dense caches, otherwise kc / vc are the pools. */
+static int stream_attn_fill(const char* who, AttnStreamBatch& sb, const AttnStreamPaging* pg, int S, bool chunk, int T, int H, int hd, const float* q, int ldq,
+                            const float* k, int ldk, const float* v, int ldv, void* kc, void* vc, int C, int ring, const int32_t* count,
+                            const void* second, float* out, int ldo, int bf16) {
+    const std::string w(who);
+    const bool t_ok = !chunk || (T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK);
+    if (pg) {
+        if (int r = paged_args_ok(who, S, H, hd, C, pg->n_pages, pg->R, pg->tw, kc, vc, pg->table)) return r;
+        if (!t_ok) return fail(w + ": 1 <= T <= 64 required");
+    } else if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C || !t_ok) {
+        return fail(w + ": S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512" + (chunk ? ", 1 <= T <= 64" : "") + " required");
+    }
+    if (!q || !k || !v || !kc || !vc || !count || !second || !out) return fail(w + ": NULL argument");
+    if (ldq < H * hd || ldk < H * hd || ldv < H * hd || ldo < H * hd) return fail(w + ": a leading dimension is narrower than H * hd");
+    if (!pg && ((reinterpret_cast<uintptr_t>(kc) & 15) || (reinterpret_cast<uintptr_t>(vc) & 15))) return fail(w + ": the caches must be 16-byte aligned");
+    memset(&sb, 0, sizeof(sb));
+    sb.count = 1; sb.S = S; sb.C = C; sb.ring = ring != 0; sb.bf16 = bf16 != 0; sb.len = count;
+    sb.active = chunk ? nullptr : static_cast<const uint8_t*>(second);
+    sb.sh = g_sh;
+    AttnStreamProblem& p = sb.pr[0];
+    p.q = q; p.k = k; p.v = v; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.out = out; p.ldo = ldo; p.kcache = kc; p.vcache = vc; p.H = H; p.hd = hd;
+    return 0;
+}
+int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                         void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
+                         int bf16, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    if (int r = stream_attn_fill("m2f_attention_stream", sb, nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
+    M2F_HIP(m2f_launch_attn_stream(sb, nullptr, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_stream_chunk(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               void* kcache, void* vcache, int C, int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo,
+                               int bf16, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    if (int r = stream_attn_fill("m2f_attention_stream_chunk", sb, nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
+    M2F_HIP(m2f_launch_attn_stream_chunk(sb, nullptr, T, n_new, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                               const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_paged", sb, &pg, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, active, out, ldo, bf16)) return r;
+    M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                     void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                     const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_chunk_paged", sb, &pg, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, n_new, out, ldo, bf16)) return r;
+    M2F_HIP(m2f_launch_attn_stream_chunk(sb, &pg, T, n_new, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+static int stream_cache_site(const char* who, int S, int H, int hd, void* kc, void* vc, int C, int bf16, const AttnStreamPaging* pg, int n_entries,
+                             const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
+                             int32_t* count, int scatter, m2f_stream_t stream) {
+    const std::string w(who);
+    if (!pg) {
+        if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) return fail(w + ": S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512 required");
+        if (!kc || !vc) return fail(w + ": NULL argument");
+        if ((reinterpret_cast<uintptr_t>(kc) & 15) || (reinterpret_cast<uintptr_t>(vc) & 15)) return fail(w + ": the caches must be 16-byte aligned");
+    }
+    if (n_entries < 0 || packed_elems < 0) return fail(w + ": n_entries, packed_elems >= 0 required");
+    if (!slots || !lengths || !row_offsets || !packed || (scatter && !count)) return fail(w + ": NULL argument");
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return fail(w + ": the packed buffer must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(row_offsets) & 7) return fail(w + ": row_offsets must be 8-byte aligned");
+    StreamCacheBatch cb;
+    memset(&cb, 0, sizeof(cb));
+    const int vpr = m2f_stream_cache_row_vecs(hd, bf16 != 0);
+    cb.count = 1;
+    cb.site[0] = {kc, vc, H, vpr, 0, 0};
+    cb.S = S; cb.C = C; cb.rowv = 2 * H * vpr; cb.n_entries = n_entries;
+    cb.slots = slots; cb.lengths = lengths; cb.row_offsets = row_offsets;
+    cb.packed = packed; cb.packed_vecs = packed_elems / (bf16 ? 8 : 4); cb.len = count;
+    M2F_HIP(m2f_launch_stream_cache(cb, pg, scatter, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, int C, int bf16, int n_entries,
+                                      const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
+                                      int64_t packed_elems, m2f_stream_t stream) {
+    return stream_cache_site("m2f_attention_stream_cache_gather", S, H, hd, const_cast<void*>(kcache), const_cast<void*>(vcache), C, bf16, nullptr,
+                             n_entries, slots, lengths, row_offsets, packed, packed_elems, nullptr, 0, stream);
+}
+int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, int C, int bf16, int n_entries,
+                                       const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
+                                       int64_t packed_elems, int32_t* count, m2f_stream_t stream) {
+    return stream_cache_site("m2f_attention_stream_cache_scatter", S, H, hd, kcache, vcache, C, bf16, nullptr, n_entries, slots, lengths, row_offsets,
+                             const_cast<void*>(packed), packed_elems, count, 1, stream);
+}
+int m2f_attention_stream_cache_gather_paged(int S, int H, int hd, const void* kpool, const void* vpool, const int32_t* table, int table_cols,
+                                            int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                            const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
+                                            m2f_stream_t stream) {
+    if (int r = paged_args_ok("m2f_attention_stream_cache_gather_paged", S, H, hd, C, n_pages, page_rows, table_cols, kpool, vpool, table)) return r;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    return stream_cache_site("m2f_attention_stream_cache_gather_paged", S, H, hd, const_cast<void*>(kpool), const_cast<void*>(vpool), C, bf16, &pg,
+                             n_entries, slots, lengths, row_offsets, packed, packed_elems, nullptr, 0, stream);
+}
+int m2f_attention_stream_cache_scatter_paged(int S, int H, int hd, void* kpool, void* vpool, const int32_t* table, int table_cols,
+                                             int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                             const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
+                                             int32_t* count, m2f_stream_t stream) {
+    if (int r = paged_args_ok("m2f_attention_stream_cache_scatter_paged", S, H, hd, C, n_pages, page_rows, table_cols, kpool, vpool, table)) return r;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    return stream_cache_site("m2f_attention_stream_cache_scatter_paged", S, H, hd, kpool, vpool, C, bf16, &pg, n_entries, slots, lengths, row_offsets,
+                             const_cast<void*>(packed), packed_elems, count, 1, stream);
+}
+
+int64_t m2f_attention_probs_elems(int B, int H, int L) { return (int64_t)m2f_attn_probs_elems(B, H, L); }
+
+int m2f_layernorm_fwd(int T, int d, const float* x, const float* gamma, const float* beta, const float* res, float* out,
+                      float* stats, float eps, m2f_stream_t stream) {
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    LnProblem& p = lb.pr[0];
+    p.x = x; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out; p.stats = stats; p.d = d;
+    lb.count = 1; lb.T = T; lb.eps = eps; lb.drop_scale = 1.f; lb.sh = g_sh;
+    M2F_HIP(m2f_launch_ln_fwd(lb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+/* diagnostic (tools/ln_stats_ab.py; not in include/m2fnet_hip.h's product surface): the LayerNorm forward over `count` problems merged in one launch
+ * as the plans do (x / out of problem i at x + i * T * ld ... the caller lays them out), statistics computed (pre = 0) or read from `stats` (pre = 1) */
+int m2f_layernorm_fwd_diag(int T, int n_prob, const int* d, const float* const* x, const float* const* gamma, const float* const* beta, float* const* out,
+                           float* const* stats, float eps, int pre, m2f_stream_t stream) {
+    if (n_prob < 1 || n_prob > M2F_LN_MAX_PROBLEMS) return fail("m2f_layernorm_fwd_diag: 1..4 problems");
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    for (int i = 0; i < n_prob; ++i) {
+        LnProblem& p = lb.pr[i];
+        p.x = x[i]; p.gamma = gamma[i]; p.beta = beta[i]; p.out = out[i]; p.stats = stats[i]; p.d = d[i];
+    }
+    lb.count = n_prob; lb.T = T; lb.eps = eps; lb.drop_scale = 1.f; lb.sh = g_sh; lb.pre_stats = pre;
+    M2F_HIP(m2f_launch_ln_fwd(lb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_layernorm_fwd_out8(int T, int d, const float* x, const float* gamma, const float* beta, const float* res, float* out,
+                           float* stats, float eps, uint8_t* out8, float out8_scale, m2f_stream_t stream) {
+    if (!out8 || (d & 3) || (reinterpret_cast<uintptr_t>(out8) & 3)) return fail("m2f_layernorm_fwd_out8: e4m3 output needs d % 4 == 0 and a 4-byte aligned buffer");
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    LnProblem& p = lb.pr[0];
+    p.x = x; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out; p.stats = stats; p.d = d;
+    lb.count = 1; lb.T = T; lb.eps = eps; lb.drop_scale = 1.f; lb.sh = g_sh; lb.out8 = out8; lb.out8_scale = out8_scale;
+    M2F_HIP(m2f_launch_ln_fwd(lb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_embed_layernorm(int T, int d, const int64_t* input_ids, const int64_t* position_ids, const float* word_emb,
+                        const float* pos_emb, const float* type_emb_row0, const float* gamma, const float* beta, float eps,
+                        float* out, int ld_out, m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_embed_ln(input_ids, position_ids, word_emb, pos_emb, type_emb_row0, gamma, beta, eps, out, ld_out, T, d, g_sh,
+                                static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_attention_long_fwd(int B, int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                           const uint8_t* key_pad, float* out, int ldo, m2f_stream_t stream) {
+    M2F_HIP(m2f_launch_attn_long_fwd(q, ldq, k, ldk, v, ldv, key_pad, out, ldo, B, S, H, hd, g_sh, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_attention_long_fwd_bf16(int B, int S, int H, int hd, const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v,
+                                int ldv, const uint8_t* key_pad, uint16_t* out16, float* out32, int ldo, m2f_stream_t stream) {
+    return m2f_attention_long_fwd_bf16_out8(B, S, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out16, out32, nullptr, 1.f, ldo, stream);
+}
+
+int m2f_attention_long_fwd_bf16_out8(int B, int S, int H, int hd, const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v,
+                                     int ldv, const uint8_t* key_pad, uint16_t* out16, float* out32, uint8_t* out8, float out8_scale, int ldo,
+                                     m2f_stream_t stream) {
+    if (!q || !k || !v || !(out16 || out32 || out8)) return fail("m2f_attention_long_fwd_bf16: NULL operand / no output");
+    if (hd < 8 || hd > 128 || (hd & 7) || ((ldq | ldk | ldv | ldo) & 7))
+        return fail("m2f_attention_long_fwd_bf16: head dim and leading dimensions must be multiples of 8, head dim <= 128");
+    if (out8 && ((hd & 15) || (ldo & 15))) return fail("m2f_attention_long_fwd_bf16: the e4m3 output needs head dim and ldo in multiples of 16");
+    M2F_HIP(m2f_launch_attn_long_fwd_bf16(q, ldq, k, ldk, v, ldv, key_pad, out16, out32, out8, out8_scale, ldo, B, S, H, hd, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_layernorm_bwd(int T, int d, const float* x, const float* gamma, const float* stats, const float* dy, const float* extra,
+                      float* dx, float* partial, float* dgamma, float* dbeta, m2f_stream_t stream) {
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    LnProblem& p = lb.pr[0];
+    p.x = x; p.gamma = gamma; p.stats = const_cast<float*>(stats); p.dy = dy; p.extra = extra; p.dx = dx; p.partial = partial; p.d = d;
+    lb.count = 1; lb.T = T; lb.eps = 0.f; lb.drop_scale = 1.f;
+    M2F_HIP(m2f_launch_ln_bwd(lb, static_cast<hipStream_t>(stream)));
+    LnReduceBatch rb;
+    memset(&rb, 0, sizeof(rb));
+    rb.it[0].partial = partial; rb.it[0].dgamma = dgamma; rb.it[0].dbeta = dbeta; rb.it[0].d = d; rb.it[0].nblk = m2f_ln_row_blocks(T);
+    rb.count = 1;
+    M2F_HIP(m2f_launch_ln_param_reduce(rb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+/* kernel-level tests of the dropout sites the row-wise kernels carry (tests/test_dropout_masks_gpu.py): the launches of the train plans */
+int m2f_layernorm_fwd_drop(int T, int d, int ld, const float* x, const float* gamma, const float* beta, const float* res, float* out,
+                           float* stats, float eps, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
+    if (ld && ld < d) return fail("m2f_layernorm_fwd_drop: ld must be 0 or at least d");
+    if (drop_site && (!rng_state || !(drop_p > 0.f && drop_p < 1.f))) return fail("m2f_layernorm_fwd_drop: a site needs an rng_state and 0 < drop_p < 1");
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    LnProblem& p = lb.pr[0];
+    p.x = x; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out; p.stats = stats; p.d = d; p.ld = ld; p.drop_site = drop_site;
+    lb.count = 1; lb.T = T; lb.eps = eps; lb.drop_scale = 1.f; lb.sh = g_sh; lb.rng = rng_state;
+    if (drop_site) drop_params(drop_p, &lb.drop_thresh, &lb.drop_scale);
+    M2F_HIP(m2f_launch_ln_fwd(lb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_layernorm_bwd_masked(int T, int d, int ld, const float* x, const float* gamma, const float* stats, const float* dy,
+                             const float* extra, float* dx, float* dx_masked, float* partial, float* dgamma, float* dbeta,
+                             uint32_t drop_site2, float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
+    if (ld && ld < d) return fail("m2f_layernorm_bwd_masked: ld must be 0 or at least d");
+    if (drop_site2 && (!rng_state || !(drop_p > 0.f && drop_p < 1.f))) return fail("m2f_layernorm_bwd_masked: a site needs an rng_state and 0 < drop_p < 1");
+    LnBatch lb;
+    memset(&lb, 0, sizeof(lb));
+    LnProblem& p = lb.pr[0];
+    p.x = x; p.gamma = gamma; p.stats = const_cast<float*>(stats); p.dy = dy; p.extra = extra; p.dx = dx; p.dx_masked = dx_masked;
+    p.partial = partial; p.d = d; p.ld = ld; p.drop_site2 = drop_site2;
+    lb.count = 1; lb.T = T; lb.eps = 0.f; lb.drop_scale = 1.f; lb.rng = rng_state;
+    if (drop_site2) drop_params(drop_p, &lb.drop_thresh, &lb.drop_scale);
+    M2F_HIP(m2f_launch_ln_bwd(lb, static_cast<hipStream_t>(stream)));
+    LnReduceBatch rb;
+    memset(&rb, 0, sizeof(rb));
+    rb.it[0].partial = partial; rb.it[0].dgamma = dgamma; rb.it[0].dbeta = dbeta; rb.it[0].d = d; rb.it[0].nblk = m2f_ln_row_blocks(T);
+    rb.count = 1;
+    M2F_HIP(m2f_launch_ln_param_reduce(rb, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_dropout_rows(float* x, float* x2, int T, int d, int ld, uint32_t site, uint32_t site2, float drop_p, const uint32_t* rng_state,
+                     m2f_stream_t stream) {
+    if (!x || !rng_state || T < 1 || d < 1 || ld < d) return fail("m2f_dropout_rows: NULL buffer / rng_state, or not 1 <= d <= ld");
+    if (!(drop_p > 0.f && drop_p < 1.f)) return fail("m2f_dropout_rows: 0 < drop_p < 1 required");
+    uint32_t thresh; float scale;
+    drop_params(drop_p, &thresh, &scale);
+    M2F_HIP(m2f_launch_dropout_inplace2(x, x2, T, d, ld, site, site2, rng_state, thresh, scale, g_sh, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
+                      int normalise, float* loss_terms, float* dlogits, float* loss_out, m2f_stream_t stream) {
+    CeArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
+    a.loss_terms = loss_terms; a.dlogits = dlogits;
+    M2F_HIP(m2f_launch_ce(a, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
+                              float label_smoothing, const float* hyper_dev, int normalise, float* loss_terms, float* dlogits,
+                              float* loss_out, m2f_stream_t stream) {
+    if (!logits || !teacher || !labels || !hyper_dev || !loss_terms || !dlogits || !loss_out)
+        return fail("m2f_cross_entropy_distill: NULL logits / teacher / labels / hyper_dev / loss_terms / dlogits / loss_out");
+    if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_distill: T >= 1 and 1 <= C <= 16 required");
+    CeDistillArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
+    a.teacher = teacher; a.hyper = hyper_dev; a.loss_terms = loss_terms; a.dlogits = dlogits;
+    M2F_HIP(m2f_launch_ce_distill(a, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
+    return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
+}
+
+int m2f_w2v_conv0(int B, int N, const float* wave, const float* w0, int k0, int s0, int C, int T0, int P0, const float* gamma,
+                  const float* beta, float eps, float* scratch, float* out32, uint16_t* out16, m2f_stream_t stream) {
+    if (!wave || !w0 || !gamma || !beta || !scratch || !out32 == !out16) return fail("m2f_w2v_conv0: NULL operand, or not exactly one output");
+    if (k0 < 1 || k0 > M2F_W2V_CONV0_MAX_TAPS || s0 < 1 || s0 > M2F_W2V_CONV0_MAX_STRIDE) return fail("m2f_w2v_conv0: kernel <= 16 and stride <= 8 only");
+    if (B < 1 || C < 1 || N < k0 || T0 != (N - k0) / s0 + 1 || P0 < T0) return fail("m2f_w2v_conv0: T0 must be (N - k0) / s0 + 1 and P0 >= T0");
+    float* stats = scratch + (int64_t)2 * B * C * m2f_w2v_conv0_chunks(T0);
+    M2F_HIP(m2f_launch_w2v_conv0(wave, B, N, w0, k0, s0, C, T0, P0, gamma, beta, eps, scratch, stats, out32, out16,
+                                 static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_w2v_feat_layernorm(int B, int S, int P, int C, const float* x, const float* gamma, const float* beta, float eps, float* out32,
+                           uint16_t* out16, m2f_stream_t stream) {
+    if (!x || !gamma || !beta || !out32) return fail("m2f_w2v_feat_layernorm: NULL operand");
+    if (B < 1 || S < 1 || P < S || C < 1 || C > M2F_W2V_FEAT_MAX_C) return fail("m2f_w2v_feat_layernorm: need S <= P and 1 <= C <= 1024");
+    M2F_HIP(m2f_launch_w2v_feat_ln(x, B, S, P, C, gamma, beta, eps, out32, out16, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_w2v_pos_conv(int B, int S, int d, int groups, int K, const float* x, const int32_t* lengths, const void* w, const float* bias,
+                     float* out, int bf16, m2f_stream_t stream) {
+    if (!x || !lengths || !w || !bias || !out) return fail("m2f_w2v_pos_conv: NULL operand");
+    if (B < 1 || S < 1 || groups < 1 || d % groups || (d / groups) % 16 || d / groups > 64 || K < 1 || K > M2F_W2V_POS_MAX_TAPS)
+        return fail("m2f_w2v_pos_conv: channels per group must be 16, 32, 48 or 64 and 1 <= K <= 256");
+    if (x == out) return fail("m2f_w2v_pos_conv: out must not alias x");
+    M2F_HIP(m2f_launch_w2v_pos_conv(x, lengths, B, S, d, groups, K, w, bias, out, bf16 != 0, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_w2v_masked_mean(int B, int S, int d, const float* x, const int32_t* lengths, float* out, m2f_stream_t stream) {
+    if (!x || !lengths || !out || B < 1 || S < 1 || d < 1) return fail("m2f_w2v_masked_mean: NULL operand or empty shape");
+    M2F_HIP(m2f_launch_w2v_masked_mean(x, lengths, B, S, d, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int64_t m2f_mel_frontend_scratch_floats(int B) {
+    return B < 1 ? 0 : (int64_t)(B + 63) / 64 * 64 + (int64_t)B * M2F_MEL_FRAMES * M2F_MEL_BANDS;
+}
+
+int m2f_mel_frontend(int B, int N, const float* wave, const int32_t* lengths, const float* basis, const float* fbT, int png_levels,
+                     float* scratch, float* img, m2f_stream_t stream) {
+    if (!wave || !lengths || !basis || !fbT || !scratch || !img) return fail("m2f_mel_frontend: NULL operand");
+    if (B < 1 || N < 1) return fail("m2f_mel_frontend: empty batch");
+    float* logmel = scratch + (int64_t)(B + 63) / 64 * 64;
+    M2F_HIP(m2f_launch_mel_frontend(wave, lengths, B, N, basis, fbT, png_levels != 0, scratch, logmel, img, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_mel_stem(int B, const float* img, const float* w, const float* bias, float* out32, uint16_t* out16, m2f_stream_t stream) {
+    if (!img || !w || !bias || !out32 == !out16) return fail("m2f_mel_stem: NULL operand, or not exactly one output");
+    if (B < 1) return fail("m2f_mel_stem: empty batch");
+    M2F_HIP(m2f_launch_mel_stem(img, B, w, bias, out32, out16, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_mel_conv(int B, int H, int W, int Cin, int Cout, int ks, int stride, const void* x, const void* w, const float* bias,
+                 const void* res, void* out, int bf16, int out_fp32, int relu, m2f_stream_t stream) {
+    if (!x || !w || !bias || !out) return fail("m2f_mel_conv: NULL operand");
+    if (B < 1 || H < 1 || W < 1 || Cin < 32 || Cin % 32 || Cout < 64 || Cout % 64 || (ks != 1 && ks != 3) || stride < 1 || stride > 2)
+        return fail("m2f_mel_conv: Cin a multiple of 32, Cout a multiple of 64, 1x1 or 3x3 windows, stride 1 or 2");
+    if (out == x || (res && out == res)) return fail("m2f_mel_conv: out must not alias x or res");
+    const int pad = ks / 2, Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+    if ((int64_t)B * Ho * Wo > (1 << 30)) return fail("m2f_mel_conv: more than 2^30 output pixels in one launch");
+    M2F_HIP(m2f_launch_mel_conv(x, w, bias, res, out, B, H, W, Cin, Cout, ks, stride, bf16 != 0, out_fp32 != 0, relu != 0,
+                                static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_mel_head(int B, int HW, int C, const void* x, int bf16_in, const float* w1t, const float* b1, int N1, const float* w2t,
+                 const float* b2, int N2, float* out, m2f_stream_t stream) {
+    if (!x || !w1t || !b1 || !w2t || !b2 || !out) return fail("m2f_mel_head: NULL operand");
+    if (B < 1 || HW < 1 || C < 1 || N1 < 1 || N2 < 1 || N2 > 512 || (C + N1) * 4 > 64 * 1024)
+        return fail("m2f_mel_head: need N2 <= 512 and C + N1 floats of LDS at most 64 KiB");
+    M2F_HIP(m2f_launch_mel_head(x, bf16_in != 0, B, HW, C, w1t, b1, N1, w2t, b2, N2, out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // The parameter map of a configuration and every table cut from it (param_tables.hip): ONE host table per configuration - offsets,
 // optimizer items, tile and slice prefixes - and ONE cache of the device copies the optimizer, norm and statistics kernels walk.
-// Shared with plan.hip, which builds its plans on the same map and its in-launch optimizer tables with the same helpers.
+// Shared with the plan files (plan.h), which build their plans on the same map and their in-launch optimizer tables with the same helpers.
 #pragma once
 #include "../../include/m2fnet_hip.h"
 #include "ops.h"

@@ -1,6 +1,6 @@
 // The per-tensor tables of a configuration and the entry points that walk the flat parameter buffer tensor by tensor: the parameter
 // shadows' table region, the Adam steps over ranges and groups, the EMA exchange, the gradient norm and the model watch's statistics.
-// Every fact has one home: param_table (the host table of a configuration - the size queries, the table region, plan.hip's coverage
+// Every fact has one home: param_table (the host table of a configuration - the size queries, the table region, plan_build.hip's coverage
 // walk and every device table derive from it), cut_slices, tensor_range (checked on the host table before any device call) and
 // device_table (the one cache of device copies).
 #include "param_tables.h"

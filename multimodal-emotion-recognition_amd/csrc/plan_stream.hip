@@ -1,0 +1,222 @@
+// Stream and chunk plans (include/m2fnet_hip.h): plans of plan.h whose attention sites run the streaming kernels against per-slot K / V caches
+// or page pools - their life cycle, m2f_stream_step / m2f_stream_prefill, and snapshot gather / scatter of live dialogues through a plan.
+#include "plan.h"
+
+using namespace m2f;
+
+extern "C" {
+
+/* One plan object, over dense caches (n_pages == 0) or page pools; sizing and creation below serve the four public entry points.  The
+   paged ones hand a page count below 1 on as -1, so that it is refused here, in its place among the other checks. */
+static m2f_plan* stream_plan_new(const m2f_config* cfg, int S, int& C, int past, int precision, int n_pages, int page_rows) {
+    if (precision != M2F_F32 && precision != M2F_BF16) { fail("bad precision"); return nullptr; }
+    if (n_pages) {
+        if (page_rows != 16 && page_rows != 32 && page_rows != 64) { fail("paged stream plan: page_rows must be 16, 32 or 64 (got " + std::to_string(page_rows) + ")"); return nullptr; }
+        if (n_pages < 1) { fail("paged stream plan: n_pages >= 1 required"); return nullptr; }
+    }
+    if (!cfg || S < 1) { fail("stream plan: S >= 1 stream slots required"); return nullptr; }
+    if (past >= 0 && C < past + 1) C = past + 1;
+    if (C < 1 || C > M2F_ATTN_STREAM_MAX_C) {
+        fail("stream plan: capacity must be 1 .. " + std::to_string(M2F_ATTN_STREAM_MAX_C) + " rows per slot (got " + std::to_string(C) +
+             "; a window of `past` utterances needs past + 1)");
+        return nullptr;
+    }
+    m2f_config c = *cfg;
+    c.dropout = 0.f;                                    // an eval plan: no dropout site
+    m2f_plan* p = plan_new(&c, S, 1, precision, 0);
+    if (!p) return nullptr;
+    const int hmax = std::max(c.audio_enabled ? c.d_audio / std::max(c.nhead_audio, 1) : 0,
+                              std::max(c.text_enabled ? c.d_text / std::max(c.nhead_text, 1) : 0, c.fam_enabled ? c.d_fam / std::max(c.nhead_fam, 1) : 0));
+    if (hmax > 128) { fail("stream plan: head dims up to 128 (got " + std::to_string(hmax) + ")"); delete p; return nullptr; }
+    p->streaming = true; p->s_cap = C; p->s_ring = past >= 0;
+    p->band_past = past < 0 ? -1 : past; p->band_future = 0;       // (what m2f_plan_get_attention_band reports)
+    if (n_pages) {
+        p->s_pages = n_pages;
+        p->s_pg.R = page_rows; p->s_pg.tw = (C + page_rows - 1) / page_rows; p->s_pg.n_pages = n_pages;
+    }
+    return p;
+}
+static int64_t stream_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows, int shared) {
+    int64_t need = -1;
+    return size_and_build(stream_plan_new(cfg, S, C, past, precision, n_pages, page_rows), shared != 0, 4096, nullptr, need) == BUILD_OK ? need : -1;
+}
+// a stream or chunk plan `p` (null: refused by its maker) bound to its buffers and built through the one size-then-build path; `dry`: its twin
+static m2f_plan* stream_build(m2f_plan* p, m2f_plan* dry, float* params, void* workspace, int64_t workspace_bytes, uint16_t* param_shadow) {
+    if (!p) { delete dry; return nullptr; }
+    p->ext_wshadow = param_shadow;
+    p->params = params; p->grads = nullptr; p->rng = nullptr;
+    p->ws_base = static_cast<char*>(workspace); p->ws_bytes = workspace_bytes;
+    int64_t need = -1;
+    const BuildStatus st = size_and_build(dry, param_shadow != nullptr, 4096, p, need);
+    if (st == BUILD_TOO_SMALL) fail("workspace too small: need " + std::to_string(need) + " bytes");
+    if (st != BUILD_OK) { delete p; return nullptr; }
+    return p;
+}
+static m2f_plan* stream_plan_create(const char* who, const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows,
+                                    float* params, void* workspace, int64_t workspace_bytes, uint16_t* param_shadow) {
+    if (!params || !workspace) { fail("params / workspace must not be NULL"); return nullptr; }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(params) & 255) || (reinterpret_cast<uintptr_t>(param_shadow) & 255)) {
+        fail("params / workspace / param_shadow must be 256-byte aligned"); return nullptr;
+    }
+    m2f_plan* p = stream_build(stream_plan_new(cfg, S, C, past, precision, n_pages, page_rows), stream_plan_new(cfg, S, C, past, precision, n_pages, page_rows),
+                               params, workspace, workspace_bytes, param_shadow);
+    if (!p) return nullptr;
+    // counters and table start at zero whatever the workspace held (page 0 is a valid id; an entry is read only once the host has set it)
+    if (hipMemset(p->s_len, 0, (size_t)S * sizeof(int)) != hipSuccess || hipMemset(p->s_active, 0, (size_t)S) != hipSuccess ||
+        (n_pages && hipMemset(p->bufs[M2F_BUF_STREAM_TABLE], 0, (size_t)S * p->s_pg.tw * sizeof(int)) != hipSuccess)) {
+        fail(std::string(who) + ": hipMemset"); delete p; return nullptr;
+    }
+    return p;
+}
+int64_t m2f_stream_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int shared) {
+    return stream_workspace_bytes(cfg, S, C, past, precision, 0, 0, shared);
+}
+m2f_plan* m2f_plan_create_stream(const m2f_config* cfg, int S, int C, int past, int precision, float* params, void* workspace,
+                                 int64_t workspace_bytes, uint16_t* param_shadow) {
+    return stream_plan_create("m2f_plan_create_stream", cfg, S, C, past, precision, 0, 0, params, workspace, workspace_bytes, param_shadow);
+}
+int64_t m2f_stream_paged_workspace_bytes(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows, int shared) {
+    return stream_workspace_bytes(cfg, S, C, past, precision, n_pages < 1 ? -1 : n_pages, page_rows, shared);
+}
+m2f_plan* m2f_plan_create_stream_paged(const m2f_config* cfg, int S, int C, int past, int precision, int n_pages, int page_rows, float* params,
+                                       void* workspace, int64_t workspace_bytes, uint16_t* param_shadow) {
+    return stream_plan_create("m2f_plan_create_stream_paged", cfg, S, C, past, precision, n_pages < 1 ? -1 : n_pages, page_rows, params, workspace,
+                              workspace_bytes, param_shadow);
+}
+static int stream_body(m2f_plan& P, hipStream_t s) {
+    if (int r = do_forward(P, s)) return r;
+    M2F_HIP(m2f_launch_stream_advance(P.s_len, P.s_active, P.B, s));
+    return 0;
+}
+int m2f_stream_step(m2f_plan* plan, int use_graph, m2f_stream_t stream) {
+    if (!plan) return fail("m2f_stream_step: NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.streaming || P.s_parent) return fail("m2f_stream_step needs a stream plan (m2f_plan_create_stream)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!use_graph || !P.warmed) { P.warmed = true; return stream_body(P, s); }
+    return replay_slot(P.graphs[SLOT_STREAM], GraphKey::forward(P.params_fresh, P.generation), s, [&] { return stream_body(P, s); });
+}
+int m2f_stream_reset(m2f_plan* plan, const uint8_t* slot_mask, m2f_stream_t stream) {
+    if (!plan) return fail("m2f_stream_reset: NULL plan (destroyed?)");
+    if (!plan->streaming || plan->s_parent) return fail("m2f_stream_reset needs a stream plan (m2f_plan_create_stream)");
+    M2F_HIP(m2f_launch_stream_reset(plan->s_len, slot_mask, plan->B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int64_t m2f_stream_cache_bytes(m2f_plan* plan) { return plan && plan->streaming && !plan->s_parent ? plan->s_cache_bytes : -1; }     // (a chunk plan owns no cache)
+
+/* Snapshot / restore of a stream plan's dialogues.  See include/m2fnet_hip.h and stream_cache.hip. */
+static void stream_sites(const m2f_plan& P, std::vector<StreamCacheSite>& sites, std::vector<int>* hds, int& rowv) {
+    const int bf16 = P.prec == M2F_PREC_BF16;
+    rowv = 0;
+    for (const Launch& l : P.built.fwd) {
+        if (l.kind != OP_ATTN_FWD) continue;
+        for (int i = 0; i < l.sb.count; ++i) {
+            const AttnStreamProblem& q = l.sb.pr[i];
+            const int vpr = m2f_stream_cache_row_vecs(q.hd, bf16);
+            sites.push_back({q.kcache, q.vcache, q.H, vpr, rowv, 0});
+            if (hds) hds->push_back(q.hd);
+            rowv += 2 * q.H * vpr;
+        }
+    }
+}
+int64_t m2f_stream_snapshot_row_elems(m2f_plan* plan) {
+    if (!plan || !plan->streaming || plan->s_parent) { fail("m2f_stream_snapshot_row_elems needs a stream plan (m2f_plan_create_stream)"); return -1; }
+    std::vector<StreamCacheSite> sites;
+    int rowv = 0;
+    stream_sites(*plan, sites, nullptr, rowv);
+    return (int64_t)rowv * (plan->prec == M2F_PREC_BF16 ? 8 : 4);
+}
+int m2f_stream_snapshot_sites(m2f_plan* plan, int* H, int* hd, int max_sites) {
+    if (!plan || !plan->streaming || plan->s_parent) return fail("m2f_stream_snapshot_sites needs a stream plan (m2f_plan_create_stream)");
+    std::vector<StreamCacheSite> sites;
+    std::vector<int> hds;
+    int rowv = 0;
+    stream_sites(*plan, sites, &hds, rowv);
+    for (size_t i = 0; i < sites.size() && (int)i < max_sites; ++i) {
+        if (H) H[i] = sites[i].H;
+        if (hd) hd[i] = hds[i];
+    }
+    return (int)sites.size();
+}
+static int stream_cache_move(m2f_plan* plan, const char* who, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets,
+                             void* packed, int64_t packed_elems, int scatter, m2f_stream_t stream) {
+    const std::string w(who);
+    if (!plan) return fail(w + ": NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.streaming || P.s_parent) return fail(w + " needs a stream plan (m2f_plan_create_stream)");
+    if (n < 0 || packed_elems < 0) return fail(w + ": n, packed_elems >= 0 required");
+    if (n == 0) return 0;
+    if (!slots || !lengths || !row_offsets || !packed) return fail(w + ": NULL argument");
+    if (reinterpret_cast<uintptr_t>(packed) & 15) return fail(w + ": the packed buffer must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(row_offsets) & 7) return fail(w + ": row_offsets must be 8-byte aligned");
+    std::vector<StreamCacheSite> sites;
+    int rowv = 0;
+    stream_sites(P, sites, nullptr, rowv);
+    if (sites.empty()) return fail(w + ": the plan has no attention site");
+    const int epv = P.prec == M2F_PREC_BF16 ? 8 : 4;            // elements per 16-byte vector
+    for (size_t s0 = 0; s0 < sites.size(); s0 += M2F_STREAM_CACHE_MAX_SITES) {
+        StreamCacheBatch cb;
+        memset(&cb, 0, sizeof(cb));
+        cb.count = (int)std::min(sites.size() - s0, (size_t)M2F_STREAM_CACHE_MAX_SITES);
+        for (int i = 0; i < cb.count; ++i) cb.site[i] = sites[s0 + i];
+        cb.S = P.B; cb.C = P.s_cap; cb.rowv = rowv; cb.n_entries = n;
+        cb.slots = slots; cb.lengths = lengths; cb.row_offsets = row_offsets;
+        cb.packed = packed; cb.packed_vecs = packed_elems / epv; cb.len = P.s_len;
+        M2F_HIP(m2f_launch_stream_cache(cb, P.s_pages ? &P.s_pg : nullptr, scatter, static_cast<hipStream_t>(stream)));
+    }
+    return 0;
+}
+int m2f_stream_gather(m2f_plan* plan, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
+                      int64_t packed_elems, m2f_stream_t stream) {
+    return stream_cache_move(plan, "m2f_stream_gather", n, slots, lengths, row_offsets, packed, packed_elems, 0, stream);
+}
+int m2f_stream_scatter(m2f_plan* plan, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
+                       int64_t packed_elems, m2f_stream_t stream) {
+    return stream_cache_move(plan, "m2f_stream_scatter", n, slots, lengths, row_offsets, const_cast<void*>(packed), packed_elems, 1, stream);
+}
+
+/* Chunk plans.  See include/m2fnet_hip.h. */
+static m2f_plan* chunk_plan_new(m2f_plan* parent, int T) {
+    if (!parent || !parent->streaming || parent->s_parent) { fail("chunk plan: the parent must be a stream plan (m2f_plan_create_stream)"); return nullptr; }
+    if (T < 2 || T > M2F_ATTN_STREAM_MAX_CHUNK) {
+        fail("chunk plan: 2 .. " + std::to_string(M2F_ATTN_STREAM_MAX_CHUNK) + " rows per slot and call (got " + std::to_string(T) + ")");
+        return nullptr;
+    }
+    m2f_plan* p = plan_new(&parent->cfg, parent->B, T, parent->prec, 0);      // (the parent's configuration: dropout already 0)
+    if (!p) return nullptr;
+    p->streaming = true; p->s_cap = parent->s_cap; p->s_ring = parent->s_ring;
+    p->band_past = parent->band_past; p->band_future = parent->band_future;
+    p->s_parent = parent; p->s_chunk = T;
+    p->s_pages = parent->s_pages; p->s_pg = parent->s_pg;                      // (a paged parent: the same pools through the same table)
+    return p;
+}
+int64_t m2f_stream_chunk_workspace_bytes(m2f_plan* parent, int T, int shared) {
+    int64_t need = -1;
+    return size_and_build(chunk_plan_new(parent, T), shared != 0, 4096, nullptr, need) == BUILD_OK ? need : -1;
+}
+m2f_plan* m2f_plan_create_stream_chunk(m2f_plan* parent, int T, float* params, void* workspace, int64_t workspace_bytes,
+                                       uint16_t* param_shadow) {
+    if (!params || !workspace) { fail("params / workspace must not be NULL"); return nullptr; }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(params) & 255) || (reinterpret_cast<uintptr_t>(param_shadow) & 255)) {
+        fail("params / workspace / param_shadow must be 256-byte aligned"); return nullptr;
+    }
+    m2f_plan* p = stream_build(chunk_plan_new(parent, T), chunk_plan_new(parent, T), params, workspace, workspace_bytes, param_shadow);
+    if (!p) return nullptr;
+    if (hipMemset(p->s_new, 0, (size_t)p->B * sizeof(int)) != hipSuccess) { fail("m2f_plan_create_stream_chunk: hipMemset"); delete p; return nullptr; }
+    return p;
+}
+static int prefill_body(m2f_plan& P, hipStream_t s) {
+    if (int r = do_forward(P, s)) return r;
+    M2F_HIP(m2f_launch_stream_advance_n(P.s_len, P.s_new, P.B, P.s_chunk, s));
+    return 0;
+}
+int m2f_stream_prefill(m2f_plan* plan, int use_graph, m2f_stream_t stream) {
+    if (!plan) return fail("m2f_stream_prefill: NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.s_parent) return fail("m2f_stream_prefill needs a chunk plan (m2f_plan_create_stream_chunk)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!use_graph || !P.warmed) { P.warmed = true; return prefill_body(P, s); }
+    return replay_slot(P.graphs[SLOT_PREFILL], GraphKey::forward(P.params_fresh, P.generation), s, [&] { return prefill_body(P, s); });
+}
+
+}  // extern "C"

@@ -508,7 +508,7 @@ class DataParallelStep:
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
             self.model._set_criterion(plan, teacher_logits, dist)
-            if self._pending or getattr(plan, "_acc", False):
+            if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:
                 plan.step(label_smoothing, class_weights is not None, False, use_graph)   # tail <- (loss, den += , num += )
@@ -522,7 +522,7 @@ class DataParallelStep:
             # bf16 exchange, whole-step form: the step itself leaves every gradient rounded in the exchange buffer (the weight-gradient
             # launch writes bf16 dW directly: no fp32 dW round trip, no rounding pass over 4 bytes per parameter before the all-reduce) -
             # the engine arms its train plans with the reducer's buffer (model._Engine._arm_grad_bf16; plans that cannot keep fp32)
-            self.reducer.buf16_filled = split == 0 and self.reducer.buf16 is not None and getattr(plan, "_g16_ref", None) is self.reducer.buf16
+            self.reducer.buf16_filled = split == 0 and self.reducer.buf16 is not None and plan._g16_ref is self.reducer.buf16
             if split > 0:
                 cw = class_weights is not None
                 plan.step_part(0, label_smoothing, cw, False, use_graph)              # tail <- (loss, den, num); fusion / classifier gradients final

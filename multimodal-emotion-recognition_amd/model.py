@@ -317,7 +317,7 @@ class _Engine:
     # -- gradients left as bf16 by the step (M2FNet.set_grad_bf16) -------------------------------------------------------------
     def _arm_grad_bf16(self, pl) -> None:
         want = self.grad_bf16_buf
-        if getattr(pl, "_g16_ref", None) is want or getattr(pl, "_g16_bad", False):
+        if pl._g16_ref is want or pl._g16_bad:
             return
         try:
             pl.grad_bf16(want)
@@ -327,7 +327,7 @@ class _Engine:
             pl._g16_bad = True                               # (fp32 mode, another table form): this plan keeps fp32 gradients ...
             self.grad_bf16_buf = None                        # ... and then so does every plan: the optimizer reads ONE buffer
             for other in self.plans.values():
-                if getattr(other, "_g16_ref", None) is not None:
+                if other._g16_ref is not None:
                     other.grad_bf16(None)
 
     def _room_for(self, nbytes: int) -> bool:
@@ -360,7 +360,7 @@ class _Engine:
         (the criterion tail's den / num start afresh too); otherwise the views of the parameters that take a fresh gradient are zeroed
         in one launch and the plan runs its accumulate form."""
         if not self.accumulate:
-            if getattr(plan, "_acc", False):
+            if plan._acc:
                 plan.accumulate_grads(False)
             return
         fresh = []
@@ -670,7 +670,7 @@ class M2FNet(nn.Module):
             eng.grad_bf16_buf = None
         else:
             for pl in list(eng.plans.values()):             # (plans left in the accumulate form by a data-parallel micro-batch group)
-                if getattr(pl, "_acc", False):
+                if pl._acc:
                     pl.accumulate_grads(False)
         if on and eng.grad_bf16_buf is None and eng.precision == runtime.BF16:
             eng.grad_bf16_buf = torch.zeros(eng.flat.numel(), dtype=torch.bfloat16, device=eng.flat.device)
@@ -704,7 +704,7 @@ class M2FNet(nn.Module):
             self._engine.accumulate = on
             if not on:                                      # every plan back in the overwrite form now, whatever runs next
                 for pl in list(self._engine.plans.values()):
-                    if getattr(pl, "_acc", False):
+                    if pl._acc:
                         pl.accumulate_grads(False)
 
     def grad_accumulation(self) -> bool:

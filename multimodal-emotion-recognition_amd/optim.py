@@ -557,13 +557,13 @@ class FusedAdam(torch.optim.Optimizer):
             return False
         if self._grouped:
             return self._prepare_fused_grouped(eng, plan)
-        if getattr(plan, "_fused_bad", False):
+        if plan._fused_bad:
             return False
         if self._hyper is None:
             self._hyper = torch.zeros(8, dtype=torch.float32, device=eng.flat.device)
         key = (self._m.data_ptr(), self._v.data_ptr(), eng.flat.data_ptr(), eng.wshadow.data_ptr(), self._hyper.data_ptr(),
                self.grad_scale.data_ptr() if self.grad_scale is not None else 0)
-        if getattr(plan, "_fused_key", None) != key:
+        if plan._fused_key != key:
             try:
                 eng.ensure_grad()
                 plan.fused_adam_setup(eng.flat, self._m, self._v, eng.wshadow, self._hyper, self.grad_scale)
@@ -587,9 +587,9 @@ class FusedAdam(torch.optim.Optimizer):
         tg = self.tensor_group_map()
         key = ("grouped", tuple(tg), self._m.data_ptr(), self._v.data_ptr(), eng.flat.data_ptr(), eng.wshadow.data_ptr(),
                self._hyper_table(eng).data_ptr(), self.grad_scale.data_ptr() if self.grad_scale is not None else 0)
-        if getattr(plan, "_fused_bad_key", None) == key:
+        if plan._fused_bad_key == key:
             return False
-        if getattr(plan, "_fused_key", None) != key:
+        if plan._fused_key != key:
             try:
                 eng.ensure_grad()
                 plan.fused_adam_setup_grouped(eng.flat, self._m, self._v, eng.wshadow, self._table, tg, self.grad_scale)

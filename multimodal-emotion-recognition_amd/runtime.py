@@ -400,6 +400,19 @@ class Plan:
         self.in_B, self.in_L = B, L
         self.version = 0          # bumped by every forward; backward checks it still owns the activations
         self._pending = None      # weak reference to the autograd node whose backward still needs this plan's activations
+        self._acc = False         # the accumulate form is on (accumulate_grads); it stays on across a rebuild, as the C side keeps it
+        self._disarm()
+
+    def _disarm(self) -> None:
+        """What the optimizer and the engine armed on this plan, as the C side holds it after create and after a rebuild (backward_outputs):
+        nothing.  The fused optimizer (optim.FusedAdam.prepare_fused) and the bf16 gradients (model._Engine._arm_grad_bf16) set up again."""
+        self._fused_key = None        # the optimizer buffers the in-launch Adam form was set up with (None: not armed)
+        self._fused_refs = None       # ... kept alive: the plan holds raw pointers
+        self._fused_err = None        # ... the last refused setup's message,
+        self._fused_bad = False       # ... for good (ungrouped optimizer: another table form, ...),
+        self._fused_bad_key = None    # ... or for this key (grouped optimizer)
+        self._g16_ref = None          # the bf16 gradient buffer the steps fill (None: fp32 gradients)
+        self._g16_bad = False         # ... this plan cannot (fp32 mode, another table form)
 
     def _unpack(self, rows: torch.Tensor) -> torch.Tensor:
         """[T, C] rows of a packed plan -> the padded [b, l, C] surface of the last batch (pad slots = 0)."""
@@ -641,7 +654,7 @@ class Plan:
         the plan cannot: fp32 mode, another table form, per-plan shadows)."""
         check(lib().m2f_plan_fused_adam_setup(self._h(), params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param_shadow.data_ptr(),
                                               hyper.data_ptr(), ptr(grad_scale)), "m2f_plan_fused_adam_setup")
-        self._fused_refs = (params, exp_avg, exp_avg_sq, param_shadow, hyper, grad_scale)      # (the plan holds raw pointers)
+        self._fused_refs = (params, exp_avg, exp_avg_sq, param_shadow, hyper, grad_scale)
 
     def grad_bf16(self, buf16) -> None:
         """m2f_plan_grad_bf16: the NEXT steps leave every gradient, rounded once, in `buf16` (bf16 [n_params]; None: back to fp32)."""
@@ -653,7 +666,7 @@ class Plan:
         the gradient buffer (on) / overwrite them (off).  Raises for a plan without a gradient buffer, with fused Adam on or bf16
         gradients armed."""
         on = bool(on)
-        if on == getattr(self, "_acc", False):
+        if on == self._acc:
             return
         check(lib().m2f_plan_accumulate_grads(self._h(), int(on)), "m2f_plan_accumulate_grads")
         self._acc = on
@@ -673,12 +686,12 @@ class Plan:
 
     def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
         """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |
-        IN_AUDIO) and / or the parameter gradients.  A change rebuilds the launch lists and drops the captured graphs and the bf16-gradient
-        arming (the engine re-arms plans that compute parameter gradients)."""
+        IN_AUDIO) and / or the parameter gradients.  A change rebuilds the launch lists and drops the captured graphs, the fused-optimizer
+        setup and the bf16-gradient arming (the optimizer sets up again at its next step, the engine re-arms plans that compute parameter
+        gradients); the accumulate form stays as it is."""
         check(lib().m2f_plan_backward_outputs(self._h(), int(input_mask), int(bool(param_grads))), "m2f_plan_backward_outputs")
         if (int(input_mask), bool(param_grads)) != (self.input_mask, self.param_grads):
-            self._g16_ref = None
-            self._g16_bad = False
+            self._disarm()
         self.input_mask, self.param_grads = int(input_mask), bool(param_grads)
 
     def input_grad(self, which: int, dst=None, valid=None, shape=None) -> torch.Tensor:

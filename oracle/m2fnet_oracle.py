@@ -106,7 +106,7 @@ class Bf16Rounding:
                 gated dgrad epilogue), ...
       dgrad_w   ... and W from the transposed parameter shadow W^T [cols][pad8(rows)] (the NN dgrad rerouted through it).
       wgrad_dy  dW = bf16(dY)^T . bf16(X): the weight-gradient table launch reads the row-major shadows (gemm_p8.h,
-      wgrad_x   gemm_ring.h TABLE form); the [T, C] criterion gradient is cast to 8-column bf16 rows in front of it (plan.hip:949).
+      wgrad_x   gemm_ring.h TABLE form); the [T, C] criterion gradient is cast to 8-column bf16 rows in front of it (plan_build.hip, build_wgrad_table).
       bias_dy   bias gradient = column sum of bf16(dY): the table forms sum the bf16 fragments they stage (gemm_p8.h:395,
                 gemm_ring.h:663), the bf16-source grouped form its staged bf16 tile (gemm.hip:829,914).  Finding: the
                 fp32-SOURCE grouped form sums the fp32 values before it rounds them (gemm.hip:185-191, a contract
@@ -118,7 +118,7 @@ class Bf16Rounding:
                 forward and its input gradient are not rounded (its weight gradient stays in the table launch).
       The criterion gradient itself is fp32 (m2f_ce_kernel) and is rounded only where it enters these products.
 
-    Dialogue attention, L <= 64 (attention.hip, AttnBatch::bf16_math = 63 in bf16 mode, plan.hip:824-826):
+    Dialogue attention, L <= 64 (attention.hip, AttnBatch::bf16_math = 63 in bf16 mode, plan_build.hip, to_launches):
       bit 1 (attention.hip:129,337,388): Q K^T and dO V^T on the bf16 MFMA - both operands rounded on the way in
                 (slab8_bf16, attention.hip:42-50), whatever the slabs hold; the scale 1/sqrt(hd) is applied to the fp32
                 product afterwards (attention.hip:113,151: s * scale; backward: p * (dp - delta) * scale).
@@ -133,7 +133,7 @@ class Bf16Rounding:
       rounding (everywhere it is rounded); attn = False switches all of them (M2F_ATTN_BF16=0).  The mode is decided per
       attention problem from its own head dim (a merged launch takes the widest head dim for attn_bwd_fast: it only
       matters at Lp = 64 with head dims 113..128 in one launch and others narrower, which no test case has).
-    Plans with L > 64 (attention_dlong.hip; picked by the plan's L, plan.hip:1329-1330, packed or not): no attention
+    Plans with L > 64 (attention_dlong.hip; picked by the plan's L, plan.hip, run_launches, packed or not): no attention
     rounding, those kernels read fp32 operands.  The L here is the batch's L (the shape bucket rounds up to a multiple of 16,
     which does not cross 64).
     LayerNorm, the residual stream, the criterion and Adam: fp32, no rounding.

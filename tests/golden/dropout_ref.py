@@ -3,7 +3,7 @@
 The mask of a dropout site is a pure integer function of (rng state, site, element index), so the host can say what it IS:
 plain numpy uint32 arithmetic, vectorised.  On top of the three hash functions this file states the rules the kernels and the plan
 builder follow - the threshold / scale of a probability, the element index of the row-wise kernels and of the attention kernels,
-the order in which csrc/plan.hip hands out sites - and turns a plan's token layout into masks in the oracle's layout, so that
+the order in which csrc/plan_build.hip hands out sites - and turns a plan's token layout into masks in the oracle's layout, so that
 oracle/m2fnet_oracle.py can run with the device's own masks (its `drop` hook).  Nothing here is imported by the product.
 """
 from __future__ import annotations
@@ -54,7 +54,7 @@ def keep(key, idx, thresh):
 
 def thresh_scale(p):
     """(thresh, scale) of a dropout probability: thresh = min(2^32 - 1, floor(p 2^32)) with p the fp32 value the C ABI receives,
-    scale = fp32(1 / (1 - p)) in fp32 arithmetic (csrc/plan.hip: drop_thresh / drop_scale, drop_params)."""
+    scale = fp32(1 / (1 - p)) in fp32 arithmetic (csrc/plan.hip: drop_thresh / drop_scale; csrc/entry_kernels.hip: drop_params)."""
     pf = np.float32(p)
     thresh = int(min(4294967295.0, np.floor(float(pf) * 4294967296.0)))
     with np.errstate(divide="ignore"):
@@ -94,7 +94,7 @@ def _sec(cfg, name):
 
 
 def site_map(cfg):
-    """The dropout sites of a train plan of the reference-style model config `cfg`, by name, in the order csrc/plan.hip's
+    """The dropout sites of a train plan of the reference-style model config `cfg`, by name, in the order csrc/plan_build.hip's
     Builder::site() hands them out (from 1): audio branch then text branch - per encoder stack and layer `attn, dropout1, ff,
     dropout2`, after the last stack `pre_proj`, then `post_proj` -, per fusion layer `attn, out`, then the classifier's one
     dropout.  The names are the ones oracle/m2fnet_oracle.py passes to its `drop` hook."""

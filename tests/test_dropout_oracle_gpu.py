@@ -1,7 +1,7 @@
 """Train-mode plans with dropout ON against the float64 oracle run under the device's own masks.
 
 A train plan draws its masks from (engine.rng, site, element index); tests/golden/dropout_ref.py reproduces that function on the
-host, names the sites in the order csrc/plan.hip numbers them and lays the masks out as the oracle sees the batch, and
+host, names the sites in the order csrc/plan_build.hip numbers them and lays the masks out as the oracle sees the batch, and
 oracle/m2fnet_oracle.py applies them through its `drop` hook where the reference applies its dropouts.  So the dropout-on forward,
 loss and EVERY parameter gradient meet an independent reference: a site indexed by the leading dimension, packed and padded plans
 indexing differently, a wrong 1 / (1 - p) at one site, two sites sharing a key, a dropout on the wrong side of a residual, the

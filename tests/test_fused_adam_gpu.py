@@ -7,7 +7,9 @@ is BIT FOR BIT against the two-launch path (m2f_step, then m2f_adam_step_shadowe
   * with the gradients divided by a device-side denominator (the data-parallel / bench form of the step: normalise = 0);
   * a learning-rate change between steps reaches the captured graph (the step-dependent factors live in device memory);
   * a second optimizer taking over the same model between captured steps is the one the replayed graph applies;
-  * fp32 models fall back to the optimizer's own kernel without being asked."""
+  * fp32 models fall back to the optimizer's own kernel without being asked;
+  * a rebuild of the plan's launch lists (m2f_plan_backward_outputs) between captured steps: the same optimizer sets the plan up again and the
+    engine re-arms the bf16 gradients, bit for bit the run that never rebuilt."""
 import pytest
 import torch
 
@@ -190,3 +192,64 @@ def test_optimizer_reads_the_bf16_gradients_of_the_step():
     assert not m_g.set_grad_bf16(False)
     m32 = _model(cfg, "fp32")
     assert not m32.set_grad_bf16(True)                               # fp32 models keep fp32 gradients
+
+
+def _rebuild(m):
+    """The launch lists of the model's one plan rebuilt in place, there and back (m2f_plan_backward_outputs): input gradients of both
+    modalities on, then the default again.  Every captured graph and whatever was armed on the plan goes with the old lists."""
+    torch.cuda.synchronize()
+    plan = next(iter(m.engine().plans.values()))
+    plan.backward_outputs(3, True)
+    plan.backward_outputs(0, True)
+    return plan
+
+
+def test_fused_optimizer_survives_a_plan_rebuild():
+    """An eager warm-up and three captured fused steps, a rebuild of the launch lists, then with the same optimizer the eager step the
+    rebuild asks for and three captured ones: no error, and parameters, both moments and the losses are bit for bit those of a model that
+    never rebuilt - with the in-launch form armed again, not the two-launch fallback."""
+    cfg, B, L, lengths, kind = synth.CASES["tiny_ragged"]
+    batch = [t.cuda() for t in synth.make_inputs(cfg, B, L, lengths, kind)]
+
+    def run(rebuild):
+        m = _model(cfg)
+        opt = FusedAdam(m, lr=1e-3, weight_decay=0.01)
+        losses = []
+        for i in range(8):
+            if rebuild and i == 4:
+                _rebuild(m)
+            losses.append(float(m.train_step(*batch, use_graph=True, optimizer=opt)))
+        torch.cuda.synchronize()
+        plan = next(iter(m.engine().plans.values()))
+        assert plan._fused_key is not None, plan._fused_err
+        return losses, m.engine().flat.detach().clone(), opt._m.clone(), opt._v.clone()
+    a, b = run(True), run(False)
+    assert a[0] == b[0], (a[0], b[0])
+    for k, x, y in zip(("p", "m", "v"), a[1:], b[1:]):
+        assert torch.equal(x, y), (k, float((x - y).abs().max()))
+
+
+def test_bf16_gradients_are_rearmed_after_a_plan_rebuild():
+    """M2FNet.set_grad_bf16, two steps, a rebuild of the launch lists: the engine arms the plan again at the next step, and that step
+    leaves the bf16 gradient buffer of a model that never rebuilt, bit for bit (the buffer is cleared first: nothing stale passes)."""
+    cfg, B, L, lengths, kind = synth.CASES["tiny_ragged"]
+    batch = [t.cuda() for t in synth.make_inputs(cfg, B, L, lengths, kind)]
+
+    def run(rebuild):
+        m = _model(cfg)
+        assert m.set_grad_bf16(True)
+        for _ in range(2):
+            m.train_step(*batch, use_graph=True)
+        if rebuild:
+            _rebuild(m)
+        eng = m.engine()
+        torch.cuda.synchronize()
+        eng.grad_bf16_buf.zero_()
+        m.train_step(*batch, use_graph=True)
+        torch.cuda.synchronize()
+        plan = next(iter(eng.plans.values()))
+        assert plan._g16_ref is eng.grad_bf16_buf
+        return eng.grad_bf16_buf.clone()
+    a, b = run(True), run(False)
+    assert bool((b != 0).any())
+    assert torch.equal(a.view(torch.int16), b.view(torch.int16))

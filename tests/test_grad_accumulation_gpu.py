@@ -145,6 +145,43 @@ def test_switch_off_restores_the_overwrite_form_for_the_optimizer_step(precision
     assert torch.equal(m_acc.loss_terms(), m_ref.loss_terms())
 
 
+def test_accumulate_form_stays_on_across_a_plan_rebuild():
+    """A rebuild of a plan's launch lists (m2f_plan_backward_outputs, there and back) while the plan is in the accumulate form: the form
+    stays on and its lists follow the rebuild - two micro-batches accumulated afterwards, captured step included, leave bit for bit the
+    gradients and the criterion tail of a plan that never rebuilt."""
+    cfg, B, L, lengths, kind = synth.CASES["tiny_ragged"]
+    mbs = [[t.cuda() for t in synth.make_inputs(cfg, B, L, lengths, kind, seed=s)] for s in (11, 12)]
+
+    def run(rebuild):
+        m = M2FNet(cfg, precision="bf16")
+        m.load_state_dict(synth.make_state_dict(cfg))
+        m = m.to("cuda").train()
+        m.set_grad_accumulation(True)
+        m.zero_grad(set_to_none=True)
+        for mb in mbs + mbs:                                 # (the first one overwrites; the accumulate form is captured after it)
+            m.train_step(*mb, use_graph=True)
+        torch.cuda.synchronize()
+        plan = next(iter(m.engine().plans.values()))
+        assert plan._acc
+        if rebuild:
+            plan.backward_outputs(3, True)
+            plan.backward_outputs(0, True)
+            assert plan._acc
+        out = []
+        for _ in range(2):                                   # (after a rebuild: one eager round, one captured)
+            m.zero_grad(set_to_none=False)                   # the engine's views, zeroed: both micro-batches accumulate
+            for mb in mbs:
+                m.train_step(*mb, use_graph=True)
+            torch.cuda.synchronize()
+            out.append((_grads(m), _tail(m)))
+        return out
+    for (ga, ta), (gb, tb) in zip(run(True), run(False)):
+        assert torch.equal(ta, tb), (ta, tb)
+        for k in ga:
+            assert torch.equal(ga[k], gb[k]), (k, (ga[k] - gb[k]).abs().max().item())
+        assert any(bool((g != 0).any()) for g in ga.values())
+
+
 def _autograd_grads(m, mb, crit):
     t, a, kp, em = mb
     loss = crit(m(t, a, kp).permute(0, 2, 1), em)

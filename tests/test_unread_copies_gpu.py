@@ -1,4 +1,4 @@
-"""bf16-mode plans do not write activation copies nobody reads (csrc/plan.hip::mark_unread_fp32; include/m2fnet_hip.h,
+"""bf16-mode plans do not write activation copies nobody reads (csrc/plan_build.hip::mark_unread_fp32; include/m2fnet_hip.h,
 m2f_plan_skipped_copies): the fp32 copy of a QKV projection, an attention output, an attention / FFN-hidden gradient, the
 bf16 shadow of a result that is only a residual term or a LayerNorm input.  The unwritten buffers are filled with NaNs when the
 plan is built, so a reader the plan builder does not know about would poison the loss and every gradient.  Checked here: the step is bit-for-bit the step that writes every
