@@ -59,7 +59,8 @@ enum {
     M2F_BUF_STREAM_TABLE = 15,  /* int32 [S, ceil(C / page_rows)]  paged stream plans, input: the page of each run of page_rows cache rows of a slot (a chunk plan: its parent's) */
     M2F_BUF_TEACHER = 16,       /* float [B*L, cls_out]  train plans, input of the distillation criterion: the teacher's logits, token rows as M2F_BUF_LOGITS */
     M2F_BUF_DISTILL = 17,       /* float [2]  train plans, input of the distillation criterion: alpha, tau (read on the device at every step) */
-    M2F_BUF_COUNT = 18
+    M2F_BUF_STREAM_ATTN = 18,   /* float [sites][S][H_site][C]  stream plans with m2f_plan_stream_attention on: the caller's buffer (NULL: off) */
+    M2F_BUF_COUNT = 19
 };
 
 const char* m2f_last_error(void);
@@ -144,6 +145,21 @@ int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
  * steps, never between a forward and its backward.  m2f_plan_get_attention_band reads the setting back (-1 = unlimited). */
 int m2f_plan_attention_band(m2f_plan* plan, int past, int future);
 int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
+/* ATTENTION MAPS: what nn.MultiheadAttention(need_weights=True) returns - the reference's fusion module computes them at every layer
+ * and throws them away (src/model.py:14) - read out of the pre-dropout probabilities that every attention site of a padded or packed
+ * plan saves at every forward (train and eval plans alike; csrc/attention_weights.hip).  m2f_plan_attention_sites: the plan's sites in
+ * state_dict order - kind 0 = audio_encoders.{index}.layers.{layer}.self_attn, 1 = text_encoders.{index}.layers.{layer}.self_attn,
+ * 2 = fusion_layers.{index}.multihead_attention (layer 0) - with their head count and head dim, up to max_sites of them (any array may
+ * be NULL); returns their number.  m2f_plan_attention_weights: the maps of the n_sites listed sites (indices into that list) of the
+ * LAST forward / step of the plan into out[i] (host array of device pointers, fp32): [B, H, L, L] (per_head) or [B, L, L] - the fp32 sum
+ * over h = 0 .. H - 1 in that order times (float)1 / H, torch's average_attn_weights - with the plan's own B and L; element (b, [h,] i, j)
+ * = P of query i, key j of dialogue b, exactly 0 where j is a padded key, where i or j lies behind the dialogue's end (packed plans)
+ * or where the plan's context band hides the pair.  Pad-query rows of padded plans hold their softmax numbers, as torch's do; a row
+ * that sees no key is zeros (torch: NaN).  Train plans with dropout: the PRE-dropout probabilities (torch returns them post-dropout).
+ * Eager, one launch per 64 sites, outside every captured graph; nothing is recaptured and no result of the plan changes.  Stream and
+ * chunk plans are refused.  No counterpart in the reference beyond the discarded return value. */
+int m2f_plan_attention_sites(m2f_plan* plan, int* kind, int* index, int* layer, int* H, int* hd, int max_sites);
+int m2f_plan_attention_weights(m2f_plan* plan, const int* sites, int n_sites, int per_head, float* const* out, m2f_stream_t stream);
 /* STREAM plan: online inference under a causal context band (past, 0).  S stream slots, each one live dialogue; a step takes ONE new
  * utterance per active slot (row s of M2F_BUF_TEXT / M2F_BUF_AUDIO, both [S, pad8(d)]; M2F_BUF_STREAM_ACTIVE [S]) and leaves its logits
  * in row s of M2F_BUF_LOGITS [S, cls_out].  Under such a band the K and V rows of an utterance at every attention site depend on
@@ -212,6 +228,20 @@ int m2f_stream_gather(m2f_plan* plan, int n, const int32_t* slots, const int32_t
                       int64_t packed_elems, m2f_stream_t stream);
 int m2f_stream_scatter(m2f_plan* plan, int n, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
                        int64_t packed_elems, m2f_stream_t stream);
+/* ATTENTION ROWS OF A STREAM: which cached utterances did the step's prediction use.  m2f_plan_stream_attention(plan, buffer, elems):
+ * from the next step on every attention launch of m2f_stream_step runs the weights-emitting form of its kernel (csrc/attention_stream.hip)
+ * and leaves each (slot, head)'s row of probabilities in `buffer` - caller-owned like every buffer a plan uses, fp32, 16-byte aligned,
+ * elems >= m2f_stream_attention_elems(plan) = sum over sites of S * H * C - laid out [site in m2f_plan_attention_sites order][S][H][C],
+ * column t = the t-th oldest live utterance of the slot (the last live column: the one that has just arrived), zeros behind the live
+ * count and in the rows of inactive slots.  buffer = NULL: off again, the kernels the step always ran.  A change drops the captured step
+ * once (as m2f_plan_distill does on train plans); the step stays one replayed graph, logits and cache rows keep their bits, and
+ * M2F_BUF_STREAM_ATTN reports the buffer.  17.8 MB at C3, S = 64, C = 512.  The chunk kernel has no weights form: m2f_stream_prefill
+ * leaves the buffer as it was.  m2f_stream_attention: the rows of the LAST step for the listed sites into out[i] (host array of
+ * device pointers) as [S, H, C] (per_head) or [S, C] by the head-average rule of m2f_plan_attention_weights; eager, one launch per 64
+ * sites, outside the step graph.  Stream plans only (a chunk plan is refused). */
+int64_t m2f_stream_attention_elems(m2f_plan* plan);
+int m2f_plan_stream_attention(m2f_plan* plan, float* buffer, int64_t buffer_elems);
+int m2f_stream_attention(m2f_plan* plan, const int* sites, int n_sites, int per_head, float* const* out, m2f_stream_t stream);
 /* Fused train-step body of src/train.py:228-230 (forward + criterion + backward) with the dropout RNG
  * advanced on the device; use_graph=1 captures the launch list into a hipGraph once and replays it. */
 int m2f_step(m2f_plan* plan, float label_smoothing, int use_class_weights, int normalise, int use_graph,
@@ -628,6 +658,13 @@ int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, cons
                       int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream);
 int64_t m2f_attention_probs_elems(int B, int H, int L);
+/* The attention map of ONE site out of the probs that m2f_attention_fwd[_band] / m2f_attention_varlen_fwd[_band] wrote for the same
+ * B, L, H (csrc/attention_weights.hip; m2f_plan_attention_weights above has the rule): out = fp32 [B, H, L, L] (per_head) or [B, L, L]
+ * (heads summed in order, times (float)1 / H).  key_pad (padded rows, [B, L]) or cu (packed rows, int32 [B + 1]) or neither (every key
+ * valid); past / future: the band the forward ran under (negative = unlimited).  Elements outside the dialogue, at padded keys or
+ * hidden by the band are written as 0 and never read from probs.  1 <= L <= 512. */
+int m2f_attention_weights(int B, int L, int H, const float* probs, const uint8_t* key_pad, const int32_t* cu, int past, int future,
+                          int per_head, float* out, m2f_stream_t stream);
 /* Streaming attention, one launch (csrc/attention_stream.hip): slot s of S takes ONE new utterance - rows s of q / k / v [S, H*hd] fp32,
  * column slices with their leading dimensions - against the rows the slot has cached.  count[s] (device int32) = utterances cached so far,
  * active[s] (device uint8).  An active slot: the new K / V rows are stored at row count % C (ring != 0) or row count (ring == 0;
@@ -657,6 +694,16 @@ int64_t m2f_attention_stream_pool_elems(int n_pages, int H, int hd, int page_row
 int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
                                const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, m2f_stream_t stream);
+/* The weights-emitting form of the step launch (the same kernel body with one more template flag; same out, same cache rows, same bits):
+ * it also stores each (slot, head)'s row of attention probabilities to weights, fp32 [S, H, C], in LOGICAL order - column t is the
+ * t-th oldest live utterance of the slot, the last live column the utterance that has just arrived (a ring: utterance u sits in row
+ * u % C, undone here; paged: the page table never enters) - zeros behind the live count min(count + 1, C) and for inactive slots. */
+int m2f_attention_stream_weights(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                 void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
+                                 int bf16, float* weights, m2f_stream_t stream);
+int m2f_attention_stream_weights_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                       void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                       const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, m2f_stream_t stream);
 int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                      void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
                                      const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream);

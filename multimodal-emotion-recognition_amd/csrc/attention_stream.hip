@@ -28,14 +28,21 @@
 // one text, so the paged form gives the dense form's bits.  Behind PAGED stand only the fetch of the slot's page ids into LDS
 // (attn_stream_rows.h: the entries of pages that hold a live row or take the new one, e < ceil(min(len + 1, C) / R)), the base pointer
 // of a head's rows and the offset of row j.
+//
+// WEIGHTS (a third flag of the body, its own instantiations; the others are the text they were): behind the softmax the wave also stores
+// its row of probabilities sc[j] * inv - the pre-normalised exponentials times the reciprocal the output row is scaled by - to
+// ww.w[problem][s][h][0 .. C) in LOGICAL order: column t is the t-th oldest live utterance, the last live column the utterance that
+// has just arrived (a ring: utterance u sits in row u % C, which is undone here; the page table never enters: the order is logical).
+// Columns behind the live count are zeros, an inactive slot gets a row of zeros.  Ordinary per-lane vector stores, 64 consecutive
+// floats per instruction.
 #include "common.h"
 #include "ops.h"
 #include "attn_stream_rows.h"
 
 namespace {
 
-template <bool BF16, bool PAGED>
-__device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg) {
+template <bool BF16, bool PAGED, bool WEIGHTS>
+__device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const AttnStreamWeights& ww) {
     typedef Row<BF16> R;
     typedef typename R::elem_t elem_t;
     constexpr int EPL = R::EPL;
@@ -61,6 +68,10 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
         for (int i = lane; i < hd; i += 64) {
             orow[i] = 0.f;
             if (orow16) orow16[i] = 0;
+        }
+        if constexpr (WEIGHTS) {
+            float* wrow = ww.w[pi] + ((size_t)s * P.H + h) * (size_t)C;
+            for (int t = lane; t < C; t += 64) wrow[t] = 0.f;
         }
         return;
     }
@@ -153,6 +164,11 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     sum = m2f_wave_sum(sum);
     const float inv = 1.0f / sum;                 // (sum >= 1: the row of the maximum contributes exp(0))
     __syncthreads();
+    if constexpr (WEIGHTS) {                      // the row of probabilities, oldest live utterance first
+        float* wrow = ww.w[pi] + ((size_t)s * P.H + h) * (size_t)C;
+        const int first = n_old + 1 - nslots;     // utterance index of column 0 (plain cache: 0, row t holds utterance t)
+        for (int t = lane; t < C; t += 64) wrow[t] = t < nslots ? sc[ab.ring ? (first + t) % C : t] * inv : 0.f;
+    }
 
     // ---- pass 2: P V ---------------------------------------------------------------------------------------------------------------
     float acc[EPL];
@@ -198,11 +214,19 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
 
 template <bool BF16>
 __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
-    attn_stream_body<BF16, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0});
+    attn_stream_body<BF16, false, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, AttnStreamWeights{{nullptr}});
 }
 template <bool BF16>
 __global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
-    attn_stream_body<BF16, true>(ab, pg);
+    attn_stream_body<BF16, true, false>(ab, pg, AttnStreamWeights{{nullptr}});
+}
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_weights_kernel(const AttnStreamBatch ab, const AttnStreamWeights ww) {
+    attn_stream_body<BF16, false, true>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, ww);
+}
+template <bool BF16>
+__global__ __launch_bounds__(64) void m2f_attn_stream_paged_weights_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const AttnStreamWeights ww) {
+    attn_stream_body<BF16, true, true>(ab, pg, ww);
 }
 
 // len[s] += active[s]: the one launch that closes a step
@@ -250,10 +274,23 @@ int m2f_attn_stream_prepare(AttnStreamBatch& ab, AttnStreamPaging* pg, int* maxW
     return blocks;
 }
 
-hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream) {
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream, const AttnStreamWeights* weights) {
     AttnStreamPaging pg = paging ? *paging : AttnStreamPaging{nullptr, 0, 0, 0, 0};
     const int blocks = ab.active ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, nullptr) : -1;
     if (blocks < 0) return hipErrorInvalidValue;
+    if (weights) {                                // the weights-emitting form: a row of [S][H][C] floats per problem
+        const AttnStreamWeights ww = *weights;
+        for (int i = 0; i < ab.count; ++i)
+            if (!ww.w[i] || (reinterpret_cast<uintptr_t>(ww.w[i]) & 3)) return hipErrorInvalidValue;
+        if (paging) {
+            if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
+            else hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
+        } else {
+            if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_weights_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, ww);
+            else hipLaunchKernelGGL(m2f_attn_stream_weights_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, ww);
+        }
+        return hipGetLastError();
+    }
     if (paging) {
         if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg);
         else hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg);

@@ -22,6 +22,8 @@ stream = len(sys.argv) > 2 and sys.argv[1] == "--stream"
 stream_chunk = len(sys.argv) > 2 and sys.argv[1] == "--stream-chunk"
 # --stream-cache <remarks>: the snapshot / restore kernels of the stream caches (stream_cache.hip) - the same rule (a lane's vectors in flight)
 stream_cache = len(sys.argv) > 2 and sys.argv[1] == "--stream-cache"
+# --attn-weights <remarks>: the attention-map gather (attention_weights.hip) - the same rule (a tile's accumulators and visibility flags)
+attn_weights = len(sys.argv) > 2 and sys.argv[1] == "--attn-weights"
 # --w2v <remarks>: the wav2vec2 front end (audio_conv.hip) - the same rule for its kernels (the positional convolution's accumulators)
 w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
 # --mel <remarks>: the audio_mel encoder (mel_resnet.hip) - the same rule for its kernels (the convolution's accumulators, the STFT sums)
@@ -37,7 +39,7 @@ metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
 # and for the distillation criterion kernel of the same file (m2f_ce_distill_kernel; its own list below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
-path = sys.argv[2] if (ring or dlong or stream or stream_chunk or stream_cache or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
+path = sys.argv[2] if (ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -71,8 +73,8 @@ if adam:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
               f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
     sys.exit(1 if bad else 0)
-if dlong or stream or stream_chunk or stream_cache or w2v or mel or gradnorm or tstats or metrics:
-    tag = "m2f_attn_dlong" if dlong else "m2f_attn_stream" if stream else "m2f_attn_stream_chunk" if stream_chunk else "m2f_stream_cache_kernel" if stream_cache else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_tstats_" if tstats else "m2f_eval_"
+if dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics:
+    tag = "m2f_attn_dlong" if dlong else "m2f_attn_stream" if stream else "m2f_attn_stream_chunk" if stream_chunk else "m2f_stream_cache_kernel" if stream_cache else "m2f_attn_weight" if attn_weights else "m2f_w2v_" if w2v else "m2f_mel_" if mel else "m2f_gradnorm_" if gradnorm else "m2f_tstats_" if tstats else "m2f_eval_"
     kernels = [r for r in rows if tag in r["name"]]
     if not kernels:
         sys.exit(f"check_spills: no {tag} kernel found in {path} - did the remark format change?")

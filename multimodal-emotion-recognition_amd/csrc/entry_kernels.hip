@@ -291,6 +291,34 @@ int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, co
     M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream)));
     return 0;
 }
+/* ... and their weights-emitting forms: the same launch, plus the rows of probabilities into weights [S, H, C] */
+static int stream_weights_ok(const char* who, const float* weights, AttnStreamWeights& ww) {
+    if (!weights || (reinterpret_cast<uintptr_t>(weights) & 3)) return fail(std::string(who) + ": weights must be a 4-byte aligned device buffer of S * H * C floats");
+    memset(&ww, 0, sizeof(ww));
+    ww.w[0] = const_cast<float*>(weights);
+    return 0;
+}
+int m2f_attention_stream_weights(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                 void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
+                                 int bf16, float* weights, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    AttnStreamWeights ww;
+    if (int r = stream_attn_fill("m2f_attention_stream_weights", sb, nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
+    if (int r = stream_weights_ok("m2f_attention_stream_weights", weights, ww)) return r;
+    M2F_HIP(m2f_launch_attn_stream(sb, nullptr, static_cast<hipStream_t>(stream), &ww));
+    return 0;
+}
+int m2f_attention_stream_weights_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                       void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                       const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, m2f_stream_t stream) {
+    AttnStreamBatch sb;
+    AttnStreamWeights ww;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_weights_paged", sb, &pg, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, active, out, ldo, bf16)) return r;
+    if (int r = stream_weights_ok("m2f_attention_stream_weights_paged", weights, ww)) return r;
+    M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream), &ww));
+    return 0;
+}
 int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                      void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
                                      const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream) {
@@ -354,6 +382,20 @@ int m2f_attention_stream_cache_scatter_paged(int S, int H, int hd, void* kpool, 
     const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
     return stream_cache_site("m2f_attention_stream_cache_scatter_paged", S, H, hd, kpool, vpool, C, bf16, &pg, n_entries, slots, lengths, row_offsets,
                              const_cast<void*>(packed), packed_elems, count, 1, stream);
+}
+
+int m2f_attention_weights(int B, int L, int H, const float* probs, const uint8_t* key_pad, const int32_t* cu, int past, int future,
+                          int per_head, float* out, m2f_stream_t stream) {
+    if (B < 1 || H < 1 || L < 1 || L > M2F_ATTN_DLONG_MAX_L) return fail("m2f_attention_weights: B, H >= 1 and 1 <= L <= 512 required");
+    if (!probs || !out) return fail("m2f_attention_weights: NULL argument");
+    if (cu && key_pad) return fail("m2f_attention_weights: at most one of cu (packed rows) and key_pad (padded rows) may be given");
+    AttnWeightsBatch wb;
+    memset(&wb, 0, sizeof(wb));
+    wb.count = 1; wb.site[0] = {probs, out, H, 1.0f / (float)H};
+    wb.B = B; wb.L = L; wb.per_head = per_head != 0; wb.key_pad = key_pad; wb.cu = cu;
+    m2f_attn_weights_set_band(wb, past, future);
+    M2F_HIP(m2f_launch_attn_weights(wb, static_cast<hipStream_t>(stream)));
+    return 0;
 }
 
 int64_t m2f_attention_probs_elems(int B, int H, int L) { return (int64_t)m2f_attn_probs_elems(B, H, L); }

@@ -241,6 +241,41 @@ bool m2f_attn_dlong_index_ok(int B, int H, int L);
 hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream);
 hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream);
 
+// Attention maps (attention_weights.hip): the saved P^T of up to 64 sites -> torch's need_weights layouts, ONE launch.  Site i: probs as
+// the forward launches above leave it ([B*H, Lp, Lp], P^T, pre-dropout), out = [B, H, L, L] (per_head) or [B, L, L] (the sequential fp32
+// sum over h = 0 .. H - 1, times inv_h = 1.0f / H computed on the host).  Element (b, [h,] i, j) is READ from probs only if i and j lie
+// inside the dialogue (cu: its cu[b+1] - cu[b] rows; key_pad: L), key j is not padded and the band (the two compares of
+// m2f_attn_band_bits, band_past / band_future stored + 1 as in AttnBatch) admits (i, j); every other element is written as 0 - the
+// long-dialogue forward leaves band-hidden block pairs and the tile rows behind a short dialogue as they were.
+#define M2F_ATTN_WEIGHTS_MAX_SITES 64
+struct AttnWeightsSite {
+    const float* probs;
+    float* out;
+    int H;
+    float inv_h;
+};
+struct AttnWeightsBatch {
+    int sb[M2F_ATTN_WEIGHTS_MAX_SITES];      // first workgroup of site i (INT_MAX for unused slots); filled by the launcher
+    AttnWeightsSite site[M2F_ATTN_WEIGHTS_MAX_SITES];
+    int count;
+    int B, L;
+    int per_head;
+    int band_past, band_future;              // stored + 1, 0 = unlimited (m2f_attn_weights_set_band)
+    int vec;                                 // filled by the launcher: 16-byte stores (L % 4 == 0, every out 16-byte aligned)
+    const uint8_t* key_pad;                  // [B, L], 1 = padded key (nullable: every key valid)
+    const int* cu;                           // packed layout (nullable): dialogue b holds cu[b+1] - cu[b] utterances; key_pad unused
+};
+inline void m2f_attn_weights_set_band(AttnWeightsBatch& wb, int past, int future) {
+    AttnBatch ab{};
+    m2f_attn_set_band(ab, past, future);
+    wb.band_past = ab.band_past; wb.band_future = ab.band_future;
+}
+hipError_t m2f_launch_attn_weights(AttnWeightsBatch& wb, hipStream_t stream);
+// ROWS mode, for the rows a stream's weights-emitting step stores: site i's probs = [B][H][L] (B = stream slots, L = capacity, already
+// in key order) -> out [B][H][L] (per_head: a copy) or [B][L] by the same head-average rule.  key_pad / cu / the band are not read:
+// the step kernel wrote every element.
+hipError_t m2f_launch_attn_weight_rows(AttnWeightsBatch& wb, hipStream_t stream);
+
 // Streaming attention (attention_stream.hip): one new utterance per stream slot against the slot's cached K / V rows.  q / k / v: the
 // new rows [S, H*hd] (fp32, column slices with a leading dimension, as AttnProblem carries them); kcache / vcache: the site's caches,
 // [S][H][C][pad4(hd)] fp32 or [S][H][C][pad8(hd)] bf16 (16-byte aligned).  len[s] = utterances cached so far (read, not advanced),
@@ -289,7 +324,11 @@ bool m2f_attn_stream_paging_ok(const AttnStreamBatch& ab, AttnStreamPaging& pg);
 // The launches; paging == nullptr: dense caches.  Both refuse (hipErrorInvalidValue, nothing launched) what m2f_attn_stream_prepare
 // refuses - a bad count, S, C > 512, hd > 128, a null or misaligned cache / pool, a paging that is not ok - and fill block_begin / bb[].
 int m2f_attn_stream_prepare(AttnStreamBatch& ab, AttnStreamPaging* pg, int* maxW);     // -> workgroups or -1; maxW: widest pad16(hd)
-hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream);
+// weights != nullptr: the weights-emitting form of the step kernel - problem i also stores its rows of probabilities to weights->w[i],
+// fp32 [S][H][C], column t = the t-th oldest live utterance of the slot (zeros behind the live count and for inactive slots).  Like the
+// paging it travels as a kernel argument of its own: a launch without it runs the kernels it always ran.
+struct AttnStreamWeights { float* w[M2F_ATTN_MAX_PROBLEMS]; };
+hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream, const AttnStreamWeights* weights = nullptr);
 hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPaging* paging, int T, const int* n_new, hipStream_t stream);
 // Snapshot / restore of those caches (stream_cache.hip has the packed layout): entry e of n_entries = the min(lengths[e], C) live
 // physical rows of slot slots[e], every listed site, K then V, packed at row row_offsets[e].  One launch for all sites and entries

@@ -39,6 +39,7 @@ struct Launch {
     GemmBatch gb;
     AttnBatch ab;
     AttnStreamBatch sb;                               // stream plans (m2f_plan_create_stream): what an OP_ATTN_FWD launch runs instead of `ab`
+    AttnStreamWeights sw{}; bool sw_on = false;       // ... and, with m2f_plan_stream_attention on, where each of its problems stores its rows of probabilities
     LnBatch lb;
     float* dptr = nullptr; int dT = 0, dd = 0, dld = 0; uint32_t dsite = 0;
     float* dptr2 = nullptr; uint32_t dsite2 = 0;      // OP_DROPOUT: a second buffer of the same shape in the same launch
@@ -112,6 +113,10 @@ struct GraphSlot { hipGraphExec_t exec = nullptr; GraphKey key{}; void reset() {
 // (SLOT_PREFILL: the chunk call of a chunk plan, m2f_stream_prefill)
 enum { SLOT_STEP = 0, SLOT_PART0, SLOT_PART1, SLOT_STEP_ACC, SLOT_EVAL, SLOT_STREAM, SLOT_PREFILL, SLOT_COUNT };
 
+// An attention site of the plan in state_dict order (m2f_plan_attention_sites): kind 0 = audio_encoders.{a}.layers.{b}.self_attn, 1 = text_encoders.{a}.layers.{b}.self_attn,
+// 2 = fusion_layers.{a}.multihead_attention; probs: the P^T its forward saves (m2f_plan_attention_weights reads it)
+struct AttnSiteRef { int kind, a, b, H, hd; const float* probs; };
+
 // Everything build_plan and its helpers write.  A rebuild is `built = Built{}` followed by build_plan: a field added here cannot survive one.
 struct Built {
     // bf16 mode: shadows of the workspace activations (same element index) and of the 2-D parameters (padded rows)
@@ -120,6 +125,7 @@ struct Built {
     std::vector<CastBatch> param_casts;  // bf16 mode, at the start of a forward: every 2-D parameter -> its W and W^T shadows ...
     std::vector<CastBatch> input_casts;  // ... and the two input staging buffers -> their activation shadows
     std::vector<Launch> fwd, bwd;
+    std::vector<AttnSiteRef> attn_sites;
     // deferred weight-gradient launches, run after the backward chain on the same stream.  (Overlapping them with the
     // chain on a second stream was measured SLOWER inside the captured graph: every fork costs the chain a 12-16 us
     // cross-queue gap and the chain's small GEMMs run ~2x longer next to a chip-filling launch; 2.85 -> 2.77 ms/step.)
@@ -217,6 +223,7 @@ struct m2f_plan {
     // plan of the same configuration; every attention site runs the chunk kernel (attention_stream_chunk.hip).  It owns no cache.
     m2f_plan* s_parent = nullptr; int s_chunk = 0;
     int* s_new = nullptr;            // device int32 [S]: utterances each slot takes in the next m2f_stream_prefill (M2F_BUF_STREAM_NEW)
+    float* s_attn = nullptr;         // m2f_plan_stream_attention: the caller's [sites][S][H][C] buffer the step's attention launches fill (M2F_BUF_STREAM_ATTN; null: off)
     uint32_t* rng = nullptr; bool use_dropout = false;
     uint32_t drop_thresh = 0; float drop_scale = 1.f;
     m2f::ParamMap pm;

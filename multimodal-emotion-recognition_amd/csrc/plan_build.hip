@@ -1060,6 +1060,12 @@ int build_plan(m2f_plan& P, char* ws_base) {
         bld.build_modality(1, P.pm.text, c.d_text, c.nhead_text, c.nlayers_text, c.ntrans_text,
                            static_cast<const float*>(P.bufs[M2F_BUF_TEXT]));
     bld.build_head();
+    for (int bi = 0; bi < 2; ++bi)
+        for (size_t e = 0; e < bld.mod[bi].L.size(); ++e)
+            for (size_t l = 0; l < bld.mod[bi].L[e].size(); ++l)
+                P.built.attn_sites.push_back({bi, (int)e, (int)l, bld.mod[bi].H, bld.mod[bi].d / bld.mod[bi].H, bld.mod[bi].L[e][l].probs});
+    for (size_t i = 0; i < bld.fam.size(); ++i)
+        P.built.attn_sites.push_back({2, (int)i, 0, c.nhead_fam, c.d_fam / c.nhead_fam, bld.fam[i].probs});
     // forward: merged branches, then fusion + classifier
     to_launches(P, merge_chains(bld.br_f[0], bld.br_f[1]), P.built.fwd);
     to_launches(P, bld.chain_f, P.built.fwd);

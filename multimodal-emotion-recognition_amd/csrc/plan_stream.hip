@@ -175,6 +175,74 @@ int m2f_stream_scatter(m2f_plan* plan, int n, const int32_t* slots, const int32_
     return stream_cache_move(plan, "m2f_stream_scatter", n, slots, lengths, row_offsets, const_cast<void*>(packed), packed_elems, 1, stream);
 }
 
+/* Attention rows of a stream plan's steps.  See include/m2fnet_hip.h, attention_stream.hip (the weights-emitting form) and attention_weights.hip. */
+int64_t m2f_stream_attention_elems(m2f_plan* plan) {
+    if (!plan || !plan->streaming || plan->s_parent) { fail("m2f_stream_attention_elems needs a stream plan (m2f_plan_create_stream)"); return -1; }
+    int64_t n = 0;
+    for (const AttnSiteRef& a : plan->built.attn_sites) n += (int64_t)plan->B * a.H * plan->s_cap;
+    return n;
+}
+int m2f_plan_stream_attention(m2f_plan* plan, float* buffer, int64_t buffer_elems) {
+    if (!plan) return fail("m2f_plan_stream_attention: NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.streaming || P.s_parent) return fail("m2f_plan_stream_attention needs a stream plan (m2f_plan_create_stream); the chunk kernel has no weights form");
+    if (buffer == P.s_attn) return 0;
+    if (buffer && ((reinterpret_cast<uintptr_t>(buffer) & 15) || buffer_elems < m2f_stream_attention_elems(plan)))
+        return fail("m2f_plan_stream_attention: the buffer must be 16-byte aligned and hold m2f_stream_attention_elems() floats");
+    // site k's rows start S * C * (heads of the sites before it) floats in; a launch's problem is found through the probabilities
+    // buffer the eval plan gave it (one per site)
+    std::vector<Launch>& fwd = P.built.fwd;
+    for (Launch& l : fwd) {
+        if (l.kind != OP_ATTN_FWD) continue;
+        memset(&l.sw, 0, sizeof(l.sw));
+        l.sw_on = false;
+        if (!buffer) continue;
+        for (int i = 0; i < l.sb.count; ++i) {
+            int64_t off = 0;
+            bool found = false;
+            for (const AttnSiteRef& a : P.built.attn_sites) {
+                if (a.probs == l.ab.pr[i].probs) { found = true; break; }
+                off += (int64_t)P.B * a.H * P.s_cap;
+            }
+            if (!found) return fail("m2f_plan_stream_attention: an attention launch holds a site the plan does not list");
+            l.sw.w[i] = buffer + off;
+        }
+        l.sw_on = true;
+    }
+    // the launches travel by value inside the captured step and run another kernel from here on: the capture goes, one eager step comes first
+    M2F_HIP(hipDeviceSynchronize());
+    P.graphs[SLOT_STREAM].reset();
+    ++P.generation;
+    P.warmed = false;
+    P.s_attn = buffer;
+    P.bufs[M2F_BUF_STREAM_ATTN] = buffer;
+    return 0;
+}
+int m2f_stream_attention(m2f_plan* plan, const int* sites, int n_sites, int per_head, float* const* out, m2f_stream_t stream) {
+    if (!plan) return fail("m2f_stream_attention: NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.streaming || P.s_parent) return fail("m2f_stream_attention needs a stream plan (m2f_plan_create_stream)");
+    if (!P.s_attn) return fail("m2f_stream_attention: attention rows are off (m2f_plan_stream_attention)");
+    if (n_sites < 0 || (n_sites > 0 && (!sites || !out))) return fail("m2f_stream_attention: NULL argument");
+    const std::vector<AttnSiteRef>& all = P.built.attn_sites;
+    std::vector<int64_t> offs(all.size() + 1, 0);
+    for (size_t k = 0; k < all.size(); ++k) offs[k + 1] = offs[k] + (int64_t)P.B * all[k].H * P.s_cap;
+    for (int i = 0; i < n_sites; ++i)
+        if (sites[i] < 0 || sites[i] >= (int)all.size() || !out[i]) return fail("m2f_stream_attention: a site outside the plan's list, or a NULL output");
+    for (int s0 = 0; s0 < n_sites; s0 += M2F_ATTN_WEIGHTS_MAX_SITES) {
+        AttnWeightsBatch wb;
+        memset(&wb, 0, sizeof(wb));
+        wb.count = std::min(n_sites - s0, M2F_ATTN_WEIGHTS_MAX_SITES);
+        for (int i = 0; i < wb.count; ++i) {
+            const AttnSiteRef& a = all[sites[s0 + i]];
+            wb.site[i] = {P.s_attn + offs[sites[s0 + i]], out[s0 + i], a.H, 1.0f / (float)a.H};
+        }
+        wb.B = P.B; wb.L = P.s_cap; wb.per_head = per_head != 0;
+        M2F_HIP(m2f_launch_attn_weight_rows(wb, static_cast<hipStream_t>(stream)));
+    }
+    return 0;
+}
+
 /* Chunk plans.  See include/m2fnet_hip.h. */
 static m2f_plan* chunk_plan_new(m2f_plan* parent, int T) {
     if (!parent || !parent->streaming || parent->s_parent) { fail("chunk plan: the parent must be a stream plan (m2f_plan_create_stream)"); return nullptr; }

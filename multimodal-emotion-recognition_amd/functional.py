@@ -130,6 +130,41 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     return out, probs
 
 
+def attention_weights(probs: torch.Tensor, B: int, L: int, H: int, key_pad: Optional[torch.Tensor] = None,
+                      cu: Optional[torch.Tensor] = None, past: Optional[int] = None, future: Optional[int] = None,
+                      average_heads: bool = True) -> torch.Tensor:
+    """The attention map of one site (m2f_attention_weights, csrc/attention_weights.hip) out of the `probs` that `attention_fwd` /
+    `attention_varlen_fwd` returned for the same B, L, H: what ``nn.MultiheadAttention(need_weights=True)`` returns, [B, L, L] (the
+    fp32 sum over the heads in order times fp32(1 / H): ``average_attn_weights=True``) or, with ``average_heads=False``, [B, H, L, L].
+    key_pad ([B, L] or [B*L], 1 = padded key) / cu (int32 [B + 1], packed rows) / past, future: what the forward was given.  An element
+    is read from `probs` only inside the dialogue, at an unpadded key and inside the band; every other one is exactly 0 - whatever a
+    reused `probs` buffer held there.  Pad-query rows of a padded batch hold their softmax numbers (as torch's do); a row that sees
+    no key is zeros (torch: NaN)."""
+    for name, v in (("B", B), ("L", L), ("H", H)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"attention_weights: {name} must be an integer >= 1, got {v!r}")
+    if L > 512:
+        raise ValueError(f"attention_weights: L <= 512 required, got {L}")
+    Lp = 16 * ((L + 15) // 16)
+    if not isinstance(probs, torch.Tensor) or probs.dtype != torch.float32 or tuple(probs.shape) != (B * H, Lp, Lp) or not probs.is_contiguous():
+        raise ValueError(f"attention_weights: probs must be a contiguous fp32 [B*H, Lp, Lp] = [{B * H}, {Lp}, {Lp}] tensor "
+                         f"(attention_fwd's second result), got {getattr(probs, 'dtype', None)} {tuple(getattr(probs, 'shape', ()))}")
+    if key_pad is not None and cu is not None:
+        raise ValueError("attention_weights: at most one of key_pad (padded rows) and cu (packed rows) may be given")
+    if key_pad is not None and key_pad.numel() != B * L:
+        raise ValueError(f"attention_weights: key_pad must hold B * L = {B * L} flags, got {tuple(key_pad.shape)}")
+    if cu is not None and (cu.dtype != torch.int32 or tuple(cu.shape) != (B + 1,)):
+        raise ValueError(f"attention_weights: cu must be int32 [B + 1] = [{B + 1}], got {cu.dtype} {tuple(cu.shape)}")
+    band = runtime.context_band(past, future)           # (raises ValueError)
+    runtime.require_gpu()
+    kp = None if key_pad is None else key_pad.to(device=probs.device, dtype=torch.uint8).contiguous()
+    cu = None if cu is None else cu.to(probs.device).contiguous()
+    out = torch.empty((B, L, L) if average_heads else (B, H, L, L), dtype=torch.float32, device=probs.device)
+    check(lib().m2f_attention_weights(B, L, H, ptr(probs), ptr(kp), ptr(cu), band[0], band[1], int(not average_heads), ptr(out),
+                                      stream_ptr()), "m2f_attention_weights")
+    return out
+
+
 def attention_long_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: Optional[torch.Tensor], B: int, S: int, H: int,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Token-level self-attention of the in-loop encoders' fp32 mode (m2f_attention_long_fwd): q / k / v [B*S, H*hd] fp32, possibly
@@ -194,16 +229,21 @@ def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool =
 
 
 def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, lengths: torch.Tensor,
-                     active: torch.Tensor, H: int, ring: bool = False, bf16: bool = False) -> torch.Tensor:
+                     active: torch.Tensor, H: int, ring: bool = False, bf16: bool = False,
+                     weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One streaming-attention launch (m2f_attention_stream): slot s takes the new rows q[s] / k[s] / v[s] ([S, H*hd] fp32, possibly column
     slices) against the rows it has cached.  kcache / vcache: `attention_stream_caches`; lengths int32 [S] = utterances cached so far
     (read, NOT advanced); active uint8 / bool [S].  An active slot stores its new K / V rows at row lengths % capacity (ring) or
     lengths (lengths < capacity required) and gets softmax(q K^T / sqrt(hd)) V over its min(lengths + 1, capacity) live rows; an
-    inactive slot gets a zero row and its caches stay as they are.  Returns out [S, H*hd]."""
+    inactive slot gets a zero row and its caches stay as they are.  Returns out [S, H*hd].
+    weights: a contiguous fp32 [S, H, capacity] tensor - the launch (m2f_attention_stream_weights, the weights-emitting form of the
+    kernel) also fills it with each slot's row of attention probabilities in logical order: column t = the t-th oldest live utterance
+    (`streaming.logical_columns`), the last live column the new one; zeros behind the live count and for inactive slots.  Same `out`, same bits."""
     runtime.require_gpu()
     S, E = q.shape
     hd = E // H
     C = kcache.shape[2]
+    _stream_weights_ok("attention_stream", weights, S, H, C)
     want = torch.bfloat16 if bf16 else torch.float32
     if kcache.dtype != want or vcache.dtype != want or not kcache.is_contiguous() or not vcache.is_contiguous():
         raise ValueError("attention_stream: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
@@ -211,9 +251,20 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
         raise ValueError("attention_stream: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    if weights is not None:
+        check(lib().m2f_attention_stream_weights(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C,
+                                                 int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights),
+                                                 stream_ptr()), "m2f_attention_stream_weights")
+        return out
     check(lib().m2f_attention_stream(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
                                      ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream")
     return out
+
+
+def _stream_weights_ok(who: str, weights, S: int, H: int, C: int) -> None:
+    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (S, H, C)
+                                or not weights.is_contiguous()):
+        raise ValueError(f"{who}: weights must be a contiguous fp32 [S, H, capacity] = [{S}, {H}, {C}] tensor")
 
 
 def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
@@ -265,19 +316,27 @@ def _paged_args(who: str, kpool, vpool, table, S: int, capacity: int, bf16: bool
 
 def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
                            lengths: torch.Tensor, active: torch.Tensor, H: int, capacity: int, ring: bool = False,
-                           bf16: bool = False) -> torch.Tensor:
+                           bf16: bool = False, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`attention_stream` over page pools (m2f_attention_stream_paged): logical cache row r of slot s - the row `attention_stream` calls r -
     is row r % page_rows of page table[s, r // page_rows].  kpool / vpool: `attention_stream_pools`; table int32 [S, ceil(capacity /
     page_rows)], read only at the entries of pages that hold a live row or take the new one.  The same bits as `attention_stream` on
-    caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd]."""
+    caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd].
+    weights: as `attention_stream` (m2f_attention_stream_weights_paged) - the order is logical, so the rows are the dense launch's bits."""
     runtime.require_gpu()
     S, E = q.shape
     hd = E // H
     n_pages, R = _paged_args("attention_stream_paged", kpool, vpool, table, S, capacity, bf16)
+    _stream_weights_ok("attention_stream_paged", weights, S, H, capacity)
     if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
         raise ValueError("attention_stream_paged: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    if weights is not None:
+        check(lib().m2f_attention_stream_weights_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
+                                                       ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act),
+                                                       ptr(out), _ld(out), int(bf16), ptr(weights), stream_ptr()),
+              "m2f_attention_stream_weights_paged")
+        return out
     check(lib().m2f_attention_stream_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
                                            table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
                                            int(bf16), stream_ptr()), "m2f_attention_stream_paged")
@@ -544,9 +603,11 @@ def cross_entropy_distill(logits: torch.Tensor, teacher: torch.Tensor, labels: t
 
 
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
-                      precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None) -> torch.Tensor:
+                      precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
+                      need_weights: bool = False):
     """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity.  past / future: context band of its
-    attention (`attention_fwd`); the reference has none."""
+    attention (`attention_fwd`); the reference has none.  need_weights: also the head-averaged attention map [B, L, L] that the
+    reference's own call computes and drops (`attention_weights`)."""
     B, L, E = text.shape
     t = text.reshape(B * L, E).contiguous()
     a = audio.reshape(B * L, E).contiguous()
@@ -554,11 +615,13 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     k = gemm(a, in_w[E:2 * E], NT, precision, bias=in_b[E:2 * E])
     v = gemm(t, in_w[2 * E:], NT, precision, bias=in_b[2 * E:])
     if L > 64:          # (the dialogue kernels of attention_fwd hold L <= 64; above, the long-dialogue kernels, padded form)
-        att, _ = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future)
+        att, probs = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future)
     else:
-        att, _ = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future)
+        att, probs = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future)
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
+    if need_weights:
+        return y.view(B, L, E), attention_weights(probs, B, L, n_head, key_pad=key_pad, past=past, future=future)
     return y.view(B, L, E)
 
 

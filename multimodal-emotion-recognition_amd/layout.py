@@ -188,6 +188,21 @@ def param_specs(c: M2FConfig) -> Tuple[List[ParamSpec], int]:
     return specs, off
 
 
+def attention_sites(cfg) -> List[Tuple[str, int, int]]:
+    """(name, heads, head dim) of every dialogue-level attention site, in ``state_dict`` order - the names are the ``state_dict``
+    prefixes of the sites' parameters.  `cfg`: an M2FConfig or the reference's ``config.model`` tree.  The C side
+    (``m2f_plan_attention_sites``) lists a plan's sites in the same order; ``M2FNet.last_attention`` keys its result by these names."""
+    c = cfg if isinstance(cfg, M2FConfig) else M2FConfig.from_model_config(cfg)
+    sites: List[Tuple[str, int, int]] = []
+    for on, prefix, d, H, nt, nl in ((c.audio_enabled, "audio_encoders", c.d_audio, c.nhead_audio, c.ntrans_audio, c.nlayers_audio),
+                                     (c.text_enabled, "text_encoders", c.d_text, c.nhead_text, c.ntrans_text, c.nlayers_text)):
+        if on:
+            sites += [(f"{prefix}.{e}.layers.{l}.self_attn", H, d // H) for e in range(nt) for l in range(nl)]
+    if c.fam_enabled:
+        sites += [(f"fusion_layers.{i}.multihead_attention", c.nhead_fam, c.d_fam // c.nhead_fam) for i in range(c.nlayers_fam)]
+    return sites
+
+
 def param_count(c: M2FConfig) -> int:
     """Number of scalar parameters (unique tensors; equals the reference's sum(p.numel()))."""
     return sum(s.numel for s in param_specs(c)[0] if not s.alias_of)

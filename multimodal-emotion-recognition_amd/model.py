@@ -92,9 +92,11 @@ class FusionAttentionModule(nn.Module):
         self.embedding_size, self.n_head, self.dropout_p = embedding_size, n_head, dropout
 
     def forward(self, text: torch.Tensor, audio: torch.Tensor, key_padding_mask: torch.Tensor,
-                past: Optional[int] = None, future: Optional[int] = None) -> torch.Tensor:
+                past: Optional[int] = None, future: Optional[int] = None, need_weights: bool = False):
         """past / future: context band of the attention (``functional.attention_fwd``): text utterance i attends to the audio of
-        utterances i - past .. i + future only, None = unlimited.  The reference's module has no such argument."""
+        utterances i - past .. i + future only, None = unlimited.  The reference's module has no such argument.
+        need_weights: return ``(y, weights [B, L, L])`` - the head-averaged attention map that the reference's own
+        ``nn.MultiheadAttention`` call computes and drops (src/model.py:14); default: ``y`` alone, as ever."""
         from . import functional as F
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("standalone FusionAttentionModule.forward is inference-only; train it inside M2FNet "
@@ -102,7 +104,7 @@ class FusionAttentionModule(nn.Module):
         return F.fam_layer_forward(text, audio, key_padding_mask, self.multihead_attention.in_proj_weight,
                                    self.multihead_attention.in_proj_bias, self.multihead_attention.out_proj.weight,
                                    self.multihead_attention.out_proj.bias, self.linear.weight, self.linear.bias,
-                                   self.n_head, past=past, future=future)
+                                   self.n_head, past=past, future=future, need_weights=need_weights)
 
 
 class _Anchor(torch.autograd.Function):
@@ -200,11 +202,17 @@ class _Engine:
         # p.mul_(), writes through the flat buffer or its views) moves the counters, the plans then re-cast the shadows at the head of
         # their forward as before.  Writes that bypass the counters (p.data...) need `invalidate_shadows()`; `flat_parameters()` calls it.  M2F_SHARED_SHADOWS=0: off.
         self.wshadow: Optional[torch.Tensor] = None
+        self.last = None                                      # (plan, version, dst, valid, (b, l)) of the most recent forward (note_forward)
         self.grad_bf16_buf: Optional[torch.Tensor] = None     # bf16 [n_params]: train plans leave their gradients here (set_grad_bf16)
         self.accumulate = False                               # torch's .grad rule at every backward (M2FNet.set_grad_accumulation)
         self._fresh_token = None
         if self.precision == runtime.BF16 and os.environ.get("M2F_SHARED_SHADOWS", "1") != "0":
             self.wshadow = runtime.param_shadow_buffer(self.cfg, device)
+
+    def note_forward(self, plan) -> None:
+        """`plan` has just run a forward for this model: `M2FNet.last_attention` reads its saved probabilities (and the row map of
+        THIS batch - a packed plan re-makes it per batch)."""
+        self.last = (plan, plan.version, plan._dst, plan._valid, (plan.in_B, plan.in_L))
 
     def _version_token(self):
         # the parameters' own counters + the flat buffer's (shared by every view of it: a write through `flat_parameters()` or a
@@ -518,10 +526,54 @@ class M2FNet(nn.Module):
         if want_bwd:
             out = _Anchor.apply(eng.anchor, text, audio, self, plan)
             plan.hold(out.grad_fn)
+            eng.note_forward(plan)
             return out
         if plan.train and plan.cfg.dropout > 0.0:
             runtime.check(runtime.lib().m2f_rng_advance(eng.rng.data_ptr(), runtime.stream_ptr()), "m2f_rng_advance")
-        return plan.forward().clone()
+        out = plan.forward().clone()
+        eng.note_forward(plan)
+        return out
+
+    # -- attention maps (what need_weights=True returns; csrc/attention_weights.hip) ---------------------------------------------------
+    def last_attention(self, average_heads: bool = True, sites=None) -> Dict[str, torch.Tensor]:
+        """The attention maps of the most recent ``forward`` / ``train_step`` / ``eval_step`` of this model: ``{site: tensor}``, the
+        sites named by the ``state_dict`` prefixes of their parameters (``layout.attention_sites``: ``audio_encoders.{e}.layers.{l}.
+        self_attn``, ``text_encoders.{e}.layers.{l}.self_attn``, ``fusion_layers.{i}.multihead_attention``), each ``[B, L, L]`` -
+        ``weights[b, i, j]`` = how much utterance i of dialogue b attends to utterance j, the heads averaged as torch's
+        ``need_weights=True`` does (fp32 sum over the heads in order, times fp32(1 / H)) - or ``[B, H, L, L]`` with
+        ``average_heads=False``.  These are the weights that the reference's fusion module computes at every layer and throws away
+        (src/model.py:14).  sites: names to return (default: all).
+
+        No second forward: every attention site saves its probabilities at every forward, and one eager gather launch turns them
+        into fresh tensors in the caller's dialogue order and ``L``, whatever bucket or packed layout ran; no logit changes by a bit.
+        Padded keys, pairs a context band hides and (packed and long-dialogue plans) the rows and columns of pad slots are exactly 0;
+        a row that sees no key is zeros where torch gives NaN.  In train mode with dropout > 0 the maps are the PRE-dropout
+        probabilities (rows sum to 1); torch returns post-dropout weights there.
+        Raises RuntimeError when no forward has run, or the plan that ran it was destroyed or has run again since (another model
+        instance cannot, a plan driven by hand can)."""
+        eng = self._engine
+        if eng is None or eng.last is None:
+            raise RuntimeError("M2FNet.last_attention: no forward has run on this model (or it was moved since)")
+        plan, version, dst, valid, shape = eng.last
+        if not plan.handle:
+            raise RuntimeError("M2FNet.last_attention: the plan holding the probabilities of the last forward was destroyed "
+                               "(evicted from the plan cache)")
+        if plan.version != version:
+            raise RuntimeError("M2FNet.last_attention: the probabilities of the last forward were overwritten by a later forward "
+                               "of the same plan")
+        names = [n for (n, _, _) in plan.attention_sites()]
+        want = names if sites is None else list(sites)
+        unknown = [n for n in want if n not in names]
+        if unknown:
+            raise ValueError(f"M2FNet.last_attention: unknown attention site(s) {unknown}; this model has {names}")
+        maps = plan.attention_maps([names.index(n) for n in want], not average_heads, dst, valid, shape)
+        return dict(zip(want, maps))
+
+    def attention_maps(self, text, audio, mask, average_heads: bool = True, sites=None):
+        """``(logits, maps)``: a no-grad ``forward`` in the model's current mode, then ``last_attention(average_heads, sites)``."""
+        with torch.no_grad():
+            logits = self(text, audio, mask)
+        return logits, self.last_attention(average_heads, sites)
 
     # -- fused fast path (forward + criterion + backward as one launch list / hipGraph) ---------------
     def train_step(self, text, audio, mask, emotion, label_smoothing: float = 0.1,
@@ -577,6 +629,7 @@ class M2FNet(nn.Module):
         else:
             loss = body()
         eng.publish_grads()
+        eng.note_forward(plan)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
@@ -620,10 +673,11 @@ class M2FNet(nn.Module):
             cur.wait_stream(eng.stream)
         else:
             body()
+        eng.note_forward(plan)
 
     # -- streaming inference (one new utterance per live dialogue; streaming.DialogueStream) -----------------------------------------
     def stream(self, max_streams: int, capacity: Optional[int] = None, use_graph: bool = True, max_chunk: int = 1,
-               pages: Optional[int] = None, page_rows: int = 16):
+               pages: Optional[int] = None, page_rows: int = 16, attention: bool = False):
         """A ``DialogueStream`` of ``max_streams`` slots over this model's weights: ``stream.step(text [S, d_t], audio [S, d_a],
         active)`` labels the utterance that has just arrived in each active slot from per-site K / V caches on the device, at the
         cost of one row per dialogue - where ``forward`` would re-run the whole prefix.  Needs a causal context band
@@ -642,6 +696,10 @@ class M2FNet(nn.Module):
         returns them at ``reset`` (``streaming.PageAllocator``).  Memory follows the utterances cached, not ``max_streams * capacity``:
         the 3.8 GB above hold 2,048 pages of 16 rows, about 2,000 live MELD-length dialogues.  Same logits, bit for bit; a call that
         would need more pages than are free raises RuntimeError and changes nothing.
+        attention: True - every step also keeps, per attention site, slot and head, the row of attention probabilities of the new
+        utterance over the cached ones, and ``stream.attention(average_heads=True, sites=None)`` returns them after a ``step`` (which
+        cached utterances did this prediction use); ``sum_sites H * max_streams * capacity * 4 B`` more memory (17.8 MB at C3, 64
+        streams, capacity 512), the same logits bit for bit, the step still one replayed graph.
         Every refusal is raised before the GPU is touched."""
         from .streaming import DialogueStream, resolve_capacity, resolve_max_chunk, resolve_pages
         past, future = self._context
@@ -654,7 +712,8 @@ class M2FNet(nn.Module):
         if isinstance(max_streams, bool) or not isinstance(max_streams, int) or max_streams < 1:
             raise ValueError(f"M2FNet.stream: max_streams must be an integer >= 1, got {max_streams!r}")
         pages, page_rows = resolve_pages(pages, page_rows)
-        return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph, resolve_max_chunk(max_chunk), pages, page_rows)
+        return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph, resolve_max_chunk(max_chunk), pages, page_rows,
+                              attention=bool(attention))
 
     def set_grad_bf16(self, on: bool = True) -> bool:
         """bf16 mode: every following training step leaves its gradients ROUNDED ONCE TO BF16 in one flat bf16 buffer - the weight-gradient

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .layout import M2FConfig, param_specs
+from .layout import M2FConfig, attention_sites, param_specs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -25,7 +25,7 @@ F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
- BUF_TEACHER, BUF_DISTILL) = range(18)
+ BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN) = range(19)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -118,6 +118,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                   c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
     "m2f_attention_probs_elems": (c_int64, [c_int, c_int, c_int]),
+    "m2f_attention_weights": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "m2f_plan_attention_sites": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "m2f_plan_attention_weights": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "m2f_attention_fwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
     "m2f_attention_bwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
@@ -139,6 +142,14 @@ SIGNATURES = {
     "m2f_attention_stream_cache_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "m2f_attention_stream": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                      c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_attention_stream_weights": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "m2f_attention_stream_weights_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                   c_void_p]),
+    "m2f_stream_attention_elems": (c_int64, [c_void_p]),
+    "m2f_plan_stream_attention": (c_int, [c_void_p, c_void_p, c_int64]),
+    "m2f_stream_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "m2f_stream_paged_workspace_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "m2f_plan_create_stream_paged": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                                                 c_void_p]),
@@ -709,6 +720,48 @@ class Plan:
             return out
         return rows.view(self.B, self.L, -1)[:b, :l].clone()
 
+    def attention_sites(self):
+        """[(name, H, hd)] of the plan's attention sites as the C side lists them (m2f_plan_attention_sites), cross-checked against
+        ``layout.attention_sites``: the index of a site in this list is what `attention_maps` takes."""
+        n_max = 4096
+        kind, index, layer, H, hd = ((c_int * n_max)() for _ in range(5))
+        n = lib().m2f_plan_attention_sites(self._h(), kind, index, layer, H, hd, n_max)
+        if n < 0 or n > n_max:
+            raise HipError("m2f_plan_attention_sites: " + lib().m2f_last_error().decode())
+        fmt = ("audio_encoders.{}.layers.{}.self_attn", "text_encoders.{}.layers.{}.self_attn", "fusion_layers.{}.multihead_attention")
+        got = [(fmt[kind[i]].format(index[i], layer[i]), H[i], hd[i]) for i in range(n)]
+        if got != attention_sites(self.cfg):
+            raise HipError("attention-site list mismatch between layout.py and csrc/plan_build.hip")
+        return got
+
+    def attention_maps(self, sites, per_head: bool, dst=None, valid=None, shape=None):
+        """m2f_plan_attention_weights: FRESH tensors, one per listed site index, holding the attention maps of the plan's last forward
+        on the padded surface of the batch - [b, l, l] (heads averaged) or [b, H, l, l] - one eager launch for all of them.  Packed
+        plans map dialogue positions back to the batch's slots through `valid` (the forward's `_valid`), with exact zeros in the rows
+        and columns of pad slots: indexing only."""
+        heads = [h for (_, h, _) in self.attention_sites()]
+        B, L = self.B, self.L
+        dev = self.workspace.device
+        outs = [torch.empty((B, heads[i], L, L) if per_head else (B, L, L), dtype=torch.float32, device=dev) for i in sites]
+        if not outs:
+            return outs
+        idx = (c_int * len(outs))(*sites)
+        ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+        check(lib().m2f_plan_attention_weights(self._h(), idx, len(outs), int(bool(per_head)), ptrs, stream_ptr()),
+              "m2f_plan_attention_weights")
+        b, l = (self.in_B, self.in_L) if shape is None else shape
+        if not self.packed:
+            return [o[:b, ..., :l, :l].clone() for o in outs]
+        rank = (torch.cumsum(valid, 1, dtype=torch.int64) - 1).clamp_(min=0)          # a slot's position inside its dialogue
+        pair = valid[:, :, None] & valid[:, None, :]
+        res = []
+        for o in outs:
+            r = rank[:, None].expand(-1, o.shape[1], -1) if per_head else rank
+            m = o[:b].gather(-2, r.unsqueeze(-1).expand(*r.shape, L))
+            m = m.gather(-1, r.unsqueeze(-2).expand(*r.shape, l))
+            res.append(m * (pair[:, None] if per_head else pair).to(m.dtype))
+        return res
+
     def fused_adam_setup_grouped(self, params, exp_avg, exp_avg_sq, param_shadow, hyper_table, tensor_group, grad_scale=None) -> None:
         """m2f_plan_fused_adam_setup_grouped: ``fused_adam_setup`` for an optimizer with parameter groups / decoupled weight decay -
         `hyper_table` the rows of ``adam_hyper_groups``, `tensor_group` the group of every parameter tensor (-1: none)."""
@@ -860,6 +913,40 @@ class StreamPlan:
         check(lib().m2f_stream_scatter(self._h(), slots.numel(), ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed), packed.numel(),
                                        stream_ptr()), "m2f_stream_scatter")
 
+    attention_sites = Plan.attention_sites
+
+    def stream_attention(self, on: bool) -> None:
+        """m2f_plan_stream_attention: from the next step on the attention launches also store each (slot, head)'s row of probabilities
+        (on: into a buffer of m2f_stream_attention_elems floats made here - [site][S][H][C], 17.8 MB at C3, S = 64, C = 512) / run the
+        kernels they always ran (off: the buffer is dropped).  A change drops the captured step once."""
+        if bool(on) == (getattr(self, "attn_buf", None) is not None):
+            return
+        if not on:
+            check(lib().m2f_plan_stream_attention(self._h(), None, 0), "m2f_plan_stream_attention")
+            self.attn_buf = None
+            return
+        n = int(lib().m2f_stream_attention_elems(self._h()))
+        if n < 0:
+            raise HipError("m2f_stream_attention_elems: " + lib().m2f_last_error().decode())
+        with torch.inference_mode(False):
+            buf = torch.zeros(max(n, 4), dtype=torch.float32, device=self.workspace.device)
+        torch.cuda.current_stream(buf.device).synchronize()          # (the switch waits for the device on the null stream)
+        check(lib().m2f_plan_stream_attention(self._h(), buf.data_ptr(), buf.numel()), "m2f_plan_stream_attention")
+        self.attn_buf = buf
+
+    def attention_rows(self, sites, per_head: bool):
+        """m2f_stream_attention: fresh tensors, one per listed site index, with the rows of the last step - [S, H, C] or, heads
+        averaged on the device, [S, C]; one eager launch."""
+        heads = [h for (_, h, _) in self.attention_sites()]
+        dev = self.workspace.device
+        outs = [torch.empty((self.S, heads[i], self.capacity) if per_head else (self.S, self.capacity), dtype=torch.float32, device=dev)
+                for i in sites]
+        if outs:
+            idx = (c_int * len(outs))(*sites)
+            ptrs = (c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+            check(lib().m2f_stream_attention(self._h(), idx, len(outs), int(bool(per_head)), ptrs, stream_ptr()), "m2f_stream_attention")
+        return outs
+
     def num_launches(self) -> int:
         return lib().m2f_plan_num_launches(self._h(), 0) + 1
 
@@ -872,6 +959,7 @@ class StreamPlan:
             _lib.m2f_plan_destroy(h)
         self.handle = None
         self.workspace = None
+        self.attn_buf = None
 
     def __del__(self):
         self.close()

@@ -99,6 +99,31 @@ def resolve_capacity(past: Optional[int], capacity: Optional[int]) -> int:
     return capacity
 
 
+def logical_columns(length: int, capacity: int, ring: bool):
+    """(first, count) of the columns of a stream's attention row once a slot has taken ``length`` utterances: column t is utterance
+    ``first + t``, t < count, the last one the utterance that has just arrived.  A plain cache keeps every utterance (first = 0, count =
+    length <= capacity); a ring keeps the last ``capacity`` of them.  Host arithmetic: what the logical order of the weights-emitting
+    kernel (``csrc/attention_stream.hip``) means."""
+    if isinstance(length, bool) or not isinstance(length, int) or length < 0:
+        raise ValueError(f"logical_columns: length must be an integer >= 0, got {length!r}")
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+        raise ValueError(f"logical_columns: capacity must be an integer >= 1, got {capacity!r}")
+    if not ring and length > capacity:
+        raise ValueError(f"logical_columns: a plain cache of {capacity} rows cannot hold {length} utterances")
+    count = min(length, capacity)
+    return length - count, count
+
+
+class StreamAttention:
+    """What ``DialogueStream.attention`` returns: ``weights[name]`` - fp32 ``[S, C]`` (heads averaged) or ``[S, H, C]`` per attention
+    site, column t of slot s = the weight of utterance ``first[s] + t`` in the prediction the last ``step`` made for slot s - with
+    ``first`` (utterance index of column 0) and ``count`` (live columns; 0 for a slot that took no utterance in that step, whose row is
+    zeros) per slot, both host lists.  Columns behind ``count`` are zeros."""
+
+    def __init__(self, weights, first, count):
+        self.weights, self.first, self.count = weights, list(first), list(count)
+
+
 def cache_bytes(cfg: M2FConfig, max_streams: int, capacity: int, bf16: bool = False) -> int:
     """2 * sum over attention sites of pad(d_site) * S * C * element size: K and V, every encoder layer of every stack and every
     fusion layer; pad(d_site) = heads * head dim padded to 4 floats (fp32 caches, 4 B) or 8 bf16 values (bf16 mode, 2 B)."""
@@ -422,8 +447,8 @@ class StreamSnapshot:
 
 
 class DialogueStream:
-    """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1, pages=None, page_rows=16)``: ``max_streams``
-    slots, each one live dialogue.
+    """``model.stream(max_streams, capacity=None, use_graph=True, max_chunk=1, pages=None, page_rows=16, attention=False)``:
+    ``max_streams`` slots, each one live dialogue.
 
     ``step(text [S, d_t], audio [S, d_a], active=None) -> logits [S, C_out]`` takes ONE new utterance per active slot and returns a
     fresh tensor with its logits (zero rows at inactive slots).  ``active`` is a host-side bool sequence or CPU tensor (None: every
@@ -465,10 +490,16 @@ class DialogueStream:
     (RuntimeError naming the slots; the stream is left exactly as it was).  ``evict(slots)`` is ``snapshot(slots)`` copied to pinned
     host memory on the engine's stream, then ``reset(slots)``: on a paged stream the pages are free when it returns, and the copy is
     ordered before any later write of the stream.  ``fork(src, dst)`` is ``restore(snapshot([src]), [dst])``.  A SNAPSHOT BELONGS TO THE
-    WEIGHTS THAT WROTE IT: the rule above for the caches holds for what was copied out of them."""
+    WEIGHTS THAT WROTE IT: the rule above for the caches holds for what was copied out of them.
+
+    ATTENTION ROWS (``attention=True``): every step's attention launches run the weights-emitting form of their kernel and keep, per
+    site, slot and head, the new utterance's row of probabilities over the cached ones (``sum_sites H * S * capacity * 4 B``; the same
+    logits bit for bit, the step still one replayed graph).  ``attention(average_heads=True, sites=None)`` after a ``step`` returns
+    them as a ``StreamAttention`` (``weights[site]`` ``[S, C]`` or ``[S, H, C]``, ``first``, ``count``): which cached utterances the
+    prediction used."""
 
     def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1,
-                 pages: Optional[int] = None, page_rows: int = 16):
+                 pages: Optional[int] = None, page_rows: int = 16, attention: bool = False):
         self.model, self.use_graph = model, bool(use_graph)
         self.max_streams, self.capacity = int(max_streams), int(capacity)
         self.max_chunk = resolve_max_chunk(max_chunk)
@@ -487,6 +518,11 @@ class DialogueStream:
         self._active_host: Optional[List[bool]] = None        # what the device's mask holds (None: not written yet)
         self._new_host: Optional[List[int]] = None            # ... and the chunk plan's per-slot row counts
         self._signature: Optional[tuple] = None               # what a snapshot of this stream carries (read from the plan once)
+        # attention rows (model.stream(..., attention=True)): the step's attention launches also store their probabilities
+        self.attention_on = bool(attention)
+        self._attn_act: Optional[List[bool]] = None           # the mask of the last step, while its rows are what the buffer holds
+        if self.attention_on:
+            self.plan.stream_attention(True)
 
     # -- plumbing ----------------------------------------------------------------------------------------------------------------
     def _on_stream(self, body):
@@ -571,6 +607,7 @@ class DialogueStream:
         for s, a in enumerate(act):
             if a:
                 self.lengths[s] += 1
+        self._attn_act = list(act)
         return out
 
     # -- public surface ----------------------------------------------------------------------------------------------------------
@@ -613,6 +650,7 @@ class DialogueStream:
         out = self._on_stream(body)
         for s, n in enumerate(new):
             self.lengths[s] += n
+        self._attn_act = None
         return out
 
     def prefill(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], counts: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -654,6 +692,7 @@ class DialogueStream:
             for i in range(max(counts, default=0)):
                 act = [c > i for c in counts]
                 out[:, i] = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
+            self._attn_act = None                           # (a history, however it was loaded: `attention` answers for a `step`)
             return out
         for i, new in enumerate(chunk_schedule(counts, T)):
             w = max(new)
@@ -662,6 +701,7 @@ class DialogueStream:
 
     def reset(self, slots: Optional[Sequence[int]] = None) -> None:
         S = self.max_streams
+        self._attn_act = None
         if slots is None:
             self._on_stream(lambda: self.plan.reset(None))
             self.lengths = [0] * S
@@ -716,6 +756,7 @@ class DialogueStream:
                 continue
             logits = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
             out[:, i] = logits[:B]
+        self._attn_act = None                               # (a whole batch, by steps or by chunks: `attention` answers for a `step`)
         return out
 
     # -- snapshots ---------------------------------------------------------------------------------------------------------------
@@ -793,6 +834,30 @@ class DialogueStream:
             raise
         for s, n in zip(slots, snap.lengths):
             self.lengths[s] = n
+        self._attn_act = None
+
+    # -- attention rows ----------------------------------------------------------------------------------------------------------
+    def attention(self, average_heads: bool = True, sites: Optional[Sequence[str]] = None) -> StreamAttention:
+        """Which cached utterances did the predictions of the last ``step`` use: a ``StreamAttention`` with, per attention site (named
+        as ``M2FNet.last_attention`` names them; `sites`: a selection, default all), fresh tensors ``[S, C]`` - the heads averaged by
+        the rule of ``last_attention``, on the device - or ``[S, H, C]``, column t of slot s being utterance ``first[s] + t`` of the
+        slot's dialogue, ``t < count[s]``.  One eager launch outside the step graph; nothing waits for the device.  Needs a stream made
+        with ``attention=True`` and a ``step`` as the last call: after ``prefill`` (the chunk kernel stores no rows), ``restore``,
+        ``reset`` or ``run`` it raises RuntimeError."""
+        if not self.attention_on:
+            raise RuntimeError("DialogueStream.attention: this stream was made without attention rows (model.stream(..., attention=True))")
+        if self._attn_act is None:
+            raise RuntimeError("DialogueStream.attention: the last call was not a step (prefill, restore, reset and run leave no "
+                               "attention rows): call step first")
+        names = [n for (n, _, _) in self.plan.attention_sites()]
+        want = names if sites is None else list(sites)
+        unknown = [n for n in want if n not in names]
+        if unknown:
+            raise ValueError(f"DialogueStream.attention: unknown attention site(s) {unknown}; this model has {names}")
+        maps = self._on_stream(lambda: self.plan.attention_rows([names.index(n) for n in want], not average_heads))
+        ring = self.past is not None
+        cols = [logical_columns(n, self.capacity, ring) if a else (0, 0) for n, a in zip(self.lengths, self._attn_act)]
+        return StreamAttention(dict(zip(want, maps)), [c[0] for c in cols], [c[1] for c in cols])
 
     def evict(self, slots: Sequence[int]) -> StreamSnapshot:
         slots = [int(s) for s in slots]

@@ -83,6 +83,60 @@ def stream_pages_settings(config):
         raise ValueError(f"runtime.stream_pages: {e}") from None
 
 
+def attention_maps_settings(config):
+    """`runtime.attention_maps`: {enabled, file, sites} - enabled: test() also writes the attention maps of the pass (M2FNet.last_attention:
+    what need_weights=True returns, heads averaged) to `file`, one .npz with an array `<dialogue>/<site>` [n, n] per dialogue of the pass
+    (in loader order, n its utterances) and site; sites: names of `mer_amd.layout.attention_sites` (empty or null: every site).  Not with
+    runtime.streaming (a streamed pass has no [L, L] map; see DialogueStream.attention).  -> None or (file, sites or None); checked on
+    the host before the GPU is touched."""
+    from train import _runtime
+    block = _runtime(config, "attention_maps", None)
+    if not block or not block.get("enabled", False):
+        return None
+    if not isinstance(block.get("enabled"), bool):
+        raise ValueError(f"runtime.attention_maps.enabled must be true or false, got {block.get('enabled')!r}")
+    path = block.get("file", None)
+    if not isinstance(path, str) or not path:
+        raise ValueError(f"runtime.attention_maps.file must be the path of the .npz to write, got {path!r}")
+    sites = block.get("sites", None)
+    if sites is not None and (isinstance(sites, str) or not all(isinstance(n, str) for n in sites)):
+        raise ValueError(f"runtime.attention_maps.sites must be a list of attention-site names, got {sites!r}")
+    from mer_amd.layout import attention_sites
+    names = [n for n, _, _ in attention_sites(config.model)]
+    unknown = [n for n in (sites or []) if n not in names]
+    if unknown:
+        raise ValueError(f"runtime.attention_maps.sites: unknown attention site(s) {unknown}; this model has {names}")
+    if bool(_runtime(config, "streaming", False)):
+        raise ValueError("runtime.attention_maps does not combine with runtime.streaming: a streamed pass keeps no [L, L] maps "
+                         "(DialogueStream.attention returns each step's rows)")
+    return path, (list(sites) if sites else None)
+
+
+class _MapCollector:
+    """The maps of a test pass, per dialogue in loader order (`runtime.attention_maps`)."""
+
+    def __init__(self, model):
+        self.model, self.out = model, getattr(model, "attention_maps_out", None)
+        self.arrays, self.n_dialogues = {}, 0
+
+    def add(self, padding_mask) -> None:
+        if self.out is None:
+            return
+        maps = {name: m.cpu().numpy() for name, m in self.model.last_attention(sites=self.out[1]).items()}
+        for b, n in enumerate((~padding_mask.bool()).sum(1).tolist()):
+            for name, m in maps.items():
+                self.arrays[f"{self.n_dialogues}/{name}"] = m[b, :n, :n]
+            self.n_dialogues += 1
+
+    def write(self) -> None:
+        if self.out is None:
+            return
+        import numpy as np
+        with open(self.out[0], "wb") as f:                 # (an open file: numpy appends no suffix to the configured path)
+            np.savez(f, **self.arrays)
+        print(f"Wrote the attention maps of {self.n_dialogues} dialogues to {self.out[0]}")
+
+
 def _stream_for(model, B, L):
     """The model's test stream, opened (again) when a batch has more dialogues or - without a window - longer ones than it holds."""
     st = getattr(model, "_test_stream", None)
@@ -103,8 +157,10 @@ def test(model, dl_test, device):
     dialogue and step, or ``model.stream_chunk`` (runtime.stream_chunk) columns per chunk call - and its logits are scored as the batched
     pass's are (on the host).
     With ``model.device_metrics`` (runtime.device_metrics) every batch is scored on the device (``M2FNet.eval_step``) and the host
-    reads the record once; ``model.test_scores`` then holds the pass's ``DeviceScores`` (confusion matrix, per-class report)."""
+    reads the record once; ``model.test_scores`` then holds the pass's ``DeviceScores`` (confusion matrix, per-class report).
+    With ``model.attention_maps_out`` (runtime.attention_maps) the batched passes also write every dialogue's attention maps."""
     model.eval()
+    maps = _MapCollector(model)
     if getattr(model, "streaming", False):
         scores = BatchScores()
         with torch.inference_mode():
@@ -122,7 +178,9 @@ def test(model, dl_test, device):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
                 model.eval_step(text, audio, padding_mask, emotion, scores)
+                maps.add(padding_mask)
         model.test_scores = scores
+        maps.write()
         return scores.result()
     scores = BatchScores()
     with torch.inference_mode():
@@ -130,6 +188,8 @@ def test(model, dl_test, device):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             scores.update(model(text, audio, padding_mask), emotion)
+            maps.add(padding_mask)
+    maps.write()
     return scores.result()
 
 
@@ -154,6 +214,7 @@ def main(config=None):
     streaming = streaming_settings(config)
     stream_chunk = stream_chunk_settings(config)
     stream_pages = stream_pages_settings(config)
+    attention_maps = attention_maps_settings(config)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     print(f"Using device {device}...")
     runtime_cfg = config.get("runtime", {}) or {}
@@ -166,6 +227,7 @@ def main(config=None):
     model.streaming = streaming
     model.stream_chunk = stream_chunk
     model.stream_pages = stream_pages
+    model.attention_maps_out = attention_maps
     from train import ema_settings
     ema = ema_settings(config)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
