@@ -145,6 +145,16 @@ int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
  * steps, never between a forward and its backward.  m2f_plan_get_attention_band reads the setting back (-1 = unlimited). */
 int m2f_plan_attention_band(m2f_plan* plan, int past, int future);
 int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
+/* Distance-decay bias (ALiBi) of EVERY attention site of the plan: a visible key's score becomes
+ * fma(-slope(h, H, gain), float(|i - j|), dot(q_i, k_j) / sqrt(hd)) in fp32, i and j the positions the band compares and slope the
+ * fixed geometric recipe of m2f_attention_fwd_bias below.  gain >= 0 and finite; 1.0 is ALiBi, 0 (the default) is off and runs the
+ * kernels the plan ran before this entry existed.  The APPLIED gain is the requested one rounded to bf16 (the launch descriptor holds
+ * 16 bits of it); m2f_plan_get_attention_bias reports the applied value.  No parameters, no change to the saved probabilities' layout:
+ * the backward kernels read the probabilities and ignore the setting.  Works on train, eval, packed, stream and chunk plans; on a
+ * stream plan before the first step or between steps (the K / V caches do not depend on it).  A chunk plan takes its parent's gain
+ * when it is created.  A change destroys the captured graphs; call it between steps, never between a forward and its backward. */
+int m2f_plan_attention_bias(m2f_plan* plan, float gain);
+int m2f_plan_get_attention_bias(m2f_plan* plan, float* gain);
 /* ATTENTION MAPS: what nn.MultiheadAttention(need_weights=True) returns - the reference's fusion module computes them at every layer
  * and throws them away (src/model.py:14) - read out of the pre-dropout probabilities that every attention site of a padded or packed
  * plan saves at every forward (train and eval plans alike; csrc/attention_weights.hip).  m2f_plan_attention_sites: the plan's sites in
@@ -756,6 +766,30 @@ int m2f_attention_varlen_bwd_band(int B, int L, int H, int hd, const float* q, i
                                   const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk,
                                   float* dv, int lddv, uint32_t drop_site, float drop_p, const uint32_t* rng_state,
                                   m2f_stream_t stream, int past, int future);
+/* DISTANCE-DECAY BIAS (ALiBi).  The forward entries above with one more term: a VISIBLE key's score is
+ * fma(-slope, float(|i - j|), dot(q_i, k_j) * (1 / sqrt(hd))), all fp32 (in bf16 mode too: behind the contraction), i and j the
+ * positions the band compares; a hidden key stays -inf.  slope = gain * base(h, H), h the 0-based head: with n = 2^floor(log2 H),
+ * base = 2^(-8 (h + 1) / n) for h < n and 2^(-4 (2 (h - n) + 1) / n) for h >= n (H = 4: 1/4, 1/16, 1/64, 1/256; H = 3: 1/16, 1/256,
+ * 1/4).  gain >= 0 and finite, used as rounded to bf16 (what a plan applies); gain = 0 runs the kernels of the entries above.  Each
+ * is a superset of its family: past / future as in the _band entries (negative = unlimited); the stream entries take the paging
+ * arguments of the _paged forms (table = NULL: dense caches, table_cols / n_pages / page_rows ignored) and the weights buffer of the
+ * _weights forms (NULL: none; the chunk form has none).  The new utterance of a stream is at distance 0, cached utterance u at
+ * distance count - u; the backward entries are unchanged - they read the probabilities the biased forward saved. */
+int m2f_attention_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                           const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs,
+                           uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain);
+int m2f_attention_varlen_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
+                                  float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream,
+                                  int past, int future, float gain);
+int m2f_attention_stream_bias(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                              void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                              const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
+                              m2f_stream_t stream);
+int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                    void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
+                                    int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
+                                    m2f_stream_t stream);
 /* The same attention for dialogues of up to 512 utterances (the kernels packed plans with L > 64 run): one workgroup per 64-row
  * block of a (dialogue, head), keys streamed in 64-row blocks.  Rows are given in one of two forms:
  *   packed: cu (int32 [B+1], device) - dialogue b owns rows cu[b] .. cu[b+1]-1 (at most L of them), T rows in all; rows cu[B] ..

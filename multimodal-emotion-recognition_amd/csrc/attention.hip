@@ -7,7 +7,10 @@
 // band_future, ops.h: query i sees keys i - past .. i + future only - attn_mask of a band shape).  A hidden key has P = 0 exactly;
 // a query that sees no key at all (a pad slot whose band holds pad keys only) has a zero row of P and a zero output row - torch
 // gives NaN there.  The backward reads the saved P^T, so the band costs it nothing: P = 0 makes dS = 0, and with it the key's
-// terms of dQ, dK and dV, exactly.
+// terms of dQ, dK and dV, exactly.  Optionally also a distance-decay bias (AttnBatch::bias_gain16, ops.h m2f_attn_bias_slope: ALiBi) -
+// the forward adds -slope_h * |i - j| to the scaled fp32 score of every visible key in one explicit fma (the BIAS instantiations; in
+// bf16 mode behind the contraction, where the scale is applied).  It is a constant with respect to Q and K and the backward recomputes
+// no score, so m2f_attn_bwd_kernel is the kernel it was.
 //
 // One workgroup of four wavefronts owns one (dialogue, head): the sequence is the utterances of a dialogue
 // (L <= 64), so the whole L x L problem fits one wave's registers.  Q/K/V (and dO, O in backward) tiles of
@@ -67,8 +70,9 @@ __device__ __forceinline__ f32x4 dot_rows_bf16(const float* arow, const float* b
     return acc;
 }
 
-// BAND: the launch has a context band (a second instantiation, so that a launch without one runs the code it always ran)
-template <int NT, bool BAND>
+// BAND: the launch has a context band (a second instantiation, so that a launch without one runs the code it always ran); BIAS: it
+// has a distance-decay bias (ops.h, m2f_attn_bias_slope) - instantiations of their own again, with or without a band
+template <int NT, bool BAND, bool BIAS = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) {
     static_assert(sizeof(AttnBatch) + 56 <= 192 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
     m2f_kernarg_warm<0, 8, 192>();                  // the descriptor block (648 B + hidden arguments) in one miss
@@ -160,12 +164,16 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
         unsigned long long vis = kvalid;
         if constexpr (BAND) vis &= m2f_attn_band_bits(ab, i, 0);
         float m = -INFINITY;
+        float nslope = 0.f;                                 // BIAS: minus the head's slope
+        if constexpr (BIAS) nslope = -m2f_attn_bias_slope(h, H, m2f_attn_bias_gain(ab.bias_gain16));
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
-                const float v = ((vis >> j) & 1ull) ? s[jt][r] * scale : -INFINITY;
+                float v = ((vis >> j) & 1ull) ? s[jt][r] * scale : -INFINITY;
+                if constexpr (BIAS)                         // + -slope * |i - j|, this lane's query to key j; a hidden key stays -inf
+                    v = ((vis >> j) & 1ull) ? __fmaf_rn(nslope, (float)abs(i - j), s[jt][r] * scale) : -INFINITY;
                 s[jt][r] = v;
                 m = fmaxf(m, v);
             }
@@ -642,10 +650,11 @@ hipError_t launch(AttnBatch& ab, hipStream_t stream) {
     const size_t lds = (size_t)(BWD ? 4 : 3) * Lp * (maxW + 2) * sizeof(float) +
                        (BWD ? (Lp + (ab.bwd_fast ? 2 * NT * NTHR : 0)) * sizeof(float) : 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const bool band = (ab.band_past | ab.band_future) != 0;
+    const bool band = (ab.band_past | ab.band_future) != 0, bias = !BWD && ab.bias_gain16 != 0;
 #define M2F_ATTN_CASE(N)                                                                                   \
     case N: {                                                                                              \
-        auto kern = BWD ? m2f_attn_bwd_kernel<N> : (band ? m2f_attn_fwd_kernel<N, true> : m2f_attn_fwd_kernel<N, false>); \
+        auto kern = BWD ? m2f_attn_bwd_kernel<N> : bias ? (band ? m2f_attn_fwd_kernel<N, true, true> : m2f_attn_fwd_kernel<N, false, true>) \
+                                                         : (band ? m2f_attn_fwd_kernel<N, true> : m2f_attn_fwd_kernel<N, false>); \
         if (lds > 64 * 1024) {                                                                             \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \

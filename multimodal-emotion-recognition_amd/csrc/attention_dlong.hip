@@ -16,6 +16,11 @@
 // of 64-row blocks that the band hides as a whole is SKIPPED by all three kernels through the same test
 // (m2f_attn_band_blocks_meet) - the forward leaves that block of the probabilities buffer as it was (a plan's buffer holds the
 // previous step's values there) and neither backward kernel reads it.  A query that sees no key gets P = 0 and a zero output row.
+// Distance-decay bias (AttnBatch::bias_gain16, ops.h m2f_attn_bias_slope): the forward's BIAS instantiations add -slope_h * |i - j| to the
+// scaled score of every visible key, i and j positions in the dialogue (block offset + row on BOTH sides), through dlong_score<> in
+// pass 1 and pass 2 alike, so the probabilities are normalised by the sum of exactly the scores they were formed from.  No block pair
+// is skipped on its account (a far block's probabilities may underflow; the band's test stays the only skip rule), and the backward
+// kernels - dkdv, dq, delta_rows - read the saved probabilities, recompute no score and are not touched by it.
 // Both layouts of AttnBatch: packed (cu: dialogue b owns rows cu[b] .. cu[b+1]-1, no pad keys) and padded (key_pad: masked
 // keys get -inf before the softmax).  Operands are read as fp32 in both precision modes; results also go to their bf16
 // shadows when the plan keeps them (out / dq / dk / dv, and AttnProblem::no_f32 as in attention.hip).
@@ -124,9 +129,17 @@ __device__ __forceinline__ unsigned long long key_bits(const AttnBatch& ab, cons
     return __ballot(lane < nk && kp == 0);
 }
 
+// the scaled score of query iq and key j (positions in the dialogue); BIAS: plus -slope * |iq - j|, one fma - both passes of the forward
+template <bool BIAS>
+__device__ __forceinline__ float dlong_score(float acc, float scale, float nslope, int iq, int j) {
+    const float x = acc * scale;
+    if constexpr (BIAS) return __fmaf_rn(nslope, (float)abs(iq - j), x);
+    return x;
+}
 // CTM: 16-column tiles of the head dim held in registers (8: hd <= 128, 16: hd <= 256); BAND: the launch has a context band (its
-// own instantiations of the three kernels, so that a launch without one runs the code it always ran)
-template <int CTM, bool BAND>
+// own instantiations of the three kernels, so that a launch without one runs the code it always ran); BIAS (forward only): it has a
+// distance-decay bias - instantiations of their own again
+template <int CTM, bool BAND, bool BIAS = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatch ab) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -147,6 +160,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
     const int i = 16 * wv + l15, iq = q0 + i;               // this lane's query row (block-local / in the dialogue)
     const float* qrow = Qs + i * ld + lg;
     const float* kb_rows = KV + l15 * ld + lg;
+    float nslope = 0.f;                                     // BIAS: minus the head's slope
+    if constexpr (BIAS) nslope = -m2f_attn_bias_slope(w.h, P.H, m2f_attn_bias_gain(ab.bias_gain16));
 
     // pass 1: row max and normaliser
     float m_run = -INFINITY, l_run = 0.f;
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
-                s[jt][r] = ((kvalid >> j) & 1ull) ? acc[r] * scale : -INFINITY;
+                s[jt][r] = ((kvalid >> j) & 1ull) ? dlong_score<BIAS>(acc[r], scale, nslope, iq, kb + j) : -INFINITY;
                 m_blk = fmaxf(m_blk, s[jt][r]);
             }
         }
@@ -208,7 +223,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int jl = 16 * jt + 4 * lg + r, j = kb + jl;
-                const float x = ((kvalid >> jl) & 1ull) ? acc[r] * scale : -INFINITY;
+                const float x = ((kvalid >> jl) & 1ull) ? dlong_score<BIAS>(acc[r], scale, nslope, iq, j) : -INFINITY;
                 float pv = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;   // (no visible key: exp(-inf + inf) would be NaN)
                 if (iq < Lp && j < Lp) probs[(size_t)j * Lp + iq] = pv;           // lanes: consecutive iq
                 if (site) pv = m2f_keep(key, drop_idx(w.bh, LM, iq, j), ab.drop_thresh) ? pv * ab.drop_scale : 0.f;
@@ -476,6 +491,13 @@ hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)2 * BLK * (maxW + 2) * sizeof(float);
+    if (ab.bias_gain16) {                                   // distance-decay bias: instantiations of their own
+        if (has_band(ab))
+            return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true, true>, blocks, lds, stream, ab)
+                               : go(m2f_attn_dlong_fwd_kernel<16, true, true>, blocks, lds, stream, ab);
+        return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, false, true>, blocks, lds, stream, ab)
+                           : go(m2f_attn_dlong_fwd_kernel<16, false, true>, blocks, lds, stream, ab);
+    }
     if (has_band(ab))
         return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, true>, blocks, lds, stream, ab);
     return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, false>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, false>, blocks, lds, stream, ab);

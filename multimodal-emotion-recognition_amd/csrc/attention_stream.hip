@@ -35,13 +35,18 @@
 // has just arrived (a ring: utterance u sits in row u % C, which is undone here; the page table never enters: the order is logical).
 // Columns behind the live count are zeros, an inactive slot gets a row of zeros.  Ordinary per-lane vector stores, 64 consecutive
 // floats per instruction.
+//
+// BIAS (a fourth flag, its own instantiations again): the launch has a distance-decay bias (ops.h, m2f_attn_bias_slope; AttnStreamBatch::
+// bias_gain).  The new utterance is utterance n_old; cache row j holds the utterance at distance n_old - j (plain cache) or
+// (pos - j + C) % C (ring), and -slope * distance is added to the scaled score where it is written - an explicit fma, one rounding
+// rule with the dialogue kernels.  The cached rows do not depend on it.
 #include "common.h"
 #include "ops.h"
 #include "attn_stream_rows.h"
 
 namespace {
 
-template <bool BF16, bool PAGED, bool WEIGHTS>
+template <bool BF16, bool PAGED, bool WEIGHTS, bool BIAS>
 __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const AttnStreamWeights& ww) {
     typedef Row<BF16> R;
     typedef typename R::elem_t elem_t;
@@ -122,6 +127,8 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
 #pragma unroll
     for (int i = 0; i < EPL; ++i) qx[i] = sq[e0 + i];
     const float scale = 1.0f / sqrtf((float)hd);
+    float nslope = 0.f;                           // BIAS: minus the head's slope
+    if constexpr (BIAS) nslope = -m2f_attn_bias_slope(h, P.H, ab.bias_gain);
 
     // ---- pass 1: scores ---------------------------------------------------------------------------------------------------------
     for (int j0 = 0; j0 < nslots; j0 += RPW * U) {
@@ -146,7 +153,13 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
 #pragma unroll
             for (int i = 0; i < EPL; ++i) d = fmaf(qx[i], kx[u][i], d);
             for (int o = CH >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-            if (c == 0 && j < nslots) sc[j] = d * scale;
+            if constexpr (BIAS) {
+                int dist = pos - j;                                             // plain cache: pos = n_old >= j; ring: (pos - j + C) % C
+                if (dist < 0) dist += C;                                        // (0 <= pos, j < C: one wrap at most, no division)
+                if (c == 0 && j < nslots) sc[j] = __fmaf_rn(nslope, (float)dist, d * scale);
+            } else {
+                if (c == 0 && j < nslots) sc[j] = d * scale;
+            }
         }
     }
     __syncthreads();
@@ -212,21 +225,21 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     }
 }
 
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
-    attn_stream_body<BF16, false, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, AttnStreamWeights{{nullptr}});
+    attn_stream_body<BF16, false, false, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, AttnStreamWeights{{nullptr}});
 }
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
-    attn_stream_body<BF16, true, false>(ab, pg, AttnStreamWeights{{nullptr}});
+    attn_stream_body<BF16, true, false, BIAS>(ab, pg, AttnStreamWeights{{nullptr}});
 }
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_weights_kernel(const AttnStreamBatch ab, const AttnStreamWeights ww) {
-    attn_stream_body<BF16, false, true>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, ww);
+    attn_stream_body<BF16, false, true, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, ww);
 }
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_paged_weights_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const AttnStreamWeights ww) {
-    attn_stream_body<BF16, true, true>(ab, pg, ww);
+    attn_stream_body<BF16, true, true, BIAS>(ab, pg, ww);
 }
 
 // len[s] += active[s]: the one launch that closes a step
@@ -277,11 +290,29 @@ int m2f_attn_stream_prepare(AttnStreamBatch& ab, AttnStreamPaging* pg, int* maxW
 hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* paging, hipStream_t stream, const AttnStreamWeights* weights) {
     AttnStreamPaging pg = paging ? *paging : AttnStreamPaging{nullptr, 0, 0, 0, 0};
     const int blocks = ab.active ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, nullptr) : -1;
-    if (blocks < 0) return hipErrorInvalidValue;
+    if (blocks < 0 || !(ab.bias_gain >= 0.f) || ab.bias_gain > 3.0e38f) return hipErrorInvalidValue;
+    if (weights)
+        for (int i = 0; i < ab.count; ++i)
+            if (!weights->w[i] || (reinterpret_cast<uintptr_t>(weights->w[i]) & 3)) return hipErrorInvalidValue;
+    if (ab.bias_gain != 0.f) {                    // distance-decay bias: the same four forms, instantiations of their own
+        const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
+        if (weights && paging) {
+            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_paged_weights_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
+            else hipLaunchKernelGGL((m2f_attn_stream_paged_weights_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
+        } else if (weights) {
+            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_weights_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, ww);
+            else hipLaunchKernelGGL((m2f_attn_stream_weights_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, ww);
+        } else if (paging) {
+            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_paged_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, pg);
+            else hipLaunchKernelGGL((m2f_attn_stream_paged_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, pg);
+        } else {
+            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab);
+            else hipLaunchKernelGGL((m2f_attn_stream_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab);
+        }
+        return hipGetLastError();
+    }
     if (weights) {                                // the weights-emitting form: a row of [S][H][C] floats per problem
         const AttnStreamWeights ww = *weights;
-        for (int i = 0; i < ab.count; ++i)
-            if (!ww.w[i] || (reinterpret_cast<uintptr_t>(ww.w[i]) & 3)) return hipErrorInvalidValue;
         if (paging) {
             if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
             else hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);

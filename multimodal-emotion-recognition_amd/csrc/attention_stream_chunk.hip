@@ -25,6 +25,9 @@
 // the last C are stored (the others would be overwritten inside the launch).  The row a ring is about to recycle for the chunk's
 // first utterance is dead to every query and is not read at all.  No atomics, one summation order: the same bits on every run.
 // len[] is NOT advanced here: every site of a prefill call reads the same counts, m2f_launch_stream_advance_n closes the call.
+// BIAS (a third flag of the body, its own instantiations): the launch has a distance-decay bias (ops.h, m2f_attn_bias_slope;
+// AttnStreamBatch::bias_gain).  Query t is utterance n_old + t, a cached row at logical index d utterance n_old - nlive + d, an own row
+// t' utterance n_old + t'; both passes add -slope * distance through biased<>, so they form the identical score.
 #include "common.h"
 #include "ops.h"
 #include "attn_stream_rows.h"
@@ -122,6 +125,8 @@ __device__ __forceinline__ f32x4 dot_tile(const float* as, const float* brow, in
 // behind the oldest live one, d(r) = (r - p0) mod C, p0 = the oldest live utterance's row.
 struct Vis {
     int ring, C, nlive, p0, n_new;
+    // BIAS: utterances between query i and cache row r (r live and visible to i); chunk row t <= i is i - t behind
+    __device__ __forceinline__ int cached_dist(int i, int r) const { return i + nlive - (ring ? r - p0 + (r < p0 ? C : 0) : r); }
     // cache row r (r < nlive: it holds a live utterance) - its utterance j = n_old - nlive + d, visible iff j >= n_old + i - (C - 1)
     __device__ __forceinline__ bool cached(int i, int r) const {
         if (r >= nlive) return false;
@@ -133,7 +138,15 @@ struct Vis {
     __device__ __forceinline__ bool own(int i, int t) const { return t < n_new && t <= i && (!ring || t >= i - (C - 1)); }
 };
 
-template <bool BF16, bool PAGED>
+// the score of a visible key `dist` utterances behind its query: x = the scaled fp32 product; BIAS: plus -slope * dist, one fma - the one
+// statement both passes go through
+template <bool BIAS>
+__device__ __forceinline__ float biased(float x, float nslope, int dist) {
+    if constexpr (BIAS) return __fmaf_rn(nslope, (float)dist, x);
+    return x;
+}
+
+template <bool BF16, bool PAGED, bool BIAS>
 __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const int T,
                                                        const int* __restrict__ new_count) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -189,6 +202,8 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
     const int dead = (ab.ring && nlive == C) ? vis.p0 : -1; // the row the chunk's first utterance recycles: outside every query's window
 
     const float scale = 1.0f / sqrtf((float)hd);
+    float nslope = 0.f;                                     // BIAS: minus the head's slope
+    if constexpr (BIAS) nslope = -m2f_attn_bias_slope(h, P.H, ab.bias_gain);
     const int ksteps = (hd + 3) >> 2;
     const int i = 16 * wv + l15;                            // this lane's query
     const bool wave_on = 16 * wv < n_new;                   // (wave-uniform: a wave without a query only stages)
@@ -228,7 +243,9 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
             for (int jt = 0; jt < 4; ++jt) {
                 const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);      // S[i][j = 16jt + 4lg + r]
 #pragma unroll
-                for (int r = 0; r < 4; ++r) x[jt][r] = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+                for (int r = 0; r < 4; ++r)
+                    x[jt][r] = vis.cached(i, kb + 16 * jt + 4 * lg + r)
+                                   ? biased<BIAS>(acc[r] * scale, nslope, BIAS ? vis.cached_dist(i, kb + 16 * jt + 4 * lg + r) : 0) : -INFINITY;
             }
             stats(x);
         }
@@ -239,7 +256,8 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
         for (int jt = 0; jt < 4; ++jt) {
             const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x[jt][r] = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+            for (int r = 0; r < 4; ++r)
+                x[jt][r] = vis.own(i, 16 * jt + 4 * lg + r) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
         }
         stats(x);
     }
@@ -273,7 +291,8 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
                 const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float x = vis.cached(i, kb + 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+                    const float x = vis.cached(i, kb + 16 * jt + 4 * lg + r)
+                                        ? biased<BIAS>(acc[r] * scale, nslope, BIAS ? vis.cached_dist(i, kb + 16 * jt + 4 * lg + r) : 0) : -INFINITY;
                     p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;      // (no visible key: exp(-inf + inf) would be NaN)
                 }
             }
@@ -290,7 +309,7 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
             const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float x = vis.own(i, 16 * jt + 4 * lg + r) ? acc[r] * scale : -INFINITY;
+                const float x = vis.own(i, 16 * jt + 4 * lg + r) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
                 p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;
             }
         }
@@ -327,14 +346,14 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
     }
 }
 
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnStreamBatch ab, const int T, const int* __restrict__ new_count) {
-    attn_stream_chunk_body<BF16, false>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, T, new_count);
+    attn_stream_chunk_body<BF16, false, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, T, new_count);
 }
-template <bool BF16>
+template <bool BF16, bool BIAS = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const int T,
                                                                            const int* __restrict__ new_count) {
-    attn_stream_chunk_body<BF16, true>(ab, pg, T, new_count);
+    attn_stream_chunk_body<BF16, true, BIAS>(ab, pg, T, new_count);
 }
 
 // len[s] += min(max(n_new[s], 0), T): the one launch that closes a prefill call
@@ -362,8 +381,15 @@ hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPag
     AttnStreamPaging pg = paging ? *paging : AttnStreamPaging{nullptr, 0, 0, 0, 0};
     int maxW = 0;
     const int blocks = n_new && T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, &maxW) : -1;
-    if (blocks < 0) return hipErrorInvalidValue;
+    if (blocks < 0 || !(ab.bias_gain >= 0.f) || ab.bias_gain > 3.0e38f) return hipErrorInvalidValue;
     const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
+    if (ab.bias_gain != 0.f) {                              // distance-decay bias: instantiations of their own
+        if (paging)
+            return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, true>, blocks, lds, stream, ab, pg, T, n_new)
+                           : go(m2f_attn_stream_chunk_paged_kernel<false, true>, blocks, lds, stream, ab, pg, T, n_new);
+        return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, true>, blocks, lds, stream, ab, T, n_new)
+                       : go(m2f_attn_stream_chunk_kernel<false, true>, blocks, lds, stream, ab, T, n_new);
+    }
     if (paging)
         return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true>, blocks, lds, stream, ab, pg, T, n_new)
                        : go(m2f_attn_stream_chunk_paged_kernel<false>, blocks, lds, stream, ab, pg, T, n_new);

@@ -16,6 +16,10 @@ ring = len(sys.argv) > 2 and sys.argv[1] == "--ring"
 # --dlong <remarks>: the long-dialogue attention kernels (attention_dlong.hip) keep their output accumulators in registers through
 # fully unrolled loops with static indices; an unroll that fails turns them into scratch arrays - refuse the build instead.
 dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
+# --attn <remarks>: the dialogue attention forward kernels (attention.hip, m2f_attn_fwd_kernel: every NT, with and without a band, with
+# and without the distance-decay bias) keep a query tile's scores in registers through fully unrolled loops - the same rule; prints the
+# register numbers of each (DESIGN.md section 3 records the biased instantiations beside the ones they were copied from)
+attn = len(sys.argv) > 2 and sys.argv[1] == "--attn"
 # --stream <remarks>: the streaming attention kernels (attention_stream.hip) - the same rule (a wave's row chunks and accumulators)
 stream = len(sys.argv) > 2 and sys.argv[1] == "--stream"
 # --stream-chunk <remarks>: its chunk form (attention_stream_chunk.hip) - the same rule (the query block's output accumulators)
@@ -39,7 +43,7 @@ metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
 # and for the distillation criterion kernel of the same file (m2f_ce_distill_kernel; its own list below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
-path = sys.argv[2] if (ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -53,7 +57,7 @@ for line in open(path, errors="replace"):
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-        m = re.search(r"\b(VGPRs|TotalSGPRs): (\d+)", line)
+        m = re.search(r"\b(VGPRs|AGPRs|TotalSGPRs): (\d+)", line)
         if m:
             cur[m.group(1)] = int(m.group(2))
 if adam:
@@ -71,6 +75,15 @@ if adam:
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if attn:
+    kernels = [r for r in rows if "m2f_attn_fwd_kernel" in r["name"]]
+    if len(kernels) != 16:
+        sys.exit(f"check_spills: expected the sixteen m2f_attn_fwd_kernel instantiations in {path}, found {len(kernels)} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('AGPRs')} AGPRs, {r.get('scratch', 0)} bytes of scratch, "
               f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
     sys.exit(1 if bad else 0)
 if dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics:

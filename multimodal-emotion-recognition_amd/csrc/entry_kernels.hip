@@ -146,6 +146,25 @@ int m2f_attention_fwd_band(int B, int L, int H, int hd, const float* q, int ldq,
     M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
+/* the gain of the _bias entries -> what the launch descriptor holds: finite, >= 0, rounded to bf16 */
+static int bias_gain_ok(const char* who, float gain, float* applied) {
+    if (!(gain >= 0.f) || !std::isfinite(gain)) return fail(std::string(who) + ": gain must be finite and >= 0");
+    *applied = m2f_attn_bias_gain(m2f_attn_bias_gain16(gain));
+    if (!std::isfinite(*applied)) return fail(std::string(who) + ": gain is out of range");
+    return 0;
+}
+int m2f_attention_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                           const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
+                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_fwd_bias", gain, &g)) return r;
+    AttnBatch ab;
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
+    m2f_attn_set_band(ab, past, future);
+    ab.bias_gain16 = m2f_attn_bias_gain16(g);
+    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
 int m2f_attention_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                       const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream) {
@@ -198,6 +217,19 @@ int m2f_attention_varlen_fwd_band(int B, int L, int H, int hd, const float* q, i
     AttnBatch ab;
     if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
     m2f_attn_set_band(ab, past, future);
+    M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_attention_varlen_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                                  float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_varlen_fwd_bias", gain, &g)) return r;
+    AttnBatch ab;
+    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
+    m2f_attn_set_band(ab, past, future);
+    ab.bias_gain16 = m2f_attn_bias_gain16(g);
     M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -317,6 +349,35 @@ int m2f_attention_stream_weights_paged(int S, int H, int hd, const float* q, int
     if (int r = stream_attn_fill("m2f_attention_stream_weights_paged", sb, &pg, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, active, out, ldo, bf16)) return r;
     if (int r = stream_weights_ok("m2f_attention_stream_weights_paged", weights, ww)) return r;
     M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream), &ww));
+    return 0;
+}
+/* ... and the supersets with a distance-decay bias: table == NULL - dense caches; weights == NULL - no rows of probabilities */
+int m2f_attention_stream_bias(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                              void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                              const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
+                              m2f_stream_t stream) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_stream_bias", gain, &g)) return r;
+    AttnStreamBatch sb;
+    AttnStreamWeights ww;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_bias", sb, table ? &pg : nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
+    if (weights) if (int r = stream_weights_ok("m2f_attention_stream_bias", weights, ww)) return r;
+    sb.bias_gain = g;
+    M2F_HIP(m2f_launch_attn_stream(sb, table ? &pg : nullptr, static_cast<hipStream_t>(stream), weights ? &ww : nullptr));
+    return 0;
+}
+int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                    void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
+                                    int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
+                                    m2f_stream_t stream) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_stream_chunk_bias", gain, &g)) return r;
+    AttnStreamBatch sb;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_chunk_bias", sb, table ? &pg : nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
+    sb.bias_gain = g;
+    M2F_HIP(m2f_launch_attn_stream_chunk(sb, table ? &pg : nullptr, T, n_new, static_cast<hipStream_t>(stream)));
     return 0;
 }
 int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,

@@ -199,6 +199,7 @@ struct AttnBatch {
     float drop_scale;
     ShadowMap sh;              // out (fwd) / dq, dk, dv (bwd) also written as bf16
     bool bwd_fast;             // set by the launcher: the backward takes its one-round-trip path (attention.hip, attn_bwd_fast)
+    uint16_t bias_gain16;      // distance-decay bias (below): the upper 16 bits of the fp32 gain, 0 = off - in the hole behind bwd_fast, the struct keeps its size
     int bf16_math;             // bf16 mode, bit mask: 1 = the head-dim contractions (Q K^T, dO V^T) round their operands to bf16 and run
                                // on v_mfma_f32_16x16x32_bf16 (fp32 accumulate): 1/8 of the MFMA instructions at 1/2 the cycles each;
                                // 2 / 4 / 8 / 16 / 32 = the Q / K / V / dO / O slab is staged from the operand's bf16 shadow (half the bytes)
@@ -208,6 +209,23 @@ inline void m2f_attn_set_band(AttnBatch& ab, int past, int future) {      // (pa
     ab.band_past = past < 0 ? 0 : (past < cap ? past : cap) + 1;
     ab.band_future = future < 0 ? 0 : (future < cap ? future : cap) + 1;
 }
+// Distance-decay bias (ALiBi), uniform per launch: a visible key's score is fma(-slope, float(|i - j|), dot * 1/sqrt(hd)) in fp32, i and
+// j the positions the band compares.  slope = gain * base(h, H): with n = 2^floor(log2 H), base = 2^(-8 (h + 1) / n) for h < n and
+// 2^(-4 (2 (h - n) + 1) / n) behind (the recipe for head counts that are no power of two).  The gain travels as the upper half of its
+// fp32 value (what a bf16 holds), so a zeroed batch means "no bias"; the applied gain is the requested one rounded to bf16.  The one
+// definition: every kernel that forms a score (attention.hip, attention_dlong.hip, attention_stream.hip, attention_stream_chunk.hip)
+// calls it, and adds the term with an explicit __fmaf_rn.  The backward kernels read the saved probabilities and never see it.
+__host__ __device__ inline float m2f_attn_bias_slope(int h, int H, float gain) {
+    int n = 1;
+    while (2 * n <= H) n *= 2;
+    const float e = h < n ? -8.0f * (float)(h + 1) / (float)n : -4.0f * (float)(2 * (h - n) + 1) / (float)n;
+    return gain * exp2f(e);
+}
+inline uint16_t m2f_attn_bias_gain16(float gain) {                         // fp32 -> the stored half, round to nearest even (gain finite, >= 0)
+    const uint32_t u = __builtin_bit_cast(uint32_t, gain);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__host__ __device__ inline float m2f_attn_bias_gain(uint16_t g16) { return __builtin_bit_cast(float, (uint32_t)g16 << 16); }
 // bit jl = the band lets query i see key kb + jl (jl = 0 .. 63); all ones without a band
 __host__ __device__ inline unsigned long long m2f_attn_band_bits(const AttnBatch& ab, int i, int kb) {
     int lo = ab.band_past ? i - (ab.band_past - 1) - kb : 0;
@@ -298,6 +316,7 @@ struct AttnStreamBatch {
     const int* len;            // device int32 [S]
     const uint8_t* active;     // device uint8 [S]
     ShadowMap sh;              // out also written as bf16
+    float bias_gain;           // distance-decay bias (m2f_attn_bias_slope): the gain, 0 = off; the new utterance is at distance 0
 };
 size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16);     // elements (fp32 or bf16) of ONE cache (K or V) of a site
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream);      // len[s] += active[s]

@@ -207,6 +207,7 @@ struct m2f_plan {
     // M2F_BUF_DTEXT / M2F_BUF_DAUDIO, and (param_grads) the parameter gradients.  Default (0, 1): parameter gradients only.
     int in_mask = 0, param_grads = 1;
     int band_past = -1, band_future = -1;   // context band of every attention launch (m2f_plan_attention_band); negative = unlimited
+    float bias_gain = 0.f;                  // distance-decay bias of every attention launch (m2f_plan_attention_bias): the applied gain, 0 = off
     bool packed = false; int* cu = nullptr;      // T token rows owned by B dialogues through cu_seqlens, device int32 [B + 1] (m2f_plan_create_packed)
     // STREAM plan (m2f_plan_create_stream): B = S stream slots of L = 1 row each, forward only; every attention site runs the streaming
     // kernel (attention_stream.hip) against its own K / V caches of `s_cap` rows per slot, a ring when the context band has a window

@@ -540,6 +540,7 @@ void to_launches(const m2f_plan& P, const std::vector<Op>& ops, std::vector<Laun
                 l.ab.cu = P.packed ? P.cu : nullptr; l.ab.T = P.T;
                 l.ab.rng = P.rng; l.ab.drop_thresh = P.drop_thresh; l.ab.drop_scale = P.drop_scale;
                 m2f_attn_set_band(l.ab, P.band_past, P.band_future);
+                l.ab.bias_gain16 = m2f_attn_bias_gain16(P.bias_gain);
                 {   // M2F_ATTN_BF16=<mask> (read when a plan is built; AttnBatch::bf16_math): 0 keeps the fp32 slabs / contractions in bf16 mode too
                     const char* e = getenv("M2F_ATTN_BF16");
                     l.ab.bf16_math = P.prec == M2F_PREC_BF16 ? (e ? atoi(e) & 63 : 63) : 0;
@@ -981,7 +982,7 @@ void build_stream_sites(m2f_plan& P, Builder& bld) {
         AttnStreamBatch& sb = l.sb;
         memset(&sb, 0, sizeof(sb));
         sb.count = l.ab.count; sb.S = S; sb.C = P.s_cap; sb.ring = P.s_ring; sb.bf16 = bf16;
-        sb.len = P.s_len; sb.active = P.s_active;
+        sb.len = P.s_len; sb.active = P.s_active; sb.bias_gain = P.bias_gain;
         for (int i = 0; i < l.ab.count; ++i) {
             const AttnProblem& a = l.ab.pr[i];
             AttnStreamProblem& q = sb.pr[i];
@@ -1020,7 +1021,7 @@ int build_chunk_sites(m2f_plan& P, Builder& bld) {
         AttnStreamBatch& sb = l.sb;
         memset(&sb, 0, sizeof(sb));
         sb.count = l.ab.count; sb.S = P.B; sb.C = P.s_cap; sb.ring = P.s_ring; sb.bf16 = P.prec == M2F_PREC_BF16;
-        sb.len = P.s_len; sb.active = nullptr;
+        sb.len = P.s_len; sb.active = nullptr; sb.bias_gain = P.bias_gain;
         for (int i = 0; i < l.ab.count; ++i) {
             const AttnProblem& a = l.ab.pr[i];
             const AttnStreamProblem& pq = pl.sb.pr[i];

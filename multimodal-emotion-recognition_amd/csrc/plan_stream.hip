@@ -254,6 +254,7 @@ static m2f_plan* chunk_plan_new(m2f_plan* parent, int T) {
     if (!p) return nullptr;
     p->streaming = true; p->s_cap = parent->s_cap; p->s_ring = parent->s_ring;
     p->band_past = parent->band_past; p->band_future = parent->band_future;
+    p->bias_gain = parent->bias_gain;                                          // (the chunk's sites take it when they are built)
     p->s_parent = parent; p->s_chunk = T;
     p->s_pages = parent->s_pages; p->s_pg = parent->s_pg;                      // (a paged parent: the same pools through the same table)
     return p;

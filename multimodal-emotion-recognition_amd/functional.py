@@ -107,20 +107,27 @@ def quantize_fp8(src: torch.Tensor, scale: float, out: Optional[torch.Tensor] = 
 
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: torch.Tensor, B: int, L: int, H: int,
                   drop_site: int = 0, drop_p: float = 0.0, rng: Optional[torch.Tensor] = None,
-                  past: Optional[int] = None, future: Optional[int] = None):
+                  past: Optional[int] = None, future: Optional[int] = None, bias: Optional[float] = None):
     """q/k/v: [B*L, H*hd] (possibly column slices).  Returns (out [B*L, H*hd], probs^T [B*H, Lp, Lp]).
     past / future: context band - query slot i sees the valid keys of slots i - past .. i + future only (None = unlimited on that
     side; (None, 0) is causal).  Hidden keys have probability exactly 0; a query that sees no key at all (a pad slot whose band
     holds pad keys only) gets a zero row of probabilities and a zero output row, where torch's masked softmax gives NaN - pad
-    slots under a band are not the reference's numbers."""
+    slots under a band are not the reference's numbers.
+    bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): a visible key's
+    score gets -slope(h, H, gain) * |i - j|, the gain applied as `runtime.position_bias` rounds it.  The backward (`attention_bwd`) reads the saved probabilities and takes no gain."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     E = q.shape[1]
     hd = E // H
     out = torch.empty(B * L, E, dtype=torch.float32, device=q.device)
     Lp = 16 * ((L + 15) // 16)
     probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     kp = key_pad.to(torch.uint8).contiguous()
-    if past is None and future is None:
+    if gain != 0.0:
+        check(lib().m2f_attention_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                           _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                           *runtime.context_band(past, future), gain), "m2f_attention_fwd_bias")
+    elif past is None and future is None:
         check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
                                       _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_fwd")
     else:
@@ -128,6 +135,20 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
                                            _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
                                            *runtime.context_band(past, future)), "m2f_attention_fwd_band")
     return out, probs
+
+
+def position_bias_slopes(H: int, gain=1.0) -> torch.Tensor:
+    """The per-head slopes of the distance-decay attention bias (ALiBi), fp32 [H] on the CPU: head h of H adds ``-slopes[h] * |i - j|``
+    to the scaled score of query i and visible key j (positions inside the dialogue).  slopes[h] = gain * base(h, H); with
+    n = 2^floor(log2 H): base = 2^(-8 (h + 1) / n) for h < n, 2^(-4 (2 (h - n) + 1) / n) for h >= n - the recipe for head counts that
+    are no power of two (H = 4: 1/4, 1/16, 1/64, 1/256; H = 3: 1/16, 1/256, 1/4).  gain: as `runtime.position_bias` takes and rounds
+    it (to bf16: what the kernels apply); None = 0: no bias.  No parameters: a constant of the model."""
+    if isinstance(H, bool) or not isinstance(H, int) or H < 1:
+        raise ValueError(f"position_bias_slopes: H must be an integer >= 1, got {H!r}")
+    g = runtime.position_bias(gain)
+    n = 1 << (H.bit_length() - 1)
+    base = [2.0 ** (-8.0 * (h + 1) / n) if h < n else 2.0 ** (-4.0 * (2 * (h - n) + 1) / n) for h in range(H)]
+    return torch.tensor([g * b for b in base], dtype=torch.float64).to(torch.float32)
 
 
 def attention_weights(probs: torch.Tensor, B: int, L: int, H: int, key_pad: Optional[torch.Tensor] = None,
@@ -230,7 +251,7 @@ def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool =
 
 def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, lengths: torch.Tensor,
                      active: torch.Tensor, H: int, ring: bool = False, bf16: bool = False,
-                     weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     weights: Optional[torch.Tensor] = None, bias: Optional[float] = None) -> torch.Tensor:
     """One streaming-attention launch (m2f_attention_stream): slot s takes the new rows q[s] / k[s] / v[s] ([S, H*hd] fp32, possibly column
     slices) against the rows it has cached.  kcache / vcache: `attention_stream_caches`; lengths int32 [S] = utterances cached so far
     (read, NOT advanced); active uint8 / bool [S].  An active slot stores its new K / V rows at row lengths % capacity (ring) or
@@ -238,8 +259,11 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
     inactive slot gets a zero row and its caches stay as they are.  Returns out [S, H*hd].
     weights: a contiguous fp32 [S, H, capacity] tensor - the launch (m2f_attention_stream_weights, the weights-emitting form of the
     kernel) also fills it with each slot's row of attention probabilities in logical order: column t = the t-th oldest live utterance
-    (`streaming.logical_columns`), the last live column the new one; zeros behind the live count and for inactive slots.  Same `out`, same bits."""
+    (`streaming.logical_columns`), the last live column the new one; zeros behind the live count and for inactive slots.  Same `out`, same bits.
+    bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): the new utterance
+    is at distance 0, the one cached before it at distance 1, ...; the cached rows do not depend on it."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     S, E = q.shape
     hd = E // H
     C = kcache.shape[2]
@@ -251,6 +275,11 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
         raise ValueError("attention_stream: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    if gain != 0.0:
+        check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None, 0, 0, 0,
+                                              C, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights), gain,
+                                              stream_ptr()), "m2f_attention_stream_bias")
+        return out
     if weights is not None:
         check(lib().m2f_attention_stream_weights(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C,
                                                  int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights),
@@ -268,13 +297,16 @@ def _stream_weights_ok(who: str, weights, S: int, H: int, C: int) -> None:
 
 
 def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
-                           lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, ring: bool = False, bf16: bool = False) -> torch.Tensor:
+                           lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, ring: bool = False, bf16: bool = False,
+                           bias: Optional[float] = None) -> torch.Tensor:
     """One chunk launch of the streaming attention (m2f_attention_stream_chunk): slot s takes its first new[s] (int32 [S], 0 .. T, T <= 64)
     rows of q / k / v ([S*T, H*hd] fp32, possibly column slices; rows s*T + t) against the rows it has cached - row by row what new[s]
     `attention_stream` launches give.  lengths int32 [S] is read, NOT advanced.  The new K / V rows go to rows (lengths + t) % capacity
     (ring) or lengths + t (lengths + new <= capacity required, else the slot is left untouched) - of more than `capacity` rows on a ring
-    the last `capacity`.  Rows t >= new[s] of the result are zeros and their input rows are never read.  Returns out [S*T, H*hd]."""
+    the last `capacity`.  Rows t >= new[s] of the result are zeros and their input rows are never read.  Returns out [S*T, H*hd].
+    bias: as `attention_stream` - row t of a chunk is utterance lengths + t."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     rows, E = q.shape
     hd = E // H
     S, C = kcache.shape[0], kcache.shape[2]
@@ -286,6 +318,11 @@ def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kc
     if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S:
         raise ValueError("attention_stream_chunk: lengths int32 [S] and new int32 [S] required")
     out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    if gain != 0.0:
+        check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None,
+                                                    0, 0, 0, C, int(ring), ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), gain,
+                                                    stream_ptr()), "m2f_attention_stream_chunk_bias")
+        return out
     check(lib().m2f_attention_stream_chunk(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
                                            ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk")
     return out
@@ -316,13 +353,15 @@ def _paged_args(who: str, kpool, vpool, table, S: int, capacity: int, bf16: bool
 
 def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
                            lengths: torch.Tensor, active: torch.Tensor, H: int, capacity: int, ring: bool = False,
-                           bf16: bool = False, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           bf16: bool = False, weights: Optional[torch.Tensor] = None, bias: Optional[float] = None) -> torch.Tensor:
     """`attention_stream` over page pools (m2f_attention_stream_paged): logical cache row r of slot s - the row `attention_stream` calls r -
     is row r % page_rows of page table[s, r // page_rows].  kpool / vpool: `attention_stream_pools`; table int32 [S, ceil(capacity /
     page_rows)], read only at the entries of pages that hold a live row or take the new one.  The same bits as `attention_stream` on
     caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd].
-    weights: as `attention_stream` (m2f_attention_stream_weights_paged) - the order is logical, so the rows are the dense launch's bits."""
+    weights: as `attention_stream` (m2f_attention_stream_weights_paged) - the order is logical, so the rows are the dense launch's bits.
+    bias: as `attention_stream`."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     S, E = q.shape
     hd = E // H
     n_pages, R = _paged_args("attention_stream_paged", kpool, vpool, table, S, capacity, bf16)
@@ -331,6 +370,11 @@ def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kp
         raise ValueError("attention_stream_paged: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    if gain != 0.0:
+        check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
+                                              table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
+                                              int(bf16), ptr(weights), gain, stream_ptr()), "m2f_attention_stream_bias")
+        return out
     if weights is not None:
         check(lib().m2f_attention_stream_weights_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
                                                        ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act),
@@ -345,10 +389,12 @@ def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kp
 
 def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
                                  table: torch.Tensor, lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, capacity: int,
-                                 ring: bool = False, bf16: bool = False) -> torch.Tensor:
+                                 ring: bool = False, bf16: bool = False, bias: Optional[float] = None) -> torch.Tensor:
     """`attention_stream_chunk` over page pools (m2f_attention_stream_chunk_paged; layout: `attention_stream_paged`).  q / k / v hold
-    S * T rows, S = table.shape[0].  The same bits, output and stored rows, as the dense chunk launch.  Returns out [S*T, H*hd]."""
+    S * T rows, S = table.shape[0].  The same bits, output and stored rows, as the dense chunk launch.  Returns out [S*T, H*hd].
+    bias: as `attention_stream_chunk`."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     rows, E = q.shape
     hd = E // H
     S = lengths.numel()
@@ -358,6 +404,11 @@ def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     if lengths.dtype != torch.int32 or new.dtype != torch.int32 or new.numel() != S:
         raise ValueError("attention_stream_chunk_paged: lengths int32 [S] and new int32 [S] required")
     out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    if gain != 0.0:
+        check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
+                                                    ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
+                                                    ptr(out), _ld(out), int(bf16), gain, stream_ptr()), "m2f_attention_stream_chunk_bias")
+        return out
     check(lib().m2f_attention_stream_chunk_paged(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
                                                  ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
                                                  ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk_paged")
@@ -448,15 +499,18 @@ def _varlen_rows(cu: Optional[torch.Tensor], key_pad: Optional[torch.Tensor]):
 def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, L: int, H: int,
                          cu: Optional[torch.Tensor] = None, key_pad: Optional[torch.Tensor] = None, drop_site: int = 0,
                          drop_p: float = 0.0, rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
-                         future: Optional[int] = None, probs: Optional[torch.Tensor] = None):
+                         future: Optional[int] = None, probs: Optional[torch.Tensor] = None, bias: Optional[float] = None):
     """Long-dialogue attention (m2f_attention_varlen_fwd, L <= 512).  q/k/v: [T, H*hd] (possibly column slices) with either
     cu (int [B+1]: dialogue b = rows cu[b] .. cu[b+1]-1, T = q.shape[0]) or key_pad ([B, L] or [B*L], True = padded key;
     T = B*L).  Returns (out [T, H*hd], probs^T [B*H, Lp, Lp]).
     past / future: context band as in `attention_fwd`, over utterance positions inside the dialogue (packed: row minus cu[b]).  Pairs
     of 64-row blocks that the band hides as a whole are skipped: their part of the probabilities buffer is NOT written (zeros in
     the fresh buffer made here; whatever it held in a buffer passed as `probs`), and `attention_varlen_bwd` given the same band
-    does not read it."""
+    does not read it.
+    bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): a visible key's
+    score gets -slope(h, H, gain) * |i - j|, the gain applied as `runtime.position_bias` rounds it."""
     runtime.require_gpu()
+    gain = runtime.position_bias(bias)                  # (raises ValueError)
     T, E = q.shape
     hd = E // H
     cu32, kp = _varlen_rows(cu, key_pad)
@@ -465,7 +519,11 @@ def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: i
     if probs is None:
         probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     assert probs.shape == (B * H, Lp, Lp) and probs.is_contiguous() and probs.dtype == torch.float32 and probs.is_cuda
-    if past is None and future is None:
+    if gain != 0.0:
+        check(lib().m2f_attention_varlen_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                                  ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                                  *runtime.context_band(past, future), gain), "m2f_attention_varlen_fwd_bias")
+    elif past is None and future is None:
         check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
                                              ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()),
               "m2f_attention_varlen_fwd")
@@ -604,10 +662,11 @@ def cross_entropy_distill(logits: torch.Tensor, teacher: torch.Tensor, labels: t
 
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
-                      need_weights: bool = False):
+                      need_weights: bool = False, bias: Optional[float] = None):
     """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity.  past / future: context band of its
     attention (`attention_fwd`); the reference has none.  need_weights: also the head-averaged attention map [B, L, L] that the
-    reference's own call computes and drops (`attention_weights`)."""
+    reference's own call computes and drops (`attention_weights`).  bias: gain of the distance-decay bias of its attention
+    (`attention_fwd`); None = off."""
     B, L, E = text.shape
     t = text.reshape(B * L, E).contiguous()
     a = audio.reshape(B * L, E).contiguous()
@@ -615,9 +674,9 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     k = gemm(a, in_w[E:2 * E], NT, precision, bias=in_b[E:2 * E])
     v = gemm(t, in_w[2 * E:], NT, precision, bias=in_b[2 * E:])
     if L > 64:          # (the dialogue kernels of attention_fwd hold L <= 64; above, the long-dialogue kernels, padded form)
-        att, probs = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future)
+        att, probs = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future, bias=bias)
     else:
-        att, probs = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future)
+        att, probs = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future, bias=bias)
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
     if need_weights:

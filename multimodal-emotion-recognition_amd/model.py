@@ -84,8 +84,11 @@ class FusionAttentionModule(nn.Module):
     """Mirror of reference src/model.py:5-20.  Inside ``M2FNet`` it is a parameter holder (the fusion stack
     runs in the plan); called on its own it executes the same gfx950 kernels layer-wise (inference only)."""
 
-    def __init__(self, embedding_size: int, n_head: int, dropout: float):
+    def __init__(self, embedding_size: int, n_head: int, dropout: float, position_bias: Optional[float] = None):
         super().__init__()
+        # gain of the distance-decay attention bias of a standalone call (runtime.position_bias: None = off; stored as applied);
+        # inside M2FNet the model's own setting rules (M2FNet.set_position_bias), this attribute is not read
+        self.position_bias = runtime.position_bias(position_bias) or None
         self.multihead_attention = _MHAParams(embedding_size, n_head)
         self.linear = _LinearParams(2 * embedding_size, embedding_size)
         self.relu = nn.ReLU()
@@ -96,7 +99,8 @@ class FusionAttentionModule(nn.Module):
         """past / future: context band of the attention (``functional.attention_fwd``): text utterance i attends to the audio of
         utterances i - past .. i + future only, None = unlimited.  The reference's module has no such argument.
         need_weights: return ``(y, weights [B, L, L])`` - the head-averaged attention map that the reference's own
-        ``nn.MultiheadAttention`` call computes and drops (src/model.py:14); default: ``y`` alone, as ever."""
+        ``nn.MultiheadAttention`` call computes and drops (src/model.py:14); default: ``y`` alone, as ever.
+        The module's ``position_bias`` (constructor; None = off) adds the distance-decay bias of ``functional.attention_fwd``."""
         from . import functional as F
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("standalone FusionAttentionModule.forward is inference-only; train it inside M2FNet "
@@ -104,7 +108,7 @@ class FusionAttentionModule(nn.Module):
         return F.fam_layer_forward(text, audio, key_padding_mask, self.multihead_attention.in_proj_weight,
                                    self.multihead_attention.in_proj_bias, self.multihead_attention.out_proj.weight,
                                    self.multihead_attention.out_proj.bias, self.linear.weight, self.linear.bias,
-                                   self.n_head, past=past, future=future, need_weights=need_weights)
+                                   self.n_head, past=past, future=future, need_weights=need_weights, bias=self.position_bias)
 
 
 class _Anchor(torch.autograd.Function):
@@ -250,11 +254,12 @@ class _Engine:
         return Bb, Lb
 
     @staticmethod
-    def plan_key(B, L, T, want_backward, dropout_active, precision, outputs=(0, True), band=(None, None)) -> Tuple:
-        """A plan's key without its instance number.  Only a non-default `outputs` / context band extends the tuple: the keys of a
-        model that uses neither are what they were before either existed."""
+    def plan_key(B, L, T, want_backward, dropout_active, precision, outputs=(0, True), band=(None, None), bias=None) -> Tuple:
+        """A plan's key without its instance number.  Only a non-default `outputs` / context band / position bias (the applied gain;
+        None or 0 = off) extends the tuple: the keys of a model that uses none of them are what they were before any existed."""
         key = (B, L, T, want_backward, dropout_active, precision) + (() if outputs == (0, True) else (outputs,))
-        return key if band == (None, None) else key + (("context",) + tuple(band),)
+        key = key if band == (None, None) else key + (("context",) + tuple(band),)
+        return key if not bias else key + (("position_bias", float(bias)),)
 
     def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None,
              outputs: Tuple[int, bool] = (0, True)) -> runtime.Plan:
@@ -263,7 +268,8 @@ class _Engine:
         85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64).
         outputs: what a backward computes - (input_mask, parameter gradients) of m2f_plan_backward_outputs; part of the key, so a
         plan of one setting never flips to another (train_step always uses the default (0, True)).
-        The model's context band (M2FNet.context) is part of the key in the same way: every band has its own plans."""
+        The model's context band (M2FNet.context) is part of the key in the same way: every band has its own plans; so is its
+        position bias (M2FNet.position_bias)."""
         b_in, l_in = B, L
         if self.shape_buckets:
             B, L = self.bucket(B, L)
@@ -278,7 +284,8 @@ class _Engine:
                 T = min(max(Tb, B), B * L)            # (every dialogue full: no spare row - runtime.Plan handles that)
         outputs = (int(outputs[0]), bool(outputs[1]))
         band = self.model.context                         # (read per call: M2FNet.set_context only changes which plans are handed out)
-        base = self.plan_key(B, L, T, want_backward, dropout_active, self.precision, outputs, band)
+        bias = self.model.position_bias                   # (read per call, as the band)
+        base = self.plan_key(B, L, T, want_backward, dropout_active, self.precision, outputs, band, bias)
         inst, key, pl, oldest = 0, None, None, None
         while True:                                       # first instance of this shape that no live autograd graph owns
             key = base + (inst,)
@@ -312,6 +319,8 @@ class _Engine:
                 pl.backward_outputs(*outputs)
             if band != (None, None):
                 pl.attention_band(*band)                  # (once, before its first launch: a plan keeps the band of its key)
+            if bias:
+                pl.attention_bias(bias)                   # (likewise: a plan keeps the gain of its key)
             self.plans[key] = pl
             self._evict(max(self.max_plans, 1), self.max_plan_bytes, protect=key)
         else:
@@ -419,11 +428,14 @@ class M2FNet(nn.Module):
     was; a partly frozen model computes and publishes all parameter gradients as before."""
 
     def __init__(self, config, precision: Optional[str] = None, shape_buckets: Optional[bool] = None,
-                 packed: Optional[bool] = None, context: Optional[Tuple[Optional[int], Optional[int]]] = None):
+                 packed: Optional[bool] = None, context: Optional[Tuple[Optional[int], Optional[int]]] = None,
+                 position_bias: Optional[float] = None):
         super().__init__()
         self.config = config
         self._context: Tuple[Optional[int], Optional[int]] = (None, None)
         self.set_context(*(context if context is not None else (None, None)))
+        self._position_bias: Optional[float] = None
+        self.set_position_bias(position_bias)
         # packed ("varlen") token layout for `train_step` and no-grad `forward` (runtime.Plan, m2f_plan_create_packed): a ragged
         # batch costs its valid utterances, not B x L slots; needs the batch's valid count on the host (one sync per call).
         # Off by default (M2F_PACKED=1 or packed=True): the reference's batches reach the model as padded tensors either way
@@ -503,6 +515,24 @@ class M2FNet(nn.Module):
         they do the pad slots of packed plans.  Takes effect at the next call; each band keeps its own plans, none is rewritten."""
         runtime.context_band(past, future)                 # (raises ValueError)
         self._context = (past, future)
+
+    # -- position bias ---------------------------------------------------------------------------------
+    @property
+    def position_bias(self) -> Optional[float]:
+        """The APPLIED gain of the distance-decay attention bias (the requested one rounded to bf16), or None when it is off."""
+        return self._position_bias
+
+    def set_position_bias(self, gain: Optional[float] = None) -> None:
+        """Distance-decay bias (ALiBi) of EVERY attention site - both modality encoders and every fusion layer: the score of query
+        utterance i and visible key utterance j of head h gets ``-slope(h, H, gain) * |i - j|`` (``functional.position_bias_slopes``
+        has the fixed geometric slopes), so near utterances weigh more than far ones where the reference's attention cannot tell
+        them apart.  ``gain``: a finite number >= 0 - 1.0 is ALiBi - applied as rounded to bf16 (``position_bias`` reports the applied
+        value); None or 0, the default: off, bit for bit what the model computed before.  One gain for the whole model, as the
+        band: one unbiased site in the stack would see another geometry.  No parameters: ``state_dict``, checkpoints and optimizers
+        are untouched.  Reaches ``forward``, autograd, ``train_step``, ``eval_step``, attention maps, ``Distiller`` and data-parallel
+        steps through the plans; takes effect at the next call, and every gain keeps its own plans.  A ``DialogueStream`` keeps
+        the gain it was created under (``DialogueStream.position_bias``) and refuses to run after a change."""
+        self._position_bias = runtime.position_bias(gain) or None
 
     # -- reference surface -----------------------------------------------------------------------------
     def forward(self, text, audio, mask):

@@ -8,7 +8,9 @@ first use raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
+import struct
 import subprocess
 from typing import Dict, Optional, Tuple
 
@@ -134,6 +136,19 @@ SIGNATURES = {
                                               c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
     "m2f_plan_attention_band": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_get_attention_band": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "m2f_plan_attention_bias": (c_int, [c_void_p, c_float]),
+    "m2f_plan_get_attention_bias": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "m2f_attention_fwd_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int, c_float]),
+    "m2f_attention_varlen_fwd_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
+                                              c_int, c_int, c_float]),
+    "m2f_attention_stream_bias": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
+                                          c_void_p]),
+    "m2f_attention_stream_chunk_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                                c_void_p]),
     "m2f_stream_workspace_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int]),
     "m2f_plan_create_stream": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_step": (c_int, [c_void_p, c_int, c_void_p]),
@@ -306,6 +321,28 @@ def context_band(past, future) -> Tuple[int, int]:
             raise ValueError(f"context band: {name} must be None (unlimited) or an integer >= 0, got {v!r}")
         out.append(v)
     return out[0], out[1]
+
+
+def position_bias(gain) -> float:
+    """The gain of the distance-decay attention bias (ALiBi: a visible key's score gets ``-slope(h, H, gain) * |i - j|``,
+    ``functional.position_bias_slopes``) as the kernels APPLY it: None -> 0.0 (off); a finite number >= 0 -> that number rounded to
+    bf16, round to nearest even (the launch descriptors hold 16 bits of it; 1.0, 0.5, 2.0 are exact); anything else raises ValueError."""
+    if gain is None:
+        return 0.0
+    if isinstance(gain, bool) or not isinstance(gain, (int, float)):
+        raise ValueError(f"position bias: the gain must be None (off) or a finite number >= 0, got {gain!r}")
+    g = float(gain)
+    if not math.isfinite(g) or g < 0.0:
+        raise ValueError(f"position bias: the gain must be None (off) or a finite number >= 0, got {gain!r}")
+    try:
+        u = struct.unpack("<I", struct.pack("<f", g))[0]
+    except OverflowError:
+        raise ValueError(f"position bias: the gain {gain!r} is out of range") from None
+    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    out = struct.unpack("<f", struct.pack("<I", u & 0xFFFFFFFF))[0]
+    if not math.isfinite(out):
+        raise ValueError(f"position bias: the gain {gain!r} is out of range")
+    return out
 
 
 def c_param_layout(c: M2FConfig) -> Tuple[list, list, int]:
@@ -695,6 +732,19 @@ class Plan:
         check(lib().m2f_plan_get_attention_band(self._h(), ctypes.byref(a), ctypes.byref(b)), "m2f_plan_get_attention_band")
         return (None if a.value < 0 else a.value, None if b.value < 0 else b.value)
 
+    def attention_bias(self, gain) -> float:
+        """m2f_plan_attention_bias: the distance-decay bias of EVERY attention site of the plan (`position_bias` has the rule and the
+        rounding); None / 0 = off.  Returns the applied gain.  A change drops the captured graphs; between steps only."""
+        check(lib().m2f_plan_attention_bias(self._h(), position_bias(gain)), "m2f_plan_attention_bias")
+        return self.bias
+
+    @property
+    def bias(self) -> float:
+        """The gain as the plan's launches apply it (0.0 = off)."""
+        g = c_float(0.0)
+        check(lib().m2f_plan_get_attention_bias(self._h(), ctypes.byref(g)), "m2f_plan_get_attention_bias")
+        return float(g.value)
+
     def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
         """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |
         IN_AUDIO) and / or the parameter gradients.  A change rebuilds the launch lists and drops the captured graphs, the fused-optimizer
@@ -914,6 +964,8 @@ class StreamPlan:
                                        stream_ptr()), "m2f_stream_scatter")
 
     attention_sites = Plan.attention_sites
+    attention_bias = Plan.attention_bias         # (before the first step or between steps; a chunk plan takes it when it is created)
+    bias = Plan.bias
 
     def stream_attention(self, on: bool) -> None:
         """m2f_plan_stream_attention: from the next step on the attention launches also store each (slot, head)'s row of probabilities
@@ -1003,6 +1055,8 @@ class StreamChunkPlan:
     _h = Plan._h
     _view = Plan._view
     params_fresh = StreamPlan.params_fresh
+    attention_bias = Plan.attention_bias         # (created with the parent's gain; a change drops the captured prefill)
+    bias = Plan.bias
     nbytes = StreamPlan.nbytes
     close = StreamPlan.close
 

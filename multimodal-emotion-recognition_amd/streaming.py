@@ -492,6 +492,13 @@ class DialogueStream:
     ordered before any later write of the stream.  ``fork(src, dst)`` is ``restore(snapshot([src]), [dst])``.  A SNAPSHOT BELONGS TO THE
     WEIGHTS THAT WROTE IT: the rule above for the caches holds for what was copied out of them.
 
+    POSITION BIAS: the stream, and its chunk plan, take the model's distance-decay gain (``M2FNet.position_bias``) when they are created;
+    ``position_bias`` reports it (the applied value, or None).  The new utterance is at distance 0 from itself, the cached ones at
+    their distance in utterances; the caches of deeper layers depend on the gain as they depend on the weights.  After
+    ``model.set_position_bias`` to another gain ``step`` / ``prefill`` / ``run`` / ``restore`` raise RuntimeError: ``reset()`` of the whole
+    stream adopts the model's gain (every dialogue starts over), or build a new stream.  The snapshot format and its signature do
+    not carry the gain: A SNAPSHOT BELONGS TO THE WEIGHTS AND THE GAIN THAT WROTE IT, and neither is checked.
+
     ATTENTION ROWS (``attention=True``): every step's attention launches run the weights-emitting form of their kernel and keep, per
     site, slot and head, the new utterance's row of probabilities over the cached ones (``sum_sites H * S * capacity * 4 B``; the same
     logits bit for bit, the step still one replayed graph).  ``attention(average_heads=True, sites=None)`` after a ``step`` returns
@@ -512,6 +519,9 @@ class DialogueStream:
         self.pages, self.page_rows = resolve_pages(pages, page_rows)
         self.plan = runtime.StreamPlan(cfg, self.max_streams, self.capacity, self.past, eng.precision, eng.flat, eng.wshadow,
                                        self.pages, self.page_rows)
+        self._bias: Optional[float] = model.position_bias     # (the applied gain or None; the chunk plan below takes the step plan's)
+        if self._bias:
+            self.plan.attention_bias(self._bias)
         self.allocator = PageAllocator(self.pages, self.max_streams, self.capacity, self.page_rows) if self.pages else None
         self.chunk_plan = runtime.StreamChunkPlan(self.plan, self.max_chunk, eng.flat, eng.wshadow) if self.max_chunk > 1 else None
         self.lengths: List[int] = [0] * self.max_streams
@@ -552,6 +562,17 @@ class DialogueStream:
                                "without dropout - call model.eval() first")
 
     @property
+    def position_bias(self) -> Optional[float]:
+        """The gain of the distance-decay attention bias this stream runs under (the applied value; None: off)."""
+        return self._bias
+
+    def _refuse_bias(self, what: str) -> None:
+        if self.model.position_bias != self._bias:
+            raise RuntimeError(f"DialogueStream.{what}: the model's position bias is now {self.model.position_bias!r}, this stream's caches "
+                               f"were written under {self._bias!r}; reset() the whole stream (it then takes the model's gain) or "
+                               "build a new one with model.stream(...)")
+
+    @property
     def pages_free(self) -> Optional[int]:
         """Free pages of a paged stream's pool (None: a dense stream)."""
         return None if self.allocator is None else self.allocator.pages_free
@@ -575,6 +596,7 @@ class DialogueStream:
     def _step(self, text, audio, act: List[bool]) -> torch.Tensor:
         """act: one entry per slot (rows of text / audio may be fewer: the leading slots)."""
         self._refuse_training("step")
+        self._refuse_bias("step")
         if self.past is None:
             full = [s for s, a in enumerate(act) if a and self.lengths[s] >= self.capacity]
             if full:
@@ -656,6 +678,7 @@ class DialogueStream:
     def prefill(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], counts: Optional[Sequence[int]] = None) -> torch.Tensor:
         S = self.max_streams
         self._refuse_training("prefill")
+        self._refuse_bias("prefill")
         cfg = self.plan.cfg
         n = None
         for x, on, name in ((text, cfg.text_enabled, "text"), (audio, cfg.audio_enabled, "audio")):
@@ -703,6 +726,11 @@ class DialogueStream:
         S = self.max_streams
         self._attn_act = None
         if slots is None:
+            if self.model.position_bias != self._bias:     # (every dialogue starts over: the stream follows the model's gain)
+                self._bias = self.model.position_bias
+                for pl in (self.plan, self.chunk_plan):
+                    if pl is not None:
+                        pl.attention_bias(self._bias)
             self._on_stream(lambda: self.plan.reset(None))
             self.lengths = [0] * S
             if self.allocator is not None:
@@ -735,6 +763,7 @@ class DialogueStream:
         S = self.max_streams
         if B > S:
             raise ValueError(f"stream.run: {B} dialogues do not fit {S} stream slots")
+        self._refuse_bias("run")
         self.reset(range(B))
         valid = (~mask.bool()).cpu()
         counts = prefix_counts(valid) if self.max_chunk > 1 else None
@@ -806,6 +835,7 @@ class DialogueStream:
         return self._snapshot(slots, pinned=False)
 
     def restore(self, snap: StreamSnapshot, slots: Optional[Sequence[int]] = None) -> None:
+        self._refuse_bias("restore")
         if snap.signature != self.signature:
             raise ValueError(f"stream.restore: the snapshot was written under (sites (H, hd), bf16, past, ring capacity) = {snap.signature}, "
                              f"this stream runs {self.signature}")

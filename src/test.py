@@ -201,16 +201,17 @@ def print_class_report(report):
 
 
 def build_model(config, device):
-    """The model as train.py built it (train.build_model): runtime.precision and runtime.context, so a model trained under a context
-    band is tested under it."""
+    """The model as train.py built it (train.build_model): runtime.precision, runtime.context and runtime.position_bias, so a model
+    trained under a context band or a position bias is tested under it."""
     from train import build_model as build
     return build(config, device)
 
 
 def main(config=None):
     config = get_config()
-    from train import context_settings
+    from train import context_settings, position_bias_settings
     context_settings(config)                               # (refusal before the GPU is touched)
+    position_bias_settings(config)
     streaming = streaming_settings(config)
     stream_chunk = stream_chunk_settings(config)
     stream_pages = stream_pages_settings(config)

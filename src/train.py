@@ -116,15 +116,16 @@ def ema_settings(cfg):
     return float(decay), flags["warmup"], flags["evaluate"]
 
 
-DISTILL_KEYS = ("enabled", "teacher_checkpoint", "teacher_weights", "alpha", "temperature", "teacher_context")
+DISTILL_KEYS = ("enabled", "teacher_checkpoint", "teacher_weights", "alpha", "temperature", "teacher_context", "teacher_position_bias")
 
 
 def resolve_distill(cfg):
-    """`runtime.distill` = {enabled, teacher_checkpoint, teacher_weights, alpha, temperature, teacher_context}: train the model against
+    """`runtime.distill` = {enabled, teacher_checkpoint, teacher_weights, alpha, temperature, teacher_context, teacher_position_bias}: train the model against
     the logits of a teacher with the `model:` geometry whose weights come from a checkpoint this loop wrote (mer_amd.distill) - the
     usual case is an online student (runtime.context: {past: ..., future: 0}) under an offline teacher (teacher_context both null).
     teacher_weights: model | ema picks the checkpoint's model_state_dict or the parameters of its ema_state_dict.  -> None when the block
-    is absent or disabled, else a dict {checkpoint, weights, alpha, temperature, context}.  Checked on the host before the GPU is
+    is absent or disabled, else a dict {checkpoint, weights, alpha, temperature, context} - plus position_bias when teacher_position_bias
+    (the teacher's own distance-decay gain; absent or null = none, `position_bias_settings` has the rule) is set.  Checked on the host before the GPU is
     touched: needs runtime.fused_step: True (the criterion lives in the train step)."""
     from mer_amd.distill import check_distill
     block = _runtime(cfg, "distill", None)
@@ -155,6 +156,7 @@ def resolve_distill(cfg):
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
             raise ValueError(f"runtime.distill.teacher_context.{k} must be null or an integer >= 0 (got {v!r})")
         band.append(v)
+    bias = _position_bias_value(block.get("teacher_position_bias", None), "runtime.distill.teacher_position_bias")
     path = block.get("teacher_checkpoint", None)
     if path is not None and not isinstance(path, str):
         raise ValueError(f"runtime.distill.teacher_checkpoint must be null or a path (got {path!r})")
@@ -164,7 +166,10 @@ def resolve_distill(cfg):
         raise ValueError("runtime.distill.enabled needs runtime.distill.teacher_checkpoint: a checkpoint written by this loop")
     if not bool(_runtime(cfg, "fused_step", True)):
         raise ValueError("runtime.distill.enabled needs runtime.fused_step: True (the distillation criterion lives in the train step)")
-    return {"checkpoint": path, "weights": weights, "alpha": alpha, "temperature": temperature, "context": (band[0], band[1])}
+    out = {"checkpoint": path, "weights": weights, "alpha": alpha, "temperature": temperature, "context": (band[0], band[1])}
+    if bias is not None:                                   # (only a teacher WITH a bias extends the settings: the others are what they were)
+        out["position_bias"] = bias
+    return out
 
 
 def attach_distiller(config, model, device):
@@ -183,7 +188,8 @@ def attach_distiller(config, model, device):
         weights = state[EMA_KEY]["parameters"]
     else:
         weights = state["model_state_dict"]
-    teacher = M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=settings["context"])
+    teacher = M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=settings["context"],
+                     position_bias=settings.get("position_bias"))
     teacher.load_state_dict(weights)
     teacher = teacher.to(device)
     distiller = Distiller(model, teacher, alpha=settings["alpha"], temperature=settings["temperature"])
@@ -222,10 +228,29 @@ def context_settings(cfg):
     return None if band == [None, None] else (band[0], band[1])
 
 
+def _position_bias_value(v, where):
+    """null -> None; a finite number >= 0 -> itself (0 -> None: off); anything else: ValueError naming `where`."""
+    from mer_amd.runtime import position_bias
+    try:
+        return position_bias(v) and float(v) or None
+    except ValueError:
+        raise ValueError(f"{where} must be null or a finite number >= 0: the gain of the distance-decay attention bias, 1.0 is ALiBi "
+                         f"(got {v!r})") from None
+
+
+def position_bias_settings(cfg):
+    """`runtime.position_bias`: null (default) or a finite number >= 0 - the gain of the distance-decay attention bias of every attention
+    site of the model (M2FNet(position_bias=...): score(i, j) -= slope_h * gain * |i - j|; 1.0 is ALiBi, applied as rounded to bf16).
+    -> None when absent, null or 0, else the number.  Checked on the host before the GPU is touched."""
+    return _position_bias_value(_runtime(cfg, "position_bias", None), "runtime.position_bias")
+
+
 def build_model(config, device):
-    """The M2FNet of `config` on `device` as train.py and test.py both build it: runtime.precision and runtime.context - so a model
-    trained under a context band is validated and tested under the same band."""
-    return M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=context_settings(config)).to(device)
+    """The M2FNet of `config` on `device` as train.py and test.py both build it: runtime.precision, runtime.context and
+    runtime.position_bias - so a model trained under a context band or a position bias is validated and tested, streamed or not, under
+    the same."""
+    return M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=context_settings(config),
+                  position_bias=position_bias_settings(config)).to(device)
 
 
 def watch_settings(cfg, world: int = 1):
@@ -515,6 +540,7 @@ def main(config=None):
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
     context_settings(config)
+    position_bias_settings(config)
     resolve_distill(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
