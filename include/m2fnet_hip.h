@@ -60,7 +60,9 @@ enum {
     M2F_BUF_TEACHER = 16,       /* float [B*L, cls_out]  train plans, input of the distillation criterion: the teacher's logits, token rows as M2F_BUF_LOGITS */
     M2F_BUF_DISTILL = 17,       /* float [2]  train plans, input of the distillation criterion: alpha, tau (read on the device at every step) */
     M2F_BUF_STREAM_ATTN = 18,   /* float [sites][S][H_site][C]  stream plans with m2f_plan_stream_attention on: the caller's buffer (NULL: off) */
-    M2F_BUF_COUNT = 19
+    M2F_BUF_SPEAKERS = 19,      /* uint8 [T]  input of a plan with speaker heads (m2f_plan_attention_speakers): the speaker id of every token row, in the plan's token order (padded: [B*L] as M2F_BUF_KEYPAD; packed: row cu[b] + i); stream plans: [S], chunk plans [S*T] - the new utterances' ids */
+    M2F_BUF_STREAM_SPEAKERS = 20,   /* uint8 [S][C]  stream plans with speaker heads: the caller's buffer of cached speaker ids by logical cache row (m2f_plan_stream_speakers; NULL: none) */
+    M2F_BUF_COUNT = 21
 };
 
 const char* m2f_last_error(void);
@@ -155,6 +157,25 @@ int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
  * when it is created.  A change destroys the captured graphs; call it between steps, never between a forward and its backward. */
 int m2f_plan_attention_bias(m2f_plan* plan, float gain);
 int m2f_plan_get_attention_bias(m2f_plan* plan, float* gain);
+/* SPEAKER HEADS of EVERY attention site of the plan: at a site with H heads, heads 0 .. n_same - 1 let query utterance i see key j only
+ * if speakers[j] == speakers[i] (the utterance itself always qualifies), heads n_same .. n_same + n_other - 1 only if they differ, the
+ * other heads are untouched.  The condition is ANDed with key padding and the context band, the distance bias applies to what stays
+ * visible; a hidden key has P = 0 exactly, a query that sees no key (an other-speaker head in a monologue) a zero row of P and a zero
+ * output row.  At a fusion site (query = text, key = audio) utterance i has one speaker in both roles.  speakers = M2F_BUF_SPEAKERS,
+ * uint8, one id per token row in the plan's token order, an INPUT like the mask, written before each forward; only equality is used,
+ * ids of pad rows are ignored.  n_same, n_other >= 0 and n_same + n_other <= the heads of every enabled site (refused otherwise, naming
+ * the site); (0, 0), the default, is off and runs the kernels the plan ran before this entry existed.  No parameters; the backward
+ * kernels read the saved probabilities and ignore the setting.  A change destroys the captured graphs; call it between steps.
+ * Stream and chunk plans: m2f_plan_stream_speakers first (the cached ids); a chunk plan takes its parent's setting when it is created. */
+int m2f_plan_attention_speakers(m2f_plan* plan, int n_same, int n_other);
+int m2f_plan_get_attention_speakers(m2f_plan* plan, int* n_same, int* n_other);
+/* Stream plans: the caller-owned array of cached speaker ids, uint8 [S][C], indexed by LOGICAL cache row (row u % C of a ring; the row a
+ * page table maps on a paged plan - the array itself is dense), one array for all sites (NULL: none; refused while speaker heads are
+ * on).  m2f_stream_step / m2f_stream_prefill of a plan with speaker heads read the new utterances' ids from M2F_BUF_SPEAKERS ([S] /
+ * [S*T]) and store them into this array in the launch that advances the counters, BEHIND the last attention launch of the step: on a
+ * ring that store overwrites the id of the utterance that has just left the window, which every attention launch of the step - they
+ * never read the row the new utterance takes - has seen consistently, as the K / V row.  Destroys the captured graphs. */
+int m2f_plan_stream_speakers(m2f_plan* plan, void* buffer);
 /* ATTENTION MAPS: what nn.MultiheadAttention(need_weights=True) returns - the reference's fusion module computes them at every layer
  * and throws them away (src/model.py:14) - read out of the pre-dropout probabilities that every attention site of a padded or packed
  * plan saves at every forward (train and eval plans alike; csrc/attention_weights.hip).  m2f_plan_attention_sites: the plan's sites in
@@ -790,6 +811,37 @@ int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q,
                                     void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
                                     int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
                                     m2f_stream_t stream);
+/* SPEAKER HEADS.  The entries above with one more condition on which keys a query sees (m2f_plan_attention_speakers has the rule):
+ * heads 0 .. n_same - 1 see the keys of the query's own speaker only, the next n_other heads the keys of the other speakers only.
+ * Each is a superset of its _bias entry: past / future / gain as there (negative = unlimited; gain 0 = no bias), n_same = n_other = 0
+ * runs the kernels of the entries above.  speakers: device uint8, one id per token row (padded: [B*L]; packed: [T], row cu[b] + i).
+ * Stream entries: spk_cache = device uint8 [S][C], the ids of the cached utterances by logical cache row (read only; the row the new
+ * utterance takes is never read), spk_new = device uint8 [S] (step) / [S][T] (chunk), the new utterances' ids.  An other-speaker head
+ * with no other speaker in sight gives a zero output row and a zero weights row.  m2f_stream_advance_speakers[_n] is the launch that
+ * closes a step / a prefill call of such a stream: the new ids into the rows the new utterances took (what the attention launch did
+ * with K / V), then count += active (or the clamped n_new).  Refused before any launch: negative counts, n_same + n_other > H, a NULL
+ * speakers / spk_cache / spk_new with a non-zero count.  m2f_attention_speaker_class: 0 untouched, 1 same-speaker, 2 other-speaker. */
+int m2f_attention_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
+                               const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
+                               const uint8_t* speakers, int n_same, int n_other);
+int m2f_attention_varlen_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                      const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                                      float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
+                                      const uint8_t* speakers, int n_same, int n_other);
+int m2f_attention_stream_speakers(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                  const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
+                                  const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream);
+int m2f_attention_stream_chunk_speakers(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                        void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
+                                        int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
+                                        const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream);
+int m2f_stream_advance_speakers(int S, int C, int ring, int32_t* count, const uint8_t* active, uint8_t* spk_cache, const uint8_t* spk_new,
+                                m2f_stream_t stream);
+int m2f_stream_advance_speakers_n(int S, int T, int C, int ring, int32_t* count, const int32_t* n_new, uint8_t* spk_cache, const uint8_t* spk_new,
+                                  m2f_stream_t stream);
+int m2f_attention_speaker_class(int h, int n_same, int n_other);
 /* The same attention for dialogues of up to 512 utterances (the kernels packed plans with L > 64 run): one workgroup per 64-row
  * block of a (dialogue, head), keys streamed in 64-row blocks.  Rows are given in one of two forms:
  *   packed: cu (int32 [B+1], device) - dialogue b owns rows cu[b] .. cu[b+1]-1 (at most L of them), T rows in all; rows cu[B] ..

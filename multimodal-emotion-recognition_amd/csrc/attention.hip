@@ -10,7 +10,11 @@
 // terms of dQ, dK and dV, exactly.  Optionally also a distance-decay bias (AttnBatch::bias_gain16, ops.h m2f_attn_bias_slope: ALiBi) -
 // the forward adds -slope_h * |i - j| to the scaled fp32 score of every visible key in one explicit fma (the BIAS instantiations; in
 // bf16 mode behind the contraction, where the scale is applied).  It is a constant with respect to Q and K and the backward recomputes
-// no score, so m2f_attn_bwd_kernel is the kernel it was.
+// no score, so m2f_attn_bwd_kernel is the kernel it was.  Optionally also SPEAKER HEADS (AttnBatch::speaker / spk_same / spk_other, ops.h
+// m2f_attn_speaker_class): the first spk_same heads of a site see the keys of the query's own speaker only, the next spk_other heads
+// the keys of the other speakers only - one more condition ANDed into the visibility of a key where the pad flag and the band are
+// tested (the SPK instantiations), so the rules above hold as they stand: P = 0 exactly for a hidden key, a zero row for a query
+// that sees none (an other-speaker head in a monologue).  The backward reads the saved probabilities and stays the text it is.
 //
 // One workgroup of four wavefronts owns one (dialogue, head): the sequence is the utterances of a dialogue
 // (L <= 64), so the whole L x L problem fits one wave's registers.  Q/K/V (and dO, O in backward) tiles of
@@ -71,11 +75,15 @@ __device__ __forceinline__ f32x4 dot_rows_bf16(const float* arow, const float* b
 }
 
 // BAND: the launch has a context band (a second instantiation, so that a launch without one runs the code it always ran); BIAS: it
-// has a distance-decay bias (ops.h, m2f_attn_bias_slope) - instantiations of their own again, with or without a band
-template <int NT, bool BAND, bool BIAS = false>
+// has a distance-decay bias (ops.h, m2f_attn_bias_slope) - instantiations of their own again, with or without a band; SPK: it has
+// speaker heads (ops.h, m2f_attn_speaker_class) - a third flag of the same kind.  The speaker ids of the dialogue's keys (lane = key,
+// token row tok0 + lane in both layouts) are fetched WITH the slabs, a range-checked byte load beside the pad flags'; a lane keeps the
+// ids of the 4 NT keys its score registers belong to as NT packed words (4 NT shuffles, once), takes its query's id with one more
+// shuffle per query tile, and tests one byte per score element: no limit on distinct ids, no LDS, no atomics.
+template <int NT, bool BAND, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) {
-    static_assert(sizeof(AttnBatch) + 56 <= 192 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
-    m2f_kernarg_warm<0, 8, 192>();                  // the descriptor block (648 B + hidden arguments) in one miss
+    static_assert(sizeof(AttnBatch) + 56 <= 256 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
+    m2f_kernarg_warm<0, 8, 256>();                  // the descriptor block (664 B + hidden arguments) in one miss: lines 0 .. 767
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int pi = 0;
@@ -104,6 +112,10 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     // memory round trip of its own, the flags' in front of the slabs and the state's behind the barrier.
     const unsigned char kpad = __builtin_amdgcn_raw_buffer_load_b8(
         m2f_make_rsrc(ab.cu ? nullptr : ab.key_pad + (size_t)b * LM, (uint32_t)LM), lane < L ? lane : 0, 0, 0);
+    int kspk = 0;                                             // SPK: the speaker id of key `lane` (0 behind the dialogue: never visible)
+    if constexpr (SPK)
+        kspk = __builtin_amdgcn_raw_buffer_load_b8(m2f_make_rsrc(ab.speaker ? ab.speaker + tok0 : nullptr, (uint32_t)(L > 0 ? L : 0)),
+                                                   lane < L ? lane : 0, 0, 0);
     u32x4 rw = m2f_rng_words(ab.rng);
     constexpr int NV = 2 * NT;                                // float4 per thread and slab: covers W <= 128
     if (slab_fast_ok<NV>(qg, P.ldq, hd, Lp, W) && slab_fast_ok<NV>(kg, P.ldk, hd, Lp, W) && slab_fast_ok<NV>(vg, P.ldv, hd, Lp, W)) {
@@ -137,11 +149,21 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     float* probs = P.probs + (size_t)bh * Lp * Lp;
     uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
     const bool w32 = !(P.no_f32 && out16);                  // (no fp32 reader: the bf16 shadow is the result)
+    // SPK: this head's class (uniform per workgroup) and the ids of the keys of this lane's score registers, one word per key tile
+    int spk_cls = M2F_SPK_NONE;
+    uint32_t spk4[NT];
+    if constexpr (SPK) {
+        spk_cls = m2f_attn_speaker_class(h, ab.spk_same, ab.spk_other);
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) spk4[jt] = m2f_spk_pack4(kspk, 16 * jt + 4 * lg);
+    }
 
 #pragma unroll 1
     for (int it = 0; it < NT; ++it) {
         f32x4 s[NT];
         const int i = 16 * it + l15;                        // this lane's query row
+        int mine = 0;                                       // SPK: its speaker
+        if constexpr (SPK) mine = __shfl(kspk, i, 64);
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
             if (ab.bf16_math & 1) {
@@ -171,9 +193,11 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
-                float v = ((vis >> j) & 1ull) ? s[jt][r] * scale : -INFINITY;
+                bool on = (vis >> j) & 1ull;
+                if constexpr (SPK) on = on && m2f_spk_sees(spk_cls, spk4[jt], r, mine);    // ... and its speaker head lets through
+                float v = on ? s[jt][r] * scale : -INFINITY;
                 if constexpr (BIAS)                         // + -slope * |i - j|, this lane's query to key j; a hidden key stays -inf
-                    v = ((vis >> j) & 1ull) ? __fmaf_rn(nslope, (float)abs(i - j), s[jt][r] * scale) : -INFINITY;
+                    v = on ? __fmaf_rn(nslope, (float)abs(i - j), s[jt][r] * scale) : -INFINITY;
                 s[jt][r] = v;
                 m = fmaxf(m, v);
             }
@@ -236,8 +260,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
 
 template <int NT>
 __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) {
-    static_assert(sizeof(AttnBatch) + 56 <= 192 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
-    m2f_kernarg_warm<0, 8, 192>();                  // the descriptor block (648 B + hidden arguments) in one miss
+    static_assert(sizeof(AttnBatch) + 56 <= 256 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
+    m2f_kernarg_warm<0, 8, 256>();                  // the descriptor block (664 B + hidden arguments) in one miss: lines 0 .. 767
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int pi = 0;
@@ -651,10 +675,14 @@ hipError_t launch(AttnBatch& ab, hipStream_t stream) {
                        (BWD ? (Lp + (ab.bwd_fast ? 2 * NT * NTHR : 0)) * sizeof(float) : 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const bool band = (ab.band_past | ab.band_future) != 0, bias = !BWD && ab.bias_gain16 != 0;
+    const bool spk = !BWD && (ab.spk_same | ab.spk_other) != 0;         // speaker heads: forward instantiations of their own
+    if (spk && !m2f_attn_speakers_ok(ab)) return hipErrorInvalidValue;
 #define M2F_ATTN_CASE(N)                                                                                   \
     case N: {                                                                                              \
         auto kern = BWD ? m2f_attn_bwd_kernel<N> : bias ? (band ? m2f_attn_fwd_kernel<N, true, true> : m2f_attn_fwd_kernel<N, false, true>) \
                                                          : (band ? m2f_attn_fwd_kernel<N, true> : m2f_attn_fwd_kernel<N, false>); \
+        if (spk) kern = bias ? (band ? m2f_attn_fwd_kernel<N, true, true, true> : m2f_attn_fwd_kernel<N, false, true, true>)      \
+                             : (band ? m2f_attn_fwd_kernel<N, true, false, true> : m2f_attn_fwd_kernel<N, false, false, true>);   \
         if (lds > 64 * 1024) {                                                                             \
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \

@@ -21,6 +21,13 @@
 // pass 1 and pass 2 alike, so the probabilities are normalised by the sum of exactly the scores they were formed from.  No block pair
 // is skipped on its account (a far block's probabilities may underflow; the band's test stays the only skip rule), and the backward
 // kernels - dkdv, dq, delta_rows - read the saved probabilities, recompute no score and are not touched by it.
+// Speaker heads (AttnBatch::speaker / spk_same / spk_other, ops.h m2f_attn_speaker_class): the forward's SPK instantiations AND one more
+// condition into the keys a query sees, beside key_bits() and the band's bits, per 64-key block: the block's speaker ids are read one per
+// lane (lane = key) where the pad flags are, a lane gathers the ids of its sixteen score elements' keys with shuffles and tests one byte
+// per element against its query's id.  The pattern is not block-shaped, so NO block is skipped on its account (the band's test stays the
+// only skip rule) and every element of a visited block is written, a hidden one as 0 - what the attention-maps gather reads.  A query
+// that sees no key (an other-speaker head in a monologue) gets P = 0 and a zero output row by the rule above.  The backward kernels
+// read the saved probabilities and stay the text they are.
 // Both layouts of AttnBatch: packed (cu: dialogue b owns rows cu[b] .. cu[b+1]-1, no pad keys) and padded (key_pad: masked
 // keys get -inf before the softmax).  Operands are read as fp32 in both precision modes; results also go to their bf16
 // shadows when the plan keeps them (out / dq / dk / dv, and AttnProblem::no_f32 as in attention.hip).
@@ -136,10 +143,19 @@ __device__ __forceinline__ float dlong_score(float acc, float scale, float nslop
     if constexpr (BIAS) return __fmaf_rn(nslope, (float)abs(iq - j), x);
     return x;
 }
+// SPK: the speaker ids of the keys of this lane's sixteen score elements (keys 16 jt + 4 lg + r of the block at kb), one word per jt
+template <bool SPK>
+__device__ __forceinline__ void dlong_key_speakers(const AttnBatch& ab, const Where& w, int kb, int nk, int lane, int lg, uint32_t (&spk4)[4]) {
+    if constexpr (SPK) {
+        const int ks = ab.speaker[w.tok0 + kb + (lane < nk ? lane : 0)];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) spk4[jt] = m2f_spk_pack4(ks, 16 * jt + 4 * lg);
+    }
+}
 // CTM: 16-column tiles of the head dim held in registers (8: hd <= 128, 16: hd <= 256); BAND: the launch has a context band (its
 // own instantiations of the three kernels, so that a launch without one runs the code it always ran); BIAS (forward only): it has a
-// distance-decay bias - instantiations of their own again
-template <int CTM, bool BAND, bool BIAS = false>
+// distance-decay bias - instantiations of their own again; SPK (forward only): it has speaker heads - likewise
+template <int CTM, bool BAND, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatch ab) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -162,6 +178,12 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
     const float* kb_rows = KV + l15 * ld + lg;
     float nslope = 0.f;                                     // BIAS: minus the head's slope
     if constexpr (BIAS) nslope = -m2f_attn_bias_slope(w.h, P.H, m2f_attn_bias_gain(ab.bias_gain16));
+    int spk_cls = M2F_SPK_NONE, mine = 0;                   // SPK: the head's class (uniform per workgroup), this lane's query's speaker
+    uint32_t spk4[4] = {0u, 0u, 0u, 0u};
+    if constexpr (SPK) {
+        spk_cls = m2f_attn_speaker_class(w.h, ab.spk_same, ab.spk_other);
+        mine = ab.speaker[w.tok0 + (iq < w.n ? iq : w.n - 1)];          // (q0 < w.n: w.n >= 1)
+    }
 
     // pass 1: row max and normaliser
     float m_run = -INFINITY, l_run = 0.f;
@@ -172,6 +194,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
         stage(KV, P.k + (w.tok0 + kb) * P.ldk + w.h * hd, P.ldk, nk, hd, W, ld, tid);
         unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
         if constexpr (BAND) kvalid &= m2f_attn_band_bits(ab, iq, kb);     // (from here on per lane: the keys its query sees)
+        dlong_key_speakers<SPK>(ab, w, kb, nk, lane, lg, spk4);
         __syncthreads();
         float s[4][4];
         float m_blk = -INFINITY;
@@ -181,7 +204,9 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
-                s[jt][r] = ((kvalid >> j) & 1ull) ? dlong_score<BIAS>(acc[r], scale, nslope, iq, kb + j) : -INFINITY;
+                bool on = (kvalid >> j) & 1ull;
+                if constexpr (SPK) on = on && m2f_spk_sees(spk_cls, spk4[jt], r, mine);
+                s[jt][r] = on ? dlong_score<BIAS>(acc[r], scale, nslope, iq, kb + j) : -INFINITY;
                 m_blk = fmaxf(m_blk, s[jt][r]);
             }
         }
@@ -215,6 +240,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
         stage(KV, P.k + (w.tok0 + kb) * P.ldk + w.h * hd, P.ldk, nk, hd, W, ld, tid);
         unsigned long long kvalid = key_bits(ab, w, kb, nk, lane);
         if constexpr (BAND) kvalid &= m2f_attn_band_bits(ab, iq, kb);
+        dlong_key_speakers<SPK>(ab, w, kb, nk, lane, lg, spk4);
         __syncthreads();
         float p[4][4];
 #pragma unroll
@@ -223,7 +249,9 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_dlong_fwd_kernel(const AttnBatc
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int jl = 16 * jt + 4 * lg + r, j = kb + jl;
-                const float x = ((kvalid >> jl) & 1ull) ? dlong_score<BIAS>(acc[r], scale, nslope, iq, j) : -INFINITY;
+                bool on = (kvalid >> jl) & 1ull;
+                if constexpr (SPK) on = on && m2f_spk_sees(spk_cls, spk4[jt], r, mine);
+                const float x = on ? dlong_score<BIAS>(acc[r], scale, nslope, iq, j) : -INFINITY;
                 float pv = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;   // (no visible key: exp(-inf + inf) would be NaN)
                 if (iq < Lp && j < Lp) probs[(size_t)j * Lp + iq] = pv;           // lanes: consecutive iq
                 if (site) pv = m2f_keep(key, drop_idx(w.bh, LM, iq, j), ab.drop_thresh) ? pv * ab.drop_scale : 0.f;
@@ -491,6 +519,20 @@ hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)2 * BLK * (maxW + 2) * sizeof(float);
+    if (ab.spk_same | ab.spk_other) {                       // speaker heads: instantiations of their own, with / without band and bias
+        if (!m2f_attn_speakers_ok(ab)) return hipErrorInvalidValue;
+        const bool band = has_band(ab), wide = maxW > 128;
+        if (ab.bias_gain16) {
+            if (band) return wide ? go(m2f_attn_dlong_fwd_kernel<16, true, true, true>, blocks, lds, stream, ab)
+                                  : go(m2f_attn_dlong_fwd_kernel<8, true, true, true>, blocks, lds, stream, ab);
+            return wide ? go(m2f_attn_dlong_fwd_kernel<16, false, true, true>, blocks, lds, stream, ab)
+                        : go(m2f_attn_dlong_fwd_kernel<8, false, true, true>, blocks, lds, stream, ab);
+        }
+        if (band) return wide ? go(m2f_attn_dlong_fwd_kernel<16, true, false, true>, blocks, lds, stream, ab)
+                              : go(m2f_attn_dlong_fwd_kernel<8, true, false, true>, blocks, lds, stream, ab);
+        return wide ? go(m2f_attn_dlong_fwd_kernel<16, false, false, true>, blocks, lds, stream, ab)
+                    : go(m2f_attn_dlong_fwd_kernel<8, false, false, true>, blocks, lds, stream, ab);
+    }
     if (ab.bias_gain16) {                                   // distance-decay bias: instantiations of their own
         if (has_band(ab))
             return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true, true>, blocks, lds, stream, ab)

@@ -40,13 +40,22 @@
 // bias_gain).  The new utterance is utterance n_old; cache row j holds the utterance at distance n_old - j (plain cache) or
 // (pos - j + C) % C (ring), and -slope * distance is added to the scaled score where it is written - an explicit fma, one rounding
 // rule with the dialogue kernels.  The cached rows do not depend on it.
+//
+// SPK (a fifth flag, its own instantiations again): the launch has speaker heads (ops.h, m2f_attn_speaker_class; AttnStreamBatch::spk_cache /
+// spk_new).  The wave reads the slot's cached speaker bytes ONCE, lane = logical row, 64 consecutive bytes per load and up to 512 B in
+// all, into LDS beside the new rows; the new utterance's id is the step input spk_new[s] and the cached byte of the row it takes (a
+// ring: the utterance that just left the window) is never read.  Pass 1 writes -inf for a row its head's class hides.  The new row is
+// visible to a same-speaker head and to an untouched one, but an other-speaker head with no other speaker cached sees NO row: there
+// the maximum is -inf, and the SPK form writes zero exponentials and scales by 0 - a zero output row, a zero weights row - where the
+// text without the flag may divide, its sum being >= 1.  The bytes are written by m2f_launch_stream_advance_speakers, behind every
+// attention launch of the step.
 #include "common.h"
 #include "ops.h"
 #include "attn_stream_rows.h"
 
 namespace {
 
-template <bool BF16, bool PAGED, bool WEIGHTS, bool BIAS>
+template <bool BF16, bool PAGED, bool WEIGHTS, bool BIAS, bool SPK = false>
 __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const AttnStreamWeights& ww) {
     typedef Row<BF16> R;
     typedef typename R::elem_t elem_t;
@@ -55,6 +64,7 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     __shared__ float sq[128], sk[128], sv[128];   // the slot's new rows of this head, zero behind hd (bf16 mode: rounded)
     __shared__ float sc[M2F_ATTN_STREAM_MAX_C];   // scores, then the unnormalised probabilities
     __shared__ int spg[32];                       // paged: the slot's page ids, entry e = logical rows e*R .. e*R + R - 1
+    __shared__ uint8_t sspk[SPK ? M2F_ATTN_STREAM_MAX_C : 4];     // SPK: the speaker ids of the slot's logical cache rows
 
     const int blk = blockIdx.x, lane = threadIdx.x;
     int pi = 0;
@@ -85,6 +95,13 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     const int lgR = PAGED ? pg.lgR : 0;
 
     if (PAGED) m2f_stream_page_ids(spg, pg, s, nslots, lane);
+    int spk_cls = M2F_SPK_NONE, mine = 0;         // SPK: the head's class (uniform per wave), the new utterance's speaker
+    if constexpr (SPK) {
+        spk_cls = m2f_attn_speaker_class(h, ab.spk_same, ab.spk_other);
+        mine = ab.spk_new[s];
+        const uint8_t* crow = ab.spk_cache + (size_t)s * C;
+        for (int j = lane; j < nslots; j += 64) sspk[j] = crow[j];       // (nslots <= C <= 512: at most eight coalesced byte loads)
+    }
     {   // the new rows -> LDS
         const float* qrow = P.q + (size_t)s * P.ldq + (size_t)h * hd;
         const float* krow = P.k + (size_t)s * P.ldk + (size_t)h * hd;
@@ -153,12 +170,17 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
 #pragma unroll
             for (int i = 0; i < EPL; ++i) d = fmaf(qx[i], kx[u][i], d);
             for (int o = CH >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+            bool hide = false;                                                  // SPK: a row the head's class hides gets -inf
+            if constexpr (SPK) {
+                const bool eq = j == pos || (j < nslots && sspk[j] == mine);    // (the new row carries `mine`; its cached byte is stale)
+                hide = spk_cls != M2F_SPK_NONE && eq != (spk_cls == M2F_SPK_SAME);
+            }
             if constexpr (BIAS) {
                 int dist = pos - j;                                             // plain cache: pos = n_old >= j; ring: (pos - j + C) % C
                 if (dist < 0) dist += C;                                        // (0 <= pos, j < C: one wrap at most, no division)
-                if (c == 0 && j < nslots) sc[j] = __fmaf_rn(nslope, (float)dist, d * scale);
+                if (c == 0 && j < nslots) sc[j] = hide ? -INFINITY : __fmaf_rn(nslope, (float)dist, d * scale);
             } else {
-                if (c == 0 && j < nslots) sc[j] = d * scale;
+                if (c == 0 && j < nslots) sc[j] = hide ? -INFINITY : d * scale;
             }
         }
     }
@@ -170,12 +192,12 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     m = m2f_wave_max(m);
     float sum = 0.f;
     for (int j = lane; j < nslots; j += 64) {
-        const float e = __expf(sc[j] - m);
+        const float e = (SPK && m == -INFINITY) ? 0.f : __expf(sc[j] - m);       // (SPK: no visible row - not exp(-inf + inf))
         sc[j] = e;
         sum += e;
     }
     sum = m2f_wave_sum(sum);
-    const float inv = 1.0f / sum;                 // (sum >= 1: the row of the maximum contributes exp(0))
+    const float inv = (SPK && !(sum > 0.f)) ? 0.f : 1.0f / sum;      // (sum >= 1: the row of the maximum contributes exp(0); SPK: or no row is visible)
     __syncthreads();
     if constexpr (WEIGHTS) {                      // the row of probabilities, oldest live utterance first
         float* wrow = ww.w[pi] + ((size_t)s * P.H + h) * (size_t)C;
@@ -225,27 +247,39 @@ __device__ __forceinline__ void attn_stream_body(const AttnStreamBatch& ab, cons
     }
 }
 
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_kernel(const AttnStreamBatch ab) {
-    attn_stream_body<BF16, false, false, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, AttnStreamWeights{{nullptr}});
+    attn_stream_body<BF16, false, false, BIAS, SPK>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, AttnStreamWeights{{nullptr}});
 }
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg) {
-    attn_stream_body<BF16, true, false, BIAS>(ab, pg, AttnStreamWeights{{nullptr}});
+    attn_stream_body<BF16, true, false, BIAS, SPK>(ab, pg, AttnStreamWeights{{nullptr}});
 }
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_weights_kernel(const AttnStreamBatch ab, const AttnStreamWeights ww) {
-    attn_stream_body<BF16, false, true, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, ww);
+    attn_stream_body<BF16, false, true, BIAS, SPK>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, ww);
 }
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(64) void m2f_attn_stream_paged_weights_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const AttnStreamWeights ww) {
-    attn_stream_body<BF16, true, true, BIAS>(ab, pg, ww);
+    attn_stream_body<BF16, true, true, BIAS, SPK>(ab, pg, ww);
 }
 
 // len[s] += active[s]: the one launch that closes a step
 __global__ void m2f_stream_advance_kernel(int* len, const uint8_t* active, int S) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < S && active[s]) len[s] = len[s] + 1;
+}
+// ... of a stream with speaker heads: first the new utterance's id into the logical row it took (ring: row len % C, the byte of the
+// utterance that just left the window; every attention launch of the step has read the old row set - they are earlier in the stream)
+__global__ void m2f_stream_advance_speakers_kernel(int* len, const uint8_t* active, int S, uint8_t* spk_cache, const uint8_t* spk_new,
+                                                   int C, int ring) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S && active[s]) {
+        const int n = len[s];
+        const int row = ring ? (n >= 0 ? n % C : -1) : n;
+        if (row >= 0 && row < C) spk_cache[(size_t)s * C + row] = spk_new[s];
+        len[s] = n + 1;
+    }
 }
 // len[s] = 0 for the slots of the mask (null: every slot)
 __global__ void m2f_stream_reset_kernel(int* len, const uint8_t* mask, int S) {
@@ -294,6 +328,24 @@ hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* p
     if (weights)
         for (int i = 0; i < ab.count; ++i)
             if (!weights->w[i] || (reinterpret_cast<uintptr_t>(weights->w[i]) & 3)) return hipErrorInvalidValue;
+    if (ab.spk_same | ab.spk_other) {             // speaker heads: the same four forms with / without the bias, instantiations of their own
+        if (!m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
+        const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
+        const bool bias = ab.bias_gain != 0.f;
+#define M2F_STREAM_SPK(KERN, ...)                                                                                              \
+        do {                                                                                                                   \
+            if (ab.bf16) { if (bias) hipLaunchKernelGGL((KERN<true, true, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__);   \
+                           else hipLaunchKernelGGL((KERN<true, false, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__); }     \
+            else { if (bias) hipLaunchKernelGGL((KERN<false, true, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__);          \
+                   else hipLaunchKernelGGL((KERN<false, false, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__); }            \
+        } while (0)
+        if (weights && paging) M2F_STREAM_SPK(m2f_attn_stream_paged_weights_kernel, ab, pg, ww);
+        else if (weights) M2F_STREAM_SPK(m2f_attn_stream_weights_kernel, ab, ww);
+        else if (paging) M2F_STREAM_SPK(m2f_attn_stream_paged_kernel, ab, pg);
+        else M2F_STREAM_SPK(m2f_attn_stream_kernel, ab);
+#undef M2F_STREAM_SPK
+        return hipGetLastError();
+    }
     if (ab.bias_gain != 0.f) {                    // distance-decay bias: the same four forms, instantiations of their own
         const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
         if (weights && paging) {
@@ -334,6 +386,13 @@ hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* p
 
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream) {
     hipLaunchKernelGGL(m2f_stream_advance_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, active, S);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_stream_advance_speakers(int* len, const uint8_t* active, int S, uint8_t* spk_cache, const uint8_t* spk_new, int C,
+                                              int ring, hipStream_t stream) {
+    if (!len || !active || !spk_cache || !spk_new || S < 1 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(m2f_stream_advance_speakers_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, active, S, spk_cache, spk_new, C, ring);
     return hipGetLastError();
 }
 

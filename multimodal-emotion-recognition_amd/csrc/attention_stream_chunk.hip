@@ -28,6 +28,12 @@
 // BIAS (a third flag of the body, its own instantiations): the launch has a distance-decay bias (ops.h, m2f_attn_bias_slope;
 // AttnStreamBatch::bias_gain).  Query t is utterance n_old + t, a cached row at logical index d utterance n_old - nlive + d, an own row
 // t' utterance n_old + t'; both passes add -slope * distance through biased<>, so they form the identical score.
+// SPK (a fourth flag, its own instantiations): the launch has speaker heads (ops.h, m2f_attn_speaker_class).  The one rule of the step
+// kernel, for cached rows and for the chunk's own rows alike: query t carries spk_new[s][t], a cached row its byte of spk_cache[s] (logical
+// row = cache row, read 64 at a time with the block they belong to, lane = row), an own row t' spk_new[s][t']; a lane gathers the ids of
+// its sixteen score elements' keys with shuffles (ops.h, m2f_spk_pack4) and both passes AND the same test into the visibility.  A query
+// whose head sees no row - an other-speaker head before another speaker has spoken - gets a zero output row (m_run stays -inf, as for a
+// band).  spk_cache is only read here; m2f_launch_stream_advance_speakers_n stores the chunk's ids behind the call's last attention launch.
 #include "common.h"
 #include "ops.h"
 #include "attn_stream_rows.h"
@@ -146,7 +152,7 @@ __device__ __forceinline__ float biased(float x, float nslope, int dist) {
     return x;
 }
 
-template <bool BF16, bool PAGED, bool BIAS>
+template <bool BF16, bool PAGED, bool BIAS, bool SPK = false>
 __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab, const AttnStreamPaging& pg, const int T,
                                                        const int* __restrict__ new_count) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -210,6 +216,30 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
     const float* qrow = Qs + i * ld + lg;
     const float* kv_rows = KV + l15 * ld + lg;
     const float* own_rows = Ks + l15 * ld + lg;
+    // SPK: the head's class (uniform per workgroup), this lane's query's speaker, the ids of the own keys of its score elements - and,
+    // per cached block, of the cached ones (cached_ids / cached_speakers below)
+    int spk_cls = M2F_SPK_NONE, mine = 0;
+    uint32_t own4[4] = {0u, 0u, 0u, 0u}, spk4[4] = {0u, 0u, 0u, 0u};
+    if constexpr (SPK) {
+        spk_cls = m2f_attn_speaker_class(h, ab.spk_same, ab.spk_other);
+        const uint8_t* nrow = ab.spk_new + row0;            // (n_new >= 1 here)
+        mine = nrow[i < n_new ? i : n_new - 1];
+        const int ko = nrow[lane < n_new ? lane : 0];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) own4[jt] = m2f_spk_pack4(ko, 16 * jt + 4 * lg);
+    }
+    // the block's ids are ISSUED with the block's K rows, in front of the barrier that commits them (lane = row; every wave, so that
+    // the load is in flight beside stage_cache's and costs no round trip of its own), and gathered behind it
+    auto cached_ids = [&](int kb, int nk) -> int {
+        if constexpr (SPK) return ab.spk_cache[(size_t)s * C + kb + (lane < nk ? lane : 0)];
+        return 0;
+    };
+    auto cached_speakers = [&](int kc_id) {                 // (every lane of the wave: the shuffles need them all)
+        if constexpr (SPK) {
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) spk4[jt] = m2f_spk_pack4(kc_id, 16 * jt + 4 * lg);
+        }
+    };
     __syncthreads();                                        // Q, the chunk's K / V and the page ids committed
 
     // ---- pass 1: row max and normaliser -----------------------------------------------------------------------------------------
@@ -236,15 +266,17 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
     for (int kb = 0; kb < nlive; kb += BLK) {
         __syncthreads();                                    // previous block consumed
         stage_cache<BF16, PAGED>(KV, kc, spg, lgR, page_stride, kb, min(BLK, nlive - kb), dead, hdp, W, ld, tid);
+        const int ids = cached_ids(kb, min(BLK, nlive - kb));
         __syncthreads();
         if (wave_on) {
             float x[4][4];
+            cached_speakers(ids);
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);      // S[i][j = 16jt + 4lg + r]
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    x[jt][r] = vis.cached(i, kb + 16 * jt + 4 * lg + r)
+                    x[jt][r] = (vis.cached(i, kb + 16 * jt + 4 * lg + r) && (!SPK || m2f_spk_sees(spk_cls, spk4[jt], r, mine)))
                                    ? biased<BIAS>(acc[r] * scale, nslope, BIAS ? vis.cached_dist(i, kb + 16 * jt + 4 * lg + r) : 0) : -INFINITY;
             }
             stats(x);
@@ -257,13 +289,13 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
             const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                x[jt][r] = vis.own(i, 16 * jt + 4 * lg + r) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
+                x[jt][r] = (vis.own(i, 16 * jt + 4 * lg + r) && (!SPK || m2f_spk_sees(spk_cls, own4[jt], r, mine))) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
         }
         stats(x);
     }
 
     // ---- pass 2: P = exp(S - m) / l, O += P V ------------------------------------------------------------------------------------------
-    const float inv = (i < n_new && l_run > 0.f) ? 1.0f / l_run : 0.f;     // (a query always sees itself: l_run >= 1 for i < n_new)
+    const float inv = (i < n_new && l_run > 0.f) ? 1.0f / l_run : 0.f;     // (a query always sees itself: l_run >= 1 for i < n_new - but for SPK, where an other-speaker head may see no row)
     f32x4 o[8];
 #pragma unroll
     for (int ct = 0; ct < 8; ++ct) o[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -283,15 +315,17 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
         const int nk = min(BLK, nlive - kb);
         __syncthreads();
         stage_cache<BF16, PAGED>(KV, kc, spg, lgR, page_stride, kb, nk, dead, hdp, W, ld, tid);
+        const int ids = cached_ids(kb, nk);
         __syncthreads();
         float p[4][4];
         if (wave_on) {
+            cached_speakers(ids);
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 const f32x4 acc = dot_tile(kv_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float x = vis.cached(i, kb + 16 * jt + 4 * lg + r)
+                    const float x = (vis.cached(i, kb + 16 * jt + 4 * lg + r) && (!SPK || m2f_spk_sees(spk_cls, spk4[jt], r, mine)))
                                         ? biased<BIAS>(acc[r] * scale, nslope, BIAS ? vis.cached_dist(i, kb + 16 * jt + 4 * lg + r) : 0) : -INFINITY;
                     p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;      // (no visible key: exp(-inf + inf) would be NaN)
                 }
@@ -309,7 +343,7 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
             const f32x4 acc = dot_tile(own_rows + 16 * jt * ld, qrow, ksteps);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float x = vis.own(i, 16 * jt + 4 * lg + r) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
+                const float x = (vis.own(i, 16 * jt + 4 * lg + r) && (!SPK || m2f_spk_sees(spk_cls, own4[jt], r, mine))) ? biased<BIAS>(acc[r] * scale, nslope, i - (16 * jt + 4 * lg + r)) : -INFINITY;
                 p[jt][r] = (m_run == -INFINITY) ? 0.f : __expf(x - m_run) * inv;
             }
         }
@@ -346,14 +380,14 @@ __device__ __forceinline__ void attn_stream_chunk_body(const AttnStreamBatch& ab
     }
 }
 
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_kernel(const AttnStreamBatch ab, const int T, const int* __restrict__ new_count) {
-    attn_stream_chunk_body<BF16, false, BIAS>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, T, new_count);
+    attn_stream_chunk_body<BF16, false, BIAS, SPK>(ab, AttnStreamPaging{nullptr, 0, 0, 0, 0}, T, new_count);
 }
-template <bool BF16, bool BIAS = false>
+template <bool BF16, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_stream_chunk_paged_kernel(const AttnStreamBatch ab, const AttnStreamPaging pg, const int T,
                                                                            const int* __restrict__ new_count) {
-    attn_stream_chunk_body<BF16, true, BIAS>(ab, pg, T, new_count);
+    attn_stream_chunk_body<BF16, true, BIAS, SPK>(ab, pg, T, new_count);
 }
 
 // len[s] += min(max(n_new[s], 0), T): the one launch that closes a prefill call
@@ -362,6 +396,24 @@ __global__ void m2f_stream_advance_n_kernel(int* len, const int* n_new, int S, i
     if (s < S) {
         const int n = min(max(n_new[s], 0), T);
         if (n) len[s] = len[s] + n;
+    }
+}
+
+// ... of a stream with speaker heads: first the chunk's ids into the logical rows its utterances took - the rows the chunk kernel stored
+// K / V to (a slot the chunk kernel left untouched keeps its bytes; of n > C new rows on a ring the last C) - one thread per slot, plain
+// byte stores, behind every attention launch of the prefill call
+__global__ void m2f_stream_advance_speakers_n_kernel(int* len, const int* n_new, int S, int T, uint8_t* spk_cache, const uint8_t* spk_new,
+                                                     int C, int ring) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S) {
+        const int n = min(max(n_new[s], 0), T), n_old = len[s];
+        const bool live = n > 0 && n_old >= 0 && (ring || (n_old <= C && n <= C - n_old));
+        if (live)
+            for (int t = n - min(n, C); t < n; ++t) {
+                const int row = ring ? (int)(((unsigned)n_old + (unsigned)t) % (unsigned)C) : n_old + t;
+                spk_cache[(size_t)s * C + row] = spk_new[(size_t)s * T + t];
+            }
+        if (n) len[s] = n_old + n;
     }
 }
 
@@ -383,6 +435,21 @@ hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPag
     const int blocks = n_new && T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, &maxW) : -1;
     if (blocks < 0 || !(ab.bias_gain >= 0.f) || ab.bias_gain > 3.0e38f) return hipErrorInvalidValue;
     const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
+    if (ab.spk_same | ab.spk_other) {                       // speaker heads: instantiations of their own, with / without the bias
+        if (!m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
+        if (ab.bias_gain != 0.f) {
+            if (paging)
+                return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, true, true>, blocks, lds, stream, ab, pg, T, n_new)
+                               : go(m2f_attn_stream_chunk_paged_kernel<false, true, true>, blocks, lds, stream, ab, pg, T, n_new);
+            return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, true, true>, blocks, lds, stream, ab, T, n_new)
+                           : go(m2f_attn_stream_chunk_kernel<false, true, true>, blocks, lds, stream, ab, T, n_new);
+        }
+        if (paging)
+            return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, false, true>, blocks, lds, stream, ab, pg, T, n_new)
+                           : go(m2f_attn_stream_chunk_paged_kernel<false, false, true>, blocks, lds, stream, ab, pg, T, n_new);
+        return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, false, true>, blocks, lds, stream, ab, T, n_new)
+                       : go(m2f_attn_stream_chunk_kernel<false, false, true>, blocks, lds, stream, ab, T, n_new);
+    }
     if (ab.bias_gain != 0.f) {                              // distance-decay bias: instantiations of their own
         if (paging)
             return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, true>, blocks, lds, stream, ab, pg, T, n_new)
@@ -399,5 +466,13 @@ hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPag
 
 hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream) {
     hipLaunchKernelGGL(m2f_stream_advance_n_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, n_new, S, T);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_stream_advance_speakers_n(int* len, const int* n_new, int S, int T, uint8_t* spk_cache, const uint8_t* spk_new, int C,
+                                                int ring, hipStream_t stream) {
+    if (!len || !n_new || !spk_cache || !spk_new || S < 1 || T < 1 || T > M2F_ATTN_STREAM_MAX_CHUNK || C < 1 || C > M2F_ATTN_STREAM_MAX_C)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(m2f_stream_advance_speakers_n_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, len, n_new, S, T, spk_cache, spk_new, C, ring);
     return hipGetLastError();
 }

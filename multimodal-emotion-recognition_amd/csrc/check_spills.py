@@ -17,7 +17,7 @@ ring = len(sys.argv) > 2 and sys.argv[1] == "--ring"
 # fully unrolled loops with static indices; an unroll that fails turns them into scratch arrays - refuse the build instead.
 dlong = len(sys.argv) > 2 and sys.argv[1] == "--dlong"
 # --attn <remarks>: the dialogue attention forward kernels (attention.hip, m2f_attn_fwd_kernel: every NT, with and without a band, with
-# and without the distance-decay bias) keep a query tile's scores in registers through fully unrolled loops - the same rule; prints the
+# and without the distance-decay bias, with and without speaker heads) keep a query tile's scores in registers through fully unrolled loops - the same rule; prints the
 # register numbers of each (DESIGN.md section 3 records the biased instantiations beside the ones they were copied from)
 attn = len(sys.argv) > 2 and sys.argv[1] == "--attn"
 # --stream <remarks>: the streaming attention kernels (attention_stream.hip) - the same rule (a wave's row chunks and accumulators)
@@ -79,8 +79,8 @@ if adam:
     sys.exit(1 if bad else 0)
 if attn:
     kernels = [r for r in rows if "m2f_attn_fwd_kernel" in r["name"]]
-    if len(kernels) != 16:
-        sys.exit(f"check_spills: expected the sixteen m2f_attn_fwd_kernel instantiations in {path}, found {len(kernels)} - did the remark format change?")
+    if len(kernels) != 32:
+        sys.exit(f"check_spills: expected the thirty-two m2f_attn_fwd_kernel instantiations in {path}, found {len(kernels)} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('AGPRs')} AGPRs, {r.get('scratch', 0)} bytes of scratch, "

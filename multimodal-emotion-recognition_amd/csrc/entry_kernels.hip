@@ -165,6 +165,30 @@ int m2f_attention_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq,
     M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
+/* the speaker-head counts of the _speakers entries: >= 0, together at most H, and ids wherever a count is non-zero */
+static int speaker_heads_ok(const char* who, int H, int n_same, int n_other, const void* ids, const char* what) {
+    const std::string w(who);
+    if (n_same < 0 || n_other < 0) return fail(w + ": n_same and n_other must be >= 0");
+    if (n_same > 255 || n_other > 255 || n_same + n_other > H)
+        return fail(w + ": n_same + n_other = " + std::to_string(n_same + n_other) + " exceeds the " + std::to_string(H) + " heads");
+    if ((n_same | n_other) && !ids) return fail(w + ": speaker heads need " + what);
+    return 0;
+}
+int m2f_attention_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
+                               const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
+                               const uint8_t* speakers, int n_same, int n_other) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_fwd_speakers", gain, &g)) return r;
+    if (int r = speaker_heads_ok("m2f_attention_fwd_speakers", H, n_same, n_other, speakers, "speakers (uint8, one per token row)")) return r;
+    AttnBatch ab;
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
+    m2f_attn_set_band(ab, past, future);
+    ab.bias_gain16 = m2f_attn_bias_gain16(g);
+    ab.speaker = (n_same | n_other) ? speakers : nullptr; ab.spk_same = (uint8_t)n_same; ab.spk_other = (uint8_t)n_other;
+    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
 int m2f_attention_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                       const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
                       const uint32_t* rng_state, m2f_stream_t stream) {
@@ -230,6 +254,22 @@ int m2f_attention_varlen_fwd_bias(int B, int L, int H, int hd, const float* q, i
     if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
     m2f_attn_set_band(ab, past, future);
     ab.bias_gain16 = m2f_attn_bias_gain16(g);
+    M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_attention_varlen_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                      const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
+                                      float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
+                                      const uint8_t* speakers, int n_same, int n_other) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_varlen_fwd_speakers", gain, &g)) return r;
+    if (int r = speaker_heads_ok("m2f_attention_varlen_fwd_speakers", H, n_same, n_other, speakers, "speakers (uint8, one per token row)")) return r;
+    AttnBatch ab;
+    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
+    m2f_attn_set_band(ab, past, future);
+    ab.bias_gain16 = m2f_attn_bias_gain16(g);
+    ab.speaker = (n_same | n_other) ? speakers : nullptr; ab.spk_same = (uint8_t)n_same; ab.spk_other = (uint8_t)n_other;
     M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -380,6 +420,58 @@ int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q,
     M2F_HIP(m2f_launch_attn_stream_chunk(sb, table ? &pg : nullptr, T, n_new, static_cast<hipStream_t>(stream)));
     return 0;
 }
+/* ... and the supersets with speaker heads: spk_cache uint8 [S][C] (read), spk_new uint8 [S] (step) / [S][T] (chunk); the advance entries
+   below store the new ids and close the step / the call */
+int m2f_attention_stream_speakers(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                  void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
+                                  const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
+                                  const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_stream_speakers", gain, &g)) return r;
+    if (int r = speaker_heads_ok("m2f_attention_stream_speakers", H, n_same, n_other, spk_new, "the new utterances' speakers (uint8 [S])")) return r;
+    if ((n_same | n_other) && !spk_cache) return fail("m2f_attention_stream_speakers: speaker heads need the cached speakers (uint8 [S][C])");
+    AttnStreamBatch sb;
+    AttnStreamWeights ww;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_speakers", sb, table ? &pg : nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
+    if (weights) if (int r = stream_weights_ok("m2f_attention_stream_speakers", weights, ww)) return r;
+    sb.bias_gain = g;
+    if (n_same | n_other) { sb.spk_cache = spk_cache; sb.spk_new = spk_new; sb.spk_same = (uint8_t)n_same; sb.spk_other = (uint8_t)n_other; }
+    M2F_HIP(m2f_launch_attn_stream(sb, table ? &pg : nullptr, static_cast<hipStream_t>(stream), weights ? &ww : nullptr));
+    return 0;
+}
+int m2f_attention_stream_chunk_speakers(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                        void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
+                                        int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
+                                        const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream) {
+    float g = 0.f;
+    if (int r = bias_gain_ok("m2f_attention_stream_chunk_speakers", gain, &g)) return r;
+    if (int r = speaker_heads_ok("m2f_attention_stream_chunk_speakers", H, n_same, n_other, spk_new, "the new utterances' speakers (uint8 [S][T])")) return r;
+    if ((n_same | n_other) && !spk_cache) return fail("m2f_attention_stream_chunk_speakers: speaker heads need the cached speakers (uint8 [S][C])");
+    AttnStreamBatch sb;
+    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
+    if (int r = stream_attn_fill("m2f_attention_stream_chunk_speakers", sb, table ? &pg : nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
+    sb.bias_gain = g;
+    if (n_same | n_other) { sb.spk_cache = spk_cache; sb.spk_new = spk_new; sb.spk_same = (uint8_t)n_same; sb.spk_other = (uint8_t)n_other; }
+    M2F_HIP(m2f_launch_attn_stream_chunk(sb, table ? &pg : nullptr, T, n_new, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_stream_advance_speakers(int S, int C, int ring, int32_t* count, const uint8_t* active, uint8_t* spk_cache, const uint8_t* spk_new,
+                                m2f_stream_t stream) {
+    if (S < 1 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) return fail("m2f_stream_advance_speakers: S >= 1, 1 <= C <= 512 required");
+    if (!count || !active || !spk_cache || !spk_new) return fail("m2f_stream_advance_speakers: NULL argument");
+    M2F_HIP(m2f_launch_stream_advance_speakers(count, active, S, spk_cache, spk_new, C, ring != 0, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_stream_advance_speakers_n(int S, int T, int C, int ring, int32_t* count, const int32_t* n_new, uint8_t* spk_cache, const uint8_t* spk_new,
+                                  m2f_stream_t stream) {
+    if (S < 1 || C < 1 || C > M2F_ATTN_STREAM_MAX_C || T < 1 || T > M2F_ATTN_STREAM_MAX_CHUNK)
+        return fail("m2f_stream_advance_speakers_n: S >= 1, 1 <= C <= 512, 1 <= T <= 64 required");
+    if (!count || !n_new || !spk_cache || !spk_new) return fail("m2f_stream_advance_speakers_n: NULL argument");
+    M2F_HIP(m2f_launch_stream_advance_speakers_n(count, n_new, S, T, spk_cache, spk_new, C, ring != 0, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+int m2f_attention_speaker_class(int h, int n_same, int n_other) { return m2f_attn_speaker_class(h, n_same, n_other); }
 int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                      void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
                                      const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream) {

@@ -203,7 +203,27 @@ struct AttnBatch {
     int bf16_math;             // bf16 mode, bit mask: 1 = the head-dim contractions (Q K^T, dO V^T) round their operands to bf16 and run
                                // on v_mfma_f32_16x16x32_bf16 (fp32 accumulate): 1/8 of the MFMA instructions at 1/2 the cycles each;
                                // 2 / 4 / 8 / 16 / 32 = the Q / K / V / dO / O slab is staged from the operand's bf16 shadow (half the bytes)
+    // Speaker heads (below), forward only: one id per token row, in the rows' own order (padded: [B, L] as key_pad; packed: row cu[b] + i),
+    // and how many heads of every problem are same-speaker / other-speaker heads.  null / (0, 0) = off.  Appended: every field above
+    // keeps its offset, the struct grew from 648 to 664 bytes (attention.hip's kernarg warm-up covers 768).
+    const uint8_t* speaker;
+    uint8_t spk_same, spk_other;
 };
+// Speaker heads: the class of head h under (n_same, n_other) - heads 0 .. n_same - 1 see the keys of the query's own speaker only (the
+// utterance itself always qualifies), the next n_other heads the keys of every OTHER speaker only, the rest are untouched.  The one
+// definition: every kernel that tests a speaker and every host check calls it.
+enum { M2F_SPK_NONE = 0, M2F_SPK_SAME = 1, M2F_SPK_OTHER = 2 };
+__host__ __device__ inline int m2f_attn_speaker_class(int h, int n_same, int n_other) {
+    return h < n_same ? M2F_SPK_SAME : (h < n_same + n_other ? M2F_SPK_OTHER : M2F_SPK_NONE);
+}
+// host: a launch with speaker heads carries the ids, and its counts fit every problem's heads (the launchers refuse the others)
+inline bool m2f_attn_speakers_ok(const AttnBatch& ab) {
+    if (!(ab.spk_same | ab.spk_other)) return true;
+    if (!ab.speaker) return false;
+    for (int i = 0; i < ab.count && i < M2F_ATTN_MAX_PROBLEMS; ++i)
+        if ((int)ab.spk_same + (int)ab.spk_other > ab.pr[i].H) return false;
+    return true;
+}
 inline void m2f_attn_set_band(AttnBatch& ab, int past, int future) {      // (past, future): >= 0, or negative = unlimited
     const int cap = 1 << 20;                                               // (far beyond any L: the same band, and i +- it cannot overflow)
     ab.band_past = past < 0 ? 0 : (past < cap ? past : cap) + 1;
@@ -317,7 +337,30 @@ struct AttnStreamBatch {
     const uint8_t* active;     // device uint8 [S]
     ShadowMap sh;              // out also written as bf16
     float bias_gain;           // distance-decay bias (m2f_attn_bias_slope): the gain, 0 = off; the new utterance is at distance 0
+    // Speaker heads (m2f_attn_speaker_class; (0, 0) = off).  spk_cache: device uint8 [S][C], the speaker id of the utterance in LOGICAL
+    // cache row j of slot s (the row index the dense addressing uses, the one a page table maps: dense on a paged stream too), ONE
+    // array per stream shared by every site; the attention launches only read it, and never the row the new utterance takes.
+    // spk_new: the ids of the new utterances - [S] (step) or [S][T] (chunk).  m2f_launch_stream_advance_speakers[_n] stores them
+    // behind the last attention launch of the step / the prefill call.
+    const uint8_t* spk_cache;
+    const uint8_t* spk_new;
+    uint8_t spk_same, spk_other;
 };
+// host: what a stream launch with speaker heads needs (the launchers refuse the others before anything is launched)
+inline bool m2f_attn_stream_speakers_ok(const AttnStreamBatch& ab) {
+    if (!(ab.spk_same | ab.spk_other)) return true;
+    if (!ab.spk_cache || !ab.spk_new) return false;
+    for (int i = 0; i < ab.count && i < M2F_ATTN_MAX_PROBLEMS; ++i)
+        if ((int)ab.spk_same + (int)ab.spk_other > ab.pr[i].H) return false;
+    return true;
+}
+// ... and the launches that close a step / a prefill call of a stream with speaker heads: the new ids into the cache rows the new
+// utterances took (ring: row u % C - the byte of the utterance that just left the window), then len += what the plain advance adds.
+// Plain byte stores, one thread per slot; stream-ordered behind the attention launches that read the old row set.
+hipError_t m2f_launch_stream_advance_speakers(int* len, const uint8_t* active, int S, uint8_t* spk_cache, const uint8_t* spk_new, int C,
+                                              int ring, hipStream_t stream);
+hipError_t m2f_launch_stream_advance_speakers_n(int* len, const int* n_new, int S, int T, uint8_t* spk_cache, const uint8_t* spk_new, int C,
+                                                int ring, hipStream_t stream);
 size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16);     // elements (fp32 or bf16) of ONE cache (K or V) of a site
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream);      // len[s] += active[s]
 hipError_t m2f_launch_stream_reset(int* len, const uint8_t* mask, int S, hipStream_t stream);          // len[s] = 0 where mask[s] (null: all)
@@ -590,6 +633,19 @@ __device__ __forceinline__ uint16_t* m2f_shadow_of(const ShadowMap& sh, const fl
     if (!sh.ws_base) return nullptr;
     const ptrdiff_t i = p - sh.ws_base;
     return (i >= 0 && (size_t)i < sh.ws_floats) ? sh.shadow + i : nullptr;
+}
+// Speaker heads, the test per score element.  `ks` = the speaker id of key `lane` of a 64-key block, held by that lane;
+// m2f_spk_pack4: the ids of keys base .. base + 3 (the four keys of one accumulator register quad), one byte each.
+__device__ __forceinline__ uint32_t m2f_spk_pack4(int ks, int base) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w |= ((uint32_t)__shfl(ks, base + r, 64) & 255u) << (8 * r);
+    return w;
+}
+// does a query of speaker `mine` under head class `cls` (wave-uniform) see key r of the pack?
+__device__ __forceinline__ bool m2f_spk_sees(int cls, uint32_t pack, int r, int mine) {
+    const bool eq = ((pack >> (8 * r)) & 255u) == (uint32_t)mine;
+    return cls == M2F_SPK_NONE || eq == (cls == M2F_SPK_SAME);
 }
 #endif
 

@@ -192,6 +192,7 @@ enum BuildStatus { BUILD_OK = 0, BUILD_FAILED, BUILD_TOO_SMALL, BUILD_OVERRAN };
 BuildStatus size_and_build(m2f_plan* dry, bool shared, int64_t slack, m2f_plan* P, int64_t& need, const std::function<int()>& before_build = nullptr);
 // plan_build.hip
 int build_plan(m2f_plan& P, char* ws_base);
+void apply_speakers(m2f_plan& P);      // the plan's speaker-head setting into every attention launch of the built lists
 int build_accumulate(m2f_plan& P);
 extern "C" __attribute__((visibility("default")))      // (an accident of the library's symbol list, kept: internal, nothing outside the library may call it)
 int table_coverage(m2f_plan& P, uint16_t* param_shadow, std::vector<GemmProblem>& tp, std::vector<int>& tensor_of, std::vector<AdamItem>& items, std::vector<int>& tensor);
@@ -208,6 +209,10 @@ struct m2f_plan {
     int in_mask = 0, param_grads = 1;
     int band_past = -1, band_future = -1;   // context band of every attention launch (m2f_plan_attention_band); negative = unlimited
     float bias_gain = 0.f;                  // distance-decay bias of every attention launch (m2f_plan_attention_bias): the applied gain, 0 = off
+    // speaker heads of every attention launch (m2f_plan_attention_speakers): same-speaker / other-speaker heads per site, (0, 0) = off; the ids are
+    // M2F_BUF_SPEAKERS.  Stream and chunk plans: s_spk = the caller's array of cached ids, uint8 [S][C] by logical row (m2f_plan_stream_speakers)
+    int spk_same = 0, spk_other = 0;
+    uint8_t* s_spk = nullptr;
     bool packed = false; int* cu = nullptr;      // T token rows owned by B dialogues through cu_seqlens, device int32 [B + 1] (m2f_plan_create_packed)
     // STREAM plan (m2f_plan_create_stream): B = S stream slots of L = 1 row each, forward only; every attention site runs the streaming
     // kernel (attention_stream.hip) against its own K / V caches of `s_cap` rows per slot, a ring when the context band has a window

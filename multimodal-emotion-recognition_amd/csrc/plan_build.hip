@@ -1038,6 +1038,19 @@ int build_chunk_sites(m2f_plan& P, Builder& bld) {
 
 namespace m2f {
 
+void apply_speakers(m2f_plan& P) {
+    const bool on = (P.spk_same | P.spk_other) != 0;
+    const uint8_t* ids = on ? static_cast<const uint8_t*>(P.bufs[M2F_BUF_SPEAKERS]) : nullptr;
+    for (Launch& l : P.built.fwd) {                      // (forward only: the backward kernels read the saved probabilities)
+        if (l.kind != OP_ATTN_FWD) continue;
+        l.ab.speaker = ids; l.ab.spk_same = (uint8_t)(on ? P.spk_same : 0); l.ab.spk_other = (uint8_t)(on ? P.spk_other : 0);
+        if (P.streaming) {
+            l.sb.spk_cache = on ? P.s_spk : nullptr; l.sb.spk_new = ids;
+            l.sb.spk_same = l.ab.spk_same; l.sb.spk_other = l.ab.spk_other;
+        }
+    }
+}
+
 int build_plan(m2f_plan& P, char* ws_base) {
     const m2f_config& c = P.cfg;
     Builder bld(P);
@@ -1086,6 +1099,10 @@ int build_plan(m2f_plan& P, char* ws_base) {
     // the tables - every other buffer of the plan sits where it sat without them
     P.bufs[M2F_BUF_TEACHER] = P.train ? bld.ar.f((size_t)T * c.cls_out) : nullptr;
     P.bufs[M2F_BUF_DISTILL] = P.train ? bld.ar.f(2) : nullptr;
+    // the speaker ids of the token rows (m2f_plan_attention_speakers), one byte each: behind everything again, in every plan
+    P.bufs[M2F_BUF_SPEAKERS] = bld.ar.alloc<uint8_t>(((size_t)T + 15) & ~(size_t)15);
+    P.bufs[M2F_BUF_STREAM_SPEAKERS] = P.s_spk;
+    apply_speakers(P);
     P.built.ws_used = bld.ar.off;
     if (P.prec == M2F_PREC_BF16 && ws_base != nullptr) {
         const float* wsf = reinterpret_cast<const float*>(ws_base);

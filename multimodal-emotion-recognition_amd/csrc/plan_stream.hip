@@ -85,7 +85,10 @@ m2f_plan* m2f_plan_create_stream_paged(const m2f_config* cfg, int S, int C, int 
 }
 static int stream_body(m2f_plan& P, hipStream_t s) {
     if (int r = do_forward(P, s)) return r;
-    M2F_HIP(m2f_launch_stream_advance(P.s_len, P.s_active, P.B, s));
+    if (P.spk_same | P.spk_other)          // speaker heads: the new ids into the rows the new utterances took, behind the step's last attention launch
+        M2F_HIP(m2f_launch_stream_advance_speakers(P.s_len, P.s_active, P.B, P.s_spk, static_cast<const uint8_t*>(P.bufs[M2F_BUF_SPEAKERS]), P.s_cap, P.s_ring, s));
+    else
+        M2F_HIP(m2f_launch_stream_advance(P.s_len, P.s_active, P.B, s));
     return 0;
 }
 int m2f_stream_step(m2f_plan* plan, int use_graph, m2f_stream_t stream) {
@@ -255,6 +258,7 @@ static m2f_plan* chunk_plan_new(m2f_plan* parent, int T) {
     p->streaming = true; p->s_cap = parent->s_cap; p->s_ring = parent->s_ring;
     p->band_past = parent->band_past; p->band_future = parent->band_future;
     p->bias_gain = parent->bias_gain;                                          // (the chunk's sites take it when they are built)
+    p->spk_same = parent->spk_same; p->spk_other = parent->spk_other; p->s_spk = parent->s_spk;      // (likewise, through apply_speakers)
     p->s_parent = parent; p->s_chunk = T;
     p->s_pages = parent->s_pages; p->s_pg = parent->s_pg;                      // (a paged parent: the same pools through the same table)
     return p;
@@ -276,7 +280,10 @@ m2f_plan* m2f_plan_create_stream_chunk(m2f_plan* parent, int T, float* params, v
 }
 static int prefill_body(m2f_plan& P, hipStream_t s) {
     if (int r = do_forward(P, s)) return r;
-    M2F_HIP(m2f_launch_stream_advance_n(P.s_len, P.s_new, P.B, P.s_chunk, s));
+    if (P.spk_same | P.spk_other)          // (as the step: the chunk's ids, then the counters)
+        M2F_HIP(m2f_launch_stream_advance_speakers_n(P.s_len, P.s_new, P.B, P.s_chunk, P.s_spk, static_cast<const uint8_t*>(P.bufs[M2F_BUF_SPEAKERS]), P.s_cap, P.s_ring, s));
+    else
+        M2F_HIP(m2f_launch_stream_advance_n(P.s_len, P.s_new, P.B, P.s_chunk, s));
     return 0;
 }
 int m2f_stream_prefill(m2f_plan* plan, int use_graph, m2f_stream_t stream) {

@@ -101,18 +101,30 @@ class Distiller:
         teacher.eval()
         teacher.requires_grad_(False)
 
-    def teacher_logits(self, text, audio, mask) -> torch.Tensor:
+    def teacher_logits(self, text, audio, mask, speakers=None) -> torch.Tensor:
         """The teacher's logits [B, L, cls_out] of the batch: its eval forward under ``torch.inference_mode()``, no host sync (a
-        packed teacher counts the batch's valid utterances on the host, as its forward always does)."""
+        packed teacher counts the batch's valid utterances on the host, as its forward always does).  speakers: the batch's ids -
+        handed on only if the TEACHER has speaker heads (it runs under its own setting)."""
         if self.teacher.training:
             self.teacher.eval()
         if mask.shape[0] == 0:                             # (an empty shard of a data-parallel batch)
             return torch.zeros(0, mask.shape[1], self.teacher.m2f_config.cls_out, dtype=torch.float32, device=mask.device)
         self.teacher.engine(mask.device)                   # (built outside inference mode: its buffers stay ordinary tensors)
         with torch.inference_mode():
+            if self.teacher.speaker_heads is not None:
+                return self.teacher(text, audio, mask, speakers=speakers)
             return self.teacher(text, audio, mask)
 
-    def train_step(self, text, audio, mask, emotion, **kw) -> torch.Tensor:
+    def train_step(self, text, audio, mask, emotion, speakers=None, **kw) -> torch.Tensor:
+        """speakers ([B, L] ids): student and teacher each run under their OWN speaker-head setting, and the batch's ids go to
+        whichever of the two has one; needed as soon as either has, refused (ValueError) when neither does."""
         pair = check_distill((self.alpha, self.temperature), "Distiller")          # (before the teacher runs)
-        u = self.teacher_logits(text, audio, mask)
+        s_on, t_on = self.student.speaker_heads is not None, self.teacher.speaker_heads is not None
+        if speakers is not None and not (s_on or t_on):
+            raise ValueError("Distiller.train_step: speakers were given, but neither the student nor the teacher has speaker heads")
+        if speakers is None and (s_on or t_on):
+            raise ValueError("Distiller.train_step: the " + ("student" if s_on else "teacher") + " has speaker heads; pass speakers= ([B, L] ids)")
+        u = self.teacher_logits(text, audio, mask, speakers)
+        if s_on:
+            kw["speakers"] = speakers
         return self.student.train_step(text, audio, mask, emotion, teacher_logits=u, distill=pair, **kw)

@@ -409,6 +409,13 @@ def reduce_metrics(values: Sequence[float], device=None) -> List[float]:
     return t.cpu().tolist()
 
 
+def _refuse_speaker_heads(model) -> None:
+    if getattr(model, "speaker_heads", None) is not None:
+        raise ValueError(f"DataParallelStep: the model has speaker_heads={model.speaker_heads}; the data-parallel step does not carry "
+                         "speaker ids yet and will not drop the setting silently - train such a model with M2FNet.train_step, or call "
+                         "model.set_speaker_heads(None)")
+
+
 class DataParallelStep:
     """One optimizer step of dialogue-sharded data-parallel training:
     m2f_step(normalise=0) -> tail <- (den, num) -> all-reduce -> fused Adam with grad_scale = global den."""
@@ -425,6 +432,7 @@ class DataParallelStep:
         (runtime.Plan.grad_bf16) instead of a rounding pass over the fp32 buffer; None = M2F_GRAD_BF16 (default on)."""
         if overlap is None:
             overlap = os.environ.get("M2F_DP_OVERLAP", "0") == "1"
+        _refuse_speaker_heads(model)          # (before the engine, the reducer or any collective)
         self.model, self.optimizer, self.overlap = model, optimizer, bool(overlap)
         self.grad_bf16 = (os.environ.get("M2F_GRAD_BF16", "1") != "0") if grad_bf16 is None else bool(grad_bf16)
         self._split: Optional[int] = None
@@ -473,6 +481,7 @@ class DataParallelStep:
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
         from .distill import resolve_distill_args
+        _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
         eng = self.model.engine()

@@ -105,10 +105,34 @@ def quantize_fp8(src: torch.Tensor, scale: float, out: Optional[torch.Tensor] = 
     return dst
 
 
+def _speaker_args(who: str, speakers, speaker_heads, H: int, rows: int, device):
+    """(ids uint8 [rows] on `device`, n_same, n_other) of a kernel-level call, or (None, 0, 0) when speaker_heads is None - the call
+    without the argument.  Raises ValueError before anything is launched."""
+    heads = runtime.speaker_heads(speaker_heads, {"this launch": H})
+    if heads is None:
+        if speakers is not None:
+            raise ValueError(f"{who}: speakers were given without speaker_heads=(n_same, n_other)")
+        return None, 0, 0
+    if speakers is None:
+        raise ValueError(f"{who}: speaker_heads={heads} needs speakers (one id per utterance)")
+    ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
+    if ids.numel() != rows:
+        raise ValueError(f"{who}: speakers must hold one id per token row ({rows}), got {ids.numel()}")
+    return ids, heads[0], heads[1]
+
+
+speaker_head_class = runtime.speaker_head_class      # (the library's own statement of the rule: csrc/ops.h, m2f_attn_speaker_class)
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: torch.Tensor, B: int, L: int, H: int,
                   drop_site: int = 0, drop_p: float = 0.0, rng: Optional[torch.Tensor] = None,
-                  past: Optional[int] = None, future: Optional[int] = None, bias: Optional[float] = None):
+                  past: Optional[int] = None, future: Optional[int] = None, bias: Optional[float] = None,
+                  speakers: Optional[torch.Tensor] = None, speaker_heads=None):
     """q/k/v: [B*L, H*hd] (possibly column slices).  Returns (out [B*L, H*hd], probs^T [B*H, Lp, Lp]).
+    speakers / speaker_heads: speaker heads (`runtime.speaker_heads` has the rule) - speakers: one id per utterance, [B, L] or [B*L],
+    uint8 / int32 / int64 with values 0 .. 255; speaker_heads = (n_same, n_other), n_same + n_other <= H.  The condition is ANDed with
+    key padding and the band, the bias applies to what stays visible; a query whose head sees no key (an other-speaker head in a
+    monologue) gets a zero row of probabilities and a zero output row.  speaker_heads=None is the call without the argument.
     past / future: context band - query slot i sees the valid keys of slots i - past .. i + future only (None = unlimited on that
     side; (None, 0) is causal).  Hidden keys have probability exactly 0; a query that sees no key at all (a pad slot whose band
     holds pad keys only) gets a zero row of probabilities and a zero output row, where torch's masked softmax gives NaN - pad
@@ -123,7 +147,13 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     Lp = 16 * ((L + 15) // 16)
     probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     kp = key_pad.to(torch.uint8).contiguous()
-    if gain != 0.0:
+    ids, n_same, n_other = _speaker_args("attention_fwd", speakers, speaker_heads, H, B * L, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_fwd_speakers(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                               _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                               *runtime.context_band(past, future), gain, ptr(ids), n_same, n_other),
+              "m2f_attention_fwd_speakers")
+    elif gain != 0.0:
         check(lib().m2f_attention_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
                                            _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
                                            *runtime.context_band(past, future), gain), "m2f_attention_fwd_bias")
@@ -249,9 +279,60 @@ def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool =
     return tuple(torch.full((S, H, capacity, hdp), fill, dtype=dt, device=device) for _ in range(2))
 
 
+def _stream_speaker_args(who: str, speakers, speaker_cache, speaker_heads, H: int, S: int, C: int, per_slot: int, device):
+    """(new ids uint8 [S * per_slot], cached ids uint8 [S, C], n_same, n_other) of a streaming launch, or (None, None, 0, 0)."""
+    heads = runtime.speaker_heads(speaker_heads, {"this launch": H})
+    if heads is None:
+        if speakers is not None or speaker_cache is not None:
+            raise ValueError(f"{who}: speakers / speaker_cache were given without speaker_heads=(n_same, n_other)")
+        return None, None, 0, 0
+    if speakers is None or speaker_cache is None:
+        raise ValueError(f"{who}: speaker_heads={heads} needs speakers (the new utterances' ids) and speaker_cache (uint8 [S, capacity])")
+    if (not isinstance(speaker_cache, torch.Tensor) or speaker_cache.dtype != torch.uint8 or tuple(speaker_cache.shape) != (S, C)
+            or not speaker_cache.is_contiguous() or speaker_cache.device != device):
+        raise ValueError(f"{who}: speaker_cache must be a contiguous uint8 [{S}, {C}] tensor on the launch's device")
+    ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
+    if ids.numel() != S * per_slot:
+        raise ValueError(f"{who}: speakers must hold {S * per_slot} ids, got {ids.numel()}")
+    return ids, speaker_cache, heads[0], heads[1]
+
+
+def stream_advance_speakers(lengths: torch.Tensor, active: torch.Tensor, speaker_cache: torch.Tensor, speakers: torch.Tensor,
+                            ring: bool = False) -> None:
+    """The launch that closes a step of a stream with speaker heads (m2f_stream_advance_speakers): for every active slot the new
+    utterance's id goes into speaker_cache[s, lengths[s] % capacity] (ring) or [s, lengths[s]], then lengths[s] += 1.  Call it BEHIND
+    the step's attention launches (`attention_stream(..., speaker_heads=)` reads the cache and does not write it)."""
+    runtime.require_gpu()
+    S, C = speaker_cache.shape
+    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S or speaker_cache.dtype != torch.uint8:
+        raise ValueError("stream_advance_speakers: lengths int32 [S], active [S] and speaker_cache uint8 [S, capacity] required")
+    act = active.to(torch.uint8).contiguous()
+    ids = runtime.speaker_ids(speakers, "stream_advance_speakers: speakers").reshape(-1).contiguous()
+    if ids.numel() != S:
+        raise ValueError(f"stream_advance_speakers: speakers must hold {S} ids")
+    check(lib().m2f_stream_advance_speakers(S, C, int(ring), ptr(lengths), ptr(act), ptr(speaker_cache), ptr(ids), stream_ptr()),
+          "m2f_stream_advance_speakers")
+
+
+def stream_advance_speakers_n(lengths: torch.Tensor, new: torch.Tensor, speaker_cache: torch.Tensor, speakers: torch.Tensor, T: int,
+                              ring: bool = False) -> None:
+    """... of a chunk call (m2f_stream_advance_speakers_n): slot s's first new[s] ids of speakers[s, :T] into the rows its chunk took -
+    the rows `attention_stream_chunk` stored K / V to - then lengths[s] += new[s]."""
+    runtime.require_gpu()
+    S, C = speaker_cache.shape
+    if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S or speaker_cache.dtype != torch.uint8:
+        raise ValueError("stream_advance_speakers_n: lengths int32 [S], new int32 [S] and speaker_cache uint8 [S, capacity] required")
+    ids = runtime.speaker_ids(speakers, "stream_advance_speakers_n: speakers").reshape(-1).contiguous()
+    if ids.numel() != S * T:
+        raise ValueError(f"stream_advance_speakers_n: speakers must hold {S * T} ids")
+    check(lib().m2f_stream_advance_speakers_n(S, T, C, int(ring), ptr(lengths), ptr(new), ptr(speaker_cache), ptr(ids), stream_ptr()),
+          "m2f_stream_advance_speakers_n")
+
+
 def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, lengths: torch.Tensor,
                      active: torch.Tensor, H: int, ring: bool = False, bf16: bool = False,
-                     weights: Optional[torch.Tensor] = None, bias: Optional[float] = None) -> torch.Tensor:
+                     weights: Optional[torch.Tensor] = None, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,
+                     speaker_cache: Optional[torch.Tensor] = None, speaker_heads=None) -> torch.Tensor:
     """One streaming-attention launch (m2f_attention_stream): slot s takes the new rows q[s] / k[s] / v[s] ([S, H*hd] fp32, possibly column
     slices) against the rows it has cached.  kcache / vcache: `attention_stream_caches`; lengths int32 [S] = utterances cached so far
     (read, NOT advanced); active uint8 / bool [S].  An active slot stores its new K / V rows at row lengths % capacity (ring) or
@@ -261,7 +342,11 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
     kernel) also fills it with each slot's row of attention probabilities in logical order: column t = the t-th oldest live utterance
     (`streaming.logical_columns`), the last live column the new one; zeros behind the live count and for inactive slots.  Same `out`, same bits.
     bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): the new utterance
-    is at distance 0, the one cached before it at distance 1, ...; the cached rows do not depend on it."""
+    is at distance 0, the one cached before it at distance 1, ...; the cached rows do not depend on it.
+    speakers / speaker_cache / speaker_heads: speaker heads (`runtime.speaker_heads`) - speakers: the new utterances' ids, [S];
+    speaker_cache: uint8 [S, capacity], the cached utterances' ids by logical cache row, READ only (`stream_advance_speakers` stores
+    the new ids and advances `lengths`); an other-speaker head with no other speaker in sight gives a zero row.  speaker_heads=None is
+    the call without the arguments."""
     runtime.require_gpu()
     gain = runtime.position_bias(bias)                  # (raises ValueError)
     S, E = q.shape
@@ -275,6 +360,12 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
         raise ValueError("attention_stream: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream", speakers, speaker_cache, speaker_heads, H, S, C, 1, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_stream_speakers(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None, 0, 0,
+                                                  0, C, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights), gain,
+                                                  ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()), "m2f_attention_stream_speakers")
+        return out
     if gain != 0.0:
         check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None, 0, 0, 0,
                                               C, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights), gain,
@@ -298,13 +389,18 @@ def _stream_weights_ok(who: str, weights, S: int, H: int, C: int) -> None:
 
 def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                            lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, ring: bool = False, bf16: bool = False,
-                           bias: Optional[float] = None) -> torch.Tensor:
+                           bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,
+                           speaker_cache: Optional[torch.Tensor] = None, speaker_heads=None) -> torch.Tensor:
     """One chunk launch of the streaming attention (m2f_attention_stream_chunk): slot s takes its first new[s] (int32 [S], 0 .. T, T <= 64)
     rows of q / k / v ([S*T, H*hd] fp32, possibly column slices; rows s*T + t) against the rows it has cached - row by row what new[s]
     `attention_stream` launches give.  lengths int32 [S] is read, NOT advanced.  The new K / V rows go to rows (lengths + t) % capacity
     (ring) or lengths + t (lengths + new <= capacity required, else the slot is left untouched) - of more than `capacity` rows on a ring
     the last `capacity`.  Rows t >= new[s] of the result are zeros and their input rows are never read.  Returns out [S*T, H*hd].
-    bias: as `attention_stream` - row t of a chunk is utterance lengths + t."""
+    bias: as `attention_stream` - row t of a chunk is utterance lengths + t.
+    speakers / speaker_cache / speaker_heads: speaker heads (`runtime.speaker_heads`) - speakers: the new utterances' ids, [S, T] (row s*T + t);
+    speaker_cache: uint8 [S, capacity], the cached utterances' ids by logical cache row, READ only (`stream_advance_speakers_n` stores
+    the new ids and advances `lengths`); an other-speaker head with no other speaker in sight gives a zero row.  speaker_heads=None is
+    the call without the arguments."""
     runtime.require_gpu()
     gain = runtime.position_bias(bias)                  # (raises ValueError)
     rows, E = q.shape
@@ -318,6 +414,12 @@ def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kc
     if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S:
         raise ValueError("attention_stream_chunk: lengths int32 [S] and new int32 [S] required")
     out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_chunk", speakers, speaker_cache, speaker_heads, H, S, C, T, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_stream_chunk_speakers(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None,
+                                                        0, 0, 0, C, int(ring), ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), gain,
+                                                        ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()), "m2f_attention_stream_chunk_speakers")
+        return out
     if gain != 0.0:
         check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None,
                                                     0, 0, 0, C, int(ring), ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), gain,
@@ -353,13 +455,16 @@ def _paged_args(who: str, kpool, vpool, table, S: int, capacity: int, bf16: bool
 
 def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
                            lengths: torch.Tensor, active: torch.Tensor, H: int, capacity: int, ring: bool = False,
-                           bf16: bool = False, weights: Optional[torch.Tensor] = None, bias: Optional[float] = None) -> torch.Tensor:
+                           bf16: bool = False, weights: Optional[torch.Tensor] = None, bias: Optional[float] = None,
+                           speakers: Optional[torch.Tensor] = None, speaker_cache: Optional[torch.Tensor] = None,
+                           speaker_heads=None) -> torch.Tensor:
     """`attention_stream` over page pools (m2f_attention_stream_paged): logical cache row r of slot s - the row `attention_stream` calls r -
     is row r % page_rows of page table[s, r // page_rows].  kpool / vpool: `attention_stream_pools`; table int32 [S, ceil(capacity /
     page_rows)], read only at the entries of pages that hold a live row or take the new one.  The same bits as `attention_stream` on
     caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd].
     weights: as `attention_stream` (m2f_attention_stream_weights_paged) - the order is logical, so the rows are the dense launch's bits.
-    bias: as `attention_stream`."""
+    bias: as `attention_stream`.  speakers / speaker_cache / speaker_heads: as `attention_stream` - speaker_cache stays the dense
+    uint8 [S, capacity] array (logical rows: the page table never enters)."""
     runtime.require_gpu()
     gain = runtime.position_bias(bias)                  # (raises ValueError)
     S, E = q.shape
@@ -370,6 +475,13 @@ def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kp
         raise ValueError("attention_stream_paged: lengths int32 [S] and active [S] required")
     act = active.to(torch.uint8).contiguous()
     out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_paged", speakers, speaker_cache, speaker_heads, H, S, capacity, 1, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_stream_speakers(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
+                                                  table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
+                                                  int(bf16), ptr(weights), gain, ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()),
+              "m2f_attention_stream_speakers")
+        return out
     if gain != 0.0:
         check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
                                               table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
@@ -389,10 +501,12 @@ def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kp
 
 def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
                                  table: torch.Tensor, lengths: torch.Tensor, new: torch.Tensor, H: int, T: int, capacity: int,
-                                 ring: bool = False, bf16: bool = False, bias: Optional[float] = None) -> torch.Tensor:
+                                 ring: bool = False, bf16: bool = False, bias: Optional[float] = None,
+                                 speakers: Optional[torch.Tensor] = None, speaker_cache: Optional[torch.Tensor] = None,
+                                 speaker_heads=None) -> torch.Tensor:
     """`attention_stream_chunk` over page pools (m2f_attention_stream_chunk_paged; layout: `attention_stream_paged`).  q / k / v hold
     S * T rows, S = table.shape[0].  The same bits, output and stored rows, as the dense chunk launch.  Returns out [S*T, H*hd].
-    bias: as `attention_stream_chunk`."""
+    bias: as `attention_stream_chunk`.  speakers / speaker_cache / speaker_heads: as `attention_stream_chunk`."""
     runtime.require_gpu()
     gain = runtime.position_bias(bias)                  # (raises ValueError)
     rows, E = q.shape
@@ -404,6 +518,13 @@ def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     if lengths.dtype != torch.int32 or new.dtype != torch.int32 or new.numel() != S:
         raise ValueError("attention_stream_chunk_paged: lengths int32 [S] and new int32 [S] required")
     out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_chunk_paged", speakers, speaker_cache, speaker_heads, H, S, capacity, T, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_stream_chunk_speakers(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
+                                                        ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
+                                                        ptr(out), _ld(out), int(bf16), gain, ptr(spk_c), ptr(ids), n_same, n_other,
+                                                        stream_ptr()), "m2f_attention_stream_chunk_speakers")
+        return out
     if gain != 0.0:
         check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
                                                     ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
@@ -499,7 +620,8 @@ def _varlen_rows(cu: Optional[torch.Tensor], key_pad: Optional[torch.Tensor]):
 def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, L: int, H: int,
                          cu: Optional[torch.Tensor] = None, key_pad: Optional[torch.Tensor] = None, drop_site: int = 0,
                          drop_p: float = 0.0, rng: Optional[torch.Tensor] = None, past: Optional[int] = None,
-                         future: Optional[int] = None, probs: Optional[torch.Tensor] = None, bias: Optional[float] = None):
+                         future: Optional[int] = None, probs: Optional[torch.Tensor] = None, bias: Optional[float] = None,
+                         speakers: Optional[torch.Tensor] = None, speaker_heads=None):
     """Long-dialogue attention (m2f_attention_varlen_fwd, L <= 512).  q/k/v: [T, H*hd] (possibly column slices) with either
     cu (int [B+1]: dialogue b = rows cu[b] .. cu[b+1]-1, T = q.shape[0]) or key_pad ([B, L] or [B*L], True = padded key;
     T = B*L).  Returns (out [T, H*hd], probs^T [B*H, Lp, Lp]).
@@ -508,7 +630,9 @@ def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: i
     the fresh buffer made here; whatever it held in a buffer passed as `probs`), and `attention_varlen_bwd` given the same band
     does not read it.
     bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): a visible key's
-    score gets -slope(h, H, gain) * |i - j|, the gain applied as `runtime.position_bias` rounds it."""
+    score gets -slope(h, H, gain) * |i - j|, the gain applied as `runtime.position_bias` rounds it.
+    speakers / speaker_heads: as `attention_fwd` - speakers holds one id per TOKEN ROW, in the rows' order ([T]; padded rows: [B, L]).
+    No block pair is skipped on their account: every element of a visited block is written, a hidden one as 0."""
     runtime.require_gpu()
     gain = runtime.position_bias(bias)                  # (raises ValueError)
     T, E = q.shape
@@ -519,7 +643,13 @@ def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: i
     if probs is None:
         probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     assert probs.shape == (B * H, Lp, Lp) and probs.is_contiguous() and probs.dtype == torch.float32 and probs.is_cuda
-    if gain != 0.0:
+    ids, n_same, n_other = _speaker_args("attention_varlen_fwd", speakers, speaker_heads, H, T, q.device)
+    if ids is not None:
+        check(lib().m2f_attention_varlen_fwd_speakers(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                                      ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                                      *runtime.context_band(past, future), gain, ptr(ids), n_same, n_other),
+              "m2f_attention_varlen_fwd_speakers")
+    elif gain != 0.0:
         check(lib().m2f_attention_varlen_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
                                                   ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
                                                   *runtime.context_band(past, future), gain), "m2f_attention_varlen_fwd_bias")
@@ -662,11 +792,13 @@ def cross_entropy_distill(logits: torch.Tensor, teacher: torch.Tensor, labels: t
 
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
-                      need_weights: bool = False, bias: Optional[float] = None):
+                      need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,
+                      speaker_heads=None):
     """FusionAttentionModule.forward (reference src/model.py:13-20), dropout = identity.  past / future: context band of its
     attention (`attention_fwd`); the reference has none.  need_weights: also the head-averaged attention map [B, L, L] that the
     reference's own call computes and drops (`attention_weights`).  bias: gain of the distance-decay bias of its attention
-    (`attention_fwd`); None = off."""
+    (`attention_fwd`); None = off.  speakers ([B, L]) / speaker_heads: speaker heads of its attention
+    (`attention_fwd`) - utterance i has one speaker as text query and as audio key."""
     B, L, E = text.shape
     t = text.reshape(B * L, E).contiguous()
     a = audio.reshape(B * L, E).contiguous()
@@ -674,9 +806,11 @@ def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin
     k = gemm(a, in_w[E:2 * E], NT, precision, bias=in_b[E:2 * E])
     v = gemm(t, in_w[2 * E:], NT, precision, bias=in_b[2 * E:])
     if L > 64:          # (the dialogue kernels of attention_fwd hold L <= 64; above, the long-dialogue kernels, padded form)
-        att, probs = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future, bias=bias)
+        att, probs = attention_varlen_fwd(q, k, v, B, L, n_head, key_pad=key_pad, past=past, future=future, bias=bias,
+                                          speakers=speakers, speaker_heads=speaker_heads)
     else:
-        att, probs = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future, bias=bias)
+        att, probs = attention_fwd(q, k, v, key_pad.reshape(-1), B, L, n_head, past=past, future=future, bias=bias,
+                                   speakers=speakers, speaker_heads=speaker_heads)
     x = gemm(att, out_w, NT, precision, bias=out_b)
     y = gemm(x, lin_w[:, :E], NT, precision, a1=t, b1=lin_w[:, E:], bias=lin_b, relu_a=True, relu_out=True)
     if need_weights:

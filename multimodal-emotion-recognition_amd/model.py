@@ -84,8 +84,11 @@ class FusionAttentionModule(nn.Module):
     """Mirror of reference src/model.py:5-20.  Inside ``M2FNet`` it is a parameter holder (the fusion stack
     runs in the plan); called on its own it executes the same gfx950 kernels layer-wise (inference only)."""
 
-    def __init__(self, embedding_size: int, n_head: int, dropout: float, position_bias: Optional[float] = None):
+    def __init__(self, embedding_size: int, n_head: int, dropout: float, position_bias: Optional[float] = None,
+                 speaker_heads: Optional[Tuple[int, int]] = None):
         super().__init__()
+        # speaker heads of a standalone call (runtime.speaker_heads: None = off); inside M2FNet the model's own setting rules
+        self.speaker_heads = runtime.speaker_heads(speaker_heads, {"this module": n_head})
         # gain of the distance-decay attention bias of a standalone call (runtime.position_bias: None = off; stored as applied);
         # inside M2FNet the model's own setting rules (M2FNet.set_position_bias), this attribute is not read
         self.position_bias = runtime.position_bias(position_bias) or None
@@ -95,20 +98,42 @@ class FusionAttentionModule(nn.Module):
         self.embedding_size, self.n_head, self.dropout_p = embedding_size, n_head, dropout
 
     def forward(self, text: torch.Tensor, audio: torch.Tensor, key_padding_mask: torch.Tensor,
-                past: Optional[int] = None, future: Optional[int] = None, need_weights: bool = False):
+                past: Optional[int] = None, future: Optional[int] = None, need_weights: bool = False,
+                speakers: Optional[torch.Tensor] = None):
         """past / future: context band of the attention (``functional.attention_fwd``): text utterance i attends to the audio of
         utterances i - past .. i + future only, None = unlimited.  The reference's module has no such argument.
         need_weights: return ``(y, weights [B, L, L])`` - the head-averaged attention map that the reference's own
         ``nn.MultiheadAttention`` call computes and drops (src/model.py:14); default: ``y`` alone, as ever.
-        The module's ``position_bias`` (constructor; None = off) adds the distance-decay bias of ``functional.attention_fwd``."""
+        The module's ``position_bias`` (constructor; None = off) adds the distance-decay bias of ``functional.attention_fwd``.
+        speakers ([B, L] ids, ``runtime.speaker_ids``): required by a module built with ``speaker_heads=(n_same, n_other)`` - text
+        utterance i then sees, on its same-speaker heads, the audio of its own speaker's utterances only, on its other-speaker heads
+        that of the others only; a module without the setting refuses the argument."""
         from . import functional as F
+        _check_speakers("FusionAttentionModule.forward", self.speaker_heads, speakers, key_padding_mask.shape)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("standalone FusionAttentionModule.forward is inference-only; train it inside M2FNet "
                                "(wrap the call in torch.no_grad())")
         return F.fam_layer_forward(text, audio, key_padding_mask, self.multihead_attention.in_proj_weight,
                                    self.multihead_attention.in_proj_bias, self.multihead_attention.out_proj.weight,
                                    self.multihead_attention.out_proj.bias, self.linear.weight, self.linear.bias,
-                                   self.n_head, past=past, future=future, need_weights=need_weights, bias=self.position_bias)
+                                   self.n_head, past=past, future=future, need_weights=need_weights, bias=self.position_bias,
+                                   speakers=speakers, speaker_heads=self.speaker_heads)
+
+
+def _check_speakers(who: str, heads, speakers, shape) -> Optional[torch.Tensor]:
+    """The batch's speaker ids as uint8 [B, L] for a model / module with speaker heads; None for one without.  A model with the setting
+    called without ids, and a model without it called WITH ids (it would ignore them), both raise ValueError."""
+    if heads is None:
+        if speakers is not None:
+            raise ValueError(f"{who}: speakers were given, but this model has no speaker heads (speaker_heads=(n_same, n_other)); "
+                             "it would ignore them")
+        return None
+    if speakers is None:
+        raise ValueError(f"{who}: this model has speaker_heads={heads}; pass speakers= (one id per utterance, [B, L])")
+    ids = runtime.speaker_ids(speakers, f"{who}: speakers")
+    if tuple(ids.shape) != tuple(shape):
+        raise ValueError(f"{who}: speakers must be [B, L] = {tuple(shape)} like the mask, got {tuple(ids.shape)}")
+    return ids
 
 
 class _Anchor(torch.autograd.Function):
@@ -254,12 +279,13 @@ class _Engine:
         return Bb, Lb
 
     @staticmethod
-    def plan_key(B, L, T, want_backward, dropout_active, precision, outputs=(0, True), band=(None, None), bias=None) -> Tuple:
+    def plan_key(B, L, T, want_backward, dropout_active, precision, outputs=(0, True), band=(None, None), bias=None, speakers=None) -> Tuple:
         """A plan's key without its instance number.  Only a non-default `outputs` / context band / position bias (the applied gain;
         None or 0 = off) extends the tuple: the keys of a model that uses none of them are what they were before any existed."""
         key = (B, L, T, want_backward, dropout_active, precision) + (() if outputs == (0, True) else (outputs,))
         key = key if band == (None, None) else key + (("context",) + tuple(band),)
-        return key if not bias else key + (("position_bias", float(bias)),)
+        key = key if not bias else key + (("position_bias", float(bias)),)
+        return key if not speakers else key + (("speaker_heads",) + tuple(speakers),)      # (a speaker setting: its own plans again)
 
     def plan(self, B: int, L: int, want_backward: bool, dropout_active: bool, valid: Optional[int] = None,
              outputs: Tuple[int, bool] = (0, True)) -> runtime.Plan:
@@ -285,7 +311,8 @@ class _Engine:
         outputs = (int(outputs[0]), bool(outputs[1]))
         band = self.model.context                         # (read per call: M2FNet.set_context only changes which plans are handed out)
         bias = self.model.position_bias                   # (read per call, as the band)
-        base = self.plan_key(B, L, T, want_backward, dropout_active, self.precision, outputs, band, bias)
+        spk = self.model.speaker_heads                    # (likewise)
+        base = self.plan_key(B, L, T, want_backward, dropout_active, self.precision, outputs, band, bias, spk)
         inst, key, pl, oldest = 0, None, None, None
         while True:                                       # first instance of this shape that no live autograd graph owns
             key = base + (inst,)
@@ -321,6 +348,8 @@ class _Engine:
                 pl.attention_band(*band)                  # (once, before its first launch: a plan keeps the band of its key)
             if bias:
                 pl.attention_bias(bias)                   # (likewise: a plan keeps the gain of its key)
+            if spk:
+                pl.attention_speakers(spk)                # (likewise)
             self.plans[key] = pl
             self._evict(max(self.max_plans, 1), self.max_plan_bytes, protect=key)
         else:
@@ -429,7 +458,7 @@ class M2FNet(nn.Module):
 
     def __init__(self, config, precision: Optional[str] = None, shape_buckets: Optional[bool] = None,
                  packed: Optional[bool] = None, context: Optional[Tuple[Optional[int], Optional[int]]] = None,
-                 position_bias: Optional[float] = None):
+                 position_bias: Optional[float] = None, speaker_heads: Optional[Tuple[int, int]] = None):
         super().__init__()
         self.config = config
         self._context: Tuple[Optional[int], Optional[int]] = (None, None)
@@ -479,6 +508,8 @@ class M2FNet(nn.Module):
         head.append(self.dropout)
         head.append(_LinearParams(c.cls_hidden, c.cls_out))
         self.output_layer = nn.Sequential(*head)
+        self._speaker_heads: Optional[Tuple[int, int]] = None
+        self.set_speaker_heads(*(speaker_heads if speaker_heads is not None else (None,)))
         self._engine: Optional[_Engine] = None
         self._grad_accumulation = False
 
@@ -534,8 +565,46 @@ class M2FNet(nn.Module):
         the gain it was created under (``DialogueStream.position_bias``) and refuses to run after a change."""
         self._position_bias = runtime.position_bias(gain) or None
 
+    # -- speaker heads ---------------------------------------------------------------------------------
+    @property
+    def speaker_heads(self) -> Optional[Tuple[int, int]]:
+        """(n_same, n_other), or None when the model has no speaker heads."""
+        return self._speaker_heads
+
+    def _site_heads(self) -> Dict[str, int]:
+        c = self.m2f_config
+        sites = {}
+        if c.audio_enabled and c.ntrans_audio * c.nlayers_audio > 0:
+            sites["the audio encoder (n_head_audio)"] = c.nhead_audio
+        if c.text_enabled and c.ntrans_text * c.nlayers_text > 0:
+            sites["the text encoder (n_head_text)"] = c.nhead_text
+        if c.fam_enabled and c.nlayers_fam > 0:
+            sites["the fusion layers (n_head_fam)"] = c.nhead_fam
+        return sites
+
+    def set_speaker_heads(self, n_same: Optional[int] = None, n_other: Optional[int] = None) -> None:
+        """Speaker-aware heads of EVERY attention site - both modality encoders and every fusion layer: at a site with H heads, heads
+        ``0 .. n_same - 1`` let query utterance i see key utterance j only if ``speakers[b, j] == speakers[b, i]`` (a speaker's own
+        earlier turns: inertia; the utterance itself always qualifies), heads ``n_same .. n_same + n_other - 1`` only if the speakers
+        differ (other people's turns: influence), the remaining heads are untouched.  The condition is ANDed with key padding and
+        the context band, the position bias applies to what stays visible; a hidden key has probability exactly 0, a query that
+        sees no key (an other-speaker head in a monologue, a first utterance under a causal band) gets a zero row where torch gives
+        NaN.  At a fusion site utterance i has one speaker as text query and as audio key.  ``set_speaker_heads(None)`` (or no
+        argument), the default: off, bit for bit what the model computed before.  ``n_same + n_other`` must fit the heads of every
+        enabled site (ValueError naming the site).  No parameters: ``state_dict``, checkpoints and optimizers are untouched.
+        With the setting on, ``forward`` / ``train_step`` / ``eval_step`` / ``attention_maps`` REQUIRE ``speakers=`` ([B, L] ids laid
+        out like ``mask``: uint8 / int32 / int64, values 0 .. 255, only equality is used, pad slots ignored) and a model without it
+        refuses the argument; ``Distiller`` hands the batch's speakers to whichever of student and teacher has the setting;
+        ``DataParallelStep`` refuses such a model.  Takes effect at the next call, every setting keeps its own plans.  A
+        ``DialogueStream`` keeps the setting it was created under and refuses to run after a change until ``reset()``."""
+        if n_same is None and n_other is None:
+            self._speaker_heads = None
+            return
+        self._speaker_heads = runtime.speaker_heads((n_same, 0 if n_other is None else n_other), self._site_heads())
+
     # -- reference surface -----------------------------------------------------------------------------
-    def forward(self, text, audio, mask):
+    def forward(self, text, audio, mask, speakers=None):
+        ids = _check_speakers("M2FNet.forward", self._speaker_heads, speakers, mask.shape)
         eng = self.engine(mask.device)
         B, L = mask.shape
         grad_on = torch.is_grad_enabled()
@@ -552,7 +621,7 @@ class M2FNet(nn.Module):
         plan = eng.plan(B, L, want_bwd, self.training and self.m2f_config.dropout > 0.0, valid, outputs)
         # (detached: the staging copies are plumbing, autograd reaches the inputs through _Anchor)
         det = lambda x: x.detach() if isinstance(x, torch.Tensor) else x          # noqa: E731
-        plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask)
+        plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask, speakers=ids)
         if want_bwd:
             out = _Anchor.apply(eng.anchor, text, audio, self, plan)
             plan.hold(out.grad_fn)
@@ -599,17 +668,18 @@ class M2FNet(nn.Module):
         maps = plan.attention_maps([names.index(n) for n in want], not average_heads, dst, valid, shape)
         return dict(zip(want, maps))
 
-    def attention_maps(self, text, audio, mask, average_heads: bool = True, sites=None):
-        """``(logits, maps)``: a no-grad ``forward`` in the model's current mode, then ``last_attention(average_heads, sites)``."""
+    def attention_maps(self, text, audio, mask, average_heads: bool = True, sites=None, speakers=None):
+        """``(logits, maps)``: a no-grad ``forward`` in the model's current mode, then ``last_attention(average_heads, sites)``.
+        speakers: as ``forward`` (a model with speaker heads; pairs its heads hide are exactly 0 in the maps)."""
         with torch.no_grad():
-            logits = self(text, audio, mask)
+            logits = self(text, audio, mask, speakers=speakers) if speakers is not None else self(text, audio, mask)
         return logits, self.last_attention(average_heads, sites)
 
     # -- fused fast path (forward + criterion + backward as one launch list / hipGraph) ---------------
     def train_step(self, text, audio, mask, emotion, label_smoothing: float = 0.1,
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
-                   distill: Optional[Tuple[float, float]] = None) -> torch.Tensor:
+                   distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -619,8 +689,11 @@ class M2FNet(nn.Module):
         changed): a schedule of alpha replays the captured step.  Distilled and plain calls mix freely on one model.
         optimizer (a ``FusedAdam`` of this model): the call is ALSO ``optimizer.step()`` (src/train.py:231) - in bf16 mode the
         weight-gradient launch applies the update itself (``FusedAdam.prepare_fused``; the matrices' ``.grad`` is then not written),
-        otherwise the optimizer's own kernel runs behind the step."""
+        otherwise the optimizer's own kernel runs behind the step.
+        speakers ([B, L] ids): required by a model with speaker heads (``set_speaker_heads``), refused by one without; an input like
+        the mask - a captured step replays while the ids change."""
         from .distill import resolve_distill_args
+        ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
         dist = resolve_distill_args(teacher_logits, distill, mask.shape[0], mask.shape[1], self.m2f_config.cls_out, mask.device,
                                     "M2FNet.train_step")
         eng = self.engine(mask.device)
@@ -632,7 +705,7 @@ class M2FNet(nn.Module):
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
 
         def body():
-            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion)
+            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
             self._set_criterion(plan, teacher_logits, dist)
@@ -673,12 +746,13 @@ class M2FNet(nn.Module):
 
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,
-                  label_smoothing: float = 0.1, use_graph: bool = True) -> None:
+                  label_smoothing: float = 0.1, use_graph: bool = True, speakers: Optional[torch.Tensor] = None) -> None:
         """Loop body of the reference's ``validate`` / ``test`` (src/train.py:252-272, src/test.py:55-74) in one call: the forward of
         a no-grad ``forward`` (same plan: buckets, packed plans, long dialogues), then the batch's criterion loss, accuracy, weighted
         F1 and confusion matrix ADDED to ``scores`` (a ``metrics.DeviceScores``), all on the device.  Returns nothing and waits for
         nothing: ``scores.last()`` is a device view of the batch's three numbers, ``scores.result()`` / ``mean_loss()`` read the pass.
-        The plan's own token rows are scored - pad and filler rows carry label -1."""
+        The plan's own token rows are scored - pad and filler rows carry label -1.  speakers: as ``train_step``."""
+        ids = _check_speakers("M2FNet.eval_step", self._speaker_heads, speakers, mask.shape)
         if self.training and self.m2f_config.dropout > 0.0:
             raise RuntimeError("M2FNet.eval_step: the model is in training mode with dropout > 0; evaluation scores the model "
                                "without dropout - call model.eval() first")
@@ -690,7 +764,7 @@ class M2FNet(nn.Module):
         plan = eng.plan(B, L, False, False, valid)
 
         def body():
-            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion)
+            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
             plan.eval_step(scores.record, label_smoothing, class_weights is not None, use_graph)

@@ -27,7 +27,7 @@ F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
- BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN) = range(19)
+ BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS) = range(21)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -149,6 +149,24 @@ SIGNATURES = {
     "m2f_attention_stream_chunk_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                                 c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                                 c_void_p]),
+    "m2f_plan_attention_speakers": (c_int, [c_void_p, c_int, c_int]),
+    "m2f_plan_get_attention_speakers": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "m2f_plan_stream_speakers": (c_int, [c_void_p, c_void_p]),
+    "m2f_attention_fwd_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int, c_float,
+                                           c_void_p, c_int, c_int]),
+    "m2f_attention_varlen_fwd_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                  c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
+                                                  c_int, c_int, c_float, c_void_p, c_int, c_int]),
+    "m2f_attention_stream_speakers": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
+                                              c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_attention_stream_chunk_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                                    c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "m2f_stream_advance_speakers": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_stream_advance_speakers_n": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_attention_speaker_class": (c_int, [c_int, c_int, c_int]),
     "m2f_stream_workspace_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int]),
     "m2f_plan_create_stream": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_step": (c_int, [c_void_p, c_int, c_void_p]),
@@ -345,6 +363,54 @@ def position_bias(gain) -> float:
     return out
 
 
+def speaker_heads(setting, heads=None) -> Optional[Tuple[int, int]]:
+    """The speaker-head setting ``(n_same, n_other)`` as the kernels take it: None -> None (off); a pair of integers >= 0, at least one
+    of them positive -> the pair.  At a site with H heads, heads 0 .. n_same - 1 are SAME-speaker heads (query utterance i sees key j
+    only if their speakers are equal - the utterance itself always qualifies), heads n_same .. n_same + n_other - 1 OTHER-speaker
+    heads (only if they differ), the rest are untouched (`speaker_head_class`).  heads: optional ``{site name: H}`` - the sum must fit
+    every site, else ValueError naming the site.  Anything else raises ValueError."""
+    if setting is None:
+        return None
+    try:
+        a, b = setting
+    except (TypeError, ValueError):
+        raise ValueError(f"speaker heads: the setting must be None (off) or a pair (n_same, n_other), got {setting!r}") from None
+    for v in (a, b):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"speaker heads: n_same and n_other must be integers >= 0, got {setting!r}")
+    if a + b == 0:
+        raise ValueError("speaker heads: at least one of n_same and n_other must be positive (None switches the heads off)")
+    for name, H in (heads or {}).items():
+        if a + b > H:
+            raise ValueError(f"speaker heads: n_same + n_other = {a + b} exceeds the {H} heads of {name}")
+    return int(a), int(b)
+
+
+SPK_NONE, SPK_SAME, SPK_OTHER = 0, 1, 2
+
+
+def speaker_head_class(h: int, n_same: int, n_other: int) -> int:
+    """The class of head h under (n_same, n_other): SPK_SAME, SPK_OTHER or SPK_NONE, as the LIBRARY states it (csrc/ops.h,
+    m2f_attn_speaker_class - the one definition every kernel calls).  A host function: no GPU needed."""
+    return int(lib().m2f_attention_speaker_class(int(h), int(n_same), int(n_other)))
+
+
+def speaker_ids(speakers, who: str = "speakers") -> "torch.Tensor":
+    """One speaker id per utterance as the kernels read it: a uint8 tensor of the same shape.  uint8 / int32 / int64 tensors are
+    accepted; values are 0 .. 255 and only equality is used; a value outside that range raises ValueError (one host sync for the wider
+    types).  Values in pad slots are ignored by every kernel."""
+    if not isinstance(speakers, torch.Tensor) or speakers.dtype not in (torch.uint8, torch.int32, torch.int64):
+        raise ValueError(f"{who}: a uint8 / int32 / int64 tensor of speaker ids is required, got "
+                         f"{getattr(speakers, 'dtype', type(speakers).__name__)}")
+    if speakers.dtype == torch.uint8:
+        return speakers
+    if speakers.numel():
+        lo, hi = int(speakers.min()), int(speakers.max())
+        if lo < 0 or hi > 255:
+            raise ValueError(f"{who}: speaker ids must be 0 .. 255, got values in [{lo}, {hi}]")
+    return speakers.to(torch.uint8)
+
+
 def c_param_layout(c: M2FConfig) -> Tuple[list, list, int]:
     cc = config_to_c(c)
     n_max = 4096
@@ -419,6 +485,7 @@ class Plan:
         self.class_w = self._view(BUF_CLASSW, (16,), torch.float32)
         self._logits = self._view(BUF_LOGITS, (self.T, C) if self.packed else (B, L, C), torch.float32)
         self.cu_in = self._view(BUF_CU_SEQLENS, (B + 1,), torch.int32)
+        self.speakers_in = self._view(BUF_SPEAKERS, (self.T,), torch.uint8)      # speaker heads: one id per token row, in the rows' order
         self._dst = self._valid = None        # packed plans: token row of every (dialogue, slot) of the last batch; its validity
         self._spare = None                    # packed plans of B * L rows: device flag "row T-1 is not owned by the last batch"
         # input gradients (train plans; m2f_plan_backward_outputs): d loss / d text, d loss / d audio in the token rows of text_in / audio_in
@@ -529,8 +596,10 @@ class Plan:
         return self._pending is not None and self._pending() is not None
 
     def set_inputs(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], key_pad: torch.Tensor,
-                   labels: Optional[torch.Tensor] = None) -> None:
+                   labels: Optional[torch.Tensor] = None, speakers: Optional[torch.Tensor] = None) -> None:
         """Device-to-device copies of one batch into the plan's staging buffers (async on the stream).
+        speakers (uint8 [b, l], `speaker_ids`; a plan with speaker heads): one id per utterance - it travels as the mask does, through
+        bucket padding (filler slots: 0) and packing (token row cu[b] + rank, as every other row of the batch).
 
         The batch may be SMALLER than the plan (b <= B dialogues of l <= L utterances: the engine rounds shapes up to a few
         buckets so that the variable dialogue lengths of real data do not create a plan per length).  The extra slots are
@@ -544,7 +613,13 @@ class Plan:
             raise HipError(f"batch {b} x {l} does not fit the plan {self.B} x {self.L}")
         self.in_B, self.in_L = b, l
         if self.packed:
-            return self._set_inputs_packed(text, audio, key_pad.reshape(b, l), labels)
+            return self._set_inputs_packed(text, audio, key_pad.reshape(b, l), labels, speakers)
+        if speakers is not None:
+            if (b, l) == (self.B, self.L):
+                self.speakers_in.copy_(speakers.reshape(self.T), non_blocking=True)
+            else:
+                self.speakers_in.zero_()
+                self.speakers_in.view(self.B, self.L)[:b, :l].copy_(speakers.reshape(b, l), non_blocking=True)
         if (b, l) == (self.B, self.L):
             if text is not None and self.cfg.text_enabled:
                 self.text_in.copy_(text.reshape(self.T, -1), non_blocking=True)
@@ -570,7 +645,7 @@ class Plan:
         if labels is not None:
             self.labels_in.view(B, L)[:b, :l].copy_(labels, non_blocking=True)
 
-    def _set_inputs_packed(self, text, audio, key_pad, labels) -> None:
+    def _set_inputs_packed(self, text, audio, key_pad, labels, speakers=None) -> None:
         """Packs a padded batch: the valid slots of dialogue b (in order) become token rows cu[b] .. cu[b+1]-1, no sync with
         the host.  Filler dialogues of a bucketed plan get one zero, unlabeled row each; row T-1 absorbs the scatter of the
         pad slots and is zeroed afterwards (the engine sizes T for valid + fillers + 1 rows).  Rows past the last dialogue are
@@ -600,6 +675,10 @@ class Plan:
         if labels is not None:
             self.labels_in.index_copy_(0, flat, labels.reshape(-1).to(torch.int64))
             self._clear_spare(self.labels_in, -1)
+        if speakers is not None:                          # (the same row map; the spare row and the fillers' rows: 0)
+            self.speakers_in.zero_()
+            self.speakers_in.index_copy_(0, flat, speakers.reshape(-1))
+            self._clear_spare(self.speakers_in, 0)
 
     def _clear_spare(self, buf: torch.Tensor, value) -> None:
         """Row T-1 of a packed buffer := value, unless the batch owns it (see `_set_inputs_packed`)."""
@@ -744,6 +823,25 @@ class Plan:
         g = c_float(0.0)
         check(lib().m2f_plan_get_attention_bias(self._h(), ctypes.byref(g)), "m2f_plan_get_attention_bias")
         return float(g.value)
+
+    def attention_speakers(self, setting) -> Optional[Tuple[int, int]]:
+        """m2f_plan_attention_speakers: speaker heads of EVERY attention site of the plan (`speaker_heads` has the rule); None = off.
+        The ids are the `speakers` argument of `set_inputs`.  A change drops the captured graphs; between steps only."""
+        a, b = speaker_heads(setting) or (0, 0)
+        try:
+            check(lib().m2f_plan_attention_speakers(self._h(), a, b), "m2f_plan_attention_speakers")
+        except HipError as e:
+            if "exceeds the" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        return self.speakers
+
+    @property
+    def speakers(self) -> Optional[Tuple[int, int]]:
+        """(n_same, n_other) as the plan's launches apply them, or None."""
+        a, b = c_int(0), c_int(0)
+        check(lib().m2f_plan_get_attention_speakers(self._h(), ctypes.byref(a), ctypes.byref(b)), "m2f_plan_get_attention_speakers")
+        return (int(a.value), int(b.value)) if (a.value or b.value) else None
 
     def backward_outputs(self, input_mask: int, param_grads: bool) -> None:
         """m2f_plan_backward_outputs: what the NEXT backward computes - input gradients of the modalities in `input_mask` (IN_TEXT |
@@ -915,6 +1013,8 @@ class StreamPlan:
         self.len = self._view(BUF_STREAM_LEN, (S,), torch.int32)
         self.active = self._view(BUF_STREAM_ACTIVE, (S,), torch.uint8)
         self.table = None if pages is None else self._view(BUF_STREAM_TABLE, (S, (capacity + page_rows - 1) // page_rows), torch.int32)
+        self.speakers_in = self._view(BUF_SPEAKERS, (S,), torch.uint8)       # speaker heads: the new utterances' ids, one per slot
+        self.spk_cache = None                                                 # ... and the cached ones (`stream_speakers`)
 
     _h = Plan._h
     _view = Plan._view
@@ -966,6 +1066,25 @@ class StreamPlan:
     attention_sites = Plan.attention_sites
     attention_bias = Plan.attention_bias         # (before the first step or between steps; a chunk plan takes it when it is created)
     bias = Plan.bias
+    attention_speakers = Plan.attention_speakers     # (`stream_speakers` first)
+    speakers = Plan.speakers
+
+    def stream_speakers(self, on: bool) -> Optional[torch.Tensor]:
+        """m2f_plan_stream_speakers: the cached speaker ids of the stream, uint8 [S, capacity] by LOGICAL cache row (row u % capacity of a
+        ring; dense on a paged stream too) - made here (on) or dropped (off; refused while the plan has speaker heads).  The step
+        stores the new ids in the launch that advances the counters."""
+        if bool(on) == (self.spk_cache is not None):
+            return self.spk_cache
+        if not on:
+            check(lib().m2f_plan_stream_speakers(self._h(), None), "m2f_plan_stream_speakers")
+            self.spk_cache = None
+            return None
+        with torch.inference_mode(False):
+            buf = torch.zeros(self.S, self.capacity, dtype=torch.uint8, device=self.workspace.device)
+        torch.cuda.current_stream(buf.device).synchronize()
+        check(lib().m2f_plan_stream_speakers(self._h(), buf.data_ptr()), "m2f_plan_stream_speakers")
+        self.spk_cache = buf
+        return buf
 
     def stream_attention(self, on: bool) -> None:
         """m2f_plan_stream_attention: from the next step on the attention launches also store each (slot, head)'s row of probabilities
@@ -1012,6 +1131,7 @@ class StreamPlan:
         self.handle = None
         self.workspace = None
         self.attn_buf = None
+        self.spk_cache = None
 
     def __del__(self):
         self.close()
@@ -1051,12 +1171,25 @@ class StreamChunkPlan:
         self.new = self._view(BUF_STREAM_NEW, (S,), torch.int32)
         self.len = parent.len
         self.pages, self.page_rows, self.table = parent.pages, parent.page_rows, parent.table     # (a paged parent: its pools, its table)
+        self.speakers_in = self._view(BUF_SPEAKERS, (S, T), torch.uint8)     # speaker heads: the chunk's ids, row s = slot s
 
     _h = Plan._h
     _view = Plan._view
     params_fresh = StreamPlan.params_fresh
     attention_bias = Plan.attention_bias         # (created with the parent's gain; a change drops the captured prefill)
     bias = Plan.bias
+    attention_speakers = Plan.attention_speakers     # (created with the parent's setting and cached ids; `follow_speakers` after a change)
+    speakers = Plan.speakers
+
+    def follow_speakers(self) -> None:
+        """Take the parent's cached-speaker array and speaker-head setting (after they changed on the parent)."""
+        par = self.parent
+        if par.spk_cache is None or par.speakers is None:      # (off: the chunk plan lets go of the array before the parent drops it)
+            self.attention_speakers(None)
+            check(lib().m2f_plan_stream_speakers(self._h(), None), "m2f_plan_stream_speakers")
+        else:
+            check(lib().m2f_plan_stream_speakers(self._h(), par.spk_cache.data_ptr()), "m2f_plan_stream_speakers")
+            self.attention_speakers(par.speakers)
     nbytes = StreamPlan.nbytes
     close = StreamPlan.close
 

@@ -356,7 +356,8 @@ class StreamSnapshot:
     ``StreamSnapshot.from_state_dict(d)`` hold tensors, ints and lists only (``torch.save`` / ``torch.load``).
     A SNAPSHOT BELONGS TO THE WEIGHTS THAT WROTE IT, like the caches it came from."""
 
-    def __init__(self, data: torch.Tensor, lengths: Sequence[int], row_offsets: Sequence[int], signature: tuple, _ready=None):
+    def __init__(self, data: torch.Tensor, lengths: Sequence[int], row_offsets: Sequence[int], signature: tuple, _ready=None,
+                 speakers: Optional[torch.Tensor] = None):
         sites, bf16, past, ring = signature
         self.signature = make_signature(sites, bf16, past, 0 if ring is None else ring)
         self.lengths = [int(n) for n in lengths]
@@ -369,6 +370,18 @@ class StreamSnapshot:
             raise ValueError(f"StreamSnapshot: data must be a 1-D {want} tensor of {sum(rows) * self.row_elems} elements, "
                              f"got {data.dtype} {tuple(data.shape)}")
         self._data, self._ready = data, _ready
+        # speaker ids of the cached utterances (a stream of a model with speaker heads; None otherwise): uint8 [sum(rows)], entry e's
+        # rows at row_offsets[e] in the order of its packed rows - the slot's cache rows 0 .. rows_e - 1
+        if speakers is not None and (speakers.dim() != 1 or speakers.dtype != torch.uint8 or speakers.numel() != sum(rows)):
+            raise ValueError(f"StreamSnapshot: speakers must be a 1-D uint8 tensor of {sum(rows)} entries, got {speakers.dtype} {tuple(speakers.shape)}")
+        self._speakers = speakers
+
+    @property
+    def speakers(self) -> Optional[torch.Tensor]:
+        if self._speakers is not None and self._ready is not None:
+            self._ready.synchronize()
+            self._ready = None
+        return self._speakers
 
     @property
     def data(self) -> torch.Tensor:
@@ -416,10 +429,15 @@ class StreamSnapshot:
         W, rows, data = self.row_elems, self.rows, self.data
         parts = [data[self.row_offsets[i] * W: (self.row_offsets[i] + rows[i]) * W] for i in idx]
         picked = torch.cat(parts) if parts else data[:0]
-        return StreamSnapshot(picked, [self.lengths[i] for i in idx], snapshot_row_offsets([rows[i] for i in idx]), self.signature)
+        spk = self.speakers
+        if spk is not None:
+            sp = [spk[self.row_offsets[i]: self.row_offsets[i] + rows[i]] for i in idx]
+            spk = torch.cat(sp) if sp else spk[:0]
+        return StreamSnapshot(picked, [self.lengths[i] for i in idx], snapshot_row_offsets([rows[i] for i in idx]), self.signature, speakers=spk)
 
     def to(self, device) -> "StreamSnapshot":
-        return StreamSnapshot(self.data.to(device), self.lengths, self.row_offsets, self.signature)
+        spk = self.speakers
+        return StreamSnapshot(self.data.to(device), self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.to(device))
 
     def cpu(self, pin: bool = False) -> "StreamSnapshot":
         data = self.data
@@ -429,13 +447,17 @@ class StreamSnapshot:
             data = host
         else:
             data = data.cpu()
-        return StreamSnapshot(data, self.lengths, self.row_offsets, self.signature)
+        spk = self.speakers
+        return StreamSnapshot(data, self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.cpu())
 
     def state_dict(self) -> dict:
         sites, bf16, past, ring = self.signature
-        return {"data": self.data, "lengths": list(self.lengths), "row_offsets": list(self.row_offsets),
-                "sites": [[H, hd] for H, hd in sites], "bf16": int(bf16), "past": -1 if past is None else past,
-                "ring": -1 if ring is None else ring}
+        d = {"data": self.data, "lengths": list(self.lengths), "row_offsets": list(self.row_offsets),
+             "sites": [[H, hd] for H, hd in sites], "bf16": int(bf16), "past": -1 if past is None else past,
+             "ring": -1 if ring is None else ring}
+        if self._speakers is not None:                     # (only a snapshot WITH speakers extends the dictionary)
+            d["speakers"] = self.speakers
+        return d
 
     @classmethod
     def from_state_dict(cls, d: dict) -> "StreamSnapshot":
@@ -443,7 +465,8 @@ class StreamSnapshot:
         ring = None if int(d["ring"]) < 0 else int(d["ring"])
         if (past is None) != (ring is None):
             raise ValueError("StreamSnapshot.from_state_dict: a window and a ring capacity come together")
-        return cls(d["data"], d["lengths"], d["row_offsets"], (tuple((int(H), int(hd)) for H, hd in d["sites"]), bool(d["bf16"]), past, ring))
+        return cls(d["data"], d["lengths"], d["row_offsets"], (tuple((int(H), int(hd)) for H, hd in d["sites"]), bool(d["bf16"]), past, ring),
+                   speakers=d.get("speakers"))
 
 
 class DialogueStream:
@@ -499,6 +522,17 @@ class DialogueStream:
     stream adopts the model's gain (every dialogue starts over), or build a new stream.  The snapshot format and its signature do
     not carry the gain: A SNAPSHOT BELONGS TO THE WEIGHTS AND THE GAIN THAT WROTE IT, and neither is checked.
 
+    SPEAKER HEADS: a stream of a model with ``speaker_heads`` keeps, beside the K / V caches, ONE ``uint8 [S, capacity]`` array of the cached
+    utterances' speaker ids for all sites, indexed by logical cache row (row ``u % capacity`` of a ring; dense on a paged stream too:
+    1 B per row).  ``step(..., speakers=[S])``, ``prefill(..., speakers=[S, n])`` and ``run(..., speakers=[B, L])`` then REQUIRE the new
+    utterances' ids (``runtime.speaker_ids``; a stream without the setting refuses them).  The new ids are stored inside the step /
+    prefill graph by the launch that advances the counters, BEHIND the last attention launch: on a ring that store overwrites the id
+    of the utterance that has just left the window, and every attention launch of the step - none reads the row the new utterance
+    takes - has seen the old row set, the order the K / V rows have.  ``reset`` needs nothing new (stale ids are never read: the live
+    count rules).  Snapshots carry the ids (``StreamSnapshot.speakers``); a snapshot with ids into a stream without, or the reverse,
+    raises RuntimeError and leaves the stream untouched.  After ``model.set_speaker_heads`` to another setting the stream refuses to
+    run until ``reset()`` of the whole stream, as after ``set_position_bias``.
+
     ATTENTION ROWS (``attention=True``): every step's attention launches run the weights-emitting form of their kernel and keep, per
     site, slot and head, the new utterance's row of probabilities over the cached ones (``sum_sites H * S * capacity * 4 B``; the same
     logits bit for bit, the step still one replayed graph).  ``attention(average_heads=True, sites=None)`` after a ``step`` returns
@@ -522,6 +556,10 @@ class DialogueStream:
         self._bias: Optional[float] = model.position_bias     # (the applied gain or None; the chunk plan below takes the step plan's)
         if self._bias:
             self.plan.attention_bias(self._bias)
+        self._spk = model.speaker_heads                        # (the chunk plan below takes the step plan's setting and cached ids)
+        if self._spk:
+            self.plan.stream_speakers(True)
+            self.plan.attention_speakers(self._spk)
         self.allocator = PageAllocator(self.pages, self.max_streams, self.capacity, self.page_rows) if self.pages else None
         self.chunk_plan = runtime.StreamChunkPlan(self.plan, self.max_chunk, eng.flat, eng.wshadow) if self.max_chunk > 1 else None
         self.lengths: List[int] = [0] * self.max_streams
@@ -566,7 +604,34 @@ class DialogueStream:
         """The gain of the distance-decay attention bias this stream runs under (the applied value; None: off)."""
         return self._bias
 
+    @property
+    def speaker_heads(self):
+        """(n_same, n_other) this stream runs under, or None."""
+        return self._spk
+
+    @property
+    def speaker_cache(self) -> Optional[torch.Tensor]:
+        """The cached speaker ids, uint8 [S, capacity] by logical cache row (None: a stream without speaker heads)."""
+        return self.plan.spk_cache
+
+    def _speakers(self, what: str, speakers, shape) -> Optional[torch.Tensor]:
+        """The new utterances' ids as uint8 of `shape` ([rows] / [rows, n]; rows <= max_streams leading slots), or None without the setting."""
+        if self._spk is None:
+            if speakers is not None:
+                raise ValueError(f"stream.{what}: speakers were given, but this stream's model has no speaker heads; it would ignore them")
+            return None
+        if speakers is None:
+            raise ValueError(f"stream.{what}: this stream runs speaker_heads={self._spk}; pass speakers= (one id per new utterance)")
+        ids = runtime.speaker_ids(speakers, f"stream.{what}: speakers")
+        if tuple(ids.shape) != tuple(shape):
+            raise ValueError(f"stream.{what}: speakers must be {tuple(shape)}, got {tuple(ids.shape)}")
+        return ids
+
     def _refuse_bias(self, what: str) -> None:
+        if self.model.speaker_heads != self._spk:
+            raise RuntimeError(f"DialogueStream.{what}: the model's speaker heads are now {self.model.speaker_heads!r}, this stream's caches "
+                               f"were written under {self._spk!r}; reset() the whole stream (it then takes the model's setting) or "
+                               "build a new one with model.stream(...)")
         if self.model.position_bias != self._bias:
             raise RuntimeError(f"DialogueStream.{what}: the model's position bias is now {self.model.position_bias!r}, this stream's caches "
                                f"were written under {self._bias!r}; reset() the whole stream (it then takes the model's gain) or "
@@ -593,8 +658,8 @@ class DialogueStream:
             self.plan.table.copy_(al.table, non_blocking=True)
             al.dirty = False
 
-    def _step(self, text, audio, act: List[bool]) -> torch.Tensor:
-        """act: one entry per slot (rows of text / audio may be fewer: the leading slots)."""
+    def _step(self, text, audio, act: List[bool], ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """act: one entry per slot (rows of text / audio may be fewer: the leading slots).  ids: `_speakers` of the call."""
         self._refuse_training("step")
         self._refuse_bias("step")
         if self.past is None:
@@ -613,6 +678,8 @@ class DialogueStream:
                 if x is None:
                     raise ValueError(f"stream.step: {name} is enabled in this model and must be given")
                 buf[: x.shape[0]].copy_(x.detach().reshape(x.shape[0], -1), non_blocking=True)
+            if ids is not None:                            # the ids travel with the inputs
+                pl.speakers_in[: ids.shape[0]].copy_(ids, non_blocking=True)
             if act != self._active_host:                   # the mask travels with the inputs (only when it changes)
                 pl.active.copy_(torch.tensor(act, dtype=torch.uint8), non_blocking=True)
                 self._active_host = list(act)
@@ -633,14 +700,15 @@ class DialogueStream:
         return out
 
     # -- public surface ----------------------------------------------------------------------------------------------------------
-    def step(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], active: Optional[Sequence[bool]] = None) -> torch.Tensor:
+    def step(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], active: Optional[Sequence[bool]] = None,
+             speakers: Optional[torch.Tensor] = None) -> torch.Tensor:
         S = self.max_streams
         for x, name in ((text, "text"), (audio, "audio")):
             if x is not None and (x.dim() != 2 or x.shape[0] != S):
                 raise ValueError(f"stream.step: {name} must be [max_streams = {S}, d], got {tuple(x.shape)}")
-        return self._step(text, audio, self._mask(active, S))
+        return self._step(text, audio, self._mask(active, S), self._speakers("step", speakers, (S,)))
 
-    def _chunk(self, text, audio, new: List[int], first: int) -> torch.Tensor:
+    def _chunk(self, text, audio, new: List[int], first: int, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One chunk call: slot s takes rows first .. first + new[s] - 1 of text / audio ([B, n, d], B <= S leading slots).  Returns the
         chunk plan's logits [S, T, C_out] as a fresh tensor, zeros at the rows past new[s]."""
         pl, cfg, eng, T = self.chunk_plan, self.chunk_plan.cfg, self._eng, self.max_chunk
@@ -661,6 +729,8 @@ class DialogueStream:
                 xs = x[:, first: first + width].detach().to(buf.device, non_blocking=True)
                 rows = torch.arange(width, device=buf.device)[None, :] < pl.new[:B, None]
                 buf[:B, :width].copy_(torch.where(rows[:, :, None], xs, torch.zeros((), dtype=xs.dtype, device=buf.device)), non_blocking=True)
+            if ids is not None:                             # ([B, n] ids: the chunk's columns; rows past a count are never read)
+                pl.speakers_in[: ids.shape[0], :width].copy_(ids[:, first: first + width], non_blocking=True)
             fresh = eng.shadows_fresh()
             pl.params_fresh(fresh)
             pl.prefill(self.use_graph)
@@ -675,7 +745,8 @@ class DialogueStream:
         self._attn_act = None
         return out
 
-    def prefill(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+    def prefill(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], counts: Optional[Sequence[int]] = None,
+                speakers: Optional[torch.Tensor] = None) -> torch.Tensor:
         S = self.max_streams
         self._refuse_training("prefill")
         self._refuse_bias("prefill")
@@ -700,10 +771,11 @@ class DialogueStream:
             if len(counts) != S or any(not 0 <= c <= n for c in counts):
                 raise ValueError(f"stream.prefill: `counts` needs {S} entries in 0 .. {n}, got {counts}")
         check_prefill_fits(self.lengths, counts, self.capacity, self.past)
+        ids = self._speakers("prefill", speakers, (S, n))
         self._reserve(counts, "prefill")                   # (the whole call's pages, before its first launch)
-        return self._feed(text, audio, counts, n)
+        return self._feed(text, audio, counts, n, ids)
 
-    def _feed(self, text, audio, counts: List[int], n: int) -> torch.Tensor:
+    def _feed(self, text, audio, counts: List[int], n: int, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """counts: one entry per slot; text / audio [B, n, d] hold the leading B slots.  Returns logits [S, n, C_out]."""
         S, T = self.max_streams, self.max_chunk
         cfg = self.plan.cfg
@@ -714,12 +786,13 @@ class DialogueStream:
         if T == 1:
             for i in range(max(counts, default=0)):
                 act = [c > i for c in counts]
-                out[:, i] = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
+                out[:, i] = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act,
+                                       None if ids is None else ids[:, i].contiguous())
             self._attn_act = None                           # (a history, however it was loaded: `attention` answers for a `step`)
             return out
         for i, new in enumerate(chunk_schedule(counts, T)):
             w = max(new)
-            out[:, i * T: i * T + w] = self._chunk(text, audio, new, i * T)[:, :w]
+            out[:, i * T: i * T + w] = self._chunk(text, audio, new, i * T, ids)[:, :w]
         return out
 
     def reset(self, slots: Optional[Sequence[int]] = None) -> None:
@@ -731,6 +804,17 @@ class DialogueStream:
                 for pl in (self.plan, self.chunk_plan):
                     if pl is not None:
                         pl.attention_bias(self._bias)
+            if self.model.speaker_heads != self._spk:      # (likewise: the stream follows the model's speaker heads)
+                self._spk = self.model.speaker_heads
+                if self._spk:
+                    self.plan.stream_speakers(True)
+                    self.plan.attention_speakers(self._spk)
+                else:
+                    self.plan.attention_speakers(None)
+                if self.chunk_plan is not None:
+                    self.chunk_plan.follow_speakers()
+                if not self._spk:
+                    self.plan.stream_speakers(False)
             self._on_stream(lambda: self.plan.reset(None))
             self.lengths = [0] * S
             if self.allocator is not None:
@@ -753,7 +837,8 @@ class DialogueStream:
         if self.allocator is not None:
             self.allocator.release(set(slots))
 
-    def run(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], mask: torch.Tensor) -> torch.Tensor:
+    def run(self, text: Optional[torch.Tensor], audio: Optional[torch.Tensor], mask: torch.Tensor,
+            speakers: Optional[torch.Tensor] = None) -> torch.Tensor:
         """A padded batch (text [B, L, d_t], audio [B, L, d_a], mask bool [B, L], True = pad; B <= max_streams) through the stream:
         resets the first B slots and feeds the batch column by column with ``active = ~mask[:, i]`` - or, on a stream with
         ``max_chunk = T > 1`` and a batch in the collate layout (every row a valid prefix followed by padding), T columns per call.
@@ -764,6 +849,7 @@ class DialogueStream:
         if B > S:
             raise ValueError(f"stream.run: {B} dialogues do not fit {S} stream slots")
         self._refuse_bias("run")
+        ids = self._speakers("run", speakers, (B, L))
         self.reset(range(B))
         valid = (~mask.bool()).cpu()
         counts = prefix_counts(valid) if self.max_chunk > 1 else None
@@ -772,7 +858,7 @@ class DialogueStream:
             counts = counts + [0] * (S - B)
             check_prefill_fits(self.lengths, counts, self.capacity, self.past)
             self._reserve(counts, "run")
-            return self._feed(text, audio, counts, L)[:B]
+            return self._feed(text, audio, counts, L, ids)[:B]
         if self.allocator is not None:                      # (the whole batch's pages, before its first step)
             rows = valid.sum(1).tolist() + [0] * (S - B)
             if self.past is None:
@@ -783,7 +869,8 @@ class DialogueStream:
             act = valid[:, i].tolist() + [False] * (S - B)
             if not any(act):
                 continue
-            logits = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act)
+            logits = self._step(None if text is None else text[:, i], None if audio is None else audio[:, i], act,
+                                None if ids is None else ids[:, i].contiguous())
             out[:, i] = logits[:B]
         self._attn_act = None                               # (a whole batch, by steps or by chunks: `attention` answers for a `step`)
         return out
@@ -818,24 +905,36 @@ class DialogueStream:
         data = torch.empty(sum(rows) * snapshot_row_elems(sig[0], sig[1]), dtype=torch.bfloat16 if sig[1] else torch.float32, device=dev)
         host = torch.empty(data.shape, dtype=data.dtype, pin_memory=True) if pinned else None
         ready = None
+        spk_c, spk = self.plan.spk_cache, None              # speaker heads: the ids of the same rows (plain indexing: tiny and not hot)
+        spk_host = torch.empty(sum(rows), dtype=torch.uint8, pin_memory=True) if (pinned and spk_c is not None) else None
 
         def body():
             nonlocal ready
             self._send_table()                              # (every path that changes the table sends it; a gather must never depend on that)
+            nonlocal spk
             if data.numel():
                 self.plan.gather(*self._entries(slots, lengths, offsets), data)
+            if spk_c is not None:
+                parts = [spk_c[s, :r] for s, r in zip(slots, rows)]
+                spk = torch.cat(parts) if parts else spk_c.new_zeros(0)
+                if spk_host is not None:
+                    spk_host.copy_(spk, non_blocking=True)
             if host is not None:
                 host.copy_(data, non_blocking=True)
                 ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(dev))
         self._on_stream(body)
-        return StreamSnapshot(data if host is None else host, lengths, offsets, sig, _ready=ready)
+        return StreamSnapshot(data if host is None else host, lengths, offsets, sig, _ready=ready,
+                              speakers=spk if spk_host is None else spk_host)
 
     def snapshot(self, slots: Optional[Sequence[int]] = None) -> StreamSnapshot:
         return self._snapshot(slots, pinned=False)
 
     def restore(self, snap: StreamSnapshot, slots: Optional[Sequence[int]] = None) -> None:
         self._refuse_bias("restore")
+        if (snap.speakers is None) != (self._spk is None):  # (before anything is released or launched: the stream stays as it is)
+            raise RuntimeError("stream.restore: the snapshot " + ("carries no speaker ids" if snap.speakers is None else "carries speaker ids") +
+                               ", this stream runs " + ("without speaker heads" if self._spk is None else f"speaker_heads={self._spk}"))
         if snap.signature != self.signature:
             raise ValueError(f"stream.restore: the snapshot was written under (sites (H, hd), bf16, past, ring capacity) = {snap.signature}, "
                              f"this stream runs {self.signature}")
@@ -844,6 +943,9 @@ class DialogueStream:
         data = snap.data
         if data.device != self._eng.device:
             raise ValueError(f"stream.restore: the snapshot lives on {data.device}, the stream on {self._eng.device}; snap.to(device) first")
+        spk = snap.speakers
+        if spk is not None and spk.device != self._eng.device:
+            raise ValueError(f"stream.restore: the snapshot's speakers live on {spk.device}, the stream on {self._eng.device}; snap.to(device) first")
         rows = snap.rows
         if not slots:
             return
@@ -856,6 +958,10 @@ class DialogueStream:
         def body():
             self._send_table()                              # the table goes first: the scatter writes through it
             self.plan.scatter(*self._entries(slots, snap.lengths, snap.row_offsets), src)
+            if spk is not None:
+                for s_, o_, r_ in zip(slots, snap.row_offsets, rows):
+                    if r_:
+                        self.plan.spk_cache[s_, :r_].copy_(spk[o_: o_ + r_], non_blocking=True)
         try:
             self._on_stream(body)
         except Exception:                                   # a launch that was refused: the host keeps describing the device -

@@ -65,10 +65,27 @@ def load_waveforms(table, wav_dir, max_seconds=WAV_MAX_SECONDS):
             for d, u in zip(table["Dialogue_ID"].tolist(), table["Utterance_ID"].tolist())]
 
 
+def dialogue_speaker_ids(speakers, rows):
+    """Per-dialogue speaker ids: the `Speaker` column's values of every table row -> int64 [N], the speakers of a dialogue numbered
+    0, 1, 2, ... in order of first appearance inside it (`rows`: the dialogues' row indices in utterance order, `build_dialogue_index`).
+    Only equality inside a dialogue matters to the model; more than 256 speakers in one dialogue are refused (ids are one byte)."""
+    speakers = list(speakers)
+    out = np.zeros(len(speakers), dtype=np.int64)
+    for d, idx in enumerate(rows):
+        seen = {}
+        for r in np.asarray(idx).tolist():
+            out[r] = seen.setdefault(speakers[r], len(seen))
+        if len(seen) > 256:
+            raise ValueError(f"dialogue {d} has {len(seen)} speakers; speaker ids are one byte (at most 256 per dialogue)")
+    return torch.as_tensor(out)
+
+
 class Dataset(torch.utils.data.Dataset):
     def __init__(self, mode="train", text_embeddings=None, audio_embeddings=None, table=None, token_ids=None, token_mask=None,
-                 waveforms=None):
-        """token_ids / token_mask ([N, S] int64, rows = table rows; `tokenised_contexts`): items and batches ALSO carry "text_ids" /
+                 waveforms=None, speakers=False):
+        """speakers (runtime.speaker_heads is set): items ALSO carry "speaker" - int64 [n], `dialogue_speaker_ids` of the table's
+        `Speaker` column - and batches "speaker" int64 [B, L], padded with 0 (M2FNet(speaker_heads=...) reads them; pad slots are ignored).
+        token_ids / token_mask ([N, S] int64, rows = table rows; `tokenised_contexts`): items and batches ALSO carry "text_ids" /
         "text_mask" - what the in-loop text encoder consumes instead of the pre-extracted "text" rows (`runtime.text_encoder`).
         waveforms (a list of 1-D float tensors, rows = table rows; `load_waveforms`): items carry "wave" and batches "waveforms" /
         "wave_lengths" / "wave_index" - what the in-loop audio encoder consumes (`runtime.audio_encoder`); the audio pickle is then
@@ -93,6 +110,11 @@ class Dataset(torch.utils.data.Dataset):
         self.dialogue_ids, self.rows = build_dialogue_index(self.text["Dialogue_ID"].to_numpy(),
                                                             self.text["Utterance_ID"].to_numpy())
         self._labels = torch.as_tensor(self.text["Emotion"].to_numpy().astype(np.int64))
+        self._speakers = None
+        if speakers:
+            if "Speaker" not in self.text:
+                raise ValueError(f"runtime.speaker_heads needs the Speaker column of the {mode} table")
+            self._speakers = dialogue_speaker_ids(self.text["Speaker"].tolist(), self.rows)
         print(f"Loaded {len(self.dialogue_ids)} dialogues for {self.mode}ing")
 
     def __len__(self):
@@ -105,6 +127,8 @@ class Dataset(torch.utils.data.Dataset):
             item["audio"] = self.audio_embeddings[rows]
         if self.waveforms is not None:
             item["wave"] = [self.waveforms[r] for r in rows.tolist()]
+        if self._speakers is not None:
+            item["speaker"] = self._speakers[rows]
         if self.token_ids is not None:
             item["text_ids"] = self.token_ids[rows]
             item["text_mask"] = self.token_mask[rows] if self.token_mask is not None else torch.ones_like(item["text_ids"])
@@ -131,6 +155,11 @@ def collate_fn(batch):
     if has_audio:
         out["audio"] = audio
     out["padding_mask"], out["emotion"] = emotion == -1, emotion
+    if "speaker" in batch[0]:                                      # speaker heads: per-dialogue ids, 0 on pads (ignored there)
+        speaker = torch.zeros(B, L, dtype=torch.int64)
+        for i, d in enumerate(batch):
+            speaker[i, : d["speaker"].shape[0]] = d["speaker"]
+        out["speaker"] = speaker
     if "wave" in batch[0]:
         # in-loop audio encoder: the waveforms of all utterances of the batch, zero-padded to the longest ([n, N] fp32), their sample
         # counts, and where each goes in the [B, L] grid (flat index b * L + t)

@@ -151,6 +151,11 @@ def _stream_for(model, B, L):
     return st
 
 
+def _speaker_kw(model, batch, device):
+    from train import _speaker_kw as kw
+    return kw(model, batch, device)
+
+
 def test(model, dl_test, device):
     """-> (accuracy, weighted_f1) over the loader, per-batch scores averaged unweighted.
     With ``model.streaming`` (runtime.streaming) every batch goes through ``DialogueStream.run`` - column by column, one new utterance per
@@ -168,7 +173,7 @@ def test(model, dl_test, device):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
                 stream = _stream_for(model, *padding_mask.shape)
-                scores.update(stream.run(text, audio, padding_mask), emotion)
+                scores.update(stream.run(text, audio, padding_mask, **_speaker_kw(model, batch, device)), emotion)
         return scores.result()
     if getattr(model, "device_metrics", False):
         from mer_amd.metrics import DeviceScores
@@ -177,7 +182,7 @@ def test(model, dl_test, device):
             for batch in tqdm(dl_test, total=len(dl_test)):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
-                model.eval_step(text, audio, padding_mask, emotion, scores)
+                model.eval_step(text, audio, padding_mask, emotion, scores, **_speaker_kw(model, batch, device))
                 maps.add(padding_mask)
         model.test_scores = scores
         maps.write()
@@ -187,7 +192,7 @@ def test(model, dl_test, device):
         for batch in tqdm(dl_test, total=len(dl_test)):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
-            scores.update(model(text, audio, padding_mask), emotion)
+            scores.update(model(text, audio, padding_mask, **_speaker_kw(model, batch, device)), emotion)
             maps.add(padding_mask)
     maps.write()
     return scores.result()
@@ -201,17 +206,18 @@ def print_class_report(report):
 
 
 def build_model(config, device):
-    """The model as train.py built it (train.build_model): runtime.precision, runtime.context and runtime.position_bias, so a model
-    trained under a context band or a position bias is tested under it."""
+    """The model as train.py built it (train.build_model): runtime.precision, runtime.context, runtime.position_bias and
+    runtime.speaker_heads, so a model trained under a context band, a position bias or speaker heads is tested under it."""
     from train import build_model as build
     return build(config, device)
 
 
 def main(config=None):
     config = get_config()
-    from train import context_settings, position_bias_settings
+    from train import context_settings, position_bias_settings, speaker_heads_settings
     context_settings(config)                               # (refusal before the GPU is touched)
     position_bias_settings(config)
+    spk_on = speaker_heads_settings(config) is not None    # (the test table then yields "speaker" ids)
     streaming = streaming_settings(config)
     stream_chunk = stream_chunk_settings(config)
     stream_pages = stream_pages_settings(config)
@@ -222,7 +228,8 @@ def main(config=None):
     if runtime_cfg.get("device_batcher", False):
         loader = DeviceLoader(Dataset(mode="test"), device=device, **config.test.data_loader)
     else:
-        loader = torch.utils.data.DataLoader(Dataset(mode="test"), collate_fn=collate_fn, **config.test.data_loader)
+        loader = torch.utils.data.DataLoader(Dataset(mode="test", **({"speakers": True} if spk_on else {})), collate_fn=collate_fn,
+                                             **config.test.data_loader)
     model = build_model(config, device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     model.streaming = streaming

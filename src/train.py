@@ -245,12 +245,51 @@ def position_bias_settings(cfg):
     return _position_bias_value(_runtime(cfg, "position_bias", None), "runtime.position_bias")
 
 
+def speaker_heads_settings(cfg, world: int = 1):
+    """`runtime.speaker_heads` = {same, other}: speaker-aware heads of every attention site of the model (M2FNet(speaker_heads=(same,
+    other)): the first `same` heads of a site see the utterances of the query's own speaker only, the next `other` heads those of the
+    other speakers only).  -> None when the key is absent or null (the loop then behaves as it does without it), else (same, other).
+    Checked on the host before the GPU is touched: integers >= 0, at least one positive (whether they fit the heads is the model's
+    check); needs runtime.device_batcher: False (the device batcher gathers no speaker ids) and a single rank (the data-parallel
+    step refuses a model with speaker heads)."""
+    from mer_amd.runtime import speaker_heads
+    block = _runtime(cfg, "speaker_heads", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.speaker_heads must be a mapping {{same, other}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - {"same", "other"})
+    if unknown:
+        raise ValueError(f"runtime.speaker_heads: unknown key(s) {unknown} (same, other)")
+    try:
+        heads = speaker_heads((block.get("same", 0), block.get("other", 0)))
+    except ValueError as e:
+        raise ValueError(f"runtime.speaker_heads: {e}") from None
+    if _runtime(cfg, "device_batcher", False):
+        raise ValueError("runtime.speaker_heads needs runtime.device_batcher: False (the device batcher gathers no speaker ids)")
+    if world > 1:
+        raise ValueError("runtime.speaker_heads does not combine with data-parallel training (DataParallelStep refuses a model with "
+                         "speaker heads): launch a single process")
+    return heads
+
+
+def _speaker_kw(model, batch, device):
+    """{speakers} of this batch when the model has speaker heads (runtime.speaker_heads), else nothing - the loop as it was."""
+    if getattr(model, "speaker_heads", None) is None:
+        return {}
+    if "speaker" not in batch:
+        raise ValueError("the model has speaker heads but the batch carries no \"speaker\" ids (Dataset(speakers=True))")
+    from mer_amd.runtime import speaker_ids
+    # range-checked and narrowed to one byte on the HOST, where the collated ids are: nothing waits for the device in front of the step
+    return {"speakers": speaker_ids(batch["speaker"], "batch[\"speaker\"]").to(device, non_blocking=True)}
+
+
 def build_model(config, device):
-    """The M2FNet of `config` on `device` as train.py and test.py both build it: runtime.precision, runtime.context and
-    runtime.position_bias - so a model trained under a context band or a position bias is validated and tested, streamed or not, under
-    the same."""
+    """The M2FNet of `config` on `device` as train.py and test.py both build it: runtime.precision, runtime.context,
+    runtime.position_bias and runtime.speaker_heads - so a model trained under a context band, a position bias or speaker heads is
+    validated and tested, streamed or not, under the same."""
     return M2FNet(config.model, precision=_runtime(config, "precision", "fp32"), context=context_settings(config),
-                  position_bias=position_bias_settings(config)).to(device)
+                  position_bias=position_bias_settings(config), speaker_heads=speaker_heads_settings(config)).to(device)
 
 
 def watch_settings(cfg, world: int = 1):
@@ -541,6 +580,7 @@ def main(config=None):
     ema_settings(config)
     context_settings(config)
     position_bias_settings(config)
+    spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
     resolve_distill(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
@@ -558,6 +598,9 @@ def main(config=None):
     ae_cfg = _runtime(config, "audio_encoder", None) or {}
     ae_on = bool(ae_cfg.get("enabled", False))
     ds_kw = {"train": {}, "val": {}}
+    if spk_on:
+        for mode in ds_kw:
+            ds_kw[mode]["speakers"] = True                 # (batches then carry "speaker")
     if ae_on:
         # waveforms of every table row, read once (dia{D}_utt{U}.wav); the audio pickle is not read
         if not ae_cfg.get("wav_dir", None):
@@ -568,7 +611,7 @@ def main(config=None):
         from utils import get_text
         for mode in ds_kw:
             table = get_text(mode)
-            ds_kw[mode] = {"table": table, "waveforms": load_waveforms(table, os.path.abspath(ae_cfg["wav_dir"]))}
+            ds_kw[mode] = dict(ds_kw[mode], table=table, waveforms=load_waveforms(table, os.path.abspath(ae_cfg["wav_dir"])))
     te_on = bool((_runtime(config, "text_encoder", None) or {}).get("enabled", False))
     if te_on:
         # the tokenizer is the caller's: a LOCAL directory with the files of the reference's RobertaTokenizer (text/dataset.py:9,42 fetch
@@ -775,7 +818,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                         class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer,
-                                        **_distill_kw(model, text, audio, padding_mask))
+                                        **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device))
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
@@ -783,11 +826,12 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                        class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask))
+                                        class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
+                                        **_speaker_kw(model, batch, device))
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
-                loss = criterion(model(text, audio, padding_mask).permute(0, 2, 1), emotion)
+                loss = criterion(model(text, audio, padding_mask, **_speaker_kw(model, batch, device)).permute(0, 2, 1), emotion)
                 loss.backward()
             optimizer.step()
         running += loss.item()
@@ -824,7 +868,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             else:
                 model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                  class_weights=criterion.weight, normalise=False, use_graph=use_graph,
-                                 **_distill_kw(model, text, audio, padding_mask))
+                                 **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device))
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
@@ -873,7 +917,7 @@ def validate(model, dl_val, criterion, device):
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
-            logits = model(text, audio, padding_mask)
+            logits = model(text, audio, padding_mask, **_speaker_kw(model, batch, device))
             loss_total += criterion(logits.permute(0, 2, 1), emotion).item()
             scores.update(logits, emotion)
     acc_sum, f1_sum = scores.sums()
@@ -893,7 +937,7 @@ def _validate_on_device(model, dl_val, criterion, device, rank, world):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             model.eval_step(text, audio, padding_mask, emotion, scores, class_weights=criterion.weight,
-                            label_smoothing=criterion.label_smoothing, use_graph=use_graph)
+                            label_smoothing=criterion.label_smoothing, use_graph=use_graph, **_speaker_kw(model, batch, device))
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks(list(scores.totals()), device=device)      # (the one read of the pass)
     n = max(n, 1.0)
     return loss_total / n, acc_sum / n, f1_sum / n
