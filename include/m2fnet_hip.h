@@ -140,7 +140,7 @@ int m2f_backward(m2f_plan* plan, m2f_stream_t stream);
 int m2f_plan_backward_outputs(m2f_plan* plan, int input_mask, int param_grads);
 /* Context band of EVERY attention site of the plan - both modality encoders and every fusion layer, forward and backward (one
  * unmasked site would leak the future): utterance i attends to utterances i - past .. i + future of its dialogue, each side >= 0
- * or negative = unlimited (m2f_attention_fwd_band below has the rule and the rows that see no key).  (-1, 0): causal, the online
+ * or negative = unlimited (m2f_attn_opts below has the rule and the rows that see no key).  (-1, 0): causal, the online
  * setting of emotion recognition in conversation; (-1, -1), the default: the reference's offline attention, bit for bit what the plan
  * computed before this entry existed.  No counterpart in the reference (its modules take no attn_mask).  Pad slots under a band
  * are not the reference's numbers (as the pad slots of packed plans).  A change destroys the captured graphs; call it between
@@ -149,7 +149,7 @@ int m2f_plan_attention_band(m2f_plan* plan, int past, int future);
 int m2f_plan_get_attention_band(m2f_plan* plan, int* past, int* future);
 /* Distance-decay bias (ALiBi) of EVERY attention site of the plan: a visible key's score becomes
  * fma(-slope(h, H, gain), float(|i - j|), dot(q_i, k_j) / sqrt(hd)) in fp32, i and j the positions the band compares and slope the
- * fixed geometric recipe of m2f_attention_fwd_bias below.  gain >= 0 and finite; 1.0 is ALiBi, 0 (the default) is off and runs the
+ * fixed geometric recipe of m2f_attn_opts::bias_gain below.  gain >= 0 and finite; 1.0 is ALiBi, 0 (the default) is off and runs the
  * kernels the plan ran before this entry existed.  The APPLIED gain is the requested one rounded to bf16 (the launch descriptor holds
  * 16 bits of it); m2f_plan_get_attention_bias reports the applied value.  No parameters, no change to the saved probabilities' layout:
  * the backward kernels read the probabilities and ignore the setting.  Works on train, eval, packed, stream and chunk plans; on a
@@ -678,18 +678,73 @@ int m2f_plan_distill(m2f_plan* plan, int on);
 int m2f_gemm_p8(int rc, int M, int N, int K, const uint16_t* a, int lda, const uint16_t* b, int ldb, float* c, int ldc,
                 const float* bias, const float* res, int ldres, int act, int relu_a, int relu_b, float* bias_grad,
                 void* scratch, int64_t scratch_bytes, int n_wg, m2f_stream_t stream);
+/* ---- dialogue attention: six launch entries, their options in two descriptors ----------------------------------------------------
+ * One entry per launch kind - m2f_attention_fwd / _bwd (L <= 64), m2f_attention_varlen_fwd / _bwd (L <= 512), m2f_attention_stream
+ * (one new utterance per slot) and m2f_attention_stream_chunk (up to T) - and every option of a forward launch is a FIELD of the
+ * descriptor its last argument points to.  opts == NULL is the plain launch; a field at its "off" value runs the kernels of the launch
+ * without it, bit for bit.  A new option is one more field (and one more template flag of the kernels), never one more entry.
+ * Refused before any launch, with a message that names the entry: a gain that is negative, not finite or out of bf16's range;
+ * negative head counts, n_same + n_other > H, a NULL speakers / spk_cache / spk_new with a non-zero count; paging arguments as below;
+ * a misaligned weights buffer, and any weights buffer at the chunk entry.
+ *
+ * past / future - CONTEXT BAND (attn_mask of a band shape): >= 0, or negative = unlimited on that side.  Query i sees key j iff j is a
+ *   valid key and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue (padded rows: the slot;
+ *   packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this one", (-1, -1) no band.  A
+ *   hidden key has P = 0 exactly.  A query that sees NO key (a pad slot whose band holds pad keys only; a valid query always sees
+ *   itself) gets a zero row of P, a zero output row and zero gradient terms, where torch's masked softmax gives NaN: such rows are pad
+ *   rows of saved activations, and the weight gradients sum over every row.  The long-dialogue kernels (varlen) skip every pair of
+ *   64-row blocks the band hides as a whole and leave its block of `probs` unwritten; the backward entries take the band as two plain
+ *   arguments and must be given the band of the forward whose probabilities they read (the short backward does not read it: the saved
+ *   P^T carries the band).  A ZERO-FILLED m2f_attn_opts is therefore a band of width zero, not "no option": start from
+ *   M2F_ATTN_OPTS_NONE.
+ * bias_gain - DISTANCE-DECAY BIAS (ALiBi): a VISIBLE key's score is fma(-slope, float(|i - j|), dot(q_i, k_j) * (1 / sqrt(hd))), all
+ *   fp32 (in bf16 mode too: behind the contraction), i and j the positions the band compares; a hidden key stays -inf.  slope = gain *
+ *   base(h, H), h the 0-based head: with n = 2^floor(log2 H), base = 2^(-8 (h + 1) / n) for h < n and 2^(-4 (2 (h - n) + 1) / n) for
+ *   h >= n (H = 4: 1/4, 1/16, 1/64, 1/256; H = 3: 1/16, 1/256, 1/4).  gain >= 0 and finite, used as rounded to bf16 (what a plan
+ *   applies); 0 = off.  The new utterance of a stream is at distance 0, cached utterance u at distance count - u.  The backward entries
+ *   read the probabilities the biased forward saved and take no gain.
+ * n_same / n_other - SPEAKER HEADS (m2f_plan_attention_speakers has the rule): heads 0 .. n_same - 1 see the keys of the query's own
+ *   speaker only, the next n_other heads the keys of the other speakers only; (0, 0) = off.  speakers: device uint8, one id per token row
+ *   (padded: [B*L]; packed: [T], row cu[b] + i).  Stream entries: spk_cache = device uint8 [S][C], the ids of the cached utterances by
+ *   logical cache row (read only; the row the new utterance takes is never read), spk_new = device uint8 [S] (step) / [S][T] (chunk),
+ *   the new utterances' ids.  An other-speaker head with no other speaker in sight gives a zero output row and a zero weights row.
+ * table, table_cols, n_pages, page_rows - PAGED caches (layout: m2f_plan_create_stream_paged): table == NULL = dense caches, the three
+ *   integers ignored; otherwise kcache / vcache are the POOLS [n_pages][H][page_rows][pad(hd)], m2f_attention_stream_pool_elems elements
+ *   each, 16-byte aligned, and table is device int32 [S, table_cols], table_cols = ceil(C / page_rows).  Same results, bit for bit, as
+ *   the dense launch on caches that hold the same rows.  Refused: page_rows outside {16, 32, 64}, misaligned pools, table_cols !=
+ *   ceil(C / page_rows), n_pages < 1, C > 512, hd > 128.
+ * weights - step entry only: the launch also stores each (slot, head)'s row of attention probabilities, fp32 [S, H, C], in LOGICAL
+ *   order - column t is the t-th oldest live utterance of the slot, the last live column the utterance that has just arrived (a ring:
+ *   utterance u sits in row u % C, undone here; paged: the page table never enters) - zeros behind the live count min(count + 1, C) and
+ *   for inactive slots.  Same out, same cache rows, same bits.  NULL = off; the chunk entry has no such kernel and refuses a buffer. */
+typedef struct m2f_attn_opts {          /* forward of the short and long-dialogue kernels */
+    int past, future;                   /* context band, negative = unlimited on that side */
+    float bias_gain;                    /* distance-decay gain, 0 = off (applied as rounded to bf16) */
+    int n_same, n_other;                /* speaker heads, (0, 0) = off */
+    const uint8_t* speakers;            /* one id per token row; needed iff n_same | n_other */
+} m2f_attn_opts;
+#define M2F_ATTN_OPTS_NONE {-1, -1, 0.f, 0, 0, NULL}        /* "no option": what opts == NULL means */
+typedef struct m2f_attn_stream_opts {   /* stream step and chunk; zero-filled = no option */
+    const int32_t* table; int table_cols, n_pages, page_rows;   /* table NULL = dense caches, else kcache / vcache are the pools */
+    float* weights;                     /* step only: [S, H, C] rows of probabilities, NULL = off */
+    float bias_gain;
+    int n_same, n_other; const uint8_t* spk_cache; const uint8_t* spk_new;
+} m2f_attn_stream_opts;
+/* sizeof and the field offsets, in declaration order, of m2f_attn_opts - which = 0 - or m2f_attn_stream_opts - which = 1 - as this library
+ * was compiled: up to max ints into out; returns how many there are, < 0 for another `which`.  Host only (bindings check their mirror). */
+int m2f_attention_opts_layout(int which, int* out, int max);
 /* softmax(q k^T / sqrt(hd) + key_padding_mask) v per (dialogue, head) (nn.MultiheadAttention inside
  * src/model.py:8,14,61,73); probs receives P^T per head, padded to Lp = 16*ceil(L/16). */
 int m2f_attention_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
                       const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs,
-                      uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream);
+                      uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, const m2f_attn_opts* opts);
 int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
                       const float* v, int ldv, const uint8_t* key_pad, const float* out, int ldo,
                       const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk,
                       int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
-                      const uint32_t* rng_state, m2f_stream_t stream);
+                      const uint32_t* rng_state, m2f_stream_t stream, int past, int future);
 int64_t m2f_attention_probs_elems(int B, int H, int L);
-/* The attention map of ONE site out of the probs that m2f_attention_fwd[_band] / m2f_attention_varlen_fwd[_band] wrote for the same
+/* The attention map of ONE site out of the probs that m2f_attention_fwd / m2f_attention_varlen_fwd wrote for the same
  * B, L, H (csrc/attention_weights.hip; m2f_plan_attention_weights above has the rule): out = fp32 [B, H, L, L] (per_head) or [B, L, L]
  * (heads summed in order, times (float)1 / H).  key_pad (padded rows, [B, L]) or cu (packed rows, int32 [B + 1]) or neither (every key
  * valid); past / future: the band the forward ran under (negative = unlimited).  Elements outside the dialogue, at padded keys or
@@ -704,9 +759,10 @@ int m2f_attention_weights(int B, int L, int H, const float* probs, const uint8_t
  * [S][H][C][pad4(hd)] float (bf16 == 0) or [S][H][C][pad8(hd)] bf16 (bf16 != 0: K, V rounded once on the way in, q where it enters
  * the product, softmax and sums fp32), 16-byte aligned, m2f_attention_stream_cache_elems elements each.  hd <= 128, C <= 512. */
 int64_t m2f_attention_stream_cache_elems(int S, int H, int hd, int C, int bf16);
+int64_t m2f_attention_stream_pool_elems(int n_pages, int H, int hd, int page_rows, int bf16);
 int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                          void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
-                         int bf16, m2f_stream_t stream);
+                         int bf16, m2f_stream_t stream, const m2f_attn_stream_opts* opts);
 /* The chunk form, one launch (csrc/attention_stream_chunk.hip): slot s takes n_new[s] (device int32, 0 .. T, T <= 64) new utterances -
  * rows s*T + t of q / k / v / out [S*T, H*hd] - and gets, row by row, what n_new[s] launches of m2f_attention_stream give: row t
  * attends to the chunk's rows <= t and to the cached utterances (ring != 0: to the last C - 1 utterances before it only), the chunk's
@@ -716,28 +772,15 @@ int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const fl
  * never read; n_new[s] == 0 leaves the slot's caches untouched.  count is NOT advanced. */
 int m2f_attention_stream_chunk(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                void* kcache, void* vcache, int C, int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo,
-                               int bf16, m2f_stream_t stream);
-/* Paged forms of the two launches above (layout: m2f_plan_create_stream_paged): kpool / vpool [n_pages][H][page_rows][pad(hd)],
- * m2f_attention_stream_pool_elems elements each, 16-byte aligned; table device int32 [S, table_cols], table_cols = ceil(C / page_rows).
- * Same results, bit for bit, as the dense launches on caches that hold the same rows.  Refused before any launch: page_rows outside
- * {16, 32, 64}, misaligned pools, table_cols != ceil(C / page_rows), C > 512, hd > 128. */
-int64_t m2f_attention_stream_pool_elems(int n_pages, int H, int hd, int page_rows, int bf16);
-int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                               void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                               const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, m2f_stream_t stream);
-/* The weights-emitting form of the step launch (the same kernel body with one more template flag; same out, same cache rows, same bits):
- * it also stores each (slot, head)'s row of attention probabilities to weights, fp32 [S, H, C], in LOGICAL order - column t is the
- * t-th oldest live utterance of the slot, the last live column the utterance that has just arrived (a ring: utterance u sits in row
- * u % C, undone here; paged: the page table never enters) - zeros behind the live count min(count + 1, C) and for inactive slots. */
-int m2f_attention_stream_weights(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                 void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
-                                 int bf16, float* weights, m2f_stream_t stream);
-int m2f_attention_stream_weights_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                       void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                       const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, m2f_stream_t stream);
-int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                     void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                     const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream);
+                               int bf16, m2f_stream_t stream, const m2f_attn_stream_opts* opts);
+/* The launch that closes a step / a prefill call of a stream with speaker heads: the new ids into the rows the new utterances took
+ * (what the attention launch did with K / V), then count += active (or the clamped n_new).  m2f_attention_speaker_class: 0 untouched,
+ * 1 same-speaker, 2 other-speaker. */
+int m2f_stream_advance_speakers(int S, int C, int ring, int32_t* count, const uint8_t* active, uint8_t* spk_cache, const uint8_t* spk_new,
+                                m2f_stream_t stream);
+int m2f_stream_advance_speakers_n(int S, int T, int C, int ring, int32_t* count, const int32_t* n_new, uint8_t* spk_cache, const uint8_t* spk_new,
+                                  m2f_stream_t stream);
+int m2f_attention_speaker_class(int h, int n_same, int n_other);
 /* Snapshot / restore of ONE site's stream caches (csrc/stream_cache.hip): the live rows of listed slots <-> a packed buffer.  Entry e
  * of n_entries holds the rows = min(lengths[e], C) live PHYSICAL cache rows 0 .. rows - 1 of slot slots[e] (a ring keeps its phase) as
  * [K, V][H][rows][pad(hd)] - the dense cache with C replaced by rows, pad columns as they are - and starts at element
@@ -746,102 +789,17 @@ int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q
  * packed -> caches and count[slot] = lengths[e] (an entry of length 0 resets its slot); rows >= min(lengths[e], C) of a listed slot,
  * every other slot and - paged - every other page are not written; the caller lists a slot once and keeps lengths <= C on a plain
  * cache.  An entry out of range (slot outside 0 .. S - 1, negative length or offset, rows past packed_elems) is skipped whole.
- * The paged forms take the pools and the table of m2f_attention_stream_paged and read the table only at the entries of pages that
- * hold a row of the entry; the packed bytes do not depend on the form.  Argument checks as m2f_attention_stream[_paged]. */
-int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, int C, int bf16, int n_entries,
-                                      const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
-                                      int64_t packed_elems, m2f_stream_t stream);
-int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, int C, int bf16, int n_entries,
-                                       const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
-                                       int64_t packed_elems, int32_t* count, m2f_stream_t stream);
-int m2f_attention_stream_cache_gather_paged(int S, int H, int hd, const void* kpool, const void* vpool, const int32_t* table, int table_cols,
-                                            int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
-                                            const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
-                                            m2f_stream_t stream);
-int m2f_attention_stream_cache_scatter_paged(int S, int H, int hd, void* kpool, void* vpool, const int32_t* table, int table_cols,
-                                             int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
-                                             const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
-                                             int32_t* count, m2f_stream_t stream);
-/* The same with a context band (attn_mask of a band shape): `past`, `future` >= 0, or negative = unlimited on that side.  Query i sees
- * key j iff j is a valid key as above and j >= i - past and j <= i + future, i and j being utterance positions inside the dialogue
- * (padded rows: the slot; packed rows: the row minus cu[b]).  (-1, 0) is causal attention, (k, 0) "the last k utterances and this
- * one", (-1, -1) the entries above - which call these.  A hidden key has P = 0 exactly.  A query that sees NO key (a pad slot whose
- * band holds pad keys only; a valid query always sees itself) gets a zero row of P, a zero output row and zero gradient terms, where
- * torch's masked softmax gives NaN: such rows are pad rows of saved activations, and the weight gradients sum over every row.  The
- * long-dialogue kernels (varlen) skip every pair of 64-row blocks the band hides as a whole and leave its block of `probs`
- * unwritten; the backward must be given the band of the forward whose probabilities it reads. */
-int m2f_attention_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                           const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs,
-                           uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future);
-int m2f_attention_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                           const float* v, int ldv, const uint8_t* key_pad, const float* out, int ldo,
-                           const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk,
-                           int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
-                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future);
-int m2f_attention_varlen_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
-                                  float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream,
-                                  int past, int future);
-int m2f_attention_varlen_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo,
-                                  const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk,
-                                  float* dv, int lddv, uint32_t drop_site, float drop_p, const uint32_t* rng_state,
-                                  m2f_stream_t stream, int past, int future);
-/* DISTANCE-DECAY BIAS (ALiBi).  The forward entries above with one more term: a VISIBLE key's score is
- * fma(-slope, float(|i - j|), dot(q_i, k_j) * (1 / sqrt(hd))), all fp32 (in bf16 mode too: behind the contraction), i and j the
- * positions the band compares; a hidden key stays -inf.  slope = gain * base(h, H), h the 0-based head: with n = 2^floor(log2 H),
- * base = 2^(-8 (h + 1) / n) for h < n and 2^(-4 (2 (h - n) + 1) / n) for h >= n (H = 4: 1/4, 1/16, 1/64, 1/256; H = 3: 1/16, 1/256,
- * 1/4).  gain >= 0 and finite, used as rounded to bf16 (what a plan applies); gain = 0 runs the kernels of the entries above.  Each
- * is a superset of its family: past / future as in the _band entries (negative = unlimited); the stream entries take the paging
- * arguments of the _paged forms (table = NULL: dense caches, table_cols / n_pages / page_rows ignored) and the weights buffer of the
- * _weights forms (NULL: none; the chunk form has none).  The new utterance of a stream is at distance 0, cached utterance u at
- * distance count - u; the backward entries are unchanged - they read the probabilities the biased forward saved. */
-int m2f_attention_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                           const float* v, int ldv, const uint8_t* key_pad, float* out, int ldo, float* probs,
-                           uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain);
-int m2f_attention_varlen_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
-                                  const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
-                                  float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream,
-                                  int past, int future, float gain);
-int m2f_attention_stream_bias(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                              void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                              const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
-                              m2f_stream_t stream);
-int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                    void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
-                                    int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
-                                    m2f_stream_t stream);
-/* SPEAKER HEADS.  The entries above with one more condition on which keys a query sees (m2f_plan_attention_speakers has the rule):
- * heads 0 .. n_same - 1 see the keys of the query's own speaker only, the next n_other heads the keys of the other speakers only.
- * Each is a superset of its _bias entry: past / future / gain as there (negative = unlimited; gain 0 = no bias), n_same = n_other = 0
- * runs the kernels of the entries above.  speakers: device uint8, one id per token row (padded: [B*L]; packed: [T], row cu[b] + i).
- * Stream entries: spk_cache = device uint8 [S][C], the ids of the cached utterances by logical cache row (read only; the row the new
- * utterance takes is never read), spk_new = device uint8 [S] (step) / [S][T] (chunk), the new utterances' ids.  An other-speaker head
- * with no other speaker in sight gives a zero output row and a zero weights row.  m2f_stream_advance_speakers[_n] is the launch that
- * closes a step / a prefill call of such a stream: the new ids into the rows the new utterances took (what the attention launch did
- * with K / V), then count += active (or the clamped n_new).  Refused before any launch: negative counts, n_same + n_other > H, a NULL
- * speakers / spk_cache / spk_new with a non-zero count.  m2f_attention_speaker_class: 0 untouched, 1 same-speaker, 2 other-speaker. */
-int m2f_attention_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                               const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
-                               const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
-                               const uint8_t* speakers, int n_same, int n_other);
-int m2f_attention_varlen_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                      const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
-                                      float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
-                                      const uint8_t* speakers, int n_same, int n_other);
-int m2f_attention_stream_speakers(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                  void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                  const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
-                                  const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream);
-int m2f_attention_stream_chunk_speakers(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                        void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
-                                        int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
-                                        const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream);
-int m2f_stream_advance_speakers(int S, int C, int ring, int32_t* count, const uint8_t* active, uint8_t* spk_cache, const uint8_t* spk_new,
-                                m2f_stream_t stream);
-int m2f_stream_advance_speakers_n(int S, int T, int C, int ring, int32_t* count, const int32_t* n_new, uint8_t* spk_cache, const uint8_t* spk_new,
-                                  m2f_stream_t stream);
-int m2f_attention_speaker_class(int h, int n_same, int n_other);
+ * table / table_cols / n_pages / page_rows: the paging fields of m2f_attn_stream_opts as plain arguments (table == NULL: dense caches);
+ * the table is read only at the entries of pages that hold a row of the entry, and the packed bytes do not depend on the form.
+ * Argument checks as m2f_attention_stream. */
+int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, const int32_t* table, int table_cols,
+                                      int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                      const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
+                                      m2f_stream_t stream);
+int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, const int32_t* table, int table_cols,
+                                       int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                       const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
+                                       int32_t* count, m2f_stream_t stream);
 /* The same attention for dialogues of up to 512 utterances (the kernels packed plans with L > 64 run): one workgroup per 64-row
  * block of a (dialogue, head), keys streamed in 64-row blocks.  Rows are given in one of two forms:
  *   packed: cu (int32 [B+1], device) - dialogue b owns rows cu[b] .. cu[b+1]-1 (at most L of them), T rows in all; rows cu[B] ..
@@ -852,12 +810,13 @@ int m2f_attention_speaker_class(int h, int n_same, int n_other);
  * Deterministic: every result element is written by one workgroup, no atomics. */
 int m2f_attention_varlen_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
                              const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo,
-                             float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream);
+                             float* probs, uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream,
+                             const m2f_attn_opts* opts);
 int m2f_attention_varlen_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
                              const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo,
                              const float* probs, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk,
                              float* dv, int lddv, uint32_t drop_site, float drop_p, const uint32_t* rng_state,
-                             m2f_stream_t stream);
+                             m2f_stream_t stream, int past, int future);
 /* out = (res ? res : 0) + LayerNorm(x) (nn.LayerNorm, eps), stats[T,2] = (mean, rstd). */
 int m2f_layernorm_fwd(int T, int d, const float* x, const float* gamma, const float* beta, const float* res,
                       float* out, float* stats, float eps, m2f_stream_t stream);

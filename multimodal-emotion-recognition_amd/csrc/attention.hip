@@ -654,6 +654,14 @@ bool attn_bwd_fast(int Lp, int maxW) {
     return maxW <= 128 && ((size_t)5 * Lp * (maxW + 2) + Lp) * sizeof(float) <= 160 * 1024;
 }
 
+template <typename K>
+hipError_t go(K kern, int blocks, size_t lds, hipStream_t stream, const AttnBatch& ab) {
+    if (lds > 64 * 1024)
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, ab);
+    return hipGetLastError();
+}
+
 template <bool BWD>
 hipError_t launch(AttnBatch& ab, hipStream_t stream) {
     if (ab.count <= 0 || ab.count > M2F_ATTN_MAX_PROBLEMS || ab.L < 1 || ab.L > 64) return hipErrorInvalidValue;
@@ -677,29 +685,20 @@ hipError_t launch(AttnBatch& ab, hipStream_t stream) {
     const bool band = (ab.band_past | ab.band_future) != 0, bias = !BWD && ab.bias_gain16 != 0;
     const bool spk = !BWD && (ab.spk_same | ab.spk_other) != 0;         // speaker heads: forward instantiations of their own
     if (spk && !m2f_attn_speakers_ok(ab)) return hipErrorInvalidValue;
-#define M2F_ATTN_CASE(N)                                                                                   \
-    case N: {                                                                                              \
-        auto kern = BWD ? m2f_attn_bwd_kernel<N> : bias ? (band ? m2f_attn_fwd_kernel<N, true, true> : m2f_attn_fwd_kernel<N, false, true>) \
-                                                         : (band ? m2f_attn_fwd_kernel<N, true> : m2f_attn_fwd_kernel<N, false>); \
-        if (spk) kern = bias ? (band ? m2f_attn_fwd_kernel<N, true, true, true> : m2f_attn_fwd_kernel<N, false, true, true>)      \
-                             : (band ? m2f_attn_fwd_kernel<N, true, false, true> : m2f_attn_fwd_kernel<N, false, false, true>);   \
-        if (lds > 64 * 1024) {                                                                             \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                        \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
-            if (e != hipSuccess) return e;                                                                 \
-        }                                                                                                  \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(NTHR), lds, stream, ab);                                 \
-        break;                                                                                             \
-    }
+    auto run = [&](auto N) {                    // backward: one kernel per NT; forward: one per combination of the three flags as well
+        constexpr int NTc = N.value;
+        if constexpr (BWD) return go(m2f_attn_bwd_kernel<NTc>, blocks, lds, stream, ab);
+        else return m2f_pick_bools([&](auto BAND, auto BIAS, auto SPK) {
+            return go(m2f_attn_fwd_kernel<NTc, BAND.value, BIAS.value, SPK.value>, blocks, lds, stream, ab);
+        }, band, bias, spk);
+    };
     switch (NT) {
-        M2F_ATTN_CASE(1)
-        M2F_ATTN_CASE(2)
-        M2F_ATTN_CASE(3)
-        M2F_ATTN_CASE(4)
+        case 1: return run(std::integral_constant<int, 1>{});
+        case 2: return run(std::integral_constant<int, 2>{});
+        case 3: return run(std::integral_constant<int, 3>{});
+        case 4: return run(std::integral_constant<int, 4>{});
         default: return hipErrorInvalidValue;
     }
-#undef M2F_ATTN_CASE
-    return hipGetLastError();
 }
 
 }  // namespace

@@ -519,30 +519,11 @@ hipError_t m2f_launch_attn_dlong_fwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)2 * BLK * (maxW + 2) * sizeof(float);
-    if (ab.spk_same | ab.spk_other) {                       // speaker heads: instantiations of their own, with / without band and bias
-        if (!m2f_attn_speakers_ok(ab)) return hipErrorInvalidValue;
-        const bool band = has_band(ab), wide = maxW > 128;
-        if (ab.bias_gain16) {
-            if (band) return wide ? go(m2f_attn_dlong_fwd_kernel<16, true, true, true>, blocks, lds, stream, ab)
-                                  : go(m2f_attn_dlong_fwd_kernel<8, true, true, true>, blocks, lds, stream, ab);
-            return wide ? go(m2f_attn_dlong_fwd_kernel<16, false, true, true>, blocks, lds, stream, ab)
-                        : go(m2f_attn_dlong_fwd_kernel<8, false, true, true>, blocks, lds, stream, ab);
-        }
-        if (band) return wide ? go(m2f_attn_dlong_fwd_kernel<16, true, false, true>, blocks, lds, stream, ab)
-                              : go(m2f_attn_dlong_fwd_kernel<8, true, false, true>, blocks, lds, stream, ab);
-        return wide ? go(m2f_attn_dlong_fwd_kernel<16, false, false, true>, blocks, lds, stream, ab)
-                    : go(m2f_attn_dlong_fwd_kernel<8, false, false, true>, blocks, lds, stream, ab);
-    }
-    if (ab.bias_gain16) {                                   // distance-decay bias: instantiations of their own
-        if (has_band(ab))
-            return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true, true>, blocks, lds, stream, ab)
-                               : go(m2f_attn_dlong_fwd_kernel<16, true, true>, blocks, lds, stream, ab);
-        return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, false, true>, blocks, lds, stream, ab)
-                           : go(m2f_attn_dlong_fwd_kernel<16, false, true>, blocks, lds, stream, ab);
-    }
-    if (has_band(ab))
-        return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, true>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, true>, blocks, lds, stream, ab);
-    return maxW <= 128 ? go(m2f_attn_dlong_fwd_kernel<8, false>, blocks, lds, stream, ab) : go(m2f_attn_dlong_fwd_kernel<16, false>, blocks, lds, stream, ab);
+    const bool spk = (ab.spk_same | ab.spk_other) != 0;
+    if (spk && !m2f_attn_speakers_ok(ab)) return hipErrorInvalidValue;
+    return m2f_pick_bools([&](auto WIDE, auto BAND, auto BIAS, auto SPK) {         // one instantiation per combination of the four flags
+        return go(m2f_attn_dlong_fwd_kernel<WIDE.value ? 16 : 8, BAND.value, BIAS.value, SPK.value>, blocks, lds, stream, ab);
+    }, maxW > 128, has_band(ab), ab.bias_gain16 != 0, spk);
 }
 
 hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream) {
@@ -550,14 +531,9 @@ hipError_t m2f_launch_attn_dlong_bwd(AttnBatch& ab, hipStream_t stream) {
     const int maxW = prepare(ab, blocks);
     if (maxW < 0) return hipErrorInvalidValue;
     const size_t lds = ((size_t)2 * BLK * (maxW + 2) + BLK) * sizeof(float);
-    if (has_band(ab)) {
-        hipError_t e = maxW <= 128 ? go(m2f_attn_dlong_dkdv_kernel<8, true>, blocks, lds, stream, ab)
-                                   : go(m2f_attn_dlong_dkdv_kernel<16, true>, blocks, lds, stream, ab);
-        if (e != hipSuccess) return e;
-        return maxW <= 128 ? go(m2f_attn_dlong_dq_kernel<8, true>, blocks, lds, stream, ab) : go(m2f_attn_dlong_dq_kernel<16, true>, blocks, lds, stream, ab);
-    }
-    hipError_t e = maxW <= 128 ? go(m2f_attn_dlong_dkdv_kernel<8, false>, blocks, lds, stream, ab)
-                               : go(m2f_attn_dlong_dkdv_kernel<16, false>, blocks, lds, stream, ab);
-    if (e != hipSuccess) return e;
-    return maxW <= 128 ? go(m2f_attn_dlong_dq_kernel<8, false>, blocks, lds, stream, ab) : go(m2f_attn_dlong_dq_kernel<16, false>, blocks, lds, stream, ab);
+    return m2f_pick_bools([&](auto WIDE, auto BAND) {
+        constexpr int CTM = WIDE.value ? 16 : 8;
+        const hipError_t e = go(m2f_attn_dlong_dkdv_kernel<CTM, BAND.value>, blocks, lds, stream, ab);
+        return e != hipSuccess ? e : go(m2f_attn_dlong_dq_kernel<CTM, BAND.value>, blocks, lds, stream, ab);
+    }, maxW > 128, has_band(ab));
 }

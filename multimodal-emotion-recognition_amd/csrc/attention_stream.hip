@@ -287,6 +287,12 @@ __global__ void m2f_stream_reset_kernel(int* len, const uint8_t* mask, int S) {
     if (s < S && (!mask || mask[s])) len[s] = 0;
 }
 
+template <typename K, typename... Args>
+hipError_t go(K kern, int blocks, hipStream_t stream, const Args&... args) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, stream, args...);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t m2f_attn_stream_cache_elems(int S, int H, int hd, int C, int bf16) { return (size_t)S * H * C * m2f_stream_hdp(hd, bf16 != 0); }
@@ -328,60 +334,17 @@ hipError_t m2f_launch_attn_stream(AttnStreamBatch& ab, const AttnStreamPaging* p
     if (weights)
         for (int i = 0; i < ab.count; ++i)
             if (!weights->w[i] || (reinterpret_cast<uintptr_t>(weights->w[i]) & 3)) return hipErrorInvalidValue;
-    if (ab.spk_same | ab.spk_other) {             // speaker heads: the same four forms with / without the bias, instantiations of their own
-        if (!m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
-        const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
-        const bool bias = ab.bias_gain != 0.f;
-#define M2F_STREAM_SPK(KERN, ...)                                                                                              \
-        do {                                                                                                                   \
-            if (ab.bf16) { if (bias) hipLaunchKernelGGL((KERN<true, true, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__);   \
-                           else hipLaunchKernelGGL((KERN<true, false, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__); }     \
-            else { if (bias) hipLaunchKernelGGL((KERN<false, true, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__);          \
-                   else hipLaunchKernelGGL((KERN<false, false, true>), dim3(blocks), dim3(64), 0, stream, __VA_ARGS__); }            \
-        } while (0)
-        if (weights && paging) M2F_STREAM_SPK(m2f_attn_stream_paged_weights_kernel, ab, pg, ww);
-        else if (weights) M2F_STREAM_SPK(m2f_attn_stream_weights_kernel, ab, ww);
-        else if (paging) M2F_STREAM_SPK(m2f_attn_stream_paged_kernel, ab, pg);
-        else M2F_STREAM_SPK(m2f_attn_stream_kernel, ab);
-#undef M2F_STREAM_SPK
-        return hipGetLastError();
-    }
-    if (ab.bias_gain != 0.f) {                    // distance-decay bias: the same four forms, instantiations of their own
-        const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
-        if (weights && paging) {
-            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_paged_weights_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
-            else hipLaunchKernelGGL((m2f_attn_stream_paged_weights_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
-        } else if (weights) {
-            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_weights_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, ww);
-            else hipLaunchKernelGGL((m2f_attn_stream_weights_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, ww);
-        } else if (paging) {
-            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_paged_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab, pg);
-            else hipLaunchKernelGGL((m2f_attn_stream_paged_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab, pg);
-        } else {
-            if (ab.bf16) hipLaunchKernelGGL((m2f_attn_stream_kernel<true, true>), dim3(blocks), dim3(64), 0, stream, ab);
-            else hipLaunchKernelGGL((m2f_attn_stream_kernel<false, true>), dim3(blocks), dim3(64), 0, stream, ab);
-        }
-        return hipGetLastError();
-    }
-    if (weights) {                                // the weights-emitting form: a row of [S][H][C] floats per problem
-        const AttnStreamWeights ww = *weights;
-        if (paging) {
-            if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
-            else hipLaunchKernelGGL(m2f_attn_stream_paged_weights_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg, ww);
-        } else {
-            if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_weights_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, ww);
-            else hipLaunchKernelGGL(m2f_attn_stream_weights_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, ww);
-        }
-        return hipGetLastError();
-    }
-    if (paging) {
-        if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab, pg);
-        else hipLaunchKernelGGL(m2f_attn_stream_paged_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab, pg);
-    } else {
-        if (ab.bf16) hipLaunchKernelGGL(m2f_attn_stream_kernel<true>, dim3(blocks), dim3(64), 0, stream, ab);
-        else hipLaunchKernelGGL(m2f_attn_stream_kernel<false>, dim3(blocks), dim3(64), 0, stream, ab);
-    }
-    return hipGetLastError();
+    const bool spk = (ab.spk_same | ab.spk_other) != 0;
+    if (spk && !m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
+    const AttnStreamWeights ww = weights ? *weights : AttnStreamWeights{{nullptr}};
+    // one instantiation per combination of the five flags; PAGED / WEIGHTS also choose the wrapper, whose argument list they shape
+    return m2f_pick_bools([&](auto BF16, auto PAGED, auto WEIGHTS, auto BIAS, auto SPK) {
+        constexpr bool b16 = BF16.value, paged = PAGED.value, wts = WEIGHTS.value, bias = BIAS.value, sp = SPK.value;
+        if constexpr (paged && wts) return go(m2f_attn_stream_paged_weights_kernel<b16, bias, sp>, blocks, stream, ab, pg, ww);
+        else if constexpr (wts) return go(m2f_attn_stream_weights_kernel<b16, bias, sp>, blocks, stream, ab, ww);
+        else if constexpr (paged) return go(m2f_attn_stream_paged_kernel<b16, bias, sp>, blocks, stream, ab, pg);
+        else return go(m2f_attn_stream_kernel<b16, bias, sp>, blocks, stream, ab);
+    }, ab.bf16 != 0, paging != nullptr, weights != nullptr, ab.bias_gain != 0.f, spk);
 }
 
 hipError_t m2f_launch_stream_advance(int* len, const uint8_t* active, int S, hipStream_t stream) {

@@ -435,33 +435,12 @@ hipError_t m2f_launch_attn_stream_chunk(AttnStreamBatch& ab, const AttnStreamPag
     const int blocks = n_new && T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK ? m2f_attn_stream_prepare(ab, paging ? &pg : nullptr, &maxW) : -1;
     if (blocks < 0 || !(ab.bias_gain >= 0.f) || ab.bias_gain > 3.0e38f) return hipErrorInvalidValue;
     const size_t lds = (size_t)4 * BLK * (maxW + 2) * sizeof(float);
-    if (ab.spk_same | ab.spk_other) {                       // speaker heads: instantiations of their own, with / without the bias
-        if (!m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
-        if (ab.bias_gain != 0.f) {
-            if (paging)
-                return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, true, true>, blocks, lds, stream, ab, pg, T, n_new)
-                               : go(m2f_attn_stream_chunk_paged_kernel<false, true, true>, blocks, lds, stream, ab, pg, T, n_new);
-            return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, true, true>, blocks, lds, stream, ab, T, n_new)
-                           : go(m2f_attn_stream_chunk_kernel<false, true, true>, blocks, lds, stream, ab, T, n_new);
-        }
-        if (paging)
-            return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, false, true>, blocks, lds, stream, ab, pg, T, n_new)
-                           : go(m2f_attn_stream_chunk_paged_kernel<false, false, true>, blocks, lds, stream, ab, pg, T, n_new);
-        return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, false, true>, blocks, lds, stream, ab, T, n_new)
-                       : go(m2f_attn_stream_chunk_kernel<false, false, true>, blocks, lds, stream, ab, T, n_new);
-    }
-    if (ab.bias_gain != 0.f) {                              // distance-decay bias: instantiations of their own
-        if (paging)
-            return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true, true>, blocks, lds, stream, ab, pg, T, n_new)
-                           : go(m2f_attn_stream_chunk_paged_kernel<false, true>, blocks, lds, stream, ab, pg, T, n_new);
-        return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true, true>, blocks, lds, stream, ab, T, n_new)
-                       : go(m2f_attn_stream_chunk_kernel<false, true>, blocks, lds, stream, ab, T, n_new);
-    }
-    if (paging)
-        return ab.bf16 ? go(m2f_attn_stream_chunk_paged_kernel<true>, blocks, lds, stream, ab, pg, T, n_new)
-                       : go(m2f_attn_stream_chunk_paged_kernel<false>, blocks, lds, stream, ab, pg, T, n_new);
-    return ab.bf16 ? go(m2f_attn_stream_chunk_kernel<true>, blocks, lds, stream, ab, T, n_new)
-                   : go(m2f_attn_stream_chunk_kernel<false>, blocks, lds, stream, ab, T, n_new);
+    const bool spk = (ab.spk_same | ab.spk_other) != 0;
+    if (spk && !m2f_attn_stream_speakers_ok(ab)) return hipErrorInvalidValue;
+    return m2f_pick_bools([&](auto BF16, auto PAGED, auto BIAS, auto SPK) {       // one instantiation per combination of the four flags
+        if constexpr (PAGED.value) return go(m2f_attn_stream_chunk_paged_kernel<BF16.value, BIAS.value, SPK.value>, blocks, lds, stream, ab, pg, T, n_new);
+        else return go(m2f_attn_stream_chunk_kernel<BF16.value, BIAS.value, SPK.value>, blocks, lds, stream, ab, T, n_new);
+    }, ab.bf16 != 0, paging != nullptr, ab.bias_gain != 0.f, spk);
 }
 
 hipError_t m2f_launch_stream_advance_n(int* len, const int* n_new, int S, int T, hipStream_t stream) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // Kernel-argument warm-up.  The kernels take their launch descriptors (GemmBatch, AttnBatch, LnBatch: 0.5-3 KB) BY VALUE; the
 // kernarg segment of a launch is cold in the scalar cache and in L2, and hipcc issues its s_loads lazily - a grouped GEMM
@@ -95,6 +96,17 @@ __device__ __forceinline__ float m2f_wave_max(float v) {
 }
 
 static inline int m2f_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Host-side pick among the instantiations of a kernel template: m2f_pick_bools(f, a, b, ...) calls f(std::bool_constant<a>{},
+// std::bool_constant<b>{}, ...) for the runtime bools a, b, ... - every combination is instantiated, so a launcher names its kernel
+// template once and a new flag is one more argument, never one more arm.
+template <typename F>
+auto m2f_pick_bools(F&& f) { return f(); }
+template <typename F, typename... Rest>
+auto m2f_pick_bools(F&& f, bool first, Rest... rest) {
+    return first ? m2f_pick_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+                 : m2f_pick_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
 
 // fp32 -> bf16 bits, round to nearest even (same rounding the GEMM staging applies; NaN stays NaN)
 __device__ __forceinline__ uint16_t m2f_bf16_bits(float x) {

@@ -137,35 +137,14 @@ static void attn_fill(AttnBatch& ab, int B, int L, int H, int hd, const float* q
     if (drop_site) drop_params(drop_p, &ab.drop_thresh, &ab.drop_scale);
 }
 
-int m2f_attention_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                           const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
-                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
-    AttnBatch ab;
-    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
-    m2f_attn_set_band(ab, past, future);
-    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-/* the gain of the _bias entries -> what the launch descriptor holds: finite, >= 0, rounded to bf16 */
+/* a gain option -> what the launch descriptor holds: finite, >= 0, rounded to bf16 */
 static int bias_gain_ok(const char* who, float gain, float* applied) {
     if (!(gain >= 0.f) || !std::isfinite(gain)) return fail(std::string(who) + ": gain must be finite and >= 0");
     *applied = m2f_attn_bias_gain(m2f_attn_bias_gain16(gain));
     if (!std::isfinite(*applied)) return fail(std::string(who) + ": gain is out of range");
     return 0;
 }
-int m2f_attention_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                           const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
-                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_fwd_bias", gain, &g)) return r;
-    AttnBatch ab;
-    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
-    m2f_attn_set_band(ab, past, future);
-    ab.bias_gain16 = m2f_attn_bias_gain16(g);
-    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-/* the speaker-head counts of the _speakers entries: >= 0, together at most H, and ids wherever a count is non-zero */
+/* the speaker-head counts: >= 0, together at most H, and ids wherever a count is non-zero */
 static int speaker_heads_ok(const char* who, int H, int n_same, int n_other, const void* ids, const char* what) {
     const std::string w(who);
     if (n_same < 0 || n_other < 0) return fail(w + ": n_same and n_other must be >= 0");
@@ -174,123 +153,75 @@ static int speaker_heads_ok(const char* who, int H, int n_same, int n_other, con
     if ((n_same | n_other) && !ids) return fail(w + ": speaker heads need " + what);
     return 0;
 }
-int m2f_attention_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                               const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
-                               const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
-                               const uint8_t* speakers, int n_same, int n_other) {
+/* m2f_attn_opts -> the launch descriptor of a forward entry (NULL: no option); every refusal comes before the launch */
+static int attn_apply(const char* who, AttnBatch& ab, const m2f_attn_opts* opts) {
+    static const m2f_attn_opts none = M2F_ATTN_OPTS_NONE;
+    const m2f_attn_opts& o = opts ? *opts : none;
     float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_fwd_speakers", gain, &g)) return r;
-    if (int r = speaker_heads_ok("m2f_attention_fwd_speakers", H, n_same, n_other, speakers, "speakers (uint8, one per token row)")) return r;
-    AttnBatch ab;
-    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
-    m2f_attn_set_band(ab, past, future);
+    if (int r = bias_gain_ok(who, o.bias_gain, &g)) return r;
+    if (int r = speaker_heads_ok(who, ab.pr[0].H, o.n_same, o.n_other, o.speakers, "speakers (uint8, one per token row)")) return r;
+    m2f_attn_set_band(ab, o.past, o.future);
     ab.bias_gain16 = m2f_attn_bias_gain16(g);
-    ab.speaker = (n_same | n_other) ? speakers : nullptr; ab.spk_same = (uint8_t)n_same; ab.spk_other = (uint8_t)n_other;
-    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
+    ab.speaker = (o.n_same | o.n_other) ? o.speakers : nullptr; ab.spk_same = (uint8_t)o.n_same; ab.spk_other = (uint8_t)o.n_other;
     return 0;
+}
+static void attn_bwd_fill(AttnBatch& ab, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                          int past, int future) {
+    AttnProblem& p = ab.pr[0];
+    p.dout = dout; p.lddo = lddo; p.dq = dq; p.dk = dk; p.dv = dv; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+    m2f_attn_set_band(ab, past, future);               // (short: the saved P^T carries the band; long: the block pairs the forward skipped)
 }
 int m2f_attention_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                       const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site, float drop_p,
-                      const uint32_t* rng_state, m2f_stream_t stream) {
-    return m2f_attention_fwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state, stream, -1, -1);
+                      const uint32_t* rng_state, m2f_stream_t stream, const m2f_attn_opts* opts) {
+    AttnBatch ab;
+    attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
+    if (int r = attn_apply("m2f_attention_fwd", ab, opts)) return r;
+    M2F_HIP(m2f_launch_attn_fwd(ab, static_cast<hipStream_t>(stream)));
+    return 0;
 }
-
 int m2f_attention_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                       const uint8_t* key_pad, const float* out, int ldo, const float* probs, const float* dout, int lddo,
                       float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
-                      const uint32_t* rng_state, m2f_stream_t stream) {
-    return m2f_attention_bwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, dout, lddo, dq, lddq, dk, lddk, dv, lddv,
-                                  drop_site, drop_p, rng_state, stream, -1, -1);
-}
-int m2f_attention_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                           const uint8_t* key_pad, const float* out, int ldo, const float* probs, const float* dout, int lddo,
-                           float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, uint32_t drop_site, float drop_p,
-                           const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+                      const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
     AttnBatch ab;
     attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, const_cast<float*>(out), ldo, const_cast<float*>(probs),
               drop_site, drop_p, rng_state);
-    AttnProblem& p = ab.pr[0];
-    p.dout = dout; p.lddo = lddo; p.dq = dq; p.dk = dk; p.dv = dv; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-    m2f_attn_set_band(ab, past, future);               // (the saved P^T carries the band: the short kernel does not read it)
+    attn_bwd_fill(ab, dout, lddo, dq, lddq, dk, lddk, dv, lddv, past, future);
     M2F_HIP(m2f_launch_attn_bwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
-static int attn_varlen_fill(AttnBatch& ab, int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
+static int attn_varlen_fill(const char* who, AttnBatch& ab, int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk,
                             const float* v, int ldv, const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs,
                             uint32_t drop_site, float drop_p, const uint32_t* rng_state) {
-    if (B < 1 || L < 1 || L > M2F_ATTN_DLONG_MAX_L) return fail("m2f_attention_varlen: 1 <= L <= 512 required (got L = " + std::to_string(L) + ")");
-    if (!cu == !key_pad) return fail("m2f_attention_varlen: exactly one of cu (packed rows) and key_pad (padded rows) must be given");
-    if (cu && T < 1) return fail("m2f_attention_varlen: packed rows need T >= 1");
-    if (!m2f_attn_dlong_index_ok(B, H, L)) return fail("m2f_attention_varlen: B * H * L * L must stay below 2^32");
+    const std::string w(who);
+    if (B < 1 || L < 1 || L > M2F_ATTN_DLONG_MAX_L) return fail(w + ": 1 <= L <= 512 required (got L = " + std::to_string(L) + ")");
+    if (!cu == !key_pad) return fail(w + ": exactly one of cu (packed rows) and key_pad (padded rows) must be given");
+    if (cu && T < 1) return fail(w + ": packed rows need T >= 1");
+    if (!m2f_attn_dlong_index_ok(B, H, L)) return fail(w + ": B * H * L * L must stay below 2^32");
     attn_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, probs, drop_site, drop_p, rng_state);
     ab.bf16_math = 0;                                          // (the long-dialogue kernels read fp32 operands only)
     ab.cu = cu; ab.T = cu ? T : B * L;
     return 0;
 }
-
 int m2f_attention_varlen_fwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                              const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
-                             float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
-    return m2f_attention_varlen_fwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state,
-                                         stream, -1, -1);
-}
-int m2f_attention_varlen_fwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                  const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
-                                  float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+                             float drop_p, const uint32_t* rng_state, m2f_stream_t stream, const m2f_attn_opts* opts) {
     AttnBatch ab;
-    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
-    m2f_attn_set_band(ab, past, future);
+    if (attn_varlen_fill("m2f_attention_varlen_fwd", ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
+    if (int r = attn_apply("m2f_attention_varlen_fwd", ab, opts)) return r;
     M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
-
-int m2f_attention_varlen_fwd_bias(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                  const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
-                                  float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_varlen_fwd_bias", gain, &g)) return r;
-    AttnBatch ab;
-    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
-    m2f_attn_set_band(ab, past, future);
-    ab.bias_gain16 = m2f_attn_bias_gain16(g);
-    M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int m2f_attention_varlen_fwd_speakers(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                      const int32_t* cu, int T, const uint8_t* key_pad, float* out, int ldo, float* probs, uint32_t drop_site,
-                                      float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future, float gain,
-                                      const uint8_t* speakers, int n_same, int n_other) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_varlen_fwd_speakers", gain, &g)) return r;
-    if (int r = speaker_heads_ok("m2f_attention_varlen_fwd_speakers", H, n_same, n_other, speakers, "speakers (uint8, one per token row)")) return r;
-    AttnBatch ab;
-    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, drop_site, drop_p, rng_state)) return -1;
-    m2f_attn_set_band(ab, past, future);
-    ab.bias_gain16 = m2f_attn_bias_gain16(g);
-    ab.speaker = (n_same | n_other) ? speakers : nullptr; ab.spk_same = (uint8_t)n_same; ab.spk_other = (uint8_t)n_other;
-    M2F_HIP(m2f_launch_attn_dlong_fwd(ab, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
 int m2f_attention_varlen_bwd(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                              const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo, const float* probs,
                              const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
-                             uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream) {
-    return m2f_attention_varlen_bwd_band(B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, out, ldo, probs, dout, lddo, dq, lddq, dk, lddk,
-                                         dv, lddv, drop_site, drop_p, rng_state, stream, -1, -1);
-}
-int m2f_attention_varlen_bwd_band(int B, int L, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                  const int32_t* cu, int T, const uint8_t* key_pad, const float* out, int ldo, const float* probs,
-                                  const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
-                                  uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
+                             uint32_t drop_site, float drop_p, const uint32_t* rng_state, m2f_stream_t stream, int past, int future) {
     AttnBatch ab;
-    if (attn_varlen_fill(ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, const_cast<float*>(out), ldo, const_cast<float*>(probs),
+    if (attn_varlen_fill("m2f_attention_varlen_bwd", ab, B, L, H, hd, q, ldq, k, ldk, v, ldv, cu, T, key_pad, const_cast<float*>(out), ldo, const_cast<float*>(probs),
                          drop_site, drop_p, rng_state)) return -1;
-    m2f_attn_set_band(ab, past, future);               // (the backward skips the block pairs the forward skipped)
-    AttnProblem& p = ab.pr[0];
-    p.dout = dout; p.lddo = lddo; p.dq = dq; p.dk = dk; p.dv = dv; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+    attn_bwd_fill(ab, dout, lddo, dq, lddq, dk, lddk, dv, lddv, past, future);
     M2F_HIP(m2f_launch_attn_dlong_bwd(ab, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -314,15 +245,15 @@ static int paged_args_ok(const char* who, int S, int H, int hd, int C, int n_pag
     if (reinterpret_cast<uintptr_t>(table) & 3) return fail(w + ": the table must be 4-byte aligned");
     return 0;
 }
-/* The four kernel-level launches: one argument check and one batch fill.  chunk: the chunk form of T rows per slot (`second` = n_new),
-   otherwise the step form (`second` = active); pg == nullptr: dense caches, otherwise kc / vc are the pools. */
-static int stream_attn_fill(const char* who, AttnStreamBatch& sb, const AttnStreamPaging* pg, int S, bool chunk, int T, int H, int hd, const float* q, int ldq,
+/* The two kernel-level launches: one argument check and one batch fill.  chunk: the chunk form of T rows per slot (`second` = n_new),
+   otherwise the step form (`second` = active); a table in the options: kc / vc are the pools, otherwise dense caches. */
+static int stream_attn_fill(const char* who, AttnStreamBatch& sb, const m2f_attn_stream_opts* o, int S, bool chunk, int T, int H, int hd, const float* q, int ldq,
                             const float* k, int ldk, const float* v, int ldv, void* kc, void* vc, int C, int ring, const int32_t* count,
                             const void* second, float* out, int ldo, int bf16) {
     const std::string w(who);
-    const bool t_ok = !chunk || (T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK);
+    const bool t_ok = !chunk || (T >= 1 && T <= M2F_ATTN_STREAM_MAX_CHUNK), pg = o && o->table;
     if (pg) {
-        if (int r = paged_args_ok(who, S, H, hd, C, pg->n_pages, pg->R, pg->tw, kc, vc, pg->table)) return r;
+        if (int r = paged_args_ok(who, S, H, hd, C, o->n_pages, o->page_rows, o->table_cols, kc, vc, o->table)) return r;
         if (!t_ok) return fail(w + ": 1 <= T <= 64 required");
     } else if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C || !t_ok) {
         return fail(w + ": S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512" + (chunk ? ", 1 <= T <= 64" : "") + " required");
@@ -338,122 +269,52 @@ static int stream_attn_fill(const char* who, AttnStreamBatch& sb, const AttnStre
     p.q = q; p.k = k; p.v = v; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.out = out; p.ldo = ldo; p.kcache = kc; p.vcache = vc; p.H = H; p.hd = hd;
     return 0;
 }
+/* m2f_attn_stream_opts -> the batch, plus what a launcher takes beside it (NULL: no option); every refusal comes before the launch.
+   chunk: spk_new holds T ids per slot, and there is no weights-emitting kernel */
+struct StreamExtras {
+    AttnStreamPaging pg;
+    AttnStreamWeights ww;
+    const AttnStreamPaging* paging = nullptr;
+    const AttnStreamWeights* weights = nullptr;
+};
+static int stream_attn_apply(const char* who, AttnStreamBatch& sb, bool chunk, const m2f_attn_stream_opts* o, StreamExtras& x) {
+    if (!o) return 0;
+    const std::string w(who);
+    float g = 0.f;
+    if (int r = bias_gain_ok(who, o->bias_gain, &g)) return r;
+    if (int r = speaker_heads_ok(who, sb.pr[0].H, o->n_same, o->n_other, o->spk_new,
+                                 chunk ? "the new utterances' speakers (uint8 [S][T])" : "the new utterances' speakers (uint8 [S])")) return r;
+    if ((o->n_same | o->n_other) && !o->spk_cache) return fail(w + ": speaker heads need the cached speakers (uint8 [S][C])");
+    if (o->weights) {
+        if (chunk) return fail(w + ": the chunk form emits no rows of probabilities, weights must be NULL");
+        if (reinterpret_cast<uintptr_t>(o->weights) & 3) return fail(w + ": weights must be a 4-byte aligned device buffer of S * H * C floats");
+        memset(&x.ww, 0, sizeof(x.ww));
+        x.ww.w[0] = o->weights;
+        x.weights = &x.ww;
+    }
+    if (o->table) { x.pg = {o->table, o->table_cols, o->page_rows, 0, o->n_pages}; x.paging = &x.pg; }
+    sb.bias_gain = g;
+    if (o->n_same | o->n_other) { sb.spk_cache = o->spk_cache; sb.spk_new = o->spk_new; sb.spk_same = (uint8_t)o->n_same; sb.spk_other = (uint8_t)o->n_other; }
+    return 0;
+}
 int m2f_attention_stream(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                          void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
-                         int bf16, m2f_stream_t stream) {
+                         int bf16, m2f_stream_t stream, const m2f_attn_stream_opts* opts) {
     AttnStreamBatch sb;
-    if (int r = stream_attn_fill("m2f_attention_stream", sb, nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
-    M2F_HIP(m2f_launch_attn_stream(sb, nullptr, static_cast<hipStream_t>(stream)));
+    StreamExtras x;
+    if (int r = stream_attn_fill("m2f_attention_stream", sb, opts, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
+    if (int r = stream_attn_apply("m2f_attention_stream", sb, false, opts, x)) return r;
+    M2F_HIP(m2f_launch_attn_stream(sb, x.paging, static_cast<hipStream_t>(stream), x.weights));
     return 0;
 }
 int m2f_attention_stream_chunk(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                void* kcache, void* vcache, int C, int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo,
-                               int bf16, m2f_stream_t stream) {
+                               int bf16, m2f_stream_t stream, const m2f_attn_stream_opts* opts) {
     AttnStreamBatch sb;
-    if (int r = stream_attn_fill("m2f_attention_stream_chunk", sb, nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
-    M2F_HIP(m2f_launch_attn_stream_chunk(sb, nullptr, T, n_new, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-int m2f_attention_stream_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                               void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                               const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, m2f_stream_t stream) {
-    AttnStreamBatch sb;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_paged", sb, &pg, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, active, out, ldo, bf16)) return r;
-    M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-/* ... and their weights-emitting forms: the same launch, plus the rows of probabilities into weights [S, H, C] */
-static int stream_weights_ok(const char* who, const float* weights, AttnStreamWeights& ww) {
-    if (!weights || (reinterpret_cast<uintptr_t>(weights) & 3)) return fail(std::string(who) + ": weights must be a 4-byte aligned device buffer of S * H * C floats");
-    memset(&ww, 0, sizeof(ww));
-    ww.w[0] = const_cast<float*>(weights);
-    return 0;
-}
-int m2f_attention_stream_weights(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                 void* kcache, void* vcache, int C, int ring, const int32_t* count, const uint8_t* active, float* out, int ldo,
-                                 int bf16, float* weights, m2f_stream_t stream) {
-    AttnStreamBatch sb;
-    AttnStreamWeights ww;
-    if (int r = stream_attn_fill("m2f_attention_stream_weights", sb, nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
-    if (int r = stream_weights_ok("m2f_attention_stream_weights", weights, ww)) return r;
-    M2F_HIP(m2f_launch_attn_stream(sb, nullptr, static_cast<hipStream_t>(stream), &ww));
-    return 0;
-}
-int m2f_attention_stream_weights_paged(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                       void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                       const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, m2f_stream_t stream) {
-    AttnStreamBatch sb;
-    AttnStreamWeights ww;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_weights_paged", sb, &pg, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, active, out, ldo, bf16)) return r;
-    if (int r = stream_weights_ok("m2f_attention_stream_weights_paged", weights, ww)) return r;
-    M2F_HIP(m2f_launch_attn_stream(sb, &pg, static_cast<hipStream_t>(stream), &ww));
-    return 0;
-}
-/* ... and the supersets with a distance-decay bias: table == NULL - dense caches; weights == NULL - no rows of probabilities */
-int m2f_attention_stream_bias(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                              void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                              const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
-                              m2f_stream_t stream) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_stream_bias", gain, &g)) return r;
-    AttnStreamBatch sb;
-    AttnStreamWeights ww;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_bias", sb, table ? &pg : nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
-    if (weights) if (int r = stream_weights_ok("m2f_attention_stream_bias", weights, ww)) return r;
-    sb.bias_gain = g;
-    M2F_HIP(m2f_launch_attn_stream(sb, table ? &pg : nullptr, static_cast<hipStream_t>(stream), weights ? &ww : nullptr));
-    return 0;
-}
-int m2f_attention_stream_chunk_bias(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                    void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
-                                    int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
-                                    m2f_stream_t stream) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_stream_chunk_bias", gain, &g)) return r;
-    AttnStreamBatch sb;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_chunk_bias", sb, table ? &pg : nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
-    sb.bias_gain = g;
-    M2F_HIP(m2f_launch_attn_stream_chunk(sb, table ? &pg : nullptr, T, n_new, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-/* ... and the supersets with speaker heads: spk_cache uint8 [S][C] (read), spk_new uint8 [S] (step) / [S][T] (chunk); the advance entries
-   below store the new ids and close the step / the call */
-int m2f_attention_stream_speakers(int S, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                  void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                  const int32_t* count, const uint8_t* active, float* out, int ldo, int bf16, float* weights, float gain,
-                                  const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_stream_speakers", gain, &g)) return r;
-    if (int r = speaker_heads_ok("m2f_attention_stream_speakers", H, n_same, n_other, spk_new, "the new utterances' speakers (uint8 [S])")) return r;
-    if ((n_same | n_other) && !spk_cache) return fail("m2f_attention_stream_speakers: speaker heads need the cached speakers (uint8 [S][C])");
-    AttnStreamBatch sb;
-    AttnStreamWeights ww;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_speakers", sb, table ? &pg : nullptr, S, false, 1, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, active, out, ldo, bf16)) return r;
-    if (weights) if (int r = stream_weights_ok("m2f_attention_stream_speakers", weights, ww)) return r;
-    sb.bias_gain = g;
-    if (n_same | n_other) { sb.spk_cache = spk_cache; sb.spk_new = spk_new; sb.spk_same = (uint8_t)n_same; sb.spk_other = (uint8_t)n_other; }
-    M2F_HIP(m2f_launch_attn_stream(sb, table ? &pg : nullptr, static_cast<hipStream_t>(stream), weights ? &ww : nullptr));
-    return 0;
-}
-int m2f_attention_stream_chunk_speakers(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                        void* kcache, void* vcache, const int32_t* table, int table_cols, int n_pages, int page_rows, int C,
-                                        int ring, const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, float gain,
-                                        const uint8_t* spk_cache, const uint8_t* spk_new, int n_same, int n_other, m2f_stream_t stream) {
-    float g = 0.f;
-    if (int r = bias_gain_ok("m2f_attention_stream_chunk_speakers", gain, &g)) return r;
-    if (int r = speaker_heads_ok("m2f_attention_stream_chunk_speakers", H, n_same, n_other, spk_new, "the new utterances' speakers (uint8 [S][T])")) return r;
-    if ((n_same | n_other) && !spk_cache) return fail("m2f_attention_stream_chunk_speakers: speaker heads need the cached speakers (uint8 [S][C])");
-    AttnStreamBatch sb;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_chunk_speakers", sb, table ? &pg : nullptr, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
-    sb.bias_gain = g;
-    if (n_same | n_other) { sb.spk_cache = spk_cache; sb.spk_new = spk_new; sb.spk_same = (uint8_t)n_same; sb.spk_other = (uint8_t)n_other; }
-    M2F_HIP(m2f_launch_attn_stream_chunk(sb, table ? &pg : nullptr, T, n_new, static_cast<hipStream_t>(stream)));
+    StreamExtras x;
+    if (int r = stream_attn_fill("m2f_attention_stream_chunk", sb, opts, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kcache, vcache, C, ring, count, n_new, out, ldo, bf16)) return r;
+    if (int r = stream_attn_apply("m2f_attention_stream_chunk", sb, true, opts, x)) return r;
+    M2F_HIP(m2f_launch_attn_stream_chunk(sb, x.paging, T, n_new, static_cast<hipStream_t>(stream)));
     return 0;
 }
 int m2f_stream_advance_speakers(int S, int C, int ring, int32_t* count, const uint8_t* active, uint8_t* spk_cache, const uint8_t* spk_new,
@@ -472,21 +333,29 @@ int m2f_stream_advance_speakers_n(int S, int T, int C, int ring, int32_t* count,
     return 0;
 }
 int m2f_attention_speaker_class(int h, int n_same, int n_other) { return m2f_attn_speaker_class(h, n_same, n_other); }
-int m2f_attention_stream_chunk_paged(int S, int T, int H, int hd, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                                     void* kpool, void* vpool, const int32_t* table, int table_cols, int n_pages, int page_rows, int C, int ring,
-                                     const int32_t* count, const int32_t* n_new, float* out, int ldo, int bf16, m2f_stream_t stream) {
-    AttnStreamBatch sb;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    if (int r = stream_attn_fill("m2f_attention_stream_chunk_paged", sb, &pg, S, true, T, H, hd, q, ldq, k, ldk, v, ldv, kpool, vpool, C, ring, count, n_new, out, ldo, bf16)) return r;
-    M2F_HIP(m2f_launch_attn_stream_chunk(sb, &pg, T, n_new, static_cast<hipStream_t>(stream)));
-    return 0;
+int m2f_attention_opts_layout(int which, int* out, int max) {
+    const std::vector<int> a = {(int)sizeof(m2f_attn_opts), (int)offsetof(m2f_attn_opts, past), (int)offsetof(m2f_attn_opts, future),
+                                (int)offsetof(m2f_attn_opts, bias_gain), (int)offsetof(m2f_attn_opts, n_same), (int)offsetof(m2f_attn_opts, n_other),
+                                (int)offsetof(m2f_attn_opts, speakers)};
+    const std::vector<int> s = {(int)sizeof(m2f_attn_stream_opts), (int)offsetof(m2f_attn_stream_opts, table), (int)offsetof(m2f_attn_stream_opts, table_cols),
+                                (int)offsetof(m2f_attn_stream_opts, n_pages), (int)offsetof(m2f_attn_stream_opts, page_rows),
+                                (int)offsetof(m2f_attn_stream_opts, weights), (int)offsetof(m2f_attn_stream_opts, bias_gain),
+                                (int)offsetof(m2f_attn_stream_opts, n_same), (int)offsetof(m2f_attn_stream_opts, n_other),
+                                (int)offsetof(m2f_attn_stream_opts, spk_cache), (int)offsetof(m2f_attn_stream_opts, spk_new)};
+    if (which != 0 && which != 1) { fail("m2f_attention_opts_layout: which must be 0 (m2f_attn_opts) or 1 (m2f_attn_stream_opts)"); return -1; }
+    const std::vector<int>& v = which ? s : a;
+    for (int i = 0; i < (int)v.size() && i < max && out; ++i) out[i] = v[i];
+    return (int)v.size();
 }
 
-static int stream_cache_site(const char* who, int S, int H, int hd, void* kc, void* vc, int C, int bf16, const AttnStreamPaging* pg, int n_entries,
-                             const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
-                             int32_t* count, int scatter, m2f_stream_t stream) {
+static int stream_cache_site(const char* who, int S, int H, int hd, void* kc, void* vc, const int32_t* table, int table_cols, int n_pages, int page_rows,
+                             int C, int bf16, int n_entries, const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
+                             int64_t packed_elems, int32_t* count, int scatter, m2f_stream_t stream) {
     const std::string w(who);
-    if (!pg) {
+    const AttnStreamPaging paging = {table, table_cols, page_rows, 0, n_pages}, *pg = table ? &paging : nullptr;
+    if (pg) {
+        if (int r = paged_args_ok(who, S, H, hd, C, n_pages, page_rows, table_cols, kc, vc, table)) return r;
+    } else {
         if (S < 1 || H < 1 || hd < 1 || hd > 128 || C < 1 || C > M2F_ATTN_STREAM_MAX_C) return fail(w + ": S, H >= 1, 1 <= hd <= 128, 1 <= C <= 512 required");
         if (!kc || !vc) return fail(w + ": NULL argument");
         if ((reinterpret_cast<uintptr_t>(kc) & 15) || (reinterpret_cast<uintptr_t>(vc) & 15)) return fail(w + ": the caches must be 16-byte aligned");
@@ -506,37 +375,20 @@ static int stream_cache_site(const char* who, int S, int H, int hd, void* kc, vo
     M2F_HIP(m2f_launch_stream_cache(cb, pg, scatter, static_cast<hipStream_t>(stream)));
     return 0;
 }
-int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, int C, int bf16, int n_entries,
-                                      const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, void* packed,
-                                      int64_t packed_elems, m2f_stream_t stream) {
-    return stream_cache_site("m2f_attention_stream_cache_gather", S, H, hd, const_cast<void*>(kcache), const_cast<void*>(vcache), C, bf16, nullptr,
-                             n_entries, slots, lengths, row_offsets, packed, packed_elems, nullptr, 0, stream);
+int m2f_attention_stream_cache_gather(int S, int H, int hd, const void* kcache, const void* vcache, const int32_t* table, int table_cols,
+                                      int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                      const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
+                                      m2f_stream_t stream) {
+    return stream_cache_site("m2f_attention_stream_cache_gather", S, H, hd, const_cast<void*>(kcache), const_cast<void*>(vcache), table, table_cols,
+                             n_pages, page_rows, C, bf16, n_entries, slots, lengths, row_offsets, packed, packed_elems, nullptr, 0, stream);
 }
-int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, int C, int bf16, int n_entries,
-                                       const int32_t* slots, const int32_t* lengths, const int64_t* row_offsets, const void* packed,
-                                       int64_t packed_elems, int32_t* count, m2f_stream_t stream) {
-    return stream_cache_site("m2f_attention_stream_cache_scatter", S, H, hd, kcache, vcache, C, bf16, nullptr, n_entries, slots, lengths, row_offsets,
-                             const_cast<void*>(packed), packed_elems, count, 1, stream);
+int m2f_attention_stream_cache_scatter(int S, int H, int hd, void* kcache, void* vcache, const int32_t* table, int table_cols,
+                                       int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
+                                       const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
+                                       int32_t* count, m2f_stream_t stream) {
+    return stream_cache_site("m2f_attention_stream_cache_scatter", S, H, hd, kcache, vcache, table, table_cols, n_pages, page_rows, C, bf16,
+                             n_entries, slots, lengths, row_offsets, const_cast<void*>(packed), packed_elems, count, 1, stream);
 }
-int m2f_attention_stream_cache_gather_paged(int S, int H, int hd, const void* kpool, const void* vpool, const int32_t* table, int table_cols,
-                                            int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
-                                            const int32_t* lengths, const int64_t* row_offsets, void* packed, int64_t packed_elems,
-                                            m2f_stream_t stream) {
-    if (int r = paged_args_ok("m2f_attention_stream_cache_gather_paged", S, H, hd, C, n_pages, page_rows, table_cols, kpool, vpool, table)) return r;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    return stream_cache_site("m2f_attention_stream_cache_gather_paged", S, H, hd, const_cast<void*>(kpool), const_cast<void*>(vpool), C, bf16, &pg,
-                             n_entries, slots, lengths, row_offsets, packed, packed_elems, nullptr, 0, stream);
-}
-int m2f_attention_stream_cache_scatter_paged(int S, int H, int hd, void* kpool, void* vpool, const int32_t* table, int table_cols,
-                                             int n_pages, int page_rows, int C, int bf16, int n_entries, const int32_t* slots,
-                                             const int32_t* lengths, const int64_t* row_offsets, const void* packed, int64_t packed_elems,
-                                             int32_t* count, m2f_stream_t stream) {
-    if (int r = paged_args_ok("m2f_attention_stream_cache_scatter_paged", S, H, hd, C, n_pages, page_rows, table_cols, kpool, vpool, table)) return r;
-    const AttnStreamPaging pg = {table, table_cols, page_rows, 0, n_pages};
-    return stream_cache_site("m2f_attention_stream_cache_scatter_paged", S, H, hd, kpool, vpool, C, bf16, &pg, n_entries, slots, lengths, row_offsets,
-                             const_cast<void*>(packed), packed_elems, count, 1, stream);
-}
-
 int m2f_attention_weights(int B, int L, int H, const float* probs, const uint8_t* key_pad, const int32_t* cu, int past, int future,
                           int per_head, float* out, m2f_stream_t stream) {
     if (B < 1 || H < 1 || L < 1 || L > M2F_ATTN_DLONG_MAX_L) return fail("m2f_attention_weights: B, H >= 1 and 1 <= L <= 512 required");

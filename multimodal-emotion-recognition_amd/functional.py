@@ -6,6 +6,7 @@ dimensions, so column slices of a wider matrix are legal operands.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -105,20 +106,25 @@ def quantize_fp8(src: torch.Tensor, scale: float, out: Optional[torch.Tensor] = 
     return dst
 
 
-def _speaker_args(who: str, speakers, speaker_heads, H: int, rows: int, device):
-    """(ids uint8 [rows] on `device`, n_same, n_other) of a kernel-level call, or (None, 0, 0) when speaker_heads is None - the call
-    without the argument.  Raises ValueError before anything is launched."""
+def _attn_opts(who: str, H: int, rows: int, device, past, future, bias, speakers, speaker_heads) -> runtime.AttnOptsC:
+    """The m2f_attn_opts of a forward launch of `rows` token rows: band, gain as applied, speaker heads with their ids (uint8 [rows] on
+    `device`, kept alive by the descriptor).  Every option at None is the launch without it.  Raises ValueError before anything is
+    launched."""
+    o = runtime.AttnOptsC()
+    o.bias_gain = runtime.position_bias(bias)
     heads = runtime.speaker_heads(speaker_heads, {"this launch": H})
     if heads is None:
         if speakers is not None:
             raise ValueError(f"{who}: speakers were given without speaker_heads=(n_same, n_other)")
-        return None, 0, 0
-    if speakers is None:
-        raise ValueError(f"{who}: speaker_heads={heads} needs speakers (one id per utterance)")
-    ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
-    if ids.numel() != rows:
-        raise ValueError(f"{who}: speakers must hold one id per token row ({rows}), got {ids.numel()}")
-    return ids, heads[0], heads[1]
+    else:
+        if speakers is None:
+            raise ValueError(f"{who}: speaker_heads={heads} needs speakers (one id per utterance)")
+        o.ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
+        if o.ids.numel() != rows:
+            raise ValueError(f"{who}: speakers must hold one id per token row ({rows}), got {o.ids.numel()}")
+        o.n_same, o.n_other, o.speakers = heads[0], heads[1], ptr(o.ids)
+    o.past, o.future = runtime.context_band(past, future)
+    return o
 
 
 speaker_head_class = runtime.speaker_head_class      # (the library's own statement of the rule: csrc/ops.h, m2f_attn_speaker_class)
@@ -140,30 +146,15 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: to
     bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): a visible key's
     score gets -slope(h, H, gain) * |i - j|, the gain applied as `runtime.position_bias` rounds it.  The backward (`attention_bwd`) reads the saved probabilities and takes no gain."""
     runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
+    opts = _attn_opts("attention_fwd", H, B * L, q.device, past, future, bias, speakers, speaker_heads)
     E = q.shape[1]
     hd = E // H
     out = torch.empty(B * L, E, dtype=torch.float32, device=q.device)
     Lp = 16 * ((L + 15) // 16)
     probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     kp = key_pad.to(torch.uint8).contiguous()
-    ids, n_same, n_other = _speaker_args("attention_fwd", speakers, speaker_heads, H, B * L, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_fwd_speakers(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                               _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                               *runtime.context_band(past, future), gain, ptr(ids), n_same, n_other),
-              "m2f_attention_fwd_speakers")
-    elif gain != 0.0:
-        check(lib().m2f_attention_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                           _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                           *runtime.context_band(past, future), gain), "m2f_attention_fwd_bias")
-    elif past is None and future is None:
-        check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                      _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_fwd")
-    else:
-        check(lib().m2f_attention_fwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                           _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                           *runtime.context_band(past, future)), "m2f_attention_fwd_band")
+    check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out), _ld(out), ptr(probs),
+                                  drop_site, drop_p, ptr(rng), stream_ptr(), ctypes.byref(opts)), "m2f_attention_fwd")
     return out, probs
 
 
@@ -279,22 +270,71 @@ def attention_stream_caches(S: int, H: int, hd: int, capacity: int, bf16: bool =
     return tuple(torch.full((S, H, capacity, hdp), fill, dtype=dt, device=device) for _ in range(2))
 
 
-def _stream_speaker_args(who: str, speakers, speaker_cache, speaker_heads, H: int, S: int, C: int, per_slot: int, device):
-    """(new ids uint8 [S * per_slot], cached ids uint8 [S, C], n_same, n_other) of a streaming launch, or (None, None, 0, 0)."""
+def _stream_opts(who: str, H: int, S: int, C: int, per_slot: int, device, bf16: bool, kc, vc, table, weights, bias, speakers,
+                 speaker_cache, speaker_heads) -> runtime.AttnStreamOptsC:
+    """The m2f_attn_stream_opts of a step (per_slot = 1) or chunk (per_slot = T) launch over S slots of capacity C, after the checks
+    that need tensors (sizes and alignment are the library's to refuse): kc / vc are dense caches (table None) or page pools, weights
+    the step's [S, H, C] rows of probabilities, bias the gain, speakers the new utterances' ids (uint8 [S * per_slot] on `device`, kept
+    alive by the descriptor) beside the cached ones.  Raises ValueError before anything is launched."""
+    o = runtime.AttnStreamOptsC()
+    o.bias_gain = runtime.position_bias(bias)
+    want = torch.bfloat16 if bf16 else torch.float32
+    if table is not None:
+        o.n_pages, o.page_rows = _paged_args(who, kc, vc, table, S, C, bf16)
+        o.table, o.table_cols = ptr(table), table.shape[1]
+    elif kc.dtype != want or vc.dtype != want or not kc.is_contiguous() or not vc.is_contiguous():
+        raise ValueError(f"{who}: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (S, H, C) or not weights.is_contiguous():
+            raise ValueError(f"{who}: weights must be a contiguous fp32 [S, H, capacity] = [{S}, {H}, {C}] tensor")
+        o.weights = ptr(weights)
     heads = runtime.speaker_heads(speaker_heads, {"this launch": H})
     if heads is None:
         if speakers is not None or speaker_cache is not None:
             raise ValueError(f"{who}: speakers / speaker_cache were given without speaker_heads=(n_same, n_other)")
-        return None, None, 0, 0
+        return o
     if speakers is None or speaker_cache is None:
         raise ValueError(f"{who}: speaker_heads={heads} needs speakers (the new utterances' ids) and speaker_cache (uint8 [S, capacity])")
     if (not isinstance(speaker_cache, torch.Tensor) or speaker_cache.dtype != torch.uint8 or tuple(speaker_cache.shape) != (S, C)
             or not speaker_cache.is_contiguous() or speaker_cache.device != device):
         raise ValueError(f"{who}: speaker_cache must be a contiguous uint8 [{S}, {C}] tensor on the launch's device")
-    ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
-    if ids.numel() != S * per_slot:
-        raise ValueError(f"{who}: speakers must hold {S * per_slot} ids, got {ids.numel()}")
-    return ids, speaker_cache, heads[0], heads[1]
+    o.ids = runtime.speaker_ids(speakers, f"{who}: speakers").reshape(-1).contiguous().to(device)
+    if o.ids.numel() != S * per_slot:
+        raise ValueError(f"{who}: speakers must hold {S * per_slot} ids, got {o.ids.numel()}")
+    o.n_same, o.n_other, o.spk_cache, o.spk_new = heads[0], heads[1], ptr(speaker_cache), ptr(o.ids)
+    return o
+
+
+def _stream_step(who: str, q, k, v, kc, vc, table, C: int, lengths, active, H: int, ring, bf16, weights, bias, speakers, speaker_cache,
+                 speaker_heads) -> torch.Tensor:
+    """`attention_stream` / `attention_stream_paged`: kc / vc are the caches (table None) or the pools of capacity C."""
+    runtime.require_gpu()
+    S, E = q.shape
+    opts = _stream_opts(who, H, S, C, 1, q.device, bf16, kc, vc, table, weights, bias, speakers, speaker_cache, speaker_heads)
+    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
+        raise ValueError(f"{who}: lengths int32 [S] and active [S] required")
+    act = active.to(torch.uint8).contiguous()
+    out = torch.empty(S, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream(S, H, E // H, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kc), ptr(vc), C, int(ring), ptr(lengths),
+                                     ptr(act), ptr(out), _ld(out), int(bf16), stream_ptr(), ctypes.byref(opts)), "m2f_attention_stream")
+    return out
+
+
+def _stream_chunk(who: str, q, k, v, kc, vc, table, S: int, C: int, lengths, new, H: int, T: int, ring, bf16, bias, speakers, speaker_cache,
+                  speaker_heads) -> torch.Tensor:
+    """`attention_stream_chunk` / `attention_stream_chunk_paged`: kc / vc are the caches (table None) or the pools of capacity C."""
+    runtime.require_gpu()
+    rows, E = q.shape
+    opts = _stream_opts(who, H, S, C, T, q.device, bf16, kc, vc, table, None, bias, speakers, speaker_cache, speaker_heads)
+    if not 1 <= T <= 64 or rows != S * T or k.shape[0] != rows or v.shape[0] != rows:
+        raise ValueError(f"{who}: q / k / v hold S * T rows, 1 <= T <= 64")
+    if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S:
+        raise ValueError(f"{who}: lengths int32 [S] and new int32 [S] required")
+    out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
+    check(lib().m2f_attention_stream_chunk(S, T, H, E // H, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kc), ptr(vc), C, int(ring),
+                                           ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), stream_ptr(), ctypes.byref(opts)),
+          "m2f_attention_stream_chunk")
+    return out
 
 
 def stream_advance_speakers(lengths: torch.Tensor, active: torch.Tensor, speaker_cache: torch.Tensor, speakers: torch.Tensor,
@@ -338,7 +378,7 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
     (read, NOT advanced); active uint8 / bool [S].  An active slot stores its new K / V rows at row lengths % capacity (ring) or
     lengths (lengths < capacity required) and gets softmax(q K^T / sqrt(hd)) V over its min(lengths + 1, capacity) live rows; an
     inactive slot gets a zero row and its caches stay as they are.  Returns out [S, H*hd].
-    weights: a contiguous fp32 [S, H, capacity] tensor - the launch (m2f_attention_stream_weights, the weights-emitting form of the
+    weights: a contiguous fp32 [S, H, capacity] tensor - the launch (m2f_attn_stream_opts::weights, the weights-emitting form of the
     kernel) also fills it with each slot's row of attention probabilities in logical order: column t = the t-th oldest live utterance
     (`streaming.logical_columns`), the last live column the new one; zeros behind the live count and for inactive slots.  Same `out`, same bits.
     bias: gain of the distance-decay bias (`position_bias_slopes`; None or 0 = off, the entries called without it): the new utterance
@@ -347,44 +387,8 @@ def attention_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: 
     speaker_cache: uint8 [S, capacity], the cached utterances' ids by logical cache row, READ only (`stream_advance_speakers` stores
     the new ids and advances `lengths`); an other-speaker head with no other speaker in sight gives a zero row.  speaker_heads=None is
     the call without the arguments."""
-    runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
-    S, E = q.shape
-    hd = E // H
-    C = kcache.shape[2]
-    _stream_weights_ok("attention_stream", weights, S, H, C)
-    want = torch.bfloat16 if bf16 else torch.float32
-    if kcache.dtype != want or vcache.dtype != want or not kcache.is_contiguous() or not vcache.is_contiguous():
-        raise ValueError("attention_stream: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
-    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
-        raise ValueError("attention_stream: lengths int32 [S] and active [S] required")
-    act = active.to(torch.uint8).contiguous()
-    out = torch.empty(S, E, dtype=torch.float32, device=q.device)
-    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream", speakers, speaker_cache, speaker_heads, H, S, C, 1, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_stream_speakers(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None, 0, 0,
-                                                  0, C, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights), gain,
-                                                  ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()), "m2f_attention_stream_speakers")
-        return out
-    if gain != 0.0:
-        check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None, 0, 0, 0,
-                                              C, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights), gain,
-                                              stream_ptr()), "m2f_attention_stream_bias")
-        return out
-    if weights is not None:
-        check(lib().m2f_attention_stream_weights(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C,
-                                                 int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), ptr(weights),
-                                                 stream_ptr()), "m2f_attention_stream_weights")
-        return out
-    check(lib().m2f_attention_stream(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
-                                     ptr(lengths), ptr(act), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream")
-    return out
-
-
-def _stream_weights_ok(who: str, weights, S: int, H: int, C: int) -> None:
-    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (S, H, C)
-                                or not weights.is_contiguous()):
-        raise ValueError(f"{who}: weights must be a contiguous fp32 [S, H, capacity] = [{S}, {H}, {C}] tensor")
+    return _stream_step("attention_stream", q, k, v, kcache, vcache, None, kcache.shape[2], lengths, active, H, ring, bf16, weights, bias,
+                        speakers, speaker_cache, speaker_heads)
 
 
 def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
@@ -401,33 +405,8 @@ def attention_stream_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kc
     speaker_cache: uint8 [S, capacity], the cached utterances' ids by logical cache row, READ only (`stream_advance_speakers_n` stores
     the new ids and advances `lengths`); an other-speaker head with no other speaker in sight gives a zero row.  speaker_heads=None is
     the call without the arguments."""
-    runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
-    rows, E = q.shape
-    hd = E // H
-    S, C = kcache.shape[0], kcache.shape[2]
-    want = torch.bfloat16 if bf16 else torch.float32
-    if kcache.dtype != want or vcache.dtype != want or not kcache.is_contiguous() or not vcache.is_contiguous():
-        raise ValueError("attention_stream_chunk: the caches must be contiguous " + ("bfloat16" if bf16 else "float32") + " tensors")
-    if not 1 <= T <= 64 or rows != S * T or k.shape[0] != rows or v.shape[0] != rows:
-        raise ValueError("attention_stream_chunk: q / k / v hold S * T rows, 1 <= T <= 64")
-    if lengths.dtype != torch.int32 or lengths.numel() != S or new.dtype != torch.int32 or new.numel() != S:
-        raise ValueError("attention_stream_chunk: lengths int32 [S] and new int32 [S] required")
-    out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
-    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_chunk", speakers, speaker_cache, speaker_heads, H, S, C, T, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_stream_chunk_speakers(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None,
-                                                        0, 0, 0, C, int(ring), ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), gain,
-                                                        ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()), "m2f_attention_stream_chunk_speakers")
-        return out
-    if gain != 0.0:
-        check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), None,
-                                                    0, 0, 0, C, int(ring), ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), gain,
-                                                    stream_ptr()), "m2f_attention_stream_chunk_bias")
-        return out
-    check(lib().m2f_attention_stream_chunk(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kcache), ptr(vcache), C, int(ring),
-                                           ptr(lengths), ptr(new), ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk")
-    return out
+    return _stream_chunk("attention_stream_chunk", q, k, v, kcache, vcache, None, kcache.shape[0], kcache.shape[2], lengths, new, H, T, ring,
+                         bf16, bias, speakers, speaker_cache, speaker_heads)
 
 
 def attention_stream_pools(n_pages: int, H: int, hd: int, page_rows: int = 16, bf16: bool = False, device="cuda", fill: float = 0.0):
@@ -458,45 +437,15 @@ def attention_stream_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kp
                            bf16: bool = False, weights: Optional[torch.Tensor] = None, bias: Optional[float] = None,
                            speakers: Optional[torch.Tensor] = None, speaker_cache: Optional[torch.Tensor] = None,
                            speaker_heads=None) -> torch.Tensor:
-    """`attention_stream` over page pools (m2f_attention_stream_paged): logical cache row r of slot s - the row `attention_stream` calls r -
+    """`attention_stream` over page pools (m2f_attn_stream_opts::table): logical cache row r of slot s - the row `attention_stream` calls r -
     is row r % page_rows of page table[s, r // page_rows].  kpool / vpool: `attention_stream_pools`; table int32 [S, ceil(capacity /
     page_rows)], read only at the entries of pages that hold a live row or take the new one.  The same bits as `attention_stream` on
     caches holding the same rows.  A refused argument raises before anything is launched.  Returns out [S, H*hd].
-    weights: as `attention_stream` (m2f_attention_stream_weights_paged) - the order is logical, so the rows are the dense launch's bits.
+    weights: as `attention_stream` - the order is logical, so the rows are the dense launch's bits.
     bias: as `attention_stream`.  speakers / speaker_cache / speaker_heads: as `attention_stream` - speaker_cache stays the dense
     uint8 [S, capacity] array (logical rows: the page table never enters)."""
-    runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
-    S, E = q.shape
-    hd = E // H
-    n_pages, R = _paged_args("attention_stream_paged", kpool, vpool, table, S, capacity, bf16)
-    _stream_weights_ok("attention_stream_paged", weights, S, H, capacity)
-    if lengths.dtype != torch.int32 or lengths.numel() != S or active.numel() != S:
-        raise ValueError("attention_stream_paged: lengths int32 [S] and active [S] required")
-    act = active.to(torch.uint8).contiguous()
-    out = torch.empty(S, E, dtype=torch.float32, device=q.device)
-    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_paged", speakers, speaker_cache, speaker_heads, H, S, capacity, 1, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_stream_speakers(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
-                                                  table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
-                                                  int(bf16), ptr(weights), gain, ptr(spk_c), ptr(ids), n_same, n_other, stream_ptr()),
-              "m2f_attention_stream_speakers")
-        return out
-    if gain != 0.0:
-        check(lib().m2f_attention_stream_bias(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
-                                              table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
-                                              int(bf16), ptr(weights), gain, stream_ptr()), "m2f_attention_stream_bias")
-        return out
-    if weights is not None:
-        check(lib().m2f_attention_stream_weights_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
-                                                       ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act),
-                                                       ptr(out), _ld(out), int(bf16), ptr(weights), stream_ptr()),
-              "m2f_attention_stream_weights_paged")
-        return out
-    check(lib().m2f_attention_stream_paged(S, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool), ptr(table),
-                                           table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(act), ptr(out), _ld(out),
-                                           int(bf16), stream_ptr()), "m2f_attention_stream_paged")
-    return out
+    return _stream_step("attention_stream_paged", q, k, v, kpool, vpool, table, capacity, lengths, active, H, ring, bf16, weights, bias,
+                        speakers, speaker_cache, speaker_heads)
 
 
 def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
@@ -504,36 +453,11 @@ def attention_stream_chunk_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
                                  ring: bool = False, bf16: bool = False, bias: Optional[float] = None,
                                  speakers: Optional[torch.Tensor] = None, speaker_cache: Optional[torch.Tensor] = None,
                                  speaker_heads=None) -> torch.Tensor:
-    """`attention_stream_chunk` over page pools (m2f_attention_stream_chunk_paged; layout: `attention_stream_paged`).  q / k / v hold
+    """`attention_stream_chunk` over page pools (m2f_attn_stream_opts::table; layout: `attention_stream_paged`).  q / k / v hold
     S * T rows, S = table.shape[0].  The same bits, output and stored rows, as the dense chunk launch.  Returns out [S*T, H*hd].
     bias: as `attention_stream_chunk`.  speakers / speaker_cache / speaker_heads: as `attention_stream_chunk`."""
-    runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
-    rows, E = q.shape
-    hd = E // H
-    S = lengths.numel()
-    n_pages, R = _paged_args("attention_stream_chunk_paged", kpool, vpool, table, S, capacity, bf16)
-    if not 1 <= T <= 64 or rows != S * T or k.shape[0] != rows or v.shape[0] != rows:
-        raise ValueError("attention_stream_chunk_paged: q / k / v hold S * T rows, 1 <= T <= 64")
-    if lengths.dtype != torch.int32 or new.dtype != torch.int32 or new.numel() != S:
-        raise ValueError("attention_stream_chunk_paged: lengths int32 [S] and new int32 [S] required")
-    out = torch.empty(rows, E, dtype=torch.float32, device=q.device)
-    ids, spk_c, n_same, n_other = _stream_speaker_args("attention_stream_chunk_paged", speakers, speaker_cache, speaker_heads, H, S, capacity, T, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_stream_chunk_speakers(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
-                                                        ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
-                                                        ptr(out), _ld(out), int(bf16), gain, ptr(spk_c), ptr(ids), n_same, n_other,
-                                                        stream_ptr()), "m2f_attention_stream_chunk_speakers")
-        return out
-    if gain != 0.0:
-        check(lib().m2f_attention_stream_chunk_bias(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
-                                                    ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
-                                                    ptr(out), _ld(out), int(bf16), gain, stream_ptr()), "m2f_attention_stream_chunk_bias")
-        return out
-    check(lib().m2f_attention_stream_chunk_paged(S, T, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kpool), ptr(vpool),
-                                                 ptr(table), table.shape[1], n_pages, R, capacity, int(ring), ptr(lengths), ptr(new),
-                                                 ptr(out), _ld(out), int(bf16), stream_ptr()), "m2f_attention_stream_chunk_paged")
-    return out
+    return _stream_chunk("attention_stream_chunk_paged", q, k, v, kpool, vpool, table, lengths.numel(), capacity, lengths, new, H, T, ring,
+                         bf16, bias, speakers, speaker_cache, speaker_heads)
 
 
 def _stream_cache_move(who: str, scatter: bool, kcache, vcache, hd: int, slots, lengths, row_offsets, packed, count, table, capacity, bf16):
@@ -553,26 +477,22 @@ def _stream_cache_move(who: str, scatter: bool, kcache, vcache, hd: int, slots, 
     H = kcache.shape[1]
     tail = (ptr(count), stream_ptr()) if scatter else (stream_ptr(),)
     if table is None:
-        S, C = kcache.shape[0], kcache.shape[2]
-        if scatter and count.numel() != S:
-            raise ValueError(f"{who}: count int32 [S] required")
-        fn = lib().m2f_attention_stream_cache_scatter if scatter else lib().m2f_attention_stream_cache_gather
-        check(fn(S, H, hd, ptr(kcache), ptr(vcache), C, int(bf16), n, ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed), packed.numel(),
-                 *tail), who)
-        return
-    S = table.shape[0] if table.dim() == 2 else -1
-    n_pages, R = _paged_args(who, kcache, vcache, table, S, capacity, bf16)
+        S, C, paging = kcache.shape[0], kcache.shape[2], (None, 0, 0, 0)
+    else:
+        S, C = table.shape[0] if table.dim() == 2 else -1, capacity
+        n_pages, R = _paged_args(who, kcache, vcache, table, S, capacity, bf16)
+        paging = (ptr(table), table.shape[1], n_pages, R)
     if scatter and count.numel() != S:
         raise ValueError(f"{who}: count int32 [S] required")
-    fn = lib().m2f_attention_stream_cache_scatter_paged if scatter else lib().m2f_attention_stream_cache_gather_paged
-    check(fn(S, H, hd, ptr(kcache), ptr(vcache), ptr(table), table.shape[1], n_pages, R, capacity, int(bf16), n, ptr(slots), ptr(lengths),
-             ptr(row_offsets), ptr(packed), packed.numel(), *tail), who)
+    fn = lib().m2f_attention_stream_cache_scatter if scatter else lib().m2f_attention_stream_cache_gather
+    check(fn(S, H, hd, ptr(kcache), ptr(vcache), *paging, C, int(bf16), n, ptr(slots), ptr(lengths), ptr(row_offsets), ptr(packed),
+             packed.numel(), *tail), who)
 
 
 def attention_stream_cache_gather(kcache: torch.Tensor, vcache: torch.Tensor, hd: int, slots: torch.Tensor, lengths: torch.Tensor,
                                   row_offsets: torch.Tensor, packed: torch.Tensor, table: Optional[torch.Tensor] = None,
                                   capacity: Optional[int] = None, bf16: bool = False) -> torch.Tensor:
-    """One site's live cache rows -> `packed` (m2f_attention_stream_cache_gather[_paged], csrc/stream_cache.hip): entry e holds the
+    """One site's live cache rows -> `packed` (m2f_attention_stream_cache_gather, csrc/stream_cache.hip): entry e holds the
     min(lengths[e], capacity) physical rows 0 .. of slot slots[e] as [K, V][H][rows][pad(hd)] at element row_offsets[e] * 2 * H * pad(hd).
     kcache / vcache: `attention_stream_caches`, or with `table` (int32 [S, ceil(capacity / page_rows)]) and `capacity` the pools of
     `attention_stream_pools`.  slots, lengths int32 [n], row_offsets int64 [n] on the device.  Returns packed."""
@@ -583,7 +503,7 @@ def attention_stream_cache_gather(kcache: torch.Tensor, vcache: torch.Tensor, hd
 def attention_stream_cache_scatter(kcache: torch.Tensor, vcache: torch.Tensor, hd: int, slots: torch.Tensor, lengths: torch.Tensor,
                                    row_offsets: torch.Tensor, packed: torch.Tensor, count: torch.Tensor, table: Optional[torch.Tensor] = None,
                                    capacity: Optional[int] = None, bf16: bool = False) -> None:
-    """The reverse of `attention_stream_cache_gather` (m2f_attention_stream_cache_scatter[_paged]): `packed` -> the rows
+    """The reverse of `attention_stream_cache_gather` (m2f_attention_stream_cache_scatter): `packed` -> the rows
     0 .. min(lengths[e], capacity) - 1 of slot slots[e], and count[slots[e]] = lengths[e]; nothing else is written."""
     _stream_cache_move("attention_stream_cache_scatter", True, kcache, vcache, hd, slots, lengths, row_offsets, packed, count, table, capacity, bf16)
 
@@ -597,15 +517,10 @@ def attention_bwd(q, k, v, key_pad, out, probs, dout, B: int, L: int, H: int, dr
     hd = E // H
     dq, dk, dv = (torch.zeros(B * L, E, dtype=torch.float32, device=q.device) for _ in range(3))
     kp = key_pad.to(torch.uint8).contiguous()
-    if past is None and future is None:
-        check(lib().m2f_attention_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                      _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
-                                      ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()), "m2f_attention_bwd")
-    else:
-        check(lib().m2f_attention_bwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
-                                           _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
-                                           ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                           *runtime.context_band(past, future)), "m2f_attention_bwd_band")
+    check(lib().m2f_attention_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp), ptr(out),
+                                  _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk),
+                                  ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                  *runtime.context_band(past, future)), "m2f_attention_bwd")
     return dq, dk, dv
 
 
@@ -634,8 +549,8 @@ def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: i
     speakers / speaker_heads: as `attention_fwd` - speakers holds one id per TOKEN ROW, in the rows' order ([T]; padded rows: [B, L]).
     No block pair is skipped on their account: every element of a visited block is written, a hidden one as 0."""
     runtime.require_gpu()
-    gain = runtime.position_bias(bias)                  # (raises ValueError)
     T, E = q.shape
+    opts = _attn_opts("attention_varlen_fwd", H, T, q.device, past, future, bias, speakers, speaker_heads)
     hd = E // H
     cu32, kp = _varlen_rows(cu, key_pad)
     out = torch.empty(T, E, dtype=torch.float32, device=q.device)
@@ -643,24 +558,8 @@ def attention_varlen_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: i
     if probs is None:
         probs = torch.zeros(B * H, Lp, Lp, dtype=torch.float32, device=q.device)
     assert probs.shape == (B * H, Lp, Lp) and probs.is_contiguous() and probs.dtype == torch.float32 and probs.is_cuda
-    ids, n_same, n_other = _speaker_args("attention_varlen_fwd", speakers, speaker_heads, H, T, q.device)
-    if ids is not None:
-        check(lib().m2f_attention_varlen_fwd_speakers(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                                      ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                                      *runtime.context_band(past, future), gain, ptr(ids), n_same, n_other),
-              "m2f_attention_varlen_fwd_speakers")
-    elif gain != 0.0:
-        check(lib().m2f_attention_varlen_fwd_bias(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                                  ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                                  *runtime.context_band(past, future), gain), "m2f_attention_varlen_fwd_bias")
-    elif past is None and future is None:
-        check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                             ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr()),
-              "m2f_attention_varlen_fwd")
-    else:
-        check(lib().m2f_attention_varlen_fwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                                  ptr(out), _ld(out), ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                                  *runtime.context_band(past, future)), "m2f_attention_varlen_fwd_band")
+    check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp), ptr(out), _ld(out),
+                                         ptr(probs), drop_site, drop_p, ptr(rng), stream_ptr(), ctypes.byref(opts)), "m2f_attention_varlen_fwd")
     return out, probs
 
 
@@ -675,16 +574,10 @@ def attention_varlen_bwd(q, k, v, out, probs, dout, B: int, L: int, H: int, cu: 
     hd = E // H
     cu32, kp = _varlen_rows(cu, key_pad)
     dq, dk, dv = (torch.zeros(T, E, dtype=torch.float32, device=q.device) for _ in range(3))
-    if past is None and future is None:
-        check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                             ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
-                                             _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr()),
-              "m2f_attention_varlen_bwd")
-    else:
-        check(lib().m2f_attention_varlen_bwd_band(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
-                                                  ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
-                                                  _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
-                                                  *runtime.context_band(past, future)), "m2f_attention_varlen_bwd_band")
+    check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu32), T, ptr(kp),
+                                         ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk),
+                                         _ld(dk), ptr(dv), _ld(dv), drop_site, drop_p, ptr(rng), stream_ptr(),
+                                         *runtime.context_band(past, future)), "m2f_attention_varlen_bwd")
     return dq, dk, dv
 
 

@@ -49,6 +49,18 @@ def config_to_c(c: M2FConfig) -> M2FConfigC:
                       float(c.dropout), float(c.ln_eps))
 
 
+class AttnOptsC(ctypes.Structure):
+    """m2f_attn_opts: the options of m2f_attention_fwd / m2f_attention_varlen_fwd.  A zero-filled one is a band of width zero: always
+    set past / future (-1 = unlimited)."""
+    _fields_ = [("past", c_int), ("future", c_int), ("bias_gain", c_float), ("n_same", c_int), ("n_other", c_int), ("speakers", c_void_p)]
+
+
+class AttnStreamOptsC(ctypes.Structure):
+    """m2f_attn_stream_opts: the options of m2f_attention_stream / m2f_attention_stream_chunk (zero-filled = none)."""
+    _fields_ = [("table", c_void_p), ("table_cols", c_int), ("n_pages", c_int), ("page_rows", c_int), ("weights", c_void_p),
+                ("bias_gain", c_float), ("n_same", c_int), ("n_other", c_int), ("spk_cache", c_void_p), ("spk_new", c_void_p)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -115,55 +127,22 @@ SIGNATURES = {
                          c_void_p, c_int, c_int, c_int, c_int, c_uint32, c_float, c_void_p, c_int, c_void_p, c_void_p,
                          c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "m2f_attention_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                  c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
+                                  c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, ctypes.POINTER(AttnOptsC)]),
     "m2f_attention_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                  c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
+                                  c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
+    "m2f_attention_opts_layout": (c_int, [c_int, ctypes.POINTER(c_int), c_int]),
     "m2f_attention_probs_elems": (c_int64, [c_int, c_int, c_int]),
     "m2f_attention_weights": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "m2f_plan_attention_sites": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "m2f_plan_attention_weights": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "m2f_attention_fwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
-    "m2f_attention_bwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                       c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
-    "m2f_attention_varlen_fwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
-                                              c_int, c_int]),
-    "m2f_attention_varlen_bwd_band": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                              c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
     "m2f_plan_attention_band": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_get_attention_band": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "m2f_plan_attention_bias": (c_int, [c_void_p, c_float]),
     "m2f_plan_get_attention_bias": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
-    "m2f_attention_fwd_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                       c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int, c_float]),
-    "m2f_attention_varlen_fwd_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
-                                              c_int, c_int, c_float]),
-    "m2f_attention_stream_bias": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
-                                          c_void_p]),
-    "m2f_attention_stream_chunk_bias": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                                c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
-                                                c_void_p]),
     "m2f_plan_attention_speakers": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_get_attention_speakers": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "m2f_plan_stream_speakers": (c_int, [c_void_p, c_void_p]),
-    "m2f_attention_fwd_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                           c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int, c_float,
-                                           c_void_p, c_int, c_int]),
-    "m2f_attention_varlen_fwd_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                                  c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
-                                                  c_int, c_int, c_float, c_void_p, c_int, c_int]),
-    "m2f_attention_stream_speakers": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                              c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
-                                              c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "m2f_attention_stream_chunk_speakers": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
-                                                    c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_stream_advance_speakers": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_stream_advance_speakers_n": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_attention_speaker_class": (c_int, [c_int, c_int, c_int]),
@@ -174,12 +153,7 @@ SIGNATURES = {
     "m2f_stream_cache_bytes": (c_int64, [c_void_p]),
     "m2f_attention_stream_cache_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "m2f_attention_stream": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                     c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "m2f_attention_stream_weights": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                             c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "m2f_attention_stream_weights_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                                   c_void_p]),
+                                     c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(AttnStreamOptsC)]),
     "m2f_stream_attention_elems": (c_int64, [c_void_p]),
     "m2f_plan_stream_attention": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_stream_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -187,32 +161,25 @@ SIGNATURES = {
     "m2f_plan_create_stream_paged": (c_void_p, [ctypes.POINTER(M2FConfigC), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                                                 c_void_p]),
     "m2f_attention_stream_pool_elems": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "m2f_attention_stream_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "m2f_attention_stream_chunk_paged": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                                 c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "m2f_stream_snapshot_row_elems": (c_int64, [c_void_p]),
     "m2f_stream_snapshot_sites": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "m2f_stream_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_scatter": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "m2f_attention_stream_cache_gather": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p, c_int64, c_void_p]),
-    "m2f_attention_stream_cache_scatter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                   c_void_p, c_int64, c_void_p, c_void_p]),
-    "m2f_attention_stream_cache_gather_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "m2f_attention_stream_cache_scatter_paged": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "m2f_attention_stream_cache_gather": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "m2f_attention_stream_cache_scatter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "m2f_stream_chunk_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "m2f_plan_create_stream_chunk": (c_void_p, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "m2f_stream_prefill": (c_int, [c_void_p, c_int, c_void_p]),
     "m2f_attention_stream_chunk": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(AttnStreamOptsC)]),
     "m2f_attention_varlen_fwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p]),
+                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_uint32, c_float, c_void_p, c_void_p,
+                                         ctypes.POINTER(AttnOptsC)]),
     "m2f_attention_varlen_bwd": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                         c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p]),
+                                         c_void_p, c_int, c_void_p, c_int, c_uint32, c_float, c_void_p, c_void_p, c_int, c_int]),
     "m2f_set_shadow_map": (c_int, [c_void_p, c_void_p, c_int64]),
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
     "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),

@@ -182,10 +182,10 @@ def attn_run(L, hd, lengths, site, form):
     check(lib().m2f_set_shadow_map(ws.data_ptr(), sh.data_ptr(), ws.numel()), "m2f_set_shadow_map")
     try:
         check(lib().m2f_attention_fwd(B_ATT, L, H_ATT, hd, ptr(qd), ld, ptr(kd), ld, ptr(vd), ld, ptr(kp), ptr(out), ld, ptr(probs), site,
-                                      P_DROP if site else 0.0, ptr(rng) if site else None, stream_ptr()), "m2f_attention_fwd")
+                                      P_DROP if site else 0.0, ptr(rng) if site else None, stream_ptr(), None), "m2f_attention_fwd")
         check(lib().m2f_attention_bwd(B_ATT, L, H_ATT, hd, ptr(qd), ld, ptr(kd), ld, ptr(vd), ld, ptr(kp), ptr(out), ld, ptr(probs), ptr(dd),
                                       ld, ptr(dq), ld, ptr(dk), ld, ptr(dv), ld, site, P_DROP if site else 0.0, ptr(rng) if site else None,
-                                      stream_ptr()), "m2f_attention_bwd")
+                                      stream_ptr(), -1, -1), "m2f_attention_bwd")
         torch.cuda.synchronize()
     finally:
         check(lib().m2f_set_shadow_map(None, None, 0), "m2f_set_shadow_map")

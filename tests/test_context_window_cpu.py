@@ -1,6 +1,7 @@
 """Host side of the context band of the dialogue attention (M2FNet(context=(past, future))): the restatement the GPU tests take their
 reference values from (tests/golden/band_ref.py) against torch's own attn_mask= / src_mask= arguments, the runtime.context block of
 the config and src/train.py's check of it (raised before any GPU use), and that a model without a band keeps its plan keys."""
+import ctypes
 import os
 import sys
 
@@ -184,8 +185,22 @@ def test_default_plan_key_is_what_it_was():
 
 
 def test_new_entries_are_declared_and_exported():
+    """The plan-level entries, and the kernel-level entries that CARRY the band: the forward ones in m2f_attn_opts, the backward ones as
+    two plain arguments.  The per-feature entries (base name + "_band") are gone from the header, the bindings and the library."""
     header = open(runtime.HEADER_PATH).read()
-    for sym in ("m2f_attention_fwd_band", "m2f_attention_bwd_band", "m2f_attention_varlen_fwd_band", "m2f_attention_varlen_bwd_band",
-                "m2f_plan_attention_band", "m2f_plan_get_attention_band"):
+    carriers = ("m2f_attention_fwd", "m2f_attention_bwd", "m2f_attention_varlen_fwd", "m2f_attention_varlen_bwd")
+    for sym in carriers + ("m2f_plan_attention_band", "m2f_plan_get_attention_band"):
         assert sym in runtime.SIGNATURES and ("int " + sym + "(") in header, sym
         assert hasattr(runtime.lib(), sym), sym
+    struct = header[header.index("typedef struct m2f_attn_opts {"):header.index("} m2f_attn_opts;")]
+    fields = [n for n, _ in runtime.AttnOptsC._fields_]
+    assert "int past, future;" in struct and "past" in fields and "future" in fields
+    for sym in ("m2f_attention_fwd", "m2f_attention_varlen_fwd"):
+        assert runtime.SIGNATURES[sym][1][-1] is ctypes.POINTER(runtime.AttnOptsC), sym
+    for sym in ("m2f_attention_bwd", "m2f_attention_varlen_bwd"):
+        assert runtime.SIGNATURES[sym][1][-2:] == [ctypes.c_int, ctypes.c_int], sym
+        decl = header[header.index("int " + sym + "("):]
+        assert decl[:decl.index(");")].rstrip().endswith("int past, int future"), sym
+    for sym in carriers:
+        old = sym + "_band"
+        assert old not in runtime.SIGNATURES and old not in header and not hasattr(runtime.lib(), old), old

@@ -1,7 +1,8 @@
-"""Context band of the dialogue attention kernels (attention.hip for L <= 64, attention_dlong.hip above; the *_band C entries) against
+"""Context band of the dialogue attention kernels (attention.hip for L <= 64, attention_dlong.hip above; past / future of the C entries) against
 tests/golden/band_ref.py under autograd: out / probs / dq / dk / dv, exact zeros at hidden keys, the rows that see no key, the
 bf16-mode forms, block skipping over a probabilities buffer that holds another launch's values, blindness to the future bit for bit,
 and the unbanded entries unchanged."""
+import ctypes
 import itertools
 
 import pytest
@@ -306,7 +307,12 @@ def _ld(t):
     return t.stride(0)
 
 
-def _raw_short(q, k, v, kp, B, L, H, dout, band_entry):
+def _no_option():
+    """An m2f_attn_opts that states "no option" field by field (the header's M2F_ATTN_OPTS_NONE), where the plain launch passes NULL."""
+    return ctypes.byref(runtime.AttnOptsC(past=-1, future=-1, bias_gain=0.0, n_same=0, n_other=0, speakers=None))
+
+
+def _raw_short(q, k, v, kp, B, L, H, dout, stated):
     E = q.shape[1]
     hd = E // H
     Lp = 16 * ((L + 15) // 16)
@@ -314,17 +320,15 @@ def _raw_short(q, k, v, kp, B, L, H, dout, band_entry):
     probs = torch.zeros(B * H, Lp, Lp, device=DEV)
     dq, dk, dv = (torch.zeros(B * L, E, device=DEV) for _ in range(3))
     kp8 = kp.reshape(-1).to(torch.uint8).contiguous()
-    tail = (-1, -1) if band_entry else ()
-    fwd = lib().m2f_attention_fwd_band if band_entry else lib().m2f_attention_fwd
-    bwd = lib().m2f_attention_bwd_band if band_entry else lib().m2f_attention_bwd
-    check(fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp8), ptr(out), _ld(out), ptr(probs), 0, 0.0, None,
-              stream_ptr(), *tail), "forward")
-    check(bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp8), ptr(out), _ld(out), ptr(probs), ptr(dout), _ld(dout),
-              ptr(dq), _ld(dq), ptr(dk), _ld(dk), ptr(dv), _ld(dv), 0, 0.0, None, stream_ptr(), *tail), "backward")
+    check(lib().m2f_attention_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp8), ptr(out), _ld(out), ptr(probs), 0,
+                                  0.0, None, stream_ptr(), _no_option() if stated else None), "forward")
+    check(lib().m2f_attention_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kp8), ptr(out), _ld(out), ptr(probs),
+                                  ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk), ptr(dv), _ld(dv), 0, 0.0, None, stream_ptr(),
+                                  -1, -1), "backward")
     return out, probs, dq, dk, dv
 
 
-def _raw_long(c, band_entry):
+def _raw_long(c, stated):
     B, L, H, E, T = c["B"], c["L"], c["H"], c["E"], c["T"]
     hd = E // H
     Lp = 16 * ((L + 15) // 16)
@@ -334,17 +338,17 @@ def _raw_long(c, band_entry):
     dq, dk, dv = (torch.zeros(T, E, device=DEV) for _ in range(3))
     cu = c["kw"].get("cu")
     kp8 = None if cu is not None else c["key_pad"].reshape(-1).to(torch.uint8).contiguous()
-    tail = (-1, -1) if band_entry else ()
-    fwd = lib().m2f_attention_varlen_fwd_band if band_entry else lib().m2f_attention_varlen_fwd
-    bwd = lib().m2f_attention_varlen_bwd_band if band_entry else lib().m2f_attention_varlen_bwd
-    check(fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu), T, ptr(kp8), ptr(out), _ld(out), ptr(probs), 0, 0.0,
-              None, stream_ptr(), *tail), "forward")
-    check(bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu), T, ptr(kp8), ptr(out), _ld(out), ptr(probs), ptr(dout),
-              _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk), ptr(dv), _ld(dv), 0, 0.0, None, stream_ptr(), *tail), "backward")
+    check(lib().m2f_attention_varlen_fwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu), T, ptr(kp8), ptr(out), _ld(out),
+                                         ptr(probs), 0, 0.0, None, stream_ptr(), _no_option() if stated else None), "forward")
+    check(lib().m2f_attention_varlen_bwd(B, L, H, hd, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(cu), T, ptr(kp8), ptr(out), _ld(out),
+                                         ptr(probs), ptr(dout), _ld(dout), ptr(dq), _ld(dq), ptr(dk), _ld(dk), ptr(dv), _ld(dv), 0, 0.0, None,
+                                         stream_ptr(), -1, -1), "backward")
     return out, probs, dq, dk, dv
 
 
 def test_band_entries_without_a_band_equal_the_plain_entries():
+    """opts = NULL and an opts that states no option give equal bits: forward and, from each forward's probabilities, backward (which
+    takes the band as two plain arguments, (-1, -1) here); short and long, packed and padded."""
     B, L, H, hd = 2, 33, 4, 15
     E = H * hd
     q, k, v, dout = (_rand(B * L, E, seed=100 + i) for i in range(4))

@@ -3,6 +3,7 @@ values from (tests/golden/position_bias_ref.py) against torch's own float attn_m
 literal values of the recipe, gain validation and rounding, the plan keys, and the runtime.position_bias entry of the config with
 src/train.py's check of it (raised before any GPU use)."""
 import math
+import ctypes
 import os
 import sys
 
@@ -126,11 +127,21 @@ def test_default_plan_key_is_what_it_was_and_a_gain_has_its_own():
 
 
 def test_new_entries_are_declared_and_exported():
+    """The plan-level entries, and the kernel-level entries that CARRY the gain, as the bias_gain field of their options descriptor.
+    The per-feature entries (base name + "_bias") are gone from the header, the bindings and the library."""
     header = open(runtime.HEADER_PATH).read()
-    for sym in ("m2f_plan_attention_bias", "m2f_plan_get_attention_bias", "m2f_attention_fwd_bias", "m2f_attention_varlen_fwd_bias",
-                "m2f_attention_stream_bias", "m2f_attention_stream_chunk_bias"):
+    carriers = {"m2f_attention_fwd": "m2f_attn_opts", "m2f_attention_varlen_fwd": "m2f_attn_opts",
+                "m2f_attention_stream": "m2f_attn_stream_opts", "m2f_attention_stream_chunk": "m2f_attn_stream_opts"}
+    mirror = {"m2f_attn_opts": runtime.AttnOptsC, "m2f_attn_stream_opts": runtime.AttnStreamOptsC}
+    for sym in tuple(carriers) + ("m2f_plan_attention_bias", "m2f_plan_get_attention_bias"):
         assert sym in runtime.SIGNATURES and ("int " + sym + "(") in header, sym
         assert hasattr(runtime.lib(), sym), sym
+    for sym, name in carriers.items():
+        struct = header[header.index("typedef struct " + name + " {"):header.index("} " + name + ";")]
+        assert "float bias_gain;" in struct and ("bias_gain", ctypes.c_float) in mirror[name]._fields_, name
+        assert runtime.SIGNATURES[sym][1][-1] is ctypes.POINTER(mirror[name]), sym
+        old = sym + "_bias"
+        assert old not in runtime.SIGNATURES and old not in header and not hasattr(runtime.lib(), old), old
 
 
 # ---- the reference against torch -----------------------------------------------------------------------------------------------------

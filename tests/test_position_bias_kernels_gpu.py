@@ -1,9 +1,10 @@
 """Distance-decay attention bias (ALiBi) at kernel level: functional.attention_fwd / attention_varlen_fwd / attention_stream[_paged] /
-attention_stream_chunk[_paged] with bias=gain (the *_bias C entries; csrc/attention.hip, attention_dlong.hip, attention_stream.hip,
+attention_stream_chunk[_paged] with bias=gain (bias_gain of the C entries' options; csrc/attention.hip, attention_dlong.hip, attention_stream.hip,
 attention_stream_chunk.hip) against tests/golden/position_bias_ref.py in float64 - outputs AND probabilities, the backward kernels fed
 the biased forward's probabilities against autograd of the reference, the bf16 contraction form, bias=None / 0 against the calls without
 the argument bit for bit, streams driven across the 64-row pass boundary and twice round a ring, the weights-emitting form, chunks on
 empty, long and ring caches, and the paged forms against the dense ones bit for bit."""
+import ctypes
 import functools
 import math
 
@@ -121,9 +122,10 @@ def test_no_gain_is_the_call_without_the_argument():
     with pytest.raises(ValueError, match="position bias"):
         F.attention_fwd(q, k, v, kp, B, L, H, bias=-1.0)
     with pytest.raises(runtime.HipError):
-        runtime.check(runtime.lib().m2f_attention_fwd_bias(B, L, H, hd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-                                                            v.stride(0), kp.to(torch.uint8).data_ptr(), q.data_ptr(), q.stride(0), None, 0, 0.0,
-                                                            None, None, -1, -1, float("nan")), "m2f_attention_fwd_bias")
+        nan_gain = runtime.AttnOptsC(past=-1, future=-1, bias_gain=float("nan"))
+        runtime.check(runtime.lib().m2f_attention_fwd(B, L, H, hd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+                                                       v.stride(0), kp.to(torch.uint8).data_ptr(), q.data_ptr(), q.stride(0), None, 0, 0.0,
+                                                       None, None, ctypes.byref(nan_gain)), "m2f_attention_fwd")
 
 
 def test_a_rounded_gain_is_what_is_applied():

@@ -2,6 +2,7 @@
 reference values from (tests/golden/speaker_heads_ref.py) against torch's own boolean attn_mask= / src_mask= arguments on the rows
 that see a key, exact zeros on the rows that see none, the head-class rule, the refused settings and ids, the plan keys, src/dataset.py's
 speaker ids and collate, the config check of src/train.py, and the snapshot's `speakers` field through select / cpu / to / state_dict."""
+import ctypes
 import os
 import sys
 
@@ -213,11 +214,26 @@ def test_default_plan_key_is_what_it_was_and_a_setting_has_its_own():
 
 
 def test_new_entries_are_declared():
+    """The plan-level entries, the advance launches, and the kernel-level entries that CARRY the speaker heads, as the n_same / n_other
+    / ids fields of their options descriptor.  The per-feature entries (base name + "_speakers") are gone from the header, the bindings
+    and the library."""
     header = open(runtime.HEADER_PATH).read()
-    for sym in ("m2f_plan_attention_speakers", "m2f_plan_get_attention_speakers", "m2f_plan_stream_speakers", "m2f_attention_fwd_speakers",
-                "m2f_attention_varlen_fwd_speakers", "m2f_attention_stream_speakers", "m2f_attention_stream_chunk_speakers",
-                "m2f_stream_advance_speakers", "m2f_stream_advance_speakers_n", "m2f_attention_speaker_class"):
+    carriers = {"m2f_attention_fwd": ("m2f_attn_opts", ("speakers",)), "m2f_attention_varlen_fwd": ("m2f_attn_opts", ("speakers",)),
+                "m2f_attention_stream": ("m2f_attn_stream_opts", ("spk_cache", "spk_new")),
+                "m2f_attention_stream_chunk": ("m2f_attn_stream_opts", ("spk_cache", "spk_new"))}
+    mirror = {"m2f_attn_opts": runtime.AttnOptsC, "m2f_attn_stream_opts": runtime.AttnStreamOptsC}
+    for sym in tuple(carriers) + ("m2f_plan_attention_speakers", "m2f_plan_get_attention_speakers", "m2f_plan_stream_speakers",
+                                  "m2f_stream_advance_speakers", "m2f_stream_advance_speakers_n", "m2f_attention_speaker_class"):
         assert sym in runtime.SIGNATURES and ("int " + sym + "(") in header, sym
+    for sym, (name, ids) in carriers.items():
+        struct = header[header.index("typedef struct " + name + " {"):header.index("} " + name + ";")]
+        fields = dict(mirror[name]._fields_)
+        assert "int n_same, n_other;" in struct and fields["n_same"] is ctypes.c_int and fields["n_other"] is ctypes.c_int, name
+        for f in ids:
+            assert ("const uint8_t* " + f + ";") in struct and fields[f] is ctypes.c_void_p, (name, f)
+        assert runtime.SIGNATURES[sym][1][-1] is ctypes.POINTER(mirror[name]), sym
+        old = sym + "_speakers"
+        assert old not in runtime.SIGNATURES and old not in header and not hasattr(runtime.lib(), old), old
     assert "M2F_BUF_SPEAKERS = 19" in header and runtime.BUF_SPEAKERS == 19 and runtime.BUF_STREAM_SPEAKERS == 20
 
 

@@ -1,11 +1,12 @@
 """Speaker-aware attention heads at kernel level: functional.attention_fwd / attention_varlen_fwd / attention_stream[_paged] /
-attention_stream_chunk[_paged] with speakers= / speaker_heads= (the *_speakers C entries; the SPK instantiations of csrc/attention.hip,
+attention_stream_chunk[_paged] with speakers= / speaker_heads= (the speaker fields of the C entries' options; the SPK instantiations of csrc/attention.hip,
 attention_dlong.hip, attention_stream.hip, attention_stream_chunk.hip) against tests/golden/speaker_heads_ref.py in float64 - outputs
 AND probabilities, the UNCHANGED backward kernels fed the new forward's probabilities against autograd of the reference, exact zeros at
 hidden pairs, the zero rows of an other-speaker head in a monologue, the bf16 contraction form, speaker_heads=None against the calls
 without the argument bit for bit, streams across the 64-row pass boundary and twice round a ring, the weights-emitting form with a zero
 row, chunks on empty, long and ring caches against the reference and against that many steps, the cached speaker bytes, the paged forms
 against the dense ones bit for bit, and every refused launch."""
+import ctypes
 import functools
 
 import pytest
@@ -421,36 +422,42 @@ def test_refused_launches():
     lib, u8 = runtime.lib(), kp.to(torch.uint8)
     ids = spk.to(torch.uint8)
     out = torch.full_like(q, 3.0)
+    def heads(speakers, n_same, n_other):
+        return ctypes.byref(runtime.AttnOptsC(past=-1, future=-1, bias_gain=0.0, n_same=n_same, n_other=n_other, speakers=speakers))
+
+    def stream_heads(spk_cache, spk_new, n_same, n_other):
+        return ctypes.byref(runtime.AttnStreamOptsC(n_same=n_same, n_other=n_other, spk_cache=spk_cache, spk_new=spk_new))
+
     args = (B, L, H, hd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), u8.data_ptr(), out.data_ptr(),
-            out.stride(0), None, 0, 0.0, None, None, -1, -1, 0.0)
+            out.stride(0), None, 0, 0.0, None, None)
     for tail in ((ids.data_ptr(), H, 1), (None, 1, 1), (ids.data_ptr(), -1, 1)):
         with pytest.raises(runtime.HipError):
-            runtime.check(lib.m2f_attention_fwd_speakers(*args, *tail), "m2f_attention_fwd_speakers")
+            runtime.check(lib.m2f_attention_fwd(*args, heads(*tail)), "m2f_attention_fwd")
     vargs = (B, L, H, hd, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), None, B * L, u8.data_ptr(),
-             out.data_ptr(), out.stride(0), None, 0, 0.0, None, None, -1, -1, 0.0)
+             out.data_ptr(), out.stride(0), None, 0, 0.0, None, None)
     for tail in ((ids.data_ptr(), H, 1), (None, 1, 1)):
         with pytest.raises(runtime.HipError):
-            runtime.check(lib.m2f_attention_varlen_fwd_speakers(*vargs, *tail), "m2f_attention_varlen_fwd_speakers")
+            runtime.check(lib.m2f_attention_varlen_fwd(*vargs, heads(*tail)), "m2f_attention_varlen_fwd")
     C = 4
     kc, vc = F.attention_stream_caches(S_, H_, HD_, C, device=DEV)
     x = _rand(S_, E_, seed=1)
     so = torch.full_like(x, 3.0)
     lengths, act = torch.zeros(S_, dtype=torch.int32, device=DEV), torch.ones(S_, dtype=torch.uint8, device=DEV)
     sc, new_ids = torch.zeros(S_, C, dtype=torch.uint8, device=DEV), torch.zeros(S_, dtype=torch.uint8, device=DEV)
-    sargs = (S_, H_, HD_, x.data_ptr(), x.stride(0), x.data_ptr(), x.stride(0), x.data_ptr(), x.stride(0), kc.data_ptr(), vc.data_ptr(), None,
-             0, 0, 0, C, 0, lengths.data_ptr(), act.data_ptr(), so.data_ptr(), so.stride(0), 0, None, 0.0)
+    sargs = (S_, H_, HD_, x.data_ptr(), x.stride(0), x.data_ptr(), x.stride(0), x.data_ptr(), x.stride(0), kc.data_ptr(), vc.data_ptr(),
+             C, 0, lengths.data_ptr(), act.data_ptr(), so.data_ptr(), so.stride(0), 0, None)
     for tail in ((sc.data_ptr(), new_ids.data_ptr(), H_, 1), (None, new_ids.data_ptr(), 1, 1), (sc.data_ptr(), None, 1, 1)):
         with pytest.raises(runtime.HipError):
-            runtime.check(lib.m2f_attention_stream_speakers(*sargs, *tail, None), "m2f_attention_stream_speakers")
+            runtime.check(lib.m2f_attention_stream(*sargs, stream_heads(*tail)), "m2f_attention_stream")
     y = _rand(S_ * 2, E_, seed=2)
     yo = torch.full_like(y, 3.0)
     new = torch.full((S_,), 2, dtype=torch.int32, device=DEV)
     ids2 = torch.zeros(S_, 2, dtype=torch.uint8, device=DEV)
-    cargs = (S_, 2, H_, HD_, y.data_ptr(), y.stride(0), y.data_ptr(), y.stride(0), y.data_ptr(), y.stride(0), kc.data_ptr(), vc.data_ptr(), None,
-             0, 0, 0, C, 0, lengths.data_ptr(), new.data_ptr(), yo.data_ptr(), yo.stride(0), 0, 0.0)
+    cargs = (S_, 2, H_, HD_, y.data_ptr(), y.stride(0), y.data_ptr(), y.stride(0), y.data_ptr(), y.stride(0), kc.data_ptr(), vc.data_ptr(),
+             C, 0, lengths.data_ptr(), new.data_ptr(), yo.data_ptr(), yo.stride(0), 0, None)
     for tail in ((sc.data_ptr(), ids2.data_ptr(), H_, 1), (None, ids2.data_ptr(), 1, 1), (sc.data_ptr(), None, 1, 1)):
         with pytest.raises(runtime.HipError):
-            runtime.check(lib.m2f_attention_stream_chunk_speakers(*cargs, *tail, None), "m2f_attention_stream_chunk_speakers")
+            runtime.check(lib.m2f_attention_stream_chunk(*cargs, stream_heads(*tail)), "m2f_attention_stream_chunk")
     torch.cuda.synchronize()
     assert torch.all(out == 3.0) and torch.all(so == 3.0) and torch.all(yo == 3.0), "nothing was launched"
     with pytest.raises(ValueError, match="speaker_cache"):
