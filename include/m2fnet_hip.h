@@ -495,14 +495,16 @@ int m2f_gemm_fp8(int M, int N, int K, const uint8_t* a8, int lda, const uint8_t*
 int m2f_quantize_fp8(const float* src, uint8_t* dst, int64_t n, float scale, m2f_stream_t stream);
 
 /* ---- kernel-level entry points (used by the parity tests; same kernels the plan launches) ---------- */
-/* Number of bf16 GEMM launches this process has issued in the RING form (csrc/gemm.hip, m2f_gemm16_ring_kernel: LDS-direct
- * operand ring, 128x128 tiles; taken by k-contiguous launches of at least M2F_RING_MIN = 200 such tiles unless M2F_RING=0).
- * Diagnostic: lets a test assert that the form it means to check actually ran. */
+/* Number of bf16 GEMM launches this process has issued in the RING form (csrc/gemm_ring.h, m2f_gemm16_ring_kernel: LDS-direct
+ * operand ring; taken by k-contiguous launches of at least M2F_RING_MIN = 200 tiles of 128x128 unless M2F_RING=0; DESIGN.md, "GEMM
+ * dispatch") or the eight-phase form.  Diagnostic: lets a test assert that the form it means to check actually ran. */
 long long m2f_gemm_ring_launches(void);
 /* The kernel form the last m2f_gemm / m2f_gemm_fp8 / m2f_gemm_p8 call (or any GEMM launch of a plan) dispatched to: one
  * M2F_FORM_* value, plus M2F_FORM_VEC when the fp32-source or skinny kernel moves its operands in 16-byte chunks, M2F_FORM_SRC16
  * when the skinny kernel reads bf16 shadows, and M2F_FORM_NN_T when a bf16 NN launch ran as the k-contiguous form through the
- * transposed shadows; M2F_FORM_NONE after a call that launched nothing.  Host-side diagnostic: lets a test assert the kernel it covers. */
+ * transposed shadows; M2F_FORM_NONE after a call that launched nothing.  Host-side diagnostic: lets a test assert the kernel it covers.
+ * Assigned at ONE site for every dispatched launch - execute() in csrc/gemm_dispatch.hip, from the chooser's GemmChoice::form; the
+ * direct entry m2f_gemm_p8 and the table launches (csrc/gemm_p8.hip), which do not go through the chooser, assign their own. */
 int m2f_gemm_last_form(void);
 enum {
     M2F_FORM_NONE = 0,
@@ -528,6 +530,30 @@ enum {
     M2F_FORM_SRC16 = 0x200,
     M2F_FORM_NN_T = 0x400
 };
+
+/* Dry run of the GEMM dispatch (host only, no HIP call, works without a GPU): the M2F_FORM_* value - bits included - that m2f_gemm
+ * (mode 0 = fp32, 1 = bf16) or m2f_gemm_fp8 (mode 2; layout 0, K1 = 0) would record for `count` (1 .. 8, one launch) identical problems
+ * of M x N x (K0 + K1) under the forced `tile` (0 = automatic); M2F_FORM_NONE for a launch the entry refuses.  It asks the chooser the
+ * launchers ask (csrc/gemm_dispatch.hip) on a synthetic batch: aligned operands that are never dereferenced, every leading dimension
+ * pad8 of its contiguous extent.  bits: what the dispatch rules look at.  stages_bf16 (nullable; modes 0 / 1): 1 when a bf16-mode
+ * launch of the batch reads bf16 shadows only (what the plan's unread-copy analysis asks). */
+enum {
+    M2F_GEMM_FORM_SHADOWS = 1,         /* every operand segment has a bf16 shadow */
+    M2F_GEMM_FORM_BT_SHADOW = 2,       /* ... and B a transposed one (layout 1) */
+    M2F_GEMM_FORM_ODD_LD = 4,          /* leading dimensions pad8(extent) + 1: neither 16-byte loads nor shadow staging */
+    M2F_GEMM_FORM_BIAS_GRAD = 8,
+    M2F_GEMM_FORM_GELU = 16,
+    M2F_GEMM_FORM_RELU_B = 32,
+    M2F_GEMM_FORM_ACC = 64,
+    M2F_GEMM_FORM_GATE = 128,
+    M2F_GEMM_FORM_DROP = 256,          /* a dropout site in the epilogue */
+    M2F_GEMM_FORM_C8 = 512,            /* fp8: the result leaves as e4m3 */
+    M2F_GEMM_FORM_SPLITK = 1024,       /* split-K scratch present */
+    M2F_GEMM_FORM_RELU_A = 2048,
+    M2F_GEMM_FORM_RELU_OUT = 4096,
+    M2F_GEMM_FORM_RES = 8192
+};
+int m2f_gemm_form(int mode, int layout, int tile, int count, int M, int N, int K0, int K1, uint32_t bits, int* stages_bf16);
 
 /* C[M,N] = epilogue(A x B); layout 0: C = A[M,K] B[N,K]^T (nn.Linear forward), 1: C = A[M,K] B[K,N]
  * (input gradient), 2: C = A[K,M]^T B[K,N] (weight gradient; bias_grad[M] = column sums of A; with accumulate != 0 both C and

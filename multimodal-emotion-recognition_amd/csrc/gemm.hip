@@ -17,7 +17,8 @@
 //     split into 4 producer waves (global -> register ring of D k-tiles -> LDS) and 4 consumer waves (LDS -> MFMA ->
 //     epilogue); tiles 64x64 (chain launches), 128x128 or 256x128 (text encoder); see the comment above gemm16_body.
 //     Chip-filling launches and the weight-gradient table launch (m2f_launch_gemm_table) run the LDS-DMA forms instead:
-//     gemm_ring.h and gemm_p8.h.
+//     gemm_ring.h and gemm_p8.h.  Which form a launch takes is decided in gemm_dispatch.hip; this unit holds the register-staged
+//     kernels and how they are launched (m2f_launch_gemm_staged).
 //   * "grouped": one launch covers several independent problems (text+audio branch, q/k/v of a fusion layer, split
 //     concat) so the 256 CUs see more workgroups per launch and the launch-latency-bound chain gets shorter;
 //   * the epilogue fuses bias, ReLU / exact GELU, dropout, residual add, ReLU-gate and accumulate (32-bit offsets from
@@ -25,8 +26,6 @@
 //     wgrad form also emits the bias gradient (column sums of dY) from the tiles it already streams.
 #include "common.h"
 #include "ops.h"
-#include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <cstring>
 
@@ -1038,21 +1037,9 @@ hipError_t launch_cfg16(const GemmBatch& gb, int total_tiles, hipStream_t stream
     static_assert(lds <= 160 * 1024, "LDS budget");
     static_assert(!DENSE || 2 * lds <= 160 * 1024, "two workgroups per CU");
     GemmBatch hb = gb;                                          // compact header for the kernel's critical path
-    for (int i = 0; i < M2F_GEMM_MAX_PROBLEMS; ++i) {
-        hb.tb[i] = i < gb.count ? gb.pr[i].tile_begin : 0x7fffffff;
-        GemmHot& h = hb.hot[i];
-        memset(&h, 0, sizeof(h));
-        if (i >= gb.count) continue;
-        const GemmProblem& p = gb.pr[i];
-        h.aq[0] = p.a.q[0]; h.aq[1] = p.a.q[1]; h.bq[0] = p.b.q[0]; h.bq[1] = p.b.q[1];
-        h.M = p.M; h.N = p.N; h.k[0] = p.a.k[0]; h.k[1] = p.a.k[1];
-        h.ldaq[0] = p.a.ldq[0]; h.ldaq[1] = p.a.ldq[1]; h.ldbq[0] = p.b.ldq[0]; h.ldbq[1] = p.b.ldq[1];
-        h.flags = p.flags; h.tile_begin = p.tile_begin; h.has_bias_grad = p.bias_grad != nullptr;
-    }
+    m2f_gemm_fill_hot(hb, true);
     void (*kern)(const GemmBatch);
     static_assert(!(DENSE && GELU), "the GELU epilogue exists for the wide forward-form kernels only");
-    m2f_g_last_form = FP8 ? (BM == 256 ? M2F_FORM_FP8_256x128 : M2F_FORM_FP8_128x128)
-                          : (BM == 256 ? M2F_FORM_BF16SRC_256x128 : BM == 128 ? M2F_FORM_BF16SRC_128 : M2F_FORM_BF16SRC_64);
     if constexpr (DENSE) kern = m2f_gemm16_dense_kernel<A_RC, B_RC, BM, BN, BK, D>;
     else kern = m2f_gemm16_kernel<A_RC, B_RC, BM, BN, BK, D, GELU, FP8>;
     if (lds > 64 * 1024) {
@@ -1074,9 +1061,6 @@ hipError_t launch_cfg(const GemmBatch& gb, int total_tiles, hipStream_t stream) 
     constexpr int lds = 2 * SA::LDS_BYTES + 2 * SB::LDS_BYTES;
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = m2f_gemm_kernel<PREC, A_RC, B_RC, BM, BN, BK, VEC, GELU>;
-    bool split = false;
-    for (int i = 0; i < gb.count; ++i) split = split || gb.pr[i].splitk > 1;
-    m2f_g_last_form = (BM == 128 ? M2F_FORM_F32SRC_128 : split ? M2F_FORM_F32SRC_SPLITK : M2F_FORM_F32SRC_64) | (VEC ? M2F_FORM_VEC : 0);
     if (lds > 64 * 1024) {
         static bool attr_set = false;
         if (!attr_set) {
@@ -1090,155 +1074,27 @@ hipError_t launch_cfg(const GemmBatch& gb, int total_tiles, hipStream_t stream) 
     return hipGetLastError();
 }
 
+// The instantiations.  The kernel set is closed: a flag that has no kernel of its own (GELU outside the forward form) folds onto the
+// kernel without it, as the launches always did.
+constexpr int bk_f32src(int prec, int tile) { return prec == M2F_PREC_F32 ? (tile == 128 ? 32 : 64) : (tile == 128 ? 64 : 128); }
+
 template <int PREC, bool A_RC, bool B_RC>
-hipError_t launch_tile(GemmBatch& gb, int tile, hipStream_t stream) {
-    auto count_tiles = [&](int bm, int bn) {
-        int t = 0;
-        for (int i = 0; i < gb.count; ++i) t += m2f_cdiv(gb.pr[i].M, bm) * m2f_cdiv(gb.pr[i].N, bn);
-        return t;
-    };
-    if (tile == 0) tile = (count_tiles(128, 128) >= 512) ? 128 : 64;     // fill 256 CUs first
-    const int bm = tile, bn = tile;
-    constexpr int BK64 = (PREC == M2F_PREC_F32) ? 64 : 128;
-    constexpr int BK128 = (PREC == M2F_PREC_F32) ? 32 : 64;
-    const int bk = tile == 128 ? BK128 : BK64;
-    // split-K when the launch cannot occupy the chip: a CU pulls operands at a fixed ~25-45 GB/s (L1 miss queue x
-    // latency), so small grids are spread over more CUs.  Only for the forward / dgrad forms on 64x64 tiles.
-    int want_s = 1;
-    const int plain = count_tiles(bm, bn);
-    if (tile == 64 && !A_RC && gb.splitk_ws && gb.splitk_cnt && plain > 0 && plain < 224) {
-        want_s = (352 + plain - 1) / plain;
-        if (want_s > 4) want_s = 4;
-    }
-    int t = 0, slabs = 0, tiles_total = 0;
-    for (int i = 0; i < gb.count; ++i) {
-        GemmProblem& p = gb.pr[i];
-        const int nk = m2f_cdiv(p.a.k[0], bk) + m2f_cdiv(p.a.k[1], bk);
-        int sp = want_s;
-        if (sp > nk / 2) sp = nk / 2;                 // at least two k-tiles per slice
-        if (sp < 1) sp = 1;
-        p.splitk = sp;
-        p.tile_begin = t;
-        p.slab_begin = slabs;                         // in slices (one [BM x BN] partial each)
-        p.cnt_begin = tiles_total;
-        p.tiles_n = m2f_cdiv(p.N, bn);
-        const int tiles = m2f_cdiv(p.M, bm) * p.tiles_n;
-        t += tiles * sp;
-        slabs += tiles * sp;
-        tiles_total += tiles;
-    }
-    if (want_s > 1 && (tiles_total > gb.splitk_max_tiles || slabs > 4 * gb.splitk_max_tiles)) {   // scratch too small: no split
-        t = 0;
-        for (int i = 0; i < gb.count; ++i) {
-            GemmProblem& p = gb.pr[i];
-            p.splitk = 1; p.tile_begin = t; p.slab_begin = 0; p.cnt_begin = 0;
-            t += m2f_cdiv(p.M, bm) * p.tiles_n;
-        }
-    }
-    if (t == 0) return hipSuccess;
-    // 16-byte loads only when every operand of every problem of the launch allows them
-    bool vec = true;
-    for (int i = 0; i < gb.count; ++i)
-        vec = vec && (gb.pr[i].flags & GF_VEC_A) && (gb.pr[i].flags & GF_VEC_B);
-    if constexpr (!A_RC && !B_RC) {                             // GELU epilogue: forward form only (text encoder)
-        bool gelu = false;
-        for (int i = 0; i < gb.count; ++i) gelu = gelu || (gb.pr[i].flags & GF_GELU_OUT);
-        if (gelu) {
-            if (tile == 128)
-                return vec ? launch_cfg<PREC, false, false, 128, 128, BK128, true, true>(gb, t, stream)
-                           : launch_cfg<PREC, false, false, 128, 128, BK128, false, true>(gb, t, stream);
-            return vec ? launch_cfg<PREC, false, false, 64, 64, BK64, true, true>(gb, t, stream)
-                       : launch_cfg<PREC, false, false, 64, 64, BK64, false, true>(gb, t, stream);
-        }
-    }
-    if (tile == 128)
-        return vec ? launch_cfg<PREC, A_RC, B_RC, 128, 128, BK128, true>(gb, t, stream)
-                   : launch_cfg<PREC, A_RC, B_RC, 128, 128, BK128, false>(gb, t, stream);
-    return vec ? launch_cfg<PREC, A_RC, B_RC, 64, 64, BK64, true>(gb, t, stream)
-               : launch_cfg<PREC, A_RC, B_RC, 64, 64, BK64, false>(gb, t, stream);
+hipError_t launch_tile(const GemmBatch& gb, bool tile128, bool vec, bool gelu, int t, hipStream_t stream) {
+    return m2f_pick_bools([&](auto T128, auto VEC, auto GELU) {
+        constexpr int T = T128.value ? 128 : 64;
+        constexpr bool G = GELU.value && !A_RC && !B_RC;        // GELU epilogue: forward form only (text encoder)
+        return launch_cfg<PREC, A_RC, B_RC, T, T, bk_f32src(PREC, T), VEC.value, G>(gb, t, stream);
+    }, tile128, vec, gelu);
 }
 
 template <bool A_RC, bool B_RC>
-hipError_t launch_tile16(GemmBatch& gb, int tile, hipStream_t stream) {
-    auto count_tiles = [&](int bm, int bn) {
-        int t = 0;
-        for (int i = 0; i < gb.count; ++i) t += m2f_cdiv(gb.pr[i].M, bm) * m2f_cdiv(gb.pr[i].N, bn);
-        return t;
-    };
-    const bool auto_tile = tile == 0;
-    // 128x128 tiles halve the bytes pulled per output element; used once the launch still fills the chip with them
-    // (wgrad launches: measured 3.25 -> 3.18 ms/step with the threshold at 256 instead of 512)
-    if (tile == 0) tile = (count_tiles(128, 128) >= (A_RC ? 256 : 512)) ? 128 : 64;
-    // very large forward-form launches (the text encoder: M = utterances x tokens): 256 (M) x 128 (N) tiles, 85 instead of
-    // 64 FLOP per byte through the L1 fill path that bounds these kernels
-    // (RoBERTa-large geometry, 512 utterances x 64 tokens: 59.3 -> 55.7 ms per forward)
-    if (tile == 128 && !A_RC && !B_RC && count_tiles(256, 128) >= 1024) tile = 256;
-    if constexpr (!A_RC && !B_RC) {
-        // Forward-form launches run the ring form (gemm_ring.h, m2f_gemm16_ring_kernel): 128x128 tiles from ~one tile per CU
-        // on, 128x64 tiles below that while those still cover most of the chip, 64x64 tiles for the rest down to 80 tiles;
-        // what remains (a few tiles, e.g. the classifier) keeps the register-staged 64x64 build below.  Measured on MI355X,
-        // fwd+bwd of the C3 step (B = 64): 3.21 ms without the ring form; 3.06 with the 128x128 form from 200 tiles (3.07 /
-        // 3.07 / 3.16 at 100 / 150 / 260); 2.91 with the 128x64 form from 150 tiles on top (2.95 / 2.91 at 200 / 100); 2.89
-        // with the 64x64 form from 80 tiles (no change down to 1).  C2 (B = 32): 1.957 -> 1.914 -> 1.853 (the 128x64 form
-        // from 100 tiles: 2.014 - launches of ~100 tiles leave too many CUs idle).  M2F_RING=0 switches the form off,
-        // M2F_RING_MIN / M2F_RING64_MIN / M2F_RING32_MIN move the thresholds.
-        static const int ring = getenv("M2F_RING") ? atoi(getenv("M2F_RING")) : 1;
-        static const int ring_min = getenv("M2F_RING_MIN") ? atoi(getenv("M2F_RING_MIN")) : 200;
-        static const int ring64_min = getenv("M2F_RING64_MIN") ? atoi(getenv("M2F_RING64_MIN")) : 150;
-        static const int ring32_min = getenv("M2F_RING32_MIN") ? atoi(getenv("M2F_RING32_MIN")) : 80;
-        // Text-encoder-sized launches (M = utterances x tokens = 32,768): 256x128 ring tiles, whose k-loop runs at the MFMA rate
-        // (1,050 cycles per 256x128x64 k-tile against 1,024) and whose fixed cost per tile is amortised by the persistent walk.
-        // RoBERTa-large geometry 50.2 -> 43.4 ms per forward, base 17.4 -> 14.5 (threshold 512 tiles; 15.0 at 1,024; no
-        // launch of the M2FNet step is that large).
-        static const int ring256_min = getenv("M2F_RING256_MIN") ? atoi(getenv("M2F_RING256_MIN")) : 512;      // tiles of 256x128
-        // Round 4: from one chip-filling round of 256 x 256 tiles on, the eight-phase form (gemm_p8.h: all eight waves load and multiply,
-        // continuous prefetch stream across tiles): 32,768 x 1,024 x 1,024 752 TFLOP/s against ~460 for the 256x128 ring form.
-        // M2F_P8=0 switches it off, M2F_P8_MIN moves the threshold (tiles of 256x256).
-        static const int p8_on = getenv("M2F_P8") ? atoi(getenv("M2F_P8")) : 1;
-        static const int p8_min = getenv("M2F_P8_MIN") ? atoi(getenv("M2F_P8_MIN")) : 256;
-        // (... and only when those tiles fill whole rounds of the chip: a 256 x 256 tile is ~25 us of work, and 336 of them on 256 CUs -
-        //  the merged QKV projections of the C3 geometry at B = 256 - ran 2 % of the STEP slower than three rounds of 256 x 128 ring tiles)
-        {
-            const int t256 = count_tiles(256, 256);
-            const int rounds = (t256 + 255) / 256;
-            if (ring && p8_on && auto_tile && t256 >= p8_min && t256 * 100 >= 85 * rounds * 256 && m2f_gemm_p8_ok(gb)) return m2f_p8_launch_kc(gb, stream);
-        }
-        if (ring && auto_tile && count_tiles(256, 128) >= ring256_min && m2f_gemm_ring256_ok(gb)) return m2f_launch_gemm_ring(gb, 256, 128, stream);
-        // (what the 256x128 ring form cannot take - it has bias / ReLU / GELU / residual epilogues only - keeps the register-staged
-        // 256x128 build from 1,024 such tiles on: RoBERTa-large geometry 52.3 vs 54.0 ms with 128x128 ring tiles)
-        // launches of 257..511 tiles of 128x128 take two rounds on 256 CUs with the second one mostly empty (the merged audio +
-        // text QKV in-projections at C3: 336 tiles); as 256x128 tiles they are one round (168 tiles).  M2F_RING256_2R=0 switches it off
-        static const int ring256_2r = getenv("M2F_RING256_2R") ? atoi(getenv("M2F_RING256_2R")) : 1;
-        if (ring && auto_tile && ring256_2r && tile != 256) {
-            const int t128 = count_tiles(128, 128);
-            if (t128 > 256 && t128 < 512 && count_tiles(256, 128) <= 256 && m2f_gemm_ring256_ok(gb) && m2f_gemm_ring_ok(gb))
-                return m2f_launch_gemm_ring(gb, 256, 128, stream);
-        }
-        if (ring && auto_tile && tile != 256 && m2f_gemm_ring_ok(gb)) {
-            if (count_tiles(128, 128) >= ring_min) return m2f_launch_gemm_ring(gb, 128, 128, stream);
-            if (count_tiles(128, 64) >= ring64_min) return m2f_launch_gemm_ring(gb, 128, 64, stream);
-            if (count_tiles(64, 64) >= ring32_min) return m2f_launch_gemm_ring(gb, 64, 64, stream);
-        }
-    }
-    const int tile_m = tile, tile_n = tile == 256 ? 128 : tile;
-    int t = 0;
-    for (int i = 0; i < gb.count; ++i) {
-        GemmProblem& p = gb.pr[i];
-        p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0;
-        p.tile_begin = t;
-        p.tiles_n = m2f_cdiv(p.N, tile_n);
-        t += m2f_cdiv(p.M, tile_m) * p.tiles_n;
-    }
-    if (t == 0) return hipSuccess;
-    if constexpr (!A_RC && !B_RC) {
-        bool gelu = false;
-        for (int i = 0; i < gb.count; ++i) gelu = gelu || (gb.pr[i].flags & GF_GELU_OUT);
-        if (gelu) {                                              // text encoder (forward form only): own instantiations
-            if (tile == 256) return launch_cfg16<false, false, 256, 128, 64, 2, false, true>(gb, t, stream);
-            if (tile == 128) return launch_cfg16<false, false, 128, 128, 64, 3, false, true>(gb, t, stream);
-            return launch_cfg16<false, false, 64, 64, 128, 2, false, true>(gb, t, stream);
-        }
-        if (tile == 256) return launch_cfg16<false, false, 256, 128, 64, 2>(gb, t, stream);
+hipError_t launch_tile16(const GemmBatch& gb, int tile, bool gelu, bool fp8, int t, hipStream_t stream) {
+    if constexpr (!A_RC && !B_RC) {     // forward form only: 256x128 tiles, the GELU epilogue (text encoder), e4m3 operands - own instantiations
+        if (tile == 256 || tile == 128)
+            return m2f_pick_bools([&](auto BIG, auto GELU, auto FP8) {
+                return launch_cfg16<false, false, BIG.value ? 256 : 128, 128, 64, BIG.value ? 2 : 3, false, GELU.value, FP8.value>(gb, t, stream);
+            }, tile == 256, gelu, fp8);
+        if (gelu) return launch_cfg16<false, false, 64, 64, 128, 2, false, true>(gb, t, stream);
     }
     if (tile == 128) return launch_cfg16<A_RC, B_RC, 128, 128, 64, 3>(gb, t, stream);
     // ONE 64x64 build for every launch size: ring depth 2 within 128 VGPRs (two workgroups per CU when the launch has more
@@ -1250,123 +1106,34 @@ hipError_t launch_tile16(GemmBatch& gb, int tile, hipStream_t stream) {
     return launch_cfg16<A_RC, B_RC, 64, 64, 128, M2F_CHAIN_D, true>(gb, t, stream);
 }
 
-// can every operand of every problem be staged from its bf16 shadow with 16-byte loads?
-bool src16_ok(const GemmBatch& gb, bool a_rc, bool b_rc) {
-    auto seg_ok = [](const GemmOperand& o, bool rc, int rows) {
-        for (int s = 0; s < 2; ++s) {
-            if (o.k[s] == 0) continue;
-            if (!o.q[s] || (reinterpret_cast<uintptr_t>(o.q[s]) & 15) || (o.ldq[s] & 7)) return false;
-            const int extent = rc ? rows : o.k[s];           // the contiguous dimension
-            if ((extent & 7) && o.ldq[s] != ((extent + 7) & ~7)) return false;   // pads must be the buffer's own zero pads
-            if (o.ldq[s] < extent) return false;
-        }
-        return true;
-    };
-    for (int i = 0; i < gb.count; ++i) {
-        const GemmProblem& p = gb.pr[i];
-        if (!seg_ok(p.a, a_rc, p.M) || !seg_ok(p.b, b_rc, p.N)) return false;
-    }
-    return true;
+// NT, NN or TN as compile-time flags (A_RC without B_RC does not exist)
+template <typename F>
+hipError_t pick_layout(bool a_rc, bool b_rc, F&& f) {
+    if (!b_rc) return f(std::false_type{}, std::false_type{});
+    if (!a_rc) return f(std::false_type{}, std::true_type{});
+    return f(std::true_type{}, std::true_type{});
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool vec_ok(const GemmOperand& o, bool rc, int rows) {
-    for (int s = 0; s < 2; ++s) {
-        if (o.k[s] == 0) continue;
-        if (!aligned16(o.p[s]) || (o.ld[s] & 3)) return false;
-        if (!rc && (o.k[s] & 3)) return false;
+// fp32-source launches: tiles numbered with the split-K bookkeeping - `splitk` consecutive workgroups share one output tile, each
+// problem takes at most the wanted factor and at least two k-tiles per slice; slab_begin in slices (one [BM x BN] partial each),
+// cnt_begin in tiles (one ticket each).  (A scratch too small for the wish arrives here as ch.splitk = 1: the chooser's fallback.)
+int number_tiles_splitk(GemmBatch& gb, int tile, int bk, int want_s) {
+    int t = 0, tiles_total = 0;
+    for (int i = 0; i < gb.count; ++i) {
+        GemmProblem& p = gb.pr[i];
+        p.splitk = m2f_gemm_splitk_of(p, want_s, bk);
+        p.tile_begin = t;
+        p.slab_begin = t;
+        p.cnt_begin = tiles_total;
+        p.tiles_n = m2f_cdiv(p.N, tile);
+        const int tiles = m2f_cdiv(p.M, tile) * p.tiles_n;
+        t += tiles * p.splitk;
+        tiles_total += tiles;
     }
-    if (rc && (rows & 3)) return false;
-    return true;
+    return t;
 }
 
 }  // namespace
-
-int m2f_gemm_table_walk(const std::vector<GemmProblem>& prs_all, int walk, int n_wg, int tile_m, int tile_n, std::vector<uint32_t>& tile_rec, std::vector<int>& wg_begin,
-                        const std::vector<int>* only) {
-    const int TILE = tile_n;
-    // `only` (nullable): walk just these problems (records still carry the index into prs_all = the device table)
-    std::vector<size_t> sel;
-    if (only) for (int i : *only) sel.push_back((size_t)i);
-    else for (size_t i = 0; i < prs_all.size(); ++i) sel.push_back(i);
-    struct View { const std::vector<GemmProblem>& a; const std::vector<size_t>& s; size_t size() const { return s.size(); }
-                  const GemmProblem& operator[](size_t i) const { return a[s[i]]; } } prs{prs_all, sel};
-    tile_rec.clear();
-    wg_begin.assign((size_t)n_wg + 1, 0);
-    if (n_wg < 1) return -1;
-    auto rec = [&](size_t p, int mt, int nt) { return (uint32_t)sel[p] | ((uint32_t)mt << 16) | ((uint32_t)nt << 24); };
-    if (prs_all.size() > 65535) return -1;
-    std::vector<std::vector<uint32_t>> per_wg((size_t)n_wg);
-    if (walk == 0) {
-        // problem by problem, m fastest inside a problem, dealt as ring_xcd_remap deals it
-        std::vector<uint32_t> all;
-        for (size_t p = 0; p < prs.size(); ++p) {
-            const int tm = m2f_cdiv(prs[p].M, tile_m), tn = m2f_cdiv(prs[p].N, TILE);
-            if (tm > 255 || tn > 255) return -1;
-            for (int nt = 0; nt < tn; ++nt)
-                for (int mt = 0; mt < tm; ++mt) all.push_back(rec(p, mt, nt));
-        }
-        const int q = n_wg >> 3, r = n_wg & 7;
-        for (int b = 0; b < n_wg; ++b) {
-            const int x = b & 7, j = b >> 3;
-            const int first = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-            for (size_t t = (size_t)first; t < all.size(); t += (size_t)n_wg) per_wg[(size_t)b].push_back(all[t]);
-        }
-    } else {
-        // items = super-tiles of up to 8 (m) x 4 (n) tiles, problem-major, n-strip-major inside a problem (consecutive items
-        // of a strip share their column panels); the item list is cut into eight contiguous ranges of about equal tile count
-        struct Item { std::vector<uint32_t> tiles; };
-        std::vector<Item> items;
-        size_t total = 0;
-        for (size_t p = 0; p < prs.size(); ++p) {
-            const int tm = m2f_cdiv(prs[p].M, tile_m), tn = m2f_cdiv(prs[p].N, TILE);
-            if (tm > 255 || tn > 255) return -1;
-            const int sm = tm < 8 ? tm : 8;
-            int sn = 32 / sm; if (sn < 1) sn = 1; if (sn > tn) sn = tn;
-            for (int n0 = 0; n0 < tn; n0 += sn)
-                for (int m0 = 0; m0 < tm; m0 += sm) {
-                    Item it;
-                    for (int nt = n0; nt < std::min(tn, n0 + sn); ++nt)
-                        for (int mt = m0; mt < std::min(tm, m0 + sm); ++mt) it.tiles.push_back(rec(p, mt, nt));
-                    total += it.tiles.size();
-                    items.push_back(std::move(it));
-                }
-        }
-        const int n_x = n_wg < 8 ? 1 : 8;
-        std::vector<std::vector<uint32_t>> seq((size_t)n_x);
-        size_t done = 0, i = 0;
-        for (int x = 0; x < n_x; ++x) {
-            const size_t target = total * (size_t)(x + 1) / (size_t)n_x;        // cumulative share after XCD x
-            while (i < items.size() && (x == n_x - 1 || done + items[i].tiles.size() / 2 < target)) {
-                seq[(size_t)x].insert(seq[(size_t)x].end(), items[i].tiles.begin(), items[i].tiles.end());
-                done += items[i].tiles.size();
-                ++i;
-            }
-        }
-        // workgroups of XCD x: b = x, x + 8, ... ; the j-th of them takes elements j, j + per_x, ... of the XCD's sequence
-        for (int x = 0; x < n_x; ++x) {
-            std::vector<int> wgs;
-            for (int b = x; b < n_wg; b += n_x) wgs.push_back(b);
-            for (size_t t = 0; t < seq[(size_t)x].size(); ++t) per_wg[(size_t)wgs[t % wgs.size()]].push_back(seq[(size_t)x][t]);
-        }
-    }
-    for (int b = 0; b < n_wg; ++b) {
-        wg_begin[(size_t)b] = (int)tile_rec.size();
-        tile_rec.insert(tile_rec.end(), per_wg[(size_t)b].begin(), per_wg[(size_t)b].end());
-    }
-    wg_begin[(size_t)n_wg] = (int)tile_rec.size();
-    {   // every tile of every problem exactly once, whatever the order
-        std::vector<uint32_t> got = tile_rec, want;
-        for (size_t p = 0; p < prs.size(); ++p)
-            for (int nt = 0; nt < m2f_cdiv(prs[p].N, TILE); ++nt)
-                for (int mt = 0; mt < m2f_cdiv(prs[p].M, tile_m); ++mt) want.push_back(rec(p, mt, nt));
-        std::sort(got.begin(), got.end());
-        std::sort(want.begin(), want.end());
-        if (got != want) return -1;
-    }
-    return (int)tile_rec.size();
-}
 
 #ifdef M2F_EXP_TIMING
 extern "C" int m2f_dbg_read(unsigned long long* out) {
@@ -1374,126 +1141,24 @@ extern "C" int m2f_dbg_read(unsigned long long* out) {
 }
 #endif
 
-hipError_t m2f_launch_gemm_table(const GemmBatch& gb, hipStream_t stream) {
-    if (!gb.table || gb.total_tiles <= 0) return hipErrorInvalidValue;
-    return gb.table_p8 ? m2f_p8_launch_table_rc(gb, stream) : m2f_ring_launch_table_rc_256x128(gb, stream);
-}
-
-hipError_t m2f_launch_gemm_table_acc(const GemmBatch& gb, hipStream_t stream) {
-    if (!gb.table || gb.total_tiles <= 0) return hipErrorInvalidValue;
-    return gb.table_p8 ? m2f_p8_launch_table_rc_acc(gb, stream) : m2f_ring_launch_table_rc_256x128_acc(gb, stream);
-}
-
-hipError_t m2f_ring_launch_256x128_fp8(GemmBatch& gb, hipStream_t stream);      // gemm_ring_256x128_fp8.hip
-
-hipError_t m2f_launch_gemm_fp8(GemmBatch& gb, hipStream_t stream) {
-    m2f_g_last_form = M2F_FORM_NONE;
-    if (gb.count != 1) return hipErrorInvalidValue;
-    GemmProblem& p = gb.pr[0];
-    if (p.M <= 0 || p.N <= 0 || p.a.k[0] <= 0 || p.a.k[1] != 0 || p.a.k[0] != p.b.k[0] || (p.a.k[0] & 15) || !p.a.q[0] || !p.b.q[0] ||
-        (p.a.ldq[0] & 15) || (p.b.ldq[0] & 15) || (reinterpret_cast<uintptr_t>(p.a.q[0]) & 15) || (reinterpret_cast<uintptr_t>(p.b.q[0]) & 15) ||
-        p.gate || (p.flags & (GF_ACCUM | GF_RELU_A | GF_RELU_B)) || p.drop_site)
-        return hipErrorInvalidValue;
-    // the staging code moves 16-byte chunks of a row whatever they hold: hand it the rows in byte pairs
-    p.a.k[0] >>= 1; p.b.k[0] >>= 1; p.a.ldq[0] >>= 1; p.b.ldq[0] >>= 1;
-    const bool gelu = p.flags & GF_GELU_OUT;
-    {   // round 4: 256x256 tiles on the eight-phase schedule (gemm_p8.h, EPI 4) from one chip-filling round on, when its tiles fill whole rounds
-        // (M2F_P8=0 / M2F_P8_MIN as for the bf16 launches; k a multiple of 128)
-        static const int p8_on = getenv("M2F_P8") ? atoi(getenv("M2F_P8")) : 1;
-        static const int p8_min = getenv("M2F_P8_MIN") ? atoi(getenv("M2F_P8_MIN")) : 256;
-        const int t256 = m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 256), rounds = m2f_cdiv(t256, 256);
-        const bool small8 = (size_t)p.M * p.a.ldq[0] * 2 < 0x80000000ull && (size_t)p.N * p.b.ldq[0] * 2 < 0x80000000ull;
-        if (p8_on && small8 && t256 >= p8_min && t256 * 100 >= 85 * rounds * 256 && !(p.a.k[0] & 63) && (!p.c8 || (p.ldc & 7) == 0))
-            return m2f_p8_launch_kc_fp8(gb, stream);
+// Executes a choice of one of the register-staged forms (gemm_dispatch.hip: m2f_gemm_choose / m2f_gemm_choose_fp8): numbers the tiles
+// and switches to the instantiation.
+hipError_t m2f_launch_gemm_staged(GemmBatch& gb, const GemmChoice& ch, int prec, int layout, hipStream_t stream) {
+    const int form = ch.form & 0xFF;
+    const bool a_rc = !ch.b_t && layout == M2F_LAYOUT_TN, b_rc = !ch.b_t && layout != M2F_LAYOUT_NT;
+    bool gelu = false;
+    for (int i = 0; i < gb.count; ++i) gelu = gelu || (gb.pr[i].flags & GF_GELU_OUT);
+    if (form > M2F_FORM_F32SRC_SPLITK) {                        // bf16-source (or e4m3) kernels
+        const int t = m2f_gemm_number_tiles(gb, ch.tile_m, ch.tile_n);
+        if (t == 0) return hipSuccess;
+        const bool fp8 = form == M2F_FORM_FP8_128x128 || form == M2F_FORM_FP8_256x128;
+        return pick_layout(a_rc, b_rc, [&](auto A, auto B) { return launch_tile16<A.value, B.value>(gb, ch.tile_m, gelu, fp8, t, stream); });
     }
-    {   // the ring form (gemm_ring_256x128_fp8.hip) from one chip-filling round of 256x128 tiles on; M2F_RING_FP8=0 keeps the register-staged build
-        static const int ring8 = getenv("M2F_RING_FP8") ? atoi(getenv("M2F_RING_FP8")) : 1;
-        const bool small = (size_t)p.M * p.a.ldq[0] * 2 < 0x80000000ull && (size_t)p.N * p.b.ldq[0] * 2 < 0x80000000ull;
-        const bool whole = p.M % 256 == 0 && p.N % 128 == 0;       // (the ring epilogue writes e4m3 results of whole tiles only)
-        if (ring8 && small && m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 128) >= 256 && !(p.flags & GF_RELU_OUT) && (!p.c8 || whole)) {
-            m2f_g_last_form = M2F_FORM_FP8_RING;
-            return m2f_ring_launch_256x128_fp8(gb, stream);
-        }
-    }
-    int tile_m = 256, tile_n = 128;
-    if (m2f_cdiv(p.M, 256) * m2f_cdiv(p.N, 128) < 1024) { tile_m = 128; tile_n = 128; }
-    p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0; p.tile_begin = 0;
-    p.tiles_n = m2f_cdiv(p.N, tile_n);
-    const int t = m2f_cdiv(p.M, tile_m) * p.tiles_n;
-    if (tile_m == 256)
-        return gelu ? launch_cfg16<false, false, 256, 128, 64, 2, false, true, true>(gb, t, stream)
-                    : launch_cfg16<false, false, 256, 128, 64, 2, false, false, true>(gb, t, stream);
-    return gelu ? launch_cfg16<false, false, 128, 128, 64, 3, false, true, true>(gb, t, stream)
-                : launch_cfg16<false, false, 128, 128, 64, 3, false, false, true>(gb, t, stream);
-}
-
-// Will m2f_launch_gemm stage this bf16-mode launch from the operands' bf16 shadows (true), or from their fp32 originals?  (Host-side
-// mirror of the dispatch below, for plan.hip::mark_unread_fp32.)
-bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout) {
-    const bool a_rc = layout == M2F_LAYOUT_TN, b_rc = layout != M2F_LAYOUT_NT;
-    if (layout == M2F_LAYOUT_NN) {
-        bool all_t = true;
-        for (int i = 0; i < gb.count; ++i)
-            for (int sgm = 0; sgm < 2; ++sgm)
-                if (gb.pr[i].b.k[sgm] && !gb.pr[i].b.qt[sgm]) all_t = false;
-        if (all_t) {
-            GemmBatch t = gb;
-            for (int i = 0; i < t.count; ++i)
-                for (int sgm = 0; sgm < 2; ++sgm) { t.pr[i].b.q[sgm] = t.pr[i].b.qt[sgm]; t.pr[i].b.ldq[sgm] = t.pr[i].b.ldqt[sgm]; }
-            if (src16_ok(t, false, false)) return true;
-        }
-    }
-    return src16_ok(gb, a_rc, b_rc);
-}
-
-hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStream_t stream) {
-    m2f_g_last_form = M2F_FORM_NONE;
-    if (gb.count <= 0 || gb.count > M2F_GEMM_MAX_PROBLEMS) return hipErrorInvalidValue;
-    const bool a_rc = layout == M2F_LAYOUT_TN;
-    const bool b_rc = layout != M2F_LAYOUT_NT;
-    for (int i = 0; i < gb.count; ++i) {
-        GemmProblem& p = gb.pr[i];
-        if (p.a.k[0] != p.b.k[0] || p.a.k[1] != p.b.k[1] || p.M <= 0 || p.N <= 0 || p.a.k[0] <= 0)
-            return hipErrorInvalidValue;
-        if (p.drop_site && !gb.rng) return hipErrorInvalidValue;
-        p.flags &= ~(uint32_t)(GF_VEC_A | GF_VEC_B);
-        if (vec_ok(p.a, a_rc, p.M)) p.flags |= GF_VEC_A;
-        if (vec_ok(p.b, b_rc, p.N)) p.flags |= GF_VEC_B;
-    }
-    {   // the classifier head's [T, n_classes] problems: FMA kernels over the whole chip instead of one column of MFMA tiles (skinny.hip)
-        const int sk = m2f_launch_gemm_skinny(gb, prec, layout, stream);
-        if (sk == 1) return hipSuccess;
-        if (sk < 0) return (hipError_t)(-sk);
-    }
-    if (prec == M2F_PREC_BF16 && layout == M2F_LAYOUT_NN) {
-        // dgrad against a weight whose TRANSPOSED bf16 shadow exists runs as the k-contiguous (forward) form, the
-        // fastest staging path: C = A * B  ==  A * (B^T)^T
-        bool all_t = true;
-        for (int i = 0; i < gb.count; ++i)
-            for (int sgm = 0; sgm < 2; ++sgm)
-                if (gb.pr[i].b.k[sgm] && !gb.pr[i].b.qt[sgm]) all_t = false;
-        if (all_t) {
-            GemmBatch t = gb;
-            for (int i = 0; i < t.count; ++i)
-                for (int sgm = 0; sgm < 2; ++sgm) { t.pr[i].b.q[sgm] = t.pr[i].b.qt[sgm]; t.pr[i].b.ldq[sgm] = t.pr[i].b.ldqt[sgm]; }
-            if (src16_ok(t, false, false)) {
-                const hipError_t e = launch_tile16<false, false>(t, tile, stream);
-                m2f_g_last_form |= M2F_FORM_NN_T;
-                return e;
-            }
-        }
-    }
-    if (prec == M2F_PREC_BF16 && src16_ok(gb, a_rc, b_rc)) {
-        if (layout == M2F_LAYOUT_NT) return launch_tile16<false, false>(gb, tile, stream);
-        if (layout == M2F_LAYOUT_NN) return launch_tile16<false, true>(gb, tile, stream);
-        return launch_tile16<true, true>(gb, tile, stream);
-    }
-    if (prec == M2F_PREC_F32) {
-        if (layout == M2F_LAYOUT_NT) return launch_tile<M2F_PREC_F32, false, false>(gb, tile, stream);
-        if (layout == M2F_LAYOUT_NN) return launch_tile<M2F_PREC_F32, false, true>(gb, tile, stream);
-        return launch_tile<M2F_PREC_F32, true, true>(gb, tile, stream);
-    }
-    if (layout == M2F_LAYOUT_NT) return launch_tile<M2F_PREC_BF16, false, false>(gb, tile, stream);
-    if (layout == M2F_LAYOUT_NN) return launch_tile<M2F_PREC_BF16, false, true>(gb, tile, stream);
-    return launch_tile<M2F_PREC_BF16, true, true>(gb, tile, stream);
+    const int t = number_tiles_splitk(gb, ch.tile_m, bk_f32src(prec, ch.tile_m), ch.splitk);
+    if (t == 0) return hipSuccess;
+    const bool vec = ch.form & M2F_FORM_VEC;                    // 16-byte loads: every operand of every problem allows them
+    return pick_layout(a_rc, b_rc, [&](auto A, auto B) {
+        if (prec == M2F_PREC_F32) return launch_tile<M2F_PREC_F32, A.value, B.value>(gb, ch.tile_m == 128, vec, gelu, t, stream);
+        return launch_tile<M2F_PREC_BF16, A.value, B.value>(gb, ch.tile_m == 128, vec, gelu, t, stream);
+    });
 }

@@ -898,27 +898,10 @@ hipError_t launch_p8_grid(const GemmBatch& hb, int tiles, hipStream_t stream) {
 // grouped launch (problems in the kernel arguments): tile order m fastest inside a problem, workgroups walk remap(b), + grid, ...
 template <bool RC, int EPI>
 hipError_t launch_p8_grouped(GemmBatch& gb, hipStream_t stream) {
-    int t = 0;
-    for (int i = 0; i < gb.count; ++i) {
-        GemmProblem& p = gb.pr[i];
-        p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0;
-        p.tile_begin = t;
-        p.tiles_n = m2f_cdiv(p.N, P8Cfg::BN);
-        t += m2f_cdiv(p.M, P8Cfg::BM) * p.tiles_n;
-    }
+    const int t = m2f_gemm_number_tiles(gb, P8Cfg::BM, P8Cfg::BN);
     if (t == 0) return hipSuccess;
     GemmBatch hb = gb;
-    for (int i = 0; i < M2F_GEMM_MAX_PROBLEMS; ++i) {
-        hb.tb[i] = i < gb.count ? gb.pr[i].tile_begin : 0x7fffffff;
-        GemmHot& h = hb.hot[i];
-        memset(&h, 0, sizeof(h));
-        if (i >= gb.count) continue;
-        const GemmProblem& p = gb.pr[i];
-        h.aq[0] = p.a.q[0]; h.aq[1] = p.a.q[1]; h.bq[0] = p.b.q[0]; h.bq[1] = p.b.q[1];
-        h.M = p.M; h.N = p.N; h.k[0] = p.a.k[0]; h.k[1] = p.a.k[1];
-        h.ldaq[0] = p.a.ldq[0]; h.ldaq[1] = p.a.ldq[1]; h.ldbq[0] = p.b.ldq[0]; h.ldbq[1] = p.b.ldq[1];
-        h.flags = p.flags; h.tile_begin = p.tile_begin; h.has_bias_grad = 0;
-    }
+    m2f_gemm_fill_hot(hb, false);
     hb.total_tiles = t;
     {
         int dev = 0, n_cu = 256; hipDeviceProp_t prop;

@@ -14,15 +14,20 @@ static int p8_skew_env() {
     static const int v = getenv("M2F_P8_SKEW") ? atoi(getenv("M2F_P8_SKEW")) : (0x20000000 | 3000);
     return v;
 }
+// the skew of a table launch (in its own copy of the batch): only where the walk's longest tile list is known (the plan / the test
+// entry fill p8_max_tiles), and the default one unless the caller chose
+static void p8_table_skew(GemmBatch& hb) {
+    if (!hb.p8_max_tiles) hb.p8_skew = 0;
+    else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
+}
 
 // the table launch: EPI 1 = overwrite, EPI 5 = accumulate (dW and the bias gradients leave as old + new; m2f_plan_accumulate_grads -
 // its own instantiation, so the overwrite form compiles as it did; fp contraction is off for the whole unit: gemm_ring.h's pragma)
 template <int EPI>
 static hipError_t p8_launch_table(const GemmBatch& gb, hipStream_t stream) {
     GemmBatch hb = gb;                                   // (ReLU on the A operand has no loop copy in this form: m2f_gemm_p8_table_ok)
-    m2f_g_last_form = M2F_FORM_P8_RC;
-    if (!hb.p8_max_tiles) hb.p8_skew = 0;               // (the plan / the test entry fill p8_max_tiles from the walk)
-    else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
+    p8_table_skew(hb);
+    m2f_g_last_form = M2F_FORM_P8_RC;                    // (table launches do not go through the chooser)
     return launch_p8_grid<true, true, EPI>(hb, hb.total_tiles, stream);
 }
 hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream) { return p8_launch_table<1>(gb, stream); }
@@ -31,7 +36,6 @@ hipError_t m2f_p8_launch_table_rc_acc(const GemmBatch& gb, hipStream_t stream) {
 // forward-form launches whose epilogue is bias / ReLU / GELU / residual (m2f_gemm_ring256_ok) and whose k is a multiple of 64
 hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream) {
     gb.p8_skew = p8_skew_env();
-    m2f_g_last_form = M2F_FORM_P8_KC;
     return launch_p8_grouped<false, 2>(gb, stream);
 }
 
@@ -39,7 +43,6 @@ hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream) {
 // the staging code moves 16-byte chunks of a row whatever they hold): de-quantising epilogue, fp32 / bf16 / e4m3 result
 hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream) {
     gb.p8_skew = p8_skew_env();
-    m2f_g_last_form = M2F_FORM_FP8_P8;
     return launch_p8_grouped<false, 4>(gb, stream);
 }
 
@@ -47,8 +50,7 @@ hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream) {
 hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream) {
     if (!gb.adam) return hipErrorInvalidValue;
     GemmBatch hb = gb;
-    if (!hb.p8_max_tiles) hb.p8_skew = 0;
-    else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
+    p8_table_skew(hb);
     return launch_p8_grid<true, true, 3>(hb, hb.total_tiles, stream);
 }
 
@@ -56,24 +58,8 @@ hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream) 
 hipError_t m2f_p8_launch_table_rc_adam_grouped(const GemmBatch& gb, hipStream_t stream) {
     if (!gb.adam) return hipErrorInvalidValue;
     GemmBatch hb = gb;
-    if (!hb.p8_max_tiles) hb.p8_skew = 0;
-    else if (!hb.p8_skew) hb.p8_skew = p8_skew_env();
+    p8_table_skew(hb);
     return launch_p8_grid<true, true, 6>(hb, hb.total_tiles, stream);
-}
-
-bool m2f_gemm_p8_table_ok(const std::vector<GemmProblem>& prs) {
-    for (const GemmProblem& p : prs)
-        if ((p.flags & GF_RELU_A) || p.a.k[1] || p.b.k[1]) return false;
-    return true;
-}
-
-bool m2f_gemm_p8_ok(const GemmBatch& gb) {
-    if (!m2f_gemm_ring256_ok(gb)) return false;
-    for (int i = 0; i < gb.count; ++i) {
-        const GemmProblem& p = gb.pr[i];
-        if (p.a.k[1] != 0 || p.b.k[1] != 0 || (p.a.k[0] & 63) || (p.flags & GF_RELU_A)) return false;
-    }
-    return true;
 }
 
 extern std::string g_m2f_p8_err;
@@ -101,6 +87,7 @@ extern "C" int m2f_gemm_p8(int rc, int M, int N, int K, const uint16_t* a, int l
     if (!rc) {
         gb.pr[0] = p; gb.count = 1;
         if (!m2f_gemm_p8_ok(gb) || bias_grad) return -1;
+        m2f_g_last_form = M2F_FORM_P8_KC;                // (the direct entry does not go through the chooser)
         return m2f_p8_launch_kc(gb, s) == hipSuccess ? 0 : -2;
     }
     std::vector<GemmProblem> prs{p};

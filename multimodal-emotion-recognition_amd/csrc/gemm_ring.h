@@ -11,8 +11,6 @@
 // (same setting as gemm.hip: the register-staged kernels repeat this arithmetic and must round identically)
 #pragma clang fp contract(off)
 
-extern long long m2f_g_ring_launches;         // host-side count of ring-form launches (gemm_ring.hip)
-
 namespace {
 
 #ifdef M2F_EXP_TIMING
@@ -785,27 +783,10 @@ hipError_t launch_ring_grid(const GemmBatch& hb, int t, hipStream_t stream) {
 
 template <int BM, int BN, int S, int EPI = 0>
 hipError_t launch_ring16(GemmBatch& gb, hipStream_t stream) {
-    int t = 0;
-    for (int i = 0; i < gb.count; ++i) {
-        GemmProblem& p = gb.pr[i];
-        p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0;
-        p.tile_begin = t;
-        p.tiles_n = m2f_cdiv(p.N, BN);
-        t += m2f_cdiv(p.M, BM) * p.tiles_n;
-    }
+    const int t = m2f_gemm_number_tiles(gb, BM, BN);
     if (t == 0) return hipSuccess;
     GemmBatch hb = gb;
-    for (int i = 0; i < M2F_GEMM_MAX_PROBLEMS; ++i) {
-        hb.tb[i] = i < gb.count ? gb.pr[i].tile_begin : 0x7fffffff;
-        GemmHot& h = hb.hot[i];
-        memset(&h, 0, sizeof(h));
-        if (i >= gb.count) continue;
-        const GemmProblem& p = gb.pr[i];
-        h.aq[0] = p.a.q[0]; h.aq[1] = p.a.q[1]; h.bq[0] = p.b.q[0]; h.bq[1] = p.b.q[1];
-        h.M = p.M; h.N = p.N; h.k[0] = p.a.k[0]; h.k[1] = p.a.k[1];
-        h.ldaq[0] = p.a.ldq[0]; h.ldaq[1] = p.a.ldq[1]; h.ldbq[0] = p.b.ldq[0]; h.ldbq[1] = p.b.ldq[1];
-        h.flags = p.flags; h.tile_begin = p.tile_begin; h.has_bias_grad = 0;
-    }
+    m2f_gemm_fill_hot(hb, false);
     hb.total_tiles = t;
     return launch_ring_grid<BM, BN, S, false, EPI>(hb, t, stream);
 }

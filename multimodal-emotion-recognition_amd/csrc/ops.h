@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include "../../include/m2fnet_hip.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -119,18 +120,41 @@ struct M2FAdamFuse {
 };
 #define M2F_SPLITK_MAX_TILES 512
 
-// RING form of the k-contiguous bf16 GEMM (gemm_ring.h): bm x bn = 128x128 or 128x64; the table form walks gb.table.
-extern int m2f_g_last_form;        // host-side record of the kernel form the last GEMM launch dispatched to (M2F_FORM_*, gemm_ring.hip)
-int m2f_launch_gemm_skinny(const GemmBatch& gb, int prec, int layout, hipStream_t stream);      // skinny.hip: 1 launched, 0 not skinny, < 0 error
-bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout);      // host: does the bf16-mode launch read bf16 shadows only?
-bool m2f_gemm_ring_ok(const GemmBatch& gb);
-bool m2f_gemm_ring256_ok(const GemmBatch& gb);       // 256x128 tiles: bias / ReLU / GELU / residual epilogues only
-hipError_t m2f_launch_gemm_ring(GemmBatch& gb, int bm, int bn, hipStream_t stream);
+// ---- GEMM dispatch (gemm_dispatch.hip): which kernel form a launch takes ------------------------------------------------------
+// The knobs of that policy, read from the environment once, at first use (defaults and their measured reasons: m2f_gemm_knobs)
+struct GemmKnobs {
+    int ring, ring_min, ring64_min, ring32_min, ring256_min, ring256_2r;      // M2F_RING, _RING_MIN, _RING64_MIN, _RING32_MIN, _RING256_MIN, _RING256_2R
+    int p8, p8_min, ring_fp8, skinny;                                         // M2F_P8, M2F_P8_MIN, M2F_RING_FP8, M2F_SKINNY
+};
+const GemmKnobs& m2f_gemm_knobs();
+// What the chooser decides for one launch; the launchers only execute it.
+struct GemmChoice {
+    int form;              // the complete M2F_FORM_* value, M2F_FORM_VEC / _SRC16 / _NN_T included (M2F_FORM_NONE: nothing to launch)
+    int tile_m, tile_n;
+    bool src16;            // every operand is staged from its bf16 shadow (no kernel of the launch reads the fp32 originals)
+    bool b_t;              // NN launch run as the k-contiguous form: B is taken through its transposed shadow (qt / ldqt)
+    int splitk;            // wanted split-K factor (1: none); a problem takes min(splitk, k-tiles / 2)
+};
+// Pure: no HIP call, nothing written, no global read but the knobs.  m2f_gemm_choose expects a validated batch (m2f_launch_gemm);
+// the fp8 chooser sees k / ldq in BYTES, as m2f_gemm_fp8 passes them (before the launcher halves them into byte pairs).
+GemmChoice m2f_gemm_choose(const GemmBatch& gb, int prec, int layout, int tile);
+GemmChoice m2f_gemm_choose_fp8(const GemmBatch& gb);
+extern int m2f_g_last_form;        // host-side record of the kernel form the last GEMM launch took (M2F_FORM_*); dispatched launches: set in gemm_execute
+extern long long m2f_g_ring_launches;         // host-side count of ring-form and eight-phase launches
+bool m2f_gemm_stages_bf16(const GemmBatch& gb, int layout);      // host: does the bf16-mode launch read bf16 shadows only?  (the chooser's answer)
+// eligibility (b_t: B's shadow is the transposed one): the ring forms, the 256x128 ring form (bias / ReLU / GELU / residual epilogues
+// only), the eight-phase 256x256 form (that epilogue set, single segment, k % 64 == 0)
+bool m2f_gemm_ring_ok(const GemmBatch& gb, bool b_t = false);
+bool m2f_gemm_ring256_ok(const GemmBatch& gb, bool b_t = false);
+bool m2f_gemm_p8_ok(const GemmBatch& gb, bool b_t = false);
+// the launchers a choice is executed by
+hipError_t m2f_launch_gemm_skinny(const GemmBatch& gb, const GemmChoice& ch, int prec, hipStream_t stream);      // skinny.hip
+hipError_t m2f_launch_gemm_staged(GemmBatch& gb, const GemmChoice& ch, int prec, int layout, hipStream_t stream);      // gemm.hip: register-staged kernels
+hipError_t m2f_launch_gemm_ring(GemmBatch& gb, int bm, int bn, hipStream_t stream);      // gemm_ring_<bm>x<bn>.hip
+hipError_t m2f_ring_launch_256x128_fp8(GemmBatch& gb, hipStream_t stream);                 // gemm_ring_256x128_fp8.hip
 hipError_t m2f_ring_launch_table_rc_256x128(const GemmBatch& gb, hipStream_t stream);      // the table form, 256 x 128 tiles (gemm_ring_table.hip)
 hipError_t m2f_ring_launch_table_rc_256x128_acc(const GemmBatch& gb, hipStream_t stream);  // ... its accumulate form, old + new (gemm_ring_table_acc.hip)
-// eight-phase 256x256 form (gemm_p8.h): forward-form launches with the 256x128 ring form's epilogue set, single segment, k % 64 == 0
-bool m2f_gemm_p8_ok(const GemmBatch& gb);
-hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream);
+hipError_t m2f_p8_launch_kc(GemmBatch& gb, hipStream_t stream);                            // gemm_p8.hip
 hipError_t m2f_p8_launch_kc_fp8(GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc(const GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream);     // Adam in the epilogue (gb.adam)
@@ -138,6 +162,45 @@ hipError_t m2f_p8_launch_table_rc_adam(const GemmBatch& gb, hipStream_t stream);
 // fp8 launches alone use that field otherwise) - gb.adam->hyper is not read; the update multiplies the parameter by the row's `decay` first
 hipError_t m2f_p8_launch_table_rc_adam_grouped(const GemmBatch& gb, hipStream_t stream);
 hipError_t m2f_p8_launch_table_rc_acc(const GemmBatch& gb, hipStream_t stream);      // accumulate form: dW, bias gradients = old + new
+
+// Numbers the tiles of a grouped launch of bm x bn tiles without split-K (tile_begin, tiles_n of every problem) -> tiles of the launch
+static inline int m2f_gemm_number_tiles(GemmBatch& gb, int bm, int bn) {
+    int t = 0;
+    for (int i = 0; i < gb.count; ++i) {
+        GemmProblem& p = gb.pr[i];
+        p.splitk = 1; p.slab_begin = 0; p.cnt_begin = 0;
+        p.tile_begin = t;
+        p.tiles_n = (p.N + bn - 1) / bn;
+        t += ((p.M + bm - 1) / bm) * p.tiles_n;
+    }
+    return t;
+}
+// split-K factor a problem takes under the launch's wish `want`: at least two k-tiles (of bk) per slice
+static inline int m2f_gemm_splitk_of(const GemmProblem& p, int want, int bk) {
+    const int nk = (p.a.k[0] + bk - 1) / bk + (p.a.k[1] + bk - 1) / bk;
+    const int sp = want < nk / 2 ? want : nk / 2;
+    return sp < 1 ? 1 : sp;
+}
+// Fills the compact header of the launcher's own copy of a numbered batch (tb[], hot[]) from its pr[]; has_bias_grad: the kernel
+// can emit one (the ring forms cannot and pass false)
+static inline void m2f_gemm_fill_hot(GemmBatch& hb, bool has_bias_grad) {
+    for (int i = 0; i < M2F_GEMM_MAX_PROBLEMS; ++i) {
+        hb.tb[i] = i < hb.count ? hb.pr[i].tile_begin : 0x7fffffff;
+        GemmHot& h = hb.hot[i];
+        memset(&h, 0, sizeof(h));
+        if (i >= hb.count) continue;
+        const GemmProblem& p = hb.pr[i];
+        h.aq[0] = p.a.q[0]; h.aq[1] = p.a.q[1]; h.bq[0] = p.b.q[0]; h.bq[1] = p.b.q[1];
+        h.M = p.M; h.N = p.N; h.k[0] = p.a.k[0]; h.k[1] = p.a.k[1];
+        h.ldaq[0] = p.a.ldq[0]; h.ldaq[1] = p.a.ldq[1]; h.ldbq[0] = p.b.ldq[0]; h.ldbq[1] = p.b.ldq[1];
+        h.flags = p.flags; h.tile_begin = p.tile_begin; h.has_bias_grad = has_bias_grad && p.bias_grad != nullptr;
+    }
+}
+// host: the bf16 shadow of C when it lies in the shadowed workspace, else null (the skinny kernels take it as an argument)
+static inline uint16_t* m2f_gemm_c_shadow(const GemmBatch& gb, const float* c) {
+    const ptrdiff_t i = gb.sh.shadow && c >= gb.sh.ws_base ? c - gb.sh.ws_base : -1;
+    return (i >= 0 && (size_t)i < gb.sh.ws_floats) ? gb.sh.shadow + i : nullptr;
+}
 
 // Launches one grouped GEMM. Returns hipSuccess or the launch error. `tile` = 0 (auto), 64 or 128.
 hipError_t m2f_launch_gemm(GemmBatch& gb, int prec, int layout, int tile, hipStream_t stream);

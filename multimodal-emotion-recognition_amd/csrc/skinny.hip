@@ -4,12 +4,11 @@
 //   NT, N <= 8:  C[t][n] = sum_k A[t][k] B[n][k] (+ bias[n]) (ReLU)            one wavefront per token row
 //   NN, K <= 8:  C[t][j] = sum_c A[t][c] B[c][j], then the ReLU / dropout gate  one thread per four output columns
 // Operand precision follows the MFMA kernels they replace: bf16 mode multiplies bf16-rounded operands (read from the bf16 shadows
-// when EVERY operand of the launch has one - the rule plan.hip::mark_unread_fp32 mirrors - else rounded on the way in) and
+// when EVERY operand of the launch has one - the chooser's rule, which plan_build.hip::mark_unread_fp32 asks too - else rounded on the way in) and
 // accumulates in fp32; fp32 mode is plain fp32.  Only the summation order differs from the MFMA forms.
 #include "common.h"
 #include "ops.h"
 #include <cstring>
-#include <cstdlib>
 
 namespace {
 
@@ -171,44 +170,19 @@ __global__ __launch_bounds__(256) void m2f_skinny_nn_kernel(const SkinnyArgs s) 
 
 }  // namespace
 
-// 1: launched; 0: not a skinny problem (the caller goes on to the MFMA kernels); < 0: HIP error code (negated)
-int m2f_launch_gemm_skinny(const GemmBatch& gb, int prec, int layout, hipStream_t stream) {
-    static const int on = getenv("M2F_SKINNY") ? atoi(getenv("M2F_SKINNY")) : 1;
-    if (!on || gb.count != 1 || (prec != M2F_PREC_BF16 && prec != M2F_PREC_F32)) return 0;
+// Executes a skinny choice (gemm_dispatch.hip decides eligibility, the shadow-source rule and the 16-byte rule: ch.form)
+hipError_t m2f_launch_gemm_skinny(const GemmBatch& gb, const GemmChoice& ch, int prec, hipStream_t stream) {
     const GemmProblem& p = gb.pr[0];
-    const int K = p.a.k[0];
-    if (p.a.k[1] || p.b.k[1] || p.res || p.drop_site || p.c8 || p.bias_grad || !p.c || K < 1 ||
-        (p.flags & (GF_ACCUM | GF_RELU_A | GF_RELU_B | GF_GELU_OUT)))
-        return 0;
-    // (whatever M: a token row's result must not depend on how many rows the launch has - packed and padded plans agree bit for bit)
-    const bool nt = layout == M2F_LAYOUT_NT && p.N <= 8 && !p.gate;
-    const bool nn = layout == M2F_LAYOUT_NN && K <= 8;
-    if (!nt && !nn) return 0;
+    const bool nt = (ch.form & 0xFF) == M2F_FORM_SKINNY_NT;
     SkinnyArgs s = {};
-    const bool use16 = prec == M2F_PREC_BF16 && p.a.q[0] && p.b.q[0] && m2f_gemm_stages_bf16(gb, layout);      // the launcher's own rule
     s.a = p.a.p[0]; s.b = p.b.p[0]; s.lda = p.a.ld[0]; s.ldb = p.b.ld[0];
-    if (use16) { s.a16 = p.a.q[0]; s.b16 = p.b.q[0]; s.lda16 = p.a.ldq[0]; s.ldb16 = p.b.ldq[0]; }
-    else if (!s.a || !s.b) return 0;
-    s.r16 = prec == M2F_PREC_BF16 && !use16;
-    s.c = p.c; s.ldc = p.ldc;
-    {
-        const ptrdiff_t i = gb.sh.shadow && p.c >= gb.sh.ws_base ? p.c - gb.sh.ws_base : -1;
-        s.c16 = (i >= 0 && (size_t)i < gb.sh.ws_floats) ? gb.sh.shadow + i : nullptr;
-    }
+    if (ch.src16) { s.a16 = p.a.q[0]; s.b16 = p.b.q[0]; s.lda16 = p.a.ldq[0]; s.ldb16 = p.b.ldq[0]; }
+    s.r16 = prec == M2F_PREC_BF16 && !ch.src16;
+    s.c = p.c; s.ldc = p.ldc; s.c16 = m2f_gemm_c_shadow(gb, p.c);
     s.bias = p.bias; s.gate = p.gate; s.ldgate = p.ldgate; s.gscale = p.gate_scale;
-    s.M = p.M; s.N = p.N; s.K = K; s.relu_out = (p.flags & GF_RELU_OUT) ? 1 : 0;
-    auto al = [](const void* q, int a) { return (reinterpret_cast<uintptr_t>(q) & (uintptr_t)(a - 1)) == 0; };
-    if (nt) {       // rows of A and B in 16-byte chunks
-        s.vec = use16 ? ((K & 7) == 0 && (s.lda16 & 7) == 0 && (s.ldb16 & 7) == 0 && al(s.a16, 16) && al(s.b16, 16))
-                      : ((K & 3) == 0 && (s.lda & 3) == 0 && (s.ldb & 3) == 0 && al(s.a, 16) && al(s.b, 16));
-    } else {        // four columns of B's rows, the gate, C (and their bf16 forms: 8 bytes)
-        s.vec = (p.N & 3) == 0 && (s.ldc & 3) == 0 && al(s.c, 16) && (!s.c16 || al(s.c16, 8)) && (!s.bias || al(s.bias, 16)) &&
-                (!s.gate || ((s.ldgate & 3) == 0 && al(s.gate, 16))) &&
-                (use16 ? ((s.ldb16 & 3) == 0 && al(s.b16, 8)) : ((s.ldb & 3) == 0 && al(s.b, 16)));
-    }
-    m2f_g_last_form = (nt ? M2F_FORM_SKINNY_NT : M2F_FORM_SKINNY_NN) | (s.vec ? M2F_FORM_VEC : 0) | (use16 ? M2F_FORM_SRC16 : 0);
+    s.M = p.M; s.N = p.N; s.K = p.a.k[0]; s.relu_out = (p.flags & GF_RELU_OUT) ? 1 : 0;
+    s.vec = (ch.form & M2F_FORM_VEC) ? 1 : 0;
     if (nt) hipLaunchKernelGGL(m2f_skinny_nt_kernel, dim3((p.M + 3) / 4), dim3(256), 0, stream, s);
     else hipLaunchKernelGGL(m2f_skinny_nn_kernel, dim3((unsigned)(((size_t)p.M * ((p.N + 3) >> 2) + 255) / 256)), dim3(256), 0, stream, s);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 1 : -(int)e;
+    return hipGetLastError();
 }

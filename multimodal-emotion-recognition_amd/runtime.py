@@ -106,6 +106,7 @@ SIGNATURES = {
     "m2f_plan_num_launches": (c_int, [c_void_p, c_int]),
     "m2f_gemm_ring_launches": (ctypes.c_longlong, []),
     "m2f_gemm_last_form": (c_int, []),
+    "m2f_gemm_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_uint32, ctypes.POINTER(c_int)]),
     "m2f_forward": (c_int, [c_void_p, c_void_p]),
     "m2f_loss": (c_int, [c_void_p, c_float, c_int, c_int, c_void_p]),
     "m2f_backward": (c_int, [c_void_p, c_void_p]),

@@ -22,6 +22,9 @@ integer pre-activation - a bound below half an integer step, so a dropped or mis
 
 Not reachable here: the NN form through TRANSPOSED bf16 shadows (m2f_gemm passes no transposed shadows; only plans do) and
 grouped multi-problem launches (plans only; the model tests cover them).
+The dispatch itself - which form a launch takes at each threshold - is pinned by tests/golden/gemm_dispatch_forms.json: one case per
+form is launched here and must take the recorded form, which m2f_gemm_form (the chooser without a launch) must name too; at a threshold
+the two neighbours and the register-staged form agree bit for bit.
 The module prints a coverage table: form -> cases -> elements compared.
 """
 import ctypes
@@ -306,6 +309,55 @@ def test_ring_forms_are_exact(form):
              (R, W, 1000, 72, full), (R, W + 1, 520, 0, full)]
     for i, (M, N, K, K1, terms) in enumerate(cases):
         _gemm_case(form, M, N, K, 0, 1, K1=K1, src16=True, terms=terms, seed=800 + 10 * form + i, unaligned_out=N % 4 != 0)
+
+
+# ---- the dispatch thresholds (tests/golden/gemm_dispatch_forms.json, recorded from the build in front of csrc/gemm_dispatch.hip) --------
+
+def _dispatch_cases():
+    import json
+    import make_gemm_dispatch_forms as D
+    return D, {c["name"]: c for c in json.load(open(D.FIXTURE))["cases"]}
+
+
+def _one_case_per_form():
+    """the cheapest fixture case of every form"""
+    _, cases = _dispatch_cases()
+    best = {}
+    for c in cases.values():
+        cost = c["M"] * c["N"] * (c["K0"] + c["K1"])
+        if c["form"] & 0xFF not in best or cost < best[c["form"] & 0xFF][0]:
+            best[c["form"] & 0xFF] = (cost, c["name"])
+    return [name for _, (_, name) in sorted(best.items())]
+
+
+@pytest.mark.parametrize("name", _one_case_per_form())
+def test_a_launch_takes_the_form_the_fixture_and_the_dry_entry_name(name):
+    """m2f_gemm / m2f_gemm_fp8 dispatch to the recorded form, and m2f_gemm_form - the same chooser, nothing launched - names it too"""
+    D, cases = _dispatch_cases()
+    c = cases[name]
+    got, _ = D.run_case(c)
+    dry = _lib().m2f_gemm_form(*D.dry_args(c), None)
+    assert got == c["form"] == dry, f"{name}: launched 0x{got:03x}, recorded 0x{c['form']:03x}, m2f_gemm_form 0x{dry:03x}"
+    _record("dispatch: " + FORMS[got & 0xFF], 0)
+
+
+@pytest.mark.parametrize("below,at", [("ring64x64_79_tiles", "ring64x64_80_tiles"), ("ring128x64_149_tiles", "ring128x64_150_tiles"),
+                                      ("ring128x128_199_tiles", "ring128x128_200_tiles"), ("p8_255_tiles", "p8_256_tiles")])
+def test_results_do_not_move_at_a_threshold(below, at):
+    """the first launch at a threshold, its neighbour below it and the register-staged form of the same problem (a forced tile takes no
+    LDS-DMA form), on the same integer data: the rows they share agree bit for bit"""
+    D, cases = _dispatch_cases()
+    lo, hi = cases[below], cases[at]
+    assert (lo["N"], lo["K0"], lo["K1"], lo["bits"]) == (hi["N"], hi["K0"], hi["K1"], hi["bits"]) and lo["M"] < hi["M"]
+    A, B = X.ints((hi["M"], hi["K0"]), 21).to(DEV), X.ints((hi["N"], hi["K0"]), 22).to(DEV)
+    f_hi, c_hi = D.run_case(hi, A, B)
+    f_lo, c_lo = D.run_case(lo, A[:lo["M"]].contiguous(), B)
+    f_st, c_st = D.run_case(dict(hi, tile=64), A, B)
+    assert (f_hi, f_lo) == (hi["form"], lo["form"]) and f_hi != f_lo and f_st & 0xFF == 4, (hex(f_hi), hex(f_lo), hex(f_st))
+    _equal(c_st, A.double() @ B.double().t(), f"{at}: register-staged")
+    assert torch.equal(c_hi, c_st), f"{at}: {FORMS[f_hi & 0xFF]} differs from the register-staged form"
+    assert torch.equal(c_lo, c_st[:lo["M"]]), f"{below}: {FORMS[f_lo & 0xFF]} differs from the register-staged form"
+    _record("dispatch: across " + FORMS[f_hi & 0xFF] + " threshold", c_hi.numel() + c_lo.numel())
 
 
 # ---- eight-phase form --------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Per-launch floor of the chain GEMMs (forward + input-gradient launches) of one bf16 step against what they take.
 
-For every grouped GEMM launch of the plan (m2f_plan_gemm_shapes) the tile configuration the launcher picks (gemm.hip::launch_tile16:
+For every grouped GEMM launch of the plan (m2f_plan_gemm_shapes) the tile configuration the launcher picks (gemm_dispatch.hip::m2f_gemm_choose:
 256x128 for two-round launches, 128x128 from 200 tiles, 128x64 from 150, 64x64 from 80, register-staged 64x64 below) and two bounds
 per workgroup tile, in cycles:
     mfma   = BM BN K / 2048        (4 SIMDs x 1,024 bf16 FLOP per clock, both waves of a SIMD sharing its pipe)
