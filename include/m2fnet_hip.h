@@ -62,7 +62,8 @@ enum {
     M2F_BUF_STREAM_ATTN = 18,   /* float [sites][S][H_site][C]  stream plans with m2f_plan_stream_attention on: the caller's buffer (NULL: off) */
     M2F_BUF_SPEAKERS = 19,      /* uint8 [T]  input of a plan with speaker heads (m2f_plan_attention_speakers): the speaker id of every token row, in the plan's token order (padded: [B*L] as M2F_BUF_KEYPAD; packed: row cu[b] + i); stream plans: [S], chunk plans [S*T] - the new utterances' ids */
     M2F_BUF_STREAM_SPEAKERS = 20,   /* uint8 [S][C]  stream plans with speaker heads: the caller's buffer of cached speaker ids by logical cache row (m2f_plan_stream_speakers; NULL: none) */
-    M2F_BUF_COUNT = 21
+    M2F_BUF_FOCAL = 21,         /* float [1]  train and eval plans, input of the focal criterion (m2f_plan_focal): gamma (read on the device at every step) */
+    M2F_BUF_COUNT = 22
 };
 
 const char* m2f_last_error(void);
@@ -423,6 +424,11 @@ int64_t m2f_eval_record_bytes(int C);
 int m2f_eval_scores(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
                     void* scratch, void* record, m2f_stream_t stream);
 int m2f_eval_step(m2f_plan* plan, float label_smoothing, int use_class_weights, void* record, int use_graph, m2f_stream_t stream);
+/* m2f_eval_scores with the focal criterion's loss (m2f_plan_focal below: numerator (1 - p_y)^gamma * CE numerator, the bits of
+ * m2f_cross_entropy_focal without a teacher for the same rows); gamma_dev: device float [1].  Confusion matrix, accuracy and weighted F1
+ * do not depend on gamma.  m2f_eval_step runs this form while m2f_plan_focal(plan, 1) is on. */
+int m2f_eval_scores_focal(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
+                          const float* gamma_dev, void* scratch, void* record, m2f_stream_t stream);
 
 /* bf16-mode plans write every activation twice - fp32 and the bf16 shadow the GEMMs / attention kernels stage from.  When a plan
  * is built, the readers of every workspace buffer are enumerated from its final launch lists; a copy nobody reads is not written
@@ -692,6 +698,22 @@ int m2f_plan_accumulate_grads(m2f_plan* plan, int on);
  * Adam, bf16 gradients and the accumulate form.  Fails for a plan without a gradient buffer. */
 int m2f_plan_distill(m2f_plan* plan, int on);
 
+/* Focal criterion (Lin et al. 2017): while m2f_plan_focal(plan, 1) is on, the criterion launch of m2f_loss / m2f_step / m2f_step_part /
+ * m2f_step_timed and the rows launch of m2f_eval_step scale the hard-label term of every labelled token row by (1 - p_y)^gamma
+ * (p = softmax(z), y the label, numCE / dCE the plain criterion's numerator and gradient, omp = sum of p_c over c != y):
+ *   num = omp^gamma * numCE                                                                den = w_y (unchanged)
+ *   dlogits_c = omp^gamma * dCE_c + numCE * gamma * omp^(gamma-1) * p_y * d_c              d_c = p_c (c != y), d_y = -omp
+ * and loss = sum num / sum den through the unchanged tail.  Without class weights and smoothing this is the mean over the labelled rows
+ * of -(1 - p_y)^gamma log p_y.  With m2f_plan_distill on as well the factor scales the hard-label term only:
+ * num = (1 - alpha) * omp^gamma * numCE + alpha * tau^2 * w_y * KL; the teacher's gradient term is unchanged.
+ * gamma = M2F_BUF_FOCAL[0], in [0, 8], is read ON THE DEVICE by every step (a captured step follows a schedule without a new capture);
+ * the call writes nothing and waits for nothing: the caller writes gamma on its stream before the first step.  gamma = 0 gives the
+ * bits of the criterion without the switch.  A row whose other classes' probabilities all underflow (omp = 0) contributes zero loss
+ * and zero gradient for gamma > 0; no gamma produces a NaN from finite logits.  A change of the switch bumps the plan's generation: no
+ * captured step or eval step replays the other form; a change of gamma alone does not.  Train and eval plans; works with fused Adam,
+ * bf16 gradients, the accumulate form and distillation. */
+int m2f_plan_focal(m2f_plan* plan, int on);
+
 /* The 256x256-tile bf16 GEMM on the eight-phase schedule (csrc/gemm_p8.h; round 4), bf16 operands handed over directly - the kernel
  * the weight-gradient table launch (rc = 1) and the text encoder's launches (rc = 0) run, for kernel-level tests and measurements.
  *   rc = 0: C[M,N] = act(A[M,K] B[N,K]^T + bias) + res   (nn.Linear forward: src/feature_extractors/text/model.py:16-21's encoder
@@ -875,6 +897,12 @@ int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, 
 int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
                               float label_smoothing, const float* hyper_dev, int normalise, float* loss_terms, float* dlogits,
                               float* loss_out, m2f_stream_t stream);
+/* The focal criterion of m2f_plan_focal on its own: m2f_cross_entropy with gamma_dev (device float [1], gamma in [0, 8]).  teacher
+ * [T, C] with hyper_dev (device float [2]: alpha, tau) adds the distillation blend of m2f_cross_entropy_distill; teacher NULL: no
+ * distillation, hyper_dev is not read. */
+int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
+                            float label_smoothing, const float* hyper_dev, const float* gamma_dev, int normalise, float* loss_terms,
+                            float* dlogits, float* loss_out, m2f_stream_t stream);
 
 /* ---- wav2vec2 audio encoder (multimodal-emotion-recognition_amd/wav2vec2.py) ------------------------------------------------------
  * The reference makes its audio embeddings in a separate stage (src/feature_extractors/audio_wav2vec2/embeddings.py:52-91:

@@ -41,7 +41,7 @@ metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
 # registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
-# and for the distillation criterion kernel of the same file (m2f_ce_distill_kernel; its own list below)
+# and for the distillation and focal criterion kernels of the same file (m2f_ce_distill_kernel, m2f_ce_focal_kernel; their own lists below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
 path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
 rows, cur = [], None
@@ -71,7 +71,11 @@ if adam:
     criterion = [r for r in rows if "m2f_ce_distill_kernel" in r["name"]]
     if len(criterion) != 1:
         sys.exit(f"check_spills: expected m2f_ce_distill_kernel in {path}, found {len(criterion)} - did the remark format change?")
-    kernels = kernels + criterion
+    # ... and the focal criterion, with and without a teacher (m2f_ce_focal_kernel<false / true>: a row's probabilities stay in registers too)
+    focal = [r for r in rows if "m2f_ce_focal_kernel" in r["name"]]
+    if len(focal) != 2:
+        sys.exit(f"check_spills: expected the two m2f_ce_focal_kernel instantiations in {path}, found {len(focal)} - did the remark format change?")
+    kernels = kernels + criterion + focal
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

@@ -84,6 +84,13 @@ __device__ __forceinline__ u32x4 m2f_rng_words(const uint32_t* rng) {
 // wait for loads issued AFTER them: the vector memory counter retires loads in order), so that it costs no wait itself.
 __device__ __forceinline__ void m2f_rng_words_arrived(u32x4& w) { asm volatile("" : "+v"(w)); }
 
+// Focal factor (1 - p_y)^gamma of a criterion row (rowops.hip m2f_ce_focal_kernel, metrics.hip m2f_eval_rows_focal_kernel: ONE function, so
+// the eval loss has the train criterion's bits).  omp is the SUM of the other classes' probabilities, never 1 - p_y.  gamma == 0 SELECTS 1;
+// omp == 0 (the other classes' expf underflowed) selects 0 for gamma > 0: powf never sees a zero base, nothing computes 0 * anything.
+__device__ __forceinline__ float m2f_focal_factor(float omp, float gamma) {
+    return gamma > 0.f ? (omp > 0.f ? powf(omp, gamma) : 0.f) : 1.f;
+}
+
 __device__ __forceinline__ float m2f_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -560,6 +560,21 @@ int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* te
     return 0;
 }
 
+int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
+                            float label_smoothing, const float* hyper_dev, const float* gamma_dev, int normalise, float* loss_terms,
+                            float* dlogits, float* loss_out, m2f_stream_t stream) {
+    if (!logits || !labels || !gamma_dev || !loss_terms || !dlogits || !loss_out)
+        return fail("m2f_cross_entropy_focal: NULL logits / labels / gamma_dev / loss_terms / dlogits / loss_out");
+    if (teacher && !hyper_dev) return fail("m2f_cross_entropy_focal: a teacher needs hyper_dev (alpha, tau)");
+    if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_focal: T >= 1 and 1 <= C <= 16 required");
+    CeFocalArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
+    a.teacher = teacher; a.hyper = teacher ? hyper_dev : nullptr; a.gamma = gamma_dev; a.loss_terms = loss_terms; a.dlogits = dlogits;
+    M2F_HIP(m2f_launch_ce_focal(a, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
     return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
 }

@@ -7,6 +7,7 @@
 //                             (numerator, weight) in exactly m2f_ce_kernel's fp32 arithmetic and operation order (rowops.hip; no
 //                             dlogits) into terms[T][2], and the (label, prediction) pair counted into a C x C integer tile in LDS
 //                             (integer adds: the counts do not depend on the order).  Each workgroup writes its tile as one partial.
+//   m2f_eval_rows_focal_kernel  its focal form (EvalArgs::gamma): the numerator of m2f_ce_focal_kernel, gamma read on the device.
 //   m2f_eval_finalize_kernel  one workgroup of 256: the row terms summed in exactly m2f_loss_finalize_kernel's order (thread-strided,
 //                             wave sum, (s0 + s1) + (s2 + s3)) - the batch loss num / den has the bits the train path's criterion
 //                             gives for the same logits -, the integer partials added, accuracy and weighted F1 in float64, and all
@@ -59,6 +60,67 @@ __global__ __launch_bounds__(256) void m2f_eval_rows_kernel(const EvalArgs a) {
         const float eps = a.label_smoothing;
         const float num = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
         a.terms[2 * t] = num;
+        a.terms[2 * t + 1] = valid ? wy : 0.f;
+        // ---- prediction: the first maximal logit; a NaN counts as maximal (torch.argmax) ----
+        float best = z[0];
+        int pred = 0;
+#pragma unroll
+        for (int c = 1; c < 16; ++c) {
+            if (c < C && !(best != best) && (z[c] > best || z[c] != z[c])) { best = z[c]; pred = c; }
+        }
+        if (valid) atomicAdd(&tile[(int)y * C + pred], 1);        // LDS integer add
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < C * C) a.partial[(size_t)blockIdx.x * C * C + threadIdx.x] = tile[threadIdx.x];
+}
+
+// The focal form of the rows launch (EvalArgs::gamma non-null): m2f_eval_rows_kernel with the numerator scaled by the focal factor, in
+// exactly m2f_ce_focal_kernel<false>'s arithmetic and order (rowops.hip: p = expf(z - lse), omp = the other classes' p added in class
+// order, m2f_focal_factor) - validation scores the criterion that trains.  No gradient; argmax and the counts do not depend on gamma.
+__global__ __launch_bounds__(256) void m2f_eval_rows_focal_kernel(const EvalArgs a) {
+    __shared__ int tile[M2F_EVAL_MAX_C * M2F_EVAL_MAX_C];
+    const int C = a.C;
+    const float gamma = a.gamma[0];
+    tile[threadIdx.x] = 0;                                        // (256 threads, 256 cells)
+    __syncthreads();
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < a.T; t += gridDim.x * 256) {
+        // ---- as m2f_ce_kernel, statement for statement ----
+        float z[16], w[16];
+        float m = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
+            w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
+            m = fmaxf(m, z[c]);
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
+        const float lse = m + logf(se);
+        const int64_t y = a.labels[t];
+        const bool valid = (y >= 0) && (y < C);
+        float wy = 0.f, logpy = 0.f, sm = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            if (c < C) {
+                const float lp = z[c] - lse;
+                sm -= w[c] * lp;
+                if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
+            }
+        }
+        const float eps = a.label_smoothing;
+        const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
+        // ---- as m2f_ce_focal_kernel ----
+        float omp = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float p = (c < C) ? expf(z[c] - lse) : 0.f;
+            if (c < C && !(valid && c == (int)y)) omp += p;
+        }
+        const bool focal = gamma > 0.f;
+        const float f = m2f_focal_factor(omp, gamma);
+        const float num_f = focal ? f * num_ce : num_ce;
+        a.terms[2 * t] = valid ? num_f : 0.f;
         a.terms[2 * t + 1] = valid ? wy : 0.f;
         // ---- prediction: the first maximal logit; a NaN counts as maximal (torch.argmax) ----
         float best = z[0];
@@ -126,7 +188,8 @@ hipError_t m2f_launch_eval_scores(const EvalArgs& a, double* record, hipStream_t
     if (!a.logits || !a.labels || !a.terms || !a.partial || !record || a.T < 1 || a.C < 1 || a.C > M2F_EVAL_MAX_C)
         return hipErrorInvalidValue;
     const int blocks = m2f_eval_blocks(a.T);
-    hipLaunchKernelGGL(m2f_eval_rows_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    if (a.gamma) hipLaunchKernelGGL(m2f_eval_rows_focal_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(m2f_eval_rows_kernel, dim3(blocks), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(m2f_eval_finalize_kernel, dim3(1), dim3(256), 0, stream, a.terms, a.T, a.C, a.partial, blocks, record);

@@ -560,6 +560,27 @@ struct CeDistillArgs {
     float* dlogits;                        // [T, C]
 };
 hipError_t m2f_launch_ce_distill(const CeDistillArgs& a, hipStream_t stream);
+// Focal criterion (Lin et al. 2017): the hard-label term scaled by (1 - p_y)^gamma.  Per token row with a valid label y
+// (ce, g = CeArgs' numerator and gradient; omp = sum of p_c over c != y, the other classes' probabilities ADDED, never 1 - p_y):
+//   numerator   = omp^gamma * ce                                                          denominator = w_y, as CeArgs
+//   dlogits_c   = omp^gamma * g_c + ce * gamma * omp^gamma * p_y * r_c      r_c = p_c / omp for c != y, r_y = -1
+// (= ce * gamma * omp^(gamma - 1) * p_y * d_c with d_c = p_c, d_y = -omp; the quotient form keeps every factor <= 1, so no gamma in
+// (0, 1) overflows at a tiny omp).  With a teacher (non-null; hyper non-null) the factor scales the hard-label term of CeDistillArgs
+// only: numerator = (1 - alpha) * omp^gamma * ce + alpha * tau^2 * w_y * KL, the teacher's gradient term unchanged.
+// gamma is READ FROM THE DEVICE (gamma[0], in [0, 8]): a captured step replays while a schedule changes it.  gamma == 0 selects factor 1
+// and slope 0: m2f_launch_ce's bits (with a teacher m2f_launch_ce_distill's).  omp == 0 selects factor and slope 0 for gamma > 0.
+struct CeFocalArgs {
+    const float* logits; int T, C;
+    const int64_t* labels;                 // [T], ignore_index = -1
+    const float* class_w;                  // [C] or null
+    float label_smoothing;
+    const float* teacher;                  // [T, C] teacher logits or null (no distillation)
+    const float* hyper;                    // device float [2]: alpha, tau; read only with a teacher
+    const float* gamma;                    // device float [1]
+    float* loss_terms;                     // [T, 2] (numerator, denominator)
+    float* dlogits;                        // [T, C]
+};
+hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream);
 // loss_out[0] = num/den, loss_out[1] = den, loss_out[2] = num.  normalise != 0: dlogits *= 1/den
 // (single-process mean-over-valid loss); normalise == 0 leaves the sum-gradient for the data-parallel
 // path, which divides by the GLOBAL denominator after the all-reduce.
@@ -580,6 +601,8 @@ struct EvalArgs {
     float label_smoothing;
     float* terms;                          // [T, 2] (numerator, denominator), as CeArgs::loss_terms
     int* partial;                          // [m2f_eval_blocks(T)][C * C]: one integer tile per workgroup of the rows launch
+    const float* gamma = nullptr;          // device float [1] or null: non-null runs the focal form of the rows launch (the loss of CeFocalArgs
+                                           // without a teacher, no gradient); null: the default form, its bits unchanged
 };
 static inline int m2f_eval_blocks(int T) { const int b = (T + 255) / 256; return b < M2F_EVAL_MAX_BLOCKS ? b : M2F_EVAL_MAX_BLOCKS; }
 hipError_t m2f_launch_eval_scores(const EvalArgs& a, double* record, hipStream_t stream);

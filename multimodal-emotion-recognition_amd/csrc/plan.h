@@ -251,6 +251,7 @@ struct m2f_plan {
     uint16_t* g16_buf = nullptr;
     m2f::AccForm acc;
     bool distill_on = false;             // m2f_plan_distill: do_loss launches the distillation criterion
+    bool focal_on = false;               // m2f_plan_focal: do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
     // graph cache: m2f_step, m2f_step_part(0), m2f_step_part(1), ...
     m2f::GraphSlot graphs[m2f::SLOT_COUNT];
     uint64_t generation = 0;      // bumped by every entry point that replaces what captured launches point to (invalidate in plan.hip)

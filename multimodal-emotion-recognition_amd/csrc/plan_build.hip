@@ -1103,6 +1103,8 @@ int build_plan(m2f_plan& P, char* ws_base) {
     P.bufs[M2F_BUF_SPEAKERS] = bld.ar.alloc<uint8_t>(((size_t)T + 15) & ~(size_t)15);
     P.bufs[M2F_BUF_STREAM_SPEAKERS] = P.s_spk;
     apply_speakers(P);
+    // gamma of the focal criterion (m2f_plan_focal), one float, train and eval plans: behind everything once more, so nothing moves
+    P.bufs[M2F_BUF_FOCAL] = bld.ar.f(1);
     P.built.ws_used = bld.ar.off;
     if (P.prec == M2F_PREC_BF16 && ws_base != nullptr) {
         const float* wsf = reinterpret_cast<const float*>(ws_base);

@@ -470,6 +470,114 @@ __global__ __launch_bounds__(256) void m2f_ce_distill_kernel(const CeDistillArgs
     a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
 }
 
+// Focal criterion (CeFocalArgs, ops.h): m2f_ce_kernel's numerator and gradient (TEACHER: m2f_ce_distill_kernel's), statement for
+// statement and in their order, with the hard-label term scaled by omp^gamma.  gamma == 0 SELECTS the unscaled values, so it gives those
+// kernels' bits.  One lane per token row, sixteen classes fully unrolled, everything in registers.
+//   omp is the other classes' probabilities ADDED (c != y), not 1 - p_y: at a margin of 20 p_y rounds to 1 and 1 - p_y to 0 or to one
+//   ulp of 1, while the sum keeps its own 24 bits.  For the same reason the y column's slope is -omp, not p_y - 1.
+//   The slope term ce * gamma * omp^(gamma-1) * p_y * d_c (d_c = p_c, d_y = -omp) is computed as ce * gamma * omp^gamma * p_y * r_c with
+//   r_c = p_c / omp <= 1, r_y = -1: no factor exceeds 1, so a gamma in (0, 1) cannot overflow omp^(gamma-1) at a tiny omp.
+//   omp == 0 (every other expf underflowed): factor, slope and every r_c are SELECTED to 0 for gamma > 0; logf / powf never see the zero.
+// An invalid row (label -1 or out of range) is a SELECT of zeros, whatever its logits or its teacher row hold.
+template <bool TEACHER>
+__global__ __launch_bounds__(256) void m2f_ce_focal_kernel(const CeFocalArgs a) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.T) return;
+    const int C = a.C;
+    const float gamma = a.gamma[0];
+    float alpha = 0.f, tau = 1.f;
+    if constexpr (TEACHER) { alpha = a.hyper[0]; tau = a.hyper[1]; }
+    float z[16], w[16], u[16];
+    float m = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
+        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
+        if constexpr (TEACHER) u[c] = (c < C) ? a.teacher[(size_t)t * C + c] : -INFINITY;
+        m = fmaxf(m, z[c]);
+    }
+    // ---- as m2f_ce_kernel ----
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
+    const float lse = m + logf(se);
+    const int64_t y = a.labels[t];
+    const bool valid = (y >= 0) && (y < C);
+    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < C) {
+            const float lp = z[c] - lse;
+            W += w[c];
+            sm -= w[c] * lp;
+            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
+        }
+    }
+    const float eps = a.label_smoothing;
+    const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
+    // ---- the focal factor: p as the gradient loop of m2f_ce_kernel computes it, omp = the other classes' p added in class order ----
+    float p[16];
+    float omp = 0.f, py = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        p[c] = (c < C) ? expf(z[c] - lse) : 0.f;
+        if (c < C) {
+            if (valid && c == (int)y) py = p[c];
+            else omp += p[c];
+        }
+    }
+    const bool focal = gamma > 0.f;
+    const bool live = focal && omp > 0.f;
+    const float f = m2f_focal_factor(omp, gamma);
+    const float slope = live ? num_ce * gamma * f * py : 0.f;
+    const float num_f = focal ? f * num_ce : num_ce;
+    // ---- the teacher term, as m2f_ce_distill_kernel ----
+    float zt[16];
+    float lsz = 0.f, lsu = 0.f, oma = 1.f, kd = 0.f, gd = 0.f;
+    if constexpr (TEACHER) {
+        float mz = -INFINITY, mu = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            zt[c] = (c < C) ? z[c] / tau : -INFINITY;
+            u[c] = (c < C) ? u[c] / tau : -INFINITY;
+            mz = fmaxf(mz, zt[c]);
+            mu = fmaxf(mu, u[c]);
+        }
+        float sz = 0.f, su = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            sz += (c < C) ? expf(zt[c] - mz) : 0.f;
+            su += (c < C) ? expf(u[c] - mu) : 0.f;
+        }
+        lsz = mz + logf(sz); lsu = mu + logf(su);
+        oma = 1.f - alpha;
+        kd = alpha * tau * tau * wy; gd = alpha * tau * wy;
+    }
+    float kl = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < C) {
+            // ---- as m2f_ce_kernel ----
+            const float pc = p[c];
+            float g = 0.f;
+            if (valid) g = (1.f - eps) * wy * (pc - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * pc - w[c]);
+            const float r = live ? ((c == (int)y) ? -1.f : pc / omp) : 0.f;
+            const float gf = focal ? (f * g + slope * r) : g;
+            if constexpr (TEACHER) {
+                const float lq = zt[c] - lsz, lpt = u[c] - lsu;
+                const float q = expf(lq), pt = expf(lpt);
+                kl += pt * (lpt - lq);
+                a.dlogits[(size_t)t * C + c] = valid ? (oma * gf + gd * (q - pt)) : 0.f;
+            } else {
+                a.dlogits[(size_t)t * C + c] = valid ? gf : 0.f;
+            }
+        }
+    }
+    if constexpr (TEACHER) a.loss_terms[2 * t] = valid ? (oma * num_f + kd * kl) : 0.f;
+    else a.loss_terms[2 * t] = valid ? num_f : 0.f;
+    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
+}
+
 // ACC (the accumulate form): den and num are added to loss_out[1], loss_out[2] (a group of micro-batches); loss_out[0] stays this batch's
 template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_loss_finalize_kernel(const float* __restrict__ terms, int T, int C,
@@ -984,6 +1092,13 @@ hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream) {
 hipError_t m2f_launch_ce_distill(const CeDistillArgs& a, hipStream_t stream) {
     if (a.C < 1 || a.C > 16 || a.T < 1 || !a.teacher || !a.hyper) return hipErrorInvalidValue;
     hipLaunchKernelGGL(m2f_ce_distill_kernel, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream) {
+    if (a.C < 1 || a.C > 16 || a.T < 1 || !a.gamma || (a.teacher && !a.hyper)) return hipErrorInvalidValue;
+    if (a.teacher) hipLaunchKernelGGL(m2f_ce_focal_kernel<true>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(m2f_ce_focal_kernel<false>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

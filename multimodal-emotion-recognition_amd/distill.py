@@ -117,8 +117,12 @@ class Distiller:
 
     def train_step(self, text, audio, mask, emotion, speakers=None, **kw) -> torch.Tensor:
         """speakers ([B, L] ids): student and teacher each run under their OWN speaker-head setting, and the batch's ids go to
-        whichever of the two has one; needed as soon as either has, refused (ValueError) when neither does."""
+        whichever of the two has one; needed as soon as either has, refused (ValueError) when neither does.
+        focal_gamma= (in ``kw``) goes to the student's step: the focal factor scales its hard-label term, the teacher term stays."""
         pair = check_distill((self.alpha, self.temperature), "Distiller")          # (before the teacher runs)
+        if kw.get("focal_gamma") is not None:
+            from .runtime import check_focal_gamma
+            kw["focal_gamma"] = check_focal_gamma(kw["focal_gamma"], "focal_gamma", "Distiller.train_step")
         s_on, t_on = self.student.speaker_heads is not None, self.teacher.speaker_heads is not None
         if speakers is not None and not (s_on or t_on):
             raise ValueError("Distiller.train_step: speakers were given, but neither the student nor the teacher has speaker heads")

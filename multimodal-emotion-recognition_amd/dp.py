@@ -473,17 +473,20 @@ class DataParallelStep:
             self.model.set_grad_bf16(False)
 
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
-                 use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None) -> torch.Tensor:
+                 use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None) -> torch.Tensor:
         """teacher_logits, distill=(alpha, temperature): as ``M2FNet.train_step`` - the rank's step runs the distillation criterion
         (one denominator: the exchange, the global den and the micro-batch group hold as they are); both or neither.
+        focal_gamma: as ``M2FNet.train_step`` - the rank's step runs the focal form of its criterion (the denominator is untouched).
         sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
+        from . import runtime
         from .distill import resolve_distill_args
         _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
+        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DataParallelStep")
         eng = self.model.engine()
         if self.overlap and self.reducer.world() > 1:
             _refuse_clipped_split(self.optimizer)     # (before any launch or collective: every rank refuses alike)
@@ -516,7 +519,7 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self.model._set_criterion(plan, teacher_logits, dist)
+            self.model._set_criterion(plan, teacher_logits, dist, gamma)
             if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

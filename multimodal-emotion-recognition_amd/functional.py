@@ -683,6 +683,34 @@ def cross_entropy_distill(logits: torch.Tensor, teacher: torch.Tensor, labels: t
     return out, dl
 
 
+def cross_entropy_focal(logits: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None, label_smoothing: float = 0.1,
+                        gamma: float = 2.0, normalise: bool = True, teacher: Optional[torch.Tensor] = None, alpha: float = 0.0,
+                        temperature: float = 1.0):
+    """The focal criterion (m2f_cross_entropy_focal): logits [T, C] fp32, labels int64 [T] (-1 = ignore) -> (loss_out[4] = loss, den,
+    num, -; dlogits [T, C]) of the cross entropy with every labelled row's hard-label term scaled by (1 - p_y)^gamma, over the ONE
+    denominator (sum of w_y).  gamma: a finite number in [0, 8] (ValueError otherwise); 0 gives `cross_entropy`'s bits.  teacher [T, C]
+    fp32 with alpha, temperature adds the blend of `cross_entropy_distill` (the factor scales the hard-label term only; gamma = 0 then
+    gives `cross_entropy_distill`'s bits)."""
+    gamma = runtime.check_focal_gamma(gamma, "gamma", "cross_entropy_focal")
+    runtime.require_gpu()
+    T, C = logits.shape
+    if logits.dtype != torch.float32:
+        raise ValueError(f"cross_entropy_focal: logits must be fp32 (got {logits.dtype})")
+    if teacher is not None and (teacher.shape != logits.shape or teacher.dtype != torch.float32):
+        raise ValueError(f"cross_entropy_focal: logits and teacher must be fp32 of one shape (got {tuple(logits.shape)} {logits.dtype}, "
+                         f"{tuple(teacher.shape)} {teacher.dtype})")
+    terms = torch.empty(T, 2, dtype=torch.float32, device=logits.device)
+    dl = torch.empty(T, C, dtype=torch.float32, device=logits.device)
+    out = torch.zeros(4, dtype=torch.float32, device=logits.device)
+    hyper = torch.tensor([float(alpha), float(temperature), gamma], dtype=torch.float32).to(logits.device, non_blocking=True)
+    logits, labels = logits.contiguous(), labels.contiguous()
+    teacher = teacher.contiguous() if teacher is not None else None
+    check(lib().m2f_cross_entropy_focal(T, C, ptr(logits), ptr(teacher), ptr(labels), ptr(class_w), label_smoothing, ptr(hyper),
+                                        ptr(hyper[2:]), int(normalise), ptr(terms), ptr(dl), ptr(out), stream_ptr()),
+          "m2f_cross_entropy_focal")
+    return out, dl
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
                       need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,

@@ -72,8 +72,10 @@ class DeviceScores:
         self.record.zero_()
 
     def update(self, logits: torch.Tensor, emotion: torch.Tensor, class_weights: Optional[torch.Tensor] = None,
-               label_smoothing: float = 0.1) -> None:
-        """Score one batch: logits ``[B, L, C]`` (or ``[T, C]``) fp32 on the device, emotion ``[B, L]`` (-1 = not scored)."""
+               label_smoothing: float = 0.1, focal_gamma: Optional[float] = None) -> None:
+        """Score one batch: logits ``[B, L, C]`` (or ``[T, C]``) fp32 on the device, emotion ``[B, L]`` (-1 = not scored).
+        focal_gamma (a finite number in [0, 8]): the loss is the focal criterion's (m2f_eval_scores_focal); None: the plain one."""
+        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DeviceScores.update")
         C = self.n_classes
         if logits.shape[-1] != C or logits.dtype != torch.float32 or logits.device != self.record.device:
             raise ValueError(f"DeviceScores.update: fp32 logits [..., {C}] on {self.record.device} expected, got "
@@ -95,6 +97,11 @@ class DeviceScores:
             cw = class_weights.to(device=rows.device, dtype=torch.float32).contiguous()
             if cw.numel() != C:
                 raise ValueError(f"DeviceScores.update: {C} class weights expected, got {cw.numel()}")
+        if gamma is not None:
+            g = torch.tensor([gamma], dtype=torch.float32).to(rows.device, non_blocking=True)
+            check(lib().m2f_eval_scores_focal(T, C, ptr(rows), ptr(labels), ptr(cw), float(label_smoothing), ptr(g), ptr(self._scratch),
+                                              ptr(self.record), stream_ptr()), "m2f_eval_scores_focal")
+            return
         check(lib().m2f_eval_scores(T, C, ptr(rows), ptr(labels), ptr(cw), float(label_smoothing), ptr(self._scratch),
                                     ptr(self.record), stream_ptr()), "m2f_eval_scores")
 

@@ -679,7 +679,8 @@ class M2FNet(nn.Module):
     def train_step(self, text, audio, mask, emotion, label_smoothing: float = 0.1,
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
-                   distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
+                   focal_gamma: Optional[float] = None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -691,9 +692,15 @@ class M2FNet(nn.Module):
         weight-gradient launch applies the update itself (``FusedAdam.prepare_fused``; the matrices' ``.grad`` is then not written),
         otherwise the optimizer's own kernel runs behind the step.
         speakers ([B, L] ids): required by a model with speaker heads (``set_speaker_heads``), refused by one without; an input like
-        the mask - a captured step replays while the ids change."""
+        the mask - a captured step replays while the ids change.
+        focal_gamma (a finite number in [0, 8]): the step's criterion is the focal form (Lin et al. 2017) - every labelled utterance's
+        hard-label term scaled by ``(1 - p_y)^gamma``, one kernel in the criterion's place, the same ``loss_terms()`` tail; with
+        ``teacher_logits`` / ``distill`` the factor scales the hard-label term only.  gamma lives on the device (uploaded only when it
+        changed): a schedule of gamma replays the captured step.  None (default): the criterion without it, bit for bit; focal and plain
+        calls mix freely on one model.  Anything else is a ValueError before any launch."""
         from .distill import resolve_distill_args
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
+        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.train_step")
         dist = resolve_distill_args(teacher_logits, distill, mask.shape[0], mask.shape[1], self.m2f_config.cls_out, mask.device,
                                     "M2FNet.train_step")
         eng = self.engine(mask.device)
@@ -708,7 +715,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist)
+            self._set_criterion(plan, teacher_logits, dist, gamma)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -736,9 +743,11 @@ class M2FNet(nn.Module):
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
-    def _set_criterion(plan, teacher_logits, dist) -> None:
+    def _set_criterion(plan, teacher_logits, dist, gamma=None) -> None:
         """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
-        temperature), or (dist None) the plain one.  After `set_inputs` (a packed plan maps the teacher rows as it mapped the batch)."""
+        temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
+        plan maps the teacher rows as it mapped the batch)."""
+        plan.set_focal(gamma)
         plan.distill(dist is not None)
         if dist is not None:
             plan.set_teacher(teacher_logits)
@@ -746,13 +755,17 @@ class M2FNet(nn.Module):
 
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,
-                  label_smoothing: float = 0.1, use_graph: bool = True, speakers: Optional[torch.Tensor] = None) -> None:
+                  label_smoothing: float = 0.1, use_graph: bool = True, speakers: Optional[torch.Tensor] = None,
+                  focal_gamma: Optional[float] = None) -> None:
         """Loop body of the reference's ``validate`` / ``test`` (src/train.py:252-272, src/test.py:55-74) in one call: the forward of
         a no-grad ``forward`` (same plan: buckets, packed plans, long dialogues), then the batch's criterion loss, accuracy, weighted
         F1 and confusion matrix ADDED to ``scores`` (a ``metrics.DeviceScores``), all on the device.  Returns nothing and waits for
         nothing: ``scores.last()`` is a device view of the batch's three numbers, ``scores.result()`` / ``mean_loss()`` read the pass.
-        The plan's own token rows are scored - pad and filler rows carry label -1.  speakers: as ``train_step``."""
+        The plan's own token rows are scored - pad and filler rows carry label -1.  speakers: as ``train_step``.
+        focal_gamma: as ``train_step`` - the loss is the focal criterion's (the bits its train kernel gives for the same rows), so
+        validation and early stopping see the criterion that trains; accuracy, F1 and the confusion matrix do not depend on it."""
         ids = _check_speakers("M2FNet.eval_step", self._speaker_heads, speakers, mask.shape)
+        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.eval_step")
         if self.training and self.m2f_config.dropout > 0.0:
             raise RuntimeError("M2FNet.eval_step: the model is in training mode with dropout > 0; evaluation scores the model "
                                "without dropout - call model.eval() first")
@@ -767,6 +780,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
+            plan.set_focal(gamma)
             plan.eval_step(scores.record, label_smoothing, class_weights is not None, use_graph)
 
         if use_graph:                                    # capture / replay on the engine's own stream

@@ -2,6 +2,7 @@
 
 * ``M2FCrossEntropyLoss``  = ``torch.nn.CrossEntropyLoss(weight, ignore_index=-1, label_smoothing=0.1)`` as the
   reference builds it (src/train.py:41-52), computed by the fused CE kernel (value + gradient in one pass).
+* ``M2FFocalLoss``         = the same with every labelled row's term scaled by ``(1 - p_y)^gamma`` (focal loss; its own kernel).
 * ``FusedAdam``            = ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` (src/train.py:56): coupled
   L2, bias-corrected; ONE kernel over the flat parameter / gradient / moment buffers instead of ~130 per-tensor
   updates.  ``state_dict()`` keeps torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` /
@@ -117,6 +118,41 @@ class M2FDistillationLoss(nn.Module):
         w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
         return _DistillFunction.apply(logits.contiguous().float(), teacher.detach().contiguous().float(), target.reshape(-1).contiguous(),
                                       w, self.label_smoothing, alpha, temperature)
+
+
+class _FocalFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits2d, target1d, weight, label_smoothing, gamma):
+        out, dl = F.cross_entropy_focal(logits2d, target1d, weight, label_smoothing, gamma, True)
+        ctx.save_for_backward(dl)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dl,) = ctx.saved_tensors
+        return dl * grad_out, None, None, None, None
+
+
+class M2FFocalLoss(M2FCrossEntropyLoss):
+    """Focal loss (Lin et al. 2017) over ``M2FCrossEntropyLoss``: every labelled row's term scaled by ``(1 - p_y)^gamma``, the sum
+    divided by the sum of the labels' class weights as ever - without weights and smoothing ``mean(-(1 - p_y)^gamma log p_y)``.  One
+    kernel (``functional.cross_entropy_focal``; the criterion ``M2FNet.train_step(focal_gamma=)`` runs inside the step) on the autograd
+    surface of its base class, which it IS: the train loop's fused step accepts it and hands ``gamma`` on.  ``gamma`` (a finite number in
+    [0, 8]; 0 = the base class's bits) is a plain attribute, read at every call: a schedule may change it."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -1, label_smoothing: float = 0.1, gamma: float = 2.0):
+        super().__init__(weight, ignore_index, label_smoothing)
+        self.gamma = runtime.check_focal_gamma(gamma, "gamma", "M2FFocalLoss")
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        gamma = runtime.check_focal_gamma(self.gamma, "gamma", "M2FFocalLoss")
+        if input.dim() == 3:
+            C = input.shape[1]
+            logits = input.permute(0, 2, 1).reshape(-1, C)
+        else:
+            logits = input
+        w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
+        return _FocalFunction.apply(logits.contiguous().float(), target.reshape(-1).contiguous(), w, self.label_smoothing, gamma)
 
 
 class FusedAdam(torch.optim.Optimizer):

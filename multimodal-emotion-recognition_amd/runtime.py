@@ -27,7 +27,7 @@ F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
- BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS) = range(21)
+ BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL) = range(22)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -100,6 +100,7 @@ SIGNATURES = {
     "m2f_eval_record_bytes": (c_int64, [c_int]),
     "m2f_eval_scores": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "m2f_eval_step": (c_int, [c_void_p, c_float, c_int, c_void_p, c_int, c_void_p]),
+    "m2f_eval_scores_focal": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_skipped_copies": (c_int, [c_void_p]),
     "m2f_plan_destroy": (None, [c_void_p]),
     "m2f_plan_buffer": (c_void_p, [c_void_p, c_int]),
@@ -185,6 +186,7 @@ SIGNATURES = {
     "m2f_plan_grad_bf16": (c_int, [c_void_p, c_void_p]),
     "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),
     "m2f_plan_distill": (c_int, [c_void_p, c_int]),
+    "m2f_plan_focal": (c_int, [c_void_p, c_int]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
@@ -233,6 +235,8 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "m2f_cross_entropy_distill": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
+    "m2f_cross_entropy_focal": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -352,6 +356,19 @@ def speaker_heads(setting, heads=None) -> Optional[Tuple[int, int]]:
         if a + b > H:
             raise ValueError(f"speaker heads: n_same + n_other = {a + b} exceeds the {H} heads of {name}")
     return int(a), int(b)
+
+
+FOCAL_GAMMA_MAX = 8.0
+
+
+def check_focal_gamma(gamma, name: str = "focal_gamma", who: str = "train_step") -> float:
+    """gamma of the focal criterion as a float; ValueError naming the argument unless it is a finite number in [0, 8].  A host function:
+    no GPU needed."""
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)):
+        raise ValueError(f"{who}: {name} must be a number in [0, {FOCAL_GAMMA_MAX:g}], got {gamma!r}")
+    if not (math.isfinite(gamma) and 0.0 <= gamma <= FOCAL_GAMMA_MAX):
+        raise ValueError(f"{who}: {name} must be a finite number in [0, {FOCAL_GAMMA_MAX:g}], got {gamma!r}")
+    return float(gamma)
 
 
 SPK_NONE, SPK_SAME, SPK_OTHER = 0, 1, 2
@@ -476,6 +493,10 @@ class Plan:
         self.distill_hyper = self._view(BUF_DISTILL, (2,), torch.float32) if train else None
         self._distill = False
         self.hyper_host = None                # host mirror of distill_hyper: what was last uploaded (None: nothing yet)
+        # gamma of the focal criterion (train and eval plans; `focal`): the float the criterion and eval-rows kernels read on the device
+        self.focal_gamma = self._view(BUF_FOCAL, (1,), torch.float32)
+        self._focal = False
+        self.gamma_host = None                # host mirror of focal_gamma, as hyper_host
         self._fam0_out = (self._view(BUF_FAM0_OUT, (self.T, pad8(cfg.d_fam)) if self.packed else (B, L, pad8(cfg.d_fam)),
                                      torch.float32)[..., : cfg.d_fam] if cfg.fam_enabled else None)
         # shape of the batch last handed to set_inputs: a plan may be larger than the batch it runs (shape buckets), the
@@ -705,6 +726,29 @@ class Plan:
         if pair != self.hyper_host:
             self.distill_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
             self.hyper_host = pair
+
+    def focal(self, on: bool) -> None:
+        """m2f_plan_focal: the NEXT losses / steps / eval steps run the focal form of the criterion with gamma = `focal_gamma` (on) / the
+        form without it (off).  A change drops the captured steps; a change of gamma alone does not.  Neither writes nor waits:
+        `set_focal_gamma` fills the buffer on the stream before the step."""
+        on = bool(on)
+        if on == self._focal:
+            return
+        check(lib().m2f_plan_focal(self._h(), int(on)), "m2f_plan_focal")
+        self._focal = on
+
+    def set_focal_gamma(self, gamma: float) -> None:
+        """gamma into `focal_gamma`, uploaded only when it differs from the host mirror of the last upload."""
+        gamma = float(gamma)
+        if gamma != self.gamma_host:
+            self.focal_gamma.copy_(torch.tensor([gamma], dtype=torch.float32), non_blocking=True)
+            self.gamma_host = gamma
+
+    def set_focal(self, gamma: Optional[float]) -> None:
+        """The criterion of the plan's next step or eval step: focal with this gamma (a number, checked by the caller), or (None) not."""
+        self.focal(gamma is not None)
+        if gamma is not None:
+            self.set_focal_gamma(gamma)
 
     def _casted(self) -> None:
         if self.shared_shadow and not self._fresh and self._on_cast is not None:

@@ -178,11 +178,13 @@ def test(model, dl_test, device):
     if getattr(model, "device_metrics", False):
         from mer_amd.metrics import DeviceScores
         scores = DeviceScores(model.m2f_config.cls_out, device)
+        gamma = getattr(model, "focal_gamma", None)            # (solver.loss_fn: Focal; set by main())
+        focal = {} if gamma is None else {"focal_gamma": gamma}
         with torch.inference_mode():
             for batch in tqdm(dl_test, total=len(dl_test)):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
-                model.eval_step(text, audio, padding_mask, emotion, scores, **_speaker_kw(model, batch, device))
+                model.eval_step(text, audio, padding_mask, emotion, scores, **_speaker_kw(model, batch, device), **focal)
                 maps.add(padding_mask)
         model.test_scores = scores
         maps.write()
@@ -236,7 +238,9 @@ def main(config=None):
     model.stream_chunk = stream_chunk
     model.stream_pages = stream_pages
     model.attention_maps_out = attention_maps
-    from train import ema_settings
+    from train import ema_settings, focal_gamma_setting
+    # (solver.loss_fn: Focal - the device record's loss is the criterion that trained, with runtime.focal_gamma; accuracy and F1 do not depend on it)
+    model.focal_gamma = focal_gamma_setting(config) if config.solver.loss_fn == "Focal" else None
     ema = ema_settings(config)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
     print("Testing...")

@@ -20,7 +20,7 @@ from metrics import BatchScores, move_batch  # noqa: E402
 from model import M2FNet  # noqa: E402
 from utils import get_config  # noqa: E402
 from mer_amd import dp  # noqa: E402
-from mer_amd.optim import MAX_GROUPS, FusedAdam, FusedAdamW, M2FCrossEntropyLoss  # noqa: E402
+from mer_amd.optim import MAX_GROUPS, FusedAdam, FusedAdamW, M2FCrossEntropyLoss, M2FFocalLoss  # noqa: E402
 from mer_amd.watch import ModelWatch, check_bins, check_kinds, check_log_freq  # noqa: E402
 
 try:
@@ -451,15 +451,33 @@ def group_batches(batches, k: int):
 
 
 # ---- construction of the solver pieces from config.solver -----------------------------------------------------------
-def build_criterion(solver, train_set, device):
-    """CE(ignore_index=-1, label_smoothing=0.1), optionally with sklearn's balanced class weights of the train labels."""
-    if solver.loss_fn != "CE":
+def focal_gamma_setting(cfg) -> float:
+    """`runtime.focal_gamma`: gamma of the focal criterion `solver.loss_fn: Focal` builds (mer_amd.optim.M2FFocalLoss) - a finite number
+    in [0, 8], default 2.0; checked on the host before the GPU is touched, ignored under `loss_fn: CE`."""
+    from mer_amd.runtime import check_focal_gamma
+    return check_focal_gamma(_runtime(cfg, "focal_gamma", 2.0), "focal_gamma", "runtime")
+
+
+def _focal_kw(criterion):
+    """{focal_gamma} for train_step / DataParallelStep / eval_step when the criterion is the focal one (its gamma as it stands: a schedule
+    may have changed it), else nothing - the calls of a CE run are today's."""
+    return {"focal_gamma": criterion.gamma} if isinstance(criterion, M2FFocalLoss) else {}
+
+
+def build_criterion(solver, train_set, device, focal_gamma: float = 2.0):
+    """CE(ignore_index=-1, label_smoothing=0.1), optionally with sklearn's balanced class weights of the train labels; `loss_fn: Focal`:
+    the same with every utterance's term scaled by (1 - p_y)^focal_gamma (M2FFocalLoss, an M2FCrossEntropyLoss: the fused step, the
+    device metrics and every training mode take it)."""
+    if solver.loss_fn not in ("CE", "Focal"):
         raise ValueError("Criterion not supported")
     class_weights = None
     if solver.balance_classes:
-        balanced = class_weight.compute_class_weight(class_weight="balanced", classes=list(range(N_CLASSES)),
-                                                     y=train_set.get_labels())
+        import numpy as np                                 # (current sklearn takes `classes` as an ndarray only)
+        balanced = class_weight.compute_class_weight(class_weight="balanced", classes=np.arange(N_CLASSES),
+                                                     y=np.asarray(train_set.get_labels()))
         class_weights = torch.as_tensor(balanced, dtype=torch.float, device=device)
+    if solver.loss_fn == "Focal":
+        return M2FFocalLoss(weight=class_weights, ignore_index=-1, label_smoothing=0.1, gamma=focal_gamma)
     return M2FCrossEntropyLoss(weight=class_weights, ignore_index=-1, label_smoothing=0.1)
 
 
@@ -582,6 +600,7 @@ def main(config=None):
     position_bias_settings(config)
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
     resolve_distill(config)
+    focal_gamma_setting(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -657,7 +676,7 @@ def main(config=None):
         object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
                                                                              n_head=config.model.AUDIO.n_head))
     attach_distiller(config, model, device)
-    criterion = build_criterion(config.solver, train_set, device)
+    criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config))
     optimizer = build_optimizer(config, model)
     optimizer.max_grad_norm = clip_grad_norm(config, world)
     attach_watch(config, model, optimizer, rank, world)
@@ -811,14 +830,16 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                           class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask))
+                           class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
+                           **_focal_kw(criterion))
         else:
             optimizer.zero_grad()
             if fused and getattr(model, "fused_optimizer", False) and isinstance(optimizer, FusedAdam):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                         class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer,
-                                        **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device))
+                                        **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
+                                        **_focal_kw(criterion))
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
@@ -827,7 +848,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                         class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                                        **_speaker_kw(model, batch, device))
+                                        **_speaker_kw(model, batch, device), **_focal_kw(criterion))
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
@@ -864,11 +885,12 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             if dp_step is not None:
                 loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                class_weights=criterion.weight, use_graph=use_graph, sync=j == len(group) - 1,
-                               **_distill_kw(model, text, audio, padding_mask))
+                               **_distill_kw(model, text, audio, padding_mask), **_focal_kw(criterion))
             else:
                 model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
                                  class_weights=criterion.weight, normalise=False, use_graph=use_graph,
-                                 **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device))
+                                 **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
+                                 **_focal_kw(criterion))
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
@@ -937,7 +959,8 @@ def _validate_on_device(model, dl_val, criterion, device, rank, world):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             model.eval_step(text, audio, padding_mask, emotion, scores, class_weights=criterion.weight,
-                            label_smoothing=criterion.label_smoothing, use_graph=use_graph, **_speaker_kw(model, batch, device))
+                            label_smoothing=criterion.label_smoothing, use_graph=use_graph, **_speaker_kw(model, batch, device),
+                            **_focal_kw(criterion))
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks(list(scores.totals()), device=device)      # (the one read of the pass)
     n = max(n, 1.0)
     return loss_total / n, acc_sum / n, f1_sum / n
