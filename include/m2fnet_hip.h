@@ -714,6 +714,30 @@ int m2f_plan_distill(m2f_plan* plan, int on);
  * bf16 gradients, the accumulate form and distillation. */
 int m2f_plan_focal(m2f_plan* plan, int on);
 
+/* Linear-chain CRF criterion (the kernel-level entries m2f_crf_* below define it): while m2f_plan_crf(plan, params, param_grad) is on,
+ * the criterion launch of m2f_loss / m2f_step / m2f_step_part / m2f_step_timed is the CRF loss over the plan's own dialogues (padded and
+ * bucket-padded plans: rows b*L + i; packed and long-dialogue plans: the plan's cu_seqlens) with the same loss_terms / loss tail
+ * (token_mean: num = logZ - score(y) per dialogue, den = labelled rows), and m2f_eval_step scores that loss (the train kernel's bits)
+ * and counts the labels against the VITERBI path over the rows that are not padding instead of the per-row argmax.  label_smoothing
+ * and class weights are not read.  params: device float [C*C + 2C] = [transitions | start | end], 16-byte aligned, the CALLER's (as
+ * m2f_plan_stream_speakers takes its buffer): it is not in the flat parameter buffer, m2f_config or any optimizer table, and its VALUES
+ * are read on the device at every step - a captured step replays while an optimizer updates them in place.  param_grad: device float
+ * [C*C + 2C], overwritten by every step with the block's gradient (divided by den when the step normalises), the dialogues' shares
+ * added in a fixed order; NULL: the block is frozen, a pure input.  params NULL: off.
+ * Excludes m2f_plan_distill and m2f_plan_focal (each refuses the other by name).  A non-NULL param_grad is refused while the plan
+ * accumulates gradients (m2f_plan_accumulate_grads) and by the split step (m2f_step_part), and they refuse it: that gradient would need
+ * the group's den / an all-reduce.  A frozen block works with all of them.  A change of the pointers or the switch bumps the plan's
+ * generation; a change of the values does not.  Train and eval plans with 2 .. 16 classes. */
+int m2f_plan_crf(m2f_plan* plan, const float* params, float* param_grad);
+
+/* The CRF's online form on a stream (m2f_crf_filter below): while m2f_plan_stream_crf(plan, params, phi) is on, m2f_stream_step (a
+ * stream plan) / m2f_stream_prefill (a chunk plan) run the forward filter over the new utterances' logits behind the classifier and in
+ * front of the launch that advances the counters, inside the same captured graph.  phi: the CALLER's device float [S, C], the slots'
+ * filter state - log P(label of the slot's last utterance | its dialogue so far), the end term not applied; a slot whose count is 0
+ * starts from `start`, whatever phi holds.  params as m2f_plan_crf (read on the device at every call).  A stream plan and its chunk
+ * plan take the same two pointers.  Both NULL: off.  The logits are unchanged either way.  C floats per slot: no window limits it. */
+int m2f_plan_stream_crf(m2f_plan* plan, const float* params, float* phi);
+
 /* The 256x256-tile bf16 GEMM on the eight-phase schedule (csrc/gemm_p8.h; round 4), bf16 operands handed over directly - the kernel
  * the weight-gradient table launch (rc = 1) and the text encoder's launches (rc = 0) run, for kernel-level tests and measurements.
  *   rc = 0: C[M,N] = act(A[M,K] B[N,K]^T + bias) + res   (nn.Linear forward: src/feature_extractors/text/model.py:16-21's encoder
@@ -903,6 +927,40 @@ int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* te
 int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
                             float label_smoothing, const float* hyper_dev, const float* gamma_dev, int normalise, float* loss_terms,
                             float* dlogits, float* loss_out, m2f_stream_t stream);
+
+/* ---- linear-chain CRF over a dialogue's labels (multimodal-emotion-recognition_amd/crf.py, csrc/crf.hip) --------------------------
+ * params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.  The block is NOT part of the flat parameter
+ * buffer or of m2f_config: the caller owns it.  Dialogue b owns token rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (int32 [B+1], device) or,
+ * cu_seqlens NULL, rows b*L .. b*L+L-1 (B * L <= T).  Rows outside every dialogue get zeros / -1.
+ *
+ * m2f_crf_nll: the chain of a dialogue is its rows with a label in [0, C), in row order (a -1 in the middle links its neighbours; the
+ * logits of an unlabelled row are never read).  For chain rows t_1 < ... < t_n with emissions e = logits and labels y:
+ *   score(y) = start[y_1] + sum_k e[t_k, y_k] + sum_{k>=2} transitions[y_{k-1}, y_k] + end[y_n],  logZ = log sum_paths exp(score)
+ *   loss_terms [T, 2]: num = logZ - score(y) on the dialogue's first chain row, den = 1 on every chain row;
+ *   loss_out [4] = loss (sum num / sum den: token_mean), den, num, -   as m2f_cross_entropy
+ *   dlogits [T, C] = P(y_k = c) - [c == y_k] on chain rows, 0 elsewhere; divided by den when normalise != 0; NULL (with param_grad
+ *   NULL): the loss alone - the forward sweep, no gradient (what m2f_eval_step runs)
+ *   param_grad [C*C + 2C] (NULL: the parameters are frozen, nothing is computed for them): d transitions, d start, d end in the layout of
+ *   params, the dialogues' shares added in dialogue order without atomics (same bits every run); divided by den when normalise != 0 (a batch without any labelled row: zeros, where loss and dlogits are 0 / 0 as the plain criterion's).
+ * alpha is carried normalised in log space and the marginals are formed from relative values: fp32 results stay within ~1e-6 of
+ * float64 at 512 rows, and transitions of -1e4 or logit margins of +-120 stay finite.  A dialogue without a chain row contributes
+ * nothing.  scratch: m2f_crf_scratch_floats(T, B, C) floats.  Three launches (two without param_grad), nothing waited for.
+ *
+ * m2f_crf_viterbi: the chain is the rows whose mask (uint8 [T]) is 0.  pred [T] = the best path's class, -1 off the chain; score [B] =
+ * the path's score (0 without a chain row).  The lowest class wins every tie.  scratch: 20 * T bytes (m2f_crf_scratch_floats covers it).
+ *
+ * m2f_crf_filter: the online form, for stream slots.  phi [S, C] in and out: log P(label of the slot's last utterance | the dialogue so
+ * far), the end term not applied.  Slot s takes rows s*rows .. s*rows + n_new[s] - 1 of logits [S*rows, C] in order (n_new NULL, rows
+ * == 1: one row); active (uint8 [S], NULL: all) = 0 leaves the slot untouched.  count [S] int32 = utterances the slot held before the
+ * call (0: the first row starts from `start`); it is read, never written.  One row per call n times gives the bits of n rows at once. */
+int64_t m2f_crf_scratch_floats(int T, int B, int C);
+int m2f_crf_nll(int T, int C, int B, int L, const int32_t* cu_seqlens, const float* logits, const int64_t* labels, const float* params,
+                int normalise, float* scratch, float* loss_terms, float* dlogits, float* param_grad, float* loss_out,
+                m2f_stream_t stream);
+int m2f_crf_viterbi(int T, int C, int B, int L, const int32_t* cu_seqlens, const float* logits, const uint8_t* mask, const float* params,
+                    void* scratch, int32_t* pred, float* score, m2f_stream_t stream);
+int m2f_crf_filter(int S, int C, int rows, const float* logits, const float* params, const int32_t* count, const uint8_t* active,
+                   const int32_t* n_new, float* phi, m2f_stream_t stream);
 
 /* ---- wav2vec2 audio encoder (multimodal-emotion-recognition_amd/wav2vec2.py) ------------------------------------------------------
  * The reference makes its audio embeddings in a separate stage (src/feature_extractors/audio_wav2vec2/embeddings.py:52-91:

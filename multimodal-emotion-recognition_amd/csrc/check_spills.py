@@ -43,7 +43,10 @@ metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
 # and for the distillation and focal criterion kernels of the same file (m2f_ce_distill_kernel, m2f_ce_focal_kernel; their own lists below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam) else sys.argv[1]
+# --crf <remarks>: the linear-chain CRF kernels (crf.hip) - a lane's transition column / row, its gradient column and the sixteen terms of
+# a step stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
+crf = len(sys.argv) > 2 and sys.argv[1] == "--crf"
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -76,6 +79,15 @@ if adam:
     if len(focal) != 2:
         sys.exit(f"check_spills: expected the two m2f_ce_focal_kernel instantiations in {path}, found {len(focal)} - did the remark format change?")
     kernels = kernels + criterion + focal
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if crf:
+    kernels = [r for r in rows if "m2f_crf_" in r["name"]]
+    if len(kernels) != 6:
+        sys.exit(f"check_spills: expected the six m2f_crf_ kernels in {path}, found {len(kernels)} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

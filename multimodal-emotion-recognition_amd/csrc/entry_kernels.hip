@@ -575,6 +575,57 @@ int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teac
     return 0;
 }
 
+int64_t m2f_crf_scratch_floats(int T, int B, int C) {
+    return T < 1 || B < 1 || C < 2 || C > 16 ? 0 : (int64_t)T * (2 * C + 2) + (int64_t)B * (C * C + 2 * C);
+}
+
+static int crf_shape_bad(const char* who, int T, int C, int B, int L, const int32_t* cu_seqlens) {
+    if (T < 1 || B < 1 || C < 2 || C > 16) return fail(std::string(who) + ": T >= 1, B >= 1 and 2 <= C <= 16 required");
+    if (!cu_seqlens && (L < 1 || (int64_t)B * L > T)) return fail(std::string(who) + ": without cu_seqlens, L >= 1 and B * L <= T required");
+    return 0;
+}
+
+int m2f_crf_nll(int T, int C, int B, int L, const int32_t* cu_seqlens, const float* logits, const int64_t* labels, const float* params,
+                int normalise, float* scratch, float* loss_terms, float* dlogits, float* param_grad, float* loss_out,
+                m2f_stream_t stream) {
+    if (!logits || !labels || !params || !scratch || !loss_terms || !loss_out)
+        return fail("m2f_crf_nll: NULL logits / labels / params / scratch / loss_terms / loss_out");
+    if (!dlogits && param_grad) return fail("m2f_crf_nll: param_grad needs dlogits (the parameter gradient comes out of the backward sweep)");
+    if (crf_shape_bad("m2f_crf_nll", T, C, B, L, cu_seqlens)) return 1;
+    CrfArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.params = params; a.cu_seqlens = cu_seqlens; a.B = B; a.L = L;
+    a.ws = scratch; a.loss_terms = loss_terms; a.dlogits = dlogits;
+    a.partial = param_grad ? scratch + (size_t)T * (2 * C + 2) : nullptr;
+    M2F_HIP(m2f_launch_crf_nll(a, static_cast<hipStream_t>(stream)));
+    // (dlogits NULL: the loss alone - nothing for the finalize launch to scale)
+    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, dlogits ? normalise : 0, static_cast<hipStream_t>(stream)));
+    if (param_grad) M2F_HIP(m2f_launch_crf_grad_reduce(a.partial, B, C, loss_out, normalise, param_grad, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_crf_viterbi(int T, int C, int B, int L, const int32_t* cu_seqlens, const float* logits, const uint8_t* mask, const float* params,
+                    void* scratch, int32_t* pred, float* score, m2f_stream_t stream) {
+    if (!logits || !mask || !params || !scratch || !pred || !score)
+        return fail("m2f_crf_viterbi: NULL logits / mask / params / scratch / pred / score");
+    if (crf_shape_bad("m2f_crf_viterbi", T, C, B, L, cu_seqlens)) return 1;
+    CrfViterbiArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.mask = mask; a.params = params; a.cu_seqlens = cu_seqlens; a.B = B; a.L = L;
+    a.ws = static_cast<int*>(scratch); a.pred = pred; a.score = score;
+    M2F_HIP(m2f_launch_crf_viterbi(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_crf_filter(int S, int C, int rows, const float* logits, const float* params, const int32_t* count, const uint8_t* active,
+                   const int32_t* n_new, float* phi, m2f_stream_t stream) {
+    if (!logits || !params || !count || !phi) return fail("m2f_crf_filter: NULL logits / params / count / phi");
+    if (S < 1 || rows < 1 || C < 2 || C > 16) return fail("m2f_crf_filter: S >= 1, rows >= 1 and 2 <= C <= 16 required");
+    if (rows > 1 && !n_new) return fail("m2f_crf_filter: a chunk (rows > 1) needs n_new");
+    CrfFilterArgs a;
+    a.logits = logits; a.S = S; a.C = C; a.rows = rows; a.params = params; a.count = count; a.active = active; a.n_new = n_new; a.phi = phi;
+    M2F_HIP(m2f_launch_crf_filter(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
     return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
 }

@@ -135,6 +135,23 @@ __global__ __launch_bounds__(256) void m2f_eval_rows_focal_kernel(const EvalArgs
     if ((int)threadIdx.x < C * C) a.partial[(size_t)blockIdx.x * C * C + threadIdx.x] = tile[threadIdx.x];
 }
 
+// The prediction form of the rows launch (EvalArgs::pred non-null): the labels are counted against pred[t] (a decoded path: the Viterbi
+// launch of crf.hip in front of it) instead of the row's argmax, and the terms are NOT written - the launch in front (the CRF loss
+// without its gradient) left them.  A labelled row without a prediction (pred < 0) is not counted.
+__global__ __launch_bounds__(256) void m2f_eval_rows_pred_kernel(const EvalArgs a) {
+    __shared__ int tile[M2F_EVAL_MAX_C * M2F_EVAL_MAX_C];
+    const int C = a.C;
+    tile[threadIdx.x] = 0;
+    __syncthreads();
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < a.T; t += gridDim.x * 256) {
+        const int64_t y = a.labels[t];
+        const int pred = a.pred[t];
+        if (y >= 0 && y < C && pred >= 0 && pred < C) atomicAdd(&tile[(int)y * C + pred], 1);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < C * C) a.partial[(size_t)blockIdx.x * C * C + threadIdx.x] = tile[threadIdx.x];
+}
+
 __global__ __launch_bounds__(256) void m2f_eval_finalize_kernel(const float* __restrict__ terms, int T, int C,
                                                                 const int* __restrict__ partial, int n_partial,
                                                                 double* __restrict__ record) {
@@ -188,7 +205,8 @@ hipError_t m2f_launch_eval_scores(const EvalArgs& a, double* record, hipStream_t
     if (!a.logits || !a.labels || !a.terms || !a.partial || !record || a.T < 1 || a.C < 1 || a.C > M2F_EVAL_MAX_C)
         return hipErrorInvalidValue;
     const int blocks = m2f_eval_blocks(a.T);
-    if (a.gamma) hipLaunchKernelGGL(m2f_eval_rows_focal_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    if (a.pred) hipLaunchKernelGGL(m2f_eval_rows_pred_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    else if (a.gamma) hipLaunchKernelGGL(m2f_eval_rows_focal_kernel, dim3(blocks), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(m2f_eval_rows_kernel, dim3(blocks), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -581,6 +581,54 @@ struct CeFocalArgs {
     float* dlogits;                        // [T, C]
 };
 hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream);
+// Linear-chain CRF over a dialogue's labels (crf.hip).  params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.
+// Dialogue b owns token rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (packed and long-dialogue plans) or, cu_seqlens null, b*L .. b*L+L-1
+// (padded and bucket-padded plans).  The CHAIN of a dialogue is its rows with a label in [0, C), in row order (a -1 in the middle links
+// its neighbours; the logits of an unlabelled row are never read).  With t_1 < ... < t_n the chain rows, e the logits, y the labels:
+//   score(y) = start[y_1] + sum_k e[t_k, y_k] + sum_{k>=2} transitions[y_{k-1}, y_k] + end[y_n]     logZ = log sum_paths exp(score)
+//   loss_terms: num = logZ - score(y) on the dialogue's first chain row, 0 elsewhere; den = 1 on every chain row (token_mean through
+//               m2f_launch_loss_finalize, unchanged)
+//   dlogits[t_k, c] = P(y_k = c) - [c == y_k], zeros on every other row (unnormalised: the finalize launch scales it)
+//   partial (nullable = frozen parameters): [B][C*C + 2C] per-dialogue d transitions, d start, d end in the layout of params;
+//               m2f_launch_crf_grad_reduce adds them in dialogue order and, normalise != 0, divides by loss_out[1]
+// A dialogue without a chain row contributes zeros everywhere.  ws: float [T * (2C + 2)] (the saved chain rows of the backward sweep).
+struct CrfArgs {
+    const float* logits; int T, C;         // [T, C]
+    const int64_t* labels;                 // [T], -1 = not on the chain
+    const float* params;                   // [C*C + 2C]
+    const int32_t* cu_seqlens; int B, L;   // [B + 1] or null (then rows b*L + i)
+    float* ws;                             // [T * (2C + 2)]
+    float* loss_terms;                     // [T, 2]
+    float* dlogits;                        // [T, C], or null: the loss only (no backward sweep; the evaluation path) - partial must be null too
+    float* partial;                        // [B, C*C + 2C] or null
+};
+hipError_t m2f_launch_crf_nll(const CrfArgs& a, hipStream_t stream);
+hipError_t m2f_launch_crf_grad_reduce(const float* partial, int B, int C, const float* loss_out, int normalise, float* grad,
+                                      hipStream_t stream);
+// Viterbi over the rows whose mask is 0: pred[t] = the best path's class (-1 off the chain), score[b] = the path's score (0 for a
+// dialogue without a chain row).  First-max rule everywhere: the lowest class wins a tie.  ws: int [T * 5] (back pointers).
+struct CrfViterbiArgs {
+    const float* logits; int T, C;
+    const uint8_t* mask;                   // [T], 1 = not on the chain; null: every row of a dialogue is on it
+    const float* params;
+    const int32_t* cu_seqlens; int B, L;
+    int* ws;                               // [T * 5]
+    int32_t* pred;                         // [T]
+    float* score;                          // [B]
+};
+hipError_t m2f_launch_crf_viterbi(const CrfViterbiArgs& a, hipStream_t stream);
+// Forward filter of the streams: per slot phi = a - logsumexp(a), a = e + logsumexp_i(phi_old[i] + transitions[i, :]), a = start + e for
+// the slot's first utterance (count[s] + rows taken so far == 0).  Slot s takes rows s*rows .. s*rows + n_new[s] - 1 of logits in order
+// (n_new null: one row; active null: every slot; an inactive slot keeps its phi).  count is read, never written.
+struct CrfFilterArgs {
+    const float* logits; int S, C, rows;   // [S * rows, C]
+    const float* params;
+    const int32_t* count;                  // [S]
+    const uint8_t* active;                 // [S] or null
+    const int32_t* n_new;                  // [S] or null
+    float* phi;                            // [S, C], in and out
+};
+hipError_t m2f_launch_crf_filter(const CrfFilterArgs& a, hipStream_t stream);
 // loss_out[0] = num/den, loss_out[1] = den, loss_out[2] = num.  normalise != 0: dlogits *= 1/den
 // (single-process mean-over-valid loss); normalise == 0 leaves the sum-gradient for the data-parallel
 // path, which divides by the GLOBAL denominator after the all-reduce.
@@ -603,6 +651,8 @@ struct EvalArgs {
     int* partial;                          // [m2f_eval_blocks(T)][C * C]: one integer tile per workgroup of the rows launch
     const float* gamma = nullptr;          // device float [1] or null: non-null runs the focal form of the rows launch (the loss of CeFocalArgs
                                            // without a teacher, no gradient); null: the default form, its bits unchanged
+    const int32_t* pred = nullptr;         // [T] or null: non-null runs the prediction form of the rows launch - the labels counted against pred
+                                           // (a decoded path, -1 = none) instead of the argmax, `terms` left as the launch in front wrote them
 };
 static inline int m2f_eval_blocks(int T) { const int b = (T + 255) / 256; return b < M2F_EVAL_MAX_BLOCKS ? b : M2F_EVAL_MAX_BLOCKS; }
 hipError_t m2f_launch_eval_scores(const EvalArgs& a, double* record, hipStream_t stream);

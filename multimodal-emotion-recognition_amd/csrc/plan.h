@@ -252,6 +252,15 @@ struct m2f_plan {
     m2f::AccForm acc;
     bool distill_on = false;             // m2f_plan_distill: do_loss launches the distillation criterion
     bool focal_on = false;               // m2f_plan_focal: do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
+    // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
+    // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace
+    bool crf_on = false;
+    const float* crf_params = nullptr;   // [C*C + 2C]
+    float* crf_grad = nullptr;           // [C*C + 2C] or null (frozen)
+    float* crf_ws = nullptr;             // m2f_crf_scratch_floats(T, B, C) floats (null: a stream plan, or cls_out outside 2 .. 16)
+    int32_t* crf_pred = nullptr;         // [T]
+    float* crf_score = nullptr;          // [B]
+    float* s_phi = nullptr;              // stream and chunk plans (m2f_plan_stream_crf): the CALLER's filter state [S, C] over crf_params, or null
     // graph cache: m2f_step, m2f_step_part(0), m2f_step_part(1), ...
     m2f::GraphSlot graphs[m2f::SLOT_COUNT];
     uint64_t generation = 0;      // bumped by every entry point that replaces what captured launches point to (invalidate in plan.hip)

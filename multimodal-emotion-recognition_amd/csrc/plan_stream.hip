@@ -83,8 +83,36 @@ m2f_plan* m2f_plan_create_stream_paged(const m2f_config* cfg, int S, int C, int 
     return stream_plan_create("m2f_plan_create_stream_paged", cfg, S, C, past, precision, n_pages < 1 ? -1 : n_pages, page_rows, params, workspace,
                               workspace_bytes, param_shadow);
 }
+// The CRF's forward filter (m2f_plan_stream_crf): behind the classifier, in FRONT of the launch that advances the counters - it reads
+// the counts the slots held before this call.  rows: 1 (step: one row per active slot) or the chunk (prefill: n_new[s] rows in order).
+static int stream_filter(m2f_plan& P, int rows, hipStream_t s) {
+    if (!P.s_phi) return 0;
+    CrfFilterArgs a;
+    a.logits = static_cast<const float*>(P.bufs[M2F_BUF_LOGITS]); a.S = P.B; a.C = P.cfg.cls_out; a.rows = rows;
+    a.params = P.crf_params; a.count = P.s_len; a.active = rows == 1 ? P.s_active : nullptr; a.n_new = rows == 1 ? nullptr : P.s_new;
+    a.phi = P.s_phi;
+    M2F_HIP(m2f_launch_crf_filter(a, s));
+    return 0;
+}
+int m2f_plan_stream_crf(m2f_plan* plan, const float* params, float* phi) {
+    if (!plan) return fail("m2f_plan_stream_crf: NULL plan (destroyed?)");
+    m2f_plan& P = *plan;
+    if (!P.streaming && !P.s_parent) return fail("m2f_plan_stream_crf needs a stream or chunk plan (m2f_plan_create_stream / m2f_plan_create_stream_chunk)");
+    if ((params == nullptr) != (phi == nullptr)) return fail("m2f_plan_stream_crf: params and phi come together (both NULL: off)");
+    if (params && (P.cfg.cls_out < 2 || P.cfg.cls_out > 16)) return fail("m2f_plan_stream_crf: 2 .. 16 classes");
+    if ((reinterpret_cast<uintptr_t>(params) & 15) || (reinterpret_cast<uintptr_t>(phi) & 3)) return fail("m2f_plan_stream_crf: params must be 16-byte aligned");
+    if (params == P.crf_params && phi == P.s_phi) return 0;
+    // the filter launch travels by value inside the captured step / prefill: the capture goes, one eager call comes first
+    M2F_HIP(hipDeviceSynchronize());
+    P.graphs[P.s_parent ? SLOT_PREFILL : SLOT_STREAM].reset();
+    ++P.generation;
+    P.warmed = false;
+    P.crf_params = params; P.s_phi = phi;
+    return 0;
+}
 static int stream_body(m2f_plan& P, hipStream_t s) {
     if (int r = do_forward(P, s)) return r;
+    if (int r = stream_filter(P, 1, s)) return r;
     if (P.spk_same | P.spk_other)          // speaker heads: the new ids into the rows the new utterances took, behind the step's last attention launch
         M2F_HIP(m2f_launch_stream_advance_speakers(P.s_len, P.s_active, P.B, P.s_spk, static_cast<const uint8_t*>(P.bufs[M2F_BUF_SPEAKERS]), P.s_cap, P.s_ring, s));
     else
@@ -280,6 +308,7 @@ m2f_plan* m2f_plan_create_stream_chunk(m2f_plan* parent, int T, float* params, v
 }
 static int prefill_body(m2f_plan& P, hipStream_t s) {
     if (int r = do_forward(P, s)) return r;
+    if (int r = stream_filter(P, P.s_chunk, s)) return r;
     if (P.spk_same | P.spk_other)          // (as the step: the chunk's ids, then the counters)
         M2F_HIP(m2f_launch_stream_advance_speakers_n(P.s_len, P.s_new, P.B, P.s_chunk, P.s_spk, static_cast<const uint8_t*>(P.bufs[M2F_BUF_SPEAKERS]), P.s_cap, P.s_ring, s));
     else

@@ -421,8 +421,11 @@ class DataParallelStep:
     m2f_step(normalise=0) -> tail <- (den, num) -> all-reduce -> fused Adam with grad_scale = global den."""
 
     def __init__(self, model, optimizer, group=None, n_buckets: int = 4, exchange: str = "fp32", overlap: Optional[bool] = None,
-                 algorithm: str = "all_reduce", grad_bf16: Optional[bool] = None):
-        """overlap: with more than one rank, run the step in two parts (runtime.Plan.step_part) and put the all-reduce of the
+                 algorithm: str = "all_reduce", grad_bf16: Optional[bool] = None, crf=None):
+        """crf: a FROZEN ``crf.LinearChainCRF`` (``crf.params.requires_grad_(False)``) - every rank's step runs the CRF criterion over
+        it (an input like the class weights: den, exchange and micro-batch groups hold as they are); a trainable one is refused by
+        name (its gradient would need an all-reduce).
+        overlap: with more than one rank, run the step in two parts (runtime.Plan.step_part) and put the all-reduce of the
         fusion stack's / classifier's gradients on the wire before the encoders' backward starts (plans that cannot be split -
         fp32 mode - exchange after the whole backward as before).  None = the environment's M2F_DP_OVERLAP (default OFF: the
         path is verified bit for bit against overlap off through gloo staging, tests/test_dp_multirank_gpu.py, but has not yet
@@ -433,6 +436,9 @@ class DataParallelStep:
         if overlap is None:
             overlap = os.environ.get("M2F_DP_OVERLAP", "0") == "1"
         _refuse_speaker_heads(model)          # (before the engine, the reducer or any collective)
+        from .crf import check_step_args
+        check_step_args("DataParallelStep", crf, model.m2f_config.cls_out, data_parallel=True)
+        self.crf = crf
         self.model, self.optimizer, self.overlap = model, optimizer, bool(overlap)
         self.grad_bf16 = (os.environ.get("M2F_GRAD_BF16", "1") != "0") if grad_bf16 is None else bool(grad_bf16)
         self._split: Optional[int] = None
@@ -487,6 +493,10 @@ class DataParallelStep:
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
         gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DataParallelStep")
+        if self.crf is not None:
+            from .crf import check_step_args
+            check_step_args("DataParallelStep", self.crf, self.model.m2f_config.cls_out, class_weights, teacher_logits, distill,
+                            focal_gamma, label_smoothing, data_parallel=True)
         eng = self.model.engine()
         if self.overlap and self.reducer.world() > 1:
             _refuse_clipped_split(self.optimizer)     # (before any launch or collective: every rank refuses alike)
@@ -519,7 +529,7 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self.model._set_criterion(plan, teacher_logits, dist, gamma)
+            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf)
             if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

@@ -711,6 +711,100 @@ def cross_entropy_focal(logits: torch.Tensor, labels: torch.Tensor, class_w: Opt
     return out, dl
 
 
+def _crf_dialogues(who: str, T: int, batch: Optional[int], cu_seqlens: Optional[torch.Tensor]):
+    """(B, L, cu) of a CRF launch: `cu_seqlens` int32 [B + 1] on the device (dialogue b owns rows cu[b] .. cu[b+1]-1), or `batch`
+    dialogues of T // batch rows each."""
+    if cu_seqlens is not None:
+        if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2:
+            raise ValueError(f"{who}: cu_seqlens must be int32 [B + 1] (got {tuple(cu_seqlens.shape)} {cu_seqlens.dtype})")
+        return cu_seqlens.numel() - 1, 0, cu_seqlens.contiguous()
+    if batch is None or batch < 1 or T % batch:
+        raise ValueError(f"{who}: without cu_seqlens, batch must divide the {T} rows (got batch={batch!r})")
+    return batch, T // batch, None
+
+
+def _crf_params(who: str, params: torch.Tensor, C: int) -> torch.Tensor:
+    if not 2 <= C <= 16:
+        raise ValueError(f"{who}: 2 <= C <= 16 required (got C = {C})")
+    if params.dtype != torch.float32 or params.numel() != C * C + 2 * C:
+        raise ValueError(f"{who}: params must be fp32 of C*C + 2*C = {C * C + 2 * C} elements "
+                         f"[transitions | start | end] (got {params.numel()} {params.dtype})")
+    return params.contiguous()
+
+
+def crf_nll(logits: torch.Tensor, labels: torch.Tensor, params: torch.Tensor, batch: Optional[int] = None,
+            cu_seqlens: Optional[torch.Tensor] = None, normalise: bool = True, param_grad: bool = True, logit_grad: bool = True):
+    """Linear-chain CRF loss (m2f_crf_nll): logits [T, C] fp32, labels int64 [T] (-1 = off the chain), params fp32 [C*C + 2C] =
+    [transitions | start | end]; dialogues by `cu_seqlens` (int32 [B + 1]) or `batch` equal spans of T // batch rows.
+    -> (loss_out[4] = loss, den, num, -; dlogits [T, C]; dparams [C*C + 2C] or None with param_grad=False; loss_terms [T, 2]).
+    logit_grad=False (with param_grad=False): the loss alone - the forward sweep, no dlogits (None)."""
+    runtime.require_gpu()
+    T, C = logits.shape
+    if logits.dtype != torch.float32:
+        raise ValueError(f"crf_nll: logits must be fp32 (got {logits.dtype})")
+    params = _crf_params("crf_nll", params, C)
+    B, L, cu = _crf_dialogues("crf_nll", T, batch, cu_seqlens)
+    dev = logits.device
+    scratch = torch.empty(int(lib().m2f_crf_scratch_floats(T, B, C)), dtype=torch.float32, device=dev)
+    terms = torch.empty(T, 2, dtype=torch.float32, device=dev)
+    if param_grad and not logit_grad:
+        raise ValueError("crf_nll: param_grad needs logit_grad (the parameter gradient comes out of the backward sweep)")
+    dl = torch.empty(T, C, dtype=torch.float32, device=dev) if logit_grad else None
+    out = torch.zeros(4, dtype=torch.float32, device=dev)
+    dp = torch.empty(C * C + 2 * C, dtype=torch.float32, device=dev) if param_grad else None
+    logits, labels = logits.contiguous(), labels.contiguous()
+    check(lib().m2f_crf_nll(T, C, B, L, ptr(cu), ptr(logits), ptr(labels), ptr(params), int(normalise), ptr(scratch), ptr(terms),
+                            ptr(dl), ptr(dp), ptr(out), stream_ptr()), "m2f_crf_nll")
+    return out, dl, dp, terms
+
+
+def crf_viterbi(logits: torch.Tensor, mask: torch.Tensor, params: torch.Tensor, batch: Optional[int] = None,
+                cu_seqlens: Optional[torch.Tensor] = None):
+    """Viterbi path (m2f_crf_viterbi): logits [T, C] fp32, mask bool / uint8 [T] (True = off the chain) -> (pred int32 [T], -1 off the
+    chain; score fp32 [B]).  The lowest class wins every tie."""
+    runtime.require_gpu()
+    T, C = logits.shape
+    if logits.dtype != torch.float32:
+        raise ValueError(f"crf_viterbi: logits must be fp32 (got {logits.dtype})")
+    params = _crf_params("crf_viterbi", params, C)
+    B, L, cu = _crf_dialogues("crf_viterbi", T, batch, cu_seqlens)
+    dev = logits.device
+    mask = mask.reshape(-1).to(torch.uint8).contiguous()
+    if mask.numel() != T:
+        raise ValueError(f"crf_viterbi: mask must have {T} elements (got {mask.numel()})")
+    scratch = torch.empty(5 * T, dtype=torch.int32, device=dev)
+    pred = torch.empty(T, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    logits = logits.contiguous()
+    check(lib().m2f_crf_viterbi(T, C, B, L, ptr(cu), ptr(logits), ptr(mask), ptr(params), ptr(scratch), ptr(pred), ptr(score),
+                                stream_ptr()), "m2f_crf_viterbi")
+    return pred, score
+
+
+def crf_filter(logits: torch.Tensor, params: torch.Tensor, phi: torch.Tensor, count: torch.Tensor,
+               active: Optional[torch.Tensor] = None, n_new: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Forward filter (m2f_crf_filter), IN PLACE on phi [S, C] fp32: logits [S, C] (one row per active slot) or [S, rows, C] with
+    n_new int32 [S] (slot s takes its first n_new[s] rows in order); count int32 [S] = utterances the slot held before the call (read
+    only); active bool / uint8 [S] or None (all).  Returns phi."""
+    runtime.require_gpu()
+    S, C = phi.shape
+    rows = 1 if logits.dim() == 2 else logits.shape[1]
+    if logits.dtype != torch.float32 or phi.dtype != torch.float32 or not phi.is_contiguous() or logits.numel() != S * rows * C:
+        raise ValueError(f"crf_filter: logits [S, C] or [S, rows, C] and a contiguous phi [S, C], both fp32, required "
+                         f"(got {tuple(logits.shape)} {logits.dtype}, {tuple(phi.shape)} {phi.dtype})")
+    params = _crf_params("crf_filter", params, C)
+    if count.dtype != torch.int32 or count.numel() != S or (n_new is not None and (n_new.dtype != torch.int32 or n_new.numel() != S)):
+        raise ValueError("crf_filter: count and n_new must be int32 [S]")
+    if rows > 1 and n_new is None:
+        raise ValueError("crf_filter: logits [S, rows, C] need n_new")
+    active = active.reshape(-1).to(torch.uint8).contiguous() if active is not None else None
+    logits, count = logits.contiguous(), count.contiguous()
+    n_new = n_new.contiguous() if n_new is not None else None
+    check(lib().m2f_crf_filter(S, C, rows, ptr(logits), ptr(params), ptr(count), ptr(active), ptr(n_new), ptr(phi), stream_ptr()),
+          "m2f_crf_filter")
+    return phi
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
                       need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,

@@ -680,7 +680,7 @@ class M2FNet(nn.Module):
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
                    distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
-                   focal_gamma: Optional[float] = None) -> torch.Tensor:
+                   focal_gamma: Optional[float] = None, crf=None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -697,8 +697,18 @@ class M2FNet(nn.Module):
         hard-label term scaled by ``(1 - p_y)^gamma``, one kernel in the criterion's place, the same ``loss_terms()`` tail; with
         ``teacher_logits`` / ``distill`` the factor scales the hard-label term only.  gamma lives on the device (uploaded only when it
         changed): a schedule of gamma replays the captured step.  None (default): the criterion without it, bit for bit; focal and plain
-        calls mix freely on one model.  Anything else is a ValueError before any launch."""
+        calls mix freely on one model.  Anything else is a ValueError before any launch.
+        crf (a ``crf.LinearChainCRF`` of cls_out classes on the model's device): the step's criterion is the linear-chain CRF over each
+        dialogue's labelled utterances (token_mean), one kernel in the criterion's place and the same tail - the step stays one
+        replayed graph.  Its parameter block is an input of the step, never part of this model's parameters; trainable,
+        ``crf.params.grad`` is a view of a gradient buffer this step overwrites, and any torch optimizer over ``crf.parameters()``
+        trains it beside ``FusedAdam`` (the values are read on the device: the captured step replays while they change).  Refused
+        (ValueError naming the pair) with class_weights, teacher_logits / distill, focal_gamma, label_smoothing != 0.0, and - trainable
+        only - under gradient accumulation; a frozen block (``crf.params.requires_grad_(False)``) works under every training mode."""
+        from .crf import check_step_args
         from .distill import resolve_distill_args
+        check_step_args("M2FNet.train_step", crf, self.m2f_config.cls_out, class_weights, teacher_logits, distill, focal_gamma,
+                        label_smoothing, accumulating=self._engine is not None and self._engine.accumulate)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
         gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.train_step")
         dist = resolve_distill_args(teacher_logits, distill, mask.shape[0], mask.shape[1], self.m2f_config.cls_out, mask.device,
@@ -715,7 +725,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist, gamma)
+            self._set_criterion(plan, teacher_logits, dist, gamma, crf)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -739,14 +749,23 @@ class M2FNet(nn.Module):
         else:
             loss = body()
         eng.publish_grads()
+        if crf is not None:
+            crf.publish_grad()
         eng.note_forward(plan)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
-    def _set_criterion(plan, teacher_logits, dist, gamma=None) -> None:
+    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None) -> None:
         """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
         temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
-        plan maps the teacher rows as it mapped the batch)."""
+        plan maps the teacher rows as it mapped the batch).  `crf` (a LinearChainCRF; the callers refused every other criterion argument
+        beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains."""
+        if crf is not None:
+            plan.set_focal(None)
+            plan.distill(False)
+            plan.set_crf(*crf.step_buffers(plan.workspace.device, want_grad=plan.train))
+            return
+        plan.set_crf(None)
         plan.set_focal(gamma)
         plan.distill(dist is not None)
         if dist is not None:
@@ -756,14 +775,19 @@ class M2FNet(nn.Module):
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,
                   label_smoothing: float = 0.1, use_graph: bool = True, speakers: Optional[torch.Tensor] = None,
-                  focal_gamma: Optional[float] = None) -> None:
+                  focal_gamma: Optional[float] = None, crf=None) -> None:
         """Loop body of the reference's ``validate`` / ``test`` (src/train.py:252-272, src/test.py:55-74) in one call: the forward of
         a no-grad ``forward`` (same plan: buckets, packed plans, long dialogues), then the batch's criterion loss, accuracy, weighted
         F1 and confusion matrix ADDED to ``scores`` (a ``metrics.DeviceScores``), all on the device.  Returns nothing and waits for
         nothing: ``scores.last()`` is a device view of the batch's three numbers, ``scores.result()`` / ``mean_loss()`` read the pass.
         The plan's own token rows are scored - pad and filler rows carry label -1.  speakers: as ``train_step``.
         focal_gamma: as ``train_step`` - the loss is the focal criterion's (the bits its train kernel gives for the same rows), so
-        validation and early stopping see the criterion that trains; accuracy, F1 and the confusion matrix do not depend on it."""
+        validation and early stopping see the criterion that trains; accuracy, F1 and the confusion matrix do not depend on it.
+        crf (a ``crf.LinearChainCRF``): the loss is the CRF loss over the labelled rows (the train kernel's bits), and predictions,
+        accuracy, F1 and the confusion matrix come from the Viterbi path over each dialogue's utterances instead of the per-row argmax.
+        The same refusals as ``train_step``."""
+        from .crf import check_step_args
+        check_step_args("M2FNet.eval_step", crf, self.m2f_config.cls_out, class_weights, None, None, focal_gamma, label_smoothing)
         ids = _check_speakers("M2FNet.eval_step", self._speaker_heads, speakers, mask.shape)
         gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.eval_step")
         if self.training and self.m2f_config.dropout > 0.0:
@@ -780,7 +804,12 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            plan.set_focal(gamma)
+            if crf is not None:
+                plan.set_focal(None)
+                plan.set_crf(*crf.step_buffers(plan.workspace.device, want_grad=False))
+            else:
+                plan.set_crf(None)
+                plan.set_focal(gamma)
             plan.eval_step(scores.record, label_smoothing, class_weights is not None, use_graph)
 
         if use_graph:                                    # capture / replay on the engine's own stream
@@ -795,7 +824,7 @@ class M2FNet(nn.Module):
 
     # -- streaming inference (one new utterance per live dialogue; streaming.DialogueStream) -----------------------------------------
     def stream(self, max_streams: int, capacity: Optional[int] = None, use_graph: bool = True, max_chunk: int = 1,
-               pages: Optional[int] = None, page_rows: int = 16, attention: bool = False):
+               pages: Optional[int] = None, page_rows: int = 16, attention: bool = False, crf=None):
         """A ``DialogueStream`` of ``max_streams`` slots over this model's weights: ``stream.step(text [S, d_t], audio [S, d_a],
         active)`` labels the utterance that has just arrived in each active slot from per-site K / V caches on the device, at the
         cost of one row per dialogue - where ``forward`` would re-run the whole prefix.  Needs a causal context band
@@ -814,6 +843,9 @@ class M2FNet(nn.Module):
         returns them at ``reset`` (``streaming.PageAllocator``).  Memory follows the utterances cached, not ``max_streams * capacity``:
         the 3.8 GB above hold 2,048 pages of 16 rows, about 2,000 live MELD-length dialogues.  Same logits, bit for bit; a call that
         would need more pages than are free raises RuntimeError and changes nothing.
+        crf (a ``crf.LinearChainCRF`` of cls_out classes on the model's device): the stream also runs the CRF's forward filter inside
+        every step / prefill graph, behind the classifier - ``stream.crf_posterior()`` returns log P(label of each slot's last utterance
+        | its dialogue so far); the logits are unchanged; C floats per slot, so it works under any window; snapshots carry the state.
         attention: True - every step also keeps, per attention site, slot and head, the row of attention probabilities of the new
         utterance over the cached ones, and ``stream.attention(average_heads=True, sites=None)`` returns them after a ``step`` (which
         cached utterances did this prediction use); ``sum_sites H * max_streams * capacity * 4 B`` more memory (17.8 MB at C3, 64
@@ -831,7 +863,7 @@ class M2FNet(nn.Module):
             raise ValueError(f"M2FNet.stream: max_streams must be an integer >= 1, got {max_streams!r}")
         pages, page_rows = resolve_pages(pages, page_rows)
         return DialogueStream(self, max_streams, resolve_capacity(past, capacity), use_graph, resolve_max_chunk(max_chunk), pages, page_rows,
-                              attention=bool(attention))
+                              attention=bool(attention), crf=crf)
 
     def set_grad_bf16(self, on: bool = True) -> bool:
         """bf16 mode: every following training step leaves its gradients ROUNDED ONCE TO BF16 in one flat bf16 buffer - the weight-gradient

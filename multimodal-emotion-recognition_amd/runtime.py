@@ -187,6 +187,8 @@ SIGNATURES = {
     "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),
     "m2f_plan_distill": (c_int, [c_void_p, c_int]),
     "m2f_plan_focal": (c_int, [c_void_p, c_int]),
+    "m2f_plan_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "m2f_plan_stream_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_plan_fused_adam": (c_int, [c_void_p, c_int]),
@@ -237,6 +239,12 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     "m2f_cross_entropy_focal": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_crf_scratch_floats": (c_int64, [c_int, c_int, c_int]),
+    "m2f_crf_nll": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p]),
+    "m2f_crf_viterbi": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "m2f_crf_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -750,6 +758,17 @@ class Plan:
         if gamma is not None:
             self.set_focal_gamma(gamma)
 
+    def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
+        """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's
+        flat block, read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan
+        keeps the two tensors alive; a change of the pointers or of the switch drops the captured steps, a change of the values does
+        not.  The focal and distillation switches must be off (the C entry refuses by name)."""
+        key = (None if params is None else params.data_ptr(), None if grad is None else grad.data_ptr())
+        if key == getattr(self, "_crf_key", (None, None)):
+            return
+        check(lib().m2f_plan_crf(self._h(), ptr(params), ptr(grad)), "m2f_plan_crf")
+        self._crf_key, self._crf_ref = key, (params, grad)
+
     def _casted(self) -> None:
         if self.shared_shadow and not self._fresh and self._on_cast is not None:
             self._on_cast()
@@ -1040,6 +1059,12 @@ class StreamPlan:
     def step(self, use_graph: bool = True) -> None:
         check(lib().m2f_stream_step(self._h(), int(use_graph), stream_ptr()), "m2f_stream_step")
 
+    def stream_crf(self, params: Optional[torch.Tensor], phi: Optional[torch.Tensor]) -> None:
+        """m2f_plan_stream_crf: the step / prefill also runs the CRF's forward filter over `params` into the caller's `phi` [S, C] (both
+        None: off).  The plan keeps the two tensors alive."""
+        check(lib().m2f_plan_stream_crf(self._h(), ptr(params), ptr(phi)), "m2f_plan_stream_crf")
+        self._crf_ref = (params, phi)
+
     def reset(self, mask: Optional[torch.Tensor] = None) -> None:
         """mask: device uint8 [S], non-zero = the slot starts a new dialogue; None = every slot."""
         check(lib().m2f_stream_reset(self._h(), ptr(mask), stream_ptr()), "m2f_stream_reset")
@@ -1204,6 +1229,7 @@ class StreamChunkPlan:
             self.attention_speakers(par.speakers)
     nbytes = StreamPlan.nbytes
     close = StreamPlan.close
+    stream_crf = StreamPlan.stream_crf
 
     def prefill(self, use_graph: bool = True) -> None:
         """forward over the chunk + len[s] += new[s]"""

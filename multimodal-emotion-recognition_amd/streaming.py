@@ -357,7 +357,7 @@ class StreamSnapshot:
     A SNAPSHOT BELONGS TO THE WEIGHTS THAT WROTE IT, like the caches it came from."""
 
     def __init__(self, data: torch.Tensor, lengths: Sequence[int], row_offsets: Sequence[int], signature: tuple, _ready=None,
-                 speakers: Optional[torch.Tensor] = None):
+                 speakers: Optional[torch.Tensor] = None, crf: Optional[torch.Tensor] = None):
         sites, bf16, past, ring = signature
         self.signature = make_signature(sites, bf16, past, 0 if ring is None else ring)
         self.lengths = [int(n) for n in lengths]
@@ -375,6 +375,18 @@ class StreamSnapshot:
         if speakers is not None and (speakers.dim() != 1 or speakers.dtype != torch.uint8 or speakers.numel() != sum(rows)):
             raise ValueError(f"StreamSnapshot: speakers must be a 1-D uint8 tensor of {sum(rows)} entries, got {speakers.dtype} {tuple(speakers.shape)}")
         self._speakers = speakers
+        # the CRF filter's state of every entry (a stream made with crf=; None otherwise): fp32 [entries, C]
+        if crf is not None and (crf.dim() != 2 or crf.dtype != torch.float32 or crf.shape[0] != len(self.lengths)):
+            raise ValueError(f"StreamSnapshot: crf must be an fp32 tensor [{len(self.lengths)}, C], got {crf.dtype} {tuple(crf.shape)}")
+        self._crf = crf
+
+    @property
+    def crf(self) -> Optional[torch.Tensor]:
+        """The CRF filter's state of every entry, fp32 [entries, C] (None: the stream ran without crf=)."""
+        if self._crf is not None and self._ready is not None:
+            self._ready.synchronize()
+            self._ready = None
+        return self._crf
 
     @property
     def speakers(self) -> Optional[torch.Tensor]:
@@ -433,11 +445,17 @@ class StreamSnapshot:
         if spk is not None:
             sp = [spk[self.row_offsets[i]: self.row_offsets[i] + rows[i]] for i in idx]
             spk = torch.cat(sp) if sp else spk[:0]
-        return StreamSnapshot(picked, [self.lengths[i] for i in idx], snapshot_row_offsets([rows[i] for i in idx]), self.signature, speakers=spk)
+        crf = self.crf
+        if crf is not None:
+            crf = crf[idx] if idx else crf[:0]
+        return StreamSnapshot(picked, [self.lengths[i] for i in idx], snapshot_row_offsets([rows[i] for i in idx]), self.signature, speakers=spk,
+                              crf=crf)
 
     def to(self, device) -> "StreamSnapshot":
         spk = self.speakers
-        return StreamSnapshot(self.data.to(device), self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.to(device))
+        crf = self.crf
+        return StreamSnapshot(self.data.to(device), self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.to(device),
+                              crf=None if crf is None else crf.to(device))
 
     def cpu(self, pin: bool = False) -> "StreamSnapshot":
         data = self.data
@@ -448,7 +466,9 @@ class StreamSnapshot:
         else:
             data = data.cpu()
         spk = self.speakers
-        return StreamSnapshot(data, self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.cpu())
+        crf = self.crf
+        return StreamSnapshot(data, self.lengths, self.row_offsets, self.signature, speakers=None if spk is None else spk.cpu(),
+                              crf=None if crf is None else crf.cpu())
 
     def state_dict(self) -> dict:
         sites, bf16, past, ring = self.signature
@@ -457,6 +477,8 @@ class StreamSnapshot:
              "ring": -1 if ring is None else ring}
         if self._speakers is not None:                     # (only a snapshot WITH speakers extends the dictionary)
             d["speakers"] = self.speakers
+        if self._crf is not None:                          # (likewise)
+            d["crf"] = self.crf
         return d
 
     @classmethod
@@ -466,7 +488,7 @@ class StreamSnapshot:
         if (past is None) != (ring is None):
             raise ValueError("StreamSnapshot.from_state_dict: a window and a ring capacity come together")
         return cls(d["data"], d["lengths"], d["row_offsets"], (tuple((int(H), int(hd)) for H, hd in d["sites"]), bool(d["bf16"]), past, ring),
-                   speakers=d.get("speakers"))
+                   speakers=d.get("speakers"), crf=d.get("crf"))
 
 
 class DialogueStream:
@@ -540,7 +562,12 @@ class DialogueStream:
     prediction used."""
 
     def __init__(self, model, max_streams: int, capacity: int, use_graph: bool = True, max_chunk: int = 1,
-                 pages: Optional[int] = None, page_rows: int = 16, attention: bool = False):
+                 pages: Optional[int] = None, page_rows: int = 16, attention: bool = False, crf=None):
+        crf_block = None
+        if crf is not None:                                 # (refused before anything is created)
+            from .crf import check_step_args
+            check_step_args("M2FNet.stream", crf, model.m2f_config.cls_out)
+            crf_block = crf.block(model.engine().device).detach()
         self.model, self.use_graph = model, bool(use_graph)
         self.max_streams, self.capacity = int(max_streams), int(capacity)
         self.max_chunk = resolve_max_chunk(max_chunk)
@@ -571,6 +598,24 @@ class DialogueStream:
         self._attn_act: Optional[List[bool]] = None           # the mask of the last step, while its rows are what the buffer holds
         if self.attention_on:
             self.plan.stream_attention(True)
+        # the CRF's forward filter (model.stream(..., crf=module)): C floats per slot, whatever the window
+        self.crf = crf
+        self._phi: Optional[torch.Tensor] = None
+        if crf is not None:
+            self._phi = torch.zeros(self.max_streams, cfg.cls_out, dtype=torch.float32, device=eng.device)
+            block = crf_block
+            torch.cuda.current_stream(eng.device).synchronize()          # (the zero-fill, before the engine's stream reads it)
+            for pl in (self.plan, self.chunk_plan):
+                if pl is not None:
+                    pl.stream_crf(block, self._phi)
+
+    def crf_posterior(self) -> torch.Tensor:
+        """``phi`` fp32 [S, C] (a copy): log P(label of the slot's LAST utterance | its dialogue so far) under the stream's CRF - the
+        forward filter, run inside every step / prefill behind the classifier; the ``end`` term is not applied online.  Rows of slots
+        that hold no utterance are zeros.  Needs a stream made with ``crf=``."""
+        if self._phi is None:
+            raise RuntimeError("DialogueStream.crf_posterior: this stream was made without a CRF (model.stream(..., crf=module))")
+        return self._on_stream(lambda: self._phi.clone())
 
     # -- plumbing ----------------------------------------------------------------------------------------------------------------
     def _on_stream(self, body):
@@ -815,7 +860,7 @@ class DialogueStream:
                     self.chunk_plan.follow_speakers()
                 if not self._spk:
                     self.plan.stream_speakers(False)
-            self._on_stream(lambda: self.plan.reset(None))
+            self._on_stream(lambda: (self.plan.reset(None), self._phi.zero_() if self._phi is not None else None))
             self.lengths = [0] * S
             if self.allocator is not None:
                 self.allocator.release()
@@ -830,6 +875,8 @@ class DialogueStream:
         def body():
             mask = host.to(dev)
             self.plan.reset(mask)
+            if self._phi is not None:
+                self._phi.masked_fill_(mask.bool()[:, None], 0.0)
             mask.record_stream(torch.cuda.current_stream(dev))
         self._on_stream(body)
         for s in slots:
@@ -907,9 +954,16 @@ class DialogueStream:
         ready = None
         spk_c, spk = self.plan.spk_cache, None              # speaker heads: the ids of the same rows (plain indexing: tiny and not hot)
         spk_host = torch.empty(sum(rows), dtype=torch.uint8, pin_memory=True) if (pinned and spk_c is not None) else None
+        phi, phi_host = None, None                          # the CRF filter's state of the same slots
+        if self._phi is not None and pinned:
+            phi_host = torch.empty(len(slots), self._phi.shape[1], dtype=torch.float32, pin_memory=True)
 
         def body():
-            nonlocal ready
+            nonlocal ready, phi
+            if self._phi is not None:
+                phi = self._phi[slots] if slots else self._phi[:0].clone()
+                if phi_host is not None:
+                    phi_host.copy_(phi, non_blocking=True)
             self._send_table()                              # (every path that changes the table sends it; a gather must never depend on that)
             nonlocal spk
             if data.numel():
@@ -925,7 +979,7 @@ class DialogueStream:
                 ready.record(torch.cuda.current_stream(dev))
         self._on_stream(body)
         return StreamSnapshot(data if host is None else host, lengths, offsets, sig, _ready=ready,
-                              speakers=spk if spk_host is None else spk_host)
+                              speakers=spk if spk_host is None else spk_host, crf=phi if phi_host is None else phi_host)
 
     def snapshot(self, slots: Optional[Sequence[int]] = None) -> StreamSnapshot:
         return self._snapshot(slots, pinned=False)
@@ -935,6 +989,11 @@ class DialogueStream:
         if (snap.speakers is None) != (self._spk is None):  # (before anything is released or launched: the stream stays as it is)
             raise RuntimeError("stream.restore: the snapshot " + ("carries no speaker ids" if snap.speakers is None else "carries speaker ids") +
                                ", this stream runs " + ("without speaker heads" if self._spk is None else f"speaker_heads={self._spk}"))
+        if (snap.crf is None) != (self._phi is None):      # (likewise)
+            raise RuntimeError("stream.restore: the snapshot " + ("carries no CRF filter state" if snap.crf is None else "carries a CRF filter state") +
+                               ", this stream runs " + ("without a CRF" if self._phi is None else "with crf="))
+        if snap.crf is not None and snap.crf.shape[1] != self._phi.shape[1]:
+            raise ValueError(f"stream.restore: the snapshot's CRF state is {tuple(snap.crf.shape)}, this stream's [*, {self._phi.shape[1]}]")
         if snap.signature != self.signature:
             raise ValueError(f"stream.restore: the snapshot was written under (sites (H, hd), bf16, past, ring capacity) = {snap.signature}, "
                              f"this stream runs {self.signature}")
@@ -962,6 +1021,8 @@ class DialogueStream:
                 for s_, o_, r_ in zip(slots, snap.row_offsets, rows):
                     if r_:
                         self.plan.spk_cache[s_, :r_].copy_(spk[o_: o_ + r_], non_blocking=True)
+            if snap.crf is not None:                        # (C floats per entry: a host copy is uploaded here, as nothing else is)
+                self._phi[slots] = snap.crf.to(self._eng.device, non_blocking=True)
         try:
             self._on_stream(body)
         except Exception:                                   # a launch that was refused: the host keeps describing the device -

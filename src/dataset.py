@@ -137,6 +137,12 @@ class Dataset(torch.utils.data.Dataset):
     def get_labels(self):
         return self.text["Emotion"].to_numpy()
 
+    def get_dialogue_labels(self):
+        """(labels, lengths): every dialogue's labels in utterance order, one dialogue after the other, and the utterances per dialogue
+        - what `LinearChainCRF.from_label_counts` counts (runtime.crf.init: bigram)."""
+        labels = self._labels.numpy()
+        return np.concatenate([labels[np.asarray(r)] for r in self.rows]), np.asarray([len(r) for r in self.rows])
+
 
 def collate_fn(batch):
     B = len(batch)

@@ -37,6 +37,12 @@ def load_model_weights(model, checkpoint_path, device, averaged: bool = False):
     else:
         model.load_state_dict(state["model_state_dict"])
         print("Scoring the live weights (model_state_dict)")
+    crf = getattr(model, "crf", None)                       # (solver.loss_fn: CRF; set by main())
+    if crf is not None:
+        if "crf_state_dict" not in state:
+            raise ValueError("solver.loss_fn is CRF but the checkpoint holds no 'crf_state_dict'")
+        crf.load_state_dict(state["crf_state_dict"])
+        print("Decoding with the checkpoint's CRF (crf_state_dict)")
     return state.get("epoch")
 
 
@@ -146,9 +152,17 @@ def _stream_for(model, B, L):
     if st is None or st.max_streams < B or (not windowed and st.capacity < L) or st.max_chunk != chunk or st.pages != pages:
         if st is not None:
             st.close()
-        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64), max_chunk=chunk, pages=pages)
+        # (solver.loss_fn: CRF - the stream also runs the forward filter: stream.crf_posterior() is there for the caller; the pass
+        #  below keeps the per-row argmax of the emission logits)
+        st = model.stream(B, capacity=None if windowed else min(512, (L + 63) // 64 * 64), max_chunk=chunk, pages=pages,
+                          crf=getattr(model, "crf", None))
         model._test_stream = st
     return st
+
+
+def decoded(crf, logits, padding_mask):
+    from train import decoded as dec
+    return dec(crf, logits, padding_mask)
 
 
 def _speaker_kw(model, batch, device):
@@ -180,6 +194,8 @@ def test(model, dl_test, device):
         scores = DeviceScores(model.m2f_config.cls_out, device)
         gamma = getattr(model, "focal_gamma", None)            # (solver.loss_fn: Focal; set by main())
         focal = {} if gamma is None else {"focal_gamma": gamma}
+        if getattr(model, "crf", None) is not None:        # (the CRF loss and the Viterbi path)
+            focal = {"label_smoothing": 0.0, "crf": model.crf}
         with torch.inference_mode():
             for batch in tqdm(dl_test, total=len(dl_test)):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
@@ -194,7 +210,8 @@ def test(model, dl_test, device):
         for batch in tqdm(dl_test, total=len(dl_test)):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
-            scores.update(model(text, audio, padding_mask, **_speaker_kw(model, batch, device)), emotion)
+            logits = model(text, audio, padding_mask, **_speaker_kw(model, batch, device))
+            scores.update(decoded(getattr(model, "crf", None), logits, padding_mask), emotion)
             maps.add(padding_mask)
     maps.write()
     return scores.result()
@@ -238,7 +255,9 @@ def main(config=None):
     model.stream_chunk = stream_chunk
     model.stream_pages = stream_pages
     model.attention_maps_out = attention_maps
-    from train import ema_settings, focal_gamma_setting
+    from train import attach_crf, build_crf, crf_settings, ema_settings, focal_gamma_setting
+    # (solver.loss_fn: CRF - the block comes from the checkpoint's 'crf_state_dict'; batched passes decode with Viterbi)
+    attach_crf(model, build_crf(dict(crf_settings(config), init="zeros", trainable=False), None, device) if config.solver.loss_fn == "CRF" else None)
     # (solver.loss_fn: Focal - the device record's loss is the criterion that trained, with runtime.focal_gamma; accuracy and F1 do not depend on it)
     model.focal_gamma = focal_gamma_setting(config) if config.solver.loss_fn == "Focal" else None
     ema = ema_settings(config)

@@ -3,6 +3,7 @@ signatures, batch-dict keys, checkpoint format ({'epoch', 'model_state_dict', 'o
 stopping / best-weights protocol and per-batch metric rule.  The model, criterion and optimizer are the HIP-backed
 ones (M2FNet plan, fused CE, fused Adam); with ``runtime.fused_step`` the loop body of the reference
 (src/train.py:227-231) runs as one hipGraph launch + one Adam kernel."""
+import math
 import os
 import sys
 from datetime import datetime
@@ -20,6 +21,7 @@ from metrics import BatchScores, move_batch  # noqa: E402
 from model import M2FNet  # noqa: E402
 from utils import get_config  # noqa: E402
 from mer_amd import dp  # noqa: E402
+from mer_amd.crf import LinearChainCRF  # noqa: E402
 from mer_amd.optim import MAX_GROUPS, FusedAdam, FusedAdamW, M2FCrossEntropyLoss, M2FFocalLoss  # noqa: E402
 from mer_amd.watch import ModelWatch, check_bins, check_kinds, check_log_freq  # noqa: E402
 
@@ -34,6 +36,7 @@ except ImportError:
     wandb = None
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict")
+CRF_KEY = "crf_state_dict"                              # present only under solver.loss_fn: CRF (the LinearChainCRF block)
 EMA_KEY = "ema_state_dict"                              # present only when runtime.ema is enabled
 N_CLASSES = 7
 
@@ -458,16 +461,76 @@ def focal_gamma_setting(cfg) -> float:
     return check_focal_gamma(_runtime(cfg, "focal_gamma", 2.0), "focal_gamma", "runtime")
 
 
+def crf_settings(cfg) -> dict:
+    """`runtime.crf` = {init: zeros | bigram, smoothing: 1.0, trainable: True, lr: 1.0e-2}: the block `solver.loss_fn: CRF` builds
+    (mer_amd.crf.LinearChainCRF).  init: bigram fills it with the log bigram, start and end frequencies of the training labels
+    (`from_label_counts`, with `smoothing`); trainable: a second torch.optim.Adam with `lr` steps it beside the model's optimizer.
+    Checked on the host before the GPU is touched; ignored under other criteria."""
+    block = dict(_runtime(cfg, "crf", None) or {})
+    unknown = sorted(set(block) - {"init", "smoothing", "trainable", "lr"})
+    if unknown:
+        raise ValueError(f"runtime.crf: unknown key(s) {unknown}; it takes init, smoothing, trainable, lr")
+    out = {"init": block.get("init", "zeros"), "smoothing": block.get("smoothing", 1.0), "trainable": block.get("trainable", True),
+           "lr": block.get("lr", 1.0e-2)}
+    if out["init"] not in ("zeros", "bigram"):
+        raise ValueError(f"runtime.crf.init must be zeros or bigram, got {out['init']!r}")
+    if not isinstance(out["trainable"], bool):
+        raise ValueError(f"runtime.crf.trainable must be true or false, got {out['trainable']!r}")
+    for key, low_ok in (("smoothing", lambda v: v >= 0.0), ("lr", lambda v: v > 0.0)):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not low_ok(v):
+            raise ValueError(f"runtime.crf.{key} must be a finite number " + (">= 0" if key == "smoothing" else "> 0") + f", got {v!r}")
+        out[key] = float(v)
+    return out
+
+
+def build_crf(settings: dict, train_set, device):
+    """The criterion of `solver.loss_fn: CRF`: a LinearChainCRF of N_CLASSES classes on `device`; `crf.optimizer` is the torch Adam that
+    steps it when it is trainable (None: frozen - a pure input of the step)."""
+    if settings["init"] == "bigram":
+        labels, lengths = train_set.get_dialogue_labels()
+        crf = LinearChainCRF.from_label_counts(labels, lengths, smoothing=settings["smoothing"], num_classes=N_CLASSES)
+    else:
+        crf = LinearChainCRF(N_CLASSES)
+    crf = crf.to(device)
+    crf.params.requires_grad_(settings["trainable"])
+    crf.optimizer = torch.optim.Adam(crf.parameters(), lr=settings["lr"]) if settings["trainable"] else None
+    return crf
+
+
+def _crit_kw(criterion, data_parallel: bool = False):
+    """The criterion's arguments of train_step / eval_step / DataParallelStep: label smoothing, class weights and gamma of the cross
+    entropies; under the CRF criterion no smoothing, no weights and (the data-parallel step holds it itself) `crf=`."""
+    if isinstance(criterion, LinearChainCRF):
+        return {"label_smoothing": 0.0, "class_weights": None, **({} if data_parallel else {"crf": criterion})}
+    return {"label_smoothing": criterion.label_smoothing, "class_weights": criterion.weight, **_focal_kw(criterion)}
+
+
+def _crf_zero_grad(criterion) -> None:
+    if getattr(criterion, "optimizer", None) is not None:
+        criterion.optimizer.zero_grad()
+
+
+def _crf_step(criterion) -> None:
+    """The second optimizer of a trainable CRF criterion, behind the model's (its gradient is the step's own buffer, or autograd's)."""
+    if getattr(criterion, "optimizer", None) is not None:
+        criterion.optimizer.step()
+
+
 def _focal_kw(criterion):
     """{focal_gamma} for train_step / DataParallelStep / eval_step when the criterion is the focal one (its gamma as it stands: a schedule
     may have changed it), else nothing - the calls of a CE run are today's."""
     return {"focal_gamma": criterion.gamma} if isinstance(criterion, M2FFocalLoss) else {}
 
 
-def build_criterion(solver, train_set, device, focal_gamma: float = 2.0):
+def build_criterion(solver, train_set, device, focal_gamma: float = 2.0, crf: dict = None):
     """CE(ignore_index=-1, label_smoothing=0.1), optionally with sklearn's balanced class weights of the train labels; `loss_fn: Focal`:
     the same with every utterance's term scaled by (1 - p_y)^focal_gamma (M2FFocalLoss, an M2FCrossEntropyLoss: the fused step, the
     device metrics and every training mode take it)."""
+    if solver.loss_fn == "CRF":
+        if solver.balance_classes:
+            raise ValueError("solver.loss_fn: CRF does not combine with solver.balance_classes (the CRF criterion has no class-weighted form)")
+        return build_crf(crf if crf is not None else crf_settings({}), train_set, device)
     if solver.loss_fn not in ("CE", "Focal"):
         raise ValueError("Criterion not supported")
     class_weights = None
@@ -566,6 +629,12 @@ def resume_if_requested(config, model, optimizer, device):
     state = torch.load(path, map_location=device)
     model.load_state_dict(state["model_state_dict"])
     optimizer.load_state_dict(state["optimizer_state_dict"])
+    crf = getattr(model, "crf", None)
+    if crf is not None:
+        if CRF_KEY in state:
+            crf.load_state_dict(state[CRF_KEY])
+        elif _rank() == 0:
+            print(f"Checkpoint {path} holds no {CRF_KEY}: the CRF block starts from its initialisation")
     if ema_settings(config) is not None:
         if EMA_KEY in state:
             optimizer.load_ema_state_dict(state[EMA_KEY])
@@ -578,12 +647,20 @@ def _has_average(optimizer) -> bool:
     return getattr(optimizer, "n_averaged", 0) > 0
 
 
+def attach_crf(model, criterion) -> None:
+    """Under `solver.loss_fn: CRF` the criterion travels on the model as `model.crf` (object.__setattr__: not a sub-module - its block is
+    neither in M2FNet's state_dict nor in the model's optimizer); checkpoints then carry it as 'crf_state_dict'."""
+    object.__setattr__(model, "crf", criterion if isinstance(criterion, LinearChainCRF) else None)
+
+
 def write_checkpoint(path, epoch, model, optimizer):
     """The reference's three entries - the LIVE weights, so a resume is exact - and, when the optimizer keeps a weight average
     (runtime.ema), FusedAdam.ema_state_dict() beside them."""
     state = dict(zip(CHECKPOINT_KEYS, (epoch, model.state_dict(), optimizer.state_dict())))
     if _has_average(optimizer):
         state[EMA_KEY] = optimizer.ema_state_dict()
+    if getattr(model, "crf", None) is not None:           # (solver.loss_fn: CRF - the block is not in the model's state_dict)
+        state[CRF_KEY] = model.crf.state_dict()
     torch.save(state, path)
 
 
@@ -601,6 +678,7 @@ def main(config=None):
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
     resolve_distill(config)
     focal_gamma_setting(config)
+    crf_settings(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     optimizer_groups(config, model_named_shapes(config.model))
     if want_dp not in (True, "auto") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -676,7 +754,8 @@ def main(config=None):
         object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
                                                                              n_head=config.model.AUDIO.n_head))
     attach_distiller(config, model, device)
-    criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config))
+    criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config), crf=crf_settings(config))
+    attach_crf(model, criterion)
     optimizer = build_optimizer(config, model)
     optimizer.max_grad_norm = clip_grad_norm(config, world)
     attach_watch(config, model, optimizer, rank, world)
@@ -684,7 +763,8 @@ def main(config=None):
         model.dp_step = dp.DataParallelStep(model, optimizer, n_buckets=int(_runtime(config, "grad_buckets", 4)),
                                             exchange=_runtime(config, "grad_exchange", "fp32"),
                                             overlap=bool(_runtime(config, "grad_overlap", False)),
-                                            algorithm=_runtime(config, "grad_algorithm", "all_reduce"))
+                                            algorithm=_runtime(config, "grad_algorithm", "all_reduce"),
+                                            crf=getattr(model, "crf", None))
     if config.wandb.enabled and rank == 0:
         start_wandb(config)
     lr_scheduler = build_scheduler(config.solver, optimizer)
@@ -730,7 +810,7 @@ class EarlyStopper:
         print(f"Early stopping: patience {self.patience} reached")
         if self.restore:                                 # the final checkpoint becomes the best one; the side file goes away
             best = torch.load(self.best_path)
-            torch.save({k: best[k] for k in CHECKPOINT_KEYS + (EMA_KEY,) if k in best}, self.save_path)
+            torch.save({k: best[k] for k in CHECKPOINT_KEYS + (EMA_KEY, CRF_KEY) if k in best}, self.save_path)
             os.remove(self.best_path)
             print(f"Best model at epoch {best['epoch']} restored")
         return True
@@ -787,7 +867,7 @@ def _step_mode(model, criterion):
     """(fused, use_graph): the whole loop body as one m2f_step launch when the model / criterion are the HIP-backed ones.
     The two switches are read from the `runtime:` block ONCE, in main(), and travel on the model (`model.step_mode`)."""
     fused, use_graph = getattr(model, "step_mode", (True, True))
-    return fused and isinstance(criterion, M2FCrossEntropyLoss) and hasattr(model, "train_step"), use_graph
+    return fused and isinstance(criterion, (M2FCrossEntropyLoss, LinearChainCRF)) and hasattr(model, "train_step"), use_graph
 
 
 def _grad_norm_log(optimizer):
@@ -829,32 +909,32 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                                                            audio_encoder=getattr(model, "audio_encoder", None))
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
-            loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                           class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                           **_focal_kw(criterion))
+            loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
+                           **_crit_kw(criterion, data_parallel=True))
         else:
             optimizer.zero_grad()
+            _crf_zero_grad(criterion)
             if fused and getattr(model, "fused_optimizer", False) and isinstance(optimizer, FusedAdam):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
-                loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                        class_weights=criterion.weight, use_graph=use_graph, optimizer=optimizer,
+                loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, optimizer=optimizer,
                                         **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                        **_focal_kw(criterion))
+                                        **_crit_kw(criterion))
+                _crf_step(criterion)
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
                                **_grad_norm_log(optimizer)})
                 continue
             if fused:
-                loss = model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                        class_weights=criterion.weight, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                                        **_speaker_kw(model, batch, device), **_focal_kw(criterion))
+                loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
+                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion))
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
                 loss = criterion(model(text, audio, padding_mask, **_speaker_kw(model, batch, device)).permute(0, 2, 1), emotion)
                 loss.backward()
             optimizer.step()
+            _crf_step(criterion)
         running += loss.item()
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
@@ -883,14 +963,12 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
             if dp_step is not None:
-                loss = dp_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                               class_weights=criterion.weight, use_graph=use_graph, sync=j == len(group) - 1,
-                               **_distill_kw(model, text, audio, padding_mask), **_focal_kw(criterion))
+                loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, sync=j == len(group) - 1,
+                               **_distill_kw(model, text, audio, padding_mask), **_crit_kw(criterion, data_parallel=True))
             else:
-                model.train_step(text, audio, padding_mask, emotion, label_smoothing=criterion.label_smoothing,
-                                 class_weights=criterion.weight, normalise=False, use_graph=use_graph,
+                model.train_step(text, audio, padding_mask, emotion, normalise=False, use_graph=use_graph,
                                  **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                 **_focal_kw(criterion))
+                                 **_crit_kw(criterion))
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
@@ -922,6 +1000,15 @@ def _rank_share(dl_val, rank, world):
     return (b for i, b in enumerate(dl_val) if i % world == rank)
 
 
+def decoded(crf, logits, padding_mask):
+    """What the scores' per-row argmax reads: the logits - or, under a CRF (a LinearChainCRF; anything else: the logits), the one-hot
+    rows of its Viterbi path over each dialogue's utterances, so that the argmax IS the path."""
+    if not isinstance(crf, LinearChainCRF):
+        return logits
+    path = crf.decode(logits, padding_mask.bool())
+    return torch.nn.functional.one_hot(path.clamp(min=0), logits.shape[-1]).to(logits.dtype)
+
+
 def validate(model, dl_val, criterion, device):
     """-> (mean batch loss, accuracy, weighted_f1); scores by the per-batch rule of ``metrics.BatchScores``.
     With several ranks the replicas are identical and the rule is a plain mean over the reference's batches
@@ -941,7 +1028,7 @@ def validate(model, dl_val, criterion, device):
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             logits = model(text, audio, padding_mask, **_speaker_kw(model, batch, device))
             loss_total += criterion(logits.permute(0, 2, 1), emotion).item()
-            scores.update(logits, emotion)
+            scores.update(decoded(criterion, logits, padding_mask), emotion)
     acc_sum, f1_sum = scores.sums()
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks([loss_total, acc_sum, f1_sum, float(scores.n_batches)], device=device)
     n = max(n, 1.0)
@@ -950,7 +1037,7 @@ def validate(model, dl_val, criterion, device):
 
 def _validate_on_device(model, dl_val, criterion, device, rank, world):
     from mer_amd.metrics import DeviceScores
-    if not isinstance(criterion, M2FCrossEntropyLoss):
+    if not isinstance(criterion, (M2FCrossEntropyLoss, LinearChainCRF)):
         raise ValueError("runtime.device_metrics: True scores with the M2FCrossEntropyLoss criterion's kernel; another criterion needs the host loop")
     scores = DeviceScores(model.m2f_config.cls_out, device)
     _, use_graph = _step_mode(model, criterion)
@@ -958,9 +1045,8 @@ def _validate_on_device(model, dl_val, criterion, device, rank, world):
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
-            model.eval_step(text, audio, padding_mask, emotion, scores, class_weights=criterion.weight,
-                            label_smoothing=criterion.label_smoothing, use_graph=use_graph, **_speaker_kw(model, batch, device),
-                            **_focal_kw(criterion))
+            model.eval_step(text, audio, padding_mask, emotion, scores, use_graph=use_graph, **_speaker_kw(model, batch, device),
+                            **_crit_kw(criterion))
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks(list(scores.totals()), device=device)      # (the one read of the pass)
     n = max(n, 1.0)
     return loss_total / n, acc_sum / n, f1_sum / n
