@@ -63,7 +63,9 @@ enum {
     M2F_BUF_SPEAKERS = 19,      /* uint8 [T]  input of a plan with speaker heads (m2f_plan_attention_speakers): the speaker id of every token row, in the plan's token order (padded: [B*L] as M2F_BUF_KEYPAD; packed: row cu[b] + i); stream plans: [S], chunk plans [S*T] - the new utterances' ids */
     M2F_BUF_STREAM_SPEAKERS = 20,   /* uint8 [S][C]  stream plans with speaker heads: the caller's buffer of cached speaker ids by logical cache row (m2f_plan_stream_speakers; NULL: none) */
     M2F_BUF_FOCAL = 21,         /* float [1]  train and eval plans, input of the focal criterion (m2f_plan_focal): gamma (read on the device at every step) */
-    M2F_BUF_COUNT = 22
+    M2F_BUF_PARTNER = 22,       /* int32 [T]  train plans, input of the R-Drop criterion (m2f_plan_rdrop): the twin of every token row, in the plan's token order (as M2F_BUF_CU_SEQLENS is an input), or -1 */
+    M2F_BUF_RDROP = 23,         /* float [1]  train plans, input of the R-Drop criterion: alpha (read on the device at every step) */
+    M2F_BUF_COUNT = 24
 };
 
 const char* m2f_last_error(void);
@@ -714,6 +716,24 @@ int m2f_plan_distill(m2f_plan* plan, int on);
  * bf16 gradients, the accumulate form and distillation. */
 int m2f_plan_focal(m2f_plan* plan, int on);
 
+/* R-Drop criterion (Liang et al. 2021): while m2f_plan_rdrop(plan, 1) is on, the criterion launch of m2f_loss / m2f_step / m2f_step_part /
+ * m2f_step_timed couples every token row r with its twin t(r) = M2F_BUF_PARTNER[r] - the same utterance a second time in the SAME plan,
+ * which the hashed dropout streams give an independent mask at every site - and adds the symmetric KL divergence between the two
+ * predictions (p = softmax(z_r), q = softmax(z_t(r)), y the shared label, numCE / dCE the plain criterion's numerator and gradient):
+ *   s_r       = 0.5 * (KL(p || q) + KL(q || p))                                        (the same bits on both rows of a pair)
+ *   num_r     = numCE_r + alpha * w_y * s_r                                            den_r = w_y (unchanged)
+ *   dlogits_r = dCE_r + alpha * w_y * (p * ((log p - log q) - KL(p || q)) + (p - q))
+ * and loss = sum num / sum den through the unchanged tail; the fourth float of the tail (loss_out[3]) receives sum w_y * s_r, the KL
+ * share of the numerator WITHOUT alpha, summed in the tail's own fixed order (added to by the accumulate form, summed over ranks by the
+ * all-reduce of the tail).  alpha = M2F_BUF_RDROP[0] >= 0 is read ON THE DEVICE by every step, and M2F_BUF_PARTNER is an input like
+ * M2F_BUF_CU_SEQLENS: the call writes nothing and waits for nothing, the caller writes both on its stream before the first step.  A twin
+ * index outside [0, T) means no twin: the plain term.  alpha = 0 gives the bits of the criterion without the switch; a row without a
+ * valid label writes zeros whatever its twin holds.  A change of the switch bumps the plan's generation: no captured step replays the
+ * other form; a change of alpha or of the map does not.  Train plans with a gradient buffer only (m2f_eval_step keeps the hard-label
+ * criterion); works with fused Adam, bf16 gradients and the accumulate form.  Refused while m2f_plan_distill, m2f_plan_focal or
+ * m2f_plan_crf is on, and each of them refuses while this is on. */
+int m2f_plan_rdrop(m2f_plan* plan, int on);
+
 /* Linear-chain CRF criterion (the kernel-level entries m2f_crf_* below define it): while m2f_plan_crf(plan, params, param_grad) is on,
  * the criterion launch of m2f_loss / m2f_step / m2f_step_part / m2f_step_timed is the CRF loss over the plan's own dialogues (padded and
  * bucket-padded plans: rows b*L + i; packed and long-dialogue plans: the plan's cu_seqlens) with the same loss_terms / loss tail
@@ -927,6 +947,12 @@ int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* te
 int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
                             float label_smoothing, const float* hyper_dev, const float* gamma_dev, int normalise, float* loss_terms,
                             float* dlogits, float* loss_out, m2f_stream_t stream);
+/* The R-Drop criterion of m2f_plan_rdrop on its own: m2f_cross_entropy with partner (device int32 [T]: the twin ROW of every row of
+ * logits, or -1) and alpha_dev (device float [1], alpha >= 0).  loss_terms: scratch of 3 * T floats here ([T, 2] numerator / denominator,
+ * then [T] w_y * s_r); loss_out[3] = sum w_y * s_r (the KL share of the numerator is alpha times it). */
+int m2f_cross_entropy_rdrop(int T, int C, const float* logits, const int32_t* partner, const int64_t* labels, const float* class_w,
+                            float label_smoothing, const float* alpha_dev, int normalise, float* loss_terms, float* dlogits,
+                            float* loss_out, m2f_stream_t stream);
 
 /* ---- linear-chain CRF over a dialogue's labels (multimodal-emotion-recognition_amd/crf.py, csrc/crf.hip) --------------------------
  * params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.  The block is NOT part of the flat parameter

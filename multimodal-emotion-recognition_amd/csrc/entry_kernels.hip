@@ -626,6 +626,21 @@ int m2f_crf_filter(int S, int C, int rows, const float* logits, const float* par
     return 0;
 }
 
+int m2f_cross_entropy_rdrop(int T, int C, const float* logits, const int32_t* partner, const int64_t* labels, const float* class_w,
+                            float label_smoothing, const float* alpha_dev, int normalise, float* loss_terms, float* dlogits,
+                            float* loss_out, m2f_stream_t stream) {
+    if (!logits || !partner || !labels || !alpha_dev || !loss_terms || !dlogits || !loss_out)
+        return fail("m2f_cross_entropy_rdrop: NULL logits / partner / labels / alpha_dev / loss_terms / dlogits / loss_out");
+    if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_rdrop: T >= 1 and 1 <= C <= 16 required");
+    CeRdropArgs a;
+    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
+    a.partner = partner; a.alpha = alpha_dev; a.loss_terms = loss_terms; a.kl_terms = loss_terms + (size_t)T * 2; a.dlogits = dlogits;
+    M2F_HIP(m2f_launch_ce_rdrop(a, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_rdrop_kl_reduce(a.kl_terms, T, loss_out, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
     return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
 }

@@ -581,6 +581,30 @@ struct CeFocalArgs {
     float* dlogits;                        // [T, C]
 };
 hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream);
+// R-Drop criterion (Liang et al. 2021): every token row r is coupled to its twin t(r) = partner[r] - the same utterance under another
+// dropout mask, a row of the SAME logits buffer.  p = softmax(z_r), q = softmax(z_t(r)), ce / g = CeArgs' numerator and gradient:
+//   s           = 0.5 * sum_c (p_c - q_c) * (logp_c - logq_c)      = 0.5 * (KL(p || q) + KL(q || p)), the same bits on both rows of a pair
+//   numerator   = ce + alpha * w_y * s                                                    denominator = w_y, as CeArgs
+//   dlogits_c   = g_c + alpha * w_y * (p_c * ((logp_c - logq_c) - KL(p || q)) + (p_c - q_c))
+// (the twin's row carries the mirror term, so the pair's two gradients are the gradient of w_y * (s_r + s_t(r)) = 2 w_y s.)  kl_terms[r] =
+// w_y * s, WITHOUT alpha: m2f_launch_rdrop_kl_reduce sums it in the finalize launch's order.  logp / logq come from the log-softmax,
+// never from log(p): a probability that underflows contributes 0 * finite = 0.  alpha is READ FROM THE DEVICE (alpha[0] >= 0): a captured
+// step replays while a warm-up changes it; alpha == 0 gives m2f_launch_ce's bits.  partner[r] outside [0, T): no twin, the plain term.
+// Rows with an invalid label write zeros whatever their twin row holds.
+struct CeRdropArgs {
+    const float* logits; int T, C;
+    const int64_t* labels;                 // [T], ignore_index = -1
+    const float* class_w;                  // [C] or null
+    float label_smoothing;
+    const int32_t* partner;                // [T]: the twin of every token row, or -1
+    const float* alpha;                    // device float [1]
+    float* loss_terms;                     // [T, 2] (numerator, denominator)
+    float* kl_terms;                       // [T]: w_y * s
+    float* dlogits;                        // [T, C]
+};
+hipError_t m2f_launch_ce_rdrop(const CeRdropArgs& a, hipStream_t stream);
+// loss_out[3] = (accumulate: +=) sum of kl_terms, summed in m2f_launch_loss_finalize's order (thread-strided, wave sum, (s0 + s1) + (s2 + s3))
+hipError_t m2f_launch_rdrop_kl_reduce(const float* kl_terms, int T, float* loss_out, hipStream_t stream, int accumulate = 0);
 // Linear-chain CRF over a dialogue's labels (crf.hip).  params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.
 // Dialogue b owns token rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (packed and long-dialogue plans) or, cu_seqlens null, b*L .. b*L+L-1
 // (padded and bucket-padded plans).  The CHAIN of a dialogue is its rows with a label in [0, C), in row order (a -1 in the middle links

@@ -251,6 +251,8 @@ struct m2f_plan {
     uint16_t* g16_buf = nullptr;
     m2f::AccForm acc;
     bool distill_on = false;             // m2f_plan_distill: do_loss launches the distillation criterion
+    bool rdrop_on = false;               // m2f_plan_rdrop: do_loss launches the R-Drop criterion (twins = M2F_BUF_PARTNER, alpha = M2F_BUF_RDROP[0])
+    float* rdrop_kl = nullptr;           // ... its per-row KL terms [T] (train plans), reduced into the tail's fourth float
     bool focal_on = false;               // m2f_plan_focal: do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
     // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
     // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace

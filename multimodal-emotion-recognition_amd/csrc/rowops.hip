@@ -578,6 +578,115 @@ __global__ __launch_bounds__(256) void m2f_ce_focal_kernel(const CeFocalArgs a) 
     a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
 }
 
+// R-Drop criterion (CeRdropArgs, ops.h): m2f_ce_kernel's numerator and gradient, statement for statement and in its order, plus alpha * w_y
+// times the symmetric KL divergence between the row's softmax and its twin's (the same utterance under another dropout mask, row
+// partner[t] of the SAME logits buffer).  One lane per token row, sixteen classes fully unrolled, everything in registers; a row reads
+// its twin's logits and writes only its own outputs.  alpha = 0 gives m2f_ce_kernel's bits: x + 0 * finite is exact.
+//   The twin load is range-checked: an index outside [0, T) means no twin, the lane then re-reads its own row and SELECTS the plain term.
+//   q is computed as the twin computes its own p (expf((u_c - max) - logf(sum))), so s = 0.5 * sum (p - q)(logp - logq) has
+//   the same bits on both rows of a pair, and twins with equal logits give s = 0 and a KL gradient of exactly 0.
+//   logp - logq comes from the two log-softmaxes, never from log(p): a probability that underflows contributes 0 * finite = 0.
+// An invalid row (label -1 or out of range) is a SELECT of zeros, whatever its twin row holds (NaN, inf).
+__global__ __launch_bounds__(256) void m2f_ce_rdrop_kernel(const CeRdropArgs a) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.T) return;
+    const int C = a.C;
+    const float alpha = a.alpha[0];
+    const int tw = a.partner[t];
+    const bool has = (tw >= 0) && (tw < a.T);
+    const int tr = has ? tw : t;
+    float z[16], w[16], u[16];
+    float m = -INFINITY, mu = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
+        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
+        u[c] = (c < C) ? a.logits[(size_t)tr * C + c] : -INFINITY;
+        m = fmaxf(m, z[c]);
+        mu = fmaxf(mu, u[c]);
+    }
+    // ---- as m2f_ce_kernel ----
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
+    const float lse = m + logf(se);
+    const int64_t y = a.labels[t];
+    const bool valid = (y >= 0) && (y < C);
+    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < C) {
+            const float lp = z[c] - lse;
+            W += w[c];
+            sm -= w[c] * lp;
+            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
+        }
+    }
+    const float eps = a.label_smoothing;
+    const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
+    // ---- the twin term ----
+    // logp_c = (z_c - m) - logf(se), NOT z_c - lse: lse = m + logf(se) is rounded at the size of m, and on saturated rows (|z| in the
+    // hundreds) that rounding, harmless to p - onehot above, would be multiplied here by log-ratios of the margin's size.  The twin's
+    // logq from its own max and sum in the same way: both lanes of a pair compute the same p, q and ratio bits.
+    float su = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) su += (c < C) ? expf(u[c] - mu) : 0.f;
+    const float lgs = logf(se), lgu = logf(su);
+    // e_c = (z_c - u_c) - (z_k - u_k), k the row's own first maximal class: logp_c - logq_c up to a constant.  The gradient needs
+    // (logp_c - logq_c) - KL(p || q) = e_c - sum_j p_j e_j; on a confident row (p_k = 1 - tiny) the direct difference of two numbers of
+    // the margin's size would lose the tiny part to rounding, while here the j = k term is exactly 0.
+    float best = -INFINITY, e0 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < C && z[c] > best) { best = z[c]; e0 = z[c] - u[c]; }
+    }
+    float p[16], q[16], e[16];
+    float ebar = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        const float lp = (c < C) ? ((z[c] - m) - lgs) : 0.f, lq = (c < C) ? ((u[c] - mu) - lgu) : 0.f;
+        p[c] = (c < C) ? expf(lp) : 0.f;
+        q[c] = (c < C) ? expf(lq) : 0.f;
+        e[c] = (c < C) ? ((z[c] - u[c]) - e0) : 0.f;
+        ebar += p[c] * e[c];
+        s2 += (p[c] - q[c]) * (lp - lq);
+    }
+    const bool live = valid && has;
+    const float ws = live ? wy * (0.5f * s2) : 0.f;
+    const float ak = alpha * wy;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < C) {
+            // ---- as m2f_ce_kernel ----
+            const float pc = expf(z[c] - lse);
+            float g = 0.f;
+            if (valid) g = (1.f - eps) * wy * (pc - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * pc - w[c]);
+            const float k = live ? (p[c] * (e[c] - ebar) + (p[c] - q[c])) : 0.f;
+            a.dlogits[(size_t)t * C + c] = valid ? (g + ak * k) : 0.f;
+        }
+    }
+    a.loss_terms[2 * t] = valid ? (num_ce + alpha * ws) : 0.f;
+    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
+    a.kl_terms[t] = ws;
+}
+
+// The KL share of the R-Drop numerator on its own: loss_out[3] = sum of kl_terms (w_y * s per row, without alpha), in exactly
+// m2f_loss_finalize_kernel's order.  ACC: added, as that kernel adds den and num.
+template <bool ACC>
+__global__ __launch_bounds__(256) void m2f_rdrop_kl_reduce_kernel(const float* __restrict__ kl_terms, int T, float* __restrict__ loss_out) {
+    __shared__ float sk[4];
+    float k = 0.f;
+    for (int t = threadIdx.x; t < T; t += 256) k += kl_terms[t];
+    k = m2f_wave_sum(k);
+    if ((threadIdx.x & 63) == 0) sk[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float kl = (sk[0] + sk[1]) + (sk[2] + sk[3]);
+        if constexpr (ACC) loss_out[3] = loss_out[3] + kl;
+        else loss_out[3] = kl;
+    }
+}
+
 // ACC (the accumulate form): den and num are added to loss_out[1], loss_out[2] (a group of micro-batches); loss_out[0] stays this batch's
 template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_loss_finalize_kernel(const float* __restrict__ terms, int T, int C,
@@ -1099,6 +1208,19 @@ hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream) {
     if (a.C < 1 || a.C > 16 || a.T < 1 || !a.gamma || (a.teacher && !a.hyper)) return hipErrorInvalidValue;
     if (a.teacher) hipLaunchKernelGGL(m2f_ce_focal_kernel<true>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(m2f_ce_focal_kernel<false>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_ce_rdrop(const CeRdropArgs& a, hipStream_t stream) {
+    if (a.C < 1 || a.C > 16 || a.T < 1 || !a.partner || !a.alpha || !a.kl_terms) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(m2f_ce_rdrop_kernel, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t m2f_launch_rdrop_kl_reduce(const float* kl_terms, int T, float* loss_out, hipStream_t stream, int accumulate) {
+    if (!kl_terms || !loss_out || T < 1) return hipErrorInvalidValue;
+    if (accumulate) hipLaunchKernelGGL(m2f_rdrop_kl_reduce_kernel<true>, dim3(1), dim3(256), 0, stream, kl_terms, T, loss_out);
+    else hipLaunchKernelGGL(m2f_rdrop_kl_reduce_kernel<false>, dim3(1), dim3(256), 0, stream, kl_terms, T, loss_out);
     return hipGetLastError();
 }
 

@@ -118,8 +118,11 @@ class Distiller:
     def train_step(self, text, audio, mask, emotion, speakers=None, **kw) -> torch.Tensor:
         """speakers ([B, L] ids): student and teacher each run under their OWN speaker-head setting, and the batch's ids go to
         whichever of the two has one; needed as soon as either has, refused (ValueError) when neither does.
-        focal_gamma= (in ``kw``) goes to the student's step: the focal factor scales its hard-label term, the teacher term stays."""
+        focal_gamma= (in ``kw``) goes to the student's step: the focal factor scales its hard-label term, the teacher term stays.
+        rdrop= is refused by name: the R-Drop criterion has no distillation form."""
         pair = check_distill((self.alpha, self.temperature), "Distiller")          # (before the teacher runs)
+        if kw.get("rdrop") is not None:
+            raise ValueError("Distiller.train_step: rdrop and distill do not combine (the R-Drop criterion has no distillation form)")
         if kw.get("focal_gamma") is not None:
             from .runtime import check_focal_gamma
             kw["focal_gamma"] = check_focal_gamma(kw["focal_gamma"], "focal_gamma", "Distiller.train_step")

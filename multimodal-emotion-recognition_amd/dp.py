@@ -479,10 +479,14 @@ class DataParallelStep:
             self.model.set_grad_bf16(False)
 
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
-                 use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None) -> torch.Tensor:
+                 use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None,
+                 rdrop=None) -> torch.Tensor:
         """teacher_logits, distill=(alpha, temperature): as ``M2FNet.train_step`` - the rank's step runs the distillation criterion
         (one denominator: the exchange, the global den and the micro-batch group hold as they are); both or neither.
         focal_gamma: as ``M2FNet.train_step`` - the rank's step runs the focal form of its criterion (the denominator is untouched).
+        rdrop (alpha): as ``M2FNet.train_step`` - the rank runs ITS shard twice in one plan (the twins are made after sharding: a pair
+        never crosses ranks) under the R-Drop criterion; the denominator is the labelled weight of both views, and the all-reduced tail
+        carries the global KL share (``model.rdrop_terms()``).  Refused beside teacher_logits / distill, focal_gamma or a CRF by name.
         sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
@@ -490,6 +494,7 @@ class DataParallelStep:
         from . import runtime
         from .distill import resolve_distill_args
         _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
+        alpha = runtime.check_rdrop_args("DataParallelStep", rdrop, teacher_logits, distill, focal_gamma, self.crf)
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
         gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DataParallelStep")
@@ -523,13 +528,18 @@ class DataParallelStep:
                 loss = self.reducer.global_loss()
             cur.wait_stream(eng.stream)
             return loss
+        if alpha is not None:                         # this rank's shard twice: view 0, then view 1
+            with torch.cuda.stream(eng.stream):
+                text, audio, mask, emotion = (None if x is None else torch.cat([x, x], 0) for x in (text, audio, mask, emotion))
+            self.model._rdrop_alpha = alpha
+            B = 2 * B
         plan = eng.plan(B, L, True, self.model.training and self.model.m2f_config.dropout > 0.0)
         with torch.cuda.stream(eng.stream):
             plan.set_inputs(text if self.model.text_enabled else None, audio if self.model.audio_enabled else None,
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf)
+            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf, alpha)
             if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

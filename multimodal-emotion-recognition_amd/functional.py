@@ -805,6 +805,31 @@ def crf_filter(logits: torch.Tensor, params: torch.Tensor, phi: torch.Tensor, co
     return phi
 
 
+def cross_entropy_rdrop(logits: torch.Tensor, partner: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None,
+                        label_smoothing: float = 0.1, alpha: float = 1.0, normalise: bool = True):
+    """The R-Drop criterion (m2f_cross_entropy_rdrop): logits [T, C] fp32, partner int32 [T] (the twin ROW of every row - the same
+    utterance under another dropout mask -, or -1), labels int64 [T] (-1 = ignore) -> (loss_out[4] = loss, den, num, kl; dlogits [T, C]) of
+    the cross entropy plus alpha * w_y * 0.5 * (KL(p || q) + KL(q || p)) on every labelled row with a twin, over the ONE denominator
+    (sum of w_y).  kl = sum of w_y * s_r WITHOUT alpha: loss = CE share + alpha * kl / den.  alpha: a finite number >= 0 (ValueError
+    otherwise); 0 gives `cross_entropy`'s bits.  The map must pair rows of one label (``runtime.rdrop_partner`` builds it)."""
+    alpha = runtime.check_rdrop_alpha(alpha, "alpha", "cross_entropy_rdrop")
+    runtime.require_gpu()
+    T, C = logits.shape
+    if logits.dtype != torch.float32:
+        raise ValueError(f"cross_entropy_rdrop: logits must be fp32 (got {logits.dtype})")
+    if partner.shape != (T,) or partner.dtype != torch.int32 or partner.device != logits.device:
+        raise ValueError(f"cross_entropy_rdrop: partner must be int32 [{T}] on {logits.device} (got {tuple(partner.shape)} {partner.dtype} "
+                         f"on {partner.device})")
+    terms = torch.empty(T, 3, dtype=torch.float32, device=logits.device)
+    dl = torch.empty(T, C, dtype=torch.float32, device=logits.device)
+    out = torch.zeros(4, dtype=torch.float32, device=logits.device)
+    a = torch.tensor([alpha], dtype=torch.float32).to(logits.device, non_blocking=True)
+    logits, labels, partner = logits.contiguous(), labels.contiguous(), partner.contiguous()
+    check(lib().m2f_cross_entropy_rdrop(T, C, ptr(logits), ptr(partner), ptr(labels), ptr(class_w), label_smoothing, ptr(a),
+                                        int(normalise), ptr(terms), ptr(dl), ptr(out), stream_ptr()), "m2f_cross_entropy_rdrop")
+    return out, dl
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
                       need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,

@@ -640,7 +640,8 @@ class M2FNet(nn.Module):
         self_attn``, ``text_encoders.{e}.layers.{l}.self_attn``, ``fusion_layers.{i}.multihead_attention``), each ``[B, L, L]`` -
         ``weights[b, i, j]`` = how much utterance i of dialogue b attends to utterance j, the heads averaged as torch's
         ``need_weights=True`` does (fp32 sum over the heads in order, times fp32(1 / H)) - or ``[B, H, L, L]`` with
-        ``average_heads=False``.  These are the weights that the reference's fusion module computes at every layer and throws away
+        ``average_heads=False``.  After ``train_step(rdrop=)``, which runs every dialogue twice, B is twice the batch: the maps of view 0,
+        then those of view 1.  These are the weights that the reference's fusion module computes at every layer and throws away
         (src/model.py:14).  sites: names to return (default: all).
 
         No second forward: every attention site saves its probabilities at every forward, and one eager gather launch turns them
@@ -680,7 +681,7 @@ class M2FNet(nn.Module):
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
                    distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
-                   focal_gamma: Optional[float] = None, crf=None) -> torch.Tensor:
+                   focal_gamma: Optional[float] = None, crf=None, rdrop: Optional[float] = None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -704,9 +705,21 @@ class M2FNet(nn.Module):
         ``crf.params.grad`` is a view of a gradient buffer this step overwrites, and any torch optimizer over ``crf.parameters()``
         trains it beside ``FusedAdam`` (the values are read on the device: the captured step replays while they change).  Refused
         (ValueError naming the pair) with class_weights, teacher_logits / distill, focal_gamma, label_smoothing != 0.0, and - trainable
-        only - under gradient accumulation; a frozen block (``crf.params.requires_grad_(False)``) works under every training mode."""
+        only - under gradient accumulation; a frozen block (``crf.params.requires_grad_(False)``) works under every training mode.
+        rdrop (alpha, a finite number >= 0): the R-Drop criterion (Liang et al. 2021).  The B dialogues run TWICE in one ordinary plan of
+        2B dialogues - view 0 and behind it view 1, the same inputs, mask, labels and speaker ids (copied device to device; buckets,
+        packed plans and long dialogues as ever) -, the hashed dropout streams give the two views independent masks at every site, and
+        one kernel in the criterion's place adds ``alpha * w_y * 0.5 * (KL(p || q) + KL(q || p))`` between each labelled utterance's two
+        predictions to the cross entropy of both views, over the one denominator (the labelled weight of both views) and the same
+        ``loss_terms()`` tail: ``0.5 * (CE(view 0) + CE(view 1)) + alpha * 0.5 * (kl_div(v0, v1) + kl_div(v1, v0))``, batchmean over the
+        labelled utterances.  ``rdrop_terms()`` gives the two shares.  alpha lives on the device (uploaded only when it changed): a
+        warm-up replays the captured step.  With dropout 0 or in eval mode the call is allowed: the twins then agree, the term and its
+        gradient are exactly zero.  None (default): today's launches, bit for bit; R-Drop and plain calls mix freely on one model.
+        Refused (ValueError naming the pair, before any launch) beside teacher_logits / distill, focal_gamma or crf.  After such a
+        step ``last_attention()`` returns the 2B dialogues' maps, view 0 first."""
         from .crf import check_step_args
         from .distill import resolve_distill_args
+        alpha = runtime.check_rdrop_args("M2FNet.train_step", rdrop, teacher_logits, distill, focal_gamma, crf)
         check_step_args("M2FNet.train_step", crf, self.m2f_config.cls_out, class_weights, teacher_logits, distill, focal_gamma,
                         label_smoothing, accumulating=self._engine is not None and self._engine.accumulate)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
@@ -717,6 +730,9 @@ class M2FNet(nn.Module):
         if optimizer is not None and eng.accumulate:
             raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
                                "gradient accumulation (set_grad_accumulation(True)); call optimizer.step() after the group's micro-batches")
+        if alpha is not None:                            # view 0, then view 1: the ordinary plan of 2B dialogues
+            text, audio, mask, emotion, ids = (None if x is None else torch.cat([x, x], 0) for x in (text, audio, mask, emotion, ids))
+            self._rdrop_alpha = alpha
         B, L = mask.shape
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
@@ -725,7 +741,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist, gamma, crf)
+            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -755,11 +771,20 @@ class M2FNet(nn.Module):
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
-    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None) -> None:
+    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None) -> None:
         """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
         temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
         plan maps the teacher rows as it mapped the batch).  `crf` (a LinearChainCRF; the callers refused every other criterion argument
-        beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains."""
+        beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains.
+        `rdrop` (alpha; likewise alone): the R-Drop criterion over the doubled batch `set_inputs` has just placed."""
+        if rdrop is not None:
+            plan.set_crf(None)
+            plan.set_focal(None)
+            plan.distill(False)
+            plan.set_rdrop(rdrop)
+            return
+        if plan.train:
+            plan.set_rdrop(None)
         if crf is not None:
             plan.set_focal(None)
             plan.distill(False)
@@ -927,6 +952,19 @@ class M2FNet(nn.Module):
         eng.ensure_grad()
         n = eng.flat.numel()
         return eng.flat_grad_ext[n: n + 3]
+
+    def rdrop_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(ce, kl)`` of the last ``train_step(rdrop=alpha)`` as device scalars: the cross-entropy share of its loss (both views,
+        over the one denominator) and the symmetric KL divergence per unit of labelled weight WITHOUT alpha - ``ce + alpha * kl`` is the
+        loss.  Read from the criterion tail (den, num and, in its fourth float, the sum of ``w_y * s``, reduced in a fixed order): with
+        accumulation on they cover the group's micro-batches, and behind a data-parallel step's all-reduce of the tail they are the
+        global values.  alpha is the last step's."""
+        eng = self.engine()
+        eng.ensure_grad()
+        n = eng.flat.numel()
+        t = eng.flat_grad_ext[n: n + 4]
+        kl = t[3] / t[1]
+        return t[2] / t[1] - getattr(self, "_rdrop_alpha", 0.0) * kl, kl
 
     def invalidate_shadows(self) -> None:
         """Call after writing parameters in a way torch's version counters do not see (``p.data`` edits, writes through

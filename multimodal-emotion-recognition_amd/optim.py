@@ -3,6 +3,8 @@
 * ``M2FCrossEntropyLoss``  = ``torch.nn.CrossEntropyLoss(weight, ignore_index=-1, label_smoothing=0.1)`` as the
   reference builds it (src/train.py:41-52), computed by the fused CE kernel (value + gradient in one pass).
 * ``M2FFocalLoss``         = the same with every labelled row's term scaled by ``(1 - p_y)^gamma`` (focal loss; its own kernel).
+* ``M2FRDropLoss``         = the same over a batch given twice, plus the symmetric KL divergence between each utterance's two predictions
+  (R-Drop; its own kernel).
 * ``FusedAdam``            = ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` (src/train.py:56): coupled
   L2, bias-corrected; ONE kernel over the flat parameter / gradient / moment buffers instead of ~130 per-tensor
   updates.  ``state_dict()`` keeps torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` /
@@ -153,6 +155,63 @@ class M2FFocalLoss(M2FCrossEntropyLoss):
             logits = input
         w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
         return _FocalFunction.apply(logits.contiguous().float(), target.reshape(-1).contiguous(), w, self.label_smoothing, gamma)
+
+
+class _RDropFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits2d, partner, target1d, weight, label_smoothing, alpha):
+        out, dl = F.cross_entropy_rdrop(logits2d, partner, target1d, weight, label_smoothing, alpha, True)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        (dl,) = ctx.saved_tensors
+        return dl * grad_out, None, None, None, None, None
+
+
+class M2FRDropLoss(M2FCrossEntropyLoss):
+    """R-Drop (Liang et al. 2021) over ``M2FCrossEntropyLoss``: the input holds every dialogue TWICE - logits ``[2B, L, C]`` (or the
+    reference's ``[2B, C, L]``), view 1 behind view 0, two forwards of one batch under independent dropout masks; the target is the
+    doubled ``[2B, L]`` labels.  The loss is the cross entropy over all ``2B``
+    dialogues' labelled utterances plus ``alpha * w_y * 0.5 * (KL(p || q) + KL(q || p))`` between each utterance's two predictions,
+    over the one denominator - without class weights ``0.5 * (CE(view 0) + CE(view 1)) + alpha * 0.5 * (kl_div(v0, v1, 'batchmean') +
+    kl_div(v1, v0, 'batchmean'))``.  One kernel (``functional.cross_entropy_rdrop``; the criterion ``M2FNet.train_step(rdrop=)`` runs
+    inside the step) on the autograd surface of its base class.  ``alpha`` (a finite number >= 0; 0 = the base class's bits) is a plain
+    attribute, read at every call: a warm-up may change it.  ``last_terms`` holds ``(loss, den, num, kl)`` of the last call on the device
+    (kl = sum of w_y * s without alpha).  ``channels_last`` (None: told apart by the target's L; where L == C the reference's layout)
+    names the layout outright."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -1, label_smoothing: float = 0.1, alpha: float = 1.0,
+                 channels_last: Optional[bool] = None):
+        super().__init__(weight, ignore_index, label_smoothing)
+        self.alpha = runtime.check_rdrop_alpha(alpha, "alpha", "M2FRDropLoss")
+        self.channels_last = channels_last    # True: [2B, L, C]; False: [2B, C, L]; None: told apart by the target's L
+        self.last_terms = None
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        alpha = runtime.check_rdrop_alpha(self.alpha, "alpha", "M2FRDropLoss")
+        if input.dim() != 3:
+            raise ValueError(f"M2FRDropLoss: logits [2B, L, C] or [2B, C, L] expected, got {tuple(input.shape)}")
+        n = input.shape[0]
+        if n % 2:
+            raise ValueError(f"M2FRDropLoss: the input holds every dialogue twice (view 0, then view 1), got {n} dialogues")
+        if target.dim() != 2 or target.shape[0] != n:
+            raise ValueError(f"M2FRDropLoss: target [{n}, L] expected (the labels of both views), got {tuple(target.shape)}")
+        Lt = target.shape[1]
+        cl = self.channels_last
+        if cl is None:                                              # (L == C: the reference's layout)
+            cl = input.shape[1] == Lt and input.shape[2] != Lt
+        if input.shape[1 if cl else 2] != Lt:
+            raise ValueError(f"M2FRDropLoss: logits {tuple(input.shape)} do not match target {tuple(target.shape)}")
+        logits = input if cl else input.permute(0, 2, 1)            # [2B, L, C] / the reference's [2B, C, L]
+        C = logits.shape[2]
+        partner = runtime.rdrop_partner(n // 2, Lt, n * Lt, L=Lt, device=logits.device)
+        w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
+        loss, self.last_terms = _RDropFunction.apply(logits.reshape(-1, C).contiguous().float(), partner, target.reshape(-1).contiguous(), w,
+                                                     self.label_smoothing, alpha)
+        return loss
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -27,7 +27,7 @@ F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
- BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL) = range(22)
+ BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL, BUF_PARTNER, BUF_RDROP) = range(24)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -187,6 +187,7 @@ SIGNATURES = {
     "m2f_plan_accumulate_grads": (c_int, [c_void_p, c_int]),
     "m2f_plan_distill": (c_int, [c_void_p, c_int]),
     "m2f_plan_focal": (c_int, [c_void_p, c_int]),
+    "m2f_plan_rdrop": (c_int, [c_void_p, c_int]),
     "m2f_plan_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_stream_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
@@ -245,6 +246,8 @@ SIGNATURES = {
     "m2f_crf_viterbi": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "m2f_crf_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_cross_entropy_rdrop": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -379,6 +382,55 @@ def check_focal_gamma(gamma, name: str = "focal_gamma", who: str = "train_step")
     return float(gamma)
 
 
+def check_rdrop_alpha(alpha, name: str = "rdrop", who: str = "train_step") -> float:
+    """alpha of the R-Drop criterion as a float; ValueError naming the argument unless it is a finite number >= 0.  A host function:
+    no GPU needed."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, got {alpha!r}")
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, got {alpha!r}")
+    return float(alpha)
+
+
+def check_rdrop_args(who: str, rdrop, teacher_logits=None, distill=None, focal_gamma=None, crf=None) -> Optional[float]:
+    """`rdrop=` of a step as a float (None: off).  The R-Drop criterion has no distillation, focal or CRF form: given beside one of them
+    it is refused with a ValueError that names the pair, before any launch.  A host function: no GPU needed."""
+    if rdrop is None:
+        return None
+    alpha = check_rdrop_alpha(rdrop, "rdrop", who)
+    for name, other in (("teacher_logits", teacher_logits), ("distill", distill), ("focal_gamma", focal_gamma), ("crf", crf)):
+        if other is not None:
+            raise ValueError(f"{who}: rdrop and {name} do not combine (the R-Drop criterion has no "
+                             f"{'distillation' if name in ('teacher_logits', 'distill') else 'focal' if name == 'focal_gamma' else 'CRF'} form)")
+    return alpha
+
+
+def rdrop_partner(pairs: int, l: int, T: int, L: Optional[int] = None, dst: Optional[torch.Tensor] = None,
+                  valid: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The twin map of the R-Drop criterion (M2F_BUF_PARTNER): int32 [T], for every token row of a plan the row of the same utterance
+    in the other view, or -1.  The plan runs `2 * pairs` dialogues of `l` slots - view 0 and behind it view 1 -, so the twin of slot
+    (b, i) is slot ((b + pairs) mod (2 * pairs), i).
+    Padded and bucketed plans (`L`: the plan's row length, L >= l): slot (b, i) is token row b * L + i; the filler rows of a bucketed
+    plan (dialogues past 2 * pairs, slots past l) get -1.
+    Packed plans (`dst`, `valid` [2 * pairs, l]: the row map `Plan.set_inputs` placed the batch with, and which slots are real): the twin
+    of row dst[b, i] is row dst[(b + pairs) mod (2 * pairs), i]; pad slots, filler dialogues' rows and the spare row get -1.
+    Pure torch on `device` (or dst's), no host synchronisation: it runs on the CPU as it runs in the step."""
+    n = 2 * int(pairs)
+    if dst is not None:
+        if dst.shape != (n, l) or valid is None or valid.shape != dst.shape:
+            raise ValueError(f"rdrop_partner: dst and valid must be [{n}, {l}] (got {tuple(dst.shape)})")
+        # (valid is the same in both views, so a real slot's twin is real; every pad slot writes -1 into the row it was sent to)
+        twin = torch.where(valid, torch.roll(dst, int(pairs), 0), torch.full_like(dst, -1)).to(torch.int32)
+        out = torch.full((T,), -1, dtype=torch.int32, device=dst.device)
+        return out.index_copy_(0, dst.reshape(-1), twin.reshape(-1))
+    if L is None or L < l or n * L > T:
+        raise ValueError(f"rdrop_partner: a padded plan needs its row length L >= {l} and T >= {n} * L (got L = {L}, T = {T})")
+    rows = torch.arange(n, device=device)[:, None] * L + torch.arange(l, device=device)[None, :]
+    out = torch.full((T,), -1, dtype=torch.int32, device=device)
+    out[rows.reshape(-1)] = torch.roll(rows, int(pairs), 0).reshape(-1).to(torch.int32)
+    return out
+
+
 SPK_NONE, SPK_SAME, SPK_OTHER = 0, 1, 2
 
 
@@ -505,6 +557,12 @@ class Plan:
         self.focal_gamma = self._view(BUF_FOCAL, (1,), torch.float32)
         self._focal = False
         self.gamma_host = None                # host mirror of focal_gamma, as hyper_host
+        # inputs of the R-Drop criterion (train plans; `rdrop`): the twin of every token row and the alpha the kernel reads on the device
+        self.partner_in = self._view(BUF_PARTNER, (self.T,), torch.int32) if train else None
+        self.rdrop_alpha = self._view(BUF_RDROP, (1,), torch.float32) if train else None
+        self._rdrop = False
+        self.alpha_host = None                # host mirror of rdrop_alpha, as hyper_host
+        self._partner_key = None              # what the padded twin map in partner_in was built for: (pairs, l); packed plans: never kept
         self._fam0_out = (self._view(BUF_FAM0_OUT, (self.T, pad8(cfg.d_fam)) if self.packed else (B, L, pad8(cfg.d_fam)),
                                      torch.float32)[..., : cfg.d_fam] if cfg.fam_enabled else None)
         # shape of the batch last handed to set_inputs: a plan may be larger than the batch it runs (shape buckets), the
@@ -757,6 +815,38 @@ class Plan:
         self.focal(gamma is not None)
         if gamma is not None:
             self.set_focal_gamma(gamma)
+
+    def rdrop(self, on: bool) -> None:
+        """m2f_plan_rdrop: the NEXT losses / steps run the R-Drop criterion on `partner_in` and `rdrop_alpha` (on) / the criterion
+        without it (off).  A change drops the captured steps; a change of alpha or of the map does not.  Neither writes nor waits.
+        The distillation, focal and CRF switches must be off (the C entry refuses by name)."""
+        on = bool(on)
+        if on == self._rdrop:
+            return
+        check(lib().m2f_plan_rdrop(self._h(), int(on)), "m2f_plan_rdrop")
+        self._rdrop = on
+
+    def set_rdrop(self, alpha: Optional[float]) -> None:
+        """The criterion of the plan's next step: R-Drop with this alpha (a number, checked by the caller), or (None) not.  AFTER
+        `set_inputs` of the doubled batch (view 0, then view 1): the twin map is written from the row map that placed it - a packed
+        plan's from `_dst`, on the device; a padded or bucketed plan's depends on the batch's shape alone and is written only when that
+        changed.  alpha is uploaded only when it differs from the host mirror of the last upload."""
+        self.rdrop(alpha is not None)
+        if alpha is None:
+            return
+        if self.in_B % 2:
+            raise HipError(f"the R-Drop criterion needs the batch twice (view 0, then view 1), got {self.in_B} dialogues")
+        pairs = self.in_B // 2
+        if self.packed:
+            self.partner_in.copy_(rdrop_partner(pairs, self.in_L, self.T, dst=self._dst, valid=self._valid), non_blocking=True)
+            self._partner_key = None
+        elif self._partner_key != (pairs, self.in_L):
+            self.partner_in.copy_(rdrop_partner(pairs, self.in_L, self.T, L=self.L, device=self.partner_in.device), non_blocking=True)
+            self._partner_key = (pairs, self.in_L)
+        alpha = float(alpha)
+        if alpha != self.alpha_host:
+            self.rdrop_alpha.copy_(torch.tensor([alpha], dtype=torch.float32), non_blocking=True)
+            self.alpha_host = alpha
 
     def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
         """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's

@@ -200,6 +200,72 @@ def attach_distiller(config, model, device):
     return distiller
 
 
+RDROP_KEYS = ("enabled", "alpha", "warmup_steps")
+
+
+def rdrop_settings(cfg):
+    """`runtime.rdrop` = {enabled: False, alpha: 1.0, warmup_steps: 0}: train() runs the R-Drop criterion inside the step
+    (M2FNet.train_step(rdrop=)) - every batch twice in one plan under independent dropout masks, alpha times the symmetric KL divergence
+    between the two predictions added to the cross entropy of both.  -> None when the block is absent or disabled, else {alpha,
+    warmup_steps}.  Checked on the host before the GPU is touched: needs runtime.fused_step: True and solver.loss_fn: CE (the criterion
+    has no focal or CRF form) and no runtime.distill."""
+    from mer_amd.runtime import check_rdrop_alpha
+    block = _runtime(cfg, "rdrop", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.rdrop must be a mapping {{{', '.join(RDROP_KEYS)}}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - set(RDROP_KEYS))
+    if unknown:
+        raise ValueError(f"runtime.rdrop: unknown key(s) {unknown} ({', '.join(RDROP_KEYS)})")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.rdrop.enabled must be true or false (got {enabled!r})")
+    alpha = check_rdrop_alpha(block.get("alpha", 1.0), "alpha", "runtime.rdrop")
+    warm = block.get("warmup_steps", 0)
+    if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
+        raise ValueError(f"runtime.rdrop.warmup_steps must be an integer >= 0 (got {warm!r})")
+    if not enabled:
+        return None
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.rdrop.enabled needs runtime.fused_step: True (the R-Drop criterion lives in the train step)")
+    solver = cfg.get("solver", None) if isinstance(cfg, dict) else getattr(cfg, "solver", None)
+    loss_fn = None if solver is None else (solver.get("loss_fn", "CE") if hasattr(solver, "get") else getattr(solver, "loss_fn", "CE"))
+    if loss_fn not in (None, "CE"):
+        raise ValueError(f"runtime.rdrop.enabled needs solver.loss_fn: CE (got {loss_fn!r}: the R-Drop criterion has no focal or CRF form)")
+    if resolve_distill(cfg) is not None:
+        raise ValueError("runtime.rdrop.enabled does not combine with runtime.distill.enabled (the R-Drop criterion has no distillation form)")
+    return {"alpha": alpha, "warmup_steps": warm}
+
+
+def _rdrop_kw(model, global_step: int):
+    """{rdrop: alpha} of optimizer step `global_step` for train_step / DataParallelStep when main() hung the runtime.rdrop settings on the
+    model (`model.rdrop`), else nothing - the calls of a run without it are today's.  warmup_steps = n: alpha * (step + 1) / n until n."""
+    r = getattr(model, "rdrop", None)
+    if r is None:
+        return {}
+    n = r["warmup_steps"]
+    return {"rdrop": r["alpha"] * min(1.0, (global_step + 1) / n) if n > 0 else r["alpha"]}
+
+
+class _RDropLog:
+    """Running means of the two shares of the R-Drop loss for wandb: {"Train/CE", "Train/RDrop_KL"} beside Train/Running_loss (CE + alpha
+    * RDrop_KL at a constant alpha).  Reads `model.rdrop_terms()` only when something is logged: two more scalars on a path that has
+    just waited for loss.item()."""
+
+    def __init__(self, model, on: bool):
+        self.model, self.on = model, on and getattr(model, "rdrop", None) is not None
+        self.ce = self.kl = 0.0
+
+    def __call__(self, step: int):
+        if not self.on:
+            return {}
+        ce, kl = self.model.rdrop_terms()
+        self.ce += ce.item()
+        self.kl += kl.item()
+        return {"Train/CE": self.ce / (step + 1), "Train/RDrop_KL": self.kl / (step + 1)}
+
+
 def _distill_kw(model, text, audio, padding_mask):
     """{teacher_logits, distill} of this batch for train_step / DataParallelStep when the model carries a Distiller, else nothing."""
     d = getattr(model, "distiller", None)
@@ -677,6 +743,7 @@ def main(config=None):
     position_bias_settings(config)
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
     resolve_distill(config)
+    rdrop_settings(config)
     focal_gamma_setting(config)
     crf_settings(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
@@ -754,6 +821,7 @@ def main(config=None):
         object.__setattr__(model, "audio_encoder", build_audio_encoder(ae_cfg, config.model.AUDIO.embedding_size, device,
                                                                              n_head=config.model.AUDIO.n_head))
     attach_distiller(config, model, device)
+    object.__setattr__(model, "rdrop", rdrop_settings(config))       # (None: off; train() passes rdrop= on in every branch)
     criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config), crf=crf_settings(config))
     attach_crf(model, criterion)
     optimizer = build_optimizer(config, model)
@@ -903,14 +971,18 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     if k > 1:
         return _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log, device, k, fused, use_graph, dp_step)
     running = 0.0
+    rdrop_log = _RDropLog(model, bool(wandb_log))
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
         text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
+        rdrop = _rdrop_kw(model, epoch * len(dl_train) + step)
+        if rdrop and not fused:
+            raise ValueError("runtime.rdrop needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                           **_crit_kw(criterion, data_parallel=True))
+                           **_crit_kw(criterion, data_parallel=True), **rdrop)
         else:
             optimizer.zero_grad()
             _crf_zero_grad(criterion)
@@ -918,16 +990,16 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, optimizer=optimizer,
                                         **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                        **_crit_kw(criterion))
+                                        **_crit_kw(criterion), **rdrop)
                 _crf_step(criterion)
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                               **_grad_norm_log(optimizer)})
+                               **_grad_norm_log(optimizer), **rdrop_log(step)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion))
+                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop)
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
@@ -939,7 +1011,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                       **_grad_norm_log(optimizer), **watched})
+                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step)})
     return running / len(dl_train)
 
 
@@ -955,8 +1027,10 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
         model.set_grad_accumulation(True)
     n_groups = (len(dl_train) + k - 1) // k
     running = 0.0
+    rdrop_log = _RDropLog(model, bool(wandb_log))
     progress = tqdm(enumerate(group_batches(dl_train, k)), total=n_groups, desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, group in progress:
+        rdrop = _rdrop_kw(model, epoch * n_groups + step)     # (one alpha per optimizer step: the group's shares add up)
         if dp_step is None:
             optimizer.zero_grad()                        # (every .grad None: the first micro-batch overwrites, den / num too)
         for j, batch in enumerate(group):
@@ -964,11 +1038,11 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
                                                                audio_encoder=getattr(model, "audio_encoder", None))
             if dp_step is not None:
                 loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, sync=j == len(group) - 1,
-                               **_distill_kw(model, text, audio, padding_mask), **_crit_kw(criterion, data_parallel=True))
+                               **_distill_kw(model, text, audio, padding_mask), **_crit_kw(criterion, data_parallel=True), **rdrop)
             else:
                 model.train_step(text, audio, padding_mask, emotion, normalise=False, use_graph=use_graph,
                                  **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                 **_crit_kw(criterion))
+                                 **_crit_kw(criterion), **rdrop)
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
@@ -978,7 +1052,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step,
-                       **_grad_norm_log(optimizer), **watched})
+                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step)})
     if dp_step is None:
         optimizer.grad_scale = None
     return running / max(n_groups, 1)
