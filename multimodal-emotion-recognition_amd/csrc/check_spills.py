@@ -41,8 +41,8 @@ metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
 # --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
 # registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
 # rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
-# and for the distillation, focal and R-Drop criterion kernels of the same file (m2f_ce_distill_kernel, m2f_ce_focal_kernel,
-# m2f_ce_rdrop_kernel; their own lists below)
+# and for the criterion kernels of the same file (m2f_ce_kernel, m2f_ce_distill_kernel, m2f_ce_focal_kernel, m2f_ce_rdrop_kernel: one
+# row definition, criterion_row.h; counted by name below)
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
 # --crf <remarks>: the linear-chain CRF kernels (crf.hip) - a lane's transition column / row, its gradient column and the sixteen terms of
 # a step stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
@@ -71,19 +71,16 @@ if adam:
     # shadow-writing: 4 forms each; the exchange
     if len(kernels) < 18:
         sys.exit(f"check_spills: expected the eighteen optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
-    # the other kernel of rowops.hip under this gate: the distillation criterion (a row's 4 x 16 values stay in registers)
-    criterion = [r for r in rows if "m2f_ce_distill_kernel" in r["name"]]
-    if len(criterion) != 1:
-        sys.exit(f"check_spills: expected m2f_ce_distill_kernel in {path}, found {len(criterion)} - did the remark format change?")
-    # ... and the focal criterion, with and without a teacher (m2f_ce_focal_kernel<false / true>: a row's probabilities stay in registers too)
-    focal = [r for r in rows if "m2f_ce_focal_kernel" in r["name"]]
-    if len(focal) != 2:
-        sys.exit(f"check_spills: expected the two m2f_ce_focal_kernel instantiations in {path}, found {len(focal)} - did the remark format change?")
-    # ... and the R-Drop criterion (m2f_ce_rdrop_kernel: a row's and its twin's logits, probabilities and log-ratios stay in registers)
-    rdrop = [r for r in rows if "m2f_ce_rdrop_kernel" in r["name"]]
-    if len(rdrop) != 1:
-        sys.exit(f"check_spills: expected m2f_ce_rdrop_kernel in {path}, found {len(rdrop)} - did the remark format change?")
-    kernels = kernels + criterion + focal + rdrop
+    # the other kernels of rowops.hip under this gate: the four criterion kernels, thin bodies over criterion_row.h's helpers (a row's
+    # logits, weights, probabilities and - with a teacher or a twin - the second row's stay in registers): the plain one, the
+    # distillation one, the focal one with and without a teacher, the R-Drop one
+    criterion = []
+    for tag, count in (("m2f_ce_kernel", 1), ("m2f_ce_distill_kernel", 1), ("m2f_ce_focal_kernel", 2), ("m2f_ce_rdrop_kernel", 1)):
+        found = [r for r in rows if tag in r["name"]]
+        if len(found) != count:
+            sys.exit(f"check_spills: expected {count} of {tag} in {path}, found {len(found)} - did the remark format change?")
+        criterion += found
+    kernels = kernels + criterion
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

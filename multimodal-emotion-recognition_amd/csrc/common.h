@@ -84,8 +84,8 @@ __device__ __forceinline__ u32x4 m2f_rng_words(const uint32_t* rng) {
 // wait for loads issued AFTER them: the vector memory counter retires loads in order), so that it costs no wait itself.
 __device__ __forceinline__ void m2f_rng_words_arrived(u32x4& w) { asm volatile("" : "+v"(w)); }
 
-// Focal factor (1 - p_y)^gamma of a criterion row (rowops.hip m2f_ce_focal_kernel, metrics.hip m2f_eval_rows_focal_kernel: ONE function, so
-// the eval loss has the train criterion's bits).  omp is the SUM of the other classes' probabilities, never 1 - p_y.  gamma == 0 SELECTS 1;
+// Focal factor (1 - p_y)^gamma of a criterion row (criterion_row.h's focal part, behind rowops.hip m2f_ce_focal_kernel and metrics.hip
+// m2f_eval_rows_kernel<true>: ONE function, so the eval loss has the train criterion's bits).  omp is the SUM of the other classes' probabilities, never 1 - p_y.  gamma == 0 SELECTS 1;
 // omp == 0 (the other classes' expf underflowed) selects 0 for gamma > 0: powf never sees a zero base, nothing computes 0 * anything.
 __device__ __forceinline__ float m2f_focal_factor(float omp, float gamma) {
     return gamma > 0.f ? (omp > 0.f ? powf(omp, gamma) : 0.f) : 1.f;
@@ -100,6 +100,29 @@ __device__ __forceinline__ float m2f_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The ONE fixed-order sum of per-row terms by a workgroup of 256 (the criterion's finalize, the R-Drop KL reduce, the eval finalize: the
+// eval loss has the train loss's bits because all three call this).  s[j] = sum over t of terms[N * t + j]: thread-strided over t,
+// wave sum, the four waves' partials through LDS, (s0 + s1) + (s2 + s3); every thread gets the sums.  Holds one __syncthreads():
+// all 256 threads call it, once per kernel.
+template <int N>
+__device__ __forceinline__ void m2f_block_sum_terms(const float* __restrict__ terms, int T, float (&s)[N]) {
+    __shared__ float part[N][4];
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = 0.f;
+    for (int t = threadIdx.x; t < T; t += 256) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) s[j] += terms[N * t + j];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        s[j] = m2f_wave_sum(s[j]);
+        if ((threadIdx.x & 63) == 0) part[j][threadIdx.x >> 6] = s[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = (part[j][0] + part[j][1]) + (part[j][2] + part[j][3]);
 }
 
 static inline int m2f_cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -536,14 +536,26 @@ int m2f_dropout_rows(float* x, float* x2, int T, int d, int ld, uint32_t site, u
     return 0;
 }
 
-int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
-                      int normalise, float* loss_terms, float* dlogits, float* loss_out, m2f_stream_t stream) {
+// The four m2f_cross_entropy* entries: their own checks and messages, then ONE filler (the common part of CeArgs) and ONE launch
+// sequence (criterion, finalize, and the KL reduce where the criterion wrote KL terms).
+static CeArgs ce_args(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
+                      float* loss_terms, float* dlogits) {
     CeArgs a;
     a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
     a.loss_terms = loss_terms; a.dlogits = dlogits;
+    return a;
+}
+
+static int ce_run(const CeArgs& a, int normalise, float* loss_out, m2f_stream_t stream) {
     M2F_HIP(m2f_launch_ce(a, static_cast<hipStream_t>(stream)));
-    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    M2F_HIP(m2f_launch_loss_finalize(a.loss_terms, a.T, a.C, a.dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
+    if (a.kl_terms) M2F_HIP(m2f_launch_rdrop_kl_reduce(a.kl_terms, a.T, loss_out, static_cast<hipStream_t>(stream)));
     return 0;
+}
+
+int m2f_cross_entropy(int T, int C, const float* logits, const int64_t* labels, const float* class_w, float label_smoothing,
+                      int normalise, float* loss_terms, float* dlogits, float* loss_out, m2f_stream_t stream) {
+    return ce_run(ce_args(T, C, logits, labels, class_w, label_smoothing, loss_terms, dlogits), normalise, loss_out, stream);
 }
 
 int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
@@ -552,12 +564,9 @@ int m2f_cross_entropy_distill(int T, int C, const float* logits, const float* te
     if (!logits || !teacher || !labels || !hyper_dev || !loss_terms || !dlogits || !loss_out)
         return fail("m2f_cross_entropy_distill: NULL logits / teacher / labels / hyper_dev / loss_terms / dlogits / loss_out");
     if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_distill: T >= 1 and 1 <= C <= 16 required");
-    CeDistillArgs a;
-    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
-    a.teacher = teacher; a.hyper = hyper_dev; a.loss_terms = loss_terms; a.dlogits = dlogits;
-    M2F_HIP(m2f_launch_ce_distill(a, static_cast<hipStream_t>(stream)));
-    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
-    return 0;
+    CeArgs a = ce_args(T, C, logits, labels, class_w, label_smoothing, loss_terms, dlogits);
+    a.teacher = teacher; a.hyper = hyper_dev;
+    return ce_run(a, normalise, loss_out, stream);
 }
 
 int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teacher, const int64_t* labels, const float* class_w,
@@ -567,12 +576,20 @@ int m2f_cross_entropy_focal(int T, int C, const float* logits, const float* teac
         return fail("m2f_cross_entropy_focal: NULL logits / labels / gamma_dev / loss_terms / dlogits / loss_out");
     if (teacher && !hyper_dev) return fail("m2f_cross_entropy_focal: a teacher needs hyper_dev (alpha, tau)");
     if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_focal: T >= 1 and 1 <= C <= 16 required");
-    CeFocalArgs a;
-    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
-    a.teacher = teacher; a.hyper = teacher ? hyper_dev : nullptr; a.gamma = gamma_dev; a.loss_terms = loss_terms; a.dlogits = dlogits;
-    M2F_HIP(m2f_launch_ce_focal(a, static_cast<hipStream_t>(stream)));
-    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
-    return 0;
+    CeArgs a = ce_args(T, C, logits, labels, class_w, label_smoothing, loss_terms, dlogits);
+    a.teacher = teacher; a.hyper = teacher ? hyper_dev : nullptr; a.gamma = gamma_dev;
+    return ce_run(a, normalise, loss_out, stream);
+}
+
+int m2f_cross_entropy_rdrop(int T, int C, const float* logits, const int32_t* partner, const int64_t* labels, const float* class_w,
+                            float label_smoothing, const float* alpha_dev, int normalise, float* loss_terms, float* dlogits,
+                            float* loss_out, m2f_stream_t stream) {
+    if (!logits || !partner || !labels || !alpha_dev || !loss_terms || !dlogits || !loss_out)
+        return fail("m2f_cross_entropy_rdrop: NULL logits / partner / labels / alpha_dev / loss_terms / dlogits / loss_out");
+    if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_rdrop: T >= 1 and 1 <= C <= 16 required");
+    CeArgs a = ce_args(T, C, logits, labels, class_w, label_smoothing, loss_terms, dlogits);
+    a.partner = partner; a.alpha = alpha_dev; a.kl_terms = loss_terms + (size_t)T * 2;
+    return ce_run(a, normalise, loss_out, stream);
 }
 
 int64_t m2f_crf_scratch_floats(int T, int B, int C) {
@@ -623,21 +640,6 @@ int m2f_crf_filter(int S, int C, int rows, const float* logits, const float* par
     CrfFilterArgs a;
     a.logits = logits; a.S = S; a.C = C; a.rows = rows; a.params = params; a.count = count; a.active = active; a.n_new = n_new; a.phi = phi;
     M2F_HIP(m2f_launch_crf_filter(a, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int m2f_cross_entropy_rdrop(int T, int C, const float* logits, const int32_t* partner, const int64_t* labels, const float* class_w,
-                            float label_smoothing, const float* alpha_dev, int normalise, float* loss_terms, float* dlogits,
-                            float* loss_out, m2f_stream_t stream) {
-    if (!logits || !partner || !labels || !alpha_dev || !loss_terms || !dlogits || !loss_out)
-        return fail("m2f_cross_entropy_rdrop: NULL logits / partner / labels / alpha_dev / loss_terms / dlogits / loss_out");
-    if (T < 1 || C < 1 || C > 16) return fail("m2f_cross_entropy_rdrop: T >= 1 and 1 <= C <= 16 required");
-    CeRdropArgs a;
-    a.logits = logits; a.T = T; a.C = C; a.labels = labels; a.class_w = class_w; a.label_smoothing = label_smoothing;
-    a.partner = partner; a.alpha = alpha_dev; a.loss_terms = loss_terms; a.kl_terms = loss_terms + (size_t)T * 2; a.dlogits = dlogits;
-    M2F_HIP(m2f_launch_ce_rdrop(a, static_cast<hipStream_t>(stream)));
-    M2F_HIP(m2f_launch_loss_finalize(loss_terms, T, C, dlogits, loss_out, normalise, static_cast<hipStream_t>(stream)));
-    M2F_HIP(m2f_launch_rdrop_kl_reduce(a.kl_terms, T, loss_out, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -534,7 +534,35 @@ hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t strea
 
 // Criterion of src/train.py:48-50 on logits [T, C] (C <= 16): CrossEntropyLoss(ignore_index=-1,
 // label_smoothing, optional class weights).  Per token it writes the loss numerator / denominator
-// terms and the UNNORMALISED gradient d(sum of numerators)/dlogits.
+// terms and the UNNORMALISED gradient d(sum of numerators)/dlogits.  ONE struct and ONE launch for the plain criterion and its
+// three extensions; m2f_launch_ce picks the kernel from which optional pointers are set.  Below, ce / g = the plain numerator and
+// gradient of a row with a valid label y; rows with an invalid label write zeros whatever their teacher or twin row holds.
+//
+// Distillation (teacher, hyper).  q = softmax(z / tau), p = softmax(teacher / tau):
+//   numerator   = (1 - alpha) * ce + alpha * tau^2 * w_y * KL(p || q)                     denominator = w_y, as the plain one
+//   dlogits     = (1 - alpha) * g  + alpha * tau * w_y * (q - p)                          (unnormalised, as the plain one)
+// alpha and tau are READ FROM THE DEVICE (hyper[0], hyper[1]): a captured step replays while a schedule changes them.
+// alpha = 0 gives the plain bits.
+//
+// Focal (gamma; Lin et al. 2017): the hard-label term scaled by (1 - p_y)^gamma.  omp = sum of p_c over c != y, the other classes'
+// probabilities ADDED, never 1 - p_y:
+//   numerator   = omp^gamma * ce
+//   dlogits_c   = omp^gamma * g_c + ce * gamma * omp^gamma * p_y * r_c      r_c = p_c / omp for c != y, r_y = -1
+// (= ce * gamma * omp^(gamma - 1) * p_y * d_c with d_c = p_c, d_y = -omp; the quotient form keeps every factor <= 1, so no gamma in
+// (0, 1) overflows at a tiny omp).  With a teacher the factor scales the hard-label term of the distillation form only:
+// numerator = (1 - alpha) * omp^gamma * ce + alpha * tau^2 * w_y * KL, the teacher's gradient term unchanged.
+// gamma is READ FROM THE DEVICE (gamma[0], in [0, 8]): a captured step replays while a schedule changes it.  gamma == 0 selects factor 1
+// and slope 0: the plain bits (with a teacher the distillation's).  omp == 0 selects factor and slope 0 for gamma > 0.
+//
+// R-Drop (partner, alpha, kl_terms; Liang et al. 2021): every token row r is coupled to its twin t(r) = partner[r] - the same utterance
+// under another dropout mask, a row of the SAME logits buffer.  p = softmax(z_r), q = softmax(z_t(r)):
+//   s           = 0.5 * sum_c (p_c - q_c) * (logp_c - logq_c)      = 0.5 * (KL(p || q) + KL(q || p)), the same bits on both rows of a pair
+//   numerator   = ce + alpha * w_y * s
+//   dlogits_c   = g_c + alpha * w_y * (p_c * ((logp_c - logq_c) - KL(p || q)) + (p_c - q_c))
+// (the twin's row carries the mirror term, so the pair's two gradients are the gradient of w_y * (s_r + s_t(r)) = 2 w_y s.)  kl_terms[r] =
+// w_y * s, WITHOUT alpha: m2f_launch_rdrop_kl_reduce sums it in the finalize launch's order.  logp / logq come from the log-softmax,
+// never from log(p): a probability that underflows contributes 0 * finite = 0.  alpha is READ FROM THE DEVICE (alpha[0] >= 0): a captured
+// step replays while a warm-up changes it; alpha == 0 gives the plain bits.  partner[r] outside [0, T): no twin, the plain term.
 struct CeArgs {
     const float* logits; int T, C;
     const int64_t* labels;                 // [T], ignore_index = -1
@@ -542,67 +570,18 @@ struct CeArgs {
     float label_smoothing;
     float* loss_terms;                     // [T, 2] (numerator, denominator)
     float* dlogits;                        // [T, C]
+    // ---- optional: what is set selects the kernel ----
+    const float* teacher = nullptr;        // [T, C] teacher logits, token rows as logits: distillation (with gamma: its focal form)
+    const float* hyper = nullptr;          // device float [2]: alpha in [0, 1], tau > 0; read only with a teacher
+    const float* gamma = nullptr;          // device float [1]: focal
+    const int32_t* partner = nullptr;      // [T]: the twin of every token row, or -1: R-Drop (no teacher, no gamma)
+    const float* alpha = nullptr;          // device float [1], with partner
+    float* kl_terms = nullptr;             // [T]: w_y * s, with partner
 };
+// partner: R-Drop; else gamma: focal (with or without a teacher); else teacher: distillation; else the plain kernel.
+// hipErrorInvalidValue for a combination without a kernel: partner with teacher or gamma, teacher without hyper, partner without
+// alpha or kl_terms.
 hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream);
-// Distillation criterion: the same launch with a teacher.  Per token row (q = softmax(z / tau), p = softmax(teacher / tau)):
-//   numerator   = (1 - alpha) * CE numerator + alpha * tau^2 * w_y * KL(p || q)          denominator = w_y, as CeArgs
-//   dlogits     = (1 - alpha) * CE gradient  + alpha * tau * w_y * (q - p)               (unnormalised, as CeArgs)
-// alpha and tau are READ FROM THE DEVICE (hyper[0], hyper[1]): a captured step replays while a schedule changes them.
-// alpha = 0 gives m2f_launch_ce's bits.  Rows with an invalid label write zeros whatever their teacher row holds.
-struct CeDistillArgs {
-    const float* logits; int T, C;
-    const int64_t* labels;                 // [T], ignore_index = -1
-    const float* class_w;                  // [C] or null
-    float label_smoothing;
-    const float* teacher;                  // [T, C] teacher logits, token rows as logits
-    const float* hyper;                    // device float [2]: alpha in [0, 1], tau > 0
-    float* loss_terms;                     // [T, 2] (numerator, denominator)
-    float* dlogits;                        // [T, C]
-};
-hipError_t m2f_launch_ce_distill(const CeDistillArgs& a, hipStream_t stream);
-// Focal criterion (Lin et al. 2017): the hard-label term scaled by (1 - p_y)^gamma.  Per token row with a valid label y
-// (ce, g = CeArgs' numerator and gradient; omp = sum of p_c over c != y, the other classes' probabilities ADDED, never 1 - p_y):
-//   numerator   = omp^gamma * ce                                                          denominator = w_y, as CeArgs
-//   dlogits_c   = omp^gamma * g_c + ce * gamma * omp^gamma * p_y * r_c      r_c = p_c / omp for c != y, r_y = -1
-// (= ce * gamma * omp^(gamma - 1) * p_y * d_c with d_c = p_c, d_y = -omp; the quotient form keeps every factor <= 1, so no gamma in
-// (0, 1) overflows at a tiny omp).  With a teacher (non-null; hyper non-null) the factor scales the hard-label term of CeDistillArgs
-// only: numerator = (1 - alpha) * omp^gamma * ce + alpha * tau^2 * w_y * KL, the teacher's gradient term unchanged.
-// gamma is READ FROM THE DEVICE (gamma[0], in [0, 8]): a captured step replays while a schedule changes it.  gamma == 0 selects factor 1
-// and slope 0: m2f_launch_ce's bits (with a teacher m2f_launch_ce_distill's).  omp == 0 selects factor and slope 0 for gamma > 0.
-struct CeFocalArgs {
-    const float* logits; int T, C;
-    const int64_t* labels;                 // [T], ignore_index = -1
-    const float* class_w;                  // [C] or null
-    float label_smoothing;
-    const float* teacher;                  // [T, C] teacher logits or null (no distillation)
-    const float* hyper;                    // device float [2]: alpha, tau; read only with a teacher
-    const float* gamma;                    // device float [1]
-    float* loss_terms;                     // [T, 2] (numerator, denominator)
-    float* dlogits;                        // [T, C]
-};
-hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream);
-// R-Drop criterion (Liang et al. 2021): every token row r is coupled to its twin t(r) = partner[r] - the same utterance under another
-// dropout mask, a row of the SAME logits buffer.  p = softmax(z_r), q = softmax(z_t(r)), ce / g = CeArgs' numerator and gradient:
-//   s           = 0.5 * sum_c (p_c - q_c) * (logp_c - logq_c)      = 0.5 * (KL(p || q) + KL(q || p)), the same bits on both rows of a pair
-//   numerator   = ce + alpha * w_y * s                                                    denominator = w_y, as CeArgs
-//   dlogits_c   = g_c + alpha * w_y * (p_c * ((logp_c - logq_c) - KL(p || q)) + (p_c - q_c))
-// (the twin's row carries the mirror term, so the pair's two gradients are the gradient of w_y * (s_r + s_t(r)) = 2 w_y s.)  kl_terms[r] =
-// w_y * s, WITHOUT alpha: m2f_launch_rdrop_kl_reduce sums it in the finalize launch's order.  logp / logq come from the log-softmax,
-// never from log(p): a probability that underflows contributes 0 * finite = 0.  alpha is READ FROM THE DEVICE (alpha[0] >= 0): a captured
-// step replays while a warm-up changes it; alpha == 0 gives m2f_launch_ce's bits.  partner[r] outside [0, T): no twin, the plain term.
-// Rows with an invalid label write zeros whatever their twin row holds.
-struct CeRdropArgs {
-    const float* logits; int T, C;
-    const int64_t* labels;                 // [T], ignore_index = -1
-    const float* class_w;                  // [C] or null
-    float label_smoothing;
-    const int32_t* partner;                // [T]: the twin of every token row, or -1
-    const float* alpha;                    // device float [1]
-    float* loss_terms;                     // [T, 2] (numerator, denominator)
-    float* kl_terms;                       // [T]: w_y * s
-    float* dlogits;                        // [T, C]
-};
-hipError_t m2f_launch_ce_rdrop(const CeRdropArgs& a, hipStream_t stream);
 // loss_out[3] = (accumulate: +=) sum of kl_terms, summed in m2f_launch_loss_finalize's order (thread-strided, wave sum, (s0 + s1) + (s2 + s3))
 hipError_t m2f_launch_rdrop_kl_reduce(const float* kl_terms, int T, float* loss_out, hipStream_t stream, int accumulate = 0);
 // Linear-chain CRF over a dialogue's labels (crf.hip).  params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.
@@ -673,7 +652,7 @@ struct EvalArgs {
     float label_smoothing;
     float* terms;                          // [T, 2] (numerator, denominator), as CeArgs::loss_terms
     int* partial;                          // [m2f_eval_blocks(T)][C * C]: one integer tile per workgroup of the rows launch
-    const float* gamma = nullptr;          // device float [1] or null: non-null runs the focal form of the rows launch (the loss of CeFocalArgs
+    const float* gamma = nullptr;          // device float [1] or null: non-null runs the focal form of the rows launch (the loss of CeArgs::gamma
                                            // without a teacher, no gradient); null: the default form, its bits unchanged
     const int32_t* pred = nullptr;         // [T] or null: non-null runs the prediction form of the rows launch - the labels counted against pred
                                            // (a decoded path, -1 = none) instead of the argmax, `terms` left as the launch in front wrote them

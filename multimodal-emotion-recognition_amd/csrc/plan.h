@@ -180,6 +180,23 @@ struct AccForm {
     void disarm() { ready = false; wg.clear(); wg_rest.clear(); }      // (`on` stays: the lists follow a rebuild, build_accumulate)
 };
 
+// The criterion's state (m2f_plan_distill, m2f_plan_focal, m2f_plan_rdrop, m2f_plan_crf): which form do_loss launches.  The switches
+// exclude each other by plan.hip's exclusions[] table (distillation and focal combine; nothing else does).
+struct Criterion {
+    bool distill_on = false;             // the teacher blend (M2F_BUF_TEACHER, alpha and tau = M2F_BUF_DISTILL)
+    bool focal_on = false;               // do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
+    bool rdrop_on = false;               // the R-Drop criterion (twins = M2F_BUF_PARTNER, alpha = M2F_BUF_RDROP[0])
+    float* rdrop_kl = nullptr;           // ... its per-row KL terms [T] (train plans), reduced into the tail's fourth float
+    // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
+    // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace
+    bool crf_on = false;
+    const float* crf_params = nullptr;   // [C*C + 2C] (stream and chunk plans: the block m2f_plan_stream_crf filters over)
+    float* crf_grad = nullptr;           // [C*C + 2C] or null (frozen)
+    float* crf_ws = nullptr;             // m2f_crf_scratch_floats(T, B, C) floats (null: a stream plan, or cls_out outside 2 .. 16)
+    int32_t* crf_pred = nullptr;         // [T]
+    float* crf_score = nullptr;          // [B]
+};
+
 // plan.hip
 m2f_plan* plan_new(const m2f_config* cfg, int B, int L, int precision, int train, int T_packed = 0);
 int do_forward(m2f_plan& P, hipStream_t s);
@@ -250,18 +267,7 @@ struct m2f_plan {
     m2f::FusedBufs fz;
     uint16_t* g16_buf = nullptr;
     m2f::AccForm acc;
-    bool distill_on = false;             // m2f_plan_distill: do_loss launches the distillation criterion
-    bool rdrop_on = false;               // m2f_plan_rdrop: do_loss launches the R-Drop criterion (twins = M2F_BUF_PARTNER, alpha = M2F_BUF_RDROP[0])
-    float* rdrop_kl = nullptr;           // ... its per-row KL terms [T] (train plans), reduced into the tail's fourth float
-    bool focal_on = false;               // m2f_plan_focal: do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
-    // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
-    // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace
-    bool crf_on = false;
-    const float* crf_params = nullptr;   // [C*C + 2C]
-    float* crf_grad = nullptr;           // [C*C + 2C] or null (frozen)
-    float* crf_ws = nullptr;             // m2f_crf_scratch_floats(T, B, C) floats (null: a stream plan, or cls_out outside 2 .. 16)
-    int32_t* crf_pred = nullptr;         // [T]
-    float* crf_score = nullptr;          // [B]
+    m2f::Criterion crit;             // which criterion do_loss launches, and what it needs
     float* s_phi = nullptr;              // stream and chunk plans (m2f_plan_stream_crf): the CALLER's filter state [S, C] over crf_params, or null
     // graph cache: m2f_step, m2f_step_part(0), m2f_step_part(1), ...
     m2f::GraphSlot graphs[m2f::SLOT_COUNT];

@@ -1107,14 +1107,14 @@ int build_plan(m2f_plan& P, char* ws_base) {
     P.bufs[M2F_BUF_FOCAL] = bld.ar.f(1);
     // workspace of the CRF criterion (m2f_plan_crf), train and eval plans whose classifier has 2 .. 16 classes: behind everything again
     if (!P.streaming && !P.s_parent && c.cls_out >= 2 && c.cls_out <= 16) {
-        P.crf_ws = bld.ar.f((size_t)T * (2 * c.cls_out + 2) + (size_t)P.B * (c.cls_out * c.cls_out + 2 * c.cls_out));
-        P.crf_pred = bld.ar.alloc<int32_t>((size_t)T);
-        P.crf_score = bld.ar.f((size_t)P.B);
+        P.crit.crf_ws = bld.ar.f((size_t)T * (2 * c.cls_out + 2) + (size_t)P.B * (c.cls_out * c.cls_out + 2 * c.cls_out));
+        P.crit.crf_pred = bld.ar.alloc<int32_t>((size_t)T);
+        P.crit.crf_score = bld.ar.f((size_t)P.B);
     }
     // inputs of the R-Drop criterion (m2f_plan_rdrop), train plans only: the twin map, alpha, and the per-row KL terms - behind everything again
     P.bufs[M2F_BUF_PARTNER] = P.train ? bld.ar.alloc<int32_t>((size_t)T) : nullptr;
     P.bufs[M2F_BUF_RDROP] = P.train ? bld.ar.f(1) : nullptr;
-    P.rdrop_kl = P.train ? bld.ar.f((size_t)T) : nullptr;
+    P.crit.rdrop_kl = P.train ? bld.ar.f((size_t)T) : nullptr;
     P.built.ws_used = bld.ar.off;
     if (P.prec == M2F_PREC_BF16 && ws_base != nullptr) {
         const float* wsf = reinterpret_cast<const float*>(ws_base);

@@ -89,7 +89,7 @@ static int stream_filter(m2f_plan& P, int rows, hipStream_t s) {
     if (!P.s_phi) return 0;
     CrfFilterArgs a;
     a.logits = static_cast<const float*>(P.bufs[M2F_BUF_LOGITS]); a.S = P.B; a.C = P.cfg.cls_out; a.rows = rows;
-    a.params = P.crf_params; a.count = P.s_len; a.active = rows == 1 ? P.s_active : nullptr; a.n_new = rows == 1 ? nullptr : P.s_new;
+    a.params = P.crit.crf_params; a.count = P.s_len; a.active = rows == 1 ? P.s_active : nullptr; a.n_new = rows == 1 ? nullptr : P.s_new;
     a.phi = P.s_phi;
     M2F_HIP(m2f_launch_crf_filter(a, s));
     return 0;
@@ -101,13 +101,13 @@ int m2f_plan_stream_crf(m2f_plan* plan, const float* params, float* phi) {
     if ((params == nullptr) != (phi == nullptr)) return fail("m2f_plan_stream_crf: params and phi come together (both NULL: off)");
     if (params && (P.cfg.cls_out < 2 || P.cfg.cls_out > 16)) return fail("m2f_plan_stream_crf: 2 .. 16 classes");
     if ((reinterpret_cast<uintptr_t>(params) & 15) || (reinterpret_cast<uintptr_t>(phi) & 3)) return fail("m2f_plan_stream_crf: params must be 16-byte aligned");
-    if (params == P.crf_params && phi == P.s_phi) return 0;
+    if (params == P.crit.crf_params && phi == P.s_phi) return 0;
     // the filter launch travels by value inside the captured step / prefill: the capture goes, one eager call comes first
     M2F_HIP(hipDeviceSynchronize());
     P.graphs[P.s_parent ? SLOT_PREFILL : SLOT_STREAM].reset();
     ++P.generation;
     P.warmed = false;
-    P.crf_params = params; P.s_phi = phi;
+    P.crit.crf_params = params; P.s_phi = phi;
     return 0;
 }
 static int stream_body(m2f_plan& P, hipStream_t s) {

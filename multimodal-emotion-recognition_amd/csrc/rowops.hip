@@ -11,6 +11,7 @@
 // them for one row of gamma.)  The general path (d % 4 != 0 or an unaligned operand) keeps the guarded element loads.
 #include "common.h"
 #include "ops.h"
+#include "criterion_row.h"
 #include <algorithm>
 
 // No floating-point contraction in this file: several kernels restate the same formulas in different surroundings (ring and
@@ -352,338 +353,110 @@ __global__ __launch_bounds__(256) void m2f_ln_param_reduce_kernel(const LnReduce
 }
 
 // ---- criterion ---------------------------------------------------------------------------------------
+// One lane per token row; the row itself and what each criterion adds to it are criterion_row.h's helpers (the ONE definition - the
+// reasons for every select and every order of operations are there).  The four kernels stay separate entry points: their register
+// budgets differ, and the build's spill gate counts them by name.  An invalid row (label -1 or out of range) is a SELECT of zeros,
+// whatever its logits, its teacher row or its twin row hold (NaN, inf).
 __global__ __launch_bounds__(256) void m2f_ce_kernel(const CeArgs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.T) return;
-    const int C = a.C;
-    float z[16], w[16];
-    float m = -INFINITY;
+    CeRow r;
+    m2f_ce_row_forward(r, a.logits, a.labels, a.class_w, a.label_smoothing, t, a.C);
+    a.loss_terms[2 * t] = r.num;
+    a.loss_terms[2 * t + 1] = r.valid ? r.wy : 0.f;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
-        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
-        m = fmaxf(m, z[c]);
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
-    const float lse = m + logf(se);
-    const int64_t y = a.labels[t];
-    const bool valid = (y >= 0) && (y < C);
-    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float lp = z[c] - lse;
-            W += w[c];
-            sm -= w[c] * lp;
-            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
-        }
-    }
-    const float eps = a.label_smoothing;
-    const float num = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
-    a.loss_terms[2 * t] = num;
-    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float p = expf(z[c] - lse);
-            float g = 0.f;
-            if (valid) g = (1.f - eps) * wy * (p - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * p - w[c]);
-            a.dlogits[(size_t)t * C + c] = g;
-        }
+        if (c < a.C) a.dlogits[(size_t)t * a.C + c] = m2f_ce_row_grad(r, c, m2f_ce_row_p(r, c));
     }
 }
 
-// Distillation criterion (CeDistillArgs, ops.h): m2f_ce_kernel's two terms and gradient, statement for statement and in its order,
-// blended with the temperature-scaled KL divergence from a teacher's logits.  alpha = 0 therefore gives m2f_ce_kernel's bits:
-// (1 - 0) * x + 0 * finite is exact.  One lane per token row, sixteen classes fully unrolled, everything in registers.
-// logp / logq come from the log-softmax (u_c / tau - lse), never from log(p): a teacher probability that underflows contributes
-// 0 * finite = 0.  An invalid row (label -1 or out of range) is a SELECT of zeros, whatever its teacher row holds (NaN, inf).
-__global__ __launch_bounds__(256) void m2f_ce_distill_kernel(const CeDistillArgs a) {
+// Distillation criterion (CeArgs::teacher, ::hyper): the plain terms blended with the temperature-scaled KL divergence from a
+// teacher's logits.
+__global__ __launch_bounds__(256) void m2f_ce_distill_kernel(const CeArgs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.T) return;
-    const int C = a.C;
-    const float alpha = a.hyper[0], tau = a.hyper[1];
-    float z[16], w[16], u[16];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
-        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
-        u[c] = (c < C) ? a.teacher[(size_t)t * C + c] : -INFINITY;
-        m = fmaxf(m, z[c]);
-    }
-    // ---- as m2f_ce_kernel ----
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
-    const float lse = m + logf(se);
-    const int64_t y = a.labels[t];
-    const bool valid = (y >= 0) && (y < C);
-    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float lp = z[c] - lse;
-            W += w[c];
-            sm -= w[c] * lp;
-            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
-        }
-    }
-    const float eps = a.label_smoothing;
-    const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
-    // ---- the teacher term: q = softmax(z / tau), p = softmax(u / tau), KL = sum_c p_c (logp_c - logq_c) ----
-    float zt[16];
-    float mz = -INFINITY, mu = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        zt[c] = (c < C) ? z[c] / tau : -INFINITY;
-        u[c] = (c < C) ? u[c] / tau : -INFINITY;
-        mz = fmaxf(mz, zt[c]);
-        mu = fmaxf(mu, u[c]);
-    }
-    float sz = 0.f, su = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        sz += (c < C) ? expf(zt[c] - mz) : 0.f;
-        su += (c < C) ? expf(u[c] - mu) : 0.f;
-    }
-    const float lsz = mz + logf(sz), lsu = mu + logf(su);
-    const float oma = 1.f - alpha;
-    const float kd = alpha * tau * tau * wy, gd = alpha * tau * wy;
+    CeRow r;
+    m2f_ce_row_forward(r, a.logits, a.labels, a.class_w, a.label_smoothing, t, a.C);
+    CeTeacher k;
+    m2f_ce_row_teacher(k, r, a.teacher, t, a.hyper[0], a.hyper[1]);
     float kl = 0.f;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float lq = zt[c] - lsz, lpt = u[c] - lsu;
-            const float q = expf(lq), pt = expf(lpt);
-            kl += pt * (lpt - lq);
-            // ---- as m2f_ce_kernel ----
-            const float p = expf(z[c] - lse);
-            float g = 0.f;
-            if (valid) g = (1.f - eps) * wy * (p - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * p - w[c]);
-            a.dlogits[(size_t)t * C + c] = valid ? (oma * g + gd * (q - pt)) : 0.f;
+        if (c < a.C) {
+            const float d = m2f_ce_teacher_class(k, c, kl);
+            const float g = m2f_ce_row_grad(r, c, m2f_ce_row_p(r, c));
+            a.dlogits[(size_t)t * a.C + c] = r.valid ? (k.oma * g + k.gd * d) : 0.f;
         }
     }
-    a.loss_terms[2 * t] = valid ? (oma * num_ce + kd * kl) : 0.f;
-    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
+    a.loss_terms[2 * t] = r.valid ? (k.oma * r.num + k.kd * kl) : 0.f;
+    a.loss_terms[2 * t + 1] = r.valid ? r.wy : 0.f;
 }
 
-// Focal criterion (CeFocalArgs, ops.h): m2f_ce_kernel's numerator and gradient (TEACHER: m2f_ce_distill_kernel's), statement for
-// statement and in their order, with the hard-label term scaled by omp^gamma.  gamma == 0 SELECTS the unscaled values, so it gives those
-// kernels' bits.  One lane per token row, sixteen classes fully unrolled, everything in registers.
-//   omp is the other classes' probabilities ADDED (c != y), not 1 - p_y: at a margin of 20 p_y rounds to 1 and 1 - p_y to 0 or to one
-//   ulp of 1, while the sum keeps its own 24 bits.  For the same reason the y column's slope is -omp, not p_y - 1.
-//   The slope term ce * gamma * omp^(gamma-1) * p_y * d_c (d_c = p_c, d_y = -omp) is computed as ce * gamma * omp^gamma * p_y * r_c with
-//   r_c = p_c / omp <= 1, r_y = -1: no factor exceeds 1, so a gamma in (0, 1) cannot overflow omp^(gamma-1) at a tiny omp.
-//   omp == 0 (every other expf underflowed): factor, slope and every r_c are SELECTED to 0 for gamma > 0; logf / powf never see the zero.
-// An invalid row (label -1 or out of range) is a SELECT of zeros, whatever its logits or its teacher row hold.
+// Focal criterion (CeArgs::gamma; TEACHER: with the distillation blend, the factor scales the hard-label term only)
 template <bool TEACHER>
-__global__ __launch_bounds__(256) void m2f_ce_focal_kernel(const CeFocalArgs a) {
+__global__ __launch_bounds__(256) void m2f_ce_focal_kernel(const CeArgs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.T) return;
-    const int C = a.C;
-    const float gamma = a.gamma[0];
-    float alpha = 0.f, tau = 1.f;
-    if constexpr (TEACHER) { alpha = a.hyper[0]; tau = a.hyper[1]; }
-    float z[16], w[16], u[16];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
-        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
-        if constexpr (TEACHER) u[c] = (c < C) ? a.teacher[(size_t)t * C + c] : -INFINITY;
-        m = fmaxf(m, z[c]);
-    }
-    // ---- as m2f_ce_kernel ----
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
-    const float lse = m + logf(se);
-    const int64_t y = a.labels[t];
-    const bool valid = (y >= 0) && (y < C);
-    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float lp = z[c] - lse;
-            W += w[c];
-            sm -= w[c] * lp;
-            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
-        }
-    }
-    const float eps = a.label_smoothing;
-    const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
-    // ---- the focal factor: p as the gradient loop of m2f_ce_kernel computes it, omp = the other classes' p added in class order ----
-    float p[16];
-    float omp = 0.f, py = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        p[c] = (c < C) ? expf(z[c] - lse) : 0.f;
-        if (c < C) {
-            if (valid && c == (int)y) py = p[c];
-            else omp += p[c];
-        }
-    }
-    const bool focal = gamma > 0.f;
-    const bool live = focal && omp > 0.f;
-    const float f = m2f_focal_factor(omp, gamma);
-    const float slope = live ? num_ce * gamma * f * py : 0.f;
-    const float num_f = focal ? f * num_ce : num_ce;
-    // ---- the teacher term, as m2f_ce_distill_kernel ----
-    float zt[16];
-    float lsz = 0.f, lsu = 0.f, oma = 1.f, kd = 0.f, gd = 0.f;
-    if constexpr (TEACHER) {
-        float mz = -INFINITY, mu = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            zt[c] = (c < C) ? z[c] / tau : -INFINITY;
-            u[c] = (c < C) ? u[c] / tau : -INFINITY;
-            mz = fmaxf(mz, zt[c]);
-            mu = fmaxf(mu, u[c]);
-        }
-        float sz = 0.f, su = 0.f;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            sz += (c < C) ? expf(zt[c] - mz) : 0.f;
-            su += (c < C) ? expf(u[c] - mu) : 0.f;
-        }
-        lsz = mz + logf(sz); lsu = mu + logf(su);
-        oma = 1.f - alpha;
-        kd = alpha * tau * tau * wy; gd = alpha * tau * wy;
-    }
+    CeRow r;
+    m2f_ce_row_forward(r, a.logits, a.labels, a.class_w, a.label_smoothing, t, a.C);
+    CeFocal f;
+    m2f_ce_row_focal(f, r, a.gamma[0]);
+    CeTeacher k;
+    if constexpr (TEACHER) m2f_ce_row_teacher(k, r, a.teacher, t, a.hyper[0], a.hyper[1]);
     float kl = 0.f;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            // ---- as m2f_ce_kernel ----
-            const float pc = p[c];
-            float g = 0.f;
-            if (valid) g = (1.f - eps) * wy * (pc - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * pc - w[c]);
-            const float r = live ? ((c == (int)y) ? -1.f : pc / omp) : 0.f;
-            const float gf = focal ? (f * g + slope * r) : g;
+        if (c < a.C) {
+            const float gf = m2f_ce_focal_grad(f, r, c, m2f_ce_row_grad(r, c, f.p[c]));
             if constexpr (TEACHER) {
-                const float lq = zt[c] - lsz, lpt = u[c] - lsu;
-                const float q = expf(lq), pt = expf(lpt);
-                kl += pt * (lpt - lq);
-                a.dlogits[(size_t)t * C + c] = valid ? (oma * gf + gd * (q - pt)) : 0.f;
+                const float d = m2f_ce_teacher_class(k, c, kl);
+                a.dlogits[(size_t)t * a.C + c] = r.valid ? (k.oma * gf + k.gd * d) : 0.f;
             } else {
-                a.dlogits[(size_t)t * C + c] = valid ? gf : 0.f;
+                a.dlogits[(size_t)t * a.C + c] = r.valid ? gf : 0.f;
             }
         }
     }
-    if constexpr (TEACHER) a.loss_terms[2 * t] = valid ? (oma * num_f + kd * kl) : 0.f;
-    else a.loss_terms[2 * t] = valid ? num_f : 0.f;
-    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
+    if constexpr (TEACHER) a.loss_terms[2 * t] = r.valid ? (k.oma * f.num_f + k.kd * kl) : 0.f;
+    else a.loss_terms[2 * t] = r.valid ? f.num_f : 0.f;
+    a.loss_terms[2 * t + 1] = r.valid ? r.wy : 0.f;
 }
 
-// R-Drop criterion (CeRdropArgs, ops.h): m2f_ce_kernel's numerator and gradient, statement for statement and in its order, plus alpha * w_y
-// times the symmetric KL divergence between the row's softmax and its twin's (the same utterance under another dropout mask, row
-// partner[t] of the SAME logits buffer).  One lane per token row, sixteen classes fully unrolled, everything in registers; a row reads
-// its twin's logits and writes only its own outputs.  alpha = 0 gives m2f_ce_kernel's bits: x + 0 * finite is exact.
-//   The twin load is range-checked: an index outside [0, T) means no twin, the lane then re-reads its own row and SELECTS the plain term.
-//   q is computed as the twin computes its own p (expf((u_c - max) - logf(sum))), so s = 0.5 * sum (p - q)(logp - logq) has
-//   the same bits on both rows of a pair, and twins with equal logits give s = 0 and a KL gradient of exactly 0.
-//   logp - logq comes from the two log-softmaxes, never from log(p): a probability that underflows contributes 0 * finite = 0.
-// An invalid row (label -1 or out of range) is a SELECT of zeros, whatever its twin row holds (NaN, inf).
-__global__ __launch_bounds__(256) void m2f_ce_rdrop_kernel(const CeRdropArgs a) {
+// R-Drop criterion (CeArgs::partner, ::alpha, ::kl_terms): the plain terms plus alpha * w_y times the symmetric KL divergence between
+// the row's softmax and its twin's (the same utterance under another dropout mask, row partner[t] of the SAME logits buffer); a row
+// reads its twin's logits and writes only its own outputs.  alpha = 0 gives m2f_ce_kernel's bits: x + 0 * finite is exact.
+// The twin load is range-checked: an index outside [0, T) means no twin, the lane then re-reads its own row and SELECTS the plain term.
+__global__ __launch_bounds__(256) void m2f_ce_rdrop_kernel(const CeArgs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.T) return;
-    const int C = a.C;
     const float alpha = a.alpha[0];
     const int tw = a.partner[t];
     const bool has = (tw >= 0) && (tw < a.T);
-    const int tr = has ? tw : t;
-    float z[16], w[16], u[16];
-    float m = -INFINITY, mu = -INFINITY;
+    CeRow r;
+    m2f_ce_row_forward(r, a.logits, a.labels, a.class_w, a.label_smoothing, t, a.C);
+    CeTwin k;
+    m2f_ce_row_twin(k, r, a.logits, has ? tw : t, has);
+    const float ak = alpha * r.wy;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-        z[c] = (c < C) ? a.logits[(size_t)t * C + c] : -INFINITY;
-        w[c] = (c < C) ? (a.class_w ? a.class_w[c] : 1.f) : 0.f;
-        u[c] = (c < C) ? a.logits[(size_t)tr * C + c] : -INFINITY;
-        m = fmaxf(m, z[c]);
-        mu = fmaxf(mu, u[c]);
-    }
-    // ---- as m2f_ce_kernel ----
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) se += (c < C) ? expf(z[c] - m) : 0.f;
-    const float lse = m + logf(se);
-    const int64_t y = a.labels[t];
-    const bool valid = (y >= 0) && (y < C);
-    float wy = 0.f, logpy = 0.f, W = 0.f, sm = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            const float lp = z[c] - lse;
-            W += w[c];
-            sm -= w[c] * lp;
-            if (valid && c == (int)y) { wy = w[c]; logpy = lp; }
+        if (c < a.C) {
+            const float g = m2f_ce_row_grad(r, c, m2f_ce_row_p(r, c));
+            a.dlogits[(size_t)t * a.C + c] = r.valid ? (g + ak * m2f_ce_twin_grad(k, c)) : 0.f;
         }
     }
-    const float eps = a.label_smoothing;
-    const float num_ce = valid ? ((1.f - eps) * (-logpy) * wy + eps * sm / (float)C) : 0.f;
-    // ---- the twin term ----
-    // logp_c = (z_c - m) - logf(se), NOT z_c - lse: lse = m + logf(se) is rounded at the size of m, and on saturated rows (|z| in the
-    // hundreds) that rounding, harmless to p - onehot above, would be multiplied here by log-ratios of the margin's size.  The twin's
-    // logq from its own max and sum in the same way: both lanes of a pair compute the same p, q and ratio bits.
-    float su = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) su += (c < C) ? expf(u[c] - mu) : 0.f;
-    const float lgs = logf(se), lgu = logf(su);
-    // e_c = (z_c - u_c) - (z_k - u_k), k the row's own first maximal class: logp_c - logq_c up to a constant.  The gradient needs
-    // (logp_c - logq_c) - KL(p || q) = e_c - sum_j p_j e_j; on a confident row (p_k = 1 - tiny) the direct difference of two numbers of
-    // the margin's size would lose the tiny part to rounding, while here the j = k term is exactly 0.
-    float best = -INFINITY, e0 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C && z[c] > best) { best = z[c]; e0 = z[c] - u[c]; }
-    }
-    float p[16], q[16], e[16];
-    float ebar = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const float lp = (c < C) ? ((z[c] - m) - lgs) : 0.f, lq = (c < C) ? ((u[c] - mu) - lgu) : 0.f;
-        p[c] = (c < C) ? expf(lp) : 0.f;
-        q[c] = (c < C) ? expf(lq) : 0.f;
-        e[c] = (c < C) ? ((z[c] - u[c]) - e0) : 0.f;
-        ebar += p[c] * e[c];
-        s2 += (p[c] - q[c]) * (lp - lq);
-    }
-    const bool live = valid && has;
-    const float ws = live ? wy * (0.5f * s2) : 0.f;
-    const float ak = alpha * wy;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < C) {
-            // ---- as m2f_ce_kernel ----
-            const float pc = expf(z[c] - lse);
-            float g = 0.f;
-            if (valid) g = (1.f - eps) * wy * (pc - ((c == (int)y) ? 1.f : 0.f)) + (eps / (float)C) * (W * pc - w[c]);
-            const float k = live ? (p[c] * (e[c] - ebar) + (p[c] - q[c])) : 0.f;
-            a.dlogits[(size_t)t * C + c] = valid ? (g + ak * k) : 0.f;
-        }
-    }
-    a.loss_terms[2 * t] = valid ? (num_ce + alpha * ws) : 0.f;
-    a.loss_terms[2 * t + 1] = valid ? wy : 0.f;
-    a.kl_terms[t] = ws;
+    a.loss_terms[2 * t] = r.valid ? (r.num + alpha * k.ws) : 0.f;
+    a.loss_terms[2 * t + 1] = r.valid ? r.wy : 0.f;
+    a.kl_terms[t] = k.ws;
 }
 
-// The KL share of the R-Drop numerator on its own: loss_out[3] = sum of kl_terms (w_y * s per row, without alpha), in exactly
-// m2f_loss_finalize_kernel's order.  ACC: added, as that kernel adds den and num.
+// The KL share of the R-Drop numerator on its own: loss_out[3] = sum of kl_terms (w_y * s per row, without alpha).  ACC: added, as
+// the finalize launch adds den and num.
 template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_rdrop_kl_reduce_kernel(const float* __restrict__ kl_terms, int T, float* __restrict__ loss_out) {
-    __shared__ float sk[4];
-    float k = 0.f;
-    for (int t = threadIdx.x; t < T; t += 256) k += kl_terms[t];
-    k = m2f_wave_sum(k);
-    if ((threadIdx.x & 63) == 0) sk[threadIdx.x >> 6] = k;
-    __syncthreads();
+    float kl[1];
+    m2f_block_sum_terms<1>(kl_terms, T, kl);
     if (threadIdx.x == 0) {
-        const float kl = (sk[0] + sk[1]) + (sk[2] + sk[3]);
-        if constexpr (ACC) loss_out[3] = loss_out[3] + kl;
-        else loss_out[3] = kl;
+        if constexpr (ACC) loss_out[3] = loss_out[3] + kl[0];
+        else loss_out[3] = kl[0];
     }
 }
 
@@ -692,15 +465,9 @@ template <bool ACC>
 __global__ __launch_bounds__(256) void m2f_loss_finalize_kernel(const float* __restrict__ terms, int T, int C,
                                                                 float* __restrict__ dlogits, float* __restrict__ loss_out,
                                                                 int normalise) {
-    __shared__ float sn[4], sd[4];
-    float n = 0.f, dd = 0.f;
-    for (int t = threadIdx.x; t < T; t += 256) { n += terms[2 * t]; dd += terms[2 * t + 1]; }
-    n = m2f_wave_sum(n);
-    dd = m2f_wave_sum(dd);
-    if ((threadIdx.x & 63) == 0) { sn[threadIdx.x >> 6] = n; sd[threadIdx.x >> 6] = dd; }
-    __syncthreads();
-    const float num = (sn[0] + sn[1]) + (sn[2] + sn[3]);
-    const float den = (sd[0] + sd[1]) + (sd[2] + sd[3]);
+    float s[2];
+    m2f_block_sum_terms<2>(terms, T, s);
+    const float num = s[0], den = s[1];
     if constexpr (ACC) {
         if (threadIdx.x == 0) { loss_out[0] = num / den; loss_out[1] = loss_out[1] + den; loss_out[2] = loss_out[2] + num; }
     } else {
@@ -1192,28 +959,16 @@ hipError_t m2f_launch_ln_param_reduce(const LnReduceBatch& rb, hipStream_t strea
     return hipGetLastError();
 }
 
+// The ONE criterion launch: the kernel follows from which optional pointers are set (ops.h, CeArgs)
 hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream) {
     if (a.C < 1 || a.C > 16 || a.T < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(m2f_ce_kernel, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_ce_distill(const CeDistillArgs& a, hipStream_t stream) {
-    if (a.C < 1 || a.C > 16 || a.T < 1 || !a.teacher || !a.hyper) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(m2f_ce_distill_kernel, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_ce_focal(const CeFocalArgs& a, hipStream_t stream) {
-    if (a.C < 1 || a.C > 16 || a.T < 1 || !a.gamma || (a.teacher && !a.hyper)) return hipErrorInvalidValue;
-    if (a.teacher) hipLaunchKernelGGL(m2f_ce_focal_kernel<true>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(m2f_ce_focal_kernel<false>, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_ce_rdrop(const CeRdropArgs& a, hipStream_t stream) {
-    if (a.C < 1 || a.C > 16 || a.T < 1 || !a.partner || !a.alpha || !a.kl_terms) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(m2f_ce_rdrop_kernel, dim3(m2f_cdiv(a.T, 256)), dim3(256), 0, stream, a);
+    if (a.partner ? (a.teacher || a.gamma || !a.alpha || !a.kl_terms) : (a.teacher && !a.hyper)) return hipErrorInvalidValue;
+    const dim3 grid(m2f_cdiv(a.T, 256)), block(256);
+    if (a.partner) hipLaunchKernelGGL(m2f_ce_rdrop_kernel, grid, block, 0, stream, a);
+    else if (a.gamma && a.teacher) hipLaunchKernelGGL(m2f_ce_focal_kernel<true>, grid, block, 0, stream, a);
+    else if (a.gamma) hipLaunchKernelGGL(m2f_ce_focal_kernel<false>, grid, block, 0, stream, a);
+    else if (a.teacher) hipLaunchKernelGGL(m2f_ce_distill_kernel, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(m2f_ce_kernel, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 
