@@ -47,7 +47,10 @@ adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
 # --crf <remarks>: the linear-chain CRF kernels (crf.hip) - a lane's transition column / row, its gradient column and the sixteen terms of
 # a step stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
 crf = len(sys.argv) > 2 and sys.argv[1] == "--crf"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf) else sys.argv[1]
+# --supcon <remarks>: the supervised contrastive kernels (supcon.hip) - a tile's MFMA accumulators, the chunk staged one step ahead and a
+# row's terms stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
+supcon = len(sys.argv) > 2 and sys.argv[1] == "--supcon"
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -93,6 +96,16 @@ if crf:
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if supcon:
+    kernels = [r for r in rows if "m2f_supcon_" in r["name"]]
+    # prep, fwd, rows, bwd, dfeat, the tail with and without accumulation, add
+    if len(kernels) != 8:
+        sys.exit(f"check_spills: expected the eight m2f_supcon_ kernels in {path}, found {len(kernels)} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('AGPRs')} AGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
               f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
     sys.exit(1 if bad else 0)
 if attn:

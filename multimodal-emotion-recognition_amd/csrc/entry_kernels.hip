@@ -643,6 +643,21 @@ int m2f_crf_filter(int S, int C, int rows, const float* logits, const float* par
     return 0;
 }
 
+int64_t m2f_supcon_scratch_floats(int N, int D) { return (int64_t)m2f_supcon_ws_floats(N, D); }
+
+int m2f_supcon(int N, int D, int C, const float* features, int ld, const int64_t* labels, const float* class_w, const float* hyper_dev,
+               float* scratch, float* row_terms, float* dfeatures, int ldd, m2f_stream_t stream) {
+    if (!features || !labels || !hyper_dev || !scratch || !row_terms || !dfeatures)
+        return fail("m2f_supcon: NULL features / labels / hyper_dev / scratch / row_terms / dfeatures");
+    if (N < 1 || D < 1 || C < 1 || ld < D || ldd < D) return fail("m2f_supcon: N >= 1, D >= 1, C >= 1, ld >= D and ldd >= D required");
+    if ((reinterpret_cast<uintptr_t>(scratch) & 15) || (reinterpret_cast<uintptr_t>(row_terms) & 15)) return fail("m2f_supcon: scratch and row_terms must be 16-byte aligned");
+    SupconArgs a;
+    a.feat = features; a.N = N; a.D = D; a.ld = ld; a.labels = labels; a.C = C; a.class_w = class_w; a.hyper = hyper_dev;
+    a.ws = scratch; a.row_terms = row_terms; a.dfeat = dfeatures; a.ldd = ldd;
+    M2F_HIP(m2f_launch_supcon(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
     return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
 }

@@ -584,6 +584,31 @@ struct CeArgs {
 hipError_t m2f_launch_ce(const CeArgs& a, hipStream_t stream);
 // loss_out[3] = (accumulate: +=) sum of kl_terms, summed in m2f_launch_loss_finalize's order (thread-strided, wave sum, (s0 + s1) + (s2 + s3))
 hipError_t m2f_launch_rdrop_kl_reduce(const float* kl_terms, int T, float* loss_out, hipStream_t stream, int accumulate = 0);
+// Supervised contrastive criterion over feature rows (supcon.hip holds the definition: V, z, s, l_i, c_i, dz, dh).  Exact fp32 on
+// v_mfma_f32_16x16x4_f32 whatever the plan's precision.  lambda and tau are READ FROM THE DEVICE (hyper[0] >= 0, hyper[1] > 0): a
+// captured step replays while a schedule changes them; lambda == 0 gives dfeat = 0 and adds 0 to every numerator.
+//   row_terms[i] = (lse_i, n_i, l_i, w_{y_i} l_i)        zeros outside V; l = 0 for a row of V without a positive (its lse is still given)
+//   dfeat[i, :]  = lambda-weighted d (sum_i w_{y_i} l_i) / d h_i, unnormalised (no 1 / den), zeros outside V
+//   loss_terms   (nullable) [N, 2]: the numerator of row i += lambda * w_{y_i} * l_i; the denominator is untouched
+struct SupconArgs {
+    const float* feat; int N, D, ld;       // [N, D], row stride ld
+    const int64_t* labels; int C;          // [N], a label outside [0, C) = not in V
+    const float* class_w;                  // [C] or null
+    const float* hyper;                    // device float [2]: lambda, tau
+    float* ws;                             // m2f_supcon_ws_floats(N, D) floats, 16-byte aligned
+    float* row_terms;                      // [N, 4], 16-byte aligned
+    float* dfeat; int ldd;                 // [N, D], row stride ldd
+    float* loss_terms = nullptr;
+};
+size_t m2f_supcon_ws_floats(int N, int D);
+hipError_t m2f_launch_supcon(const SupconArgs& a, hipStream_t stream);
+// loss_out[3] = (accumulate: +=) sum of row_terms' w l in m2f_launch_loss_finalize's order; scale[0] = the factor that launch multiplies
+// dlogits by for the same loss_terms (1 / den, the same bits; 1 without normalise)
+hipError_t m2f_launch_supcon_tail(const float* row_terms, const float* loss_terms, int T, float* loss_out, float* scale, int normalise,
+                                  hipStream_t stream, int accumulate = 0);
+// dh[i, :] += (h[i, :] > 0 ? gate_scale : 0) * scale[0] * dfeat[i, :] over [T, d] buffers of one row stride; write16: dh's bf16 shadow too
+hipError_t m2f_launch_supcon_add(float* dh, const float* h, const float* dfeat, const float* scale, int T, int d, int ld, float gate_scale,
+                                 int write16, ShadowMap sh, hipStream_t stream);
 // Linear-chain CRF over a dialogue's labels (crf.hip).  params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.
 // Dialogue b owns token rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (packed and long-dialogue plans) or, cu_seqlens null, b*L .. b*L+L-1
 // (padded and bucket-padded plans).  The CHAIN of a dialogue is its rows with a label in [0, C), in row order (a -1 in the middle links

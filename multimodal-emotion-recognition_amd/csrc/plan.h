@@ -180,13 +180,23 @@ struct AccForm {
     void disarm() { ready = false; wg.clear(); wg_rest.clear(); }      // (`on` stays: the lists follow a rebuild, build_accumulate)
 };
 
-// The criterion's state (m2f_plan_distill, m2f_plan_focal, m2f_plan_rdrop, m2f_plan_crf): which form do_loss launches.  The switches
-// exclude each other by plan.hip's exclusions[] table (distillation and focal combine; nothing else does).
+// The criterion's state (m2f_plan_distill, m2f_plan_focal, m2f_plan_rdrop, m2f_plan_crf, m2f_plan_supcon): which form do_loss launches.  The
+// switches exclude each other by plan.hip's exclusions[] table (distillation and focal combine; nothing else does).
 struct Criterion {
     bool distill_on = false;             // the teacher blend (M2F_BUF_TEACHER, alpha and tau = M2F_BUF_DISTILL)
     bool focal_on = false;               // do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
     bool rdrop_on = false;               // the R-Drop criterion (twins = M2F_BUF_PARTNER, alpha = M2F_BUF_RDROP[0])
     float* rdrop_kl = nullptr;           // ... its per-row KL terms [T] (train plans), reduced into the tail's fourth float
+    // m2f_plan_supcon: do_loss runs the supervised contrastive kernels (supcon.hip) on the classifier's last hidden activation behind the
+    // cross-entropy launch, the backward adds their gradient behind the GEMM that writes that activation's gradient (bwd[0]).  Train plans;
+    // the buffers sit at the end of the workspace, (lambda, tau) = M2F_BUF_SUPCON
+    bool supcon_on = false;
+    float* supcon_ws = nullptr;          // m2f_supcon_ws_floats(T, cls_hidden) floats
+    float* supcon_rows = nullptr;        // [T, 4] row terms (lse, n, l, w l); w l reduced into the tail's fourth float
+    float* supcon_dfeat = nullptr;       // [T, pad8(cls_hidden)]: the unnormalised gradient w.r.t. the stored activation
+    float* supcon_scale = nullptr;       // [1]: what the finalize launch multiplies dlogits by (1 / den, or 1)
+    float* supcon_dh = nullptr;          // the chain's gradient of that activation (bwd[0]'s output) ...
+    float supcon_gate = 1.f;             // ... and its gate scale (the dropout scale when the activation carries a dropout site)
     // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
     // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace
     bool crf_on = false;

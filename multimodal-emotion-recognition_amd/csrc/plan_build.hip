@@ -346,6 +346,7 @@ struct Builder {
         }
         float* logits = ar.f((size_t)T * C);
         P.bufs[M2F_BUF_LOGITS] = logits;
+        P.bufs[M2F_BUF_FEATURES] = hbuf[nhid - 1];
         {
             const LinP& lp = P.pm.cls[nhid];
             GemmProblem g = gp_make(hbuf[nhid - 1], hidp, W(lp.w), hid, T, C, hid, logits, C);
@@ -376,6 +377,8 @@ struct Builder {
             GemmProblem g = gp_make(dlogits, C, W(lp.w), hid, T, hid, C, dh, hidp);
             g.gate = hbuf[nhid - 1]; g.ldgate = hidp; g.gate_scale = hsite[nhid - 1] ? gs : 1.f;
             chain_b.push_back(op_gemm(M2F_LAYOUT_NN, g));
+            // (m2f_plan_supcon adds its gradient to this launch's output, the first of the backward list, under the same gate)
+            P.crit.supcon_dh = dh; P.crit.supcon_gate = g.gate_scale;
         }
         for (int j = nhid - 1; j >= 1; --j) {
             const LinP& lp = P.pm.cls[j];
@@ -614,6 +617,9 @@ int mark_unread_fp32(m2f_plan& P, const float* wsf, size_t ws_floats, const std:
     mark(static_cast<const float*>(P.bufs[M2F_BUF_FAM0_OUT]), T, pad8(P.cfg.d_fam), pad8(P.cfg.d_fam));
     mark(static_cast<const float*>(P.bufs[M2F_BUF_DTEXT]), T, pad8(P.cfg.d_text), pad8(P.cfg.d_text));
     mark(static_cast<const float*>(P.bufs[M2F_BUF_DAUDIO]), T, pad8(P.cfg.d_audio), pad8(P.cfg.d_audio));
+    // (m2f_plan_supcon's add launch reads and rewrites the fp32 gradient of the classifier's last hidden activation; the activation itself
+    // is a gate operand, marked with its launch)
+    if (P.train) mark(P.crit.supcon_dh, T, pad8(P.cfg.cls_hidden), (size_t)P.cfg.cls_hidden);
     auto operand = [&](const GemmOperand& o, size_t rows_hint, bool launch16) {
         for (int sg = 0; sg < 2; ++sg)
             if (o.k[sg] > 0 && o.p[sg]) {
@@ -1115,6 +1121,13 @@ int build_plan(m2f_plan& P, char* ws_base) {
     P.bufs[M2F_BUF_PARTNER] = P.train ? bld.ar.alloc<int32_t>((size_t)T) : nullptr;
     P.bufs[M2F_BUF_RDROP] = P.train ? bld.ar.f(1) : nullptr;
     P.crit.rdrop_kl = P.train ? bld.ar.f((size_t)T) : nullptr;
+    // the supervised contrastive criterion (m2f_plan_supcon), train plans only: (lambda, tau), the kernels' workspace, the row terms, the
+    // gradient w.r.t. the stored activation and the step's scale - behind everything again
+    P.bufs[M2F_BUF_SUPCON] = P.train ? bld.ar.f(2) : nullptr;
+    P.crit.supcon_ws = P.train ? bld.ar.f(m2f_supcon_ws_floats(T, c.cls_hidden)) : nullptr;
+    P.crit.supcon_rows = P.train ? bld.ar.f((size_t)T * 4) : nullptr;
+    P.crit.supcon_dfeat = P.train ? bld.ar.f((size_t)T * Builder::pad8(c.cls_hidden)) : nullptr;
+    P.crit.supcon_scale = P.train ? bld.ar.f(1) : nullptr;
     P.built.ws_used = bld.ar.off;
     if (P.prec == M2F_PREC_BF16 && ws_base != nullptr) {
         const float* wsf = reinterpret_cast<const float*>(ws_base);

@@ -480,13 +480,14 @@ class DataParallelStep:
 
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
                  use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None,
-                 rdrop=None) -> torch.Tensor:
+                 rdrop=None, supcon=None) -> torch.Tensor:
         """teacher_logits, distill=(alpha, temperature): as ``M2FNet.train_step`` - the rank's step runs the distillation criterion
         (one denominator: the exchange, the global den and the micro-batch group hold as they are); both or neither.
         focal_gamma: as ``M2FNet.train_step`` - the rank's step runs the focal form of its criterion (the denominator is untouched).
         rdrop (alpha): as ``M2FNet.train_step`` - the rank runs ITS shard twice in one plan (the twins are made after sharding: a pair
         never crosses ranks) under the R-Drop criterion; the denominator is the labelled weight of both views, and the all-reduced tail
         carries the global KL share (``model.rdrop_terms()``).  Refused beside teacher_logits / distill, focal_gamma or a CRF by name.
+        supcon: refused by name (ValueError): the contrast set of ``M2FNet.train_step(supcon=)`` is the whole batch, a shard's is not.
         sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
@@ -494,6 +495,9 @@ class DataParallelStep:
         from . import runtime
         from .distill import resolve_distill_args
         _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
+        if supcon is not None:
+            raise ValueError("DataParallelStep: supcon is refused (the supervised contrastive criterion contrasts the whole batch; a "
+                             "per-shard contrast set is a different objective - run it on one device through M2FNet.train_step)")
         alpha = runtime.check_rdrop_args("DataParallelStep", rdrop, teacher_logits, distill, focal_gamma, self.crf)
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")

@@ -830,6 +830,38 @@ def cross_entropy_rdrop(logits: torch.Tensor, partner: torch.Tensor, labels: tor
     return out, dl
 
 
+def supcon(features: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch.Tensor] = None, weight: float = 1.0,
+           temperature: float = 0.1, n_classes: Optional[int] = None):
+    """The supervised contrastive kernels on their own (m2f_supcon; csrc/supcon.hip holds the definition).  features: fp32 [N, D], rows
+    contiguous (a row stride > D is read in place); labels int64 [N] (a label outside [0, n_classes) = not contrasted); class_w fp32
+    [n_classes] or None; n_classes defaults to class_w's length, else to 1 + the largest label (one host read).  -> (row_terms [N, 4] =
+    (lse_i, n_i, l_i, w_y l_i), dfeatures [N, D] = the gradient of ``weight * sum_i w_y l_i`` w.r.t. features, unnormalised).  Rows
+    without a valid label or with a zero norm, and anchors without a positive, give exactly 0.  weight finite >= 0, temperature finite
+    > 0 (ValueError otherwise).  Exact fp32, no atomics: the same bits at every call."""
+    w, t = runtime.check_supcon_pair((weight, temperature), "(weight, temperature)", "supcon")
+    runtime.require_gpu()
+    if features.dim() != 2 or features.dtype != torch.float32 or features.stride(1) != 1 or features.stride(0) < features.shape[1]:
+        raise ValueError(f"supcon: features must be fp32 [N, D] with contiguous rows (got {tuple(features.shape)} {features.dtype}, "
+                         f"strides {features.stride()})")
+    N, D = features.shape
+    if labels.shape != (N,) or labels.dtype != torch.int64 or labels.device != features.device:
+        raise ValueError(f"supcon: labels must be int64 [{N}] on {features.device} (got {tuple(labels.shape)} {labels.dtype} on {labels.device})")
+    if class_w is not None:
+        class_w = class_w.to(device=features.device, dtype=torch.float32).contiguous()
+    C = int(n_classes) if n_classes is not None else (class_w.numel() if class_w is not None else max(int(labels.max()) + 1, 1))
+    if class_w is not None and class_w.numel() < C:
+        raise ValueError(f"supcon: class_w holds {class_w.numel()} weights for {C} classes")
+    dev = features.device
+    scratch = torch.empty(int(lib().m2f_supcon_scratch_floats(N, D)), dtype=torch.float32, device=dev)
+    rows = torch.empty(N, 4, dtype=torch.float32, device=dev)
+    dfeat = torch.empty(N, D, dtype=torch.float32, device=dev)
+    hyper = torch.tensor([w, t], dtype=torch.float32).to(dev, non_blocking=True)
+    labels = labels.contiguous()
+    check(lib().m2f_supcon(N, D, C, ptr(features), features.stride(0), ptr(labels), ptr(class_w), ptr(hyper), ptr(scratch), ptr(rows),
+                           ptr(dfeat), D, stream_ptr()), "m2f_supcon")
+    return rows, dfeat
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
                       need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,

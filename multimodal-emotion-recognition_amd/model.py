@@ -622,6 +622,8 @@ class M2FNet(nn.Module):
         # (detached: the staging copies are plumbing, autograd reaches the inputs through _Anchor)
         det = lambda x: x.detach() if isinstance(x, torch.Tensor) else x          # noqa: E731
         plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask, speakers=ids)
+        if plan.train:
+            plan.set_supcon(None)                  # (the criterion is the caller's here: nothing joins the backward at the hidden features)
         if want_bwd:
             out = _Anchor.apply(eng.anchor, text, audio, self, plan)
             plan.hold(out.grad_fn)
@@ -681,7 +683,8 @@ class M2FNet(nn.Module):
                    class_weights: Optional[torch.Tensor] = None, normalise: bool = True,
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
                    distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
-                   focal_gamma: Optional[float] = None, crf=None, rdrop: Optional[float] = None) -> torch.Tensor:
+                   focal_gamma: Optional[float] = None, crf=None, rdrop: Optional[float] = None,
+                   supcon: Optional[Tuple[float, float]] = None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -716,10 +719,22 @@ class M2FNet(nn.Module):
         warm-up replays the captured step.  With dropout 0 or in eval mode the call is allowed: the twins then agree, the term and its
         gradient are exactly zero.  None (default): today's launches, bit for bit; R-Drop and plain calls mix freely on one model.
         Refused (ValueError naming the pair, before any launch) beside teacher_logits / distill, focal_gamma or crf.  After such a
-        step ``last_attention()`` returns the 2B dialogues' maps, view 0 first."""
+        step ``last_attention()`` returns the 2B dialogues' maps, view 0 first.
+        supcon (weight, temperature; weight finite and >= 0, temperature finite and > 0): the supervised contrastive criterion (Khosla et
+        al. 2020) on the classifier's last hidden activation ``h`` - post-ReLU, and post-dropout in train mode: what the final Linear
+        reads, ``last_features()``.  Over V = the labelled utterances of ALL dialogues of the batch with ``||h|| > 0``, ``z = h / ||h||``:
+        ``l_i = logsumexp_{a in V, a != i} (z_i . z_a / temperature) - mean_{p: y_p = y_i, p != i} (z_i . z_p / temperature)`` (0 for an
+        utterance without a positive), and ``weight * w_y * l_i`` joins the utterance's numerator over the one denominator:
+        ``loss = CE + weight * sum(w l) / sum(w)``.  Exact-fp32 kernels in both precision modes; the gradient enters the backward at the
+        hidden activation's gradient.  ``supcon_terms()`` gives the two shares.  The pair lives on the device (uploaded only when it
+        changed): a weight schedule replays the captured step; weight 0 gives the plain step's loss and gradients.  None (default):
+        today's launches, bit for bit; contrastive and plain calls mix freely on one model.  Under gradient accumulation each
+        micro-batch contrasts within itself.  Refused (ValueError naming the pair, before any launch) beside teacher_logits / distill,
+        focal_gamma, crf or rdrop."""
         from .crf import check_step_args
         from .distill import resolve_distill_args
         alpha = runtime.check_rdrop_args("M2FNet.train_step", rdrop, teacher_logits, distill, focal_gamma, crf)
+        con = runtime.check_supcon_args("M2FNet.train_step", supcon, teacher_logits, distill, focal_gamma, crf, rdrop)
         check_step_args("M2FNet.train_step", crf, self.m2f_config.cls_out, class_weights, teacher_logits, distill, focal_gamma,
                         label_smoothing, accumulating=self._engine is not None and self._engine.accumulate)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
@@ -736,12 +751,14 @@ class M2FNet(nn.Module):
         B, L = mask.shape
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
+        if con is not None:
+            self._supcon_weight = con[0]
 
         def body():
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha)
+            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha, con)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -771,12 +788,22 @@ class M2FNet(nn.Module):
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
-    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None) -> None:
+    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None, supcon=None) -> None:
         """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
         temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
         plan maps the teacher rows as it mapped the batch).  `crf` (a LinearChainCRF; the callers refused every other criterion argument
         beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains.
-        `rdrop` (alpha; likewise alone): the R-Drop criterion over the doubled batch `set_inputs` has just placed."""
+        `rdrop` (alpha; likewise alone): the R-Drop criterion over the doubled batch `set_inputs` has just placed.
+        `supcon` ((weight, temperature); likewise alone): the plain criterion plus the contrastive term on the hidden features."""
+        if plan.train and supcon is None:
+            plan.set_supcon(None)
+        if supcon is not None:
+            plan.set_crf(None)
+            plan.set_focal(None)
+            plan.distill(False)
+            plan.set_rdrop(None)
+            plan.set_supcon(supcon)
+            return
         if rdrop is not None:
             plan.set_crf(None)
             plan.set_focal(None)
@@ -965,6 +992,36 @@ class M2FNet(nn.Module):
         t = eng.flat_grad_ext[n: n + 4]
         kl = t[3] / t[1]
         return t[2] / t[1] - getattr(self, "_rdrop_alpha", 0.0) * kl, kl
+
+    def supcon_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(ce, con)`` of the last ``train_step(supcon=(weight, temperature))`` as device scalars: the cross-entropy share of its
+        loss and the contrastive term per unit of labelled weight WITHOUT the weight - ``ce + weight * con`` is the loss.  Read from the
+        criterion tail (den, num and, in its fourth float, the sum of ``w_y * l``, reduced in a fixed order): with accumulation on they
+        cover the group's micro-batches.  The weight is the last step's."""
+        eng = self.engine()
+        eng.ensure_grad()
+        n = eng.flat.numel()
+        t = eng.flat_grad_ext[n: n + 4]
+        con = t[3] / t[1]
+        return t[2] / t[1] - getattr(self, "_supcon_weight", 0.0) * con, con
+
+    def last_features(self) -> torch.Tensor:
+        """The classifier's last hidden activation of the most recent ``forward`` / ``train_step`` / ``eval_step`` of this model as a
+        fresh, detached ``[B, L, cls_hidden]`` tensor in the caller's dialogue order, whatever bucket, packed or long-dialogue plan ran:
+        post-ReLU and - in train mode with dropout > 0 - post-dropout, the operand the final Linear reads and what ``train_step(supcon=)``
+        contrasts.  Pad slots are 0.  No second forward.  Raises RuntimeError when no forward has run, or the plan that ran it was
+        destroyed or has run again since."""
+        eng = self._engine
+        if eng is None or eng.last is None:
+            raise RuntimeError("M2FNet.last_features: no forward has run on this model (or it was moved since)")
+        plan, version, dst, valid, shape = eng.last
+        if not plan.handle:
+            raise RuntimeError("M2FNet.last_features: the plan holding the activations of the last forward was destroyed "
+                               "(evicted from the plan cache)")
+        if plan.version != version:
+            raise RuntimeError("M2FNet.last_features: the activations of the last forward were overwritten by a later forward "
+                               "of the same plan")
+        return plan.features(dst, valid, shape).detach()
 
     def invalidate_shadows(self) -> None:
         """Call after writing parameters in a way torch's version counters do not see (``p.data`` edits, writes through

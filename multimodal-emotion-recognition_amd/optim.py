@@ -5,6 +5,7 @@
 * ``M2FFocalLoss``         = the same with every labelled row's term scaled by ``(1 - p_y)^gamma`` (focal loss; its own kernel).
 * ``M2FRDropLoss``         = the same over a batch given twice, plus the symmetric KL divergence between each utterance's two predictions
   (R-Drop; its own kernel).
+* ``M2FSupConLoss``        = the supervised contrastive loss over utterance features (Khosla et al. 2020; its own exact-fp32 kernels).
 * ``FusedAdam``            = ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` (src/train.py:56): coupled
   L2, bias-corrected; ONE kernel over the flat parameter / gradient / moment buffers instead of ~130 per-tensor
   updates.  ``state_dict()`` keeps torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` /
@@ -211,6 +212,57 @@ class M2FRDropLoss(M2FCrossEntropyLoss):
         w = self.weight.to(device=logits.device, dtype=torch.float32) if self.weight is not None else None
         loss, self.last_terms = _RDropFunction.apply(logits.reshape(-1, C).contiguous().float(), partner, target.reshape(-1).contiguous(), w,
                                                      self.label_smoothing, alpha)
+        return loss
+
+
+class _SupConFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat2d, target1d, weight, temperature, n_classes):
+        rows, dfeat = F.supcon(feat2d, target1d, weight, 1.0, temperature, n_classes)
+        w = torch.ones(n_classes, dtype=torch.float32, device=feat2d.device) if weight is None else weight
+        ok = (target1d >= 0) & (target1d < n_classes)
+        den = (w[target1d.clamp(0, n_classes - 1)] * ok).sum()
+        ctx.save_for_backward(dfeat, den)
+        ctx.mark_non_differentiable(rows)
+        return rows[:, 3].sum() / den, rows
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        dfeat, den = ctx.saved_tensors
+        return dfeat * (grad_out / den), None, None, None, None
+
+
+class M2FSupConLoss(nn.Module):
+    """Supervised contrastive loss (Khosla et al. 2020) over utterance features, the term ``M2FNet.train_step(supcon=)`` adds inside
+    the step, on the autograd surface: features ``[N, D]`` or ``[B, L, D]`` (fp32), targets ``[N]`` or ``[B, L]`` with ``ignore_index``
+    (-1, the padding label) for rows that are not contrasted.  With V = the labelled rows of a non-zero norm, ``z = h / ||h||``:
+    ``l_i = logsumexp_{a in V, a != i}(z_i . z_a / temperature) - mean_{p in V, p != i, y_p = y_i}(z_i . z_p / temperature)`` (0 without a
+    positive), and the loss is ``sum_i w_{y_i} l_i / sum_i w_{y_i}`` over the LABELLED rows - the criterion's own denominator, so
+    ``M2FCrossEntropyLoss(...)(logits, y) + weight * M2FSupConLoss(...)(h, y)`` is the step's loss.  One family of exact-fp32 kernels
+    (``functional.supcon``).  ``temperature`` (finite, > 0) is a plain attribute, read at every call.  ``last_terms`` holds the per-row
+    ``(lse, n, l, w l)`` of the last call on the device.  n_classes: the weight's length, else 1 + the largest target (one host read);
+    pass it to avoid the read."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -1, temperature: float = 0.1,
+                 n_classes: Optional[int] = None):
+        super().__init__()
+        if ignore_index != -1:
+            raise ValueError("M2FSupConLoss: ignore_index must be -1 (the padding label the kernels skip)")
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+        self.temperature = runtime.check_supcon_pair((0.0, temperature), "temperature", "M2FSupConLoss")[1]
+        self.n_classes = n_classes
+        self.last_terms = None
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        t = runtime.check_supcon_pair((0.0, self.temperature), "temperature", "M2FSupConLoss")[1]
+        if input.dim() not in (2, 3) or target.shape != input.shape[:-1]:
+            raise ValueError(f"M2FSupConLoss: features [N, D] / [B, L, D] with targets [N] / [B, L] expected, got {tuple(input.shape)} "
+                             f"and {tuple(target.shape)}")
+        w = self.weight.to(device=input.device, dtype=torch.float32) if self.weight is not None else None
+        tgt = target.reshape(-1).contiguous()
+        C = self.n_classes if self.n_classes is not None else (w.numel() if w is not None else max(int(tgt.max()) + 1, 1))
+        loss, self.last_terms = _SupConFunction.apply(input.reshape(-1, input.shape[-1]).contiguous().float(), tgt, w, t, C)
         return loss
 
 

@@ -27,7 +27,8 @@ F32, BF16 = 0, 1
 PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16": BF16}
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
- BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL, BUF_PARTNER, BUF_RDROP) = range(24)
+ BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL, BUF_PARTNER, BUF_RDROP, BUF_SUPCON,
+ BUF_FEATURES) = range(26)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -188,6 +189,7 @@ SIGNATURES = {
     "m2f_plan_distill": (c_int, [c_void_p, c_int]),
     "m2f_plan_focal": (c_int, [c_void_p, c_int]),
     "m2f_plan_rdrop": (c_int, [c_void_p, c_int]),
+    "m2f_plan_supcon": (c_int, [c_void_p, c_int]),
     "m2f_plan_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_stream_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
@@ -248,6 +250,9 @@ SIGNATURES = {
     "m2f_crf_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_cross_entropy_rdrop": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "m2f_supcon_scratch_floats": (c_int64, [c_int, c_int]),
+    "m2f_supcon": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                           c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -403,6 +408,38 @@ def check_rdrop_args(who: str, rdrop, teacher_logits=None, distill=None, focal_g
             raise ValueError(f"{who}: rdrop and {name} do not combine (the R-Drop criterion has no "
                              f"{'distillation' if name in ('teacher_logits', 'distill') else 'focal' if name == 'focal_gamma' else 'CRF'} form)")
     return alpha
+
+
+def check_supcon_pair(supcon, name: str = "supcon", who: str = "train_step") -> Tuple[float, float]:
+    """(weight, temperature) of the supervised contrastive criterion as floats; ValueError naming the argument unless it is a pair of
+    numbers with weight finite and >= 0 and temperature finite and > 0.  A host function: no GPU needed."""
+    if not isinstance(supcon, (tuple, list)) or len(supcon) != 2:
+        raise ValueError(f"{who}: {name} must be a pair (weight, temperature), got {supcon!r}")
+    w, t = supcon
+    for v in (w, t):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{who}: {name} must be a pair of numbers (weight, temperature), got {supcon!r}")
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"{who}: {name} weight must be a finite number >= 0, got {w!r}")
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"{who}: {name} temperature must be a finite number > 0, got {t!r}")
+    return float(w), float(t)
+
+
+def check_supcon_args(who: str, supcon, teacher_logits=None, distill=None, focal_gamma=None, crf=None,
+                      rdrop=None) -> Optional[Tuple[float, float]]:
+    """`supcon=` of a step as (weight, temperature) floats (None: off).  The supervised contrastive criterion rides on the plain cross
+    entropy only: given beside teacher_logits, distill, focal_gamma, crf or rdrop it is refused with a ValueError that names the pair,
+    before any launch.  A host function: no GPU needed."""
+    if supcon is None:
+        return None
+    pair = check_supcon_pair(supcon, "supcon", who)
+    forms = {"teacher_logits": "distillation", "distill": "distillation", "focal_gamma": "focal", "crf": "CRF", "rdrop": "R-Drop"}
+    for name, other in (("teacher_logits", teacher_logits), ("distill", distill), ("focal_gamma", focal_gamma), ("crf", crf),
+                        ("rdrop", rdrop)):
+        if other is not None:
+            raise ValueError(f"{who}: supcon and {name} do not combine (the supervised contrastive criterion has no {forms[name]} form)")
+    return pair
 
 
 def rdrop_partner(pairs: int, l: int, T: int, L: Optional[int] = None, dst: Optional[torch.Tensor] = None,
@@ -563,6 +600,13 @@ class Plan:
         self._rdrop = False
         self.alpha_host = None                # host mirror of rdrop_alpha, as hyper_host
         self._partner_key = None              # what the padded twin map in partner_in was built for: (pairs, l); packed plans: never kept
+        # the supervised contrastive criterion (train plans; `supcon`): the (weight, temperature) pair its kernels read on the device
+        self.supcon_hyper = self._view(BUF_SUPCON, (2,), torch.float32) if train else None
+        self._supcon = False
+        self.supcon_host = None               # host mirror of supcon_hyper, as hyper_host
+        # the classifier's last hidden activation as stored, in the plan's token rows (what `supcon` contrasts; `features`)
+        hid = cfg.cls_hidden
+        self._features = self._view(BUF_FEATURES, (self.T, pad8(hid)) if self.packed else (B, L, pad8(hid)), torch.float32)[..., :hid]
         self._fam0_out = (self._view(BUF_FAM0_OUT, (self.T, pad8(cfg.d_fam)) if self.packed else (B, L, pad8(cfg.d_fam)),
                                      torch.float32)[..., : cfg.d_fam] if cfg.fam_enabled else None)
         # shape of the batch last handed to set_inputs: a plan may be larger than the batch it runs (shape buckets), the
@@ -599,6 +643,17 @@ class Plan:
         if self.packed:
             return self._unpack(self._dlogits)
         return self._dlogits[: self.in_B, : self.in_L]
+
+    def features(self, dst=None, valid=None, shape=None) -> torch.Tensor:
+        """The classifier's last hidden activation of the plan's last forward as a fresh [b, l, cls_hidden] tensor in the caller's
+        dialogue order (post-ReLU, and post-dropout in train mode: the operand the final Linear reads); pad slots are 0.  dst / valid /
+        shape: the row map and batch shape of the forward meant (default: the last `set_inputs`)."""
+        b, l = (self.in_B, self.in_L) if shape is None else shape
+        if self.packed:
+            dst, valid = (self._dst, self._valid) if dst is None else (dst, valid)
+            return self._features[dst] * valid[..., None].to(self._features.dtype)
+        pad = self.keypad_in.view(self.B, self.L)[:b, :l].bool()
+        return self._features[:b, :l].masked_fill(pad[..., None], 0.0)
 
     @property
     def fam0_out(self) -> Optional[torch.Tensor]:
@@ -847,6 +902,27 @@ class Plan:
         if alpha != self.alpha_host:
             self.rdrop_alpha.copy_(torch.tensor([alpha], dtype=torch.float32), non_blocking=True)
             self.alpha_host = alpha
+
+    def supcon(self, on: bool) -> None:
+        """m2f_plan_supcon: the NEXT losses / steps add the supervised contrastive term on the hidden features (on) / do not (off).
+        A change drops the captured steps; a change of the pair does not.  Neither writes nor waits.  The distillation, focal, R-Drop
+        and CRF switches must be off (the C entry refuses by name)."""
+        on = bool(on)
+        if on == self._supcon:
+            return
+        check(lib().m2f_plan_supcon(self._h(), int(on)), "m2f_plan_supcon")
+        self._supcon = on
+
+    def set_supcon(self, pair: Optional[Tuple[float, float]]) -> None:
+        """The contrastive term of the plan's next step: (weight, temperature) - numbers, checked by the caller -, or (None) not.  The
+        pair is uploaded only when it differs from the host mirror of the last upload."""
+        self.supcon(pair is not None)
+        if pair is None:
+            return
+        pair = (float(pair[0]), float(pair[1]))
+        if pair != self.supcon_host:
+            self.supcon_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
+            self.supcon_host = pair
 
     def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
         """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's

@@ -266,6 +266,76 @@ class _RDropLog:
         return {"Train/CE": self.ce / (step + 1), "Train/RDrop_KL": self.kl / (step + 1)}
 
 
+SUPCON_KEYS = ("enabled", "weight", "temperature", "warmup_steps")
+
+
+def supcon_settings(cfg):
+    """`runtime.supcon` = {enabled: False, weight: 0.1, temperature: 0.1, warmup_steps: 0}: train() adds the supervised contrastive term
+    on the classifier's hidden features inside the step (M2FNet.train_step(supcon=)).  -> None when the block is absent or disabled,
+    else {weight, temperature, warmup_steps}.  Checked on the host before the GPU is touched: needs runtime.fused_step: True and
+    solver.loss_fn: CE (the term rides on the plain cross entropy), no runtime.distill, no runtime.rdrop and one process (a shard's
+    contrast set is a different objective)."""
+    from mer_amd.runtime import check_supcon_pair
+    block = _runtime(cfg, "supcon", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.supcon must be a mapping {{{', '.join(SUPCON_KEYS)}}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - set(SUPCON_KEYS))
+    if unknown:
+        raise ValueError(f"runtime.supcon: unknown key(s) {unknown} ({', '.join(SUPCON_KEYS)})")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.supcon.enabled must be true or false (got {enabled!r})")
+    weight, temperature = check_supcon_pair((block.get("weight", 0.1), block.get("temperature", 0.1)), "(weight, temperature)", "runtime.supcon")
+    warm = block.get("warmup_steps", 0)
+    if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
+        raise ValueError(f"runtime.supcon.warmup_steps must be an integer >= 0 (got {warm!r})")
+    if not enabled:
+        return None
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.supcon.enabled needs runtime.fused_step: True (the supervised contrastive criterion lives in the train step)")
+    solver = cfg.get("solver", None) if isinstance(cfg, dict) else getattr(cfg, "solver", None)
+    loss_fn = None if solver is None else (solver.get("loss_fn", "CE") if hasattr(solver, "get") else getattr(solver, "loss_fn", "CE"))
+    if loss_fn not in (None, "CE"):
+        raise ValueError(f"runtime.supcon.enabled needs solver.loss_fn: CE (got {loss_fn!r}: the supervised contrastive criterion has no focal or CRF form)")
+    if resolve_distill(cfg) is not None:
+        raise ValueError("runtime.supcon.enabled does not combine with runtime.distill.enabled (the supervised contrastive criterion has no distillation form)")
+    if rdrop_settings(cfg) is not None:
+        raise ValueError("runtime.supcon.enabled does not combine with runtime.rdrop.enabled (the supervised contrastive criterion has no R-Drop form)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("runtime.supcon.enabled runs in one process (the data-parallel step refuses supcon: a shard's contrast set is a different objective)")
+    return {"weight": weight, "temperature": temperature, "warmup_steps": warm}
+
+
+def _supcon_kw(model, global_step: int):
+    """{supcon: (weight, temperature)} of optimizer step `global_step` for train_step when main() hung the runtime.supcon settings on
+    the model (`model.supcon`), else nothing - the calls of a run without it are today's.  warmup_steps = n: weight * (step + 1) / n
+    until n."""
+    r = getattr(model, "supcon", None)
+    if r is None:
+        return {}
+    n = r["warmup_steps"]
+    return {"supcon": (r["weight"] * min(1.0, (global_step + 1) / n) if n > 0 else r["weight"], r["temperature"])}
+
+
+class _SupConLog:
+    """Running means of the two shares of the loss for wandb: {"Train/CE", "Train/SupCon"} beside Train/Running_loss (CE + weight *
+    SupCon at a constant weight).  Reads `model.supcon_terms()` only when something is logged."""
+
+    def __init__(self, model, on: bool):
+        self.model, self.on = model, on and getattr(model, "supcon", None) is not None
+        self.ce = self.con = 0.0
+
+    def __call__(self, step: int):
+        if not self.on:
+            return {}
+        ce, con = self.model.supcon_terms()
+        self.ce += ce.item()
+        self.con += con.item()
+        return {"Train/CE": self.ce / (step + 1), "Train/SupCon": self.con / (step + 1)}
+
+
 def _distill_kw(model, text, audio, padding_mask):
     """{teacher_logits, distill} of this batch for train_step / DataParallelStep when the model carries a Distiller, else nothing."""
     d = getattr(model, "distiller", None)
@@ -744,6 +814,7 @@ def main(config=None):
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
     resolve_distill(config)
     rdrop_settings(config)
+    supcon_settings(config)
     focal_gamma_setting(config)
     crf_settings(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
@@ -822,6 +893,7 @@ def main(config=None):
                                                                              n_head=config.model.AUDIO.n_head))
     attach_distiller(config, model, device)
     object.__setattr__(model, "rdrop", rdrop_settings(config))       # (None: off; train() passes rdrop= on in every branch)
+    object.__setattr__(model, "supcon", supcon_settings(config))     # (None: off; train() passes supcon= on to train_step)
     criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config), crf=crf_settings(config))
     attach_crf(model, criterion)
     optimizer = build_optimizer(config, model)
@@ -972,6 +1044,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         return _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log, device, k, fused, use_graph, dp_step)
     running = 0.0
     rdrop_log = _RDropLog(model, bool(wandb_log))
+    supcon_log = _SupConLog(model, bool(wandb_log))
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
         text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
@@ -979,6 +1052,9 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         rdrop = _rdrop_kw(model, epoch * len(dl_train) + step)
         if rdrop and not fused:
             raise ValueError("runtime.rdrop needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+        supcon = _supcon_kw(model, epoch * len(dl_train) + step)
+        if supcon and (not fused or dp_step is not None):
+            raise ValueError("runtime.supcon needs runtime.fused_step: True, the M2FCrossEntropyLoss criterion and one process")
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
@@ -990,16 +1066,16 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, optimizer=optimizer,
                                         **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                        **_crit_kw(criterion), **rdrop)
+                                        **_crit_kw(criterion), **rdrop, **supcon)
                 _crf_step(criterion)
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                               **_grad_norm_log(optimizer), **rdrop_log(step)})
+                               **_grad_norm_log(optimizer), **rdrop_log(step), **supcon_log(step)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop)
+                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop, **supcon)
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
@@ -1011,7 +1087,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step)})
+                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step)})
     return running / len(dl_train)
 
 
@@ -1028,9 +1104,13 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
     n_groups = (len(dl_train) + k - 1) // k
     running = 0.0
     rdrop_log = _RDropLog(model, bool(wandb_log))
+    supcon_log = _SupConLog(model, bool(wandb_log))
     progress = tqdm(enumerate(group_batches(dl_train, k)), total=n_groups, desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, group in progress:
         rdrop = _rdrop_kw(model, epoch * n_groups + step)     # (one alpha per optimizer step: the group's shares add up)
+        supcon = _supcon_kw(model, epoch * n_groups + step)   # (likewise one weight; each micro-batch contrasts within itself)
+        if supcon and dp_step is not None:
+            raise ValueError("runtime.supcon needs one process (the data-parallel step refuses supcon)")
         if dp_step is None:
             optimizer.zero_grad()                        # (every .grad None: the first micro-batch overwrites, den / num too)
         for j, batch in enumerate(group):
@@ -1042,7 +1122,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
             else:
                 model.train_step(text, audio, padding_mask, emotion, normalise=False, use_graph=use_graph,
                                  **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                 **_crit_kw(criterion), **rdrop)
+                                 **_crit_kw(criterion), **rdrop, **supcon)
         if dp_step is None:
             terms = model.loss_terms()
             optimizer.grad_scale = terms[1:2]            # the group's den: gradients / den = the mean over every valid utterance
@@ -1052,7 +1132,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step,
-                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step)})
+                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step)})
     if dp_step is None:
         optimizer.grad_scale = None
     return running / max(n_groups, 1)
