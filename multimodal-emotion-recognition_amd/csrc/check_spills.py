@@ -50,7 +50,10 @@ crf = len(sys.argv) > 2 and sys.argv[1] == "--crf"
 # --supcon <remarks>: the supervised contrastive kernels (supcon.hip) - a tile's MFMA accumulators, the chunk staged one step ahead and a
 # row's terms stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
 supcon = len(sys.argv) > 2 and sys.argv[1] == "--supcon"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon) else sys.argv[1]
+# --aux <remarks>: the auxiliary label head's kernels (aux_head.hip) - a row's 16-byte pieces, the sixteen logits, the row's terms and the
+# sixteen accumulators of a parameter-gradient lane stay in registers through unrolled loops with static indices: zero scratch, no spills
+aux = len(sys.argv) > 2 and sys.argv[1] == "--aux"
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -106,6 +109,16 @@ if supcon:
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('AGPRs')} AGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if aux:
+    kernels = [r for r in rows if "m2f_aux_" in r["name"]]
+    # rows and join for 1, 2 and 4 pieces per lane, the tail with and without accumulation, the gradient's partials and their reduce
+    if len(kernels) != 10:
+        sys.exit(f"check_spills: expected the ten m2f_aux_ kernels in {path}, found {len(kernels)} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
               f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
     sys.exit(1 if bad else 0)
 if attn:

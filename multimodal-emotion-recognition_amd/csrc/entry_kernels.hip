@@ -658,6 +658,74 @@ int m2f_supcon(int N, int D, int C, const float* features, int ld, const int64_t
     return 0;
 }
 
+int64_t m2f_aux_head_scratch_floats(int N, int D, int A) { return (int64_t)m2f_aux_head_ws_floats(N, D, A); }
+
+// what every stand-alone entry of the auxiliary head asks of its shapes and feature rows; nullptr: fine
+static const char* aux_head_shape_error(int N, int D, int A, const float* features, int ld, const float* params, const float* scratch) {
+    if (N < 1 || D < 1 || D > 1024) return "N >= 1 and 1 <= D <= 1024 required";
+    if (A < 2 || A > 16) return "2 <= A <= 16 auxiliary classes required";
+    if (!features || !params || !scratch) return "NULL features / params / scratch";
+    if (ld < ((D + 3) & ~3) || (ld & 3) || (reinterpret_cast<uintptr_t>(features) & 15)) return "feature rows must be 16-byte aligned: ld a multiple of 4, >= D rounded up to 4";
+    if ((reinterpret_cast<uintptr_t>(params) & 15) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return "params and scratch must be 16-byte aligned";
+    return nullptr;
+}
+
+int m2f_aux_head(int N, int D, int A, int C, const float* features, int ld, const float* params, const int64_t* labels,
+                 const int64_t* aux_labels, const float* class_w, const float* hyper_dev, float* scratch, float* aux_logits,
+                 float* row_terms, float* dfeatures, int ldd, float* dparams, m2f_stream_t stream) {
+    if (const char* e = aux_head_shape_error(N, D, A, features, ld, params, scratch)) return fail(std::string("m2f_aux_head: ") + e);
+    if (!labels || !aux_labels || !hyper_dev || !aux_logits || !row_terms || !dfeatures) return fail("m2f_aux_head: NULL labels / aux_labels / hyper_dev / aux_logits / row_terms / dfeatures");
+    if (C < 1 || ldd < ((D + 3) & ~3) || (ldd & 3) || (reinterpret_cast<uintptr_t>(dfeatures) & 15)) return fail("m2f_aux_head: C >= 1 and 16-byte aligned dfeatures rows (ldd a multiple of 4, >= D rounded up to 4) required");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* g = scratch;
+    float* part = g + (size_t)N * 16 + (((size_t)N + 3) & ~(size_t)3);
+    AuxHeadArgs a;
+    a.feat = features; a.N = N; a.D = D; a.ld = ld; a.params = params; a.A = A; a.labels = labels; a.C = C; a.class_w = class_w;
+    a.aux_labels = aux_labels; a.hyper = hyper_dev; a.aux_logits = aux_logits; a.ldu = A; a.g = g; a.row_term = row_terms;
+    M2F_HIP(m2f_launch_aux_rows(a, s));
+    M2F_HIP(m2f_launch_aux_join(dfeatures, ldd, nullptr, 0, g, 16, params, A, N, D, nullptr, hyper_dev, 1.f, 0, 0, ShadowMap{nullptr, nullptr, 0}, s));
+    if (dparams) M2F_HIP(m2f_launch_aux_param_grad(features, ld, g, 16, A, N, D, part, nullptr, hyper_dev, dparams, s));
+    return 0;
+}
+
+int m2f_aux_head_forward(int N, int D, int A, const float* features, int ld, const float* params, float* scratch, float* logits,
+                         m2f_stream_t stream) {
+    // (scratch is not used by the forward: accepted for symmetry with the other entries, may be NULL)
+    if (const char* e = aux_head_shape_error(N, D, A, features, ld, params, features)) return fail(std::string("m2f_aux_head_forward: ") + e);
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail("m2f_aux_head_forward: scratch must be 16-byte aligned or NULL");
+    if (!logits) return fail("m2f_aux_head_forward: NULL logits");
+    AuxHeadArgs a{};
+    a.feat = features; a.N = N; a.D = D; a.ld = ld; a.params = params; a.A = A; a.aux_logits = logits; a.ldu = A;
+    M2F_HIP(m2f_launch_aux_rows(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_aux_head_backward(int N, int D, int A, const float* features, int ld, const float* params, const float* g, float* scratch,
+                          float* dfeatures, int ldd, float* dparams, m2f_stream_t stream) {
+    if (const char* e = aux_head_shape_error(N, D, A, features, ld, params, scratch)) return fail(std::string("m2f_aux_head_backward: ") + e);
+    if (!g) return fail("m2f_aux_head_backward: NULL g");
+    if (dfeatures && (ldd < ((D + 3) & ~3) || (ldd & 3) || (reinterpret_cast<uintptr_t>(dfeatures) & 15))) return fail("m2f_aux_head_backward: dfeatures rows must be 16-byte aligned (ldd a multiple of 4, >= D rounded up to 4)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* part = scratch + (size_t)N * 16 + (((size_t)N + 3) & ~(size_t)3);
+    if (dfeatures) M2F_HIP(m2f_launch_aux_join(dfeatures, ldd, nullptr, 0, g, A, params, A, N, D, nullptr, nullptr, 1.f, 0, 0, ShadowMap{nullptr, nullptr, 0}, s));
+    if (dparams) M2F_HIP(m2f_launch_aux_param_grad(features, ld, g, A, A, N, D, part, nullptr, nullptr, dparams, s));
+    return 0;
+}
+
+int m2f_aux_head_join(int N, int D, int A, float* dh, int ldd, const float* h, int ld, const float* g, int ldg, const float* params,
+                      const float* scale_dev, const float* hyper_dev, float gate_scale, int add, uint16_t* shadow, m2f_stream_t stream) {
+    if (N < 1 || D < 1 || D > 1024) return fail("m2f_aux_head_join: N >= 1 and 1 <= D <= 1024 required");
+    if (A < 2 || A > 16) return fail("m2f_aux_head_join: 2 <= A <= 16 auxiliary classes required");
+    if (!dh || !g || !params || ldg < A) return fail("m2f_aux_head_join: NULL dh / g / params, or ldg < A");
+    auto rows_bad = [&](const float* p, int l) { return l < ((D + 3) & ~3) || (l & 3) || (reinterpret_cast<uintptr_t>(p) & 15); };
+    if (rows_bad(dh, ldd) || (h && rows_bad(h, ld))) return fail("m2f_aux_head_join: dh and h rows must be 16-byte aligned (row strides multiples of 4, >= D rounded up to 4)");
+    if (reinterpret_cast<uintptr_t>(params) & 15) return fail("m2f_aux_head_join: params must be 16-byte aligned");
+    // (the caller's shadow maps dh element for element, as the plan's activation shadow maps its workspace)
+    const ShadowMap sh{shadow ? dh : nullptr, shadow, shadow ? (size_t)N * ldd : 0};
+    M2F_HIP(m2f_launch_aux_join(dh, ldd, h, ld, g, ldg, params, A, N, D, scale_dev, hyper_dev, gate_scale, add, shadow ? 1 : 0, sh, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_w2v_conv0_scratch_floats(int B, int C, int T0) {
     return B < 1 || C < 1 || T0 < 1 ? 0 : (int64_t)2 * B * C * (m2f_w2v_conv0_chunks(T0) + 1);
 }

@@ -609,6 +609,37 @@ hipError_t m2f_launch_supcon_tail(const float* row_terms, const float* loss_term
 // dh[i, :] += (h[i, :] > 0 ? gate_scale : 0) * scale[0] * dfeat[i, :] over [T, d] buffers of one row stride; write16: dh's bf16 shadow too
 hipError_t m2f_launch_supcon_add(float* dh, const float* h, const float* dfeat, const float* scale, int T, int d, int ld, float gate_scale,
                                  int write16, ShadowMap sh, hipStream_t stream);
+// Auxiliary label head over feature rows (aux_head.hip holds the definition: u = W h + b scored against its own labels, weighted by the
+// PRIMARY label's class weight).  Exact fp32 whatever the plan's precision.  lambda and eps_a are READ FROM THE DEVICE (hyper[0] >= 0,
+// 0 <= hyper[1] < 1): a captured step replays while a schedule changes them; lambda == 0 adds 0 to every numerator and gradient.
+//   aux_logits[i, c] = u_ic (every row)      row_term[i] = w_{y_i} a_i      g[i, c] = w_{y_i} d a_i / d u_ic   (zeros on an ignored row)
+//   loss_terms   (nullable) [N, 2]: the numerator of row i += lambda * w_{y_i} * a_i; the denominator is untouched
+struct AuxHeadArgs {
+    const float* feat; int N, D, ld;       // [N, D], row stride ld (a multiple of 4, rows 16-byte aligned), D <= 1,024
+    const float* params; int A;            // [W (A x D) | b (A)], 16-byte aligned, 2 <= A <= 16
+    const int64_t* labels; int C;          // [N] primary labels, a label outside [0, C) = ignored row
+    const float* class_w;                  // [C] or null
+    const int64_t* aux_labels;             // [N], a label outside [0, A) = ignored row; null: the logits alone (labels, hyper, g, row_term unused)
+    const float* hyper;                    // device float [2]: lambda, eps_a
+    float* aux_logits; int ldu;            // [N, A], row stride ldu
+    float* g;                              // [N, 16]
+    float* row_term;                       // [N]
+    float* loss_terms = nullptr;
+};
+// g [N, 16] | row_term [N] | the parameter gradient's partials, one per 16 rows
+size_t m2f_aux_head_ws_floats(int N, int D, int A);
+hipError_t m2f_launch_aux_rows(const AuxHeadArgs& a, hipStream_t stream);
+// loss_out[3] = (accumulate: +=) sum of row_term in m2f_launch_loss_finalize's order; scale[0] = the factor that launch multiplies dlogits
+// by for the same loss_terms (1 / den, the same bits; 1 without normalise)
+hipError_t m2f_launch_aux_tail(const float* row_term, const float* loss_terms, int T, float* loss_out, float* scale, int normalise,
+                               hipStream_t stream, int accumulate = 0);
+// dh[i, :] = (add: dh[i, :] +) gate * scale[0] * hyper[0] * sum_c g[i, c] W[c, :], gate = (h[i, :] > 0 ? gate_scale : 0) or (h null) 1;
+// scale / hyper null = 1; write16: dh's bf16 shadow too.  g: [N, A] with row stride ldg
+hipError_t m2f_launch_aux_join(float* dh, int ldd, const float* h, int ld, const float* g, int ldg, const float* params, int A, int N, int D,
+                               const float* scale, const float* hyper, float gate_scale, int add, int write16, ShadowMap sh, hipStream_t stream);
+// grad [A D + A] = scale[0] * hyper[0] * [g^T h | sum_i g[i, :]] (overwritten); part: the third share of m2f_aux_head_ws_floats
+hipError_t m2f_launch_aux_param_grad(const float* h, int ld, const float* g, int ldg, int A, int N, int D, float* part, const float* scale,
+                                     const float* hyper, float* grad, hipStream_t stream);
 // Linear-chain CRF over a dialogue's labels (crf.hip).  params: float [C*C + 2C] = [transitions row-major C x C | start C | end C], 2 <= C <= 16.
 // Dialogue b owns token rows cu_seqlens[b] .. cu_seqlens[b+1]-1 (packed and long-dialogue plans) or, cu_seqlens null, b*L .. b*L+L-1
 // (padded and bucket-padded plans).  The CHAIN of a dialogue is its rows with a label in [0, C), in row order (a -1 in the middle links

@@ -180,8 +180,9 @@ struct AccForm {
     void disarm() { ready = false; wg.clear(); wg_rest.clear(); }      // (`on` stays: the lists follow a rebuild, build_accumulate)
 };
 
-// The criterion's state (m2f_plan_distill, m2f_plan_focal, m2f_plan_rdrop, m2f_plan_crf, m2f_plan_supcon): which form do_loss launches.  The
-// switches exclude each other by plan.hip's exclusions[] table (distillation and focal combine; nothing else does).
+// The criterion's state (m2f_plan_distill, m2f_plan_focal, m2f_plan_rdrop, m2f_plan_crf, m2f_plan_supcon, m2f_plan_aux_head): which form
+// do_loss launches.  The switches exclude each other by plan.hip's exclusions[] table (focal combines with distillation and with the
+// auxiliary head; nothing else does).
 struct Criterion {
     bool distill_on = false;             // the teacher blend (M2F_BUF_TEACHER, alpha and tau = M2F_BUF_DISTILL)
     bool focal_on = false;               // do_loss and the eval rows launch run their focal forms (gamma = M2F_BUF_FOCAL[0])
@@ -197,6 +198,16 @@ struct Criterion {
     float* supcon_scale = nullptr;       // [1]: what the finalize launch multiplies dlogits by (1 / den, or 1)
     float* supcon_dh = nullptr;          // the chain's gradient of that activation (bwd[0]'s output) ...
     float supcon_gate = 1.f;             // ... and its gate scale (the dropout scale when the activation carries a dropout site)
+    // m2f_plan_aux_head: do_loss runs the auxiliary label head's rows kernel (aux_head.hip) on the same activation behind the cross-entropy
+    // launch, the backward joins its gradient behind bwd[0] (supcon_dh / supcon_gate: the same join point, so the two exclude each other)
+    // and, with a trainable block, writes the block's gradient.  The block and its gradient are the CALLER's (never part of the flat
+    // buffer); (lambda, eps_a) = M2F_BUF_AUX, the labels = M2F_BUF_AUX_LABELS, the logits = M2F_BUF_AUX_LOGITS
+    bool aux_on = false;
+    const float* aux_params = nullptr;   // [W (aux_A x cls_hidden) | b (aux_A)]
+    float* aux_grad = nullptr;           // the same size, or null (frozen)
+    int aux_A = 0;
+    float* aux_ws = nullptr;             // m2f_aux_head_ws_floats(T, cls_hidden, 16) floats: g [T, 16] | row terms [T] | the gradient's partials
+    float* aux_scale = nullptr;          // [1]: what the finalize launch multiplies dlogits by (1 / den, or 1)
     // m2f_plan_crf: do_loss runs the linear-chain CRF criterion (crf.hip), the eval step the CRF loss and the Viterbi path.  The parameter
     // block and its gradient are the CALLER's (never part of the flat buffer); crf_ws / crf_pred / crf_score sit at the end of the workspace
     bool crf_on = false;
@@ -260,7 +271,7 @@ struct m2f_plan {
     uint32_t* rng = nullptr; bool use_dropout = false;
     uint32_t drop_thresh = 0; float drop_scale = 1.f;
     m2f::ParamMap pm;
-    void* bufs[M2F_BUF_COUNT] = {nullptr};
+    void* bufs[M2F_BUF_END] = {nullptr};
     float* loss_terms = nullptr;
     int* eval_partial = nullptr;     // m2f_eval_step: the rows launch's integer tiles (its row terms go to loss_terms, as the criterion's do)
     bool eval_warmed = false;        // ... and one eager m2f_eval_step before its first capture (`warmed` belongs to the train step)

@@ -1128,6 +1128,13 @@ int build_plan(m2f_plan& P, char* ws_base) {
     P.crit.supcon_rows = P.train ? bld.ar.f((size_t)T * 4) : nullptr;
     P.crit.supcon_dfeat = P.train ? bld.ar.f((size_t)T * Builder::pad8(c.cls_hidden)) : nullptr;
     P.crit.supcon_scale = P.train ? bld.ar.f(1) : nullptr;
+    // the auxiliary label head (m2f_plan_aux_head), train plans only: (lambda, eps_a), the second labels, the head's logits and the kernels'
+    // workspace sized for 16 classes - behind everything again, whether or not the switch is on
+    P.bufs[M2F_BUF_AUX] = P.train ? bld.ar.f(2) : nullptr;
+    P.bufs[M2F_BUF_AUX_LABELS] = P.train ? bld.ar.alloc<int64_t>((size_t)T) : nullptr;
+    P.bufs[M2F_BUF_AUX_LOGITS] = P.train ? bld.ar.f((size_t)T * 16) : nullptr;
+    P.crit.aux_ws = P.train && c.cls_hidden <= 1024 ? bld.ar.f(m2f_aux_head_ws_floats(T, c.cls_hidden, 16)) : nullptr;
+    P.crit.aux_scale = P.train ? bld.ar.f(1) : nullptr;
     P.built.ws_used = bld.ar.off;
     if (P.prec == M2F_PREC_BF16 && ws_base != nullptr) {
         const float* wsf = reinterpret_cast<const float*>(ws_base);

@@ -119,11 +119,13 @@ class Distiller:
         """speakers ([B, L] ids): student and teacher each run under their OWN speaker-head setting, and the batch's ids go to
         whichever of the two has one; needed as soon as either has, refused (ValueError) when neither does.
         focal_gamma= (in ``kw``) goes to the student's step: the focal factor scales its hard-label term, the teacher term stays.
-        rdrop= and supcon= are refused by name: neither criterion has a distillation form."""
+        rdrop=, supcon= and aux= are refused by name: none of them has a distillation form."""
         pair = check_distill((self.alpha, self.temperature), "Distiller")          # (before the teacher runs)
         if kw.get("supcon") is not None:
             raise ValueError("Distiller.train_step: supcon and distill do not combine (the supervised contrastive criterion has no "
                              "distillation form)")
+        if kw.get("aux") is not None:
+            raise ValueError("Distiller.train_step: aux and distill do not combine (the auxiliary head has no distillation form)")
         if kw.get("rdrop") is not None:
             raise ValueError("Distiller.train_step: rdrop and distill do not combine (the R-Drop criterion has no distillation form)")
         if kw.get("focal_gamma") is not None:

@@ -480,7 +480,7 @@ class DataParallelStep:
 
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
                  use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None,
-                 rdrop=None, supcon=None) -> torch.Tensor:
+                 rdrop=None, supcon=None, aux=None, aux_label_smoothing: float = 0.0) -> torch.Tensor:
         """teacher_logits, distill=(alpha, temperature): as ``M2FNet.train_step`` - the rank's step runs the distillation criterion
         (one denominator: the exchange, the global den and the micro-batch group hold as they are); both or neither.
         focal_gamma: as ``M2FNet.train_step`` - the rank's step runs the focal form of its criterion (the denominator is untouched).
@@ -488,6 +488,10 @@ class DataParallelStep:
         never crosses ranks) under the R-Drop criterion; the denominator is the labelled weight of both views, and the all-reduced tail
         carries the global KL share (``model.rdrop_terms()``).  Refused beside teacher_logits / distill, focal_gamma or a CRF by name.
         supcon: refused by name (ValueError): the contrast set of ``M2FNet.train_step(supcon=)`` is the whole batch, a shard's is not.
+        aux (head, aux_labels, weight), aux_label_smoothing: as ``M2FNet.train_step`` with a FROZEN head - the rank's step adds the
+        auxiliary term of its shard's rows to its numerators (one denominator: the exchange and the global den hold as they are, the
+        all-reduced tail carries the global share, ``model.aux_terms()``).  A trainable head is refused by name (ValueError): its
+        gradient would need an all-reduce of its own - freeze it with ``head.params.requires_grad_(False)``.
         sync=False: this rank's micro-batch only - forward, criterion, backward into the gradient buffer (the first call after a
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
@@ -499,6 +503,11 @@ class DataParallelStep:
             raise ValueError("DataParallelStep: supcon is refused (the supervised contrastive criterion contrasts the whole batch; a "
                              "per-shard contrast set is a different objective - run it on one device through M2FNet.train_step)")
         alpha = runtime.check_rdrop_args("DataParallelStep", rdrop, teacher_logits, distill, focal_gamma, self.crf)
+        from .aux_head import check_step_args as check_aux_args
+        ax = check_aux_args("DataParallelStep", aux, self.model.m2f_config.cls_hidden, mask.shape, aux_label_smoothing, teacher_logits, distill,
+                            self.crf, rdrop, supcon, data_parallel=True, device=mask.device)
+        if ax is not None:
+            self.model._aux_weight, self.model._aux_classes = ax[2], ax[0].num_classes
         B, L = mask.shape
         dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
         gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DataParallelStep")
@@ -543,7 +552,7 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf, alpha)
+            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf, alpha, None, ax)
             if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

@@ -862,6 +862,131 @@ def supcon(features: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch
     return rows, dfeat
 
 
+def _aux_rows(features: torch.Tensor, who: str) -> torch.Tensor:
+    """fp32 [N, D] feature rows as the auxiliary head's kernels read them: 16-byte aligned rows of a stride that is a multiple of 4
+    (read in place when they are; else copied once into such a buffer)."""
+    if features.dim() != 2 or features.dtype != torch.float32:
+        raise ValueError(f"{who}: features must be fp32 [N, D] (got {tuple(features.shape)} {features.dtype})")
+    N, D = features.shape
+    if D < 1 or D > 1024:
+        raise ValueError(f"{who}: 1 <= D <= 1024 feature columns required (got {D})")
+    if N > 0 and features.stride(1) == 1 and features.stride(0) >= (D + 3) // 4 * 4 and features.stride(0) % 4 == 0 and features.data_ptr() % 16 == 0:
+        return features
+    buf = torch.zeros(N, (D + 3) // 4 * 4, dtype=torch.float32, device=features.device)
+    buf[:, :D] = features
+    return buf[:, :D]
+
+
+def _aux_block(params: torch.Tensor, D: int, who: str) -> int:
+    """The class count of a head's block [W (A x D) | b (A)]; ValueError unless it is fp32, contiguous, 16-byte aligned, 2 <= A <= 16."""
+    if params.dim() != 1 or params.dtype != torch.float32 or not params.is_contiguous() or params.data_ptr() % 16:
+        raise ValueError(f"{who}: params must be one contiguous, 16-byte aligned fp32 block [W | b] (got {tuple(params.shape)} {params.dtype})")
+    A, rest = divmod(params.numel(), D + 1)
+    if rest or not 2 <= A <= 16:
+        raise ValueError(f"{who}: params holds {params.numel()} floats: A * {D} + A with 2 <= A <= 16 expected")
+    return A
+
+
+def aux_head(features: torch.Tensor, labels: torch.Tensor, aux_labels: torch.Tensor, params: torch.Tensor,
+             hyper: Tuple[float, float] = (1.0, 0.0), class_weights: Optional[torch.Tensor] = None, n_classes: Optional[int] = None):
+    """The auxiliary label head's kernels on their own (m2f_aux_head; csrc/aux_head.hip holds the definition).  features: fp32 [N, D];
+    labels / aux_labels int64 [N] (the primary and the second label; a row with either outside its range is ignored); params: the head's
+    fp32 block [W (A x D) | b (A)]; hyper = (weight, label smoothing of the auxiliary term); class_weights: the PRIMARY classes' weights
+    or None; n_classes defaults to their count, else to 1 + the largest primary label (one host read).
+    -> (aux_logits [N, A] = W h + b for every row, row_terms [N] = w_y a_i, dfeatures [N, D] and dparams [A D + A] = the gradient of
+    ``weight * sum_i w_y a_i`` w.r.t. features (no gate) and the block, unnormalised).  Ignored rows give exact zeros in the last three,
+    whatever their features hold.  Exact fp32, no atomics: the same bits at every call."""
+    from .aux_head import check_pair
+    w, eps = check_pair(hyper[0], hyper[1], "aux_head")
+    runtime.require_gpu()
+    feat = _aux_rows(features, "aux_head")
+    N, D = feat.shape
+    A = _aux_block(params, D, "aux_head")
+    dev = feat.device
+    for name, t in (("labels", labels), ("aux_labels", aux_labels)):
+        if t.shape != (N,) or t.dtype != torch.int64 or t.device != dev:
+            raise ValueError(f"aux_head: {name} must be int64 [{N}] on {dev} (got {tuple(t.shape)} {t.dtype} on {t.device})")
+    if class_weights is not None:
+        class_weights = class_weights.to(device=dev, dtype=torch.float32).contiguous()
+    C = int(n_classes) if n_classes is not None else (class_weights.numel() if class_weights is not None else max(int(labels.max()) + 1, 1))
+    if class_weights is not None and class_weights.numel() < C:
+        raise ValueError(f"aux_head: class_weights holds {class_weights.numel()} weights for {C} classes")
+    scratch = torch.empty(int(lib().m2f_aux_head_scratch_floats(N, D, A)), dtype=torch.float32, device=dev)
+    logits = torch.empty(N, A, dtype=torch.float32, device=dev)
+    rows = torch.empty(N, dtype=torch.float32, device=dev)
+    ldd = (D + 3) // 4 * 4
+    dfeat = torch.zeros(N, ldd, dtype=torch.float32, device=dev)
+    dparams = torch.empty(A * D + A, dtype=torch.float32, device=dev)
+    hyp = torch.tensor([w, eps], dtype=torch.float32).to(dev, non_blocking=True)
+    labels, aux_labels = labels.contiguous(), aux_labels.contiguous()
+    check(lib().m2f_aux_head(N, D, A, C, ptr(feat), feat.stride(0), ptr(params), ptr(labels), ptr(aux_labels), ptr(class_weights), ptr(hyp),
+                             ptr(scratch), ptr(logits), ptr(rows), ptr(dfeat), ldd, ptr(dparams), stream_ptr()), "m2f_aux_head")
+    return logits, rows, dfeat[:, :D], dparams
+
+
+def aux_head_forward(features: torch.Tensor, params: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """logits [N, A] = W h + b of the head's block over fp32 feature rows [N, D] (m2f_aux_head_forward: the rows kernel without a label)."""
+    runtime.require_gpu()
+    feat = _aux_rows(features, "aux_head_forward")
+    N, D = feat.shape
+    A = _aux_block(params, D, "aux_head_forward")
+    if A != num_classes:
+        raise ValueError(f"aux_head_forward: the block holds {A} classes, {num_classes} expected")
+    logits = torch.empty(N, A, dtype=torch.float32, device=feat.device)
+    check(lib().m2f_aux_head_forward(N, D, A, ptr(feat), feat.stride(0), ptr(params), None, ptr(logits), stream_ptr()),
+          "m2f_aux_head_forward")
+    return logits
+
+
+def aux_head_backward(features: torch.Tensor, params: torch.Tensor, g: torch.Tensor, num_classes: int, want_features: bool = True,
+                      want_params: bool = True):
+    """(dfeatures [N, D] = g W or None, dparams [A D + A] = [g^T h | sum_i g_i] or None) from an upstream gradient g [N, A]
+    (m2f_aux_head_backward: the join and parameter-gradient kernels of the step)."""
+    runtime.require_gpu()
+    feat = _aux_rows(features, "aux_head_backward")
+    N, D = feat.shape
+    A = _aux_block(params, D, "aux_head_backward")
+    if A != num_classes or g.shape != (N, A) or g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError(f"aux_head_backward: g must be contiguous fp32 [{N}, {A}] (got {tuple(g.shape)} {g.dtype})")
+    dev = feat.device
+    scratch = torch.empty(int(lib().m2f_aux_head_scratch_floats(N, D, A)), dtype=torch.float32, device=dev)
+    ldd = (D + 3) // 4 * 4
+    dfeat = torch.zeros(N, ldd, dtype=torch.float32, device=dev) if want_features else None
+    dparams = torch.empty(A * D + A, dtype=torch.float32, device=dev) if want_params else None
+    check(lib().m2f_aux_head_backward(N, D, A, ptr(feat), feat.stride(0), ptr(params), ptr(g), ptr(scratch), ptr(dfeat), ldd, ptr(dparams),
+                                      stream_ptr()), "m2f_aux_head_backward")
+    return (dfeat[:, :D] if want_features else None), dparams
+
+
+def aux_head_join(dh: torch.Tensor, g: torch.Tensor, params: torch.Tensor, h: Optional[torch.Tensor] = None, scale: float = 1.0,
+                  weight: float = 1.0, gate_scale: float = 1.0, add: bool = True, shadow: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The step's join launch on the caller's buffers (m2f_aux_head_join), IN PLACE: dh[i, :] = (add: dh[i, :] +) gate * scale * weight *
+    sum_c g[i, c] W[c, :], gate = (h[i, :] > 0 ? gate_scale : 0) or (h None) 1.  dh / h: fp32 [N, D] views with 16-byte aligned rows of
+    one stride each (a multiple of 4; ValueError otherwise - nothing is copied, the launch writes dh itself); g fp32 [N, A]; params the
+    head's block.  shadow: an int16 tensor of N * dh.stride(0) elements that receives the bf16 bits (nearest even) of every dh element the
+    launch writes - what the step does to the plan's activation shadow in bf16 mode.  -> dh."""
+    runtime.require_gpu()
+    for name, t in (("dh", dh), ("h", h)):
+        if t is None:
+            continue
+        if (t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < (t.shape[1] + 3) // 4 * 4
+                or t.data_ptr() % 16 or t.shape != dh.shape):
+            raise ValueError(f"aux_head_join: {name} must be fp32 {tuple(dh.shape)} with 16-byte aligned rows, row stride a multiple of 4 "
+                             f"(got {tuple(t.shape)} {t.dtype}, strides {t.stride()})")
+    N, D = dh.shape
+    A = _aux_block(params, D, "aux_head_join")
+    if g.dim() != 2 or g.shape != (N, A) or g.dtype != torch.float32 or g.stride(1) != 1:
+        raise ValueError(f"aux_head_join: g must be fp32 [{N}, {A}] (got {tuple(g.shape)} {g.dtype})")
+    if shadow is not None and (shadow.dtype != torch.int16 or shadow.numel() != N * dh.stride(0) or not shadow.is_contiguous()):
+        raise ValueError(f"aux_head_join: shadow must be a contiguous int16 tensor of {N * dh.stride(0)} elements")
+    dev = dh.device
+    pair = torch.tensor([float(scale), float(weight)], dtype=torch.float32).to(dev, non_blocking=True)
+    check(lib().m2f_aux_head_join(N, D, A, ptr(dh), dh.stride(0), ptr(h), h.stride(0) if h is not None else 0, ptr(g), g.stride(0), ptr(params),
+                                  pair.data_ptr(), pair.data_ptr() + 4, float(gate_scale), int(bool(add)), ptr(shadow), stream_ptr()),
+          "m2f_aux_head_join")
+    return dh
+
+
 def fam_layer_forward(text, audio, key_pad, in_w, in_b, out_w, out_b, lin_w, lin_b, n_head: int,
                       precision: int = runtime.F32, past: Optional[int] = None, future: Optional[int] = None,
                       need_weights: bool = False, bias: Optional[float] = None, speakers: Optional[torch.Tensor] = None,

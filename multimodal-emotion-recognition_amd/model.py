@@ -624,6 +624,7 @@ class M2FNet(nn.Module):
         plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask, speakers=ids)
         if plan.train:
             plan.set_supcon(None)                  # (the criterion is the caller's here: nothing joins the backward at the hidden features)
+            plan.set_aux(None)
         if want_bwd:
             out = _Anchor.apply(eng.anchor, text, audio, self, plan)
             plan.hold(out.grad_fn)
@@ -684,7 +685,7 @@ class M2FNet(nn.Module):
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
                    distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
                    focal_gamma: Optional[float] = None, crf=None, rdrop: Optional[float] = None,
-                   supcon: Optional[Tuple[float, float]] = None) -> torch.Tensor:
+                   supcon: Optional[Tuple[float, float]] = None, aux=None, aux_label_smoothing: float = 0.0) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -730,11 +731,27 @@ class M2FNet(nn.Module):
         changed): a weight schedule replays the captured step; weight 0 gives the plain step's loss and gradients.  None (default):
         today's launches, bit for bit; contrastive and plain calls mix freely on one model.  Under gradient accumulation each
         micro-batch contrasts within itself.  Refused (ValueError naming the pair, before any launch) beside teacher_logits / distill,
-        focal_gamma, crf or rdrop."""
+        focal_gamma, crf or rdrop.
+        aux (head, aux_labels, weight): an ``aux_head.AuxiliaryHead`` over ``cls_hidden``, a second label per utterance (int64
+        ``[B, L]``, laid out like ``emotion``; a value outside the head's classes = ignored) and a weight (finite, >= 0).  For every
+        utterance with an emotion label AND an auxiliary label, ``weight * w_y * a`` joins the numerator over the one denominator, ``a``
+        the cross entropy (``aux_label_smoothing``, no class weights of its own) of ``head(h)`` against the auxiliary label, ``h`` =
+        ``last_features()``: with no class weights and every row labelled twice the loss is ``CE(z, y) + weight * CE(head(h), s)``.
+        Exact-fp32 kernels in both precision modes inside the one step graph; the gradient enters the backward at the hidden
+        activation's gradient, and a trainable head's own gradient lands in ``head.params.grad`` (overwritten by every step; step it with
+        an optimizer of your own, as a CRF's block).  ``aux_terms()`` gives the two shares, ``last_aux_logits()`` the head's logits.
+        The weight and the smoothing live on the device (uploaded only when changed): a weight schedule replays the captured step;
+        weight 0 gives the plain step's loss and gradients.  None (default): today's launches, bit for bit; auxiliary and plain calls
+        mix freely on one model.  Combines with focal_gamma (the focal factor scales the emotion term only); refused (ValueError naming
+        the pair, before any launch) beside teacher_logits / distill, crf, rdrop or supcon, and - a trainable head - under gradient
+        accumulation."""
+        from .aux_head import check_step_args as check_aux_args
         from .crf import check_step_args
         from .distill import resolve_distill_args
         alpha = runtime.check_rdrop_args("M2FNet.train_step", rdrop, teacher_logits, distill, focal_gamma, crf)
         con = runtime.check_supcon_args("M2FNet.train_step", supcon, teacher_logits, distill, focal_gamma, crf, rdrop)
+        ax = check_aux_args("M2FNet.train_step", aux, self.m2f_config.cls_hidden, mask.shape, aux_label_smoothing, teacher_logits, distill, crf,
+                            rdrop, supcon, accumulating=self._engine is not None and self._engine.accumulate, device=mask.device)
         check_step_args("M2FNet.train_step", crf, self.m2f_config.cls_out, class_weights, teacher_logits, distill, focal_gamma,
                         label_smoothing, accumulating=self._engine is not None and self._engine.accumulate)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
@@ -753,12 +770,14 @@ class M2FNet(nn.Module):
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
         if con is not None:
             self._supcon_weight = con[0]
+        if ax is not None:
+            self._aux_weight, self._aux_classes = ax[2], ax[0].num_classes
 
         def body():
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha, con)
+            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha, con, ax)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -784,19 +803,34 @@ class M2FNet(nn.Module):
         eng.publish_grads()
         if crf is not None:
             crf.publish_grad()
+        if ax is not None:
+            ax[0].publish_grad()
         eng.note_forward(plan)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
     @staticmethod
-    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None, supcon=None) -> None:
+    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None, supcon=None, aux=None) -> None:
         """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
         temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
         plan maps the teacher rows as it mapped the batch).  `crf` (a LinearChainCRF; the callers refused every other criterion argument
         beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains.
         `rdrop` (alpha; likewise alone): the R-Drop criterion over the doubled batch `set_inputs` has just placed.
-        `supcon` ((weight, temperature); likewise alone): the plain criterion plus the contrastive term on the hidden features."""
+        `supcon` ((weight, temperature); likewise alone): the plain criterion plus the contrastive term on the hidden features.
+        `aux` ((head, aux_labels, weight, label smoothing); beside `gamma` at most): the plain or focal criterion plus the auxiliary head's
+        term, its labels placed as `set_inputs` placed the emotion labels."""
+        if plan.train and aux is None:
+            plan.set_aux(None)
         if plan.train and supcon is None:
             plan.set_supcon(None)
+        if aux is not None:
+            plan.set_crf(None)
+            plan.distill(False)
+            plan.set_rdrop(None)
+            plan.set_focal(gamma)
+            head, labels, weight, eps = aux
+            plan.set_aux_labels(labels)
+            plan.set_aux(*head.step_buffers(plan.workspace.device, want_grad=plan.train), head.num_classes, (weight, eps))
+            return
         if supcon is not None:
             plan.set_crf(None)
             plan.set_focal(None)
@@ -1004,6 +1038,36 @@ class M2FNet(nn.Module):
         t = eng.flat_grad_ext[n: n + 4]
         con = t[3] / t[1]
         return t[2] / t[1] - getattr(self, "_supcon_weight", 0.0) * con, con
+
+    def aux_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(ce, aux)`` of the last ``train_step(aux=(head, aux_labels, weight))`` as device scalars: the emotion criterion's share of
+        its loss and the auxiliary term per unit of labelled weight WITHOUT the weight - ``ce + weight * aux`` is the loss.  Read from
+        the criterion tail (den, num and, in its fourth float, the sum of ``w_y * a``, reduced in a fixed order): with accumulation on
+        they cover the group's micro-batches.  The weight is the last step's."""
+        eng = self.engine()
+        eng.ensure_grad()
+        n = eng.flat.numel()
+        t = eng.flat_grad_ext[n: n + 4]
+        aux = t[3] / t[1]
+        return t[2] / t[1] - getattr(self, "_aux_weight", 0.0) * aux, aux
+
+    def last_aux_logits(self) -> torch.Tensor:
+        """The auxiliary head's logits of the most recent ``train_step(aux=)`` of this model as a fresh ``[B, L, A]`` tensor in the
+        caller's dialogue order, whatever bucket, packed or long-dialogue plan ran: ``head(last_features())``.  Pad slots are 0.
+        Raises RuntimeError when no such step has run, or the plan that ran it was destroyed or has run again since."""
+        eng = self._engine
+        if eng is None or eng.last is None or getattr(self, "_aux_classes", None) is None:
+            raise RuntimeError("M2FNet.last_aux_logits: no train_step(aux=) has run on this model (or it was moved since)")
+        plan, version, dst, valid, shape = eng.last
+        if not plan.handle:
+            raise RuntimeError("M2FNet.last_aux_logits: the plan holding the activations of the last step was destroyed "
+                               "(evicted from the plan cache)")
+        if plan.version != version:
+            raise RuntimeError("M2FNet.last_aux_logits: the activations of the last step were overwritten by a later forward "
+                               "of the same plan")
+        if not plan.train or plan._aux_key[0] is None:
+            raise RuntimeError("M2FNet.last_aux_logits: the last forward of this model was not a train_step(aux=)")
+        return plan.aux_logits(self._aux_classes, dst, valid, shape).detach()
 
     def last_features(self) -> torch.Tensor:
         """The classifier's last hidden activation of the most recent ``forward`` / ``train_step`` / ``eval_step`` of this model as a

@@ -6,6 +6,8 @@
 * ``M2FRDropLoss``         = the same over a batch given twice, plus the symmetric KL divergence between each utterance's two predictions
   (R-Drop; its own kernel).
 * ``M2FSupConLoss``        = the supervised contrastive loss over utterance features (Khosla et al. 2020; its own exact-fp32 kernels).
+* ``M2FAuxiliaryLoss``     = the cross entropy of an ``aux_head.AuxiliaryHead`` over utterance features against a second label, per unit
+  of the emotion criterion's labelled weight (the term ``train_step(aux=)`` adds; its own exact-fp32 kernels).
 * ``FusedAdam``            = ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` (src/train.py:56): coupled
   L2, bias-corrected; ONE kernel over the flat parameter / gradient / moment buffers instead of ~130 per-tensor
   updates.  ``state_dict()`` keeps torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` /
@@ -263,6 +265,68 @@ class M2FSupConLoss(nn.Module):
         tgt = target.reshape(-1).contiguous()
         C = self.n_classes if self.n_classes is not None else (w.numel() if w is not None else max(int(tgt.max()) + 1, 1))
         loss, self.last_terms = _SupConFunction.apply(input.reshape(-1, input.shape[-1]).contiguous().float(), tgt, w, t, C)
+        return loss
+
+
+class _AuxHeadLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat2d, params, target1d, aux1d, weight, eps, n_classes):
+        logits, rows, dfeat, dparams = F.aux_head(feat2d, target1d, aux1d, params, (1.0, eps), weight, n_classes)
+        w = torch.ones(n_classes, dtype=torch.float32, device=feat2d.device) if weight is None else weight
+        ok = (target1d >= 0) & (target1d < n_classes)
+        den = (w[target1d.clamp(0, n_classes - 1)] * ok).sum()
+        # (no row with an emotion label: den = 0 - the term and its gradient are 0, as the step's are; a select, no 0 / 0)
+        inv = torch.where(den > 0, 1.0 / den.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(den))
+        ctx.save_for_backward(dfeat, dparams, inv)
+        ctx.mark_non_differentiable(logits, rows)
+        return rows.sum() * inv, logits, rows
+
+    @staticmethod
+    def backward(ctx, grad_out, _l, _r):
+        dfeat, dparams, inv = ctx.saved_tensors
+        k = grad_out * inv
+        return (dfeat * k if ctx.needs_input_grad[0] else None), (dparams * k if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+class M2FAuxiliaryLoss(nn.Module):
+    """The auxiliary label head's term, the one ``M2FNet.train_step(aux=)`` adds inside the step, on the autograd surface:
+    ``loss(features, head, emotion, aux_labels)`` with features ``[N, D]`` or ``[B, L, D]`` (fp32), an ``aux_head.AuxiliaryHead`` over
+    ``D``, and the two targets ``[N]`` or ``[B, L]`` with ``ignore_index`` (-1, the padding label).  For every row with both labels valid,
+    ``a_i`` = the cross entropy (``label_smoothing``, no class weights of its own) of ``head``'s logits against the auxiliary label; the
+    loss is ``sum_i w_{y_i} a_i / sum_i w_{y_i}``, the denominator over the rows with an EMOTION label - the criterion's own, so
+    ``M2FCrossEntropyLoss(...)(logits, y) + weight * M2FAuxiliaryLoss(...)(h, head, y, s)`` is the step's loss.  ``weight``: the
+    emotion classes' weights or None.  Differentiable with respect to the features and the head's block: the kernels give the gradient
+    at unit weight and torch scales it by ``grad_out / den``, where the step scales by ``(1 / den) * weight`` inside its reduce launch -
+    the two agree to a few fp32 eps, bit equality with the step is NOT offered.  No row with an emotion label: the loss and its
+    gradients are 0, as the step's.  ``last_logits`` /
+    ``last_terms`` hold the head's logits and the per-row ``w_y a_i`` of the last call on the device.  n_classes: the weight's length,
+    else 1 + the largest emotion target (one host read); pass it to avoid the read."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: int = -1, label_smoothing: float = 0.0,
+                 n_classes: Optional[int] = None):
+        super().__init__()
+        from .aux_head import check_pair
+        if ignore_index != -1:
+            raise ValueError("M2FAuxiliaryLoss: ignore_index must be -1 (the padding label the kernels skip)")
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+        self.label_smoothing = check_pair(0.0, label_smoothing, "M2FAuxiliaryLoss")[1]
+        self.n_classes = n_classes
+        self.last_logits = self.last_terms = None
+
+    def forward(self, input: torch.Tensor, head, target: torch.Tensor, aux_target: torch.Tensor) -> torch.Tensor:
+        from .aux_head import AuxiliaryHead, check_pair
+        eps = check_pair(0.0, self.label_smoothing, "M2FAuxiliaryLoss")[1]
+        if not isinstance(head, AuxiliaryHead) or input.dim() not in (2, 3) or input.shape[-1] != head.in_features:
+            raise ValueError(f"M2FAuxiliaryLoss: features [N, D] / [B, L, D] and an AuxiliaryHead over D expected, got {tuple(input.shape)} "
+                             f"and {head!r}")
+        if target.shape != input.shape[:-1] or aux_target.shape != input.shape[:-1]:
+            raise ValueError(f"M2FAuxiliaryLoss: targets {tuple(input.shape[:-1])} expected, got {tuple(target.shape)} and {tuple(aux_target.shape)}")
+        w = self.weight.to(device=input.device, dtype=torch.float32) if self.weight is not None else None
+        tgt = target.reshape(-1).contiguous()
+        C = self.n_classes if self.n_classes is not None else (w.numel() if w is not None else max(int(tgt.max()) + 1, 1))
+        loss, self.last_logits, self.last_terms = _AuxHeadLossFunction.apply(
+            input.reshape(-1, input.shape[-1]).contiguous().float(), head.block(input.device), tgt, aux_target.reshape(-1).contiguous(), w, eps, C)
         return loss
 
 

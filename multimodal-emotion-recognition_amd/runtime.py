@@ -28,7 +28,7 @@ PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16":
 (BUF_TEXT, BUF_AUDIO, BUF_KEYPAD, BUF_LABELS, BUF_CLASSW, BUF_LOGITS, BUF_LOSS, BUF_DLOGITS,
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
  BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL, BUF_PARTNER, BUF_RDROP, BUF_SUPCON,
- BUF_FEATURES) = range(26)
+ BUF_FEATURES, BUF_AUX, BUF_AUX_LABELS, BUF_AUX_LOGITS) = range(29)
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -191,6 +191,7 @@ SIGNATURES = {
     "m2f_plan_rdrop": (c_int, [c_void_p, c_int]),
     "m2f_plan_supcon": (c_int, [c_void_p, c_int]),
     "m2f_plan_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "m2f_plan_aux_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "m2f_plan_stream_crf": (c_int, [c_void_p, c_void_p, c_void_p]),
     "m2f_plan_backward_outputs": (c_int, [c_void_p, c_int, c_int]),
     "m2f_plan_fused_adam_setup": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -253,6 +254,14 @@ SIGNATURES = {
     "m2f_supcon_scratch_floats": (c_int64, [c_int, c_int]),
     "m2f_supcon": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                            c_void_p]),
+    "m2f_aux_head_scratch_floats": (c_int64, [c_int, c_int, c_int]),
+    "m2f_aux_head": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "m2f_aux_head_forward": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "m2f_aux_head_backward": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p]),
+    "m2f_aux_head_join": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_float, c_int, c_void_p, c_void_p]),
     "m2f_w2v_conv0": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "m2f_w2v_conv0_scratch_floats": (c_int64, [c_int, c_int, c_int]),
@@ -604,6 +613,13 @@ class Plan:
         self.supcon_hyper = self._view(BUF_SUPCON, (2,), torch.float32) if train else None
         self._supcon = False
         self.supcon_host = None               # host mirror of supcon_hyper, as hyper_host
+        # the auxiliary label head (train plans; `set_aux`): the (weight, label smoothing) pair its kernels read on the device, the second
+        # label of every token row (placed as labels_in is) and the head's logits of the last step
+        self.aux_hyper = self._view(BUF_AUX, (2,), torch.float32) if train else None
+        self.aux_labels_in = self._view(BUF_AUX_LABELS, (self.T,), torch.int64) if train else None
+        self._aux_logits = self._view(BUF_AUX_LOGITS, (self.T, 16) if self.packed else (B, L, 16), torch.float32) if train else None
+        self._aux_key, self._aux_ref = (None, None, 0), None
+        self.aux_host = None                  # host mirror of aux_hyper, as hyper_host
         # the classifier's last hidden activation as stored, in the plan's token rows (what `supcon` contrasts; `features`)
         hid = cfg.cls_hidden
         self._features = self._view(BUF_FEATURES, (self.T, pad8(hid)) if self.packed else (B, L, pad8(hid)), torch.float32)[..., :hid]
@@ -654,6 +670,17 @@ class Plan:
             return self._features[dst] * valid[..., None].to(self._features.dtype)
         pad = self.keypad_in.view(self.B, self.L)[:b, :l].bool()
         return self._features[:b, :l].masked_fill(pad[..., None], 0.0)
+
+    def aux_logits(self, num_aux: int, dst=None, valid=None, shape=None) -> torch.Tensor:
+        """The auxiliary head's logits of the plan's last step as a fresh [b, l, num_aux] tensor in the caller's dialogue order; pad
+        slots are 0.  dst / valid / shape: as `features`."""
+        b, l = (self.in_B, self.in_L) if shape is None else shape
+        rows = self._aux_logits[..., :num_aux]
+        if self.packed:
+            dst, valid = (self._dst, self._valid) if dst is None else (dst, valid)
+            return rows[dst] * valid[..., None].to(rows.dtype)
+        pad = self.keypad_in.view(self.B, self.L)[:b, :l].bool()
+        return rows[:b, :l].masked_fill(pad[..., None], 0.0)
 
     @property
     def fam0_out(self) -> Optional[torch.Tensor]:
@@ -923,6 +950,40 @@ class Plan:
         if pair != self.supcon_host:
             self.supcon_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
             self.supcon_host = pair
+
+    def set_aux_labels(self, labels: torch.Tensor) -> None:
+        """The second labels of the last batch ([b, l] int64, padded surface) into the plan's buffer: they travel as `set_inputs` moves
+        the emotion labels - filler slots of a bucketed plan -1, packed plans through the batch's row map with the spare row cleared."""
+        if self.aux_labels_in is None:
+            raise HipError("this plan holds no auxiliary label buffer (an eval plan)")
+        if self.packed:
+            self.aux_labels_in.fill_(-1)
+            self.aux_labels_in.index_copy_(0, self._dst.reshape(-1), labels.reshape(-1).to(torch.int64))
+            self._clear_spare(self.aux_labels_in, -1)
+            return
+        if (self.in_B, self.in_L) == (self.B, self.L):
+            self.aux_labels_in.copy_(labels.reshape(self.T), non_blocking=True)
+            return
+        self.aux_labels_in.fill_(-1)
+        self.aux_labels_in.view(self.B, self.L)[: self.in_B, : self.in_L].copy_(labels, non_blocking=True)
+
+    def set_aux(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None, num_aux: int = 0,
+                pair: Optional[Tuple[float, float]] = None) -> None:
+        """m2f_plan_aux_head: the plan's NEXT losses / steps add the auxiliary label head over `params` (the module's flat block [W | b],
+        read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan keeps the two
+        tensors alive; a change of the pointers, of num_aux or of the switch drops the captured steps, a change of the values or of
+        `pair` = (weight, label smoothing) - uploaded only when it differs from the host mirror of the last upload - does not.  The
+        distillation, R-Drop, CRF and supervised contrastive switches must be off (the C entry refuses by name)."""
+        key = (None if params is None else params.data_ptr(), None if grad is None else grad.data_ptr(), int(num_aux) if params is not None else 0)
+        if key != self._aux_key:
+            check(lib().m2f_plan_aux_head(self._h(), ptr(params), ptr(grad), key[2]), "m2f_plan_aux_head")
+            self._aux_key, self._aux_ref = key, (params, grad)
+        if params is None or pair is None:
+            return
+        pair = (float(pair[0]), float(pair[1]))
+        if pair != self.aux_host:
+            self.aux_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
+            self.aux_host = pair
 
     def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
         """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's

@@ -14,6 +14,7 @@ import torch
 from utils import get_config, get_text
 
 EMOTIONS = {"neutral": 0, "joy": 1, "sadness": 2, "anger": 3, "surprise": 4, "fear": 5, "disgust": 6}
+SENTIMENTS = {"neutral": 0, "positive": 1, "negative": 2}          # MELD's second label per utterance (runtime.aux_head)
 
 
 def build_dialogue_index(dialogue_ids, utterance_ids):
@@ -82,8 +83,10 @@ def dialogue_speaker_ids(speakers, rows):
 
 class Dataset(torch.utils.data.Dataset):
     def __init__(self, mode="train", text_embeddings=None, audio_embeddings=None, table=None, token_ids=None, token_mask=None,
-                 waveforms=None, speakers=False):
-        """speakers (runtime.speaker_heads is set): items ALSO carry "speaker" - int64 [n], `dialogue_speaker_ids` of the table's
+                 waveforms=None, speakers=False, sentiment=False):
+        """sentiment (runtime.aux_head is enabled): items ALSO carry "sentiment" - int64 [n], `SENTIMENTS` of the table's `Sentiment`
+        column, anything else -1 - and batches "sentiment" int64 [B, L], padded with -1 like the emotion.
+        speakers (runtime.speaker_heads is set): items ALSO carry "speaker" - int64 [n], `dialogue_speaker_ids` of the table's
         `Speaker` column - and batches "speaker" int64 [B, L], padded with 0 (M2FNet(speaker_heads=...) reads them; pad slots are ignored).
         token_ids / token_mask ([N, S] int64, rows = table rows; `tokenised_contexts`): items and batches ALSO carry "text_ids" /
         "text_mask" - what the in-loop text encoder consumes instead of the pre-extracted "text" rows (`runtime.text_encoder`).
@@ -110,6 +113,11 @@ class Dataset(torch.utils.data.Dataset):
         self.dialogue_ids, self.rows = build_dialogue_index(self.text["Dialogue_ID"].to_numpy(),
                                                             self.text["Utterance_ID"].to_numpy())
         self._labels = torch.as_tensor(self.text["Emotion"].to_numpy().astype(np.int64))
+        self._sentiment = None
+        if sentiment:
+            if "Sentiment" not in self.text:
+                raise ValueError(f"runtime.aux_head needs the Sentiment column of the {mode} table")
+            self._sentiment = torch.as_tensor(np.asarray([SENTIMENTS.get(v, -1) for v in self.text["Sentiment"].tolist()], dtype=np.int64))
         self._speakers = None
         if speakers:
             if "Speaker" not in self.text:
@@ -129,6 +137,8 @@ class Dataset(torch.utils.data.Dataset):
             item["wave"] = [self.waveforms[r] for r in rows.tolist()]
         if self._speakers is not None:
             item["speaker"] = self._speakers[rows]
+        if self._sentiment is not None:
+            item["sentiment"] = self._sentiment[rows]
         if self.token_ids is not None:
             item["text_ids"] = self.token_ids[rows]
             item["text_mask"] = self.token_mask[rows] if self.token_mask is not None else torch.ones_like(item["text_ids"])
@@ -166,6 +176,11 @@ def collate_fn(batch):
         for i, d in enumerate(batch):
             speaker[i, : d["speaker"].shape[0]] = d["speaker"]
         out["speaker"] = speaker
+    if "sentiment" in batch[0]:                                    # the auxiliary head's labels: -1 on pads, as the emotion
+        sentiment = torch.full((B, L), -1, dtype=torch.int64)
+        for i, d in enumerate(batch):
+            sentiment[i, : d["sentiment"].shape[0]] = d["sentiment"]
+        out["sentiment"] = sentiment
     if "wave" in batch[0]:
         # in-loop audio encoder: the waveforms of all utterances of the batch, zero-padded to the longest ([n, N] fp32), their sample
         # counts, and where each goes in the [B, L] grid (flat index b * L + t)

@@ -43,6 +43,13 @@ def load_model_weights(model, checkpoint_path, device, averaged: bool = False):
             raise ValueError("solver.loss_fn is CRF but the checkpoint holds no 'crf_state_dict'")
         crf.load_state_dict(state["crf_state_dict"])
         print("Decoding with the checkpoint's CRF (crf_state_dict)")
+    head = getattr(model, "aux_head", None)                 # (runtime.aux_head; set by main())
+    if head is not None:
+        if "aux_head_state_dict" in state:
+            head.load_state_dict(state["aux_head_state_dict"])
+            print("Reporting the accuracy of the checkpoint's auxiliary head (aux_head_state_dict)")
+        else:
+            print("The checkpoint holds no 'aux_head_state_dict': the auxiliary accuracy is that of an untrained head")
     return state.get("epoch")
 
 
@@ -196,24 +203,36 @@ def test(model, dl_test, device):
         focal = {} if gamma is None else {"focal_gamma": gamma}
         if getattr(model, "crf", None) is not None:        # (the CRF loss and the Viterbi path)
             focal = {"label_smoothing": 0.0, "crf": model.crf}
+        from train import AuxAccuracy
+        aux_acc = AuxAccuracy(model)
         with torch.inference_mode():
             for batch in tqdm(dl_test, total=len(dl_test)):
                 text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                                audio_encoder=getattr(model, "audio_encoder", None))
                 model.eval_step(text, audio, padding_mask, emotion, scores, **_speaker_kw(model, batch, device), **focal)
+                aux_acc.update(model, batch, device)
                 maps.add(padding_mask)
         model.test_scores = scores
         maps.write()
+        if aux_acc.result() is not None:
+            model.aux_test_accuracy = aux_acc.result()
+            print(f"Aux_accuracy=[{aux_acc.result() * 100:.3f}%]")
         return scores.result()
     scores = BatchScores()
+    from train import AuxAccuracy
+    aux_acc = AuxAccuracy(model)                              # (runtime.aux_head: the head's accuracy beside the emotion scores)
     with torch.inference_mode():
         for batch in tqdm(dl_test, total=len(dl_test)):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             logits = model(text, audio, padding_mask, **_speaker_kw(model, batch, device))
             scores.update(decoded(getattr(model, "crf", None), logits, padding_mask), emotion)
+            aux_acc.update(model, batch, device)
             maps.add(padding_mask)
     maps.write()
+    if aux_acc.result() is not None:
+        model.aux_test_accuracy = aux_acc.result()
+        print(f"Aux_accuracy=[{aux_acc.result() * 100:.3f}%]")
     return scores.result()
 
 
@@ -237,6 +256,8 @@ def main(config=None):
     context_settings(config)                               # (refusal before the GPU is touched)
     position_bias_settings(config)
     spk_on = speaker_heads_settings(config) is not None    # (the test table then yields "speaker" ids)
+    from train import aux_head_settings
+    aux_on = aux_head_settings(config)                     # (the test table then yields the second label; refuses the device batcher)
     streaming = streaming_settings(config)
     stream_chunk = stream_chunk_settings(config)
     stream_pages = stream_pages_settings(config)
@@ -247,8 +268,8 @@ def main(config=None):
     if runtime_cfg.get("device_batcher", False):
         loader = DeviceLoader(Dataset(mode="test"), device=device, **config.test.data_loader)
     else:
-        loader = torch.utils.data.DataLoader(Dataset(mode="test", **({"speakers": True} if spk_on else {})), collate_fn=collate_fn,
-                                             **config.test.data_loader)
+        ds_kw = dict(({"speakers": True} if spk_on else {}), **({aux_on["labels"]: True} if aux_on is not None else {}))
+        loader = torch.utils.data.DataLoader(Dataset(mode="test", **ds_kw), collate_fn=collate_fn, **config.test.data_loader)
     model = build_model(config, device)
     model.device_metrics = bool(runtime_cfg.get("device_metrics", False))
     model.streaming = streaming
@@ -261,6 +282,9 @@ def main(config=None):
     # (solver.loss_fn: Focal - the device record's loss is the criterion that trained, with runtime.focal_gamma; accuracy and F1 do not depend on it)
     model.focal_gamma = focal_gamma_setting(config) if config.solver.loss_fn == "Focal" else None
     ema = ema_settings(config)
+    # (runtime.aux_head - the head comes from the checkpoint's 'aux_head_state_dict'; the pass also prints its accuracy)
+    from train import attach_aux_head
+    attach_aux_head(model, aux_on, config.model.CLASSIFIER.hidden_size, device, with_optimizer=False)
     load_model_weights(model, config.checkpoint.load_path, device, averaged=ema is not None and ema[2])
     print("Testing...")
     accuracy, weighted_f1 = test(model, loader, device)

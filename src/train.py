@@ -36,6 +36,7 @@ except ImportError:
     wandb = None
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict")
+AUX_KEY = "aux_head_state_dict"                         # present only under runtime.aux_head.enabled (the AuxiliaryHead's weight and bias)
 CRF_KEY = "crf_state_dict"                              # present only under solver.loss_fn: CRF (the LinearChainCRF block)
 EMA_KEY = "ema_state_dict"                              # present only when runtime.ema is enabled
 N_CLASSES = 7
@@ -334,6 +335,144 @@ class _SupConLog:
         self.ce += ce.item()
         self.con += con.item()
         return {"Train/CE": self.ce / (step + 1), "Train/SupCon": self.con / (step + 1)}
+
+
+AUX_KEYS = ("enabled", "labels", "weight", "label_smoothing", "lr", "warmup_steps")
+AUX_LABEL_COLUMNS = {"sentiment": 3}                    # batch key -> classes (dataset.SENTIMENTS)
+
+
+def aux_head_settings(cfg):
+    """`runtime.aux_head` = {enabled: False, labels: sentiment, weight: 0.5, label_smoothing: 0.0, lr: 1.0e-3, warmup_steps: 0}: train()
+    trains a second linear head over the classifier's hidden features against the table's second label inside the step
+    (M2FNet.train_step(aux=)).  -> None when the block is absent or disabled, else {labels, weight, label_smoothing, lr, warmup_steps}.
+    Checked on the host before the GPU is touched: needs runtime.device_batcher: False (the DataLoader path carries the second label),
+    runtime.fused_step: True, solver.loss_fn: CE or Focal, no runtime.distill / rdrop / supcon, runtime.grad_accumulation 1 and one
+    process (the head trains: its gradient is normalised by one batch's den and is not all-reduced)."""
+    from mer_amd.aux_head import check_pair
+    block = _runtime(cfg, "aux_head", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.aux_head must be a mapping {{{', '.join(AUX_KEYS)}}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - set(AUX_KEYS))
+    if unknown:
+        raise ValueError(f"runtime.aux_head: unknown key(s) {unknown} ({', '.join(AUX_KEYS)})")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.aux_head.enabled must be true or false (got {enabled!r})")
+    labels = block.get("labels", "sentiment")
+    if labels not in AUX_LABEL_COLUMNS:
+        raise ValueError(f"runtime.aux_head.labels must be one of {sorted(AUX_LABEL_COLUMNS)} (got {labels!r})")
+    weight, smoothing = check_pair(block.get("weight", 0.5), block.get("label_smoothing", 0.0), "runtime.aux_head")
+    lr = block.get("lr", 1.0e-3)
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not (math.isfinite(lr) and lr > 0.0):
+        raise ValueError(f"runtime.aux_head.lr must be a finite number > 0 (got {lr!r})")
+    warm = block.get("warmup_steps", 0)
+    if isinstance(warm, bool) or not isinstance(warm, int) or warm < 0:
+        raise ValueError(f"runtime.aux_head.warmup_steps must be an integer >= 0 (got {warm!r})")
+    if not enabled:
+        return None
+    if bool(_runtime(cfg, "device_batcher", False)):
+        raise ValueError("runtime.aux_head.enabled needs runtime.device_batcher: False (the device batcher gathers the emotion label only; "
+                         "the DataLoader path carries the second label)")
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.aux_head.enabled needs runtime.fused_step: True (the auxiliary head lives in the train step)")
+    solver = cfg.get("solver", None) if isinstance(cfg, dict) else getattr(cfg, "solver", None)
+    loss_fn = None if solver is None else (solver.get("loss_fn", "CE") if hasattr(solver, "get") else getattr(solver, "loss_fn", "CE"))
+    if loss_fn not in (None, "CE", "Focal"):
+        raise ValueError(f"runtime.aux_head.enabled needs solver.loss_fn: CE or Focal (got {loss_fn!r}: the CRF criterion has no auxiliary form)")
+    if resolve_distill(cfg) is not None:
+        raise ValueError("runtime.aux_head.enabled does not combine with runtime.distill.enabled (the auxiliary head has no distillation form)")
+    if rdrop_settings(cfg) is not None:
+        raise ValueError("runtime.aux_head.enabled does not combine with runtime.rdrop.enabled (both write the criterion tail's fourth float)")
+    if supcon_settings(cfg) is not None:
+        raise ValueError("runtime.aux_head.enabled does not combine with runtime.supcon.enabled (both join the backward at the hidden activation's gradient)")
+    if int(_runtime(cfg, "grad_accumulation", 1) or 1) > 1:
+        raise ValueError("runtime.aux_head.enabled does not combine with runtime.grad_accumulation > 1 (the head trains: its gradient would need the group's den)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("runtime.aux_head.enabled runs in one process (the head trains: the data-parallel step does not all-reduce its gradient)")
+    return {"labels": labels, "weight": weight, "label_smoothing": smoothing, "lr": float(lr), "warmup_steps": warm}
+
+
+def attach_aux_head(model, settings, hidden_size: int, device, with_optimizer: bool = True) -> None:
+    """Under runtime.aux_head the head travels on the model as `model.aux_head` (object.__setattr__: not a sub-module - its block is neither
+    in M2FNet's state_dict nor in the model's optimizer), with its settings and the torch Adam that steps its block behind the model's
+    optimizer, as the CRF's (with_optimizer False - test.py: `head.optimizer` is None); checkpoints then carry it as
+    'aux_head_state_dict'.  settings None: `model.aux_head` is None."""
+    head = None
+    if settings is not None:
+        from mer_amd.aux_head import AuxiliaryHead
+        head = AuxiliaryHead(int(hidden_size), AUX_LABEL_COLUMNS[settings["labels"]]).to(device)
+        head.settings = dict(settings)
+        head.optimizer = torch.optim.Adam(head.parameters(), lr=settings["lr"]) if with_optimizer else None
+    object.__setattr__(model, "aux_head", head)
+
+
+def _aux_zero_grad(aux) -> None:
+    """`aux`: what `_aux_kw` returned.  The head's own optimizer, in front of the step (nothing without a head)."""
+    if aux and getattr(aux["aux"][0], "optimizer", None) is not None:
+        aux["aux"][0].optimizer.zero_grad()
+
+
+def _aux_step(aux) -> None:
+    """The head's own optimizer, behind the model's (its gradient is the step's own buffer); nothing without a head."""
+    if aux and getattr(aux["aux"][0], "optimizer", None) is not None:
+        aux["aux"][0].optimizer.step()
+
+
+def _aux_kw(model, batch, device, global_step: int):
+    """{aux: (head, labels, weight), aux_label_smoothing} of optimizer step `global_step` for train_step when main() hung an auxiliary
+    head on the model (`model.aux_head`), else nothing - the calls of a run without it are today's.  warmup_steps = n: weight *
+    (step + 1) / n until n."""
+    head = getattr(model, "aux_head", None)
+    if head is None:
+        return {}
+    r = head.settings
+    if r["labels"] not in batch:
+        raise ValueError(f"runtime.aux_head: the batch carries no {r['labels']!r} (Dataset({r['labels']}=True) and runtime.device_batcher: False are needed)")
+    n = r["warmup_steps"]
+    weight = r["weight"] * min(1.0, (global_step + 1) / n) if n > 0 else r["weight"]
+    return {"aux": (head, batch[r["labels"]].to(device, non_blocking=True), weight), "aux_label_smoothing": r["label_smoothing"]}
+
+
+class _AuxLog:
+    """Running means of the two shares of the loss for wandb: {"Train/CE", "Train/Aux"} beside Train/Running_loss (CE + weight * Aux at
+    a constant weight).  Reads `model.aux_terms()` only when something is logged."""
+
+    def __init__(self, model, on: bool):
+        self.model, self.on = model, on and getattr(model, "aux_head", None) is not None
+        self.ce = self.aux = 0.0
+
+    def __call__(self, step: int):
+        if not self.on:
+            return {}
+        ce, aux = self.model.aux_terms()
+        self.ce += ce.item()
+        self.aux += aux.item()
+        return {"Train/CE": self.ce / (step + 1), "Train/Aux": self.aux / (step + 1)}
+
+
+class AuxAccuracy:
+    """The auxiliary head's accuracy over an evaluation pass, on the host: `update(model, batch, device)` behind a batch's forward counts
+    `head(model.last_features()).argmax` against the batch's second label over the utterances that carry one.  Off (every call a
+    no-op, `result()` None) when the model has no head or the batches no such label."""
+
+    def __init__(self, model):
+        self.head = getattr(model, "aux_head", None)
+        self.hits = self.count = 0
+
+    def update(self, model, batch, device) -> None:
+        if self.head is None or self.head.settings["labels"] not in batch:
+            return
+        labels = batch[self.head.settings["labels"]].to(device)
+        with torch.no_grad():
+            pred = self.head(model.last_features()).argmax(-1)
+        ok = labels >= 0
+        self.hits += int(((pred == labels) & ok).sum())
+        self.count += int(ok.sum())
+
+    def result(self):
+        return self.hits / self.count if self.count else None
 
 
 def _distill_kw(model, text, audio, padding_mask):
@@ -771,6 +910,12 @@ def resume_if_requested(config, model, optimizer, device):
             crf.load_state_dict(state[CRF_KEY])
         elif _rank() == 0:
             print(f"Checkpoint {path} holds no {CRF_KEY}: the CRF block starts from its initialisation")
+    head = getattr(model, "aux_head", None)
+    if head is not None:
+        if AUX_KEY in state:
+            head.load_state_dict(state[AUX_KEY])
+        elif _rank() == 0:
+            print(f"Checkpoint {path} holds no {AUX_KEY}: the auxiliary head starts from its initialisation")
     if ema_settings(config) is not None:
         if EMA_KEY in state:
             optimizer.load_ema_state_dict(state[EMA_KEY])
@@ -797,6 +942,8 @@ def write_checkpoint(path, epoch, model, optimizer):
         state[EMA_KEY] = optimizer.ema_state_dict()
     if getattr(model, "crf", None) is not None:           # (solver.loss_fn: CRF - the block is not in the model's state_dict)
         state[CRF_KEY] = model.crf.state_dict()
+    if getattr(model, "aux_head", None) is not None:      # (runtime.aux_head - likewise outside the model's state_dict)
+        state[AUX_KEY] = model.aux_head.state_dict()
     torch.save(state, path)
 
 
@@ -815,6 +962,7 @@ def main(config=None):
     resolve_distill(config)
     rdrop_settings(config)
     supcon_settings(config)
+    aux_on = aux_head_settings(config)
     focal_gamma_setting(config)
     crf_settings(config)
     watch_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
@@ -836,6 +984,9 @@ def main(config=None):
     if spk_on:
         for mode in ds_kw:
             ds_kw[mode]["speakers"] = True                 # (batches then carry "speaker")
+    if aux_on is not None:
+        for mode in ds_kw:
+            ds_kw[mode][aux_on["labels"]] = True           # (batches then carry the second label)
     if ae_on:
         # waveforms of every table row, read once (dia{D}_utt{U}.wav); the audio pickle is not read
         if not ae_cfg.get("wav_dir", None):
@@ -894,6 +1045,7 @@ def main(config=None):
     attach_distiller(config, model, device)
     object.__setattr__(model, "rdrop", rdrop_settings(config))       # (None: off; train() passes rdrop= on in every branch)
     object.__setattr__(model, "supcon", supcon_settings(config))     # (None: off; train() passes supcon= on to train_step)
+    attach_aux_head(model, aux_on, config.model.CLASSIFIER.hidden_size, device)      # (None: off; train() passes aux= on to train_step)
     criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config), crf=crf_settings(config))
     attach_crf(model, criterion)
     optimizer = build_optimizer(config, model)
@@ -991,9 +1143,13 @@ def training_loop(model, dl_train, dl_val, criterion, optimizer, lr_scheduler, s
         if rank0:
             print(f"Epoch: {epoch} lr: {lr_now:.3E} Train=[{train_loss:.3E}] Val=[{val_loss:.3E}] "
                   f"Accuracy=[{accuracy * 100:.3f}%] Weighted_F1=[{weighted_f1 * 100:.3f}%]")
+        aux_accuracy = getattr(model, "aux_val_accuracy", None)          # (runtime.aux_head: the head's accuracy of this validation pass)
+        if rank0 and aux_accuracy is not None:
+            print(f"Epoch: {epoch} Aux_accuracy=[{aux_accuracy * 100:.3f}%]")
         if log_to_wandb:
             wandb.log({"Params/Epoch": epoch, "Params/Learning_Rate": lr_now, "Train/Loss": train_loss,
-                       "Validation/Loss": val_loss, "Validation/Accuracy": accuracy, "Validation/Weighted_F1": weighted_f1})
+                       "Validation/Loss": val_loss, "Validation/Accuracy": accuracy, "Validation/Weighted_F1": weighted_f1,
+                       **({} if aux_accuracy is None else {"Validation/Aux_accuracy": aux_accuracy})})
         if stopper.should_stop(val_loss, epoch, model, optimizer):
             break
     if log_to_wandb:
@@ -1045,6 +1201,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     running = 0.0
     rdrop_log = _RDropLog(model, bool(wandb_log))
     supcon_log = _SupConLog(model, bool(wandb_log))
+    aux_log = _AuxLog(model, bool(wandb_log))
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
         text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
@@ -1055,6 +1212,9 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         supcon = _supcon_kw(model, epoch * len(dl_train) + step)
         if supcon and (not fused or dp_step is not None):
             raise ValueError("runtime.supcon needs runtime.fused_step: True, the M2FCrossEntropyLoss criterion and one process")
+        aux = _aux_kw(model, batch, device, epoch * len(dl_train) + step)
+        if aux and (not fused or dp_step is not None):
+            raise ValueError("runtime.aux_head needs runtime.fused_step: True, the M2FCrossEntropyLoss criterion and one process")
         if dp_step is not None:
             # sharded step: local sum-gradient -> RCCL all-reduce with the global denominator -> fused Adam, all inside
             loss = dp_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
@@ -1062,20 +1222,22 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         else:
             optimizer.zero_grad()
             _crf_zero_grad(criterion)
+            _aux_zero_grad(aux)
             if fused and getattr(model, "fused_optimizer", False) and isinstance(optimizer, FusedAdam):
                 # forward, criterion, backward AND optimizer.step() as one launch list (src/train.py:227-231 of the reference)
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, optimizer=optimizer,
                                         **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
-                                        **_crit_kw(criterion), **rdrop, **supcon)
+                                        **_crit_kw(criterion), **rdrop, **supcon, **aux)
                 _crf_step(criterion)
+                _aux_step(aux)
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                               **_grad_norm_log(optimizer), **rdrop_log(step), **supcon_log(step)})
+                               **_grad_norm_log(optimizer), **rdrop_log(step), **supcon_log(step), **aux_log(step)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
-                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop, **supcon)
+                                        **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop, **supcon, **aux)
             else:
                 if getattr(model, "distiller", None) is not None:
                     raise ValueError("runtime.distill needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
@@ -1083,11 +1245,12 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 loss.backward()
             optimizer.step()
             _crf_step(criterion)
+            _aux_step(aux)
         running += loss.item()
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step)})
+                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step), **aux_log(step)})
     return running / len(dl_train)
 
 
@@ -1099,6 +1262,8 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
     optimizer steps of the group losses num / den."""
     if not fused:
         raise ValueError("runtime.grad_accumulation > 1 needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+    if getattr(model, "aux_head", None) is not None:
+        raise ValueError("runtime.aux_head does not combine with runtime.grad_accumulation > 1 (the head trains: its gradient would need the group's den)")
     if dp_step is None:
         model.set_grad_accumulation(True)
     n_groups = (len(dl_train) + k - 1) // k
@@ -1163,6 +1328,13 @@ def decoded(crf, logits, padding_mask):
     return torch.nn.functional.one_hot(path.clamp(min=0), logits.shape[-1]).to(logits.dtype)
 
 
+def _note_aux_accuracy(model, aux_acc) -> None:
+    """The auxiliary head's accuracy of a validation pass (runtime.aux_head) travels on the model as `model.aux_val_accuracy` for the
+    epoch's print and wandb line.  Nothing without a head: the pass of a run without it is today's."""
+    if aux_acc.head is not None:
+        model.aux_val_accuracy = aux_acc.result()
+
+
 def validate(model, dl_val, criterion, device):
     """-> (mean batch loss, accuracy, weighted_f1); scores by the per-batch rule of ``metrics.BatchScores``.
     With several ranks the replicas are identical and the rule is a plain mean over the reference's batches
@@ -1176,6 +1348,7 @@ def validate(model, dl_val, criterion, device):
     if getattr(model, "device_metrics", False):
         return _validate_on_device(model, dl_val, criterion, device, rank, world)
     scores, loss_total = BatchScores(), 0.0
+    aux_acc = AuxAccuracy(model)
     with torch.inference_mode():
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
@@ -1183,6 +1356,8 @@ def validate(model, dl_val, criterion, device):
             logits = model(text, audio, padding_mask, **_speaker_kw(model, batch, device))
             loss_total += criterion(logits.permute(0, 2, 1), emotion).item()
             scores.update(decoded(criterion, logits, padding_mask), emotion)
+            aux_acc.update(model, batch, device)
+    _note_aux_accuracy(model, aux_acc)
     acc_sum, f1_sum = scores.sums()
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks([loss_total, acc_sum, f1_sum, float(scores.n_batches)], device=device)
     n = max(n, 1.0)
@@ -1195,12 +1370,15 @@ def _validate_on_device(model, dl_val, criterion, device, rank, world):
         raise ValueError("runtime.device_metrics: True scores with the M2FCrossEntropyLoss criterion's kernel; another criterion needs the host loop")
     scores = DeviceScores(model.m2f_config.cls_out, device)
     _, use_graph = _step_mode(model, criterion)
+    aux_acc = AuxAccuracy(model)
     with torch.inference_mode():
         for batch in tqdm(_rank_share(dl_val, rank, world), total=(len(dl_val) - rank + world - 1) // world, desc="Validation", disable=rank != 0):
             text, audio, emotion, padding_mask = move_batch(batch, device, text_encoder=getattr(model, "text_encoder", None),
                                                            audio_encoder=getattr(model, "audio_encoder", None))
             model.eval_step(text, audio, padding_mask, emotion, scores, use_graph=use_graph, **_speaker_kw(model, batch, device),
                             **_crit_kw(criterion))
+            aux_acc.update(model, batch, device)
+    _note_aux_accuracy(model, aux_acc)
     loss_total, acc_sum, f1_sum, n = dp.sum_over_ranks(list(scores.totals()), device=device)      # (the one read of the pass)
     n = max(n, 1.0)
     return loss_total / n, acc_sum / n, f1_sum / n
