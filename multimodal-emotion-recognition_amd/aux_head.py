@@ -48,13 +48,10 @@ def check_pair(weight, label_smoothing, who: str = "train_step") -> Tuple[float,
     return float(weight), float(label_smoothing)
 
 
-def check_step_args(who: str, aux, in_features: int, mask_shape=None, label_smoothing: float = 0.0, teacher_logits=None, distill=None,
-                    crf=None, rdrop=None, supcon=None, accumulating: bool = False, data_parallel: bool = False, device=None):
-    """The host refusals of ``aux=`` in a step: -> (head, aux_labels, weight, label_smoothing) or (aux None) None.  device: where the
-    step runs (the labels must be there; None: not checked).  Every pair the
-    auxiliary head has no form for is a ValueError naming the pair, before any launch.  A host function: no GPU needed."""
-    if aux is None:
-        return None
+def check_step_args(who: str, aux, in_features: int, mask_shape=None, label_smoothing: float = 0.0, device=None):
+    """``aux=`` of a step -> (head, aux_labels, weight, label_smoothing); ValueError unless it is a triple of an AuxiliaryHead over
+    `in_features`, int64 labels of `mask_shape` on `device` (where the step runs; None: not checked) and a valid weight.  What the
+    auxiliary head is refused beside is criterion.RULES' business.  A host function: no GPU needed."""
     if not isinstance(aux, (tuple, list)) or len(aux) != 3:
         raise ValueError(f"{who}: aux= must be a triple (head, aux_labels, weight), got {type(aux).__name__}")
     head, labels, weight = aux
@@ -69,21 +66,7 @@ def check_step_args(who: str, aux, in_features: int, mask_shape=None, label_smoo
         raise ValueError(f"{who}: aux= labels must be int64 {list(mask_shape) if mask_shape is not None else '[B, L]'}, laid out like emotion (got {got})")
     if device is not None and labels.device != torch.device(device):
         raise ValueError(f"{who}: aux= labels are on {labels.device}, the step runs on {device} (move them as emotion is moved)")
-    pair = check_pair(weight, label_smoothing, who)
-    for name, other, why in (("teacher_logits", teacher_logits, "the auxiliary head has no distillation form"),
-                             ("distill", distill, "the auxiliary head has no distillation form"),
-                             ("crf", crf, "the CRF criterion has no auxiliary form"),
-                             ("rdrop", rdrop, "both write the criterion tail's fourth float"),
-                             ("supcon", supcon, "both join the backward at the hidden activation's gradient")):
-        if other is not None:
-            raise ValueError(f"{who}: aux and {name} do not combine ({why})")
-    if head.trainable and accumulating:
-        raise ValueError(f"{who}: a trainable aux= head does not combine with gradient accumulation (its gradient would need the "
-                         "group's den); freeze it with head.params.requires_grad_(False)")
-    if head.trainable and data_parallel:
-        raise ValueError(f"{who}: a trainable aux= head does not combine with DataParallelStep (its gradient would need an all-reduce); "
-                         "freeze it with head.params.requires_grad_(False)")
-    return head, labels, pair[0], pair[1]
+    return (head, labels) + check_pair(weight, label_smoothing, who)
 
 
 class _HeadFunction(torch.autograd.Function):

@@ -67,30 +67,14 @@ def label_count_params(labels, lengths, num_classes: int, smoothing: float = 1.0
     return block.astype(np.float32)
 
 
-def check_step_args(who: str, crf, num_classes: int, class_weights=None, teacher_logits=None, distill=None, focal_gamma=None,
-                    label_smoothing: float = 0.0, accumulating: bool = False, data_parallel: bool = False) -> None:
-    """The host refusals of ``crf=`` in a step: every pair the CRF criterion has no form for is a ValueError naming the pair, before any
-    launch.  A host function: no GPU needed."""
-    if crf is None:
-        return
+def check_step_args(who: str, crf, num_classes: int) -> "LinearChainCRF":
+    """``crf=`` of a step or a stream: ValueError unless it is a LinearChainCRF over the classifier's classes.  What the CRF criterion is
+    refused beside is criterion.RULES' business.  A host function: no GPU needed."""
     if not isinstance(crf, LinearChainCRF):
         raise ValueError(f"{who}: crf= must be a LinearChainCRF (got {type(crf).__name__})")
     if crf.num_classes != num_classes:
         raise ValueError(f"{who}: crf= has {crf.num_classes} classes, the model's classifier has {num_classes}")
-    if class_weights is not None:
-        raise ValueError(f"{who}: crf= does not combine with class_weights (the CRF criterion has no class-weighted form)")
-    if teacher_logits is not None or distill is not None:
-        raise ValueError(f"{who}: crf= does not combine with teacher_logits / distill (the CRF criterion has no distillation form)")
-    if focal_gamma is not None:
-        raise ValueError(f"{who}: crf= does not combine with focal_gamma (the CRF criterion has no focal form)")
-    if label_smoothing != 0.0:
-        raise ValueError(f"{who}: crf= does not combine with label_smoothing != 0.0 (got {label_smoothing!r}); pass label_smoothing=0.0")
-    if crf.trainable and accumulating:
-        raise ValueError(f"{who}: a trainable crf= does not combine with gradient accumulation (its gradient would need the group's "
-                         "den); freeze it with crf.params.requires_grad_(False)")
-    if crf.trainable and data_parallel:
-        raise ValueError(f"{who}: a trainable crf= does not combine with DataParallelStep (its gradient would need an all-reduce); "
-                         "freeze it with crf.params.requires_grad_(False)")
+    return crf
 
 
 class _CRFFunction(torch.autograd.Function):

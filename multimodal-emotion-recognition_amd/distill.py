@@ -121,16 +121,13 @@ class Distiller:
         focal_gamma= (in ``kw``) goes to the student's step: the focal factor scales its hard-label term, the teacher term stays.
         rdrop=, supcon= and aux= are refused by name: none of them has a distillation form."""
         pair = check_distill((self.alpha, self.temperature), "Distiller")          # (before the teacher runs)
-        if kw.get("supcon") is not None:
-            raise ValueError("Distiller.train_step: supcon and distill do not combine (the supervised contrastive criterion has no "
-                             "distillation form)")
-        if kw.get("aux") is not None:
-            raise ValueError("Distiller.train_step: aux and distill do not combine (the auxiliary head has no distillation form)")
-        if kw.get("rdrop") is not None:
-            raise ValueError("Distiller.train_step: rdrop and distill do not combine (the R-Drop criterion has no distillation form)")
-        if kw.get("focal_gamma") is not None:
-            from .runtime import check_focal_gamma
-            kw["focal_gamma"] = check_focal_gamma(kw["focal_gamma"], "focal_gamma", "Distiller.train_step")
+        from .criterion import resolve
+        c = self.student.m2f_config
+        spec = resolve("Distiller.train_step", num_classes=c.cls_out, cls_hidden=c.cls_hidden, mask_shape=mask.shape, device=mask.device,
+                       label_smoothing=None, class_weights=None, distilling=True,       # (neither is looked at before the teacher runs)
+                       **{name: kw.get(name) for name in ("focal_gamma", "rdrop", "supcon", "aux")})
+        if spec.gamma is not None:
+            kw["focal_gamma"] = spec.gamma
         s_on, t_on = self.student.speaker_heads is not None, self.teacher.speaker_heads is not None
         if speakers is not None and not (s_on or t_on):
             raise ValueError("Distiller.train_step: speakers were given, but neither the student nor the teacher has speaker heads")

@@ -436,10 +436,9 @@ class DataParallelStep:
         if overlap is None:
             overlap = os.environ.get("M2F_DP_OVERLAP", "0") == "1"
         _refuse_speaker_heads(model)          # (before the engine, the reducer or any collective)
-        from .crf import check_step_args
-        check_step_args("DataParallelStep", crf, model.m2f_config.cls_out, data_parallel=True)
         self.crf = crf
         self.model, self.optimizer, self.overlap = model, optimizer, bool(overlap)
+        self._resolve(None, 0.0, None)        # (its own crf: a LinearChainCRF of the model's classes, frozen)
         self.grad_bf16 = (os.environ.get("M2F_GRAD_BF16", "1") != "0") if grad_bf16 is None else bool(grad_bf16)
         self._split: Optional[int] = None
         self._pending = False          # micro-batches of this rank since the last synced call wrote the gradient buffer (sync=False)
@@ -478,6 +477,14 @@ class DataParallelStep:
         if eng.grad_bf16_buf is not None:
             self.model.set_grad_bf16(False)
 
+    def _resolve(self, mask, label_smoothing, class_weights, **criterion_args):
+        """``criterion.resolve`` for a step of this object (its crf among the arguments); mask None: the constructor's check."""
+        from .criterion import resolve
+        c = self.model.m2f_config
+        return resolve("DataParallelStep", num_classes=c.cls_out, cls_hidden=c.cls_hidden, mask_shape=None if mask is None else mask.shape,
+                       device=None if mask is None else mask.device, label_smoothing=label_smoothing, class_weights=class_weights,
+                       data_parallel=True, crf=self.crf, **criterion_args)
+
     def __call__(self, text, audio, mask, emotion, label_smoothing: float = 0.1, class_weights=None,
                  use_graph: bool = True, sync: bool = True, teacher_logits=None, distill=None, focal_gamma=None,
                  rdrop=None, supcon=None, aux=None, aux_label_smoothing: float = 0.0) -> torch.Tensor:
@@ -496,25 +503,11 @@ class DataParallelStep:
         synced one overwrites, later ones accumulate, den / num of the tail too), no collective, no optimizer step; returns the
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
-        from . import runtime
-        from .distill import resolve_distill_args
         _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
-        if supcon is not None:
-            raise ValueError("DataParallelStep: supcon is refused (the supervised contrastive criterion contrasts the whole batch; a "
-                             "per-shard contrast set is a different objective - run it on one device through M2FNet.train_step)")
-        alpha = runtime.check_rdrop_args("DataParallelStep", rdrop, teacher_logits, distill, focal_gamma, self.crf)
-        from .aux_head import check_step_args as check_aux_args
-        ax = check_aux_args("DataParallelStep", aux, self.model.m2f_config.cls_hidden, mask.shape, aux_label_smoothing, teacher_logits, distill,
-                            self.crf, rdrop, supcon, data_parallel=True, device=mask.device)
-        if ax is not None:
-            self.model._aux_weight, self.model._aux_classes = ax[2], ax[0].num_classes
+        spec = self._resolve(mask, label_smoothing, class_weights, teacher_logits=teacher_logits, distill=distill, focal_gamma=focal_gamma,
+                             rdrop=rdrop, supcon=supcon, aux=aux, aux_label_smoothing=aux_label_smoothing)
+        self.model._last_criterion = spec
         B, L = mask.shape
-        dist = resolve_distill_args(teacher_logits, distill, B, L, self.model.m2f_config.cls_out, mask.device, "DataParallelStep")
-        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "DataParallelStep")
-        if self.crf is not None:
-            from .crf import check_step_args
-            check_step_args("DataParallelStep", self.crf, self.model.m2f_config.cls_out, class_weights, teacher_logits, distill,
-                            focal_gamma, label_smoothing, data_parallel=True)
         eng = self.model.engine()
         if self.overlap and self.reducer.world() > 1:
             _refuse_clipped_split(self.optimizer)     # (before any launch or collective: every rank refuses alike)
@@ -541,10 +534,9 @@ class DataParallelStep:
                 loss = self.reducer.global_loss()
             cur.wait_stream(eng.stream)
             return loss
-        if alpha is not None:                         # this rank's shard twice: view 0, then view 1
+        if spec.rdrop is not None:                    # this rank's shard twice: view 0, then view 1
             with torch.cuda.stream(eng.stream):
                 text, audio, mask, emotion = (None if x is None else torch.cat([x, x], 0) for x in (text, audio, mask, emotion))
-            self.model._rdrop_alpha = alpha
             B = 2 * B
         plan = eng.plan(B, L, True, self.model.training and self.model.m2f_config.dropout > 0.0)
         with torch.cuda.stream(eng.stream):
@@ -552,7 +544,7 @@ class DataParallelStep:
                             mask, emotion)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self.model._set_criterion(plan, teacher_logits, dist, gamma, self.crf, alpha, None, ax)
+            plan.set_criterion(spec)
             if self._pending or plan._acc:
                 plan.accumulate_grads(self._pending)  # (the first micro-batch of a group overwrites; plans not in a group: today's form)
             if not sync:

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import runtime
+from .criterion import PLAIN, resolve
 from .layout import M2FConfig, param_specs
 
 
@@ -512,6 +513,7 @@ class M2FNet(nn.Module):
         self.set_speaker_heads(*(speaker_heads if speaker_heads is not None else (None,)))
         self._engine: Optional[_Engine] = None
         self._grad_accumulation = False
+        self._last_criterion = PLAIN                       # the criterion.Criterion of the last train step (M2FNet's or a DataParallelStep's)
 
     # -- device plumbing -------------------------------------------------------------------------------
     def _apply(self, fn, *args, **kwargs):
@@ -623,7 +625,7 @@ class M2FNet(nn.Module):
         det = lambda x: x.detach() if isinstance(x, torch.Tensor) else x          # noqa: E731
         plan.set_inputs(det(text) if self.text_enabled else None, det(audio) if self.audio_enabled else None, mask, speakers=ids)
         if plan.train:
-            plan.set_supcon(None)                  # (the criterion is the caller's here: nothing joins the backward at the hidden features)
+            plan.supcon(False)                     # (the criterion is the caller's here: nothing joins the backward at the hidden features)
             plan.set_aux(None)
         if want_bwd:
             out = _Anchor.apply(eng.anchor, text, audio, self, plan)
@@ -745,39 +747,25 @@ class M2FNet(nn.Module):
         mix freely on one model.  Combines with focal_gamma (the focal factor scales the emotion term only); refused (ValueError naming
         the pair, before any launch) beside teacher_logits / distill, crf, rdrop or supcon, and - a trainable head - under gradient
         accumulation."""
-        from .aux_head import check_step_args as check_aux_args
-        from .crf import check_step_args
-        from .distill import resolve_distill_args
-        alpha = runtime.check_rdrop_args("M2FNet.train_step", rdrop, teacher_logits, distill, focal_gamma, crf)
-        con = runtime.check_supcon_args("M2FNet.train_step", supcon, teacher_logits, distill, focal_gamma, crf, rdrop)
-        ax = check_aux_args("M2FNet.train_step", aux, self.m2f_config.cls_hidden, mask.shape, aux_label_smoothing, teacher_logits, distill, crf,
-                            rdrop, supcon, accumulating=self._engine is not None and self._engine.accumulate, device=mask.device)
-        check_step_args("M2FNet.train_step", crf, self.m2f_config.cls_out, class_weights, teacher_logits, distill, focal_gamma,
-                        label_smoothing, accumulating=self._engine is not None and self._engine.accumulate)
+        spec = self._resolve("M2FNet.train_step", mask, label_smoothing, class_weights, teacher_logits=teacher_logits, distill=distill,
+                             focal_gamma=focal_gamma, crf=crf, rdrop=rdrop, supcon=supcon, aux=aux, aux_label_smoothing=aux_label_smoothing)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
-        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.train_step")
-        dist = resolve_distill_args(teacher_logits, distill, mask.shape[0], mask.shape[1], self.m2f_config.cls_out, mask.device,
-                                    "M2FNet.train_step")
         eng = self.engine(mask.device)
         if optimizer is not None and eng.accumulate:
             raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
                                "gradient accumulation (set_grad_accumulation(True)); call optimizer.step() after the group's micro-batches")
-        if alpha is not None:                            # view 0, then view 1: the ordinary plan of 2B dialogues
+        if spec.rdrop is not None:                       # view 0, then view 1: the ordinary plan of 2B dialogues
             text, audio, mask, emotion, ids = (None if x is None else torch.cat([x, x], 0) for x in (text, audio, mask, emotion, ids))
-            self._rdrop_alpha = alpha
         B, L = mask.shape
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
         plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
-        if con is not None:
-            self._supcon_weight = con[0]
-        if ax is not None:
-            self._aux_weight, self._aux_classes = ax[2], ax[0].num_classes
+        self._last_criterion = spec
 
         def body():
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            self._set_criterion(plan, teacher_logits, dist, gamma, crf, alpha, con, ax)
+            plan.set_criterion(spec)
             if optimizer is None:
                 eng.begin_backward(plan)
                 return plan.step(label_smoothing, class_weights is not None, normalise, use_graph)
@@ -801,62 +789,18 @@ class M2FNet(nn.Module):
         else:
             loss = body()
         eng.publish_grads()
-        if crf is not None:
-            crf.publish_grad()
-        if ax is not None:
-            ax[0].publish_grad()
+        for block in (spec.crf, spec.aux and spec.aux[0]):
+            if block is not None:
+                block.publish_grad()
         eng.note_forward(plan)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
 
-    @staticmethod
-    def _set_criterion(plan, teacher_logits, dist, gamma=None, crf=None, rdrop=None, supcon=None, aux=None) -> None:
-        """The criterion of the plan's next step: the distillation criterion with this batch's teacher rows and `dist` = (alpha,
-        temperature), or (dist None) the plain one; the focal form of either with `gamma`, or (None) not.  After `set_inputs` (a packed
-        plan maps the teacher rows as it mapped the batch).  `crf` (a LinearChainCRF; the callers refused every other criterion argument
-        beside it): the chain criterion over its block, its gradient to the module's buffer when it is trainable and the plan trains.
-        `rdrop` (alpha; likewise alone): the R-Drop criterion over the doubled batch `set_inputs` has just placed.
-        `supcon` ((weight, temperature); likewise alone): the plain criterion plus the contrastive term on the hidden features.
-        `aux` ((head, aux_labels, weight, label smoothing); beside `gamma` at most): the plain or focal criterion plus the auxiliary head's
-        term, its labels placed as `set_inputs` placed the emotion labels."""
-        if plan.train and aux is None:
-            plan.set_aux(None)
-        if plan.train and supcon is None:
-            plan.set_supcon(None)
-        if aux is not None:
-            plan.set_crf(None)
-            plan.distill(False)
-            plan.set_rdrop(None)
-            plan.set_focal(gamma)
-            head, labels, weight, eps = aux
-            plan.set_aux_labels(labels)
-            plan.set_aux(*head.step_buffers(plan.workspace.device, want_grad=plan.train), head.num_classes, (weight, eps))
-            return
-        if supcon is not None:
-            plan.set_crf(None)
-            plan.set_focal(None)
-            plan.distill(False)
-            plan.set_rdrop(None)
-            plan.set_supcon(supcon)
-            return
-        if rdrop is not None:
-            plan.set_crf(None)
-            plan.set_focal(None)
-            plan.distill(False)
-            plan.set_rdrop(rdrop)
-            return
-        if plan.train:
-            plan.set_rdrop(None)
-        if crf is not None:
-            plan.set_focal(None)
-            plan.distill(False)
-            plan.set_crf(*crf.step_buffers(plan.workspace.device, want_grad=plan.train))
-            return
-        plan.set_crf(None)
-        plan.set_focal(gamma)
-        plan.distill(dist is not None)
-        if dist is not None:
-            plan.set_teacher(teacher_logits)
-            plan.set_distill_hyper(*dist)
+    def _resolve(self, who: str, mask, label_smoothing, class_weights, **criterion_args):
+        """``criterion.resolve`` for a step of this model on `mask`'s batch (`who` names the entry point in the refusals)."""
+        c = self.m2f_config
+        return resolve(who, num_classes=c.cls_out, cls_hidden=c.cls_hidden, mask_shape=mask.shape, device=mask.device,
+                       label_smoothing=label_smoothing, class_weights=class_weights,
+                       accumulating=self._engine is not None and self._engine.accumulate, **criterion_args)
 
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,
@@ -872,10 +816,8 @@ class M2FNet(nn.Module):
         crf (a ``crf.LinearChainCRF``): the loss is the CRF loss over the labelled rows (the train kernel's bits), and predictions,
         accuracy, F1 and the confusion matrix come from the Viterbi path over each dialogue's utterances instead of the per-row argmax.
         The same refusals as ``train_step``."""
-        from .crf import check_step_args
-        check_step_args("M2FNet.eval_step", crf, self.m2f_config.cls_out, class_weights, None, None, focal_gamma, label_smoothing)
+        spec = self._resolve("M2FNet.eval_step", mask, label_smoothing, class_weights, evaluating=True, focal_gamma=focal_gamma, crf=crf)
         ids = _check_speakers("M2FNet.eval_step", self._speaker_heads, speakers, mask.shape)
-        gamma = None if focal_gamma is None else runtime.check_focal_gamma(focal_gamma, "focal_gamma", "M2FNet.eval_step")
         if self.training and self.m2f_config.dropout > 0.0:
             raise RuntimeError("M2FNet.eval_step: the model is in training mode with dropout > 0; evaluation scores the model "
                                "without dropout - call model.eval() first")
@@ -890,12 +832,7 @@ class M2FNet(nn.Module):
             plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
             if class_weights is not None:
                 plan.class_w[: class_weights.numel()].copy_(class_weights)
-            if crf is not None:
-                plan.set_focal(None)
-                plan.set_crf(*crf.step_buffers(plan.workspace.device, want_grad=False))
-            else:
-                plan.set_crf(None)
-                plan.set_focal(gamma)
+            plan.set_criterion(spec)
             plan.eval_step(scores.record, label_smoothing, class_weights is not None, use_graph)
 
         if use_graph:                                    # capture / replay on the engine's own stream
@@ -1014,49 +951,44 @@ class M2FNet(nn.Module):
         n = eng.flat.numel()
         return eng.flat_grad_ext[n: n + 3]
 
+    def _term_shares(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(ce, term) from the criterion tail: den, num and, in its fourth float, the sum of the weighted term's rows; the weight is the
+        last step's (``_last_criterion``)."""
+        eng = self.engine()
+        eng.ensure_grad()
+        n = eng.flat.numel()
+        t = eng.flat_grad_ext[n: n + 4]
+        term = t[3] / t[1]
+        return t[2] / t[1] - self._last_criterion.term_weight * term, term
+
     def rdrop_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(ce, kl)`` of the last ``train_step(rdrop=alpha)`` as device scalars: the cross-entropy share of its loss (both views,
         over the one denominator) and the symmetric KL divergence per unit of labelled weight WITHOUT alpha - ``ce + alpha * kl`` is the
         loss.  Read from the criterion tail (den, num and, in its fourth float, the sum of ``w_y * s``, reduced in a fixed order): with
         accumulation on they cover the group's micro-batches, and behind a data-parallel step's all-reduce of the tail they are the
         global values.  alpha is the last step's."""
-        eng = self.engine()
-        eng.ensure_grad()
-        n = eng.flat.numel()
-        t = eng.flat_grad_ext[n: n + 4]
-        kl = t[3] / t[1]
-        return t[2] / t[1] - getattr(self, "_rdrop_alpha", 0.0) * kl, kl
+        return self._term_shares()
 
     def supcon_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(ce, con)`` of the last ``train_step(supcon=(weight, temperature))`` as device scalars: the cross-entropy share of its
         loss and the contrastive term per unit of labelled weight WITHOUT the weight - ``ce + weight * con`` is the loss.  Read from the
         criterion tail (den, num and, in its fourth float, the sum of ``w_y * l``, reduced in a fixed order): with accumulation on they
         cover the group's micro-batches.  The weight is the last step's."""
-        eng = self.engine()
-        eng.ensure_grad()
-        n = eng.flat.numel()
-        t = eng.flat_grad_ext[n: n + 4]
-        con = t[3] / t[1]
-        return t[2] / t[1] - getattr(self, "_supcon_weight", 0.0) * con, con
+        return self._term_shares()
 
     def aux_terms(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(ce, aux)`` of the last ``train_step(aux=(head, aux_labels, weight))`` as device scalars: the emotion criterion's share of
         its loss and the auxiliary term per unit of labelled weight WITHOUT the weight - ``ce + weight * aux`` is the loss.  Read from
         the criterion tail (den, num and, in its fourth float, the sum of ``w_y * a``, reduced in a fixed order): with accumulation on
         they cover the group's micro-batches.  The weight is the last step's."""
-        eng = self.engine()
-        eng.ensure_grad()
-        n = eng.flat.numel()
-        t = eng.flat_grad_ext[n: n + 4]
-        aux = t[3] / t[1]
-        return t[2] / t[1] - getattr(self, "_aux_weight", 0.0) * aux, aux
+        return self._term_shares()
 
     def last_aux_logits(self) -> torch.Tensor:
         """The auxiliary head's logits of the most recent ``train_step(aux=)`` of this model as a fresh ``[B, L, A]`` tensor in the
         caller's dialogue order, whatever bucket, packed or long-dialogue plan ran: ``head(last_features())``.  Pad slots are 0.
         Raises RuntimeError when no such step has run, or the plan that ran it was destroyed or has run again since."""
         eng = self._engine
-        if eng is None or eng.last is None or getattr(self, "_aux_classes", None) is None:
+        if eng is None or eng.last is None:
             raise RuntimeError("M2FNet.last_aux_logits: no train_step(aux=) has run on this model (or it was moved since)")
         plan, version, dst, valid, shape = eng.last
         if not plan.handle:
@@ -1065,9 +997,9 @@ class M2FNet(nn.Module):
         if plan.version != version:
             raise RuntimeError("M2FNet.last_aux_logits: the activations of the last step were overwritten by a later forward "
                                "of the same plan")
-        if not plan.train or plan._aux_key[0] is None:
+        if not plan.train or "aux" not in plan.held or self._last_criterion.aux is None:
             raise RuntimeError("M2FNet.last_aux_logits: the last forward of this model was not a train_step(aux=)")
-        return plan.aux_logits(self._aux_classes, dst, valid, shape).detach()
+        return plan.aux_logits(self._last_criterion.aux[0].num_classes, dst, valid, shape).detach()
 
     def last_features(self) -> torch.Tensor:
         """The classifier's last hidden activation of the most recent ``forward`` / ``train_step`` / ``eval_step`` of this model as a

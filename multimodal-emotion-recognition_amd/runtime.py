@@ -406,19 +406,6 @@ def check_rdrop_alpha(alpha, name: str = "rdrop", who: str = "train_step") -> fl
     return float(alpha)
 
 
-def check_rdrop_args(who: str, rdrop, teacher_logits=None, distill=None, focal_gamma=None, crf=None) -> Optional[float]:
-    """`rdrop=` of a step as a float (None: off).  The R-Drop criterion has no distillation, focal or CRF form: given beside one of them
-    it is refused with a ValueError that names the pair, before any launch.  A host function: no GPU needed."""
-    if rdrop is None:
-        return None
-    alpha = check_rdrop_alpha(rdrop, "rdrop", who)
-    for name, other in (("teacher_logits", teacher_logits), ("distill", distill), ("focal_gamma", focal_gamma), ("crf", crf)):
-        if other is not None:
-            raise ValueError(f"{who}: rdrop and {name} do not combine (the R-Drop criterion has no "
-                             f"{'distillation' if name in ('teacher_logits', 'distill') else 'focal' if name == 'focal_gamma' else 'CRF'} form)")
-    return alpha
-
-
 def check_supcon_pair(supcon, name: str = "supcon", who: str = "train_step") -> Tuple[float, float]:
     """(weight, temperature) of the supervised contrastive criterion as floats; ValueError naming the argument unless it is a pair of
     numbers with weight finite and >= 0 and temperature finite and > 0.  A host function: no GPU needed."""
@@ -433,22 +420,6 @@ def check_supcon_pair(supcon, name: str = "supcon", who: str = "train_step") -> 
     if not (math.isfinite(t) and t > 0.0):
         raise ValueError(f"{who}: {name} temperature must be a finite number > 0, got {t!r}")
     return float(w), float(t)
-
-
-def check_supcon_args(who: str, supcon, teacher_logits=None, distill=None, focal_gamma=None, crf=None,
-                      rdrop=None) -> Optional[Tuple[float, float]]:
-    """`supcon=` of a step as (weight, temperature) floats (None: off).  The supervised contrastive criterion rides on the plain cross
-    entropy only: given beside teacher_logits, distill, focal_gamma, crf or rdrop it is refused with a ValueError that names the pair,
-    before any launch.  A host function: no GPU needed."""
-    if supcon is None:
-        return None
-    pair = check_supcon_pair(supcon, "supcon", who)
-    forms = {"teacher_logits": "distillation", "distill": "distillation", "focal_gamma": "focal", "crf": "CRF", "rdrop": "R-Drop"}
-    for name, other in (("teacher_logits", teacher_logits), ("distill", distill), ("focal_gamma", focal_gamma), ("crf", crf),
-                        ("rdrop", rdrop)):
-        if other is not None:
-            raise ValueError(f"{who}: supcon and {name} do not combine (the supervised contrastive criterion has no {forms[name]} form)")
-    return pair
 
 
 def rdrop_partner(pairs: int, l: int, T: int, L: Optional[int] = None, dst: Optional[torch.Tensor] = None,
@@ -475,6 +446,15 @@ def rdrop_partner(pairs: int, l: int, T: int, L: Optional[int] = None, dst: Opti
     out = torch.full((T,), -1, dtype=torch.int32, device=device)
     out[rows.reshape(-1)] = torch.roll(rows, int(pairs), 0).reshape(-1).to(torch.int32)
     return out
+
+
+def criterion_transition(held: dict, wanted: dict) -> list:
+    """The single-switch calls that take a plan's criterion from `held` to `wanted`, as [(switch, value)]: both map the switches that
+    are on - "distill", "focal", "rdrop", "supcon" to True, "crf" and "aux" to the key of their buffers - and a value of None switches
+    off.  Every switch held and not wanted goes off FIRST, then every wanted switch that is not held (or held under another key) goes
+    on: whatever the two states, no call meets a switch it is refused beside (csrc/plan.hip, exclusions[]), since `wanted` combines.
+    Nothing for equal states.  A host function: no GPU needed."""
+    return [(sw, None) for sw in held if sw not in wanted] + [(sw, v) for sw, v in wanted.items() if held.get(sw) != v]
 
 
 SPK_NONE, SPK_SAME, SPK_OTHER = 0, 1, 2
@@ -593,33 +573,26 @@ class Plan:
         else:
             self.loss = self._view(BUF_LOSS, (4,), torch.float32)
         self._dlogits = self._view(BUF_DLOGITS, (self.T, C) if self.packed else (B, L, C), torch.float32)
-        # inputs of the distillation criterion (train plans with a gradient buffer; `distill`): the teacher's logits in the token rows
-        # of the plan's own logits, and the (alpha, temperature) pair the criterion kernel reads on the device
+        # The criterion (`set_criterion`).  held: the switches that are on - "distill", "focal", "rdrop", "supcon": True; "crf", "aux": the
+        # key of their buffers - as the C side holds them; uploaded: per hyper-parameter buffer, what was last copied into it
+        self.held, self.uploaded, self._block_refs = {}, {}, {}
+        # inputs of the distillation criterion (train plans with a gradient buffer): the teacher's logits in the token rows of the plan's
+        # own logits, and the (alpha, temperature) pair the criterion kernel reads on the device
         self._teacher = self._view(BUF_TEACHER, (self.T, C) if self.packed else (B, L, C), torch.float32) if train else None
         self.distill_hyper = self._view(BUF_DISTILL, (2,), torch.float32) if train else None
-        self._distill = False
-        self.hyper_host = None                # host mirror of distill_hyper: what was last uploaded (None: nothing yet)
-        # gamma of the focal criterion (train and eval plans; `focal`): the float the criterion and eval-rows kernels read on the device
+        # gamma of the focal criterion (train and eval plans): the float the criterion and eval-rows kernels read on the device
         self.focal_gamma = self._view(BUF_FOCAL, (1,), torch.float32)
-        self._focal = False
-        self.gamma_host = None                # host mirror of focal_gamma, as hyper_host
-        # inputs of the R-Drop criterion (train plans; `rdrop`): the twin of every token row and the alpha the kernel reads on the device
+        # inputs of the R-Drop criterion (train plans): the twin of every token row and the alpha the kernel reads on the device
         self.partner_in = self._view(BUF_PARTNER, (self.T,), torch.int32) if train else None
         self.rdrop_alpha = self._view(BUF_RDROP, (1,), torch.float32) if train else None
-        self._rdrop = False
-        self.alpha_host = None                # host mirror of rdrop_alpha, as hyper_host
         self._partner_key = None              # what the padded twin map in partner_in was built for: (pairs, l); packed plans: never kept
-        # the supervised contrastive criterion (train plans; `supcon`): the (weight, temperature) pair its kernels read on the device
+        # the supervised contrastive criterion (train plans): the (weight, temperature) pair its kernels read on the device
         self.supcon_hyper = self._view(BUF_SUPCON, (2,), torch.float32) if train else None
-        self._supcon = False
-        self.supcon_host = None               # host mirror of supcon_hyper, as hyper_host
-        # the auxiliary label head (train plans; `set_aux`): the (weight, label smoothing) pair its kernels read on the device, the second
-        # label of every token row (placed as labels_in is) and the head's logits of the last step
+        # the auxiliary label head (train plans): the (weight, label smoothing) pair its kernels read on the device, the second label of
+        # every token row (placed as labels_in is) and the head's logits of the last step
         self.aux_hyper = self._view(BUF_AUX, (2,), torch.float32) if train else None
         self.aux_labels_in = self._view(BUF_AUX_LABELS, (self.T,), torch.int64) if train else None
         self._aux_logits = self._view(BUF_AUX_LOGITS, (self.T, 16) if self.packed else (B, L, 16), torch.float32) if train else None
-        self._aux_key, self._aux_ref = (None, None, 0), None
-        self.aux_host = None                  # host mirror of aux_hyper, as hyper_host
         # the classifier's last hidden activation as stored, in the plan's token rows (what `supcon` contrasts; `features`)
         hid = cfg.cls_hidden
         self._features = self._view(BUF_FEATURES, (self.T, pad8(hid)) if self.packed else (B, L, pad8(hid)), torch.float32)[..., :hid]
@@ -858,39 +831,86 @@ class Plan:
             self._teacher.zero_()                 # filler slots of a bucketed plan: label -1, the criterion selects zeros there
         self._teacher[: self.in_B, : self.in_L].copy_(u.reshape(self.in_B, self.in_L, -1))
 
+    # -- the criterion ---------------------------------------------------------------------------------------------------------------
+    def _switch(self, name: str, on: bool) -> None:
+        """m2f_plan_<name>(plan, on), asked only when it differs from what the plan holds."""
+        on = bool(on)
+        if on == (name in self.held):
+            return
+        check(getattr(lib(), "m2f_plan_" + name)(self._h(), int(on)), "m2f_plan_" + name)
+        if on:
+            self.held[name] = True
+        else:
+            del self.held[name]
+
     def distill(self, on: bool) -> None:
         """m2f_plan_distill: the NEXT losses / steps run the distillation criterion on `teacher` and `distill_hyper` (on) / the plain
         criterion (off).  A change drops the captured steps.  Neither writes nor waits: `set_distill_hyper` and `set_teacher` fill the
         two buffers on the stream before the step.  Raises for a plan without a gradient buffer."""
-        on = bool(on)
-        if on == self._distill:
-            return
-        check(lib().m2f_plan_distill(self._h(), int(on)), "m2f_plan_distill")
-        self._distill = on
-
-    def set_distill_hyper(self, alpha: float, temperature: float) -> None:
-        """(alpha, temperature) into `distill_hyper`, uploaded only when the pair differs from the host mirror of the last upload."""
-        pair = (float(alpha), float(temperature))
-        if pair != self.hyper_host:
-            self.distill_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
-            self.hyper_host = pair
+        self._switch("distill", on)
 
     def focal(self, on: bool) -> None:
         """m2f_plan_focal: the NEXT losses / steps / eval steps run the focal form of the criterion with gamma = `focal_gamma` (on) / the
         form without it (off).  A change drops the captured steps; a change of gamma alone does not.  Neither writes nor waits:
         `set_focal_gamma` fills the buffer on the stream before the step."""
-        on = bool(on)
-        if on == self._focal:
-            return
-        check(lib().m2f_plan_focal(self._h(), int(on)), "m2f_plan_focal")
-        self._focal = on
+        self._switch("focal", on)
+
+    def rdrop(self, on: bool) -> None:
+        """m2f_plan_rdrop: the NEXT losses / steps run the R-Drop criterion on `partner_in` and `rdrop_alpha` (on) / the criterion
+        without it (off).  A change drops the captured steps; a change of alpha or of the map does not.  Neither writes nor waits.
+        The distillation, focal and CRF switches must be off (the C entry refuses by name)."""
+        self._switch("rdrop", on)
+
+    def supcon(self, on: bool) -> None:
+        """m2f_plan_supcon: the NEXT losses / steps add the supervised contrastive term on the hidden features (on) / do not (off).
+        A change drops the captured steps; a change of the pair does not.  Neither writes nor waits.  The distillation, focal, R-Drop
+        and CRF switches must be off (the C entry refuses by name)."""
+        self._switch("supcon", on)
+
+    def _block(self, name: str, entry: str, params, grad, *extra) -> None:
+        """The switch of a criterion that reads a parameter block: held under the key of its two tensors, which the plan keeps alive
+        (params None: off)."""
+        key = None if params is None else (params.data_ptr(), None if grad is None else grad.data_ptr(), *extra)
+        if key != self.held.get(name):
+            check(getattr(lib(), entry)(self._h(), ptr(params), ptr(grad), *extra), entry)
+            self._block_refs[name] = (params, grad)
+            if key is None:
+                del self.held[name]
+            else:
+                self.held[name] = key
+
+    def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
+        """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's
+        flat block, read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan
+        keeps the two tensors alive; a change of the pointers or of the switch drops the captured steps, a change of the values does
+        not.  The focal and distillation switches must be off (the C entry refuses by name)."""
+        self._block("crf", "m2f_plan_crf", params, grad)
+
+    def set_aux(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None, num_aux: int = 0,
+                pair: Optional[Tuple[float, float]] = None) -> None:
+        """m2f_plan_aux_head: the plan's NEXT losses / steps add the auxiliary label head over `params` (the module's flat block [W | b],
+        read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan keeps the two
+        tensors alive; a change of the pointers, of num_aux or of the switch drops the captured steps, a change of the values or of
+        `pair` = (weight, label smoothing) - uploaded only when it differs from the last upload - does not.  The distillation, R-Drop,
+        CRF and supervised contrastive switches must be off (the C entry refuses by name)."""
+        self._block("aux", "m2f_plan_aux_head", params, grad, int(num_aux) if params is not None else 0)
+        if params is not None and pair is not None:
+            self._upload("aux_hyper", (float(pair[0]), float(pair[1])))
+
+    def _upload(self, buf: str, value) -> None:
+        """A hyper-parameter (a float, or a tuple of floats) into the plan's buffer of that name - only when it differs from what was
+        last copied there: a schedule replays the captured step, and an unchanged value costs nothing."""
+        if self.uploaded.get(buf) != value:
+            getattr(self, buf).copy_(torch.tensor(value, dtype=torch.float32).reshape(-1), non_blocking=True)
+            self.uploaded[buf] = value
+
+    def set_distill_hyper(self, alpha: float, temperature: float) -> None:
+        """(alpha, temperature) into `distill_hyper` (`_upload`)."""
+        self._upload("distill_hyper", (float(alpha), float(temperature)))
 
     def set_focal_gamma(self, gamma: float) -> None:
-        """gamma into `focal_gamma`, uploaded only when it differs from the host mirror of the last upload."""
-        gamma = float(gamma)
-        if gamma != self.gamma_host:
-            self.focal_gamma.copy_(torch.tensor([gamma], dtype=torch.float32), non_blocking=True)
-            self.gamma_host = gamma
+        """gamma into `focal_gamma` (`_upload`)."""
+        self._upload("focal_gamma", float(gamma))
 
     def set_focal(self, gamma: Optional[float]) -> None:
         """The criterion of the plan's next step or eval step: focal with this gamma (a number, checked by the caller), or (None) not."""
@@ -898,24 +918,10 @@ class Plan:
         if gamma is not None:
             self.set_focal_gamma(gamma)
 
-    def rdrop(self, on: bool) -> None:
-        """m2f_plan_rdrop: the NEXT losses / steps run the R-Drop criterion on `partner_in` and `rdrop_alpha` (on) / the criterion
-        without it (off).  A change drops the captured steps; a change of alpha or of the map does not.  Neither writes nor waits.
-        The distillation, focal and CRF switches must be off (the C entry refuses by name)."""
-        on = bool(on)
-        if on == self._rdrop:
-            return
-        check(lib().m2f_plan_rdrop(self._h(), int(on)), "m2f_plan_rdrop")
-        self._rdrop = on
-
-    def set_rdrop(self, alpha: Optional[float]) -> None:
-        """The criterion of the plan's next step: R-Drop with this alpha (a number, checked by the caller), or (None) not.  AFTER
-        `set_inputs` of the doubled batch (view 0, then view 1): the twin map is written from the row map that placed it - a packed
-        plan's from `_dst`, on the device; a padded or bucketed plan's depends on the batch's shape alone and is written only when that
-        changed.  alpha is uploaded only when it differs from the host mirror of the last upload."""
-        self.rdrop(alpha is not None)
-        if alpha is None:
-            return
+    def _place_partner(self) -> None:
+        """The twin map of the doubled batch `set_inputs` has just placed (view 0, then view 1), written from the row map that placed
+        it - a packed plan's from `_dst`, on the device; a padded or bucketed plan's depends on the batch's shape alone and is written
+        only when that changed."""
         if self.in_B % 2:
             raise HipError(f"the R-Drop criterion needs the batch twice (view 0, then view 1), got {self.in_B} dialogues")
         pairs = self.in_B // 2
@@ -925,37 +931,10 @@ class Plan:
         elif self._partner_key != (pairs, self.in_L):
             self.partner_in.copy_(rdrop_partner(pairs, self.in_L, self.T, L=self.L, device=self.partner_in.device), non_blocking=True)
             self._partner_key = (pairs, self.in_L)
-        alpha = float(alpha)
-        if alpha != self.alpha_host:
-            self.rdrop_alpha.copy_(torch.tensor([alpha], dtype=torch.float32), non_blocking=True)
-            self.alpha_host = alpha
 
-    def supcon(self, on: bool) -> None:
-        """m2f_plan_supcon: the NEXT losses / steps add the supervised contrastive term on the hidden features (on) / do not (off).
-        A change drops the captured steps; a change of the pair does not.  Neither writes nor waits.  The distillation, focal, R-Drop
-        and CRF switches must be off (the C entry refuses by name)."""
-        on = bool(on)
-        if on == self._supcon:
-            return
-        check(lib().m2f_plan_supcon(self._h(), int(on)), "m2f_plan_supcon")
-        self._supcon = on
-
-    def set_supcon(self, pair: Optional[Tuple[float, float]]) -> None:
-        """The contrastive term of the plan's next step: (weight, temperature) - numbers, checked by the caller -, or (None) not.  The
-        pair is uploaded only when it differs from the host mirror of the last upload."""
-        self.supcon(pair is not None)
-        if pair is None:
-            return
-        pair = (float(pair[0]), float(pair[1]))
-        if pair != self.supcon_host:
-            self.supcon_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
-            self.supcon_host = pair
-
-    def set_aux_labels(self, labels: torch.Tensor) -> None:
+    def _place_aux_labels(self, labels: torch.Tensor) -> None:
         """The second labels of the last batch ([b, l] int64, padded surface) into the plan's buffer: they travel as `set_inputs` moves
         the emotion labels - filler slots of a bucketed plan -1, packed plans through the batch's row map with the spare row cleared."""
-        if self.aux_labels_in is None:
-            raise HipError("this plan holds no auxiliary label buffer (an eval plan)")
         if self.packed:
             self.aux_labels_in.fill_(-1)
             self.aux_labels_in.index_copy_(0, self._dst.reshape(-1), labels.reshape(-1).to(torch.int64))
@@ -967,34 +946,50 @@ class Plan:
         self.aux_labels_in.fill_(-1)
         self.aux_labels_in.view(self.B, self.L)[: self.in_B, : self.in_L].copy_(labels, non_blocking=True)
 
-    def set_aux(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None, num_aux: int = 0,
-                pair: Optional[Tuple[float, float]] = None) -> None:
-        """m2f_plan_aux_head: the plan's NEXT losses / steps add the auxiliary label head over `params` (the module's flat block [W | b],
-        read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan keeps the two
-        tensors alive; a change of the pointers, of num_aux or of the switch drops the captured steps, a change of the values or of
-        `pair` = (weight, label smoothing) - uploaded only when it differs from the host mirror of the last upload - does not.  The
-        distillation, R-Drop, CRF and supervised contrastive switches must be off (the C entry refuses by name)."""
-        key = (None if params is None else params.data_ptr(), None if grad is None else grad.data_ptr(), int(num_aux) if params is not None else 0)
-        if key != self._aux_key:
-            check(lib().m2f_plan_aux_head(self._h(), ptr(params), ptr(grad), key[2]), "m2f_plan_aux_head")
-            self._aux_key, self._aux_ref = key, (params, grad)
-        if params is None or pair is None:
+    def set_criterion(self, spec) -> None:
+        """The criterion of the plan's NEXT step or eval step: `spec`, a ``criterion.Criterion`` (checked by ``criterion.resolve``).
+        AFTER `set_inputs` (a packed plan maps teacher rows, auxiliary labels and twins as it mapped the batch).  The switches move
+        by `criterion_transition` - whatever the plan held, in an order no C entry refuses -, the batch's criterion inputs are placed,
+        and every hyper-parameter goes through `_upload`.  A step whose criterion is the plan's last one calls no m2f_plan_* entry and
+        uploads nothing: captured steps replay across schedules, and are dropped exactly when a switch or a block's pointers change.
+        A CRF's or an auxiliary head's block is an input of the step; trainable, its gradient goes to the module's buffer when the
+        plan trains."""
+        if not self.held and not spec.kinds:
             return
-        pair = (float(pair[0]), float(pair[1]))
-        if pair != self.aux_host:
-            self.aux_hyper.copy_(torch.tensor(pair, dtype=torch.float32), non_blocking=True)
-            self.aux_host = pair
+        dev, blocks, wanted = self.workspace.device, {}, {k: True for k in spec.kinds}
+        if spec.crf is not None:
+            blocks["crf"] = spec.crf.step_buffers(dev, want_grad=self.train)
+        if spec.aux is not None:
+            blocks["aux"] = (*spec.aux[0].step_buffers(dev, want_grad=self.train), spec.aux[0].num_classes)
+        for name, (params, grad, *extra) in blocks.items():
+            wanted[name] = (params.data_ptr(), None if grad is None else grad.data_ptr(), *extra)
+        for switch, value in criterion_transition(self.held, wanted):
+            if switch in ("crf", "aux"):
+                (self.set_crf if switch == "crf" else self.set_aux)(*(blocks[switch] if value is not None else (None,)))
+            else:
+                self._switch(switch, value is not None)
+        if spec.distill is not None:
+            self.set_teacher(spec.teacher_logits)
+            self.set_distill_hyper(*spec.distill)
+        if spec.gamma is not None:
+            self.set_focal_gamma(spec.gamma)
+        if spec.rdrop is not None:
+            self._place_partner()
+            self._upload("rdrop_alpha", spec.rdrop)
+        if spec.supcon is not None:
+            self._upload("supcon_hyper", spec.supcon)
+        if spec.aux is not None:
+            self._place_aux_labels(spec.aux[1])
+            self._upload("aux_hyper", spec.aux[2:])
 
-    def set_crf(self, params: Optional[torch.Tensor], grad: Optional[torch.Tensor] = None) -> None:
-        """m2f_plan_crf: the criterion of the plan's NEXT losses / steps / eval steps is the linear-chain CRF over `params` (the module's
-        flat block, read on the device at every step), its gradient written to `grad` (None: frozen) - or (params None) not.  The plan
-        keeps the two tensors alive; a change of the pointers or of the switch drops the captured steps, a change of the values does
-        not.  The focal and distillation switches must be off (the C entry refuses by name)."""
-        key = (None if params is None else params.data_ptr(), None if grad is None else grad.data_ptr())
-        if key == getattr(self, "_crf_key", (None, None)):
-            return
-        check(lib().m2f_plan_crf(self._h(), ptr(params), ptr(grad)), "m2f_plan_crf")
-        self._crf_key, self._crf_ref = key, (params, grad)
+    # (what the tests of the single criteria read the held switches and the uploads by)
+    _supcon = property(lambda self: "supcon" in self.held)
+    _crf_key = property(lambda self: self.held.get("crf", (None, None)))
+    _aux_key = property(lambda self: self.held.get("aux", (None, None, 0)), lambda self, key: self.held.__setitem__("aux", key))
+    gamma_host = property(lambda self: self.uploaded.get("focal_gamma"))
+    alpha_host = property(lambda self: self.uploaded.get("rdrop_alpha"))
+    supcon_host = property(lambda self: self.uploaded.get("supcon_hyper"))
+    aux_host = property(lambda self: self.uploaded.get("aux_hyper"))
 
     def _casted(self) -> None:
         if self.shared_shadow and not self._fresh and self._on_cast is not None:

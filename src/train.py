@@ -239,32 +239,37 @@ def rdrop_settings(cfg):
     return {"alpha": alpha, "warmup_steps": warm}
 
 
+def _warmed(value: float, warmup_steps: int, global_step: int) -> float:
+    """A criterion weight at optimizer step `global_step` under a linear warm-up: value * (step + 1) / warmup_steps until warmup_steps
+    (0: the value from the first step)."""
+    return value * min(1.0, (global_step + 1) / warmup_steps) if warmup_steps > 0 else value
+
+
 def _rdrop_kw(model, global_step: int):
     """{rdrop: alpha} of optimizer step `global_step` for train_step / DataParallelStep when main() hung the runtime.rdrop settings on the
-    model (`model.rdrop`), else nothing - the calls of a run without it are today's.  warmup_steps = n: alpha * (step + 1) / n until n."""
+    model (`model.rdrop`), else nothing - the calls of a run without it are today's.  alpha is `_warmed`."""
     r = getattr(model, "rdrop", None)
-    if r is None:
-        return {}
-    n = r["warmup_steps"]
-    return {"rdrop": r["alpha"] * min(1.0, (global_step + 1) / n) if n > 0 else r["alpha"]}
+    return {} if r is None else {"rdrop": _warmed(r["alpha"], r["warmup_steps"], global_step)}
 
 
-class _RDropLog:
-    """Running means of the two shares of the R-Drop loss for wandb: {"Train/CE", "Train/RDrop_KL"} beside Train/Running_loss (CE + alpha
-    * RDrop_KL at a constant alpha).  Reads `model.rdrop_terms()` only when something is logged: two more scalars on a path that has
-    just waited for loss.item()."""
+class _SharesLog:
+    """Running means of the two shares of the loss for wandb, for whichever weighted term main() hung on the model: {"Train/CE"} and
+    {"Train/RDrop_KL"} (`model.rdrop`), {"Train/SupCon"} (`model.supcon`) or {"Train/Aux"} (`model.aux_head`), beside Train/Running_loss
+    (CE + weight * share at a constant weight).  Reads `model.*_terms()` only when something is logged: two more scalars on a path that
+    has just waited for loss.item()."""
+    TERMS = (("rdrop", "rdrop_terms", "Train/RDrop_KL"), ("supcon", "supcon_terms", "Train/SupCon"), ("aux_head", "aux_terms", "Train/Aux"))
 
     def __init__(self, model, on: bool):
-        self.model, self.on = model, on and getattr(model, "rdrop", None) is not None
-        self.ce = self.kl = 0.0
+        self.model = model
+        self.terms = [(fn, key, [0.0, 0.0]) for attr, fn, key in self.TERMS if on and getattr(model, attr, None) is not None]
 
     def __call__(self, step: int):
-        if not self.on:
-            return {}
-        ce, kl = self.model.rdrop_terms()
-        self.ce += ce.item()
-        self.kl += kl.item()
-        return {"Train/CE": self.ce / (step + 1), "Train/RDrop_KL": self.kl / (step + 1)}
+        out = {}
+        for fn, key, sums in self.terms:
+            for i, share in enumerate(getattr(self.model, fn)()):
+                sums[i] += share.item()
+            out.update({"Train/CE": sums[0] / (step + 1), key: sums[1] / (step + 1)})
+        return out
 
 
 SUPCON_KEYS = ("enabled", "weight", "temperature", "warmup_steps")
@@ -311,30 +316,9 @@ def supcon_settings(cfg):
 
 def _supcon_kw(model, global_step: int):
     """{supcon: (weight, temperature)} of optimizer step `global_step` for train_step when main() hung the runtime.supcon settings on
-    the model (`model.supcon`), else nothing - the calls of a run without it are today's.  warmup_steps = n: weight * (step + 1) / n
-    until n."""
+    the model (`model.supcon`), else nothing - the calls of a run without it are today's.  The weight is `_warmed`."""
     r = getattr(model, "supcon", None)
-    if r is None:
-        return {}
-    n = r["warmup_steps"]
-    return {"supcon": (r["weight"] * min(1.0, (global_step + 1) / n) if n > 0 else r["weight"], r["temperature"])}
-
-
-class _SupConLog:
-    """Running means of the two shares of the loss for wandb: {"Train/CE", "Train/SupCon"} beside Train/Running_loss (CE + weight *
-    SupCon at a constant weight).  Reads `model.supcon_terms()` only when something is logged."""
-
-    def __init__(self, model, on: bool):
-        self.model, self.on = model, on and getattr(model, "supcon", None) is not None
-        self.ce = self.con = 0.0
-
-    def __call__(self, step: int):
-        if not self.on:
-            return {}
-        ce, con = self.model.supcon_terms()
-        self.ce += ce.item()
-        self.con += con.item()
-        return {"Train/CE": self.ce / (step + 1), "Train/SupCon": self.con / (step + 1)}
+    return {} if r is None else {"supcon": (_warmed(r["weight"], r["warmup_steps"], global_step), r["temperature"])}
 
 
 AUX_KEYS = ("enabled", "labels", "weight", "label_smoothing", "lr", "warmup_steps")
@@ -422,34 +406,15 @@ def _aux_step(aux) -> None:
 
 def _aux_kw(model, batch, device, global_step: int):
     """{aux: (head, labels, weight), aux_label_smoothing} of optimizer step `global_step` for train_step when main() hung an auxiliary
-    head on the model (`model.aux_head`), else nothing - the calls of a run without it are today's.  warmup_steps = n: weight *
-    (step + 1) / n until n."""
+    head on the model (`model.aux_head`), else nothing - the calls of a run without it are today's.  The weight is `_warmed`."""
     head = getattr(model, "aux_head", None)
     if head is None:
         return {}
     r = head.settings
     if r["labels"] not in batch:
         raise ValueError(f"runtime.aux_head: the batch carries no {r['labels']!r} (Dataset({r['labels']}=True) and runtime.device_batcher: False are needed)")
-    n = r["warmup_steps"]
-    weight = r["weight"] * min(1.0, (global_step + 1) / n) if n > 0 else r["weight"]
+    weight = _warmed(r["weight"], r["warmup_steps"], global_step)
     return {"aux": (head, batch[r["labels"]].to(device, non_blocking=True), weight), "aux_label_smoothing": r["label_smoothing"]}
-
-
-class _AuxLog:
-    """Running means of the two shares of the loss for wandb: {"Train/CE", "Train/Aux"} beside Train/Running_loss (CE + weight * Aux at
-    a constant weight).  Reads `model.aux_terms()` only when something is logged."""
-
-    def __init__(self, model, on: bool):
-        self.model, self.on = model, on and getattr(model, "aux_head", None) is not None
-        self.ce = self.aux = 0.0
-
-    def __call__(self, step: int):
-        if not self.on:
-            return {}
-        ce, aux = self.model.aux_terms()
-        self.ce += ce.item()
-        self.aux += aux.item()
-        return {"Train/CE": self.ce / (step + 1), "Train/Aux": self.aux / (step + 1)}
 
 
 class AuxAccuracy:
@@ -1199,9 +1164,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
     if k > 1:
         return _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log, device, k, fused, use_graph, dp_step)
     running = 0.0
-    rdrop_log = _RDropLog(model, bool(wandb_log))
-    supcon_log = _SupConLog(model, bool(wandb_log))
-    aux_log = _AuxLog(model, bool(wandb_log))
+    shares_log = _SharesLog(model, bool(wandb_log))
     progress = tqdm(enumerate(dl_train), total=len(dl_train), desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, batch in progress:
         text, audio, emotion, padding_mask = move_batch(batch, device, non_blocking=True, text_encoder=getattr(model, "text_encoder", None),
@@ -1233,7 +1196,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 running += loss.item()
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                               **_grad_norm_log(optimizer), **rdrop_log(step), **supcon_log(step), **aux_log(step)})
+                               **_grad_norm_log(optimizer), **shares_log(step)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
@@ -1250,7 +1213,7 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
-                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step), **aux_log(step)})
+                       **_grad_norm_log(optimizer), **watched, **shares_log(step)})
     return running / len(dl_train)
 
 
@@ -1268,8 +1231,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
         model.set_grad_accumulation(True)
     n_groups = (len(dl_train) + k - 1) // k
     running = 0.0
-    rdrop_log = _RDropLog(model, bool(wandb_log))
-    supcon_log = _SupConLog(model, bool(wandb_log))
+    shares_log = _SharesLog(model, bool(wandb_log))          # (no auxiliary head here: refused above)
     progress = tqdm(enumerate(group_batches(dl_train, k)), total=n_groups, desc=f"Epoch {epoch}", disable=_rank() != 0)
     for step, group in progress:
         rdrop = _rdrop_kw(model, epoch * n_groups + step)     # (one alpha per optimizer step: the group's shares add up)
@@ -1297,7 +1259,7 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
         watched = _watch_log(optimizer, wandb_log)
         if wandb_log:
             wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * n_groups + step,
-                       **_grad_norm_log(optimizer), **watched, **rdrop_log(step), **supcon_log(step)})
+                       **_grad_norm_log(optimizer), **watched, **shares_log(step)})
     if dp_step is None:
         optimizer.grad_scale = None
     return running / max(n_groups, 1)

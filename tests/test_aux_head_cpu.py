@@ -1,5 +1,5 @@
 """Host side of the auxiliary label head: the float64 reference (tests/golden/aux_head_ref.py) against nn.Linear + F.cross_entropy, the
-head module (init, views, state_dict), the argument checks (aux_head.check_step_args), Dataset(sentiment=True) / collate_fn, the drop-in
+head module (init, views, state_dict), the argument checks (criterion.resolve), Dataset(sentiment=True) / collate_fn, the drop-in
 parser (src/train.py aux_head_settings), the loop with the key off and on (a stand-in model: the calls, the log lines and the checkpoint
 entry), the shipped runtime.* keys and the header / ctypes agreement.  No GPU."""
 import os
@@ -16,7 +16,8 @@ sys.path.insert(0, os.path.join(ROOT, "src"))
 import aux_head_ref as ref  # noqa: E402
 import mer_amd  # noqa: E402,F401
 from mer_amd import runtime  # noqa: E402
-from mer_amd.aux_head import AuxiliaryHead, check_pair, check_step_args  # noqa: E402
+from mer_amd.aux_head import AuxiliaryHead, check_pair  # noqa: E402
+from mer_amd.criterion import PLAIN, resolve  # noqa: E402
 
 
 @pytest.mark.parametrize("N,D,A,eps", [(1, 20, 2, 0.0), (15, 100, 3, 0.1), (65, 20, 3, 0.1), (130, 64, 16, 0.0)])
@@ -99,15 +100,25 @@ def test_head_module_is_a_linear_layer_over_one_block():
             AuxiliaryHead(bad, 3)
 
 
+def check_step_args(who, aux, in_features, mask_shape=None, label_smoothing=0.0, device="cpu", **kw):
+    """`aux=` through criterion.resolve -> the checked (head, aux_labels, weight, label_smoothing), or PLAIN for None"""
+    spec = resolve(who, num_classes=7, cls_hidden=in_features, mask_shape=mask_shape, device=device, label_smoothing=0.1, class_weights=None,
+                   aux=aux, aux_label_smoothing=label_smoothing, **kw)
+    return spec if spec is PLAIN else spec.aux
+
+
 def test_check_step_args():
+    from mer_amd.crf import LinearChainCRF
     head, s = AuxiliaryHead(64, 3), torch.zeros(4, 6, dtype=torch.int64)
-    assert check_step_args("step", None, 64) is None
+    assert check_step_args("step", None, 64) is PLAIN
     assert check_step_args("step", (head, s, 1), 64, (4, 6), 0.1) == (head, s, 1.0, 0.1)
     assert check_pair(0, 0) == (0.0, 0.0)
+    # (valid values beside it: the arguments that PRIORITY looks at before aux are checked before it)
+    beside = {"teacher_logits": torch.zeros(4, 6, 7), "distill": (0.5, 2.0), "crf": LinearChainCRF(7), "rdrop": 1.0, "supcon": (0.1, 0.1)}
     for name, why in (("teacher_logits", "no distillation form"), ("distill", "no distillation form"), ("crf", "no auxiliary form"),
                       ("rdrop", "fourth float"), ("supcon", "hidden activation's gradient")):
         with pytest.raises(ValueError, match=f"step: aux and {name} do not combine .*{why}"):
-            check_step_args("step", (head, s, 0.5), 64, (4, 6), **{name: object()})
+            check_step_args("step", (head, s, 0.5), 64, (4, 6), **{name: beside[name]})
     for bad, msg in (((head, s), "must be a triple"), ((torch.nn.Linear(64, 3), s, 0.5), "needs an AuxiliaryHead first"),
                      ((AuxiliaryHead(48, 3), s, 0.5), "in_features 48, the model's classifier hidden width is 64"),
                      ((head, s[:, :5], 0.5), "labels must be int64 \\[4, 6\\]"), ((head, s.int(), 0.5), "labels must be int64"),

@@ -133,10 +133,14 @@ def test_viterbi_inputs_are_decided_by_more_than_rounding():
 
 def test_step_refusals_name_their_pair():
     """`crf=` beside anything the CRF criterion has no form for is a ValueError on the host, before any launch."""
-    from mer_amd.crf import check_step_args
+    from mer_amd.criterion import PLAIN, resolve
+
+    def check_step_args(who, crf, num_classes, class_weights=None, label_smoothing=0.0, **kw):
+        return resolve(who, num_classes=num_classes, cls_hidden=64, mask_shape=(1, 1), device="cpu", label_smoothing=label_smoothing,
+                       class_weights=class_weights, crf=crf, **kw)
     crf = LinearChainCRF(7)
-    check_step_args("train_step", None, 7, class_weights=torch.ones(7), label_smoothing=0.1)          # no crf: nothing to refuse
-    check_step_args("train_step", crf, 7)
+    assert check_step_args("train_step", None, 7, class_weights=torch.ones(7), label_smoothing=0.1) is PLAIN          # no crf: nothing to refuse
+    assert check_step_args("train_step", crf, 7).crf is crf
     for kw, name in (({"class_weights": torch.ones(7)}, "class_weights"), ({"teacher_logits": torch.zeros(1)}, "teacher_logits / distill"),
                      ({"distill": (0.5, 2.0)}, "teacher_logits / distill"), ({"focal_gamma": 0.0}, "focal_gamma"),
                      ({"label_smoothing": 0.1}, "label_smoothing != 0.0")):
@@ -150,8 +154,13 @@ def test_step_refusals_name_their_pair():
         check_step_args("train_step", crf, 7, accumulating=True)
     with pytest.raises(ValueError, match="trainable crf= does not combine with DataParallelStep"):
         check_step_args("DataParallelStep", crf, 7, data_parallel=True)
+    # an evaluation step writes no gradient: a trainable block is an input there, whatever the training mode
+    assert check_step_args("M2FNet.eval_step", crf, 7, evaluating=True, accumulating=True).crf is crf
+    assert check_step_args("M2FNet.eval_step", crf, 7, evaluating=True, accumulating=True, data_parallel=True, focal_gamma=None).crf is crf
+    with pytest.raises(ValueError, match="eval_step: crf= does not combine with focal_gamma"):
+        check_step_args("M2FNet.eval_step", crf, 7, evaluating=True, accumulating=True, focal_gamma=2.0)
     crf.params.requires_grad_(False)                      # frozen: a pure input, fine under both
-    check_step_args("train_step", crf, 7, accumulating=True, data_parallel=True)
+    assert check_step_args("train_step", crf, 7, accumulating=True, data_parallel=True).crf is crf
     with pytest.raises(ValueError, match="move the module"):
         crf.block("cuda:0")
 

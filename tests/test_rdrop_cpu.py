@@ -191,7 +191,10 @@ def test_check_rdrop_alpha_refuses_and_names_the_argument(bad):
 def test_check_rdrop_alpha_accepts():
     assert runtime.check_rdrop_alpha(0) == 0.0 and runtime.check_rdrop_alpha(5) == 5.0 and runtime.check_rdrop_alpha(0.3) == 0.3
     assert isinstance(runtime.check_rdrop_alpha(1), float)
-    assert runtime.check_rdrop_args("here", None, focal_gamma=2.0) is None            # off: nothing to refuse
+    from mer_amd.criterion import resolve
+    spec = resolve("here", num_classes=7, cls_hidden=64, mask_shape=(2, 5), device="cpu", label_smoothing=0.1, class_weights=None,
+                   rdrop=None, focal_gamma=2.0)
+    assert spec.rdrop is None and spec.gamma == 2.0                                   # off: nothing to refuse
 
 
 def test_steps_refuse_before_they_touch_a_device():

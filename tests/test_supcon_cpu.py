@@ -1,5 +1,5 @@
 """Host side of the supervised contrastive criterion: the float64 reference (tests/golden/supcon_ref.py) against float64 autograd of a
-plain per-anchor loop, the argument checks (runtime.check_supcon_args), the drop-in parser (src/train.py supcon_settings) and the
+plain per-anchor loop, the argument checks (criterion.resolve), the drop-in parser (src/train.py supcon_settings) and the
 shipped runtime.* keys.  No GPU."""
 import os
 import sys
@@ -52,18 +52,31 @@ def test_reference_degenerate_batches_cost_nothing():
     assert not r["rows"][:, 1:].any() and not r["grad"].any() and r["den"].item() > 0.0
 
 
+def _check_supcon_args(who, supcon, **kw):
+    """`supcon=` through criterion.resolve -> the checked (weight, temperature), or PLAIN for None"""
+    from mer_amd.criterion import PLAIN, resolve
+    spec = resolve(who, num_classes=7, cls_hidden=64, mask_shape=(4, 6), device="cpu", label_smoothing=0.0, class_weights=None,
+                   supcon=supcon, **kw)
+    return spec if spec is PLAIN else spec.supcon
+
+
 def test_check_supcon_args():
-    assert runtime.check_supcon_args("step", None, focal_gamma=2.0) is None
-    assert runtime.check_supcon_args("step", (0, 1)) == (0.0, 1.0)
-    assert runtime.check_supcon_args("step", [0.25, 0.07]) == (0.25, 0.07)
+    from mer_amd.crf import LinearChainCRF
+    assert _check_supcon_args("step", None, focal_gamma=2.0) is None
+    assert _check_supcon_args("step", (0, 1)) == (0.0, 1.0)
+    assert _check_supcon_args("step", [0.25, 0.07]) == (0.25, 0.07)
     for bad in (0.1, (0.1,), (0.1, 0.1, 0.1), ("a", 0.1), (True, 0.1), (0.1, False), (-0.1, 0.1), (0.1, 0.0), (0.1, -1.0),
                 (float("nan"), 0.1), (float("inf"), 0.1), (0.1, float("nan")), (0.1, float("inf"))):
         with pytest.raises(ValueError, match="step: supcon"):
-            runtime.check_supcon_args("step", bad)
+            _check_supcon_args("step", bad)
     forms = {"teacher_logits": "distillation", "distill": "distillation", "focal_gamma": "focal", "crf": "CRF", "rdrop": "R-Drop"}
+    # (valid values beside it: rdrop, which PRIORITY looks at before supcon, is checked before it)
+    beside = {"teacher_logits": torch.zeros(4, 6, 7), "distill": (0.5, 2.0), "focal_gamma": 2.0, "crf": LinearChainCRF(7), "rdrop": 1.0}
     for name, form in forms.items():
         with pytest.raises(ValueError, match=f"step: supcon and {name} do not combine \\(the supervised contrastive criterion has no {form} form\\)"):
-            runtime.check_supcon_args("step", (0.1, 0.1), **{name: object()})
+            _check_supcon_args("step", (0.1, 0.1), **{name: beside[name]})
+    with pytest.raises(ValueError, match="DataParallelStep: supcon is refused"):
+        _check_supcon_args("DataParallelStep", (0.1, 0.1), data_parallel=True)
     assert "m2f_plan_supcon" in runtime.SIGNATURES and "m2f_supcon" in runtime.SIGNATURES and "m2f_supcon_scratch_floats" in runtime.SIGNATURES
     assert (runtime.BUF_SUPCON, runtime.BUF_FEATURES) == (24, 25)
 
