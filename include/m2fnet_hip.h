@@ -375,6 +375,27 @@ int m2f_grad_sumsq(const m2f_config* cfg, const void* grads, int grads_bf16, int
 int m2f_grad_norm_finalize(const m2f_config* cfg, const double* scratch, const float* den_ptr, double max_norm, float* record,
                            m2f_stream_t stream);
 
+/* Sharpness-aware minimisation (SAM; Foret et al., ICLR 2021) on the flat parameter buffer (optim.FusedAdam(sam_rho=...)).  No
+ * counterpart in the reference.
+ *
+ * m2f_sam_perturb: w <- w + rho * g^ / (||g^|| + 1e-12), g^ = g / den (den = *grad_scale_ptr, or 1 when NULL), over every parameter
+ * element.  `scratch` holds the partial sums of squares m2f_grad_sumsq has left for the SAME gradient buffer over ALL tensors.  Two
+ * launches on `stream`: a finalize launch writes four floats, computed in float64 and rounded once each,
+ *   record[0] = ||g^|| = sqrt(sum of squares) / den        record[1] = c = rho / (||g^|| + 1e-12) / den
+ *   record[2] = den                                        record[3] = sqrt(sum of squares)
+ * and the perturbation reads c when it runs: saved[i] <- params[i], params[i] <- fma(c, g[i], params[i]), one fused multiply-add per
+ * element.  Exactly one of grads (fp32) / grads_bf16 (bf16, same indexing) is non-NULL; params, the gradients and saved (fp32, the
+ * flat size) are 16-byte aligned.  param_shadow (the buffer of m2f_param_shadow_init, or NULL): the kernel also writes the W / W^T
+ * bf16 shadows of every 2-D parameter from the perturbed value, as m2f_adam_step_shadowed lays them out.  The alignment pads between
+ * tensors are neither read nor written in any buffer.  A zero gradient leaves every parameter's bits.  Same bits on every run.
+ *
+ * m2f_sam_restore: params[i] <- saved[i] over every parameter element (pads untouched): the bits from before the perturbation.  The
+ * shadows are NOT rewritten: the caller's next optimizer step (or its casts) does that. */
+int m2f_sam_perturb(const m2f_config* cfg, float* params, const float* grads, const uint16_t* grads_bf16, float* saved,
+                    uint16_t* param_shadow, const double* scratch, const float* grad_scale_ptr, double rho, float* record,
+                    m2f_stream_t stream);
+int m2f_sam_restore(const m2f_config* cfg, float* params, const float* saved, m2f_stream_t stream);
+
 /* Per-tensor statistics and histograms of one flat buffer in the model's parameter layout (the model watch: what
  * wandb.watch(model, log="all") of the reference's loop, src/train.py:132-138, logs per parameter and per gradient tensor, computed
  * where the values live).  `a`: fp32, or (a_is_bf16 != 0) bf16 with the same indexing, 16-byte aligned; `b` (fp32, or NULL): the

@@ -34,6 +34,10 @@ w2v = len(sys.argv) > 2 and sys.argv[1] == "--w2v"
 mel = len(sys.argv) > 2 and sys.argv[1] == "--mel"
 # --gradnorm <remarks>: the gradient-norm kernels (gradnorm.hip) - the same rule (a slice's loads and float64 accumulators stay in registers)
 gradnorm = len(sys.argv) > 2 and sys.argv[1] == "--gradnorm"
+# --sam <remarks>: the sharpness-aware minimisation kernels (sam.hip): the finalize launch, the shadow-writing and the flat perturbation for
+# fp32 and bf16 gradients, the restore - a tile's loads are all issued before the arithmetic and stay in registers: zero scratch, no
+# spills; prints the register numbers of each
+sam = len(sys.argv) > 2 and sys.argv[1] == "--sam"
 # --tstats <remarks>: the model-watch kernels (tensor_stats.hip) - the same rule (a slice's loads, float64 sums and counters stay in registers)
 tstats = len(sys.argv) > 2 and sys.argv[1] == "--tstats"
 # --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
@@ -53,7 +57,7 @@ supcon = len(sys.argv) > 2 and sys.argv[1] == "--supcon"
 # --aux <remarks>: the auxiliary label head's kernels (aux_head.hip) - a row's 16-byte pieces, the sixteen logits, the row's terms and the
 # sixteen accumulators of a parameter-gradient lane stay in registers through unrolled loops with static indices: zero scratch, no spills
 aux = len(sys.argv) > 2 and sys.argv[1] == "--aux"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux) else sys.argv[1]
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux or sam) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -87,6 +91,15 @@ if adam:
             sys.exit(f"check_spills: expected {count} of {tag} in {path}, found {len(found)} - did the remark format change?")
         criterion += found
     kernels = kernels + criterion
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if sam:
+    kernels = [r for r in rows if "m2f_sam_" in r["name"]]
+    if len(kernels) != 6:
+        sys.exit(f"check_spills: expected the six m2f_sam_ kernels in {path}, found {len(kernels)} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

@@ -809,6 +809,18 @@ hipError_t m2f_launch_grad_sumsq(const void* g, int g_is_bf16, const ParamSlice*
 hipError_t m2f_launch_grad_norm_finalize(const double* partial, int n, const float* den_ptr, double max_norm, float* record,
                                          hipStream_t stream);
 
+// Sharpness-aware minimisation (sam.hip).  The finalize launch sums partial[0, n) as the clip finalize does and writes record =
+// (norm / den, c, den, sqrt(sum of squares)), c = rho / (norm / den + 1e-12) / den; the perturb launches read c = record[1] when they run:
+// saved <- w, w <- fma(c, g, w) over parameter elements only.  Shadowed form: items as m2f_launch_adam_shadowed walks them, except that a
+// 1-D item's `cols` is the tensor's own element count (no pad), tile_begin from 0; it writes the W / W^T bf16 shadows of w' as that kernel
+// lays them out.  Flat form and restore (w <- saved): every tensor's ParamSlices.
+hipError_t m2f_launch_sam_finalize(const double* partial, int n, const float* den_ptr, double rho, float* record, hipStream_t stream);
+hipError_t m2f_launch_sam_perturb_shadowed(float* p, const void* g, int g_is_bf16, float* saved, uint16_t* shadow, const AdamItem* items,
+                                           const int* tile_begin, int n_items, int total_tiles, const float* record, hipStream_t stream);
+hipError_t m2f_launch_sam_perturb_flat(float* p, const void* g, int g_is_bf16, float* saved, const ParamSlice* slices, int n_slices,
+                                       const float* record, hipStream_t stream);
+hipError_t m2f_launch_sam_restore(float* p, const float* saved, const ParamSlice* slices, int n_slices, hipStream_t stream);
+
 // Per-tensor statistics and histograms of a flat buffer (tensor_stats.hip).  slices: every tensor's ParamSlices, tag = the index of the slice's
 // tensor; tensor_begin[t] = first slice of tensor t, [n_tensors] = n_slices.  Pass 1 writes partial[s] (a slice's finite count is
 // n - nan - inf), the finalize launch the record header (M2F_TSTATS_HEADER doubles: den, n_tensors, bins, 0) and one row per tensor

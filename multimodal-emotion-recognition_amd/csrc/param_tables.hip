@@ -266,8 +266,10 @@ int tensor_range(const char* what, const ParamTable& t, int64_t first, int64_t e
 // what the norm and the statistics walk; kept for the life of the process.  OWNED_ITEMS / OWNED_SLICES: the tensors some group of `map`
 // owns, as the grouped kernels walk them - items re-tiled from 0 with their groups (shadow-writing form) or slices tagged with the group
 // (flat form, exchange).  An optimizer has one map until add_param_group changes it, so those stay few: beyond 32 the oldest goes
-// (after a device sync: a kernel may read it).
-enum TableKind { ALL_SLICES, OWNED_ITEMS, OWNED_SLICES };
+// (after a device sync: a kernel may read it).  SAM_ITEMS: every tensor's item, 1-D runs cut at the tensor's last element (the host
+// table's run on to the next tensor: its pad is the Adam kernel's to rewrite, nobody else's), re-tiled from 0 - what the shadow-writing
+// perturbation walks; no map, kept for the life of the process.
+enum TableKind { ALL_SLICES, OWNED_ITEMS, OWNED_SLICES, SAM_ITEMS };
 struct DeviceTable {
     const ParamTable* host = nullptr; int device = -1; TableKind kind = ALL_SLICES; std::vector<int> map;      // the key
     std::vector<int> own_before;             // [n + 1]: owned tensors in front of tensor i
@@ -295,7 +297,15 @@ const DeviceTable* device_table(const char* what, const ParamTable& host, TableK
     for (size_t i = 0; i < n; ++i) { t->own_before.push_back(owned); owned += !map || map[i] >= 0; }
     t->own_before.push_back(owned);
     std::vector<char*> d;
-    if (kind == OWNED_ITEMS) {
+    if (kind == SAM_ITEMS) {
+        std::vector<AdamItem> items = host.items;
+        for (size_t i = 0; i < n; ++i)
+            if (items[i].rows == 0) items[i].cols = (int)host.numels[i];
+        retile(items, nullptr, false, t->begin);
+        if (upload_packed(t->dev, {{items.data(), items.size() * sizeof(AdamItem)}, {t->begin.data(), t->begin.size() * sizeof(int)}}, d))
+            return nullptr;
+        t->items = reinterpret_cast<const AdamItem*>(d[0]); t->tb = reinterpret_cast<const int*>(d[1]);
+    } else if (kind == OWNED_ITEMS) {
         std::vector<AdamItem> items = host.items;
         std::vector<int> grp = t->map;
         retile(items, &grp, false, t->begin);
@@ -315,9 +325,9 @@ const DeviceTable* device_table(const char* what, const ParamTable& host, TableK
     }
     if (map) {
         size_t mapped = 0;
-        for (const DeviceTable* x : g_device_tables) mapped += x->kind != ALL_SLICES;
+        for (const DeviceTable* x : g_device_tables) mapped += !x->map.empty();
         if (mapped >= 32) {
-            auto oldest = std::find_if(g_device_tables.begin(), g_device_tables.end(), [](const DeviceTable* x) { return x->kind != ALL_SLICES; });
+            auto oldest = std::find_if(g_device_tables.begin(), g_device_tables.end(), [](const DeviceTable* x) { return !x->map.empty(); });
             (void)hipDeviceSynchronize();
             if ((*oldest)->dev) (void)hipFree((*oldest)->dev);
             delete *oldest;
@@ -501,6 +511,42 @@ int m2f_grad_norm_finalize(const m2f_config* cfg, const double* scratch, const f
     const ParamTable* h = param_table(*cfg);
     if (!h) return 1;
     M2F_HIP(m2f_launch_grad_norm_finalize(scratch, h->slice_begin.back(), den_ptr, max_norm, record, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- sharpness-aware minimisation (sam.hip) --------------------------------------------------------------------------------------
+int m2f_sam_perturb(const m2f_config* cfg, float* params, const float* grads, const uint16_t* grads_bf16, float* saved, uint16_t* param_shadow,
+                    const double* scratch, const float* grad_scale_ptr, double rho, float* record, m2f_stream_t stream) {
+    if (!cfg || !params || !saved || !scratch || !record) return fail("m2f_sam_perturb: NULL configuration / buffer");
+    if (!grads == !grads_bf16) return fail("m2f_sam_perturb: exactly one of grads / grads_bf16");
+    if (!(rho > 0.0) || !std::isfinite(rho)) return fail("m2f_sam_perturb: rho must be a finite number > 0");
+    const void* g = grads ? static_cast<const void*>(grads) : static_cast<const void*>(grads_bf16);
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(saved)) & 15)
+        return fail("m2f_sam_perturb: the flat buffers must be 16-byte aligned");
+    if (params == saved) return fail("m2f_sam_perturb: params and saved are the same buffer");
+    if (param_shadow && (reinterpret_cast<uintptr_t>(param_shadow) & 255)) return fail("m2f_sam_perturb: 256-byte aligned shadow buffer required");
+    const ParamTable* h = param_table(*cfg, param_shadow != nullptr);
+    if (!h) return 1;
+    const DeviceTable* t = device_table("m2f_sam_perturb", *h, param_shadow ? SAM_ITEMS : ALL_SLICES, nullptr);
+    if (!t) return 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    M2F_HIP(m2f_launch_sam_finalize(scratch, h->slice_begin.back(), grad_scale_ptr, rho, record, s));
+    if (param_shadow)
+        M2F_HIP(m2f_launch_sam_perturb_shadowed(params, g, grads_bf16 != nullptr, saved, param_shadow, t->items, t->tb, h->n(), t->count(), record, s));
+    else
+        M2F_HIP(m2f_launch_sam_perturb_flat(params, g, grads_bf16 != nullptr, saved, t->slices, h->slice_begin.back(), record, s));
+    return 0;
+}
+
+int m2f_sam_restore(const m2f_config* cfg, float* params, const float* saved, m2f_stream_t stream) {
+    if (!cfg || !params || !saved) return fail("m2f_sam_restore: NULL configuration / buffer");
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(saved)) & 15) return fail("m2f_sam_restore: the flat buffers must be 16-byte aligned");
+    if (params == saved) return fail("m2f_sam_restore: params and saved are the same buffer");
+    const ParamTable* h = param_table(*cfg);
+    if (!h) return 1;
+    const DeviceTable* t = device_table("m2f_sam_restore", *h, ALL_SLICES, nullptr);
+    if (!t) return 1;
+    M2F_HIP(m2f_launch_sam_restore(params, saved, t->slices, h->slice_begin.back(), static_cast<hipStream_t>(stream)));
     return 0;
 }
 

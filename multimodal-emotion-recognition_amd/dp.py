@@ -379,6 +379,14 @@ def _refuse_clipped_split(optimizer) -> None:
                            "step (the global norm needs every bucket's reduced gradients before the first update); use overlap=False")
 
 
+def _refuse_sam(optimizer) -> None:
+    """Sharpness-aware minimisation needs a second forward + backward between the exchange and the update, and a norm over the reduced
+    gradient of every rank: out of scope under data parallelism."""
+    if getattr(optimizer, "sam_rho", None) is not None:
+        raise RuntimeError("mer_amd.dp.DataParallelStep: sharpness-aware minimisation (FusedAdam.sam_rho) is not implemented under data "
+                           "parallelism (the step exchanges and updates once; SAM needs a second pass in between); set sam_rho=None")
+
+
 def sum_over_ranks(values: Sequence[float], device=None) -> List[float]:
     """SUM over ranks, float64 (per-batch validation sums: every rank ends with the same totals)."""
     t = torch.tensor(list(values), dtype=torch.float64, device=device)
@@ -436,6 +444,7 @@ class DataParallelStep:
         if overlap is None:
             overlap = os.environ.get("M2F_DP_OVERLAP", "0") == "1"
         _refuse_speaker_heads(model)          # (before the engine, the reducer or any collective)
+        _refuse_sam(optimizer)
         self.crf = crf
         self.model, self.optimizer, self.overlap = model, optimizer, bool(overlap)
         self._resolve(None, 0.0, None)        # (its own crf: a LinearChainCRF of the model's classes, frozen)
@@ -504,6 +513,7 @@ class DataParallelStep:
         micro-batch's local loss.  The next sync=True call accumulates its own micro-batch, exchanges once and steps once with the
         global den of every micro-batch of every rank.  A rank whose micro-batches were all empty contributes zeros."""
         _refuse_speaker_heads(self.model)     # (set after construction: before any launch or collective, every rank alike)
+        _refuse_sam(self.optimizer)
         spec = self._resolve(mask, label_smoothing, class_weights, teacher_logits=teacher_logits, distill=distill, focal_gamma=focal_gamma,
                              rdrop=rdrop, supcon=supcon, aux=aux, aux_label_smoothing=aux_label_smoothing)
         self.model._last_criterion = spec

@@ -750,6 +750,10 @@ class M2FNet(nn.Module):
         spec = self._resolve("M2FNet.train_step", mask, label_smoothing, class_weights, teacher_logits=teacher_logits, distill=distill,
                              focal_gamma=focal_gamma, crf=crf, rdrop=rdrop, supcon=supcon, aux=aux, aux_label_smoothing=aux_label_smoothing)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
+        if optimizer is not None and getattr(optimizer, "sam_rho", None) is not None:
+            raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
+                               "sharpness-aware minimisation (optimizer.sam_rho): the in-launch optimizer cannot wait for the second "
+                               "pass; call M2FNet.sam_step(..., optimizer), or set sam_rho = None")
         eng = self.engine(mask.device)
         if optimizer is not None and eng.accumulate:
             raise RuntimeError("M2FNet.train_step: optimizer= (the optimizer step inside the train step) does not combine with "
@@ -794,6 +798,28 @@ class M2FNet(nn.Module):
                 block.publish_grad()
         eng.note_forward(plan)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
+
+    def sam_step(self, text, audio, mask, emotion, optimizer, **train_step_arguments) -> torch.Tensor:
+        """One optimizer step of sharpness-aware minimisation (Foret et al., ICLR 2021; ``FusedAdam(sam_rho=...)``): ``train_step``
+        at ``w``, ``optimizer.first_step()`` (``w <- w + e``), ``train_step`` on the same batch at ``w + e``, ``optimizer.step()``
+        (``w`` restored to its bits, then the update with the second gradient).  Returns the FIRST pass's loss, the loss at ``w``.
+        ``train_step_arguments``: every keyword of ``train_step`` but ``optimizer`` - criterion arguments, ``speakers=``,
+        ``class_weights``, ``use_graph`` - handed to both passes unchanged.  Both passes run the one plan of the batch's shape and
+        replay its one captured graph; with dropout on, the second pass draws fresh masks, as every torch implementation of SAM does.
+        Nothing waits for the host.  Under gradient accumulation the two passes are two sweeps over the group's micro-batches: make
+        the calls by hand (``FusedAdam``'s docstring has the loop)."""
+        if getattr(optimizer, "sam_rho", None) is None:
+            raise RuntimeError("M2FNet.sam_step: optimizer.sam_rho is None; construct the optimizer with sam_rho= (or set the attribute)")
+        if getattr(optimizer, "sam_pending", False):
+            raise RuntimeError("M2FNet.sam_step: a perturbation is already pending on the optimizer; call step() or restore() first")
+        if self._grad_accumulation:
+            raise RuntimeError("M2FNet.sam_step: under gradient accumulation (set_grad_accumulation(True)) the two passes are two sweeps "
+                               "over the group's micro-batches; make the calls by hand (see FusedAdam's docstring)")
+        loss = self.train_step(text, audio, mask, emotion, **train_step_arguments)
+        optimizer.first_step()
+        self.train_step(text, audio, mask, emotion, **train_step_arguments)
+        optimizer.step()
+        return loss
 
     def _resolve(self, who: str, mask, label_smoothing, class_weights, **criterion_args):
         """``criterion.resolve`` for a step of this model on `mask`'s batch (`who` names the entry point in the refusals)."""

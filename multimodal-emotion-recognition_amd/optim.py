@@ -385,11 +385,43 @@ class FusedAdam(torch.optim.Optimizer):
     that logs ``gradients`` or ``updates`` is attached (the in-launch optimizer never stores the matrices' gradients); with other kinds
     the in-launch step is counted and the buffers are collected as they are before it.  In ``step_ranges`` on a due step `before_each`
     runs for all ranges first, as with clipping.  Parameters, moments, shadows and the EMA are what they are without it, bit for bit.
-    None (the default): the step as it was, launch for launch."""
+    None (the default): the step as it was, launch for launch.
+
+    ``sam_rho`` (keyword-only constructor argument and plain attribute; a finite number > 0 or None; may be changed between steps, so a
+    schedule works; not part of ``state_dict``): sharpness-aware minimisation (Foret et al., ICLR 2021), one perturbation per optimizer
+    step.  ``first_step()`` reduces the L2 norm of the gradient buffer ``step()`` would read at that moment (fp32, the bf16 buffer of
+    ``set_grad_bf16``, or an accumulation group's sum; divided by ``grad_scale`` where one is set) with the clip's launches into a
+    record of its own, and one kernel moves every parameter to ``w + rho * g / (||g|| + 1e-12)`` - one fp32 coefficient formed in
+    float64 on the device, one fused multiply-add per element - keeping ``w`` in a backup buffer of the flat size and, in bf16 mode,
+    writing the bf16 shadows of the moved matrices itself (``engine.shadows_fresh()`` stays true).  An ordinary ``train_step`` on the
+    same batch then leaves the gradient at ``w + e`` in the same buffers, and ``step()`` restores ``w`` to its bits before it runs
+    today's update on that gradient: clipping, the EMA and the watch see the second gradient, exactly as they see the only one
+    without SAM.  ``model.sam_step(...)`` makes the four calls.  ``restore()`` abandons a perturbation; ``sam_norm()`` is the norm
+    of the last ``first_step`` on the device.  Nothing waits for the host.  With ``sam_rho`` set, ``step()`` without a pending
+    perturbation raises (a loop cannot silently train without SAM); ``first_step()`` while one is pending raises, and so do
+    ``averaged_parameters()``, ``ema_state_dict()`` and ``prepare_fused()`` while one is pending.  ``prepare_fused`` returns False (the
+    in-launch optimizer cannot wait for a second pass) and ``train_step(optimizer=...)`` refuses by name; ``step_ranges`` and
+    ``dp.DataParallelStep`` refuse; a grouped optimizer that leaves a tensor in no group refuses (that tensor must keep every bit,
+    and the norm's index set would differ).  A checkpoint, ``model.state_dict()`` or this optimizer's ``state_dict()`` taken WHILE a
+    perturbation is pending holds ``w + e``, not ``w``: save after ``step()`` (or ``restore()``).  Under gradient accumulation the
+    two passes are two sweeps over the group's micro-batches::
+
+        optimizer.zero_grad()
+        for mb in group:
+            model.train_step(*mb, normalise=False)
+        optimizer.grad_scale = model.loss_terms()[1:2]
+        optimizer.first_step()
+        optimizer.zero_grad()
+        for mb in group:
+            model.train_step(*mb, normalise=False)
+        optimizer.step()
+
+    None (the default): every launch of the step as it was, bit for bit."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: Optional[float] = None, *, params=None, decoupled_weight_decay: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False, watch=None, **torch_options):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, watch=None, sam_rho: Optional[float] = None,
+                 **torch_options):
         for k, v in torch_options.items():
             if k not in _TORCH_ONLY:
                 raise TypeError(f"FusedAdam.__init__() got an unexpected keyword argument {k!r}")
@@ -403,6 +435,12 @@ class FusedAdam(torch.optim.Optimizer):
         self._averaged_in = False                          # inside averaged_parameters(): model <-> average exchanged
         self.watch = watch                                 # watch.ModelWatch or None
         self._n_steps = 0                                  # optimizer steps taken (every form): the watch's schedule
+        self.sam_rho = runtime.check_sam_rho(sam_rho)      # sharpness-aware minimisation: first_step() / step()
+        self._sam_saved: Optional[torch.Tensor] = None     # fp32, the layout of engine.flat: w while w + e is in the model
+        self._sam_scratch: Optional[torch.Tensor] = None   # float64 partial sums of squares, SAM's own (the clip keeps its own)
+        self._sam_record: Optional[torch.Tensor] = None    # 4 fp32 on the device: norm, c, divisor, sqrt(sum of squares)
+        self._sam_cfg = None
+        self._sam_pending = False                          # between first_step() and step() / restore(): the model holds w + e
         # grouped: anything but ONE coupled group over model.parameters() - the hyper table and the grouped kernels instead of
         # the single-group entries
         self._grouped = params is not None or bool(decoupled_weight_decay)
@@ -555,6 +593,7 @@ class FusedAdam(torch.optim.Optimizer):
         """``{"decay", "warmup", "n_averaged", "parameters": {name: tensor}}``; ``parameters`` has the names and shapes of
         ``model.state_dict()`` and loads into the reference's ``M2FNet``.  A tensor in no parameter group is not averaged: its entry is
         its live value."""
+        self._refuse_pending("ema_state_dict()")
         if self._ema is None:
             raise RuntimeError("FusedAdam.ema_state_dict: no EMA step has run yet (ema_decay is None, or step() has not been called)")
         eng = self._bind()
@@ -618,6 +657,7 @@ class FusedAdam(torch.optim.Optimizer):
         ``model.state_dict()``, ``forward``, ``eval_step`` and a checkpoint see the average (the bf16 shadows are re-cast by the next
         forward, inside and again after); ``step()``, ``step_ranges()``, ``prepare_fused()`` and a nested entry raise."""
         self._refuse_averaged("averaged_parameters()")
+        self._refuse_pending("averaged_parameters()")
         if self._ema is None or self._n_averaged == 0:
             raise RuntimeError("FusedAdam.averaged_parameters: there is no average yet (no step has run with ema_decay set)")
         eng = self._bind()
@@ -695,16 +735,9 @@ class FusedAdam(torch.optim.Optimizer):
         """Device scalar (a view): ``min(1, max_grad_norm / (grad_norm + 1e-6))`` of the last clipping step."""
         return self._clip_value(1, "clip_coef")
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._refuse_averaged("step()")
-        eng = self._bind()
-        ema, ema_w = self._ema_begin(eng)                    # one average update per optimizer step: every launch gets the same weight
-        g = self.param_groups[0]
+    def _grad_buffer(self, eng) -> torch.Tensor:
+        """The flat gradient buffer ``step()`` reads: the bf16 buffer where a step left its gradients rounded (M2FNet.set_grad_bf16),
+        else the engine's fp32 buffer - after gathering foreign ``.grad`` tensors into it where the engine's views are not published."""
         flat_grad = eng.ensure_grad()
         # fast path: the engine published its flat-buffer views as .grad (checked on the two end parameters);
         # otherwise gather foreign .grad tensors into the flat buffer first
@@ -717,6 +750,86 @@ class FusedAdam(torch.optim.Optimizer):
                     view.zero_()
                 elif p.grad.data_ptr() != view.data_ptr():
                     view.copy_(p.grad)
+        return flat_grad
+
+    # ---- sharpness-aware minimisation ---------------------------------------------------------------------------------------------
+    def _refuse_pending(self, what: str) -> None:
+        if self._sam_pending:
+            raise RuntimeError(f"FusedAdam.{what} while a sharpness-aware perturbation is pending: the model holds w + e; call step() "
+                               "or restore() first")
+
+    @property
+    def sam_pending(self) -> bool:
+        """Between ``first_step()`` and ``step()`` / ``restore()``: the model's parameters are ``w + e``."""
+        return self._sam_pending
+
+    @torch.no_grad()
+    def first_step(self) -> None:
+        """SAM's ascent step on the gradient ``step()`` would read now: ``w <- w + sam_rho * g / (||g|| + 1e-12)`` (class docstring).
+        Three launches on the current stream - the sum of squares, the record with the coefficient, the perturbation - and no host
+        wait.  Run ``train_step`` on the same batch next, then ``step()``."""
+        self._refuse_averaged("first_step()")
+        rho = runtime.check_sam_rho(self.sam_rho)
+        if rho is None:
+            raise RuntimeError("FusedAdam.first_step(): sam_rho is None; set it to the perturbation's radius first")
+        if self._sam_pending:
+            raise RuntimeError("FusedAdam.first_step(): a perturbation is already pending (the model holds w + e); call step() or "
+                               "restore() first")
+        if self._grouped and not self._owns_everything():
+            raise RuntimeError("FusedAdam.first_step(): sharpness-aware minimisation needs parameter groups that cover every tensor of "
+                               "the model - a tensor in no group must keep every bit, and the norm would run over another index set")
+        eng = self._bind()
+        flat_grad = self._grad_buffer(eng)
+        if self._sam_record is None or self._sam_record.device != eng.flat.device or self._sam_cfg is not eng.cfg:
+            self._sam_scratch = runtime.grad_norm_scratch(eng.cfg, eng.flat.device)
+            self._sam_record = torch.zeros(4, dtype=torch.float32, device=eng.flat.device)
+            self._sam_saved = torch.zeros_like(eng.flat)
+            self._sam_cfg = eng.cfg
+        runtime.grad_sumsq(eng.cfg, flat_grad, self._sam_scratch)
+        runtime.sam_perturb(eng.cfg, eng.flat, flat_grad, self._sam_saved, eng.wshadow, self._sam_scratch, self._sam_record, rho,
+                            self.grad_scale)
+        if eng.wshadow is not None:
+            eng.mark_shadows_fresh()                         # (the kernel wrote W and W^T of every matrix from w + e)
+        self._sam_pending = True
+
+    def _sam_restore(self, eng) -> None:
+        runtime.sam_restore(eng.cfg, eng.flat, self._sam_saved)
+        eng.invalidate_shadows()                             # (they hold w + e until an optimizer kernel or the forward's casts rewrite them)
+        self._sam_pending = False
+
+    @torch.no_grad()
+    def restore(self) -> bool:
+        """Abandons a pending perturbation: the parameters get their bits from before ``first_step()`` (one launch) and the bf16
+        shadows are invalidated (the next forward re-casts them).  Returns whether there was one; without one it does nothing."""
+        if not self._sam_pending:
+            return False
+        self._sam_restore(self._bind())
+        return True
+
+    def sam_norm(self) -> torch.Tensor:
+        """Device scalar (a view: the next ``first_step()`` overwrites it): L2 norm of the gradient the last ``first_step()`` read,
+        divided by ``grad_scale``."""
+        if self._sam_record is None:
+            raise RuntimeError("FusedAdam.sam_norm: first_step() has not run yet")
+        return self._sam_record[0]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._refuse_averaged("step()")
+        if not self._sam_pending and runtime.check_sam_rho(self.sam_rho) is not None:
+            raise RuntimeError("FusedAdam.step(): sam_rho is set and no perturbation is pending - this step would train without "
+                               "sharpness-aware minimisation; call first_step() and a second train_step first (M2FNet.sam_step does), "
+                               "or set sam_rho = None")
+        eng = self._bind()
+        if self._sam_pending:                                # w's bits from before first_step(), then today's step on the second gradient
+            self._sam_restore(eng)
+        ema, ema_w = self._ema_begin(eng)                    # one average update per optimizer step: every launch gets the same weight
+        g = self.param_groups[0]
+        flat_grad = self._grad_buffer(eng)
         watch = self._watch_due()
         if watch is not None:
             self._watch_before(watch, eng, flat_grad)
@@ -757,9 +870,11 @@ class FusedAdam(torch.optim.Optimizer):
         their ``.grad`` keeps whatever it held.  Returns False (and changes nothing) when the plan cannot; call ``finish_fused``
         after the step.  With ``max_grad_norm`` set it returns False: the in-launch optimizer updates elements before the global norm
         can exist, so ``train_step(optimizer=...)`` takes its two-launch branch (the step, then ``step()``).  With ``ema_decay`` set it
-        returns False as well: the in-launch optimizer has no EMA stream (its epilogue is at its register budget)."""
+        returns False as well: the in-launch optimizer has no EMA stream (its epilogue is at its register budget).  With ``sam_rho`` set
+        it returns False too: the in-launch optimizer cannot wait for SAM's second pass."""
         self._refuse_averaged("prepare_fused()")
-        if self.max_grad_norm is not None or self.ema_decay is not None:
+        self._refuse_pending("prepare_fused()")
+        if self.max_grad_norm is not None or self.ema_decay is not None or self.sam_rho is not None:
             return False
         if self.watch is not None and ("gradients" in self.watch.kinds or "updates" in self.watch.kinds):
             return False
@@ -836,8 +951,13 @@ class FusedAdam(torch.optim.Optimizer):
         With ``max_grad_norm`` set the global norm needs every range's gradients: `before_each` runs for ALL ranges first, then the
         norm launches over the whole buffer, then the ranges' updates with the clip record's divisor - the updates no longer hide
         under the exchange of the following buckets; that is the price of a global norm.  A due step of an attached ``watch`` does the
-        same, on that step only: every range's `before_each` first, then the collections over the whole buffers, then the updates."""
+        same, on that step only: every range's `before_each` first, then the collections over the whole buffers, then the updates.
+        Refused (RuntimeError) with ``sam_rho`` set: sharpness-aware minimisation under data parallelism is not implemented."""
         self._refuse_averaged("step_ranges()")
+        self._refuse_pending("step_ranges()")
+        if runtime.check_sam_rho(self.sam_rho) is not None:
+            raise RuntimeError("FusedAdam.step_ranges(): sharpness-aware minimisation (sam_rho) is not implemented for range-wise steps "
+                               "(the data-parallel path); set sam_rho = None")
         eng = self._bind()
         g = self.param_groups[0]
         flat_grad = eng.ensure_grad() if grads is None else grads
@@ -966,6 +1086,6 @@ class FusedAdamW(FusedAdam):
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  max_grad_norm: Optional[float] = None, *, params=None, ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                 watch=None, **torch_options):
+                 watch=None, sam_rho: Optional[float] = None, **torch_options):
         super().__init__(model, lr, betas, eps, weight_decay, max_grad_norm, params=params, decoupled_weight_decay=True,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, watch=watch, **torch_options)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, watch=watch, sam_rho=sam_rho, **torch_options)

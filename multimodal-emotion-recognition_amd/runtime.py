@@ -91,6 +91,9 @@ SIGNATURES = {
     "m2f_grad_norm_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC)]),
     "m2f_grad_sumsq": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p]),
     "m2f_grad_norm_finalize": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+    "m2f_sam_perturb": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                ctypes.c_double, c_void_p, c_void_p]),
+    "m2f_sam_restore": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_void_p]),
     "m2f_tensor_stats_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
     "m2f_tensor_stats_record_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
     "m2f_tensor_stats": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -1539,6 +1542,33 @@ def grad_norm_finalize(cfg: M2FConfig, scratch: torch.Tensor, record: torch.Tens
     cc = config_to_c(cfg)
     check(lib().m2f_grad_norm_finalize(ctypes.byref(cc), scratch.data_ptr(), ptr(den), float(max_norm), record.data_ptr(), stream_ptr()),
           "m2f_grad_norm_finalize")
+
+
+def check_sam_rho(rho, who: str = "FusedAdam") -> Optional[float]:
+    """``sam_rho``: None, or a finite number > 0 (-> float); anything else is a ValueError."""
+    if rho is None:
+        return None
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not math.isfinite(rho) or not rho > 0.0:
+        raise ValueError(f"{who}.sam_rho must be None or a finite number > 0 (got {rho!r})")
+    return float(rho)
+
+
+def sam_perturb(cfg: M2FConfig, params: torch.Tensor, grads: torch.Tensor, saved: torch.Tensor, param_shadow: Optional[torch.Tensor],
+                scratch: torch.Tensor, record: torch.Tensor, rho: float, grad_scale: Optional[torch.Tensor] = None) -> None:
+    """m2f_sam_perturb on the current stream: `scratch` holds grad_sumsq's partials of `grads` (fp32 or bf16, the WHOLE flat buffer);
+    record <- (||g / grad_scale||, c, grad_scale, sqrt(sum of squares)), saved <- params, params <- fma(c, grads, params) over parameter
+    elements, and - with `param_shadow` - the bf16 shadows of the perturbed matrices."""
+    cc = config_to_c(cfg)
+    g16 = grads.dtype == torch.bfloat16
+    check(lib().m2f_sam_perturb(ctypes.byref(cc), params.data_ptr(), None if g16 else grads.data_ptr(), grads.data_ptr() if g16 else None,
+                                saved.data_ptr(), ptr(param_shadow), scratch.data_ptr(), ptr(grad_scale), float(rho), record.data_ptr(),
+                                stream_ptr()), "m2f_sam_perturb")
+
+
+def sam_restore(cfg: M2FConfig, params: torch.Tensor, saved: torch.Tensor) -> None:
+    """m2f_sam_restore on the current stream: params <- saved over parameter elements (the pads keep what they hold)."""
+    cc = config_to_c(cfg)
+    check(lib().m2f_sam_restore(ctypes.byref(cc), params.data_ptr(), saved.data_ptr(), stream_ptr()), "m2f_sam_restore")
 
 
 TSTATS_HEADER, TSTATS_FIELDS, TSTATS_MAX_BINS = 4, 9, 256      # csrc/ops.h M2F_TSTATS_*

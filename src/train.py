@@ -120,6 +120,41 @@ def ema_settings(cfg):
     return float(decay), flags["warmup"], flags["evaluate"]
 
 
+def sam_settings(cfg, world: int = 1):
+    """`runtime.sam` = {enabled, rho}: sharpness-aware minimisation (FusedAdam.sam_rho; the loop calls M2FNet.sam_step).  -> None when
+    the block is absent or disabled, else rho.  Checked on the host before the GPU is touched: the loop body must be the fused step
+    (runtime.fused_step: True) with the optimizer outside it (runtime.fused_optimizer: False - the in-launch optimizer cannot wait for
+    the second pass), one micro-batch per step (runtime.grad_accumulation: 1) and one process (data parallelism is refused)."""
+    block = _runtime(cfg, "sam", None)
+    if block is None:
+        return None
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.sam must be a mapping {{enabled, rho}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - {"enabled", "rho"})
+    if unknown:
+        raise ValueError(f"runtime.sam: unknown key(s) {unknown} (enabled, rho)")
+    enabled = block.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"runtime.sam.enabled must be true or false (got {enabled!r})")
+    rho = block.get("rho", 0.05)
+    if isinstance(rho, bool) or not isinstance(rho, (int, float)) or not rho > 0 or rho != rho or rho == float("inf"):
+        raise ValueError(f"runtime.sam.rho must be a positive finite number (got {rho!r})")
+    if not enabled:
+        return None
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.sam.enabled needs runtime.fused_step: True (both passes run train_step)")
+    if bool(_runtime(cfg, "fused_optimizer", False)):
+        raise ValueError("runtime.sam.enabled does not combine with runtime.fused_optimizer: True "
+                         "(the optimizer inside the step cannot wait for the second pass)")
+    if int(_runtime(cfg, "grad_accumulation", 1) or 1) > 1:
+        raise ValueError("runtime.sam.enabled does not combine with runtime.grad_accumulation > 1 in this loop "
+                         "(FusedAdam's docstring has the two-sweep form)")
+    if world > 1:
+        raise ValueError("runtime.sam.enabled does not combine with data-parallel training (DataParallelStep refuses an optimizer "
+                         "with sam_rho set); run one process")
+    return float(rho)
+
+
 DISTILL_KEYS = ("enabled", "teacher_checkpoint", "teacher_weights", "alpha", "temperature", "teacher_context", "teacher_position_bias")
 
 
@@ -663,6 +698,9 @@ def build_optimizer(config, model):
     cut = optimizer_groups(config, [(n, tuple(p.shape)) for n, p in model.named_parameters(remove_duplicate=False)])
     ema = ema_settings(config)
     ema_kw = {} if ema is None else {"ema_decay": ema[0], "ema_warmup": ema[1]}
+    rho = sam_settings(config)
+    if rho is not None:
+        ema_kw["sam_rho"] = rho
     if cut is None:
         return FusedAdam(model, lr=config.solver.lr, weight_decay=config.solver.weight_decay, **ema_kw)
     name, groups, _ = cut
@@ -921,6 +959,7 @@ def main(config=None):
     grad_accumulation_steps(config, int(os.environ.get("WORLD_SIZE", "1")))      # (refusals before the GPU is touched)
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
+    sam_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     context_settings(config)
     position_bias_settings(config)
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
@@ -1139,6 +1178,14 @@ def _grad_norm_log(optimizer):
     return {"Train/Grad_norm": float(optimizer.grad_norm())}
 
 
+def _sam_log(optimizer):
+    """{"Train/SAM_grad_norm": ...} of the step just taken when the optimizer runs sharpness-aware minimisation (runtime.sam): the norm
+    of the first pass's gradient, else nothing.  One more scalar read on a path that already waits for loss.item() every step."""
+    if getattr(optimizer, "sam_rho", None) is None:
+        return {}
+    return {"Train/SAM_grad_norm": float(optimizer.sam_norm())}
+
+
 def _watch_log(optimizer, wandb_log):
     """After a due step of the optimizer's watch (runtime.watch): reads its record - one copy, on a path that has just waited for
     loss.item() - appends the JSON line to runtime.watch.file and returns {"gradients/<name>": wandb.Histogram, ...} for the step's
@@ -1198,6 +1245,22 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
                                **_grad_norm_log(optimizer), **shares_log(step)})
                 continue
+            sam = getattr(optimizer, "sam_rho", None) is not None
+            if sam and not fused:
+                raise ValueError("runtime.sam needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+            if sam:
+                # sharpness-aware minimisation: the step at w, the perturbation, the step at w + e, the restore and the update
+                loss = model.sam_step(text, audio, padding_mask, emotion, optimizer, use_graph=use_graph,
+                                      **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
+                                      **_crit_kw(criterion), **rdrop, **supcon, **aux)
+                _crf_step(criterion)
+                _aux_step(aux)
+                running += loss.item()
+                watched = _watch_log(optimizer, wandb_log)
+                if wandb_log:
+                    wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
+                               **_grad_norm_log(optimizer), **_sam_log(optimizer), **watched, **shares_log(step)})
+                continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
                                         **_speaker_kw(model, batch, device), **_crit_kw(criterion), **rdrop, **supcon, **aux)
@@ -1225,6 +1288,8 @@ def _train_accumulating(model, dl_train, criterion, optimizer, epoch, wandb_log,
     optimizer steps of the group losses num / den."""
     if not fused:
         raise ValueError("runtime.grad_accumulation > 1 needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+    if getattr(optimizer, "sam_rho", None) is not None:
+        raise ValueError("runtime.sam does not combine with runtime.grad_accumulation > 1 in this loop (FusedAdam's docstring has the two-sweep form)")
     if getattr(model, "aux_head", None) is not None:
         raise ValueError("runtime.aux_head does not combine with runtime.grad_accumulation > 1 (the head trains: its gradient would need the group's den)")
     if dp_step is None:
