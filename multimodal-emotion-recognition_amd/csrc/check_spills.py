@@ -42,12 +42,13 @@ sam = len(sys.argv) > 2 and sys.argv[1] == "--sam"
 tstats = len(sys.argv) > 2 and sys.argv[1] == "--tstats"
 # --metrics <remarks>: the evaluation-score kernels (metrics.hip) - the same rule (a row's logits and class weights stay in registers)
 metrics = len(sys.argv) > 2 and sys.argv[1] == "--metrics"
-# --adam <remarks>: the grouped optimizer kernels of rowops.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
+# --adam <remarks>: the grouped optimizer kernels of adam.hip (parameter groups, AdamW): a group's hyper row must stay in scalar
 # registers and a tile's p / g / m / v in vector registers - zero scratch, no spills; prints the register numbers of each.  The same
-# rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to,
-# and for the criterion kernels of the same file (m2f_ce_kernel, m2f_ce_distill_kernel, m2f_ce_focal_kernel, m2f_ce_rdrop_kernel: one
-# row definition, criterion_row.h; counted by name below)
+# rule for the single-group kernels and the exchange kernel, whose EMA forms (the average stream) carry more per tile than they used to
 adam = len(sys.argv) > 2 and sys.argv[1] == "--adam"
+# --criterion <remarks>: the criterion kernels of rowops.hip (m2f_ce_kernel, m2f_ce_distill_kernel, m2f_ce_focal_kernel,
+# m2f_ce_rdrop_kernel: one row definition, criterion_row.h; counted by name below) - the same rule
+criterion = len(sys.argv) > 2 and sys.argv[1] == "--criterion"
 # --crf <remarks>: the linear-chain CRF kernels (crf.hip) - a lane's transition column / row, its gradient column and the sixteen terms of
 # a step stay in registers through unrolled loops with static indices: zero scratch, no spills; prints the register numbers of each
 crf = len(sys.argv) > 2 and sys.argv[1] == "--crf"
@@ -57,7 +58,7 @@ supcon = len(sys.argv) > 2 and sys.argv[1] == "--supcon"
 # --aux <remarks>: the auxiliary label head's kernels (aux_head.hip) - a row's 16-byte pieces, the sixteen logits, the row's terms and the
 # sixteen accumulators of a parameter-gradient lane stay in registers through unrolled loops with static indices: zero scratch, no spills
 aux = len(sys.argv) > 2 and sys.argv[1] == "--aux"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux or sam) else sys.argv[1]
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux or sam or criterion) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -81,16 +82,21 @@ if adam:
     # shadow-writing: 4 forms each; the exchange
     if len(kernels) < 18:
         sys.exit(f"check_spills: expected the eighteen optimizer kernels in {path}, found {len(kernels)} - did the remark format change?")
-    # the other kernels of rowops.hip under this gate: the four criterion kernels, thin bodies over criterion_row.h's helpers (a row's
-    # logits, weights, probabilities and - with a teacher or a twin - the second row's stay in registers): the plain one, the
-    # distillation one, the focal one with and without a teacher, the R-Drop one
-    criterion = []
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if criterion:
+    # the four criterion kernels, thin bodies over criterion_row.h's helpers (a row's logits, weights, probabilities and - with a teacher
+    # or a twin - the second row's stay in registers): the plain one, the distillation one, the focal one with and without a teacher,
+    # the R-Drop one
+    kernels = []
     for tag, count in (("m2f_ce_kernel", 1), ("m2f_ce_distill_kernel", 1), ("m2f_ce_focal_kernel", 2), ("m2f_ce_rdrop_kernel", 1)):
         found = [r for r in rows if tag in r["name"]]
         if len(found) != count:
             sys.exit(f"check_spills: expected {count} of {tag} in {path}, found {len(found)} - did the remark format change?")
-        criterion += found
-    kernels = kernels + criterion
+        kernels += found
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

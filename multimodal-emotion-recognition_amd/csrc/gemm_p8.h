@@ -29,6 +29,7 @@
 // overtakes an older (range-checked, zero-filling) piece of the same region.
 #pragma once
 #include "gemm_ring.h"
+#include "param_walk.h"      // adam4: the one Adam update of four elements, shared with adam.hip
 
 namespace {
 
@@ -117,20 +118,6 @@ __device__ __forceinline__ void p8_swap2(uint32_t& x, uint32_t& y) {
     auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
     auto q = __builtin_amdgcn_permlane16_swap(r[0], r[1], false, false);
     x = q[0]; y = q[1];
-}
-
-// torch.optim.Adam's update of four consecutive elements: the arithmetic of rowops.hip::adam4, contractions spelled out the same way
-// (every optimizer kernel must produce the same bits: tests/test_shared_shadows_gpu.py compares the trajectories)
-__device__ __forceinline__ void p8_adam4(f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv, float gs, float lr_bc1, float beta1,
-                                         float beta2, float eps, float wd, float inv_sqrt_bc2) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gr = __builtin_fmaf(gg[e], gs, wd * pp[e]);     // coupled L2 (Adam, not AdamW)
-        mm[e] = __builtin_fmaf(beta1, mm[e], (1.f - beta1) * gr);
-        vv[e] = __builtin_fmaf(beta2, vv[e], ((1.f - beta2) * gr) * gr);
-        const float denom = __builtin_fmaf(sqrtf(vv[e]), inv_sqrt_bc2, eps);
-        pp[e] = __builtin_fmaf(-lr_bc1, mm[e] / denom, pp[e]);
-    }
 }
 
 // EPI: 3 = the weight-gradient table with the OPTIMIZER in its epilogue: the accumulators are the gradient; the lane that holds four
@@ -612,8 +599,8 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                     const size_t oc = (size_t)((uint32_t)(row * ldc + col));
                     const char* sl = ringp + (n % 5) * 3072;
                     f32x4 pp = *reinterpret_cast<const f32x4*>(sl), mm = *reinterpret_cast<const f32x4*>(sl + 1024), vv = *reinterpret_cast<const f32x4*>(sl + 2048);
-                    if constexpr (EPI == 6) pp = pp * decay;          // AdamW's param.mul_(1 - lr * wd): rowops.hip::adamw4
-                    p8_adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+                    if constexpr (EPI == 6) pp = pp * decay;          // AdamW's param.mul_(1 - lr * wd): param_walk.h adamw4
+                    adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
                     *reinterpret_cast<f32x4*>(Pp + oc) = pp;
                     __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(Mp + oc));
                     __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(Vp + oc));
@@ -663,7 +650,7 @@ __global__ __launch_bounds__(512) void m2f_gemm_p8_kernel(const GemmBatch gb) {
                                     pp[e] = Pp[oc]; mm[e] = Mp[oc]; vv[e] = Vp[oc];
                                 }
                                 if constexpr (EPI == 6) pp = pp * decay;
-                                p8_adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
+                                adam4(pp, acc[a][b][i][j], mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
 #pragma unroll
                                 for (int e = 0; e < 4; ++e)
                                     if (in[e]) {

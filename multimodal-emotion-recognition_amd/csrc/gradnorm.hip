@@ -18,36 +18,15 @@
 #include <stdint.h>
 #include "common.h"
 #include "ops.h"
+#include "block_sum.h"
+#include "param_walk.h"
 
 namespace {
-
-// butterfly over the 64 lanes: every lane ends with the same sum, formed in the same order
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// workgroup sum of one double per lane: wave shuffle tree, then the WAVES wave sums through LDS, added in wave order by thread 0.
-// `red` = WAVES doubles the caller does not touch until its next barrier.  The result is valid in thread 0 only.
-template <int WAVES>
-__device__ __forceinline__ double block_sum(double x, double* red) {
-    x = wave_sum(x);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) s += red[w];
-    }
-    return s;
-}
 
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
 
 // sixteen bytes of gradients: 4 fp32 or 8 bf16 values
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ u32x4 load16(const void* p) {
     if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
@@ -69,12 +48,6 @@ __device__ __forceinline__ void square16(const u32x4& r, double (&acc)[4]) {
         acc[0] = __builtin_fma(a0, a0, acc[0]); acc[1] = __builtin_fma(a1, a1, acc[1]);
         acc[2] = __builtin_fma(a2, a2, acc[2]); acc[3] = __builtin_fma(a3, a3, acc[3]);
     }
-}
-
-template <bool G16>
-__device__ __forceinline__ double grad1(const void* g, long long o) {
-    if constexpr (G16) return (double)__builtin_bit_cast(float, (uint32_t)static_cast<const uint16_t*>(g)[o] << 16);
-    else return (double)static_cast<const float*>(g)[o];
 }
 
 // G16: the buffer holds bf16 (M2FNet.set_grad_bf16, the data-parallel bf16 exchange), same indexing.  NT: nontemporal loads.
@@ -106,7 +79,7 @@ __global__ __launch_bounds__(256) void m2f_gradnorm_sumsq_kernel(const void* __r
                     square16<G16>(load16<NT>(base + (size_t)e * ESZ), acc);
                 } else {
                     for (int k = e; k < sl.n; ++k) {
-                        const double a = grad1<G16>(g, sl.off + k);
+                        const double a = (double)param_grad1<G16>(g, sl.off + k);
                         acc[0] = __builtin_fma(a, a, acc[0]);
                     }
                 }

@@ -784,7 +784,7 @@ hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, floa
 // decay = 1 - lr * weight_decay for a decoupled group (whose coupled weight decay is 0), 1.0f otherwise.  rows_host: n_groups x 8 floats,
 // passed to the refresh kernel by value.  The shadow-writing form walks items[] (the tensors some group owns, re-tiled; item_group[] runs
 // parallel to it); the flat form walks slices of at most M2F_PARAM_SLICE elements of one owned tensor (fp32 mode: no shadows).
-// ParamSlice: the one slice of the per-tensor kernels (rowops.hip, gradnorm.hip, tensor_stats.hip) - at most M2F_PARAM_SLICE
+// ParamSlice: the one slice of the per-tensor kernels (adam.hip and sam.hip through param_walk.h; gradnorm.hip, tensor_stats.hip) - at most M2F_PARAM_SLICE
 // consecutive elements of ONE parameter tensor (`off`: its first element in the flat buffer; only the last slice of a tensor is short),
 // cut by the host from the parameter map (param_tables.hip), so the alignment pads between tensors belong to no slice.  tag: the owning
 // group for the grouped Adam and exchange kernels, the tensor's index for the statistics kernels; the norm kernel does not read it.

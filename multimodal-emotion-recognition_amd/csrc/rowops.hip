@@ -1,6 +1,6 @@
 // Row-wise (HBM-bound) kernels of the M2FNet step for gfx950: LayerNorm forward/backward with fused
-// residual / dropout, the label-smoothed cross-entropy criterion (reference src/train.py:48-50), the
-// dropout-mask re-application used in backward, and the fused Adam update (src/train.py:56).
+// residual / dropout, the label-smoothed cross-entropy criterion (reference src/train.py:48-50) and the
+// dropout-mask re-application used in backward.  (The fused optimizer is adam.hip.)
 // One wavefront per token row, rows cached in registers, 16-byte coalesced accesses, wave shuffles for
 // the row reductions; column reductions (dgamma/dbeta) go through per-block partials (deterministic,
 // no atomics, no memset).
@@ -12,10 +12,11 @@
 #include "common.h"
 #include "ops.h"
 #include "criterion_row.h"
+#include "param_walk.h"
 #include <algorithm>
 
 // No floating-point contraction in this file: several kernels restate the same formulas in different surroundings (ring and
-// register-staged GEMM epilogues, fp32 and bf16 attention forms, flat and shadow-writing Adam), and with -ffp-contract=fast (the
+// register-staged GEMM epilogues, fp32 and bf16 attention forms), and with -ffp-contract=fast (the
 // HIP default) the compiler is free to fuse a*b+c in one of them and not in the other - a 1-ulp difference that would break the
 // bit-for-bit comparisons the tests make between the forms.  These kernels are bound by memory or by MFMA, not by VALU multiplies.
 #pragma clang fp contract(off)
@@ -559,360 +560,6 @@ __global__ void m2f_rng_advance_kernel(uint32_t* rng) {
     }
 }
 
-// Adam update of four consecutive elements (registers in, registers out).  Every optimizer kernel of this file goes through this
-// one function and its contractions are spelled out (the file is compiled with fp contraction off): left to the compiler
-// (contract(fast)) the flat kernel and the shadow-writing kernel fused `g * gs + wd * p` differently once one of them became a
-// template, and a data-parallel run (bucket-wise shadow-writing steps) drifted from the single-process run by an ulp per step.
-__device__ __forceinline__ void adam4(f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv, float gs, float lr_bc1, float beta1,
-                                      float beta2, float eps, float wd, float inv_sqrt_bc2) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gr = __builtin_fmaf(gg[e], gs, wd * pp[e]);     // coupled L2 (Adam, not AdamW)
-        mm[e] = __builtin_fmaf(beta1, mm[e], (1.f - beta1) * gr);
-        vv[e] = __builtin_fmaf(beta2, vv[e], ((1.f - beta2) * gr) * gr);
-        const float denom = __builtin_fmaf(sqrtf(vv[e]), inv_sqrt_bc2, eps);
-        pp[e] = __builtin_fmaf(-lr_bc1, mm[e] / denom, pp[e]);
-    }
-}
-
-// The grouped kernels' update (one hyper row per parameter group, m2f_adam_hyper_groups_kernel): torch.optim.AdamW multiplies the
-// parameter by `decay` = 1 - lr * weight_decay first (torch's param.mul_: ONE rounded fp32 multiply; the row of a decoupled group holds
-// a coupled weight decay of 0), then the statements of adam4.  A coupled group's row holds decay = 1.0f, an exact multiply: its result
-// is adam4's, bit for bit.
-__device__ __forceinline__ void adamw4(f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv, float gs, float lr_bc1, float beta1,
-                                       float beta2, float eps, float wd, float inv_sqrt_bc2, float decay) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) pp[e] = pp[e] * decay;
-    adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
-}
-
-// Exponential moving average of the weights (optim.FusedAdam(ema_decay=...); torch.optim.swa_utils.AveragedModel.update_parameters with
-// get_ema_multi_avg_fn(decay): e.lerp_(p, 1 - decay)) of four consecutive elements, applied to the parameter adam4 / adamw4 has just
-// produced.  w = (float)(1 - decay_t), formed in double on the host, the same for every launch of one step.  Written once, with its
-// contraction spelled out, for adam4's reason: every form of the update must give the average the same bits.  w == 1 is the first
-// update (torch's n_averaged == 0 copy): the average becomes the parameter's bits, whatever the buffer held.
-__device__ __forceinline__ void ema4(f32x4& ee, const f32x4& pp, float w) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ee[e] = (w == 1.0f) ? pp[e] : __builtin_fmaf(w, pp[e] - ee[e], ee[e]);
-}
-
-// G16: the gradient buffer holds bf16 (the data-parallel bf16 exchange), everything else stays fp32
-// EMA: one more stream - the average `ema` of the parameters, read and written once per step like m and v and nontemporal like them
-// (8 B per parameter on top of 28); EMA == false is the kernel without it, `ema` / `ema_w` unread.
-template <bool G16, bool EMA>
-__global__ __launch_bounds__(256) void m2f_adam_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, int64_t n4, float lr_bc1, float beta1, float beta2,
-                                                       float eps, float wd, float inv_sqrt_bc2, const float* __restrict__ gs_ptr,
-                                                       float* __restrict__ ema, float ema_w) {
-    // g, m, v are streamed once per step: nontemporal accesses keep them from displacing p (re-read by the bf16 cast that
-    // opens the next forward) in the L2 / Infinity Cache; measured 0.554 -> 0.524 ms per C3 step for the optimizer part
-    const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
-        f32x4 gg;
-        if constexpr (G16) {
-            const uint2 raw = reinterpret_cast<const uint2*>(g)[i];
-            gg[0] = __builtin_bit_cast(float, raw.x << 16); gg[1] = __builtin_bit_cast(float, raw.x & 0xFFFF0000u);
-            gg[2] = __builtin_bit_cast(float, raw.y << 16); gg[3] = __builtin_bit_cast(float, raw.y & 0xFFFF0000u);
-        } else {
-            gg = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-        }
-        f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
-        f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
-        adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
-        reinterpret_cast<f32x4*>(p)[i] = pp;
-        __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m) + i);
-        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
-        if constexpr (EMA) {
-            f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(ema) + i);
-            ema4(ee, pp, ema_w);
-            __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema) + i);
-        }
-    }
-}
-
-// four consecutive gradient elements from the fp32 buffer or (G16: the data-parallel bf16 exchange) from the reduced bf16 buffer
-template <bool G16>
-__device__ __forceinline__ f32x4 adam_grad4(const void* g, long long o) {
-    if constexpr (G16) {
-        const uint2 raw = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(g) + o);
-        return (f32x4){__builtin_bit_cast(float, raw.x << 16), __builtin_bit_cast(float, raw.x & 0xFFFF0000u),
-                       __builtin_bit_cast(float, raw.y << 16), __builtin_bit_cast(float, raw.y & 0xFFFF0000u)};
-    } else {
-        return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(static_cast<const float*>(g) + o));
-    }
-}
-template <bool G16>
-__device__ __forceinline__ float adam_grad1(const void* g, long long o) {
-    if constexpr (G16) return __builtin_bit_cast(float, (uint32_t)static_cast<const uint16_t*>(g)[o] << 16);
-    else return static_cast<const float*>(g)[o];
-}
-
-// see ops.h (AdamItem).  Persistent 1-D grid over tiles [tile_first, total_tiles) of items[0, n_items) (tile_begin[] holds absolute
-// tile numbers); tile -> item by bisection of the prefix array (kept in LDS).
-// GROUPED: items[] holds the tensors some parameter group owns, item_group[] (parallel to items[]) their group, and the six factors
-// plus `decay` come from row item_group[i] of the hyper table `hyt` instead of the arguments - the item is the same in every lane of
-// the workgroup, so the row arrives by scalar loads and costs no vector register.
-// EMA: the average stream of ema4 (see m2f_adam_kernel) over exactly the elements whose parameter the tile writes.
-template <bool G16, bool GROUPED = false, bool EMA = false>
-__device__ __forceinline__ void adam_shadow_body(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, uint16_t* __restrict__ sh,
-                                                 const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
-                                                 int n_items, int tile_first, int total_tiles, float lr_bc1, float beta1,
-                                                 float beta2, float eps, float wd, float inv_sqrt_bc2,
-                                                 const float* __restrict__ gs_ptr, const float* __restrict__ hyt = nullptr,
-                                                 const int* __restrict__ item_group = nullptr, float* __restrict__ ema = nullptr,
-                                                 float ema_w = 0.f) {
-    __shared__ float tile[64][65];
-    __shared__ int tb[M2F_ADAM_MAX_ITEMS + 1];
-    const int tid = threadIdx.x;
-    for (int i = tid; i <= n_items; i += 256) tb[i] = tile_begin[i];
-    __syncthreads();
-    const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
-    for (int t = tile_first + (int)blockIdx.x; t < total_tiles; t += gridDim.x) {
-        int lo = 0, hi = n_items - 1;                               // last item whose first tile is <= t (block-uniform)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (tb[mid] <= t) lo = mid; else hi = mid - 1;
-        }
-        const AdamItem it = items[lo];
-        const int tl = t - tb[lo];
-        float decay = 1.f;
-        if constexpr (GROUPED) {
-            const float* __restrict__ h = hyt + 8 * item_group[__builtin_amdgcn_readfirstlane(lo)];
-            lr_bc1 = h[0]; beta1 = h[1]; beta2 = h[2]; eps = h[3]; wd = h[4]; inv_sqrt_bc2 = h[5]; decay = h[6];
-        }
-        auto update = [&](f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv) {
-            if constexpr (GROUPED) adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
-            else adam4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2);
-        };
-        if (it.rows == 0) {                                         // 1-D parameter: 4096 consecutive elements per tile
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const long long idx = (long long)tl * 4096 + q * 1024 + tid * 4;
-                if (idx < it.cols) {
-                    const long long o = it.off + idx;
-                    f32x4 pp = *reinterpret_cast<const f32x4*>(p + o);
-                    const f32x4 gg = adam_grad4<G16>(g, o);
-                    f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + o));
-                    f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + o));
-                    update(pp, gg, mm, vv);
-                    *reinterpret_cast<f32x4*>(p + o) = pp;
-                    __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
-                    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
-                    if constexpr (EMA) {
-                        f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
-                        ema4(ee, pp, ema_w);
-                        __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
-                    }
-                }
-            }
-            continue;
-        }
-        const int rows = it.rows, cols = it.cols, ldd = (cols + 7) & ~7, ldt = (rows + 7) & ~7;
-        const int r0 = (tl / it.tiles_c) << 6, c0 = (tl % it.tiles_c) << 6;
-        const int lr = tid >> 4, c = 4 * (tid & 15), gc = c0 + c;
-        const bool vec = (cols & 3) == 0;                           // then every 4-column group is whole and 16-byte aligned
-        f32x4 pp[4], gg[4], mm[4], vv[4];
-        bool in[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                               // all loads of the tile first, then the arithmetic
-            const int gr = r0 + lr + 16 * i;
-            in[i] = gr < rows && gc < cols;
-            const long long o = it.off + (long long)(in[i] ? gr : 0) * cols + (in[i] ? gc : 0);
-            if (vec) {
-                pp[i] = *reinterpret_cast<const f32x4*>(p + o);
-                gg[i] = adam_grad4<G16>(g, o);
-                mm[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + o));
-                vv[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + o));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long long oe = o + ((in[i] && gc + e < cols) ? e : 0);
-                    pp[i][e] = p[oe]; gg[i][e] = adam_grad1<G16>(g, oe); mm[i][e] = m[oe]; vv[i][e] = v[oe];
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = lr + 16 * i, gr = r0 + r;
-            update(pp[i], gg[i], mm[i], vv[i]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) tile[r][c + e] = (in[i] && gc + e < cols) ? pp[i][e] : 0.f;
-            if (in[i]) {
-                const long long o = it.off + (long long)gr * cols + gc;
-                uint16_t* q = sh + it.soff + (long long)gr * ldd + gc;
-                if (vec) {
-                    *reinterpret_cast<f32x4*>(p + o) = pp[i];
-                    __builtin_nontemporal_store(mm[i], reinterpret_cast<f32x4*>(m + o));
-                    __builtin_nontemporal_store(vv[i], reinterpret_cast<f32x4*>(v + o));
-                    uint2 w;
-                    w.x = (uint32_t)m2f_bf16_bits(pp[i][0]) | ((uint32_t)m2f_bf16_bits(pp[i][1]) << 16);
-                    w.y = (uint32_t)m2f_bf16_bits(pp[i][2]) | ((uint32_t)m2f_bf16_bits(pp[i][3]) << 16);
-                    *reinterpret_cast<uint2*>(q) = w;
-                    if constexpr (EMA) {
-                        f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
-                        ema4(ee, pp[i], ema_w);
-                        __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (gc + e < cols) { p[o + e] = pp[i][e]; m[o + e] = mm[i][e]; v[o + e] = vv[i][e]; q[e] = m2f_bf16_bits(pp[i][e]); }
-                    if constexpr (EMA) {
-                        f32x4 ee = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gc + e < cols) ee[e] = ema[o + e];
-                        ema4(ee, pp[i], ema_w);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) if (gc + e < cols) ema[o + e] = ee[e];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        {   // W^T shadow: 8 consecutive source rows of one column per lane = 16 bytes of a dst_t row (m2f_tile64)
-            const int r8 = tid & 7;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int cc = (tid >> 3) + 32 * j;
-                const int gcol = c0 + cc, gr0 = r0 + 8 * r8;
-                if (gcol < cols && gr0 < ldt) {
-                    uint16_t h[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) h[k] = m2f_bf16_bits(tile[8 * r8 + k][cc]);
-                    uint4 w;
-                    w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16); w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-                    w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16); w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
-                    *reinterpret_cast<uint4*>(sh + it.soff_t + (long long)gcol * ldt + gr0) = w;      // soff_t, ldt: multiples of 8
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-template <bool G16, bool EMA>
-__global__ __launch_bounds__(256) void m2f_adam_shadow_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, uint16_t* __restrict__ sh,
-                                                              const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
-                                                              int n_items, int tile_first, int total_tiles, float lr_bc1, float beta1,
-                                                              float beta2, float eps, float wd, float inv_sqrt_bc2,
-                                                              const float* __restrict__ gs_ptr, float* __restrict__ ema, float ema_w) {
-    adam_shadow_body<G16, false, EMA>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, lr_bc1, beta1, beta2, eps, wd,
-                                      inv_sqrt_bc2, gs_ptr, nullptr, nullptr, ema, ema_w);
-}
-// the same update with the step-dependent factors read from device memory (m2f_launch_adam_hyper): a node of the captured step graph
-__global__ __launch_bounds__(256) void m2f_adam_shadow_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                  float* __restrict__ v, uint16_t* __restrict__ sh,
-                                                                  const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
-                                                                  int n_items, int total_tiles, const float* __restrict__ hy,
-                                                                  const float* __restrict__ gs_ptr) {
-    adam_shadow_body<false>(p, g, m, v, sh, items, tile_begin, n_items, 0, total_tiles, hy[0], hy[1], hy[2], hy[3], hy[4], hy[5], gs_ptr);
-}
-
-// Parameter groups (optim.FusedAdam(params=[...]), FusedAdamW): the shadow-writing update over the tensors of items[] with the hyper
-// row of each item's group.  The rows live in device memory (refreshed once per step by m2f_adam_hyper_groups_kernel), so this ONE
-// form serves the eager step, the [first, end) ranges of the data-parallel path and a captured graph.
-template <bool G16, bool EMA>
-__global__ __launch_bounds__(256) void m2f_adam_shadow_grouped_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                                      float* __restrict__ v, uint16_t* __restrict__ sh,
-                                                                      const AdamItem* __restrict__ items, const int* __restrict__ tile_begin,
-                                                                      const int* __restrict__ item_group, int n_items, int tile_first,
-                                                                      int total_tiles, const float* __restrict__ hyt,
-                                                                      const float* __restrict__ gs_ptr, float* __restrict__ ema, float ema_w) {
-    adam_shadow_body<G16, true, EMA>(p, g, m, v, sh, items, tile_begin, n_items, tile_first, total_tiles, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gs_ptr,
-                                     hyt, item_group, ema, ema_w);
-}
-
-// fp32 mode (no shadows to write): the flat kernel runs over pads and tensors alike and cannot know a group, so the grouped form
-// walks SLICES - at most M2F_PARAM_SLICE consecutive elements of one owned tensor (ops.h ParamSlice; cut by the host from the parameter
-// map as the gradient norm's are: pads belong to no slice) - each with its group's hyper row.  16-byte accesses, g / m / v nontemporal
-// as in m2f_adam_kernel; the last 1-3 elements of a tensor whose size is no multiple of 4 go one by one, nothing behind them is touched.
-template <bool G16, bool EMA>
-__global__ __launch_bounds__(256) void m2f_adam_slices_kernel(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, const ParamSlice* __restrict__ slices, int s0, int s1,
-                                                              const float* __restrict__ hyt, const float* __restrict__ gs_ptr,
-                                                              float* __restrict__ ema, float ema_w) {
-    const float gs = gs_ptr ? 1.0f / *gs_ptr : 1.0f;
-    const int tid = threadIdx.x;
-    for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
-        const ParamSlice sl = slices[s];
-        const float* __restrict__ h = hyt + 8 * sl.tag;
-        const float lr_bc1 = h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4], inv_sqrt_bc2 = h[5], decay = h[6];
-#pragma unroll 2
-        for (int j = 0; j < M2F_PARAM_SLICE / 1024; ++j) {
-            const int e = (j * 256 + tid) * 4;
-            const long long o = sl.off + e;                         // tensor offsets are multiples of 64 elements: 16-byte aligned
-            if (e + 4 <= sl.n) {
-                f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + o));
-                const f32x4 gg = adam_grad4<G16>(g, o);
-                f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + o));
-                f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + o));
-                adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
-                *reinterpret_cast<f32x4*>(p + o) = pp;
-                __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + o));
-                __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + o));
-                if constexpr (EMA) {
-                    f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ema + o));
-                    ema4(ee, pp, ema_w);
-                    __builtin_nontemporal_store(ee, reinterpret_cast<f32x4*>(ema + o));
-                }
-            } else if (e < sl.n) {
-                f32x4 pp = {0.f, 0.f, 0.f, 0.f}, gg = pp, mm = pp, vv = pp;
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (e + k < sl.n) { pp[k] = p[o + k]; gg[k] = adam_grad1<G16>(g, o + k); mm[k] = m[o + k]; vv[k] = v[o + k]; }
-                adamw4(pp, gg, mm, vv, gs, lr_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, decay);
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (e + k < sl.n) { p[o + k] = pp[k]; m[o + k] = mm[k]; v[o + k] = vv[k]; }
-                if constexpr (EMA) {
-                    f32x4 ee = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) if (e + k < sl.n) ee[k] = ema[o + k];
-                    ema4(ee, pp, ema_w);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) if (e + k < sl.n) ema[o + k] = ee[k];
-                }
-            }
-        }
-    }
-}
-
-// optim.FusedAdam.averaged_parameters(): params[i] <-> ema[i] in place over the slices [s0, s1) of whole owned tensors (the list the
-// flat grouped kernel walks: pads and the tensors of no group belong to no slice and are not touched).  16-byte accesses; the last
-// 1-3 elements of a tensor whose size is no multiple of 4 go one by one.  Run twice, it restores both buffers bit for bit.
-__global__ __launch_bounds__(256) void m2f_ema_exchange_kernel(float* __restrict__ p, float* __restrict__ ema,
-                                                               const ParamSlice* __restrict__ slices, int s0, int s1) {
-    const int tid = threadIdx.x;
-    for (int s = s0 + (int)blockIdx.x; s < s1; s += (int)gridDim.x) {
-        const ParamSlice sl = slices[s];
-#pragma unroll 2
-        for (int j = 0; j < M2F_PARAM_SLICE / 1024; ++j) {
-            const int e = (j * 256 + tid) * 4;
-            const long long o = sl.off + e;
-            if (e + 4 <= sl.n) {
-                const f32x4 pp = *reinterpret_cast<const f32x4*>(p + o);
-                const f32x4 ee = *reinterpret_cast<const f32x4*>(ema + o);
-                *reinterpret_cast<f32x4*>(p + o) = ee;
-                *reinterpret_cast<f32x4*>(ema + o) = pp;
-            } else if (e < sl.n) {
-                for (int k = 0; k < 3; ++k)
-                    if (e + k < sl.n) { const float a = p[o + k]; p[o + k] = ema[o + k]; ema[o + k] = a; }
-            }
-        }
-    }
-}
-
-// the hyper table: G rows of 8 floats (lr / bc1, beta1, beta2, eps, coupled wd, 1 / sqrt(bc2), decay, spare), formed by the host and
-// passed BY VALUE - no host buffer to keep alive, no sync, and a captured graph that reads the table sees the new rows at its next replay
-struct AdamHyperRows { float r[M2F_ADAM_MAX_GROUPS * 8]; };
-__global__ __launch_bounds__(M2F_ADAM_MAX_GROUPS * 8) void m2f_adam_hyper_groups_kernel(float* __restrict__ h, int n, const AdamHyperRows rows) {
-    const int i = threadIdx.x;
-    if (i < n) h[i] = rows.r[i];
-}
-
 template <bool BWD>
 hipError_t ln_launch(LnBatch& lb, hipStream_t stream) {
     if (lb.count <= 0 || lb.count > M2F_LN_MAX_PROBLEMS || lb.T <= 0) return hipErrorInvalidValue;
@@ -1207,47 +854,22 @@ hipError_t m2f_launch_rng_advance(uint32_t* rng, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t m2f_launch_adam_shadowed(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
-                                    const int* tile_begin, int n_items, int tile_first, int total_tiles, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                                    float* ema, float ema_w, hipStream_t stream) {
-    const int n_tiles = total_tiles - tile_first;
-    if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || tile_first < 0 || n_tiles < 1 || !items || !tile_begin || !shadow) return hipErrorInvalidValue;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const int blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, n_items, tile_first,
-                           total_tiles, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale_ptr, ema, ema_w);
-    };
-    if (ema) { if (g_is_bf16) go(m2f_adam_shadow_kernel<true, true>); else go(m2f_adam_shadow_kernel<false, true>); }
-    else if (g_is_bf16) go(m2f_adam_shadow_kernel<true, false>);
-    else go(m2f_adam_shadow_kernel<false, false>);
-    return hipGetLastError();
-}
-
 // fp32 -> bf16 of the flat-buffer ranges of `items` (whole tensors incl. their pads: rows > 0 -> rows x cols elements, else `cols`): the
 // gradients the weight-gradient table launch did NOT write as bf16 itself (biases, LayerNorm, the matrices outside the table) when the
 // step leaves its gradients in a bf16 buffer (m2f_plan_grad_bf16); tiles of 4,096 elements, tile -> item by bisection
 __global__ __launch_bounds__(256) void m2f_cast_items_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, const AdamItem* __restrict__ items,
                                                             const int* __restrict__ tile_begin, int n_items, int total_tiles) {
     __shared__ int tb[M2F_ADAM_MAX_ITEMS + 1];
-    for (int i = threadIdx.x; i <= n_items; i += 256) tb[i] = tile_begin[i];
-    __syncthreads();
+    walk_prefix(tb, tile_begin, n_items);
     for (int t = blockIdx.x; t < total_tiles; t += gridDim.x) {
-        int lo = 0, hi = n_items - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tb[mid] <= t) lo = mid; else hi = mid - 1; }
-        const AdamItem it = items[lo];
+        const WalkTile wt = walk_tile(tb, items, n_items, t);
+        const AdamItem& it = wt.it;
         const long long n = it.rows > 0 ? (long long)it.rows * it.cols : (long long)it.cols;
-        const long long base = (long long)(t - tb[lo]) * 4096;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const long long idx = base + q * 1024 + threadIdx.x * 4;
+            const long long idx = walk_run_index(wt.tl, q);
             if (idx + 3 < n) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(src + it.off + idx);
-                uint2 w;
-                w.x = (uint32_t)m2f_bf16_bits(v[0]) | ((uint32_t)m2f_bf16_bits(v[1]) << 16);
-                w.y = (uint32_t)m2f_bf16_bits(v[2]) | ((uint32_t)m2f_bf16_bits(v[3]) << 16);
-                *reinterpret_cast<uint2*>(dst + it.off + idx) = w;
+                *reinterpret_cast<u32x2*>(dst + it.off + idx) = param_bf16x4(*reinterpret_cast<const f32x4*>(src + it.off + idx));
             } else {
                 for (int e = 0; e < 4; ++e) if (idx + e < n) dst[it.off + idx + e] = m2f_bf16_bits(src[it.off + idx + e]);
             }
@@ -1257,90 +879,5 @@ __global__ __launch_bounds__(256) void m2f_cast_items_kernel(const float* __rest
 hipError_t m2f_launch_cast_items(const float* src, uint16_t* dst, const AdamItem* items, const int* tile_begin, int n_items, int total_tiles, hipStream_t stream) {
     if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || total_tiles < 1 || !items || !tile_begin || !src || !dst) return hipErrorInvalidValue;
     hipLaunchKernelGGL(m2f_cast_items_kernel, dim3(total_tiles < 2048 ? total_tiles : 2048), dim3(256), 0, stream, src, dst, items, tile_begin, n_items, total_tiles);
-    return hipGetLastError();
-}
-
-// step-dependent factors of the update in device memory (a captured graph cannot take them as kernel arguments): one thread
-__global__ void m2f_adam_hyper_kernel(float* __restrict__ h, float lr_bc1, float beta1, float beta2, float eps, float wd, float inv_sqrt_bc2) {
-    h[0] = lr_bc1; h[1] = beta1; h[2] = beta2; h[3] = eps; h[4] = wd; h[5] = inv_sqrt_bc2; h[6] = 0.f; h[7] = 0.f;
-}
-hipError_t m2f_launch_adam_hyper(float* hyper_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int step, hipStream_t stream) {
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);       // as m2f_launch_adam_shadowed computes them
-    hipLaunchKernelGGL(m2f_adam_hyper_kernel, dim3(1), dim3(1), 0, stream, hyper_dev, (float)(lr / bc1), beta1, beta2, eps, weight_decay,
-                       (float)(1.0 / sqrt(bc2)));
-    return hipGetLastError();
-}
-// the shadow-writing kernel with those factors read from `hyper_dev` (m2f_adam_shadow_dev_kernel: same body, same arithmetic)
-hipError_t m2f_launch_adam_shadowed_dev(float* p, const float* g, float* m, float* v, uint16_t* shadow, const AdamItem* items, const int* tile_begin,
-                                        int n_items, int total_tiles, const float* hyper_dev, const float* grad_scale_ptr, hipStream_t stream) {
-    if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || total_tiles < 1 || !items || !tile_begin || !shadow || !hyper_dev) return hipErrorInvalidValue;
-    const int blocks = total_tiles < 256 * 8 ? total_tiles : 256 * 8;
-    hipLaunchKernelGGL(m2f_adam_shadow_dev_kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, n_items, total_tiles,
-                       hyper_dev, grad_scale_ptr);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_adam(float* p, const void* g, int g_is_bf16, float* m, float* v, int64_t n, float lr, float beta1,
-                           float beta2, float eps, float weight_decay, int step, const float* grad_scale_ptr,
-                           float* ema, float ema_w, hipStream_t stream) {
-    if (n & 3) return hipErrorInvalidValue;      // flat buffers are padded to 64 floats per tensor
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const int64_t n4 = n >> 2;
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, n4, (float)(lr / bc1), beta1, beta2, eps, weight_decay,
-                           (float)(1.0 / sqrt(bc2)), grad_scale_ptr, ema, ema_w);
-    };
-    if (ema) { if (g_is_bf16) go(m2f_adam_kernel<true, true>); else go(m2f_adam_kernel<false, true>); }
-    else if (g_is_bf16) go(m2f_adam_kernel<true, false>);
-    else go(m2f_adam_kernel<false, false>);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_adam_hyper_groups(float* table_dev, const float* rows_host, int n_groups, hipStream_t stream) {
-    if (!table_dev || !rows_host || n_groups < 1 || n_groups > M2F_ADAM_MAX_GROUPS) return hipErrorInvalidValue;
-    AdamHyperRows rows;
-    for (int i = 0; i < M2F_ADAM_MAX_GROUPS * 8; ++i) rows.r[i] = i < n_groups * 8 ? rows_host[i] : 0.f;
-    hipLaunchKernelGGL(m2f_adam_hyper_groups_kernel, dim3(1), dim3(M2F_ADAM_MAX_GROUPS * 8), 0, stream, table_dev, n_groups * 8, rows);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_adam_shadowed_grouped(float* p, const void* g, int g_is_bf16, float* m, float* v, uint16_t* shadow, const AdamItem* items,
-                                            const int* tile_begin, const int* item_group, int n_items, int tile_first, int total_tiles,
-                                            const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w,
-                                            hipStream_t stream) {
-    const int n_tiles = total_tiles - tile_first;
-    if (n_items < 1 || n_items > M2F_ADAM_MAX_ITEMS || tile_first < 0 || n_tiles < 1 || !items || !tile_begin || !item_group || !shadow || !hyper_table)
-        return hipErrorInvalidValue;
-    const int blocks = n_tiles < 256 * 8 ? n_tiles : 256 * 8;
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, shadow, items, tile_begin, item_group, n_items, tile_first,
-                           total_tiles, hyper_table, grad_scale_ptr, ema, ema_w);
-    };
-    if (ema) { if (g_is_bf16) go(m2f_adam_shadow_grouped_kernel<true, true>); else go(m2f_adam_shadow_grouped_kernel<false, true>); }
-    else if (g_is_bf16) go(m2f_adam_shadow_grouped_kernel<true, false>);
-    else go(m2f_adam_shadow_grouped_kernel<false, false>);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_adam_slices(float* p, const void* g, int g_is_bf16, float* m, float* v, const ParamSlice* slices, int s0, int s1,
-                                  const float* hyper_table, const float* grad_scale_ptr, float* ema, float ema_w, hipStream_t stream) {
-    if (!p || !g || !m || !v || !slices || !hyper_table || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
-    if (s1 == s0) return hipSuccess;
-    const int blocks = s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8;
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, p, g, m, v, slices, s0, s1, hyper_table, grad_scale_ptr, ema, ema_w);
-    };
-    if (ema) { if (g_is_bf16) go(m2f_adam_slices_kernel<true, true>); else go(m2f_adam_slices_kernel<false, true>); }
-    else if (g_is_bf16) go(m2f_adam_slices_kernel<true, false>);
-    else go(m2f_adam_slices_kernel<false, false>);
-    return hipGetLastError();
-}
-
-hipError_t m2f_launch_ema_exchange(float* p, float* ema, const ParamSlice* slices, int s0, int s1, hipStream_t stream) {
-    if (!p || !ema || !slices || s0 < 0 || s1 < s0) return hipErrorInvalidValue;
-    if (s1 == s0) return hipSuccess;
-    hipLaunchKernelGGL(m2f_ema_exchange_kernel, dim3(s1 - s0 < 256 * 8 ? s1 - s0 : 256 * 8), dim3(256), 0, stream, p, ema, slices, s0, s1);
     return hipGetLastError();
 }

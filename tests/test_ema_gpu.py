@@ -1,4 +1,4 @@
-"""The exponential moving average of the weights inside the optimizer kernels (FusedAdam(ema_decay=...); csrc/rowops.hip: the EMA
+"""The exponential moving average of the weights inside the optimizer kernels (FusedAdam(ema_decay=...); csrc/adam.hip: the EMA
 forms of the flat, shadow-writing, grouped and slice kernels, ema4, the exchange kernel).
 
 What is compared against what:

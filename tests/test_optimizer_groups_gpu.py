@@ -1,4 +1,4 @@
-"""Parameter groups and decoupled weight decay on the device: FusedAdam(params=[...]) / FusedAdamW (csrc/rowops.hip: the grouped
+"""Parameter groups and decoupled weight decay on the device: FusedAdam(params=[...]) / FusedAdamW (csrc/adam.hip: the grouped
 shadow-writing and slice kernels, the hyper table; csrc/gemm_p8.h EPI 6: the grouped in-launch optimizer).
 
 What is compared against what:

@@ -1,4 +1,4 @@
-"""The weight average inside the optimizer kernels (FusedAdam(ema_decay=...), csrc/rowops.hip) at bench geometry C3, bf16 mode.
+"""The weight average inside the optimizer kernels (FusedAdam(ema_decay=...), csrc/adam.hip) at bench geometry C3, bf16 mode.
 
 Prints one JSON object with, for fp32 gradients and for bf16 gradients (M2FNet.set_grad_bf16):
   * "step_ms": the whole step - train_step + optimizer.step() - in three variants alternated in one process on the same model, timed
