@@ -80,6 +80,15 @@ __device__ __forceinline__ f32x4 dot_rows_bf16(const float* arow, const float* b
 // token row tok0 + lane in both layouts) are fetched WITH the slabs, a range-checked byte load beside the pad flags'; a lane keeps the
 // ids of the 4 NT keys its score registers belong to as NT packed words (4 NT shuffles, once), takes its query's id with one more
 // shuffle per query tile, and tests one byte per score element: no limit on distinct ids, no LDS, no atomics.
+// Result stores of the one-tile (NT == 1) forward and backward kernels, the ones a training step launches: write-through when
+// M2F_WT_ATTN is set (common.h) - a relaxed agent-scope atomic store is `global_store_dword / _short ... sc1` on gfx950, the
+// same bytes as the plain store.  Every other tile count keeps plain stores.
+template <bool WT, typename T>
+__device__ __forceinline__ void attn_st(T* p, T v) {
+    if constexpr (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+
 template <int NT, bool BAND, bool BIAS = false, bool SPK = false>
 __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) {
     static_assert(sizeof(AttnBatch) + 56 <= 256 + 512, "m2f_kernarg_warm ranges no longer cover AttnBatch + the hidden arguments");
@@ -149,6 +158,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
     float* probs = P.probs + (size_t)bh * Lp * Lp;
     uint16_t* out16 = m2f_shadow_of(ab.sh, P.out);
     const bool w32 = !(P.no_f32 && out16);                  // (no fp32 reader: the bf16 shadow is the result)
+    constexpr bool WT = M2F_WT_ATTN && NT == 1;
     // SPK: this head's class (uniform per workgroup) and the ids of the keys of this lane's score registers, one word per key tile
     int spk_cls = M2F_SPK_NONE;
     uint32_t spk4[NT];
@@ -221,7 +231,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * jt + 4 * lg + r;
                 float p = s[jt][r] * inv;
-                if (wv == 0) probs[(size_t)j * Lp + i] = p;  // P^T, pre-dropout (lanes: consecutive i); one wave writes it
+                if (wv == 0) attn_st<WT>(probs + (size_t)j * Lp + i, p);  // P^T, pre-dropout (lanes: consecutive i); one wave writes it
                 if (site) p = m2f_keep(key, (uint32_t)((bh * LM + i) * LM + j), ab.drop_thresh) ? p * ab.drop_scale : 0.f;
                 s[jt][r] = p;
             }
@@ -240,8 +250,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
                 const int io = 16 * it + 4 * lg + r;
                 if (io < L && c < hd) {
                     const size_t idx = (tok0 + io) * P.ldo + h * hd + c;
-                    if (w32) P.out[idx] = o[r];
-                    if (out16) out16[idx] = m2f_bf16_bits(o[r]);
+                    if (w32) attn_st<WT>(P.out + idx, o[r]);
+                    if (out16) attn_st<WT>(out16 + idx, m2f_bf16_bits(o[r]));
                 }
             }
         }
@@ -252,8 +262,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_fwd_kernel(const AttnBatch ab) 
         for (int r = tail0 + wv; r < ab.T; r += NWAVE)
             for (int c = lane; c < hd; c += 64) {
                 const size_t idx = (size_t)r * P.ldo + h * hd + c;
-                if (w32) P.out[idx] = 0.f;
-                if (out16) out16[idx] = 0;
+                if (w32) attn_st<WT>(P.out + idx, 0.f);
+                if (out16) attn_st<WT>(out16 + idx, (uint16_t)0);
             }
     }
 }
@@ -376,6 +386,7 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
     uint16_t* dk16 = m2f_shadow_of(ab.sh, P.dk);
     uint16_t* dv16 = m2f_shadow_of(ab.sh, P.dv);
     const bool w32 = !(P.no_f32 && dq16 && dk16 && dv16);
+    constexpr bool WT = M2F_WT_ATTN && NT == 1;
 
     // ---- orientation X: lane = query row i, registers = keys j  ->  dQ = dS K ----------------------
 #pragma unroll 1
@@ -422,8 +433,8 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
                 const int io = 16 * it + 4 * lg + r;
                 if (io < L && c < hd) {
                     const size_t idx = (tok0 + io) * P.lddq + h * hd + c;
-                    if (w32) P.dq[idx] = o[r];
-                    if (dq16) dq16[idx] = m2f_bf16_bits(o[r]);
+                    if (w32) attn_st<WT>(P.dq + idx, o[r]);
+                    if (dq16) attn_st<WT>(dq16 + idx, m2f_bf16_bits(o[r]));
                 }
             }
         }
@@ -482,9 +493,9 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
                 const int jo = 16 * jt + 4 * lg + r;
                 if (jo < L && c < hd) {
                     const size_t ik = (tok0 + jo) * P.lddk + h * hd + c, iv = (tok0 + jo) * P.lddv + h * hd + c;
-                    if (w32) { P.dk[ik] = dk[r]; P.dv[iv] = dv[r]; }
-                    if (dk16) dk16[ik] = m2f_bf16_bits(dk[r]);
-                    if (dv16) dv16[iv] = m2f_bf16_bits(dv[r]);
+                    if (w32) { attn_st<WT>(P.dk + ik, dk[r]); attn_st<WT>(P.dv + iv, dv[r]); }
+                    if (dk16) attn_st<WT>(dk16 + ik, m2f_bf16_bits(dk[r]));
+                    if (dv16) attn_st<WT>(dv16 + iv, m2f_bf16_bits(dv[r]));
                 }
             }
         }
@@ -495,10 +506,10 @@ __global__ __launch_bounds__(NTHR) void m2f_attn_bwd_kernel(const AttnBatch ab) 
         for (int r = tail0 + wv; r < ab.T; r += NWAVE)
             for (int c = lane; c < hd; c += 64) {
                 const size_t iq = (size_t)r * P.lddq + h * hd + c, ik = (size_t)r * P.lddk + h * hd + c, iv = (size_t)r * P.lddv + h * hd + c;
-                if (w32) { P.dq[iq] = 0.f; P.dk[ik] = 0.f; P.dv[iv] = 0.f; }
-                if (dq16) dq16[iq] = 0;
-                if (dk16) dk16[ik] = 0;
-                if (dv16) dv16[iv] = 0;
+                if (w32) { attn_st<WT>(P.dq + iq, 0.f); attn_st<WT>(P.dk + ik, 0.f); attn_st<WT>(P.dv + iv, 0.f); }
+                if (dq16) attn_st<WT>(dq16 + iq, (uint16_t)0);
+                if (dk16) attn_st<WT>(dk16 + ik, (uint16_t)0);
+                if (dv16) attn_st<WT>(dv16 + iv, (uint16_t)0);
             }
     }
 }

@@ -74,6 +74,41 @@ __device__ __forceinline__ m2f_rsrc_t m2f_make_rsrc(const void* p, uint32_t byte
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
                                              __builtin_amdgcn_readfirstlane(p ? (int)bytes : 0), 0x00020000);
 }
+// ---- result stores through a buffer descriptor: plain (L2 write-back) or write-through ----------------
+// WT = true sets the descriptor store's cache-policy operand to 16: on gfx950 `buffer_store_dwordx4 ... offen sc1`, the
+// write-through form - the bytes leave the XCD's L2 while the kernel still runs instead of at the release that ends it.  WT =
+// false emits the plain form of the same instruction.  Never `nt`.  `off` is the byte offset into the descriptor's range; a store
+// outside the range is dropped.  Which kernel family writes through is a compile-time choice (M2F_WT_RING, M2F_WT_ROWS,
+// M2F_WT_ATTN below, 1 or 0): no runtime flag, no second instantiation.  No fence or wait goes with these stores: every wave
+// drains its own at s_endpgm and visibility across launches stays the kernel boundary's.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <bool WT>
+__device__ __forceinline__ void m2f_store_b128(m2f_rsrc_t rs, uint32_t off, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (int)off, 0, WT ? 16 : 0);
+}
+template <bool WT>
+__device__ __forceinline__ void m2f_store_b64(m2f_rsrc_t rs, uint32_t off, uint32_t lo, uint32_t hi) {
+    const u32x2 w = {lo, hi};
+    __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)off, 0, WT ? 16 : 0);
+}
+template <bool WT>
+__device__ __forceinline__ void m2f_store_b32(m2f_rsrc_t rs, uint32_t off, uint32_t w) {
+    __builtin_amdgcn_raw_buffer_store_b32(w, rs, (int)off, 0, WT ? 16 : 0);
+}
+// Which families write their results through: the ones that passed the A/B on the C3 bf16 step.  The
+// LayerNorm kernels do (-0.044 ms per step).  The ring epilogue's fp32 C stores (-0.018 ms) and the one-tile attention kernels'
+// (-0.016 ms) were faster in every alternated run but by less than three times the runs' own spread: measured, not kept, off.
+// `make wt_flip_ring / wt_flip_rows / wt_flip_attn` build the library with ONE family's switch turned over, for the next A/B.
+#ifndef M2F_WT_RING
+#define M2F_WT_RING 0
+#endif
+#ifndef M2F_WT_ROWS
+#define M2F_WT_ROWS 1
+#endif
+#ifndef M2F_WT_ATTN
+#define M2F_WT_ATTN 0
+#endif
+
 // the dropout state (seed_lo, seed_hi, step_lo, step_hi) as one 16-byte load in flight with the caller's other loads; zeros for a
 // null `rng` (a launch without a dropout site)
 __device__ __forceinline__ u32x4 m2f_rng_words(const uint32_t* rng) {

@@ -77,8 +77,12 @@ struct RingEpi {
     const float* bias; const float* res; const float* gate; float* C; uint16_t* C16;
     float gscale; uint32_t site, key; bool relu_out, accum, vec, gelu, no32;
     float acc_scale, c8_scale; uint8_t* c8;      // fp8 launches (EPI 4): de-quantisation factor; e4m3 result instead of fp32 C
+    m2f_rsrc_t rc;                               // write-through stores (M2F_WT_RING, EPI 0 / 3): C as a buffer range
 };
-template <int BM, int BN>
+// the epilogue forms whose 16-byte path stores fp32 C write-through (the step's launches; common.h, m2f_store_b128).  The bf16 shadow's
+// 8-byte pieces stay plain stores: a write-through store narrower than 16 bytes is a fabric write of its own
+template <int EPI> constexpr bool ring_wt_stores = M2F_WT_RING && (EPI == 0 || EPI == 3);
+template <int BM, int BN, int EPI = 0>
 __device__ __forceinline__ RingEpi ring_epilogue_args(const GemmBatch& gb, const GemmProblem& P, int m0, int n0) {
     RingEpi E;
     E.M = P.M; E.N = P.N; E.ldc = P.ldc; E.ldres = P.ldres; E.ldgate = P.ldgate;
@@ -94,6 +98,13 @@ __device__ __forceinline__ RingEpi ring_epilogue_args(const GemmBatch& gb, const
     E.vec = (m0 + BM <= E.M) && (n0 + BN <= E.N) && (E.c8 ? ((reinterpret_cast<uintptr_t>(E.c8) & 3) == 0) : al16(E.C)) && ((E.ldc & 3) == 0) && (!E.bias || al16(E.bias)) &&
             (!E.res || (al16(E.res) && (E.ldres & 3) == 0)) && (!E.gate || (al16(E.gate) && (E.ldgate & 3) == 0)) &&
             (!E.C16 || (reinterpret_cast<uintptr_t>(E.C16) & 7) == 0);                  // block-uniform
+    if constexpr (ring_wt_stores<EPI>) {
+        // C's reachable range, (M - 1) ldc + N elements, as one descriptor; the epilogue's 32-bit element offset `oc` times 4 must fit
+        // the descriptor's 32-bit byte offset - a launch beyond that takes the element path's plain stores
+        const unsigned long long cb = ((unsigned long long)(uint32_t)(E.M - 1) * (uint32_t)E.ldc + (uint32_t)E.N) * 4ull;
+        E.vec = E.vec && cb <= 0xFFFFFFFFull;
+        E.rc = m2f_make_rsrc(E.C, (uint32_t)cb);
+    }
     return E;
 }
 
@@ -202,12 +213,15 @@ __device__ __forceinline__ void ring_epilogue(const GemmBatch& gb, const RingEpi
                     if constexpr (EPI == 4) {                        // fp8 launches: e4m3(result * c8_scale) instead of fp32 C (block-uniform), no shadow
                         if (c8) *reinterpret_cast<uint32_t*>(c8 + (size_t)oc) = m2f_fp8x4_bits(v[0] * c8s, v[1] * c8s, v[2] * c8s, v[3] * c8s);
                         else if constexpr (!(F & 32)) *reinterpret_cast<f32x4*>(C + (size_t)oc) = v;      // (F & 32: bf16 shadow only, GF_NO_F32)
-                    } else if constexpr (!(F & 32)) *reinterpret_cast<f32x4*>(C + (size_t)oc) = v;      // F & 32: C has no fp32 reader (GF_NO_F32)
+                    } else if constexpr (!(F & 32)) {               // F & 32: C has no fp32 reader (GF_NO_F32)
+                        if constexpr (ring_wt_stores<EPI>) m2f_store_b128<true>(E.rc, oc * 4u, v);
+                        else *reinterpret_cast<f32x4*>(C + (size_t)oc) = v;
+                    }
                     if (C16) {
                         uint2 hh;
                         hh.x = (uint32_t)m2f_bf16_bits(v[0]) | ((uint32_t)m2f_bf16_bits(v[1]) << 16);
                         hh.y = (uint32_t)m2f_bf16_bits(v[2]) | ((uint32_t)m2f_bf16_bits(v[3]) << 16);
-                        *reinterpret_cast<uint2*>(C16 + (size_t)oc) = hh;
+                        *reinterpret_cast<uint2*>(C16 + (size_t)oc) = hh;      // (plain: written through, these 8-byte pieces cost the step 0.02-0.06 ms)
                     }
                 }
                 if (b == 0) { M2F_TS(6); }
@@ -695,7 +709,7 @@ __device__ __forceinline__ void ring_consumer(const GemmBatch& gb, char* smem, i
                 slot = slot + 1 == S ? 0 : slot + 1;
             }
         };
-        const RingEpi E = ring_epilogue_args<BM, BN>(gb, P, m0, n0);
+        const RingEpi E = ring_epilogue_args<BM, BN, EPI>(gb, P, m0, n0);
         M2F_TS(1);
         const unsigned long long tc1 = M2F_NOW();
         {

@@ -92,6 +92,37 @@ __device__ __forceinline__ void row_load_buf(RowRegs<NV>& r, const float* p, int
         r.v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (lane + 64 * j), 0, 0));
 }
 
+// 16-byte path, write-through result stores (M2F_WT_ROWS, common.h): the row's NV chunks - and the 8-byte pieces of its bf16 shadow -
+// through a descriptor of the row's bytes; chunks behind the row's end are dropped by the range check.  Same values, same bytes as
+// row_store / row_store_bf16 (d % 4 == 0 here; the shadow of a 16-byte aligned fp32 row is 8-byte aligned).
+template <int NV>
+__device__ __forceinline__ void row_store_wt(const RowRegs<NV>& r, float* p, int d, int lane) {
+    const m2f_rsrc_t rs = m2f_make_rsrc(p, 4u * (uint32_t)d);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) m2f_store_b128<true>(rs, 16u * (uint32_t)(lane + 64 * j), r.v[j]);
+}
+template <int NV>
+__device__ __forceinline__ void row_store_bf16_wt(const RowRegs<NV>& r, uint16_t* q, int d, int lane) {
+    const m2f_rsrc_t rs = m2f_make_rsrc(q, 2u * (uint32_t)d);
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        m2f_store_b64<true>(rs, 8u * (uint32_t)(lane + 64 * j), (uint32_t)m2f_bf16_bits(r.v[j][0]) | ((uint32_t)m2f_bf16_bits(r.v[j][1]) << 16),
+                            (uint32_t)m2f_bf16_bits(r.v[j][2]) | ((uint32_t)m2f_bf16_bits(r.v[j][3]) << 16));
+}
+// one body for both policies: the 16-byte path of a write-through build stores through the descriptor, everything else as before
+template <int NV, bool VEC>
+__device__ __forceinline__ void ln_store(const RowRegs<NV>& r, float* p, int d, int lane) {
+    if constexpr (VEC && M2F_WT_ROWS) row_store_wt(r, p, d, lane);
+    else row_store(r, p, d, VEC, lane);
+}
+template <int NV, bool VEC>
+__device__ __forceinline__ void ln_store_bf16(const RowRegs<NV>& r, uint16_t* q, int d, int lane) {
+    if constexpr (VEC && M2F_WT_ROWS) {
+        if ((reinterpret_cast<uintptr_t>(q) & 7) == 0) { row_store_bf16_wt(r, q, d, lane); return; }      // (wave-uniform)
+    }
+    row_store_bf16(r, q, d, lane);
+}
+
 // the problem a workgroup belongs to: bb[] is ascending (INT_MAX in unused slots), fetched as one 16-byte block, no branches
 __device__ __forceinline__ int ln_problem_of(const LnBatch& lb) {
     static_assert(M2F_LN_MAX_PROBLEMS == 4, "the search below reads bb[1..3]");
@@ -170,8 +201,8 @@ __device__ __forceinline__ void ln_fwd_body(const LnBatch& lb, const LnProblem& 
                 }
                 x.v[j][e] = y;
             }
-        row_store(x, P.out + (size_t)row * ld, d, VEC, lane);
-        if (out16) row_store_bf16(x, out16 + (size_t)row * ld, d, lane);
+        ln_store<NV, VEC>(x, P.out + (size_t)row * ld, d, lane);
+        if (out16) ln_store_bf16<NV, VEC>(x, out16 + (size_t)row * ld, d, lane);
         if (lb.out8 && pi == 0) {
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
@@ -181,7 +212,9 @@ __device__ __forceinline__ void ln_fwd_body(const LnBatch& lb, const LnProblem& 
                         m2f_fp8x4_bits(x.v[j][0] * lb.out8_scale, x.v[j][1] * lb.out8_scale, x.v[j][2] * lb.out8_scale, x.v[j][3] * lb.out8_scale);
             }
         }
-        if (lane == 0) { P.stats[2 * row] = mean; P.stats[2 * row + 1] = rstd; }
+        if constexpr (VEC && M2F_WT_ROWS) {                 // the row's statistics: one 8-byte piece (the array is 8-byte aligned per row)
+            if (lane == 0) m2f_store_b64<true>(m2f_make_rsrc(P.stats + 2 * (size_t)row, 8), 0, __builtin_bit_cast(uint32_t, mean), __builtin_bit_cast(uint32_t, rstd));
+        } else if (lane == 0) { P.stats[2 * row] = mean; P.stats[2 * row + 1] = rstd; }
     }
 }
 
@@ -276,10 +309,10 @@ __device__ __forceinline__ void ln_bwd_body(const LnBatch& lb, const LnProblem& 
                 msk.v[j][e] = dm;
                 dy.v[j][e] = P.extra ? dx + ex.v[j][e] : dx;
             }
-        row_store(dy, P.dx + (size_t)row * ld, d, VEC, lane);
-        if (dx16) row_store_bf16(dy, dx16 + (size_t)row * ld, d, lane);
-        if (dxm32) row_store(msk, P.dx_masked + (size_t)row * ld, d, VEC, lane);
-        if (dxm16) row_store_bf16(msk, dxm16 + (size_t)row * ld, d, lane);
+        ln_store<NV, VEC>(dy, P.dx + (size_t)row * ld, d, lane);
+        if (dx16) ln_store_bf16<NV, VEC>(dy, dx16 + (size_t)row * ld, d, lane);
+        if (dxm32) ln_store<NV, VEC>(msk, P.dx_masked + (size_t)row * ld, d, lane);
+        if (dxm16) ln_store_bf16<NV, VEC>(msk, dxm16 + (size_t)row * ld, d, lane);
     }
     // per-block partial dgamma / dbeta: waves -> LDS -> fixed-order sum (deterministic)
     float* mine = red + (size_t)wave * 2 * dpad;
@@ -287,12 +320,14 @@ __device__ __forceinline__ void ln_bwd_body(const LnBatch& lb, const LnProblem& 
     row_store(db, mine + dpad, dpad, true, lane);
     __syncthreads();
     float* out = P.partial + (size_t)blk * 2 * d;
+    const m2f_rsrc_t rpart = m2f_make_rsrc(out, 8u * (uint32_t)d);
     for (int c = threadIdx.x; c < 2 * d; c += 256) {
         const int which = c >= d, cc = which ? c - d : c;
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < LN_WAVES; ++w) s += red[(size_t)w * 2 * dpad + which * dpad + cc];
-        out[c] = s;
+        if constexpr (VEC && M2F_WT_ROWS) m2f_store_b32<true>(rpart, 4u * (uint32_t)c, __builtin_bit_cast(uint32_t, s));
+        else out[c] = s;
     }
 }
 
