@@ -71,8 +71,17 @@ enum {
     M2F_BUF_AUX = 26,           /* float [2]  train plans, input of the auxiliary label head (m2f_plan_aux_head): (lambda, eps_a), read on the device at every step */
     M2F_BUF_AUX_LABELS = 27,    /* int64 [T]  train plans, input of the auxiliary label head: the second label of every token row, in the plan's token order (as M2F_BUF_LABELS); a value outside [0, num_aux) = ignored */
     M2F_BUF_AUX_LOGITS = 28,    /* float [T, 16]  train plans, the auxiliary head's logits of the last step (columns 0 .. num_aux-1 of every row); read-only for the caller */
-    M2F_BUF_END = 29
+    M2F_BUF_END = 29,           /* the ids above; kept at its value for callers built against it - M2F_BUF_LIMIT bounds m2f_plan_buffer's ids */
+    /* the adversarial state of a plan (m2f_plan_adversarial): pointers into the CALLER's state buffer, NULL while it is off */
+    M2F_BUF_ADV = 29,           /* float [2]  (epsilon, step_size) of the ascent, read on the device by every m2f_plan_adv_ascend / m2f_plan_adv_begin */
+    M2F_BUF_ADV_SKIP = 30,      /* uint8 [T]  input: 1 = the token row is padding or a filler row - the ascent neither reads it for a norm nor writes it */
+    M2F_BUF_ADV_DELTA_TEXT = 31,    /* float [T, pad8(d_text)]   the perturbation of the text rows (token rows as M2F_BUF_TEXT); NULL: not asked for */
+    M2F_BUF_ADV_DELTA_AUDIO = 32,   /* float [T, pad8(d_audio)]  the perturbation of the audio rows */
+    M2F_BUF_LIMIT = 33
 };
+/* the hash sites of the uniform start of the perturbation (m2f_adv_init): far above every dropout site a plan hands out (1, 2, ...) */
+#define M2F_ADV_SITE_TEXT 0xAD510001u
+#define M2F_ADV_SITE_AUDIO 0xAD510002u
 
 const char* m2f_last_error(void);
 int m2f_device_check(void);            /* 0 iff the current HIP device is gfx950 */
@@ -396,6 +405,30 @@ int m2f_sam_perturb(const m2f_config* cfg, float* params, const float* grads, co
                     m2f_stream_t stream);
 int m2f_sam_restore(const m2f_config* cfg, float* params, const float* saved, m2f_stream_t stream);
 
+/* Adversarial training on the input embeddings (FGM, Miyato et al. 2017; PGD, Madry et al. 2018; FreeLB, Zhu et al. 2020): the ascent
+ * step on a perturbation delta of T token rows of width d (row stride ld: a multiple of 4 floats, >= d rounded up to 4; every buffer
+ * 16-byte aligned).  No counterpart in the reference.  With (epsilon, step) = hyper_dev[0 .. 1] read ON THE DEVICE and ||.|| the L2 norm
+ * of the row (norm_kind 0, "utterance") or over all rows that are not skipped (1, "batch"):
+ *   u      = g / ||g||
+ *   cand   = delta + step * u                      (||g|| == 0 or not finite: cand = delta)
+ *   delta' = cand * min(1, epsilon / ||cand||)     (||cand|| == 0: delta' = cand)
+ *   x      = x_clean + delta'                      (one fp32 add)
+ * delta is updated in place.  key_pad (uint8 [T]): a row with a non-zero flag is neither read for a norm nor written - its x and delta
+ * keep their bits; columns d .. ld - 1 are never written and enter no sum.  g NULL: a zero gradient (the projection alone).  The sums of
+ * squares are float64 in one fixed order, the two quotients are rounded once to fp32, the elements are fp32 (cand = fma(step / ||g||, g,
+ * delta)): ||delta'|| <= epsilon * (1 + 2^-22).  norm_kind 0: one launch, one wave per row, the row in registers for d <= 1,024 (a looping
+ * form above).  norm_kind 1: two launches - float64 partials of sum g^2, sum delta^2 and sum delta . g per slice of 16 rows into
+ * `scratch` (m2f_adv_scratch_bytes bytes, 16-byte aligned), then every workgroup adds them in index order and gets ||cand||^2 = sum delta^2 +
+ * 2 (step / ||g||) sum delta . g + step^2 by algebra.  No atomics: same bits on every run.
+ * m2f_adv_init: delta[t, c] = fp32(init_mag / sqrt(d)) * (2 * (h >> 8) * 2^-24 - 1) over the rows that are not skipped, h the dropout
+ * hash (csrc/common.h: the hash behind the keep decision) of element t * d + c under `site` and the state rng_state (4 x uint32 on the
+ * device); the other rows keep their bits. */
+int64_t m2f_adv_scratch_bytes(int T);
+int m2f_adv_ascend(int T, int d, int ld, const float* x_clean, const float* g, float* delta, float* x, const uint8_t* key_pad,
+                   const float* hyper_dev, int norm_kind, void* scratch, m2f_stream_t stream);
+int m2f_adv_init(int T, int d, int ld, float* delta, const uint8_t* key_pad, float init_mag, const uint32_t* rng_state, uint32_t site,
+                 m2f_stream_t stream);
+
 /* Per-tensor statistics and histograms of one flat buffer in the model's parameter layout (the model watch: what
  * wandb.watch(model, log="all") of the reference's loop, src/train.py:132-138, logs per parameter and per gradient tensor, computed
  * where the values live).  `a`: fp32, or (a_is_bf16 != 0) bf16 with the same indexing, 16-byte aligned; `b` (fp32, or NULL): the
@@ -711,6 +744,25 @@ int m2f_plan_grad_bf16(m2f_plan* plan, uint16_t* grads_bf16);
  * m2f_plan_accumulate_grads(plan, 0) restores the overwrite form.  Fails for a plan without a gradient buffer, with fused Adam on or
  * bf16 gradients armed; while it is on, m2f_step_part, m2f_plan_fused_adam(plan, 1) and m2f_plan_grad_bf16(plan, non-NULL) fail. */
 int m2f_plan_accumulate_grads(m2f_plan* plan, int on);
+
+/* The adversarial state of a train plan: per modality of modality_mask (1 text, 2 audio; enabled modalities only) a perturbation
+ * delta and a copy x_clean of the staged input, [T, pad8(d)] floats each, beside (epsilon, step_size), the rows' skip flags and the
+ * batch norm's scratch - all inside `state`, the CALLER's device buffer of m2f_plan_adversarial_bytes bytes (256-byte aligned, kept
+ * alive while it is on; as m2f_plan_stream_speakers takes its buffer): a plan that never asks has the workspace it always had.  The ids
+ * M2F_BUF_ADV .. M2F_BUF_ADV_DELTA_AUDIO then point into it.  modality_mask 0 (or state NULL): off.  Nothing here changes a launch list
+ * or a captured graph: the ascent writes the fp32 staging buffers M2F_BUF_TEXT / M2F_BUF_AUDIO, which every forward reads (in bf16 mode
+ * through the input casts at the head of its launch list).
+ * m2f_plan_adv_begin: x_clean <- the staged inputs, delta <- 0 (device-to-device copies and fills on `stream`); init_mag > 0: delta <-
+ * the uniform start of m2f_adv_init under M2F_ADV_SITE_TEXT / M2F_ADV_SITE_AUDIO and the plan's dropout state as it is now (NULL state:
+ * refused), projected onto the epsilon ball of norm_kind, and the staged inputs <- x_clean + delta.  The caller has written
+ * M2F_BUF_ADV_SKIP and M2F_BUF_ADV on the stream before.
+ * m2f_plan_adv_ascend: m2f_adv_ascend per modality on the plan's own M2F_BUF_DTEXT / M2F_BUF_DAUDIO (the plan computes them:
+ * m2f_plan_backward_outputs with the modality's bit), delta and x_clean, writing the staged inputs.  One launch per norm_kind-0 call and
+ * modality, two per norm_kind-1 call; waits for nothing. */
+int64_t m2f_plan_adversarial_bytes(m2f_plan* plan, int modality_mask);
+int m2f_plan_adversarial(m2f_plan* plan, int modality_mask, void* state, int64_t state_bytes);
+int m2f_plan_adv_begin(m2f_plan* plan, float init_mag, int norm_kind, m2f_stream_t stream);
+int m2f_plan_adv_ascend(m2f_plan* plan, int norm_kind, m2f_stream_t stream);
 
 /* Distillation criterion: while m2f_plan_distill(plan, 1) is on, the criterion launch of m2f_loss / m2f_step / m2f_step_part /
  * m2f_step_timed blends the hard-label cross entropy with the KL divergence from a teacher's logits (M2F_BUF_TEACHER), per token row

@@ -58,7 +58,11 @@ supcon = len(sys.argv) > 2 and sys.argv[1] == "--supcon"
 # --aux <remarks>: the auxiliary label head's kernels (aux_head.hip) - a row's 16-byte pieces, the sixteen logits, the row's terms and the
 # sixteen accumulators of a parameter-gradient lane stay in registers through unrolled loops with static indices: zero scratch, no spills
 aux = len(sys.argv) > 2 and sys.argv[1] == "--aux"
-path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux or sam or criterion) else sys.argv[1]
+# --adv <remarks>: the adversarial ascent kernels (adversarial.hip): the register forms for 1, 2 and 4 pieces per lane and the looping
+# form, each per row and per batch, the batch norm's partials and the uniform start - a row's pieces of g, delta and x_clean are all
+# loaded before the arithmetic and stay in registers: zero scratch, no spills; prints the register numbers of each
+adv = len(sys.argv) > 2 and sys.argv[1] == "--adv"
+path = sys.argv[2] if (attn or ring or dlong or stream or stream_chunk or stream_cache or attn_weights or w2v or mel or gradnorm or tstats or metrics or adam or crf or supcon or aux or adv or sam or criterion) else sys.argv[1]
 rows, cur = [], None
 for line in open(path, errors="replace"):
     m = re.search(r"Function Name: (\S+)", line)
@@ -106,6 +110,15 @@ if sam:
     kernels = [r for r in rows if "m2f_sam_" in r["name"]]
     if len(kernels) != 6:
         sys.exit(f"check_spills: expected the six m2f_sam_ kernels in {path}, found {len(kernels)} - did the remark format change?")
+    bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
+    for r in kernels:
+        print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "
+              f"{r.get('vgpr_spill', 0)} VGPRs spilled", file=sys.stderr if r in bad else sys.stdout)
+    sys.exit(1 if bad else 0)
+if adv:
+    kernels = [r for r in rows if "m2f_adv_" in r["name"]]
+    if len(kernels) != 10:
+        sys.exit(f"check_spills: expected the ten m2f_adv_ kernels in {path}, found {len(kernels)} - did the remark format change?")
     bad = [r for r in kernels if r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0]
     for r in kernels:
         print(f"check_spills: {r['name']}: {r.get('VGPRs')} VGPRs, {r.get('TotalSGPRs')} SGPRs, {r.get('scratch', 0)} bytes of scratch, "

@@ -658,6 +658,45 @@ int m2f_supcon(int N, int D, int C, const float* features, int ld, const int64_t
     return 0;
 }
 
+int64_t m2f_adv_scratch_bytes(int T) {
+    if (T < 1) { fail("m2f_adv_scratch_bytes: T >= 1 required"); return -1; }
+    return (int64_t)m2f_adv_slices(T) * 3 * (int64_t)sizeof(double);
+}
+
+// what both stand-alone entries of the adversarial ascent ask of their rows; nullptr: fine
+static const char* adv_shape_error(int T, int d, int ld) {
+    if (T < 1 || d < 1) return "T >= 1 and d >= 1 required";
+    if ((ld & 3) || ld < ((d + 3) & ~3)) return "rows must be 16-byte aligned: ld a multiple of 4, >= d rounded up to 4";
+    if ((int64_t)T * d >= ((int64_t)1 << 32)) return "T * d must stay below 2^32";
+    return nullptr;
+}
+
+int m2f_adv_ascend(int T, int d, int ld, const float* x_clean, const float* g, float* delta, float* x, const uint8_t* key_pad,
+                   const float* hyper_dev, int norm_kind, void* scratch, m2f_stream_t stream) {
+    if (const char* e = adv_shape_error(T, d, ld)) return fail(std::string("m2f_adv_ascend: ") + e);
+    if (!x_clean || !delta || !x || !key_pad || !hyper_dev) return fail("m2f_adv_ascend: NULL x_clean / delta / x / key_pad / hyper_dev");
+    if (norm_kind != 0 && norm_kind != 1) return fail("m2f_adv_ascend: norm_kind is 0 (utterance) or 1 (batch)");
+    if (norm_kind == 1 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15))) return fail("m2f_adv_ascend: the batch norm needs 16-byte aligned scratch of m2f_adv_scratch_bytes bytes");
+    if ((reinterpret_cast<uintptr_t>(x_clean) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(delta) | reinterpret_cast<uintptr_t>(x)) & 15)
+        return fail("m2f_adv_ascend: x_clean, g, delta and x must be 16-byte aligned");
+    if (x == x_clean || delta == x || delta == x_clean || (g && (g == delta || g == x))) return fail("m2f_adv_ascend: x_clean, g, delta and x must be four buffers");
+    AdvArgs a{};
+    a.T = T; a.d = d; a.ld = ld; a.x_clean = x_clean; a.g = g; a.delta = delta; a.x = x; a.skip = key_pad; a.hyper = hyper_dev;
+    a.partial = static_cast<double*>(scratch);
+    M2F_HIP(m2f_launch_adv_ascend(a, norm_kind, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int m2f_adv_init(int T, int d, int ld, float* delta, const uint8_t* key_pad, float init_mag, const uint32_t* rng_state, uint32_t site,
+                 m2f_stream_t stream) {
+    if (const char* e = adv_shape_error(T, d, ld)) return fail(std::string("m2f_adv_init: ") + e);
+    if (!delta || !key_pad || !rng_state) return fail("m2f_adv_init: NULL delta / key_pad / rng_state");
+    if (!(init_mag >= 0.f) || !std::isfinite(init_mag)) return fail("m2f_adv_init: init_mag must be a finite number >= 0");
+    const float scale = (float)((double)init_mag / std::sqrt((double)d));
+    M2F_HIP(m2f_launch_adv_init(delta, T, d, ld, key_pad, scale, rng_state, site, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int64_t m2f_aux_head_scratch_floats(int N, int D, int A) { return (int64_t)m2f_aux_head_ws_floats(N, D, A); }
 
 // what every stand-alone entry of the auxiliary head asks of its shapes and feature rows; nullptr: fine

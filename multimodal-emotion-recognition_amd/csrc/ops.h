@@ -821,6 +821,20 @@ hipError_t m2f_launch_sam_perturb_flat(float* p, const void* g, int g_is_bf16, f
                                        const float* record, hipStream_t stream);
 hipError_t m2f_launch_sam_restore(float* p, const float* saved, const ParamSlice* slices, int n_slices, hipStream_t stream);
 
+// Adversarial ascent on one modality's token rows (adversarial.hip has the definition).  Rows of width d, row stride ld (a multiple of 4,
+// >= d rounded up to 4; 16-byte aligned buffers); skip[t] != 0: row t is neither read for a norm nor written; hyper = (epsilon, step) on
+// the device; g may be null (zero gradient: the projection alone).  batch_norm: the L2 norm over all rows instead of per row - two
+// launches, partial = 3 * m2f_adv_slices(T) doubles of scratch (the launcher fills n_slices).
+struct AdvArgs {
+    const float* x_clean; const float* g; float* delta; float* x; const uint8_t* skip; const float* hyper; double* partial;
+    int T, d, ld, n_slices;
+};
+int m2f_adv_slices(int T);
+hipError_t m2f_launch_adv_ascend(const AdvArgs& a, int batch_norm, hipStream_t stream);
+// delta[t, c] = scale * (2 * (h >> 8) * 2^-24 - 1) over the rows that are not skipped, h the dropout hash of element t * d + c under `site`
+hipError_t m2f_launch_adv_init(float* delta, int T, int d, int ld, const uint8_t* skip, float scale, const uint32_t* rng, uint32_t site,
+                               hipStream_t stream);
+
 // Per-tensor statistics and histograms of a flat buffer (tensor_stats.hip).  slices: every tensor's ParamSlices, tag = the index of the slice's
 // tensor; tensor_begin[t] = first slice of tensor t, [n_tensors] = n_slices.  Pass 1 writes partial[s] (a slice's finite count is
 // n - nan - inf), the finalize launch the record header (M2F_TSTATS_HEADER doubles: den, n_tensors, bins, 0) and one row per tensor

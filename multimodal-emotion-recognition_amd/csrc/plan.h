@@ -271,7 +271,7 @@ struct m2f_plan {
     uint32_t* rng = nullptr; bool use_dropout = false;
     uint32_t drop_thresh = 0; float drop_scale = 1.f;
     m2f::ParamMap pm;
-    void* bufs[M2F_BUF_END] = {nullptr};
+    void* bufs[M2F_BUF_LIMIT] = {nullptr};
     float* loss_terms = nullptr;
     int* eval_partial = nullptr;     // m2f_eval_step: the rows launch's integer tiles (its row terms go to loss_terms, as the criterion's do)
     bool eval_warmed = false;        // ... and one eager m2f_eval_step before its first capture (`warmed` belongs to the train step)
@@ -289,6 +289,11 @@ struct m2f_plan {
     uint16_t* g16_buf = nullptr;
     m2f::AccForm acc;
     m2f::Criterion crit;             // which criterion do_loss launches, and what it needs
+    // m2f_plan_adversarial: the modalities that hold a perturbation, and per modality (0 text, 1 audio) delta and x_clean inside the caller's
+    // state buffer; hyper / skip / scratch are bufs[M2F_BUF_ADV], bufs[M2F_BUF_ADV_SKIP] and adv_scratch
+    int adv_mask = 0;
+    float* adv_delta[2] = {nullptr, nullptr}; float* adv_clean[2] = {nullptr, nullptr};
+    double* adv_scratch = nullptr;
     float* s_phi = nullptr;              // stream and chunk plans (m2f_plan_stream_crf): the CALLER's filter state [S, C] over crf_params, or null
     // graph cache: m2f_step, m2f_step_part(0), m2f_step_part(1), ...
     m2f::GraphSlot graphs[m2f::SLOT_COUNT];

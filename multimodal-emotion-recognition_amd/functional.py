@@ -862,6 +862,87 @@ def supcon(features: torch.Tensor, labels: torch.Tensor, class_w: Optional[torch
     return rows, dfeat
 
 
+def _adv_rows(t: torch.Tensor, d: int) -> Tuple[torch.Tensor, bool]:
+    """[T, d] fp32 rows as the adversarial kernels read them - 16-byte aligned rows of a stride that is a multiple of 4 -: the tensor
+    itself when it is such a view, else a copy in such a buffer (and True: results travel back)."""
+    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= (d + 3) // 4 * 4 and t.data_ptr() % 16 == 0:
+        return t, False
+    buf = torch.zeros(t.shape[0], (d + 7) // 8 * 8, dtype=torch.float32, device=t.device)
+    buf[:, :d] = t
+    return buf[:, :d], True
+
+
+def adversarial_ascend(x_clean: torch.Tensor, g: Optional[torch.Tensor], delta: torch.Tensor, x: Optional[torch.Tensor] = None,
+                       key_pad: Optional[torch.Tensor] = None, epsilon: float = 1.0, step_size: Optional[float] = None,
+                       norm: str = "utterance"):
+    """One ascent step of embedding-space adversarial training on its own (m2f_adv_ascend; csrc/adversarial.hip holds the definition):
+    ``u = g / ||g||``, ``cand = delta + step_size * u`` (a zero or non-finite norm: ``cand = delta``), ``delta <- cand * min(1, epsilon
+    / ||cand||)``, ``x <- x_clean + delta``; the norm is each row's L2 norm ("utterance") or the L2 norm over all rows that are not
+    padding ("batch").  x_clean, g, delta, x: fp32 ``[..., d]`` of one shape on one device, the leading dimensions are the rows; g None
+    = a zero gradient (the projection alone).  key_pad (bool / uint8, the leading shape; True = padding): those rows are neither read for
+    a norm nor written.  delta is updated IN PLACE and x written (allocated when None: padding rows then hold x_clean); returns
+    ``(delta, x)``.  Rows that are 16-byte aligned views with a stride that is a multiple of 4 (``buf[:, :d]`` of a padded buffer) are
+    used in place - the columns behind d are never written -, anything else through a copy.  step_size None = epsilon.  Sums of squares
+    in float64 in a fixed order, no atomics: the same bits at every call."""
+    eps, step, _ = runtime.check_adv_hyper(epsilon, step_size, 0.0, "adversarial_ascend")
+    kind = runtime.adv_norm_kind(norm, "adversarial_ascend")
+    runtime.require_gpu()
+    dev, shape = x_clean.device, x_clean.shape
+    if x is None:
+        x = x_clean.clone()
+    for name, t in (("x_clean", x_clean), ("g", g), ("delta", delta), ("x", x)):
+        if t is None and name == "g":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != shape or t.device != dev or t.dim() < 2:
+            raise ValueError(f"adversarial_ascend: {name} must be fp32 {tuple(shape)} on {dev} like x_clean (at least 2-D)")
+    d = shape[-1]
+    T = x_clean.numel() // d
+    if T < 1 or d < 1:
+        raise ValueError(f"adversarial_ascend: at least one row and one column required, got {tuple(shape)}")
+    if key_pad is None:
+        skip = torch.zeros(T, dtype=torch.uint8, device=dev)
+    else:
+        if key_pad.shape != shape[:-1] or key_pad.device != dev:
+            raise ValueError(f"adversarial_ascend: key_pad must be {tuple(shape[:-1])} on {dev}, got {tuple(key_pad.shape)} on {key_pad.device}")
+        skip = key_pad.reshape(T).to(torch.uint8).contiguous()
+
+    def rows(t):
+        t2 = t if t.dim() == 2 else t.reshape(T, d)          # (a view whenever the leading dimensions are contiguous; else a copy)
+        r, copied = _adv_rows(t2, d)
+        return r, copied or (t2.data_ptr() != t.data_ptr())
+
+    xc, _ = rows(x_clean)
+    gr = None if g is None else rows(g)[0]
+    dl, dl_back = rows(delta)
+    xo, xo_back = rows(x)
+    scratch = torch.empty(int(lib().m2f_adv_scratch_bytes(T)) // 8, dtype=torch.float64, device=dev) if kind else None
+    hyper = torch.tensor([eps, step], dtype=torch.float32).to(dev, non_blocking=True)
+    check(lib().m2f_adv_ascend(T, d, xc.stride(0), ptr(xc), ptr(gr), ptr(dl), ptr(xo), ptr(skip), ptr(hyper), kind, ptr(scratch),
+                               stream_ptr()), "m2f_adv_ascend")
+    if dl_back:
+        delta.copy_(dl.reshape(shape))
+    if xo_back:
+        x.copy_(xo.reshape(shape))
+    return delta, x
+
+
+def adversarial_init(delta: torch.Tensor, init_mag: float, rng: torch.Tensor, site: int, key_pad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The uniform start of a perturbation on its own (m2f_adv_init): ``delta[t, c] <- fp32(init_mag / sqrt(d)) * (2 * (h >> 8) * 2^-24 -
+    1)`` IN PLACE over the rows that are not padding, h the dropout hash of element ``t * d + c`` under `site` and the state `rng` (int32
+    [4] on the device).  delta: fp32 [T, d], rows as `adversarial_ascend` takes them (else through a copy)."""
+    _, _, mag = runtime.check_adv_hyper(0.0, None, init_mag, "adversarial_init")
+    runtime.require_gpu()
+    if delta.dim() != 2 or delta.dtype != torch.float32:
+        raise ValueError(f"adversarial_init: delta must be fp32 [T, d], got {tuple(delta.shape)} {delta.dtype}")
+    T, d = delta.shape
+    skip = (torch.zeros(T, dtype=torch.uint8, device=delta.device) if key_pad is None else key_pad.reshape(T).to(torch.uint8).contiguous())
+    dl, back = _adv_rows(delta, d)
+    check(lib().m2f_adv_init(T, d, dl.stride(0), ptr(dl), ptr(skip), mag, ptr(rng), int(site) & 0xFFFFFFFF, stream_ptr()), "m2f_adv_init")
+    if back:
+        delta.copy_(dl)
+    return delta
+
+
 def _aux_rows(features: torch.Tensor, who: str) -> torch.Tensor:
     """fp32 [N, D] feature rows as the auxiliary head's kernels read them: 16-byte aligned rows of a stride that is a multiple of 4
     (read in place when they are; else copied once into such a buffer)."""

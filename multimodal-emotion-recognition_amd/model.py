@@ -233,6 +233,8 @@ class _Engine:
         # their forward as before.  Writes that bypass the counters (p.data...) need `invalidate_shadows()`; `flat_parameters()` calls it.  M2F_SHARED_SHADOWS=0: off.
         self.wshadow: Optional[torch.Tensor] = None
         self.last = None                                      # (plan, version, dst, valid, (b, l)) of the most recent forward (note_forward)
+        self.last_inputs = None                               # ... of the most recent train_step(input_grads=) + its input mask (last_input_grads)
+        self.last_adv = None                                  # ... of the most recent adversarial_step + its modality mask (last_perturbation)
         self.grad_bf16_buf: Optional[torch.Tensor] = None     # bf16 [n_params]: train plans leave their gradients here (set_grad_bf16)
         self.accumulate = False                               # torch's .grad rule at every backward (M2FNet.set_grad_accumulation)
         self._fresh_token = None
@@ -294,7 +296,7 @@ class _Engine:
         a multiple of 64, plus one row per filler dialogue and one spare) instead of B x L slots; batches that are at least
         85 % full keep the padded plan.  Batches with L > 64 always get a packed plan (padded plans hold L <= 64).
         outputs: what a backward computes - (input_mask, parameter gradients) of m2f_plan_backward_outputs; part of the key, so a
-        plan of one setting never flips to another (train_step always uses the default (0, True)).
+        plan of one setting never flips to another (train_step uses the default (0, True) unless it is asked for input_grads=).
         The model's context band (M2FNet.context) is part of the key in the same way: every band has its own plans; so is its
         position bias (M2FNet.position_bias)."""
         b_in, l_in = B, L
@@ -687,7 +689,8 @@ class M2FNet(nn.Module):
                    use_graph: bool = True, optimizer=None, teacher_logits: Optional[torch.Tensor] = None,
                    distill: Optional[Tuple[float, float]] = None, speakers: Optional[torch.Tensor] = None,
                    focal_gamma: Optional[float] = None, crf=None, rdrop: Optional[float] = None,
-                   supcon: Optional[Tuple[float, float]] = None, aux=None, aux_label_smoothing: float = 0.0) -> torch.Tensor:
+                   supcon: Optional[Tuple[float, float]] = None, aux=None, aux_label_smoothing: float = 0.0,
+                   input_grads=None) -> torch.Tensor:
         """Body of reference src/train.py:227-230 in one call: returns the (device) loss scalar and leaves
         the gradients in ``p.grad`` (views of the flat buffer).
         teacher_logits (fp32 [B, L, cls_out] on the model's device) with distill=(alpha, temperature): the step's criterion is the
@@ -746,7 +749,24 @@ class M2FNet(nn.Module):
         weight 0 gives the plain step's loss and gradients.  None (default): today's launches, bit for bit; auxiliary and plain calls
         mix freely on one model.  Combines with focal_gamma (the focal factor scales the emotion term only); refused (ValueError naming
         the pair, before any launch) beside teacher_logits / distill, crf, rdrop or supcon, and - a trainable head - under gradient
-        accumulation."""
+        accumulation.
+        input_grads ("text", "audio" or both, enabled modalities only): the step ALSO leaves d loss / d text and / or d loss / d audio
+        - one more dgrad launch inside the same replayed graph, on a plan of its own (key ``outputs=(mask, True)``; the parameter
+        gradients keep their bits) - and ``last_input_grads()`` returns them as fresh ``[B, L, d]`` tensors.  With ``normalise=False``
+        they are the gradients of the un-normalised numerator, as the parameter gradients are.  None (default): today's plan key,
+        launches and bits.  Refused by name beside optimizer= (the in-launch optimizer), bf16 gradients (``set_grad_bf16``) and rdrop."""
+        in_mask = 0
+        if input_grads is not None:
+            in_mask = runtime.input_modalities(input_grads, self.text_enabled, self.audio_enabled, "M2FNet.train_step")
+            if optimizer is not None:
+                raise RuntimeError("M2FNet.train_step: input_grads= does not combine with optimizer= (the optimizer step inside the train "
+                                   "step: its fused setup belongs to the plan without input gradients); call optimizer.step() yourself")
+            if rdrop is not None:
+                raise ValueError("M2FNet.train_step: input_grads= does not combine with rdrop (the step runs every dialogue twice: "
+                                 "there is no one gradient per input row)")
+            if self._engine is not None and self._engine.grad_bf16_buf is not None:
+                raise RuntimeError("M2FNet.train_step: input_grads= does not combine with bf16 gradients (set_grad_bf16(True)): the "
+                                   "plan that also computes input gradients keeps fp32 gradients; call set_grad_bf16(False) first")
         spec = self._resolve("M2FNet.train_step", mask, label_smoothing, class_weights, teacher_logits=teacher_logits, distill=distill,
                              focal_gamma=focal_gamma, crf=crf, rdrop=rdrop, supcon=supcon, aux=aux, aux_label_smoothing=aux_label_smoothing)
         ids = _check_speakers("M2FNet.train_step", self._speaker_heads, speakers, mask.shape)
@@ -762,7 +782,11 @@ class M2FNet(nn.Module):
             text, audio, mask, emotion, ids = (None if x is None else torch.cat([x, x], 0) for x in (text, audio, mask, emotion, ids))
         B, L = mask.shape
         valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
-        plan = eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid)
+        if in_mask and eng.grad_bf16_buf is not None:
+            raise RuntimeError("M2FNet.train_step: input_grads= does not combine with bf16 gradients (set_grad_bf16(True)): the plan "
+                               "that also computes input gradients keeps fp32 gradients; call set_grad_bf16(False) first")
+        plan = (eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid, (in_mask, True)) if in_mask
+                else eng.plan(B, L, True, self.training and self.m2f_config.dropout > 0.0, valid))
         self._last_criterion = spec
 
         def body():
@@ -797,7 +821,168 @@ class M2FNet(nn.Module):
             if block is not None:
                 block.publish_grad()
         eng.note_forward(plan)
+        if in_mask:
+            eng.last_inputs = eng.last + (in_mask,)
         return loss[0].clone()          # (the buffer is overwritten by the next step)
+
+    def _last_rows(self, who: str, what: str, record):
+        """(plan, dst, valid, shape, mask) of `record` (an engine's last_inputs / last_adv), or the RuntimeError that says why not."""
+        if record is None:
+            raise RuntimeError(f"M2FNet.{who}: no {what} has run on this model (or it was moved since)")
+        plan, version, dst, valid, shape, mask = record
+        if not plan.handle:
+            raise RuntimeError(f"M2FNet.{who}: the plan of the last {what} was destroyed (evicted from the plan cache)")
+        if plan.version != version:
+            raise RuntimeError(f"M2FNet.{who}: the buffers of the last {what} were overwritten by a later step of the same plan")
+        return plan, dst, valid, shape, mask
+
+    def last_input_grads(self) -> Dict[str, torch.Tensor]:
+        """``{"text": d loss / d text, "audio": d loss / d audio}`` (the modalities asked for) of the most recent
+        ``train_step(input_grads=)`` of this model: fresh ``[B, L, d]`` tensors in the caller's dialogue order, whatever bucket, packed or
+        long-dialogue plan ran; pad slots are exact zeros.  Raises RuntimeError when no such step has run, or the plan that ran it was
+        destroyed or has run again since."""
+        eng = self._engine
+        plan, dst, valid, shape, mask = self._last_rows("last_input_grads", "train_step(input_grads=)", eng.last_inputs if eng else None)
+        out = {}
+        for name, bit in (("text", runtime.IN_TEXT), ("audio", runtime.IN_AUDIO)):
+            if mask & bit:
+                g = plan.input_grad(bit, dst, valid, shape)
+                if not plan.packed:                          # (a padded plan computes numbers at pad slots, as the reference does)
+                    g = g.masked_fill(plan.keypad_in.view(plan.B, plan.L)[: shape[0], : shape[1]].bool()[..., None], 0.0)
+                out[name] = g
+        return out
+
+    def last_perturbation(self) -> Dict[str, torch.Tensor]:
+        """``{modality: delta}`` of the most recent ``adversarial_step`` of this model: the final perturbation of every perturbed
+        modality as a fresh ``[B, L, d]`` tensor in the caller's dialogue order; pad slots are exact zeros.  Raises as
+        ``last_input_grads``."""
+        eng = self._engine
+        plan, dst, valid, shape, mask = self._last_rows("last_perturbation", "adversarial_step", eng.last_adv if eng else None)
+        return {name: plan.perturbation(bit, dst, valid, shape)
+                for name, bit in (("text", runtime.IN_TEXT), ("audio", runtime.IN_AUDIO)) if mask & bit}
+
+    def adversarial_step(self, text, audio, mask, emotion, optimizer=None, *, epsilon, steps: int = 2, step_size: Optional[float] = None,
+                         norm: str = "utterance", modalities=None, init_mag: float = 0.0, same_dropout: bool = True,
+                         **train_step_arguments) -> torch.Tensor:
+        """Embedding-space adversarial training in one call (FGM, Miyato et al. 2017; PGD, Madry et al. 2018; FreeLB, Zhu et al. 2020):
+        ``steps`` = K >= 1 passes of the train step on ONE plan, each on ``x_clean + delta`` of the perturbed modalities, nothing
+        waiting for the host.  The batch is staged once; pass 0 overwrites the gradients; before every later pass one row-wise launch
+        per modality (csrc/adversarial.hip) takes the input gradients the pass before left - ``delta <- project(delta + step_size * g /
+        ||g||)`` onto the ``epsilon`` ball, ``||.||`` per utterance row (``norm="utterance"``) or over all valid rows of the modality
+        (``"batch"``), rows that are padding untouched - and the pass ADDS its gradients (the accumulate form): the call leaves exactly
+        what this loop over the public pieces leaves::
+
+            model.set_grad_accumulation(True); optimizer.zero_grad()
+            for k in range(K):                      # delta_0 = 0; delta_k from last_input_grads() through functional.adversarial_ascend
+                model.train_step(text + delta_t, audio + delta_a, mask, emotion, normalise=False, input_grads=...)
+
+        ``.grad`` is the fp32 sum of the K un-normalised gradients and ``loss_terms()[1:]`` the summed den / num.  Returns the loss of
+        pass 0 (the clean loss when ``init_mag = 0``).  ``steps=2, step_size=epsilon`` (the default) is FGM with the clean loss kept,
+        ``steps=K`` PGD / FreeLB (K passes, averaged gradient).  step_size None = epsilon.
+        optimizer (a ``FusedAdam`` of this model without sam_rho): the call also sets ``optimizer.grad_scale`` to the group's den, runs
+        ``optimizer.step()`` - clipping, EMA, the watch, parameter groups and AdamW see the summed gradient, as after any accumulation
+        group - and puts the previous ``grad_scale`` back.
+        modalities: a subset of ("text", "audio") to perturb (None: every enabled one).  init_mag > 0: delta starts uniform in
+        ``+- init_mag / sqrt(d)`` per element (the device's hash under a site of its own; tests/golden/adversarial_ref.py is the host
+        replica), projected, instead of at zero.  same_dropout (FreeLB's rule): every pass draws the masks of pass 0; False: fresh masks
+        per pass.  Either way the dropout state afterwards is the one a single step leaves.
+        ``train_step_arguments``: label_smoothing, class_weights, use_graph, speakers and the criterion arguments of ``train_step``;
+        a frozen CRF or auxiliary head works, a trainable one is refused as under accumulation.  (epsilon, step_size) live on the device
+        (uploaded only when changed): a schedule replays the captured graphs - after the second call on a shape every pass does.
+        Refused by name, before any launch: bf16 gradients (``set_grad_bf16``), the caller's own ``set_grad_accumulation(True)``, a SAM
+        optimizer, rdrop, ``DataParallelStep`` / more than one process, ``steps < 1``, a non-finite or negative epsilon / step_size /
+        init_mag, an unknown norm, a disabled modality.  ``last_perturbation()`` returns the final delta."""
+        who = "M2FNet.adversarial_step"
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"{who}: steps must be an integer >= 1, got {steps!r}")
+        eps, step, mag = runtime.check_adv_hyper(epsilon, step_size, init_mag, who)
+        kind = runtime.adv_norm_kind(norm, who)
+        adv_mask = runtime.input_modalities(modalities, self.text_enabled, self.audio_enabled, who, "modalities")
+        for name in ("normalise", "input_grads"):
+            if name in train_step_arguments:
+                raise TypeError(f"{who}: {name}= is not an argument of the passes (the call normalises nothing and asks for the input "
+                                "gradients itself)")
+        if train_step_arguments.get("rdrop") is not None:
+            raise ValueError(f"{who}: rdrop does not combine with adversarial_step (the R-Drop step runs every dialogue twice: there is "
+                             "no one perturbation per input row)")
+        if type(optimizer).__name__ == "DataParallelStep" or (torch.distributed.is_available() and torch.distributed.is_initialized()
+                                                              and torch.distributed.get_world_size() > 1):
+            raise RuntimeError(f"{who}: DataParallelStep / more than one process is not supported (the passes accumulate on one device "
+                               "and the perturbation's norm is this rank's)")
+        if optimizer is not None and getattr(optimizer, "sam_rho", None) is not None:
+            raise RuntimeError(f"{who}: a SAM optimizer (optimizer.sam_rho) does not combine with adversarial_step: both re-run the "
+                               "batch, one moving the weights, one the inputs; set sam_rho = None")
+        if self._grad_accumulation:
+            raise RuntimeError(f"{who}: gradient accumulation is on (set_grad_accumulation(True)): the K passes are an accumulation group "
+                               "of their own; call set_grad_accumulation(False) first")
+        if self._engine is not None and self._engine.grad_bf16_buf is not None:
+            raise RuntimeError(f"{who}: bf16 gradients are on (set_grad_bf16(True)); the passes accumulate fp32 gradients - call "
+                               "set_grad_bf16(False) first")
+        label_smoothing = train_step_arguments.pop("label_smoothing", 0.1)
+        class_weights = train_step_arguments.pop("class_weights", None)
+        use_graph = train_step_arguments.pop("use_graph", True)
+        speakers = train_step_arguments.pop("speakers", None)
+        spec = self._resolve(who, mask, label_smoothing, class_weights, accumulating=steps > 1, **train_step_arguments)
+        ids = _check_speakers(who, self._speaker_heads, speakers, mask.shape)
+        eng = self.engine(mask.device)
+        if eng.grad_bf16_buf is not None:
+            raise RuntimeError(f"{who}: bf16 gradients are on (set_grad_bf16(True)); the passes accumulate fp32 gradients - call "
+                               "set_grad_bf16(False) first")
+        B, L = mask.shape
+        valid = int((~mask.bool()).sum()) if (self.packed or L > 64) else None
+        dropout_on = self.training and self.m2f_config.dropout > 0.0
+        plan = eng.plan(B, L, True, dropout_on, valid, (adv_mask, True))
+        self._last_criterion = spec
+        cw = class_weights is not None
+
+        def body():
+            plan.set_inputs(text if self.text_enabled else None, audio if self.audio_enabled else None, mask, emotion, speakers=ids)
+            if cw:
+                plan.class_w[: class_weights.numel()].copy_(class_weights)
+            plan.set_criterion(spec)
+            plan.adversarial(adv_mask)                        # (the mask is part of the plan's key: allocated once per plan)
+            plan.adv_begin(eps, step, mag, kind)
+            saved = eng.rng.clone() if dropout_on else None   # (16 bytes, device to device)
+            after0 = None
+            first = None
+            for k in range(steps):
+                if k:
+                    plan.adv_ascend(kind)
+                    if dropout_on and same_dropout:
+                        eng.rng.copy_(saved)                  # the masks of pass 0 again
+                plan.accumulate_grads(k > 0)
+                out = plan.step(label_smoothing, cw, False, use_graph)
+                if k == 0:
+                    first = out[0].clone()
+                    after0 = eng.rng.clone() if dropout_on else None
+            plan.accumulate_grads(False)
+            if dropout_on:
+                eng.rng.copy_(after0)                         # the state a single step leaves
+            return first
+
+        if use_graph:                                    # capture / replay on the engine's own stream
+            cur = torch.cuda.current_stream(eng.device)
+            eng.stream.wait_stream(cur)
+            with torch.cuda.stream(eng.stream):
+                loss = body()
+            cur.wait_stream(eng.stream)
+        else:
+            loss = body()
+        eng.publish_grads()
+        for block in (spec.crf, spec.aux and spec.aux[0]):
+            if block is not None:
+                block.publish_grad()
+        eng.note_forward(plan)
+        eng.last_adv = eng.last + (adv_mask,)
+        eng.last_inputs = eng.last + (adv_mask,)
+        if optimizer is not None:
+            held = optimizer.grad_scale
+            optimizer.grad_scale = self.loss_terms()[1:2]
+            try:
+                optimizer.step()
+            finally:
+                optimizer.grad_scale = held
+        return loss
 
     def sam_step(self, text, audio, mask, emotion, optimizer, **train_step_arguments) -> torch.Tensor:
         """One optimizer step of sharpness-aware minimisation (Foret et al., ICLR 2021; ``FusedAdam(sam_rho=...)``): ``train_step``
@@ -821,12 +1006,14 @@ class M2FNet(nn.Module):
         optimizer.step()
         return loss
 
-    def _resolve(self, who: str, mask, label_smoothing, class_weights, **criterion_args):
-        """``criterion.resolve`` for a step of this model on `mask`'s batch (`who` names the entry point in the refusals)."""
+    def _resolve(self, who: str, mask, label_smoothing, class_weights, accumulating: Optional[bool] = None, **criterion_args):
+        """``criterion.resolve`` for a step of this model on `mask`'s batch (`who` names the entry point in the refusals).
+        accumulating: None = whether gradient accumulation is on; True: the step accumulates by itself (adversarial_step)."""
         c = self.m2f_config
+        if accumulating is None:
+            accumulating = self._engine is not None and self._engine.accumulate
         return resolve(who, num_classes=c.cls_out, cls_hidden=c.cls_hidden, mask_shape=mask.shape, device=mask.device,
-                       label_smoothing=label_smoothing, class_weights=class_weights,
-                       accumulating=self._engine is not None and self._engine.accumulate, **criterion_args)
+                       label_smoothing=label_smoothing, class_weights=class_weights, accumulating=bool(accumulating), **criterion_args)
 
     # -- evaluation fast path (forward + scoring as one launch list / hipGraph) -----------------------
     def eval_step(self, text, audio, mask, emotion, scores, class_weights: Optional[torch.Tensor] = None,

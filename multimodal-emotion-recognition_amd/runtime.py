@@ -29,6 +29,9 @@ PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, "bf16": BF16, "bfloat16":
  BUF_FAM0_OUT, BUF_CU_SEQLENS, BUF_DTEXT, BUF_DAUDIO, BUF_STREAM_LEN, BUF_STREAM_ACTIVE, BUF_STREAM_NEW, BUF_STREAM_TABLE,
  BUF_TEACHER, BUF_DISTILL, BUF_STREAM_ATTN, BUF_SPEAKERS, BUF_STREAM_SPEAKERS, BUF_FOCAL, BUF_PARTNER, BUF_RDROP, BUF_SUPCON,
  BUF_FEATURES, BUF_AUX, BUF_AUX_LABELS, BUF_AUX_LOGITS) = range(29)
+BUF_ADV, BUF_ADV_SKIP, BUF_ADV_DELTA_TEXT, BUF_ADV_DELTA_AUDIO = range(29, 33)      # a plan's adversarial state (m2f_plan_adversarial)
+ADV_SITE_TEXT, ADV_SITE_AUDIO = 0xAD510001, 0xAD510002                             # hash sites of the perturbation's uniform start
+ADV_NORMS = {"utterance": 0, "batch": 1}                                           # norm_kind of m2f_adv_ascend
 IN_TEXT, IN_AUDIO = 1, 2            # input_mask bits of m2f_plan_backward_outputs
 
 c_void_p, c_int, c_float, c_int64, c_uint32 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
@@ -94,6 +97,13 @@ SIGNATURES = {
     "m2f_sam_perturb": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 ctypes.c_double, c_void_p, c_void_p]),
     "m2f_sam_restore": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_void_p, c_void_p]),
+    "m2f_adv_scratch_bytes": (c_int64, [c_int]),
+    "m2f_adv_ascend": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "m2f_adv_init": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_uint32, c_void_p]),
+    "m2f_plan_adversarial_bytes": (c_int64, [c_void_p, c_int]),
+    "m2f_plan_adversarial": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
+    "m2f_plan_adv_begin": (c_int, [c_void_p, c_float, c_int, c_void_p]),
+    "m2f_plan_adv_ascend": (c_int, [c_void_p, c_int, c_void_p]),
     "m2f_tensor_stats_scratch_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
     "m2f_tensor_stats_record_bytes": (c_int64, [ctypes.POINTER(M2FConfigC), c_int]),
     "m2f_tensor_stats": (c_int, [ctypes.POINTER(M2FConfigC), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -425,6 +435,48 @@ def check_supcon_pair(supcon, name: str = "supcon", who: str = "train_step") -> 
     return float(w), float(t)
 
 
+def check_adv_hyper(epsilon, step_size=None, init_mag=0.0, who: str = "adversarial_step") -> Tuple[float, float, float]:
+    """(epsilon, step_size, init_mag) of the adversarial ascent as floats: each a finite number >= 0 (bool, NaN, inf, negative or
+    anything that is no number: ValueError naming it); step_size None = epsilon."""
+    out = []
+    for name, v in (("epsilon", epsilon), ("step_size", epsilon if step_size is None else step_size), ("init_mag", init_mag)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{who}: {name} must be a finite number >= 0, got {v!r}")
+        out.append(float(v))
+    return tuple(out)
+
+
+def adv_norm_kind(norm, who: str = "adversarial_step") -> int:
+    """norm_kind of m2f_adv_ascend for "utterance" (the row's L2 norm) or "batch" (the L2 norm over all valid rows of the modality)."""
+    if not isinstance(norm, str) or norm not in ADV_NORMS:
+        raise ValueError(f"{who}: unknown norm {norm!r}; one of {sorted(ADV_NORMS)}")
+    return ADV_NORMS[norm]
+
+
+def input_modalities(names, text_enabled: bool, audio_enabled: bool, who: str, what: str = "input_grads") -> int:
+    """The IN_TEXT | IN_AUDIO mask of a subset of ("text", "audio") (a name, or an iterable of names; None: every enabled modality).
+    An unknown name, an empty subset and a modality the model has disabled are ValueErrors naming it."""
+    enabled = {"text": text_enabled, "audio": audio_enabled}
+    if names is None:
+        names = [n for n, on in enabled.items() if on]
+    if isinstance(names, str):
+        names = (names,)
+    try:
+        names = list(names)
+    except TypeError:
+        raise ValueError(f"{who}: {what} must be a subset of ('text', 'audio'), got {names!r}") from None
+    mask = 0
+    for n in names:
+        if n not in enabled:
+            raise ValueError(f"{who}: {what} names {n!r}; a subset of ('text', 'audio') is expected")
+        if not enabled[n]:
+            raise ValueError(f"{who}: {what} names {n!r}, but the {n} modality of this model is disabled")
+        mask |= IN_TEXT if n == "text" else IN_AUDIO
+    if not mask:
+        raise ValueError(f"{who}: {what} is empty; name 'text', 'audio' or both (None: no input gradient)")
+    return mask
+
+
 def rdrop_partner(pairs: int, l: int, T: int, L: Optional[int] = None, dst: Optional[torch.Tensor] = None,
                   valid: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
     """The twin map of the R-Drop criterion (M2F_BUF_PARTNER): int32 [T], for every token row of a plan the row of the same utterance
@@ -606,6 +658,10 @@ class Plan:
         self.in_B, self.in_L = B, L
         self.version = 0          # bumped by every forward; backward checks it still owns the activations
         self._pending = None      # weak reference to the autograd node whose backward still needs this plan's activations
+        # the adversarial state (`adversarial`): the caller-side buffer the C side points into, the modalities it covers, its views
+        self._adv_state, self.adv_mask = None, 0
+        self.adv_hyper = self.adv_skip = None
+        self.adv_delta = {}
         self._acc = False         # the accumulate form is on (accumulate_grads); it stays on across a rebuild, as the C side keeps it
         self._disarm()
 
@@ -1005,7 +1061,7 @@ class Plan:
         return self.logits
 
     def nbytes(self) -> int:
-        return self.workspace.numel()
+        return self.workspace.numel() + (self._adv_state.numel() if self._adv_state is not None else 0)
 
     def loss_fwd(self, label_smoothing: float = 0.1, use_class_weights: bool = False, normalise: bool = True):
         check(lib().m2f_loss(self._h(), label_smoothing, int(use_class_weights), int(normalise), stream_ptr()),
@@ -1108,6 +1164,85 @@ class Plan:
         if (int(input_mask), bool(param_grads)) != (self.input_mask, self.param_grads):
             self._disarm()
         self.input_mask, self.param_grads = int(input_mask), bool(param_grads)
+
+    # -- adversarial training on the input embeddings (csrc/adversarial.hip) ----------------------------------------------------------
+    def adversarial(self, mask: int) -> None:
+        """m2f_plan_adversarial: the plan holds a perturbation and a clean copy of the staged input of every modality in `mask`
+        (IN_TEXT | IN_AUDIO), in a buffer of its own beside the workspace - allocated here, on first use or when the mask grows (a
+        plan that never asks keeps the memory it always had).  0: off, the buffer is dropped."""
+        mask = int(mask)
+        if mask == self.adv_mask:
+            return
+        if not mask:
+            check(lib().m2f_plan_adversarial(self._h(), 0, None, 0), "m2f_plan_adversarial")
+            self._adv_state, self.adv_mask, self.adv_hyper, self.adv_skip, self.adv_delta = None, 0, None, None, {}
+            self.uploaded.pop("adv_hyper", None)
+            return
+        nbytes = lib().m2f_plan_adversarial_bytes(self._h(), mask)
+        if nbytes < 0:
+            raise HipError("m2f_plan_adversarial_bytes: " + lib().m2f_last_error().decode())
+        state = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.workspace.device)
+        base = state.data_ptr() + (-state.data_ptr()) % 256
+        check(lib().m2f_plan_adversarial(self._h(), mask, base, nbytes), "m2f_plan_adversarial")
+        self._adv_state, self.adv_mask = state, mask
+        self.uploaded.pop("adv_hyper", None)
+
+        def view(which, shape, dtype):
+            off = lib().m2f_plan_buffer(self.handle, which) - state.data_ptr()
+            n = 1
+            for v in shape:
+                n *= v
+            return state[off: off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(*shape)
+
+        pad8 = lambda w: (w + 7) // 8 * 8
+        self.adv_hyper = view(BUF_ADV, (2,), torch.float32)
+        self.adv_skip = view(BUF_ADV_SKIP, (self.T,), torch.uint8)
+        self.adv_delta = {}
+        for bit, which, d in ((IN_TEXT, BUF_ADV_DELTA_TEXT, self.cfg.d_text), (IN_AUDIO, BUF_ADV_DELTA_AUDIO, self.cfg.d_audio)):
+            if mask & bit:
+                self.adv_delta[bit] = view(which, (self.T, pad8(d)), torch.float32)[:, :d]
+
+    def adv_place_skip(self) -> None:
+        """The skip flags of the batch `set_inputs` has just placed: 1 for every token row that holds no utterance of the batch - pad
+        slots, the rows of filler dialogues (which a bucketed or packed plan keeps live but unlabeled), the rows behind the last
+        dialogue of a packed plan.  On the device, no host wait."""
+        if self.packed:
+            self.adv_skip.fill_(1)
+            self.adv_skip.index_copy_(0, self._dst.reshape(-1), (~self._valid).reshape(-1).to(torch.uint8))
+            self._clear_spare(self.adv_skip, 1)              # (the pad slots' scatter target, unless the batch owns it)
+            return
+        if (self.in_B, self.in_L) == (self.B, self.L):
+            self.adv_skip.copy_(self.keypad_in, non_blocking=True)
+            return
+        self.adv_skip.fill_(1)
+        self.adv_skip.view(self.B, self.L)[: self.in_B, : self.in_L].copy_(self.keypad_in.view(self.B, self.L)[: self.in_B, : self.in_L])
+
+    def adv_begin(self, epsilon: float, step_size: float, init_mag: float = 0.0, norm_kind: int = 0) -> None:
+        """m2f_plan_adv_begin behind the skip flags and the (epsilon, step_size) pair (uploaded only when it changed): AFTER `set_inputs`."""
+        self.adv_place_skip()
+        self._upload("adv_hyper", (float(epsilon), float(step_size)))
+        check(lib().m2f_plan_adv_begin(self._h(), float(init_mag), int(norm_kind), stream_ptr()), "m2f_plan_adv_begin")
+
+    def adv_ascend(self, norm_kind: int = 0) -> None:
+        """m2f_plan_adv_ascend: one ascent step on the input gradients the last backward left; the staged inputs become x_clean + delta."""
+        check(lib().m2f_plan_adv_ascend(self._h(), int(norm_kind), stream_ptr()), "m2f_plan_adv_ascend")
+
+    def perturbation(self, which: int, dst=None, valid=None, shape=None) -> torch.Tensor:
+        """A FRESH [b, l, d] tensor of the perturbation of modality `which` in the caller's dialogue order; pad slots are exact zeros.
+        The row map as `input_grad`."""
+        rows = self.adv_delta.get(which)
+        if rows is None:
+            raise HipError("this plan holds no perturbation of that modality")
+        return self._rows_out(rows, dst, valid, shape)
+
+    def _rows_out(self, rows: torch.Tensor, dst=None, valid=None, shape=None) -> torch.Tensor:
+        """[T, d] token rows -> a fresh [b, l, d] tensor in the caller's order with exact zeros at pad slots (`input_grad`'s mapping)."""
+        b, l = (self.in_B, self.in_L) if shape is None else shape
+        if self.packed:
+            dst, valid = (self._dst, self._valid) if dst is None else (dst, valid)
+            return rows[dst] * valid[..., None].to(rows.dtype)
+        pad = self.keypad_in.view(self.B, self.L)[:b, :l].bool()
+        return rows.view(self.B, self.L, -1)[:b, :l].masked_fill(pad[..., None], 0.0)
 
     def input_grad(self, which: int, dst=None, valid=None, shape=None) -> torch.Tensor:
         """A FRESH tensor (never a view of the plan's buffer, which the next backward overwrites) holding d loss / d text (which =
@@ -1216,6 +1351,7 @@ class Plan:
             _lib.m2f_plan_destroy(h)
         self.handle = None
         self.workspace = None
+        self._adv_state = None
 
     def __del__(self):
         self.close()

@@ -155,6 +155,75 @@ def sam_settings(cfg, world: int = 1):
     return float(rho)
 
 
+ADVERSARIAL_DEFAULTS = {"enabled": False, "epsilon": 1.0, "steps": 2, "step_size": None, "norm": "utterance", "modalities": None,
+                        "same_dropout": True}
+
+
+def adversarial_settings(cfg, world: int = 1):
+    """`runtime.adversarial` = {enabled, epsilon, steps, step_size, norm, modalities, same_dropout}: adversarial training on the input
+    embeddings (the loop calls M2FNet.adversarial_step).  -> None when the block is absent or disabled, else the keyword arguments of
+    that call.  Checked on the host before the GPU is touched: the loop body must be the fused step (runtime.fused_step: True) with the
+    optimizer outside it (runtime.fused_optimizer: False), one micro-batch per step (runtime.grad_accumulation: 1 - the passes are an
+    accumulation group of their own), fp32 gradients (runtime.grad_bf16: False), one process, and neither runtime.sam nor runtime.rdrop."""
+    from mer_amd.runtime import ADV_NORMS
+    block = _runtime(cfg, "adversarial", None)
+    if block is None:
+        return None
+    keys = ", ".join(ADVERSARIAL_DEFAULTS)
+    if not hasattr(block, "keys"):
+        raise ValueError(f"runtime.adversarial must be a mapping {{{keys}}} (got {block!r})")
+    unknown = sorted(set(block.keys()) - set(ADVERSARIAL_DEFAULTS))
+    if unknown:
+        raise ValueError(f"runtime.adversarial: unknown key(s) {unknown} ({keys})")
+    v = {k: block.get(k, d) for k, d in ADVERSARIAL_DEFAULTS.items()}
+    for k in ("enabled", "same_dropout"):
+        if not isinstance(v[k], bool):
+            raise ValueError(f"runtime.adversarial.{k} must be true or false (got {v[k]!r})")
+    for k in ("epsilon", "step_size"):
+        x = v[k]
+        if k == "step_size" and x is None:
+            continue
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x or x == float("inf") or x < 0:
+            raise ValueError(f"runtime.adversarial.{k} must be a finite number >= 0 (got {x!r})")
+    if isinstance(v["steps"], bool) or not isinstance(v["steps"], int) or v["steps"] < 1:
+        raise ValueError(f"runtime.adversarial.steps must be an integer >= 1 (got {v['steps']!r})")
+    if not isinstance(v["norm"], str) or v["norm"] not in ADV_NORMS:
+        raise ValueError(f"runtime.adversarial.norm must be one of {sorted(ADV_NORMS)} (got {v['norm']!r})")
+    mods = v["modalities"]
+    if mods is not None:
+        if isinstance(mods, str) or not hasattr(mods, "__iter__") or not list(mods) or any(m not in ("text", "audio") for m in mods):
+            raise ValueError(f"runtime.adversarial.modalities must be null or a non-empty list of text / audio (got {mods!r})")
+        mods = list(mods)
+    if not v["enabled"]:
+        return None
+    if not bool(_runtime(cfg, "fused_step", True)):
+        raise ValueError("runtime.adversarial.enabled needs runtime.fused_step: True (every pass runs train_step)")
+    if bool(_runtime(cfg, "fused_optimizer", False)):
+        raise ValueError("runtime.adversarial.enabled does not combine with runtime.fused_optimizer: True "
+                         "(the optimizer inside the step cannot wait for the later passes)")
+    if int(_runtime(cfg, "grad_accumulation", 1) or 1) > 1:
+        raise ValueError("runtime.adversarial.enabled does not combine with runtime.grad_accumulation > 1 "
+                         "(the passes are an accumulation group of their own)")
+    if bool(_runtime(cfg, "grad_bf16", False)):
+        raise ValueError("runtime.adversarial.enabled does not combine with runtime.grad_bf16: True (the passes accumulate fp32 gradients)")
+    if world > 1:
+        raise ValueError("runtime.adversarial.enabled does not combine with data-parallel training; run one process")
+    if sam_settings(cfg, world) is not None:
+        raise ValueError("runtime.adversarial.enabled does not combine with runtime.sam.enabled (both re-run the batch)")
+    if rdrop_settings(cfg) is not None:
+        raise ValueError("runtime.adversarial.enabled does not combine with runtime.rdrop.enabled (the R-Drop step runs every dialogue twice)")
+    return {"epsilon": float(v["epsilon"]), "steps": v["steps"], "step_size": None if v["step_size"] is None else float(v["step_size"]),
+            "norm": v["norm"], "modalities": mods, "same_dropout": v["same_dropout"]}
+
+
+def _adv_delta_norm(model, padding_mask):
+    """The mean L2 norm of the final perturbation's rows over the valid utterances and the perturbed modalities of the adversarial step
+    just taken: a device scalar (read where loss.item() is)."""
+    valid = (~padding_mask.bool()).to(torch.float32)
+    norms = [(d.norm(dim=-1) * valid).sum() / valid.sum().clamp_min(1.0) for d in model.last_perturbation().values()]
+    return sum(norms) / len(norms)
+
+
 DISTILL_KEYS = ("enabled", "teacher_checkpoint", "teacher_weights", "alpha", "temperature", "teacher_context", "teacher_position_bias")
 
 
@@ -960,6 +1029,7 @@ def main(config=None):
     clip_grad_norm(config, int(os.environ.get("WORLD_SIZE", "1")))
     ema_settings(config)
     sam_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
+    adversarial_settings(config, int(os.environ.get("WORLD_SIZE", "1")))
     context_settings(config)
     position_bias_settings(config)
     spk_on = speaker_heads_settings(config, int(os.environ.get("WORLD_SIZE", "1"))) is not None
@@ -1049,6 +1119,7 @@ def main(config=None):
     attach_distiller(config, model, device)
     object.__setattr__(model, "rdrop", rdrop_settings(config))       # (None: off; train() passes rdrop= on in every branch)
     object.__setattr__(model, "supcon", supcon_settings(config))     # (None: off; train() passes supcon= on to train_step)
+    object.__setattr__(model, "adversarial", adversarial_settings(config, world))    # (None: off; train() then calls adversarial_step)
     attach_aux_head(model, aux_on, config.model.CLASSIFIER.hidden_size, device)      # (None: off; train() passes aux= on to train_step)
     criterion = build_criterion(config.solver, train_set, device, focal_gamma=focal_gamma_setting(config), crf=crf_settings(config))
     attach_crf(model, criterion)
@@ -1260,6 +1331,23 @@ def train(model, dl_train, criterion, optimizer, epoch, wandb_log, device):
                 if wandb_log:
                     wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
                                **_grad_norm_log(optimizer), **_sam_log(optimizer), **watched, **shares_log(step)})
+                continue
+            adv = getattr(model, "adversarial", None)
+            if adv and not fused:
+                raise ValueError("runtime.adversarial needs runtime.fused_step: True and the M2FCrossEntropyLoss criterion")
+            if adv:
+                # adversarial training on the input embeddings: K passes on text + delta / audio + delta, the summed gradient applied
+                loss = model.adversarial_step(text, audio, padding_mask, emotion, optimizer, use_graph=use_graph, **adv,
+                                              **_distill_kw(model, text, audio, padding_mask), **_speaker_kw(model, batch, device),
+                                              **_crit_kw(criterion), **supcon, **aux)
+                _crf_step(criterion)
+                _aux_step(aux)
+                delta_norm = _adv_delta_norm(model, padding_mask) if wandb_log else None
+                running += loss.item()
+                watched = _watch_log(optimizer, wandb_log)
+                if wandb_log:
+                    wandb.log({"Train/Running_loss": running / (step + 1), "Params/Global_step": epoch * len(dl_train) + step,
+                               "Train/Adv_delta_norm": float(delta_norm), **_grad_norm_log(optimizer), **watched, **shares_log(step)})
                 continue
             if fused:
                 loss = model.train_step(text, audio, padding_mask, emotion, use_graph=use_graph, **_distill_kw(model, text, audio, padding_mask),
